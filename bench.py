@@ -17,8 +17,21 @@ restatement compresses like text of that kind (ratio ~0.47; synth.enwik_like).  
     MINLZ_BENCH_ONE_GPU=1 python bench.py --gpus 2 ...  # TEST mode: N ranks, all on cuda:0, over gloo (host-staged) — runs the N > 1
                                                         # code path on a 1-GPU box; the line carries config.TEST_MODE and is no measurement
 
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full          # the headline plus every leg described below
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # also writes the last timed step's outputs as DIR/*.npy
+
 Prints ONE JSON line on rank 0.  value = uncompressed bytes through the encode+decode pair per second, whole job
-(all ranks).  roofline = dominant kernel against HBM peak (algorithmic bytes N + C per launch / HIP-event launch
+(all ranks); ms_per_step = wall time of one timed step.  A plain run (no --full) does only what that headline needs:
+set-up (input, upload, one checked encode + decode that also yields the decode descriptors), warm-up (--warmup steps,
+then max(3, min(--steps, 8)) more: the pass --full times per kernel), the timed steps, the optional output dump and
+the line; config then carries no per-kernel figures, and roofline and cpu_baseline are null.
+--full adds everything below: HIP-event timers on the short pass before the timed steps (config.kernel_ms, encode_MBps,
+decode_MBps) and on the dominant kernel inside them, the extra legs and, with N > 1, the strong-scaling leg
+and the single-process child.  --dump-outputs DIR (blocks mode, rank 0) writes after the timed steps what the last one
+computed: compressed_lengths.npy and decoded_lengths.npy (float64, one per block), and compressed_sample.npy /
+decoded_sample.npy (float32, the bytes at up to 4 Mi fixed, seeded positions of the compressed blocks laid end to end
+and of the decoded stream; every byte when there are fewer).  The inputs depend only on the arguments.
+roofline = dominant kernel against HBM peak (algorithmic bytes N + C per launch / HIP-event launch
 time).  cpu_baseline = the CPU oracle (a C restatement of the reference's pure-Go L1 encoder + decoder, NOT the
 reference's AMD64 asm) on this box's cores: threads started and buffers touched before the clock, a sweep over
 thread counts with the best one reported, and the single-thread rate.  On rank 0 of a 1-GPU run the line also
@@ -364,6 +377,35 @@ def single_process_mode(args):
         many.close(); one.close()
 
 
+DUMP_SAMPLE = 1 << 22      # bytes per sampled array: 2 x 16 MiB of float32 at most
+
+
+def _sample_positions(n, seed):
+    """Sorted positions in [0, n): all of them when n <= DUMP_SAMPLE, else DUMP_SAMPLE drawn by a fixed seed."""
+    if n <= DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).integers(0, n, DUMP_SAMPLE, dtype=np.int64))
+
+
+def dump_outputs(out_dir, leg, dev):
+    """--dump-outputs: what the last timed step handed its caller — every block's compressed and decoded length, and the
+    bytes at fixed positions of the compressed blocks (laid end to end) and of the decoded stream — as DIR/<name>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize(dev)
+    clen = leg.enc_len.cpu().numpy()
+    dlen = leg.dec_len.cpu().numpy()
+    cpos = _sample_positions(int(clen.sum()), seed=1)
+    starts = np.concatenate([[0], np.cumsum(clen)[:-1]])
+    blk = np.searchsorted(starts, cpos, side="right") - 1
+    cidx = torch.from_numpy(blk * leg.stride + (cpos - starts[blk])).to(dev)
+    didx = torch.from_numpy(_sample_positions(leg.S, seed=2)).to(dev)
+    arrays = {"compressed_lengths": clen.astype(np.float64), "decoded_lengths": dlen.astype(np.float64),
+              "compressed_sample": leg.enc[cidx].cpu().numpy().astype(np.float32),
+              "decoded_sample": leg.dec[didx].cpu().numpy().astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -384,7 +426,17 @@ def main():
     ap.add_argument("--file", default=os.environ.get("MINLZ_BENCH_FILE"), help="real input (e.g. enwik8); every rank reads its own --bytes slice, wrapping around")
     ap.add_argument("--single-process", action="store_true",
                     help="ONE process with one context over --gpus devices (mlz_init_devices), host-pointer calls: the form a Go host binds; prints end_to_end_MBps")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the per-kernel breakdown and roofline, the CPU baseline (--no-cpu drops it), the foreign-stream, CRC, "
+                         "end-to-end, round-1 stand-in and BASELINE config legs (--no-extras drops them); with N > 1 the config-3 strong-scaling leg "
+                         "and the single-process child")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64; blocks mode, rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.single_process or args.mode != "blocks"):
+        ap.error("--dump-outputs applies to the default blocks mode")
 
     if args.single_process:
         return single_process_mode(args)
@@ -514,11 +566,12 @@ def main():
             assert self.dec_len.cpu().tolist() == self.blk_len, "decode reported errors"
             assert torch.equal(self.dec[:self.S], self.src), "GPU decode(encode(x)) != x"
 
-        def timed(self, steps, warmup, collective=None):
+        def timed(self, steps, warmup, collective=None, breakdown=True):
             """K steps bracketed by synchronize (+ barrier); returns (seconds, per-kernel HIP-event means in ms).
             Every HIP event pair leaves the device idle for ~10 us at a kernel boundary (rocprofv3 timeline), so the timed
             region records events around the dominant kernel only — its launch time over exactly the timed steps is what the
-            roofline uses — and the full per-kernel breakdown comes from a short pass of its own, outside the clock."""
+            roofline uses — and the full per-kernel breakdown comes from a short pass of its own, outside the clock.
+            breakdown=False (a plain run's headline): no timers and no events; the dict comes back empty."""
             from minlz_amd import _lib
             L = _lib.lib()
             names = [L.mlz_timer_name(i).decode() for i in range(16)]
@@ -533,15 +586,17 @@ def main():
             for _ in range(warmup):
                 step()
             torch.cuda.synchronize(dev)
-            # breakdown pass (all timers), also tells which kernel dominates
-            ctx.set_option(12, 0xffffffff)
-            ctx.set_option(mz.OPT_TIMING, 2)
+            # breakdown pass (all timers), also tells which kernel dominates.  Without the breakdown the same steps run untimed:
+            # the timed steps then follow as much device work as they always have, so ms_per_step keeps its meaning.
+            if breakdown:
+                ctx.set_option(12, 0xffffffff)
+                ctx.set_option(mz.OPT_TIMING, 2)
             for _ in range(max(3, min(steps, 8))):
                 step()
             if collective is not None and hasattr(collective, "drain"):
                 collective.drain()
             torch.cuda.synchronize(dev)
-            kern = dict(ctx.timers())
+            kern = dict(ctx.timers()) if breakdown else {}
             ctx.set_option(mz.OPT_TIMING, 0)
             dom = max(kern, key=kern.get) if kern else None
             # timed region
@@ -609,12 +664,14 @@ def main():
     else:
         collective = None
 
-    elapsed, kavg = main_leg.timed(args.steps, args.warmup, collective)
+    elapsed, kavg = main_leg.timed(args.steps, args.warmup, collective, breakdown=args.full)
     if dist is not None:
         while pending:
             shard.finish_gather(pending.pop())
         torch.cuda.synchronize(dev)
         gather_info = {"root": 0, "payload_bytes_per_step": int(collective.payload), "transport": "isend/irecv of one compact run per rank into rank 0's HBM, overlapped with decode"}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, main_leg, dev)
     if dist is not None:
         cdev = "cpu" if dist.get_backend() == "gloo" else dev
         tt = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
@@ -629,7 +686,7 @@ def main():
     # ---- N > 1: BASELINE config 3 as a STRONG-scaling leg in the same line (the headline above is weak scaling: every rank its own
     # stream): one JSON stream of --strong-bytes (default 4 GiB), LevelBalanced, written and read by all ranks (stream_leg) ----
     strong = None
-    if dist is not None and args.strong_bytes > 0 and args.level == 1 and not args.file:
+    if args.full and dist is not None and args.strong_bytes > 0 and args.level == 1 and not args.file:
         del main_leg.enc, main_leg.dec
         torch.cuda.empty_cache()
         try:
@@ -642,7 +699,7 @@ def main():
     # legs are over).  A child, because that path has never run on more than one GPU: whatever it does on a real node, the line above it survives.
     # PCIe-inclusive, never `value`. ----
     single_process = None
-    if dist is not None and world > 1 and args.level == 1 and not args.file:
+    if args.full and dist is not None and world > 1 and args.level == 1 and not args.file:
         if rank == 0:
             try:
                 env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "GROUP_RANK", "ROLE_RANK",
@@ -711,7 +768,7 @@ def main():
             for d, t in (("enc", enc_ms), ("dec", dec_ms)) if t}
 
     extras = {}
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         import oracle as O
         # ---- foreign streams: the same data encoded by the reference's algorithm (oracle L1); decode only ----
         lens = []
@@ -949,19 +1006,22 @@ def main():
             extras["small_stream_blocks"] = sm
 
     cpu = None
-    if not args.no_cpu and world == 1:   # the CPU leg runs on rank 0 of the single-GPU run only
+    if args.full and not args.no_cpu and world == 1:   # the CPU leg runs on rank 0 of the single-GPU run only
         cpu = cpu_baseline(host)
 
     cfg = {"workload": "%s, %d B per GPU in 8 MiB blocks (%d blocks), level %d, far=%d; step = encode all blocks + decode all blocks, HBM-resident"
                        % (wname, S, nblk, args.level, args.far),
-           "block_size": BLOCK, "bytes_per_gpu": S, "ratio": round(C_all / total_bytes, 4),
-           "encode_MBps": round(S / 1e6 / (enc_ms / 1e3), 1) if enc_ms else None,
-           "decode_MBps": round(S / 1e6 / (dec_ms / 1e3), 1) if dec_ms else None,
-           "kernel_ms": {k: round(v, 4) for k, v in kavg.items()},
-           "hbm_read_frac_north_star": round((S / 1e9 / ((enc_ms + dec_ms) / 1e3)) / HBM_PEAK_GBS, 5) if enc_ms + dec_ms else None,
-           "ranks": dist.get_world_size() if dist is not None else 1,
-           "backend": ("rccl (torch nccl)" if dist.get_backend() == "nccl" else dist.get_backend()) if dist is not None else "none (single process)",
-           "device": ctx.device_name()}
+           "block_size": BLOCK, "bytes_per_gpu": S, "ratio": round(C_all / total_bytes, 4)}
+    if args.full:
+        cfg.update({"encode_MBps": round(S / 1e6 / (enc_ms / 1e3), 1) if enc_ms else None,
+                    "decode_MBps": round(S / 1e6 / (dec_ms / 1e3), 1) if dec_ms else None,
+                    "kernel_ms": {k: round(v, 4) for k, v in kavg.items()},
+                    "hbm_read_frac_north_star": round((S / 1e9 / ((enc_ms + dec_ms) / 1e3)) / HBM_PEAK_GBS, 5) if enc_ms + dec_ms else None})
+    else:
+        cfg["legs"] = "headline only: per-kernel figures, roofline, cpu_baseline and the other legs come with --full"
+    cfg.update({"ranks": dist.get_world_size() if dist is not None else 1,
+                "backend": ("rccl (torch nccl)" if dist.get_backend() == "nccl" else dist.get_backend()) if dist is not None else "none (single process)",
+                "device": ctx.device_name()})
     if dist is not None and dist.get_backend() == "gloo":
         cfg["TEST_MODE"] = "MINLZ_BENCH_ONE_GPU: all ranks on one GPU over gloo — exercises the N > 1 code path, not a scaling measurement"
     cfg.update(extras)

@@ -179,7 +179,7 @@ def test_bench_one_rank_over_rccl(mode):
     env["MINLZ_BENCH_FORCE_DIST"] = "1"
     env["MASTER_PORT"] = str(_free_port())
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-extras", "--bytes", "33554432",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-extras", "--bytes", "33554432",
            "--strong-bytes", "50331648"]
     if mode == "stream":
         cmd += ["--mode", "stream", "--workload", "json", "--level", "2"]
@@ -204,7 +204,7 @@ def test_bench_two_ranks_on_one_gpu(mode):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["MINLZ_BENCH_ONE_GPU"] = "1"
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-extras", "--bytes", "33554432",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-extras", "--bytes", "33554432",
            "--strong-bytes", str(5 * (8 << 20) + 12345)]          # five blocks and a bit over two ranks: uneven ranges, a ragged last block
     if mode == "stream":
         cmd += ["--mode", "stream", "--workload", "json", "--level", "2"]
