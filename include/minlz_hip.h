@@ -212,11 +212,12 @@ const char* mlz_timer_name(int idx);
  * reader.go:830-859 — are run as one batched launch.  which: 0 = batches run, 1 = requests served.
  * which = 2: blocks of the last decode call that matched no tile-level pattern of this library's encoder and went through the
  * general-block path (mlz_decode_general.hip.inc): the reference's own blocks, and this library's LevelBalanced ones
- *            (summed over the internal groups a batch ran as).
+ *            (summed over the whole call: the internal groups of a device batch, the host groups of mlz_decode_batch /
+ *            mlz_decode_block, the groups of mlz_stream_decode; 0 after a call with no block to decode in tiles).
  * which = 3 / 4: bytes of device workspace the context holds for encoding / decoding (grow-only: the high-water mark so far).
  * which = 5: decode calls whose general blocks fell back to the tile chain because the general pass's buffers could not be allocated.
- * which = 6: workgroups per block (1, 2 or 4) the general-block pass of the last decode call settled with (the largest over its internal groups);
- *            0 = it had no general block. */
+ * which = 6: workgroups per block (1, 2 or 4) the general-block pass of the last decode call settled with (the largest over the
+ *            groups of the call, as for 2); 0 = it had no general block. */
 int64_t mlz_get_counter(mlz_ctx* ctx, int which);
 
 #ifdef __cplusplus

@@ -92,7 +92,8 @@ struct mlz_ctx {
     int index_passes = 0;                    // MLZ_OPT_INDEX_PASSES
     int debug_stop = 0;                      // debug option 16: decode stops after the index pass (timing experiments with broken kernel variants)
     void* last_gen = nullptr;                // GenCtl of the last decode call's last group (device memory)
-    uint64_t acc_call = 0;                   // the call_seq whose first group has reset d_gen_acc
+    uint64_t acc_call = 0;                   // the decode call (dec_call) whose first schedule kernel has reset d_gen_acc
+    uint64_t dec_call = 0;                   // call_seq at the start of the last decode API call: its host groups, stream groups and internal groups share it
     std::string err;
     std::string dev_name;
     hipStream_t stream = nullptr;  // used by the host-pointer calls
@@ -597,8 +598,8 @@ int decode_parallel(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, uint8_t* d
             hipLaunchKernelGGL(dec_viol_kernel, dim3((segs + 255) / 256), dim3(256), 0, st, seg_block, ws + o_sviol, dec, jump ? &gen->n_general : nullptr, segs);
         if (tiles) {
             HIPCHK(c, c->d_gen_acc.ensure(64));
-            const uint32_t reset = c->acc_call != c->call_seq ? 1u : 0u;
-            c->acc_call = c->call_seq;
+            const uint32_t reset = c->acc_call != c->dec_call ? 1u : 0u;
+            c->acc_call = c->dec_call;
             hipLaunchKernelGGL(dec_schedule_kernel, dim3(1), dim3(1024), 0, st, blocks, tile_block, dec, order, tiles, uint32_t(n),
                                jump ? reinterpret_cast<uint32_t*>(ws + o_glist) : nullptr, reinterpret_cast<uint32_t*>(gen), gen_settle_wgs(c, n),
                                c->d_gen_acc.as<uint32_t>(), reset);
@@ -667,12 +668,17 @@ int decode_device_group(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, uint8_
     return decode_parallel(c, st, d_src, d_dst, desc, n, d_out_len, raw_body, mirror);
 }
 
+// A decode API call starts: counters 2 and 6 (mlz_get_counter) describe it alone from here on.  Every decode_device_locked of the call
+// (host groups, stream groups) adds to d_gen_acc, the first schedule kernel of the call resets it, and a call that launches none reports 0.
+void begin_decode_call(mlz_ctx* c) { c->call_seq++; c->dec_call = c->call_seq; }
+
 int decode_device_locked(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, uint8_t* d_dst, const mlz_block_desc* desc, int n, int64_t* d_out_len,
-                         bool raw_body, const uint64_t* mirror = nullptr) {
+                         bool raw_body, const uint64_t* mirror = nullptr, bool new_call = true /* false: a part of a call begun by the caller */) {
     if (n <= 0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     WorkspaceOrder order(c, st);
     c->call_seq++;
+    if (new_call) c->dec_call = c->call_seq;
     return for_each_group(c, desc, n, true, [&](int b0, int cnt) {
         return decode_device_group(c, st, d_src, d_dst, desc + b0, cnt, d_out_len + b0, raw_body, mirror ? mirror + b0 : nullptr);
     });
@@ -773,6 +779,7 @@ int host_batch(mlz_ctx* c, bool encode, int level, int n, const uint8_t* const* 
         if (!mirror[size_t(i)]) use_mirror = false;
     }
     const uint64_t* mir = use_mirror ? mirror.data() : nullptr;
+    if (!encode) begin_decode_call(c);   // (one call however many groups)
     HIPCHK(c, c->d_in.ensure(in_total + 64));
     HIPCHK(c, c->d_out.ensure(out_total + 64));
     HIPCHK(c, c->d_len.ensure(sizeof(int64_t) * n));
@@ -791,7 +798,7 @@ int host_batch(mlz_ctx* c, bool encode, int level, int n, const uint8_t* const* 
         r = encode ? encode_device_locked(c, st, level, c->d_in.as<uint8_t>(), c->d_out.as<uint8_t>(), desc.data() + b0, cnt, c->d_len.as<int64_t>() + b0, with_header,
                                           mir ? mir + b0 : nullptr)
                    : decode_device_locked(c, st, c->d_in.as<uint8_t>(), c->d_out.as<uint8_t>(), desc.data() + b0, cnt, c->d_len.as<int64_t>() + b0, !with_header,
-                                          mir ? mir + b0 : nullptr);
+                                          mir ? mir + b0 : nullptr, false);
         if (r) { (void)hipStreamSynchronize(c->s_in); (void)hipStreamSynchronize(st); (void)hipStreamSynchronize(c->s_out); return r; }
         HIPCHK(c, hipEventRecord(c->evpool[3 * g + 1], st));
         HIPCHK(c, hipStreamWaitEvent(c->s_out, c->evpool[3 * g + 1], 0));
@@ -882,6 +889,8 @@ int multi_host_batch(mlz_ctx* c, bool encode, int level, int n, const uint8_t* c
                      int64_t* out_len) {
     Workers w(c);
     if (w.n == 1) return host_batch(w.list[0], encode, level, n, src, src_len, dst, dst_cap, out_len, true, nullptr);
+    if (!encode)   // a device that gets no block of this call has no general block in it either (counters 2 / 6 sum over the devices)
+        for (size_t j = 0; j < w.n; j++) { std::lock_guard<std::mutex> lk(w.list[j]->mu); begin_decode_call(w.list[j]); }
     std::vector<uint64_t> pre(size_t(n) + 1, 0);
     for (int i = 0; i < n; i++) {
         uint64_t wt = src_len[i];
@@ -1204,7 +1213,7 @@ int64_t mlz_get_counter(mlz_ctx* c, int which) {
         // 2: blocks of the last decode call that fit no level pattern; 6: workgroups per block (1, 2 or 4) its general pass settled with (0 = no general block).
         // Both over ALL internal groups of the call (sum / maximum, kept by dec_schedule_kernel); waits for the device.
         std::lock_guard<std::mutex> lk(c->mu);
-        if (!c->d_gen_acc.p) return 0;
+        if (!c->d_gen_acc.p || c->acc_call != c->dec_call) return 0;   // (the last decode call launched no schedule kernel: nothing reset the words)
         uint32_t v[2] = {0, 0};
         if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
             hipMemcpy(v, c->d_gen_acc.p, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return -MLZ_ERR_HIP;

@@ -601,7 +601,7 @@ int64_t stream_decode_range(mlz_ctx* c, bool ignore_crc, const uint8_t* src, std
         }
         if (!ddesc.empty()) {
             // minLZDecode(dst[:n], tokens) contract: lengths come back compacted, scatter them to chunk order below
-            r = decode_device_locked(c, sm, d_in, d_out, ddesc.data(), int(ddesc.size()), c->d_len.as<int64_t>() + r0, true, mir_base ? dmir.data() : nullptr);
+            r = decode_device_locked(c, sm, d_in, d_out, ddesc.data(), int(ddesc.size()), c->d_len.as<int64_t>() + r0, true, mir_base ? dmir.data() : nullptr, false);
             if (r) return r;
         }
         if (!ignore_crc) {
@@ -646,6 +646,7 @@ int64_t stream_decode_over(mlz_ctx* const* workers, size_t k, bool ignore_crc, c
     const int64_t total = stream_parse(src, slen, &chunks);
     if (total < 0) return total;
     if (size_t(total) > dst_cap) return -MLZ_ERR_DST_TOO_SMALL;
+    for (size_t j = 0; j < k; j++) { std::lock_guard<std::mutex> lk(workers[j]->mu); begin_decode_call(workers[j]); }   // (workers that get no chunk included)
     const size_t nck = chunks.size();
     if (nck == 0) return 0;
     if (k > nck) k = nck;
