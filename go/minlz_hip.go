@@ -260,7 +260,8 @@ func HIPDecodeStream(dst, src []byte, ignoreCRC bool) ([]byte, error) {
 	}
 	dl := C.mlz_stream_decoded_len(bytePtr(src), C.size_t(len(src)))
 	if dl < 0 {
-		return nil, hipError(int(-dl))
+		// a framing error: the chunks in front of it are decoded first, and their first error wins (stream order)
+		dl = C.mlz_stream_decoded_prefix_len(bytePtr(src), C.size_t(len(src)))
 	}
 	if cap(dst) < int(dl) {
 		dst = make([]byte, int(dl))

@@ -167,6 +167,10 @@ int64_t mlz_stream_bound(uint64_t n, uint32_t block_size, uint32_t flags); /* ds
 int64_t mlz_stream_encode(mlz_ctx* ctx, int level, uint32_t block_size, uint32_t flags, const uint8_t* src, size_t n, uint8_t* dst,
                           size_t dst_cap);
 int64_t mlz_stream_decoded_len(const uint8_t* src, size_t n); /* host-only chunk walk: total decoded bytes */
+/* Host-only: the decoded bytes of the chunks in front of the stream's first framing error (the total when it has none).  The Reader
+ * reports the first error in stream order: mlz_stream_decode into this much room decodes those chunks and returns their first error,
+ * or the framing error when they all pass. */
+int64_t mlz_stream_decoded_prefix_len(const uint8_t* src, size_t n);
 int64_t mlz_stream_decode(mlz_ctx* ctx, uint32_t flags, const uint8_t* src, size_t n, uint8_t* dst, size_t dst_cap);
 
 /* The device-resident Writer over several devices: range j of the stream lies in HBM at d_src[j] (src_len[j] bytes; every range but the last a whole

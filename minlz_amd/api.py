@@ -353,8 +353,8 @@ def stream_decode(src, ignore_crc=False, ctx=None):
     ctx = ctx or default_context()
     a = _np(src)
     n = _lib.lib().mlz_stream_decoded_len(_ptr(a), a.size)
-    if n < 0:
-        _raise(n, ctx)
+    if n < 0:   # a framing error: the chunks in front of it are decoded first, and their first error wins (stream order)
+        n = _lib.lib().mlz_stream_decoded_prefix_len(_ptr(a), a.size)
     out = np.empty(max(n, 1), dtype=np.uint8)
     r = _lib.lib().mlz_stream_decode(ctx.handle, STREAM_IGNORE_CRC if ignore_crc else 0, _ptr(a), a.size, out.ctypes.data, n)
     if r < 0:

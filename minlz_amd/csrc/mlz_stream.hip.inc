@@ -453,7 +453,8 @@ struct StreamChunk {
     size_t crc_idx;             // type 0x03: where the device left the CRC of its compressed bytes
 };
 
-// Reader.Read's chunk walk (reader.go:248-543).  Fills `chunks`, returns total decoded bytes or -MLZ_ERR_*.
+// Reader.Read's chunk walk (reader.go:248-543).  Fills `chunks`, returns total decoded bytes or -MLZ_ERR_*; on an error `chunks` holds the
+// chunks in front of it, which the Reader decodes (and may fail on) before it reaches the error.
 int64_t stream_parse(const uint8_t* src, size_t slen, std::vector<StreamChunk>* chunks) {
     size_t p = 0, out = 0, max_block = kMaxBlockSize, stream_out = 0;
     bool read_header = false, want_eof = false;
@@ -486,9 +487,10 @@ int64_t stream_parse(const uint8_t* src, size_t slen, std::vector<StreamChunk>* 
             break;
         }
         case kChunkUncompressed: {
-            if (clen < 4 || clen > size_t(mlz_max_encoded_len(max_block)) + 4 || slen - p < clen) return -MLZ_ERR_CORRUPT;
+            if (clen < 4 || clen > size_t(mlz_max_encoded_len(max_block)) + 4 || slen - p < 4) return -MLZ_ERR_CORRUPT;
             const size_t nn = clen - 4;
-            if (nn > max_block) return -MLZ_ERR_TOO_LARGE;
+            if (nn > max_block) return -MLZ_ERR_TOO_LARGE;   // (before the bytes are read: reader.go:411-464)
+            if (slen - p < clen) return -MLZ_ERR_CORRUPT;
             StreamChunk ck;
             ck.type = type;
             std::memcpy(&ck.crc, src + p, 4);
@@ -639,13 +641,29 @@ int64_t stream_decode_range(mlz_ctx* c, bool ignore_crc, const uint8_t* src, std
     return 0;
 }
 
+int64_t stream_decode_chunks(mlz_ctx* const* workers, size_t k, bool ignore_crc, const uint8_t* src, std::vector<StreamChunk>& chunks, uint8_t* dst,
+                             size_t total);
+
 // The chunk walk, then the chunks dealt to `workers` in contiguous ranges of about equal output (one worker: this thread).
 // The Reader reports the first error in stream order: the lowest failing range's.
+// A framing error comes after the chunks in front of it: those are decoded and checked first, and their first error wins; the framing
+// error is reported only when they all pass (and fit in dst: else -MLZ_ERR_DST_TOO_SMALL, where the Reader's write would fail).
 int64_t stream_decode_over(mlz_ctx* const* workers, size_t k, bool ignore_crc, const uint8_t* src, size_t slen, uint8_t* dst, size_t dst_cap) {
     std::vector<StreamChunk> chunks;
-    const int64_t total = stream_parse(src, slen, &chunks);
-    if (total < 0) return total;
-    if (size_t(total) > dst_cap) return -MLZ_ERR_DST_TOO_SMALL;
+    const int64_t parsed = stream_parse(src, slen, &chunks);
+    if (parsed < 0) {
+        const size_t prefix = chunks.empty() ? 0 : chunks.back().out_off + chunks.back().n;
+        if (prefix > dst_cap) return -MLZ_ERR_DST_TOO_SMALL;
+        const int64_t r = prefix ? stream_decode_chunks(workers, k, ignore_crc, src, chunks, dst, prefix) : 0;
+        return r < 0 ? r : parsed;
+    }
+    if (size_t(parsed) > dst_cap) return -MLZ_ERR_DST_TOO_SMALL;
+    return stream_decode_chunks(workers, k, ignore_crc, src, chunks, dst, size_t(parsed));
+}
+
+// The parsed chunks (total: their decoded bytes) dealt to the workers; returns total or the first error in stream order.
+int64_t stream_decode_chunks(mlz_ctx* const* workers, size_t k, bool ignore_crc, const uint8_t* src, std::vector<StreamChunk>& chunks, uint8_t* dst,
+                             size_t total) {
     for (size_t j = 0; j < k; j++) { std::lock_guard<std::mutex> lk(workers[j]->mu); begin_decode_call(workers[j]); }   // (workers that get no chunk included)
     const size_t nck = chunks.size();
     if (nck == 0) return 0;
@@ -654,7 +672,7 @@ int64_t stream_decode_over(mlz_ctx* const* workers, size_t k, bool ignore_crc, c
         mlz_ctx* c = workers[0];
         std::lock_guard<std::mutex> lk(c->mu);
         const int64_t r = stream_decode_range(c, ignore_crc, src, chunks, 0, nck, dst, uint64_t(total));
-        return r ? r : total;
+        return r ? r : int64_t(total);
     }
     // range j ends where the output passes j + 1 k-ths of the total
     std::vector<size_t> cut(k + 1, nck);
@@ -678,7 +696,7 @@ int64_t stream_decode_over(mlz_ctx* const* workers, size_t k, bool ignore_crc, c
     work(0);
     for (std::thread& t : th) t.join();
     for (size_t j = 0; j < k; j++) if (rcs[j]) return rcs[j];
-    return total;
+    return int64_t(total);
 }
 
 }  // namespace
@@ -790,6 +808,14 @@ int64_t mlz_stream_decoded_len(const uint8_t* src, size_t n) {
     if (!src && n) return -MLZ_ERR_ARG;
     std::vector<StreamChunk> chunks;
     return stream_parse(src, n, &chunks);
+}
+
+int64_t mlz_stream_decoded_prefix_len(const uint8_t* src, size_t n) {
+    if (!src && n) return -MLZ_ERR_ARG;
+    std::vector<StreamChunk> chunks;
+    const int64_t r = stream_parse(src, n, &chunks);
+    if (r >= 0) return r;
+    return chunks.empty() ? 0 : int64_t(chunks.back().out_off + chunks.back().n);
 }
 
 int64_t mlz_stream_decode(mlz_ctx* c, uint32_t flags, const uint8_t* src, size_t n, uint8_t* dst, size_t dst_cap) {

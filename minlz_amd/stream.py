@@ -221,7 +221,15 @@ class Reader:
         if not pending:
             return
         comp = [(i, p) for i, p in enumerate(pending) if p[0] in ("c", "c3")]
-        decoded = self.backend.decode_bodies([p[1] for _, p in comp]) if comp else []
+        try:
+            decoded = self.backend.decode_bodies([p[1] for _, p in comp]) if comp else []
+        except api.MinLZError:
+            # the Reader reports the first error in stream order: a chunk in front of the corrupt one may fail its CRC
+            for p in pending:
+                d = self.backend.decode_bodies([p[1]])[0] if p[0] in ("c", "c3") else p[1]
+                if not self.ignore_crc and self.backend.crcs([p[3] if p[0] == "c3" else d])[0] != p[2]:
+                    raise api.ErrCRC()
+            raise
         res = [None] * len(pending)
         for (i, _), d in zip(comp, decoded):
             res[i] = d
@@ -239,10 +247,18 @@ class Reader:
 
     def WriteTo(self, w):
         """Reader.WriteTo / DecodeConcurrent (reader.go:575-992): returns bytes written."""
+        pending = []
+        try:
+            return self._write_to(w, pending)
+        except api.MinLZError:
+            # a framing error is reported after the chunks in front of it: theirs come first in stream order
+            self._drain(pending, w)
+            raise
+
+    def _write_to(self, w, pending):
         max_block = self.max_block_org
         read_header = want_eof = False
         stream_out = 0
-        pending = []
         while True:
             hdr = self._read_full(4, allow_eof=not want_eof or self.partial)
             if hdr is None:

@@ -148,9 +148,12 @@ def test_stream_abi_errors(ctx):
     with pytest.raises(mz.ErrCRC):
         mz.stream_decode(bytes(bad), ctx=ctx)
     assert mz.stream_decode(bytes(bad), ignore_crc=True, ctx=ctx) == d    # ReaderIgnoreCRC
-    bad = bytearray(st); bad[40] ^= 0xff                     # token bytes: corrupt data or CRC mismatch
-    with pytest.raises((mz.ErrCorrupt, mz.ErrCRC)):
+    bad = bytearray(st); bad[40] ^= 0xff                     # token bytes: corrupt data or CRC mismatch, exactly as the oracle says
+    with pytest.raises(O.OracleError) as want:
+        O.stream_decode(bytes(bad), len(d))
+    with pytest.raises(mz.MinLZError) as got:
         mz.stream_decode(bytes(bad), ctx=ctx)
+    assert got.value.code == want.value.code
     with pytest.raises(mz.ErrCorrupt):
         mz.stream_decode(bytes(st[:len(st) // 2]), ctx=ctx)  # truncated inside a chunk
     with pytest.raises(mz.ErrCorrupt):
@@ -195,5 +198,8 @@ def test_chunk_type_3_crc_over_compressed_bytes(ctx):
     assert out.getvalue() == d
     bad = bytearray(s3)
     bad[len(bad) // 2] ^= 0x40
-    with pytest.raises(mz.MinLZError):
+    with pytest.raises(O.OracleError) as want:
+        O.stream_decode(bytes(bad), len(d))
+    with pytest.raises(mz.MinLZError) as got:
         mz.stream_decode(bytes(bad), ctx=ctx)
+    assert got.value.code == want.value.code

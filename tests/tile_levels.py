@@ -5,7 +5,8 @@ conformant to one of the three level patterns (the exec pass then runs its tiles
 settled by a team of 1, 2 or 4 workgroups).  A miss there is not an error: it is a schedule under which a tile may read a source tile
 that has not been written yet.  This module says, byte range by byte range and in the slow obvious way, what the verdict must be.
 
-- walk(body, dlen): the tokens of a block body, parsed from the format as oracle/minlz_oracle.c decodes it.
+- walk(body, dlen): the tokens of a block body, parsed from the format as oracle/minlz_oracle.c decodes it; walk_tokens(body) adds each
+  token's stream offset, header length and form.
 - apply(ops, dlen): the bytes those tokens produce.
 - verdict(ops, dlen): the patterns the block fits, the one the decoder must pick, general or not, and the team size.
 - cases(): hand-built blocks (body, expected bytes, intended verdict) around the rule; the intent is stated per (destination tile,
@@ -75,9 +76,14 @@ def make_verdict(fits, nearest, crosses):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the format (oracle/minlz_oracle.c, mlzo_decode_body)
 # ---------------------------------------------------------------------------------------------------------------------------------
-def walk(body, dlen):
-    """Yields (dpos, lit, off, cp) per token: output position, literal bytes, effective offset (a repeat's is the one in force) and
-    copy length.  Raises ValueError on a body the oracle would reject for its framing."""
+Token = namedtuple("Token", "spos hlen form dpos lit off cp")
+# spos: stream offset of the token; hlen: its header bytes (tag, length and offset fields; the literal bytes follow them); form: "literal",
+# "repeat", "copy1", "copy2", "copy3" or "copy2_lits" (a fused copy3 with literals is "copy3" with lit != b"")
+
+
+def walk_tokens(body):
+    """Yields a Token per token of a block body, as oracle/minlz_oracle.c parses it (off: the effective offset; a repeat's is the one in
+    force).  Raises ValueError on a token that runs past the end of the body; says nothing about offsets or the total."""
     b = bytes(body)
     n = len(b)
     s, d, offset = 0, 0, 1   # the initial offset is 1
@@ -90,6 +96,7 @@ def walk(body, dlen):
         return int.from_bytes(b[at:at + k], "little")
 
     while s < n:
+        t0 = s
         t = b[s]
         kind = t & 3
         lit = b""
@@ -100,15 +107,16 @@ def walk(body, dlen):
             length = x + 1 if x < 29 else uint(s + 1, k - 1) + 30
             s += k
             if t & 4:                            # repeat: a copy at the offset in force
-                yield d, b"", offset, length
+                yield Token(t0, k, "repeat", d, b"", offset, length)
                 d += length
                 continue
             need(length)
-            yield d, b[s:s + length], offset, 0
+            yield Token(t0, k, "literal", d, b[s:s + length], offset, 0)
             s += length
             d += length
             continue
         if kind == 1:                            # copy1
+            form = "copy1"
             need(2)
             length = (t >> 2) & 15
             offset = (uint(s, 2) >> 6) + 1
@@ -120,6 +128,7 @@ def walk(body, dlen):
             else:
                 length += 4
         elif kind == 2:                          # copy2
+            form = "copy2"
             need(3)
             length = t >> 2
             offset = uint(s + 1, 2) + 64
@@ -137,11 +146,13 @@ def walk(body, dlen):
             s += 4
             litlen = (val >> 3) & 3
             if not val & 4:
+                form = "copy2_lits"
                 length = 4 + ((val >> 5) & 7)
                 offset = ((val >> 8) & 0xFFFF) + 64
                 s -= 1
                 litlen += 1
             else:
+                form = "copy3"
                 lt = (val >> 5) & 63
                 offset = (val >> 11) + 65536
                 if lt < 61:
@@ -154,8 +165,17 @@ def walk(body, dlen):
             need(litlen)
             lit = b[s:s + litlen]
             s += litlen
-        yield d, lit, offset, length
+        yield Token(t0, s - t0 - len(lit), form, d, lit, offset, length)
         d += len(lit) + length
+
+
+def walk(body, dlen):
+    """Yields (dpos, lit, off, cp) per token: output position, literal bytes, effective offset (a repeat's is the one in force) and
+    copy length.  Raises ValueError on a body the oracle would reject for its framing."""
+    d = 0
+    for t in walk_tokens(body):
+        yield t.dpos, t.lit, t.off, t.cp
+        d = t.dpos + len(t.lit) + t.cp
     if d != dlen:
         raise ValueError("body decodes to %d bytes, not %d" % (d, dlen))
 
