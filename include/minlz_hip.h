@@ -199,10 +199,19 @@ int64_t mlz_stream_encode_gather_device(mlz_ctx* ctx, int level, uint32_t block_
                                 * far-source lines still in the L2); 0 = the separate serializer kernel of rounds 2-5 on the same records (byte-identical; cross-checks) */
 #define MLZ_OPT_LEVEL0_KERNEL 23 /* decode: 1 (default) = a batch's level-0 tiles, when no more than the device has CUs, are decoded by dec_level0_kernel before the exec pass; 0 = by the exec pass (cross-checks) */
 #define MLZ_OPT_FOLD_LAYOUT 24  /* encode: 1 (default) = a group whose every block has tiles and room gets its layout (piece offsets, stored-or-not, header, length) from the gather kernel; 0 = always encode_layout_kernel (cross-checks) */
-#define MLZ_OPT_INDEX_PASSES 15 /* decode, cross-checks: 1 = the index pass as the three kernels of rounds 2-3 instead of dec_index1 / dec_index2 / dec_viol (default 0) */
-/* (debug, timing experiments: option 16 = 1 makes mlz_decode_batch_device return after the index pass, without output) */
 #define MLZ_OPT_GEN_SPIN 9     /* patience of the general-block decode with a tile's ready flag, in polls (~0.3 us each; default 2^24); tests */
 #define MLZ_OPT_GEN_PACKED 13  /* tests: 1 = general blocks settle through the byte-packed pool (the fallback of tiles whose slots do not fit) */
+#define MLZ_OPT_DEBUG_STATUS 3      /* debug: 1 = a failed block's negative length carries the failure site (bits 8 and up) besides the error code */
+#define MLZ_OPT_PROFILE 4           /* debug: 1 = per-phase cycle counters on (16 x u64: 0-7 encode, 8-15 decode) */
+#define MLZ_OPT_PROFILE_READ 5      /* debug: copy the counters (128 bytes) to the host buffer whose address is the value */
+#define MLZ_OPT_TILE_TIMELINE_READ 7 /* debug: copy the exec pass's per-tile timeline (4 x u64 per tile, 100 MHz clock) to the host buffer whose address is the value */
+#define MLZ_OPT_GENERAL_ALGO 8      /* decode: 0 = general blocks by the pointer-jumping pass (default), 1 = on the exec pass's tile chain */
+#define MLZ_OPT_HOST_GROUP_ENC 10   /* tuning: MiB per group of a host-pointer encode batch */
+#define MLZ_OPT_HOST_GROUP_DEC 11   /* tuning: MiB per group of a host-pointer decode batch */
+#define MLZ_OPT_TIMER_MASK 12       /* which timers record events (bit i = mlz_timer_name(i); default all) */
+#define MLZ_OPT_FAR_SLICES_L2 18    /* debug, cross-checks: 1 = LevelBalanced's far tables by far_build_kernel (the slice kernel of round 4) even without tile levels */
+#define MLZ_OPT_GEN_SETTLE_CAP 20   /* tuning: role S workgroups of the general-block pass at most (default: a quarter of the device) */
+/* (15 and 16 are retired: they selected a removed index pass and a debug stop; the numbers are not reused) */
 int mlz_set_option(mlz_ctx* ctx, int opt, int64_t value);
 /* Milliseconds spent in each kernel family, measured with HIP events on the caller's stream.
  * mlz_set_option(ctx, MLZ_TIMER_ENABLE, 1): the last *_batch_device call (mlz_get_timers waits for it);

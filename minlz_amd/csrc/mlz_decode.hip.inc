@@ -15,10 +15,9 @@
 //   D3 index     mlz_decode_index.hip.inc (round 4): per segment, from its true entry — the regions chained through D1's region
 //                exits, token starts found by a lane per region, then a lane per token: the block's TOKEN LIST (stream position
 //                of every token, per 64 tokens {output position, repeat offset}), per 32 KiB output tile the token covering its
-//                first byte, the level conformance of every copy; the three kernels of rounds 2-3 (a: per-region walk, b: per-block
-//                scan, c: lists) are kept below as a cross-check (MLZ_OPT_INDEX_PASSES); d (here): the tile schedule.
+//                first byte, the level conformance of every copy; dec_viol_kernel and the tile schedule (D3d) are here.
 //   D4 exec      mlz_decode_exec.hip.inc: one 3-wave workgroup per 32 KiB output tile, a lane per TOKEN (64 consecutive
-//                entries of the token list D3c made), literals and copies from earlier tiles unordered, copies inside
+//                entries of the token list D3 made), literals and copies from earlier tiles unordered, copies inside
 //                the tile in dependency passes, tile image in LDS flushed with 16-byte write-through stores; a tile
 //                waits once for its lower-level source tiles (workgroup i takes the i-th tile of the level-ordered schedule: no deadlock).
 //   general      mlz_decode_general.hip.inc: blocks without a level structure (other encoders', and this library's LevelBalanced):
@@ -26,16 +25,6 @@
 //
 // Output is bit-exact with the reference for valid input; invalid input is reported as corrupt
 // exactly when the reference's decoder does (length/offset/stream-end checks).
-
-#ifndef MLZ_DBG_UPFRONT
-#define MLZ_DBG_UPFRONT 1
-#endif
-#ifndef MLZ_DBG_WIDE_N
-#define MLZ_DBG_WIDE_N 1
-#endif
-#ifndef MLZ_DBG_WIDE_F
-#define MLZ_DBG_WIDE_F 1
-#endif
 
 namespace mlz {
 
@@ -53,11 +42,11 @@ struct DecBlock {
     uint32_t dlen;      // decoded bytes
     int32_t status;     // 0 ok, else MLZ_ERR_*
     uint32_t literals;  // 1 = stored block: body is copied verbatim
-    uint32_t total_out; // filled by D3b
-    uint32_t general;   // set by D3c when the block fits neither level pattern (bit 0); bit 1: the block is
+    uint32_t total_out; // filled by D3
+    uint32_t general;   // set by D3 when the block fits neither level pattern (bit 0); bit 1: the block is
                         // decoded by the pointer-jumping pass (mlz_decode_general.hip.inc) instead of tile by tile
-    uint32_t viol;      // D3c: bit 0 = some copy breaks the fast level pattern, bit 1 = ... the dense one, bit 2 = ... the three-level one
-    uint32_t ntok;      // D3b: tokens in the stream (the exec pass deals them out 64 at a time)
+    uint32_t viol;      // D3: bit 0 = some copy breaks the fast level pattern, bit 1 = ... the dense one, bit 2 = ... the three-level one
+    uint32_t ntok;      // D3: tokens in the stream (the exec pass deals them out 64 at a time)
 };
 __device__ __forceinline__ int lane_of(int tid) { return tid & 63; }
 constexpr uint32_t kViolAll = 7;   // a block that breaks every pattern (bits 0-2) is a general block
@@ -311,10 +300,10 @@ __global__ __launch_bounds__(kExitThreads) void dec_exit_kernel(const uint8_t* _
     __syncthreads();
     const uint32_t r0 = uint32_t(tid) * 64;
     if (tid < int(kSegThreads)) {
-    // These "region exits" are what the index pass (D3a) chains through once the true entry of the segment is known.  Kept
+    // These "region exits" are what the index pass (D3) chains through once the true entry of the segment is known.  Kept
     // as ONE BYTE per stream byte: the distance of the exit from the end of the region, 255 = further than 254 bytes (a long
     // literal) or the path ends — whoever needs that exit decodes the token at the offset itself (round 2 kept 16-bit
-    // positions: twice the traffic here and a conversion of 64 values per lane in D3a).
+    // positions: twice the traffic here and a conversion of 64 values per lane in D3).
     {
         uint8_t* rx = rexit_tab + (size_t(seg) << kSegLog) + r0;
         const uint32_t rend = r0 + 64;
@@ -336,59 +325,31 @@ __global__ __launch_bounds__(kExitThreads) void dec_exit_kernel(const uint8_t* _
     // value.  Two levels keep it parallel: each wave finishes its own group of consecutive regions right to left
     // (one LDS round trip per region), then the groups are finished right to left by the whole workgroup.
     // (Plain pointer doubling over all 8192 entries took seven rounds and half of this kernel's time.)
-#ifndef MLZ_EXIT_JUMP
-#define MLZ_EXIT_JUMP 0
-#endif
-    if (!MLZ_EXIT_JUMP) {
-        constexpr uint32_t kWaves = kExitThreads / 64;
-        constexpr uint32_t kGroupRegions = (kSeg / 64) / kWaves;      // regions per wave
-        constexpr uint32_t kGroup = kGroupRegions * 64;               // offsets per group
-        static_assert(kGroupRegions * kWaves * 64 == kSeg, "whole regions per wave");
-        const uint32_t lane = uint32_t(tid) & 63, wv = uint32_t(tid) >> 6;
-        __syncthreads();
-        {
-            const uint32_t g0 = wv * kGroup, g1 = g0 + kGroup;
-            for (int r = int(kGroupRegions) - 2; r >= 0; r--) {  // (the group's last region points beyond the group already)
-                const uint32_t i = g0 + uint32_t(r) * 64 + lane;
-                const uint32_t v = jmp[pj(i)];
-                if (v < g1) jmp[pj(i)] = jmp[pj(v)];              // v lies in a later region of my group: final within the group
-            }
+    constexpr uint32_t kWaves = kExitThreads / 64;
+    constexpr uint32_t kGroupRegions = (kSeg / 64) / kWaves;      // regions per wave
+    constexpr uint32_t kGroup = kGroupRegions * 64;               // offsets per group
+    static_assert(kGroupRegions * kWaves * 64 == kSeg, "whole regions per wave");
+    const uint32_t lane = uint32_t(tid) & 63, wv = uint32_t(tid) >> 6;
+    __syncthreads();
+    {
+        const uint32_t g0 = wv * kGroup, g1 = g0 + kGroup;
+        for (int r = int(kGroupRegions) - 2; r >= 0; r--) {  // (the group's last region points beyond the group already)
+            const uint32_t i = g0 + uint32_t(r) * 64 + lane;
+            const uint32_t v = jmp[pj(i)];
+            if (v < g1) jmp[pj(i)] = jmp[pj(v)];              // v lies in a later region of my group: final within the group
         }
-        __syncthreads();
-        // Every entry now points beyond its GROUP.  Only the first kExitKeep offsets' exits are kept, so they alone are followed to the
-        // segment's end: at most one hop per group (rounds 2-3 finished all 8192 entries group by group, 7 barriers and 14 updates per
-        // thread, to keep 256 of them).
-        static_assert(kExitKeep <= kExitThreads, "a thread per kept exit");
-        if (tid < int(kExitKeep)) {
-            uint32_t v = jmp[pj(uint32_t(tid))];
-            while (v < kSeg) v = jmp[pj(v)];
-            exit_tab[size_t(seg) * kExitKeep + tid] = s0 + (v & 0x7fffffffu);
-        }
-        return;
-    } else {
-    // pointer jumping until every entry has left the segment
-    for (;;) {
-        __syncthreads();
-        bool pending = false;
-        for (uint32_t i0 = h0; i0 < h0 + kExitSpan; i0 += 16) {  // 16 independent look-ups in flight
-            uint32_t v[16], u[16];
-#pragma unroll
-            for (uint32_t q = 0; q < 16; q++) v[q] = jmp[pj(i0 + q)];
-#pragma unroll
-            for (uint32_t q = 0; q < 16; q++) u[q] = v[q] < kSeg ? jmp[pj(v[q])] : v[q];
-#pragma unroll
-            for (uint32_t q = 0; q < 16; q++) {
-                if (v[q] < kSeg) { jmp[pj(i0 + q)] = u[q]; pending |= u[q] < kSeg; }
-            }
-        }
-        if (!__syncthreads_or(pending)) break;
     }
+    __syncthreads();
+    // Every entry now points beyond its GROUP.  Only the first kExitKeep offsets' exits are kept (a segment is entered where a token of the
+    // previous one ends, i.e. a few bytes in — further in only behind a long literal run, and dec_chain_kernel then follows the region exits:
+    // exit_slow), so they alone are followed to the segment's end: at most one hop per group (rounds 2-3 finished all 8192 entries group by
+    // group, 7 barriers and 14 updates per thread, to keep 256 of them; keeping all 8192 was 4 bytes of workspace traffic per stream byte).
+    static_assert(kExitKeep <= kExitThreads, "a thread per kept exit");
+    if (tid < int(kExitKeep)) {
+        uint32_t v = jmp[pj(uint32_t(tid))];
+        while (v < kSeg) v = jmp[pj(v)];
+        exit_tab[size_t(seg) * kExitKeep + tid] = s0 + (v & 0x7fffffffu);
     }
-    // Only the exits of the segment's first kExitKeep offsets are kept: a segment is entered where a token of the previous
-    // one ends, i.e. a few bytes in — further in only behind a long literal run, and dec_chain_kernel then follows the region
-    // exits (exit_slow).  (Keeping all 8192 of them was 4 bytes of workspace traffic per stream byte.)
-    uint32_t* ex = exit_tab + size_t(seg) * kExitKeep;
-    for (uint32_t i = tid; i < kExitKeep; i += kExitThreads) ex[i] = s0 + (jmp[pj(i)] & 0x7fffffffu);
 }
 
 // exit of a parse that enters its segment at body offset pos, from the region exits (D1) — the slow way, for entries
@@ -583,352 +544,6 @@ __global__ __launch_bounds__(kChainThreads) void dec_chain_kernel(const BlockInf
         pos = et(pos);
     }
     if (pos != d.clen) dec[bi].status = 1 | (1 << 8);
-}
-
-// ---------------- D3: index ----------------
-// Shared by the two index passes: loads the segment, computes per-region exits, chains the
-// regions from the true entry and lets every lane walk its region.
-struct RegionWalk {
-    uint32_t entry;  // segment-relative offset of the first token starting in my region (0xffff = none)
-    uint32_t out;    // output bytes produced by tokens starting in my region
-    uint32_t last;   // last explicit offset set by those tokens (0 = none)
-    uint32_t ntok;   // tokens starting in my region
-};
-
-__device__ __forceinline__ RegionWalk dec_region_walk(const uint8_t* src, uint32_t s0, uint32_t clen, uint32_t entry_abs,
-                                                      uint8_t* rex8, uint16_t* rentry, const uint8_t* __restrict__ rexit_g, int tid) {
-    const uint32_t avail = clen - s0;
-    rentry[tid] = 0xffff;
-    const uint32_t r0 = uint32_t(tid) * 64, r1 = r0 + 64;
-    // region exit of every offset in my region (computed by D1, dec_exit_kernel: ONE BYTE per offset, the distance from the end
-    // of the region, 255 = further than that or the end of the path), staged in LDS for the chain below.  8.5 KiB per segment:
-    // the pass is short of wavefronts, not of anything else, and LDS is what limits the workgroups per CU.  Rows of 64 + 4
-    // bytes: the threads' dword stores fall into different banks.
-    {
-        const uint4* g = reinterpret_cast<const uint4*>(rexit_g + r0);
-        uint4 xs[4];
-#pragma unroll
-        for (uint32_t q = 0; q < 4; q++) xs[q] = g[q];   // all four requests before the first LDS store
-        uint32_t* row = reinterpret_cast<uint32_t*>(rex8 + uint32_t(tid) * 68);
-#pragma unroll
-        for (uint32_t q = 0; q < 4; q++) { row[4 * q] = xs[q].x; row[4 * q + 1] = xs[q].y; row[4 * q + 2] = xs[q].z; row[4 * q + 3] = xs[q].w; }
-    }
-    __syncthreads();
-    if (tid == 0) {  // chain the regions from the true entry
-        uint32_t p = entry_abs - s0;
-        while (p < kSeg && p < avail) {
-            rentry[p >> 6] = uint16_t(p);
-            const uint32_t rend = ((p >> 6) + 1) * 64;
-            const uint32_t dlt = rex8[(p >> 6) * 68 + (p & 63)];
-            if (dlt != 255) { p = rend + dlt; continue; }
-            // a long token (or the end of the path): token by token until the region is left
-            uint64_t q = p;
-            while (q < rend && q < avail) q += tok_advance(uint32_t(ld64_clamped(src, s0 + uint32_t(q), clen)));
-            p = q > 0x7fffffffull ? 0x7fffffffu : uint32_t(q);
-        }
-    }
-    __syncthreads();
-    RegionWalk rw;
-    rw.entry = rentry[tid]; rw.out = 0; rw.last = 0; rw.ntok = 0;
-    const bool whole = uint64_t(s0) + kSeg + 8 <= clen;   // every 8-byte read of this segment stays inside the stream
-    if (rw.entry != 0xffff) {
-        uint32_t p = rw.entry;
-        const uint32_t lim = r1 < avail ? r1 : avail;
-        while (p < lim) {
-            // (token bytes straight from global memory: a lane's region is one cache line, and without an 8 KiB stage of the segment
-            // twice as many workgroups fit a CU — the pass is short of wavefronts, not of bandwidth)
-            Tok t = decode_tok(whole ? ld64u(src + s0 + p) : ld64_clamped(src, s0 + p, clen));
-            rw.out += t.lit + t.cp;
-            rw.ntok++;
-            if (t.off) rw.last = t.off;
-            p += t.hdr + t.lit;   // (< 2^25: a literal run is at most 2^24 + 29 bytes)
-        }
-    }
-    return rw;
-}
-
-constexpr uint32_t kRexitEntries = kSeg + 2 * (kSeg >> 6) + 8;  // padded (pr)
-constexpr uint32_t kRex8Bytes = kSegThreads * 68;   // one byte per offset, rows of 64 + 4
-constexpr uint32_t kIndexLds = kRex8Bytes + kSegThreads * 2 + kSegThreads * 8 + 64;   // region exits (bytes), region entries, scan scratch
-constexpr uint32_t kTokStage = 4096;                    // D3c: token positions of a segment staged in LDS (16 bits each) before they go out in order
-constexpr uint32_t kIndexCLds = kSegThreads * 8 + 64 + kTokStage * 2;   // D3c: scan scratch + the stage
-
-// Exclusive scan over the 128 regions of a segment, done by its two wavefronts: `out` summed, `last` = last
-// non-zero value carried forward.  Returns (sum of out before me + run0, offset in force before me or rep0);
-// *tot_out / *tot_last receive the segment totals (tot_last = 0 when no region set an offset).
-struct RegionPrefix { uint32_t dpos, rep, rank; };
-__device__ __forceinline__ RegionPrefix region_scan(uint32_t out, uint32_t last, uint32_t ntok, uint32_t run0, uint32_t rep0, uint32_t rank0,
-                                                    uint32_t* red /* >= 8 words of LDS */, int tid, uint64_t* tot_out, uint32_t* tot_last, uint32_t* tot_ntok) {
-    const int lane = tid & 63, wv = tid >> 6;
-    // 64-bit-safe prefix sum of `out` (two 32-bit scans of 24-bit and 8-bit parts)
-    const uint32_t lo_incl = wave_incl_scan_u32(out & 0xffffffu), hi_incl = wave_incl_scan_u32(out >> 24);
-    const uint64_t incl = uint64_t(lo_incl) + (uint64_t(hi_incl) << 24);
-    const uint32_t tag = last ? uint32_t(lane) + 1 : 0;
-    const uint32_t t_incl = wave_incl_max_u32(tag);
-    const uint32_t t_excl = uint32_t(__builtin_amdgcn_update_dpp(0, int(t_incl), 0x138 /* wave_shr:1 */, 0xf, 0xf, true));
-    const uint32_t l_from = __shfl(last, int(t_excl ? t_excl - 1 : 0));
-    const uint32_t t_all = rdlane(t_incl, 63);
-    const uint32_t w_last = t_all ? rdlane(last, int(t_all - 1)) : 0;
-    const uint64_t w_sum = (uint64_t(rdlane(hi_incl, 63)) << 24) + rdlane(lo_incl, 63);
-    const uint32_t n_incl = wave_incl_scan_u32(ntok);   // (at most one token per stream byte: 32 bits are plenty)
-    const uint32_t w_ntok = rdlane(n_incl, 63);         // (read with all lanes on: under `lane == 0` the scan itself may be sunk into the branch)
-    if (lane == 0) { red[4 * wv] = uint32_t(w_sum); red[4 * wv + 1] = uint32_t(w_sum >> 32); red[4 * wv + 2] = w_last; red[4 * wv + 3] = w_ntok; }
-    __syncthreads();
-    const uint64_t sum0 = uint64_t(red[0]) | (uint64_t(red[1]) << 32), sum1 = uint64_t(red[4]) | (uint64_t(red[5]) << 32);
-    const uint32_t last0 = red[2], last1 = red[6];
-    *tot_out = sum0 + sum1;
-    *tot_last = last1 ? last1 : last0;
-    *tot_ntok = red[3] + red[7];
-    uint64_t before = uint64_t(run0) + (incl - out) + (wv ? sum0 : 0);
-    RegionPrefix r;
-    r.dpos = before > 0x7fffffffull ? 0x7fffffffu : uint32_t(before);
-    r.rep = t_excl ? l_from : (wv && last0 ? last0 : rep0);
-    r.rank = rank0 + (n_incl - ntok) + (wv ? red[3] : 0);
-    __syncthreads();
-    return r;
-}
-
-// D3a: per-segment totals; also leaves each region's entry / output / last offset for D3c.
-__global__ __launch_bounds__(kSegThreads) void dec_index_a_kernel(const uint8_t* __restrict__ src_base, const BlockInfo* __restrict__ blocks,
-                                                          const uint32_t* __restrict__ seg_block, const DecBlock* __restrict__ dec,
-                                                          const uint32_t* __restrict__ seg_entry, uint32_t* __restrict__ seg_out,
-                                                          uint32_t* __restrict__ seg_last, const uint8_t* __restrict__ rexit_tab,
-                                                          uint32_t* __restrict__ reg_out, uint32_t* __restrict__ reg_last,
-                                                          uint32_t* __restrict__ reg_entry /* entry | token count << 16 */, uint32_t* __restrict__ seg_ntok) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    uint8_t* rex8 = smem;
-    uint16_t* rentry = reinterpret_cast<uint16_t*>(smem + kRex8Bytes);
-    uint32_t* red = reinterpret_cast<uint32_t*>(rentry + kSegThreads);
-    const uint32_t seg = blockIdx.x;
-    const uint32_t e = seg_entry[seg];
-    const int tid = threadIdx.x;
-    if (e == kNone) { if (tid == 0) { seg_out[seg] = 0; seg_last[seg] = 0; seg_ntok[seg] = 0; } return; }
-    const uint32_t bi = seg_block[seg];
-    const BlockInfo b = blocks[bi];
-    const DecBlock d = dec[bi];
-    if (d.status != 0) { if (tid == 0) { seg_out[seg] = 0; seg_last[seg] = 0; seg_ntok[seg] = 0; } return; }
-    const uint32_t s0 = (seg - b.first_seg) << kSegLog;
-    RegionWalk rw = dec_region_walk(src_base + b.src_off + d.body_off, s0, d.clen, e, rex8, rentry, rexit_tab + (size_t(seg) << kSegLog), tid);
-    const size_t ri = size_t(seg) * kSegThreads + tid;
-    reg_out[ri] = rw.out; reg_last[ri] = rw.last; reg_entry[ri] = (rw.entry & 0xffffu) | (rw.ntok << 16);
-    uint64_t tot; uint32_t tl_, tn_;
-    (void)region_scan(rw.out, rw.last, rw.ntok, 0, 0, 0, red, tid, &tot, &tl_, &tn_);
-    if (tid == 0) {
-        seg_out[seg] = tot > 0x7fffffffull ? 0x7fffffffu : uint32_t(tot);
-        seg_last[seg] = tl_;
-        seg_ntok[seg] = tn_;
-    }
-}
-
-// D3b: per block, exclusive scan of segment totals + carried repeat offset; validates the total.
-// One wavefront per block: 64 segments per round, DPP prefix sum for the totals and a prefix maximum
-// over "index of the last segment that set an offset" for the repeat offset in force.
-__global__ __launch_bounds__(64) void dec_index_b_kernel(const BlockInfo* __restrict__ blocks, DecBlock* __restrict__ dec, uint32_t* __restrict__ seg_out,
-                                                        uint32_t* __restrict__ seg_last, const uint32_t* __restrict__ seg_entry, uint32_t* __restrict__ seg_ntok, int n) {
-    const int bi = blockIdx.x;
-    const int lane = threadIdx.x;
-    if (bi >= n) return;
-    const BlockInfo b = blocks[bi];
-    const DecBlock d = dec[bi];
-    if (d.status != 0 || d.literals) return;
-    const uint32_t nseg = (d.clen + kSeg - 1) >> kSegLog;
-    uint64_t run = 0;      // output bytes before the current round (64-bit: corrupt streams can claim anything)
-    uint32_t rep = 1;      // initial repeat offset is 1 (decode.go:185)
-    uint32_t rank = 0;     // tokens before the current round
-    // every lane takes 16 consecutive segments: sixteen independent loads, a local pass, one wave scan of the lane totals
-    // (64 segments per round with a load each was 8 dependent memory round trips for an 8 MiB block)
-    for (uint32_t k0 = 0; k0 < nseg; k0 += 1024) {
-        uint32_t o[16], l[16], nt[16];
-#pragma unroll
-        for (int j = 0; j < 16; j++) {
-            const uint32_t k = k0 + uint32_t(lane) * 16 + j;
-            const uint32_t seg = b.first_seg + (k < nseg ? k : 0);
-            o[j] = seg_out[seg]; l[j] = seg_last[seg]; nt[j] = seg_ntok[seg];
-            if (k >= nseg) { o[j] = 0; l[j] = 0; nt[j] = 0; }
-        }
-        uint64_t mine = 0;
-        uint32_t mylast = 0;   // last offset set inside my sixteen segments (0 = none)
-        uint32_t myn = 0;
-#pragma unroll
-        for (int j = 0; j < 16; j++) { mine += o[j]; myn += nt[j]; if (l[j]) mylast = l[j]; }
-        const uint32_t n_incl = wave_incl_scan_u32(myn);
-        uint32_t rk = rank + n_incl - myn;
-        // exclusive prefix of the lane totals in 64 bits: two 32-bit scans (low 24 bits, the rest)
-        const uint32_t lo_incl = wave_incl_scan_u32(uint32_t(mine) & 0xffffffu), hi_incl = wave_incl_scan_u32(uint32_t(mine >> 24));
-        const uint64_t incl = uint64_t(lo_incl) + (uint64_t(hi_incl) << 24);
-        uint64_t at = run + incl - mine;
-        // repeat offset in force before my first segment: the last non-zero `mylast` among earlier lanes, else the carried one
-        const uint32_t tag = mylast ? uint32_t(lane) + 1 : 0;
-        const uint32_t last_incl = wave_incl_max_u32(tag);
-        const uint32_t last_excl = uint32_t(__builtin_amdgcn_update_dpp(0, int(last_incl), 0x138 /* wave_shr:1 */, 0xf, 0xf, true));
-        const uint32_t l_from = __shfl(mylast, int(last_excl ? last_excl - 1 : 0));
-        uint32_t r = last_excl ? l_from : rep;
-#pragma unroll
-        for (int j = 0; j < 16; j++) {
-            const uint32_t k = k0 + uint32_t(lane) * 16 + j;
-            if (k < nseg) {
-                const uint32_t seg = b.first_seg + k;
-                seg_out[seg] = at > 0x7fffffffull ? 0x7fffffffu : uint32_t(at);
-                seg_last[seg] = r;
-                seg_ntok[seg] = rk;
-            }
-            at += o[j];
-            rk += nt[j];
-            if (l[j]) r = l[j];
-        }
-        run += (uint64_t(rdlane(hi_incl, 63)) << 24) + rdlane(lo_incl, 63);
-        rank += rdlane(n_incl, 63);
-        const uint32_t last_all = rdlane(last_incl, 63);
-        if (last_all) rep = rdlane(mylast, int(last_all - 1));
-    }
-    if (lane == 0) {
-        dec[bi].total_out = run > 0xffffffffull ? 0xffffffffu : uint32_t(run);
-        dec[bi].ntok = rank;
-        if (run != d.dlen) dec[bi].status = 1 | (2 << 8);  // d != len(dst), decode.go:615
-    }
-}
-
-// D3c: tile starts.
-__global__ __launch_bounds__(kSegThreads) void dec_index_c_kernel(const uint8_t* __restrict__ src_base, const BlockInfo* __restrict__ blocks,
-                                                          const uint32_t* __restrict__ seg_block, DecBlock* __restrict__ dec,
-                                                          const uint32_t* __restrict__ seg_entry, const uint32_t* __restrict__ seg_out,
-                                                          const uint32_t* __restrict__ seg_last, TileStart* __restrict__ tile_start,
-                                                          const uint32_t* __restrict__ reg_out,
-                                                          const uint32_t* __restrict__ reg_last, const uint32_t* __restrict__ reg_entry,
-                                                          const uint32_t* __restrict__ seg_rank, uint32_t* __restrict__ tok_pos,
-                                                          uint32_t* __restrict__ round_d, uint32_t* __restrict__ round_rep,
-                                                          uint32_t* __restrict__ n_general /* null: general blocks stay on the tile path */) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    uint32_t* red = reinterpret_cast<uint32_t*>(smem);
-    const uint32_t seg = blockIdx.x;
-    const uint32_t e = seg_entry[seg];
-    const int tid = threadIdx.x;
-    // a segment no token starts in (inside one long literal): position 0 is a safe lower bound for the exec pass
-    if (e == kNone) return;   // a segment no token starts in (inside one long literal): no list entries
-    const uint32_t bi = seg_block[seg];
-    const BlockInfo b = blocks[bi];
-    const DecBlock d = dec[bi];
-    if (d.status != 0) return;
-    const uint32_t s0 = (seg - b.first_seg) << kSegLog;
-    const uint32_t avail = d.clen - s0;
-    // region results of D3a (entry, output bytes, last offset): no second chain / walk here
-    const uint8_t* srcb = src_base + b.src_off + d.body_off;
-    const bool whole = uint64_t(s0) + kSeg + 8 <= d.clen;   // every 8-byte read of this segment stays inside the stream
-    RegionWalk rw;
-    {
-        const size_t ri = size_t(seg) * kSegThreads + tid;
-        const uint32_t en = reg_entry[ri];
-        rw.entry = en & 0xffffu; rw.ntok = en >> 16; rw.out = reg_out[ri]; rw.last = reg_last[ri];
-    }
-    uint64_t tot_unused; uint32_t last_unused, seg_tokens;
-    const RegionPrefix pre = region_scan(rw.out, rw.last, rw.ntok, seg_out[seg], seg_last[seg], seg_rank[seg], red, tid, &tot_unused, &last_unused, &seg_tokens);
-    uint32_t dpos = pre.dpos, rep = pre.rep, rank = pre.rank;
-    // The block's token list (the exec pass hands its tokens out 64 at a time, a lane per token): stream position of every
-    // token in stream order, and for every 64th token the output position where it starts and the repeat offset in force
-    // there.  The list is indexed like the stream (a token has at least one byte): entries first_seg * kSeg onwards.
-    uint32_t* tpos = tok_pos + (size_t(b.first_seg) << kSegLog);
-    uint32_t* rd = round_d + (size_t(b.first_seg) << (kSegLog - 6));
-    uint32_t* rr = round_rep + (size_t(b.first_seg) << (kSegLog - 6));
-    // The positions go through LDS: a lane's tokens are ~15 consecutive list entries, so the lanes' own stores would touch 64
-    // different cache lines per instruction; staged (segment-relative, 16 bits) they leave as whole lines.  A segment with more
-    // than kTokStage tokens (under two stream bytes per token) writes the rest directly.
-    uint16_t* stage = reinterpret_cast<uint16_t*>(smem + kSegThreads * 8 + 64);
-    const uint32_t seg_rank0 = seg_rank[seg];
-    // (a region no token starts in has entry 0xffff: its walk below is empty)
-    uint32_t p = rw.entry;
-    const uint32_t r1 = uint32_t(tid) * 64 + 64;
-    TileStart* ts = tile_start + b.first_tile;
-    uint32_t viol = 0;  // bit 0: breaks the fast level pattern, bit 1: the dense one, bit 2: the three-level one
-    uint32_t mask_kq = 0xffffffffu, ok_fast = 0, ok_dense = 0, ok_three = 0;   // which source tiles (mod 16) tile mask_kq may read, per pattern
-    const uint32_t lim = r1 < avail ? r1 : avail;
-    while (p < lim) {
-        Tok t = decode_tok(whole ? ld64u(srcb + s0 + p) : ld64_clamped(srcb, s0 + p, d.clen));   // (from global memory, like D3a)
-        const uint32_t olen = t.lit + t.cp;
-        if (rank - seg_rank0 < kTokStage) stage[rank - seg_rank0] = uint16_t(p); else tpos[rank] = s0 + p;
-        if ((rank & 63) == 0) { rd[rank >> 6] = dpos; rr[rank >> 6] = rep; }
-        if (t.cp) {
-            // Level conformance (DESIGN.md "Tile levels"): every tile a copy writes to reads, for its part of the
-            // copy, only itself or tiles of a strictly lower level.  Streams made by this library's encoder satisfy
-            // it (their copies never leave a tile), which lets the exec pass run tiles level by level instead of in
-            // position order; a copy of another encoder may straddle tiles — each part is checked for its own tile
-            // (the exec pass clips copies to its tile anyway); anything else is flagged and decoded by the
-            // position-independent path.
-            const uint32_t off = t.off ? t.off : rep;
-            const uint32_t dc = dpos + t.lit;
-            if (off != 0 && off <= dc && uint64_t(dc) + t.cp <= d.dlen) {
-                const uint32_t kd = dc >> kTileLog, kend = (dc + t.cp - 1) >> kTileLog;
-                const uint32_t sw0 = dc - off;
-                // The three verdicts per (destination tile, source tile) pair.  A lane's tokens mostly write to ONE tile, so what that tile may
-                // read — per pattern a 16-bit mask over the period of the source tiles with a strictly lower level — is kept from
-                // token to token; a source tile then costs a shift and an and-not per pattern instead of two table look-ups and three compares.
-                auto lower_mask = [](uint32_t pattern, uint32_t kq) -> uint32_t {   // bit t: tile t of the period has a lower level than tile kq
-                    const uint32_t mine = (pattern >> (2 * (kq & 15))) & 3;
-                    // level of tile t < mine  <=>  t's 2-bit field is below mine: the patterns are constants, so the three possible answers are too
-                    uint32_t lt1 = 0, lt2 = 0, lt3 = 0;
-                    for (uint32_t t = 0; t < 16; t++) {
-                        const uint32_t l = (pattern >> (2 * t)) & 3;
-                        lt1 |= (l < 1 ? 1u : 0u) << t; lt2 |= (l < 2 ? 1u : 0u) << t; lt3 |= (l < 3 ? 1u : 0u) << t;
-                    }
-                    return mine == 0 ? 0u : mine == 1 ? lt1 : mine == 2 ? lt2 : lt3;
-                };
-                auto check = [&](uint32_t kq, uint32_t s0t, uint32_t s1t) {  // tile kq reads tiles s0t..s1t (below kq)
-                    if (kq != mask_kq) {
-                        mask_kq = kq;
-                        ok_fast = lower_mask(kPatternFast, kq); ok_dense = lower_mask(kPatternDense, kq); ok_three = lower_mask(kPatternThree, kq);
-                    }
-                    for (uint32_t tsrc = s0t; tsrc <= s1t && tsrc < kq; tsrc++) {
-                        const uint32_t bit = 1u << (tsrc & 15);
-                        if (!(ok_fast & bit)) viol |= 1;
-                        if (!(ok_dense & bit)) viol |= 2;
-                        if (!(ok_three & bit)) viol |= 4;
-                    }
-                };
-                if (viol == kViolAll) {
-                    // nothing left to find out
-                } else if (kend == kd) {  // the usual case: the copy lands in one tile
-                    const uint32_t s0t = sw0 >> kTileLog;
-                    if (s0t != kd) check(kd, s0t, ((off >= t.cp ? sw0 + t.cp : dc) - 1) >> kTileLog);
-                } else {
-                    for (uint32_t kq = kd; kq <= kend && viol != kViolAll; kq++) {
-                        uint32_t s0t, s1t;  // source tiles of the part of the copy that lands in tile kq
-                        if (off >= t.cp) {
-                            const uint32_t p0 = kq == kd ? dc : kq << kTileLog;
-                            const uint32_t p1 = kq == kend ? dc + t.cp : (kq + 1) << kTileLog;
-                            s0t = (p0 - off) >> kTileLog; s1t = (p1 - 1 - off) >> kTileLog;
-                        } else {  // overlapping copy: every byte comes from the window [dc - off, dc)
-                            s0t = sw0 >> kTileLog; s1t = (dc - 1) >> kTileLog;
-                        }
-                        if (s0t < kq) check(kq, s0t, s1t);
-                    }
-                }
-            }
-        }
-        if (olen) {
-            // tiles whose first byte lies in [dpos, dpos + olen)
-            uint32_t k0 = (dpos + kTile - 1) >> kTileLog;
-            uint64_t endp = uint64_t(dpos) + olen;
-            for (uint64_t k = k0; (k << kTileLog) < endp && k < b.n_tiles; k++) {
-                TileStart v; v.cpos = s0 + p; v.d = dpos; v.rep = rep; v.rank = rank;
-                ts[k] = v;
-            }
-        }
-        dpos += olen;
-        rank++;
-        if (t.off) rep = t.off;
-        p += t.hdr + t.lit;   // (< 2^25)
-    }
-    __syncthreads();
-    {
-        const uint32_t ns = seg_tokens < kTokStage ? seg_tokens : kTokStage;
-        for (uint32_t q = uint32_t(tid); q < ns; q += kSegThreads) tpos[seg_rank0 + q] = s0 + stage[q];
-    }
-    // one atomic per wavefront at most, and none once the block's word already has the bits (d was read at entry)
-    viol = (ballot64(viol & 1) ? 1u : 0u) | (ballot64(viol & 2) ? 2u : 0u) | (ballot64(viol & 4) ? 4u : 0u);
-    if ((viol & ~d.viol) && lane_of(tid) == int(ctz64(ballot64(true)))) {
-        const uint32_t old = atomicOr(&dec[bi].viol, viol | kViolNearAll) & kViolAll;   // (this form of the index pass does not measure dependency distances: 1)
-        // the block fits no pattern once all bits are set: whoever sets the last one flags it
-        if ((old | viol) == kViolAll && old != kViolAll && atomicOr(&dec[bi].general, n_general ? 3u : 1u) == 0 && n_general) atomicAdd(n_general, 1u);
-    }
 }
 
 // ---------------- D3 / 3: verdicts ----------------

@@ -2,7 +2,7 @@
 // after mlz_decode.hip.inc).
 //
 // One 192-thread workgroup (3 wavefronts; four tiles per CU, bounded by the 32 KiB tile image in LDS) per 32 KiB output tile, in schedule order
-// (workgroup i takes the i-th tile of the schedule: a tile only ever waits on tiles of workgroups dispatched before its own).  The index pass (D3c) left the block's
+// (workgroup i takes the i-th tile of the schedule: a tile only ever waits on tiles of workgroups dispatched before its own).  The index pass (D3) left the block's
 // TOKEN LIST — the stream position of every token, in stream order — and, for every 64th token, the output position where
 // it starts and the repeat offset in force there.  ROUNDS of 64 consecutive tokens are dealt round-robin to the waves and
 // the tile is built in LDS; lane k handles the round's k-th token:
@@ -25,13 +25,6 @@
 // tile 0.385 (4: 0.403, 2: 0.426, 5 / 6 / 8: 0.46 / 0.50 / 0.49: a wave's own work per round and the ordered chain are of one size).
 // The reference (decode.go:178-622) is one sequential loop over the tokens of a block.
 
-#ifndef MLZ_EXP_NOWAIT
-#define MLZ_EXP_NOWAIT 0
-#endif
-#ifndef MLZ_EXP_NOP2
-#define MLZ_EXP_NOP2 0
-#endif
-
 namespace mlz {
 
 #ifndef MLZ_EXEC_WAVES
@@ -42,17 +35,11 @@ constexpr int kExecThreads = 64 * kExecWaves;
 #ifndef MLZ_EXEC_MINWAVES
 #define MLZ_EXEC_MINWAVES 4   // waves per SIMD the register allocation has to leave room for
 #endif
-#ifndef MLZ_EXEC_LDSPAD
-#define MLZ_EXEC_LDSPAD 0
-#endif
-#ifndef MLZ_EXEC_TOKTAB
-#define MLZ_EXEC_TOKTAB 1
-#endif
 #ifndef MLZ_EXEC_PAIR
 #define MLZ_EXEC_PAIR 2    // rounds per turn of the ordered section (1 = rounds 3-5; see the kernel).  (Measured and not kept in round 6: "early copies",
                            // in-tile copies that read nothing of the previous round going before the turn — profiles/r06_a_exec_early_copies.txt.)
 #endif
-constexpr uint32_t kExecLds = kTile + 64 + (MLZ_EXEC_TOKTAB ? 1024 : 0) + MLZ_EXEC_LDSPAD;   // tile image, shared words, the token table (mlz_toktab.h) (+ padding: occupancy experiments)
+constexpr uint32_t kExecLds = kTile + 64 + 1024;   // tile image, shared words, the token table (mlz_toktab.h)
 
 // non-overlapping copy of len (1..32) bytes inside LDS, any alignment (unaligned DS access is on).
 // ALL lanes read four 8-byte pieces at offsets min(8k, max(len, 8) - 8) first — one LDS round trip whatever the mix of
@@ -106,11 +93,6 @@ __global__ __launch_bounds__(kExecThreads, MLZ_EXEC_MINWAVES) void dec_exec2_ker
                                                                  uint32_t* __restrict__ tile_done, uint32_t* __restrict__ ticket, uint32_t total_tiles,
                                                                  unsigned long long* __restrict__ prof,
                                                                  const uint32_t* __restrict__ gen_ctl /* GenCtl */, uint32_t l0_grid /* workgroups dec_level0_kernel ran with; 0 = not launched */) {
-#ifdef MLZ_EXEC_SKIP
-    // timing experiments: what the exec pass leaves behind for the next call's passes (1 = nothing, 2 = it has read the token list)
-    if (MLZ_EXEC_SKIP == 2) { uint32_t a = 0; for (uint32_t i = blockIdx.x * 4096 + threadIdx.x; i < blockIdx.x * 4096 + 4096; i += kExecThreads) a += tok_pos[i]; if (a == 0x12345678u) dst_base[0] = 1; }
-    return;
-#endif
     extern __shared__ __attribute__((aligned(16))) uint8_t tilebuf[];
     volatile uint32_t* sh = reinterpret_cast<volatile uint32_t*>(tilebuf + kTile);  // [0] ticket, [2] failure site, [3] turn: first chunk not yet complete
     // ([2] and [3] are polled together with one 8-byte read)
@@ -124,7 +106,7 @@ __global__ __launch_bounds__(kExecThreads, MLZ_EXEC_MINWAVES) void dec_exec2_ker
     (void)ticket;
     if (tid == 0) { sh[2] = 0; if (MLZ_PROFILE) { sh[4] = 0; sh[5] = 0; } }
     uint32_t* toktab = reinterpret_cast<uint32_t*>(tilebuf + kTile + 64);
-    if (MLZ_EXEC_TOKTAB) for (int i = tid; i < 256; i += kExecThreads) toktab[i] = g_toktab.e[i];
+    for (int i = tid; i < 256; i += kExecThreads) toktab[i] = g_toktab.e[i];
     __syncthreads();
     uint32_t gt = blockIdx.x;
     if (gt >= total_tiles) return;
@@ -174,7 +156,7 @@ __global__ __launch_bounds__(kExecThreads, MLZ_EXEC_MINWAVES) void dec_exec2_ker
         const uint32_t clen = db.clen;
         {
             const TileStart ts = tile_start[gt];
-            // The block's token list (D3c): stream position of every token in stream order, and per ROUND of 64 consecutive tokens
+            // The block's token list (D3): stream position of every token in stream order, and per ROUND of 64 consecutive tokens
             // (rounds are aligned to the block's token numbering, not to tiles) the output position of its first token and the
             // repeat offset in force there.  My tile's tokens are r_first (the token covering its first byte) .. r_last (the one
             // covering the next tile's first byte); the rounds they lie in are dealt round-robin to the waves, in full: tokens of
@@ -194,9 +176,6 @@ __global__ __launch_bounds__(kExecThreads, MLZ_EXEC_MINWAVES) void dec_exec2_ker
 
             // wait until tile tt of this block is published
             auto wait_tile = [&](uint32_t tt) {
-#ifdef MLZ_EXP_NOTILEWAIT
-                return;   // timing experiment: no tile waits for another (wrong output)
-#endif
                 const uint32_t age = k - 1 - tt;
                 if (age < 64 && ((known_done >> age) & 1)) return;
                 if (age >= 64 && age < 128 && ((known_done2 >> (age - 64)) & 1)) return;
@@ -212,14 +191,7 @@ __global__ __launch_bounds__(kExecThreads, MLZ_EXEC_MINWAVES) void dec_exec2_ker
 
             // Level-conformant block: every tile this one reads from has a lower level and an earlier
             // ticket; wait for all of them at once (lane t polls tile k-1-t) and pay ONE acquire.
-#ifdef MLZ_EXP_NOTILEWAIT
-            all_known = true;
-#endif
-            if (MLZ_DBG_UPFRONT && !db.general && tile_level_p(k, block_pattern(db)) > 0
-#ifdef MLZ_EXP_NOTILEWAIT
-                && false
-#endif
-            ) {
+            if (!db.general && tile_level_p(k, block_pattern(db)) > 0) {
                 const int32_t tt = int32_t(k) - 1 - lane, tt2 = tt - 64;
                 const bool want = tt >= 0 && tile_level_p(uint32_t(tt), block_pattern(db)) < tile_level_p(k, block_pattern(db));
                 const bool want2 = tt2 >= 0 && tile_level_p(uint32_t(tt2), block_pattern(db)) < tile_level_p(k, block_pattern(db));
@@ -287,12 +259,11 @@ __global__ __launch_bounds__(kExecThreads, MLZ_EXEC_MINWAVES) void dec_exec2_ker
                         const uint32_t R = (j << 6) + uint32_t(lane);
                         const bool is_tok = R < ntok && !bad;
                         // ---- parse ----
+                        // (the table form: ~36 instructions and an LDS word against ~65 of decode_tok's select form)
                         Tok t;
-                        if (MLZ_EXEC_TOKTAB) {   // the table form: ~36 instructions and an LDS word against ~65 of the select form
-                            const uint32_t tt = toktab[uint32_t(w_t) & 0xff];
-                            const uint32_t ol = tok_olen(w_t, tt);
-                            t.lit = tok_lit(ol, tt); t.cp = ol - t.lit; t.off = tok_off(uint32_t(w_t), tt); t.hdr = tok_adv(uint32_t(w_t), tt) - t.lit;
-                        } else t = decode_tok(w_t);
+                        const uint32_t tt = toktab[uint32_t(w_t) & 0xff];
+                        const uint32_t ol = tok_olen(w_t, tt);
+                        t.lit = tok_lit(ol, tt); t.cp = ol - t.lit; t.off = tok_off(uint32_t(w_t), tt); t.hdr = tok_adv(uint32_t(w_t), tt) - t.lit;
                         const uint32_t lit = is_tok ? t.lit : 0, len = is_tok ? t.cp : 0;
                         const uint32_t olen = lit + len;
                         const uint32_t incl = wave_incl_scan(olen);
@@ -473,7 +444,7 @@ __global__ __launch_bounds__(kExecThreads, MLZ_EXEC_MINWAVES) void dec_exec2_ker
                         const CopyPlan plan = in.plan;
                         const uint32_t len = in.len, off = in.off, dc = in.dc, mine_v = in.mine_v, iv_lo = in.iv_lo, iv_hi = in.iv_hi;
                         const uint64_t pmask = in.pmask, smask = in.smask;
-                        if (pmask && !MLZ_EXP_NOP2) {
+                        if (pmask) {
                             // Ordered copies of the round, in passes: a copy goes in the first pass in which none of the lanes in its
                             // dependency interval is still to do.  "Simple" copies (plain, <= 32 bytes, source and destination inside
                             // the tile) go lane-parallel; the others (overlapping, long, straddling the tile) one per pass with 64 lanes.
@@ -567,7 +538,7 @@ __global__ __launch_bounds__(kExecThreads, MLZ_EXEC_MINWAVES) void dec_exec2_ker
                 }
                 {
                         // ---- my turn comes when every unit before mine is complete ----
-                        if (!bad && !MLZ_EXP_NOWAIT) {
+                        if (!bad) {
                             uint32_t spins = 0;
                             while (true) {
                                 const uint64_t ft = *reinterpret_cast<volatile uint64_t*>(tilebuf + kTile + 8);  // failure site, turn

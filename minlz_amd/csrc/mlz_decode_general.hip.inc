@@ -7,7 +7,7 @@
 // 1.26 ms of the 2.2 ms a 100 MB stream took).  Now the work is split by what it depends on:
 //
 //   role E ("explain", every tile of every general block, any order, any CU): the tile's tokens are parsed a lane per
-//          token (the token list of D3c) and every output byte of the tile is reduced IN LDS to a 16-bit pointer to its
+//          token (the token list of D3) and every output byte of the tile is reduced IN LDS to a 16-bit pointer to its
 //          TERMINAL byte inside the tile — a literal byte (copied from the stream into the tile image right away) or a
 //          byte that a copy token reads from an EARLIER tile ("external": the token leaves one entry {source position,
 //          pool slot, length <= 8} per 8 bytes).  Terminals live in the tile's POOL: literals at the bottom, slots at
@@ -41,7 +41,7 @@ constexpr uint32_t kGenLds = 4 * kTile + 256 + 12 * kGenMaxTiles;   // E: map (2
 static_assert(kTile <= 32768, "15-bit in-tile pointers / pool offsets");
 
 struct GenCtl {
-    uint32_t n_general;   // blocks flagged general by D3c (first word: mlz_get_counter 2 reads it)
+    uint32_t n_general;   // blocks flagged general by D3 (first word: mlz_get_counter 2 reads it)
     uint32_t e_ticket;    // role E: next ticket
     uint32_t max_tiles;   // D3d: the largest tile count among the general blocks
     uint32_t failed;      // somebody gave up waiting (debug)
@@ -78,11 +78,7 @@ __device__ __forceinline__ void store8_wt(void* p, uint64_t v) { __hip_atomic_st
 __device__ __forceinline__ void store16_wt_a(void* p, uint4 v) {   // 16-byte write-through store, 64-bit lane address
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     const u32x4 x = {v.x, v.y, v.z, v.w};
-#ifdef MLZ_GEN_PLAINST
-    __builtin_memcpy(p, &v, 16);
-#else
     asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(x) : "memory");
-#endif
 }
 
 // values that ARE the same in every lane, moved to scalar registers (the compiler cannot tell for what it loaded through a vector load:
@@ -102,12 +98,6 @@ __device__ __forceinline__ uint32_t opaque(uint32_t x) { asm volatile("" : "+v"(
 #define MLZ_GEN_PROF 0    // debug build: phase clocks (100 MHz) of the first E and the first S workgroup, printed by the kernel
 #endif
 #define MLZ_GP(i) do { if (MLZ_GEN_PROF) { const unsigned long long t_now = __builtin_amdgcn_s_memrealtime(); gp[i] += t_now - gp_prev; gp_prev = t_now; } } while (0)
-#ifndef MLZ_GEN_STOP
-#define MLZ_GEN_STOP 0    // timing experiments: 1 = role E only (wrong output)
-#endif
-#ifndef MLZ_GEN_ABL
-#define MLZ_GEN_ABL 0     // timing ablations of role S (wrong output): 1 no pool writes, 2 no gather reads, 4 no flush stores, 16 no scatter at all, 32 no prefetch loads in the steps
-#endif
 #ifndef MLZ_GEN_EP
 #define MLZ_GEN_EP 3      // role S: external entries per thread that are prefetched (x 1024 threads per tile; the rest take a plain loop)
 #endif
@@ -136,7 +126,6 @@ __device__ __forceinline__ void dec_general_body(const uint8_t* __restrict__ src
                                                                   const uint32_t* __restrict__ order = nullptr, const uint32_t* __restrict__ tile_block = nullptr,
                                                                   uint32_t* __restrict__ tile_done = nullptr) {
     const uint32_t ngen = L0 ? 0u : __hip_atomic_load(&ctl->n_general, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (MLZ_GEN_STOP == 2) return;
     extern __shared__ __attribute__((aligned(16))) uint8_t gl[];
     // shared words: [0] ticket / flag verdict, [1] entries, [2] failure, [3] literal bytes.  (Not `volatile`: the address-space inference skips
     // volatile accesses and they become FLAT instructions; every hand-over of these words goes through a barrier anyway.)
@@ -498,7 +487,6 @@ __device__ __forceinline__ void dec_general_body(const uint8_t* __restrict__ src
                    gp[2] / 100.0 / gp_tiles, gp[3] / 100.0 / gp_tiles, gp[4] / 100.0 / gp_tiles);
         return;
     }
-    if (MLZ_GEN_STOP == 1) return;
 
     // =========================== role S ===========================
     // Software-pipelined over the block's tiles: what step k needs from global memory is requested one or two steps earlier —
@@ -663,14 +651,12 @@ __device__ __forceinline__ void dec_general_body(const uint8_t* __restrict__ src
                 }
                 x.x = uint32_t(acc); x.y = uint32_t(acc >> 32);
             }
-            if (MLZ_GEN_ABL & 1) { if (x.x == 0x12345678u && x.y == len) pool[where] = 1; return; }
             if (!packed) *reinterpret_cast<uint2*>(pool + where) = x;                // an aligned 8-byte slot of its own
             else lds_store_exact(pool + where, uint4{x.x, x.y, 0u, 0u}, len);       // byte-packed pool: nothing beyond the entry's bytes
         };
         bool dead = false;
         uint32_t xd_safe = 0;   // a team: sources ending at or below this position were requested a step ahead
         auto step = [&](uint32_t k, ExtEnt (&ENc)[EP], ExtEnt (&ENn)[EP]) {
-            constexpr bool kLoads = !(MLZ_GEN_ABL & 32);
             if (k + 2 * team + 1 > known && known < ntile) {
                 const uint32_t v = ensure(k + 2 * team + 1 < ntile ? k + 2 * team + 1 : ntile);
                 if (v != 1) { fail_block(v); dead = true; return; }
@@ -705,7 +691,7 @@ __device__ __forceinline__ void dec_general_body(const uint8_t* __restrict__ src
                 MLZ_GP(5);
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // the other members' stores (other CUs, maybe other XCDs)
                 // every source is final now; those that end at or below tile k - 2 team's end were requested a step ago (xd_safe), the rest here
-                if (kLoads) load_XD_range(k, ENc, xd_safe, 0xffffffffu);
+                load_XD_range(k, ENc, xd_safe, 0xffffffffu);
             } else {
                 // This CU's L1 may hold lines of dst from before the workgroup's own stores (a 128-byte line can span two tiles): dropped once
                 // per step, before the step's loads of settled bytes (XD) — every store that matters to them has been acknowledged by then
@@ -715,12 +701,12 @@ __device__ __forceinline__ void dec_general_body(const uint8_t* __restrict__ src
             // ---- the pool: literal bytes (from role E), then the entries' bytes; slots and literals are disjoint, a packed pool needs the barrier between ----
             if (my < uni(s_ltop[k])) { reinterpret_cast<uint4*>(pool + my)[0] = B[0]; reinterpret_cast<uint4*>(pool + my)[1] = B[1]; }
             if (packed) __syncthreads();
-            if (kLoads) load_B(k1);
+            load_B(k1);
             if (!packed) {
 #pragma unroll
                 for (uint32_t i = 0; i < EP; i++) {
                     const uint32_t e = uint32_t(tid) + i * kGenThreads;
-                    if (e < ne && !(MLZ_GEN_ABL & 16)) place(rlo, false, ENc[i], XD[i], true);
+                    if (e < ne) place(rlo, false, ENc[i], XD[i], true);
                 }
             }
             if (packed || ne > EP * kGenThreads) {   // a packed tile (rare: exact stores), or the entries beyond the prefetched ones: a plain loop
@@ -728,14 +714,12 @@ __device__ __forceinline__ void dec_general_body(const uint8_t* __restrict__ src
 #pragma unroll 1
                 for (uint32_t e = uint32_t(tid) + (packed ? 0u : EP * kGenThreads); e < ne; e += kGenThreads) place(rlo, packed, ext[e], uint2{0u, 0u}, false);
             }
-            if (kLoads) {
-                if (!tm) load_XD(k1, ENn);
-                else {   // my next tile's sources in what is settled by now: every tile up to k - team (their bytes were acquired at this step's top)
-                    xd_safe = k >= team ? (k - team + 1) << kTileLog : 0u;
-                    load_XD_range(k1, ENn, 0u, xd_safe);
-                }
-                load_EN(k2, ENc);
+            if (!tm) load_XD(k1, ENn);
+            else {   // my next tile's sources in what is settled by now: every tile up to k - team (their bytes were acquired at this step's top)
+                xd_safe = k >= team ? (k - team + 1) << kTileLog : 0u;
+                load_XD_range(k1, ENn, 0u, xd_safe);
             }
+            load_EN(k2, ENc);
             __syncthreads();            // every terminal of the tile has its byte
             MLZ_GP(2);
             gp_tiles++; gp_ext += ne;
@@ -747,7 +731,7 @@ __device__ __forceinline__ void dec_general_body(const uint8_t* __restrict__ src
                 // their own first (a second persistent set of 16 registers made the allocator spill 80)
 #pragma unroll
                 for (int q = 0; q < 16; q++) asm volatile("" : "+v"(m16[q]));
-                if (kLoads) load_M(k1);
+                load_M(k1);
                 uint32_t ow[8];
                 // (ds_read_u8_d16 / _d16_hi pairs would pack two bytes per register without a shift, but with SRAM ECC on — MI300 / MI355 — a d16
                 //  load clears the half it does not write: measured wrong, not kept)
@@ -757,8 +741,7 @@ __device__ __forceinline__ void dec_general_body(const uint8_t* __restrict__ src
 #pragma unroll
                     for (int q = 4 * hf; q < 4 * hf + 4; q++) {
                         const uint32_t a = m16[2 * q], c = m16[2 * q + 1];
-                        if (MLZ_GEN_ABL & 2) ow[q] = a ^ (c << 3);
-                        else ow[q] = uint32_t(pool[a & 0xffffu]) | (uint32_t(pool[a >> 16]) << 8) | (uint32_t(pool[c & 0xffffu]) << 16) | (uint32_t(pool[c >> 16]) << 24);
+                        ow[q] = uint32_t(pool[a & 0xffffu]) | (uint32_t(pool[a >> 16]) << 8) | (uint32_t(pool[c & 0xffffu]) << 16) | (uint32_t(pool[c >> 16]) << 24);
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -766,8 +749,7 @@ __device__ __forceinline__ void dec_general_body(const uint8_t* __restrict__ src
                 reinterpret_cast<uint4*>(cur + my)[0] = o0;
                 reinterpret_cast<uint4*>(cur + my)[1] = o1;
                 const uint32_t* cur32 = reinterpret_cast<const uint32_t*>(cur);
-                if ((MLZ_GEN_ABL & 4) && o0.x != 0x9abcdef1u) {
-                } else if (my + 32 <= n) {
+                if (my + 32 <= n) {
                     const uint32_t at = opaque(tstart + my);
                     if (tm && dst_aligned) { store16_wt_a(dst + at, o0); store16_wt_a(dst + (at + 16), o1); }   // (write-through: other members read these bytes)
                     else { __builtin_memcpy(dst + at, &o0, 16); __builtin_memcpy(dst + (at + 16), &o1, 16); }

@@ -1,6 +1,5 @@
 // mlz_decode_index.hip.inc — D3, the index pass of the parallel decoder: dec_index1_kernel (per segment) and dec_index2_kernel (per token)
-// (round 4; dec_viol_kernel, in mlz_decode.hip.inc, gathers their verdict bytes per block; included by mlz_hip.hip after mlz_decode.hip.inc, whose older three-kernel form —
-// dec_index_a / _b / _c — stays selectable for cross-checks: MLZ_OPT_INDEX_PASSES).
+// (round 4; dec_viol_kernel, in mlz_decode.hip.inc, gathers their verdict bytes per block; included by mlz_hip.hip after mlz_decode.hip.inc).
 //
 // Input: the true entry offset of every 8 KiB segment of the token stream (D2) and D1's region exits.  Output: what the exec pass
 // (mlz_decode_exec.hip.inc) and the general-block pass work from — the block's TOKEN LIST (stream position of every token), per 64
@@ -32,6 +31,7 @@ namespace mlz {
 
 constexpr uint32_t kIdxThreads = kSegThreads;                 // 128: a lane per 64-byte region in the walk
 constexpr uint32_t kIdxStage = kSeg / 2;                      // 4096 token positions (16 bits each) per pass through the buffer
+constexpr uint32_t kRex8Bytes = kSegThreads * 68;             // region exits: one byte per offset, rows of 64 + 4
 constexpr uint32_t kIdxSegBytes = kSeg + 32;                  // the segment, 16 bytes behind it, padding
 constexpr uint32_t kIdxBuf = kRex8Bytes > kIdxSegBytes ? kRex8Bytes : kIdxSegBytes;   // ONE buffer: the region exits, then the segment's bytes, then the token list
 constexpr uint32_t kIdxLds = kIdxBuf + kSegThreads * 2 + 1024 + 256 + 512;   // ... + region entries, token table, scratch, the chain's group walks (phase 1)
@@ -109,9 +109,6 @@ __global__ __launch_bounds__(kIdxThreads) void dec_index1_kernel(const uint8_t* 
     if (tid == 0) atomicAdd(&g_idxprof[15], 1ull);
 #endif
 
-#if defined(MLZ_IDX_ABL) && MLZ_IDX_ABL == 5
-    if (e != 0x12345u) return;
-#endif
     uint64_t mask = 0;      // token starts in my region
     uint32_t rank0 = 0;     // segment-relative rank of the first of them
     uint32_t ntok_seg = 0;
@@ -142,11 +139,8 @@ __global__ __launch_bounds__(kIdxThreads) void dec_index1_kernel(const uint8_t* 
         }
         __syncthreads();
         IDXP(0);
-#if defined(MLZ_IDX_ABL) && MLZ_IDX_ABL == 3
-        return;
-#endif
         auto lds4 = [&](uint32_t p) -> uint32_t { const uint32_t i = p >> 2; return __builtin_amdgcn_alignbyte(segw[i + 1], segw[i], p); };
-        // One step of the region chain (the same verdicts as D1 / dec_region_walk): from path position p to the first one beyond p's region.
+        // One step of the region chain (the same verdicts as D1): from path position p to the first one beyond p's region.
         auto hop = [&](uint32_t p) -> uint32_t {
             const uint32_t rend = ((p >> 6) + 1) * 64;
             const uint32_t dlt = rex8[(p >> 6) * 68 + (p & 63)];
@@ -162,11 +156,7 @@ __global__ __launch_bounds__(kIdxThreads) void dec_index1_kernel(const uint8_t* 
         // entries are taken from walk k - 1 (group 0: walk 0); if some walk did not meet its predecessor (a literal longer than a
         // group, the end of the stream, hostile input), one thread chains the segment as before.
         const uint32_t e_rel = e - s0;
-#if defined(MLZ_IDX_ABL) && MLZ_IDX_ABL == 6
-        if (wv == 7) {
-#else
         if (wv == 0) {
-#endif
             bool ok = true;
             if (lane < int(kIdxGroups) - 1) {   // (walk g serves group g + 1: the last group needs none of its own)
                 const uint32_t g = uint32_t(lane), gstart = 64 * kIdxGrp * g, gend = gstart + 2 * 64 * kIdxGrp;
@@ -217,9 +207,6 @@ __global__ __launch_bounds__(kIdxThreads) void dec_index1_kernel(const uint8_t* 
             __syncthreads();
         }
         IDXP(1);
-#if defined(MLZ_IDX_ABL) && (MLZ_IDX_ABL == 2 || MLZ_IDX_ABL == 6)
-        return;
-#endif
         // ---- the walk: token starts of my region, their output bytes, the last token with an offset of its own ----
         uint32_t rout = 0, plast = 0xffffffffu;   // (a region has at most 64 tokens of less than 2^25 bytes each)
         {
@@ -259,9 +246,6 @@ __global__ __launch_bounds__(kIdxThreads) void dec_index1_kernel(const uint8_t* 
         ntok_seg = n_w0 + qagg[2].ntok + qagg[3].ntok;
         IDXP(2);
     }
-#if defined(MLZ_IDX_ABL) && MLZ_IDX_ABL == 4
-    return;
-#endif
     // ---- the token list of the segment (16-bit positions, stream order) and its aggregates ----
     uint16_t* tl = tok16 + (size_t(seg) << kSegLog);
     const uint32_t nchunk = (ntok_seg + kIdxStage - 1) / kIdxStage;   // 1 unless tokens average less than two bytes
@@ -363,7 +347,6 @@ __global__ __launch_bounds__(kIdx2Threads) void dec_index2_kernel(const uint8_t*
         const uint32_t npred = seg - b.first_seg;
         uint32_t so = 0, sn = 0, near_key = 0, near_last = 0;   // (at most 16 words of at most 2^24 per thread)
         bool missing = !(my_word >> 63) || !(w_before >> 63) || !(w_upto >> 63);
-#ifndef MLZ_IDX2_NOLB
         for (uint32_t j0 = 0; j0 < npred; j0 += 4 * kIdx2Threads) {
             unsigned long long w[4];
 #pragma unroll
@@ -380,7 +363,6 @@ __global__ __launch_bounds__(kIdx2Threads) void dec_index2_kernel(const uint8_t*
                 if (la && !near_key) { near_key = 0xffffffffu - j; near_last = la; }   // (j ascends: the first one found is this thread's nearest)
             }
         }
-#endif
         const uint32_t s_lo = rdlane(wave_incl_scan_u32(so & 0xffffffu), 63), s_hi = rdlane(wave_incl_scan_u32(so >> 24), 63);
         const uint32_t s_n = rdlane(wave_incl_scan_u32(sn), 63);
         const uint32_t kmax = rdlane(wave_incl_max_u32(near_key), 63);
@@ -407,16 +389,13 @@ __global__ __launch_bounds__(kIdx2Threads) void dec_index2_kernel(const uint8_t*
             return;
         }
     }
-    if (last_seg && tid == 0 && (blockIdx.x & 1) == 0) {   // the block's totals (what dec_index_b_kernel did)
+    if (last_seg && tid == 0 && (blockIdx.x & 1) == 0) {   // the block's totals
         const IdxAgg incl = idx_join(base, mine);
         dec[bi].total_out = incl.out;
         dec[bi].ntok = incl.ntok;
         if (incl.out != d.dlen) dec[bi].status = 1 | (2 << 8);   // d != len(dst), decode.go:615
     }
     if (ntok_seg == 0) return;
-#ifdef MLZ_IDX2_NOLOOP
-    return;
-#endif
     // ---- the lists ----
     const IdxAgg pre = wv ? idx_join(base, before) : base;
     if (lo >= hi) return;

@@ -49,39 +49,13 @@ __device__ __forceinline__ uint64_t ld64u(const uint8_t* p) {
 constexpr int kFarTagBits = 9;
 constexpr uint32_t kFarTagMask = (1u << kFarTagBits) - 1;
 struct FarHash { uint32_t idx, tag; };
-#ifndef MLZ_FAR_HASH32
-#define MLZ_FAR_HASH32 4
-#endif
 // (tagmask: which of the 9 tag bits a table uses — all of them, or far_tag_mask(FB) below)
 __device__ __forceinline__ FarHash far_hash(uint64_t v, int bits, uint32_t tagmask = kFarTagMask) {
-#if MLZ_FAR_HASH32 == 4
     // Round 3: two 32-bit multiplies and an add.  On gfx950 v_mul_lo_u32 issues in the same 4 cycles as v_mul_u32_u24 / v_mad_u32_u24
-    // (profiles/r03_valu_rate.txt: the "quarter rate" of older parts does not apply), so the four 24-bit multiply-adds below bought
+    // (profiles/r03_valu_rate.txt: the "quarter rate" of older parts does not apply), so four 24-bit multiply-adds bought
     // nothing over this; the model's ratio is a hair better (enwik-like 0.4687 -> 0.4685).
     const uint32_t a = (uint32_t(v) * 0x9E3779B1u + uint32_t(v >> 32)) * 0x85EBCA77u;
     return {a >> (32 - bits), (a >> (32 - bits - kFarTagBits)) & tagmask};
-#elif MLZ_FAR_HASH32 == 3
-    // four 24-bit multiply-adds (v_mad_u32_u24 is full rate; a 32-bit integer multiply is quarter rate and the
-    // kernels are bound by instruction issue): every input bit reaches the index bits through two of the products
-    const uint32_t lo = uint32_t(v), hi = uint32_t(v >> 32);
-    uint32_t a = __umul24(lo, 0x9E3779u);
-    a += __umul24(lo >> 8, 0x85EBCBu);
-    a += __umul24(hi, 0xC2B2AFu);
-    a += __umul24(hi >> 8, 0x27D4EBu);
-    return {a >> (32 - bits), (a >> (32 - bits - kFarTagBits)) & kFarTagMask};
-#elif MLZ_FAR_HASH32
-    // two 32-bit multiplies (integer multiplies are quarter rate on CDNA; the 64-bit product costs four)
-    const uint32_t h = (uint32_t(v) * 0x9E3779B1u) ^ (uint32_t(v >> 32) * 0x85EBCA77u);
-#if MLZ_FAR_HASH32 == 2
-    const uint32_t g = h;
-#else
-    const uint32_t g = h * 0xC2B2AE3Du;  // spread: index from the top bits, tag from the next ones
-#endif
-    return {g >> (32 - bits), (g >> (32 - bits - kFarTagBits)) & kFarTagMask};
-#else
-    const uint64_t prod = v * 0xcf1bbcdcb7a56463ull;
-    return {uint32_t(prod >> (64 - bits)), uint32_t(prod >> (64 - bits - kFarTagBits)) & kFarTagMask};
-#endif
 }
 __device__ __forceinline__ uint32_t ctz64(uint64_t v) { return __builtin_ctzll(v); }
 __device__ __forceinline__ uint64_t ballot64(bool p) { return __ballot(p); }
@@ -99,7 +73,7 @@ __device__ __forceinline__ uint32_t rdfirst(uint32_t v) { return __builtin_amdgc
 // dense is 7 % smaller than fast on text (CPU model: 0.3379 -> 0.3097).  three gives up 1.5 % (enwik-like) / 2.7 % (text) / 0.8 % (JSON)
 // of dense's size for a decode round less and a far-table level set less: exec pass 0.525 -> 0.473 ms, far build 0.082 -> 0.052,
 // match kernel 0.704 -> 0.688 ms per 100 MB (encode + decode 57.2 -> 61.1 GB/s); the other three-level patterns tried are within
-// 0.5 % of it either way (DESIGN.md section 3).  The decoder recognises all three (mlz_decode.hip.inc, D3c) and falls back to the
+// 0.5 % of it either way (DESIGN.md section 3).  The decoder recognises all three (mlz_decode.hip.inc, D3) and falls back to the
 // position-order path for anything else.
 constexpr uint32_t kPatternFast = 0xE4E4E4E4u;
 #ifndef MLZ_PATTERN_DENSE

@@ -35,9 +35,6 @@ constexpr uint32_t kPieceLog = kTileLog - kSubLog;
 constexpr uint32_t kPiece = 1u << kPieceLog;             // 8 KiB
 constexpr uint32_t kRecPerPiece = kPiece / 4;            // a match is at least 4 bytes
 constexpr uint32_t kM2Pad = 256;                         // zero bytes behind the tile (windows and 36-byte reads run past it)
-#ifndef MLZ_M2_LDSPAD
-#define MLZ_M2_LDSPAD 0
-#endif
 // Near tables: piece k of a tile indexes (k + 1) x 8 KiB of positions (the earlier pieces are seeded into it) and gets
 // (k + 1) x kM2Unit entries — the same positions per entry for every piece.  Two workgroups of 32 KiB + 4 tables fit a
 // CU's 160 KiB either way; graded tables of 2048 / 4096 / 6144 / 8192 entries (40 KiB) use what four 4096-entry tables
@@ -45,7 +42,7 @@ constexpr uint32_t kM2Pad = 256;                         // zero bytes behind th
 template <int HB> struct M2Cfg {                                                      // HB = hash bits of the near tables
     static constexpr uint32_t kUnit = (1u << HB) / kSub;                               // entries per 8 KiB of indexed positions
     static constexpr uint32_t kEntries = kUnit * (kSub * (kSub + 1) / 2);              // all four tables
-    static constexpr uint32_t kLds = kTile + kM2Pad + 2 * kEntries + MLZ_M2_LDSPAD;    // (pad: occupancy experiments)
+    static constexpr uint32_t kLds = kTile + kM2Pad + 2 * kEntries;
 };
 // Near-table sizes.  13 hash bits: 40 KiB of tables, 72 KiB per workgroup, two workgroups per CU.  12 bits: 20 KiB of tables,
 // 52 KiB per workgroup, THREE per CU — the kernel is bound by VALU issue with two waves per SIMD covering each other's waits
@@ -71,27 +68,6 @@ constexpr uint32_t kSkipShift = 10;
 constexpr uint32_t kSeedStride = MLZ_M2_SEEDSTRIDE;    // which positions of the earlier pieces a piece's near table is seeded with                      // growing skip over incompressible data
 #ifndef MLZ_M2_NW
 #define MLZ_M2_NW 4
-#endif
-#ifndef MLZ_M2_FAR_GATE
-#define MLZ_M2_FAR_GATE 0
-#endif
-#ifndef MLZ_M2_LAZY_COST
-#define MLZ_M2_LAZY_COST 1
-#endif
-// ablation switches (timing experiments: remove one phase, re-measure; the output is then wrong or worse)
-#ifndef MLZ_ABL2
-#define MLZ_ABL2 0
-#endif
-#define MLZ_ABL2_NOSTORE 1
-#define MLZ_ABL2_NOWALK 2
-#define MLZ_ABL2_NOLAZY 4
-#define MLZ_ABL2_NOEXT 8
-#define MLZ_ABL2_NOFARCMP 16
-#define MLZ_ABL2_NOVERIFY 32
-// LDS-access ablations (round 6, profiles/r06_b_m2_lds_ablation.txt: which accesses make the bank conflicts; the output is wrong):
-// 1 = near-table look-up and insert at lane-linear addresses, 2 = near-candidate bytes read at lane-linear addresses (p - 64), 4 = seeding stores linear
-#ifndef MLZ_ABL3
-#define MLZ_ABL3 0
 #endif
 
 __device__ __forceinline__ uint32_t albyte(uint32_t hi, uint32_t lo, uint32_t sh) { return __builtin_amdgcn_alignbyte(hi, lo, sh); }
@@ -133,9 +109,6 @@ __device__ unsigned long long g_m2prof[16];   // debug build only: per-phase cyc
 
 constexpr uint32_t kSerRing = 4096;
 constexpr uint32_t kSerLds = kSub * kSerRing;
-#ifndef MLZ_M2_FUSE_SER
-#define MLZ_M2_FUSE_SER 1   // the wave that matched a piece serializes it as well (serialize_piece below); 0 = compiled out
-#endif
 template <uint32_t RING, bool LDSSRC>
 __device__ __forceinline__ uint32_t serialize_piece(const uint8_t* __restrict__ sblk, const uint8_t* __restrict__ s, const uint32_t* ldata, const BlockInfo& b,
                                                     const uint32_t base, const uint32_t ps, const uint32_t tl, const uint32_t cnt, const uint2* __restrict__ rp,
@@ -198,14 +171,14 @@ __global__ __launch_bounds__(256, FP ? 1 : MLZ_M2_MINW) void match_tiles_kernel(
             const uint32_t q = (nv << 4) + tid;
             reinterpret_cast<uint8_t*>(ldata)[q] = q < tl ? s[q] : uint8_t(0);
         }
-        constexpr uint32_t kAllV = (kM2Lds - MLZ_M2_LDSPAD) >> 4;  // data + pad + tables, in 16-byte units
+        constexpr uint32_t kAllV = kM2Lds >> 4;  // data + pad + tables, in 16-byte units
         for (uint32_t q = nv + 1 + tid; q < kAllV; q += 256) dv[q] = uint4{0, 0, 0, 0};
     }
     __syncthreads();
     const uint32_t ps = wv << kPieceLog;
     const size_t pid = size_t(gt) * kSub + wv;
     if (ps >= tl) {
-        if (lane == 0) { piece_cnt[pid] = 0; if (MLZ_M2_FUSE_SER && scratch) piece_size[pid] = 0; }
+        if (lane == 0) { piece_cnt[pid] = 0; if (scratch) piece_size[pid] = 0; }
         return;
     }
     const uint32_t pe = ps + kPiece < tl ? ps + kPiece : tl;
@@ -227,8 +200,6 @@ __global__ __launch_bounds__(256, FP ? 1 : MLZ_M2_MINW) void match_tiles_kernel(
             for (int u = 0; u < 4; u++) {
                 const uint32_t p = q0 + kSS * (64 * u + lane);
                 const uint32_t h32 = v4[u] * 2654435761u;
-                if (MLZ_ABL3 & 4) table[((64 * u + lane) & 1023u) + (h32 == 0x12345u ? 1 : 0)] = uint16_t(p | near_tag<kM2HashBits>(h32));
-                else
                 *near_slot(table, h32, tsize) = uint16_t(p | near_tag<kM2HashBits>(h32));
             }
         }
@@ -306,7 +277,6 @@ __global__ __launch_bounds__(256, FP ? 1 : MLZ_M2_MINW) void match_tiles_kernel(
                 const uint32_t h32 = m[w][0] * 2654435761u;
                 const uint32_t ntag = near_tag<kM2HashBits>(h32);
                 uint16_t* slot = near_slot(table, h32, tsize);
-                if (MLZ_ABL3 & 1) slot = table + ((64 * w + lane) & (tsize - 1) & 1023u) + (h32 == 0x12345u ? 1 : 0);
                 e[w] = *slot ^ ntag;                         // bit 15 clear <=> the stored hash bit agrees
                 *slot = uint16_t(p | ntag);
             }
@@ -318,22 +288,21 @@ __global__ __launch_bounds__(256, FP ? 1 : MLZ_M2_MINW) void match_tiles_kernel(
                 const uint32_t p = cur + 64 * w + lane;
                 // positions are below 2^15 and a disagreeing hash bit sets bit 15 of e: "an earlier position whose stored bit agrees" is ONE compare
                 const bool near_ok = e[w] < p;
-                const uint32_t cand = (MLZ_ABL3 & 2) ? ((p - 64) & 0x7fffu) | (e[w] == 0x12345u ? 1u : 0u) : e[w] & 0x7fffu;
+                const uint32_t cand = e[w] & 0x7fffu;
                 const uint32_t NA = cand >> 2;
                 const uint32_t c0 = ldata[NA], c1 = ldata[NA + 1];
                 c2[w] = ldata[NA + 2];
                 const uint32_t x[2] = {m[w][0] ^ albyte(c1, c0, cand), m[w][1] ^ albyte(c2[w], c1, cand)};
                 const uint32_t l8 = min(first_diff_bit(x) >> 3, 8u);
-                const uint32_t l_near = (MLZ_ABL2 & MLZ_ABL2_NOVERIFY) ? (near_ok ? (cand & 7) + 1 : 0) : l8;
-                best[w] = near_ok && l_near >= 4 ? l_near : 0;
+                best[w] = near_ok && l8 >= 4 ? l8 : 0;
                 boff[w] = p - cand;
             }
             M2P(2);  // verify
             // ---- phase D: straight-line extension to 32 bytes (LDS, short latency: plain branches) ----
 #pragma unroll
             for (int w = 0; w < NW; w++) {
-                if (!(MLZ_ABL2 & MLZ_ABL2_NOEXT) && best[w] == 8 && lim[w] > 8) {
-                    const uint32_t cand = (MLZ_ABL3 & 2) ? ((cur + 64 * w + lane - 64) & 0x7fffu) : e[w] & 0x7fffu;
+                if (best[w] == 8 && lim[w] > 8) {
+                    const uint32_t cand = e[w] & 0x7fffu;
                     const uint32_t NA = cand >> 2;
                     uint32_t c[7];
                     c[0] = c2[w];
@@ -356,8 +325,7 @@ __global__ __launch_bounds__(256, FP ? 1 : MLZ_M2_MINW) void match_tiles_kernel(
                         const uint32_t x[8] = {m[w][0] ^ cx.x, m[w][1] ^ cx.y, m[w][2] ^ cx.z, m[w][3] ^ cx.w, m[w][4] ^ cy.x, m[w][5] ^ cy.y, m[w][6] ^ cy.z, m[w][7] ^ cy.w};
                         const uint32_t cleft = kTile - (q & (kTile - 1));     // the source must not leave its tile
                         const uint32_t lf = min(first_diff_bit(x) >> 3, min(cleft, lim[w]));
-                        const bool take = q != kNoFar && !(MLZ_M2_FAR_GATE && best[w] >= 8) && lf >= kFarMin && lf > best[w] + 2;
-                        if (!(MLZ_ABL2 & MLZ_ABL2_NOFARCMP) && take) { best[w] = lf; boff[w] = pa - q; }
+                        if (q != kNoFar && lf >= kFarMin && lf > best[w] + 2) { best[w] = lf; boff[w] = pa - q; }
                     };
                     far_cmp(fq[w], fx[w], fy[w]);
                     if constexpr (FP) far_cmp(gq[w], gx[w], gy[w]);   // the previous epoch's candidate after this epoch's
@@ -440,12 +408,12 @@ __global__ __launch_bounds__(256, FP ? 1 : MLZ_M2_MINW) void match_tiles_kernel(
             // evaluated right to left with one lane shift per step (the shifts fold into the max / compare as DPP operands);
             // the look-ahead does not cross into the next window (0.01 % of output on the CPU model).
             const uint32_t cost = boff[w] > kMaxCopy2Offset ? 2u : boff[w] > kMaxCopy1Offset ? 1u : 0u;   // token size - 2
-            const uint32_t g = MLZ_M2_LAZY_COST && best[w] >= 4 ? best[w] - cost : best[w] + 2;
+            const uint32_t g = best[w] >= 4 ? best[w] - cost : best[w] + 2;
             const uint32_t g1 = g - 1, g2 = g - 2;
             const uint32_t u = max(g1, uint32_t(__builtin_amdgcn_update_dpp(0, int(g2), 0x130 /* wave_shl:1 */, 0xf, 0xf, true)));
             const uint32_t v2 = max(g, uint32_t(__builtin_amdgcn_update_dpp(0, int(u), 0x130, 0xf, 0xf, true)));
             const uint32_t mx = uint32_t(__builtin_amdgcn_update_dpp(0, int(v2), 0x130, 0xf, 0xf, true));
-            mask[w] = ballot64(best[w] >= 4 && ((MLZ_ABL2 & MLZ_ABL2_NOLAZY) ? true : mx <= g));
+            mask[w] = ballot64(best[w] >= 4 && mx <= g);
         }
         M2P(5);  // lazy
         uint64_t startmask[NW];
@@ -455,7 +423,6 @@ __global__ __launch_bounds__(256, FP ? 1 : MLZ_M2_MINW) void match_tiles_kernel(
             lenx[w] = best[w];
             const uint32_t w0 = cur + 64 * w;
             uint64_t mm = mask[w];
-            if (MLZ_ABL2 & MLZ_ABL2_NOWALK) mm &= 1;
             if (pos > w0) mm = pos - w0 >= 64 ? 0 : mm & (~0ull << (pos - w0));
             const uint32_t nxt = uint32_t(lane) + best[w];  // window-relative end of my candidate
             uint64_t sm = 0;
@@ -487,9 +454,6 @@ __global__ __launch_bounds__(256, FP ? 1 : MLZ_M2_MINW) void match_tiles_kernel(
                         const uint32_t srcleft = kTile - (q_abs & (kTile - 1));
                         if (mp + srcleft < end) end = mp + srcleft;
                     }
-#ifdef MLZ_M2_NOCOOPFAR
-                    if (is_far) end = mp + L;  // timing experiment: far matches are not extended past the lane cap
-#endif
                     if (is_far) {
 #ifndef MLZ_M2_COOPK
 #define MLZ_M2_COOPK 4
@@ -557,7 +521,7 @@ __global__ __launch_bounds__(256, FP ? 1 : MLZ_M2_MINW) void match_tiles_kernel(
                 any = true;
                 const bool sel = (sm >> lane) & 1;
                 const uint32_t idx = cnt + __builtin_amdgcn_mbcnt_hi(uint32_t(sm >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(sm), 0));
-                if (sel && !((MLZ_ABL2 & MLZ_ABL2_NOSTORE) && cnt != 0xfffffffu)) rp[idx] = uint2{(cur + 64 * w + lane) | (lenx[w] << 16), boff[w]};
+                if (sel) rp[idx] = uint2{(cur + 64 * w + lane) | (lenx[w] << 16), boff[w]};
                 cnt += uint32_t(__builtin_popcountll(sm));
             }
         }
@@ -575,7 +539,6 @@ __global__ __launch_bounds__(256, FP ? 1 : MLZ_M2_MINW) void match_tiles_kernel(
 #ifdef MLZ_M2_PROF
     if (lane == 0) for (int i = 0; i < 10; i++) atomicAdd(&g_m2prof[i], m2pc[i]);
 #endif
-#if MLZ_M2_FUSE_SER
     if (scratch) {
         // The piece's tokens, by the wave that found them (serialize_piece): records read back through the L2 (my stores have completed, and what
         // this CU's L1 may hold of those lines is dropped), literals and the bytes in front of the matches from the tile's LDS copy — the other
@@ -588,23 +551,19 @@ __global__ __launch_bounds__(256, FP ? 1 : MLZ_M2_MINW) void match_tiles_kernel(
 #ifndef MLZ_M2_SER_RING
 #define MLZ_M2_SER_RING 4096   // (timing experiments: 2048 = one instantiation for all four waves)
 #endif
-#ifndef MLZ_M2_SER_LDS
-#define MLZ_M2_SER_LDS 1       // (timing experiments: 0 = literals and the bytes in front of the matches from memory, as the separate kernel reads them)
-#endif
         constexpr uint32_t kRingN = MLZ_M2_SER_RING;
         constexpr uint32_t kRing0 = 2 * kM2Unit >= kRingN ? kRingN : 2048u;
         static_assert(2 * kM2Unit >= 2048 && 4 * kM2Unit >= kRingN, "a wave's near table holds its serializer ring");
         uint32_t sz;
-        if (kRing0 != kRingN && wv == 0) sz = serialize_piece<kRing0, MLZ_M2_SER_LDS != 0>(sblk, s, ldata, b, base, ps, tl, cnt, rp, ring, scratch + pid * kPieceScratch, lane);
-        else sz = serialize_piece<kRingN, MLZ_M2_SER_LDS != 0>(sblk, s, ldata, b, base, ps, tl, cnt, rp, ring, scratch + pid * kPieceScratch, lane);
+        if (kRing0 != kRingN && wv == 0) sz = serialize_piece<kRing0, true>(sblk, s, ldata, b, base, ps, tl, cnt, rp, ring, scratch + pid * kPieceScratch, lane);
+        else sz = serialize_piece<kRingN, true>(sblk, s, ldata, b, base, ps, tl, cnt, rp, ring, scratch + pid * kPieceScratch, lane);
         if (lane == 0) piece_size[pid] = sz;
     }
-#endif
 }
 
 // ---- serialize: token records -> token bytes of the piece (in the piece's scratch), piece_size ----
 // serialize_piece: ONE wavefront turns the records of ONE piece into its token bytes.  Called at the end of match_tiles_kernel by the wave
-// that made the records (round 6, MLZ_M2_FUSE_SER: the tile's bytes are still in LDS — literals and the bytes in front of a match come from
+// that made the records (round 6, option 21: the tile's bytes are still in LDS — literals and the bytes in front of a match come from
 // there —, the records and the far sources' lines are still in this XCD's L2, the ring lives in the wave's own near table, which nobody needs
 // any more; the kernel is bound by VALU issue with a quarter of its issue slots idle, and this pass is mostly waiting for loads), or by
 // serialize_pieces_kernel (rounds 2-5: a kernel of its own that read source, records and a line per far token again: 518 MB of traffic).

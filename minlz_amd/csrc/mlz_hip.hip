@@ -89,8 +89,6 @@ struct mlz_ctx {
     std::vector<SingleReq*> q_pending;
     bool q_leader = false;
     uint64_t q_batches = 0, q_requests = 0;  // mlz_get_counter
-    int index_passes = 0;                    // MLZ_OPT_INDEX_PASSES
-    int debug_stop = 0;                      // debug option 16: decode stops after the index pass (timing experiments with broken kernel variants)
     void* last_gen = nullptr;                // GenCtl of the last decode call's last group (device memory)
     uint64_t acc_call = 0;                   // the decode call (dec_call) whose first schedule kernel has reset d_gen_acc
     uint64_t dec_call = 0;                   // call_seq at the start of the last decode API call: its host groups, stream groups and internal groups share it
@@ -408,7 +406,7 @@ int encode_device_group(mlz_ctx* c, hipStream_t st, int level, const uint8_t* d_
             HIPCHK(c, c->d_recs.ensure(units * kRecPerPiece * sizeof(uint2)));
             HIPCHK(c, c->d_piece_cnt.ensure(units * sizeof(uint32_t)));
             // the match kernel's waves serialize their pieces themselves (option 21, default on); else serialize_pieces_kernel below
-            uint8_t* fuse_scratch = MLZ_M2_FUSE_SER && c->fuse_ser ? c->d_scratch.as<uint8_t>() : nullptr;
+            uint8_t* fuse_scratch = c->fuse_ser ? c->d_scratch.as<uint8_t>() : nullptr;
             {
                 Timer t(c, T_ENC_TILES, st);
                 const uint32_t grid = ((tiles + 7) / 8) * 8;  // whole rounds of the eight XCDs (see the kernel's workgroup -> tile map)
@@ -487,15 +485,8 @@ int decode_parallel(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, uint8_t* d
     const size_t o_exit = o_dec + al(sizeof(DecBlock) * n);
     const size_t o_rexit = o_exit + al(size_t(segs) * kExitKeep * 4);
     const size_t o_entry = o_rexit + al(size_t(segs) * kSeg);
-    const size_t o_sout = o_entry + al(size_t(segs) * 4);
-    const size_t o_slast = o_sout + al(size_t(segs) * 4);
-    const size_t o_tstart = o_slast + al(size_t(segs) * 4);
-    const size_t o_rout = o_tstart + al(size_t(tiles) * sizeof(TileStart));
-    const size_t reg_words = c->index_passes ? size_t(segs) * kSegThreads : 0;   // per-region records of the three-kernel index pass only
-    const size_t o_rlast = o_rout + al(reg_words * 4);
-    const size_t o_rentry = o_rlast + al(reg_words * 4);
-    const size_t o_sntok = o_rentry + al(reg_words * 4);
-    const size_t o_tpos = o_sntok + al(size_t(segs) * 4);                       // token list: a token has at least one stream byte
+    const size_t o_tstart = o_entry + al(size_t(segs) * 4);
+    const size_t o_tpos = o_tstart + al(size_t(tiles) * sizeof(TileStart));     // token list: a token has at least one stream byte
     const size_t o_rd = o_tpos + al(size_t(segs) * kSeg * 4);
     const size_t o_rr = o_rd + al(size_t(segs) * kSegThreads * 4);              // (per 64 tokens: indexed like the 64-byte chunks)
     const size_t o_order = o_rr + al(size_t(segs) * kSegThreads * 4);
@@ -507,20 +498,14 @@ int decode_parallel(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, uint8_t* d
     const size_t o_sstate = o_gen + al(sizeof(GenCtl));                          // per segment: aggregate words of the index pass (the segment's, then three prefixes over its quarters; zeroed with the flags)
     const size_t o_sviol = o_sstate + al(size_t(segs) * 32);                    // ... and which level patterns its quarters' copies break (zeroed)
     const size_t o_tok16 = o_sviol + al(size_t(segs) * 4);                    // ... and its token positions inside the segment (16 bits per stream byte; not zeroed)
-    const size_t total = o_tok16 + al(c->index_passes ? 0 : size_t(segs) * kSeg * 2);
+    const size_t total = o_tok16 + al(size_t(segs) * kSeg * 2);
     HIPCHK(c, c->d_dec.ensure(total));
     uint8_t* ws = c->d_dec.as<uint8_t>();
     DecBlock* dec = reinterpret_cast<DecBlock*>(ws + o_dec);
     uint32_t* exit_tab = reinterpret_cast<uint32_t*>(ws + o_exit);
     uint8_t* rexit_tab = reinterpret_cast<uint8_t*>(ws + o_rexit);
     uint32_t* seg_entry = reinterpret_cast<uint32_t*>(ws + o_entry);
-    uint32_t* seg_out = reinterpret_cast<uint32_t*>(ws + o_sout);
-    uint32_t* seg_last = reinterpret_cast<uint32_t*>(ws + o_slast);
     TileStart* tile_start = reinterpret_cast<TileStart*>(ws + o_tstart);
-    uint32_t* reg_out = reinterpret_cast<uint32_t*>(ws + o_rout);
-    uint32_t* reg_last = reinterpret_cast<uint32_t*>(ws + o_rlast);
-    uint32_t* reg_entry = reinterpret_cast<uint32_t*>(ws + o_rentry);
-    uint32_t* seg_ntok = reinterpret_cast<uint32_t*>(ws + o_sntok);
     uint32_t* tok_pos = reinterpret_cast<uint32_t*>(ws + o_tpos);
     uint32_t* round_d = reinterpret_cast<uint32_t*>(ws + o_rd);
     uint32_t* round_rep = reinterpret_cast<uint32_t*>(ws + o_rr);
@@ -546,8 +531,6 @@ int decode_parallel(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, uint8_t* d
     const uint32_t* seg_block = c->d_seg_block_cur().as<uint32_t>();
     if (!c->dec_attrs) {
         HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(dec_exit_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kExitLds));
-        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(dec_index_a_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kIndexLds));
-        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(dec_index_c_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kIndexCLds));
         HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(dec_index1_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kIdxLds));
         HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(dec_exec2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kExecLds));
         c->dec_attrs = true;
@@ -568,21 +551,12 @@ int decode_parallel(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, uint8_t* d
     }
     {
         Timer t(c, T_DEC_INDEX, st);
-        if (segs && !c->index_passes) {
+        if (segs) {
             unsigned long long* sstate = reinterpret_cast<unsigned long long*>(ws + o_sstate);
             uint16_t* tok16 = reinterpret_cast<uint16_t*>(ws + o_tok16);
             hipLaunchKernelGGL(dec_index1_kernel, dim3(segs), dim3(kIdxThreads), kIdxLds, st, d_src, blocks, seg_block, dec, seg_entry, rexit_tab, sstate, sstate + segs, tok16);
             hipLaunchKernelGGL(dec_index2_kernel, dim3(2 * segs), dim3(kIdx2Threads), 0, st, d_src, blocks, seg_block, dec, sstate, sstate + segs, tok16, tile_start, tok_pos,
                                round_d, round_rep, ws + o_sviol);
-        }
-        if (c->index_passes) {   // the three-kernel form (cross-checks)
-            if (segs)
-                hipLaunchKernelGGL(dec_index_a_kernel, dim3(segs), dim3(kSegThreads), kIndexLds, st, d_src, blocks, seg_block, dec, seg_entry, seg_out, seg_last, rexit_tab, reg_out, reg_last, reg_entry, seg_ntok);
-            hipLaunchKernelGGL(dec_index_b_kernel, dim3(n), dim3(64), 0, st, blocks, dec, seg_out, seg_last, seg_entry, seg_ntok, n);
-            if (segs)
-                hipLaunchKernelGGL(dec_index_c_kernel, dim3(segs), dim3(kSegThreads), kIndexCLds, st, d_src, blocks, seg_block, dec, seg_entry, seg_out, seg_last,
-                                   tile_start, reg_out, reg_last, reg_entry, seg_ntok, tok_pos, round_d, round_rep,
-                                   jump ? &gen->n_general : nullptr);
         }
         if (jump && segs && !c->gen_attr) {
             HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(dec_general_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kGenLds));
@@ -594,7 +568,7 @@ int decode_parallel(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, uint8_t* d
             c->gen_grid = per_cu >= 1 ? c->n_cus * per_cu : 0;
             c->gen_attr = true;
         }
-        if (segs && !c->index_passes)
+        if (segs)
             hipLaunchKernelGGL(dec_viol_kernel, dim3((segs + 255) / 256), dim3(256), 0, st, seg_block, ws + o_sviol, dec, jump ? &gen->n_general : nullptr, segs);
         if (tiles) {
             HIPCHK(c, c->d_gen_acc.ensure(64));
@@ -605,13 +579,12 @@ int decode_parallel(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, uint8_t* d
                                c->d_gen_acc.as<uint32_t>(), reset);
         }
     }
-    if (c->debug_stop) { HIPCHK(c, hipGetLastError()); return 0; }
     {
         Timer t(c, T_DEC_EXEC, st);
         unsigned long long* prof = c->prof_on ? c->d_prof.as<unsigned long long>() : nullptr;
         // level-0 tiles first, by role E of the general pass, when they are few (dec_level0_kernel; option 23 = 0: off)
         uint32_t l0_grid = 0;
-        if (tiles && c->level0_by_e && !c->index_passes && c->decode_algo == 0) {
+        if (tiles && c->level0_by_e && c->decode_algo == 0) {
             if (!c->l0_attr) {
                 HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(dec_level0_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kGenLds));
                 c->l0_attr = true;
@@ -626,7 +599,7 @@ int decode_parallel(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, uint8_t* d
     }
     {
         Timer tg(c, T_DEC_GENERAL, st);   // (+ the result pass)
-        if (jump && segs) {  // returns at once unless D3c flagged a general block
+        if (jump && segs) {  // returns at once unless D3 flagged a general block
             if (c->gen_grid == 0) { c->err = "dec_general_kernel: the device cannot hold a workgroup"; return -MLZ_ERR_HIP; }
             // role S: one workgroup per general block, at most a quarter of the device (more blocks take turns); role E: the rest
             const uint32_t nS = gen_settle_wgs(c, n);
@@ -1124,7 +1097,7 @@ int mlz_decode_batch_device(mlz_ctx* c, void* stream, const uint8_t* d_src, uint
 int mlz_set_option(mlz_ctx* c, int opt, int64_t value) {
     if (!c) return -MLZ_ERR_ARG;
     if (!c->kids.empty()) {   // every device alike (the debug read-backs 5 / 7: the first device's)
-        if (opt == 5 || opt == 7) return mlz_set_option(c->kids[0], opt, value);
+        if (opt == MLZ_OPT_PROFILE_READ || opt == MLZ_OPT_TILE_TIMELINE_READ) return mlz_set_option(c->kids[0], opt, value);
         for (mlz_ctx* k : c->kids) { const int r = mlz_set_option(k, opt, value); if (r) return r; }
         return 0;
     }
@@ -1132,35 +1105,33 @@ int mlz_set_option(mlz_ctx* c, int opt, int64_t value) {
     switch (opt) {
     case MLZ_OPT_DECODE_ALGO: c->decode_algo = int(value); return 0;
     case MLZ_OPT_ENCODE_FAR: c->encode_far = int(value); return 0;
-    case 8: c->general_algo = int(value); return 0;  // 0 = pointer-jumping pass for general blocks (default), 1 = tile chain
-    case 12: c->timer_mask = uint32_t(value); return 0;  // which timers record events (bit = index of mlz_timer_name)
-    case 10: c->host_group_enc = size_t(value > 0 ? value : 1) << 20; return 0;  // tuning: MiB per group of a host-pointer encode batch
-    case 11: c->host_group_dec = size_t(value > 0 ? value : 1) << 20; return 0;  // ... of a decode batch
-    case 15: c->index_passes = int(value); return 0;  // decode: 1 = the index pass as the three kernels of rounds 2-3 (dec_index_a / _b / _c: cross-checks), 0 = dec_index1 / dec_index2 / dec_viol (default)
-    case 16: c->debug_stop = int(value); return 0;  // debug: decode_batch_device returns after the index pass (out_len is not written)
+    case MLZ_OPT_GENERAL_ALGO: c->general_algo = int(value); return 0;  // 0 = pointer-jumping pass for general blocks (default), 1 = tile chain
+    case MLZ_OPT_TIMER_MASK: c->timer_mask = uint32_t(value); return 0;  // which timers record events (bit = index of mlz_timer_name)
+    case MLZ_OPT_HOST_GROUP_ENC: c->host_group_enc = size_t(value > 0 ? value : 1) << 20; return 0;  // tuning: MiB per group of a host-pointer encode batch
+    case MLZ_OPT_HOST_GROUP_DEC: c->host_group_dec = size_t(value > 0 ? value : 1) << 20; return 0;  // ... of a decode batch
     case MLZ_OPT_DEVICE_GROUP: c->device_group = size_t(value > 0 ? value : 1) << 20; return 0;  // MiB of uncompressed data per internal group of a device batch
-    case 18: c->far_slices_l2 = int(value); return 0;  // debug / cross-check: LevelBalanced's far tables by the slice kernel of round 4
+    case MLZ_OPT_FAR_SLICES_L2: c->far_slices_l2 = int(value); return 0;  // debug / cross-check: LevelBalanced's far tables by the slice kernel of round 4
     case MLZ_OPT_L2_GAP: if (value < 1 || value > 16) return -MLZ_ERR_ARG; c->l2_gap = int(value); return 0;
-    case 24: c->fold_layout = int(value); return 0;  // encode: 1 (default) = layout inside the gather kernel where possible, 0 = always the separate layout kernel (cross-checks)
-    case 23: c->level0_by_e = int(value); return 0;  // decode: 1 (default) = level-0 tiles, when no more than CUs, by dec_level0_kernel before the exec pass; 0 = by the exec pass
-    case 21: c->fuse_ser = int(value); return 0;  // encode: 1 (default) = the match kernel serializes its pieces itself, 0 = the separate serializer kernel of rounds 2-5 (cross-checks)
-    case 20: c->gen_settle_cap = int(value); return 0;  // tuning: role S workgroups of the general pass at most
-    case 14: c->l2_free = int(value); return 0;  // LevelBalanced: 1 = no tile levels (ratio of the reference's L2 and better; blocks decode as general blocks)
-    case 13: c->gen_force_packed = int(value); return 0;  // tests: general blocks settle through the byte-packed pool (fallback path of dec_general_kernel)
-    case 9: c->gen_spin_limit = value > 0 ? uint32_t(value) : 1u; return 0;  // grid-barrier patience of the general-block pass, in polls (tests)
-    case 3: c->debug_status = int(value); return 0;  // debug: report failure sites in the error code
-    case 4: {  // debug: per-phase cycle counters (16 x u64: 0-7 encode, 8-15 decode)
+    case MLZ_OPT_FOLD_LAYOUT: c->fold_layout = int(value); return 0;  // encode: 1 (default) = layout inside the gather kernel where possible, 0 = always the separate layout kernel (cross-checks)
+    case MLZ_OPT_LEVEL0_KERNEL: c->level0_by_e = int(value); return 0;  // decode: 1 (default) = level-0 tiles, when no more than CUs, by dec_level0_kernel before the exec pass; 0 = by the exec pass
+    case MLZ_OPT_FUSED_SERIALIZER: c->fuse_ser = int(value); return 0;  // encode: 1 (default) = the match kernel serializes its pieces itself, 0 = the separate serializer kernel of rounds 2-5 (cross-checks)
+    case MLZ_OPT_GEN_SETTLE_CAP: c->gen_settle_cap = int(value); return 0;  // tuning: role S workgroups of the general pass at most
+    case MLZ_OPT_L2_FREE: c->l2_free = int(value); return 0;  // LevelBalanced: 1 = no tile levels (ratio of the reference's L2 and better; blocks decode as general blocks)
+    case MLZ_OPT_GEN_PACKED: c->gen_force_packed = int(value); return 0;  // tests: general blocks settle through the byte-packed pool (fallback path of dec_general_kernel)
+    case MLZ_OPT_GEN_SPIN: c->gen_spin_limit = value > 0 ? uint32_t(value) : 1u; return 0;  // grid-barrier patience of the general-block pass, in polls (tests)
+    case MLZ_OPT_DEBUG_STATUS: c->debug_status = int(value); return 0;  // debug: report failure sites in the error code
+    case MLZ_OPT_PROFILE: {  // debug: per-phase cycle counters (16 x u64: 0-7 encode, 8-15 decode)
         c->prof_on = value != 0;
         if (c->prof_on) { if (c->d_prof.ensure(kProfBytes) != hipSuccess) return -MLZ_ERR_HIP; if (hipMemset(c->d_prof.p, 0, kProfBytes) != hipSuccess) return -MLZ_ERR_HIP; }
         return 0;
     }
-    case 5: {  // debug: read the counters back into a host buffer whose address is `value`
+    case MLZ_OPT_PROFILE_READ: {  // debug: read the counters back into a host buffer whose address is `value`
         if (!c->d_prof.p) return -MLZ_ERR_ARG;
         if (hipDeviceSynchronize() != hipSuccess) return -MLZ_ERR_HIP;
         if (hipMemcpy(reinterpret_cast<void*>(value), c->d_prof.p, 128, hipMemcpyDeviceToHost) != hipSuccess) return -MLZ_ERR_HIP;
         return 0;
     }
-    case 7: {  // debug: read the exec pass's per-tile timeline (kProfTiles x 4 u64, 100 MHz clock) into a host buffer
+    case MLZ_OPT_TILE_TIMELINE_READ: {  // debug: read the exec pass's per-tile timeline (kProfTiles x 4 u64, 100 MHz clock) into a host buffer
         if (!c->d_prof.p) return -MLZ_ERR_ARG;
         if (hipDeviceSynchronize() != hipSuccess) return -MLZ_ERR_HIP;
         if (hipMemcpy(reinterpret_cast<void*>(value), c->d_prof.as<uint8_t>() + 256, kProfBytes - 256, hipMemcpyDeviceToHost) != hipSuccess) return -MLZ_ERR_HIP;

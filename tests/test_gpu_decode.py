@@ -275,11 +275,10 @@ def test_general_block_paths_agree(ctx):
         assert (v[0] == o[0]) and (v[0] == "err" or v[1] == o[1])
 
 
-def test_index_pass_forms_agree(ctx):
-    # The index pass (token list, tile starts, level conformance, block totals) exists in two forms: dec_index1 / dec_index2 (default)
-    # and the three kernels of rounds 2-3 (MLZ_OPT_INDEX_PASSES = 1).  Same output and the same verdicts on own streams of every
-    # level, on the oracle's streams (general blocks), on dense token streams (more than one stage of tokens per segment) and on
-    # mutated streams.
+def test_index_pass_on_own_foreign_and_mutated_streams(ctx):
+    # The index pass (token list, tile starts, level conformance, block totals): the right output on own streams of every level, on
+    # the oracle's streams (general blocks) and on dense token streams (more than one stage of tokens per segment), and the oracle's
+    # verdicts on mutated streams.
     rng = np.random.default_rng(77)
     datas = [synth.text_like(3 << 20, 4), synth.enwik_like(2 << 20, 5), synth.json_like(1 << 20, 6), bytes(rng.integers(0, 4, 300_000, dtype=np.uint8)),
              b"ab" * 200_000 + bytes(rng.integers(0, 256, 70_000, dtype=np.uint8)) + b"xyz" * 100_000]
@@ -297,17 +296,9 @@ def test_index_pass_forms_agree(ctx):
             pos = int(rng.integers(4, len(m)))
             m[pos] ^= int(rng.integers(1, 256))
             mutated.append(bytes(m))
-    results = {}
-    for passes in (0, 1):
-        ctx.set_option(mz.OPT_INDEX_PASSES, passes)
-        try:
-            assert mz.decode_batch(encs, ctx) == want
-            results[passes] = (ctx.general_blocks(), [gpu_decode_result(m, ctx) for m in mutated])
-        finally:
-            ctx.set_option(mz.OPT_INDEX_PASSES, 0)
-    assert results[0] == results[1]
-    for m, v in zip(mutated, results[0][1]):
-        assert v == oracle_decode_result(m)
+    assert mz.decode_batch(encs, ctx) == want
+    for m in mutated:
+        assert gpu_decode_result(m, ctx) == oracle_decode_result(m)
 
 
 def test_own_streams_take_the_tile_path(ctx):

@@ -17,7 +17,7 @@ from tests import tile_levels as TL
 
 pytestmark = pytest.mark.gpu
 
-OPT_DECODE_ALGO, OPT_GENERAL_ALGO, OPT_HOST_GROUP_DEC, OPT_INDEX_PASSES, OPT_DEVICE_GROUP, OPT_L2_GAP, OPT_LEVEL0_BY_E = 1, 8, 11, 15, 17, 19, 23
+OPT_DECODE_ALGO, OPT_GENERAL_ALGO, OPT_HOST_GROUP_DEC, OPT_DEVICE_GROUP, OPT_L2_GAP, OPT_LEVEL0_BY_E = 1, 8, 11, 17, 19, 23
 COPIES = 8
 
 
@@ -73,8 +73,6 @@ def _expected_team(cases, how):
     teams = [c.intended.team for c in cases if c.intended.general]
     if not teams:
         return 0
-    if how == "index":      # the three-kernel index pass measures no dependency distance: team 1 (dec_index_c_kernel)
-        return 1
     if how == "groups":     # one block per internal group: the largest over the groups
         return max(teams)
     return min(teams)       # one group: the smallest of the batch (fewer than 16 general blocks: no cap by the settling workgroups)
@@ -82,7 +80,6 @@ def _expected_team(cases, how):
 
 LEGS = [
     ("default", {}, "batch"),
-    ("index_three_kernels", {OPT_INDEX_PASSES: 1}, "index"),
     ("level0_by_exec", {OPT_LEVEL0_BY_E: 0}, None),
     ("general_on_tile_chain", {OPT_GENERAL_ALGO: 1}, None),
     ("serial", {OPT_DECODE_ALGO: 1}, None),

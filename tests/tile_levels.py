@@ -1,6 +1,6 @@
 """Plain restatement of the decoder's tile-level classification (DESIGN.md "Tile levels"), and hand-built blocks next to its rule.
 
-The decoder's index pass (dec_index2_kernel + dec_viol_kernel, or dec_index_c_kernel in the three-kernel form) decides per block:
+The decoder's index pass (dec_index2_kernel + dec_viol_kernel) decides per block:
 conformant to one of the three level patterns (the exec pass then runs its tiles level by level), or general (dec_general_kernel,
 settled by a team of 1, 2 or 4 workgroups).  A miss there is not an error: it is a schedule under which a tile may read a source tile
 that has not been written yet.  This module says, byte range by byte range and in the slow obvious way, what the verdict must be.
