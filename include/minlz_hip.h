@@ -184,6 +184,26 @@ int64_t mlz_stream_decode(mlz_ctx* ctx, uint32_t flags, const uint8_t* src, size
 int64_t mlz_stream_encode_gather_device(mlz_ctx* ctx, int level, uint32_t block_size, uint32_t flags, const uint8_t* const* d_src, const size_t* src_len,
                                         int n_ranges, uint8_t* d_dst, size_t dst_cap);
 
+/* The device-resident Reader: the stream lies in HBM at d_src (n bytes), on a device of the context; the call runs on that device (-MLZ_ERR_ARG if none
+ * of the context's devices holds d_src, as for the *_batch_device calls; one HBM-resident stream is not fanned out over several devices).  `stream` is
+ * a hipStream_t (NULL = default); both calls are synchronous, like mlz_stream_encode_gather_device.  n is at most 2^36.
+ *
+ * mlz_stream_decoded_len_device: the chunk walk alone.  Returns what mlz_stream_decoded_len returns for the same bytes; *prefix_len (may be NULL)
+ *   receives what mlz_stream_decoded_prefix_len returns.
+ * mlz_stream_decode_device: NewReader(src) read to EOF, into d_dst on the same device.  Returns what mlz_stream_decode returns for the same bytes,
+ *   flags and dst_cap: the decoded size, or the first error in stream order (the chunks in front of a framing error are decoded and checked first).
+ *   On success d_dst[0, result) holds the decoded bytes; nothing outside d_dst[0, dst_cap) is written in any case, d_src is only read, and no byte
+ *   at d_src + n or beyond enters the verdict.
+ *
+ * The chunk starts are found on the device from the bytes alone (every chunk type advances the Reader by 4 + its length, so the step is defined for every
+ * byte offset: exits of 4 KiB and 256 KiB regions for every offset, then the true entries top-down).  No payload crosses PCIe: 32 bytes per chunk visit
+ * the host (offset, type and length, decoded length, CRC, the header checks' outcome; skippable chunks inside the stream: none), where the Reader's running
+ * state is applied to them, and 12 bytes per chunk of results come back after the decode (16 for chunks of type 0x03).  Workspace: 8 bytes per stream
+ * byte + 12 bytes per 4 KiB of stream + 32 bytes per chunk, part of the decode workspace that mlz_get_counter(ctx, 4) reports, next to what the block
+ * decode of the chunks takes (above). */
+int64_t mlz_stream_decoded_len_device(mlz_ctx* ctx, void* stream, const uint8_t* d_src, size_t n, uint64_t* prefix_len);
+int64_t mlz_stream_decode_device(mlz_ctx* ctx, void* stream, uint32_t flags, const uint8_t* d_src, size_t n, uint8_t* d_dst, size_t dst_cap);
+
 /* ---- tuning / introspection (not part of the reference surface) ---- */
 #define MLZ_OPT_DECODE_ALGO 1  /* 0 = parallel (default), 1 = serial one-wave-per-block, 3 = parallel with every block on the tile path (cross-checks) */
 #define MLZ_OPT_ENCODE_FAR 2   /* 0 = tile-local matches only, 1 = + far matches (default) */

@@ -159,6 +159,20 @@ class Context:
         if r:
             _raise(r, self)
 
+    def stream_decoded_len_device(self, d_src, n, stream=None):
+        """mlz_stream_decoded_len_device: the chunk walk of a stream in device memory -> (result, prefix_len).  `result` is the raw return
+        value (the decoded size, or -MLZ_ERR_* for a framing error: nothing is raised, so that a caller can size the output for the prefix)."""
+        prefix = C.c_uint64(0)
+        r = _lib.lib().mlz_stream_decoded_len_device(self.handle, stream, d_src, n, C.byref(prefix))
+        return int(r), int(prefix.value)
+
+    def stream_decode_device(self, d_src, n, d_dst, dst_cap, ignore_crc=False, stream=None):
+        """mlz_stream_decode_device: NewReader(src) read to EOF, source and destination in device memory -> decoded size."""
+        r = _lib.lib().mlz_stream_decode_device(self.handle, stream, STREAM_IGNORE_CRC if ignore_crc else 0, d_src, n, d_dst, dst_cap)
+        if r < 0:
+            _raise(r, self)
+        return int(r)
+
 
 _default = None
 _default_lock = threading.Lock()

@@ -127,6 +127,7 @@ struct mlz_ctx {
     bool farbin_attr = false;
     // decode workspace
     DevBuf d_dec, d_idx;
+    DevBuf d_walk, d_walk_tab;   // the device-resident Reader's chunk walk: exit tables (8 bytes per stream byte) and the chunk table
     DevBuf d_gen_acc;      // two words summed over a call's internal groups by dec_schedule_kernel: general blocks, largest team (mlz_get_counter 2 / 6)
     int general_algo = 0;  // 0 = pointer-jumping pass for general blocks, 1 = tile chain in the exec pass
     size_t host_group_enc = kHostGroupEncodeDefault, host_group_dec = kHostGroupDecodeDefault;  // host-pointer batches: bytes per overlapped group
@@ -964,7 +965,7 @@ void mlz_destroy(mlz_ctx* c) {
     }
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    for (DevBuf* b : {&c->d_place, &c->d_crc, &c->d_crc_tabs, &c->d_crc_tiles, &c->d_prof, &c->d_blocks_k[0], &c->d_blocks_k[1], &c->d_tile_block_k[0], &c->d_tile_block_k[1], &c->d_seg_block_k[0], &c->d_seg_block_k[1], &c->d_scratch, &c->d_tile_size, &c->d_tile_out, &c->d_flags, &c->d_far, &c->d_farbin, &c->d_recs, &c->d_piece_cnt, &c->d_dec, &c->d_idx, &c->d_gen_acc, &c->d_in, &c->d_out, &c->d_len})
+    for (DevBuf* b : {&c->d_place, &c->d_crc, &c->d_crc_tabs, &c->d_crc_tiles, &c->d_prof, &c->d_blocks_k[0], &c->d_blocks_k[1], &c->d_tile_block_k[0], &c->d_tile_block_k[1], &c->d_seg_block_k[0], &c->d_seg_block_k[1], &c->d_scratch, &c->d_tile_size, &c->d_tile_out, &c->d_flags, &c->d_far, &c->d_farbin, &c->d_recs, &c->d_piece_cnt, &c->d_dec, &c->d_idx, &c->d_walk, &c->d_walk_tab, &c->d_gen_acc, &c->d_in, &c->d_out, &c->d_len})
         b->release();
     for (int k = 0; k < 2; k++) if (c->pinned_k[k]) (void)hipHostFree(c->pinned_k[k]);
     if (c->pinned2) (void)hipHostFree(c->pinned2);
@@ -1194,7 +1195,7 @@ int64_t mlz_get_counter(mlz_ctx* c, int which) {
         std::lock_guard<std::mutex> lk(c->mu);
         size_t e = 0, d = 0;
         for (const DevBuf* b : {&c->d_scratch, &c->d_tile_size, &c->d_tile_out, &c->d_flags, &c->d_far, &c->d_recs, &c->d_piece_cnt, &c->d_farbin}) e += b->cap;
-        for (const DevBuf* b : {&c->d_dec, &c->d_idx}) d += b->cap;
+        for (const DevBuf* b : {&c->d_dec, &c->d_idx, &c->d_walk, &c->d_walk_tab}) d += b->cap;
         return int64_t(which == 3 ? e : d);
     }
     if (which == 5) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->gen_fallbacks); }
@@ -1276,3 +1277,4 @@ int mlz_debug_idxprof(unsigned long long* out) {
 }  // extern "C"
 
 #include "mlz_stream.hip.inc"
+#include "mlz_stream_walk.hip.inc"

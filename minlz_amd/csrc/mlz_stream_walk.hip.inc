@@ -1,0 +1,369 @@
+// mlz_stream_walk.hip.inc — the device-resident Reader: the chunk walk of a .mz stream that lies in HBM, and its decode in place
+// (included at the end of mlz_hip.hip, behind mlz_stream.hip.inc whose chunk types and decode helpers it uses).
+//
+// A stream carries no table of its chunks, but every chunk type advances the Reader by 4 + clen (stream_parse: all of its cases do), so
+// next(p) = p + 4 + clen(p) is defined for EVERY byte offset p and the chunk starts are the orbit of offset 0 under next.  A parse that
+// starts at a wrong offset never falls in step with the real one (unlike a token stream: mlz_decode.hip.inc D2 guesses, this cannot), so the
+// exits are kept for every offset and the orbit is followed top-down through two sizes of region:
+//
+//   W1 exits   walk_exit_kernel    a workgroup per 4 KiB region (kWalkR0), bytes staged in LDS with 16-byte loads; next(i) for each of its
+//                                  offsets, finished to the region's EXIT (the first orbit point behind the region) by pointer jumping in LDS:
+//                                  one round for the usual region (garbage lengths average 8 MiB), ten for a region of empty chunks.
+//                                  x0[p] = exit - region base, a u32 per stream byte.
+//   W2 lift    walk_lift_kernel    a lane per four offsets: x1[p] = exit of p's 256 KiB region (kWalkR1), by following x0 while it stays inside
+//                                  (about one offset in 60 has to take a second hop).
+//   W3 top     walk_top_kernel     ONE lane follows x1 from offset 0 and notes the entry of every 256 KiB region the orbit visits: a chain of
+//                                  min(chunks, n / 256 KiB) dependent loads — bounded by the stream's size, not by its chunk count.
+//   W4 mid     walk_mid_kernel     a lane per entered 256 KiB region follows x0 from its entry (at most 64 hops) and notes the entry of every
+//                                  4 KiB region on the way.
+//   W5 count / scan / emit         a lane per entered 4 KiB region steps through the chunk headers inside it (usually one), counts those that
+//                                  enter the table, and after an exclusive scan of the counts writes their records (walk_classify,
+//                                  mlz_stream_walk.h) in stream order.  Skippable chunks that lie inside the stream never enter the table.
+//
+// The table (32 bytes per chunk) is read back and the Reader's running state (block size, header / EOF bookkeeping, output offsets, the
+// first error) is applied to it on the host by walk_parse_table — the same code the host check runs (a serial pass over 32-byte
+// records; streams of very many DATA chunks would want it as scans on the device).  Decode and CRC then run on the stream where it lies: descriptors point into
+// d_src (token-only mode, nothing is patched) and d_dst, stored chunks are copied by one kernel over a descriptor list.
+// Workspace: 8 bytes per stream byte (x0, x1) + 12 bytes per 4 KiB + 32 bytes per table entry.
+
+#include "mlz_stream_walk.h"
+
+namespace mlz {
+
+constexpr int kWalkR0Log = 12, kWalkR1Log = 18;
+constexpr uint32_t kWalkR0 = 1u << kWalkR0Log, kWalkR1 = 1u << kWalkR1Log;
+constexpr uint32_t kWalkStop = 0xffffffffu;     // no header can be read at this offset (fewer than 4 bytes left): the orbit ends here
+constexpr uint32_t kWalkNoEntry = 0xffffffffu;
+constexpr uint64_t kWalkNoEntry64 = ~uint64_t(0);
+constexpr uint32_t kWalkThreads = 256, kWalkPer = kWalkR0 / kWalkThreads;
+
+// W1.  LDS: 4 KiB + 3 bytes of the stream (+ up to 15 in front: the loads are 16-byte aligned) and a u32 per offset = 20.1 KiB.
+__global__ __launch_bounds__(kWalkThreads) void walk_exit_kernel(const uint8_t* __restrict__ src, uint64_t n, uint32_t* __restrict__ x0) {
+    __shared__ uint4 bufv[(kWalkR0 + 3 + 15 + 15) / 16 + 1];
+    __shared__ uint32_t t[kWalkR0];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t base = uint64_t(blockIdx.x) << kWalkR0Log;
+    const uint32_t rem = uint32_t(n - base < kWalkR0 + 3 ? n - base : kWalkR0 + 3);   // bytes of the stream from base on that matter here
+    const uint8_t* g = src + base;
+    const uint32_t mis = uint32_t(reinterpret_cast<uintptr_t>(g) & 15);
+    // aligned 16-byte loads: the first holds g[0] and the last g[rem - 1], so every one of them touches a byte of the stream's own pages
+    const uint4* ga = reinterpret_cast<const uint4*>(g - mis);
+    const uint32_t nvec = (mis + rem + 15) >> 4;
+    for (uint32_t k = tid; k < nvec; k += kWalkThreads) bufv[k] = ga[k];
+    __syncthreads();
+    const uint8_t* buf = reinterpret_cast<const uint8_t*>(bufv) + mis;
+    uint32_t v[kWalkPer];
+#pragma unroll
+    for (uint32_t k = 0; k < kWalkPer; k++) {
+        const uint32_t i = k * kWalkThreads + tid;
+        uint32_t h = 0;
+        const bool ok = i + 4 <= rem;
+        if (ok) __builtin_memcpy(&h, buf + i, 4);
+        v[k] = ok ? i + 4 + (h >> 8) : kWalkStop;
+        t[i] = v[k];
+    }
+    // pointer jumping in place: t[i] is always a point of i's orbit and only moves forward, so a value read while its owner replaces it
+    // is as good as the old one
+    for (;;) {
+        __syncthreads();
+        bool more = false;
+#pragma unroll
+        for (uint32_t k = 0; k < kWalkPer; k++) {
+            if (v[k] < kWalkR0) {
+                v[k] = t[v[k]];
+                t[k * kWalkThreads + tid] = v[k];
+                more = more || v[k] < kWalkR0;
+            }
+        }
+        if (!__syncthreads_or(more)) break;
+    }
+    const uint32_t own = uint32_t(n - base < kWalkR0 ? n - base : kWalkR0);
+#pragma unroll
+    for (uint32_t k = 0; k < kWalkPer; k++) {
+        const uint32_t i = k * kWalkThreads + tid;
+        if (i < own) x0[base + i] = v[k];
+    }
+}
+
+// W2.  x0 and x1 are 16-byte aligned and padded to a multiple of four entries.
+__global__ __launch_bounds__(256) void walk_lift_kernel(uint64_t n, const uint32_t* __restrict__ x0, uint32_t* __restrict__ x1) {
+    const uint64_t p0 = (uint64_t(blockIdx.x) * 256 + threadIdx.x) * 4;
+    if (p0 >= n) return;
+    const uint4 in = *reinterpret_cast<const uint4*>(x0 + p0);
+    uint32_t v[4] = {in.x, in.y, in.z, in.w};
+    const uint64_t base1 = p0 & ~uint64_t(kWalkR1 - 1), end1 = base1 + kWalkR1;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        if (p0 + j >= n) { v[j] = kWalkStop; continue; }
+        uint64_t base0 = p0 & ~uint64_t(kWalkR0 - 1);
+        uint32_t x = v[j];
+        for (;;) {
+            if (x == kWalkStop) break;
+            const uint64_t e = base0 + x;     // (strictly behind the offset it was read at: the loop ends)
+            if (e >= end1 || e >= n) { x = uint32_t(e - base1); break; }
+            base0 = e & ~uint64_t(kWalkR0 - 1);
+            x = x0[e];
+        }
+        v[j] = x;
+    }
+    *reinterpret_cast<uint4*>(x1 + p0) = make_uint4(v[0], v[1], v[2], v[3]);
+}
+
+// W3.
+__global__ __launch_bounds__(64) void walk_top_kernel(uint64_t n, const uint32_t* __restrict__ x1, uint64_t* __restrict__ entry1) {
+    if (threadIdx.x != 0) return;
+    uint64_t e = 0;
+    while (e < n) {
+        const uint64_t r1 = e >> kWalkR1Log;
+        entry1[r1] = e;
+        const uint32_t x = x1[e];
+        if (x == kWalkStop) break;
+        e = (r1 << kWalkR1Log) + x;
+    }
+}
+
+// W4.
+__global__ __launch_bounds__(64) void walk_mid_kernel(uint64_t n, uint32_t nreg1, const uint32_t* __restrict__ x0, const uint64_t* __restrict__ entry1,
+                                                      uint32_t* __restrict__ entry0) {
+    const uint32_t r1 = blockIdx.x * 64 + threadIdx.x;
+    if (r1 >= nreg1) return;
+    uint64_t e = entry1[r1];
+    if (e == kWalkNoEntry64) return;
+    const uint64_t end1 = (uint64_t(r1) + 1) << kWalkR1Log;
+    while (e < end1 && e < n) {
+        const uint64_t r0 = e >> kWalkR0Log;
+        entry0[r0] = uint32_t(e & (kWalkR0 - 1));
+        const uint32_t x = x0[e];
+        if (x == kWalkStop) break;
+        e = (r0 << kWalkR0Log) + x;
+    }
+}
+
+// W5: the chunk headers of one entered 4 KiB region, in order.  EMIT = false counts the table's entries, EMIT = true writes them.
+template <bool EMIT>
+__global__ __launch_bounds__(64) void walk_list_kernel(const uint8_t* __restrict__ src, uint64_t n, uint32_t nreg0, const uint32_t* __restrict__ entry0,
+                                                       uint32_t* __restrict__ counts, const uint32_t* __restrict__ first, WalkChunk* __restrict__ table) {
+    const uint32_t r0 = blockIdx.x * 64 + threadIdx.x;
+    if (r0 >= nreg0) return;
+    const uint32_t ent = entry0[r0];
+    uint32_t cnt = 0;
+    if (ent != kWalkNoEntry) {
+        const uint64_t base = uint64_t(r0) << kWalkR0Log;
+        const uint64_t end = base + kWalkR0 < n ? base + kWalkR0 : n;
+        uint64_t e = base + ent;
+        const uint32_t at = EMIT ? first[r0] : 0;
+        while (e < end) {
+            if (n - e < 4) {   // the stub the orbit ends on
+                if (EMIT) table[at + cnt] = walk_classify(src, n, e);
+                cnt++;
+                break;
+            }
+            const uint8_t type = src[e];
+            const uint32_t clen = uint32_t(src[e + 1]) | uint32_t(src[e + 2]) << 8 | uint32_t(src[e + 3]) << 16;
+            if (!walk_skippable(type, clen, n - e - 4)) {
+                if (EMIT) table[at + cnt] = walk_classify(src, n, e);
+                cnt++;
+            }
+            e += 4 + uint64_t(clen);
+        }
+    }
+    if (!EMIT) counts[r0] = cnt;
+}
+
+// Exclusive scan of the per-region counts by one workgroup: a contiguous slab per thread, the slab sums scanned in LDS.  total[0] = the sum.
+__global__ __launch_bounds__(1024) void walk_scan_kernel(const uint32_t* __restrict__ counts, uint32_t nreg0, uint32_t* __restrict__ first, uint32_t* __restrict__ total) {
+    __shared__ uint32_t sums[1024];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t per = (nreg0 + 1023) / 1024;
+    const uint32_t b = tid * per < nreg0 ? tid * per : nreg0, e = b + per < nreg0 ? b + per : nreg0;
+    uint32_t s = 0;
+    for (uint32_t i = b; i < e; i++) s += counts[i];
+    sums[tid] = s;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024; d <<= 1) {
+        const uint32_t add = tid >= d ? sums[tid - d] : 0;
+        __syncthreads();
+        sums[tid] += add;
+        __syncthreads();
+    }
+    uint32_t run = sums[tid] - s;
+    for (uint32_t i = b; i < e; i++) { first[i] = run; run += counts[i]; }
+    if (tid == 1023) total[0] = sums[1023];
+}
+
+}  // namespace mlz
+
+namespace {
+
+constexpr uint64_t kWalkMaxStream = uint64_t(1) << 36;   // (the table's entries are counted in 32 bits: one per 4 bytes at the most)
+
+// The chunk walk of d_src[0, n) on c's device: `chunks` = the data chunks in front of the first framing error, *parsed = what stream_parse
+// returns for the same bytes.  Returns 0 or -MLZ_ERR_HIP.  Synchronous on st.  Caller holds c->mu.
+int stream_walk_device(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, size_t n, std::vector<StreamChunk>* chunks, int64_t* parsed) {
+    chunks->clear();
+    *parsed = 0;
+    if (n == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t nreg0 = (uint64_t(n) + kWalkR0 - 1) >> kWalkR0Log, nreg1 = (uint64_t(n) + kWalkR1 - 1) >> kWalkR1Log;
+    const size_t xlen = (size_t(n) + 3) & ~size_t(3);
+    // x0 | x1 | entry1 | entry0 | counts | first | total
+    const size_t o_x1 = xlen * 4, o_e1 = o_x1 + xlen * 4, o_e0 = o_e1 + size_t(nreg1) * 8, o_cnt = o_e0 + size_t(nreg0) * 4, o_first = o_cnt + size_t(nreg0) * 4,
+                 o_total = (o_first + size_t(nreg0) * 4 + 15) & ~size_t(15);
+    HIPCHK(c, c->d_walk.ensure(o_total + 16));
+    int r = ensure_stream_objects(c, 0, 64);
+    if (r) return r;
+    uint8_t* ws = c->d_walk.as<uint8_t>();
+    uint32_t* x0 = reinterpret_cast<uint32_t*>(ws);
+    uint32_t* x1 = reinterpret_cast<uint32_t*>(ws + o_x1);
+    uint64_t* entry1 = reinterpret_cast<uint64_t*>(ws + o_e1);
+    uint32_t* entry0 = reinterpret_cast<uint32_t*>(ws + o_e0);
+    uint32_t* counts = reinterpret_cast<uint32_t*>(ws + o_cnt);
+    uint32_t* first = reinterpret_cast<uint32_t*>(ws + o_first);
+    uint32_t* total = reinterpret_cast<uint32_t*>(ws + o_total);
+    uint32_t h_total = 0;
+    {
+        WorkspaceOrder order(c, st);
+        HIPCHK(c, hipMemsetAsync(ws + o_e1, 0xff, o_cnt - o_e1, st));   // entry1 and entry0: no entry
+        hipLaunchKernelGGL(mlz::walk_exit_kernel, dim3(uint32_t(nreg0)), dim3(mlz::kWalkThreads), 0, st, d_src, uint64_t(n), x0);
+        hipLaunchKernelGGL(mlz::walk_lift_kernel, dim3(uint32_t((xlen / 4 + 255) / 256)), dim3(256), 0, st, uint64_t(n), x0, x1);
+        hipLaunchKernelGGL(mlz::walk_top_kernel, dim3(1), dim3(64), 0, st, uint64_t(n), x1, entry1);
+        hipLaunchKernelGGL(mlz::walk_mid_kernel, dim3(uint32_t((nreg1 + 63) / 64)), dim3(64), 0, st, uint64_t(n), uint32_t(nreg1), x0, entry1, entry0);
+        hipLaunchKernelGGL(mlz::walk_list_kernel<false>, dim3(uint32_t((nreg0 + 63) / 64)), dim3(64), 0, st, d_src, uint64_t(n), uint32_t(nreg0), entry0, counts, first,
+                           static_cast<mlz::WalkChunk*>(nullptr));
+        hipLaunchKernelGGL(mlz::walk_scan_kernel, dim3(1), dim3(1024), 0, st, counts, uint32_t(nreg0), first, total);
+        HIPCHK(c, hipMemcpyAsync(c->pinned2, total, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        HIPCHK(c, hipGetLastError());
+        h_total = *static_cast<uint32_t*>(c->pinned2);
+        if (h_total) {
+            HIPCHK(c, c->d_walk_tab.ensure(size_t(h_total) * sizeof(mlz::WalkChunk)));
+            r = ensure_stream_objects(c, 0, size_t(h_total) * sizeof(mlz::WalkChunk));
+            if (r) return r;
+            mlz::WalkChunk* tab = c->d_walk_tab.as<mlz::WalkChunk>();
+            hipLaunchKernelGGL(mlz::walk_list_kernel<true>, dim3(uint32_t((nreg0 + 63) / 64)), dim3(64), 0, st, d_src, uint64_t(n), uint32_t(nreg0), entry0, counts, first, tab);
+            HIPCHK(c, hipMemcpyAsync(c->pinned2, tab, size_t(h_total) * sizeof(mlz::WalkChunk), hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));
+            HIPCHK(c, hipGetLastError());
+        }
+    }
+    chunks->reserve(h_total);
+    *parsed = mlz::walk_parse_table(static_cast<const mlz::WalkChunk*>(c->pinned2), h_total, kMaxBlockSize,
+                                 [&](uint8_t type, uint32_t crc, uint64_t body_off, uint64_t body_len, uint64_t nn, uint64_t out_off) {
+                                     StreamChunk ck{};
+                                     ck.type = type; ck.crc = crc; ck.body_off = size_t(body_off); ck.body_len = size_t(body_len); ck.n = size_t(nn); ck.out_off = size_t(out_off);
+                                     chunks->push_back(ck);
+                                 });
+    return 0;
+}
+
+// All chunks of a walked stream, where they lie: decode (token-only mode: d_src is not touched), stored chunks by one kernel, CRC over d_dst.
+// Per chunk 8 + 4 (+ 4 for type 0x03) bytes of results come back.  Returns 0 or the first chunk's error in stream order.
+int64_t stream_decode_chunks_device(mlz_ctx* c, hipStream_t sm, bool ignore_crc, const uint8_t* d_src, std::vector<StreamChunk>& chunks, uint8_t* d_dst) {
+    const size_t nck = chunks.size();
+    begin_decode_call(c);
+    if (nck == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    size_t n_place = 0;
+    for (const StreamChunk& ck : chunks)
+        if (ck.type == kChunkUncompressed) n_place += (ck.n + kPlacePiece - 1) / kPlacePiece;
+    HIPCHK(c, c->d_len.ensure(sizeof(int64_t) * nck));
+    HIPCHK(c, c->d_crc.ensure(sizeof(uint32_t) * 2 * nck + 64));
+    int r = ensure_stream_objects(c, 0, nck * 16 + 64 + n_place * sizeof(PlaceDesc));
+    if (r) return r;
+    int64_t* h_len = static_cast<int64_t*>(c->pinned2);
+    uint32_t* h_crc = reinterpret_cast<uint32_t*>(h_len + nck);
+    uint32_t* h_crc3 = h_crc + nck;
+    PlaceDesc* h_place = reinterpret_cast<PlaceDesc*>((reinterpret_cast<uintptr_t>(h_crc3 + nck) + 63) & ~uintptr_t(63));
+    if (n_place) {   // stored chunks: 64 KiB pieces, one launch
+        size_t q = 0;
+        for (const StreamChunk& ck : chunks)
+            if (ck.type == kChunkUncompressed)
+                for (size_t o = 0; o < ck.n; o += kPlacePiece) h_place[q++] = PlaceDesc{ck.body_off + o, ck.out_off + o, uint32_t(std::min<size_t>(kPlacePiece, ck.n - o)), 0};
+        HIPCHK(c, c->d_place.ensure(n_place * sizeof(PlaceDesc)));
+        HIPCHK(c, hipMemcpyAsync(c->d_place.p, h_place, n_place * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
+        hipLaunchKernelGGL(stream_place2_kernel, dim3(uint32_t(n_place)), dim3(256), 0, sm, d_src, d_src, d_dst, c->d_place.as<PlaceDesc>());
+    }
+    // groups of chunks covering ~64 MiB of output, as stream_decode_range forms them
+    std::vector<mlz_block_desc> ddesc, cdesc(nck), c3desc;
+    size_t n_dec = 0, n_c3 = 0;
+    for (size_t c0 = 0; c0 < nck;) {
+        size_t c1 = c0, acc = 0;
+        while (c1 < nck && acc < kStreamGroupBytes) acc += chunks[c1++].n;
+        ddesc.clear(); c3desc.clear();
+        for (size_t i = c0; i < c1; i++) {
+            StreamChunk& ck = chunks[i];
+            cdesc[i] = mlz_block_desc{ck.out_off, ck.type == kChunkMinLZCompCRC ? uint64_t(0) : uint64_t(ck.n), 0, 0};
+            if (ck.type == kChunkUncompressed) continue;
+            ck.res_idx = n_dec + ddesc.size();
+            ddesc.push_back(mlz_block_desc{ck.body_off, ck.body_len, ck.out_off, ck.n});
+            if (ck.type == kChunkMinLZCompCRC) {
+                ck.crc_idx = n_c3 + c3desc.size();
+                c3desc.push_back(mlz_block_desc{ck.body_off, ck.body_len, 0, 0});
+            }
+        }
+        if (!ddesc.empty()) {
+            r = decode_device_locked(c, sm, d_src, d_dst, ddesc.data(), int(ddesc.size()), c->d_len.as<int64_t>() + n_dec, true, nullptr, false);
+            if (r) return r;
+        }
+        if (!ignore_crc) {
+            r = crc_device_locked(c, sm, d_dst, cdesc.data() + c0, int(c1 - c0), c->d_crc.as<uint32_t>() + c0);
+            if (r) return r;
+            if (!c3desc.empty()) {
+                r = crc_device_locked(c, sm, d_src, c3desc.data(), int(c3desc.size()), c->d_crc.as<uint32_t>() + nck + n_c3);
+                if (r) return r;
+            }
+        }
+        n_dec += ddesc.size(); n_c3 += c3desc.size();
+        c0 = c1;
+    }
+    if (n_dec) HIPCHK(c, hipMemcpyAsync(h_len, c->d_len.p, sizeof(int64_t) * n_dec, hipMemcpyDeviceToHost, sm));
+    if (!ignore_crc) HIPCHK(c, hipMemcpyAsync(h_crc, c->d_crc.p, sizeof(uint32_t) * (nck + n_c3), hipMemcpyDeviceToHost, sm));
+    HIPCHK(c, hipStreamSynchronize(sm));
+    HIPCHK(c, hipGetLastError());
+    for (size_t i = 0; i < nck; i++) {
+        const StreamChunk& ck = chunks[i];
+        if (ck.type != kChunkUncompressed) {
+            const int64_t got = h_len[ck.res_idx];
+            if (got != int64_t(ck.n)) return got < 0 ? got : -MLZ_ERR_CORRUPT;
+        }
+        if (!ignore_crc && (ck.type == kChunkMinLZCompCRC ? h_crc3[ck.crc_idx] : h_crc[i]) != ck.crc) return -MLZ_ERR_CRC;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t mlz_stream_decoded_len_device(mlz_ctx* c, void* stream, const uint8_t* d_src, size_t n, uint64_t* prefix_len) {
+    if (!c || (!d_src && n) || uint64_t(n) > kWalkMaxStream) return -MLZ_ERR_ARG;
+    if (n && !(c = owner_of(c, d_src))) return -MLZ_ERR_ARG;
+    if (!c->kids.empty()) c = c->kids[0];   // (an empty stream: any device)
+    std::lock_guard<std::mutex> lk(c->mu);
+    std::vector<StreamChunk> chunks;
+    int64_t r = 0;
+    const int e = stream_walk_device(c, static_cast<hipStream_t>(stream), d_src, n, &chunks, &r);
+    if (e) return e;
+    if (prefix_len) *prefix_len = r >= 0 ? uint64_t(r) : chunks.empty() ? 0 : uint64_t(chunks.back().out_off + chunks.back().n);
+    return r;
+}
+
+int64_t mlz_stream_decode_device(mlz_ctx* c, void* stream, uint32_t flags, const uint8_t* d_src, size_t n, uint8_t* d_dst, size_t dst_cap) {
+    if (!c || (!d_src && n) || (!d_dst && dst_cap) || uint64_t(n) > kWalkMaxStream) return -MLZ_ERR_ARG;
+    if (n && !(c = owner_of(c, d_src))) return -MLZ_ERR_ARG;
+    if (!c->kids.empty()) c = c->kids[0];
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0;
+    std::vector<StreamChunk> chunks;
+    int64_t parsed = 0;
+    const int e = stream_walk_device(c, st, d_src, n, &chunks, &parsed);
+    if (e) return e;
+    // as stream_decode_over: the chunks in front of a framing error are decoded and checked first
+    const size_t total = parsed >= 0 ? size_t(parsed) : chunks.empty() ? 0 : chunks.back().out_off + chunks.back().n;
+    if (total > dst_cap) return -MLZ_ERR_DST_TOO_SMALL;
+    const int64_t r = (parsed >= 0 || total) ? stream_decode_chunks_device(c, st, ignore_crc, d_src, chunks, d_dst) : 0;
+    return r < 0 ? r : parsed;
+}
+
+}  // extern "C"

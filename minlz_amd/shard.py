@@ -149,6 +149,20 @@ class HipTensorCodec:
             self.ctx.crc_batch_device(st, base.data_ptr(), desc, crc32.data_ptr())
         return crc32[:n].to(torch.int64) & 0xFFFFFFFF
 
+    def decode_stream(self, t, ignore_crc=False):
+        """A whole .mz stream that lies on the device (uint8 tensor) -> its decoded bytes, a new uint8 tensor on the same device.  The chunks
+        are found on the device (mlz_stream_decoded_len_device sizes the output) and decoded where they lie (mlz_stream_decode_device): no
+        payload visits the host.  Raises the Reader's first error in stream order, like api.stream_decode."""
+        if t.dtype != torch.uint8 or not t.is_cuda:
+            raise ValueError("decode_stream: a uint8 tensor on the device")
+        t = t.contiguous()
+        st = torch.cuda.current_stream(t.device).cuda_stream
+        n, prefix = self.ctx.stream_decoded_len_device(t.data_ptr(), t.numel(), stream=st)
+        cap = n if n >= 0 else prefix   # a framing error: the chunks in front of it are decoded and checked first
+        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=t.device)
+        r = self.ctx.stream_decode_device(t.data_ptr(), t.numel(), out.data_ptr(), cap, ignore_crc=ignore_crc, stream=st)
+        return out[:r]
+
 
 def frame_run(codec, src, block_lens, level):
     """Encode this rank's blocks and frame them into one contiguous run of stream chunks on the device.
