@@ -198,11 +198,48 @@ int64_t mlz_stream_encode_gather_device(mlz_ctx* ctx, int level, uint32_t block_
  * The chunk starts are found on the device from the bytes alone (every chunk type advances the Reader by 4 + its length, so the step is defined for every
  * byte offset: exits of 4 KiB and 256 KiB regions for every offset, then the true entries top-down).  No payload crosses PCIe: 32 bytes per chunk visit
  * the host (offset, type and length, decoded length, CRC, the header checks' outcome; skippable chunks inside the stream: none), where the Reader's running
- * state is applied to them, and 12 bytes per chunk of results come back after the decode (16 for chunks of type 0x03).  Workspace: 8 bytes per stream
+ * state is applied to them, and 12 bytes per chunk of results come back after the decode.  Workspace: 8 bytes per stream
  * byte + 12 bytes per 4 KiB of stream + 32 bytes per chunk, part of the decode workspace that mlz_get_counter(ctx, 4) reports, next to what the block
  * decode of the chunks takes (above). */
 int64_t mlz_stream_decoded_len_device(mlz_ctx* ctx, void* stream, const uint8_t* d_src, size_t n, uint64_t* prefix_len);
 int64_t mlz_stream_decode_device(mlz_ctx* ctx, void* stream, uint32_t flags, const uint8_t* d_src, size_t n, uint8_t* d_dst, size_t dst_cap);
+
+/* The device-resident ReadSeeker: Reader.ReadSeeker / ReadSeeker.ReadAt (reader.go:1322-1487) for a stream that lies in HBM, with the chunk walk's table
+ * in the place of the seek index (index.go:114 Index.Find): any byte ranges of the decoded stream, decoded on the device into device memory.
+ *
+ * mlz_stream_open_device: runs the chunk walk once and keeps its result on the host, in the handle: the data chunks with body offset and length, decoded
+ *   length, CRC, type and output offset.  Returns the decoded size (what mlz_stream_decoded_len_device returns for the same bytes) and the handle in *out.
+ *   A stream with a framing error gets no handle: that same negative value is returned and *out is NULL (a seeker over a stream whose end nobody can
+ *   vouch for is not offered; mlz_stream_decode_device keeps its "prefix first" behaviour).  Arguments as for mlz_stream_decode_device (d_src on a device
+ *   of the context, n at most 2^36); an empty stream opens with size 0.  The handle REFERS to d_src, which the caller keeps alive and unchanged until
+ *   mlz_dev_reader_close, and to the context, which must outlive the handle.  Several handles may be open on one context; they share its workspace
+ *   (calls are serialised by the context's lock), not their tables.
+ * mlz_dev_reader_size: the decoded size again.
+ * mlz_dev_reader_read: for every i, decoded bytes [ranges[i].off, + len) to d_dst[ranges[i].dst_off, + len); returns the sum of the lengths.  d_dst is on
+ *   the handle's device.  Source ranges may overlap, repeat, come in any order and be empty.  -MLZ_ERR_ARG: a range runs beyond the decoded size, two
+ *   destinations overlap, d_dst is not on the handle's device; -MLZ_ERR_DST_TOO_SMALL: dst_off + len > dst_cap.  These are decided before anything is
+ *   launched, and nothing is written.
+ *   Exactly the chunks that hold at least one requested byte are decoded, each of them ONCE per call however many ranges touch it and always whole (the
+ *   block is the granularity of random access, as in the reference), and each one's CRC is checked over the whole chunk unless flags has
+ *   MLZ_STREAM_IGNORE_CRC (types 0x01 and 0x02 over the decoded bytes, 0x03 over the token bytes).  The result is the error of the first failing touched
+ *   chunk in stream order (-MLZ_ERR_CORRUPT, -MLZ_ERR_CRC, -MLZ_ERR_HIP); a broken chunk that no range touches is not noticed: that is what seeking
+ *   means.  After an error the contents of the ranges' destinations are unspecified.  In every case nothing outside the union of the ranges'
+ *   destinations is written (gaps between them included), d_src is only read, and no byte at d_src + n or beyond enters any result.
+ *   A compressed chunk that exactly one range touches and covers wholly is decoded straight into its place in d_dst; any other touched compressed chunk is
+ *   decoded into a scratch buffer of the context and its wanted parts are copied out; stored chunks are copied from the stream where it lies.  The work
+ *   runs in groups of about 64 MiB of chunk output, so the scratch is at most a group plus one block whatever the ranges; it is part of the decode
+ *   workspace (mlz_get_counter 4).  Synchronous; `stream` as for mlz_stream_decode_device.
+ * mlz_dev_reader_close: frees the handle (NULL: nothing). */
+typedef struct mlz_dev_reader mlz_dev_reader;
+typedef struct {
+    uint64_t off;     /* first decoded byte wanted */
+    uint64_t len;     /* how many */
+    uint64_t dst_off; /* where in d_dst they go */
+} mlz_range;
+int64_t mlz_stream_open_device(mlz_ctx* ctx, void* stream, const uint8_t* d_src, size_t n, mlz_dev_reader** out);
+int64_t mlz_dev_reader_size(const mlz_dev_reader* reader);
+int64_t mlz_dev_reader_read(mlz_dev_reader* reader, void* stream, uint32_t flags, const mlz_range* ranges, size_t n_ranges, uint8_t* d_dst, size_t dst_cap);
+void mlz_dev_reader_close(mlz_dev_reader* reader);
 
 /* ---- tuning / introspection (not part of the reference surface) ---- */
 #define MLZ_OPT_DECODE_ALGO 1  /* 0 = parallel (default), 1 = serial one-wave-per-block, 3 = parallel with every block on the tile path (cross-checks) */
@@ -250,7 +287,9 @@ const char* mlz_timer_name(int idx);
  * which = 3 / 4: bytes of device workspace the context holds for encoding / decoding (grow-only: the high-water mark so far).
  * which = 5: decode calls whose general blocks fell back to the tile chain because the general pass's buffers could not be allocated.
  * which = 6: workgroups per block (1, 2 or 4) the general-block pass of the last decode call settled with (the largest over the
- *            groups of the call, as for 2); 0 = it had no general block. */
+ *            groups of the call, as for 2); 0 = it had no general block.
+ * which = 7 / 8: the plan of the context's last mlz_dev_reader_read: 7 = chunks it decoded or copied (each touched chunk counts once), 8 = decoded bytes
+ *            it put into the scratch (chunks decoded straight into d_dst and stored chunks: none). */
 int64_t mlz_get_counter(mlz_ctx* ctx, int which);
 
 #ifdef __cplusplus

@@ -18,7 +18,13 @@ SYMBOLS = [
     "mlz_stream_decode", "mlz_get_counter", "mlz_init_devices", "mlz_device_count", "mlz_device_ctx",
     "mlz_stream_encode_gather_device", "mlz_release_stream", "mlz_stream_decoded_prefix_len",
     "mlz_stream_decoded_len_device", "mlz_stream_decode_device",
+    "mlz_stream_open_device", "mlz_dev_reader_size", "mlz_dev_reader_read", "mlz_dev_reader_close",
 ]
+
+
+class Range(C.Structure):
+    """mlz_range: decoded bytes [off, off + len) -> d_dst[dst_off, dst_off + len)."""
+    _fields_ = [("off", C.c_uint64), ("len", C.c_uint64), ("dst_off", C.c_uint64)]
 
 
 class BlockDesc(C.Structure):
@@ -73,5 +79,9 @@ def lib():
     L.mlz_stream_decode.argtypes = [vp, u32, vp, sz, vp, sz]; L.mlz_stream_decode.restype = i64
     L.mlz_stream_decoded_len_device.argtypes = [vp, vp, vp, sz, C.POINTER(u64)]; L.mlz_stream_decoded_len_device.restype = i64
     L.mlz_stream_decode_device.argtypes = [vp, vp, u32, vp, sz, vp, sz]; L.mlz_stream_decode_device.restype = i64
+    L.mlz_stream_open_device.argtypes = [vp, vp, vp, sz, C.POINTER(vp)]; L.mlz_stream_open_device.restype = i64
+    L.mlz_dev_reader_size.argtypes = [vp]; L.mlz_dev_reader_size.restype = i64
+    L.mlz_dev_reader_read.argtypes = [vp, vp, u32, vp, sz, vp, sz]; L.mlz_dev_reader_read.restype = i64
+    L.mlz_dev_reader_close.argtypes = [vp]; L.mlz_dev_reader_close.restype = None
     _lib = L
     return L

@@ -174,6 +174,57 @@ class Context:
         return int(r)
 
 
+    def stream_open_device(self, d_src, n, stream=None):
+        """mlz_stream_open_device: a stream in device memory opened for range reads -> DeviceReader.  The caller keeps d_src alive and unchanged
+        while the reader is open.  A stream with a framing error raises that error (no reader)."""
+        h = C.c_void_p()
+        r = _lib.lib().mlz_stream_open_device(self.handle, stream, d_src, n, C.byref(h))
+        if r < 0:
+            _raise(r, self)
+        return DeviceReader(self, h, int(r))
+
+    def range_plan(self):
+        """(chunks decoded or copied, decoded bytes put into the scratch) by the context's last DeviceReader.read (mlz_get_counter 7, 8)."""
+        L = _lib.lib()
+        return int(L.mlz_get_counter(self.handle, 7)), int(L.mlz_get_counter(self.handle, 8))
+
+
+class DeviceReader:
+    """mlz_dev_reader: the device-resident ReadSeeker of one stream (Context.stream_open_device).  A context manager; close() frees it."""
+
+    def __init__(self, ctx, handle, size):
+        self.ctx, self.handle, self.size = ctx, handle, size
+
+    def read(self, ranges, d_dst, dst_cap, ignore_crc=False, stream=None):
+        """mlz_dev_reader_read.  ranges: (off, len, dst_off) triples, or a C-contiguous uint64 array of shape (k, 3): decoded bytes
+        [off, off + len) go to d_dst[dst_off, dst_off + len).  -> the sum of the lengths."""
+        if not self.handle:
+            raise ValueError("DeviceReader is closed")
+        a = np.ascontiguousarray(ranges, dtype=np.uint64).reshape(-1, 3)
+        r = _lib.lib().mlz_dev_reader_read(self.handle, stream, STREAM_IGNORE_CRC if ignore_crc else 0, a.ctypes.data if a.size else None, a.shape[0], d_dst, dst_cap)
+        if r < 0:
+            _raise(r, self.ctx)
+        return int(r)
+
+    def close(self):
+        if self.handle:
+            _lib.lib().mlz_dev_reader_close(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            if self.ctx.handle:   # (a reader that outlived its context has nothing left to free it with: the context owned the device)
+                self.close()
+        except Exception:
+            pass
+
+
 _default = None
 _default_lock = threading.Lock()
 

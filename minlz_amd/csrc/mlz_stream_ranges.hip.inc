@@ -1,0 +1,171 @@
+// mlz_stream_ranges.hip.inc — the device-resident ReadSeeker: range reads of a .mz stream that lies in HBM (included at the end of
+// mlz_hip.hip, behind mlz_stream_walk.hip.inc whose walk and chunk-list decode it uses).
+//
+// Reader.ReadSeeker / ReadSeeker.ReadAt (reader.go:1322-1487) over Index.Find (index.go:114), with the chunk table of the device walk in
+// the place of the seek index: mlz_stream_open_device walks the stream once and keeps the table of its data chunks on the host;
+// mlz_dev_reader_read plans the ranges of a call against it (plan_ranges, mlz_stream_ranges.h: the touched chunks, each decoded once — in
+// its place in the destination when one range covers it wholly, else in the context's scratch —, in groups of about 64 MiB), runs the
+// groups through stream_run_chunk_jobs (decode, CRC over whole chunks, verdicts in stream order) and moves the wanted parts of partly
+// wanted chunks, and of stored chunks from the stream itself, with ONE launch of stream_range_copy_kernel per group.
+
+namespace mlz {
+
+// Pieces of at most this many bytes are copied by 16 lanes each (four to a wavefront), longer ones by a workgroup each.  (0 builds the
+// library with one workgroup per piece throughout: tools/stream_ranges_time.py times the copy both ways.)
+#ifndef MLZ_RANGE_SHORT_MAX
+#define MLZ_RANGE_SHORT_MAX 1024
+#endif
+constexpr uint32_t kRangeShortMax = MLZ_RANGE_SHORT_MAX;
+constexpr uint32_t kRangeShortPerWg = 16;   // 256 threads / 16 lanes
+
+// descs[0, n_long): a workgroup per piece (wg_copy, as stream_place2_kernel); descs[n_long, n_all): 16 lanes per piece.  desc.pad selects the
+// source (0 = the scratch, 1 = the stream: stored chunks).  The short form stores destination-aligned 16-byte vectors, lane i of a piece's
+// 16 at aligned base + 16 i (+ 256 per further round); the ragged first and last vector are written bytewise by their lane; a full vector's
+// 16 source bytes are loaded from where they lie, at whatever alignment, so no byte outside the piece is read or written.
+__global__ __launch_bounds__(256) void stream_range_copy_kernel(const uint8_t* __restrict__ scratch, const uint8_t* __restrict__ stream, uint8_t* __restrict__ dst,
+                                                                const PlaceDesc* __restrict__ descs, uint32_t n_long, uint32_t n_all) {
+    if (blockIdx.x < n_long) {
+        const PlaceDesc d = descs[blockIdx.x];
+        wg_copy(dst + d.dst_off, (d.pad ? stream : scratch) + d.src_off, d.len, threadIdx.x, 256);
+        return;
+    }
+    const uint32_t idx = n_long + (blockIdx.x - n_long) * kRangeShortPerWg + (threadIdx.x >> 4);
+    if (idx >= n_all) return;
+    const uint32_t lane = threadIdx.x & 15;
+    const PlaceDesc d = descs[idx];
+    uint8_t* o = dst + d.dst_off;
+    const uint32_t mis = uint32_t(reinterpret_cast<uintptr_t>(o) & 15);
+    const uint8_t* s = (d.pad ? stream : scratch) + d.src_off - mis;   // s + x is the source of destination byte (o - mis) + x; only x in [mis, end) is touched
+    o -= mis;
+    const uint32_t end = mis + d.len;
+    for (uint32_t lo = lane * 16; lo < end; lo += 256) {
+        if (lo >= mis && lo + 16 <= end) {
+            uint4 x;
+            __builtin_memcpy(&x, s + lo, 16);
+            *reinterpret_cast<uint4*>(o + lo) = x;
+        } else {
+            const uint32_t b = lo > mis ? lo : mis, e = lo + 16 < end ? lo + 16 : end;
+            for (uint32_t k = b; k < e; k++) o[k] = s[k];
+        }
+    }
+}
+
+}  // namespace mlz
+
+// A stream opened for range reads: the walk's result.  Refers to the caller's d_src and to the (per-device) context.
+struct mlz_dev_reader {
+    mlz_ctx* ctx = nullptr;
+    const uint8_t* d_src = nullptr;
+    size_t n = 0;
+    int64_t size = 0;
+    std::vector<StreamChunk> chunks;          // the data chunks: body offset and length, decoded length, CRC, type, output offset
+    std::vector<mlz::RangeChunk> rchunks;     // the planner's view of them
+};
+
+namespace {
+
+static_assert(sizeof(mlz_range) == sizeof(mlz::ByteRange) && offsetof(mlz_range, dst_off) == offsetof(mlz::ByteRange, dst_off), "mlz_range is the planner's ByteRange");
+
+int64_t dev_reader_read_locked(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, const mlz::RangePlan& plan, uint8_t* d_dst) {
+    mlz_ctx* c = rd->ctx;
+    const size_t nt = plan.touched.size();
+    if (nt == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    size_t n_pieces = 0;
+    for (const mlz::RangeSeg& sg : plan.segs) n_pieces += size_t((sg.len + kPlacePiece - 1) / kPlacePiece);
+    if (plan.scratch_max) HIPCHK(c, c->d_range.ensure(size_t(plan.scratch_max)));
+    if (n_pieces) HIPCHK(c, c->d_place.ensure(n_pieces * sizeof(PlaceDesc)));
+    int r = ensure_stream_objects(c, 0, chunk_jobs_pinned(nt) + 64 + n_pieces * sizeof(PlaceDesc));
+    if (r) return r;
+    PlaceDesc* h_place = reinterpret_cast<PlaceDesc*>((reinterpret_cast<uintptr_t>(static_cast<uint8_t*>(c->pinned2) + chunk_jobs_pinned(nt)) + 63) & ~uintptr_t(63));
+    const uint8_t* scratch = c->d_range.as<uint8_t>();
+    std::vector<ChunkJob> jobs(nt);
+    for (size_t t = 0; t < nt; t++) {
+        const mlz::RangeTouched& tc = plan.touched[t];
+        const StreamChunk& ck = rd->chunks[tc.chunk];
+        jobs[t] = ChunkJob{tc.chunk, tc.where == mlz::kRangeDirect ? d_dst + tc.at : tc.where == mlz::kRangeScratch ? scratch + tc.at : rd->d_src + ck.body_off};
+    }
+    std::vector<size_t> gend(plan.groups.size());
+    for (size_t g = 0; g < gend.size(); g++) gend[g] = plan.groups[g].t1;
+    size_t placed = 0;
+    // a group's segments, cut into pieces of 64 KiB: the long ones in front, the short ones behind; built while the group's decode runs
+    auto copy_group = [&](size_t g) -> int {
+        const mlz::RangeGroup& gr = plan.groups[g];
+        size_t n_long = 0, n_short = 0;
+        for (size_t s = gr.s0; s < gr.s1; s++) {
+            const uint64_t len = plan.segs[s].len, full = len / kPlacePiece, rest = len % kPlacePiece;
+            n_long += size_t(full);
+            if (rest) (rest <= mlz::kRangeShortMax ? n_short : n_long)++;
+        }
+        if (n_long + n_short == 0) return 0;
+        PlaceDesc* out = h_place + placed;
+        size_t ql = 0, qs = n_long;
+        for (size_t s = gr.s0; s < gr.s1; s++) {
+            const mlz::RangeSeg& sg = plan.segs[s];
+            const mlz::RangeTouched& tc = plan.touched[sg.touched];
+            const bool stored = tc.where == mlz::kRangeStored;
+            const uint64_t from = (stored ? uint64_t(rd->chunks[tc.chunk].body_off) : tc.at) + sg.rel;
+            for (uint64_t o = 0; o < sg.len; o += kPlacePiece) {
+                const uint32_t len = uint32_t(std::min<uint64_t>(kPlacePiece, sg.len - o));
+                out[len <= mlz::kRangeShortMax ? qs++ : ql++] = PlaceDesc{from + o, sg.dst_off + o, len, stored ? 1u : 0u};
+            }
+        }
+        PlaceDesc* d_place = c->d_place.as<PlaceDesc>() + placed;
+        HIPCHK(c, hipMemcpyAsync(d_place, out, (n_long + n_short) * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
+        const size_t grid = n_long + (n_short + mlz::kRangeShortPerWg - 1) / mlz::kRangeShortPerWg;
+        hipLaunchKernelGGL(mlz::stream_range_copy_kernel, dim3(uint32_t(grid)), dim3(256), 0, sm, scratch, rd->d_src, d_dst, d_place, uint32_t(n_long), uint32_t(n_long + n_short));
+        placed += n_long + n_short;
+        return 0;
+    };
+    {   // (a call that only copies stored chunks launches nothing else: its copies are ordered behind the workspace's last user all the same)
+        WorkspaceOrder order(c, sm);
+    }
+    return stream_run_chunk_jobs(c, sm, ignore_crc, rd->d_src, rd->chunks, jobs, gend, copy_group);
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t mlz_stream_open_device(mlz_ctx* c, void* stream, const uint8_t* d_src, size_t n, mlz_dev_reader** out) {
+    if (out) *out = nullptr;
+    if (!c || !out || (!d_src && n) || uint64_t(n) > kWalkMaxStream) return -MLZ_ERR_ARG;
+    if (n && !(c = owner_of(c, d_src))) return -MLZ_ERR_ARG;
+    if (!c->kids.empty()) c = c->kids[0];   // (an empty stream: any device)
+    std::lock_guard<std::mutex> lk(c->mu);
+    mlz_dev_reader* rd = new (std::nothrow) mlz_dev_reader;
+    if (!rd) return -MLZ_ERR_HIP;
+    int64_t parsed = 0;
+    const int e = stream_walk_device(c, static_cast<hipStream_t>(stream), d_src, n, &rd->chunks, &parsed);
+    if (e || parsed < 0) { delete rd; return e ? e : parsed; }   // a framing error: no handle
+    rd->ctx = c; rd->d_src = d_src; rd->n = n; rd->size = parsed;
+    rd->rchunks.reserve(rd->chunks.size());
+    for (const StreamChunk& ck : rd->chunks) rd->rchunks.push_back(mlz::RangeChunk{uint64_t(ck.out_off), uint64_t(ck.n), ck.type});
+    *out = rd;
+    return parsed;
+}
+
+int64_t mlz_dev_reader_size(const mlz_dev_reader* rd) { return rd ? rd->size : -MLZ_ERR_ARG; }
+
+int64_t mlz_dev_reader_read(mlz_dev_reader* rd, void* stream, uint32_t flags, const mlz_range* ranges, size_t n_ranges, uint8_t* d_dst, size_t dst_cap) {
+    if (!rd || (!ranges && n_ranges) || (!d_dst && dst_cap)) return -MLZ_ERR_ARG;
+    mlz_ctx* c = rd->ctx;
+    std::lock_guard<std::mutex> lk(c->mu);
+    mlz::RangePlan plan;
+    const int pr = mlz::plan_ranges(rd->rchunks.data(), rd->rchunks.size(), uint64_t(rd->size), reinterpret_cast<const mlz::ByteRange*>(ranges), n_ranges, uint64_t(dst_cap), &plan);
+    if (pr < 0) return pr;
+    if (plan.total) {   // the destination: on the handle's device
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, d_dst) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != c->device) { (void)hipGetLastError(); return -MLZ_ERR_ARG; }
+    }
+    begin_decode_call(c);
+    c->range_chunks = plan.touched.size();
+    c->range_scratch = plan.scratch_total;
+    const int64_t r = dev_reader_read_locked(rd, static_cast<hipStream_t>(stream), (flags & MLZ_STREAM_IGNORE_CRC) != 0, plan, d_dst);
+    if (r < 0) (void)hipStreamSynchronize(static_cast<hipStream_t>(stream));   // nothing of a failed call is left in flight
+    return r < 0 ? r : int64_t(plan.total);
+}
+
+void mlz_dev_reader_close(mlz_dev_reader* rd) { delete rd; }
+
+}  // extern "C"

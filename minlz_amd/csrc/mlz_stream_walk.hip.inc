@@ -27,6 +27,7 @@
 // Workspace: 8 bytes per stream byte (x0, x1) + 12 bytes per 4 KiB + 32 bytes per table entry.
 
 #include "mlz_stream_walk.h"
+#include "mlz_stream_ranges.h"
 
 namespace mlz {
 
@@ -256,9 +257,81 @@ int stream_walk_device(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, size_t 
     return 0;
 }
 
-// All chunks of a walked stream, where they lie: decode (token-only mode: d_src is not touched), stored chunks by one kernel, CRC over d_dst.
-// Per chunk 8 + 4 (+ 4 for type 0x03) bytes of results come back.  Returns 0 or the first chunk's error in stream order.
-int64_t stream_decode_chunks_device(mlz_ctx* c, hipStream_t sm, bool ignore_crc, const uint8_t* d_src, std::vector<StreamChunk>& chunks, uint8_t* d_dst) {
+// One chunk of a decode list: `at` is where a compressed chunk (0x02 / 0x03) is decoded to, and where the bytes of a stored one (0x01) lie
+// for its CRC.  The targets of one list may lie in several allocations (the caller's destination, the context's scratch, the stream itself).
+struct ChunkJob { size_t ck; const uint8_t* at; };
+
+constexpr size_t chunk_jobs_pinned(size_t nj) { return nj * 16 + 64; }   // bytes of c->pinned2 a list of nj jobs takes, from its start
+
+// The decode / CRC / verdict of a list of chunks of a stream that lies at d_src, shared by the whole-stream call and the range read.  jobs: in
+// stream order; gend[g]: one past the last job of group g (range_group_ends: about 64 MiB of chunk output).  Per group one decode launch
+// sequence (token-only mode: d_src is not touched) and one CRC launch over all its chunks — 0x01 / 0x02 over the bytes at `at`, 0x03 over the
+// token bytes in the stream —, each with the lowest target address as its base pointer and the targets' distances from it in the descriptors;
+// after_group(g) is then called with sm still running (the range read enqueues the group's copy there).  One synchronise at the end; per chunk
+// 8 + 4 bytes of results come back.  The caller has begun the decode call, sized c->pinned2 (chunk_jobs_pinned(jobs.size()) bytes at its
+// start are used here) and holds c->mu.  Returns 0 or the error of the first failing chunk of the list.
+template <class AfterGroup>
+int64_t stream_run_chunk_jobs(mlz_ctx* c, hipStream_t sm, bool ignore_crc, const uint8_t* d_src, const std::vector<StreamChunk>& chunks,
+                              const std::vector<ChunkJob>& jobs, const std::vector<size_t>& gend, AfterGroup after_group) {
+    const size_t nj = jobs.size();
+    if (nj == 0) return 0;
+    HIPCHK(c, c->d_len.ensure(sizeof(int64_t) * nj));
+    HIPCHK(c, c->d_crc.ensure(sizeof(uint32_t) * nj + 64));
+    if (c->pinned2_cap < chunk_jobs_pinned(nj)) { c->err = "stream_run_chunk_jobs: the result buffer was not sized"; return -MLZ_ERR_HIP; }
+    int64_t* h_len = static_cast<int64_t*>(c->pinned2);
+    uint32_t* h_crc = reinterpret_cast<uint32_t*>(h_len + nj);
+    std::vector<mlz_block_desc> ddesc, cdesc;
+    std::vector<size_t> res_idx(nj, 0);
+    size_t n_dec = 0;
+    int r = 0;
+    for (size_t g = 0, j0 = 0; g < gend.size(); j0 = gend[g++]) {
+        const size_t j1 = gend[g];
+        uintptr_t dbase = ~uintptr_t(0), cbase = ~uintptr_t(0);
+        for (size_t j = j0; j < j1; j++) {
+            const StreamChunk& ck = chunks[jobs[j].ck];
+            if (ck.type != kChunkUncompressed) dbase = std::min(dbase, reinterpret_cast<uintptr_t>(jobs[j].at));
+            cbase = std::min(cbase, reinterpret_cast<uintptr_t>(ck.type == kChunkMinLZCompCRC ? d_src + ck.body_off : jobs[j].at));
+        }
+        ddesc.clear(); cdesc.clear();
+        for (size_t j = j0; j < j1; j++) {
+            const StreamChunk& ck = chunks[jobs[j].ck];
+            const uintptr_t at = reinterpret_cast<uintptr_t>(jobs[j].at);
+            if (ck.type == kChunkMinLZCompCRC) cdesc.push_back(mlz_block_desc{uint64_t(reinterpret_cast<uintptr_t>(d_src + ck.body_off) - cbase), ck.body_len, 0, 0});
+            else cdesc.push_back(mlz_block_desc{uint64_t(at - cbase), ck.n, 0, 0});
+            if (ck.type == kChunkUncompressed) continue;
+            res_idx[j] = n_dec + ddesc.size();
+            ddesc.push_back(mlz_block_desc{ck.body_off, ck.body_len, uint64_t(at - dbase), ck.n});
+        }
+        if (!ddesc.empty()) {
+            r = decode_device_locked(c, sm, d_src, reinterpret_cast<uint8_t*>(dbase), ddesc.data(), int(ddesc.size()), c->d_len.as<int64_t>() + n_dec, true, nullptr, false);
+            if (r) return r;
+        }
+        if (!ignore_crc) {
+            r = crc_device_locked(c, sm, reinterpret_cast<const uint8_t*>(cbase), cdesc.data(), int(j1 - j0), c->d_crc.as<uint32_t>() + j0);
+            if (r) return r;
+        }
+        n_dec += ddesc.size();
+        r = after_group(g);
+        if (r) return r;
+    }
+    if (n_dec) HIPCHK(c, hipMemcpyAsync(h_len, c->d_len.p, sizeof(int64_t) * n_dec, hipMemcpyDeviceToHost, sm));
+    if (!ignore_crc) HIPCHK(c, hipMemcpyAsync(h_crc, c->d_crc.p, sizeof(uint32_t) * nj, hipMemcpyDeviceToHost, sm));
+    HIPCHK(c, hipStreamSynchronize(sm));
+    HIPCHK(c, hipGetLastError());
+    for (size_t j = 0; j < nj; j++) {
+        const StreamChunk& ck = chunks[jobs[j].ck];
+        if (ck.type != kChunkUncompressed) {
+            const int64_t got = h_len[res_idx[j]];
+            if (got != int64_t(ck.n)) return got < 0 ? got : -MLZ_ERR_CORRUPT;
+        }
+        if (!ignore_crc && h_crc[j] != ck.crc) return -MLZ_ERR_CRC;
+    }
+    return 0;
+}
+
+// All chunks of a walked stream, where they lie: stored chunks by one kernel, then decode and CRC over d_dst (stream_run_chunk_jobs).
+// Returns 0 or the first chunk's error in stream order.
+int64_t stream_decode_chunks_device(mlz_ctx* c, hipStream_t sm, bool ignore_crc, const uint8_t* d_src, const std::vector<StreamChunk>& chunks, uint8_t* d_dst) {
     const size_t nck = chunks.size();
     begin_decode_call(c);
     if (nck == 0) return 0;
@@ -266,14 +339,9 @@ int64_t stream_decode_chunks_device(mlz_ctx* c, hipStream_t sm, bool ignore_crc,
     size_t n_place = 0;
     for (const StreamChunk& ck : chunks)
         if (ck.type == kChunkUncompressed) n_place += (ck.n + kPlacePiece - 1) / kPlacePiece;
-    HIPCHK(c, c->d_len.ensure(sizeof(int64_t) * nck));
-    HIPCHK(c, c->d_crc.ensure(sizeof(uint32_t) * 2 * nck + 64));
-    int r = ensure_stream_objects(c, 0, nck * 16 + 64 + n_place * sizeof(PlaceDesc));
+    int r = ensure_stream_objects(c, 0, chunk_jobs_pinned(nck) + 64 + n_place * sizeof(PlaceDesc));
     if (r) return r;
-    int64_t* h_len = static_cast<int64_t*>(c->pinned2);
-    uint32_t* h_crc = reinterpret_cast<uint32_t*>(h_len + nck);
-    uint32_t* h_crc3 = h_crc + nck;
-    PlaceDesc* h_place = reinterpret_cast<PlaceDesc*>((reinterpret_cast<uintptr_t>(h_crc3 + nck) + 63) & ~uintptr_t(63));
+    PlaceDesc* h_place = reinterpret_cast<PlaceDesc*>((reinterpret_cast<uintptr_t>(static_cast<uint8_t*>(c->pinned2) + chunk_jobs_pinned(nck)) + 63) & ~uintptr_t(63));
     if (n_place) {   // stored chunks: 64 KiB pieces, one launch
         size_t q = 0;
         for (const StreamChunk& ck : chunks)
@@ -283,52 +351,11 @@ int64_t stream_decode_chunks_device(mlz_ctx* c, hipStream_t sm, bool ignore_crc,
         HIPCHK(c, hipMemcpyAsync(c->d_place.p, h_place, n_place * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
         hipLaunchKernelGGL(stream_place2_kernel, dim3(uint32_t(n_place)), dim3(256), 0, sm, d_src, d_src, d_dst, c->d_place.as<PlaceDesc>());
     }
-    // groups of chunks covering ~64 MiB of output, as stream_decode_range forms them
-    std::vector<mlz_block_desc> ddesc, cdesc(nck), c3desc;
-    size_t n_dec = 0, n_c3 = 0;
-    for (size_t c0 = 0; c0 < nck;) {
-        size_t c1 = c0, acc = 0;
-        while (c1 < nck && acc < kStreamGroupBytes) acc += chunks[c1++].n;
-        ddesc.clear(); c3desc.clear();
-        for (size_t i = c0; i < c1; i++) {
-            StreamChunk& ck = chunks[i];
-            cdesc[i] = mlz_block_desc{ck.out_off, ck.type == kChunkMinLZCompCRC ? uint64_t(0) : uint64_t(ck.n), 0, 0};
-            if (ck.type == kChunkUncompressed) continue;
-            ck.res_idx = n_dec + ddesc.size();
-            ddesc.push_back(mlz_block_desc{ck.body_off, ck.body_len, ck.out_off, ck.n});
-            if (ck.type == kChunkMinLZCompCRC) {
-                ck.crc_idx = n_c3 + c3desc.size();
-                c3desc.push_back(mlz_block_desc{ck.body_off, ck.body_len, 0, 0});
-            }
-        }
-        if (!ddesc.empty()) {
-            r = decode_device_locked(c, sm, d_src, d_dst, ddesc.data(), int(ddesc.size()), c->d_len.as<int64_t>() + n_dec, true, nullptr, false);
-            if (r) return r;
-        }
-        if (!ignore_crc) {
-            r = crc_device_locked(c, sm, d_dst, cdesc.data() + c0, int(c1 - c0), c->d_crc.as<uint32_t>() + c0);
-            if (r) return r;
-            if (!c3desc.empty()) {
-                r = crc_device_locked(c, sm, d_src, c3desc.data(), int(c3desc.size()), c->d_crc.as<uint32_t>() + nck + n_c3);
-                if (r) return r;
-            }
-        }
-        n_dec += ddesc.size(); n_c3 += c3desc.size();
-        c0 = c1;
-    }
-    if (n_dec) HIPCHK(c, hipMemcpyAsync(h_len, c->d_len.p, sizeof(int64_t) * n_dec, hipMemcpyDeviceToHost, sm));
-    if (!ignore_crc) HIPCHK(c, hipMemcpyAsync(h_crc, c->d_crc.p, sizeof(uint32_t) * (nck + n_c3), hipMemcpyDeviceToHost, sm));
-    HIPCHK(c, hipStreamSynchronize(sm));
-    HIPCHK(c, hipGetLastError());
-    for (size_t i = 0; i < nck; i++) {
-        const StreamChunk& ck = chunks[i];
-        if (ck.type != kChunkUncompressed) {
-            const int64_t got = h_len[ck.res_idx];
-            if (got != int64_t(ck.n)) return got < 0 ? got : -MLZ_ERR_CORRUPT;
-        }
-        if (!ignore_crc && (ck.type == kChunkMinLZCompCRC ? h_crc3[ck.crc_idx] : h_crc[i]) != ck.crc) return -MLZ_ERR_CRC;
-    }
-    return 0;
+    std::vector<ChunkJob> jobs(nck);
+    for (size_t i = 0; i < nck; i++) jobs[i] = ChunkJob{i, d_dst + chunks[i].out_off};
+    std::vector<size_t> gend;
+    mlz::range_group_ends(nck, [&](size_t i) { return uint64_t(chunks[i].n); }, &gend);
+    return stream_run_chunk_jobs(c, sm, ignore_crc, d_src, chunks, jobs, gend, [](size_t) { return 0; });
 }
 
 }  // namespace

@@ -163,6 +163,51 @@ class HipTensorCodec:
         r = self.ctx.stream_decode_device(t.data_ptr(), t.numel(), out.data_ptr(), cap, ignore_crc=ignore_crc, stream=st)
         return out[:r]
 
+    def open_stream(self, t):
+        """A .mz stream that lies on the device (uint8 tensor) opened for range reads -> DeviceStream (ReadAt, read_ranges).  The chunk walk
+        runs once, here; a framing error raises."""
+        if t.dtype != torch.uint8 or not t.is_cuda:
+            raise ValueError("open_stream: a uint8 tensor on the device")
+        return DeviceStream(self.ctx, t.contiguous())
+
+
+class DeviceStream:
+    """A .mz stream on the device opened for random access (HipTensorCodec.open_stream): ReadSeeker.ReadAt (reader.go:1401-1487) with the
+    device walk's chunk table in the place of the seek index.  Keeps the stream's tensor alive."""
+
+    def __init__(self, ctx, t):
+        self.t = t
+        st = torch.cuda.current_stream(t.device).cuda_stream
+        self.reader = ctx.stream_open_device(t.data_ptr(), t.numel(), stream=st)
+        self.size = self.reader.size
+
+    def read_ranges(self, offsets, lengths, ignore_crc=False):
+        """Decoded bytes [offsets[i], offsets[i] + lengths[i]) for every i, back to back in the order given -> one new uint8 tensor."""
+        r = np.empty((len(offsets), 3), dtype=np.uint64)
+        r[:, 0] = offsets
+        r[:, 1] = lengths
+        total = int(r[:, 1].sum())
+        r[:, 2] = np.cumsum(r[:, 1]) - r[:, 1]
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=self.t.device)
+        st = torch.cuda.current_stream(self.t.device).cuda_stream
+        got = self.reader.read(r, out.data_ptr(), total, ignore_crc=ignore_crc, stream=st)
+        return out[:got]
+
+    def ReadAt(self, n, offset, ignore_crc=False):
+        """Up to n decoded bytes from `offset`, clamped at the end of the stream -> a new uint8 tensor."""
+        if n < 0 or offset < 0 or offset > self.size:
+            raise ValueError("ReadAt: offset outside the stream")
+        return self.read_ranges([offset], [min(n, self.size - offset)], ignore_crc)
+
+    def close(self):
+        self.reader.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
 
 def frame_run(codec, src, block_lens, level):
     """Encode this rank's blocks and frame them into one contiguous run of stream chunks on the device.
