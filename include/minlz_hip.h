@@ -207,7 +207,8 @@ int64_t mlz_stream_decode_device(mlz_ctx* ctx, void* stream, uint32_t flags, con
 /* The device-resident ReadSeeker: Reader.ReadSeeker / ReadSeeker.ReadAt (reader.go:1322-1487) for a stream that lies in HBM, with the chunk walk's table
  * in the place of the seek index (index.go:114 Index.Find): any byte ranges of the decoded stream, decoded on the device into device memory.
  *
- * mlz_stream_open_device: runs the chunk walk once and keeps its result on the host, in the handle: the data chunks with body offset and length, decoded
+ * mlz_stream_open_device: runs the chunk walk once and keeps its result on the host, in the handle (mlz_dev_reader_read plans against it there; the
+ *   first mlz_dev_reader_read_device of a handle also uploads it, 24 bytes per data chunk, into device memory that the handle owns until it is closed): the data chunks with body offset and length, decoded
  *   length, CRC, type and output offset.  Returns the decoded size (what mlz_stream_decoded_len_device returns for the same bytes) and the handle in *out.
  *   A stream with a framing error gets no handle: that same negative value is returned and *out is NULL (a seeker over a stream whose end nobody can
  *   vouch for is not offered; mlz_stream_decode_device keeps its "prefix first" behaviour).  Arguments as for mlz_stream_decode_device (d_src on a device
@@ -229,6 +230,21 @@ int64_t mlz_stream_decode_device(mlz_ctx* ctx, void* stream, uint32_t flags, con
  *   decoded into a scratch buffer of the context and its wanted parts are copied out; stored chunks are copied from the stream where it lies.  The work
  *   runs in groups of about 64 MiB of chunk output, so the scratch is at most a group plus one block whatever the ranges; it is part of the decode
  *   workspace (mlz_get_counter 4).  Synchronous; `stream` as for mlz_stream_decode_device.
+ * mlz_dev_reader_read_device: the same read with the ranges in DEVICE memory, planned by kernels: d_off[i], d_len[i] (i < n_ranges) are the offsets and
+ *   lengths, on the handle's device like d_dst and d_starts.  The output is PACKED: range i goes to d_dst[s_i, s_i + d_len[i]) with s_i = the sum of the
+ *   lengths in front of it, in the order given; when d_starts is not NULL it receives the n_ranges + 1 values s_0 ... s_n (s_n = the total).  Returns the
+ *   total.  (Explicit destination offsets stay with mlz_dev_reader_read: that they do not overlap takes a sort to check.)
+ *   -MLZ_ERR_ARG: a pointer that is not device memory of the handle's device (decided with hipPointerGetAttributes before anything is launched);
+ *   n_ranges > 2^31; a range that runs beyond the decoded size (off > size or len > size - off: an int64 -1 is such a value); more than 2^31 - 1
+ *   workgroups in one copy launch (total / 64 KiB + n_ranges / 16).  -MLZ_ERR_DST_TOO_SMALL: the total exceeds dst_cap.  The last three are found by the
+ *   kernels and reported after the call's first read-back, before any decode or copy is enqueued: nothing is written to d_dst or d_starts.
+ *   Everything else is mlz_dev_reader_read's contract: exactly the touched chunks are decoded, each once and whole, with its CRC; the same three classes
+ *   (straight into its place / through the scratch / stored, copied from the stream) chosen by the same rule; the first failing touched chunk's error in
+ *   stream order; nothing outside d_dst[0, total) is written; d_src, d_off and d_len are only read; empty, overlapping, repeated and unordered source
+ *   ranges are allowed; groups of about 64 MiB, the scratch at most a group plus one block; synchronous.  n_ranges == 0 returns 0 and launches nothing.
+ *   What visits the host is proportional to the touched chunks, never to the ranges: a 32-byte header (error word, total, copy pieces, touched chunks),
+ *   then 16 bytes per touched chunk down (chunk, class, place) and 16 up (group, class, scratch offset) — mlz_get_counter(ctx, 9) —, and the decode's
+ *   12 bytes of results per chunk.  Workspace: 16 bytes per range + 28 per data chunk of the stream, part of mlz_get_counter(ctx, 4).
  * mlz_dev_reader_close: frees the handle (NULL: nothing). */
 typedef struct mlz_dev_reader mlz_dev_reader;
 typedef struct {
@@ -239,6 +255,8 @@ typedef struct {
 int64_t mlz_stream_open_device(mlz_ctx* ctx, void* stream, const uint8_t* d_src, size_t n, mlz_dev_reader** out);
 int64_t mlz_dev_reader_size(const mlz_dev_reader* reader);
 int64_t mlz_dev_reader_read(mlz_dev_reader* reader, void* stream, uint32_t flags, const mlz_range* ranges, size_t n_ranges, uint8_t* d_dst, size_t dst_cap);
+int64_t mlz_dev_reader_read_device(mlz_dev_reader* reader, void* stream, uint32_t flags, const uint64_t* d_off, const uint64_t* d_len, size_t n_ranges,
+                                   uint8_t* d_dst, size_t dst_cap, uint64_t* d_starts /* may be NULL */);
 void mlz_dev_reader_close(mlz_dev_reader* reader);
 
 /* ---- tuning / introspection (not part of the reference surface) ---- */
@@ -288,8 +306,11 @@ const char* mlz_timer_name(int idx);
  * which = 5: decode calls whose general blocks fell back to the tile chain because the general pass's buffers could not be allocated.
  * which = 6: workgroups per block (1, 2 or 4) the general-block pass of the last decode call settled with (the largest over the
  *            groups of the call, as for 2); 0 = it had no general block.
- * which = 7 / 8: the plan of the context's last mlz_dev_reader_read: 7 = chunks it decoded or copied (each touched chunk counts once), 8 = decoded bytes
- *            it put into the scratch (chunks decoded straight into d_dst and stored chunks: none). */
+ * which = 7 / 8: the plan of the context's last mlz_dev_reader_read or mlz_dev_reader_read_device: 7 = chunks it decoded or copied (each touched chunk counts once), 8 = decoded bytes
+ *            it put into the scratch (chunks decoded straight into d_dst and stored chunks: none).
+ * which = 9: bytes of plan data that crossed between host and device, both directions together, during the context's last mlz_dev_reader_read_device:
+ *            32 + 32 per touched chunk (32 alone for a refused call or one that touches nothing).  Not counted: the results of the chunks' decode and CRC
+ *            (12 bytes per chunk, as in every stream decode) and the one-time upload of a handle's chunk table. */
 int64_t mlz_get_counter(mlz_ctx* ctx, int which);
 
 #ifdef __cplusplus

@@ -188,6 +188,11 @@ class Context:
         L = _lib.lib()
         return int(L.mlz_get_counter(self.handle, 7)), int(L.mlz_get_counter(self.handle, 8))
 
+    def range_plan_host_bytes(self):
+        """Bytes of plan data that crossed between host and device, both directions together, in the context's last DeviceReader.read_device
+        (mlz_get_counter 9): a header and two records per TOUCHED CHUNK, nothing per range."""
+        return int(_lib.lib().mlz_get_counter(self.handle, 9))
+
 
 class DeviceReader:
     """mlz_dev_reader: the device-resident ReadSeeker of one stream (Context.stream_open_device).  A context manager; close() frees it."""
@@ -202,6 +207,17 @@ class DeviceReader:
             raise ValueError("DeviceReader is closed")
         a = np.ascontiguousarray(ranges, dtype=np.uint64).reshape(-1, 3)
         r = _lib.lib().mlz_dev_reader_read(self.handle, stream, STREAM_IGNORE_CRC if ignore_crc else 0, a.ctypes.data if a.size else None, a.shape[0], d_dst, dst_cap)
+        if r < 0:
+            _raise(r, self.ctx)
+        return int(r)
+
+    def read_device(self, d_off, d_len, n, d_dst, dst_cap, d_starts=None, ignore_crc=False, stream=None):
+        """mlz_dev_reader_read_device.  d_off, d_len: device addresses of n uint64 offsets and lengths; decoded bytes [off[i], off[i] + len[i])
+        go to d_dst packed in the order given; d_starts (device address of n + 1 uint64, or None) receives where each range starts and the
+        total.  -> the sum of the lengths."""
+        if not self.handle:
+            raise ValueError("DeviceReader is closed")
+        r = _lib.lib().mlz_dev_reader_read_device(self.handle, stream, STREAM_IGNORE_CRC if ignore_crc else 0, d_off, d_len, n, d_dst, dst_cap, d_starts)
         if r < 0:
             _raise(r, self.ctx)
         return int(r)

@@ -22,22 +22,11 @@ constexpr uint32_t kRangeShortPerWg = 16;   // 256 threads / 16 lanes
 // source (0 = the scratch, 1 = the stream: stored chunks).  The short form stores destination-aligned 16-byte vectors, lane i of a piece's
 // 16 at aligned base + 16 i (+ 256 per further round); the ragged first and last vector are written bytewise by their lane; a full vector's
 // 16 source bytes are loaded from where they lie, at whatever alignment, so no byte outside the piece is read or written.
-__global__ __launch_bounds__(256) void stream_range_copy_kernel(const uint8_t* __restrict__ scratch, const uint8_t* __restrict__ stream, uint8_t* __restrict__ dst,
-                                                                const PlaceDesc* __restrict__ descs, uint32_t n_long, uint32_t n_all) {
-    if (blockIdx.x < n_long) {
-        const PlaceDesc d = descs[blockIdx.x];
-        wg_copy(dst + d.dst_off, (d.pad ? stream : scratch) + d.src_off, d.len, threadIdx.x, 256);
-        return;
-    }
-    const uint32_t idx = n_long + (blockIdx.x - n_long) * kRangeShortPerWg + (threadIdx.x >> 4);
-    if (idx >= n_all) return;
-    const uint32_t lane = threadIdx.x & 15;
-    const PlaceDesc d = descs[idx];
-    uint8_t* o = dst + d.dst_off;
+__device__ __forceinline__ void lanes16_copy(uint8_t* o, const uint8_t* s, uint32_t len, uint32_t lane) {
     const uint32_t mis = uint32_t(reinterpret_cast<uintptr_t>(o) & 15);
-    const uint8_t* s = (d.pad ? stream : scratch) + d.src_off - mis;   // s + x is the source of destination byte (o - mis) + x; only x in [mis, end) is touched
+    s -= mis;   // s + x is the source of destination byte (o - mis) + x; only x in [mis, end) is touched
     o -= mis;
-    const uint32_t end = mis + d.len;
+    const uint32_t end = mis + len;
     for (uint32_t lo = lane * 16; lo < end; lo += 256) {
         if (lo >= mis && lo + 16 <= end) {
             uint4 x;
@@ -50,11 +39,25 @@ __global__ __launch_bounds__(256) void stream_range_copy_kernel(const uint8_t* _
     }
 }
 
+__global__ __launch_bounds__(256) void stream_range_copy_kernel(const uint8_t* __restrict__ scratch, const uint8_t* __restrict__ stream, uint8_t* __restrict__ dst,
+                                                                const PlaceDesc* __restrict__ descs, uint32_t n_long, uint32_t n_all) {
+    if (blockIdx.x < n_long) {
+        const PlaceDesc d = descs[blockIdx.x];
+        wg_copy(dst + d.dst_off, (d.pad ? stream : scratch) + d.src_off, d.len, threadIdx.x, 256);
+        return;
+    }
+    const uint32_t idx = n_long + (blockIdx.x - n_long) * kRangeShortPerWg + (threadIdx.x >> 4);
+    if (idx >= n_all) return;
+    const PlaceDesc d = descs[idx];
+    lanes16_copy(dst + d.dst_off, (d.pad ? stream : scratch) + d.src_off, d.len, threadIdx.x & 15);
+}
+
 }  // namespace mlz
 
 // A stream opened for range reads: the walk's result.  Refers to the caller's d_src and to the (per-device) context.
 struct mlz_dev_reader {
     mlz_ctx* ctx = nullptr;
+    void* d_chunks = nullptr;                 // the table as the plan kernels read it (mlz::RdevChunk), uploaded by the first mlz_dev_reader_read_device
     const uint8_t* d_src = nullptr;
     size_t n = 0;
     int64_t size = 0;
@@ -166,6 +169,12 @@ int64_t mlz_dev_reader_read(mlz_dev_reader* rd, void* stream, uint32_t flags, co
     return r < 0 ? r : int64_t(plan.total);
 }
 
-void mlz_dev_reader_close(mlz_dev_reader* rd) { delete rd; }
+void mlz_dev_reader_close(mlz_dev_reader* rd) {
+    if (rd && rd->d_chunks) {
+        std::lock_guard<std::mutex> lk(rd->ctx->mu);
+        if (hipSetDevice(rd->ctx->device) == hipSuccess) (void)hipFree(rd->d_chunks);
+    }
+    delete rd;
+}
 
 }  // extern "C"

@@ -181,8 +181,18 @@ class DeviceStream:
         self.reader = ctx.stream_open_device(t.data_ptr(), t.numel(), stream=st)
         self.size = self.reader.size
 
-    def read_ranges(self, offsets, lengths, ignore_crc=False):
-        """Decoded bytes [offsets[i], offsets[i] + lengths[i]) for every i, back to back in the order given -> one new uint8 tensor."""
+    def read_ranges(self, offsets, lengths, ignore_crc=False, return_starts=False):
+        """Decoded bytes [offsets[i], offsets[i] + lengths[i]) for every i, back to back in the order given -> one new uint8 tensor.
+        return_starts: -> (that tensor, the n + 1 places where the ranges start in it and its size: int64 on the stream's device).
+        Two CUDA tensors (int64 or uint64, contiguous, on the stream's device) take the device path (mlz_dev_reader_read_device): the ranges
+        stay in device memory and are planned by kernels; the one thing that visits the host is the scalar int(lengths.sum()), which sizes the
+        output.  Lists and numpy arrays (and tensors on the CPU) are planned on the host."""
+        if torch.is_tensor(offsets) and torch.is_tensor(lengths) and offsets.is_cuda and lengths.is_cuda:
+            return self._read_ranges_device(offsets, lengths, ignore_crc, return_starts)
+        if torch.is_tensor(offsets):
+            offsets = offsets.numpy()
+        if torch.is_tensor(lengths):
+            lengths = lengths.numpy()
         r = np.empty((len(offsets), 3), dtype=np.uint64)
         r[:, 0] = offsets
         r[:, 1] = lengths
@@ -191,7 +201,28 @@ class DeviceStream:
         out = torch.empty(max(total, 1), dtype=torch.uint8, device=self.t.device)
         st = torch.cuda.current_stream(self.t.device).cuda_stream
         got = self.reader.read(r, out.data_ptr(), total, ignore_crc=ignore_crc, stream=st)
+        if return_starts:
+            return out[:got], torch.from_numpy(np.concatenate([r[:, 2], [total]]).astype(np.int64)).to(self.t.device)
         return out[:got]
+
+    def _read_ranges_device(self, offsets, lengths, ignore_crc, return_starts):
+        dev = self.t.device
+        for a in (offsets, lengths):
+            if a.dtype not in (torch.int64, torch.uint64) or a.dim() != 1 or not a.is_contiguous() or a.device != dev:
+                raise ValueError("read_ranges: device ranges are contiguous 1-d int64 or uint64 tensors on the stream's device")
+        n = offsets.numel()
+        if lengths.numel() != n:
+            raise ValueError("read_ranges: as many lengths as offsets")
+        # (a length that is negative as int64 is beyond every stream: the call finds it whatever this sum comes to)
+        total = int(lengths.view(torch.int64).sum()) if n else 0
+        if total < 0 or total > n * self.size:
+            total = 0
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        starts = torch.zeros(n + 1, dtype=torch.int64, device=dev) if return_starts else None
+        st = torch.cuda.current_stream(dev).cuda_stream
+        got = self.reader.read_device(offsets.data_ptr() if n else None, lengths.data_ptr() if n else None, n, out.data_ptr(), total,
+                                      d_starts=starts.data_ptr() if return_starts and n else None, ignore_crc=ignore_crc, stream=st)
+        return (out[:got], starts) if return_starts else out[:got]
 
     def ReadAt(self, n, offset, ignore_crc=False):
         """Up to n decoded bytes from `offset`, clamped at the end of the stream -> a new uint8 tensor."""

@@ -3,7 +3,9 @@ process, every shape warmed up, REPS timed repetitions with the variants alterna
 synchronise):
 
   t_open   mlz_stream_open_device (the chunk walk + keeping the table), once per stream: the median of REPS opens
-  t_read   mlz_dev_reader_read of the shape's ranges
+  t_read   mlz_dev_reader_read of the shape's ranges (a host array, planned on the host)
+  t_read_dev  mlz_dev_reader_read_device of the same offsets and lengths as two CUDA tensors (uploaded outside the timed window, as t_alt's
+           index tensor is built outside it): planned by kernels; mlz_get_counter 9 (plan bytes between host and device) is printed with it
   t_alt    the same bytes without it: mlz_stream_decode_device of the whole stream into a buffer, plus for (c) a torch gather of the same
            ranges from that buffer (its index tensor is built outside the timed window)
 
@@ -102,6 +104,13 @@ def measure(name, s, d, bs, only=None, ignore_crc=False):
         def read():
             assert rd.read(r, out.data_ptr(), total, ignore_crc=ignore_crc) == total
 
+        d_off = torch.from_numpy(r[:, 0].astype(np.int64)).cuda()
+        d_len = torch.from_numpy(r[:, 1].astype(np.int64)).cuda()
+        out_dev = torch.empty(len(d) + 64, dtype=torch.uint8, device="cuda")
+
+        def read_dev():
+            assert rd.read_device(d_off.data_ptr(), d_len.data_ptr(), len(r), out_dev.data_ptr(), total, ignore_crc=ignore_crc) == total
+
         def alt():
             assert ctx.stream_decode_device(t.data_ptr(), n, whole.data_ptr(), len(d), ignore_crc=ignore_crc) == len(d)
             if idx is not None:
@@ -113,13 +122,21 @@ def measure(name, s, d, bs, only=None, ignore_crc=False):
         for off, ln, dst in r[:: max(1, len(r) // 50)].tolist():
             assert np.array_equal(got[dst:dst + ln], dn[off:off + ln]), (name, shape)
         chunks, scratch = ctx.range_plan()
-        ts = timed([("t_read", read), ("t_alt", alt)])
+        read_dev()
+        torch.cuda.synchronize()
+        got = out_dev[:total].cpu().numpy()
+        for off, ln, dst in r[:: max(1, len(r) // 50)].tolist():
+            assert np.array_equal(got[dst:dst + ln], dn[off:off + ln]), (name, shape, "device ranges")
+        assert ctx.range_plan() == (chunks, scratch)
+        plan_bytes = ctx.range_plan_host_bytes()
+        ts = timed([("t_read", read), ("t_read_dev", read_dev), ("t_alt", alt)])
         med = {k: statistics.median(v) for k, v in ts.items()}
         say("  (%s) %6d ranges, %9d bytes, %5d chunks touched, %9d bytes through the scratch" % (shape, len(r), total, chunks, scratch))
-        for k in ("t_read", "t_alt"):
+        for k in ("t_read", "t_read_dev", "t_alt"):
             v = sorted(ts[k])
-            say("       %-7s median %8.3f ms   min %8.3f   p90 %8.3f" % (k, med[k], v[0], v[int(0.9 * (len(v) - 1))]))
-        say("       t_read %s t_alt   %s" % ("<=" if med["t_read"] <= med["t_alt"] else "> ", json.dumps({"input": name[:3], "shape": shape, "t_read": round(med["t_read"], 4), "t_alt": round(med["t_alt"], 4)})))
+            say("       %-10s median %8.3f ms   min %8.3f   p90 %8.3f" % (k, med[k], v[0], v[int(0.9 * (len(v) - 1))]))
+        say("       t_read %s t_alt, t_read_dev %s t_alt   %s" % ("<=" if med["t_read"] <= med["t_alt"] else "> ", "<=" if med["t_read_dev"] <= med["t_alt"] else "> ", json.dumps(
+            {"input": name[:3], "shape": shape, "t_read": round(med["t_read"], 4), "t_read_dev": round(med["t_read_dev"], 4), "t_alt": round(med["t_alt"], 4), "plan_bytes": plan_bytes})))
     rd.close()
 
 
