@@ -163,6 +163,10 @@ int mlz_crc_batch_device(mlz_ctx* ctx, void* stream, const uint8_t* d_base, cons
  * Copies to and from the device overlap the kernels group by group (~256 MiB). */
 #define MLZ_STREAM_ADD_INDEX 1u
 #define MLZ_STREAM_IGNORE_CRC 2u
+/* Block search tables (SPEC_SEARCH.md; the reference's Writer with search tables and WithoutCompression(), table type 1): honoured by
+ * mlz_stream_encode_gather_device and mlz_stream_bound only — mlz_stream_encode returns -MLZ_ERR_ARG when it is set.  See below. */
+#define MLZ_STREAM_SEARCH_TABLES 4u
+#define MLZ_STREAM_SEARCH_MATCH_LEN(m) ((uint32_t)(m) << 8) /* bits 8..11; 0 = the reference's default 6; 1..8 valid; 9..15: -MLZ_ERR_ARG */
 int64_t mlz_stream_bound(uint64_t n, uint32_t block_size, uint32_t flags); /* dst_cap that always suffices */
 int64_t mlz_stream_encode(mlz_ctx* ctx, int level, uint32_t block_size, uint32_t flags, const uint8_t* src, size_t n, uint8_t* dst,
                           size_t dst_cap);
@@ -180,7 +184,16 @@ int64_t mlz_stream_decode(mlz_ctx* ctx, uint32_t flags, const uint8_t* src, size
  * is known (the in-order emit, writer.go:219-272); the runs then travel GPU to GPU into d_dst (hipMemcpyPeerAsync: xGMI between the GPUs of a node; a run
  * already on d_dst's device is framed in place).  No payload crosses PCIe and there is no collective: a gather of variable-length runs to one consumer
  * is n - 1 point-to-point copies, which is also all RCCL's gather would issue.  Bytes are identical to mlz_stream_encode of the concatenated ranges.
- * Synchronous; returns the stream size.  Works on a one-device context too (n_ranges ranges encoded one after the other). */
+ * Synchronous; returns the stream size.  Works on a one-device context too (n_ranges ranges encoded one after the other).
+ * MLZ_STREAM_SEARCH_TABLES (| MLZ_STREAM_SEARCH_MATCH_LEN(M)): the stream also carries the reference's block search tables, type 1 (no prefix), as uncompressed
+ * table chunks: `44 03 00 00 01 M B` directly behind the stream header (B = the bits of block_size - 1, within 8 .. 23) and `45 len24 | 01 M B | R | crc32le |
+ * table` in front of the data chunk of every block that was stored compressed and whose table has at most 70 % of its 2^B bits set (stored blocks get none,
+ * writer.go:528-540).  Bit HashValue(window of M bytes, B, M) is set for every position of the block; the last M - 1 positions take their missing bytes from
+ * the next block (of the next range, too: 7 bytes of it visit the host), zeros beyond it; the stream's last block has no such positions.  The table is folded in
+ * halves R times, while at most a quarter of the folded bits are set and 32 bytes remain.  Two kernels build and fold the tables over the raw blocks in HBM;
+ * 12 more bytes per block visit the host (table bytes or 0, R, CRC).  The seek index names a block by the offset at which its chunks start: its table chunk
+ * when it has one.  mlz_stream_bound with the flag adds 7 + (12 + max(32, 2^(B - 3))) per block.  Without the flag every byte is what it was before the
+ * flag existed.  Out of scope: prefix tables (types 2 to 4), compressed tables (0x46), sidecars and remote references (0x47). */
 int64_t mlz_stream_encode_gather_device(mlz_ctx* ctx, int level, uint32_t block_size, uint32_t flags, const uint8_t* const* d_src, const size_t* src_len,
                                         int n_ranges, uint8_t* d_dst, size_t dst_cap);
 
@@ -259,6 +272,32 @@ int64_t mlz_dev_reader_read_device(mlz_dev_reader* reader, void* stream, uint32_
                                    uint8_t* d_dst, size_t dst_cap, uint64_t* d_starts /* may be NULL */);
 void mlz_dev_reader_close(mlz_dev_reader* reader);
 
+/* Pattern search over a stream that lies in HBM, with the reference's block search tables (SPEC_SEARCH.md; search_table.go, search_index.go) where
+ * the stream has them: table type 1 (no prefix) in uncompressed table chunks (0x45) behind an info chunk (0x44).  Prefix tables (types 2 to 4),
+ * compressed tables (0x46) and remote references (0x47) are stepped over: their blocks count as having no table.
+ *
+ * mlz_dev_reader_search: returns the number of positions p of the decoded stream with decoded[p, p + pattern_len) == pattern (overlapping occurrences
+ *   count; the value may exceed cap); d_offsets (on the handle's device; may be NULL when cap == 0) receives the min(total, cap) smallest positions in
+ *   ascending order and nothing beyond them is written.  `pattern` is host memory, pattern_len 1 .. 256.  -MLZ_ERR_ARG: pattern_len 0 or above 256, a
+ *   NULL pattern, d_offsets NULL with cap > 0 or not on the handle's device.  Synchronous; `stream` as for mlz_dev_reader_read.
+ *   Tables: (M, B) is that of the stream's info chunk, the first 0x44 between the identifier and the first data chunk.  A data chunk's table is the first
+ *   0x45 chunk between the previous data chunk's end and its own start whose type is 1, whose M and B are the stream's, with R <= B - 8, a payload of
+ *   8 + 2^(B - R - 3) bytes and a good CRC (not checked under MLZ_STREAM_IGNORE_CRC).  Anything else — no info chunk, pattern_len < M, a broken CRC —
+ *   means the chunk has no usable table.  The tables are located by a kernel (one lane per data chunk) and their CRCs checked once per handle.
+ *   Plan: the pattern's pattern_len - M + 1 windows are looked up in every table; a chunk is a candidate when all are present in its own table, or
+ *   when its table holds the first j and the next chunk's the others for some 1 <= j (SPEC_SEARCH B.4.1; a next chunk without a usable table or of
+ *   fewer than pattern_len bytes holds everything).  Exactly the candidates and the chunks that hold any of the pattern_len - 1 bytes behind a
+ *   candidate's end are decoded (stored chunks: copied), each once, with their CRCs as in mlz_dev_reader_read; chunks without a usable table are always
+ *   candidates.  Errors as for mlz_dev_reader_read: the first failing decoded chunk in stream order; a broken chunk the plan skips goes unnoticed.
+ *   MLZ_SEARCH_NO_TABLES: every data chunk is decoded and scanned (cross-checks, the timing baseline).
+ *   stats (host, may be NULL) receives: data chunks of the stream, chunks decoded or copied, chunks with a usable table, 0.  mlz_get_counter 10 / 11
+ *   report the second and third for the context's last search.
+ *   Workspace: the decoded chunks go through the ReadSeeker's scratch in groups of about 64 MiB; one bit per decoded byte of the set marks the
+ *   occurrences between the count pass and the write pass (part of mlz_get_counter 4). */
+#define MLZ_SEARCH_NO_TABLES 8u
+int64_t mlz_dev_reader_search(mlz_dev_reader* reader, void* stream, uint32_t flags, const uint8_t* pattern, size_t pattern_len, uint64_t* d_offsets, size_t cap,
+                              uint64_t* stats /* host, may be NULL: 4 values */);
+
 /* ---- tuning / introspection (not part of the reference surface) ---- */
 #define MLZ_OPT_DECODE_ALGO 1  /* 0 = parallel (default), 1 = serial one-wave-per-block, 3 = parallel with every block on the tile path (cross-checks) */
 #define MLZ_OPT_ENCODE_FAR 2   /* 0 = tile-local matches only, 1 = + far matches (default) */
@@ -310,7 +349,9 @@ const char* mlz_timer_name(int idx);
  *            it put into the scratch (chunks decoded straight into d_dst and stored chunks: none).
  * which = 9: bytes of plan data that crossed between host and device, both directions together, during the context's last mlz_dev_reader_read_device:
  *            32 + 32 per touched chunk (32 alone for a refused call or one that touches nothing).  Not counted: the results of the chunks' decode and CRC
- *            (12 bytes per chunk, as in every stream decode) and the one-time upload of a handle's chunk table. */
+ *            (12 bytes per chunk, as in every stream decode) and the one-time upload of a handle's chunk table.
+ * which = 10 / 11: the context's last mlz_dev_reader_search: 10 = chunks it decoded or copied, 11 = chunks with a usable search table (0 when the call
+ *            used none: MLZ_SEARCH_NO_TABLES, no info chunk, a pattern shorter than M). */
 int64_t mlz_get_counter(mlz_ctx* ctx, int which);
 
 #ifdef __cplusplus

@@ -19,7 +19,7 @@ SYMBOLS = [
     "mlz_stream_encode_gather_device", "mlz_release_stream", "mlz_stream_decoded_prefix_len",
     "mlz_stream_decoded_len_device", "mlz_stream_decode_device",
     "mlz_stream_open_device", "mlz_dev_reader_size", "mlz_dev_reader_read", "mlz_dev_reader_close",
-    "mlz_dev_reader_read_device",
+    "mlz_dev_reader_read_device", "mlz_dev_reader_search",
 ]
 
 
@@ -85,5 +85,6 @@ def lib():
     L.mlz_dev_reader_read.argtypes = [vp, vp, u32, vp, sz, vp, sz]; L.mlz_dev_reader_read.restype = i64
     L.mlz_dev_reader_close.argtypes = [vp]; L.mlz_dev_reader_close.restype = None
     L.mlz_dev_reader_read_device.argtypes = [vp, vp, u32, vp, vp, sz, vp, sz, vp]; L.mlz_dev_reader_read_device.restype = i64
+    L.mlz_dev_reader_search.argtypes = [vp, vp, u32, vp, sz, vp, sz, C.POINTER(u64)]; L.mlz_dev_reader_search.restype = i64
     _lib = L
     return L

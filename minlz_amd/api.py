@@ -130,12 +130,14 @@ class Context:
         if r:
             _raise(r, self)
 
-    def stream_encode_gather_device(self, level, block_size, add_index, d_srcs, lens, d_dst, dst_cap):
+    def stream_encode_gather_device(self, level, block_size, add_index, d_srcs, lens, d_dst, dst_cap, search_match_len=None):
         """mlz_stream_encode_gather_device: ranges of one stream resident on the context's devices -> the framed stream in d_dst (device memory).
+        search_match_len: None = no search tables; 0 = block search tables with the reference's default match length (6); 1 .. 8 = with that one.
         Returns the stream size."""
         n = len(d_srcs)
         sp = (C.c_void_p * n)(*d_srcs); sl = (C.c_size_t * n)(*lens)
-        r = _lib.lib().mlz_stream_encode_gather_device(self.handle, level, block_size, STREAM_ADD_INDEX if add_index else 0, sp, sl, n, d_dst, dst_cap)
+        flags = (STREAM_ADD_INDEX if add_index else 0) | (0 if search_match_len is None else STREAM_SEARCH_TABLES | (search_match_len & 15) << 8)
+        r = _lib.lib().mlz_stream_encode_gather_device(self.handle, level, block_size, flags, sp, sl, n, d_dst, dst_cap)
         if r < 0:
             _raise(r, self)
         return int(r)
@@ -188,6 +190,11 @@ class Context:
         L = _lib.lib()
         return int(L.mlz_get_counter(self.handle, 7)), int(L.mlz_get_counter(self.handle, 8))
 
+    def search_plan(self):
+        """(chunks decoded or copied, chunks with a usable search table) of the context's last DeviceReader.search (mlz_get_counter 10, 11)."""
+        L = _lib.lib()
+        return int(L.mlz_get_counter(self.handle, 10)), int(L.mlz_get_counter(self.handle, 11))
+
     def range_plan_host_bytes(self):
         """Bytes of plan data that crossed between host and device, both directions together, in the context's last DeviceReader.read_device
         (mlz_get_counter 9): a header and two records per TOUCHED CHUNK, nothing per range."""
@@ -221,6 +228,20 @@ class DeviceReader:
         if r < 0:
             _raise(r, self.ctx)
         return int(r)
+
+    def search(self, pattern, d_offsets, cap, ignore_crc=False, no_tables=False, stream=None):
+        """mlz_dev_reader_search.  pattern: 1 .. 256 bytes; d_offsets: device address of room for `cap` uint64 (None with cap == 0), which
+        receives the smallest min(total, cap) positions of the pattern in the decoded stream, ascending.
+        -> (total, (data chunks, chunks decoded or copied, chunks with a usable search table))."""
+        if not self.handle:
+            raise ValueError("DeviceReader is closed")
+        p = bytes(pattern)
+        stats = (C.c_uint64 * 4)()
+        flags = (STREAM_IGNORE_CRC if ignore_crc else 0) | (SEARCH_NO_TABLES if no_tables else 0)
+        r = _lib.lib().mlz_dev_reader_search(self.handle, stream, flags, p, len(p), d_offsets, cap, stats)
+        if r < 0:
+            _raise(r, self.ctx)
+        return int(r), (int(stats[0]), int(stats[1]), int(stats[2]))
 
     def close(self):
         if self.handle:
@@ -411,7 +432,7 @@ def decode_batch(blocks, ctx=None):
     return res
 
 
-STREAM_ADD_INDEX, STREAM_IGNORE_CRC = 1, 2
+STREAM_ADD_INDEX, STREAM_IGNORE_CRC, STREAM_SEARCH_TABLES, SEARCH_NO_TABLES = 1, 2, 4, 8
 
 
 def stream_encode(src, level=LevelFastest, block_size=2 << 20, add_index=False, ctx=None):

@@ -24,6 +24,7 @@
 #include "mlz_encode2.hip.inc"
 #include "mlz_decode_serial.hip.inc"
 #include "mlz_toktab.h"
+#include "mlz_stream_search.h"
 #include "mlz_decode.hip.inc"
 #include "mlz_decode_index.hip.inc"
 #include "mlz_decode_exec.hip.inc"
@@ -125,12 +126,15 @@ struct mlz_ctx {
     // encode workspace
     DevBuf d_scratch, d_tile_size, d_tile_out, d_flags, d_far, d_recs, d_piece_cnt, d_farbin;
     bool farbin_attr = false;
+    DevBuf d_stab;               // the device-resident Writer's block search tables: 2^(B - 3) bytes per block of a range, 8 bytes of verdict each
+    bool stab_attr = false;
     // decode workspace
     DevBuf d_dec, d_idx;
     DevBuf d_walk, d_walk_tab;   // the device-resident Reader's chunk walk: exit tables (8 bytes per stream byte) and the chunk table
     DevBuf d_range;              // the device-resident ReadSeeker: where partly wanted chunks of a group are decoded (a group plus one block at the most)
     DevBuf d_rplan;              // mlz_dev_reader_read_device: the plan kernels' workspace (16 bytes per range, 28 per chunk of the stream)
     uint64_t range_plan_host = 0;   // plan bytes that crossed between host and device in the last mlz_dev_reader_read_device (mlz_get_counter 9)
+    uint64_t search_chunks = 0, search_tables = 0;  // the last mlz_dev_reader_search: chunks decoded or copied, chunks with a usable table (mlz_get_counter 10 / 11)
     uint64_t range_chunks = 0, range_scratch = 0;   // the last range read: chunks decoded or copied, decoded bytes that went through d_range (mlz_get_counter 7 / 8)
     DevBuf d_gen_acc;      // two words summed over a call's internal groups by dec_schedule_kernel: general blocks, largest team (mlz_get_counter 2 / 6)
     int general_algo = 0;  // 0 = pointer-jumping pass for general blocks, 1 = tile chain in the exec pass
@@ -969,7 +973,7 @@ void mlz_destroy(mlz_ctx* c) {
     }
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    for (DevBuf* b : {&c->d_place, &c->d_crc, &c->d_crc_tabs, &c->d_crc_tiles, &c->d_prof, &c->d_blocks_k[0], &c->d_blocks_k[1], &c->d_tile_block_k[0], &c->d_tile_block_k[1], &c->d_seg_block_k[0], &c->d_seg_block_k[1], &c->d_scratch, &c->d_tile_size, &c->d_tile_out, &c->d_flags, &c->d_far, &c->d_farbin, &c->d_recs, &c->d_piece_cnt, &c->d_dec, &c->d_idx, &c->d_walk, &c->d_walk_tab, &c->d_range, &c->d_rplan, &c->d_gen_acc, &c->d_in, &c->d_out, &c->d_len})
+    for (DevBuf* b : {&c->d_place, &c->d_crc, &c->d_crc_tabs, &c->d_crc_tiles, &c->d_prof, &c->d_blocks_k[0], &c->d_blocks_k[1], &c->d_tile_block_k[0], &c->d_tile_block_k[1], &c->d_seg_block_k[0], &c->d_seg_block_k[1], &c->d_scratch, &c->d_tile_size, &c->d_tile_out, &c->d_flags, &c->d_far, &c->d_farbin, &c->d_recs, &c->d_piece_cnt, &c->d_dec, &c->d_idx, &c->d_walk, &c->d_walk_tab, &c->d_range, &c->d_rplan, &c->d_stab, &c->d_gen_acc, &c->d_in, &c->d_out, &c->d_len})
         b->release();
     for (int k = 0; k < 2; k++) if (c->pinned_k[k]) (void)hipHostFree(c->pinned_k[k]);
     if (c->pinned2) (void)hipHostFree(c->pinned2);
@@ -1198,13 +1202,14 @@ int64_t mlz_get_counter(mlz_ctx* c, int which) {
     if (which == 3 || which == 4) {  // device workspace this context holds: 3 = encode side, 4 = decode side (grow-only buffers: the high-water mark of the calls so far)
         std::lock_guard<std::mutex> lk(c->mu);
         size_t e = 0, d = 0;
-        for (const DevBuf* b : {&c->d_scratch, &c->d_tile_size, &c->d_tile_out, &c->d_flags, &c->d_far, &c->d_recs, &c->d_piece_cnt, &c->d_farbin}) e += b->cap;
+        for (const DevBuf* b : {&c->d_scratch, &c->d_tile_size, &c->d_tile_out, &c->d_flags, &c->d_far, &c->d_recs, &c->d_piece_cnt, &c->d_farbin, &c->d_stab}) e += b->cap;
         for (const DevBuf* b : {&c->d_dec, &c->d_idx, &c->d_walk, &c->d_walk_tab, &c->d_range, &c->d_rplan}) d += b->cap;
         return int64_t(which == 3 ? e : d);
     }
     if (which == 5) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->gen_fallbacks); }
     if (which == 7 || which == 8) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(which == 7 ? c->range_chunks : c->range_scratch); }
     if (which == 9) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->range_plan_host); }
+    if (which == 10 || which == 11) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(which == 10 ? c->search_chunks : c->search_tables); }
     std::lock_guard<std::mutex> lk(c->q_mu);
     return which == 0 ? int64_t(c->q_batches) : which == 1 ? int64_t(c->q_requests) : -MLZ_ERR_ARG;
 }
@@ -1282,7 +1287,9 @@ int mlz_debug_idxprof(unsigned long long* out) {
 
 }  // extern "C"
 
+#include "mlz_search_tables.hip.inc"
 #include "mlz_stream.hip.inc"
 #include "mlz_stream_walk.hip.inc"
 #include "mlz_stream_ranges.hip.inc"
 #include "mlz_stream_ranges_dev.hip.inc"
+#include "mlz_stream_search.hip.inc"

@@ -1,0 +1,151 @@
+// mlz_search_tables.hip.inc — the device-resident Writer's block search tables (included in mlz_hip.hip in front of mlz_stream.hip.inc, whose
+// stream_gather_range calls search_tables_build).
+//
+// The reference's Writer with search tables (SPEC_SEARCH.md; search_table.go, search_index.go:30-63, unsafe_disabled.go:52-87), table type 1:
+// a bitmap of 2^B bits per block, bit HashValue(window of M bytes, B, M) set for every position of the block — the last M - 1 positions take
+// their missing bytes from the next block, zeros beyond it; the stream's last block has no such positions —, dropped when more than 70 % of
+// its bits are set, else folded in halves while a quarter of the folded bits at the most are set and 32 bytes at the least remain.
+//
+// stab_build_kernel: a workgroup keeps the bitmap (B <= 20: all of it, 128 KiB at the most; above: one slice of 2^20 bits, so 2, 4 or 8
+//   workgroups hash a block's windows and each keeps the bits of its slice) in LDS, where a set bit is one non-returning ds_or; a device-scope
+//   atomic per window would cost several times the whole encode (DESIGN.md section 0).  Few large blocks: several workgroups take parts of a
+//   block and merge into the zeroed table in HBM with non-returning dword atomicOr (words that are not zero only).
+// stab_reduce_kernel: a workgroup per block counts the bits, applies the rules above fold by fold (search_reduce_rule's conditions) and leaves
+//   the table compact at the front of its slot; 8 bytes per block (table bytes or 0, R) go to the host next to the sizes and CRCs.
+
+namespace mlz {
+
+constexpr uint32_t kStabSliceBits = 20, kStabThreads = 1024, kStabPerThread = 8;
+
+struct StabArgs {
+    const uint8_t* src;      // the range
+    uint64_t len;            // its bytes
+    uint64_t tail;           // the bytes behind the range (the next range's first ones), little-endian
+    uint32_t tail_n;         // how many of them exist (0: the range ends the stream)
+    uint32_t bs, cnt, B, M, parts, slices;
+    uint32_t* tabs;          // cnt tables of 2^B bits
+};
+
+// byte q of the range, continued by the next range's first bytes and zeros
+__device__ __forceinline__ uint64_t stab_byte(const StabArgs& a, uint64_t q) {
+    if (q < a.len) return a.src[q];
+    const uint64_t over = q - a.len;
+    return over < a.tail_n ? (a.tail >> (8 * over)) & 0xff : 0;
+}
+
+__global__ __launch_bounds__(kStabThreads) void stab_build_kernel(const StabArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    uint32_t* bits = reinterpret_cast<uint32_t*>(smem);
+    const uint32_t tid = threadIdx.x;
+    const uint32_t part = blockIdx.x % a.parts, slice = (blockIdx.x / a.parts) % a.slices, b = blockIdx.x / (a.parts * a.slices);
+    const uint32_t lbits = a.B < kStabSliceBits ? a.B : kStabSliceBits, words = 1u << (lbits - 5);
+    for (uint32_t i = tid; i < words; i += kStabThreads) bits[i] = 0;
+    __syncthreads();
+    const uint64_t b0 = uint64_t(b) * a.bs;
+    const uint32_t blen = uint32_t(a.len - b0 < a.bs ? a.len - b0 : a.bs);
+    const bool next = b + 1 < a.cnt || a.tail_n != 0;
+    // positions [0, npos): every one with a next block, else those whose window lies inside the block
+    const uint32_t npos = next ? blen : (blen >= a.M ? blen - a.M + 1 : 0);
+    const uint32_t per = ((npos + a.parts - 1) / a.parts + kStabPerThread - 1) & ~(kStabPerThread - 1);
+    const uint32_t p0 = part * per, p1 = p0 + per < npos ? p0 + per : npos;
+    const uint32_t M = a.M, B = a.B;
+    for (uint32_t i = p0 + tid * kStabPerThread; i < p1; i += kStabThreads * kStabPerThread) {
+        const uint64_t q = b0 + i;
+        uint64_t lo, hi;
+        if (q + 16 <= a.len) {
+            __builtin_memcpy(&lo, a.src + q, 8);
+            __builtin_memcpy(&hi, a.src + q + 8, 8);
+        } else {
+            lo = hi = 0;
+            for (uint32_t j = 0; j < 8; j++) { lo |= stab_byte(a, q + j) << (8 * j); hi |= stab_byte(a, q + 8 + j) << (8 * j); }
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < kStabPerThread; j++) {
+            if (i + j >= p1) break;
+            const uint64_t v = j ? (lo >> (8 * j)) | (hi << (64 - 8 * j)) : lo;
+            const uint32_t h = search_hash(v, B, M);
+            if ((h >> kStabSliceBits) == slice) {
+                const uint32_t x = h & ((1u << kStabSliceBits) - 1);
+                atomicOr(&bits[x >> 5], 1u << (x & 31));
+            }
+        }
+    }
+    __syncthreads();
+    uint32_t* out = a.tabs + (size_t(b) << (B - 5)) + (size_t(slice) << (kStabSliceBits - 5));
+    if (a.parts == 1) {
+        for (uint32_t i = tid; i < words; i += kStabThreads) out[i] = bits[i];
+    } else {
+        for (uint32_t i = tid; i < words; i += kStabThreads) {
+            const uint32_t w = bits[i];
+            if (w) atomicOr(&out[i], w);
+        }
+    }
+}
+
+// info[b] = (table bytes or 0, R); the table of 2^(B - R) bits is left at the front of its slot
+__global__ __launch_bounds__(kStabThreads) void stab_reduce_kernel(uint32_t* __restrict__ tabs, uint32_t B, uint2* __restrict__ info) {
+    __shared__ uint32_t wsum[kStabThreads / 64];
+    const uint32_t tid = threadIdx.x, b = blockIdx.x;
+    uint32_t* t = tabs + (size_t(b) << (B - 5));
+    // the workgroup's sum of `mine`
+    auto total = [&](uint32_t mine) -> uint32_t {
+        for (int o = 32; o; o >>= 1) mine += __shfl_down(mine, o);
+        __syncthreads();
+        if ((tid & 63) == 0) wsum[tid >> 6] = mine;
+        __syncthreads();
+        uint32_t s = 0;
+        for (uint32_t w = 0; w < kStabThreads / 64; w++) s += wsum[w];
+        return s;
+    };
+    uint32_t words = 1u << (B - 5), pop = 0;
+    for (uint32_t i = tid; i < words; i += kStabThreads) pop += uint32_t(__popc(t[i]));
+    pop = total(pop);
+    if (search_table_dropped(pop, B)) {
+        if (tid == 0) info[b] = make_uint2(0, 0);
+        return;
+    }
+    uint32_t R = 0;
+    while (words * 4 >= 64) {
+        const uint32_t half = words >> 1;
+        uint32_t p = 0;
+        for (uint32_t i = tid; i < half; i += kStabThreads) p += uint32_t(__popc(t[i] | t[half + i]));
+        p = total(p);
+        if (!search_fold_accepted(p, uint64_t(half) * 32)) break;
+        for (uint32_t i = tid; i < half; i += kStabThreads) t[i] |= t[half + i];
+        __syncthreads();
+        words = half; R++;
+    }
+    if (tid == 0) info[b] = make_uint2(words * 4, R);
+}
+
+}  // namespace mlz
+
+namespace {
+
+// The tables of the cnt blocks of a range (len bytes at d_src), built and reduced on sm: c->d_stab then holds cnt slots of 2^(B - 3) bytes, each
+// with its block's table at the front, and behind them (at *info_off) cnt records (table bytes or 0, R).  tail: the tail_n <= 7 bytes that
+// follow the range in the stream (the next range's first ones).  Caller holds c->mu.
+int search_tables_build(mlz_ctx* c, hipStream_t sm, const uint8_t* d_src, size_t len, uint32_t bs, size_t cnt, uint32_t M, uint32_t B, uint64_t tail, uint32_t tail_n,
+                        size_t* info_off) {
+    const size_t slot = size_t(1) << (B - 3);
+    *info_off = cnt * slot;
+    HIPCHK(c, c->d_stab.ensure(cnt * slot + cnt * sizeof(uint2) + 64));
+    const uint32_t lbits = std::min(B, mlz::kStabSliceBits), lds = 1u << (lbits - 3);
+    if (!c->stab_attr) {
+        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(mlz::stab_build_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 1u << (mlz::kStabSliceBits - 3)));
+        c->stab_attr = true;
+    }
+    mlz::StabArgs a{};
+    a.src = d_src; a.len = len; a.tail = tail; a.tail_n = tail_n; a.bs = bs; a.cnt = uint32_t(cnt); a.B = B; a.M = M;
+    a.slices = 1u << (B - lbits);
+    // few large blocks: parts of at least 64 KiB, until the device has about two workgroups per CU
+    const uint64_t want = std::max<uint64_t>(1, uint64_t(2 * std::max(c->n_cus, 1)) / (cnt * a.slices));
+    a.parts = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(want, bs >> 16)));
+    a.tabs = c->d_stab.as<uint32_t>();
+    if (a.parts > 1) HIPCHK(c, hipMemsetAsync(a.tabs, 0, cnt * slot, sm));
+    hipLaunchKernelGGL(mlz::stab_build_kernel, dim3(uint32_t(cnt * a.slices * a.parts)), dim3(mlz::kStabThreads), lds, sm, a);
+    hipLaunchKernelGGL(mlz::stab_reduce_kernel, dim3(uint32_t(cnt)), dim3(mlz::kStabThreads), 0, sm, a.tabs, B, reinterpret_cast<uint2*>(c->d_stab.as<uint8_t>() + *info_off));
+    return 0;
+}
+
+}  // namespace

@@ -130,9 +130,18 @@ int ensure_stream_objects(mlz_ctx* c, size_t n_events, size_t pinned_bytes) {
     return 0;
 }
 
-size_t stream_bound(uint64_t n, uint32_t bs, bool add_index) {
+size_t stream_bound(uint64_t n, uint32_t bs, bool add_index, bool search_tables = false) {
     const uint64_t nblk = (n + bs - 1) / bs;
-    return size_t(10 + nblk * (8 + 5) + n + 4 + 10 + (add_index ? SeekIndex::bound(size_t(nblk)) : 0));
+    // search tables: the info chunk and, per block, a table chunk with the unreduced table
+    const uint64_t tables = search_tables ? 7 + nblk * mlz::search_chunk_bound(mlz::search_table_bits(bs)) : 0;
+    return size_t(10 + nblk * (8 + 5) + n + 4 + 10 + (add_index ? SeekIndex::bound(size_t(nblk)) : 0) + tables);
+}
+
+// MLZ_STREAM_SEARCH_TABLES in `flags`: the match length M (bits 8 .. 11, 0 = the reference's default), 0 when the flag is clear, -1 for 9 .. 15
+int stream_search_match_len(uint32_t flags) {
+    if (!(flags & MLZ_STREAM_SEARCH_TABLES)) return 0;
+    const uint32_t m = (flags >> 8) & 15;
+    return m == 0 ? int(mlz::kSearchDefaultMatchLen) : m <= 8 ? int(m) : -1;
 }
 
 // Chunk bodies of a group into a page-locked destination: one workgroup per 64 KiB piece copies from the encode output in HBM to
@@ -356,12 +365,25 @@ int64_t stream_encode_over(mlz_ctx* const* workers, size_t k, int level, uint32_
 
 // ---- the device-resident Writer over several devices: sources in each device's HBM, the framed stream gathered GPU to GPU ----
 // Chunk bodies and 8-byte chunk headers into a run of chunks: desc.pad selects the source (0 = the encoder's output, 1 = the raw block, for
-// stored chunks); a header is eight literal bytes at a destination offset.
+// stored chunks; stream_place3_kernel: 2 = the block's search table); a header is eight literal bytes at a destination offset (a table chunk's: twelve).
 struct HdrDesc { uint64_t dst_off; uint8_t b[8]; };
 __global__ __launch_bounds__(256) void stream_place2_kernel(const uint8_t* __restrict__ d_enc, const uint8_t* __restrict__ d_raw, uint8_t* __restrict__ run,
                                                             const PlaceDesc* __restrict__ descs) {
     const PlaceDesc d = descs[blockIdx.x];
     mlz::wg_copy(run + d.dst_off, (d.pad ? d_raw : d_enc) + d.src_off, d.len, threadIdx.x, 256);
+}
+struct TabHdrDesc { uint64_t dst_off; uint8_t b[12]; uint32_t pad; };
+__global__ __launch_bounds__(256) void stream_place3_kernel(const uint8_t* __restrict__ d_enc, const uint8_t* __restrict__ d_raw, const uint8_t* __restrict__ d_tab,
+                                                            uint8_t* __restrict__ run, const PlaceDesc* __restrict__ descs) {
+    const PlaceDesc d = descs[blockIdx.x];
+    mlz::wg_copy(run + d.dst_off, (d.pad == 2 ? d_tab : d.pad ? d_raw : d_enc) + d.src_off, d.len, threadIdx.x, 256);
+}
+__global__ __launch_bounds__(64) void stream_tabhdr_kernel(uint8_t* __restrict__ run, const TabHdrDesc* __restrict__ hd, uint32_t n) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const TabHdrDesc h = hd[i];
+#pragma unroll
+    for (int k = 0; k < 12; k++) run[h.dst_off + k] = h.b[k];
 }
 __global__ __launch_bounds__(64) void stream_hdr_kernel(uint8_t* __restrict__ run, const HdrDesc* __restrict__ hd, uint32_t n) {
     const uint32_t i = blockIdx.x * 64 + threadIdx.x;
@@ -375,21 +397,27 @@ __global__ __launch_bounds__(64) void stream_hdr_kernel(uint8_t* __restrict__ ru
 // block) to the host, the run of chunks framed on the device, then moved to its place in d_dst on device dst_dev (the same device: framed in
 // place; another one: hipMemcpyPeerAsync, which rides xGMI between the GPUs of a node).  Payload never visits the host.
 int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d_src, size_t len, size_t b0, uint8_t* d_dst, int dst_dev, bool have_header,
-                            StreamEncShared* sh, size_t j, uint32_t* framed) {
+                            StreamEncShared* sh, size_t j, uint32_t* framed, uint32_t search_m = 0 /* > 0: search tables of this match length */, uint64_t tail = 0,
+                            uint32_t tail_n = 0 /* the bytes that follow the range in the stream, 7 at the most */) {
     HIPCHK(c, hipSetDevice(c->device));
     const size_t cnt = (len + bs - 1) / bs;
     if (cnt == 0) { sh->publish(j, 0); return 0; }
+    const uint32_t search_b = mlz::search_table_bits(bs);
+    const size_t tab_slot = size_t(1) << (search_b - 3);
     const size_t ostride = (size_t(bs) + 16 + 63) & ~size_t(63);
     HIPCHK(c, c->d_out.ensure(cnt * ostride + 64));
     HIPCHK(c, c->d_len.ensure(sizeof(int64_t) * cnt));
     HIPCHK(c, c->d_crc.ensure(sizeof(uint32_t) * cnt + 64));
-    const size_t max_pieces = cnt * ((size_t(bs) + kPlacePiece - 1) / kPlacePiece + 1);
-    int r = ensure_stream_objects(c, 1, cnt * 12 + 128 + max_pieces * sizeof(PlaceDesc) + cnt * sizeof(HdrDesc));
+    const size_t max_pieces = cnt * ((size_t(bs) + kPlacePiece - 1) / kPlacePiece + 1 + (search_m ? (tab_slot + kPlacePiece - 1) / kPlacePiece : 0));
+    int r = ensure_stream_objects(c, 1, cnt * 12 + 128 + max_pieces * sizeof(PlaceDesc) + cnt * sizeof(HdrDesc) + (search_m ? cnt * (12 + sizeof(TabHdrDesc)) + 64 : 0));
     if (r) return r;
     int64_t* h_len = static_cast<int64_t*>(c->pinned2);
     uint32_t* h_crc = reinterpret_cast<uint32_t*>(h_len + cnt);
     PlaceDesc* h_place = reinterpret_cast<PlaceDesc*>((reinterpret_cast<uintptr_t>(h_crc + cnt) + 63) & ~uintptr_t(63));
     HdrDesc* h_hdr = reinterpret_cast<HdrDesc*>(h_place + max_pieces);
+    TabHdrDesc* h_tabhdr = reinterpret_cast<TabHdrDesc*>(h_hdr + cnt);                // search tables: a table chunk's header per block,
+    uint2* h_tabinfo = reinterpret_cast<uint2*>(h_tabhdr + (search_m ? cnt : 0));      // (table bytes or 0, R)
+    uint32_t* h_tabcrc = reinterpret_cast<uint32_t*>(h_tabinfo + (search_m ? cnt : 0));   // and the table's CRC
     std::vector<mlz_block_desc> desc(cnt);
     for (size_t i = 0; i < cnt; i++) {
         desc[i].src_off = i * size_t(bs); desc[i].src_len = std::min<size_t>(bs, len - i * size_t(bs));
@@ -401,17 +429,56 @@ int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d
     if (r) return r;
     r = crc_device_locked(c, sm, d_src, desc.data(), int(cnt), c->d_crc.as<uint32_t>());
     if (r) return r;
+    size_t tabinfo_off = 0;
+    if (search_m) {
+        r = search_tables_build(c, sm, d_src, len, bs, cnt, search_m, search_b, tail, tail_n, &tabinfo_off);
+        if (r) return r;
+        HIPCHK(c, hipMemcpyAsync(h_tabinfo, c->d_stab.as<uint8_t>() + tabinfo_off, sizeof(uint2) * cnt, hipMemcpyDeviceToHost, sm));
+    }
     HIPCHK(c, hipMemcpyAsync(h_len, c->d_len.p, sizeof(int64_t) * cnt, hipMemcpyDeviceToHost, sm));
     HIPCHK(c, hipMemcpyAsync(h_crc, c->d_crc.p, sizeof(uint32_t) * cnt, hipMemcpyDeviceToHost, sm));
     HIPCHK(c, hipStreamSynchronize(sm));
-    // the run's layout: [type][len24][crc][body] per block (see stream_encode_groups)
-    size_t run = 0, n_place = 0;
+    size_t n_tabs = 0;
+    if (search_m) {
+        // a table goes in front of a block that was stored compressed (writer.go:528-540); its CRC is the stream's, over the table's bytes
+        HIPCHK(c, hipGetLastError());
+        std::vector<mlz_block_desc> tdesc;
+        for (size_t i = 0; i < cnt; i++) {
+            if (h_len[i] < 0) return h_len[i];
+            if (h_len[i] == int64_t(desc[i].src_len) + 2) h_tabinfo[i].x = 0;
+            if (h_tabinfo[i].x) tdesc.push_back(mlz_block_desc{i * tab_slot, h_tabinfo[i].x, 0, 0});
+        }
+        n_tabs = tdesc.size();
+        if (n_tabs) {
+            HIPCHK(c, c->d_crc.ensure(sizeof(uint32_t) * (cnt + n_tabs) + 64));
+            r = crc_device_locked(c, sm, c->d_stab.as<uint8_t>(), tdesc.data(), int(n_tabs), c->d_crc.as<uint32_t>());
+            if (r) return r;
+            HIPCHK(c, hipMemcpyAsync(h_tabcrc, c->d_crc.p, sizeof(uint32_t) * n_tabs, hipMemcpyDeviceToHost, sm));
+            HIPCHK(c, hipStreamSynchronize(sm));
+        }
+    }
+    // the run's layout: [type][len24][crc][body] per block (see stream_encode_groups), a block's table chunk in front of it
+    size_t run = 0, n_place = 0, tab_at = 0;
     for (size_t i = 0; i < cnt; i++) {
         const int64_t elen = h_len[i];
         if (elen < 0) return elen;
         const size_t bl = size_t(desc[i].src_len);
         const bool stored = elen == int64_t(bl) + 2;
         const size_t body = stored ? bl : size_t(elen) - 1, chunk_len = 4 + body;
+        framed[b0 + i] = 0;
+        if (search_m && h_tabinfo[i].x) {   // 45 len24 | 01 M B | R | crc32le | table
+            const uint32_t tb = h_tabinfo[i].x, tlen = 8 + tb;
+            TabHdrDesc& th = h_tabhdr[tab_at];
+            th.dst_off = run; th.pad = 0;
+            th.b[0] = mlz::kChunkSearchTable; th.b[1] = uint8_t(tlen); th.b[2] = uint8_t(tlen >> 8); th.b[3] = uint8_t(tlen >> 16);
+            th.b[4] = 1; th.b[5] = uint8_t(search_m); th.b[6] = uint8_t(search_b); th.b[7] = uint8_t(h_tabinfo[i].y);
+            std::memcpy(th.b + 8, &h_tabcrc[tab_at], 4);
+            for (size_t q = 0; q < tb; q += kPlacePiece)
+                h_place[n_place++] = PlaceDesc{i * tab_slot + q, run + 12 + q, uint32_t(std::min<size_t>(kPlacePiece, tb - q)), 2u};
+            tab_at++;
+            framed[b0 + i] = 12 + tb;
+            run += 12 + tb;
+        }
         HdrDesc& h = h_hdr[i];
         h.dst_off = run;
         h.b[0] = stored ? kChunkUncompressed : kChunkMinLZ;
@@ -420,23 +487,28 @@ int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d
         const size_t from = stored ? desc[i].src_off : desc[i].dst_off + 1;
         for (size_t q = 0; q < body; q += kPlacePiece)
             h_place[n_place++] = PlaceDesc{from + q, run + 8 + q, uint32_t(std::min<size_t>(kPlacePiece, body - q)), stored ? 1u : 0u};
-        framed[b0 + i] = uint32_t(8 + body);
+        framed[b0 + i] += uint32_t(8 + body);
         run += 8 + body;
     }
     sh->publish(j, int64_t(run));
     const int64_t before = sh->base_of(j);
     if (before < 0) return -MLZ_ERR_HIP;
-    const size_t base = (have_header ? 10 : 0) + size_t(before);
+    const size_t base = (have_header ? (search_m ? 17 : 10) : 0) + size_t(before);
     // frame the run: in place when d_dst is on this device, else in a local buffer that then travels
     const bool local = c->device == dst_dev;
     uint8_t* d_run = d_dst + base;
     if (!local) { HIPCHK(c, c->d_in.ensure(run + 64)); d_run = c->d_in.as<uint8_t>(); }
-    HIPCHK(c, c->d_place.ensure(n_place * sizeof(PlaceDesc) + cnt * sizeof(HdrDesc) + 64));
+    HIPCHK(c, c->d_place.ensure(n_place * sizeof(PlaceDesc) + cnt * sizeof(HdrDesc) + n_tabs * sizeof(TabHdrDesc) + 64));
     PlaceDesc* d_place = c->d_place.as<PlaceDesc>();
     HdrDesc* d_hdr = reinterpret_cast<HdrDesc*>(d_place + n_place);
     if (n_place) HIPCHK(c, hipMemcpyAsync(d_place, h_place, n_place * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
     HIPCHK(c, hipMemcpyAsync(d_hdr, h_hdr, cnt * sizeof(HdrDesc), hipMemcpyHostToDevice, sm));
-    if (n_place) hipLaunchKernelGGL(stream_place2_kernel, dim3(uint32_t(n_place)), dim3(256), 0, sm, d_out, d_src, d_run, d_place);
+    if (search_m) {
+        TabHdrDesc* d_tabhdr = reinterpret_cast<TabHdrDesc*>(d_hdr + cnt);
+        if (n_tabs) HIPCHK(c, hipMemcpyAsync(d_tabhdr, h_tabhdr, n_tabs * sizeof(TabHdrDesc), hipMemcpyHostToDevice, sm));
+        if (n_place) hipLaunchKernelGGL(stream_place3_kernel, dim3(uint32_t(n_place)), dim3(256), 0, sm, d_out, d_src, c->d_stab.as<uint8_t>(), d_run, d_place);
+        if (n_tabs) hipLaunchKernelGGL(stream_tabhdr_kernel, dim3(uint32_t((n_tabs + 63) / 64)), dim3(64), 0, sm, d_run, d_tabhdr, uint32_t(n_tabs));
+    } else if (n_place) hipLaunchKernelGGL(stream_place2_kernel, dim3(uint32_t(n_place)), dim3(256), 0, sm, d_out, d_src, d_run, d_place);
     hipLaunchKernelGGL(stream_hdr_kernel, dim3(uint32_t((cnt + 63) / 64)), dim3(64), 0, sm, d_run, d_hdr, uint32_t(cnt));
     if (!local) HIPCHK(c, hipMemcpyPeerAsync(d_dst + base, dst_dev, d_run, c->device, run, sm));
     HIPCHK(c, hipStreamSynchronize(sm));
@@ -705,13 +777,15 @@ extern "C" {
 
 int64_t mlz_stream_bound(uint64_t n, uint32_t block_size, uint32_t flags) {
     if (block_size < kMinStreamBlock || block_size > kMaxBlockSize) return -MLZ_ERR_ARG;
-    return int64_t(stream_bound(n, block_size, (flags & MLZ_STREAM_ADD_INDEX) != 0));
+    if (stream_search_match_len(flags) < 0) return -MLZ_ERR_ARG;
+    return int64_t(stream_bound(n, block_size, (flags & MLZ_STREAM_ADD_INDEX) != 0, (flags & MLZ_STREAM_SEARCH_TABLES) != 0));
 }
 
 int64_t mlz_stream_encode(mlz_ctx* c, int level, uint32_t block_size, uint32_t flags, const uint8_t* src, size_t n, uint8_t* dst, size_t dst_cap) {
     if (!c || (!src && n) || !dst) return -MLZ_ERR_ARG;
     if (block_size < kMinStreamBlock || block_size > kMaxBlockSize) return -MLZ_ERR_ARG;  // writer.go:1238-1246
     if (!valid_level(level)) return -MLZ_ERR_INVALID_LEVEL;
+    if (flags & MLZ_STREAM_SEARCH_TABLES) return -MLZ_ERR_ARG;   // search tables: the device-resident Writer only
     Workers w(c);
     return stream_encode_over(w.list, w.n, level, block_size, (flags & MLZ_STREAM_ADD_INDEX) != 0, src, n, dst, dst_cap);
 }
@@ -722,6 +796,8 @@ int64_t mlz_stream_encode_gather_device(mlz_ctx* c, int level, uint32_t block_si
     if (block_size < kMinStreamBlock || block_size > kMaxBlockSize) return -MLZ_ERR_ARG;
     if (!valid_level(level)) return -MLZ_ERR_INVALID_LEVEL;
     const bool add_index = (flags & MLZ_STREAM_ADD_INDEX) != 0;
+    const int search_m = stream_search_match_len(flags);
+    if (search_m < 0) return -MLZ_ERR_ARG;
     Workers w(c);
     const size_t k = size_t(n_ranges);
     // every range on the device that holds it; all but the last are whole blocks (a short block ends a stream)
@@ -747,7 +823,18 @@ int64_t mlz_stream_encode_gather_device(mlz_ctx* c, int level, uint32_t block_si
     hipPointerAttribute_t dat;
     if (hipPointerGetAttributes(&dat, d_dst) != hipSuccess || dat.type != hipMemoryTypeDevice) { (void)hipGetLastError(); return -MLZ_ERR_ARG; }
     const int dst_dev = dat.device;
-    if (dst_cap < stream_bound(n, block_size, add_index)) return -MLZ_ERR_DST_TOO_SMALL;
+    if (dst_cap < stream_bound(n, block_size, add_index, search_m > 0)) return -MLZ_ERR_DST_TOO_SMALL;
+    // search tables: a range's last block indexes windows that run into the next non-empty range, whose first bytes (7 at the most) the host hands over
+    std::vector<uint64_t> next_bytes(k, 0);
+    std::vector<uint32_t> next_n(k, 0);
+    if (search_m > 1)
+        for (size_t j = 0; j + 1 < k; j++) {
+            size_t q = j + 1;
+            while (q < k && !src_len[q]) q++;
+            if (q == k || !src_len[j]) continue;
+            next_n[j] = uint32_t(std::min<size_t>(7, src_len[q]));
+            if (hipSetDevice(own[q]->device) != hipSuccess || hipMemcpy(&next_bytes[j], d_src[q], next_n[j], hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
+        }
     const size_t nblk = first[k];
     std::vector<uint32_t> framed(nblk, 0);
     StreamEncShared sh(k);
@@ -767,7 +854,7 @@ int64_t mlz_stream_encode_gather_device(mlz_ctx* c, int level, uint32_t block_si
         mlz_ctx* kc = ctxs[q];
         std::lock_guard<std::mutex> lk(kc->mu);
         for (size_t j : by_ctx[q]) {
-            rcs[j] = stream_gather_range(kc, level, block_size, d_src[j], src_len[j], first[j], d_dst, dst_dev, n > 0, &sh, j, framed.data());
+            rcs[j] = stream_gather_range(kc, level, block_size, d_src[j], src_len[j], first[j], d_dst, dst_dev, n > 0, &sh, j, framed.data(), uint32_t(search_m), next_bytes[j], next_n[j]);
             if (rcs[j]) { sh.fail(); (void)hipStreamSynchronize(kc->stream); }
         }
     };
@@ -786,12 +873,17 @@ int64_t mlz_stream_encode_gather_device(mlz_ctx* c, int level, uint32_t block_si
     SeekIndex index;
     index.reset(block_size);
     size_t o = 0;
-    uint8_t head[10];
+    uint8_t head[17];
     if (n > 0) {
         std::memcpy(head, kMagicChunk, 9);
         head[9] = uint8_t((32 - __builtin_clz(block_size - 1)) - 10);
-        HIPCHK(c0, hipMemcpy(d_dst, head, 10, hipMemcpyHostToDevice));
         o = 10;
+        if (search_m) {   // the info chunk: 44 03 00 00 | 01 M B
+            const uint8_t info[7] = {mlz::kChunkSearchInfo, 3, 0, 0, 1, uint8_t(search_m), uint8_t(mlz::search_table_bits(block_size))};
+            std::memcpy(head + 10, info, 7);
+            o = 17;
+        }
+        HIPCHK(c0, hipMemcpy(d_dst, head, o, hipMemcpyHostToDevice));
         index.add(0, 0);
     }
     for (size_t i = 0; i < nblk; i++) { index.add(int64_t(o), int64_t(i * size_t(block_size))); o += framed[i]; }

@@ -63,6 +63,15 @@ struct mlz_dev_reader {
     int64_t size = 0;
     std::vector<StreamChunk> chunks;          // the data chunks: body offset and length, decoded length, CRC, type, output offset
     std::vector<mlz::RangeChunk> rchunks;     // the planner's view of them
+    // mlz_dev_reader_search: (M, B) of the stream's info chunk and every data chunk's search table, found by the first search of the handle
+    // ([0]: table CRCs checked, [1]: under MLZ_STREAM_IGNORE_CRC)
+    struct SearchTables {
+        bool ready = false, info = false;
+        uint32_t M = 0, B = 0;
+        size_t usable = 0;
+        void* d_tabs = nullptr;               // mlz::SearchTab per data chunk, device memory the handle owns
+        std::vector<mlz::SearchTab> tabs;
+    } search[2];
 };
 
 namespace {
@@ -170,9 +179,10 @@ int64_t mlz_dev_reader_read(mlz_dev_reader* rd, void* stream, uint32_t flags, co
 }
 
 void mlz_dev_reader_close(mlz_dev_reader* rd) {
-    if (rd && rd->d_chunks) {
+    if (rd && (rd->d_chunks || rd->search[0].d_tabs || rd->search[1].d_tabs)) {
         std::lock_guard<std::mutex> lk(rd->ctx->mu);
-        if (hipSetDevice(rd->ctx->device) == hipSuccess) (void)hipFree(rd->d_chunks);
+        if (hipSetDevice(rd->ctx->device) == hipSuccess)
+            for (void* p : {rd->d_chunks, rd->search[0].d_tabs, rd->search[1].d_tabs}) if (p) (void)hipFree(p);
     }
     delete rd;
 }

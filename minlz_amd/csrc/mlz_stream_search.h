@@ -1,0 +1,182 @@
+// mlz_stream_search.h — what the block search tables' writer, the device-resident pattern search (mlz_stream_search.hip.inc) and their host
+// check (tools/stream_search_check.cpp) share: the table hash (SPEC_SEARCH.md 3.1), the size and the bytes of a table chunk (2.0, 2.1, 3.2),
+// the probe of one table and the rule that turns the probes of all chunks into the set of chunks to decode (Appendix B.4.1).
+// Plain C++: compiles for the host alone and for gfx950.  Table type 1 (no prefix), uncompressed table chunks (0x45) only.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+#if defined(__HIPCC__)
+#define MLZ_SEARCH_HD __host__ __device__ inline
+#else
+#define MLZ_SEARCH_HD inline
+#endif
+
+namespace mlz {
+
+constexpr uint8_t kChunkSearchInfo = 0x44, kChunkSearchTable = 0x45;
+constexpr uint32_t kSearchMaxPattern = 256, kSearchDefaultMatchLen = 6;
+constexpr uint32_t kSearchNoTable = 0xffffffffu;
+
+// A data chunk's table as the search keeps it: where its bytes lie in the stream, their number, the reductions (kSearchNoTable: no usable
+// table) and the CRC its chunk states.
+struct SearchTab { uint64_t off; uint32_t bytes, R, crc, pad; };
+static_assert(sizeof(SearchTab) == 24, "a record shared with the kernels");
+
+// HashValue(val, tableSize, matchLen): `val` holds the window's bytes little-endian (bytes beyond matchLen are ignored).
+MLZ_SEARCH_HD uint32_t search_hash(uint64_t val, uint32_t B, uint32_t M) {
+    switch (M) {
+    case 1: return uint32_t(val & 0xff);
+    case 2: return B >= 16 ? uint32_t(val & 0xffff) : (uint32_t(val << 16) * 40503u) >> (32 - B);
+    case 3: return (uint32_t(val << 8) * 506832829u) >> (32 - B);
+    case 4: return (uint32_t(val) * 2654435761u) >> (32 - B);
+    case 5: return uint32_t(((val << 24) * 889523592379ull) >> (64 - B));
+    case 6: return uint32_t(((val << 16) * 227718039650203ull) >> (64 - B));
+    case 7: return uint32_t(((val << 8) * 58295818150454627ull) >> (64 - B));
+    default: return uint32_t((val * 0xcf1bbcdcb7a56463ull) >> (64 - B));
+    }
+}
+
+// autoTableSize: bits of (block_size - 1), within 8 .. 23.
+MLZ_SEARCH_HD uint32_t search_table_bits(uint32_t block_size) {
+    uint32_t b = 0;
+    for (uint32_t v = block_size - 1; v; v >>= 1) b++;
+    return b < 8 ? 8 : b > 23 ? 23 : b;
+}
+
+// Bytes a table chunk takes at the most: 4 (chunk header) + 8 (type, M, B, R, CRC) + the unreduced table.
+MLZ_SEARCH_HD uint64_t search_chunk_bound(uint32_t B) { return 12 + (uint64_t(1) << (B - 3)); }
+
+// The payload of a 0x45 chunk (`clen` bytes at p, all readable): the reductions R of a type 1 table of (M, B) whose length fits, else -1.
+// The table's bytes are p[8 .. clen), its CRC the little-endian word at p + 4.
+MLZ_SEARCH_HD int search_table_reductions(const uint8_t* p, uint32_t clen, uint32_t M, uint32_t B) {
+    if (clen < 8 + 32 || p[0] != 1 || p[1] != M || p[2] != B) return -1;
+    const uint32_t R = p[3];
+    if (R > B - 8) return -1;
+    return clen - 8 == (1u << (B - R - 3)) ? int(R) : -1;
+}
+
+// The payload of a 0x44 chunk: (M, B) of a type 1 stream, else false.
+MLZ_SEARCH_HD bool search_info(const uint8_t* p, uint32_t clen, uint32_t* M, uint32_t* B) {
+    if (clen < 3 || p[0] != 1 || p[1] < 1 || p[1] > 8 || p[2] < 8 || p[2] > 23) return false;
+    *M = p[1]; *B = p[2];
+    return true;
+}
+
+// One table against the pattern's windows (h[i] = the hash of window i at B bits; bits = B - R of this table): a = the leading windows
+// present, s = the trailing ones.  Both are nw when all are present.
+MLZ_SEARCH_HD void search_probe(const uint8_t* table, uint32_t bits, const uint32_t* h, uint32_t nw, uint32_t* a, uint32_t* s) {
+    const uint32_t mask = (1u << bits) - 1;
+    auto has = [&](uint32_t i) { const uint32_t x = h[i] & mask; return (table[x >> 3] >> (x & 7)) & 1; };
+    uint32_t lead = 0, trail = 0;
+    while (lead < nw && has(lead)) lead++;
+    if (lead == nw) { *a = *s = nw; return; }
+    while (trail < nw && has(nw - 1 - trail)) trail++;
+    *a = lead; *s = trail;
+}
+
+// Chunk k may hold the start of an occurrence: all windows in its own table, or a split of them between its table (the first j, 1 <= j < nw,
+// tail windows included) and the next chunk's (the last nw - j).  s_next = nw when the next chunk has no usable table or decodes to fewer
+// bytes than the pattern has.
+MLZ_SEARCH_HD bool search_candidate(uint32_t a_k, uint32_t s_next, uint32_t nw, bool last) {
+    if (a_k == nw) return true;
+    if (last) return false;
+    const uint32_t lo = nw - s_next > 1 ? nw - s_next : 1, hi = a_k < nw - 1 ? a_k : nw - 1;
+    return lo <= hi;
+}
+
+// The decoded set: every candidate plus the chunks behind it that hold any of the L - 1 bytes after its end.  a[k], s[k]: the probe of
+// chunk k (nw, nw without a usable table); n[k] > 0: its decoded bytes.  take[k] = 1 for the chunks to decode.  Returns their number.
+template <class A, class S, class N>
+size_t search_decoded_set(size_t nck, A a_of, S s_of, N n_of, uint32_t nw, uint32_t L, uint8_t* take) {
+    for (size_t k = 0; k < nck; k++) take[k] = 0;
+    for (size_t k = 0; k < nck; k++) {
+        if (!n_of(k)) continue;   // (a chunk of no bytes holds nothing)
+        const bool last = k + 1 == nck;
+        const uint32_t s_next = last ? 0 : (n_of(k + 1) < L ? nw : s_of(k + 1));
+        if (!search_candidate(a_of(k), s_next, nw, last)) continue;
+        take[k] = 1;
+        uint64_t need = L - 1;
+        for (size_t j = k + 1; j < nck && need; j++) {
+            const uint64_t nj = n_of(j);
+            if (nj) take[j] = 1;
+            need = nj >= need ? 0 : need - nj;
+        }
+    }
+    size_t cnt = 0;
+    for (size_t k = 0; k < nck; k++) cnt += take[k];
+    return cnt;
+}
+
+// ---- the decoded set in the scratch ----
+// The chunks of the decoded set ("jobs", in stream order) are decoded group by group into one scratch buffer that every group reuses.  A group
+// starts behind kSearchPad bytes of room; chunks that are neighbours in the decoded stream lie side by side, so a run of neighbours is one
+// piece of decoded stream, and where a run goes on in the next group its last L - 1 bytes are copied in front of that group's first chunk.
+// A tile is up to kSearchTile start positions of one run: scratch[src_off + i, + L) is compared for i < count, position i is decoded byte
+// gpos + i.  Every start position of every run whose L bytes lie inside the run is in exactly one tile, in ascending order.
+constexpr uint32_t kSearchTile = 8192, kSearchTileWords = kSearchTile / 64, kSearchPad = 256;
+struct SearchTile { int64_t src_off; uint64_t gpos; uint32_t count, pad; };
+static_assert(sizeof(SearchTile) == 24 && kSearchPad >= kSearchMaxPattern, "a record shared with the kernels; the carried bytes fit in front of a group");
+struct SearchLayout {
+    std::vector<uint64_t> at;            // per job: where its chunk lies in the scratch
+    std::vector<SearchTile> tiles;       // group by group
+    std::vector<size_t> tile_end;        // per group: one past its last tile
+    std::vector<uint32_t> carry;         // per group: bytes that go from its end, scratch[used - carry, used), to scratch[kSearchPad - carry, kSearchPad)
+    std::vector<uint64_t> used;          // per group: the end of its last chunk in the scratch
+    uint64_t scratch_max = 0;
+};
+// gend[g]: one past the last job of group g; out_off_of(j), n_of(j): job j's place in the decoded stream and its decoded bytes
+template <class Off, class N>
+void search_layout(size_t n_jobs, const std::vector<size_t>& gend, Off out_off_of, N n_of, uint32_t L, SearchLayout* lay) {
+    const size_t ng = gend.size();
+    lay->at.assign(n_jobs, 0); lay->tiles.clear(); lay->tile_end.assign(ng, 0); lay->carry.assign(ng, 0); lay->used.assign(ng, 0); lay->scratch_max = 0;
+    auto adjacent = [&](size_t i) { return out_off_of(i - 1) + n_of(i - 1) == out_off_of(i); };
+    uint64_t run_have = 0;   // bytes of the current run that lie in the scratch in front of the next chunk
+    for (size_t g = 0, j0 = 0; g < ng; j0 = gend[g++]) {
+        const size_t j1 = gend[g];
+        uint64_t o = kSearchPad;
+        for (size_t j = j0; j < j1;) {
+            size_t e = j + 1;   // a part: jobs [j, e) are neighbours
+            while (e < j1 && adjacent(e)) e++;
+            if (!(j == j0 && j0 > 0 && adjacent(j0))) run_have = 0;
+            const uint64_t ps = o, gp = out_off_of(j);
+            for (size_t i = j; i < e; i++) { lay->at[i] = o; o += n_of(i); }
+            const uint64_t lower = ps - (run_have < L - 1 ? run_have : L - 1);
+            if (o - lower >= L)
+                for (uint64_t s0 = lower, upper = o - L + 1; s0 < upper; s0 += kSearchTile)
+                    lay->tiles.push_back(SearchTile{int64_t(s0), gp + s0 - ps, uint32_t(upper - s0 < kSearchTile ? upper - s0 : kSearchTile), 0});
+            run_have += o - ps;
+            j = e;
+        }
+        lay->used[g] = o;
+        if (j1 < n_jobs && adjacent(j1)) lay->carry[g] = uint32_t(run_have < L - 1 ? run_have : L - 1);
+        if (o > lay->scratch_max) lay->scratch_max = o;
+        lay->tile_end[g] = lay->tiles.size();
+    }
+}
+
+// ---- the writer's side: the reductions of one table (3.2, the reference's population rules) ----
+// A block whose unfolded table has more than 70 % of its 2^B bits set gets no table; a fold to half_bits bits is accepted while a quarter of
+// them at the most are set.  (stab_reduce_kernel applies the two fold by fold; search_reduce_rule is the whole rule over given counts.)
+MLZ_SEARCH_HD bool search_table_dropped(uint32_t pop, uint32_t B) { return uint64_t(pop) * 100 / (uint64_t(1) << B) > 70; }
+MLZ_SEARCH_HD bool search_fold_accepted(uint32_t pop_folded, uint64_t half_bits) { return uint64_t(pop_folded) * 100 <= half_bits * 25; }
+// pop[r] = the set bits of the table folded r times (r = 0: as built), for r = 0 .. B - 8.  Returns the bytes of the table to store and *R,
+// or 0 when the block gets no table (more than 70 % of the unfolded bits are set).
+MLZ_SEARCH_HD uint32_t search_reduce_rule(const uint32_t* pop, uint32_t B, uint32_t* R) {
+    const uint64_t total = uint64_t(1) << B;
+    *R = 0;
+    if (search_table_dropped(pop[0], B)) return 0;
+    uint32_t r = 0;
+    uint64_t bytes = total >> 3;
+    while (bytes >= 64) {
+        const uint64_t half_bits = (bytes >> 1) << 3;
+        if (!search_fold_accepted(pop[r + 1], half_bits)) break;
+        bytes >>= 1; r++;
+    }
+    *R = r;
+    return uint32_t(bytes);
+}
+
+}  // namespace mlz

@@ -224,6 +224,15 @@ class DeviceStream:
                                       d_starts=starts.data_ptr() if return_starts and n else None, ignore_crc=ignore_crc, stream=st)
         return (out[:got], starts) if return_starts else out[:got]
 
+    def search(self, pattern, max_results, ignore_crc=False, no_tables=False):
+        """Where `pattern` (1 .. 256 bytes) occurs in the decoded stream -> (the smallest min(total, max_results) positions, ascending: an
+        int64 tensor on the stream's device; the total).  Only the blocks whose search tables admit the pattern are decoded."""
+        dev = self.t.device
+        out = torch.empty(max(max_results, 1), dtype=torch.int64, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        total, _ = self.reader.search(pattern, out.data_ptr() if max_results else None, max_results, ignore_crc=ignore_crc, no_tables=no_tables, stream=st)
+        return out[:min(total, max_results)], total
+
     def ReadAt(self, n, offset, ignore_crc=False):
         """Up to n decoded bytes from `offset`, clamped at the end of the stream -> a new uint8 tensor."""
         if n < 0 or offset < 0 or offset > self.size:
