@@ -575,4 +575,19 @@ __device__ __forceinline__ void wg_copy(uint8_t* __restrict__ d, const uint8_t* 
     if (uint32_t(tid) < n - done) d[done + tid] = s[done + tid];
 }
 
+// Exclusive prefix of v over the N lanes of the workgroup (Hillis-Steele in lds[N]; *total, when wanted: the sum); op is associative
+template <uint32_t N, class T, class Op> __device__ __forceinline__ T wg_scan(T v, T* lds, uint32_t tid, Op op, T* total = nullptr) {
+    __syncthreads();   // (lds may still be read from the scan before)
+    lds[tid] = v;
+    __syncthreads();
+    for (uint32_t d = 1; d < N; d <<= 1) {
+        const T a = tid >= d ? lds[tid - d] : T{};
+        __syncthreads();
+        if (tid >= d) lds[tid] = op(a, lds[tid]);
+        __syncthreads();
+    }
+    if (total) *total = lds[N - 1];
+    return tid ? lds[tid - 1] : T{};
+}
+
 }  // namespace mlz

@@ -50,6 +50,22 @@ struct DevBuf {
     template <class T> T* as() { return static_cast<T*>(p); }
 };
 
+// The layout of a workspace (a DevBuf, the pinned result buffer c->pinned2), region by region: a bump allocator over a byte count.  ensure()
+// of either kind frees and reallocates a buffer that grows, so a pointer taken before it is stale.  Hence the order of every phase: take all
+// of its regions, ensure the buffer ONCE with `bytes`, then turn regions into pointers — at(base) is the only way to one.
+template <class T> struct Region {
+    size_t off;
+    T* at(void* base) const { return reinterpret_cast<T*>(static_cast<uint8_t*>(base) + off); }
+};
+struct Carve {
+    size_t bytes = 0;
+    template <class T> Region<T> take(size_t count, size_t align = 16) {
+        const size_t off = (bytes + align - 1) & ~(align - 1);
+        bytes = off + count * sizeof(T);
+        return Region<T>{off};
+    }
+};
+
 constexpr size_t kProfTiles = 4096;                      // debug timeline: tiles recorded by the exec pass
 constexpr size_t kProfBytes = 256 + kProfTiles * 32;
 

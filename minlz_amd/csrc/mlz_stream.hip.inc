@@ -149,6 +149,10 @@ int stream_search_match_len(uint32_t flags) {
 // kernel of the stream: 22.6 GB/s against 31.3 into pageable memory for 100 MB).
 struct PlaceDesc { uint64_t src_off, dst_off; uint32_t len, pad; };
 constexpr uint32_t kPlacePiece = 64 << 10;
+// The span of `len` bytes from src_off to dst_off, cut into pieces of 64 KiB: put(PlaceDesc) for each, in order
+template <class Put> void place_pieces(uint64_t src_off, uint64_t dst_off, uint64_t len, uint32_t pad, Put put) {
+    for (uint64_t o = 0; o < len; o += kPlacePiece) put(PlaceDesc{src_off + o, dst_off + o, uint32_t(std::min<uint64_t>(kPlacePiece, len - o)), pad});
+}
 __global__ __launch_bounds__(256) void stream_place_kernel(const uint8_t* __restrict__ d_out, uint8_t* __restrict__ host_alias, const PlaceDesc* __restrict__ descs) {
     const PlaceDesc d = descs[blockIdx.x];
     mlz::wg_copy(host_alias + d.dst_off, d_out + d.src_off, d.len, threadIdx.x, 256);

@@ -1,6 +1,6 @@
 // mlz_stream_ranges.h — the plan of a range read on the device-resident ReadSeeker (mlz_stream_ranges.hip.inc), shared with its host check
 // (tools/stream_ranges_check.cpp): from the chunk list of an opened stream and a list of byte ranges to "which chunks, decoded where, in
-// which groups, and which pieces are then copied where".  Plain C++: compiles for the host alone.
+// which groups, and which pieces are then copied where".  Plain C++: compiles for the host alone and for gfx950.
 //
 // Rules (a touched chunk = one that holds at least one requested byte; it is decoded whole, once, however many ranges touch it):
 //   direct   a compressed chunk touched by exactly one range which covers it wholly decodes straight into its place in the destination;
@@ -20,9 +20,18 @@
 #include <algorithm>
 #include <vector>
 
+#if defined(__HIPCC__)
+#define MLZ_RANGE_HD __host__ __device__ inline
+#else
+#define MLZ_RANGE_HD inline
+#endif
+
 namespace mlz {
 
-struct RangeChunk { uint64_t out_off, n; uint8_t type; };     // a data chunk: its decoded bytes are [out_off, out_off + n) of the stream's; type 0x01 = stored
+// A data chunk as the planners and the plan kernels see it: decoded bytes [out_off, out_off + n) of the stream's, its body in the stream; type
+// 0x01 = stored.  (Named for the kernels of mlz_stream_ranges_dev.hip.inc, whose exported names carry it.)
+struct RdevChunk { uint64_t out_off, body_off; uint32_t n, type; };
+static_assert(sizeof(RdevChunk) == 24, "a record shared with the kernels");
 struct ByteRange { uint64_t off, len, dst_off; };             // decoded bytes [off, off + len) -> destination [dst_off, dst_off + len)   (= mlz_range)
 
 constexpr uint64_t kRangeGroupBytes = uint64_t(64) << 20;
@@ -51,10 +60,27 @@ template <class N> void range_group_ends(size_t count, N n_of, std::vector<size_
     }
 }
 
+// The chunk that holds byte `off` (off < size, nck > 0): a guess from avg = max(1, size / nck), corrected by a few steps, else a binary search.
+MLZ_RANGE_HD uint32_t range_locate(const RdevChunk* ck, uint32_t nck, uint64_t avg, uint64_t off) {
+    const uint64_t q = off / avg;
+    uint32_t g = q < nck - 1 ? uint32_t(q) : nck - 1;
+    for (int s = 0; s < 16; s++) {
+        if (ck[g].out_off > off) g--;                         // (chunk 0 starts at 0: never below it)
+        else if (ck[g].out_off + ck[g].n <= off) g++;         // (the last chunk ends at size: never beyond it)
+        else return g;
+    }
+    uint32_t lo = 0, hi = nck;   // the last chunk that starts at or in front of off (empty chunks share their successor's offset)
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (ck[mid].out_off <= off) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
 // ck[0, nck): the stream's data chunks in order (out_off running, the last one ends at `size`).  Returns 0, or -kRangeErrArg (a range runs
 // beyond the decoded size; two destinations overlap), -kRangeErrDstTooSmall (a destination runs beyond dst_cap): the argument rules that need
 // no device.  Empty ranges ask for nothing and overlap nothing.
-inline int plan_ranges(const RangeChunk* ck, size_t nck, uint64_t size, const ByteRange* r, size_t nr, uint64_t dst_cap, RangePlan* p) {
+inline int plan_ranges(const RdevChunk* ck, size_t nck, uint64_t size, const ByteRange* r, size_t nr, uint64_t dst_cap, RangePlan* p) {
     p->touched.clear(); p->segs.clear(); p->groups.clear();
     p->total = p->scratch_total = p->scratch_max = 0;
     for (size_t i = 0; i < nr; i++)
@@ -82,23 +108,7 @@ inline int plan_ranges(const RangeChunk* ck, size_t nck, uint64_t size, const By
     p->total = total;
     if (!total || !nck) return 0;
 
-    // the chunk that holds byte `off` (off < size)
     const uint64_t avg = std::max<uint64_t>(1, size / nck);
-    auto locate = [&](uint64_t off) -> size_t {
-        size_t g = size_t(std::min<uint64_t>(nck - 1, off / avg));
-        for (int s = 0; s < 16; s++) {
-            if (ck[g].out_off > off) g--;
-            else if (ck[g].out_off + ck[g].n <= off) g++;
-            else return g;
-        }
-        size_t lo = 0, hi = nck;   // the last chunk that starts at or in front of off (empty chunks share their successor's offset)
-        while (hi - lo > 1) {
-            const size_t mid = lo + (hi - lo) / 2;
-            if (ck[mid].out_off <= off) lo = mid; else hi = mid;
-        }
-        return lo;
-    };
-
     // pass 1: how many ranges touch each chunk, and whether one of them covers it wholly
     std::vector<uint32_t> cnt(nck, 0), first(nr, 0);
     std::vector<uint8_t> cov(nck, 0);
@@ -106,7 +116,7 @@ inline int plan_ranges(const RangeChunk* ck, size_t nck, uint64_t size, const By
     for (size_t i = 0; i < nr; i++) {
         if (!r[i].len) continue;
         const uint64_t off = r[i].off, end = off + r[i].len;
-        size_t j = locate(off);
+        size_t j = range_locate(ck, uint32_t(nck), avg, off);
         first[i] = uint32_t(j);
         cmin = std::min(cmin, j);
         for (; j < nck && ck[j].out_off < end; j++) {

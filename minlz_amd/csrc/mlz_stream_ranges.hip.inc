@@ -57,12 +57,12 @@ __global__ __launch_bounds__(256) void stream_range_copy_kernel(const uint8_t* _
 // A stream opened for range reads: the walk's result.  Refers to the caller's d_src and to the (per-device) context.
 struct mlz_dev_reader {
     mlz_ctx* ctx = nullptr;
-    void* d_chunks = nullptr;                 // the table as the plan kernels read it (mlz::RdevChunk), uploaded by the first mlz_dev_reader_read_device
+    void* d_chunks = nullptr;                 // `dchunks` where the plan kernels can read it, uploaded by the first mlz_dev_reader_read_device
     const uint8_t* d_src = nullptr;
     size_t n = 0;
     int64_t size = 0;
     std::vector<StreamChunk> chunks;          // the data chunks: body offset and length, decoded length, CRC, type, output offset
-    std::vector<mlz::RangeChunk> rchunks;     // the planner's view of them
+    std::vector<mlz::RdevChunk> dchunks;      // the planners' and the plan kernels' view of them
     // mlz_dev_reader_search: (M, B) of the stream's info chunk and every data chunk's search table, found by the first search of the handle
     // ([0]: table CRCs checked, [1]: under MLZ_STREAM_IGNORE_CRC)
     struct SearchTables {
@@ -87,9 +87,12 @@ int64_t dev_reader_read_locked(mlz_dev_reader* rd, hipStream_t sm, bool ignore_c
     for (const mlz::RangeSeg& sg : plan.segs) n_pieces += size_t((sg.len + kPlacePiece - 1) / kPlacePiece);
     if (plan.scratch_max) HIPCHK(c, c->d_range.ensure(size_t(plan.scratch_max)));
     if (n_pieces) HIPCHK(c, c->d_place.ensure(n_pieces * sizeof(PlaceDesc)));
-    int r = ensure_stream_objects(c, 0, chunk_jobs_pinned(nt) + 64 + n_pieces * sizeof(PlaceDesc));
+    Carve pin;
+    const ChunkJobResults res = take_chunk_job_results(&pin, nt);
+    const auto r_place = pin.take<PlaceDesc>(n_pieces, 64);
+    int r = ensure_stream_objects(c, 0, pin.bytes);
     if (r) return r;
-    PlaceDesc* h_place = reinterpret_cast<PlaceDesc*>((reinterpret_cast<uintptr_t>(static_cast<uint8_t*>(c->pinned2) + chunk_jobs_pinned(nt)) + 63) & ~uintptr_t(63));
+    PlaceDesc* h_place = r_place.at(c->pinned2);
     const uint8_t* scratch = c->d_range.as<uint8_t>();
     std::vector<ChunkJob> jobs(nt);
     for (size_t t = 0; t < nt; t++) {
@@ -117,10 +120,7 @@ int64_t dev_reader_read_locked(mlz_dev_reader* rd, hipStream_t sm, bool ignore_c
             const mlz::RangeTouched& tc = plan.touched[sg.touched];
             const bool stored = tc.where == mlz::kRangeStored;
             const uint64_t from = (stored ? uint64_t(rd->chunks[tc.chunk].body_off) : tc.at) + sg.rel;
-            for (uint64_t o = 0; o < sg.len; o += kPlacePiece) {
-                const uint32_t len = uint32_t(std::min<uint64_t>(kPlacePiece, sg.len - o));
-                out[len <= mlz::kRangeShortMax ? qs++ : ql++] = PlaceDesc{from + o, sg.dst_off + o, len, stored ? 1u : 0u};
-            }
+            place_pieces(from, sg.dst_off, sg.len, stored ? 1u : 0u, [&](const PlaceDesc& d) { out[d.len <= mlz::kRangeShortMax ? qs++ : ql++] = d; });
         }
         PlaceDesc* d_place = c->d_place.as<PlaceDesc>() + placed;
         HIPCHK(c, hipMemcpyAsync(d_place, out, (n_long + n_short) * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
@@ -132,7 +132,7 @@ int64_t dev_reader_read_locked(mlz_dev_reader* rd, hipStream_t sm, bool ignore_c
     {   // (a call that only copies stored chunks launches nothing else: its copies are ordered behind the workspace's last user all the same)
         WorkspaceOrder order(c, sm);
     }
-    return stream_run_chunk_jobs(c, sm, ignore_crc, rd->d_src, rd->chunks, jobs, gend, copy_group);
+    return stream_run_chunk_jobs(c, sm, ignore_crc, rd->d_src, rd->chunks, jobs, gend, res, copy_group);
 }
 
 }  // namespace
@@ -141,9 +141,7 @@ extern "C" {
 
 int64_t mlz_stream_open_device(mlz_ctx* c, void* stream, const uint8_t* d_src, size_t n, mlz_dev_reader** out) {
     if (out) *out = nullptr;
-    if (!c || !out || (!d_src && n) || uint64_t(n) > kWalkMaxStream) return -MLZ_ERR_ARG;
-    if (n && !(c = owner_of(c, d_src))) return -MLZ_ERR_ARG;
-    if (!c->kids.empty()) c = c->kids[0];   // (an empty stream: any device)
+    if (!out || !(c = stream_ctx(c, d_src, n))) return -MLZ_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     mlz_dev_reader* rd = new (std::nothrow) mlz_dev_reader;
     if (!rd) return -MLZ_ERR_HIP;
@@ -151,8 +149,8 @@ int64_t mlz_stream_open_device(mlz_ctx* c, void* stream, const uint8_t* d_src, s
     const int e = stream_walk_device(c, static_cast<hipStream_t>(stream), d_src, n, &rd->chunks, &parsed);
     if (e || parsed < 0) { delete rd; return e ? e : parsed; }   // a framing error: no handle
     rd->ctx = c; rd->d_src = d_src; rd->n = n; rd->size = parsed;
-    rd->rchunks.reserve(rd->chunks.size());
-    for (const StreamChunk& ck : rd->chunks) rd->rchunks.push_back(mlz::RangeChunk{uint64_t(ck.out_off), uint64_t(ck.n), ck.type});
+    rd->dchunks.reserve(rd->chunks.size());
+    for (const StreamChunk& ck : rd->chunks) rd->dchunks.push_back(mlz::RdevChunk{uint64_t(ck.out_off), uint64_t(ck.body_off), uint32_t(ck.n), ck.type});
     *out = rd;
     return parsed;
 }
@@ -164,17 +162,14 @@ int64_t mlz_dev_reader_read(mlz_dev_reader* rd, void* stream, uint32_t flags, co
     mlz_ctx* c = rd->ctx;
     std::lock_guard<std::mutex> lk(c->mu);
     mlz::RangePlan plan;
-    const int pr = mlz::plan_ranges(rd->rchunks.data(), rd->rchunks.size(), uint64_t(rd->size), reinterpret_cast<const mlz::ByteRange*>(ranges), n_ranges, uint64_t(dst_cap), &plan);
+    const int pr = mlz::plan_ranges(rd->dchunks.data(), rd->dchunks.size(), uint64_t(rd->size), reinterpret_cast<const mlz::ByteRange*>(ranges), n_ranges, uint64_t(dst_cap), &plan);
     if (pr < 0) return pr;
-    if (plan.total) {   // the destination: on the handle's device
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, d_dst) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != c->device) { (void)hipGetLastError(); return -MLZ_ERR_ARG; }
-    }
+    if (plan.total && !on_device(c, d_dst)) return -MLZ_ERR_ARG;   // the destination: on the handle's device
     begin_decode_call(c);
     c->range_chunks = plan.touched.size();
     c->range_scratch = plan.scratch_total;
-    const int64_t r = dev_reader_read_locked(rd, static_cast<hipStream_t>(stream), (flags & MLZ_STREAM_IGNORE_CRC) != 0, plan, d_dst);
-    if (r < 0) (void)hipStreamSynchronize(static_cast<hipStream_t>(stream));   // nothing of a failed call is left in flight
+    hipStream_t sm = static_cast<hipStream_t>(stream);
+    const int64_t r = settled(sm, dev_reader_read_locked(rd, sm, (flags & MLZ_STREAM_IGNORE_CRC) != 0, plan, d_dst));
     return r < 0 ? r : int64_t(plan.total);
 }
 

@@ -18,63 +18,39 @@
 
 #include "mlz_stream_ranges.h"
 
-#if defined(__HIPCC__)
-#define MLZ_RDEV_HD __host__ __device__ inline
-#else
-#define MLZ_RDEV_HD inline
-#endif
-
 namespace mlz {
 
-struct RdevChunk { uint64_t out_off, body_off; uint32_t n, type; };    // a data chunk as the kernels see it: decoded bytes [out_off, + n), its body in the stream
 struct RdevHeader { uint64_t total, pieces; uint32_t err, touched; uint64_t pad; };   // the first read-back: sum of the lengths, long pieces, "a range is out of bounds", touched chunks
 struct RdevTouched { uint32_t chunk, where; uint64_t at; };            // the second read-back.  direct: offset in the destination; else 0
 struct RdevPlace { uint64_t base; uint32_t group, where; };            // the upload, per touched chunk.  scratch: offset in the scratch
-static_assert(sizeof(RdevChunk) == 24 && sizeof(RdevHeader) == 32 && sizeof(RdevTouched) == 16 && sizeof(RdevPlace) == 16, "records shared with the kernels");
+static_assert(sizeof(RdevHeader) == 32 && sizeof(RdevTouched) == 16 && sizeof(RdevPlace) == 16, "records shared with the kernels");
 
 constexpr uint32_t kRdevBlock = 1024;                        // ranges per block of the per-range pass: one prefix block
 constexpr uint64_t kRdevMaxRanges = uint64_t(1) << 31;       // a range's index is a 32-bit addend
 constexpr uint64_t kRdevMaxGrid = (uint64_t(1) << 31) - 1;   // long pieces + ranges / 16 of one call: one launch
 
-MLZ_RDEV_HD uint64_t rdev_sat_add(uint64_t a, uint64_t b) { return a + b < a ? ~uint64_t(0) : a + b; }   // (2^31 lengths below 2^63 can pass 2^64)
-
-// The chunk that holds byte `off` (off < size, nck > 0): plan_ranges' locate.  avg = max(1, size / nck).
-MLZ_RDEV_HD uint32_t rdev_locate(const RdevChunk* ck, uint32_t nck, uint64_t avg, uint64_t off) {
-    const uint64_t q = off / avg;
-    uint32_t g = q < nck - 1 ? uint32_t(q) : nck - 1;
-    for (int s = 0; s < 16; s++) {
-        if (ck[g].out_off > off) g--;                         // (chunk 0 starts at 0: never below it)
-        else if (ck[g].out_off + ck[g].n <= off) g++;         // (the last chunk ends at size: never beyond it)
-        else return g;
-    }
-    uint32_t lo = 0, hi = nck;   // the last chunk that starts at or in front of off (empty chunks share their successor's offset)
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (ck[mid].out_off <= off) lo = mid; else hi = mid;
-    }
-    return lo;
-}
+MLZ_RANGE_HD uint64_t rdev_sat_add(uint64_t a, uint64_t b) { return a + b < a ? ~uint64_t(0) : a + b; }   // (2^31 lengths below 2^63 can pass 2^64)
 
 // One range.  bad: it runs beyond the decoded size.  live: it asks for a byte; then [j0, j1] are its first and last touched chunk (both
 // non-empty; empty ones between them are "touched" by the difference arrays and dropped by rdev_chunk_rule).  pieces: its long pieces.
 struct RdevRange { uint32_t j0, j1; uint64_t pieces; bool bad, live; };
-MLZ_RDEV_HD RdevRange rdev_range_rule(const RdevChunk* ck, uint32_t nck, uint64_t size, uint64_t avg, uint64_t off, uint64_t len, uint32_t short_max, uint32_t piece) {
+MLZ_RANGE_HD RdevRange rdev_range_rule(const RdevChunk* ck, uint32_t nck, uint64_t size, uint64_t avg, uint64_t off, uint64_t len, uint32_t short_max, uint32_t piece) {
     RdevRange r{0, 0, 0, false, false};
     r.bad = off > size || len > size - off;
     r.live = !r.bad && len > 0 && nck > 0;
     if (!r.live) return r;
     const uint64_t last = off + len - 1;
-    r.j0 = rdev_locate(ck, nck, avg, off);
-    r.j1 = last < ck[r.j0].out_off + ck[r.j0].n ? r.j0 : rdev_locate(ck, nck, avg, last);
+    r.j0 = range_locate(ck, nck, avg, off);
+    r.j1 = last < ck[r.j0].out_off + ck[r.j0].n ? r.j0 : range_locate(ck, nck, avg, last);
     r.pieces = len > short_max ? (len + piece - 1) / piece : 0;
     return r;
 }
 
 // Where range i's bytes start in the packed destination: its block's offset + its offset in the block.
-MLZ_RDEV_HD uint64_t rdev_start(const uint64_t* block_off, const uint64_t* local, uint64_t i) { return block_off[i / kRdevBlock] + local[i]; }
+MLZ_RANGE_HD uint64_t rdev_start(const uint64_t* block_off, const uint64_t* local, uint64_t i) { return block_off[i / kRdevBlock] + local[i]; }
 
 // One chunk with the running sums of the difference arrays at its index: false = not touched (or empty).  off / len: the range arrays.
-MLZ_RDEV_HD bool rdev_chunk_rule(const RdevChunk& c, uint32_t j, uint32_t cnt, uint32_t who, const uint64_t* off, const uint64_t* len, const uint64_t* block_off,
+MLZ_RANGE_HD bool rdev_chunk_rule(const RdevChunk& c, uint32_t j, uint32_t cnt, uint32_t who, const uint64_t* off, const uint64_t* len, const uint64_t* block_off,
                                  const uint64_t* local, RdevTouched* t) {
     if (!cnt || !c.n) return false;
     t->chunk = j; t->where = kRangeScratch; t->at = 0;
@@ -89,7 +65,7 @@ MLZ_RDEV_HD bool rdev_chunk_rule(const RdevChunk& c, uint32_t j, uint32_t cnt, u
 // The range that owns long piece p (p < the number of pieces): the last block, then the last range in it, whose exclusive piece prefix is at
 // most p (ranges and blocks without pieces share their successor's prefix and are stepped over).  n: ranges, nb: blocks.  *q: the piece's
 // index in its range.
-MLZ_RDEV_HD uint64_t rdev_piece_owner(const uint64_t* piece_block_off, const uint32_t* piece_local, uint64_t n, uint64_t nb, uint64_t p, uint64_t* q) {
+MLZ_RANGE_HD uint64_t rdev_piece_owner(const uint64_t* piece_block_off, const uint32_t* piece_local, uint64_t n, uint64_t nb, uint64_t p, uint64_t* q) {
     uint64_t lo = 0, hi = nb;
     while (hi - lo > 1) {
         const uint64_t mid = lo + (hi - lo) / 2;
@@ -109,7 +85,7 @@ MLZ_RDEV_HD uint64_t rdev_piece_owner(const uint64_t* piece_block_off, const uin
 // The part of a range (decoded bytes from `off` on, packed at `start`) inside the window [wb, we) that lies in the non-empty chunk c with
 // place pl, for the gather of group `group`: false = nothing to copy here (another group's chunk, a direct one, no common byte).
 // *src: offset in the stream (*from_stream) or in the scratch; *dst: offset in the destination.
-MLZ_RDEV_HD bool rdev_intersect(const RdevChunk& c, const RdevPlace& pl, uint32_t group, uint64_t off, uint64_t start, uint64_t wb, uint64_t we, uint64_t* src,
+MLZ_RANGE_HD bool rdev_intersect(const RdevChunk& c, const RdevPlace& pl, uint32_t group, uint64_t off, uint64_t start, uint64_t wb, uint64_t we, uint64_t* src,
                                 uint64_t* dst, uint32_t* n, bool* from_stream) {
     if (pl.group != group || pl.where == kRangeDirect) return false;
     const uint64_t b = wb > c.out_off ? wb : c.out_off, e = we < c.out_off + c.n ? we : c.out_off + c.n;

@@ -50,12 +50,13 @@ __device__ __forceinline__ void rdev_wave_add(uint32_t* __restrict__ cntd, uint3
 }
 
 // R1.  Range i of block b is lane (i % 1024) / 4's: a lane's four ranges are neighbours, so its running sums are the prefix.
+struct RdevSums { uint64_t l, p; };   // lengths and long pieces: one scan for both
 __global__ __launch_bounds__(kRdevThreads) void rdev_range_kernel(const RdevChunk* __restrict__ ck, uint32_t nck, uint64_t size, uint64_t avg, const uint64_t* __restrict__ d_off,
                                                                   const uint64_t* __restrict__ d_len, uint64_t n, uint32_t short_max, uint32_t* __restrict__ first,
                                                                   uint64_t* __restrict__ len_local, uint32_t* __restrict__ piece_local, uint64_t* __restrict__ len_block,
                                                                   uint64_t* __restrict__ piece_block, uint32_t* __restrict__ cntd, uint32_t* __restrict__ whod, RdevHeader* __restrict__ hdr) {
     __shared__ uint32_t lc[kRdevLdsChunks], lw[kRdevLdsChunks];
-    __shared__ uint64_t sl[kRdevThreads], sp[kRdevThreads];
+    __shared__ RdevSums ss[kRdevThreads];
     const uint32_t tid = threadIdx.x;
     const bool in_lds = nck < kRdevLdsChunks;   // nck + 1 words
     if (in_lds) {
@@ -92,21 +93,15 @@ __global__ __launch_bounds__(kRdevThreads) void rdev_range_kernel(const RdevChun
     }
     if (bad) hdr->err = 1;
     // exclusive prefix of the lanes' sums over the workgroup
-    sl[tid] = tl; sp[tid] = tp;
-    __syncthreads();
-    for (uint32_t d = 1; d < kRdevThreads; d <<= 1) {
-        const uint64_t al = tid >= d ? sl[tid - d] : 0, ap = tid >= d ? sp[tid - d] : 0;
-        __syncthreads();
-        sl[tid] = rdev_sat_add(sl[tid], al); sp[tid] = rdev_sat_add(sp[tid], ap);
-        __syncthreads();
-    }
-    uint64_t rl = tid ? sl[tid - 1] : 0, rp = tid ? sp[tid - 1] : 0;
+    RdevSums sum;
+    const RdevSums run = wg_scan<kRdevThreads>(RdevSums{tl, tp}, ss, tid, [](RdevSums x, RdevSums y) { return RdevSums{rdev_sat_add(x.l, y.l), rdev_sat_add(x.p, y.p)}; }, &sum);
+    uint64_t rl = run.l, rp = run.p;
 #pragma unroll
     for (uint32_t k = 0; k < kRdevPer; k++) {
         if (i0 + k < n) { len_local[i0 + k] = rl; piece_local[i0 + k] = uint32_t(rp); }
         rl = rdev_sat_add(rl, lens[k]); rp = rdev_sat_add(rp, pcs[k]);
     }
-    if (tid == kRdevThreads - 1) { len_block[blockIdx.x] = sl[tid]; piece_block[blockIdx.x] = sp[tid]; }
+    if (tid == kRdevThreads - 1) { len_block[blockIdx.x] = sum.l; piece_block[blockIdx.x] = sum.p; }
     if (in_lds) {   // (the LDS adds were all made in front of the scan's first barrier)
         for (uint32_t k = tid; k <= nck; k += kRdevThreads) {
             if (lc[k]) atomicAdd(&cntd[k], lc[k]);
@@ -116,21 +111,6 @@ __global__ __launch_bounds__(kRdevThreads) void rdev_range_kernel(const RdevChun
 }
 
 constexpr uint32_t kRdevScanThreads = 1024;
-
-// exclusive prefix of v over the 1024 lanes of the workgroup (*total: the sum); OP is associative
-template <class T, class Op> __device__ __forceinline__ T rdev_wg_scan(T v, T* lds, uint32_t tid, Op op, T* total) {
-    __syncthreads();   // (lds may still be read from the scan before)
-    lds[tid] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < kRdevScanThreads; d <<= 1) {
-        const T a = tid >= d ? lds[tid - d] : T{};
-        __syncthreads();
-        if (tid >= d) lds[tid] = op(a, lds[tid]);
-        __syncthreads();
-    }
-    *total = lds[kRdevScanThreads - 1];
-    return tid ? lds[tid - 1] : T{};
-}
 
 struct RdevPair { uint32_t c, w; };
 
@@ -148,8 +128,8 @@ __global__ __launch_bounds__(kRdevScanThreads) void rdev_chunk_kernel(const Rdev
         const uint64_t b = tid * per < nb ? tid * per : nb, e = b + per < nb ? b + per : nb;
         uint64_t sl = 0, sp = 0, tot_l = 0, tot_p = 0;
         for (uint64_t k = b; k < e; k++) { sl = rdev_sat_add(sl, len_block[k]); sp = rdev_sat_add(sp, piece_block[k]); }
-        uint64_t rl = rdev_wg_scan(sl, s64, tid, sat, &tot_l);
-        uint64_t rp = rdev_wg_scan(sp, s64, tid, sat, &tot_p);
+        uint64_t rl = wg_scan<kRdevScanThreads>(sl, s64, tid, sat, &tot_l);
+        uint64_t rp = wg_scan<kRdevScanThreads>(sp, s64, tid, sat, &tot_p);
         for (uint64_t k = b; k < e; k++) {
             const uint64_t l = len_block[k], p = piece_block[k];
             len_block[k] = rl; piece_block[k] = rp;
@@ -163,7 +143,7 @@ __global__ __launch_bounds__(kRdevScanThreads) void rdev_chunk_kernel(const Rdev
     const uint32_t b = uint64_t(tid) * per < nck ? tid * per : nck, e = nck - b > per ? b + per : nck;
     RdevPair s{0, 0}, tot{0, 0};
     for (uint32_t j = b; j < e; j++) { s.c += cntd[j]; s.w += whod[j]; }
-    const RdevPair run0 = rdev_wg_scan(s, s32, tid, [](RdevPair x, RdevPair y) { return RdevPair{x.c + y.c, x.w + y.w}; }, &tot);
+    const RdevPair run0 = wg_scan<kRdevScanThreads>(s, s32, tid, [](RdevPair x, RdevPair y) { return RdevPair{x.c + y.c, x.w + y.w}; }, &tot);
     RdevTouched t;
     uint32_t mine = 0;
     RdevPair run = run0;
@@ -172,7 +152,7 @@ __global__ __launch_bounds__(kRdevScanThreads) void rdev_chunk_kernel(const Rdev
         mine += rdev_chunk_rule(ck[j], j, run.c, run.w, d_off, d_len, len_block, len_local, &t) ? 1u : 0u;
     }
     RdevPair nt{0, 0};
-    uint32_t at = rdev_wg_scan(RdevPair{mine, 0}, s32, tid, [](RdevPair x, RdevPair y) { return RdevPair{x.c + y.c, 0}; }, &nt).c;
+    uint32_t at = wg_scan<kRdevScanThreads>(RdevPair{mine, 0}, s32, tid, [](RdevPair x, RdevPair y) { return RdevPair{x.c + y.c, 0}; }, &nt).c;
     run = run0;
     for (uint32_t j = b; j < e; j++) {
         run.c += cntd[j]; run.w += whod[j];
@@ -205,7 +185,7 @@ __global__ __launch_bounds__(256) void rdev_gather_kernel(const RdevGatherArgs a
         const uint64_t i = rdev_piece_owner(a.piece_block, a.piece_local, a.n, a.nb, blockIdx.x, &q);
         const uint64_t off = a.d_off[i], end = off + a.d_len[i], start = rdev_start(a.len_block, a.len_local, i);
         const uint64_t wb = off + q * kPlacePiece, we = end - wb > kPlacePiece ? wb + kPlacePiece : end;
-        for (uint32_t j = q ? rdev_locate(a.ck, a.nck, a.avg, wb) : a.first[i]; j < a.nck && a.ck[j].out_off < we; j++) {
+        for (uint32_t j = q ? range_locate(a.ck, a.nck, a.avg, wb) : a.first[i]; j < a.nck && a.ck[j].out_off < we; j++) {
             const RdevChunk c = a.ck[j];
             if (!c.n) continue;
             if (rdev_intersect(c, a.place[a.slot[j]], a.group, off, start, wb, we, &src, &dst, &len, &from_stream))
@@ -230,55 +210,41 @@ __global__ __launch_bounds__(256) void rdev_gather_kernel(const RdevGatherArgs a
 
 namespace {
 
-bool on_device(const mlz_ctx* c, const void* p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != c->device) { (void)hipGetLastError(); return false; }
-    return true;
-}
-
 int64_t dev_reader_read_device_locked(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, const uint64_t* d_off, const uint64_t* d_len, uint64_t n, uint8_t* d_dst, uint64_t dst_cap,
                                       uint64_t* d_starts, uint64_t* total_out) {
     mlz_ctx* c = rd->ctx;
     const size_t nck = rd->chunks.size();
     HIPCHK(c, hipSetDevice(c->device));
     if (nck && !rd->d_chunks) {   // once per handle: the chunk table where kernels can read it
-        std::vector<mlz::RdevChunk> t(nck);
-        for (size_t j = 0; j < nck; j++) t[j] = mlz::RdevChunk{uint64_t(rd->chunks[j].out_off), uint64_t(rd->chunks[j].body_off), uint32_t(rd->chunks[j].n), rd->chunks[j].type};
         HIPCHK(c, hipMalloc(&rd->d_chunks, nck * sizeof(mlz::RdevChunk)));
-        HIPCHK(c, hipMemcpy(rd->d_chunks, t.data(), nck * sizeof(mlz::RdevChunk), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(rd->d_chunks, rd->dchunks.data(), nck * sizeof(mlz::RdevChunk), hipMemcpyHostToDevice));
     }
     const uint64_t nb = (n + mlz::kRdevBlock - 1) / mlz::kRdevBlock;
-    auto up = [](size_t v) { return (v + 15) & ~size_t(15); };
     // header | count differences | index differences | slot | touched, then places | first | piece prefix | length prefix | block sums
-    const size_t o_cnt = sizeof(mlz::RdevHeader), o_who = up(o_cnt + (nck + 1) * 4), o_slot = up(o_who + (nck + 1) * 4), o_touched = up(o_slot + nck * 4),
-                 o_first = up(o_touched + nck * sizeof(mlz::RdevTouched)), o_plocal = up(o_first + size_t(n) * 4), o_llocal = up(o_plocal + size_t(n) * 4),
-                 o_lblock = up(o_llocal + size_t(n) * 8), o_pblock = up(o_lblock + size_t(nb) * 8), ws_bytes = o_pblock + size_t(nb) * 8;
-    HIPCHK(c, c->d_rplan.ensure(ws_bytes));
+    Carve cv;   // (the header and the difference arrays lie in front: one memset clears them)
+    const auto r_hdr = cv.take<mlz::RdevHeader>(1);
+    const auto r_cntd = cv.take<uint32_t>(nck + 1), r_whod = cv.take<uint32_t>(nck + 1), r_slot = cv.take<uint32_t>(nck);
+    const auto r_touched = cv.take<mlz::RdevTouched>(nck);
+    const auto r_first = cv.take<uint32_t>(size_t(n)), r_plocal = cv.take<uint32_t>(size_t(n));
+    const auto r_llocal = cv.take<uint64_t>(size_t(n)), r_lblock = cv.take<uint64_t>(size_t(nb)), r_pblock = cv.take<uint64_t>(size_t(nb));
+    HIPCHK(c, c->d_rplan.ensure(cv.bytes));
     int r = ensure_stream_objects(c, 0, 64);
     if (r) return r;
-    uint8_t* ws = c->d_rplan.as<uint8_t>();
-    mlz::RdevHeader* hdr = reinterpret_cast<mlz::RdevHeader*>(ws);
-    uint32_t* cntd = reinterpret_cast<uint32_t*>(ws + o_cnt);
-    uint32_t* whod = reinterpret_cast<uint32_t*>(ws + o_who);
-    uint32_t* slot = reinterpret_cast<uint32_t*>(ws + o_slot);
-    mlz::RdevTouched* touched = reinterpret_cast<mlz::RdevTouched*>(ws + o_touched);
-    uint32_t* first = reinterpret_cast<uint32_t*>(ws + o_first);
-    uint32_t* piece_local = reinterpret_cast<uint32_t*>(ws + o_plocal);
-    uint64_t* len_local = reinterpret_cast<uint64_t*>(ws + o_llocal);
-    uint64_t* len_block = reinterpret_cast<uint64_t*>(ws + o_lblock);
-    uint64_t* piece_block = reinterpret_cast<uint64_t*>(ws + o_pblock);
+    void* ws = c->d_rplan.p;
+    mlz::RdevHeader* hdr = r_hdr.at(ws);
+    mlz::RdevTouched* touched = r_touched.at(ws);
+    uint32_t *cntd = r_cntd.at(ws), *whod = r_whod.at(ws), *slot = r_slot.at(ws), *first = r_first.at(ws), *piece_local = r_plocal.at(ws);
+    uint64_t *len_local = r_llocal.at(ws), *len_block = r_lblock.at(ws), *piece_block = r_pblock.at(ws);
     const mlz::RdevChunk* ck = static_cast<const mlz::RdevChunk*>(rd->d_chunks);
     const uint64_t size = uint64_t(rd->size), avg = std::max<uint64_t>(1, nck ? size / nck : 1);
 
     WorkspaceOrder order(c, sm);
-    HIPCHK(c, hipMemsetAsync(ws, 0, o_slot, sm));   // header and difference arrays
+    HIPCHK(c, hipMemsetAsync(ws, 0, r_slot.off, sm));   // header and difference arrays
     hipLaunchKernelGGL(mlz::rdev_range_kernel, dim3(uint32_t(nb)), dim3(mlz::kRdevThreads), 0, sm, ck, uint32_t(nck), size, avg, d_off, d_len, n, mlz::kRangeShortMax, first, len_local,
                        piece_local, len_block, piece_block, cntd, whod, hdr);
     hipLaunchKernelGGL(mlz::rdev_chunk_kernel, dim3(1), dim3(mlz::kRdevScanThreads), 0, sm, ck, uint32_t(nck), d_off, d_len, nb, len_block, piece_block, len_local, cntd, whod, slot,
                        touched, hdr);
-    HIPCHK(c, hipMemcpyAsync(c->pinned2, hdr, sizeof(mlz::RdevHeader), hipMemcpyDeviceToHost, sm));
-    HIPCHK(c, hipStreamSynchronize(sm));
-    HIPCHK(c, hipGetLastError());
+    if ((r = fetch(c, sm, c->pinned2, hdr, sizeof(mlz::RdevHeader)))) return r;
     const mlz::RdevHeader h = *static_cast<const mlz::RdevHeader*>(c->pinned2);
     c->range_plan_host = sizeof(mlz::RdevHeader);
     if (h.err) return -MLZ_ERR_ARG;
@@ -293,14 +259,15 @@ int64_t dev_reader_read_device_locked(mlz_dev_reader* rd, hipStream_t sm, bool i
         return 0;
     }
     // the touched chunks come down, their places go up: behind the part of the pinned buffer that stream_run_chunk_jobs uses
-    const size_t o_list = (chunk_jobs_pinned(nt) + 63) & ~size_t(63);
-    r = ensure_stream_objects(c, 0, o_list + nt * (sizeof(mlz::RdevTouched) + sizeof(mlz::RdevPlace)));
+    Carve pin;
+    const ChunkJobResults res = take_chunk_job_results(&pin, nt);
+    const auto r_htouched = pin.take<mlz::RdevTouched>(nt, 64);
+    const auto r_hplace = pin.take<mlz::RdevPlace>(nt);
+    r = ensure_stream_objects(c, 0, pin.bytes);
     if (r) return r;
-    mlz::RdevTouched* h_touched = reinterpret_cast<mlz::RdevTouched*>(static_cast<uint8_t*>(c->pinned2) + o_list);
-    mlz::RdevPlace* h_place = reinterpret_cast<mlz::RdevPlace*>(h_touched + nt);
-    HIPCHK(c, hipMemcpyAsync(h_touched, touched, nt * sizeof(mlz::RdevTouched), hipMemcpyDeviceToHost, sm));
-    HIPCHK(c, hipStreamSynchronize(sm));
-    HIPCHK(c, hipGetLastError());
+    mlz::RdevTouched* h_touched = r_htouched.at(c->pinned2);
+    mlz::RdevPlace* h_place = r_hplace.at(c->pinned2);
+    if ((r = fetch(c, sm, h_touched, touched, nt * sizeof(mlz::RdevTouched)))) return r;
     std::vector<mlz::RdevPlace> places;
     std::vector<size_t> gend;
     std::vector<uint8_t> group_copies;
@@ -330,7 +297,7 @@ int64_t dev_reader_read_device_locked(mlz_dev_reader* rd, hipStream_t sm, bool i
         hipLaunchKernelGGL(mlz::rdev_gather_kernel, dim3(uint32_t(grid)), dim3(256), 0, sm, ga);
         return 0;
     };
-    return stream_run_chunk_jobs(c, sm, ignore_crc, rd->d_src, rd->chunks, jobs, gend, copy_group);
+    return stream_run_chunk_jobs(c, sm, ignore_crc, rd->d_src, rd->chunks, jobs, gend, res, copy_group);
 }
 
 }  // namespace
@@ -347,8 +314,7 @@ extern "C" int64_t mlz_dev_reader_read_device(mlz_dev_reader* rd, void* stream, 
     begin_decode_call(c);
     c->range_chunks = c->range_scratch = 0;
     uint64_t total = 0;
-    const int64_t r = dev_reader_read_device_locked(rd, static_cast<hipStream_t>(stream), (flags & MLZ_STREAM_IGNORE_CRC) != 0, d_off, d_len, uint64_t(n_ranges), d_dst, uint64_t(dst_cap),
-                                                    d_starts, &total);
-    if (r < 0) (void)hipStreamSynchronize(static_cast<hipStream_t>(stream));   // nothing of a failed call is left in flight
+    hipStream_t sm = static_cast<hipStream_t>(stream);
+    const int64_t r = settled(sm, dev_reader_read_device_locked(rd, sm, (flags & MLZ_STREAM_IGNORE_CRC) != 0, d_off, d_len, uint64_t(n_ranges), d_dst, uint64_t(dst_cap), d_starts, &total));
     return r < 0 ? r : int64_t(total);
 }

@@ -23,8 +23,8 @@ __global__ __launch_bounds__(64) void search_info_kernel(const uint8_t* __restri
     SearchInfo r{0, 0, 0, 0};
     bool seen_id = false;
     for (uint64_t p = 0; p + 4 <= limit;) {
-        const uint8_t type = src[p];
-        const uint32_t clen = uint32_t(src[p + 1]) | uint32_t(src[p + 2]) << 8 | uint32_t(src[p + 3]) << 16;
+        uint8_t type;
+        const uint32_t clen = walk_header(src, p, &type);
         if (search_is_data(type)) break;
         if (type == 0xff) seen_id = true;
         else if (type == kChunkSearchInfo && seen_id) {
@@ -47,8 +47,8 @@ __global__ __launch_bounds__(64) void search_locate_kernel(const uint8_t* __rest
         const uint64_t limit = hop[k].limit;
         uint32_t left = skip[k];
         for (uint64_t p = hop[k].from; p + 4 <= limit;) {
-            const uint8_t type = src[p];
-            const uint32_t clen = uint32_t(src[p + 1]) | uint32_t(src[p + 2]) << 8 | uint32_t(src[p + 3]) << 16;
+            uint8_t type;
+            const uint32_t clen = walk_header(src, p, &type);
             if (search_is_data(type)) break;
             if (type == kChunkSearchTable && p + 4 + clen <= limit) {
                 const int R = search_table_reductions(src + p + 4, clen, in.M, in.B);
@@ -110,18 +110,10 @@ __global__ __launch_bounds__(1024) void search_prefix_kernel(const uint32_t* __r
     uint64_t carry = 0;
     for (uint32_t base = 0; base < nt; base += 1024) {
         const uint32_t i = base + tid;
-        const uint64_t v = i < nt ? counts[i] : 0;
-        lds[tid] = v;
-        __syncthreads();
-        for (uint32_t d = 1; d < 1024; d <<= 1) {
-            const uint64_t x = tid >= d ? lds[tid - d] : 0;
-            __syncthreads();
-            lds[tid] += x;
-            __syncthreads();
-        }
-        if (i < nt) prefix[i] = carry + lds[tid] - v;
-        carry += lds[1023];
-        __syncthreads();
+        uint64_t sum;
+        const uint64_t before = wg_scan<1024>(uint64_t(i < nt ? counts[i] : 0), lds, tid, [](uint64_t x, uint64_t y) { return x + y; }, &sum);
+        if (i < nt) prefix[i] = carry + before;
+        carry += sum;
     }
     if (tid == 0) *total = carry;
 }
@@ -135,15 +127,7 @@ __global__ __launch_bounds__(kSearchTileWords) void search_write_kernel(const Se
     if (first >= cap) return;
     uint64_t w = masks[size_t(tile) * kSearchTileWords + tid];
     const uint32_t c = uint32_t(__popcll(w));
-    lds[tid] = c;
-    __syncthreads();
-    for (uint32_t d = 1; d < kSearchTileWords; d <<= 1) {
-        const uint32_t x = tid >= d ? lds[tid - d] : 0;
-        __syncthreads();
-        lds[tid] += x;
-        __syncthreads();
-    }
-    uint64_t at = first + lds[tid] - c;
+    uint64_t at = first + wg_scan<kSearchTileWords>(c, lds, tid, [](uint32_t x, uint32_t y) { return x + y; });
     const uint64_t g = tiles[tile].gpos + uint64_t(tid) * 64;
     for (; w && at < cap; w &= w - 1, at++) out[at] = g + uint64_t(__builtin_ctzll(w));
 }
@@ -161,20 +145,23 @@ int64_t dev_reader_search_tables(mlz_dev_reader* rd, hipStream_t sm, bool ignore
     std::vector<mlz::SearchHop> hop(nck);
     for (size_t k = 0; k < nck; k++) hop[k] = mlz::SearchHop{k ? uint64_t(rd->chunks[k - 1].body_off + rd->chunks[k - 1].body_len) : 0, uint64_t(rd->chunks[k].body_off)};
     std::vector<uint32_t> skip(nck, 0);
-    const size_t o_skip = nck * sizeof(mlz::SearchHop), o_info = (o_skip + nck * 4 + 15) & ~size_t(15), o_crc = o_info + sizeof(mlz::SearchInfo), ws_bytes = o_crc + nck * 4;
-    HIPCHK(c, c->d_rplan.ensure(ws_bytes));
+    Carve cv, pin;   // workspace: hops | skips | info | table CRCs; what comes back: tables | table CRCs | info
+    const auto r_hop = cv.take<mlz::SearchHop>(nck);
+    const auto r_skip = cv.take<uint32_t>(nck);
+    const auto r_info = cv.take<mlz::SearchInfo>(1);
+    const auto r_crc = cv.take<uint32_t>(nck);
+    const auto r_htabs = pin.take<mlz::SearchTab>(nck);
+    const auto r_hcrc = pin.take<uint32_t>(nck, 4);
+    const auto r_hinfo = pin.take<mlz::SearchInfo>(1, 4);
+    HIPCHK(c, c->d_rplan.ensure(cv.bytes));
     if (!st.d_tabs) HIPCHK(c, hipMalloc(&st.d_tabs, nck * sizeof(mlz::SearchTab)));
-    int r = ensure_stream_objects(c, 0, nck * (sizeof(mlz::SearchTab) + 4) + sizeof(mlz::SearchInfo));
+    int r = ensure_stream_objects(c, 0, pin.bytes);
     if (r) return r;
-    uint8_t* ws = c->d_rplan.as<uint8_t>();
-    mlz::SearchHop* d_hop = reinterpret_cast<mlz::SearchHop*>(ws);
-    uint32_t* d_skip = reinterpret_cast<uint32_t*>(ws + o_skip);
-    mlz::SearchInfo* d_info = reinterpret_cast<mlz::SearchInfo*>(ws + o_info);
-    uint32_t* d_crc = reinterpret_cast<uint32_t*>(ws + o_crc);
-    mlz::SearchTab* d_tabs = static_cast<mlz::SearchTab*>(st.d_tabs);
-    mlz::SearchTab* h_tabs = static_cast<mlz::SearchTab*>(c->pinned2);
-    uint32_t* h_crc = reinterpret_cast<uint32_t*>(h_tabs + nck);
-    mlz::SearchInfo* h_info = reinterpret_cast<mlz::SearchInfo*>(h_crc + nck);
+    void* ws = c->d_rplan.p;
+    mlz::SearchHop* d_hop = r_hop.at(ws);
+    mlz::SearchInfo *d_info = r_info.at(ws), *h_info = r_hinfo.at(c->pinned2);
+    uint32_t *d_skip = r_skip.at(ws), *d_crc = r_crc.at(ws), *h_crc = r_hcrc.at(c->pinned2);
+    mlz::SearchTab *d_tabs = static_cast<mlz::SearchTab*>(st.d_tabs), *h_tabs = r_htabs.at(c->pinned2);
     { WorkspaceOrder order(c, sm); }
     HIPCHK(c, hipMemcpyAsync(d_hop, hop.data(), nck * sizeof(mlz::SearchHop), hipMemcpyHostToDevice, sm));
     hipLaunchKernelGGL(mlz::search_info_kernel, dim3(1), dim3(64), 0, sm, rd->d_src, hop[0].limit, d_info);
@@ -182,9 +169,7 @@ int64_t dev_reader_search_tables(mlz_dev_reader* rd, hipStream_t sm, bool ignore
         HIPCHK(c, hipMemcpyAsync(d_skip, skip.data(), nck * 4, hipMemcpyHostToDevice, sm));
         hipLaunchKernelGGL(mlz::search_locate_kernel, dim3(uint32_t((nck + 63) / 64)), dim3(64), 0, sm, rd->d_src, d_hop, d_skip, uint32_t(nck), d_info, d_tabs);
         HIPCHK(c, hipMemcpyAsync(h_tabs, d_tabs, nck * sizeof(mlz::SearchTab), hipMemcpyDeviceToHost, sm));
-        HIPCHK(c, hipMemcpyAsync(h_info, d_info, sizeof(mlz::SearchInfo), hipMemcpyDeviceToHost, sm));
-        HIPCHK(c, hipStreamSynchronize(sm));
-        HIPCHK(c, hipGetLastError());
+        if ((r = fetch(c, sm, h_info, d_info, sizeof(mlz::SearchInfo)))) return r;
         st.tabs.assign(h_tabs, h_tabs + nck);
         st.M = h_info->M; st.B = h_info->B; st.info = h_info->ok != 0;
         if (ignore_crc || !st.info) break;
@@ -195,9 +180,7 @@ int64_t dev_reader_search_tables(mlz_dev_reader* rd, hipStream_t sm, bool ignore
         if (desc.empty()) break;
         r = crc_device_locked(c, sm, rd->d_src, desc.data(), int(desc.size()), d_crc);
         if (r) return r;
-        HIPCHK(c, hipMemcpyAsync(h_crc, d_crc, desc.size() * 4, hipMemcpyDeviceToHost, sm));
-        HIPCHK(c, hipStreamSynchronize(sm));
-        HIPCHK(c, hipGetLastError());
+        if ((r = fetch(c, sm, h_crc, d_crc, desc.size() * 4))) return r;
         bool again = false;
         for (size_t i = 0; i < who.size(); i++)
             if (h_crc[i] != st.tabs[who[i]].crc) { skip[who[i]]++; again = true; }   // a broken table: the next one that fits, if there is one
@@ -234,19 +217,19 @@ int64_t dev_reader_search_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t fl
                 for (uint32_t j = 0; j < st.M; j++) v |= uint64_t(pattern[i + j]) << (8 * j);
                 hs[i] = mlz::search_hash(v, st.B, st.M);
             }
-            const size_t o_out = (size_t(nw) * 4 + 15) & ~size_t(15);
-            HIPCHK(c, c->d_rplan.ensure(o_out + nck * 8));
+            Carve cv;
+            const auto r_hs = cv.take<uint32_t>(nw);
+            const auto r_out = cv.take<uint2>(nck);
+            HIPCHK(c, c->d_rplan.ensure(cv.bytes));
             int e = ensure_stream_objects(c, 0, nck * 8);
             if (e) return e;
-            uint32_t* d_hs = c->d_rplan.as<uint32_t>();
-            uint2* d_out = reinterpret_cast<uint2*>(c->d_rplan.as<uint8_t>() + o_out);
+            uint32_t* d_hs = r_hs.at(c->d_rplan.p);
+            uint2* d_out = r_out.at(c->d_rplan.p);
             { WorkspaceOrder order(c, sm); }
             HIPCHK(c, hipMemcpyAsync(d_hs, hs.data(), size_t(nw) * 4, hipMemcpyHostToDevice, sm));
             hipLaunchKernelGGL(mlz::search_probe_kernel, dim3(uint32_t((nck + 63) / 64)), dim3(64), 0, sm, rd->d_src, static_cast<const mlz::SearchTab*>(st.d_tabs), uint32_t(nck), st.B,
                                d_hs, nw, d_out);
-            HIPCHK(c, hipMemcpyAsync(c->pinned2, d_out, nck * 8, hipMemcpyDeviceToHost, sm));
-            HIPCHK(c, hipStreamSynchronize(sm));
-            HIPCHK(c, hipGetLastError());
+            if ((e = fetch(c, sm, c->pinned2, d_out, nck * 8))) return e;
             const uint32_t* as = static_cast<const uint32_t*>(c->pinned2);
             n_take = mlz::search_decoded_set(nck, [&](size_t k) { return as[2 * k]; }, [&](size_t k) { return as[2 * k + 1]; },
                                              [&](size_t k) { return uint64_t(rd->chunks[k].n); }, nw, L, take.data());
@@ -282,60 +265,61 @@ int64_t dev_reader_search_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t fl
         for (size_t i = j0; i < gend[g]; i++) {
             const StreamChunk& ck = rd->chunks[jobs[i].ck];
             if (ck.type == kChunkUncompressed)
-                for (size_t q = 0; q < ck.n; q += kPlacePiece) places.push_back(PlaceDesc{ck.body_off + q, at[i] + q, uint32_t(std::min<size_t>(kPlacePiece, ck.n - q)), 1});
+                place_pieces(ck.body_off, at[i], ck.n, 1, [&](const PlaceDesc& d) { places.push_back(d); });
         }
         place_end[g] = places.size();
     }
     const size_t nt = tiles.size(), np = places.size();
     if (nt > 0x7fffffffu) return -MLZ_ERR_ARG;
-    // workspace: pattern | carried bytes | total | tiles | counts | prefix | bitmaps
-    const size_t o_carry = mlz::kSearchMaxPattern, o_total = o_carry + mlz::kSearchMaxPattern, o_tiles = o_total + 16, o_counts = o_tiles + nt * sizeof(mlz::SearchTile),
-                 o_prefix = (o_counts + nt * 4 + 15) & ~size_t(15), o_masks = o_prefix + nt * 8, ws_bytes = o_masks + nt * mlz::kSearchTileWords * 8;
-    HIPCHK(c, c->d_rplan.ensure(ws_bytes));
+    Carve cv, pin;   // workspace: pattern | carried bytes | total | tiles | counts | prefix | bitmaps; pinned: results | tiles | places | pattern
+    const auto r_pat = cv.take<uint8_t>(mlz::kSearchMaxPattern), r_carry = cv.take<uint8_t>(mlz::kSearchMaxPattern);
+    const auto r_total = cv.take<uint64_t>(2);
+    const auto r_tiles = cv.take<mlz::SearchTile>(nt);
+    const auto r_counts = cv.take<uint32_t>(nt, 4);
+    const auto r_prefix = cv.take<uint64_t>(nt), r_masks = cv.take<uint64_t>(nt * mlz::kSearchTileWords, 8);
+    const ChunkJobResults res = take_chunk_job_results(&pin, jobs.size());
+    const auto r_htiles = pin.take<mlz::SearchTile>(nt, 64);
+    const auto r_hplaces = pin.take<PlaceDesc>(np, 8);
+    const auto r_hpat = pin.take<uint8_t>(mlz::kSearchMaxPattern + 16, 8);
+    HIPCHK(c, c->d_rplan.ensure(cv.bytes));
     HIPCHK(c, c->d_range.ensure(size_t(scratch_max) + 64));
     if (np) HIPCHK(c, c->d_place.ensure(np * sizeof(PlaceDesc)));
-    const size_t p_tiles = (chunk_jobs_pinned(jobs.size()) + 63) & ~size_t(63), p_places = p_tiles + nt * sizeof(mlz::SearchTile), p_pat = p_places + np * sizeof(PlaceDesc);
-    int e = ensure_stream_objects(c, 0, p_pat + mlz::kSearchMaxPattern + 16);
+    int e = ensure_stream_objects(c, 0, pin.bytes);
     if (e) return e;
-    uint8_t* pin = static_cast<uint8_t*>(c->pinned2);
-    if (nt) std::memcpy(pin + p_tiles, tiles.data(), nt * sizeof(mlz::SearchTile));
-    if (np) std::memcpy(pin + p_places, places.data(), np * sizeof(PlaceDesc));
-    std::memcpy(pin + p_pat, pattern, L);
-    uint8_t* ws = c->d_rplan.as<uint8_t>();
-    uint8_t* scratch = c->d_range.as<uint8_t>();
-    mlz::SearchTile* d_tiles = reinterpret_cast<mlz::SearchTile*>(ws + o_tiles);
-    uint32_t* d_counts = reinterpret_cast<uint32_t*>(ws + o_counts);
-    uint64_t* d_prefix = reinterpret_cast<uint64_t*>(ws + o_prefix);
-    uint64_t* d_masks = reinterpret_cast<uint64_t*>(ws + o_masks);
-    uint64_t* d_total = reinterpret_cast<uint64_t*>(ws + o_total);
+    uint8_t *ws = r_pat.at(c->d_rplan.p), *h_pat = r_hpat.at(c->pinned2), *scratch = c->d_range.as<uint8_t>();
+    mlz::SearchTile *d_tiles = r_tiles.at(c->d_rplan.p), *h_tiles = r_htiles.at(c->pinned2);
+    PlaceDesc* h_places = r_hplaces.at(c->pinned2);
+    if (nt) std::memcpy(h_tiles, tiles.data(), nt * sizeof(mlz::SearchTile));
+    if (np) std::memcpy(h_places, places.data(), np * sizeof(PlaceDesc));
+    std::memcpy(h_pat, pattern, L);
+    uint32_t* d_counts = r_counts.at(c->d_rplan.p);
+    uint64_t *d_prefix = r_prefix.at(c->d_rplan.p), *d_masks = r_masks.at(c->d_rplan.p), *d_total = r_total.at(c->d_rplan.p);
     for (size_t i = 0; i < jobs.size(); i++) {
         const StreamChunk& ck = rd->chunks[jobs[i].ck];
         jobs[i].at = ck.type == kChunkUncompressed ? rd->d_src + ck.body_off : scratch + at[i];   // (a stored chunk's CRC: over the stream's own bytes)
     }
     { WorkspaceOrder order(c, sm); }
-    HIPCHK(c, hipMemcpyAsync(ws, pin + p_pat, L, hipMemcpyHostToDevice, sm));
+    HIPCHK(c, hipMemcpyAsync(ws, h_pat, L, hipMemcpyHostToDevice, sm));
     HIPCHK(c, hipMemsetAsync(d_total, 0, 16, sm));
-    if (nt) HIPCHK(c, hipMemcpyAsync(d_tiles, pin + p_tiles, nt * sizeof(mlz::SearchTile), hipMemcpyHostToDevice, sm));
-    if (np) HIPCHK(c, hipMemcpyAsync(c->d_place.p, pin + p_places, np * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
+    if (nt) HIPCHK(c, hipMemcpyAsync(d_tiles, h_tiles, nt * sizeof(mlz::SearchTile), hipMemcpyHostToDevice, sm));
+    if (np) HIPCHK(c, hipMemcpyAsync(c->d_place.p, h_places, np * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
     auto scan_group = [&](size_t g) -> int {
         const size_t t0 = g ? tile_end[g - 1] : 0, t1 = tile_end[g], q0 = g ? place_end[g - 1] : 0, q1 = place_end[g];
         if (q1 > q0) hipLaunchKernelGGL(stream_place2_kernel, dim3(uint32_t(q1 - q0)), dim3(256), 0, sm, rd->d_src, rd->d_src, scratch, c->d_place.as<PlaceDesc>() + q0);
         if (t1 > t0) hipLaunchKernelGGL(mlz::search_scan_kernel, dim3(uint32_t(t1 - t0)), dim3(256), 0, sm, scratch, d_tiles, uint32_t(t0), ws, L, d_masks, d_counts);
         if (carry[g]) {   // the run goes on in the next group: its last bytes in front of that group's first chunk
-            HIPCHK(c, hipMemcpyAsync(ws + o_carry, scratch + used[g] - carry[g], carry[g], hipMemcpyDeviceToDevice, sm));
-            HIPCHK(c, hipMemcpyAsync(scratch + mlz::kSearchPad - carry[g], ws + o_carry, carry[g], hipMemcpyDeviceToDevice, sm));
+            HIPCHK(c, hipMemcpyAsync(ws + r_carry.off, scratch + used[g] - carry[g], carry[g], hipMemcpyDeviceToDevice, sm));
+            HIPCHK(c, hipMemcpyAsync(scratch + mlz::kSearchPad - carry[g], ws + r_carry.off, carry[g], hipMemcpyDeviceToDevice, sm));
         }
         return 0;
     };
-    const int64_t r = stream_run_chunk_jobs(c, sm, ignore_crc, rd->d_src, rd->chunks, jobs, gend, scan_group);
+    const int64_t r = stream_run_chunk_jobs(c, sm, ignore_crc, rd->d_src, rd->chunks, jobs, gend, res, scan_group);
     if (r < 0) return r;
     if (nt == 0) return 0;
     hipLaunchKernelGGL(mlz::search_prefix_kernel, dim3(1), dim3(1024), 0, sm, d_counts, uint32_t(nt), d_prefix, d_total);
     if (cap) hipLaunchKernelGGL(mlz::search_write_kernel, dim3(uint32_t(nt)), dim3(mlz::kSearchTileWords), 0, sm, d_tiles, d_masks, d_prefix, cap, d_offsets);
-    HIPCHK(c, hipMemcpyAsync(pin, d_total, 8, hipMemcpyDeviceToHost, sm));
-    HIPCHK(c, hipStreamSynchronize(sm));
-    HIPCHK(c, hipGetLastError());
-    return int64_t(*reinterpret_cast<const uint64_t*>(pin));
+    if ((e = fetch(c, sm, c->pinned2, d_total, 8))) return e;
+    return int64_t(*static_cast<const uint64_t*>(c->pinned2));
 }
 
 }  // namespace
@@ -348,7 +332,6 @@ extern "C" int64_t mlz_dev_reader_search(mlz_dev_reader* rd, void* stream, uint3
     if (hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
     if (cap && !on_device(c, d_offsets)) return -MLZ_ERR_ARG;
     begin_decode_call(c);
-    const int64_t r = dev_reader_search_locked(rd, static_cast<hipStream_t>(stream), flags, pattern, uint32_t(pattern_len), d_offsets, uint64_t(cap), stats);
-    if (r < 0) (void)hipStreamSynchronize(static_cast<hipStream_t>(stream));   // nothing of a failed call is left in flight
-    return r;
+    hipStream_t sm = static_cast<hipStream_t>(stream);
+    return settled(sm, dev_reader_search_locked(rd, sm, flags, pattern, uint32_t(pattern_len), d_offsets, uint64_t(cap), stats));
 }

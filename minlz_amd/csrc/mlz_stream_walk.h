@@ -49,13 +49,19 @@ MLZ_WALK_HD int walk_uvarint(const uint8_t* b, size_t n, uint64_t* out) {
 // and it never enters the table.
 MLZ_WALK_HD bool walk_skippable(uint8_t type, uint64_t clen, uint64_t left /* bytes behind the header */) { return type > 0x3f && type != 0xff && left >= clen; }
 
+// The 4-byte header of the chunk at p (p + 4 <= n): the length of what follows; *type: the chunk's type
+MLZ_WALK_HD uint32_t walk_header(const uint8_t* src, uint64_t p, uint8_t* type) {
+    *type = src[p];
+    return uint32_t(src[p + 1]) | uint32_t(src[p + 2]) << 8 | uint32_t(src[p + 3]) << 16;
+}
+
 // The record of the chunk whose header is at p (p < n).  Reads src[p .. min(n, p + 4 + 14)) and nothing else.
 MLZ_WALK_HD WalkChunk walk_classify(const uint8_t* src, uint64_t n, uint64_t p) {
     WalkChunk w{};
     w.off = p;
     if (n - p < 4) { w.flags = kWalkStub; return w; }
-    const uint8_t type = src[p];
-    const uint32_t clen = uint32_t(src[p + 1]) | uint32_t(src[p + 2]) << 8 | uint32_t(src[p + 3]) << 16;
+    uint8_t type;
+    const uint32_t clen = walk_header(src, p, &type);
     w.tl = uint32_t(type) << 24 | clen;
     const uint8_t* b = src + p + 4;
     const uint64_t left = n - (p + 4);

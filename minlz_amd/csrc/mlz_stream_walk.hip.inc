@@ -159,8 +159,8 @@ __global__ __launch_bounds__(64) void walk_list_kernel(const uint8_t* __restrict
                 cnt++;
                 break;
             }
-            const uint8_t type = src[e];
-            const uint32_t clen = uint32_t(src[e + 1]) | uint32_t(src[e + 2]) << 8 | uint32_t(src[e + 3]) << 16;
+            uint8_t type;
+            const uint32_t clen = walk_header(src, e, &type);
             if (!walk_skippable(type, clen, n - e - 4)) {
                 if (EMIT) table[at + cnt] = walk_classify(src, n, e);
                 cnt++;
@@ -179,17 +179,9 @@ __global__ __launch_bounds__(1024) void walk_scan_kernel(const uint32_t* __restr
     const uint32_t b = tid * per < nreg0 ? tid * per : nreg0, e = b + per < nreg0 ? b + per : nreg0;
     uint32_t s = 0;
     for (uint32_t i = b; i < e; i++) s += counts[i];
-    sums[tid] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        const uint32_t add = tid >= d ? sums[tid - d] : 0;
-        __syncthreads();
-        sums[tid] += add;
-        __syncthreads();
-    }
-    uint32_t run = sums[tid] - s;
+    uint32_t sum, run = wg_scan<1024>(s, sums, tid, [](uint32_t x, uint32_t y) { return x + y; }, &sum);
     for (uint32_t i = b; i < e; i++) { first[i] = run; run += counts[i]; }
-    if (tid == 1023) total[0] = sums[1023];
+    if (tid == 1023) total[0] = sum;
 }
 
 }  // namespace mlz
@@ -197,6 +189,33 @@ __global__ __launch_bounds__(1024) void walk_scan_kernel(const uint32_t* __restr
 namespace {
 
 constexpr uint64_t kWalkMaxStream = uint64_t(1) << 36;   // (the table's entries are counted in 32 bits: one per 4 bytes at the most)
+
+// The per-device context that serves a call on the stream d_src[0, n) (an empty stream: any device), or nullptr: an argument error
+mlz_ctx* stream_ctx(mlz_ctx* c, const uint8_t* d_src, size_t n) {
+    if (!c || (!d_src && n) || uint64_t(n) > kWalkMaxStream) return nullptr;
+    if (n && !(c = owner_of(c, d_src))) return nullptr;
+    return c->kids.empty() ? c : c->kids[0];
+}
+
+bool on_device(const mlz_ctx* c, const void* p) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != c->device) { (void)hipGetLastError(); return false; }
+    return true;
+}
+
+// `bytes` from device memory to the host, waited for; an error of anything sm was given before shows here too
+int fetch(mlz_ctx* c, hipStream_t sm, void* host, const void* dev, size_t bytes) {
+    HIPCHK(c, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, sm));
+    HIPCHK(c, hipStreamSynchronize(sm));
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// The result of a call's body as the entry point returns it: nothing of a failed call is left in flight
+int64_t settled(hipStream_t sm, int64_t r) {
+    if (r < 0) (void)hipStreamSynchronize(sm);
+    return r;
+}
 
 // The chunk walk of d_src[0, n) on c's device: `chunks` = the data chunks in front of the first framing error, *parsed = what stream_parse
 // returns for the same bytes.  Returns 0 or -MLZ_ERR_HIP.  Synchronous on st.  Caller holds c->mu.
@@ -207,24 +226,20 @@ int stream_walk_device(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, size_t 
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t nreg0 = (uint64_t(n) + kWalkR0 - 1) >> kWalkR0Log, nreg1 = (uint64_t(n) + kWalkR1 - 1) >> kWalkR1Log;
     const size_t xlen = (size_t(n) + 3) & ~size_t(3);
-    // x0 | x1 | entry1 | entry0 | counts | first | total
-    const size_t o_x1 = xlen * 4, o_e1 = o_x1 + xlen * 4, o_e0 = o_e1 + size_t(nreg1) * 8, o_cnt = o_e0 + size_t(nreg0) * 4, o_first = o_cnt + size_t(nreg0) * 4,
-                 o_total = (o_first + size_t(nreg0) * 4 + 15) & ~size_t(15);
-    HIPCHK(c, c->d_walk.ensure(o_total + 16));
+    Carve cv;   // x0 | x1 | entry1 | entry0 | counts | first | total; entry1 and entry0 lie side by side: one memset clears both
+    const auto r_x0 = cv.take<uint32_t>(xlen), r_x1 = cv.take<uint32_t>(xlen);
+    const auto r_e1 = cv.take<uint64_t>(size_t(nreg1));
+    const auto r_e0 = cv.take<uint32_t>(size_t(nreg0), 4), r_cnt = cv.take<uint32_t>(size_t(nreg0), 4), r_first = cv.take<uint32_t>(size_t(nreg0), 4), r_total = cv.take<uint32_t>(4);
+    HIPCHK(c, c->d_walk.ensure(cv.bytes));
     int r = ensure_stream_objects(c, 0, 64);
     if (r) return r;
-    uint8_t* ws = c->d_walk.as<uint8_t>();
-    uint32_t* x0 = reinterpret_cast<uint32_t*>(ws);
-    uint32_t* x1 = reinterpret_cast<uint32_t*>(ws + o_x1);
-    uint64_t* entry1 = reinterpret_cast<uint64_t*>(ws + o_e1);
-    uint32_t* entry0 = reinterpret_cast<uint32_t*>(ws + o_e0);
-    uint32_t* counts = reinterpret_cast<uint32_t*>(ws + o_cnt);
-    uint32_t* first = reinterpret_cast<uint32_t*>(ws + o_first);
-    uint32_t* total = reinterpret_cast<uint32_t*>(ws + o_total);
+    void* ws = c->d_walk.p;
+    uint32_t *x0 = r_x0.at(ws), *x1 = r_x1.at(ws), *entry0 = r_e0.at(ws), *counts = r_cnt.at(ws), *first = r_first.at(ws), *total = r_total.at(ws);
+    uint64_t* entry1 = r_e1.at(ws);
     uint32_t h_total = 0;
     {
         WorkspaceOrder order(c, st);
-        HIPCHK(c, hipMemsetAsync(ws + o_e1, 0xff, o_cnt - o_e1, st));   // entry1 and entry0: no entry
+        HIPCHK(c, hipMemsetAsync(entry1, 0xff, r_cnt.off - r_e1.off, st));   // entry1 and entry0: no entry
         hipLaunchKernelGGL(mlz::walk_exit_kernel, dim3(uint32_t(nreg0)), dim3(mlz::kWalkThreads), 0, st, d_src, uint64_t(n), x0);
         hipLaunchKernelGGL(mlz::walk_lift_kernel, dim3(uint32_t((xlen / 4 + 255) / 256)), dim3(256), 0, st, uint64_t(n), x0, x1);
         hipLaunchKernelGGL(mlz::walk_top_kernel, dim3(1), dim3(64), 0, st, uint64_t(n), x1, entry1);
@@ -232,9 +247,7 @@ int stream_walk_device(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, size_t 
         hipLaunchKernelGGL(mlz::walk_list_kernel<false>, dim3(uint32_t((nreg0 + 63) / 64)), dim3(64), 0, st, d_src, uint64_t(n), uint32_t(nreg0), entry0, counts, first,
                            static_cast<mlz::WalkChunk*>(nullptr));
         hipLaunchKernelGGL(mlz::walk_scan_kernel, dim3(1), dim3(1024), 0, st, counts, uint32_t(nreg0), first, total);
-        HIPCHK(c, hipMemcpyAsync(c->pinned2, total, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        HIPCHK(c, hipGetLastError());
+        if ((r = fetch(c, st, c->pinned2, total, 4))) return r;
         h_total = *static_cast<uint32_t*>(c->pinned2);
         if (h_total) {
             HIPCHK(c, c->d_walk_tab.ensure(size_t(h_total) * sizeof(mlz::WalkChunk)));
@@ -242,9 +255,7 @@ int stream_walk_device(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, size_t 
             if (r) return r;
             mlz::WalkChunk* tab = c->d_walk_tab.as<mlz::WalkChunk>();
             hipLaunchKernelGGL(mlz::walk_list_kernel<true>, dim3(uint32_t((nreg0 + 63) / 64)), dim3(64), 0, st, d_src, uint64_t(n), uint32_t(nreg0), entry0, counts, first, tab);
-            HIPCHK(c, hipMemcpyAsync(c->pinned2, tab, size_t(h_total) * sizeof(mlz::WalkChunk), hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-            HIPCHK(c, hipGetLastError());
+            if ((r = fetch(c, st, c->pinned2, tab, size_t(h_total) * sizeof(mlz::WalkChunk)))) return r;
         }
     }
     chunks->reserve(h_total);
@@ -261,25 +272,27 @@ int stream_walk_device(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, size_t 
 // for its CRC.  The targets of one list may lie in several allocations (the caller's destination, the context's scratch, the stream itself).
 struct ChunkJob { size_t ck; const uint8_t* at; };
 
-constexpr size_t chunk_jobs_pinned(size_t nj) { return nj * 16 + 64; }   // bytes of c->pinned2 a list of nj jobs takes, from its start
+// What comes back per job, in c->pinned2: the caller takes the regions from its carve of that buffer, in front of its last ensure
+struct ChunkJobResults { Region<int64_t> len; Region<uint32_t> crc; };
+ChunkJobResults take_chunk_job_results(Carve* pin, size_t nj) { return ChunkJobResults{pin->take<int64_t>(nj), pin->take<uint32_t>(nj, 4)}; }
 
 // The decode / CRC / verdict of a list of chunks of a stream that lies at d_src, shared by the whole-stream call and the range read.  jobs: in
 // stream order; gend[g]: one past the last job of group g (range_group_ends: about 64 MiB of chunk output).  Per group one decode launch
 // sequence (token-only mode: d_src is not touched) and one CRC launch over all its chunks — 0x01 / 0x02 over the bytes at `at`, 0x03 over the
 // token bytes in the stream —, each with the lowest target address as its base pointer and the targets' distances from it in the descriptors;
 // after_group(g) is then called with sm still running (the range read enqueues the group's copy there).  One synchronise at the end; per chunk
-// 8 + 4 bytes of results come back.  The caller has begun the decode call, sized c->pinned2 (chunk_jobs_pinned(jobs.size()) bytes at its
-// start are used here) and holds c->mu.  Returns 0 or the error of the first failing chunk of the list.
+// 8 + 4 bytes of results come back, to `res`.  The caller has begun the decode call, sized c->pinned2 for its carve (res is part of it)
+// and holds c->mu.  Returns 0 or the error of the first failing chunk of the list.
 template <class AfterGroup>
 int64_t stream_run_chunk_jobs(mlz_ctx* c, hipStream_t sm, bool ignore_crc, const uint8_t* d_src, const std::vector<StreamChunk>& chunks,
-                              const std::vector<ChunkJob>& jobs, const std::vector<size_t>& gend, AfterGroup after_group) {
+                              const std::vector<ChunkJob>& jobs, const std::vector<size_t>& gend, const ChunkJobResults& res, AfterGroup after_group) {
     const size_t nj = jobs.size();
     if (nj == 0) return 0;
     HIPCHK(c, c->d_len.ensure(sizeof(int64_t) * nj));
     HIPCHK(c, c->d_crc.ensure(sizeof(uint32_t) * nj + 64));
-    if (c->pinned2_cap < chunk_jobs_pinned(nj)) { c->err = "stream_run_chunk_jobs: the result buffer was not sized"; return -MLZ_ERR_HIP; }
-    int64_t* h_len = static_cast<int64_t*>(c->pinned2);
-    uint32_t* h_crc = reinterpret_cast<uint32_t*>(h_len + nj);
+    if (c->pinned2_cap < res.crc.off + sizeof(uint32_t) * nj) { c->err = "stream_run_chunk_jobs: the result buffer was not sized"; return -MLZ_ERR_HIP; }
+    int64_t* h_len = res.len.at(c->pinned2);
+    uint32_t* h_crc = res.crc.at(c->pinned2);
     std::vector<mlz_block_desc> ddesc, cdesc;
     std::vector<size_t> res_idx(nj, 0);
     size_t n_dec = 0;
@@ -339,15 +352,17 @@ int64_t stream_decode_chunks_device(mlz_ctx* c, hipStream_t sm, bool ignore_crc,
     size_t n_place = 0;
     for (const StreamChunk& ck : chunks)
         if (ck.type == kChunkUncompressed) n_place += (ck.n + kPlacePiece - 1) / kPlacePiece;
-    int r = ensure_stream_objects(c, 0, chunk_jobs_pinned(nck) + 64 + n_place * sizeof(PlaceDesc));
+    Carve pin;
+    const ChunkJobResults res = take_chunk_job_results(&pin, nck);
+    const auto r_place = pin.take<PlaceDesc>(n_place, 64);
+    int r = ensure_stream_objects(c, 0, pin.bytes);
     if (r) return r;
-    PlaceDesc* h_place = reinterpret_cast<PlaceDesc*>((reinterpret_cast<uintptr_t>(static_cast<uint8_t*>(c->pinned2) + chunk_jobs_pinned(nck)) + 63) & ~uintptr_t(63));
     if (n_place) {   // stored chunks: 64 KiB pieces, one launch
+        HIPCHK(c, c->d_place.ensure(n_place * sizeof(PlaceDesc)));
+        PlaceDesc* h_place = r_place.at(c->pinned2);
         size_t q = 0;
         for (const StreamChunk& ck : chunks)
-            if (ck.type == kChunkUncompressed)
-                for (size_t o = 0; o < ck.n; o += kPlacePiece) h_place[q++] = PlaceDesc{ck.body_off + o, ck.out_off + o, uint32_t(std::min<size_t>(kPlacePiece, ck.n - o)), 0};
-        HIPCHK(c, c->d_place.ensure(n_place * sizeof(PlaceDesc)));
+            if (ck.type == kChunkUncompressed) place_pieces(ck.body_off, ck.out_off, ck.n, 0, [&](const PlaceDesc& d) { h_place[q++] = d; });
         HIPCHK(c, hipMemcpyAsync(c->d_place.p, h_place, n_place * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
         hipLaunchKernelGGL(stream_place2_kernel, dim3(uint32_t(n_place)), dim3(256), 0, sm, d_src, d_src, d_dst, c->d_place.as<PlaceDesc>());
     }
@@ -355,7 +370,7 @@ int64_t stream_decode_chunks_device(mlz_ctx* c, hipStream_t sm, bool ignore_crc,
     for (size_t i = 0; i < nck; i++) jobs[i] = ChunkJob{i, d_dst + chunks[i].out_off};
     std::vector<size_t> gend;
     mlz::range_group_ends(nck, [&](size_t i) { return uint64_t(chunks[i].n); }, &gend);
-    return stream_run_chunk_jobs(c, sm, ignore_crc, d_src, chunks, jobs, gend, [](size_t) { return 0; });
+    return stream_run_chunk_jobs(c, sm, ignore_crc, d_src, chunks, jobs, gend, res, [](size_t) { return 0; });
 }
 
 }  // namespace
@@ -363,9 +378,7 @@ int64_t stream_decode_chunks_device(mlz_ctx* c, hipStream_t sm, bool ignore_crc,
 extern "C" {
 
 int64_t mlz_stream_decoded_len_device(mlz_ctx* c, void* stream, const uint8_t* d_src, size_t n, uint64_t* prefix_len) {
-    if (!c || (!d_src && n) || uint64_t(n) > kWalkMaxStream) return -MLZ_ERR_ARG;
-    if (n && !(c = owner_of(c, d_src))) return -MLZ_ERR_ARG;
-    if (!c->kids.empty()) c = c->kids[0];   // (an empty stream: any device)
+    if (!(c = stream_ctx(c, d_src, n))) return -MLZ_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     std::vector<StreamChunk> chunks;
     int64_t r = 0;
@@ -376,9 +389,7 @@ int64_t mlz_stream_decoded_len_device(mlz_ctx* c, void* stream, const uint8_t* d
 }
 
 int64_t mlz_stream_decode_device(mlz_ctx* c, void* stream, uint32_t flags, const uint8_t* d_src, size_t n, uint8_t* d_dst, size_t dst_cap) {
-    if (!c || (!d_src && n) || (!d_dst && dst_cap) || uint64_t(n) > kWalkMaxStream) return -MLZ_ERR_ARG;
-    if (n && !(c = owner_of(c, d_src))) return -MLZ_ERR_ARG;
-    if (!c->kids.empty()) c = c->kids[0];
+    if ((!d_dst && dst_cap) || !(c = stream_ctx(c, d_src, n))) return -MLZ_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0;

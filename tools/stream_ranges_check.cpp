@@ -42,7 +42,7 @@ int main(int argc, char** argv) {
     if (!f) { std::perror(argv[1]); return 2; }
     uint64_t head[4];
     std::vector<uint64_t> raw;
-    std::vector<RangeChunk> ck;
+    std::vector<RdevChunk> ck;
     std::vector<ByteRange> rg;
     std::vector<uint8_t> data, dst, scratch;
     RangePlan plan;
@@ -56,7 +56,7 @@ int main(int argc, char** argv) {
             if (!get(f, raw.data(), raw.size() * 8)) { std::fprintf(stderr, "short file\n"); return 2; }
             ck.resize(size_t(nck));
             size = 0;
-            for (size_t i = 0; i < nck; i++) { ck[i] = RangeChunk{size, raw[2 * i], uint8_t(raw[2 * i + 1])}; size += raw[2 * i]; }
+            for (size_t i = 0; i < nck; i++) { ck[i] = RdevChunk{size, size, uint32_t(raw[2 * i]), uint32_t(raw[2 * i + 1])}; size += raw[2 * i]; }
         }
         rg.resize(size_t(nr));
         static_assert(sizeof(ByteRange) == 24, "three u64s");
@@ -81,7 +81,7 @@ int main(int argc, char** argv) {
             for (const RangeGroup& g : plan.groups) {
                 for (size_t t = g.t0; t < g.t1; t++) {
                     const RangeTouched& tc = plan.touched[t];
-                    const RangeChunk& c = ck[tc.chunk];
+                    const RdevChunk& c = ck[tc.chunk];
                     if (tc.where == kRangeDirect) {
                         if (tc.at + c.n > dst.size()) { bad = true; continue; }
                         std::memcpy(dst.data() + tc.at, data.data() + c.out_off, size_t(c.n));
@@ -94,7 +94,7 @@ int main(int argc, char** argv) {
                 for (size_t s = g.s0; s < g.s1; s++) {
                     const RangeSeg& sg = plan.segs[s];
                     const RangeTouched& tc = plan.touched[sg.touched];
-                    const RangeChunk& c = ck[tc.chunk];
+                    const RdevChunk& c = ck[tc.chunk];
                     // (a segment of another group's chunk, or of a direct one, would be a planner's fault)
                     if (sg.touched < g.t0 || sg.touched >= g.t1 || tc.where == kRangeDirect || sg.rel + sg.len > c.n || sg.dst_off + sg.len > dst.size()) { bad = true; continue; }
                     const uint8_t* from = tc.where == kRangeStored ? data.data() + c.out_off + sg.rel : scratch.data() + tc.at + sg.rel;

@@ -46,7 +46,6 @@ int main(int argc, char** argv) {
     if (!f) { std::perror(argv[1]); return 2; }
     uint64_t head[4];
     std::vector<uint64_t> raw, off, len;
-    std::vector<RangeChunk> hck;
     std::vector<RdevChunk> ck;
     std::vector<ByteRange> rg;
     std::vector<uint8_t> data, dst, scratch;
@@ -58,10 +57,9 @@ int main(int argc, char** argv) {
         if (!reuse) {
             raw.resize(size_t(nck64) * 2);
             if (!get(f, raw.data(), raw.size() * 8)) { std::fprintf(stderr, "short file\n"); return 2; }
-            hck.resize(size_t(nck64)); ck.resize(size_t(nck64));
+            ck.resize(size_t(nck64));
             size = 0;
             for (size_t i = 0; i < nck64; i++) {
-                hck[i] = RangeChunk{size, raw[2 * i], uint8_t(raw[2 * i + 1])};
                 ck[i] = RdevChunk{size, size, uint32_t(raw[2 * i]), uint32_t(raw[2 * i + 1])};   // (a stored chunk's body: the decoded bytes themselves)
                 size += raw[2 * i];
             }
@@ -124,7 +122,7 @@ int main(int argc, char** argv) {
             uint64_t s = 0;
             for (size_t i = 0; i < n; i++) { rg[i] = ByteRange{off[i], len[i], s}; s += len[i]; }
         }
-        const int prc = plan_ranges(hck.data(), hck.size(), size, rg.data(), rg.size(), dst_cap, &plan);
+        const int prc = plan_ranges(ck.data(), ck.size(), size, rg.data(), rg.size(), dst_cap, &plan);
         if (prc != rc) diff |= 1;
         if (rc < 0) { std::printf("%d 0 0 0 0 0 0 0 %u\n", rc, diff); continue; }
         for (size_t i = 0; i < n; i++) if (rdev_start(len_block.data(), len_local.data(), i) != rg[i].dst_off) diff |= 32;
@@ -178,7 +176,7 @@ int main(int argc, char** argv) {
                         if (i >= n || len[i] <= kShortMax || q * kPiece >= len[i]) { diff |= 64; continue; }
                         const uint64_t o = off[i], end = o + len[i], start = rdev_start(len_block.data(), len_local.data(), i);
                         const uint64_t wb = o + q * kPiece, we = end - wb > kPiece ? wb + kPiece : end;
-                        for (uint32_t j = q ? rdev_locate(ck.data(), nck, avg, wb) : first[i]; j < nck && ck[j].out_off < we; j++) {
+                        for (uint32_t j = q ? range_locate(ck.data(), nck, avg, wb) : first[i]; j < nck && ck[j].out_off < we; j++) {
                             if (!ck[j].n) continue;
                             if (rdev_intersect(ck[j], places[slot[j]], uint32_t(g), o, start, wb, we, &src, &to, &cn, &from_stream)) copy(ck[j]);
                         }
