@@ -164,7 +164,8 @@ int mlz_crc_batch_device(mlz_ctx* ctx, void* stream, const uint8_t* d_base, cons
 #define MLZ_STREAM_ADD_INDEX 1u
 #define MLZ_STREAM_IGNORE_CRC 2u
 /* Block search tables (SPEC_SEARCH.md; the reference's Writer with search tables and WithoutCompression(), table type 1): honoured by
- * mlz_stream_encode_gather_device and mlz_stream_bound only — mlz_stream_encode returns -MLZ_ERR_ARG when it is set.  See below. */
+ * mlz_stream_encode_gather_device and mlz_stream_bound only — mlz_stream_encode returns -MLZ_ERR_ARG when it is set.  See below; table types 2 and 3
+ * (byte prefixes) are configured with an mlz_search_tables through mlz_stream_encode_gather_device_tables. */
 #define MLZ_STREAM_SEARCH_TABLES 4u
 #define MLZ_STREAM_SEARCH_MATCH_LEN(m) ((uint32_t)(m) << 8) /* bits 8..11; 0 = the reference's default 6; 1..8 valid; 9..15: -MLZ_ERR_ARG */
 int64_t mlz_stream_bound(uint64_t n, uint32_t block_size, uint32_t flags); /* dst_cap that always suffices */
@@ -193,9 +194,34 @@ int64_t mlz_stream_decode(mlz_ctx* ctx, uint32_t flags, const uint8_t* src, size
  * halves R times, while at most a quarter of the folded bits are set and 32 bytes remain.  Two kernels build and fold the tables over the raw blocks in HBM;
  * 12 more bytes per block visit the host (table bytes or 0, R, CRC).  The seek index names a block by the offset at which its chunks start: its table chunk
  * when it has one.  mlz_stream_bound with the flag adds 7 + (12 + max(32, 2^(B - 3))) per block.  Without the flag every byte is what it was before the
- * flag existed.  Out of scope: prefix tables (types 2 to 4), compressed tables (0x46), sidecars and remote references (0x47). */
+ * flag existed.  Out of scope: the long prefix (type 4), compressed tables (0x46), sidecars and remote references (0x47). */
 int64_t mlz_stream_encode_gather_device(mlz_ctx* ctx, int level, uint32_t block_size, uint32_t flags, const uint8_t* const* d_src, const size_t* src_len,
                                         int n_ranges, uint8_t* d_dst, size_t dst_cap);
+
+/* Search tables with byte prefixes (SPEC_SEARCH.md 3.3; the reference's WithBytePrefix / WithMaskPrefix): table type 2 (1 to 8 prefix byte values) and
+ * type 3 (a 256-bit mask of them: value v is a prefix byte when prefix[v >> 3] >> (v & 7) & 1; an empty mask is valid).  A flags word cannot carry a byte
+ * set, hence the struct.  The info chunk is `44 len24 | T M B | field` and a table chunk `45 len24 | T M B | field | R | crc32le | table`, the field being
+ * 8 bytes for type 2 (the values in the order given, unused places repeat the last one) and the 32 mask bytes for type 3.  A block's table holds bit
+ * HashValue(window at q, B, M) for the positions q whose preceding byte block[q - 1] is a prefix byte: 1 <= q <= n in a block of n bytes that is not the
+ * stream's last (position n is the window that lies wholly in the next block's first M bytes, zeros beyond a shorter one; across ranges 8 bytes of the next
+ * range visit the host), 1 <= q <= n - M in the last; position 0 belongs to the block before.  A fold is accepted while at most a tenth of the folded bits
+ * are set (type 1: a quarter); a block without any indexed position gets the all-zero table of 32 bytes (R = B - 8), which lets a searcher skip it.  The
+ * 70 % rule, the 32-byte minimum, stored blocks (no table), the table's place in front of its block and the seek index are as for type 1.
+ * mlz_stream_encode_gather_device_tables: cfg == NULL is mlz_stream_encode_gather_device.  With a cfg, flags must not carry MLZ_STREAM_SEARCH_TABLES or
+ *   match-length bits; table_type 1 gives the bytes the flag gives for the same match length.  -MLZ_ERR_ARG: those flags, a type outside 1 .. 3,
+ *   match_len > 8, type 2 with n_prefix outside 1 .. 8, reserved != 0.
+ * mlz_stream_bound_tables: the dst_cap that always suffices for that call: mlz_stream_bound without tables + 7 + f + (12 + f + max(32, 2^(B - 3))) per
+ *   block, f = 0, 8 or 32 bytes of prefix field.  cfg == NULL is mlz_stream_bound. */
+typedef struct {
+    uint8_t table_type; /* 1, 2 or 3 */
+    uint8_t match_len;  /* 0 = 6; 1 .. 8 */
+    uint8_t n_prefix;   /* type 2: 1 .. 8 values in prefix[0 .. n_prefix); ignored otherwise */
+    uint8_t reserved;   /* 0 */
+    uint8_t prefix[32]; /* type 2: the values; type 3: the mask */
+} mlz_search_tables;
+int64_t mlz_stream_bound_tables(uint64_t n, uint32_t block_size, uint32_t flags, const mlz_search_tables* cfg);
+int64_t mlz_stream_encode_gather_device_tables(mlz_ctx* ctx, int level, uint32_t block_size, uint32_t flags, const mlz_search_tables* cfg,
+                                               const uint8_t* const* d_src, const size_t* src_len, int n_ranges, uint8_t* d_dst, size_t dst_cap);
 
 /* The device-resident Reader: the stream lies in HBM at d_src (n bytes), on a device of the context; the call runs on that device (-MLZ_ERR_ARG if none
  * of the context's devices holds d_src, as for the *_batch_device calls; one HBM-resident stream is not fanned out over several devices).  `stream` is
@@ -273,22 +299,26 @@ int64_t mlz_dev_reader_read_device(mlz_dev_reader* reader, void* stream, uint32_
 void mlz_dev_reader_close(mlz_dev_reader* reader);
 
 /* Pattern search over a stream that lies in HBM, with the reference's block search tables (SPEC_SEARCH.md; search_table.go, search_index.go) where
- * the stream has them: table type 1 (no prefix) in uncompressed table chunks (0x45) behind an info chunk (0x44).  Prefix tables (types 2 to 4),
- * compressed tables (0x46) and remote references (0x47) are stepped over: their blocks count as having no table.
+ * the stream has them: table types 1 (no prefix), 2 (1 to 8 prefix byte values) and 3 (a mask of prefix byte values) in uncompressed table chunks
+ * (0x45) behind an info chunk (0x44).  Long-prefix tables (type 4), compressed tables (0x46) and remote references (0x47) are stepped over: their
+ * blocks count as having no table.
  *
  * mlz_dev_reader_search: returns the number of positions p of the decoded stream with decoded[p, p + pattern_len) == pattern (overlapping occurrences
  *   count; the value may exceed cap); d_offsets (on the handle's device; may be NULL when cap == 0) receives the min(total, cap) smallest positions in
  *   ascending order and nothing beyond them is written.  `pattern` is host memory, pattern_len 1 .. 256.  -MLZ_ERR_ARG: pattern_len 0 or above 256, a
  *   NULL pattern, d_offsets NULL with cap > 0 or not on the handle's device.  Synchronous; `stream` as for mlz_dev_reader_read.
- *   Tables: (M, B) is that of the stream's info chunk, the first 0x44 between the identifier and the first data chunk.  A data chunk's table is the first
- *   0x45 chunk between the previous data chunk's end and its own start whose type is 1, whose M and B are the stream's, with R <= B - 8, a payload of
- *   8 + 2^(B - R - 3) bytes and a good CRC (not checked under MLZ_STREAM_IGNORE_CRC).  Anything else — no info chunk, pattern_len < M, a broken CRC —
- *   means the chunk has no usable table.  The tables are located by a kernel (one lane per data chunk) and their CRCs checked once per handle.
+ *   Tables: (T, M, B, prefix field) is that of the stream's info chunk, the first 0x44 between the identifier and the first data chunk, when its type
+ *   is 1, 2 or 3 and its payload holds the field.  A data chunk's table is the first 0x45 chunk between the previous data chunk's end and its own start
+ *   whose T, M, B and prefix field are byte-equal to the stream's, with R <= B - 8, a payload of 8 + field + 2^(B - R - 3) bytes and a good CRC (not checked
+ *   under MLZ_STREAM_IGNORE_CRC).  Anything else — no info chunk, pattern_len < M, a broken CRC — means the chunk has no usable table.  The tables are located by a kernel (one lane per data chunk) and their CRCs checked once per handle.
  *   Plan: the pattern's pattern_len - M + 1 windows are looked up in every table; a chunk is a candidate when all are present in its own table, or
  *   when its table holds the first j and the next chunk's the others for some 1 <= j (SPEC_SEARCH B.4.1; a next chunk without a usable table or of
  *   fewer than pattern_len bytes holds everything).  Exactly the candidates and the chunks that hold any of the pattern_len - 1 bytes behind a
  *   candidate's end are decoded (stored chunks: copied), each once, with their CRCs as in mlz_dev_reader_read; chunks without a usable table are always
  *   candidates.  Errors as for mlz_dev_reader_read: the first failing decoded chunk in stream order; a broken chunk the plan skips goes unnoticed.
+ *   Prefix tables (types 2 and 3): the windows looked up are those that start at 1 <= i <= pattern_len - M behind a prefix byte pattern[i - 1] — the only
+ *   ones a block indexes, each in the block that holds the byte in front of it.  Without any such window the tables cannot serve the pattern: every data
+ *   chunk is decoded and the third statistic is 0.  The split rule is the same over these windows, with j >= 0 when pattern[0] is no prefix byte.
  *   MLZ_SEARCH_NO_TABLES: every data chunk is decoded and scanned (cross-checks, the timing baseline).
  *   stats (host, may be NULL) receives: data chunks of the stream, chunks decoded or copied, chunks with a usable table, 0.  mlz_get_counter 10 / 11
  *   report the second and third for the context's last search.

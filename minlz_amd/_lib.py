@@ -20,12 +20,18 @@ SYMBOLS = [
     "mlz_stream_decoded_len_device", "mlz_stream_decode_device",
     "mlz_stream_open_device", "mlz_dev_reader_size", "mlz_dev_reader_read", "mlz_dev_reader_close",
     "mlz_dev_reader_read_device", "mlz_dev_reader_search",
+    "mlz_stream_bound_tables", "mlz_stream_encode_gather_device_tables",
 ]
 
 
 class Range(C.Structure):
     """mlz_range: decoded bytes [off, off + len) -> d_dst[dst_off, dst_off + len)."""
     _fields_ = [("off", C.c_uint64), ("len", C.c_uint64), ("dst_off", C.c_uint64)]
+
+
+class SearchTables(C.Structure):
+    """mlz_search_tables: table type 1, 2 (n_prefix byte values in prefix) or 3 (prefix = a 256-bit mask), match length (0 = 6)."""
+    _fields_ = [("table_type", C.c_uint8), ("match_len", C.c_uint8), ("n_prefix", C.c_uint8), ("reserved", C.c_uint8), ("prefix", C.c_uint8 * 32)]
 
 
 class BlockDesc(C.Structure):
@@ -77,6 +83,9 @@ def lib():
     L.mlz_stream_decoded_prefix_len.argtypes = [vp, sz]; L.mlz_stream_decoded_prefix_len.restype = i64
     L.mlz_stream_encode_gather_device.argtypes = [vp, i32, u32, u32, C.POINTER(vp), C.POINTER(sz), i32, vp, sz]
     L.mlz_stream_encode_gather_device.restype = i64
+    L.mlz_stream_bound_tables.argtypes = [u64, u32, u32, C.POINTER(SearchTables)]; L.mlz_stream_bound_tables.restype = i64
+    L.mlz_stream_encode_gather_device_tables.argtypes = [vp, i32, u32, u32, C.POINTER(SearchTables), C.POINTER(vp), C.POINTER(sz), i32, vp, sz]
+    L.mlz_stream_encode_gather_device_tables.restype = i64
     L.mlz_stream_decode.argtypes = [vp, u32, vp, sz, vp, sz]; L.mlz_stream_decode.restype = i64
     L.mlz_stream_decoded_len_device.argtypes = [vp, vp, vp, sz, C.POINTER(u64)]; L.mlz_stream_decoded_len_device.restype = i64
     L.mlz_stream_decode_device.argtypes = [vp, vp, u32, vp, sz, vp, sz]; L.mlz_stream_decode_device.restype = i64

@@ -130,12 +130,22 @@ class Context:
         if r:
             _raise(r, self)
 
-    def stream_encode_gather_device(self, level, block_size, add_index, d_srcs, lens, d_dst, dst_cap, search_match_len=None):
+    def stream_encode_gather_device(self, level, block_size, add_index, d_srcs, lens, d_dst, dst_cap, search_match_len=None, search_prefix=None):
         """mlz_stream_encode_gather_device: ranges of one stream resident on the context's devices -> the framed stream in d_dst (device memory).
         search_match_len: None = no search tables; 0 = block search tables with the reference's default match length (6); 1 .. 8 = with that one.
+        search_prefix (with search_match_len): an iterable of byte values; the tables then index only the positions behind one of them
+        (mlz_stream_encode_gather_device_tables: 1 to 8 distinct values give table type 2, in sorted order, more give type 3).
         Returns the stream size."""
         n = len(d_srcs)
         sp = (C.c_void_p * n)(*d_srcs); sl = (C.c_size_t * n)(*lens)
+        if search_prefix is not None:
+            if search_match_len is None:
+                raise ValueError("search_prefix needs search_match_len")
+            cfg = search_tables_config(search_match_len, search_prefix)
+            r = _lib.lib().mlz_stream_encode_gather_device_tables(self.handle, level, block_size, STREAM_ADD_INDEX if add_index else 0, C.byref(cfg), sp, sl, n, d_dst, dst_cap)
+            if r < 0:
+                _raise(r, self)
+            return int(r)
         flags = (STREAM_ADD_INDEX if add_index else 0) | (0 if search_match_len is None else STREAM_SEARCH_TABLES | (search_match_len & 15) << 8)
         r = _lib.lib().mlz_stream_encode_gather_device(self.handle, level, block_size, flags, sp, sl, n, d_dst, dst_cap)
         if r < 0:
@@ -232,6 +242,8 @@ class DeviceReader:
     def search(self, pattern, d_offsets, cap, ignore_crc=False, no_tables=False, stream=None):
         """mlz_dev_reader_search.  pattern: 1 .. 256 bytes; d_offsets: device address of room for `cap` uint64 (None with cap == 0), which
         receives the smallest min(total, cap) positions of the pattern in the decoded stream, ascending.
+        Uses the stream's block search tables of type 1, 2 or 3 (with a prefix table: the pattern's windows that follow a prefix byte; a
+        pattern without one is served by decoding every chunk, and the usable-table count is then 0).
         -> (total, (data chunks, chunks decoded or copied, chunks with a usable search table))."""
         if not self.handle:
             raise ValueError("DeviceReader is closed")
@@ -433,6 +445,25 @@ def decode_batch(blocks, ctx=None):
 
 
 STREAM_ADD_INDEX, STREAM_IGNORE_CRC, STREAM_SEARCH_TABLES, SEARCH_NO_TABLES = 1, 2, 4, 8
+
+
+def search_tables_config(match_len, prefix):
+    """An mlz_search_tables for a set of prefix byte values: 1 to 8 distinct values -> table type 2 (sorted), more -> type 3 (the mask; an
+    empty set too: the empty mask is valid and indexes nothing)."""
+    vals = sorted({int(v) for v in prefix})
+    if vals and (vals[0] < 0 or vals[-1] > 255):
+        raise ValueError("search_prefix: byte values")
+    cfg = _lib.SearchTables()
+    cfg.match_len = match_len & 255
+    if 1 <= len(vals) <= 8:
+        cfg.table_type, cfg.n_prefix = 2, len(vals)
+        for i, v in enumerate(vals):
+            cfg.prefix[i] = v
+    else:
+        cfg.table_type = 3
+        for v in vals:
+            cfg.prefix[v >> 3] |= 1 << (v & 7)
+    return cfg
 
 
 def stream_encode(src, level=LevelFastest, block_size=2 << 20, add_index=False, ctx=None):

@@ -5,11 +5,18 @@
 // a bitmap of 2^B bits per block, bit HashValue(window of M bytes, B, M) set for every position of the block — the last M - 1 positions take
 // their missing bytes from the next block, zeros beyond it; the stream's last block has no such positions —, dropped when more than 70 % of
 // its bits are set, else folded in halves while a quarter of the folded bits at the most are set and 32 bytes at the least remain.
+// Table types 2 and 3 (SPEC_SEARCH.md 3.3; search_index.go:85-137): only the positions q >= 1 of a block whose preceding byte block[q - 1]
+// is one of the configured prefix bytes; a block that is not the stream's last indexes position n too (the window that lies wholly in the
+// next block's first M bytes, behind a prefix byte that is the block's last one), the stream's last block the positions up to n - M; a fold
+// is accepted while a tenth of the folded bits at the most are set.
 //
 // stab_build_kernel: a workgroup keeps the bitmap (B <= 20: all of it, 128 KiB at the most; above: one slice of 2^20 bits, so 2, 4 or 8
 //   workgroups hash a block's windows and each keeps the bits of its slice) in LDS, where a set bit is one non-returning ds_or; a device-scope
 //   atomic per window would cost several times the whole encode (DESIGN.md section 0).  Few large blocks: several workgroups take parts of a
 //   block and merge into the zeroed table in HBM with non-returning dword atomicOr (words that are not zero only).
+//   stab_build_kernel<true> is the prefix form: a lane's 16 bytes start one byte in front of its 8 positions, the 256-bit set of prefix bytes
+//   lies in 32 bytes of LDS (a per-lane byte indexes it with one ds_read), and the hash and the ds_or run for positions behind a prefix byte only:
+//   a lane first gathers its 8 positions' verdicts into a bit mask and then loops over the set bits.
 // stab_reduce_kernel: a workgroup per block counts the bits, applies the rules above fold by fold (search_reduce_rule's conditions) and leaves
 //   the table compact at the front of its slot; 8 bytes per block (table bytes or 0, R) go to the host next to the sizes and CRCs.
 
@@ -24,6 +31,7 @@ struct StabArgs {
     uint32_t tail_n;         // how many of them exist (0: the range ends the stream)
     uint32_t bs, cnt, B, M, parts, slices;
     uint32_t* tabs;          // cnt tables of 2^B bits
+    uint32_t mask[8];        // the prefix form: byte v is a prefix byte when mask[v >> 5] >> (v & 31) & 1
 };
 
 // byte q of the range, continued by the next range's first bytes and zeros
@@ -33,6 +41,7 @@ __device__ __forceinline__ uint64_t stab_byte(const StabArgs& a, uint64_t q) {
     return over < a.tail_n ? (a.tail >> (8 * over)) & 0xff : 0;
 }
 
+template <bool kPrefix>
 __global__ __launch_bounds__(kStabThreads) void stab_build_kernel(const StabArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint32_t* bits = reinterpret_cast<uint32_t*>(smem);
@@ -40,17 +49,30 @@ __global__ __launch_bounds__(kStabThreads) void stab_build_kernel(const StabArgs
     const uint32_t part = blockIdx.x % a.parts, slice = (blockIdx.x / a.parts) % a.slices, b = blockIdx.x / (a.parts * a.slices);
     const uint32_t lbits = a.B < kStabSliceBits ? a.B : kStabSliceBits, words = 1u << (lbits - 5);
     for (uint32_t i = tid; i < words; i += kStabThreads) bits[i] = 0;
+    [[maybe_unused]] const uint32_t* pmask = bits + words;   // the prefix form: 32 bytes behind the bitmap
+    if constexpr (kPrefix) { if (tid < 8) bits[words + tid] = a.mask[tid]; }
     __syncthreads();
     const uint64_t b0 = uint64_t(b) * a.bs;
     const uint32_t blen = uint32_t(a.len - b0 < a.bs ? a.len - b0 : a.bs);
     const bool next = b + 1 < a.cnt || a.tail_n != 0;
-    // positions [0, npos): every one with a next block, else those whose window lies inside the block
-    const uint32_t npos = next ? blen : (blen >= a.M ? blen - a.M + 1 : 0);
+    // positions [0, npos): every one with a next block, else those whose window lies inside the block.  The prefix form: position 0 is
+    // never indexed (it belongs to the block before), position blen of a block with a next one is (its window lies in the next block)
+    const uint32_t npos = kPrefix ? (next ? blen + 1 : (blen >= a.M ? blen - a.M + 1 : 0)) : (next ? blen : (blen >= a.M ? blen - a.M + 1 : 0));
     const uint32_t per = ((npos + a.parts - 1) / a.parts + kStabPerThread - 1) & ~(kStabPerThread - 1);
     const uint32_t p0 = part * per, p1 = p0 + per < npos ? p0 + per : npos;
     const uint32_t M = a.M, B = a.B;
+    auto mark = [&](uint64_t v) {   // the window's bit, when it falls into this workgroup's slice
+        const uint32_t h = search_hash(v, B, M);
+        if ((h >> kStabSliceBits) == slice) {
+            const uint32_t x = h & ((1u << kStabSliceBits) - 1);
+            atomicOr(&bits[x >> 5], 1u << (x & 31));
+        }
+    };
     for (uint32_t i = p0 + tid * kStabPerThread; i < p1; i += kStabThreads * kStabPerThread) {
-        const uint64_t q = b0 + i;
+        // the prefix form reads from one byte in front of its first position (a part's first position looks at the part before it); the
+        // block's first lane has no such byte and shifts a zero in, for position 0, which is skipped
+        const uint32_t back = kPrefix && i ? 1 : 0;
+        const uint64_t q = b0 + i - back;
         uint64_t lo, hi;
         if (q + 16 <= a.len) {
             __builtin_memcpy(&lo, a.src + q, 8);
@@ -59,14 +81,28 @@ __global__ __launch_bounds__(kStabThreads) void stab_build_kernel(const StabArgs
             lo = hi = 0;
             for (uint32_t j = 0; j < 8; j++) { lo |= stab_byte(a, q + j) << (8 * j); hi |= stab_byte(a, q + 8 + j) << (8 * j); }
         }
+        if constexpr (kPrefix) {
+            if (!back) { hi = (hi << 8) | (lo >> 56); lo <<= 8; }
+            // bit j of todo: position i + j lies behind a prefix byte (byte j of lo).  Then one hash per set bit: a wave runs as many
+            // rounds as its busiest lane has such positions, not 8 (a branch around the hash would run it in nearly every round: some
+            // lane of the 64 almost always has a prefix byte at a given j)
+            uint32_t todo = 0;
 #pragma unroll
-        for (uint32_t j = 0; j < kStabPerThread; j++) {
-            if (i + j >= p1) break;
-            const uint64_t v = j ? (lo >> (8 * j)) | (hi << (64 - 8 * j)) : lo;
-            const uint32_t h = search_hash(v, B, M);
-            if ((h >> kStabSliceBits) == slice) {
-                const uint32_t x = h & ((1u << kStabSliceBits) - 1);
-                atomicOr(&bits[x >> 5], 1u << (x & 31));
+            for (uint32_t j = 0; j < kStabPerThread; j++) {
+                const uint32_t pb = uint32_t(lo >> (8 * j)) & 0xff;
+                todo |= ((pmask[pb >> 5] >> (pb & 31)) & 1) << j;
+            }
+            if (p1 - i < kStabPerThread) todo &= (1u << (p1 - i)) - 1;   // the part's last positions
+            if (i == 0) todo &= ~1u;                                      // position 0 belongs to the block before
+            for (; todo; todo &= todo - 1) {
+                const uint32_t sh = 8 * (uint32_t(__builtin_ctz(todo)) + 1);   // the window starts one byte behind its prefix byte
+                mark(sh < 64 ? (lo >> sh) | (hi << (64 - sh)) : hi);
+            }
+        } else {
+#pragma unroll
+            for (uint32_t j = 0; j < kStabPerThread; j++) {
+                if (i + j >= p1) break;
+                mark(j ? (lo >> (8 * j)) | (hi << (64 - 8 * j)) : lo);
             }
         }
     }
@@ -83,7 +119,7 @@ __global__ __launch_bounds__(kStabThreads) void stab_build_kernel(const StabArgs
 }
 
 // info[b] = (table bytes or 0, R); the table of 2^(B - R) bits is left at the front of its slot
-__global__ __launch_bounds__(kStabThreads) void stab_reduce_kernel(uint32_t* __restrict__ tabs, uint32_t B, uint2* __restrict__ info) {
+__global__ __launch_bounds__(kStabThreads) void stab_reduce_kernel(uint32_t* __restrict__ tabs, uint32_t B, uint32_t fold_limit /* per cent */, uint2* __restrict__ info) {
     __shared__ uint32_t wsum[kStabThreads / 64];
     const uint32_t tid = threadIdx.x, b = blockIdx.x;
     uint32_t* t = tabs + (size_t(b) << (B - 5));
@@ -110,7 +146,7 @@ __global__ __launch_bounds__(kStabThreads) void stab_reduce_kernel(uint32_t* __r
         uint32_t p = 0;
         for (uint32_t i = tid; i < half; i += kStabThreads) p += uint32_t(__popc(t[i] | t[half + i]));
         p = total(p);
-        if (!search_fold_accepted(p, uint64_t(half) * 32)) break;
+        if (!search_fold_accepted(p, uint64_t(half) * 32, fold_limit)) break;
         for (uint32_t i = tid; i < half; i += kStabThreads) t[i] |= t[half + i];
         __syncthreads();
         words = half; R++;
@@ -123,16 +159,17 @@ __global__ __launch_bounds__(kStabThreads) void stab_reduce_kernel(uint32_t* __r
 namespace {
 
 // The tables of the cnt blocks of a range (len bytes at d_src), built and reduced on sm: c->d_stab then holds cnt slots of 2^(B - 3) bytes, each
-// with its block's table at the front, and behind them (at *info_off) cnt records (table bytes or 0, R).  tail: the tail_n <= 7 bytes that
-// follow the range in the stream (the next range's first ones).  Caller holds c->mu.
-int search_tables_build(mlz_ctx* c, hipStream_t sm, const uint8_t* d_src, size_t len, uint32_t bs, size_t cnt, uint32_t M, uint32_t B, uint64_t tail, uint32_t tail_n,
-                        size_t* info_off) {
+// with its block's table at the front, and behind them (at *info_off) cnt records (table bytes or 0, R).  tail: the tail_n <= 8 bytes that
+// follow the range in the stream (the next range's first ones).  T, field: the table type and its prefix field.  Caller holds c->mu.
+int search_tables_build(mlz_ctx* c, hipStream_t sm, const uint8_t* d_src, size_t len, uint32_t bs, size_t cnt, uint32_t T, const uint8_t* field, uint32_t M, uint32_t B,
+                        uint64_t tail, uint32_t tail_n, size_t* info_off) {
     const size_t slot = size_t(1) << (B - 3);
     *info_off = cnt * slot;
     HIPCHK(c, c->d_stab.ensure(cnt * slot + cnt * sizeof(uint2) + 64));
     const uint32_t lbits = std::min(B, mlz::kStabSliceBits), lds = 1u << (lbits - 3);
     if (!c->stab_attr) {
-        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(mlz::stab_build_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 1u << (mlz::kStabSliceBits - 3)));
+        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(mlz::stab_build_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 1u << (mlz::kStabSliceBits - 3)));
+        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(mlz::stab_build_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (1u << (mlz::kStabSliceBits - 3)) + 32));
         c->stab_attr = true;
     }
     mlz::StabArgs a{};
@@ -143,8 +180,13 @@ int search_tables_build(mlz_ctx* c, hipStream_t sm, const uint8_t* d_src, size_t
     a.parts = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(want, bs >> 16)));
     a.tabs = c->d_stab.as<uint32_t>();
     if (a.parts > 1) HIPCHK(c, hipMemsetAsync(a.tabs, 0, cnt * slot, sm));
-    hipLaunchKernelGGL(mlz::stab_build_kernel, dim3(uint32_t(cnt * a.slices * a.parts)), dim3(mlz::kStabThreads), lds, sm, a);
-    hipLaunchKernelGGL(mlz::stab_reduce_kernel, dim3(uint32_t(cnt)), dim3(mlz::kStabThreads), 0, sm, a.tabs, B, reinterpret_cast<uint2*>(c->d_stab.as<uint8_t>() + *info_off));
+    if (T == 1) hipLaunchKernelGGL(mlz::stab_build_kernel<false>, dim3(uint32_t(cnt * a.slices * a.parts)), dim3(mlz::kStabThreads), lds, sm, a);
+    else {
+        mlz::search_prefix_mask(T, field, a.mask);
+        hipLaunchKernelGGL(mlz::stab_build_kernel<true>, dim3(uint32_t(cnt * a.slices * a.parts)), dim3(mlz::kStabThreads), lds + 32, sm, a);
+    }
+    hipLaunchKernelGGL(mlz::stab_reduce_kernel, dim3(uint32_t(cnt)), dim3(mlz::kStabThreads), 0, sm, a.tabs, B, mlz::search_fold_limit(T),
+                       reinterpret_cast<uint2*>(c->d_stab.as<uint8_t>() + *info_off));
     return 0;
 }
 

@@ -130,10 +130,10 @@ int ensure_stream_objects(mlz_ctx* c, size_t n_events, size_t pinned_bytes) {
     return 0;
 }
 
-size_t stream_bound(uint64_t n, uint32_t bs, bool add_index, bool search_tables = false) {
+size_t stream_bound(uint64_t n, uint32_t bs, bool add_index, uint32_t table_type = 0 /* 0: no search tables */) {
     const uint64_t nblk = (n + bs - 1) / bs;
-    // search tables: the info chunk and, per block, a table chunk with the unreduced table
-    const uint64_t tables = search_tables ? 7 + nblk * mlz::search_chunk_bound(mlz::search_table_bits(bs)) : 0;
+    // search tables: the info chunk and, per block, a table chunk with the unreduced table; both carry the type's prefix field
+    const uint64_t tables = table_type ? 7 + mlz::search_field_len(table_type) + nblk * mlz::search_chunk_bound(mlz::search_table_bits(bs), table_type) : 0;
     return size_t(10 + nblk * (8 + 5) + n + 4 + 10 + (add_index ? SeekIndex::bound(size_t(nblk)) : 0) + tables);
 }
 
@@ -142,6 +142,32 @@ int stream_search_match_len(uint32_t flags) {
     if (!(flags & MLZ_STREAM_SEARCH_TABLES)) return 0;
     const uint32_t m = (flags >> 8) & 15;
     return m == 0 ? int(mlz::kSearchDefaultMatchLen) : m <= 8 ? int(m) : -1;
+}
+
+// The Writer's search tables: T = 0 without them, else the table type, the match length and the prefix field as the chunks carry it
+struct StreamTables {
+    uint32_t T = 0, M = 0;
+    uint8_t field[mlz::kSearchMaxField] = {};
+    uint32_t flen() const { return mlz::search_field_len(T); }
+    uint32_t overlap() const { return T == 1 ? M - 1 : M; }   // bytes of the next block that a block's windows reach
+};
+// flags and an mlz_search_tables (may be NULL) -> the configuration; false: -MLZ_ERR_ARG
+bool stream_tables_config(uint32_t flags, const mlz_search_tables* cfg, StreamTables* st) {
+    *st = StreamTables{};
+    if (!cfg) {
+        const int m = stream_search_match_len(flags);
+        if (m < 0) return false;
+        if (m) { st->T = 1; st->M = uint32_t(m); }
+        return true;
+    }
+    if ((flags & (MLZ_STREAM_SEARCH_TABLES | MLZ_STREAM_SEARCH_MATCH_LEN(15))) || cfg->table_type < 1 || cfg->table_type > 3 || cfg->match_len > 8 || cfg->reserved) return false;
+    st->T = cfg->table_type;
+    st->M = cfg->match_len ? cfg->match_len : mlz::kSearchDefaultMatchLen;
+    if (st->T == 2) {
+        if (cfg->n_prefix < 1 || cfg->n_prefix > 8) return false;
+        for (uint32_t i = 0; i < 8; i++) st->field[i] = cfg->prefix[i < cfg->n_prefix ? i : cfg->n_prefix - 1u];
+    } else if (st->T == 3) std::memcpy(st->field, cfg->prefix, 32);
+    return true;
 }
 
 // Chunk bodies of a group into a page-locked destination: one workgroup per 64 KiB piece copies from the encode output in HBM to
@@ -369,14 +395,15 @@ int64_t stream_encode_over(mlz_ctx* const* workers, size_t k, int level, uint32_
 
 // ---- the device-resident Writer over several devices: sources in each device's HBM, the framed stream gathered GPU to GPU ----
 // Chunk bodies and 8-byte chunk headers into a run of chunks: desc.pad selects the source (0 = the encoder's output, 1 = the raw block, for
-// stored chunks; stream_place3_kernel: 2 = the block's search table); a header is eight literal bytes at a destination offset (a table chunk's: twelve).
+// stored chunks; stream_place3_kernel: 2 = the block's search table); a header is eight literal bytes at a destination offset (a table chunk's: twelve
+// and its prefix field, 20 or 44 with table type 2 or 3).
 struct HdrDesc { uint64_t dst_off; uint8_t b[8]; };
 __global__ __launch_bounds__(256) void stream_place2_kernel(const uint8_t* __restrict__ d_enc, const uint8_t* __restrict__ d_raw, uint8_t* __restrict__ run,
                                                             const PlaceDesc* __restrict__ descs) {
     const PlaceDesc d = descs[blockIdx.x];
     mlz::wg_copy(run + d.dst_off, (d.pad ? d_raw : d_enc) + d.src_off, d.len, threadIdx.x, 256);
 }
-struct TabHdrDesc { uint64_t dst_off; uint8_t b[12]; uint32_t pad; };
+struct TabHdrDesc { uint64_t dst_off; uint8_t b[12 + mlz::kSearchMaxField]; uint32_t n; };
 __global__ __launch_bounds__(256) void stream_place3_kernel(const uint8_t* __restrict__ d_enc, const uint8_t* __restrict__ d_raw, const uint8_t* __restrict__ d_tab,
                                                             uint8_t* __restrict__ run, const PlaceDesc* __restrict__ descs) {
     const PlaceDesc d = descs[blockIdx.x];
@@ -385,9 +412,8 @@ __global__ __launch_bounds__(256) void stream_place3_kernel(const uint8_t* __res
 __global__ __launch_bounds__(64) void stream_tabhdr_kernel(uint8_t* __restrict__ run, const TabHdrDesc* __restrict__ hd, uint32_t n) {
     const uint32_t i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
-    const TabHdrDesc h = hd[i];
-#pragma unroll
-    for (int k = 0; k < 12; k++) run[h.dst_off + k] = h.b[k];
+    const TabHdrDesc& h = hd[i];
+    for (uint32_t k = 0; k < h.n; k++) run[h.dst_off + k] = h.b[k];
 }
 __global__ __launch_bounds__(64) void stream_hdr_kernel(uint8_t* __restrict__ run, const HdrDesc* __restrict__ hd, uint32_t n) {
     const uint32_t i = blockIdx.x * 64 + threadIdx.x;
@@ -401,11 +427,12 @@ __global__ __launch_bounds__(64) void stream_hdr_kernel(uint8_t* __restrict__ ru
 // block) to the host, the run of chunks framed on the device, then moved to its place in d_dst on device dst_dev (the same device: framed in
 // place; another one: hipMemcpyPeerAsync, which rides xGMI between the GPUs of a node).  Payload never visits the host.
 int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d_src, size_t len, size_t b0, uint8_t* d_dst, int dst_dev, bool have_header,
-                            StreamEncShared* sh, size_t j, uint32_t* framed, uint32_t search_m = 0 /* > 0: search tables of this match length */, uint64_t tail = 0,
-                            uint32_t tail_n = 0 /* the bytes that follow the range in the stream, 7 at the most */) {
+                            StreamEncShared* sh, size_t j, uint32_t* framed, const StreamTables& stb = StreamTables{} /* T > 0: search tables */, uint64_t tail = 0,
+                            uint32_t tail_n = 0 /* the bytes that follow the range in the stream, 8 at the most */) {
     HIPCHK(c, hipSetDevice(c->device));
     const size_t cnt = (len + bs - 1) / bs;
     if (cnt == 0) { sh->publish(j, 0); return 0; }
+    const uint32_t search_m = stb.T ? stb.M : 0, flen = stb.flen(), thdr = 12 + flen;   // thdr: a table chunk's bytes in front of its table
     const uint32_t search_b = mlz::search_table_bits(bs);
     const size_t tab_slot = size_t(1) << (search_b - 3);
     const size_t ostride = (size_t(bs) + 16 + 63) & ~size_t(63);
@@ -435,7 +462,7 @@ int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d
     if (r) return r;
     size_t tabinfo_off = 0;
     if (search_m) {
-        r = search_tables_build(c, sm, d_src, len, bs, cnt, search_m, search_b, tail, tail_n, &tabinfo_off);
+        r = search_tables_build(c, sm, d_src, len, bs, cnt, stb.T, stb.field, search_m, search_b, tail, tail_n, &tabinfo_off);
         if (r) return r;
         HIPCHK(c, hipMemcpyAsync(h_tabinfo, c->d_stab.as<uint8_t>() + tabinfo_off, sizeof(uint2) * cnt, hipMemcpyDeviceToHost, sm));
     }
@@ -470,18 +497,20 @@ int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d
         const bool stored = elen == int64_t(bl) + 2;
         const size_t body = stored ? bl : size_t(elen) - 1, chunk_len = 4 + body;
         framed[b0 + i] = 0;
-        if (search_m && h_tabinfo[i].x) {   // 45 len24 | 01 M B | R | crc32le | table
-            const uint32_t tb = h_tabinfo[i].x, tlen = 8 + tb;
+        if (search_m && h_tabinfo[i].x) {   // 45 len24 | T M B | prefix field | R | crc32le | table
+            const uint32_t tb = h_tabinfo[i].x, tlen = thdr - 4 + tb;
             TabHdrDesc& th = h_tabhdr[tab_at];
-            th.dst_off = run; th.pad = 0;
+            th.dst_off = run; th.n = thdr;
             th.b[0] = mlz::kChunkSearchTable; th.b[1] = uint8_t(tlen); th.b[2] = uint8_t(tlen >> 8); th.b[3] = uint8_t(tlen >> 16);
-            th.b[4] = 1; th.b[5] = uint8_t(search_m); th.b[6] = uint8_t(search_b); th.b[7] = uint8_t(h_tabinfo[i].y);
-            std::memcpy(th.b + 8, &h_tabcrc[tab_at], 4);
+            th.b[4] = uint8_t(stb.T); th.b[5] = uint8_t(search_m); th.b[6] = uint8_t(search_b);
+            std::memcpy(th.b + 7, stb.field, flen);
+            th.b[7 + flen] = uint8_t(h_tabinfo[i].y);
+            std::memcpy(th.b + 8 + flen, &h_tabcrc[tab_at], 4);
             for (size_t q = 0; q < tb; q += kPlacePiece)
-                h_place[n_place++] = PlaceDesc{i * tab_slot + q, run + 12 + q, uint32_t(std::min<size_t>(kPlacePiece, tb - q)), 2u};
+                h_place[n_place++] = PlaceDesc{i * tab_slot + q, run + thdr + q, uint32_t(std::min<size_t>(kPlacePiece, tb - q)), 2u};
             tab_at++;
-            framed[b0 + i] = 12 + tb;
-            run += 12 + tb;
+            framed[b0 + i] = thdr + tb;
+            run += thdr + tb;
         }
         HdrDesc& h = h_hdr[i];
         h.dst_off = run;
@@ -497,7 +526,7 @@ int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d
     sh->publish(j, int64_t(run));
     const int64_t before = sh->base_of(j);
     if (before < 0) return -MLZ_ERR_HIP;
-    const size_t base = (have_header ? (search_m ? 17 : 10) : 0) + size_t(before);
+    const size_t base = (have_header ? (search_m ? 17 + flen : 10) : 0) + size_t(before);
     // frame the run: in place when d_dst is on this device, else in a local buffer that then travels
     const bool local = c->device == dst_dev;
     uint8_t* d_run = d_dst + base;
@@ -781,8 +810,14 @@ extern "C" {
 
 int64_t mlz_stream_bound(uint64_t n, uint32_t block_size, uint32_t flags) {
     if (block_size < kMinStreamBlock || block_size > kMaxBlockSize) return -MLZ_ERR_ARG;
-    if (stream_search_match_len(flags) < 0) return -MLZ_ERR_ARG;
-    return int64_t(stream_bound(n, block_size, (flags & MLZ_STREAM_ADD_INDEX) != 0, (flags & MLZ_STREAM_SEARCH_TABLES) != 0));
+    return mlz_stream_bound_tables(n, block_size, flags, nullptr);
+}
+
+int64_t mlz_stream_bound_tables(uint64_t n, uint32_t block_size, uint32_t flags, const mlz_search_tables* cfg) {
+    if (block_size < kMinStreamBlock || block_size > kMaxBlockSize) return -MLZ_ERR_ARG;
+    StreamTables stb;
+    if (!stream_tables_config(flags, cfg, &stb)) return -MLZ_ERR_ARG;
+    return int64_t(stream_bound(n, block_size, (flags & MLZ_STREAM_ADD_INDEX) != 0, stb.T));
 }
 
 int64_t mlz_stream_encode(mlz_ctx* c, int level, uint32_t block_size, uint32_t flags, const uint8_t* src, size_t n, uint8_t* dst, size_t dst_cap) {
@@ -796,12 +831,17 @@ int64_t mlz_stream_encode(mlz_ctx* c, int level, uint32_t block_size, uint32_t f
 
 int64_t mlz_stream_encode_gather_device(mlz_ctx* c, int level, uint32_t block_size, uint32_t flags, const uint8_t* const* d_src, const size_t* src_len,
                                         int n_ranges, uint8_t* d_dst, size_t dst_cap) {
+    return mlz_stream_encode_gather_device_tables(c, level, block_size, flags, nullptr, d_src, src_len, n_ranges, d_dst, dst_cap);
+}
+
+int64_t mlz_stream_encode_gather_device_tables(mlz_ctx* c, int level, uint32_t block_size, uint32_t flags, const mlz_search_tables* cfg, const uint8_t* const* d_src,
+                                               const size_t* src_len, int n_ranges, uint8_t* d_dst, size_t dst_cap) {
     if (!c || !d_src || !src_len || n_ranges <= 0 || !d_dst) return -MLZ_ERR_ARG;
     if (block_size < kMinStreamBlock || block_size > kMaxBlockSize) return -MLZ_ERR_ARG;
     if (!valid_level(level)) return -MLZ_ERR_INVALID_LEVEL;
     const bool add_index = (flags & MLZ_STREAM_ADD_INDEX) != 0;
-    const int search_m = stream_search_match_len(flags);
-    if (search_m < 0) return -MLZ_ERR_ARG;
+    StreamTables stb;
+    if (!stream_tables_config(flags, cfg, &stb)) return -MLZ_ERR_ARG;
     Workers w(c);
     const size_t k = size_t(n_ranges);
     // every range on the device that holds it; all but the last are whole blocks (a short block ends a stream)
@@ -827,16 +867,16 @@ int64_t mlz_stream_encode_gather_device(mlz_ctx* c, int level, uint32_t block_si
     hipPointerAttribute_t dat;
     if (hipPointerGetAttributes(&dat, d_dst) != hipSuccess || dat.type != hipMemoryTypeDevice) { (void)hipGetLastError(); return -MLZ_ERR_ARG; }
     const int dst_dev = dat.device;
-    if (dst_cap < stream_bound(n, block_size, add_index, search_m > 0)) return -MLZ_ERR_DST_TOO_SMALL;
-    // search tables: a range's last block indexes windows that run into the next non-empty range, whose first bytes (7 at the most) the host hands over
+    if (dst_cap < stream_bound(n, block_size, add_index, stb.T)) return -MLZ_ERR_DST_TOO_SMALL;
+    // search tables: a range's last block indexes windows that run into the next non-empty range, whose first bytes (M - 1, with a prefix table M: 8 at the most) the host hands over
     std::vector<uint64_t> next_bytes(k, 0);
     std::vector<uint32_t> next_n(k, 0);
-    if (search_m > 1)
+    if (stb.T && stb.overlap())
         for (size_t j = 0; j + 1 < k; j++) {
             size_t q = j + 1;
             while (q < k && !src_len[q]) q++;
             if (q == k || !src_len[j]) continue;
-            next_n[j] = uint32_t(std::min<size_t>(7, src_len[q]));
+            next_n[j] = uint32_t(std::min<size_t>(stb.T == 1 ? 7 : 8, src_len[q]));
             if (hipSetDevice(own[q]->device) != hipSuccess || hipMemcpy(&next_bytes[j], d_src[q], next_n[j], hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
         }
     const size_t nblk = first[k];
@@ -858,7 +898,7 @@ int64_t mlz_stream_encode_gather_device(mlz_ctx* c, int level, uint32_t block_si
         mlz_ctx* kc = ctxs[q];
         std::lock_guard<std::mutex> lk(kc->mu);
         for (size_t j : by_ctx[q]) {
-            rcs[j] = stream_gather_range(kc, level, block_size, d_src[j], src_len[j], first[j], d_dst, dst_dev, n > 0, &sh, j, framed.data(), uint32_t(search_m), next_bytes[j], next_n[j]);
+            rcs[j] = stream_gather_range(kc, level, block_size, d_src[j], src_len[j], first[j], d_dst, dst_dev, n > 0, &sh, j, framed.data(), stb, next_bytes[j], next_n[j]);
             if (rcs[j]) { sh.fail(); (void)hipStreamSynchronize(kc->stream); }
         }
     };
@@ -877,15 +917,16 @@ int64_t mlz_stream_encode_gather_device(mlz_ctx* c, int level, uint32_t block_si
     SeekIndex index;
     index.reset(block_size);
     size_t o = 0;
-    uint8_t head[17];
+    uint8_t head[17 + mlz::kSearchMaxField];
     if (n > 0) {
         std::memcpy(head, kMagicChunk, 9);
         head[9] = uint8_t((32 - __builtin_clz(block_size - 1)) - 10);
         o = 10;
-        if (search_m) {   // the info chunk: 44 03 00 00 | 01 M B
-            const uint8_t info[7] = {mlz::kChunkSearchInfo, 3, 0, 0, 1, uint8_t(search_m), uint8_t(mlz::search_table_bits(block_size))};
+        if (stb.T) {   // the info chunk: 44 len24 | T M B | prefix field
+            const uint8_t info[7] = {mlz::kChunkSearchInfo, uint8_t(3 + stb.flen()), 0, 0, uint8_t(stb.T), uint8_t(stb.M), uint8_t(mlz::search_table_bits(block_size))};
             std::memcpy(head + 10, info, 7);
-            o = 17;
+            std::memcpy(head + 17, stb.field, stb.flen());
+            o = 17 + stb.flen();
         }
         HIPCHK(c0, hipMemcpy(d_dst, head, o, hipMemcpyHostToDevice));
         index.add(0, 0);

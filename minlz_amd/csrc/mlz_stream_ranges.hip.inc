@@ -63,11 +63,12 @@ struct mlz_dev_reader {
     int64_t size = 0;
     std::vector<StreamChunk> chunks;          // the data chunks: body offset and length, decoded length, CRC, type, output offset
     std::vector<mlz::RdevChunk> dchunks;      // the planners' and the plan kernels' view of them
-    // mlz_dev_reader_search: (M, B) of the stream's info chunk and every data chunk's search table, found by the first search of the handle
+    // mlz_dev_reader_search: (T, M, B, prefix field) of the stream's info chunk and every data chunk's search table, found by the first search of the handle
     // ([0]: table CRCs checked, [1]: under MLZ_STREAM_IGNORE_CRC)
     struct SearchTables {
         bool ready = false, info = false;
-        uint32_t M = 0, B = 0;
+        uint32_t M = 0, B = 0, T = 0;
+        uint8_t field[mlz::kSearchMaxField] = {};
         size_t usable = 0;
         void* d_tabs = nullptr;               // mlz::SearchTab per data chunk, device memory the handle owns
         std::vector<mlz::SearchTab> tabs;

@@ -1,7 +1,8 @@
 // mlz_stream_search.h — what the block search tables' writer, the device-resident pattern search (mlz_stream_search.hip.inc) and their host
 // check (tools/stream_search_check.cpp) share: the table hash (SPEC_SEARCH.md 3.1), the size and the bytes of a table chunk (2.0, 2.1, 3.2),
 // the probe of one table and the rule that turns the probes of all chunks into the set of chunks to decode (Appendix B.4.1).
-// Plain C++: compiles for the host alone and for gfx950.  Table type 1 (no prefix), uncompressed table chunks (0x45) only.
+// Plain C++: compiles for the host alone and for gfx950.  Table types 1 (no prefix), 2 (1 to 8 prefix byte values) and 3 (a 256-bit mask of
+// prefix byte values; SPEC_SEARCH.md 3.3), uncompressed table chunks (0x45) only.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -46,23 +47,56 @@ MLZ_SEARCH_HD uint32_t search_table_bits(uint32_t block_size) {
     return b < 8 ? 8 : b > 23 ? 23 : b;
 }
 
-// Bytes a table chunk takes at the most: 4 (chunk header) + 8 (type, M, B, R, CRC) + the unreduced table.
-MLZ_SEARCH_HD uint64_t search_chunk_bound(uint32_t B) { return 12 + (uint64_t(1) << (B - 3)); }
+// The prefix field that follows `T M B` in the info chunk and in every table chunk: none for type 1, the 8 values of type 2 (unused places
+// repeat the last value), the 32 bytes of type 3's mask (value v is a prefix byte when field[v >> 3] >> (v & 7) & 1).
+constexpr uint32_t kSearchMaxField = 32;
+MLZ_SEARCH_HD uint32_t search_field_len(uint32_t T) { return T == 2 ? 8 : T == 3 ? 32 : 0; }
+// mask[v >> 5] >> (v & 31) & 1: v is a prefix byte of (T, field).  Type 1 has no prefix bytes.
+MLZ_SEARCH_HD void search_prefix_mask(uint32_t T, const uint8_t* field, uint32_t mask[8]) {
+    for (uint32_t i = 0; i < 8; i++) mask[i] = 0;
+    if (T == 2) for (uint32_t i = 0; i < 8; i++) mask[field[i] >> 5] |= 1u << (field[i] & 31);
+    if (T == 3) for (uint32_t i = 0; i < 32; i++) mask[i >> 2] |= uint32_t(field[i]) << (8 * (i & 3));
+}
+MLZ_SEARCH_HD bool search_is_prefix(const uint32_t mask[8], uint8_t v) { return (mask[v >> 5] >> (v & 31)) & 1; }
 
-// The payload of a 0x45 chunk (`clen` bytes at p, all readable): the reductions R of a type 1 table of (M, B) whose length fits, else -1.
-// The table's bytes are p[8 .. clen), its CRC the little-endian word at p + 4.
-MLZ_SEARCH_HD int search_table_reductions(const uint8_t* p, uint32_t clen, uint32_t M, uint32_t B) {
-    if (clen < 8 + 32 || p[0] != 1 || p[1] != M || p[2] != B) return -1;
-    const uint32_t R = p[3];
+// Bytes a table chunk takes at the most: 4 (chunk header) + 8 (type, M, B, R, CRC) + the prefix field + the unreduced table.
+MLZ_SEARCH_HD uint64_t search_chunk_bound(uint32_t B, uint32_t T = 1) { return 12 + search_field_len(T) + (uint64_t(1) << (B - 3)); }
+
+// The payload of a 0x45 chunk (`clen` bytes at p, all readable): the reductions R of a table of the stream's (T, M, B, field) whose length
+// fits, else -1.  With f = search_field_len(T): the CRC is the little-endian word at p + 4 + f, the table's bytes are p[8 + f .. clen).
+MLZ_SEARCH_HD int search_table_reductions(const uint8_t* p, uint32_t clen, uint32_t M, uint32_t B, uint32_t T = 1, const uint8_t* field = nullptr) {
+    const uint32_t f = search_field_len(T);
+    if (clen < 8 + f + 32 || p[0] != T || p[1] != M || p[2] != B) return -1;
+    for (uint32_t i = 0; i < f; i++) if (p[3 + i] != field[i]) return -1;
+    const uint32_t R = p[3 + f];
     if (R > B - 8) return -1;
-    return clen - 8 == (1u << (B - R - 3)) ? int(R) : -1;
+    return clen - 8 - f == (1u << (B - R - 3)) ? int(R) : -1;
 }
 
-// The payload of a 0x44 chunk: (M, B) of a type 1 stream, else false.
-MLZ_SEARCH_HD bool search_info(const uint8_t* p, uint32_t clen, uint32_t* M, uint32_t* B) {
-    if (clen < 3 || p[0] != 1 || p[1] < 1 || p[1] > 8 || p[2] < 8 || p[2] > 23) return false;
-    *M = p[1]; *B = p[2];
+// The payload of a 0x44 chunk: (T, M, B) and the prefix field (kSearchMaxField bytes of room, zeros behind the field) of a stream of type
+// 1, 2 or 3, else false (type 4 and a payload shorter than the field included).
+MLZ_SEARCH_HD bool search_info(const uint8_t* p, uint32_t clen, uint32_t* T, uint32_t* M, uint32_t* B, uint8_t* field) {
+    if (clen < 3 || p[0] < 1 || p[0] > 3 || p[1] < 1 || p[1] > 8 || p[2] < 8 || p[2] > 23) return false;
+    const uint32_t f = search_field_len(p[0]);
+    if (clen < 3 + f) return false;
+    *T = p[0]; *M = p[1]; *B = p[2];
+    for (uint32_t i = 0; i < kSearchMaxField; i++) field[i] = i < f ? p[3 + i] : 0;
     return true;
+}
+
+// The pattern's windows that the tables can answer for (w[i] = where window i starts in the pattern, ascending; room for L values) and
+// t_min.  Type 1: every window 0 .. L - M, t_min = 1.  Types 2 and 3: the windows 1 <= i <= L - M behind a prefix byte P[i - 1]; t_min = 1
+// when P[0] is a prefix byte, else 0.  Returns their number; 0 = the tables cannot serve this pattern.
+MLZ_SEARCH_HD uint32_t search_windows(const uint8_t* pat, uint32_t L, uint32_t T, uint32_t M, const uint8_t* field, uint32_t* w, uint32_t* t_min) {
+    *t_min = 1;
+    if (L < M) return 0;
+    uint32_t nw = 0;
+    if (T == 1) { for (uint32_t i = 0; i + M <= L; i++) w[nw++] = i; return nw; }
+    uint32_t mask[8];
+    search_prefix_mask(T, field, mask);
+    *t_min = search_is_prefix(mask, pat[0]) ? 1 : 0;
+    for (uint32_t i = 1; i + M <= L; i++) if (search_is_prefix(mask, pat[i - 1])) w[nw++] = i;
+    return nw;
 }
 
 // One table against the pattern's windows (h[i] = the hash of window i at B bits; bits = B - R of this table): a = the leading windows
@@ -77,26 +111,28 @@ MLZ_SEARCH_HD void search_probe(const uint8_t* table, uint32_t bits, const uint3
     *a = lead; *s = trail;
 }
 
-// Chunk k may hold the start of an occurrence: all windows in its own table, or a split of them between its table (the first j, 1 <= j < nw,
+// Chunk k may hold the start of an occurrence: all windows in its own table, or a split of them between its table (the first j, t_min <= j < nw,
 // tail windows included) and the next chunk's (the last nw - j).  s_next = nw when the next chunk has no usable table or decodes to fewer
-// bytes than the pattern has.
-MLZ_SEARCH_HD bool search_candidate(uint32_t a_k, uint32_t s_next, uint32_t nw, bool last) {
+// bytes than the pattern has.  t_min: the fewest windows an occurrence that starts in chunk k leaves in k's table — 1 for type 1 (window 0
+// starts with the occurrence) and for a prefix table whose pattern starts with a prefix byte, else 0 (a window is indexed in the block that
+// holds the byte in front of it, so a short head of the occurrence may leave none).
+MLZ_SEARCH_HD bool search_candidate(uint32_t a_k, uint32_t s_next, uint32_t nw, bool last, uint32_t t_min = 1) {
     if (a_k == nw) return true;
     if (last) return false;
-    const uint32_t lo = nw - s_next > 1 ? nw - s_next : 1, hi = a_k < nw - 1 ? a_k : nw - 1;
-    return lo <= hi;
+    const uint32_t lo = nw - s_next > t_min ? nw - s_next : t_min;
+    return lo <= a_k;   // (a_k < nw here)
 }
 
 // The decoded set: every candidate plus the chunks behind it that hold any of the L - 1 bytes after its end.  a[k], s[k]: the probe of
 // chunk k (nw, nw without a usable table); n[k] > 0: its decoded bytes.  take[k] = 1 for the chunks to decode.  Returns their number.
 template <class A, class S, class N>
-size_t search_decoded_set(size_t nck, A a_of, S s_of, N n_of, uint32_t nw, uint32_t L, uint8_t* take) {
+size_t search_decoded_set(size_t nck, A a_of, S s_of, N n_of, uint32_t nw, uint32_t L, uint8_t* take, uint32_t t_min = 1) {
     for (size_t k = 0; k < nck; k++) take[k] = 0;
     for (size_t k = 0; k < nck; k++) {
         if (!n_of(k)) continue;   // (a chunk of no bytes holds nothing)
         const bool last = k + 1 == nck;
         const uint32_t s_next = last ? 0 : (n_of(k + 1) < L ? nw : s_of(k + 1));
-        if (!search_candidate(a_of(k), s_next, nw, last)) continue;
+        if (!search_candidate(a_of(k), s_next, nw, last, t_min)) continue;
         take[k] = 1;
         uint64_t need = L - 1;
         for (size_t j = k + 1; j < nck && need; j++) {
@@ -159,12 +195,13 @@ void search_layout(size_t n_jobs, const std::vector<size_t>& gend, Off out_off_o
 
 // ---- the writer's side: the reductions of one table (3.2, the reference's population rules) ----
 // A block whose unfolded table has more than 70 % of its 2^B bits set gets no table; a fold to half_bits bits is accepted while a quarter of
-// them at the most are set.  (stab_reduce_kernel applies the two fold by fold; search_reduce_rule is the whole rule over given counts.)
+// them at the most are set (a tenth with a prefix table).  (stab_reduce_kernel applies the two fold by fold; search_reduce_rule is the whole rule over given counts.)
 MLZ_SEARCH_HD bool search_table_dropped(uint32_t pop, uint32_t B) { return uint64_t(pop) * 100 / (uint64_t(1) << B) > 70; }
-MLZ_SEARCH_HD bool search_fold_accepted(uint32_t pop_folded, uint64_t half_bits) { return uint64_t(pop_folded) * 100 <= half_bits * 25; }
+MLZ_SEARCH_HD uint32_t search_fold_limit(uint32_t T) { return T == 1 ? 25 : 10; }
+MLZ_SEARCH_HD bool search_fold_accepted(uint32_t pop_folded, uint64_t half_bits, uint32_t limit = 25) { return uint64_t(pop_folded) * 100 <= half_bits * limit; }
 // pop[r] = the set bits of the table folded r times (r = 0: as built), for r = 0 .. B - 8.  Returns the bytes of the table to store and *R,
 // or 0 when the block gets no table (more than 70 % of the unfolded bits are set).
-MLZ_SEARCH_HD uint32_t search_reduce_rule(const uint32_t* pop, uint32_t B, uint32_t* R) {
+MLZ_SEARCH_HD uint32_t search_reduce_rule(const uint32_t* pop, uint32_t B, uint32_t* R, uint32_t limit = 25) {
     const uint64_t total = uint64_t(1) << B;
     *R = 0;
     if (search_table_dropped(pop[0], B)) return 0;
@@ -172,7 +209,7 @@ MLZ_SEARCH_HD uint32_t search_reduce_rule(const uint32_t* pop, uint32_t B, uint3
     uint64_t bytes = total >> 3;
     while (bytes >= 64) {
         const uint64_t half_bits = (bytes >> 1) << 3;
-        if (!search_fold_accepted(pop[r + 1], half_bits)) break;
+        if (!search_fold_accepted(pop[r + 1], half_bits, limit)) break;
         bytes >>= 1; r++;
     }
     *R = r;

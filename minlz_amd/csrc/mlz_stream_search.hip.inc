@@ -1,8 +1,9 @@
 // mlz_stream_search.hip.inc — mlz_dev_reader_search: where a byte string occurs in a .mz stream that lies in HBM (included at the end of
 // mlz_hip.hip, behind the device-resident ReadSeeker whose handle, chunk-list decode and scratch it uses).
 //
-// The stream's block search tables (SPEC_SEARCH.md: an info chunk 0x44 behind the identifier, a bit table 0x45 in front of a block) say
-// which blocks can hold the pattern's windows of M bytes.  Per handle, once: search_info_kernel reads the info chunk, search_locate_kernel
+// The stream's block search tables (SPEC_SEARCH.md: an info chunk 0x44 behind the identifier, a bit table 0x45 in front of a block; table
+// types 1, 2 and 3) say which blocks can hold the pattern's windows of M bytes — with a prefix table (types 2 and 3) the windows behind one
+// of the stream's prefix bytes, which are the only ones its blocks index.  Per handle, once: search_info_kernel reads the info chunk, search_locate_kernel
 // (one lane per data chunk) hops over the chunk headers between the previous data chunk's end and its own start to the first table chunk
 // that fits, and the existing CRC pass checks the tables.  Per call: search_probe_kernel looks the pattern's windows up in every table
 // (8 bytes per chunk come back), the rule of mlz_stream_search.h turns that into the set of chunks to decode, stream_run_chunk_jobs decodes
@@ -12,7 +13,7 @@
 
 namespace mlz {
 
-struct SearchInfo { uint32_t M, B, ok, pad; };
+struct SearchInfo { uint32_t M, B, ok, T; uint8_t field[kSearchMaxField]; };
 struct SearchHop { uint64_t from, limit; };                               // where a lane starts to hop and the data chunk's body, which it never reaches
 
 __device__ __forceinline__ bool search_is_data(uint8_t t) { return t >= 1 && t <= 3; }
@@ -20,7 +21,7 @@ __device__ __forceinline__ bool search_is_data(uint8_t t) { return t >= 1 && t <
 __global__ __launch_bounds__(64) void search_info_kernel(const uint8_t* __restrict__ src, uint64_t limit /* the first data chunk's body, or the stream's end */,
                                                          SearchInfo* __restrict__ out) {
     if (blockIdx.x || threadIdx.x) return;
-    SearchInfo r{0, 0, 0, 0};
+    SearchInfo r{};
     bool seen_id = false;
     for (uint64_t p = 0; p + 4 <= limit;) {
         uint8_t type;
@@ -28,7 +29,7 @@ __global__ __launch_bounds__(64) void search_info_kernel(const uint8_t* __restri
         if (search_is_data(type)) break;
         if (type == 0xff) seen_id = true;
         else if (type == kChunkSearchInfo && seen_id) {
-            if (p + 4 + clen <= limit) r.ok = search_info(src + p + 4, clen, &r.M, &r.B) ? 1 : 0;
+            if (p + 4 + clen <= limit) r.ok = search_info(src + p + 4, clen, &r.T, &r.M, &r.B, r.field) ? 1 : 0;
             break;
         }
         p += 4 + uint64_t(clen);
@@ -51,10 +52,11 @@ __global__ __launch_bounds__(64) void search_locate_kernel(const uint8_t* __rest
             const uint32_t clen = walk_header(src, p, &type);
             if (search_is_data(type)) break;
             if (type == kChunkSearchTable && p + 4 + clen <= limit) {
-                const int R = search_table_reductions(src + p + 4, clen, in.M, in.B);
+                const int R = search_table_reductions(src + p + 4, clen, in.M, in.B, in.T, in.field);
                 if (R >= 0 && left-- == 0) {
-                    const uint8_t* q = src + p + 8;
-                    t = SearchTab{p + 12, clen - 8, uint32_t(R), uint32_t(q[0]) | uint32_t(q[1]) << 8 | uint32_t(q[2]) << 16 | uint32_t(q[3]) << 24, 0};
+                    const uint32_t f = search_field_len(in.T);
+                    const uint8_t* q = src + p + 8 + f;
+                    t = SearchTab{p + 12 + f, clen - 8 - f, uint32_t(R), uint32_t(q[0]) | uint32_t(q[1]) << 8 | uint32_t(q[2]) << 16 | uint32_t(q[3]) << 24, 0};
                     break;
                 }
             }
@@ -136,7 +138,7 @@ __global__ __launch_bounds__(kSearchTileWords) void search_write_kernel(const Se
 
 namespace {
 
-// Once per handle and CRC mode: (M, B) of the stream and every data chunk's table.  Caller holds c->mu.
+// Once per handle and CRC mode: (T, M, B, prefix field) of the stream and every data chunk's table.  Caller holds c->mu.
 int64_t dev_reader_search_tables(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc) {
     mlz_dev_reader::SearchTables& st = rd->search[ignore_crc ? 1 : 0];
     if (st.ready) return 0;
@@ -171,7 +173,8 @@ int64_t dev_reader_search_tables(mlz_dev_reader* rd, hipStream_t sm, bool ignore
         HIPCHK(c, hipMemcpyAsync(h_tabs, d_tabs, nck * sizeof(mlz::SearchTab), hipMemcpyDeviceToHost, sm));
         if ((r = fetch(c, sm, h_info, d_info, sizeof(mlz::SearchInfo)))) return r;
         st.tabs.assign(h_tabs, h_tabs + nck);
-        st.M = h_info->M; st.B = h_info->B; st.info = h_info->ok != 0;
+        st.M = h_info->M; st.B = h_info->B; st.T = h_info->T; st.info = h_info->ok != 0;
+        std::memcpy(st.field, h_info->field, sizeof(st.field));
         if (ignore_crc || !st.info) break;
         std::vector<mlz_block_desc> desc;
         std::vector<size_t> who;
@@ -207,14 +210,16 @@ int64_t dev_reader_search_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t fl
         const int64_t r = dev_reader_search_tables(rd, sm, ignore_crc);
         if (r) return r;
         const mlz_dev_reader::SearchTables& st = rd->search[ignore_crc ? 1 : 0];
-        with_tables = st.info && L >= st.M && st.usable;
+        // the windows the tables answer for: all of them (type 1), or those behind a prefix byte; none: the tables cannot serve this pattern
+        uint32_t win[mlz::kSearchMaxPattern], t_min = 1;
+        const uint32_t nw = st.info && st.usable ? mlz::search_windows(pattern, L, st.T, st.M, st.field, win, &t_min) : 0;
+        with_tables = nw != 0;
         if (with_tables) {
             // the windows' hashes go up, two counts per chunk come back
-            const uint32_t nw = L - st.M + 1;
             std::vector<uint32_t> hs(nw);
             for (uint32_t i = 0; i < nw; i++) {
                 uint64_t v = 0;
-                for (uint32_t j = 0; j < st.M; j++) v |= uint64_t(pattern[i + j]) << (8 * j);
+                for (uint32_t j = 0; j < st.M; j++) v |= uint64_t(pattern[win[i] + j]) << (8 * j);
                 hs[i] = mlz::search_hash(v, st.B, st.M);
             }
             Carve cv;
@@ -232,7 +237,7 @@ int64_t dev_reader_search_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t fl
             if ((e = fetch(c, sm, c->pinned2, d_out, nck * 8))) return e;
             const uint32_t* as = static_cast<const uint32_t*>(c->pinned2);
             n_take = mlz::search_decoded_set(nck, [&](size_t k) { return as[2 * k]; }, [&](size_t k) { return as[2 * k + 1]; },
-                                             [&](size_t k) { return uint64_t(rd->chunks[k].n); }, nw, L, take.data());
+                                             [&](size_t k) { return uint64_t(rd->chunks[k].n); }, nw, L, take.data(), t_min);
             c->search_tables = st.usable;
         }
     }

@@ -11,6 +11,12 @@
 //           -> the occurrences found by search_layout's tiles, executed as the search executes them: the taken chunks of a group copied to
 //           their places in ONE reused scratch, every tile compared position by position, the carried bytes copied in front of the next
 //           group: "count tiles groups scratch_max :" and the positions
+// The prefix tables' rules (table types 2 and 3), for tests/test_stream_search_prefix_host.py:
+//   kind 6  as kind 3, over a stream of any table type 1 .. 3                  -> "T M B usable nw t_min :" and the decoded set (usable, nw = 0: the tables
+//           were not used)
+//   kind 7  u32 nck, nw, L, t_min; nck x u32 a; nck x u32 s; nck x u64 n       -> the decoded set (search_decoded_set with t_min)
+//   kind 8  u32 B, limit; (B - 8 + 1) x u32 pop                                -> table bytes and R (search_reduce_rule with the fold limit in per cent)
+//   kind 9  u32 T, M, L; 32 bytes of prefix field; pattern                     -> "t_min :" and the starts of the checkable windows (search_windows)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -43,7 +49,7 @@ void print_set(const std::vector<uint8_t>& take) {
     std::printf("\n");
 }
 
-void run_stream(const uint8_t* s, uint64_t slen, const uint8_t* pat, uint32_t L, uint32_t flags) {
+void run_stream(const uint8_t* s, uint64_t slen, const uint8_t* pat, uint32_t L, uint32_t flags, bool prefix_kind = false) {
     // the data chunks (a valid stream: the walk's table)
     std::vector<Data> ck;
     uint64_t end = 0;
@@ -62,7 +68,8 @@ void run_stream(const uint8_t* s, uint64_t slen, const uint8_t* pat, uint32_t L,
     const size_t nck = ck.size();
     auto is_data = [](uint8_t t) { return t >= 1 && t <= 3; };
     // search_info_kernel
-    uint32_t M = 0, B = 0;
+    uint32_t M = 0, B = 0, T = 0;
+    uint8_t field[mlz::kSearchMaxField] = {};
     bool ok = false, seen_id = false;
     const uint64_t limit0 = nck ? ck[0].body_off : slen;
     for (uint64_t p = 0; p + 4 <= limit0;) {
@@ -70,7 +77,7 @@ void run_stream(const uint8_t* s, uint64_t slen, const uint8_t* pat, uint32_t L,
         const uint32_t clen = uint32_t(s[p + 1]) | uint32_t(s[p + 2]) << 8 | uint32_t(s[p + 3]) << 16;
         if (is_data(type)) break;
         if (type == 0xff) seen_id = true;
-        else if (type == mlz::kChunkSearchInfo && seen_id) { if (p + 4 + clen <= limit0) ok = mlz::search_info(s + p + 4, clen, &M, &B); break; }
+        else if (type == mlz::kChunkSearchInfo && seen_id) { if (p + 4 + clen <= limit0) ok = mlz::search_info(s + p + 4, clen, &T, &M, &B, field); break; }
         p += 4 + uint64_t(clen);
     }
     // search_locate_kernel and the CRC rounds
@@ -84,32 +91,36 @@ void run_stream(const uint8_t* s, uint64_t slen, const uint8_t* pat, uint32_t L,
                 const uint32_t clen = uint32_t(s[p + 1]) | uint32_t(s[p + 2]) << 8 | uint32_t(s[p + 3]) << 16;
                 if (is_data(type)) break;
                 if (type == mlz::kChunkSearchTable && p + 4 + clen <= limit) {
-                    const int R = mlz::search_table_reductions(s + p + 4, clen, M, B);
-                    uint32_t crc; std::memcpy(&crc, s + p + 8, 4);
-                    if (R >= 0 && ((flags & 2) || masked_crc(s + p + 12, clen - 8) == crc)) { tabs[k] = mlz::SearchTab{p + 12, clen - 8, uint32_t(R), crc, 0}; usable++; break; }
+                    const int R = mlz::search_table_reductions(s + p + 4, clen, M, B, T, field);
+                    const uint32_t f = mlz::search_field_len(T);
+                    uint32_t crc = 0;
+                    if (R >= 0) std::memcpy(&crc, s + p + 8 + f, 4);
+                    if (R >= 0 && ((flags & 2) || masked_crc(s + p + 12 + f, clen - 8 - f) == crc)) { tabs[k] = mlz::SearchTab{p + 12 + f, clen - 8 - f, uint32_t(R), crc, 0}; usable++; break; }
                 }
                 p += 4 + uint64_t(clen);
             }
         }
     std::vector<uint8_t> take(nck, 0);
-    const bool with = !(flags & 1) && ok && L >= M && usable;
-    if (!with) {
+    uint32_t win[mlz::kSearchMaxPattern], t_min = 1;
+    const uint32_t nw = !(flags & 1) && ok && usable ? mlz::search_windows(pat, L, T, M, field, win, &t_min) : 0;
+    if (!nw) {
         for (size_t k = 0; k < nck; k++) take[k] = ck[k].n ? 1 : 0;
-        std::printf("%u %u 0 :", M, B);
+        if (prefix_kind) std::printf("%u %u %u 0 0 %u :", T, M, B, t_min);
+        else std::printf("%u %u 0 :", M, B);
         print_set(take);
         return;
     }
-    const uint32_t nw = L - M + 1;
     std::vector<uint32_t> h(nw), a(nck, nw), sv(nck, nw);
     for (uint32_t i = 0; i < nw; i++) {
         uint64_t v = 0;
-        for (uint32_t j = 0; j < M; j++) v |= uint64_t(pat[i + j]) << (8 * j);
+        for (uint32_t j = 0; j < M; j++) v |= uint64_t(pat[win[i] + j]) << (8 * j);
         h[i] = mlz::search_hash(v, B, M);
     }
     for (size_t k = 0; k < nck; k++)
         if (tabs[k].R != mlz::kSearchNoTable) mlz::search_probe(s + tabs[k].off, B - tabs[k].R, h.data(), nw, &a[k], &sv[k]);
-    mlz::search_decoded_set(nck, [&](size_t k) { return a[k]; }, [&](size_t k) { return sv[k]; }, [&](size_t k) { return ck[k].n; }, nw, L, take.data());
-    std::printf("%u %u %zu :", M, B, usable);
+    mlz::search_decoded_set(nck, [&](size_t k) { return a[k]; }, [&](size_t k) { return sv[k]; }, [&](size_t k) { return ck[k].n; }, nw, L, take.data(), t_min);
+    if (prefix_kind) std::printf("%u %u %u %zu %u %u :", T, M, B, usable, nw, t_min);
+    else std::printf("%u %u %zu :", M, B, usable);
     print_set(take);
 }
 
@@ -194,6 +205,38 @@ int main(int argc, char** argv) {
             }
             std::printf("%zu %zu %zu %llu :", found.size(), lay.tiles.size(), gend.size(), (unsigned long long)lay.scratch_max);
             for (uint64_t p : found) std::printf(" %llu", (unsigned long long)p);
+            std::printf("\n");
+        } else if (kind == 6) {
+            const uint64_t slen = in.get<uint64_t>();
+            const uint32_t L = in.get<uint32_t>(), flags = in.get<uint32_t>();
+            const uint8_t* s = in.bytes(size_t(slen));
+            const uint8_t* pat = in.bytes(L);
+            run_stream(s, slen, pat, L, flags, true);
+        } else if (kind == 7) {
+            const uint32_t nck = in.get<uint32_t>(), nw = in.get<uint32_t>(), L = in.get<uint32_t>(), t_min = in.get<uint32_t>();
+            std::vector<uint32_t> a(nck), s(nck);
+            std::vector<uint64_t> n(nck);
+            for (auto& v : a) v = in.get<uint32_t>();
+            for (auto& v : s) v = in.get<uint32_t>();
+            for (auto& v : n) v = in.get<uint64_t>();
+            std::vector<uint8_t> take(nck);
+            mlz::search_decoded_set(nck, [&](size_t k) { return a[k]; }, [&](size_t k) { return s[k]; }, [&](size_t k) { return n[k]; }, nw, L, take.data(), t_min);
+            print_set(take);
+        } else if (kind == 8) {
+            const uint32_t B = in.get<uint32_t>(), limit = in.get<uint32_t>();
+            std::vector<uint32_t> pop(B - 8 + 1);
+            for (auto& v : pop) v = in.get<uint32_t>();
+            uint32_t R = 0;
+            const uint32_t bytes = mlz::search_reduce_rule(pop.data(), B, &R, limit);
+            std::printf(" %u %u\n", bytes, R);
+        } else if (kind == 9) {
+            const uint32_t T = in.get<uint32_t>(), M = in.get<uint32_t>(), L = in.get<uint32_t>();
+            const uint8_t* field = in.bytes(mlz::kSearchMaxField);
+            const uint8_t* pat = in.bytes(L);
+            uint32_t win[mlz::kSearchMaxPattern], t_min = 0;
+            const uint32_t nw = mlz::search_windows(pat, L, T, M, field, win, &t_min);
+            std::printf("%u :", t_min);
+            for (uint32_t i = 0; i < nw; i++) std::printf(" %u", win[i]);
             std::printf("\n");
         } else {
             std::fprintf(stderr, "unknown record %u\n", kind);
