@@ -277,3 +277,76 @@ func HIPDecodeStream(dst, src []byte, ignoreCRC bool) ([]byte, error) {
 	}
 	return dst[:n], nil
 }
+
+// LongPrefixTables configures block search tables of type 4 (SPEC_SEARCH.md 3.3.4; WriterSearchTable with WithLongPrefix / WithExtras):
+// every block indexes the Extras + 1 windows of MatchLen bytes behind each occurrence of Prefix (1 to 256 bytes).
+// MatchLen 0 is the reference's default 6; MatchLen + Extras is at most 16.
+type LongPrefixTables struct {
+	Prefix   []byte
+	MatchLen int
+	Extras   int
+}
+
+func (t LongPrefixTables) cfg() (C.mlz_search_long_prefix, error) {
+	var c C.mlz_search_long_prefix
+	if len(t.Prefix) < 1 || len(t.Prefix) > 256 || t.MatchLen < 0 || t.MatchLen > 8 || t.Extras < 0 || t.Extras > 15 {
+		return c, fmt.Errorf("minlz: long-prefix search tables: prefix of 1..256 bytes, match length 0..8, extras 0..15")
+	}
+	c.match_len = C.uint8_t(t.MatchLen)
+	c.extras = C.uint8_t(t.Extras)
+	c.prefix_len = C.uint16_t(len(t.Prefix))
+	for i, b := range t.Prefix {
+		c.prefix[i] = C.uint8_t(b)
+	}
+	return c, nil
+}
+
+// HIPStreamBoundLongPrefix is mlz_stream_bound_long_prefix: the room HIPEncodeStreamDeviceLongPrefix needs for n bytes of input.
+func HIPStreamBoundLongPrefix(n, blockSize int, addIndex bool, t LongPrefixTables) (int, error) {
+	c, err := t.cfg()
+	if err != nil {
+		return 0, err
+	}
+	var flags C.uint32_t
+	if addIndex {
+		flags |= C.MLZ_STREAM_ADD_INDEX
+	}
+	r := C.mlz_stream_bound_long_prefix(C.uint64_t(n), C.uint32_t(blockSize), flags, &c)
+	if r < 0 {
+		return 0, hipError(int(-r))
+	}
+	return int(r), nil
+}
+
+// HIPEncodeStreamDeviceLongPrefix is mlz_stream_encode_gather_device_long_prefix: the ranges of one stream, resident in the memory of the
+// context's devices (dSrc: device addresses, srcLen: their bytes; all ranges but the last are whole blocks), become the framed stream
+// with type 4 search tables at the device address dDst (dstCap bytes of room).  It returns the stream's size.  mlz_dev_reader_search
+// uses these tables with no further configuration.
+func HIPEncodeStreamDeviceLongPrefix(dDst unsafe.Pointer, dstCap int, dSrc []unsafe.Pointer, srcLen []int, level, blockSize int, addIndex bool, t LongPrefixTables) (int, error) {
+	c := hipContext()
+	if c == nil {
+		return 0, ErrHIP
+	}
+	if len(dSrc) == 0 || len(dSrc) != len(srcLen) {
+		return 0, fmt.Errorf("minlz: one length per source range")
+	}
+	cfg, err := t.cfg()
+	if err != nil {
+		return 0, err
+	}
+	var flags C.uint32_t
+	if addIndex {
+		flags |= C.MLZ_STREAM_ADD_INDEX
+	}
+	lens := make([]C.size_t, len(srcLen))
+	for i, n := range srcLen {
+		lens[i] = C.size_t(n)
+	}
+	// device addresses are not Go pointers (cgo's pointer check passes them): the slice is the array of const uint8_t* the ABI asks for
+	r := C.mlz_stream_encode_gather_device_long_prefix(c, C.int(level), C.uint32_t(blockSize), flags, &cfg,
+		(**C.uint8_t)(unsafe.Pointer(&dSrc[0])), &lens[0], C.int(len(dSrc)), (*C.uint8_t)(dDst), C.size_t(dstCap))
+	if r < 0 {
+		return 0, hipError(int(-r))
+	}
+	return int(r), nil
+}

@@ -194,7 +194,8 @@ int64_t mlz_stream_decode(mlz_ctx* ctx, uint32_t flags, const uint8_t* src, size
  * halves R times, while at most a quarter of the folded bits are set and 32 bytes remain.  Two kernels build and fold the tables over the raw blocks in HBM;
  * 12 more bytes per block visit the host (table bytes or 0, R, CRC).  The seek index names a block by the offset at which its chunks start: its table chunk
  * when it has one.  mlz_stream_bound with the flag adds 7 + (12 + max(32, 2^(B - 3))) per block.  Without the flag every byte is what it was before the
- * flag existed.  Out of scope: the long prefix (type 4), compressed tables (0x46), sidecars and remote references (0x47). */
+ * flag existed.  Table type 4 (the long prefix) is written by mlz_stream_encode_gather_device_long_prefix below.  Out of scope: compressed tables (0x46),
+ * sidecars and remote references (0x47). */
 int64_t mlz_stream_encode_gather_device(mlz_ctx* ctx, int level, uint32_t block_size, uint32_t flags, const uint8_t* const* d_src, const size_t* src_len,
                                         int n_ranges, uint8_t* d_dst, size_t dst_cap);
 
@@ -222,6 +223,31 @@ typedef struct {
 int64_t mlz_stream_bound_tables(uint64_t n, uint32_t block_size, uint32_t flags, const mlz_search_tables* cfg);
 int64_t mlz_stream_encode_gather_device_tables(mlz_ctx* ctx, int level, uint32_t block_size, uint32_t flags, const mlz_search_tables* cfg,
                                                const uint8_t* const* d_src, const size_t* src_len, int n_ranges, uint8_t* d_dst, size_t dst_cap);
+
+/* Search tables with a long prefix and extra matches (SPEC_SEARCH.md 3.3.4, A.4, B.1; the reference's WithLongPrefix / WithExtras): table type 4.  The
+ * prefix field of the info chunk and of every table chunk is `K-1 | E | pfx` (2 + K bytes).  A block of n bytes indexes every start p of the K-byte prefix
+ * — 0 <= p <= n - 1 when a block follows, 0 <= p <= n - K - M - E in the stream's last block — with the E + 1 bits HashValue(window at p + K + j, B, M),
+ * j = 0 .. E.  Prefix and windows run into the K - 1 + M + E bytes that follow the block in the stream (across ranges these bytes visit the host); the
+ * windows run into zeros beyond the stream's end, a prefix does not.  An occurrence belongs to the block in which its prefix starts.  The table rules are
+ * those of types 2 and 3: dropped above 70 %, a fold accepted up to a tenth, 32 bytes at the least, the all-zero table (R = B - 8) for a block without an
+ * indexed start, none for a stored block, in front of its block, the seek index points at the table chunk.
+ * mlz_stream_encode_gather_device_long_prefix: -MLZ_ERR_ARG for a NULL cfg, prefix_len outside 1 .. 256, match_len > 8, match_len + extras > 16 (after the
+ *   default), extras > 15, reserved bytes that are not 0, flags that carry MLZ_STREAM_SEARCH_TABLES or match-length bits; nothing is written then.  An
+ *   empty stream has no header and no info chunk.  mlz_stream_encode_gather_device_tables keeps refusing table_type 4.
+ * mlz_stream_bound_long_prefix: the dst_cap that always suffices: mlz_stream_bound without tables + (7 + 2 + K) + (12 + 2 + K + max(32, 2^(B - 3))) per
+ *   block.  Needs no device.
+ * mlz_dev_reader_search uses these tables with no new call: the pattern's groups are the prefix's occurrences P[i, i + K) == pfx with i + K + M + E <= L,
+ *   a table is probed for whole groups, and a pattern without a group (the reference's prefix-only query included) decodes every chunk. */
+typedef struct {
+    uint8_t match_len;   /* 1 .. 8; 0 = 6 */
+    uint8_t extras;      /* 0 .. 15, match_len + extras <= 16 */
+    uint16_t prefix_len; /* 1 .. 256 */
+    uint8_t reserved[4]; /* 0 */
+    uint8_t prefix[256];
+} mlz_search_long_prefix;
+int64_t mlz_stream_bound_long_prefix(uint64_t n, uint32_t block_size, uint32_t flags, const mlz_search_long_prefix* cfg);
+int64_t mlz_stream_encode_gather_device_long_prefix(mlz_ctx* ctx, int level, uint32_t block_size, uint32_t flags, const mlz_search_long_prefix* cfg,
+                                                    const uint8_t* const* d_src, const size_t* src_len, int n_ranges, uint8_t* d_dst, size_t dst_cap);
 
 /* The device-resident Reader: the stream lies in HBM at d_src (n bytes), on a device of the context; the call runs on that device (-MLZ_ERR_ARG if none
  * of the context's devices holds d_src, as for the *_batch_device calls; one HBM-resident stream is not fanned out over several devices).  `stream` is
@@ -299,16 +325,16 @@ int64_t mlz_dev_reader_read_device(mlz_dev_reader* reader, void* stream, uint32_
 void mlz_dev_reader_close(mlz_dev_reader* reader);
 
 /* Pattern search over a stream that lies in HBM, with the reference's block search tables (SPEC_SEARCH.md; search_table.go, search_index.go) where
- * the stream has them: table types 1 (no prefix), 2 (1 to 8 prefix byte values) and 3 (a mask of prefix byte values) in uncompressed table chunks
- * (0x45) behind an info chunk (0x44).  Long-prefix tables (type 4), compressed tables (0x46) and remote references (0x47) are stepped over: their
- * blocks count as having no table.
+ * the stream has them: table types 1 (no prefix), 2 (1 to 8 prefix byte values), 3 (a mask of prefix byte values) and 4 (a long prefix with extra
+ * matches) in uncompressed table chunks (0x45) behind an info chunk (0x44).  Compressed tables (0x46) and remote references (0x47) are stepped over:
+ * their blocks count as having no table.
  *
  * mlz_dev_reader_search: returns the number of positions p of the decoded stream with decoded[p, p + pattern_len) == pattern (overlapping occurrences
  *   count; the value may exceed cap); d_offsets (on the handle's device; may be NULL when cap == 0) receives the min(total, cap) smallest positions in
  *   ascending order and nothing beyond them is written.  `pattern` is host memory, pattern_len 1 .. 256.  -MLZ_ERR_ARG: pattern_len 0 or above 256, a
  *   NULL pattern, d_offsets NULL with cap > 0 or not on the handle's device.  Synchronous; `stream` as for mlz_dev_reader_read.
  *   Tables: (T, M, B, prefix field) is that of the stream's info chunk, the first 0x44 between the identifier and the first data chunk, when its type
- *   is 1, 2 or 3 and its payload holds the field.  A data chunk's table is the first 0x45 chunk between the previous data chunk's end and its own start
+ *   is 1 .. 4 and its payload holds the field (type 4: with E <= 15 and M + E <= 16).  A data chunk's table is the first 0x45 chunk between the previous data chunk's end and its own start
  *   whose T, M, B and prefix field are byte-equal to the stream's, with R <= B - 8, a payload of 8 + field + 2^(B - R - 3) bytes and a good CRC (not checked
  *   under MLZ_STREAM_IGNORE_CRC).  Anything else — no info chunk, pattern_len < M, a broken CRC — means the chunk has no usable table.  The tables are located by a kernel (one lane per data chunk) and their CRCs checked once per handle.
  *   Plan: the pattern's pattern_len - M + 1 windows are looked up in every table; a chunk is a candidate when all are present in its own table, or

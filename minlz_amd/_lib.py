@@ -21,6 +21,7 @@ SYMBOLS = [
     "mlz_stream_open_device", "mlz_dev_reader_size", "mlz_dev_reader_read", "mlz_dev_reader_close",
     "mlz_dev_reader_read_device", "mlz_dev_reader_search",
     "mlz_stream_bound_tables", "mlz_stream_encode_gather_device_tables",
+    "mlz_stream_bound_long_prefix", "mlz_stream_encode_gather_device_long_prefix",
 ]
 
 
@@ -32,6 +33,11 @@ class Range(C.Structure):
 class SearchTables(C.Structure):
     """mlz_search_tables: table type 1, 2 (n_prefix byte values in prefix) or 3 (prefix = a 256-bit mask), match length (0 = 6)."""
     _fields_ = [("table_type", C.c_uint8), ("match_len", C.c_uint8), ("n_prefix", C.c_uint8), ("reserved", C.c_uint8), ("prefix", C.c_uint8 * 32)]
+
+
+class SearchLongPrefix(C.Structure):
+    """mlz_search_long_prefix: table type 4, a prefix of 1 .. 256 bytes, match length (0 = 6) and extras (0 .. 15, match_len + extras <= 16)."""
+    _fields_ = [("match_len", C.c_uint8), ("extras", C.c_uint8), ("prefix_len", C.c_uint16), ("reserved", C.c_uint8 * 4), ("prefix", C.c_uint8 * 256)]
 
 
 class BlockDesc(C.Structure):
@@ -86,6 +92,9 @@ def lib():
     L.mlz_stream_bound_tables.argtypes = [u64, u32, u32, C.POINTER(SearchTables)]; L.mlz_stream_bound_tables.restype = i64
     L.mlz_stream_encode_gather_device_tables.argtypes = [vp, i32, u32, u32, C.POINTER(SearchTables), C.POINTER(vp), C.POINTER(sz), i32, vp, sz]
     L.mlz_stream_encode_gather_device_tables.restype = i64
+    L.mlz_stream_bound_long_prefix.argtypes = [u64, u32, u32, C.POINTER(SearchLongPrefix)]; L.mlz_stream_bound_long_prefix.restype = i64
+    L.mlz_stream_encode_gather_device_long_prefix.argtypes = [vp, i32, u32, u32, C.POINTER(SearchLongPrefix), C.POINTER(vp), C.POINTER(sz), i32, vp, sz]
+    L.mlz_stream_encode_gather_device_long_prefix.restype = i64
     L.mlz_stream_decode.argtypes = [vp, u32, vp, sz, vp, sz]; L.mlz_stream_decode.restype = i64
     L.mlz_stream_decoded_len_device.argtypes = [vp, vp, vp, sz, C.POINTER(u64)]; L.mlz_stream_decoded_len_device.restype = i64
     L.mlz_stream_decode_device.argtypes = [vp, vp, u32, vp, sz, vp, sz]; L.mlz_stream_decode_device.restype = i64

@@ -130,14 +130,31 @@ class Context:
         if r:
             _raise(r, self)
 
-    def stream_encode_gather_device(self, level, block_size, add_index, d_srcs, lens, d_dst, dst_cap, search_match_len=None, search_prefix=None):
+    def stream_encode_gather_device(self, level, block_size, add_index, d_srcs, lens, d_dst, dst_cap, search_match_len=None, search_prefix=None,
+                                    search_long_prefix=None, search_extras=0):
         """mlz_stream_encode_gather_device: ranges of one stream resident on the context's devices -> the framed stream in d_dst (device memory).
         search_match_len: None = no search tables; 0 = block search tables with the reference's default match length (6); 1 .. 8 = with that one.
         search_prefix (with search_match_len): an iterable of byte values; the tables then index only the positions behind one of them
         (mlz_stream_encode_gather_device_tables: 1 to 8 distinct values give table type 2, in sorted order, more give type 3).
+        search_long_prefix (with search_match_len, not with search_prefix): 1 .. 256 bytes; the tables then index the search_extras + 1
+        windows behind every occurrence of that byte string (mlz_stream_encode_gather_device_long_prefix, table type 4; search_extras 0 .. 15,
+        match length + extras <= 16).
         Returns the stream size."""
         n = len(d_srcs)
         sp = (C.c_void_p * n)(*d_srcs); sl = (C.c_size_t * n)(*lens)
+        if search_long_prefix is not None:
+            if search_prefix is not None:
+                raise ValueError("search_long_prefix and search_prefix exclude each other")
+            if search_match_len is None:
+                raise ValueError("search_long_prefix needs search_match_len")
+            cfg = search_long_prefix_config(search_match_len, search_long_prefix, search_extras)
+            r = _lib.lib().mlz_stream_encode_gather_device_long_prefix(self.handle, level, block_size, STREAM_ADD_INDEX if add_index else 0, C.byref(cfg), sp, sl, n,
+                                                                       d_dst, dst_cap)
+            if r < 0:
+                _raise(r, self)
+            return int(r)
+        if search_extras:
+            raise ValueError("search_extras needs search_long_prefix")
         if search_prefix is not None:
             if search_match_len is None:
                 raise ValueError("search_prefix needs search_match_len")
@@ -242,7 +259,7 @@ class DeviceReader:
     def search(self, pattern, d_offsets, cap, ignore_crc=False, no_tables=False, stream=None):
         """mlz_dev_reader_search.  pattern: 1 .. 256 bytes; d_offsets: device address of room for `cap` uint64 (None with cap == 0), which
         receives the smallest min(total, cap) positions of the pattern in the decoded stream, ascending.
-        Uses the stream's block search tables of type 1, 2 or 3 (with a prefix table: the pattern's windows that follow a prefix byte; a
+        Uses the stream's block search tables of type 1, 2, 3 or 4 (with a prefix table: the pattern's windows that follow a prefix byte; a
         pattern without one is served by decoding every chunk, and the usable-table count is then 0).
         -> (total, (data chunks, chunks decoded or copied, chunks with a usable search table))."""
         if not self.handle:
@@ -463,6 +480,24 @@ def search_tables_config(match_len, prefix):
         cfg.table_type = 3
         for v in vals:
             cfg.prefix[v >> 3] |= 1 << (v & 7)
+    return cfg
+
+
+def search_long_prefix_config(match_len, prefix, extras=0):
+    """An mlz_search_long_prefix (table type 4): a prefix of 1 .. 256 bytes, match length 0 (= 6) .. 8, extras 0 .. 15 with match length +
+    extras <= 16.  ValueError outside these ranges."""
+    pfx = bytes(prefix)
+    match_len, extras = int(match_len), int(extras)
+    if not 1 <= len(pfx) <= 256:
+        raise ValueError("search_long_prefix: 1 .. 256 bytes")
+    if not 0 <= match_len <= 8:
+        raise ValueError("search_match_len: 0 .. 8")
+    if not 0 <= extras <= 15 or (match_len or 6) + extras > 16:
+        raise ValueError("search_extras: 0 .. 15, match length + extras <= 16")
+    cfg = _lib.SearchLongPrefix()
+    cfg.match_len, cfg.extras, cfg.prefix_len = match_len, extras, len(pfx)
+    for i, v in enumerate(pfx):
+        cfg.prefix[i] = v
     return cfg
 
 

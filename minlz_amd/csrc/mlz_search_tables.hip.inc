@@ -17,6 +17,13 @@
 //   stab_build_kernel<true> is the prefix form: a lane's 16 bytes start one byte in front of its 8 positions, the 256-bit set of prefix bytes
 //   lies in 32 bytes of LDS (a per-lane byte indexes it with one ds_read), and the hash and the ds_or run for positions behind a prefix byte only:
 //   a lane first gathers its 8 positions' verdicts into a bit mask and then loops over the set bits.
+// Table type 4 (SPEC_SEARCH.md 3.3.4; search_index.go: buildTablePrefixLong, the overlap tail and the straddling prefix, whose union this is):
+//   every start p of the K-byte prefix in the block — all of 0 .. n - 1 with a block behind, 0 .. n - K - M - E in the stream's last block —
+//   sets the E + 1 bits of the windows at p + K + j; prefix and windows run into the K - 1 + M + E bytes that follow the block, the windows
+//   into zeros beyond the stream's end (a prefix never does).
+// stab_build_long_kernel is that form: a lane's 8 positions are prefix starts and every read goes forward.  Stage one compares the first
+//   min(K, 8) prefix bytes in registers with the lane's 16 loaded bytes and gathers 8 verdicts into a bit mask; stage two loops over the set
+//   bits only, compares the rest of the prefix (in LDS behind the bitmap) and hashes the E + 1 windows.
 // stab_reduce_kernel: a workgroup per block counts the bits, applies the rules above fold by fold (search_reduce_rule's conditions) and leaves
 //   the table compact at the front of its slot; 8 bytes per block (table bytes or 0, R) go to the host next to the sizes and CRCs.
 
@@ -118,6 +125,92 @@ __global__ __launch_bounds__(kStabThreads) void stab_build_kernel(const StabArgs
     }
 }
 
+// The long-prefix form (table type 4).  The bytes behind the range (K - 1 + M + E at the most) and the prefix travel in the kernel arguments.
+constexpr uint32_t kStabLongTail = 272;   // >= 255 + 16
+struct StabLongArgs {
+    const uint8_t* src;
+    uint64_t len;
+    uint32_t tail_n;         // bytes of `tail` that exist (0: the range ends the stream)
+    uint32_t bs, cnt, B, M, E, K, parts, slices;
+    uint32_t* tabs;
+    uint8_t pfx[kSearchMaxPrefix];
+    uint8_t tail[kStabLongTail];
+};
+
+__global__ __launch_bounds__(kStabThreads) void stab_build_long_kernel(const StabLongArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    uint32_t* bits = reinterpret_cast<uint32_t*>(smem);
+    const uint32_t tid = threadIdx.x;
+    const uint32_t part = blockIdx.x % a.parts, slice = (blockIdx.x / a.parts) % a.slices, b = blockIdx.x / (a.parts * a.slices);
+    const uint32_t lbits = a.B < kStabSliceBits ? a.B : kStabSliceBits, words = 1u << (lbits - 5);
+    for (uint32_t i = tid; i < words; i += kStabThreads) bits[i] = 0;
+    uint8_t* lpfx = smem + words * 4;            // the prefix and, behind it, the bytes that follow the range
+    uint8_t* ltail = lpfx + kSearchMaxPrefix;
+    if (tid < a.K) lpfx[tid] = a.pfx[tid];
+    if (tid < kStabLongTail) ltail[tid] = tid < a.tail_n ? a.tail[tid] : 0;
+    __syncthreads();
+    const uint32_t M = a.M, B = a.B, E = a.E, K = a.K;
+    const uint64_t b0 = uint64_t(b) * a.bs, real = a.len + a.tail_n;   // real: where the stream's bytes that this range can see end
+    const uint32_t blen = uint32_t(a.len - b0 < a.bs ? a.len - b0 : a.bs);
+    const bool next = b + 1 < a.cnt || a.tail_n != 0;
+    // prefix starts [0, npos): every position with a block behind, else those whose prefix and windows lie inside the block
+    const uint32_t npos = next ? blen : (blen >= K + M + E ? blen - K - M - E + 1 : 0);
+    const uint32_t per = ((npos + a.parts - 1) / a.parts + kStabPerThread - 1) & ~(kStabPerThread - 1);
+    const uint32_t p0 = part * per, p1 = p0 + per < npos ? p0 + per : npos;
+    auto byte_at = [&](uint64_t q) -> uint64_t {   // byte q of the range, continued by the bytes behind it and zeros
+        if (q < a.len) return a.src[q];
+        const uint64_t over = q - a.len;
+        return over < kStabLongTail ? ltail[over] : 0;
+    };
+    auto load8 = [&](uint64_t q) -> uint64_t {
+        uint64_t v = 0;
+        if (q + 8 <= a.len) __builtin_memcpy(&v, a.src + q, 8);
+        else for (uint32_t j = 0; j < 8; j++) v |= byte_at(q + j) << (8 * j);
+        return v;
+    };
+    const uint32_t k8 = K < 8 ? K : 8;
+    const uint64_t m8 = k8 == 8 ? ~uint64_t(0) : (uint64_t(1) << (8 * k8)) - 1;
+    uint64_t p8 = 0;
+    for (uint32_t j = 0; j < k8; j++) p8 |= uint64_t(lpfx[j]) << (8 * j);
+    for (uint32_t i = p0 + tid * kStabPerThread; i < p1; i += kStabThreads * kStabPerThread) {
+        const uint64_t q = b0 + i;
+        const uint64_t lo = load8(q), hi = load8(q + 8);
+        // bit j of todo: the prefix's first bytes stand at position i + j.  Then one round per set bit: a wave runs as many rounds as its
+        // busiest lane has such positions
+        uint32_t todo = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < kStabPerThread; j++) {
+            const uint64_t v = j ? (lo >> (8 * j)) | (hi << (64 - 8 * j)) : lo;
+            todo |= uint32_t((v & m8) == p8) << j;
+        }
+        if (p1 - i < kStabPerThread) todo &= (1u << (p1 - i)) - 1;   // the part's last positions
+        for (; todo; todo &= todo - 1) {
+            const uint64_t s = q + uint32_t(__builtin_ctz(todo));
+            if (s + K > real) continue;                               // a prefix does not run beyond the stream's end
+            uint32_t t = 8;
+            while (t < K && byte_at(s + t) == lpfx[t]) t++;
+            if (t < K) continue;
+            for (uint32_t e = 0; e <= E; e++) {
+                const uint32_t h = search_hash(load8(s + K + e), B, M);
+                if ((h >> kStabSliceBits) == slice) {
+                    const uint32_t x = h & ((1u << kStabSliceBits) - 1);
+                    atomicOr(&bits[x >> 5], 1u << (x & 31));
+                }
+            }
+        }
+    }
+    __syncthreads();
+    uint32_t* out = a.tabs + (size_t(b) << (B - 5)) + (size_t(slice) << (kStabSliceBits - 5));
+    if (a.parts == 1) {
+        for (uint32_t i = tid; i < words; i += kStabThreads) out[i] = bits[i];
+    } else {
+        for (uint32_t i = tid; i < words; i += kStabThreads) {
+            const uint32_t w = bits[i];
+            if (w) atomicOr(&out[i], w);
+        }
+    }
+}
+
 // info[b] = (table bytes or 0, R); the table of 2^(B - R) bits is left at the front of its slot
 __global__ __launch_bounds__(kStabThreads) void stab_reduce_kernel(uint32_t* __restrict__ tabs, uint32_t B, uint32_t fold_limit /* per cent */, uint2* __restrict__ info) {
     __shared__ uint32_t wsum[kStabThreads / 64];
@@ -160,9 +253,10 @@ namespace {
 
 // The tables of the cnt blocks of a range (len bytes at d_src), built and reduced on sm: c->d_stab then holds cnt slots of 2^(B - 3) bytes, each
 // with its block's table at the front, and behind them (at *info_off) cnt records (table bytes or 0, R).  tail: the tail_n <= 8 bytes that
-// follow the range in the stream (the next range's first ones).  T, field: the table type and its prefix field.  Caller holds c->mu.
+// follow the range in the stream (the next range's first ones); table type 4: long_tail, tail_n <= K - 1 + M + E bytes.  T, field: the table
+// type and its prefix field.  Caller holds c->mu.
 int search_tables_build(mlz_ctx* c, hipStream_t sm, const uint8_t* d_src, size_t len, uint32_t bs, size_t cnt, uint32_t T, const uint8_t* field, uint32_t M, uint32_t B,
-                        uint64_t tail, uint32_t tail_n, size_t* info_off) {
+                        uint64_t tail, uint32_t tail_n, size_t* info_off, const uint8_t* long_tail = nullptr) {
     const size_t slot = size_t(1) << (B - 3);
     *info_off = cnt * slot;
     HIPCHK(c, c->d_stab.ensure(cnt * slot + cnt * sizeof(uint2) + 64));
@@ -170,6 +264,8 @@ int search_tables_build(mlz_ctx* c, hipStream_t sm, const uint8_t* d_src, size_t
     if (!c->stab_attr) {
         HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(mlz::stab_build_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 1u << (mlz::kStabSliceBits - 3)));
         HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(mlz::stab_build_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (1u << (mlz::kStabSliceBits - 3)) + 32));
+        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(mlz::stab_build_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (1u << (mlz::kStabSliceBits - 3)) + mlz::kSearchMaxPrefix + mlz::kStabLongTail));
         c->stab_attr = true;
     }
     mlz::StabArgs a{};
@@ -180,7 +276,14 @@ int search_tables_build(mlz_ctx* c, hipStream_t sm, const uint8_t* d_src, size_t
     a.parts = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(want, bs >> 16)));
     a.tabs = c->d_stab.as<uint32_t>();
     if (a.parts > 1) HIPCHK(c, hipMemsetAsync(a.tabs, 0, cnt * slot, sm));
-    if (T == 1) hipLaunchKernelGGL(mlz::stab_build_kernel<false>, dim3(uint32_t(cnt * a.slices * a.parts)), dim3(mlz::kStabThreads), lds, sm, a);
+    if (T == 4) {
+        mlz::StabLongArgs la{};
+        la.src = d_src; la.len = len; la.tail_n = std::min(tail_n, mlz::kStabLongTail); la.bs = bs; la.cnt = uint32_t(cnt); la.B = B; la.M = M;
+        la.E = mlz::search_long_e(field); la.K = mlz::search_long_k(field); la.parts = a.parts; la.slices = a.slices; la.tabs = a.tabs;
+        std::memcpy(la.pfx, mlz::search_long_prefix(field), la.K);
+        if (la.tail_n) std::memcpy(la.tail, long_tail, la.tail_n);
+        hipLaunchKernelGGL(mlz::stab_build_long_kernel, dim3(uint32_t(cnt * a.slices * a.parts)), dim3(mlz::kStabThreads), lds + mlz::kSearchMaxPrefix + mlz::kStabLongTail, sm, la);
+    } else if (T == 1) hipLaunchKernelGGL(mlz::stab_build_kernel<false>, dim3(uint32_t(cnt * a.slices * a.parts)), dim3(mlz::kStabThreads), lds, sm, a);
     else {
         mlz::search_prefix_mask(T, field, a.mask);
         hipLaunchKernelGGL(mlz::stab_build_kernel<true>, dim3(uint32_t(cnt * a.slices * a.parts)), dim3(mlz::kStabThreads), lds + 32, sm, a);

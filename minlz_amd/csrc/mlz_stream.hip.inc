@@ -130,10 +130,10 @@ int ensure_stream_objects(mlz_ctx* c, size_t n_events, size_t pinned_bytes) {
     return 0;
 }
 
-size_t stream_bound(uint64_t n, uint32_t bs, bool add_index, uint32_t table_type = 0 /* 0: no search tables */) {
+size_t stream_bound(uint64_t n, uint32_t bs, bool add_index, bool with_tables = false, uint32_t field_len = 0 /* of the tables' prefix field */) {
     const uint64_t nblk = (n + bs - 1) / bs;
     // search tables: the info chunk and, per block, a table chunk with the unreduced table; both carry the type's prefix field
-    const uint64_t tables = table_type ? 7 + mlz::search_field_len(table_type) + nblk * mlz::search_chunk_bound(mlz::search_table_bits(bs), table_type) : 0;
+    const uint64_t tables = with_tables ? 7 + field_len + nblk * mlz::search_chunk_bound(mlz::search_table_bits(bs), field_len) : 0;
     return size_t(10 + nblk * (8 + 5) + n + 4 + 10 + (add_index ? SeekIndex::bound(size_t(nblk)) : 0) + tables);
 }
 
@@ -148,8 +148,9 @@ int stream_search_match_len(uint32_t flags) {
 struct StreamTables {
     uint32_t T = 0, M = 0;
     uint8_t field[mlz::kSearchMaxField] = {};
-    uint32_t flen() const { return mlz::search_field_len(T); }
-    uint32_t overlap() const { return T == 1 ? M - 1 : M; }   // bytes of the next block that a block's windows reach
+    uint32_t flen() const { return mlz::search_field_len(T, field); }
+    // bytes behind a block that its prefixes and windows reach
+    uint32_t overlap() const { return T == 1 ? M - 1 : T == 4 ? mlz::search_long_k(field) - 1 + M + mlz::search_long_e(field) : M; }
 };
 // flags and an mlz_search_tables (may be NULL) -> the configuration; false: -MLZ_ERR_ARG
 bool stream_tables_config(uint32_t flags, const mlz_search_tables* cfg, StreamTables* st) {
@@ -167,6 +168,20 @@ bool stream_tables_config(uint32_t flags, const mlz_search_tables* cfg, StreamTa
         if (cfg->n_prefix < 1 || cfg->n_prefix > 8) return false;
         for (uint32_t i = 0; i < 8; i++) st->field[i] = cfg->prefix[i < cfg->n_prefix ? i : cfg->n_prefix - 1u];
     } else if (st->T == 3) std::memcpy(st->field, cfg->prefix, 32);
+    return true;
+}
+
+// An mlz_search_long_prefix -> the configuration of table type 4; false: -MLZ_ERR_ARG
+bool stream_long_prefix_config(uint32_t flags, const mlz_search_long_prefix* cfg, StreamTables* st) {
+    *st = StreamTables{};
+    if (!cfg || (flags & (MLZ_STREAM_SEARCH_TABLES | MLZ_STREAM_SEARCH_MATCH_LEN(15)))) return false;
+    if (cfg->prefix_len < 1 || cfg->prefix_len > mlz::kSearchMaxPrefix || cfg->match_len > 8 || cfg->extras > mlz::kSearchMaxExtras) return false;
+    for (uint8_t r : cfg->reserved) if (r) return false;
+    st->T = 4;
+    st->M = cfg->match_len ? cfg->match_len : mlz::kSearchDefaultMatchLen;
+    if (st->M + cfg->extras > mlz::kSearchMaxGroupWindows) return false;
+    st->field[0] = uint8_t(cfg->prefix_len - 1); st->field[1] = cfg->extras;
+    std::memcpy(st->field + 2, cfg->prefix, cfg->prefix_len);
     return true;
 }
 
@@ -396,24 +411,32 @@ int64_t stream_encode_over(mlz_ctx* const* workers, size_t k, int level, uint32_
 // ---- the device-resident Writer over several devices: sources in each device's HBM, the framed stream gathered GPU to GPU ----
 // Chunk bodies and 8-byte chunk headers into a run of chunks: desc.pad selects the source (0 = the encoder's output, 1 = the raw block, for
 // stored chunks; stream_place3_kernel: 2 = the block's search table); a header is eight literal bytes at a destination offset (a table chunk's: twelve
-// and its prefix field, 20 or 44 with table type 2 or 3).
+// and its prefix field, 20 or 44 with table type 2 or 3; type 4's field of 2 + K bytes is the same in every table chunk and travels once, in
+// the kernel's arguments: TabHdrDesc::b then holds `45 len24 T M B` and `R crc32le`, and the field goes between the two).
 struct HdrDesc { uint64_t dst_off; uint8_t b[8]; };
 __global__ __launch_bounds__(256) void stream_place2_kernel(const uint8_t* __restrict__ d_enc, const uint8_t* __restrict__ d_raw, uint8_t* __restrict__ run,
                                                             const PlaceDesc* __restrict__ descs) {
     const PlaceDesc d = descs[blockIdx.x];
     mlz::wg_copy(run + d.dst_off, (d.pad ? d_raw : d_enc) + d.src_off, d.len, threadIdx.x, 256);
 }
-struct TabHdrDesc { uint64_t dst_off; uint8_t b[12 + mlz::kSearchMaxField]; uint32_t n; };
+struct TabHdrDesc { uint64_t dst_off; uint8_t b[12 + 32]; uint32_t n; };
+struct TabLongField { uint32_t n; uint8_t b[mlz::kSearchMaxField + 2]; };   // n = 0: table types 1 .. 3
 __global__ __launch_bounds__(256) void stream_place3_kernel(const uint8_t* __restrict__ d_enc, const uint8_t* __restrict__ d_raw, const uint8_t* __restrict__ d_tab,
                                                             uint8_t* __restrict__ run, const PlaceDesc* __restrict__ descs) {
     const PlaceDesc d = descs[blockIdx.x];
     mlz::wg_copy(run + d.dst_off, (d.pad == 2 ? d_tab : d.pad ? d_raw : d_enc) + d.src_off, d.len, threadIdx.x, 256);
 }
-__global__ __launch_bounds__(64) void stream_tabhdr_kernel(uint8_t* __restrict__ run, const TabHdrDesc* __restrict__ hd, uint32_t n) {
+__global__ __launch_bounds__(64) void stream_tabhdr_kernel(uint8_t* __restrict__ run, const TabHdrDesc* __restrict__ hd, uint32_t n, const TabLongField lf) {
     const uint32_t i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
     const TabHdrDesc& h = hd[i];
-    for (uint32_t k = 0; k < h.n; k++) run[h.dst_off + k] = h.b[k];
+    if (lf.n == 0) {
+        for (uint32_t k = 0; k < h.n; k++) run[h.dst_off + k] = h.b[k];
+        return;
+    }
+    for (uint32_t k = 0; k < 7; k++) run[h.dst_off + k] = h.b[k];
+    for (uint32_t k = 0; k < lf.n; k++) run[h.dst_off + 7 + k] = lf.b[k];
+    for (uint32_t k = 0; k < 5; k++) run[h.dst_off + 7 + lf.n + k] = h.b[7 + k];
 }
 __global__ __launch_bounds__(64) void stream_hdr_kernel(uint8_t* __restrict__ run, const HdrDesc* __restrict__ hd, uint32_t n) {
     const uint32_t i = blockIdx.x * 64 + threadIdx.x;
@@ -428,7 +451,8 @@ __global__ __launch_bounds__(64) void stream_hdr_kernel(uint8_t* __restrict__ ru
 // place; another one: hipMemcpyPeerAsync, which rides xGMI between the GPUs of a node).  Payload never visits the host.
 int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d_src, size_t len, size_t b0, uint8_t* d_dst, int dst_dev, bool have_header,
                             StreamEncShared* sh, size_t j, uint32_t* framed, const StreamTables& stb = StreamTables{} /* T > 0: search tables */, uint64_t tail = 0,
-                            uint32_t tail_n = 0 /* the bytes that follow the range in the stream, 8 at the most */) {
+                            uint32_t tail_n = 0 /* the bytes that follow the range in the stream, 8 at the most */,
+                            const uint8_t* long_tail = nullptr /* table type 4: the tail_n bytes that follow, K - 1 + M + E at the most */) {
     HIPCHK(c, hipSetDevice(c->device));
     const size_t cnt = (len + bs - 1) / bs;
     if (cnt == 0) { sh->publish(j, 0); return 0; }
@@ -462,7 +486,7 @@ int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d
     if (r) return r;
     size_t tabinfo_off = 0;
     if (search_m) {
-        r = search_tables_build(c, sm, d_src, len, bs, cnt, stb.T, stb.field, search_m, search_b, tail, tail_n, &tabinfo_off);
+        r = search_tables_build(c, sm, d_src, len, bs, cnt, stb.T, stb.field, search_m, search_b, tail, tail_n, &tabinfo_off, long_tail);
         if (r) return r;
         HIPCHK(c, hipMemcpyAsync(h_tabinfo, c->d_stab.as<uint8_t>() + tabinfo_off, sizeof(uint2) * cnt, hipMemcpyDeviceToHost, sm));
     }
@@ -503,9 +527,10 @@ int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d
             th.dst_off = run; th.n = thdr;
             th.b[0] = mlz::kChunkSearchTable; th.b[1] = uint8_t(tlen); th.b[2] = uint8_t(tlen >> 8); th.b[3] = uint8_t(tlen >> 16);
             th.b[4] = uint8_t(stb.T); th.b[5] = uint8_t(search_m); th.b[6] = uint8_t(search_b);
-            std::memcpy(th.b + 7, stb.field, flen);
-            th.b[7 + flen] = uint8_t(h_tabinfo[i].y);
-            std::memcpy(th.b + 8 + flen, &h_tabcrc[tab_at], 4);
+            const uint32_t inl = stb.T == 4 ? 0 : flen;   // the field's bytes inside the record
+            std::memcpy(th.b + 7, stb.field, inl);
+            th.b[7 + inl] = uint8_t(h_tabinfo[i].y);
+            std::memcpy(th.b + 8 + inl, &h_tabcrc[tab_at], 4);
             for (size_t q = 0; q < tb; q += kPlacePiece)
                 h_place[n_place++] = PlaceDesc{i * tab_slot + q, run + thdr + q, uint32_t(std::min<size_t>(kPlacePiece, tb - q)), 2u};
             tab_at++;
@@ -540,7 +565,9 @@ int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d
         TabHdrDesc* d_tabhdr = reinterpret_cast<TabHdrDesc*>(d_hdr + cnt);
         if (n_tabs) HIPCHK(c, hipMemcpyAsync(d_tabhdr, h_tabhdr, n_tabs * sizeof(TabHdrDesc), hipMemcpyHostToDevice, sm));
         if (n_place) hipLaunchKernelGGL(stream_place3_kernel, dim3(uint32_t(n_place)), dim3(256), 0, sm, d_out, d_src, c->d_stab.as<uint8_t>(), d_run, d_place);
-        if (n_tabs) hipLaunchKernelGGL(stream_tabhdr_kernel, dim3(uint32_t((n_tabs + 63) / 64)), dim3(64), 0, sm, d_run, d_tabhdr, uint32_t(n_tabs));
+        TabLongField lf{};
+        if (stb.T == 4) { lf.n = flen; std::memcpy(lf.b, stb.field, flen); }
+        if (n_tabs) hipLaunchKernelGGL(stream_tabhdr_kernel, dim3(uint32_t((n_tabs + 63) / 64)), dim3(64), 0, sm, d_run, d_tabhdr, uint32_t(n_tabs), lf);
     } else if (n_place) hipLaunchKernelGGL(stream_place2_kernel, dim3(uint32_t(n_place)), dim3(256), 0, sm, d_out, d_src, d_run, d_place);
     hipLaunchKernelGGL(stream_hdr_kernel, dim3(uint32_t((cnt + 63) / 64)), dim3(64), 0, sm, d_run, d_hdr, uint32_t(cnt));
     if (!local) HIPCHK(c, hipMemcpyPeerAsync(d_dst + base, dst_dev, d_run, c->device, run, sm));
@@ -817,7 +844,14 @@ int64_t mlz_stream_bound_tables(uint64_t n, uint32_t block_size, uint32_t flags,
     if (block_size < kMinStreamBlock || block_size > kMaxBlockSize) return -MLZ_ERR_ARG;
     StreamTables stb;
     if (!stream_tables_config(flags, cfg, &stb)) return -MLZ_ERR_ARG;
-    return int64_t(stream_bound(n, block_size, (flags & MLZ_STREAM_ADD_INDEX) != 0, stb.T));
+    return int64_t(stream_bound(n, block_size, (flags & MLZ_STREAM_ADD_INDEX) != 0, stb.T != 0, stb.flen()));
+}
+
+int64_t mlz_stream_bound_long_prefix(uint64_t n, uint32_t block_size, uint32_t flags, const mlz_search_long_prefix* cfg) {
+    if (block_size < kMinStreamBlock || block_size > kMaxBlockSize) return -MLZ_ERR_ARG;
+    StreamTables stb;
+    if (!stream_long_prefix_config(flags, cfg, &stb)) return -MLZ_ERR_ARG;
+    return int64_t(stream_bound(n, block_size, (flags & MLZ_STREAM_ADD_INDEX) != 0, true, stb.flen()));
 }
 
 int64_t mlz_stream_encode(mlz_ctx* c, int level, uint32_t block_size, uint32_t flags, const uint8_t* src, size_t n, uint8_t* dst, size_t dst_cap) {
@@ -834,14 +868,43 @@ int64_t mlz_stream_encode_gather_device(mlz_ctx* c, int level, uint32_t block_si
     return mlz_stream_encode_gather_device_tables(c, level, block_size, flags, nullptr, d_src, src_len, n_ranges, d_dst, dst_cap);
 }
 
+}  // extern "C"
+
+namespace {
+int64_t stream_encode_gather_device_with(mlz_ctx* c, int level, uint32_t block_size, uint32_t flags, const StreamTables& stb, const uint8_t* const* d_src,
+                                         const size_t* src_len, int n_ranges, uint8_t* d_dst, size_t dst_cap);
+}
+
+extern "C" {
+
 int64_t mlz_stream_encode_gather_device_tables(mlz_ctx* c, int level, uint32_t block_size, uint32_t flags, const mlz_search_tables* cfg, const uint8_t* const* d_src,
                                                const size_t* src_len, int n_ranges, uint8_t* d_dst, size_t dst_cap) {
     if (!c || !d_src || !src_len || n_ranges <= 0 || !d_dst) return -MLZ_ERR_ARG;
     if (block_size < kMinStreamBlock || block_size > kMaxBlockSize) return -MLZ_ERR_ARG;
     if (!valid_level(level)) return -MLZ_ERR_INVALID_LEVEL;
-    const bool add_index = (flags & MLZ_STREAM_ADD_INDEX) != 0;
     StreamTables stb;
     if (!stream_tables_config(flags, cfg, &stb)) return -MLZ_ERR_ARG;
+    return stream_encode_gather_device_with(c, level, block_size, flags, stb, d_src, src_len, n_ranges, d_dst, dst_cap);
+}
+
+int64_t mlz_stream_encode_gather_device_long_prefix(mlz_ctx* c, int level, uint32_t block_size, uint32_t flags, const mlz_search_long_prefix* cfg,
+                                                    const uint8_t* const* d_src, const size_t* src_len, int n_ranges, uint8_t* d_dst, size_t dst_cap) {
+    if (!c || !d_src || !src_len || n_ranges <= 0 || !d_dst) return -MLZ_ERR_ARG;
+    if (block_size < kMinStreamBlock || block_size > kMaxBlockSize) return -MLZ_ERR_ARG;
+    if (!valid_level(level)) return -MLZ_ERR_INVALID_LEVEL;
+    StreamTables stb;
+    if (!stream_long_prefix_config(flags, cfg, &stb)) return -MLZ_ERR_ARG;
+    return stream_encode_gather_device_with(c, level, block_size, flags, stb, d_src, src_len, n_ranges, d_dst, dst_cap);
+}
+
+}  // extern "C"
+
+namespace {
+
+// The device-resident Writer behind mlz_stream_encode_gather_device, _tables and _long_prefix: arguments checked, stb the tables' configuration
+int64_t stream_encode_gather_device_with(mlz_ctx* c, int level, uint32_t block_size, uint32_t flags, const StreamTables& stb, const uint8_t* const* d_src,
+                                         const size_t* src_len, int n_ranges, uint8_t* d_dst, size_t dst_cap) {
+    const bool add_index = (flags & MLZ_STREAM_ADD_INDEX) != 0;
     Workers w(c);
     const size_t k = size_t(n_ranges);
     // every range on the device that holds it; all but the last are whole blocks (a short block ends a stream)
@@ -867,11 +930,25 @@ int64_t mlz_stream_encode_gather_device_tables(mlz_ctx* c, int level, uint32_t b
     hipPointerAttribute_t dat;
     if (hipPointerGetAttributes(&dat, d_dst) != hipSuccess || dat.type != hipMemoryTypeDevice) { (void)hipGetLastError(); return -MLZ_ERR_ARG; }
     const int dst_dev = dat.device;
-    if (dst_cap < stream_bound(n, block_size, add_index, stb.T)) return -MLZ_ERR_DST_TOO_SMALL;
+    if (dst_cap < stream_bound(n, block_size, add_index, stb.T != 0, stb.flen())) return -MLZ_ERR_DST_TOO_SMALL;
     // search tables: a range's last block indexes windows that run into the next non-empty range, whose first bytes (M - 1, with a prefix table M: 8 at the most) the host hands over
     std::vector<uint64_t> next_bytes(k, 0);
     std::vector<uint32_t> next_n(k, 0);
-    if (stb.T && stb.overlap())
+    // table type 4: up to K - 1 + M + E bytes, gathered across as many following ranges as it takes
+    const uint32_t long_need = stb.T == 4 ? stb.overlap() : 0;
+    std::vector<uint8_t> long_tail(long_need ? k * size_t(long_need) : 0, 0);
+    if (long_need)
+        for (size_t j = 0; j + 1 < k; j++) {
+            if (!src_len[j]) continue;
+            for (size_t q = j + 1; q < k && next_n[j] < long_need; q++) {
+                const size_t take = std::min<size_t>(long_need - next_n[j], src_len[q]);
+                if (!take) continue;
+                if (hipSetDevice(own[q]->device) != hipSuccess ||
+                    hipMemcpy(long_tail.data() + j * size_t(long_need) + next_n[j], d_src[q], take, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
+                next_n[j] += uint32_t(take);
+            }
+        }
+    else if (stb.T && stb.overlap())
         for (size_t j = 0; j + 1 < k; j++) {
             size_t q = j + 1;
             while (q < k && !src_len[q]) q++;
@@ -898,7 +975,8 @@ int64_t mlz_stream_encode_gather_device_tables(mlz_ctx* c, int level, uint32_t b
         mlz_ctx* kc = ctxs[q];
         std::lock_guard<std::mutex> lk(kc->mu);
         for (size_t j : by_ctx[q]) {
-            rcs[j] = stream_gather_range(kc, level, block_size, d_src[j], src_len[j], first[j], d_dst, dst_dev, n > 0, &sh, j, framed.data(), stb, next_bytes[j], next_n[j]);
+            rcs[j] = stream_gather_range(kc, level, block_size, d_src[j], src_len[j], first[j], d_dst, dst_dev, n > 0, &sh, j, framed.data(), stb, next_bytes[j], next_n[j],
+                                         long_need ? long_tail.data() + j * size_t(long_need) : nullptr);
             if (rcs[j]) { sh.fail(); (void)hipStreamSynchronize(kc->stream); }
         }
     };
@@ -923,7 +1001,8 @@ int64_t mlz_stream_encode_gather_device_tables(mlz_ctx* c, int level, uint32_t b
         head[9] = uint8_t((32 - __builtin_clz(block_size - 1)) - 10);
         o = 10;
         if (stb.T) {   // the info chunk: 44 len24 | T M B | prefix field
-            const uint8_t info[7] = {mlz::kChunkSearchInfo, uint8_t(3 + stb.flen()), 0, 0, uint8_t(stb.T), uint8_t(stb.M), uint8_t(mlz::search_table_bits(block_size))};
+            const uint32_t ilen = 3 + stb.flen();
+            const uint8_t info[7] = {mlz::kChunkSearchInfo, uint8_t(ilen), uint8_t(ilen >> 8), 0, uint8_t(stb.T), uint8_t(stb.M), uint8_t(mlz::search_table_bits(block_size))};
             std::memcpy(head + 10, info, 7);
             std::memcpy(head + 17, stb.field, stb.flen());
             o = 17 + stb.flen();
@@ -940,6 +1019,10 @@ int64_t mlz_stream_encode_gather_device_tables(mlz_ctx* c, int level, uint32_t b
     HIPCHK(c0, hipMemcpy(d_dst + o, tail.data(), t, hipMemcpyHostToDevice));
     return int64_t(o + t);
 }
+
+}  // namespace
+
+extern "C" {
 
 int64_t mlz_stream_decoded_len(const uint8_t* src, size_t n) {
     if (!src && n) return -MLZ_ERR_ARG;

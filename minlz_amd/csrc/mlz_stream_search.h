@@ -1,8 +1,8 @@
 // mlz_stream_search.h — what the block search tables' writer, the device-resident pattern search (mlz_stream_search.hip.inc) and their host
 // check (tools/stream_search_check.cpp) share: the table hash (SPEC_SEARCH.md 3.1), the size and the bytes of a table chunk (2.0, 2.1, 3.2),
 // the probe of one table and the rule that turns the probes of all chunks into the set of chunks to decode (Appendix B.4.1).
-// Plain C++: compiles for the host alone and for gfx950.  Table types 1 (no prefix), 2 (1 to 8 prefix byte values) and 3 (a 256-bit mask of
-// prefix byte values; SPEC_SEARCH.md 3.3), uncompressed table chunks (0x45) only.
+// Plain C++: compiles for the host alone and for gfx950.  Table types 1 (no prefix), 2 (1 to 8 prefix byte values), 3 (a 256-bit mask of
+// prefix byte values; SPEC_SEARCH.md 3.3) and 4 (a long prefix of 1 to 256 bytes with extra matches; 3.3.4), uncompressed table chunks (0x45) only.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -48,9 +48,17 @@ MLZ_SEARCH_HD uint32_t search_table_bits(uint32_t block_size) {
 }
 
 // The prefix field that follows `T M B` in the info chunk and in every table chunk: none for type 1, the 8 values of type 2 (unused places
-// repeat the last value), the 32 bytes of type 3's mask (value v is a prefix byte when field[v >> 3] >> (v & 7) & 1).
-constexpr uint32_t kSearchMaxField = 32;
-MLZ_SEARCH_HD uint32_t search_field_len(uint32_t T) { return T == 2 ? 8 : T == 3 ? 32 : 0; }
+// repeat the last value), the 32 bytes of type 3's mask (value v is a prefix byte when field[v >> 3] >> (v & 7) & 1), type 4's `K-1 | E | pfx`
+// (2 + K bytes: the prefix of K = 1 .. 256 bytes and the extras E = 0 .. 15, M + E <= 16).  The length of a type 4 field stands in its first
+// byte, so search_field_len reads the field (which may be NULL for the other types).
+constexpr uint32_t kSearchMaxField = 258, kSearchMaxPrefix = 256, kSearchMaxExtras = 15, kSearchMaxGroupWindows = 16;
+// The most window starts search_windows writes: L of type 1 .. 3, 255 groups of 16 windows of type 4
+constexpr uint32_t kSearchMaxWindows = 255 * kSearchMaxGroupWindows;
+MLZ_SEARCH_HD uint32_t search_field_len(uint32_t T, const uint8_t* field) { return T == 2 ? 8 : T == 3 ? 32 : T == 4 ? 3u + field[0] : 0; }
+// Type 4: the prefix's bytes, their number K and the extras E of a field
+MLZ_SEARCH_HD uint32_t search_long_k(const uint8_t* field) { return 1u + field[0]; }
+MLZ_SEARCH_HD uint32_t search_long_e(const uint8_t* field) { return field[1]; }
+MLZ_SEARCH_HD const uint8_t* search_long_prefix(const uint8_t* field) { return field + 2; }
 // mask[v >> 5] >> (v & 31) & 1: v is a prefix byte of (T, field).  Type 1 has no prefix bytes.
 MLZ_SEARCH_HD void search_prefix_mask(uint32_t T, const uint8_t* field, uint32_t mask[8]) {
     for (uint32_t i = 0; i < 8; i++) mask[i] = 0;
@@ -60,12 +68,12 @@ MLZ_SEARCH_HD void search_prefix_mask(uint32_t T, const uint8_t* field, uint32_t
 MLZ_SEARCH_HD bool search_is_prefix(const uint32_t mask[8], uint8_t v) { return (mask[v >> 5] >> (v & 31)) & 1; }
 
 // Bytes a table chunk takes at the most: 4 (chunk header) + 8 (type, M, B, R, CRC) + the prefix field + the unreduced table.
-MLZ_SEARCH_HD uint64_t search_chunk_bound(uint32_t B, uint32_t T = 1) { return 12 + search_field_len(T) + (uint64_t(1) << (B - 3)); }
+MLZ_SEARCH_HD uint64_t search_chunk_bound(uint32_t B, uint32_t field_len = 0) { return 12 + field_len + (uint64_t(1) << (B - 3)); }
 
 // The payload of a 0x45 chunk (`clen` bytes at p, all readable): the reductions R of a table of the stream's (T, M, B, field) whose length
-// fits, else -1.  With f = search_field_len(T): the CRC is the little-endian word at p + 4 + f, the table's bytes are p[8 + f .. clen).
+// fits, else -1 (a type 4 table whose prefix or extras differ from the stream's included).  With f = search_field_len(T, field): the CRC is the little-endian word at p + 4 + f, the table's bytes are p[8 + f .. clen).
 MLZ_SEARCH_HD int search_table_reductions(const uint8_t* p, uint32_t clen, uint32_t M, uint32_t B, uint32_t T = 1, const uint8_t* field = nullptr) {
-    const uint32_t f = search_field_len(T);
+    const uint32_t f = search_field_len(T, field);
     if (clen < 8 + f + 32 || p[0] != T || p[1] != M || p[2] != B) return -1;
     for (uint32_t i = 0; i < f; i++) if (p[3 + i] != field[i]) return -1;
     const uint32_t R = p[3 + f];
@@ -74,24 +82,45 @@ MLZ_SEARCH_HD int search_table_reductions(const uint8_t* p, uint32_t clen, uint3
 }
 
 // The payload of a 0x44 chunk: (T, M, B) and the prefix field (kSearchMaxField bytes of room, zeros behind the field) of a stream of type
-// 1, 2 or 3, else false (type 4 and a payload shorter than the field included).
+// 1 .. 4, else false (a payload shorter than the field and a type 4 field with more than 15 extras or M + E > 16 included).
 MLZ_SEARCH_HD bool search_info(const uint8_t* p, uint32_t clen, uint32_t* T, uint32_t* M, uint32_t* B, uint8_t* field) {
-    if (clen < 3 || p[0] < 1 || p[0] > 3 || p[1] < 1 || p[1] > 8 || p[2] < 8 || p[2] > 23) return false;
-    const uint32_t f = search_field_len(p[0]);
+    if (clen < 3 || p[0] < 1 || p[0] > 4 || p[1] < 1 || p[1] > 8 || p[2] < 8 || p[2] > 23) return false;
+    if (p[0] == 4 && (clen < 5 || p[4] > kSearchMaxExtras || p[1] + p[4] > kSearchMaxGroupWindows)) return false;
+    const uint32_t f = search_field_len(p[0], p + 3);
     if (clen < 3 + f) return false;
     *T = p[0]; *M = p[1]; *B = p[2];
     for (uint32_t i = 0; i < kSearchMaxField; i++) field[i] = i < f ? p[3 + i] : 0;
     return true;
 }
 
-// The pattern's windows that the tables can answer for (w[i] = where window i starts in the pattern, ascending; room for L values) and
-// t_min.  Type 1: every window 0 .. L - M, t_min = 1.  Types 2 and 3: the windows 1 <= i <= L - M behind a prefix byte P[i - 1]; t_min = 1
-// when P[0] is a prefix byte, else 0.  Returns their number; 0 = the tables cannot serve this pattern.
-MLZ_SEARCH_HD uint32_t search_windows(const uint8_t* pat, uint32_t L, uint32_t T, uint32_t M, const uint8_t* field, uint32_t* w, uint32_t* t_min) {
+// The pattern's windows that the tables can answer for, in groups of *gsize windows that one block's table holds together, and t_min.
+// w[g * gsize + j] = where window j of group g starts in the pattern, groups ascending; room for kSearchMaxWindows values (L for types
+// 1 .. 3).  Returns the number of groups; 0 = the tables cannot serve this pattern.
+// Type 1: every window 0 .. L - M is a group of one, t_min = 1.  Types 2 and 3: the windows 1 <= i <= L - M behind a prefix byte P[i - 1],
+// groups of one; t_min = 1 when P[0] is a prefix byte, else 0.  Type 4: a group per prefix occurrence P[i, i + K) == pfx with
+// i + K + M + E <= L, its E + 1 windows start at i + K + j; t_min = 1 when the first group has i = 0, else 0.
+MLZ_SEARCH_HD uint32_t search_windows(const uint8_t* pat, uint32_t L, uint32_t T, uint32_t M, const uint8_t* field, uint32_t* w, uint32_t* t_min,
+                                      uint32_t* gsize = nullptr) {
     *t_min = 1;
+    if (gsize) *gsize = 1;
     if (L < M) return 0;
     uint32_t nw = 0;
     if (T == 1) { for (uint32_t i = 0; i + M <= L; i++) w[nw++] = i; return nw; }
+    if (T == 4) {
+        const uint32_t K = search_long_k(field), E = search_long_e(field), gs = E + 1;
+        const uint8_t* pfx = search_long_prefix(field);
+        if (gsize) *gsize = gs;
+        *t_min = 0;
+        for (uint32_t i = 0; i + K + M + E <= L; i++) {
+            uint32_t j = 0;
+            while (j < K && pat[i + j] == pfx[j]) j++;
+            if (j < K) continue;
+            if (nw == 0 && i == 0) *t_min = 1;
+            for (j = 0; j < gs; j++) w[nw * gs + j] = i + K + j;
+            nw++;
+        }
+        return nw;
+    }
     uint32_t mask[8];
     search_prefix_mask(T, field, mask);
     *t_min = search_is_prefix(mask, pat[0]) ? 1 : 0;
@@ -99,11 +128,17 @@ MLZ_SEARCH_HD uint32_t search_windows(const uint8_t* pat, uint32_t L, uint32_t T
     return nw;
 }
 
-// One table against the pattern's windows (h[i] = the hash of window i at B bits; bits = B - R of this table): a = the leading windows
-// present, s = the trailing ones.  Both are nw when all are present.
-MLZ_SEARCH_HD void search_probe(const uint8_t* table, uint32_t bits, const uint32_t* h, uint32_t nw, uint32_t* a, uint32_t* s) {
+// One table against the pattern's nw groups of gsize windows (h[g * gsize + j] = the hash of window j of group g at B bits; bits = B - R of
+// this table): a = the leading groups whose windows are all present, s = the trailing ones.  Both are nw when all are present.
+MLZ_SEARCH_HD void search_probe(const uint8_t* table, uint32_t bits, const uint32_t* h, uint32_t nw, uint32_t* a, uint32_t* s, uint32_t gsize = 1) {
     const uint32_t mask = (1u << bits) - 1;
-    auto has = [&](uint32_t i) { const uint32_t x = h[i] & mask; return (table[x >> 3] >> (x & 7)) & 1; };
+    auto has = [&](uint32_t g) {
+        for (uint32_t j = 0; j < gsize; j++) {
+            const uint32_t x = h[g * gsize + j] & mask;
+            if (!((table[x >> 3] >> (x & 7)) & 1)) return false;
+        }
+        return true;
+    };
     uint32_t lead = 0, trail = 0;
     while (lead < nw && has(lead)) lead++;
     if (lead == nw) { *a = *s = nw; return; }
@@ -115,7 +150,9 @@ MLZ_SEARCH_HD void search_probe(const uint8_t* table, uint32_t bits, const uint3
 // tail windows included) and the next chunk's (the last nw - j).  s_next = nw when the next chunk has no usable table or decodes to fewer
 // bytes than the pattern has.  t_min: the fewest windows an occurrence that starts in chunk k leaves in k's table — 1 for type 1 (window 0
 // starts with the occurrence) and for a prefix table whose pattern starts with a prefix byte, else 0 (a window is indexed in the block that
-// holds the byte in front of it, so a short head of the occurrence may leave none).
+// holds the byte in front of it, so a short head of the occurrence may leave none).  Type 4 counts groups, not windows: a group lies in the
+// table of the block in which its prefix starts, all its windows together, so an occurrence splits between two tables at a group border only;
+// t_min = 1 when the pattern starts with the prefix.
 MLZ_SEARCH_HD bool search_candidate(uint32_t a_k, uint32_t s_next, uint32_t nw, bool last, uint32_t t_min = 1) {
     if (a_k == nw) return true;
     if (last) return false;

@@ -2,8 +2,9 @@
 // mlz_hip.hip, behind the device-resident ReadSeeker whose handle, chunk-list decode and scratch it uses).
 //
 // The stream's block search tables (SPEC_SEARCH.md: an info chunk 0x44 behind the identifier, a bit table 0x45 in front of a block; table
-// types 1, 2 and 3) say which blocks can hold the pattern's windows of M bytes — with a prefix table (types 2 and 3) the windows behind one
-// of the stream's prefix bytes, which are the only ones its blocks index.  Per handle, once: search_info_kernel reads the info chunk, search_locate_kernel
+// types 1 to 4) say which blocks can hold the pattern's windows of M bytes — with a prefix table (types 2 and 3) the windows behind one
+// of the stream's prefix bytes, which are the only ones its blocks index; with a long-prefix table (type 4) the groups of E + 1 windows behind
+// an occurrence of the stream's prefix in the pattern, probed group by group.  Per handle, once: search_info_kernel reads the info chunk, search_locate_kernel
 // (one lane per data chunk) hops over the chunk headers between the previous data chunk's end and its own start to the first table chunk
 // that fits, and the existing CRC pass checks the tables.  Per call: search_probe_kernel looks the pattern's windows up in every table
 // (8 bytes per chunk come back), the rule of mlz_stream_search.h turns that into the set of chunks to decode, stream_run_chunk_jobs decodes
@@ -13,7 +14,7 @@
 
 namespace mlz {
 
-struct SearchInfo { uint32_t M, B, ok, T; uint8_t field[kSearchMaxField]; };
+struct SearchInfo { uint32_t M, B, ok, T; uint8_t field[kSearchMaxField + 2]; };
 struct SearchHop { uint64_t from, limit; };                               // where a lane starts to hop and the data chunk's body, which it never reaches
 
 __device__ __forceinline__ bool search_is_data(uint8_t t) { return t >= 1 && t <= 3; }
@@ -21,7 +22,8 @@ __device__ __forceinline__ bool search_is_data(uint8_t t) { return t >= 1 && t <
 __global__ __launch_bounds__(64) void search_info_kernel(const uint8_t* __restrict__ src, uint64_t limit /* the first data chunk's body, or the stream's end */,
                                                          SearchInfo* __restrict__ out) {
     if (blockIdx.x || threadIdx.x) return;
-    SearchInfo r{};
+    out->M = out->B = out->ok = out->T = 0;   // (filled in place: the field is too large for registers)
+    for (uint32_t i = 0; i < sizeof(out->field); i++) out->field[i] = 0;
     bool seen_id = false;
     for (uint64_t p = 0; p + 4 <= limit;) {
         uint8_t type;
@@ -29,12 +31,11 @@ __global__ __launch_bounds__(64) void search_info_kernel(const uint8_t* __restri
         if (search_is_data(type)) break;
         if (type == 0xff) seen_id = true;
         else if (type == kChunkSearchInfo && seen_id) {
-            if (p + 4 + clen <= limit) r.ok = search_info(src + p + 4, clen, &r.T, &r.M, &r.B, r.field) ? 1 : 0;
+            if (p + 4 + clen <= limit) out->ok = search_info(src + p + 4, clen, &out->T, &out->M, &out->B, out->field) ? 1 : 0;
             break;
         }
         p += 4 + uint64_t(clen);
     }
-    *out = r;
 }
 
 // skip[k]: fitting tables in front of chunk k that an earlier round found broken (CRC) and that are passed over
@@ -43,7 +44,7 @@ __global__ __launch_bounds__(64) void search_locate_kernel(const uint8_t* __rest
     const uint32_t k = blockIdx.x * 64 + threadIdx.x;
     if (k >= nck) return;
     SearchTab t{0, 0, kSearchNoTable, 0, 0};
-    const SearchInfo in = *info;
+    struct { uint32_t M, B, ok, T; const uint8_t* field; } in{info->M, info->B, info->ok, info->T, info->field};
     if (in.ok) {
         const uint64_t limit = hop[k].limit;
         uint32_t left = skip[k];
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(64) void search_locate_kernel(const uint8_t* __rest
             if (type == kChunkSearchTable && p + 4 + clen <= limit) {
                 const int R = search_table_reductions(src + p + 4, clen, in.M, in.B, in.T, in.field);
                 if (R >= 0 && left-- == 0) {
-                    const uint32_t f = search_field_len(in.T);
+                    const uint32_t f = search_field_len(in.T, in.field);
                     const uint8_t* q = src + p + 8 + f;
                     t = SearchTab{p + 12 + f, clen - 8 - f, uint32_t(R), uint32_t(q[0]) | uint32_t(q[1]) << 8 | uint32_t(q[2]) << 16 | uint32_t(q[3]) << 24, 0};
                     break;
@@ -67,12 +68,12 @@ __global__ __launch_bounds__(64) void search_locate_kernel(const uint8_t* __rest
 }
 
 __global__ __launch_bounds__(64) void search_probe_kernel(const uint8_t* __restrict__ src, const SearchTab* __restrict__ tabs, uint32_t nck, uint32_t B,
-                                                          const uint32_t* __restrict__ hashes, uint32_t nw, uint2* __restrict__ out) {
+                                                          const uint32_t* __restrict__ hashes, uint32_t nw, uint32_t gsize, uint2* __restrict__ out) {
     const uint32_t k = blockIdx.x * 64 + threadIdx.x;
     if (k >= nck) return;
     const SearchTab t = tabs[k];
     uint32_t a = nw, s = nw;
-    if (t.R != kSearchNoTable) search_probe(src + t.off, B - t.R, hashes, nw, &a, &s);
+    if (t.R != kSearchNoTable) search_probe(src + t.off, B - t.R, hashes, nw, &a, &s, gsize);
     out[k] = make_uint2(a, s);
 }
 
@@ -211,19 +212,22 @@ int64_t dev_reader_search_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t fl
         if (r) return r;
         const mlz_dev_reader::SearchTables& st = rd->search[ignore_crc ? 1 : 0];
         // the windows the tables answer for: all of them (type 1), or those behind a prefix byte; none: the tables cannot serve this pattern
-        uint32_t win[mlz::kSearchMaxPattern], t_min = 1;
-        const uint32_t nw = st.info && st.usable ? mlz::search_windows(pattern, L, st.T, st.M, st.field, win, &t_min) : 0;
+        // (type 4: the groups of windows behind the prefix's occurrences in the pattern; nw counts groups of gsize windows)
+        std::vector<uint32_t> win(st.T == 4 ? mlz::kSearchMaxWindows : mlz::kSearchMaxPattern);
+        uint32_t t_min = 1, gsize = 1;
+        const uint32_t nw = st.info && st.usable ? mlz::search_windows(pattern, L, st.T, st.M, st.field, win.data(), &t_min, &gsize) : 0;
         with_tables = nw != 0;
         if (with_tables) {
             // the windows' hashes go up, two counts per chunk come back
-            std::vector<uint32_t> hs(nw);
-            for (uint32_t i = 0; i < nw; i++) {
+            const uint32_t nh = nw * gsize;
+            std::vector<uint32_t> hs(nh);
+            for (uint32_t i = 0; i < nh; i++) {
                 uint64_t v = 0;
                 for (uint32_t j = 0; j < st.M; j++) v |= uint64_t(pattern[win[i] + j]) << (8 * j);
                 hs[i] = mlz::search_hash(v, st.B, st.M);
             }
             Carve cv;
-            const auto r_hs = cv.take<uint32_t>(nw);
+            const auto r_hs = cv.take<uint32_t>(nh);
             const auto r_out = cv.take<uint2>(nck);
             HIPCHK(c, c->d_rplan.ensure(cv.bytes));
             int e = ensure_stream_objects(c, 0, nck * 8);
@@ -231,9 +235,9 @@ int64_t dev_reader_search_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t fl
             uint32_t* d_hs = r_hs.at(c->d_rplan.p);
             uint2* d_out = r_out.at(c->d_rplan.p);
             { WorkspaceOrder order(c, sm); }
-            HIPCHK(c, hipMemcpyAsync(d_hs, hs.data(), size_t(nw) * 4, hipMemcpyHostToDevice, sm));
+            HIPCHK(c, hipMemcpyAsync(d_hs, hs.data(), size_t(nh) * 4, hipMemcpyHostToDevice, sm));
             hipLaunchKernelGGL(mlz::search_probe_kernel, dim3(uint32_t((nck + 63) / 64)), dim3(64), 0, sm, rd->d_src, static_cast<const mlz::SearchTab*>(st.d_tabs), uint32_t(nck), st.B,
-                               d_hs, nw, d_out);
+                               d_hs, nw, gsize, d_out);
             if ((e = fetch(c, sm, c->pinned2, d_out, nck * 8))) return e;
             const uint32_t* as = static_cast<const uint32_t*>(c->pinned2);
             n_take = mlz::search_decoded_set(nck, [&](size_t k) { return as[2 * k]; }, [&](size_t k) { return as[2 * k + 1]; },

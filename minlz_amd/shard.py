@@ -226,7 +226,7 @@ class DeviceStream:
 
     def search(self, pattern, max_results, ignore_crc=False, no_tables=False):
         """Where `pattern` (1 .. 256 bytes) occurs in the decoded stream -> (the smallest min(total, max_results) positions, ascending: an
-        int64 tensor on the stream's device; the total).  Only the blocks whose search tables (types 1, 2 and 3) admit the pattern are decoded."""
+        int64 tensor on the stream's device; the total).  Only the blocks whose search tables (types 1 to 4) admit the pattern are decoded."""
         dev = self.t.device
         out = torch.empty(max(max_results, 1), dtype=torch.int64, device=dev)
         st = torch.cuda.current_stream(dev).cuda_stream

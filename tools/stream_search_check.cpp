@@ -17,6 +17,10 @@
 //   kind 7  u32 nck, nw, L, t_min; nck x u32 a; nck x u32 s; nck x u64 n       -> the decoded set (search_decoded_set with t_min)
 //   kind 8  u32 B, limit; (B - 8 + 1) x u32 pop                                -> table bytes and R (search_reduce_rule with the fold limit in per cent)
 //   kind 9  u32 T, M, L; 32 bytes of prefix field; pattern                     -> "t_min :" and the starts of the checkable windows (search_windows)
+// The long-prefix tables' rules (table type 4), for tests/test_stream_search_long_prefix_host.py:
+//   kind 10 as kind 3, over a stream of any table type 1 .. 4                  -> "T M B usable ng t_min gsize :" and the decoded set (ng = the pattern's
+//           groups of gsize windows; usable, ng = 0: the tables were not used)
+//   kind 11 u32 M, L, field bytes; the field (K-1 | E | pfx); pattern          -> "t_min gsize :" and the start of every group's first window
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -49,7 +53,7 @@ void print_set(const std::vector<uint8_t>& take) {
     std::printf("\n");
 }
 
-void run_stream(const uint8_t* s, uint64_t slen, const uint8_t* pat, uint32_t L, uint32_t flags, bool prefix_kind = false) {
+void run_stream(const uint8_t* s, uint64_t slen, const uint8_t* pat, uint32_t L, uint32_t flags, bool prefix_kind = false, bool long_kind = false) {
     // the data chunks (a valid stream: the walk's table)
     std::vector<Data> ck;
     uint64_t end = 0;
@@ -92,7 +96,7 @@ void run_stream(const uint8_t* s, uint64_t slen, const uint8_t* pat, uint32_t L,
                 if (is_data(type)) break;
                 if (type == mlz::kChunkSearchTable && p + 4 + clen <= limit) {
                     const int R = mlz::search_table_reductions(s + p + 4, clen, M, B, T, field);
-                    const uint32_t f = mlz::search_field_len(T);
+                    const uint32_t f = mlz::search_field_len(T, field);
                     uint32_t crc = 0;
                     if (R >= 0) std::memcpy(&crc, s + p + 8 + f, 4);
                     if (R >= 0 && ((flags & 2) || masked_crc(s + p + 12 + f, clen - 8 - f) == crc)) { tabs[k] = mlz::SearchTab{p + 12 + f, clen - 8 - f, uint32_t(R), crc, 0}; usable++; break; }
@@ -101,25 +105,28 @@ void run_stream(const uint8_t* s, uint64_t slen, const uint8_t* pat, uint32_t L,
             }
         }
     std::vector<uint8_t> take(nck, 0);
-    uint32_t win[mlz::kSearchMaxPattern], t_min = 1;
-    const uint32_t nw = !(flags & 1) && ok && usable ? mlz::search_windows(pat, L, T, M, field, win, &t_min) : 0;
+    std::vector<uint32_t> win(mlz::kSearchMaxWindows);
+    uint32_t t_min = 1, gsize = 1;
+    const uint32_t nw = !(flags & 1) && ok && usable ? mlz::search_windows(pat, L, T, M, field, win.data(), &t_min, &gsize) : 0;
     if (!nw) {
         for (size_t k = 0; k < nck; k++) take[k] = ck[k].n ? 1 : 0;
-        if (prefix_kind) std::printf("%u %u %u 0 0 %u :", T, M, B, t_min);
+        if (long_kind) std::printf("%u %u %u 0 0 %u %u :", T, M, B, t_min, gsize);
+        else if (prefix_kind) std::printf("%u %u %u 0 0 %u :", T, M, B, t_min);
         else std::printf("%u %u 0 :", M, B);
         print_set(take);
         return;
     }
-    std::vector<uint32_t> h(nw), a(nck, nw), sv(nck, nw);
-    for (uint32_t i = 0; i < nw; i++) {
+    std::vector<uint32_t> h(nw * gsize), a(nck, nw), sv(nck, nw);
+    for (uint32_t i = 0; i < nw * gsize; i++) {
         uint64_t v = 0;
         for (uint32_t j = 0; j < M; j++) v |= uint64_t(pat[win[i] + j]) << (8 * j);
         h[i] = mlz::search_hash(v, B, M);
     }
     for (size_t k = 0; k < nck; k++)
-        if (tabs[k].R != mlz::kSearchNoTable) mlz::search_probe(s + tabs[k].off, B - tabs[k].R, h.data(), nw, &a[k], &sv[k]);
+        if (tabs[k].R != mlz::kSearchNoTable) mlz::search_probe(s + tabs[k].off, B - tabs[k].R, h.data(), nw, &a[k], &sv[k], gsize);
     mlz::search_decoded_set(nck, [&](size_t k) { return a[k]; }, [&](size_t k) { return sv[k]; }, [&](size_t k) { return ck[k].n; }, nw, L, take.data(), t_min);
-    if (prefix_kind) std::printf("%u %u %u %zu %u %u :", T, M, B, usable, nw, t_min);
+    if (long_kind) std::printf("%u %u %u %zu %u %u %u :", T, M, B, usable, nw, t_min, gsize);
+    else if (prefix_kind) std::printf("%u %u %u %zu %u %u :", T, M, B, usable, nw, t_min);
     else std::printf("%u %u %zu :", M, B, usable);
     print_set(take);
 }
@@ -231,12 +238,28 @@ int main(int argc, char** argv) {
             std::printf(" %u %u\n", bytes, R);
         } else if (kind == 9) {
             const uint32_t T = in.get<uint32_t>(), M = in.get<uint32_t>(), L = in.get<uint32_t>();
-            const uint8_t* field = in.bytes(mlz::kSearchMaxField);
+            const uint8_t* field = in.bytes(32);
             const uint8_t* pat = in.bytes(L);
             uint32_t win[mlz::kSearchMaxPattern], t_min = 0;
             const uint32_t nw = mlz::search_windows(pat, L, T, M, field, win, &t_min);
             std::printf("%u :", t_min);
             for (uint32_t i = 0; i < nw; i++) std::printf(" %u", win[i]);
+            std::printf("\n");
+        } else if (kind == 10) {
+            const uint64_t slen = in.get<uint64_t>();
+            const uint32_t L = in.get<uint32_t>(), flags = in.get<uint32_t>();
+            const uint8_t* s = in.bytes(size_t(slen));
+            const uint8_t* pat = in.bytes(L);
+            run_stream(s, slen, pat, L, flags, true, true);
+        } else if (kind == 11) {
+            const uint32_t M = in.get<uint32_t>(), L = in.get<uint32_t>(), flen = in.get<uint32_t>();
+            const uint8_t* field = in.bytes(flen);
+            const uint8_t* pat = in.bytes(L);
+            std::vector<uint32_t> win(mlz::kSearchMaxWindows);
+            uint32_t t_min = 0, gsize = 0;
+            const uint32_t ng = mlz::search_windows(pat, L, 4, M, field, win.data(), &t_min, &gsize);
+            std::printf("%u %u :", t_min, gsize);
+            for (uint32_t g = 0; g < ng; g++) std::printf(" %u", win[g * gsize]);
             std::printf("\n");
         } else {
             std::fprintf(stderr, "unknown record %u\n", kind);
