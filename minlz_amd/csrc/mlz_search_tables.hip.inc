@@ -24,6 +24,9 @@
 // stab_build_long_kernel is that form: a lane's 8 positions are prefix starts and every read goes forward.  Stage one compares the first
 //   min(K, 8) prefix bytes in registers with the lane's 16 loaded bytes and gathers 8 verdicts into a bit mask; stage two loops over the set
 //   bits only, compares the rest of the prefix (in LDS behind the bitmap) and hashes the E + 1 windows.
+// Both forms share stab_zero, stab_share, stab_positions, stab_mark and stab_flush (the zeroing of the bitmap, a workgroup's (part, slice, block)
+//   and its positions, the slice-filtered bit and the write-out or merge); they stay kernels of their own: the short forms keep the bytes behind
+//   the range in a register, the long form in LDS.
 // stab_reduce_kernel: a workgroup per block counts the bits, applies the rules above fold by fold (search_reduce_rule's conditions) and leaves
 //   the table compact at the front of its slot; 8 bytes per block (table bytes or 0, R) go to the host next to the sizes and CRCs.
 
@@ -31,15 +34,58 @@ namespace mlz {
 
 constexpr uint32_t kStabSliceBits = 20, kStabThreads = 1024, kStabPerThread = 8;
 
-struct StabArgs {
+// What every build kernel is told
+struct StabCommon {
     const uint8_t* src;      // the range
     uint64_t len;            // its bytes
-    uint64_t tail;           // the bytes behind the range (the next range's first ones), little-endian
-    uint32_t tail_n;         // how many of them exist (0: the range ends the stream)
+    uint32_t tail_n;         // how many bytes behind the range (the next range's first ones) exist (0: the range ends the stream)
     uint32_t bs, cnt, B, M, parts, slices;
     uint32_t* tabs;          // cnt tables of 2^B bits
+};
+struct StabArgs : StabCommon {
+    uint64_t tail;           // the bytes behind the range, little-endian
     uint32_t mask[8];        // the prefix form: byte v is a prefix byte when mask[v >> 5] >> (v & 31) & 1
 };
+
+// A workgroup's bitmap in LDS: all 2^B bits, or its slice of 2^20
+__device__ __forceinline__ uint32_t stab_words(const StabCommon& a) { return 1u << ((a.B < kStabSliceBits ? a.B : kStabSliceBits) - 5); }
+__device__ __forceinline__ void stab_zero(uint32_t* bits, uint32_t words) {
+    for (uint32_t i = threadIdx.x; i < words; i += kStabThreads) bits[i] = 0;
+}
+// The workgroup's share: part `part` of block b's positions, the bits of slice `slice`.  next: a block follows this one in the stream
+struct StabShare { uint32_t part, slice, b, blen; uint64_t b0; bool next; };
+__device__ __forceinline__ StabShare stab_share(const StabCommon& a) {
+    StabShare w;
+    w.part = blockIdx.x % a.parts; w.slice = (blockIdx.x / a.parts) % a.slices; w.b = blockIdx.x / (a.parts * a.slices);
+    w.b0 = uint64_t(w.b) * a.bs;
+    w.blen = uint32_t(a.len - w.b0 < a.bs ? a.len - w.b0 : a.bs);
+    w.next = w.b + 1 < a.cnt || a.tail_n != 0;
+    return w;
+}
+// [*p0, *p1): the part's positions of the block's npos, a multiple of a lane's 8 each
+__device__ __forceinline__ void stab_positions(const StabCommon& a, uint32_t part, uint32_t npos, uint32_t* p0, uint32_t* p1) {
+    const uint32_t per = ((npos + a.parts - 1) / a.parts + kStabPerThread - 1) & ~(kStabPerThread - 1);
+    *p0 = part * per; *p1 = *p0 + per < npos ? *p0 + per : npos;
+}
+// bit h of the table, when it falls into this workgroup's slice
+__device__ __forceinline__ void stab_mark(uint32_t* bits, uint32_t slice, uint32_t h) {
+    if ((h >> kStabSliceBits) == slice) {
+        const uint32_t x = h & ((1u << kStabSliceBits) - 1);
+        atomicOr(&bits[x >> 5], 1u << (x & 31));
+    }
+}
+// The bitmap to the block's table in HBM: written out, or, when several parts share the (zeroed) table, merged by its words that are not zero
+__device__ __forceinline__ void stab_flush(const StabCommon& a, const StabShare& w, const uint32_t* bits, uint32_t words) {
+    uint32_t* out = a.tabs + (size_t(w.b) << (a.B - 5)) + (size_t(w.slice) << (kStabSliceBits - 5));
+    if (a.parts == 1) {
+        for (uint32_t i = threadIdx.x; i < words; i += kStabThreads) out[i] = bits[i];
+    } else {
+        for (uint32_t i = threadIdx.x; i < words; i += kStabThreads) {
+            const uint32_t v = bits[i];
+            if (v) atomicOr(&out[i], v);
+        }
+    }
+}
 
 // byte q of the range, continued by the next range's first bytes and zeros
 __device__ __forceinline__ uint64_t stab_byte(const StabArgs& a, uint64_t q) {
@@ -52,29 +98,21 @@ template <bool kPrefix>
 __global__ __launch_bounds__(kStabThreads) void stab_build_kernel(const StabArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint32_t* bits = reinterpret_cast<uint32_t*>(smem);
-    const uint32_t tid = threadIdx.x;
-    const uint32_t part = blockIdx.x % a.parts, slice = (blockIdx.x / a.parts) % a.slices, b = blockIdx.x / (a.parts * a.slices);
-    const uint32_t lbits = a.B < kStabSliceBits ? a.B : kStabSliceBits, words = 1u << (lbits - 5);
-    for (uint32_t i = tid; i < words; i += kStabThreads) bits[i] = 0;
+    const uint32_t tid = threadIdx.x, words = stab_words(a);
+    stab_zero(bits, words);
     [[maybe_unused]] const uint32_t* pmask = bits + words;   // the prefix form: 32 bytes behind the bitmap
     if constexpr (kPrefix) { if (tid < 8) bits[words + tid] = a.mask[tid]; }
     __syncthreads();
-    const uint64_t b0 = uint64_t(b) * a.bs;
-    const uint32_t blen = uint32_t(a.len - b0 < a.bs ? a.len - b0 : a.bs);
-    const bool next = b + 1 < a.cnt || a.tail_n != 0;
+    const StabShare w = stab_share(a);
+    const uint64_t b0 = w.b0;
+    const uint32_t blen = w.blen;
     // positions [0, npos): every one with a next block, else those whose window lies inside the block.  The prefix form: position 0 is
     // never indexed (it belongs to the block before), position blen of a block with a next one is (its window lies in the next block)
-    const uint32_t npos = kPrefix ? (next ? blen + 1 : (blen >= a.M ? blen - a.M + 1 : 0)) : (next ? blen : (blen >= a.M ? blen - a.M + 1 : 0));
-    const uint32_t per = ((npos + a.parts - 1) / a.parts + kStabPerThread - 1) & ~(kStabPerThread - 1);
-    const uint32_t p0 = part * per, p1 = p0 + per < npos ? p0 + per : npos;
+    const uint32_t npos = kPrefix ? (w.next ? blen + 1 : (blen >= a.M ? blen - a.M + 1 : 0)) : (w.next ? blen : (blen >= a.M ? blen - a.M + 1 : 0));
+    uint32_t p0, p1;
+    stab_positions(a, w.part, npos, &p0, &p1);
     const uint32_t M = a.M, B = a.B;
-    auto mark = [&](uint64_t v) {   // the window's bit, when it falls into this workgroup's slice
-        const uint32_t h = search_hash(v, B, M);
-        if ((h >> kStabSliceBits) == slice) {
-            const uint32_t x = h & ((1u << kStabSliceBits) - 1);
-            atomicOr(&bits[x >> 5], 1u << (x & 31));
-        }
-    };
+    auto mark = [&](uint64_t v) { stab_mark(bits, w.slice, search_hash(v, B, M)); };
     for (uint32_t i = p0 + tid * kStabPerThread; i < p1; i += kStabThreads * kStabPerThread) {
         // the prefix form reads from one byte in front of its first position (a part's first position looks at the part before it); the
         // block's first lane has no such byte and shifts a zero in, for position 0, which is skipped
@@ -114,49 +152,34 @@ __global__ __launch_bounds__(kStabThreads) void stab_build_kernel(const StabArgs
         }
     }
     __syncthreads();
-    uint32_t* out = a.tabs + (size_t(b) << (B - 5)) + (size_t(slice) << (kStabSliceBits - 5));
-    if (a.parts == 1) {
-        for (uint32_t i = tid; i < words; i += kStabThreads) out[i] = bits[i];
-    } else {
-        for (uint32_t i = tid; i < words; i += kStabThreads) {
-            const uint32_t w = bits[i];
-            if (w) atomicOr(&out[i], w);
-        }
-    }
+    stab_flush(a, w, bits, words);
 }
 
 // The long-prefix form (table type 4).  The bytes behind the range (K - 1 + M + E at the most) and the prefix travel in the kernel arguments.
 constexpr uint32_t kStabLongTail = 272;   // >= 255 + 16
-struct StabLongArgs {
-    const uint8_t* src;
-    uint64_t len;
-    uint32_t tail_n;         // bytes of `tail` that exist (0: the range ends the stream)
-    uint32_t bs, cnt, B, M, E, K, parts, slices;
-    uint32_t* tabs;
+struct StabLongArgs : StabCommon {
+    uint32_t E, K;
     uint8_t pfx[kSearchMaxPrefix];
-    uint8_t tail[kStabLongTail];
+    uint8_t tail[kStabLongTail];   // the bytes behind the range
 };
 
 __global__ __launch_bounds__(kStabThreads) void stab_build_long_kernel(const StabLongArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint32_t* bits = reinterpret_cast<uint32_t*>(smem);
-    const uint32_t tid = threadIdx.x;
-    const uint32_t part = blockIdx.x % a.parts, slice = (blockIdx.x / a.parts) % a.slices, b = blockIdx.x / (a.parts * a.slices);
-    const uint32_t lbits = a.B < kStabSliceBits ? a.B : kStabSliceBits, words = 1u << (lbits - 5);
-    for (uint32_t i = tid; i < words; i += kStabThreads) bits[i] = 0;
+    const uint32_t tid = threadIdx.x, words = stab_words(a);
+    stab_zero(bits, words);
     uint8_t* lpfx = smem + words * 4;            // the prefix and, behind it, the bytes that follow the range
     uint8_t* ltail = lpfx + kSearchMaxPrefix;
     if (tid < a.K) lpfx[tid] = a.pfx[tid];
     if (tid < kStabLongTail) ltail[tid] = tid < a.tail_n ? a.tail[tid] : 0;
     __syncthreads();
     const uint32_t M = a.M, B = a.B, E = a.E, K = a.K;
-    const uint64_t b0 = uint64_t(b) * a.bs, real = a.len + a.tail_n;   // real: where the stream's bytes that this range can see end
-    const uint32_t blen = uint32_t(a.len - b0 < a.bs ? a.len - b0 : a.bs);
-    const bool next = b + 1 < a.cnt || a.tail_n != 0;
+    const StabShare w = stab_share(a);
+    const uint64_t b0 = w.b0, real = a.len + a.tail_n;   // real: where the stream's bytes that this range can see end
     // prefix starts [0, npos): every position with a block behind, else those whose prefix and windows lie inside the block
-    const uint32_t npos = next ? blen : (blen >= K + M + E ? blen - K - M - E + 1 : 0);
-    const uint32_t per = ((npos + a.parts - 1) / a.parts + kStabPerThread - 1) & ~(kStabPerThread - 1);
-    const uint32_t p0 = part * per, p1 = p0 + per < npos ? p0 + per : npos;
+    const uint32_t npos = w.next ? w.blen : (w.blen >= K + M + E ? w.blen - K - M - E + 1 : 0);
+    uint32_t p0, p1;
+    stab_positions(a, w.part, npos, &p0, &p1);
     auto byte_at = [&](uint64_t q) -> uint64_t {   // byte q of the range, continued by the bytes behind it and zeros
         if (q < a.len) return a.src[q];
         const uint64_t over = q - a.len;
@@ -190,25 +213,11 @@ __global__ __launch_bounds__(kStabThreads) void stab_build_long_kernel(const Sta
             uint32_t t = 8;
             while (t < K && byte_at(s + t) == lpfx[t]) t++;
             if (t < K) continue;
-            for (uint32_t e = 0; e <= E; e++) {
-                const uint32_t h = search_hash(load8(s + K + e), B, M);
-                if ((h >> kStabSliceBits) == slice) {
-                    const uint32_t x = h & ((1u << kStabSliceBits) - 1);
-                    atomicOr(&bits[x >> 5], 1u << (x & 31));
-                }
-            }
+            for (uint32_t e = 0; e <= E; e++) stab_mark(bits, w.slice, search_hash(load8(s + K + e), B, M));
         }
     }
     __syncthreads();
-    uint32_t* out = a.tabs + (size_t(b) << (B - 5)) + (size_t(slice) << (kStabSliceBits - 5));
-    if (a.parts == 1) {
-        for (uint32_t i = tid; i < words; i += kStabThreads) out[i] = bits[i];
-    } else {
-        for (uint32_t i = tid; i < words; i += kStabThreads) {
-            const uint32_t w = bits[i];
-            if (w) atomicOr(&out[i], w);
-        }
-    }
+    stab_flush(a, w, bits, words);
 }
 
 // info[b] = (table bytes or 0, R); the table of 2^(B - R) bits is left at the front of its slot
@@ -252,11 +261,15 @@ __global__ __launch_bounds__(kStabThreads) void stab_reduce_kernel(uint32_t* __r
 namespace {
 
 // The tables of the cnt blocks of a range (len bytes at d_src), built and reduced on sm: c->d_stab then holds cnt slots of 2^(B - 3) bytes, each
-// with its block's table at the front, and behind them (at *info_off) cnt records (table bytes or 0, R).  tail: the tail_n <= 8 bytes that
-// follow the range in the stream (the next range's first ones); table type 4: long_tail, tail_n <= K - 1 + M + E bytes.  T, field: the table
-// type and its prefix field.  Caller holds c->mu.
+// with its block's table at the front, and behind them (at *info_off) cnt records (table bytes or 0, R).  tail: the tail_n bytes that follow
+// the range in the stream (the next range's first ones, StreamTables::overlap() at the most; host memory).  T, field: the table type and
+// its prefix field.  Caller holds c->mu.
+// The short forms take the first 8 of them, in a register.  They come as M - 1 (type 1) or M (types 2, 3) bytes: search_hash reads only the
+// M low bytes of its argument, so zeros behind them give the bits that more of the stream's bytes would.  The kernels read "a block
+// follows" from tail_n != 0: type 1 with M = 1 reaches no byte behind its block (tail_n is 0 there), and with or without a following block
+// its blocks index all their blen positions.
 int search_tables_build(mlz_ctx* c, hipStream_t sm, const uint8_t* d_src, size_t len, uint32_t bs, size_t cnt, uint32_t T, const uint8_t* field, uint32_t M, uint32_t B,
-                        uint64_t tail, uint32_t tail_n, size_t* info_off, const uint8_t* long_tail = nullptr) {
+                        const uint8_t* tail, uint32_t tail_n, size_t* info_off) {
     const size_t slot = size_t(1) << (B - 3);
     *info_off = cnt * slot;
     HIPCHK(c, c->d_stab.ensure(cnt * slot + cnt * sizeof(uint2) + 64));
@@ -268,25 +281,32 @@ int search_tables_build(mlz_ctx* c, hipStream_t sm, const uint8_t* d_src, size_t
                                       (1u << (mlz::kStabSliceBits - 3)) + mlz::kSearchMaxPrefix + mlz::kStabLongTail));
         c->stab_attr = true;
     }
-    mlz::StabArgs a{};
-    a.src = d_src; a.len = len; a.tail = tail; a.tail_n = tail_n; a.bs = bs; a.cnt = uint32_t(cnt); a.B = B; a.M = M;
+    mlz::StabCommon a{};
+    a.src = d_src; a.len = len; a.bs = bs; a.cnt = uint32_t(cnt); a.B = B; a.M = M;
+    a.tail_n = std::min(tail_n, T == 4 ? mlz::kStabLongTail : 8u);
     a.slices = 1u << (B - lbits);
     // few large blocks: parts of at least 64 KiB, until the device has about two workgroups per CU
     const uint64_t want = std::max<uint64_t>(1, uint64_t(2 * std::max(c->n_cus, 1)) / (cnt * a.slices));
     a.parts = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(want, bs >> 16)));
     a.tabs = c->d_stab.as<uint32_t>();
     if (a.parts > 1) HIPCHK(c, hipMemsetAsync(a.tabs, 0, cnt * slot, sm));
+    const dim3 grid(uint32_t(cnt * a.slices * a.parts)), wg(mlz::kStabThreads);
     if (T == 4) {
         mlz::StabLongArgs la{};
-        la.src = d_src; la.len = len; la.tail_n = std::min(tail_n, mlz::kStabLongTail); la.bs = bs; la.cnt = uint32_t(cnt); la.B = B; la.M = M;
-        la.E = mlz::search_long_e(field); la.K = mlz::search_long_k(field); la.parts = a.parts; la.slices = a.slices; la.tabs = a.tabs;
+        static_cast<mlz::StabCommon&>(la) = a;
+        la.E = mlz::search_long_e(field); la.K = mlz::search_long_k(field);
         std::memcpy(la.pfx, mlz::search_long_prefix(field), la.K);
-        if (la.tail_n) std::memcpy(la.tail, long_tail, la.tail_n);
-        hipLaunchKernelGGL(mlz::stab_build_long_kernel, dim3(uint32_t(cnt * a.slices * a.parts)), dim3(mlz::kStabThreads), lds + mlz::kSearchMaxPrefix + mlz::kStabLongTail, sm, la);
-    } else if (T == 1) hipLaunchKernelGGL(mlz::stab_build_kernel<false>, dim3(uint32_t(cnt * a.slices * a.parts)), dim3(mlz::kStabThreads), lds, sm, a);
-    else {
-        mlz::search_prefix_mask(T, field, a.mask);
-        hipLaunchKernelGGL(mlz::stab_build_kernel<true>, dim3(uint32_t(cnt * a.slices * a.parts)), dim3(mlz::kStabThreads), lds + 32, sm, a);
+        if (a.tail_n) std::memcpy(la.tail, tail, a.tail_n);
+        hipLaunchKernelGGL(mlz::stab_build_long_kernel, grid, wg, lds + mlz::kSearchMaxPrefix + mlz::kStabLongTail, sm, la);
+    } else {
+        mlz::StabArgs sa{};
+        static_cast<mlz::StabCommon&>(sa) = a;
+        if (a.tail_n) std::memcpy(&sa.tail, tail, a.tail_n);
+        if (T == 1) hipLaunchKernelGGL(mlz::stab_build_kernel<false>, grid, wg, lds, sm, sa);
+        else {
+            mlz::search_prefix_mask(T, field, sa.mask);
+            hipLaunchKernelGGL(mlz::stab_build_kernel<true>, grid, wg, lds + 32, sm, sa);
+        }
     }
     hipLaunchKernelGGL(mlz::stab_reduce_kernel, dim3(uint32_t(cnt)), dim3(mlz::kStabThreads), 0, sm, a.tabs, B, mlz::search_fold_limit(T),
                        reinterpret_cast<uint2*>(c->d_stab.as<uint8_t>() + *info_off));

@@ -9,6 +9,12 @@
 // Blocks are encoded / decoded / checksummed on the device in groups of ~256 MiB; the host-to-device
 // copy of group g+1 and the device-to-host copy of group g-1 run on their own streams while group g
 // is in the kernels (the reference overlaps I/O and compression with goroutines, writer.go:501-560).
+//
+// Both Writers (mlz_stream_encode over host memory, stream_encode_groups; the device-resident one, stream_gather_range under
+// stream_encode_gather_device_with) frame with the same helpers: chunk_shape and put_chunk_header for a block's chunk, put_stream_head and
+// stream_foot for what stands around the chunks, place_pieces + stream_place_kernel for chunk bodies that a kernel moves (stream_hdr_kernel and
+// stream_tabhdr_kernel write the device-resident Writer's chunk headers).  StreamTables is the one configuration of the search tables,
+// whichever call it came in by.
 
 namespace {
 
@@ -130,13 +136,6 @@ int ensure_stream_objects(mlz_ctx* c, size_t n_events, size_t pinned_bytes) {
     return 0;
 }
 
-size_t stream_bound(uint64_t n, uint32_t bs, bool add_index, bool with_tables = false, uint32_t field_len = 0 /* of the tables' prefix field */) {
-    const uint64_t nblk = (n + bs - 1) / bs;
-    // search tables: the info chunk and, per block, a table chunk with the unreduced table; both carry the type's prefix field
-    const uint64_t tables = with_tables ? 7 + field_len + nblk * mlz::search_chunk_bound(mlz::search_table_bits(bs), field_len) : 0;
-    return size_t(10 + nblk * (8 + 5) + n + 4 + 10 + (add_index ? SeekIndex::bound(size_t(nblk)) : 0) + tables);
-}
-
 // MLZ_STREAM_SEARCH_TABLES in `flags`: the match length M (bits 8 .. 11, 0 = the reference's default), 0 when the flag is clear, -1 for 9 .. 15
 int stream_search_match_len(uint32_t flags) {
     if (!(flags & MLZ_STREAM_SEARCH_TABLES)) return 0;
@@ -144,59 +143,151 @@ int stream_search_match_len(uint32_t flags) {
     return m == 0 ? int(mlz::kSearchDefaultMatchLen) : m <= 8 ? int(m) : -1;
 }
 
-// The Writer's search tables: T = 0 without them, else the table type, the match length and the prefix field as the chunks carry it
+// The Writer's search tables: T = 0 without them, else the table type, the match length and the prefix field as the chunks carry it.
+// valid = false: what the caller handed in is no configuration (-MLZ_ERR_ARG, behind the checks of the call's other arguments)
 struct StreamTables {
+    bool valid = true;
     uint32_t T = 0, M = 0;
     uint8_t field[mlz::kSearchMaxField] = {};
     uint32_t flen() const { return mlz::search_field_len(T, field); }
     // bytes behind a block that its prefixes and windows reach
     uint32_t overlap() const { return T == 1 ? M - 1 : T == 4 ? mlz::search_long_k(field) - 1 + M + mlz::search_long_e(field) : M; }
+    // the stream's head: magic chunk and, with tables, the info chunk
+    uint32_t head_bytes() const { return T ? 17 + flen() : 10; }
 };
-// flags and an mlz_search_tables (may be NULL) -> the configuration; false: -MLZ_ERR_ARG
-bool stream_tables_config(uint32_t flags, const mlz_search_tables* cfg, StreamTables* st) {
-    *st = StreamTables{};
+StreamTables no_stream_tables() { StreamTables st; st.valid = false; return st; }
+// flags and an mlz_search_tables (may be NULL) -> the configuration
+StreamTables stream_tables_config(uint32_t flags, const mlz_search_tables* cfg) {
+    StreamTables st;
     if (!cfg) {
         const int m = stream_search_match_len(flags);
-        if (m < 0) return false;
-        if (m) { st->T = 1; st->M = uint32_t(m); }
-        return true;
+        if (m < 0) return no_stream_tables();
+        if (m) { st.T = 1; st.M = uint32_t(m); }
+        return st;
     }
-    if ((flags & (MLZ_STREAM_SEARCH_TABLES | MLZ_STREAM_SEARCH_MATCH_LEN(15))) || cfg->table_type < 1 || cfg->table_type > 3 || cfg->match_len > 8 || cfg->reserved) return false;
-    st->T = cfg->table_type;
-    st->M = cfg->match_len ? cfg->match_len : mlz::kSearchDefaultMatchLen;
-    if (st->T == 2) {
-        if (cfg->n_prefix < 1 || cfg->n_prefix > 8) return false;
-        for (uint32_t i = 0; i < 8; i++) st->field[i] = cfg->prefix[i < cfg->n_prefix ? i : cfg->n_prefix - 1u];
-    } else if (st->T == 3) std::memcpy(st->field, cfg->prefix, 32);
-    return true;
+    if ((flags & (MLZ_STREAM_SEARCH_TABLES | MLZ_STREAM_SEARCH_MATCH_LEN(15))) || cfg->table_type < 1 || cfg->table_type > 3 || cfg->match_len > 8 || cfg->reserved) return no_stream_tables();
+    st.T = cfg->table_type;
+    st.M = cfg->match_len ? cfg->match_len : mlz::kSearchDefaultMatchLen;
+    if (st.T == 2) {
+        if (cfg->n_prefix < 1 || cfg->n_prefix > 8) return no_stream_tables();
+        for (uint32_t i = 0; i < 8; i++) st.field[i] = cfg->prefix[i < cfg->n_prefix ? i : cfg->n_prefix - 1u];
+    } else if (st.T == 3) std::memcpy(st.field, cfg->prefix, 32);
+    return st;
+}
+// An mlz_search_long_prefix -> the configuration of table type 4
+StreamTables stream_long_prefix_config(uint32_t flags, const mlz_search_long_prefix* cfg) {
+    if (!cfg || (flags & (MLZ_STREAM_SEARCH_TABLES | MLZ_STREAM_SEARCH_MATCH_LEN(15)))) return no_stream_tables();
+    if (cfg->prefix_len < 1 || cfg->prefix_len > mlz::kSearchMaxPrefix || cfg->match_len > 8 || cfg->extras > mlz::kSearchMaxExtras) return no_stream_tables();
+    for (uint8_t r : cfg->reserved) if (r) return no_stream_tables();
+    StreamTables st;
+    st.T = 4;
+    st.M = cfg->match_len ? cfg->match_len : mlz::kSearchDefaultMatchLen;
+    if (st.M + cfg->extras > mlz::kSearchMaxGroupWindows) return no_stream_tables();
+    st.field[0] = uint8_t(cfg->prefix_len - 1); st.field[1] = cfg->extras;
+    std::memcpy(st.field + 2, cfg->prefix, cfg->prefix_len);
+    return st;
 }
 
-// An mlz_search_long_prefix -> the configuration of table type 4; false: -MLZ_ERR_ARG
-bool stream_long_prefix_config(uint32_t flags, const mlz_search_long_prefix* cfg, StreamTables* st) {
-    *st = StreamTables{};
-    if (!cfg || (flags & (MLZ_STREAM_SEARCH_TABLES | MLZ_STREAM_SEARCH_MATCH_LEN(15)))) return false;
-    if (cfg->prefix_len < 1 || cfg->prefix_len > mlz::kSearchMaxPrefix || cfg->match_len > 8 || cfg->extras > mlz::kSearchMaxExtras) return false;
-    for (uint8_t r : cfg->reserved) if (r) return false;
-    st->T = 4;
-    st->M = cfg->match_len ? cfg->match_len : mlz::kSearchDefaultMatchLen;
-    if (st->M + cfg->extras > mlz::kSearchMaxGroupWindows) return false;
-    st->field[0] = uint8_t(cfg->prefix_len - 1); st->field[1] = cfg->extras;
-    std::memcpy(st->field + 2, cfg->prefix, cfg->prefix_len);
-    return true;
+size_t stream_bound(uint64_t n, uint32_t bs, bool add_index, const StreamTables& stb) {
+    const uint64_t nblk = (n + bs - 1) / bs;
+    // search tables: the info chunk and, per block, a table chunk with the unreduced table; both carry the type's prefix field
+    const uint64_t tables = stb.T ? 7 + stb.flen() + nblk * mlz::search_chunk_bound(mlz::search_table_bits(bs), stb.flen()) : 0;
+    return size_t(10 + nblk * (8 + 5) + n + 4 + 10 + (add_index ? SeekIndex::bound(size_t(nblk)) : 0) + tables);
 }
 
-// Chunk bodies of a group into a page-locked destination: one workgroup per 64 KiB piece copies from the encode output in HBM to
-// the caller's buffer (the per-block copy-out of a pinned buffer runs as shader copies on this ROCm build and queues up behind every
-// kernel of the stream: 22.6 GB/s against 31.3 into pageable memory for 100 MB).
+// ---- framing, said once for mlz_stream_encode and the device-resident Writer ----
+// A block as the encoder leaves it is `00 uvarint(N) tokens` or the stored form `00 00 raw` (encode.go:74-139, :223-228); only the stored form
+// has length N + 2 (tokens are < N - N/32 - 5).  Its chunk's body is the block minus its leading 0x00, or the raw bytes.
+struct ChunkShape { bool stored; size_t body; };
+ChunkShape chunk_shape(int64_t elen, size_t src_len) {
+    const bool stored = elen == int64_t(src_len) + 2;
+    return ChunkShape{stored, stored ? src_len : size_t(elen) - 1};
+}
+// The 8 bytes in front of a chunk's body: type, len24 (the CRC's 4 bytes and the body), crc
+void put_chunk_header(uint8_t* b, const ChunkShape& s, uint32_t crc) {
+    const size_t chunk_len = 4 + s.body;
+    b[0] = s.stored ? kChunkUncompressed : kChunkMinLZ;
+    b[1] = uint8_t(chunk_len); b[2] = uint8_t(chunk_len >> 8); b[3] = uint8_t(chunk_len >> 16);
+    std::memcpy(b + 4, &crc, 4);
+}
+// The stream's head (stb.head_bytes() bytes; it goes out with the first block, writer.go:463-467): the magic chunk and, with tables, the info
+// chunk `44 len24 | T M B | prefix field`
+void put_stream_head(uint8_t* b, uint32_t bs, const StreamTables& stb) {
+    std::memcpy(b, kMagicChunk, 9);
+    b[9] = uint8_t((32 - __builtin_clz(bs - 1)) - 10);  // log2(block size) - 10, writer.go:1553-1556
+    if (!stb.T) return;
+    const uint32_t ilen = 3 + stb.flen();
+    const uint8_t info[7] = {mlz::kChunkSearchInfo, uint8_t(ilen), uint8_t(ilen >> 8), 0, uint8_t(stb.T), uint8_t(stb.M), uint8_t(mlz::search_table_bits(bs))};
+    std::memcpy(b + 10, info, 7);
+    std::memcpy(b + 17, stb.field, stb.flen());
+}
+// The stream's foot: the EOF chunk (writer.go:1063-1074), then the index (writer.go:1080-1122) over the blocks' chunks, whose bytes (a table
+// chunk in front included) are `framed`.  *at: where the foot goes, behind `head` bytes and the chunks.
+std::vector<uint8_t> stream_foot(size_t n, uint32_t bs, size_t head, const std::vector<uint32_t>& framed, bool add_index, size_t* at) {
+    SeekIndex index;
+    index.reset(bs);
+    if (n > 0) index.add(0, 0);  // the stream header's own entry (writer.go:236-243): the first block's (head, 0) is then dropped (index.go:87-90)
+    size_t o = n > 0 ? head : 0;
+    for (size_t i = 0; i < framed.size(); i++) {
+        index.add(int64_t(o), int64_t(i * size_t(bs)));  // writer.go:945
+        o += framed[i];
+    }
+    *at = o;
+    std::vector<uint8_t> foot(16 + (add_index ? SeekIndex::bound(framed.size()) : 0));
+    const size_t vn = put_uvarint64(foot.data() + 4, n);
+    foot[0] = kChunkEOF; foot[1] = uint8_t(vn); foot[2] = 0; foot[3] = 0;
+    size_t t = 4 + vn;
+    if (add_index) t += index.append_to(foot.data() + t, int64_t(n), int64_t(o + t));
+    foot.resize(t);
+    return foot;
+}
+// What a call over several workers returns: the first worker's own verdict (one that only stopped because another one failed says -MLZ_ERR_HIP)
+int64_t first_own_verdict(const std::vector<int64_t>& rcs) {
+    for (int64_t r : rcs) if (r && r != -MLZ_ERR_HIP) return r;
+    for (int64_t r : rcs) if (r) return r;
+    return 0;
+}
+
+// ---- kernels that lay chunks out ----
+// Chunk bodies: one workgroup per 64 KiB piece copies from a source in HBM to the destination, a run of chunks in HBM or, through its device
+// alias, the caller's page-locked buffer (the per-block copy-out of a pinned buffer runs as shader copies on this ROCm build and queues up
+// behind every kernel of the stream: 22.6 GB/s against 31.3 into pageable memory for 100 MB).  desc.pad selects the source: for the Writer
+// 0 = the encoder's output, 1 = the raw block (stored chunks), 2 = the block's search table; a caller with fewer sources passes nullptr.
 struct PlaceDesc { uint64_t src_off, dst_off; uint32_t len, pad; };
 constexpr uint32_t kPlacePiece = 64 << 10;
 // The span of `len` bytes from src_off to dst_off, cut into pieces of 64 KiB: put(PlaceDesc) for each, in order
 template <class Put> void place_pieces(uint64_t src_off, uint64_t dst_off, uint64_t len, uint32_t pad, Put put) {
     for (uint64_t o = 0; o < len; o += kPlacePiece) put(PlaceDesc{src_off + o, dst_off + o, uint32_t(std::min<uint64_t>(kPlacePiece, len - o)), pad});
 }
-__global__ __launch_bounds__(256) void stream_place_kernel(const uint8_t* __restrict__ d_out, uint8_t* __restrict__ host_alias, const PlaceDesc* __restrict__ descs) {
+__global__ __launch_bounds__(256) void stream_place_kernel(const uint8_t* __restrict__ src0, const uint8_t* __restrict__ src1, const uint8_t* __restrict__ src2,
+                                                           uint8_t* __restrict__ dst, const PlaceDesc* __restrict__ descs) {
     const PlaceDesc d = descs[blockIdx.x];
-    mlz::wg_copy(host_alias + d.dst_off, d_out + d.src_off, d.len, threadIdx.x, 256);
+    mlz::wg_copy(dst + d.dst_off, (d.pad == 2 ? src2 : d.pad ? src1 : src0) + d.src_off, d.len, threadIdx.x, 256);
+}
+// Chunk headers of the device-resident Writer: eight literal bytes at a destination offset (a table chunk's: twelve and its prefix field, 20 or
+// 44 with table type 2 or 3; type 4's field of 2 + K bytes is the same in every table chunk and travels once, in the kernel's arguments:
+// TabHdrDesc::b then holds `45 len24 T M B` and `R crc32le`, and the field goes between the two).
+struct HdrDesc { uint64_t dst_off; uint8_t b[8]; };
+struct TabHdrDesc { uint64_t dst_off; uint8_t b[12 + 32]; uint32_t n; };
+struct TabLongField { uint32_t n; uint8_t b[mlz::kSearchMaxField + 2]; };   // n = 0: table types 1 .. 3
+__global__ __launch_bounds__(64) void stream_tabhdr_kernel(uint8_t* __restrict__ run, const TabHdrDesc* __restrict__ hd, uint32_t n, const TabLongField lf) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const TabHdrDesc& h = hd[i];
+    if (lf.n == 0) {
+        for (uint32_t k = 0; k < h.n; k++) run[h.dst_off + k] = h.b[k];
+        return;
+    }
+    for (uint32_t k = 0; k < 7; k++) run[h.dst_off + k] = h.b[k];
+    for (uint32_t k = 0; k < lf.n; k++) run[h.dst_off + 7 + k] = lf.b[k];
+    for (uint32_t k = 0; k < 5; k++) run[h.dst_off + 7 + lf.n + k] = h.b[7 + k];
+}
+__global__ __launch_bounds__(64) void stream_hdr_kernel(uint8_t* __restrict__ run, const HdrDesc* __restrict__ hd, uint32_t n) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const HdrDesc h = hd[i];
+#pragma unroll
+    for (int k = 0; k < 8; k++) run[h.dst_off + k] = h.b[k];
 }
 
 // What the workers of one stream-encode call share when the stream's blocks are dealt to several devices (mlz_init_devices): the framed size of every
@@ -231,6 +322,7 @@ struct StreamEncShared {
     }
 };
 
+
 // Worker j of k: the stream's GROUPS of blocks (kStreamGroupBytes of input each) j, j + k, j + 2k, ... — copy-in, encode, CRC, and the chunks
 // `[type][len24][crc][body]` written to their FINAL place in dst.  Everything is enqueued up front; a group's chunks are placed as soon as its sizes
 // and those of the groups before it are known (one device: its own earlier groups; several: the other devices' groups of the same pipeline step, which
@@ -252,12 +344,16 @@ int64_t stream_encode_groups(mlz_ctx* c, int level, uint32_t bs, const uint8_t* 
     HIPCHK(c, c->d_len.ensure(sizeof(int64_t) * cap_blocks));
     HIPCHK(c, c->d_crc.ensure(sizeof(uint32_t) * cap_blocks + 64));
     // (a page-locked destination: the chunk bodies are placed by a kernel, stream_place_kernel)
-    const size_t max_pieces = cap_blocks * ((size_t(bs) + kPlacePiece - 1) / kPlacePiece + 1);
-    int r = ensure_stream_objects(c, 3 * mine, cap_blocks * 12 + 64 + (mir_base ? max_pieces * sizeof(PlaceDesc) : 0));
+    const size_t max_pieces = mir_base ? cap_blocks * ((size_t(bs) + kPlacePiece - 1) / kPlacePiece + 1) : 0;
+    Carve pin;
+    const auto r_len = pin.take<int64_t>(cap_blocks);
+    const auto r_crc = pin.take<uint32_t>(cap_blocks);
+    const auto r_place = pin.take<PlaceDesc>(max_pieces, 64);
+    int r = ensure_stream_objects(c, 3 * mine, pin.bytes);
     if (r) return r;
-    int64_t* h_len = static_cast<int64_t*>(c->pinned2);
-    uint32_t* h_crc = reinterpret_cast<uint32_t*>(h_len + cap_blocks);
-    PlaceDesc* h_place = reinterpret_cast<PlaceDesc*>((reinterpret_cast<uintptr_t>(h_crc + cap_blocks) + 63) & ~uintptr_t(63));
+    int64_t* h_len = r_len.at(c->pinned2);
+    uint32_t* h_crc = r_crc.at(c->pinned2);
+    PlaceDesc* h_place = r_place.at(c->pinned2);
     size_t n_place = 0;
     if (mir_base) HIPCHK(c, c->d_place.ensure(max_pieces * sizeof(PlaceDesc)));
     // local slot li * pg + i <-> block (j + li * k) * pg + i of the stream; offsets inside this worker's d_in / d_out
@@ -292,8 +388,6 @@ int64_t stream_encode_groups(mlz_ctx* c, int level, uint32_t bs, const uint8_t* 
         HIPCHK(c, hipEventRecord(e_len, c->s_out));
     }
     // collect, group by group: sizes -> the group's place -> chunk headers (host) and bodies (copy-out stream)
-    // block = `00 uvarint(N) tokens` or the stored form `00 00 raw` (encode.go:74-139, :223-228); only the stored form has length N + 2
-    // (tokens are < N - N/32 - 5).  Chunk = 4 header bytes + crc + (block minus its leading 0x00), or + the raw bytes.
     size_t place_done = 0;
     for (size_t li = 0; li < mine; li++) {
         const size_t g = j + li * k, l0 = li * pg, cnt = count_of(li);
@@ -301,40 +395,27 @@ int64_t stream_encode_groups(mlz_ctx* c, int level, uint32_t bs, const uint8_t* 
         int64_t gbytes = 0;
         for (size_t i = l0; i < l0 + cnt; i++) {
             if (h_len[i] < 0) return h_len[i];
-            const size_t bl = size_t(desc[i].src_len);
-            gbytes += h_len[i] == int64_t(bl) + 2 ? int64_t(8 + bl) : int64_t(8 + size_t(h_len[i]) - 1);
+            gbytes += int64_t(8 + chunk_shape(h_len[i], size_t(desc[i].src_len)).body);
         }
         sh->publish(g, gbytes);
         const int64_t before = sh->base_of(g);
         if (before < 0) return -MLZ_ERR_HIP;   // (the failing worker reports its own error; this one only stops)
         size_t o = (n > 0 ? 10 : 0) + size_t(before);   // (behind the stream header)
         for (size_t i = l0; i < l0 + cnt; i++) {
-            const int64_t len = h_len[i];
-            const size_t bl = size_t(desc[i].src_len);
-            const bool stored = len == int64_t(bl) + 2;
+            const ChunkShape s = chunk_shape(h_len[i], size_t(desc[i].src_len));
             uint8_t* ob = dst + o;
-            size_t chunk_len;
-            if (!stored) {
-                chunk_len = 4 + size_t(len) - 1;  // crc + (block minus its leading 0x00)
-                ob[0] = kChunkMinLZ;
-                if (!mir_base) HIPCHK(c, hipMemcpyAsync(ob + 8, d_out + desc[i].dst_off + 1, size_t(len) - 1, hipMemcpyDeviceToHost, c->s_out));
-                else
-                    for (size_t q = 0; q < size_t(len) - 1; q += kPlacePiece)
-                        h_place[n_place++] = PlaceDesc{desc[i].dst_off + 1 + q, o + 8 + q, uint32_t(std::min<size_t>(kPlacePiece, size_t(len) - 1 - q)), 0};
-            } else {
-                chunk_len = 4 + bl;
-                ob[0] = kChunkUncompressed;
-                std::memcpy(ob + 8, src + (first_block(li) + (i - l0)) * size_t(bs), bl);
-            }
-            ob[1] = uint8_t(chunk_len); ob[2] = uint8_t(chunk_len >> 8); ob[3] = uint8_t(chunk_len >> 16);
-            std::memcpy(ob + 4, &h_crc[i], 4);
-            framed[first_block(li) + (i - l0)] = uint32_t(4 + chunk_len);
-            o += 4 + chunk_len;
+            put_chunk_header(ob, s, h_crc[i]);
+            if (s.stored) std::memcpy(ob + 8, src + (first_block(li) + (i - l0)) * size_t(bs), s.body);
+            else if (!mir_base) HIPCHK(c, hipMemcpyAsync(ob + 8, d_out + desc[i].dst_off + 1, s.body, hipMemcpyDeviceToHost, c->s_out));
+            else place_pieces(desc[i].dst_off + 1, o + 8, s.body, 0, [&](const PlaceDesc& d) { h_place[n_place++] = d; });
+            framed[first_block(li) + (i - l0)] = uint32_t(8 + s.body);
+            o += 8 + s.body;
         }
         if (mir_base && n_place > place_done) {   // this group's bodies: descriptors up, one launch
             PlaceDesc* d_place = c->d_place.as<PlaceDesc>();
             HIPCHK(c, hipMemcpyAsync(d_place + place_done, h_place + place_done, (n_place - place_done) * sizeof(PlaceDesc), hipMemcpyHostToDevice, c->s_out));
-            hipLaunchKernelGGL(stream_place_kernel, dim3(uint32_t(n_place - place_done)), dim3(256), 0, c->s_out, d_out, reinterpret_cast<uint8_t*>(mir_base), d_place + place_done);
+            hipLaunchKernelGGL(stream_place_kernel, dim3(uint32_t(n_place - place_done)), dim3(256), 0, c->s_out, d_out, nullptr, nullptr, reinterpret_cast<uint8_t*>(mir_base),
+                               d_place + place_done);
             place_done = n_place;
         }
     }
@@ -349,18 +430,11 @@ int64_t stream_encode_over(mlz_ctx* const* workers, size_t k, int level, uint32_
                            size_t dst_cap) {
     mlz_ctx* c0 = workers[0];
     const size_t nblk = (n + bs - 1) / bs;
-    if (dst_cap < stream_bound(n, bs, add_index)) return -MLZ_ERR_DST_TOO_SMALL;
-    size_t o = 0;
-    if (n > 0) {  // the header goes out with the first block (writer.go:463-467)
-        std::memcpy(dst, kMagicChunk, 9);
-        dst[9] = uint8_t((32 - __builtin_clz(bs - 1)) - 10);  // log2(block size) - 10, writer.go:1553-1556
-        o = 10;
-    }
-    SeekIndex index;
-    index.reset(bs);
-    if (n > 0) index.add(0, 0);  // the stream header's own entry (writer.go:236-243): the first block's (10, 0) is then dropped (index.go:87-90)
+    const StreamTables plain;
+    if (dst_cap < stream_bound(n, bs, add_index, plain)) return -MLZ_ERR_DST_TOO_SMALL;
+    if (n > 0) put_stream_head(dst, bs, plain);
+    std::vector<uint32_t> framed(nblk, 0);
     if (nblk) {
-        std::vector<uint32_t> framed(nblk, 0);
         // blocks per group: 64 MiB for one device; several devices want a few pipeline steps each (a device with ONE group has nothing to put its
         // copy-out under): at least two groups per device, of 16 MiB or more
         size_t gbytes = kStreamGroupBytes;
@@ -390,69 +464,23 @@ int64_t stream_encode_over(mlz_ctx* const* workers, size_t k, int level, uint32_
             for (size_t j = 1; j < k; j++) th.emplace_back(work, j);
             work(0);
             for (std::thread& t : th) t.join();
-            // the first worker's own verdict (a worker that only stopped because another one failed says -MLZ_ERR_HIP)
-            for (size_t j = 0; j < k && rc == 0; j++) if (rcs[j] && rcs[j] != -MLZ_ERR_HIP) rc = rcs[j];
-            for (size_t j = 0; j < k && rc == 0; j++) rc = rcs[j];
+            rc = first_own_verdict(rcs);
         }
         if (rc) return rc;
-        for (size_t i = 0; i < nblk; i++) {
-            index.add(int64_t(o), int64_t(i * size_t(bs)));  // writer.go:945
-            o += framed[i];
-        }
     }
-    // EOF chunk (writer.go:1063-1074), then the index (writer.go:1080-1122)
-    const size_t vn = put_uvarint64(dst + o + 4, n);
-    dst[o] = kChunkEOF; dst[o + 1] = uint8_t(vn); dst[o + 2] = 0; dst[o + 3] = 0;
-    o += 4 + vn;
-    if (add_index) o += index.append_to(dst + o, int64_t(n), int64_t(o));
-    return int64_t(o);
+    size_t o = 0;
+    const std::vector<uint8_t> foot = stream_foot(n, bs, plain.head_bytes(), framed, add_index, &o);
+    std::memcpy(dst + o, foot.data(), foot.size());
+    return int64_t(o + foot.size());
 }
 
 // ---- the device-resident Writer over several devices: sources in each device's HBM, the framed stream gathered GPU to GPU ----
-// Chunk bodies and 8-byte chunk headers into a run of chunks: desc.pad selects the source (0 = the encoder's output, 1 = the raw block, for
-// stored chunks; stream_place3_kernel: 2 = the block's search table); a header is eight literal bytes at a destination offset (a table chunk's: twelve
-// and its prefix field, 20 or 44 with table type 2 or 3; type 4's field of 2 + K bytes is the same in every table chunk and travels once, in
-// the kernel's arguments: TabHdrDesc::b then holds `45 len24 T M B` and `R crc32le`, and the field goes between the two).
-struct HdrDesc { uint64_t dst_off; uint8_t b[8]; };
-__global__ __launch_bounds__(256) void stream_place2_kernel(const uint8_t* __restrict__ d_enc, const uint8_t* __restrict__ d_raw, uint8_t* __restrict__ run,
-                                                            const PlaceDesc* __restrict__ descs) {
-    const PlaceDesc d = descs[blockIdx.x];
-    mlz::wg_copy(run + d.dst_off, (d.pad ? d_raw : d_enc) + d.src_off, d.len, threadIdx.x, 256);
-}
-struct TabHdrDesc { uint64_t dst_off; uint8_t b[12 + 32]; uint32_t n; };
-struct TabLongField { uint32_t n; uint8_t b[mlz::kSearchMaxField + 2]; };   // n = 0: table types 1 .. 3
-__global__ __launch_bounds__(256) void stream_place3_kernel(const uint8_t* __restrict__ d_enc, const uint8_t* __restrict__ d_raw, const uint8_t* __restrict__ d_tab,
-                                                            uint8_t* __restrict__ run, const PlaceDesc* __restrict__ descs) {
-    const PlaceDesc d = descs[blockIdx.x];
-    mlz::wg_copy(run + d.dst_off, (d.pad == 2 ? d_tab : d.pad ? d_raw : d_enc) + d.src_off, d.len, threadIdx.x, 256);
-}
-__global__ __launch_bounds__(64) void stream_tabhdr_kernel(uint8_t* __restrict__ run, const TabHdrDesc* __restrict__ hd, uint32_t n, const TabLongField lf) {
-    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    const TabHdrDesc& h = hd[i];
-    if (lf.n == 0) {
-        for (uint32_t k = 0; k < h.n; k++) run[h.dst_off + k] = h.b[k];
-        return;
-    }
-    for (uint32_t k = 0; k < 7; k++) run[h.dst_off + k] = h.b[k];
-    for (uint32_t k = 0; k < lf.n; k++) run[h.dst_off + 7 + k] = lf.b[k];
-    for (uint32_t k = 0; k < 5; k++) run[h.dst_off + 7 + lf.n + k] = h.b[7 + k];
-}
-__global__ __launch_bounds__(64) void stream_hdr_kernel(uint8_t* __restrict__ run, const HdrDesc* __restrict__ hd, uint32_t n) {
-    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    const HdrDesc h = hd[i];
-#pragma unroll
-    for (int k = 0; k < 8; k++) run[h.dst_off + k] = h.b[k];
-}
-
 // Range j (blocks [b0, b0 + cnt) of the stream, its bytes at d_src on c's device): encode + CRC on the device, sizes and CRCs (12 bytes per
 // block) to the host, the run of chunks framed on the device, then moved to its place in d_dst on device dst_dev (the same device: framed in
 // place; another one: hipMemcpyPeerAsync, which rides xGMI between the GPUs of a node).  Payload never visits the host.
-int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d_src, size_t len, size_t b0, uint8_t* d_dst, int dst_dev, bool have_header,
-                            StreamEncShared* sh, size_t j, uint32_t* framed, const StreamTables& stb = StreamTables{} /* T > 0: search tables */, uint64_t tail = 0,
-                            uint32_t tail_n = 0 /* the bytes that follow the range in the stream, 8 at the most */,
-                            const uint8_t* long_tail = nullptr /* table type 4: the tail_n bytes that follow, K - 1 + M + E at the most */) {
+// stb: the search tables (T > 0), whose builder takes the tail_n bytes at `tail` (host memory) that follow the range in the stream.
+int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d_src, size_t len, size_t b0, uint8_t* d_dst, int dst_dev, StreamEncShared* sh, size_t j,
+                            uint32_t* framed, const StreamTables& stb, const uint8_t* tail, uint32_t tail_n) {
     HIPCHK(c, hipSetDevice(c->device));
     const size_t cnt = (len + bs - 1) / bs;
     if (cnt == 0) { sh->publish(j, 0); return 0; }
@@ -464,15 +492,24 @@ int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d
     HIPCHK(c, c->d_len.ensure(sizeof(int64_t) * cnt));
     HIPCHK(c, c->d_crc.ensure(sizeof(uint32_t) * cnt + 64));
     const size_t max_pieces = cnt * ((size_t(bs) + kPlacePiece - 1) / kPlacePiece + 1 + (search_m ? (tab_slot + kPlacePiece - 1) / kPlacePiece : 0));
-    int r = ensure_stream_objects(c, 1, cnt * 12 + 128 + max_pieces * sizeof(PlaceDesc) + cnt * sizeof(HdrDesc) + (search_m ? cnt * (12 + sizeof(TabHdrDesc)) + 64 : 0));
+    const size_t tcnt = search_m ? cnt : 0;
+    Carve pin;   // what comes back: sizes | CRCs | (table bytes or 0, R) | table CRCs; what goes up: pieces | chunk headers | table chunk headers
+    const auto r_len = pin.take<int64_t>(cnt);
+    const auto r_crc = pin.take<uint32_t>(cnt);
+    const auto r_tabinfo = pin.take<uint2>(tcnt);
+    const auto r_tabcrc = pin.take<uint32_t>(tcnt);
+    const auto r_place = pin.take<PlaceDesc>(max_pieces, 64);
+    const auto r_hdr = pin.take<HdrDesc>(cnt);
+    const auto r_tabhdr = pin.take<TabHdrDesc>(tcnt);
+    int r = ensure_stream_objects(c, 1, pin.bytes);
     if (r) return r;
-    int64_t* h_len = static_cast<int64_t*>(c->pinned2);
-    uint32_t* h_crc = reinterpret_cast<uint32_t*>(h_len + cnt);
-    PlaceDesc* h_place = reinterpret_cast<PlaceDesc*>((reinterpret_cast<uintptr_t>(h_crc + cnt) + 63) & ~uintptr_t(63));
-    HdrDesc* h_hdr = reinterpret_cast<HdrDesc*>(h_place + max_pieces);
-    TabHdrDesc* h_tabhdr = reinterpret_cast<TabHdrDesc*>(h_hdr + cnt);                // search tables: a table chunk's header per block,
-    uint2* h_tabinfo = reinterpret_cast<uint2*>(h_tabhdr + (search_m ? cnt : 0));      // (table bytes or 0, R)
-    uint32_t* h_tabcrc = reinterpret_cast<uint32_t*>(h_tabinfo + (search_m ? cnt : 0));   // and the table's CRC
+    int64_t* h_len = r_len.at(c->pinned2);
+    uint32_t* h_crc = r_crc.at(c->pinned2);
+    uint2* h_tabinfo = r_tabinfo.at(c->pinned2);
+    uint32_t* h_tabcrc = r_tabcrc.at(c->pinned2);
+    PlaceDesc* h_place = r_place.at(c->pinned2);
+    HdrDesc* h_hdr = r_hdr.at(c->pinned2);
+    TabHdrDesc* h_tabhdr = r_tabhdr.at(c->pinned2);
     std::vector<mlz_block_desc> desc(cnt);
     for (size_t i = 0; i < cnt; i++) {
         desc[i].src_off = i * size_t(bs); desc[i].src_len = std::min<size_t>(bs, len - i * size_t(bs));
@@ -484,9 +521,9 @@ int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d
     if (r) return r;
     r = crc_device_locked(c, sm, d_src, desc.data(), int(cnt), c->d_crc.as<uint32_t>());
     if (r) return r;
-    size_t tabinfo_off = 0;
     if (search_m) {
-        r = search_tables_build(c, sm, d_src, len, bs, cnt, stb.T, stb.field, search_m, search_b, tail, tail_n, &tabinfo_off, long_tail);
+        size_t tabinfo_off = 0;
+        r = search_tables_build(c, sm, d_src, len, bs, cnt, stb.T, stb.field, search_m, search_b, tail, tail_n, &tabinfo_off);
         if (r) return r;
         HIPCHK(c, hipMemcpyAsync(h_tabinfo, c->d_stab.as<uint8_t>() + tabinfo_off, sizeof(uint2) * cnt, hipMemcpyDeviceToHost, sm));
     }
@@ -500,7 +537,7 @@ int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d
         std::vector<mlz_block_desc> tdesc;
         for (size_t i = 0; i < cnt; i++) {
             if (h_len[i] < 0) return h_len[i];
-            if (h_len[i] == int64_t(desc[i].src_len) + 2) h_tabinfo[i].x = 0;
+            if (chunk_shape(h_len[i], size_t(desc[i].src_len)).stored) h_tabinfo[i].x = 0;
             if (h_tabinfo[i].x) tdesc.push_back(mlz_block_desc{i * tab_slot, h_tabinfo[i].x, 0, 0});
         }
         n_tabs = tdesc.size();
@@ -512,14 +549,12 @@ int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d
             HIPCHK(c, hipStreamSynchronize(sm));
         }
     }
-    // the run's layout: [type][len24][crc][body] per block (see stream_encode_groups), a block's table chunk in front of it
+    // the run's layout: [type][len24][crc][body] per block, a block's table chunk in front of it
     size_t run = 0, n_place = 0, tab_at = 0;
+    auto put_piece = [&](const PlaceDesc& d) { h_place[n_place++] = d; };
     for (size_t i = 0; i < cnt; i++) {
-        const int64_t elen = h_len[i];
-        if (elen < 0) return elen;
-        const size_t bl = size_t(desc[i].src_len);
-        const bool stored = elen == int64_t(bl) + 2;
-        const size_t body = stored ? bl : size_t(elen) - 1, chunk_len = 4 + body;
+        if (h_len[i] < 0) return h_len[i];
+        const ChunkShape s = chunk_shape(h_len[i], size_t(desc[i].src_len));
         framed[b0 + i] = 0;
         if (search_m && h_tabinfo[i].x) {   // 45 len24 | T M B | prefix field | R | crc32le | table
             const uint32_t tb = h_tabinfo[i].x, tlen = thdr - 4 + tb;
@@ -531,49 +566,143 @@ int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d
             std::memcpy(th.b + 7, stb.field, inl);
             th.b[7 + inl] = uint8_t(h_tabinfo[i].y);
             std::memcpy(th.b + 8 + inl, &h_tabcrc[tab_at], 4);
-            for (size_t q = 0; q < tb; q += kPlacePiece)
-                h_place[n_place++] = PlaceDesc{i * tab_slot + q, run + thdr + q, uint32_t(std::min<size_t>(kPlacePiece, tb - q)), 2u};
+            place_pieces(i * tab_slot, run + thdr, tb, 2, put_piece);
             tab_at++;
             framed[b0 + i] = thdr + tb;
             run += thdr + tb;
         }
-        HdrDesc& h = h_hdr[i];
-        h.dst_off = run;
-        h.b[0] = stored ? kChunkUncompressed : kChunkMinLZ;
-        h.b[1] = uint8_t(chunk_len); h.b[2] = uint8_t(chunk_len >> 8); h.b[3] = uint8_t(chunk_len >> 16);
-        std::memcpy(h.b + 4, &h_crc[i], 4);
-        const size_t from = stored ? desc[i].src_off : desc[i].dst_off + 1;
-        for (size_t q = 0; q < body; q += kPlacePiece)
-            h_place[n_place++] = PlaceDesc{from + q, run + 8 + q, uint32_t(std::min<size_t>(kPlacePiece, body - q)), stored ? 1u : 0u};
-        framed[b0 + i] += uint32_t(8 + body);
-        run += 8 + body;
+        h_hdr[i].dst_off = run;
+        put_chunk_header(h_hdr[i].b, s, h_crc[i]);
+        place_pieces(s.stored ? desc[i].src_off : desc[i].dst_off + 1, run + 8, s.body, s.stored ? 1 : 0, put_piece);
+        framed[b0 + i] += uint32_t(8 + s.body);
+        run += 8 + s.body;
     }
     sh->publish(j, int64_t(run));
     const int64_t before = sh->base_of(j);
     if (before < 0) return -MLZ_ERR_HIP;
-    const size_t base = (have_header ? (search_m ? 17 + flen : 10) : 0) + size_t(before);
+    const size_t base = stb.head_bytes() + size_t(before);   // (a range with a block in it: the stream has a head)
     // frame the run: in place when d_dst is on this device, else in a local buffer that then travels
     const bool local = c->device == dst_dev;
     uint8_t* d_run = d_dst + base;
     if (!local) { HIPCHK(c, c->d_in.ensure(run + 64)); d_run = c->d_in.as<uint8_t>(); }
-    HIPCHK(c, c->d_place.ensure(n_place * sizeof(PlaceDesc) + cnt * sizeof(HdrDesc) + n_tabs * sizeof(TabHdrDesc) + 64));
-    PlaceDesc* d_place = c->d_place.as<PlaceDesc>();
-    HdrDesc* d_hdr = reinterpret_cast<HdrDesc*>(d_place + n_place);
+    Carve up;
+    const auto u_place = up.take<PlaceDesc>(n_place);
+    const auto u_hdr = up.take<HdrDesc>(cnt);
+    const auto u_tabhdr = up.take<TabHdrDesc>(n_tabs);
+    HIPCHK(c, c->d_place.ensure(up.bytes));
+    PlaceDesc* d_place = u_place.at(c->d_place.p);
+    HdrDesc* d_hdr = u_hdr.at(c->d_place.p);
+    TabHdrDesc* d_tabhdr = u_tabhdr.at(c->d_place.p);
     if (n_place) HIPCHK(c, hipMemcpyAsync(d_place, h_place, n_place * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
     HIPCHK(c, hipMemcpyAsync(d_hdr, h_hdr, cnt * sizeof(HdrDesc), hipMemcpyHostToDevice, sm));
-    if (search_m) {
-        TabHdrDesc* d_tabhdr = reinterpret_cast<TabHdrDesc*>(d_hdr + cnt);
-        if (n_tabs) HIPCHK(c, hipMemcpyAsync(d_tabhdr, h_tabhdr, n_tabs * sizeof(TabHdrDesc), hipMemcpyHostToDevice, sm));
-        if (n_place) hipLaunchKernelGGL(stream_place3_kernel, dim3(uint32_t(n_place)), dim3(256), 0, sm, d_out, d_src, c->d_stab.as<uint8_t>(), d_run, d_place);
+    if (n_tabs) HIPCHK(c, hipMemcpyAsync(d_tabhdr, h_tabhdr, n_tabs * sizeof(TabHdrDesc), hipMemcpyHostToDevice, sm));
+    if (n_place) hipLaunchKernelGGL(stream_place_kernel, dim3(uint32_t(n_place)), dim3(256), 0, sm, d_out, d_src, search_m ? c->d_stab.as<uint8_t>() : nullptr, d_run, d_place);
+    if (n_tabs) {
         TabLongField lf{};
         if (stb.T == 4) { lf.n = flen; std::memcpy(lf.b, stb.field, flen); }
-        if (n_tabs) hipLaunchKernelGGL(stream_tabhdr_kernel, dim3(uint32_t((n_tabs + 63) / 64)), dim3(64), 0, sm, d_run, d_tabhdr, uint32_t(n_tabs), lf);
-    } else if (n_place) hipLaunchKernelGGL(stream_place2_kernel, dim3(uint32_t(n_place)), dim3(256), 0, sm, d_out, d_src, d_run, d_place);
+        hipLaunchKernelGGL(stream_tabhdr_kernel, dim3(uint32_t((n_tabs + 63) / 64)), dim3(64), 0, sm, d_run, d_tabhdr, uint32_t(n_tabs), lf);
+    }
     hipLaunchKernelGGL(stream_hdr_kernel, dim3(uint32_t((cnt + 63) / 64)), dim3(64), 0, sm, d_run, d_hdr, uint32_t(cnt));
     if (!local) HIPCHK(c, hipMemcpyPeerAsync(d_dst + base, dst_dev, d_run, c->device, run, sm));
     HIPCHK(c, hipStreamSynchronize(sm));
     HIPCHK(c, hipGetLastError());
     return 0;
+}
+
+// The device-resident Writer behind mlz_stream_encode_gather_device, _tables and _long_prefix, which hand in their configuration as stb
+int64_t stream_encode_gather_device_with(mlz_ctx* c, int level, uint32_t block_size, uint32_t flags, const StreamTables& stb, const uint8_t* const* d_src,
+                                         const size_t* src_len, int n_ranges, uint8_t* d_dst, size_t dst_cap) {
+    if (!c || !d_src || !src_len || n_ranges <= 0 || !d_dst) return -MLZ_ERR_ARG;
+    if (block_size < kMinStreamBlock || block_size > kMaxBlockSize) return -MLZ_ERR_ARG;
+    if (!valid_level(level)) return -MLZ_ERR_INVALID_LEVEL;
+    if (!stb.valid) return -MLZ_ERR_ARG;
+    const bool add_index = (flags & MLZ_STREAM_ADD_INDEX) != 0;
+    Workers w(c);
+    const size_t k = size_t(n_ranges);
+    // every range on the device that holds it; all but the last are whole blocks (a short block ends a stream)
+    std::vector<mlz_ctx*> own(k, nullptr);
+    std::vector<size_t> first(k + 1, 0);
+    size_t n = 0;
+    for (size_t j = 0; j < k; j++) {
+        if (src_len[j] && !d_src[j]) return -MLZ_ERR_ARG;
+        if (j + 1 < k && src_len[j] % block_size) return -MLZ_ERR_ARG;
+        first[j + 1] = first[j] + (src_len[j] + block_size - 1) / block_size;
+        n += src_len[j];
+        if (!src_len[j]) { own[j] = w.list[0]; continue; }
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, d_src[j]) != hipSuccess || at.type != hipMemoryTypeDevice) { (void)hipGetLastError(); return -MLZ_ERR_ARG; }
+        // the contexts on that device (one, unless the device was listed twice) take its ranges in turn
+        size_t on_dev = 0, earlier = 0;
+        for (size_t q = 0; q < w.n; q++) on_dev += w.list[q]->device == at.device ? 1 : 0;
+        if (!on_dev) return -MLZ_ERR_ARG;
+        for (size_t i = 0; i < j; i++) earlier += (src_len[i] && own[i]->device == at.device) ? 1 : 0;
+        for (size_t q = 0, hit = 0; q < w.n; q++)
+            if (w.list[q]->device == at.device && hit++ == earlier % on_dev) own[j] = w.list[q];
+    }
+    hipPointerAttribute_t dat;
+    if (hipPointerGetAttributes(&dat, d_dst) != hipSuccess || dat.type != hipMemoryTypeDevice) { (void)hipGetLastError(); return -MLZ_ERR_ARG; }
+    const int dst_dev = dat.device;
+    if (dst_cap < stream_bound(n, block_size, add_index, stb)) return -MLZ_ERR_DST_TOO_SMALL;
+    // search tables: a range's last block indexes prefixes and windows that run into the bytes behind it, stb.overlap() of them at the most, which
+    // the host hands over.  They all lie in the first non-empty range that follows: every range but the last is a whole number of blocks of
+    // at least 4 KiB, more than any overlap (K - 1 + M + E <= 271), and behind the last range the stream ends (zeros stand for what is missing)
+    const size_t need = stb.T ? stb.overlap() : 0;
+    std::vector<uint8_t> tails(k * need + 1, 0);
+    std::vector<uint32_t> tail_n(k, 0);
+    for (size_t j = 0; need && j + 1 < k; j++) {
+        size_t q = j + 1;
+        while (q < k && !src_len[q]) q++;
+        if (q == k || !src_len[j]) continue;
+        tail_n[j] = uint32_t(std::min(need, src_len[q]));
+        if (hipSetDevice(own[q]->device) != hipSuccess || hipMemcpy(&tails[j * need], d_src[q], tail_n[j], hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
+    }
+    std::vector<uint32_t> framed(first[k], 0);
+    StreamEncShared sh(k);
+    std::vector<int64_t> rcs(k, 0);
+    // two ranges may share a context (more ranges than contexts on a device): they queue on its lock in range order — the base_of() hand-over
+    // only ever waits for LOWER ranges, which hold or have held the lock first when threads start in order; to be safe against any start order a
+    // context's ranges run on ONE thread, lowest first
+    std::vector<std::vector<size_t>> by_ctx;
+    std::vector<mlz_ctx*> ctxs;
+    for (size_t j = 0; j < k; j++) {
+        size_t q = 0;
+        while (q < ctxs.size() && ctxs[q] != own[j]) q++;
+        if (q == ctxs.size()) { ctxs.push_back(own[j]); by_ctx.emplace_back(); }
+        by_ctx[q].push_back(j);
+    }
+    auto work = [&](size_t q) {
+        mlz_ctx* kc = ctxs[q];
+        std::lock_guard<std::mutex> lk(kc->mu);
+        for (size_t j : by_ctx[q]) {
+            rcs[j] = stream_gather_range(kc, level, block_size, d_src[j], src_len[j], first[j], d_dst, dst_dev, &sh, j, framed.data(), stb, &tails[j * need], tail_n[j]);
+            if (rcs[j]) { sh.fail(); (void)hipStreamSynchronize(kc->stream); }
+        }
+    };
+    std::vector<std::thread> th;
+    for (size_t q = 1; q < ctxs.size(); q++) th.emplace_back(work, q);
+    work(0);
+    for (std::thread& t : th) t.join();
+    const int64_t rc = first_own_verdict(rcs);
+    if (rc) { std::lock_guard<std::mutex> lk(c->mu); for (size_t j = 0; j < k; j++) if (rcs[j] == rc) { c->err = own[j]->err; break; } return rc; }
+    // stream header, EOF chunk and index: a few bytes from the host (writer.go:463-467, :1063-1122)
+    mlz_ctx* c0 = w.list[0];
+    std::lock_guard<std::mutex> lk(c0->mu);
+    HIPCHK(c0, hipSetDevice(dst_dev));
+    if (n > 0) {
+        uint8_t head[17 + mlz::kSearchMaxField];
+        put_stream_head(head, block_size, stb);
+        HIPCHK(c0, hipMemcpy(d_dst, head, stb.head_bytes(), hipMemcpyHostToDevice));
+    }
+    size_t o = 0;
+    const std::vector<uint8_t> foot = stream_foot(n, block_size, stb.head_bytes(), framed, add_index, &o);
+    HIPCHK(c0, hipMemcpy(d_dst + o, foot.data(), foot.size(), hipMemcpyHostToDevice));
+    return int64_t(o + foot.size());
+}
+
+// mlz_stream_bound, _tables and _long_prefix
+int64_t stream_bound_checked(uint64_t n, uint32_t block_size, uint32_t flags, const StreamTables& stb) {
+    if (block_size < kMinStreamBlock || block_size > kMaxBlockSize || !stb.valid) return -MLZ_ERR_ARG;
+    return int64_t(stream_bound(n, block_size, (flags & MLZ_STREAM_ADD_INDEX) != 0, stb));
 }
 
 struct StreamChunk {
@@ -773,26 +902,6 @@ int64_t stream_decode_range(mlz_ctx* c, bool ignore_crc, const uint8_t* src, std
     return 0;
 }
 
-int64_t stream_decode_chunks(mlz_ctx* const* workers, size_t k, bool ignore_crc, const uint8_t* src, std::vector<StreamChunk>& chunks, uint8_t* dst,
-                             size_t total);
-
-// The chunk walk, then the chunks dealt to `workers` in contiguous ranges of about equal output (one worker: this thread).
-// The Reader reports the first error in stream order: the lowest failing range's.
-// A framing error comes after the chunks in front of it: those are decoded and checked first, and their first error wins; the framing
-// error is reported only when they all pass (and fit in dst: else -MLZ_ERR_DST_TOO_SMALL, where the Reader's write would fail).
-int64_t stream_decode_over(mlz_ctx* const* workers, size_t k, bool ignore_crc, const uint8_t* src, size_t slen, uint8_t* dst, size_t dst_cap) {
-    std::vector<StreamChunk> chunks;
-    const int64_t parsed = stream_parse(src, slen, &chunks);
-    if (parsed < 0) {
-        const size_t prefix = chunks.empty() ? 0 : chunks.back().out_off + chunks.back().n;
-        if (prefix > dst_cap) return -MLZ_ERR_DST_TOO_SMALL;
-        const int64_t r = prefix ? stream_decode_chunks(workers, k, ignore_crc, src, chunks, dst, prefix) : 0;
-        return r < 0 ? r : parsed;
-    }
-    if (size_t(parsed) > dst_cap) return -MLZ_ERR_DST_TOO_SMALL;
-    return stream_decode_chunks(workers, k, ignore_crc, src, chunks, dst, size_t(parsed));
-}
-
 // The parsed chunks (total: their decoded bytes) dealt to the workers; returns total or the first error in stream order.
 int64_t stream_decode_chunks(mlz_ctx* const* workers, size_t k, bool ignore_crc, const uint8_t* src, std::vector<StreamChunk>& chunks, uint8_t* dst,
                              size_t total) {
@@ -831,28 +940,30 @@ int64_t stream_decode_chunks(mlz_ctx* const* workers, size_t k, bool ignore_crc,
     return int64_t(total);
 }
 
+// The chunk walk, then the chunks dealt to `workers` in contiguous ranges of about equal output (one worker: this thread).
+// The Reader reports the first error in stream order: the lowest failing range's.
+// A framing error comes after the chunks in front of it: those are decoded and checked first, and their first error wins; the framing
+// error is reported only when they all pass (and fit in dst: else -MLZ_ERR_DST_TOO_SMALL, where the Reader's write would fail).
+int64_t stream_decode_over(mlz_ctx* const* workers, size_t k, bool ignore_crc, const uint8_t* src, size_t slen, uint8_t* dst, size_t dst_cap) {
+    std::vector<StreamChunk> chunks;
+    const int64_t parsed = stream_parse(src, slen, &chunks);
+    if (parsed < 0) {
+        const size_t prefix = chunks.empty() ? 0 : chunks.back().out_off + chunks.back().n;
+        if (prefix > dst_cap) return -MLZ_ERR_DST_TOO_SMALL;
+        const int64_t r = prefix ? stream_decode_chunks(workers, k, ignore_crc, src, chunks, dst, prefix) : 0;
+        return r < 0 ? r : parsed;
+    }
+    if (size_t(parsed) > dst_cap) return -MLZ_ERR_DST_TOO_SMALL;
+    return stream_decode_chunks(workers, k, ignore_crc, src, chunks, dst, size_t(parsed));
+}
+
 }  // namespace
 
 extern "C" {
 
-int64_t mlz_stream_bound(uint64_t n, uint32_t block_size, uint32_t flags) {
-    if (block_size < kMinStreamBlock || block_size > kMaxBlockSize) return -MLZ_ERR_ARG;
-    return mlz_stream_bound_tables(n, block_size, flags, nullptr);
-}
-
-int64_t mlz_stream_bound_tables(uint64_t n, uint32_t block_size, uint32_t flags, const mlz_search_tables* cfg) {
-    if (block_size < kMinStreamBlock || block_size > kMaxBlockSize) return -MLZ_ERR_ARG;
-    StreamTables stb;
-    if (!stream_tables_config(flags, cfg, &stb)) return -MLZ_ERR_ARG;
-    return int64_t(stream_bound(n, block_size, (flags & MLZ_STREAM_ADD_INDEX) != 0, stb.T != 0, stb.flen()));
-}
-
-int64_t mlz_stream_bound_long_prefix(uint64_t n, uint32_t block_size, uint32_t flags, const mlz_search_long_prefix* cfg) {
-    if (block_size < kMinStreamBlock || block_size > kMaxBlockSize) return -MLZ_ERR_ARG;
-    StreamTables stb;
-    if (!stream_long_prefix_config(flags, cfg, &stb)) return -MLZ_ERR_ARG;
-    return int64_t(stream_bound(n, block_size, (flags & MLZ_STREAM_ADD_INDEX) != 0, true, stb.flen()));
-}
+int64_t mlz_stream_bound(uint64_t n, uint32_t block_size, uint32_t flags) { return stream_bound_checked(n, block_size, flags, stream_tables_config(flags, nullptr)); }
+int64_t mlz_stream_bound_tables(uint64_t n, uint32_t block_size, uint32_t flags, const mlz_search_tables* cfg) { return stream_bound_checked(n, block_size, flags, stream_tables_config(flags, cfg)); }
+int64_t mlz_stream_bound_long_prefix(uint64_t n, uint32_t block_size, uint32_t flags, const mlz_search_long_prefix* cfg) { return stream_bound_checked(n, block_size, flags, stream_long_prefix_config(flags, cfg)); }
 
 int64_t mlz_stream_encode(mlz_ctx* c, int level, uint32_t block_size, uint32_t flags, const uint8_t* src, size_t n, uint8_t* dst, size_t dst_cap) {
     if (!c || (!src && n) || !dst) return -MLZ_ERR_ARG;
@@ -863,166 +974,19 @@ int64_t mlz_stream_encode(mlz_ctx* c, int level, uint32_t block_size, uint32_t f
     return stream_encode_over(w.list, w.n, level, block_size, (flags & MLZ_STREAM_ADD_INDEX) != 0, src, n, dst, dst_cap);
 }
 
+// The device-resident Writer: each call converts its configuration; the arguments are checked in one place, stream_encode_gather_device_with
 int64_t mlz_stream_encode_gather_device(mlz_ctx* c, int level, uint32_t block_size, uint32_t flags, const uint8_t* const* d_src, const size_t* src_len,
                                         int n_ranges, uint8_t* d_dst, size_t dst_cap) {
-    return mlz_stream_encode_gather_device_tables(c, level, block_size, flags, nullptr, d_src, src_len, n_ranges, d_dst, dst_cap);
+    return stream_encode_gather_device_with(c, level, block_size, flags, stream_tables_config(flags, nullptr), d_src, src_len, n_ranges, d_dst, dst_cap);
 }
-
-}  // extern "C"
-
-namespace {
-int64_t stream_encode_gather_device_with(mlz_ctx* c, int level, uint32_t block_size, uint32_t flags, const StreamTables& stb, const uint8_t* const* d_src,
-                                         const size_t* src_len, int n_ranges, uint8_t* d_dst, size_t dst_cap);
-}
-
-extern "C" {
-
 int64_t mlz_stream_encode_gather_device_tables(mlz_ctx* c, int level, uint32_t block_size, uint32_t flags, const mlz_search_tables* cfg, const uint8_t* const* d_src,
                                                const size_t* src_len, int n_ranges, uint8_t* d_dst, size_t dst_cap) {
-    if (!c || !d_src || !src_len || n_ranges <= 0 || !d_dst) return -MLZ_ERR_ARG;
-    if (block_size < kMinStreamBlock || block_size > kMaxBlockSize) return -MLZ_ERR_ARG;
-    if (!valid_level(level)) return -MLZ_ERR_INVALID_LEVEL;
-    StreamTables stb;
-    if (!stream_tables_config(flags, cfg, &stb)) return -MLZ_ERR_ARG;
-    return stream_encode_gather_device_with(c, level, block_size, flags, stb, d_src, src_len, n_ranges, d_dst, dst_cap);
+    return stream_encode_gather_device_with(c, level, block_size, flags, stream_tables_config(flags, cfg), d_src, src_len, n_ranges, d_dst, dst_cap);
 }
-
 int64_t mlz_stream_encode_gather_device_long_prefix(mlz_ctx* c, int level, uint32_t block_size, uint32_t flags, const mlz_search_long_prefix* cfg,
                                                     const uint8_t* const* d_src, const size_t* src_len, int n_ranges, uint8_t* d_dst, size_t dst_cap) {
-    if (!c || !d_src || !src_len || n_ranges <= 0 || !d_dst) return -MLZ_ERR_ARG;
-    if (block_size < kMinStreamBlock || block_size > kMaxBlockSize) return -MLZ_ERR_ARG;
-    if (!valid_level(level)) return -MLZ_ERR_INVALID_LEVEL;
-    StreamTables stb;
-    if (!stream_long_prefix_config(flags, cfg, &stb)) return -MLZ_ERR_ARG;
-    return stream_encode_gather_device_with(c, level, block_size, flags, stb, d_src, src_len, n_ranges, d_dst, dst_cap);
+    return stream_encode_gather_device_with(c, level, block_size, flags, stream_long_prefix_config(flags, cfg), d_src, src_len, n_ranges, d_dst, dst_cap);
 }
-
-}  // extern "C"
-
-namespace {
-
-// The device-resident Writer behind mlz_stream_encode_gather_device, _tables and _long_prefix: arguments checked, stb the tables' configuration
-int64_t stream_encode_gather_device_with(mlz_ctx* c, int level, uint32_t block_size, uint32_t flags, const StreamTables& stb, const uint8_t* const* d_src,
-                                         const size_t* src_len, int n_ranges, uint8_t* d_dst, size_t dst_cap) {
-    const bool add_index = (flags & MLZ_STREAM_ADD_INDEX) != 0;
-    Workers w(c);
-    const size_t k = size_t(n_ranges);
-    // every range on the device that holds it; all but the last are whole blocks (a short block ends a stream)
-    std::vector<mlz_ctx*> own(k, nullptr);
-    std::vector<size_t> first(k + 1, 0);
-    size_t n = 0;
-    for (size_t j = 0; j < k; j++) {
-        if (src_len[j] && !d_src[j]) return -MLZ_ERR_ARG;
-        if (j + 1 < k && src_len[j] % block_size) return -MLZ_ERR_ARG;
-        first[j + 1] = first[j] + (src_len[j] + block_size - 1) / block_size;
-        n += src_len[j];
-        if (!src_len[j]) { own[j] = w.list[0]; continue; }
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, d_src[j]) != hipSuccess || at.type != hipMemoryTypeDevice) { (void)hipGetLastError(); return -MLZ_ERR_ARG; }
-        // the contexts on that device (one, unless the device was listed twice) take its ranges in turn
-        size_t on_dev = 0, earlier = 0;
-        for (size_t q = 0; q < w.n; q++) on_dev += w.list[q]->device == at.device ? 1 : 0;
-        if (!on_dev) return -MLZ_ERR_ARG;
-        for (size_t i = 0; i < j; i++) earlier += (src_len[i] && own[i]->device == at.device) ? 1 : 0;
-        for (size_t q = 0, hit = 0; q < w.n; q++)
-            if (w.list[q]->device == at.device && hit++ == earlier % on_dev) own[j] = w.list[q];
-    }
-    hipPointerAttribute_t dat;
-    if (hipPointerGetAttributes(&dat, d_dst) != hipSuccess || dat.type != hipMemoryTypeDevice) { (void)hipGetLastError(); return -MLZ_ERR_ARG; }
-    const int dst_dev = dat.device;
-    if (dst_cap < stream_bound(n, block_size, add_index, stb.T != 0, stb.flen())) return -MLZ_ERR_DST_TOO_SMALL;
-    // search tables: a range's last block indexes windows that run into the next non-empty range, whose first bytes (M - 1, with a prefix table M: 8 at the most) the host hands over
-    std::vector<uint64_t> next_bytes(k, 0);
-    std::vector<uint32_t> next_n(k, 0);
-    // table type 4: up to K - 1 + M + E bytes, gathered across as many following ranges as it takes
-    const uint32_t long_need = stb.T == 4 ? stb.overlap() : 0;
-    std::vector<uint8_t> long_tail(long_need ? k * size_t(long_need) : 0, 0);
-    if (long_need)
-        for (size_t j = 0; j + 1 < k; j++) {
-            if (!src_len[j]) continue;
-            for (size_t q = j + 1; q < k && next_n[j] < long_need; q++) {
-                const size_t take = std::min<size_t>(long_need - next_n[j], src_len[q]);
-                if (!take) continue;
-                if (hipSetDevice(own[q]->device) != hipSuccess ||
-                    hipMemcpy(long_tail.data() + j * size_t(long_need) + next_n[j], d_src[q], take, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
-                next_n[j] += uint32_t(take);
-            }
-        }
-    else if (stb.T && stb.overlap())
-        for (size_t j = 0; j + 1 < k; j++) {
-            size_t q = j + 1;
-            while (q < k && !src_len[q]) q++;
-            if (q == k || !src_len[j]) continue;
-            next_n[j] = uint32_t(std::min<size_t>(stb.T == 1 ? 7 : 8, src_len[q]));
-            if (hipSetDevice(own[q]->device) != hipSuccess || hipMemcpy(&next_bytes[j], d_src[q], next_n[j], hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
-        }
-    const size_t nblk = first[k];
-    std::vector<uint32_t> framed(nblk, 0);
-    StreamEncShared sh(k);
-    std::vector<int64_t> rcs(k, 0);
-    // two ranges may share a context (more ranges than contexts on a device): they queue on its lock in range order — the base_of() hand-over
-    // only ever waits for LOWER ranges, which hold or have held the lock first when threads start in order; to be safe against any start order a
-    // context's ranges run on ONE thread, lowest first
-    std::vector<std::vector<size_t>> by_ctx;
-    std::vector<mlz_ctx*> ctxs;
-    for (size_t j = 0; j < k; j++) {
-        size_t q = 0;
-        while (q < ctxs.size() && ctxs[q] != own[j]) q++;
-        if (q == ctxs.size()) { ctxs.push_back(own[j]); by_ctx.emplace_back(); }
-        by_ctx[q].push_back(j);
-    }
-    auto work = [&](size_t q) {
-        mlz_ctx* kc = ctxs[q];
-        std::lock_guard<std::mutex> lk(kc->mu);
-        for (size_t j : by_ctx[q]) {
-            rcs[j] = stream_gather_range(kc, level, block_size, d_src[j], src_len[j], first[j], d_dst, dst_dev, n > 0, &sh, j, framed.data(), stb, next_bytes[j], next_n[j],
-                                         long_need ? long_tail.data() + j * size_t(long_need) : nullptr);
-            if (rcs[j]) { sh.fail(); (void)hipStreamSynchronize(kc->stream); }
-        }
-    };
-    std::vector<std::thread> th;
-    for (size_t q = 1; q < ctxs.size(); q++) th.emplace_back(work, q);
-    work(0);
-    for (std::thread& t : th) t.join();
-    int64_t rc = 0;
-    for (size_t j = 0; j < k && rc == 0; j++) if (rcs[j] && rcs[j] != -MLZ_ERR_HIP) rc = rcs[j];
-    for (size_t j = 0; j < k && rc == 0; j++) rc = rcs[j];
-    if (rc) { std::lock_guard<std::mutex> lk(c->mu); for (size_t j = 0; j < k; j++) if (rcs[j] == rc) { c->err = own[j]->err; break; } return rc; }
-    // stream header, EOF chunk and index: a few bytes from the host (writer.go:463-467, :1063-1122)
-    mlz_ctx* c0 = w.list[0];
-    std::lock_guard<std::mutex> lk(c0->mu);
-    HIPCHK(c0, hipSetDevice(dst_dev));
-    SeekIndex index;
-    index.reset(block_size);
-    size_t o = 0;
-    uint8_t head[17 + mlz::kSearchMaxField];
-    if (n > 0) {
-        std::memcpy(head, kMagicChunk, 9);
-        head[9] = uint8_t((32 - __builtin_clz(block_size - 1)) - 10);
-        o = 10;
-        if (stb.T) {   // the info chunk: 44 len24 | T M B | prefix field
-            const uint32_t ilen = 3 + stb.flen();
-            const uint8_t info[7] = {mlz::kChunkSearchInfo, uint8_t(ilen), uint8_t(ilen >> 8), 0, uint8_t(stb.T), uint8_t(stb.M), uint8_t(mlz::search_table_bits(block_size))};
-            std::memcpy(head + 10, info, 7);
-            std::memcpy(head + 17, stb.field, stb.flen());
-            o = 17 + stb.flen();
-        }
-        HIPCHK(c0, hipMemcpy(d_dst, head, o, hipMemcpyHostToDevice));
-        index.add(0, 0);
-    }
-    for (size_t i = 0; i < nblk; i++) { index.add(int64_t(o), int64_t(i * size_t(block_size))); o += framed[i]; }
-    std::vector<uint8_t> tail(16 + (add_index ? SeekIndex::bound(nblk) : 0));
-    const size_t vn = put_uvarint64(tail.data() + 4, n);
-    tail[0] = kChunkEOF; tail[1] = uint8_t(vn); tail[2] = 0; tail[3] = 0;
-    size_t t = 4 + vn;
-    if (add_index) t += index.append_to(tail.data() + t, int64_t(n), int64_t(o + t));
-    HIPCHK(c0, hipMemcpy(d_dst + o, tail.data(), t, hipMemcpyHostToDevice));
-    return int64_t(o + t);
-}
-
-}  // namespace
-
-extern "C" {
 
 int64_t mlz_stream_decoded_len(const uint8_t* src, size_t n) {
     if (!src && n) return -MLZ_ERR_ARG;

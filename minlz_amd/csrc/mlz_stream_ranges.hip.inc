@@ -18,7 +18,7 @@ namespace mlz {
 constexpr uint32_t kRangeShortMax = MLZ_RANGE_SHORT_MAX;
 constexpr uint32_t kRangeShortPerWg = 16;   // 256 threads / 16 lanes
 
-// descs[0, n_long): a workgroup per piece (wg_copy, as stream_place2_kernel); descs[n_long, n_all): 16 lanes per piece.  desc.pad selects the
+// descs[0, n_long): a workgroup per piece (wg_copy, as stream_place_kernel); descs[n_long, n_all): 16 lanes per piece.  desc.pad selects the
 // source (0 = the scratch, 1 = the stream: stored chunks).  The short form stores destination-aligned 16-byte vectors, lane i of a piece's
 // 16 at aligned base + 16 i (+ 256 per further round); the ragged first and last vector are written bytewise by their lane; a full vector's
 // 16 source bytes are loaded from where they lie, at whatever alignment, so no byte outside the piece is read or written.

@@ -314,7 +314,7 @@ int64_t dev_reader_search_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t fl
     if (np) HIPCHK(c, hipMemcpyAsync(c->d_place.p, h_places, np * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
     auto scan_group = [&](size_t g) -> int {
         const size_t t0 = g ? tile_end[g - 1] : 0, t1 = tile_end[g], q0 = g ? place_end[g - 1] : 0, q1 = place_end[g];
-        if (q1 > q0) hipLaunchKernelGGL(stream_place2_kernel, dim3(uint32_t(q1 - q0)), dim3(256), 0, sm, rd->d_src, rd->d_src, scratch, c->d_place.as<PlaceDesc>() + q0);
+        if (q1 > q0) hipLaunchKernelGGL(stream_place_kernel, dim3(uint32_t(q1 - q0)), dim3(256), 0, sm, rd->d_src, rd->d_src, nullptr, scratch, c->d_place.as<PlaceDesc>() + q0);
         if (t1 > t0) hipLaunchKernelGGL(mlz::search_scan_kernel, dim3(uint32_t(t1 - t0)), dim3(256), 0, sm, scratch, d_tiles, uint32_t(t0), ws, L, d_masks, d_counts);
         if (carry[g]) {   // the run goes on in the next group: its last bytes in front of that group's first chunk
             HIPCHK(c, hipMemcpyAsync(ws + r_carry.off, scratch + used[g] - carry[g], carry[g], hipMemcpyDeviceToDevice, sm));

@@ -364,7 +364,7 @@ int64_t stream_decode_chunks_device(mlz_ctx* c, hipStream_t sm, bool ignore_crc,
         for (const StreamChunk& ck : chunks)
             if (ck.type == kChunkUncompressed) place_pieces(ck.body_off, ck.out_off, ck.n, 0, [&](const PlaceDesc& d) { h_place[q++] = d; });
         HIPCHK(c, hipMemcpyAsync(c->d_place.p, h_place, n_place * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
-        hipLaunchKernelGGL(stream_place2_kernel, dim3(uint32_t(n_place)), dim3(256), 0, sm, d_src, d_src, d_dst, c->d_place.as<PlaceDesc>());
+        hipLaunchKernelGGL(stream_place_kernel, dim3(uint32_t(n_place)), dim3(256), 0, sm, d_src, nullptr, nullptr, d_dst, c->d_place.as<PlaceDesc>());
     }
     std::vector<ChunkJob> jobs(nck);
     for (size_t i = 0; i < nck; i++) jobs[i] = ChunkJob{i, d_dst + chunks[i].out_off};

@@ -14,11 +14,11 @@ import oracle as O
 from minlz_amd import _lib, shard, stream as S, synth
 from tests import search_cases as SC
 from tests import search_tables as ST
+from tests.search_gpu import SENT, data_for, gather_into
 
 pytestmark = pytest.mark.gpu
 
 MLZ_ERR_ARG = 8
-SENT = 0x5A5A5A5A5A5A5A5A
 
 
 def gather(ctx, parts, level, bs, add_index, M):
@@ -27,21 +27,7 @@ def gather(ctx, parts, level, bs, add_index, M):
     n = sum(len(p) for p in parts)
     flags = (1 if add_index else 0) | (0 if M is None else 4 | (M << 8))
     cap = L.mlz_stream_bound(n, bs, flags)
-    assert cap > 0
-    srcs = [torch.from_numpy(np.frombuffer(p, np.uint8).copy()).cuda() if len(p) else torch.empty(0, dtype=torch.uint8, device="cuda") for p in parts]
-    dst = torch.full((cap + 64,), 0x5A, dtype=torch.uint8, device="cuda")
-    got = ctx.stream_encode_gather_device(level, bs, add_index, [t.data_ptr() if t.numel() else None for t in srcs], [t.numel() for t in srcs], dst.data_ptr(), cap,
-                                          search_match_len=M)
-    o = dst.cpu().numpy()
-    assert got <= cap and (o[cap:] == 0x5A).all()
-    return o[:got].tobytes()
-
-
-def data_for(kind, bs, nblk, tail, seed=4, random_block=1):
-    d = bytearray(getattr(synth, kind)(bs * nblk + tail, seed).tobytes())
-    if random_block is not None:
-        d[random_block * bs:(random_block + 1) * bs] = synth.random_bytes(bs, seed=6).tobytes()
-    return bytes(d)
+    return gather_into(ctx, parts, cap, level, bs, add_index, search_match_len=M)
 
 
 def check_stream(ctx, stream, d, bs, M, add_index, what):

@@ -17,17 +17,13 @@ from tests import search_cases as SC
 from tests import search_long_prefix_cases as LC
 from tests import search_long_prefix_tables as SL
 from tests import search_prefix_cases as PC
+from tests.search_gpu import SENT, Searcher, data_for, first_difference, gather_into, on_device
 
 pytestmark = pytest.mark.gpu
 
 MLZ_ERR_ARG = 8
-SENT = 0x5A5A5A5A5A5A5A5A
 FILL = ord("a")
 ME = [(6, 0), (6, 3), (8, 8), (1, 15)]
-
-
-def on_device(parts):
-    return [torch.from_numpy(np.frombuffer(p, np.uint8).copy()).cuda() if len(p) else torch.empty(0, dtype=torch.uint8, device="cuda") for p in parts]
 
 
 def gather(ctx, parts, bs, add_index, M=None, pfx=None, E=0, level=1):
@@ -40,18 +36,8 @@ def gather(ctx, parts, bs, add_index, M=None, pfx=None, E=0, level=1):
         cap = L.mlz_stream_bound(n, bs, idx)
     else:
         cap = L.mlz_stream_bound_long_prefix(n, bs, idx, C.byref(search_long_prefix_config(M, pfx, E)))
-    assert cap > 0
-    srcs = on_device(parts)
-    dst = torch.full((cap + 64,), 0x5A, dtype=torch.uint8, device="cuda")
     kw = {} if pfx is None else dict(search_match_len=M, search_long_prefix=pfx, search_extras=E)
-    got = ctx.stream_encode_gather_device(level, bs, add_index, [t.data_ptr() if t.numel() else None for t in srcs], [t.numel() for t in srcs], dst.data_ptr(), cap, **kw)
-    o = dst.cpu().numpy()
-    assert got <= cap and (o[cap:] == 0x5A).all()
-    return o[:got].tobytes()
-
-
-def first_difference(a, b):
-    return next((i for i in range(min(len(a), len(b))) if a[i] != b[i]), min(len(a), len(b)))
+    return gather_into(ctx, parts, cap, level, bs, add_index, **kw)
 
 
 def writer_case(ctx, d, bs, M, E, pfx, add_index=False, cuts=None, what=""):
@@ -67,13 +53,6 @@ def writer_case(ctx, d, bs, M, E, pfx, add_index=False, cuts=None, what=""):
     assert SL.read_tables(on) == (4, M, B, field, tables), what
     assert mz.stream_decode(on, ctx=ctx) == d and O.stream_decode(on, len(d)) == d, what
     return on, tables
-
-
-def data_for(kind, bs, nblk, tail, seed=4, random_block=1):
-    d = bytearray(getattr(synth, kind)(bs * nblk + tail, seed).tobytes())
-    if random_block is not None:
-        d[random_block * bs:(random_block + 1) * bs] = synth.random_bytes(bs, seed=6).tobytes()
-    return bytes(d)
 
 
 def popcount(table):
@@ -303,27 +282,6 @@ def test_writer_arguments(ctx):
 
 
 # ---- search ----
-
-class Searcher:
-    def __init__(self, ctx, stream):
-        self.ctx = ctx
-        self.t = torch.from_numpy(np.frombuffer(stream, np.uint8).copy()).cuda()
-        self.rd = ctx.stream_open_device(self.t.data_ptr(), len(stream))
-
-    def __call__(self, pattern, cap, **kw):
-        """-> (total, positions, stats); checks that nothing beyond min(total, cap) was written."""
-        out = torch.full((cap + 8,), SENT, dtype=torch.int64, device="cuda")
-        total, stats = self.rd.search(pattern, out.data_ptr(), cap, **kw)
-        torch.cuda.synchronize()
-        o = out.cpu().numpy()
-        k = min(total, cap)
-        assert (o[k:] == SENT).all(), "written beyond the results"
-        assert self.ctx.search_plan() == stats[1:]
-        return total, o[:k].tolist(), stats
-
-    def close(self):
-        self.rd.close()
-
 
 def check_search(sr, stream, d, pattern, what, cap=None, ignore_crc=False):
     want = SL.brute(d, pattern)
