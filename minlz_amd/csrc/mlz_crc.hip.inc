@@ -2,16 +2,13 @@
 //
 // Replaces crc() of the reference (minlz.go:133-140: Castagnoli CRC, rotate by 15, add
 // 0xa282ead8), which the stream Writer/Reader compute per block over the UNCOMPRESSED bytes
-// (writer.go:887, reader.go:341-351).  CRCs are linear, so a block is cut into 1 KiB pieces, one
-// per lane; each lane runs the byte-wise table CRC over its piece (256-entry table in LDS), multiplies
-// the result by x^(8 * bytes_after_me) mod P (square-and-multiply over a table of x^(2^k)), and the
-// pieces are XOR-reduced:  crc(A || B) = crc(A) * x^(8|B|) xor crc(B).
+// (writer.go:887, reader.go:341-351).  CRCs are linear, so a block is cut into pieces; each piece's
+// table CRC is multiplied by x^(8 * bytes_after_it) mod P (constants from tables, or square-and-multiply
+// over a table of x^(2^k)), and the pieces are XOR-reduced:  crc(A || B) = crc(A) * x^(8|B|) xor crc(B).
 
 namespace mlz {
 
 constexpr uint32_t kCrcPoly = 0x82f63b78u;  // reflected Castagnoli polynomial
-constexpr uint32_t kCrcPiece = 1024;        // bytes per lane
-constexpr uint32_t kCrcGroup = 256 * kCrcPiece;  // bytes per workgroup
 
 struct CrcPow { uint32_t x2n[32]; };  // x^(2^k) mod P, reflected (bit 31 = x^0)
 
@@ -127,47 +124,6 @@ __global__ __launch_bounds__(64) void crc_block_kernel(const BlockInfo* __restri
         c = acc ^ tile_crc[b.first_tile + last];
     }
     if (lane == 0) out[bi] = ((c >> 15) | (c << 17)) + 0xa282ead8u;
-}
-
-__global__ __launch_bounds__(256) void crc_kernel(const uint8_t* __restrict__ base, const BlockInfo* __restrict__ blocks, CrcPow pw,
-                                                  uint32_t* __restrict__ out /* zero-initialised, one word per block */) {
-    __shared__ uint32_t tab[256];
-    const int tid = threadIdx.x;
-    {
-        uint32_t c = uint32_t(tid);
-        for (int k = 0; k < 8; k++) c = (c & 1) ? (c >> 1) ^ kCrcPoly : c >> 1;
-        tab[tid] = c;
-    }
-    __syncthreads();
-    const BlockInfo b = blocks[blockIdx.y];
-    const uint64_t start = uint64_t(blockIdx.x) * kCrcGroup + uint64_t(tid) * kCrcPiece;
-    if (start >= b.src_len) return;
-    const uint64_t n = b.src_len - start < kCrcPiece ? b.src_len - start : kCrcPiece;
-    const uint8_t* p = base + b.src_off + start;
-    uint32_t c = 0xffffffffu;
-    uint64_t i = 0;
-    for (; i + 8 <= n; i += 8) {
-        uint64_t w;
-        __builtin_memcpy(&w, p + i, 8);
-#pragma unroll
-        for (int k = 0; k < 8; k++) { c = tab[(c ^ uint32_t(w)) & 0xff] ^ (c >> 8); w >>= 8; }
-    }
-    for (; i < n; i++) c = tab[(c ^ p[i]) & 0xff] ^ (c >> 8);
-    c = ~c;
-    const uint64_t after = b.src_len - start - n;
-    if (after) c = crc_mulmod(crc_x2n(pw, after, 3), c);
-    // xor-reduce within the wave, then one atomic per wave
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c ^= __shfl_xor(c, d);
-    if ((tid & 63) == 0) atomicXor(&out[blockIdx.y], c);
-}
-
-// out[i] = (c >> 15 | c << 17) + 0xa282ead8  (minlz.go:139)
-__global__ void crc_mask_kernel(uint32_t* __restrict__ out, int n) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t c = out[i];
-    out[i] = ((c >> 15) | (c << 17)) + 0xa282ead8u;
 }
 
 }  // namespace mlz

@@ -106,7 +106,6 @@ struct mlz_ctx {
     std::vector<SingleReq*> q_pending;
     bool q_leader = false;
     uint64_t q_batches = 0, q_requests = 0;  // mlz_get_counter
-    void* last_gen = nullptr;                // GenCtl of the last decode call's last group (device memory)
     uint64_t acc_call = 0;                   // the decode call (dec_call) whose first schedule kernel has reset d_gen_acc
     uint64_t dec_call = 0;                   // call_seq at the start of the last decode API call: its host groups, stream groups and internal groups share it
     std::string err;
@@ -141,9 +140,7 @@ struct mlz_ctx {
     bool ws_recorded = false;   // mlz_release_stream: ws_done already covers the last call (its stream may be gone by the next one)
     // encode workspace
     DevBuf d_scratch, d_tile_size, d_tile_out, d_flags, d_far, d_recs, d_piece_cnt, d_farbin;
-    bool farbin_attr = false;
     DevBuf d_stab;               // the device-resident Writer's block search tables: 2^(B - 3) bytes per block of a range, 8 bytes of verdict each
-    bool stab_attr = false;
     // decode workspace
     DevBuf d_dec, d_idx;
     DevBuf d_walk, d_walk_tab;   // the device-resident Reader's chunk walk: exit tables (8 bytes per stream byte) and the chunk table
@@ -166,7 +163,6 @@ struct mlz_ctx {
     int gen_force_packed = 0;  // tests: every tile of a general block takes the byte-packed pool (the fallback path)
     int fold_layout = 1;       // option 24: the encode layout rides in the gather kernel when every block of the group has tiles and room (0: always encode_layout_kernel)
     int level0_by_e = 1;       // option 23: few level-0 tiles are decoded by dec_level0_kernel before the exec pass (0: by the exec pass, rounds 2-5)
-    bool l0_attr = false;
     int fuse_ser = 1;          // option 21: the match kernel serializes its pieces itself (0: serialize_pieces_kernel, rounds 2-5; cross-checks)
     // host-pointer staging
     DevBuf d_in, d_out, d_len, d_crc, d_crc_tabs, d_crc_tiles;
@@ -178,12 +174,18 @@ struct mlz_ctx {
     // options
     int decode_algo = 0;
     int encode_far = 1;
-    bool enc_attrs = false, far_attr = false, dec_attrs = false, gen_attr = false;  // per device: dynamic-LDS limits raised
+    bool enc_attrs = false, far_attr = false, farbin_attr = false, stab_attr = false, dec_attrs = false, gen_attr = false, l0_attr = false;  // per device: dynamic-LDS limits raised (raise_lds_once)
     uint32_t timer_mask = 0xffffffffu;  // timers that record events (an event pair costs ~10 us of idle device per kernel boundary)
     int timing = 0;  // 0 off, 1 = the last call's kernel times, 2 = running mean over the calls since it was enabled (no sync per call)
     int debug_status = 0;
     bool prof_on = false;
     DevBuf d_prof;
+    // Every DevBuf above, once, by side: 0 = what mlz_get_counter 3 sums (encode), 1 = counter 4 (decode), 2 = the rest; mlz_destroy frees all three.  A buffer added to the struct is added here.
+    std::vector<DevBuf*> bufs(int side) {
+        if (side == 0) return {&d_scratch, &d_tile_size, &d_tile_out, &d_flags, &d_far, &d_recs, &d_piece_cnt, &d_farbin, &d_stab};
+        if (side == 1) return {&d_dec, &d_idx, &d_walk, &d_walk_tab, &d_range, &d_rplan};
+        return {&d_blocks_k[0], &d_blocks_k[1], &d_tile_block_k[0], &d_tile_block_k[1], &d_seg_block_k[0], &d_seg_block_k[1], &d_place, &d_gen_acc, &d_in, &d_out, &d_len, &d_crc, &d_crc_tabs, &d_crc_tiles, &d_prof};
+    }
     // A ring of event pairs per timer, resolved kTimerRing uses later (long complete by then), so reading the clock never stalls the caller and
     // launches can run ahead of the device.  A device batch runs as one or more internal groups, each firing the timers: acc_ms sums them and
     // ev_calls counts the API calls a timer fired in.  timing == 1 restarts a timer's sum at the first firing of a new call (the last call's
@@ -335,159 +337,176 @@ template <class F> int for_each_group(mlz_ctx* c, const mlz_block_desc* desc, in
     return 0;
 }
 
-int encode_device_group(mlz_ctx* c, hipStream_t st, int level, const uint8_t* d_src, uint8_t* d_dst, const mlz_block_desc* desc, int n,
-                        int64_t* d_out_len, bool with_header, const uint64_t* mirror) {
-    uint32_t tiles = 0;
-    int r = upload_blocks(c, st, desc, n, false, &tiles, nullptr, mirror);
-    if (r) return r;
-    // Every level goes through the match + serialize kernels on 8 KiB pieces (mlz_encode2.hip.inc); LevelBalanced is their
-    // configuration with larger near tables, denser far tables and a second far probe (kL2*).
-    const bool l2new = level == MLZ_LEVEL_BALANCED;
-    const uint32_t sub_log = kSubLog;
-    const size_t units = size_t(tiles) << sub_log;
-    HIPCHK(c, c->d_tile_size.ensure(sizeof(uint32_t) * (units + 1)));
-    HIPCHK(c, c->d_tile_out.ensure(sizeof(uint32_t) * (units + 1)));
-    HIPCHK(c, c->d_flags.ensure(sizeof(uint32_t) * n));
-    const BlockInfo* blocks = c->d_blocks_cur().as<BlockInfo>();
-    const uint32_t* tile_block = c->d_tile_block_cur().as<uint32_t>();
-    if (level != MLZ_LEVEL_UNCOMPRESSED && tiles > 0) {
-        HIPCHK(c, c->d_scratch.ensure(units * kPieceScratch));
-        uint64_t maxlen = 0;
-        for (int i = 0; i < n; i++) maxlen = std::max<uint64_t>(maxlen, std::min<uint64_t>(desc[i].src_len, kMaxBlockSize));
-        const uint32_t epochs = uint32_t((maxlen + (1u << kEpochLog) - 1) >> kEpochLog);
-        // LevelBalanced: far matching forced on, both epochs probed and a cost-aware lazy parse (DESIGN.md "Levels").
-        // LevelSuperFast: tile-local matches only (no far tables are built or probed).
-        const bool far = ((c->encode_far && level != MLZ_LEVEL_SUPERFAST) || level == MLZ_LEVEL_BALANCED) && maxlen > kTile;
-        const uint32_t pattern = (level == MLZ_LEVEL_BALANCED && c->l2_free) ? kPatternFree : level_pattern_of(level);   // LevelBalanced: dense (four levels); the faster levels: three (DESIGN.md "Tile levels"); the decoder knows both and round 1's kPatternFast
-        bool any_big = false, any_small = false;
-        for (int i = 0; i < n; i++) (std::min<uint64_t>(desc[i].src_len, kMaxBlockSize) >= kM2BigBlock ? any_big : any_small) = true;
-        if (!c->enc_attrs) {  // per context = per device
-            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(match_tiles_kernel<true, MLZ_M2_NW, kM2HashBitsBig>), hipFuncAttributeMaxDynamicSharedMemorySize, M2Cfg<kM2HashBitsBig>::kLds));
-            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(match_tiles_kernel<true, MLZ_M2_NW, kM2HashBitsSmall, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, M2Cfg<kM2HashBitsSmall>::kLds));
-            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(match_tiles_kernel<false, MLZ_M2_NW, kM2HashBitsBig>), hipFuncAttributeMaxDynamicSharedMemorySize, M2Cfg<kM2HashBitsBig>::kLds));
-            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(match_tiles_kernel<false, MLZ_M2_NW, kM2HashBitsSmall>), hipFuncAttributeMaxDynamicSharedMemorySize, M2Cfg<kM2HashBitsSmall>::kLds));
-            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(match_tiles_kernel<false, MLZ_M2_NW, kM2HashBitsSuperFast>), hipFuncAttributeMaxDynamicSharedMemorySize, M2Cfg<kM2HashBitsSuperFast>::kLds));
-            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(match_tiles_kernel<true, MLZ_M2_NW, kM2HashBitsSmall, kL2FarBits, true>), hipFuncAttributeMaxDynamicSharedMemorySize, M2Cfg<kM2HashBitsSmall>::kLds));
-            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(match_tiles_kernel<true, MLZ_M2_NW, kM2HashBitsSmall, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, M2Cfg<kM2HashBitsSmall>::kLds));
-            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(match_tiles_kernel<false, MLZ_M2_NW, kM2HashBitsSmall, kL2FarBits, true>), hipFuncAttributeMaxDynamicSharedMemorySize, M2Cfg<kM2HashBitsSmall>::kLds));
-            c->enc_attrs = true;
-        }
-        // LevelFastest: blocks below 1 MiB have far tables that go with their length (small_far_bits); the tables of a batch
-        // are as far apart as its largest block needs
-        const int fbits = any_big ? (l2new ? kL2FarBits : kFarBits) : small_far_bits(maxlen) + (l2new ? 1 : 0);
-        if (far) {
-            Timer t(c, T_FAR, st);
-            const size_t words = (size_t(n) * far_sets(pattern) * epochs) << fbits;
-            HIPCHK(c, c->d_far.ensure(words * 4));
-            if (!c->far_attr) {
-                HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(far_build_kernel<kFarBits, kFarStride>), hipFuncAttributeMaxDynamicSharedMemorySize, 4u << kFarSliceBits));
-                HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(far_build_kernel<0, kFarStride>), hipFuncAttributeMaxDynamicSharedMemorySize, 4u << kFarSliceBits));
-                HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(far_build_kernel<0, kL2FarStride>), hipFuncAttributeMaxDynamicSharedMemorySize, 4u << kFarSliceBits));
-                HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(far_build_kernel<kL2FarBits, kL2FarStride>), hipFuncAttributeMaxDynamicSharedMemorySize, 4u << kFarSliceBits));
-                c->far_attr = true;
-            }
-            if (any_big) {
-                if (l2new && pattern == kPatternFree && !c->far_slices_l2) {
-                    // no level sets: the windows sorted by slice once (far_bin_kernel), every slice workgroup reads its eighth (far_slice_kernel)
-                    using FBn = FarBin<kL2FarBits, kL2FarStride>;
-                    const size_t units2 = size_t(tiles) * 2;
-                    HIPCHK(c, c->d_farbin.ensure(units2 * FBn::kPerUnit * 4 + units2 * FBn::kOffs * 4 + 256));
-                    uint32_t* bins = c->d_farbin.as<uint32_t>();
-                    uint32_t* binoff = bins + units2 * FBn::kPerUnit;
-                    constexpr uint32_t kSliceLds = (4u << kBinSliceBits) + 256 * 4 + 132 * 4;
-                    if (!c->farbin_attr) {
-                        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(far_bin_kernel<kL2FarBits, kL2FarStride>), hipFuncAttributeMaxDynamicSharedMemorySize, FBn::kLds));
-                        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(far_slice_kernel<kL2FarBits, kL2FarStride>), hipFuncAttributeMaxDynamicSharedMemorySize, kSliceLds));
-                        c->farbin_attr = true;
-                    }
-                    hipLaunchKernelGGL((far_bin_kernel<kL2FarBits, kL2FarStride>), dim3(uint32_t(units2)), dim3(256), FBn::kLds, st, d_src, blocks, tile_block, bins, binoff);
-                    hipLaunchKernelGGL((far_slice_kernel<kL2FarBits, kL2FarStride>), dim3(FBn::kSlices, epochs, n), dim3(1024), kSliceLds, st, blocks,
-                                       bins, binoff, c->d_far.as<uint32_t>(), epochs);
-                } else if (l2new)
-                    hipLaunchKernelGGL((far_build_kernel<kL2FarBits, kL2FarStride>), dim3(far_slices(kL2FarBits), epochs, n), dim3(1024), 4u << kFarSliceBits, st, d_src,
-                                       blocks, c->d_far.as<uint32_t>(), epochs, pattern, uint32_t(fbits), any_small ? 1u : 2u);
-                else
-                    hipLaunchKernelGGL((far_build_kernel<kFarBits, kFarStride>), dim3(far_slices(kFarBits), epochs, n), dim3(1024), 4u << kFarSliceBits, st, d_src,
-                                       blocks, c->d_far.as<uint32_t>(), epochs, pattern, uint32_t(fbits), any_small ? 1u : 2u);
-            }
-            if (any_small) {
-                uint64_t max_small = 0;
-                for (int i = 0; i < n; i++) if (desc[i].src_len < kBigBlock) max_small = std::max<uint64_t>(max_small, desc[i].src_len);
-                const int sb = small_far_bits(max_small) + (l2new ? 1 : 0);
-                const uint32_t lds = 4u << std::min<int>(sb, kFarSliceBits);   // small tables leave room for more workgroups per CU
-                const dim3 grid(1u << (std::max<int>(sb, kFarSliceBits) - kFarSliceBits), 1, n);
-                if (l2new)
-                    hipLaunchKernelGGL((far_build_kernel<0, kL2FarStride>), grid, dim3(1024), lds, st, d_src, blocks, c->d_far.as<uint32_t>(), epochs, pattern,
-                                       uint32_t(fbits), any_big ? 0u : 2u);
-                else
-                    hipLaunchKernelGGL((far_build_kernel<0, kFarStride>), grid, dim3(1024), lds, st, d_src, blocks, c->d_far.as<uint32_t>(), epochs, pattern,
-                                       uint32_t(fbits), any_big ? 0u : 2u);
-            }
-        }
-        const uint32_t* ftab = far ? c->d_far.as<uint32_t>() : nullptr;
-        // LevelBalanced without levels: far sources at least l2_gap tiles back (MLZ_OPT_L2_GAP)
-        const uint32_t far_gap = pattern == kPatternFree && level == MLZ_LEVEL_BALANCED ? uint32_t(c->l2_gap - 1) << kTileLog : 0u;
-        {
-            HIPCHK(c, c->d_recs.ensure(units * kRecPerPiece * sizeof(uint2)));
-            HIPCHK(c, c->d_piece_cnt.ensure(units * sizeof(uint32_t)));
-            // the match kernel's waves serialize their pieces themselves (option 21, default on); else serialize_pieces_kernel below
-            uint8_t* fuse_scratch = c->fuse_ser ? c->d_scratch.as<uint8_t>() : nullptr;
-            {
-                Timer t(c, T_ENC_TILES, st);
-                const uint32_t grid = ((tiles + 7) / 8) * 8;  // whole rounds of the eight XCDs (see the kernel's workgroup -> tile map)
-#define MLZ_LAUNCH_M2(F, HB, CLS, ...)                                                                                                       \
-    hipLaunchKernelGGL((match_tiles_kernel<F, MLZ_M2_NW, HB, ##__VA_ARGS__>), dim3(grid), dim3(256), M2Cfg<HB>::kLds, st, d_src, blocks, tile_block,        \
-                       c->d_recs.as<uint2>(), c->d_piece_cnt.as<uint32_t>(), ftab, epochs, pattern, tiles, uint32_t(CLS), uint32_t(fbits), far_gap, fuse_scratch, c->d_tile_size.as<uint32_t>())
-                if (level == MLZ_LEVEL_SUPERFAST) MLZ_LAUNCH_M2(false, kM2HashBitsSuperFast, 2);
-                else if (l2new && far) {
-                    // the same kernel for both block classes, with far tables of the level's size or of the block's
-                    if (any_big)
-                        hipLaunchKernelGGL((match_tiles_kernel<true, MLZ_M2_NW, kM2HashBitsSmall, kL2FarBits, true>), dim3(grid), dim3(256), M2Cfg<kM2HashBitsSmall>::kLds,
-                                           st, d_src, blocks, tile_block, c->d_recs.as<uint2>(), c->d_piece_cnt.as<uint32_t>(), ftab, epochs, pattern, tiles,
-                                           any_small ? 1u : 2u, uint32_t(fbits), far_gap, fuse_scratch, c->d_tile_size.as<uint32_t>());
-                    if (any_small)
-                        hipLaunchKernelGGL((match_tiles_kernel<true, MLZ_M2_NW, kM2HashBitsSmall, 0, true>), dim3(grid), dim3(256), M2Cfg<kM2HashBitsSmall>::kLds, st,
-                                           d_src, blocks, tile_block, c->d_recs.as<uint2>(), c->d_piece_cnt.as<uint32_t>(), ftab, epochs, pattern, tiles,
-                                           any_big ? 0u : 2u, uint32_t(fbits), far_gap, fuse_scratch, c->d_tile_size.as<uint32_t>());
-                }
-                else if (l2new)   // blocks of one tile: no far tables, but the same near-table seeding as the level's other blocks
-                    hipLaunchKernelGGL((match_tiles_kernel<false, MLZ_M2_NW, kM2HashBitsSmall, kL2FarBits, true>), dim3(grid), dim3(256), M2Cfg<kM2HashBitsSmall>::kLds, st,
-                                       d_src, blocks, tile_block, c->d_recs.as<uint2>(), c->d_piece_cnt.as<uint32_t>(), ftab, epochs, pattern, tiles, 2u, uint32_t(fbits), far_gap, fuse_scratch, c->d_tile_size.as<uint32_t>());
-                else {
-                    // one launch per block class that occurs in the batch (usually one)
-                    if (any_big) { if (far) MLZ_LAUNCH_M2(true, kM2HashBitsBig, any_small ? 1 : 2); else MLZ_LAUNCH_M2(false, kM2HashBitsBig, any_small ? 1 : 2); }
-                    if (any_small) { if (far) MLZ_LAUNCH_M2(true, kM2HashBitsSmall, any_big ? 0 : 2, 0); else MLZ_LAUNCH_M2(false, kM2HashBitsSmall, any_big ? 0 : 2); }
-                }
-#undef MLZ_LAUNCH_M2
-            }
-            if (!fuse_scratch) {
-                Timer t(c, T_ENC_SER, st);
-                hipLaunchKernelGGL(serialize_pieces_kernel, dim3(tiles), dim3(256), kSerLds, st, d_src, blocks, tile_block, c->d_recs.as<uint2>(),
-                                   c->d_piece_cnt.as<uint32_t>(), c->d_scratch.as<uint8_t>(), c->d_tile_size.as<uint32_t>());
-            }
+// Raises the dynamic-LDS limit of every kernel of `list` (entries with .fn and .lds) the first time a context, that is a device, comes by.
+template <class List> int raise_lds_once(mlz_ctx* c, bool& raised, const List& list) {
+    if (raised) return 0;
+    for (const auto& k : list) HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, int(k.lds)));
+    raised = true;
+    return 0;
+}
+template <class Fn> struct Kernel { Fn fn; uint32_t lds; };   // a kernel and the dynamic LDS it is launched with
+struct AnyKernel : Kernel<const void*> { template <class F> AnyKernel(F* f, uint32_t l) : Kernel{reinterpret_cast<const void*>(f), l} {} };   // ... in a list of kernels that share no signature
+using Kernels = std::initializer_list<AnyKernel>;
+
+// ---- encode: every instantiation of the match kernel and of the far-table kernel, named once, with the dynamic LDS it is launched with.  A launch takes a
+// row of these tables and the limits are raised for a whole table at once, so no instantiation runs without its limit.  Every level goes through the match +
+// serialize kernels on 8 KiB pieces (mlz_encode2.hip.inc); LevelBalanced is their configuration with larger near tables, denser far tables and a second far probe (kL2*).
+using MatchFn = void (*)(const uint8_t*, const BlockInfo*, const uint32_t*, uint2*, uint32_t*, const uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t,
+                         uint32_t, uint8_t*, uint32_t*);
+enum MatchId { M_L1_BIG_FAR, M_L1_SMALL_FAR, M_L1_BIG, M_L1_SMALL, M_SUPERFAST, M_L2_BIG, M_L2_SMALL, M_L2_ONE_TILE, M_COUNT };
+const Kernel<MatchFn> kMatch[M_COUNT] = {
+    {match_tiles_kernel<true, MLZ_M2_NW, kM2HashBitsBig, kFarBits, false>, M2Cfg<kM2HashBitsBig>::kLds},
+    {match_tiles_kernel<true, MLZ_M2_NW, kM2HashBitsSmall, 0, false>, M2Cfg<kM2HashBitsSmall>::kLds},                  // far tables of the block's own size
+    {match_tiles_kernel<false, MLZ_M2_NW, kM2HashBitsBig, kFarBits, false>, M2Cfg<kM2HashBitsBig>::kLds},
+    {match_tiles_kernel<false, MLZ_M2_NW, kM2HashBitsSmall, kFarBits, false>, M2Cfg<kM2HashBitsSmall>::kLds},
+    {match_tiles_kernel<false, MLZ_M2_NW, kM2HashBitsSuperFast, kFarBits, false>, M2Cfg<kM2HashBitsSuperFast>::kLds},  // (MLZ_L1_HB = 12, the default: the function of M_L1_BIG)
+    {match_tiles_kernel<true, MLZ_M2_NW, kM2HashBitsSmall, kL2FarBits, true>, M2Cfg<kM2HashBitsSmall>::kLds},          // LevelBalanced: one configuration for both block classes,
+    {match_tiles_kernel<true, MLZ_M2_NW, kM2HashBitsSmall, 0, true>, M2Cfg<kM2HashBitsSmall>::kLds},                   // with far tables of the level's size or of the block's
+    {match_tiles_kernel<false, MLZ_M2_NW, kM2HashBitsSmall, kL2FarBits, true>, M2Cfg<kM2HashBitsSmall>::kLds},         // no far tables, but the level's near-table seeding
+};
+using FarBuildFn = void (*)(const uint8_t*, const BlockInfo*, uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t);
+const Kernel<FarBuildFn> kFarBuild[4] = {   // [2 * LevelBalanced + blocks of kBigBlock and more]; the smaller blocks' tables go with their length
+    {far_build_kernel<0, kFarStride>, 4u << kFarSliceBits}, {far_build_kernel<kFarBits, kFarStride>, 4u << kFarSliceBits},
+    {far_build_kernel<0, kL2FarStride>, 4u << kFarSliceBits}, {far_build_kernel<kL2FarBits, kL2FarStride>, 4u << kFarSliceBits},
+};
+
+// The match launches of a group: one per block class that occurs in it (usually one), each workgroup leaving at once when its block belongs
+// to the other class.  cls: 2 = every block, 1 = those of kM2BigBlock and more, 0 = the smaller ones.
+struct MatchPlan { int n; struct { MatchId id; uint32_t cls; } launch[2]; };
+MatchPlan match_plan(int level, bool far, bool any_big, bool any_small) {
+    if (level == MLZ_LEVEL_SUPERFAST) return {1, {{M_SUPERFAST, 2u}}};
+    const bool l2 = level == MLZ_LEVEL_BALANCED;
+    if (l2 && !far) return {1, {{M_L2_ONE_TILE, 2u}}};   // (the level forces far matching on: no block of the group exceeds a tile)
+    MatchPlan p{};
+    if (any_big) p.launch[p.n++] = {l2 ? M_L2_BIG : far ? M_L1_BIG_FAR : M_L1_BIG, any_small ? 1u : 2u};
+    if (any_small) p.launch[p.n++] = {l2 ? M_L2_SMALL : far ? M_L1_SMALL_FAR : M_L1_SMALL, any_big ? 0u : 2u};
+    return p;
+}
+
+// What the parts of a group's encode read; encode_device_group computes it once.
+struct EncGroup {
+    int level, n;
+    const BlockInfo* blocks; const uint32_t* tile_block;   // the group's descriptors on the device
+    uint32_t tiles, epochs, pattern, far_gap;
+    size_t units;            // pieces
+    bool far, any_big, any_small;   // far tables are built and probed; block classes that occur
+    int fbits;               // far tables lie 2^fbits entries apart
+};
+
+int encode_far_tables(mlz_ctx* c, hipStream_t st, const EncGroup& g, const uint8_t* d_src, const mlz_block_desc* desc) {
+    Timer t(c, T_FAR, st);
+    const bool l2 = g.level == MLZ_LEVEL_BALANCED;
+    HIPCHK(c, c->d_far.ensure(((size_t(g.n) * far_sets(g.pattern) * g.epochs) << g.fbits) * 4));
+    if (int r = raise_lds_once(c, c->far_attr, kFarBuild)) return r;
+    auto build = [&](const Kernel<FarBuildFn>& v, dim3 grid, uint32_t lds, uint32_t cls) {
+        hipLaunchKernelGGL(v.fn, grid, dim3(1024), lds, st, d_src, g.blocks, c->d_far.as<uint32_t>(), g.epochs, g.pattern, uint32_t(g.fbits), cls);
+    };
+    if (g.any_big) {
+        if (l2 && g.pattern == kPatternFree && !c->far_slices_l2) {
+            // no level sets: the windows sorted by slice once (far_bin_kernel), every slice workgroup reads its eighth (far_slice_kernel)
+            using FBn = FarBin<kL2FarBits, kL2FarStride>;
+            const size_t units2 = size_t(g.tiles) * 2;
+            HIPCHK(c, c->d_farbin.ensure(units2 * FBn::kPerUnit * 4 + units2 * FBn::kOffs * 4 + 256));
+            uint32_t* bins = c->d_farbin.as<uint32_t>();
+            uint32_t* binoff = bins + units2 * FBn::kPerUnit;
+            constexpr uint32_t kSliceLds = (4u << kBinSliceBits) + 256 * 4 + 132 * 4;
+            if (int r = raise_lds_once(c, c->farbin_attr, Kernels{{far_bin_kernel<kL2FarBits, kL2FarStride>, FBn::kLds}, {far_slice_kernel<kL2FarBits, kL2FarStride>, kSliceLds}})) return r;
+            hipLaunchKernelGGL((far_bin_kernel<kL2FarBits, kL2FarStride>), dim3(uint32_t(units2)), dim3(256), FBn::kLds, st, d_src, g.blocks, g.tile_block, bins, binoff);
+            hipLaunchKernelGGL((far_slice_kernel<kL2FarBits, kL2FarStride>), dim3(FBn::kSlices, g.epochs, g.n), dim3(1024), kSliceLds, st, g.blocks, bins, binoff, c->d_far.as<uint32_t>(), g.epochs);
+        } else
+            build(kFarBuild[2 * l2 + 1], dim3(far_slices(l2 ? kL2FarBits : kFarBits), g.epochs, g.n), kFarBuild[2 * l2 + 1].lds, g.any_small ? 1u : 2u);
+    }
+    if (g.any_small) {
+        uint64_t max_small = 0;
+        for (int i = 0; i < g.n; i++) if (desc[i].src_len < kBigBlock) max_small = std::max<uint64_t>(max_small, desc[i].src_len);
+        const int sb = small_far_bits(max_small) + (l2 ? 1 : 0);
+        const uint32_t lds = 4u << std::min<int>(sb, kFarSliceBits);   // small tables leave room for more workgroups per CU
+        build(kFarBuild[2 * l2], dim3(1u << (std::max<int>(sb, kFarSliceBits) - kFarSliceBits), 1, g.n), lds, g.any_big ? 0u : 2u);
+    }
+    return 0;
+}
+
+// The match kernel on every tile of the group, and the serializer where the match kernel's waves do not serialize their pieces themselves.
+int encode_match(mlz_ctx* c, hipStream_t st, const EncGroup& g, const uint8_t* d_src) {
+    HIPCHK(c, c->d_recs.ensure(g.units * kRecPerPiece * sizeof(uint2)));
+    HIPCHK(c, c->d_piece_cnt.ensure(g.units * sizeof(uint32_t)));
+    if (int r = raise_lds_once(c, c->enc_attrs, kMatch)) return r;
+    const uint32_t* ftab = g.far ? c->d_far.as<uint32_t>() : nullptr;
+    uint8_t* fuse_scratch = c->fuse_ser ? c->d_scratch.as<uint8_t>() : nullptr;   // option 21, default on
+    {
+        Timer t(c, T_ENC_TILES, st);
+        const uint32_t grid = ((g.tiles + 7) / 8) * 8;  // whole rounds of the eight XCDs (see the kernel's workgroup -> tile map)
+        const MatchPlan plan = match_plan(g.level, g.far, g.any_big, g.any_small);
+        for (int i = 0; i < plan.n; i++) {
+            const Kernel<MatchFn>& v = kMatch[plan.launch[i].id];
+            hipLaunchKernelGGL(v.fn, dim3(grid), dim3(256), v.lds, st, d_src, g.blocks, g.tile_block, c->d_recs.as<uint2>(), c->d_piece_cnt.as<uint32_t>(), ftab, g.epochs,
+                               g.pattern, g.tiles, plan.launch[i].cls, uint32_t(g.fbits), g.far_gap, fuse_scratch, c->d_tile_size.as<uint32_t>());
         }
     }
-    // The layout (piece offsets, stored-or-not, header, length) rides in the gather when every block of the group has tiles and room — the common case;
-    // an empty, oversize or too tightly bounded block needs encode_layout_kernel's verdicts (option 24 = 0: always the separate kernel).
-    bool fold = c->fold_layout && tiles > 0 && level != MLZ_LEVEL_UNCOMPRESSED;
-    for (int i = 0; fold && i < n; i++) {
+    if (!fuse_scratch) {
+        Timer t(c, T_ENC_SER, st);
+        hipLaunchKernelGGL(serialize_pieces_kernel, dim3(g.tiles), dim3(256), kSerLds, st, d_src, g.blocks, g.tile_block, c->d_recs.as<uint2>(),
+                           c->d_piece_cnt.as<uint32_t>(), c->d_scratch.as<uint8_t>(), c->d_tile_size.as<uint32_t>());
+    }
+    return 0;
+}
+
+// The layout (piece offsets, stored-or-not, header, length) rides in the gather when every block of the group has tiles and room — the common case;
+// an empty, oversize or too tightly bounded block needs encode_layout_kernel's verdicts (option 24 = 0: always the separate kernel).
+void encode_layout_gather(mlz_ctx* c, hipStream_t st, const EncGroup& g, const uint8_t* d_src, uint8_t* d_dst, const mlz_block_desc* desc, int64_t* d_out_len,
+                          bool with_header) {
+    bool fold = c->fold_layout && g.tiles > 0 && g.level != MLZ_LEVEL_UNCOMPRESSED;
+    for (int i = 0; fold && i < g.n; i++) {
         const uint64_t len = desc[i].src_len;
         if (len == 0 || len > kMaxBlockSize || desc[i].dst_cap < (with_header ? len + 2 : len)) fold = false;
     }
     if (!fold) {
         Timer t(c, T_ENC_LAYOUT, st);
-        hipLaunchKernelGGL(encode_layout_kernel, dim3(n), dim3(64), 0, st, blocks, c->d_tile_size.as<uint32_t>(), c->d_tile_out.as<uint32_t>(), d_dst,
-                           d_out_len, c->d_flags.as<uint32_t>(), level, with_header ? 1 : 0, sub_log);
+        hipLaunchKernelGGL(encode_layout_kernel, dim3(g.n), dim3(64), 0, st, g.blocks, c->d_tile_size.as<uint32_t>(), c->d_tile_out.as<uint32_t>(), d_dst, d_out_len,
+                           c->d_flags.as<uint32_t>(), g.level, with_header ? 1 : 0, kSubLog);
     }
-    if (tiles > 0) {
+    if (g.tiles > 0) {
         Timer t(c, T_ENC_GATHER, st);
-        if (fold)
-            hipLaunchKernelGGL(encode_gather2_kernel<true>, dim3(tiles), dim3(256), 0, st, d_src, blocks, tile_block, c->d_scratch.as<uint8_t>(),
-                               c->d_tile_size.as<uint32_t>(), c->d_tile_out.as<uint32_t>(), d_dst, c->d_flags.as<uint32_t>(), with_header ? 1 : 0, level, d_out_len);
-        else
-            hipLaunchKernelGGL(encode_gather2_kernel<false>, dim3(tiles), dim3(256), 0, st, d_src, blocks, tile_block, c->d_scratch.as<uint8_t>(),
-                               c->d_tile_size.as<uint32_t>(), c->d_tile_out.as<uint32_t>(), d_dst, c->d_flags.as<uint32_t>(), with_header ? 1 : 0, level, d_out_len);
+        const auto gather = fold ? encode_gather2_kernel<true> : encode_gather2_kernel<false>;
+        hipLaunchKernelGGL(gather, dim3(g.tiles), dim3(256), 0, st, d_src, g.blocks, g.tile_block, c->d_scratch.as<uint8_t>(),
+                           c->d_tile_size.as<uint32_t>(), c->d_tile_out.as<uint32_t>(), d_dst, c->d_flags.as<uint32_t>(), with_header ? 1 : 0, g.level, d_out_len);
     }
+}
+
+int encode_device_group(mlz_ctx* c, hipStream_t st, int level, const uint8_t* d_src, uint8_t* d_dst, const mlz_block_desc* desc, int n,
+                        int64_t* d_out_len, bool with_header, const uint64_t* mirror) {
+    EncGroup g{level, n};
+    int r = upload_blocks(c, st, desc, n, false, &g.tiles, nullptr, mirror);
+    if (r) return r;
+    g.blocks = c->d_blocks_cur().as<BlockInfo>(); g.tile_block = c->d_tile_block_cur().as<uint32_t>();
+    g.units = size_t(g.tiles) << kSubLog;
+    HIPCHK(c, c->d_tile_size.ensure(sizeof(uint32_t) * (g.units + 1)));
+    HIPCHK(c, c->d_tile_out.ensure(sizeof(uint32_t) * (g.units + 1)));
+    HIPCHK(c, c->d_flags.ensure(sizeof(uint32_t) * n));
+    if (level != MLZ_LEVEL_UNCOMPRESSED && g.tiles > 0) {
+        HIPCHK(c, c->d_scratch.ensure(g.units * kPieceScratch));
+        const bool l2 = level == MLZ_LEVEL_BALANCED;
+        uint64_t maxlen = 0;
+        for (int i = 0; i < n; i++) {
+            const uint64_t len = std::min<uint64_t>(desc[i].src_len, kMaxBlockSize);
+            maxlen = std::max(maxlen, len);
+            (len >= kM2BigBlock ? g.any_big : g.any_small) = true;
+        }
+        g.epochs = uint32_t((maxlen + (1u << kEpochLog) - 1) >> kEpochLog);
+        // LevelBalanced: far matching forced on, both epochs probed and a cost-aware lazy parse (DESIGN.md "Levels").
+        // LevelSuperFast: tile-local matches only (no far tables are built or probed).
+        g.far = ((c->encode_far && level != MLZ_LEVEL_SUPERFAST) || l2) && maxlen > kTile;
+        g.pattern = (l2 && c->l2_free) ? kPatternFree : level_pattern_of(level);   // LevelBalanced: dense (four levels); the faster levels: three (DESIGN.md "Tile levels"); the decoder knows both and round 1's kPatternFast
+        // LevelFastest: blocks below 1 MiB have far tables that go with their length (small_far_bits); the tables of a batch
+        // are as far apart as its largest block needs
+        g.fbits = g.any_big ? (l2 ? kL2FarBits : kFarBits) : small_far_bits(maxlen) + (l2 ? 1 : 0);
+        // LevelBalanced without levels: far sources at least l2_gap tiles back (MLZ_OPT_L2_GAP)
+        g.far_gap = g.pattern == kPatternFree && l2 ? uint32_t(c->l2_gap - 1) << kTileLog : 0u;
+        if (g.far) r = encode_far_tables(c, st, g, d_src, desc);
+        if (!r) r = encode_match(c, st, g, d_src);
+        if (r) return r;
+    }
+    encode_layout_gather(c, st, g, d_src, d_dst, desc, d_out_len, with_header);
     HIPCHK(c, hipGetLastError());
     return 0;
 }
@@ -504,69 +523,63 @@ int decode_parallel(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, uint8_t* d
     uint32_t tiles = 0, segs = 0;
     int r = upload_blocks(c, st, desc, n, true, &tiles, &segs, mirror);
     if (r) return r;
-    // carve the workspace
-    auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-    const size_t o_dec = 0;
-    const size_t o_exit = o_dec + al(sizeof(DecBlock) * n);
-    const size_t o_rexit = o_exit + al(size_t(segs) * kExitKeep * 4);
-    const size_t o_entry = o_rexit + al(size_t(segs) * kSeg);
-    const size_t o_tstart = o_entry + al(size_t(segs) * 4);
-    const size_t o_tpos = o_tstart + al(size_t(tiles) * sizeof(TileStart));     // token list: a token has at least one stream byte
-    const size_t o_rd = o_tpos + al(size_t(segs) * kSeg * 4);
-    const size_t o_rr = o_rd + al(size_t(segs) * kSegThreads * 4);              // (per 64 tokens: indexed like the 64-byte chunks)
-    const size_t o_order = o_rr + al(size_t(segs) * kSegThreads * 4);
-    const size_t o_glist = o_order + al(size_t(tiles) * 4);                     // general blocks of the batch (D3d)
-    const size_t o_xcnt = o_glist + al(size_t(n) * 4);                          // per-tile records of dec_general_kernel (GenTile)
-    const size_t o_done = o_xcnt + al(size_t(tiles) * sizeof(GenTile));
-    const size_t o_ticket = o_done + al(size_t(tiles) * 4);
-    const size_t o_gen = o_ticket + 256;  // GenCtl (zeroed with the flags)
-    const size_t o_sstate = o_gen + al(sizeof(GenCtl));                          // per segment: aggregate words of the index pass (the segment's, then three prefixes over its quarters; zeroed with the flags)
-    const size_t o_sviol = o_sstate + al(size_t(segs) * 32);                    // ... and which level patterns its quarters' copies break (zeroed)
-    const size_t o_tok16 = o_sviol + al(size_t(segs) * 4);                    // ... and its token positions inside the segment (16 bits per stream byte; not zeroed)
-    const size_t total = o_tok16 + al(size_t(segs) * kSeg * 2);
-    HIPCHK(c, c->d_dec.ensure(total));
-    uint8_t* ws = c->d_dec.as<uint8_t>();
-    DecBlock* dec = reinterpret_cast<DecBlock*>(ws + o_dec);
-    uint32_t* exit_tab = reinterpret_cast<uint32_t*>(ws + o_exit);
-    uint8_t* rexit_tab = reinterpret_cast<uint8_t*>(ws + o_rexit);
-    uint32_t* seg_entry = reinterpret_cast<uint32_t*>(ws + o_entry);
-    TileStart* tile_start = reinterpret_cast<TileStart*>(ws + o_tstart);
-    uint32_t* tok_pos = reinterpret_cast<uint32_t*>(ws + o_tpos);
-    uint32_t* round_d = reinterpret_cast<uint32_t*>(ws + o_rd);
-    uint32_t* round_rep = reinterpret_cast<uint32_t*>(ws + o_rr);
-    uint32_t* order = reinterpret_cast<uint32_t*>(ws + o_order);
-    uint32_t* tile_done = reinterpret_cast<uint32_t*>(ws + o_done);
-    uint32_t* ticket = reinterpret_cast<uint32_t*>(ws + o_ticket);
-    GenCtl* gen = reinterpret_cast<GenCtl*>(ws + o_gen);
-    c->last_gen = gen;
+    // the workspace, every region on a 256-byte boundary
+    constexpr size_t kAl = 256;
+    Carve cv;
+    const auto r_dec = cv.take<DecBlock>(size_t(n), kAl);
+    const auto r_exit = cv.take<uint32_t>(size_t(segs) * kExitKeep, kAl);
+    const auto r_rexit = cv.take<uint8_t>(size_t(segs) * kSeg, kAl);
+    const auto r_entry = cv.take<uint32_t>(segs, kAl);
+    const auto r_tstart = cv.take<TileStart>(tiles, kAl);
+    const auto r_tpos = cv.take<uint32_t>(size_t(segs) * kSeg, kAl);              // token list: a token has at least one stream byte
+    const auto r_rd = cv.take<uint32_t>(size_t(segs) * kSegThreads, kAl), r_rr = cv.take<uint32_t>(size_t(segs) * kSegThreads, kAl);   // (per 64 tokens: indexed like the 64-byte chunks)
+    const auto r_order = cv.take<uint32_t>(tiles, kAl), r_glist = cv.take<uint32_t>(size_t(n), kAl);   // the tile schedule; the general blocks of the batch (D3d)
+    const auto r_xcnt = cv.take<GenTile>(tiles, kAl);                             // per-tile records of dec_general_kernel
+    // dec_header_kernel zeroes everything between the two marks as one span: the order of these five regions is the contract
+    const size_t zero_begin = cv.take<uint32_t>(0, kAl).off;
+    const auto r_done = cv.take<uint32_t>(tiles, kAl), r_ticket = cv.take<uint32_t>(kAl / 4, kAl);
+    const auto r_gen = cv.take<GenCtl>(1, kAl);
+    const auto r_sstate = cv.take<unsigned long long>(size_t(segs) * 4, kAl);     // per segment: aggregate words of the index pass (the segment's, then three prefixes over its quarters)
+    const auto r_sviol = cv.take<uint8_t>(size_t(segs) * 4, kAl);                 // ... and which level patterns its quarters' copies break
+    const size_t zero_end = cv.take<uint32_t>(0, kAl).off;
+    const auto r_tok16 = cv.take<uint16_t>(size_t(segs) * kSeg, kAl);             // ... and its token positions inside the segment (16 bits per stream byte; not zeroed)
+    HIPCHK(c, c->d_dec.ensure(cv.take<uint8_t>(0, kAl).off));
+    void* ws = c->d_dec.p;
+    DecBlock* dec = r_dec.at(ws);
+    TileStart* tile_start = r_tstart.at(ws);
+    uint8_t *rexit_tab = r_rexit.at(ws), *sviol = r_sviol.at(ws);
+    uint32_t *exit_tab = r_exit.at(ws), *seg_entry = r_entry.at(ws), *tok_pos = r_tpos.at(ws), *round_d = r_rd.at(ws), *round_rep = r_rr.at(ws), *order = r_order.at(ws);
+    uint32_t *tile_done = r_done.at(ws), *ticket = r_ticket.at(ws);
+    GenCtl* gen = r_gen.at(ws);
+    uint32_t* gen_words = reinterpret_cast<uint32_t*>(gen);   // the kernels outside the general pass read its words by index
+    unsigned long long* sstate = r_sstate.at(ws);
+    uint16_t* tok16 = r_tok16.at(ws);
     // General blocks (streams of other encoders) go through dec_general_kernel when its workspace — 2 B of map and 1 B of pool per
     // output byte, 8 B per possible token for the external entries — is affordable (<= 64 GiB) and the current exec pass is in use.
-    const size_t map_bytes = (size_t(tiles) << kTileLog) * 3;   // maps, then pools
-    const size_t ext_entries = (size_t(segs) << kSegLog) + size_t(tiles) * kExtPerTile + 64 * size_t(n);
+    Carve idx;
+    const auto r_gmap = idx.take<uint16_t>(size_t(tiles) << kTileLog);
+    const auto r_gpool = idx.take<uint8_t>(size_t(tiles) << kTileLog);
+    const auto r_ext = idx.take<ExtEnt>((size_t(segs) << kSegLog) + size_t(tiles) * kExtPerTile + 64 * size_t(n));
     bool jump = c->general_algo == 0 && c->decode_algo == 0 && tiles > 0;
-    if (jump && c->d_idx.ensure(map_bytes + ext_entries * sizeof(ExtEnt) + 256) != hipSuccess) {
+    if (jump && c->d_idx.ensure(idx.bytes + 256) != hipSuccess) {
         // The device cannot hold the pass's buffers (another tenant's memory, a small part): not a reason to fail the call — general blocks
         // then stay on the exec pass's tile chain, which needs none (slow, correct).  Counted, so that a caller can see it: mlz_get_counter(ctx, 5).
         (void)hipGetLastError();
         c->gen_fallbacks++;
         jump = false;
     }
+    uint32_t* gen_list = jump ? r_glist.at(ws) : nullptr;   // null: general blocks stay on the tile path
     const BlockInfo* blocks = c->d_blocks_cur().as<BlockInfo>();
     const uint32_t* tile_block = c->d_tile_block_cur().as<uint32_t>();
     const uint32_t* seg_block = c->d_seg_block_cur().as<uint32_t>();
-    if (!c->dec_attrs) {
-        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(dec_exit_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kExitLds));
-        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(dec_index1_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kIdxLds));
-        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(dec_exec2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kExecLds));
-        c->dec_attrs = true;
-    }
+    if ((r = raise_lds_once(c, c->dec_attrs, Kernels{{dec_exit_kernel, kExitLds}, {dec_index1_kernel, kIdxLds}, {dec_exec2_kernel, kExecLds}}))) return r;
     {
         Timer t(c, T_DEC_PARSE, st);
         // the header pass also initialises the workspace words the later passes expect (two memsets = two more launches otherwise)
-        const uint32_t n_ff = segs, n_zero = uint32_t((o_tok16 - o_done) / 4);
+        const uint32_t n_ff = segs, n_zero = uint32_t((zero_end - zero_begin) / 4);
         const uint32_t hdr_grid = std::max<uint32_t>(uint32_t(n + 63) / 64, std::min<uint32_t>((std::max(n_ff, n_zero) + 255) / 256, 256u));
         hipLaunchKernelGGL(dec_header_kernel, dim3(hdr_grid), dim3(64), 0, st, d_src, blocks, dec, n, raw_body ? 1 : 0, seg_entry, n_ff,
-                           reinterpret_cast<uint32_t*>(ws + o_done), n_zero);
+                           tile_done, n_zero);
         if (segs)
             hipLaunchKernelGGL(dec_exit_kernel, dim3(segs), dim3(kExitThreads), kExitLds, st, d_src, blocks, seg_block, dec, exit_tab, rexit_tab);
     }
@@ -577,31 +590,27 @@ int decode_parallel(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, uint8_t* d
     {
         Timer t(c, T_DEC_INDEX, st);
         if (segs) {
-            unsigned long long* sstate = reinterpret_cast<unsigned long long*>(ws + o_sstate);
-            uint16_t* tok16 = reinterpret_cast<uint16_t*>(ws + o_tok16);
             hipLaunchKernelGGL(dec_index1_kernel, dim3(segs), dim3(kIdxThreads), kIdxLds, st, d_src, blocks, seg_block, dec, seg_entry, rexit_tab, sstate, sstate + segs, tok16);
             hipLaunchKernelGGL(dec_index2_kernel, dim3(2 * segs), dim3(kIdx2Threads), 0, st, d_src, blocks, seg_block, dec, sstate, sstate + segs, tok16, tile_start, tok_pos,
-                               round_d, round_rep, ws + o_sviol);
+                               round_d, round_rep, sviol);
         }
         if (jump && segs && !c->gen_attr) {
-            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(dec_general_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kGenLds));
+            if ((r = raise_lds_once(c, c->gen_attr, Kernels{{dec_general_kernel, kGenLds}}))) return r;
             // how many of its workgroups the device holds at once (1024 threads + 132 KiB of LDS: one per CU).  Not a correctness
             // requirement — role E never waits and role S only waits for role E, whose workgroups come first in the grid —: it
             // sizes the grid so that the settling workgroups start beside the explaining ones instead of behind them.
             int per_cu = 0;
             HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(dec_general_kernel), kGenThreads, kGenLds));
             c->gen_grid = per_cu >= 1 ? c->n_cus * per_cu : 0;
-            c->gen_attr = true;
         }
         if (segs)
-            hipLaunchKernelGGL(dec_viol_kernel, dim3((segs + 255) / 256), dim3(256), 0, st, seg_block, ws + o_sviol, dec, jump ? &gen->n_general : nullptr, segs);
+            hipLaunchKernelGGL(dec_viol_kernel, dim3((segs + 255) / 256), dim3(256), 0, st, seg_block, sviol, dec, jump ? &gen->n_general : nullptr, segs);
         if (tiles) {
             HIPCHK(c, c->d_gen_acc.ensure(64));
             const uint32_t reset = c->acc_call != c->dec_call ? 1u : 0u;
             c->acc_call = c->dec_call;
             hipLaunchKernelGGL(dec_schedule_kernel, dim3(1), dim3(1024), 0, st, blocks, tile_block, dec, order, tiles, uint32_t(n),
-                               jump ? reinterpret_cast<uint32_t*>(ws + o_glist) : nullptr, reinterpret_cast<uint32_t*>(gen), gen_settle_wgs(c, n),
-                               c->d_gen_acc.as<uint32_t>(), reset);
+                               gen_list, gen_words, gen_settle_wgs(c, n), c->d_gen_acc.as<uint32_t>(), reset);
         }
     }
     {
@@ -610,17 +619,14 @@ int decode_parallel(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, uint8_t* d
         // level-0 tiles first, by role E of the general pass, when they are few (dec_level0_kernel; option 23 = 0: off)
         uint32_t l0_grid = 0;
         if (tiles && c->level0_by_e && c->decode_algo == 0) {
-            if (!c->l0_attr) {
-                HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(dec_level0_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kGenLds));
-                c->l0_attr = true;
-            }
+            if ((r = raise_lds_once(c, c->l0_attr, Kernels{{dec_level0_kernel, kGenLds}}))) return r;
             l0_grid = std::min<uint32_t>(uint32_t(c->n_cus), tiles);
             hipLaunchKernelGGL(dec_level0_kernel, dim3(l0_grid), dim3(kGenThreads), kGenLds, st, d_src, d_dst, blocks, dec, tok_pos, round_d, round_rep, tile_start,
                                order, tile_block, tile_done, gen);
         }
         if (tiles)
             hipLaunchKernelGGL(dec_exec2_kernel, dim3(tiles), dim3(kExecThreads), kExecLds, st, d_src, d_dst, blocks, tile_block, dec, tile_start, tok_pos,
-                               round_d, round_rep, order, tile_done, ticket, tiles, prof, reinterpret_cast<const uint32_t*>(gen), l0_grid);
+                               round_d, round_rep, order, tile_done, ticket, tiles, prof, gen_words, l0_grid);
     }
     {
         Timer tg(c, T_DEC_GENERAL, st);   // (+ the result pass)
@@ -629,10 +635,12 @@ int decode_parallel(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, uint8_t* d
             // role S: one workgroup per general block, at most a quarter of the device (more blocks take turns); role E: the rest
             const uint32_t nS = gen_settle_wgs(c, n);
             const uint32_t nE = std::max<uint32_t>(1u, uint32_t(c->gen_grid) > nS ? uint32_t(c->gen_grid) - nS : 1u);
+            uint16_t* gmap = r_gmap.at(c->d_idx.p);
+            uint8_t* gpool = r_gpool.at(c->d_idx.p);
+            ExtEnt* ext = r_ext.at(c->d_idx.p);
+            GenTile* gen_tile = r_xcnt.at(ws);
             hipLaunchKernelGGL(dec_general_kernel, dim3(nE + nS), dim3(kGenThreads), kGenLds, st, d_src, d_dst, blocks, dec, tok_pos, round_d, round_rep, tile_start,
-                               reinterpret_cast<const uint32_t*>(ws + o_glist), c->d_idx.as<uint16_t>(), c->d_idx.as<uint8_t>() + (size_t(tiles) << kTileLog) * 2,
-                               reinterpret_cast<ExtEnt*>(c->d_idx.as<uint8_t>() + map_bytes), reinterpret_cast<GenTile*>(ws + o_xcnt), tile_done, gen, nE, nS,
-                               c->gen_spin_limit, uint32_t(c->gen_force_packed), d_out_len, n, c->debug_status);   // (+ the results: D5)
+                               gen_list, gmap, gpool, ext, gen_tile, tile_done, gen, nE, nS, c->gen_spin_limit, uint32_t(c->gen_force_packed), d_out_len, n, c->debug_status);   // (+ the results: D5)
         } else
             hipLaunchKernelGGL(dec_finish_kernel, dim3((n + 63) / 64), dim3(64), 0, st, dec, d_out_len, n, c->debug_status);
     }
@@ -868,6 +876,9 @@ struct Workers {
     mlz_ctx* next() const { return n == 1 ? list[0] : list[one->rr.fetch_add(1, std::memory_order_relaxed) % n]; }   // single-block calls: the kids in turn
 };
 
+// How the four single-block entry points end: the request through the queue of one of the context's devices; what it produced, or the batch's failure.
+int64_t run_single(mlz_ctx* c, SingleReq rq) { submit_single(Workers(c).next(), rq); return rq.rc ? rq.rc : rq.out; }
+
 // The kid whose device holds `p` (a device-resident call on a several-device context), or the context itself.
 mlz_ctx* owner_of(mlz_ctx* c, const void* p) {
     if (c->kids.empty()) return c;
@@ -989,8 +1000,7 @@ void mlz_destroy(mlz_ctx* c) {
     }
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    for (DevBuf* b : {&c->d_place, &c->d_crc, &c->d_crc_tabs, &c->d_crc_tiles, &c->d_prof, &c->d_blocks_k[0], &c->d_blocks_k[1], &c->d_tile_block_k[0], &c->d_tile_block_k[1], &c->d_seg_block_k[0], &c->d_seg_block_k[1], &c->d_scratch, &c->d_tile_size, &c->d_tile_out, &c->d_flags, &c->d_far, &c->d_farbin, &c->d_recs, &c->d_piece_cnt, &c->d_dec, &c->d_idx, &c->d_walk, &c->d_walk_tab, &c->d_range, &c->d_rplan, &c->d_stab, &c->d_gen_acc, &c->d_in, &c->d_out, &c->d_len})
-        b->release();
+    for (int side = 0; side < 3; side++) for (DevBuf* b : c->bufs(side)) b->release();
     for (int k = 0; k < 2; k++) if (c->pinned_k[k]) (void)hipHostFree(c->pinned_k[k]);
     if (c->pinned2) (void)hipHostFree(c->pinned2);
     if (c->s_in) (void)hipStreamDestroy(c->s_in);
@@ -1045,9 +1055,7 @@ int64_t mlz_encode(mlz_ctx* c, int level, const uint8_t* src, size_t n, uint8_t*
     if (n > kMaxBlockSize) return -MLZ_ERR_TOO_LARGE;
     if (int64_t(dst_cap) < mlz_max_encoded_len(n)) return -MLZ_ERR_DST_TOO_SMALL;
     if (!valid_level(level)) return -MLZ_ERR_INVALID_LEVEL;
-    SingleReq rq{true, true, false, level, src, n, dst, dst_cap, 0};
-    submit_single(Workers(c).next(), rq);
-    return rq.rc ? rq.rc : rq.out;
+    return run_single(c, {true, true, false, level, src, n, dst, dst_cap, 0});
 }
 
 int64_t mlz_encode_block(mlz_ctx* c, int level, const uint8_t* src, size_t n, uint8_t* dst, size_t dst_cap) {
@@ -1055,38 +1063,30 @@ int64_t mlz_encode_block(mlz_ctx* c, int level, const uint8_t* src, size_t n, ui
     if (n > kMaxBlockSize) return -MLZ_ERR_TOO_LARGE;
     if (dst_cap < n) return -MLZ_ERR_DST_TOO_SMALL;
     if (!valid_level(level)) return -MLZ_ERR_INVALID_LEVEL;
-    SingleReq rq{true, false, false, level, src, n, dst, dst_cap, 0};
-    submit_single(Workers(c).next(), rq);
-    return rq.rc ? rq.rc : rq.out;
+    return run_single(c, {true, false, false, level, src, n, dst, dst_cap, 0});
 }
 
 int64_t mlz_decode(mlz_ctx* c, const uint8_t* src, size_t n, uint8_t* dst, size_t dst_cap) {
     if (!c || !src || (!dst && dst_cap)) return -MLZ_ERR_ARG;
-    int64_t dl = mlz_decoded_len(src, n);
     uint64_t body, dlen; int lits;
     int e = parse_block_header(src, n, &body, &dlen, &lits);
     if (e) return -e;
     if (dlen > dst_cap) return -MLZ_ERR_DST_TOO_SMALL;
-    (void)dl;
     if (dlen == 0) return 0;
-    SingleReq rq{false, true, false, 0, src, n, dst, dst_cap, 0};
-    submit_single(Workers(c).next(), rq);
-    return rq.rc ? rq.rc : rq.out;
+    return run_single(c, {false, true, false, 0, src, n, dst, dst_cap, 0});
 }
 
 int mlz_decode_block(mlz_ctx* c, const uint8_t* src, size_t clen, uint8_t* dst, size_t n) {
     if (!c || (!src && clen) || (!dst && n)) return -MLZ_ERR_ARG;
     if (n > kMaxBlockSize) return -MLZ_ERR_TOO_LARGE;
     if (n == 0) return clen == 0 ? 0 : 1;
-    SingleReq rq{false, false, true, 0, src, clen, dst, n, n};
-    submit_single(Workers(c).next(), rq);
-    if (rq.rc) return rq.rc;
-    if (rq.out == int64_t(n)) return 0;
+    const int64_t out = run_single(c, {false, false, true, 0, src, clen, dst, n, n});   // (a failed batch: -MLZ_ERR_HIP, the only code a decode batch fails with)
+    if (out == int64_t(n)) return 0;
     // Only a DEVICE failure (-MLZ_ERR_HIP: a launch that failed, a bounded wait that gave up) is passed on as < 0, the shim's cue
     // to run its CPU decoder (go/minlz_hip.go: r < 0, counted in hipFallbacks).  Every other per-block code (corrupt, too large,
     // unsupported, destination too small) is a verdict on the INPUT: minLZDecode's contract has one value for those, 1 = corrupt
     // (decode.go:26), and a healthy device never makes the caller decode a block twice.
-    if (rq.out == -MLZ_ERR_HIP) return -MLZ_ERR_HIP;
+    if (out == -MLZ_ERR_HIP) return -MLZ_ERR_HIP;
     return 1;
 }
 
@@ -1217,10 +1217,9 @@ int64_t mlz_get_counter(mlz_ctx* c, int which) {
     }
     if (which == 3 || which == 4) {  // device workspace this context holds: 3 = encode side, 4 = decode side (grow-only buffers: the high-water mark of the calls so far)
         std::lock_guard<std::mutex> lk(c->mu);
-        size_t e = 0, d = 0;
-        for (const DevBuf* b : {&c->d_scratch, &c->d_tile_size, &c->d_tile_out, &c->d_flags, &c->d_far, &c->d_recs, &c->d_piece_cnt, &c->d_farbin, &c->d_stab}) e += b->cap;
-        for (const DevBuf* b : {&c->d_dec, &c->d_idx, &c->d_walk, &c->d_walk_tab, &c->d_range, &c->d_rplan}) d += b->cap;
-        return int64_t(which == 3 ? e : d);
+        size_t sum = 0;
+        for (const DevBuf* b : c->bufs(which - 3)) sum += b->cap;
+        return int64_t(sum);
     }
     if (which == 5) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->gen_fallbacks); }
     if (which == 7 || which == 8) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(which == 7 ? c->range_chunks : c->range_scratch); }

@@ -274,13 +274,9 @@ int search_tables_build(mlz_ctx* c, hipStream_t sm, const uint8_t* d_src, size_t
     *info_off = cnt * slot;
     HIPCHK(c, c->d_stab.ensure(cnt * slot + cnt * sizeof(uint2) + 64));
     const uint32_t lbits = std::min(B, mlz::kStabSliceBits), lds = 1u << (lbits - 3);
-    if (!c->stab_attr) {
-        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(mlz::stab_build_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 1u << (mlz::kStabSliceBits - 3)));
-        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(mlz::stab_build_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (1u << (mlz::kStabSliceBits - 3)) + 32));
-        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(mlz::stab_build_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (1u << (mlz::kStabSliceBits - 3)) + mlz::kSearchMaxPrefix + mlz::kStabLongTail));
-        c->stab_attr = true;
-    }
+    constexpr uint32_t kBitmap = 1u << (mlz::kStabSliceBits - 3);
+    if (int r = raise_lds_once(c, c->stab_attr, Kernels{{mlz::stab_build_kernel<false>, kBitmap}, {mlz::stab_build_kernel<true>, kBitmap + 32},
+                                                        {mlz::stab_build_long_kernel, kBitmap + mlz::kSearchMaxPrefix + mlz::kStabLongTail}})) return r;
     mlz::StabCommon a{};
     a.src = d_src; a.len = len; a.bs = bs; a.cnt = uint32_t(cnt); a.B = B; a.M = M;
     a.tail_n = std::min(tail_n, T == 4 ? mlz::kStabLongTail : 8u);
