@@ -354,6 +354,36 @@ void mlz_dev_reader_close(mlz_dev_reader* reader);
 int64_t mlz_dev_reader_search(mlz_dev_reader* reader, void* stream, uint32_t flags, const uint8_t* pattern, size_t pattern_len, uint64_t* d_offsets, size_t cap,
                               uint64_t* stats /* host, may be NULL: 4 values */);
 
+/* mlz_dev_reader_search_many: up to MLZ_SEARCH_MAX_PATTERNS patterns in one call; the chunks that any pattern's tables admit are decoded once
+ *   and scanned once for all of them.  `patterns` (host) holds the patterns' bytes back to back, pattern_len (host) their n_patterns lengths, each 1 .. 256.
+ *   Returns the number of pairs (p, i) with decoded[p, p + pattern_len[i]) == pattern i (overlapping occurrences count; duplicate patterns count each for
+ *   itself; the value may exceed cap).  d_counts (device, n_patterns values; may be NULL) receives every pattern's own number of occurrences, complete
+ *   whatever cap is.  d_offsets[k] and d_which[k] (device; both may be NULL when cap == 0) receive the min(total, cap) smallest pairs in ascending order
+ *   of (position, pattern index): two patterns that match at one position give two pairs, and the cut at cap may fall between them.  Nothing beyond
+ *   these is written, and nothing outside the three arrays.  After an error return the arrays' contents are unspecified (never beyond their sizes).
+ *   Equivalence: for a stream whose tables are truthful — every stream this library or the reference writes — the result is that of n_patterns calls
+ *   of mlz_dev_reader_search on the same handle with the same flags: d_counts[i] is call i's return value and the pairs are the merge of the n_patterns
+ *   position lists.  A table with a good CRC that lies (a cleared bit) may make the two differ: this call scans every chunk it decodes for every
+ *   pattern, so it also reports occurrences of pattern i in chunks that only another pattern's tables admitted.
+ *   Flags: MLZ_STREAM_IGNORE_CRC and MLZ_SEARCH_NO_TABLES as for mlz_dev_reader_search.
+ *   -MLZ_ERR_ARG, each decided before anything is launched, nothing written: n_patterns > MLZ_SEARCH_MAX_PATTERNS; a length of 0 or above 256; NULL
+ *   patterns or pattern_len with n_patterns > 0; d_offsets or d_which NULL with cap > 0; a device pointer that is not on the handle's device.
+ *   n_patterns == 0 returns 0 and launches nothing.  Decode and CRC errors as for mlz_dev_reader_search: the first failing decoded chunk in stream order.
+ *   Plan: per pattern the rule of mlz_dev_reader_search, unchanged; a chunk is decoded when any pattern's set holds it.  The host computes the
+ *   patterns' windows and hashes; a kernel over (data chunk, pattern) probes the tables and marks one byte per data chunk, and only those bytes come
+ *   back.  A pattern the tables cannot serve (shorter than M; no window behind a prefix under table types 2 to 4) puts every non-empty chunk into the set.
+ *   stats (host, may be NULL): data chunks of the stream; chunks decoded or copied; chunks with a usable table, or 0 when no pattern could use the
+ *   tables; patterns the tables could not serve (all of them under MLZ_SEARCH_NO_TABLES or without usable tables).  mlz_get_counter 10 / 11 report
+ *   the second and third for this call too. */
+#define MLZ_SEARCH_MAX_PATTERNS 4096
+int64_t mlz_dev_reader_search_many(mlz_dev_reader* reader, void* stream, uint32_t flags,
+                                   const uint8_t* patterns,          /* host: the patterns' bytes back to back */
+                                   const uint32_t* pattern_len,      /* host: n_patterns lengths, each 1 .. 256 */
+                                   size_t n_patterns,
+                                   uint64_t* d_counts,               /* device, n_patterns values; may be NULL */
+                                   uint64_t* d_offsets, uint32_t* d_which, size_t cap,   /* device; both may be NULL when cap == 0 */
+                                   uint64_t* stats /* host, may be NULL: 4 values */);
+
 /* ---- tuning / introspection (not part of the reference surface) ---- */
 #define MLZ_OPT_DECODE_ALGO 1  /* 0 = parallel (default), 1 = serial one-wave-per-block, 3 = parallel with every block on the tile path (cross-checks) */
 #define MLZ_OPT_ENCODE_FAR 2   /* 0 = tile-local matches only, 1 = + far matches (default) */

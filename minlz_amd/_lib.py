@@ -19,7 +19,7 @@ SYMBOLS = [
     "mlz_stream_encode_gather_device", "mlz_release_stream", "mlz_stream_decoded_prefix_len",
     "mlz_stream_decoded_len_device", "mlz_stream_decode_device",
     "mlz_stream_open_device", "mlz_dev_reader_size", "mlz_dev_reader_read", "mlz_dev_reader_close",
-    "mlz_dev_reader_read_device", "mlz_dev_reader_search",
+    "mlz_dev_reader_read_device", "mlz_dev_reader_search", "mlz_dev_reader_search_many",
     "mlz_stream_bound_tables", "mlz_stream_encode_gather_device_tables",
     "mlz_stream_bound_long_prefix", "mlz_stream_encode_gather_device_long_prefix",
 ]
@@ -104,5 +104,6 @@ def lib():
     L.mlz_dev_reader_close.argtypes = [vp]; L.mlz_dev_reader_close.restype = None
     L.mlz_dev_reader_read_device.argtypes = [vp, vp, u32, vp, vp, sz, vp, sz, vp]; L.mlz_dev_reader_read_device.restype = i64
     L.mlz_dev_reader_search.argtypes = [vp, vp, u32, vp, sz, vp, sz, C.POINTER(u64)]; L.mlz_dev_reader_search.restype = i64
+    L.mlz_dev_reader_search_many.argtypes = [vp, vp, u32, vp, vp, sz, vp, vp, vp, sz, C.POINTER(u64)]; L.mlz_dev_reader_search_many.restype = i64
     _lib = L
     return L

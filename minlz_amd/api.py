@@ -218,7 +218,7 @@ class Context:
         return int(L.mlz_get_counter(self.handle, 7)), int(L.mlz_get_counter(self.handle, 8))
 
     def search_plan(self):
-        """(chunks decoded or copied, chunks with a usable search table) of the context's last DeviceReader.search (mlz_get_counter 10, 11)."""
+        """(chunks decoded or copied, chunks with a usable search table) of the context's last DeviceReader.search or search_many (mlz_get_counter 10, 11)."""
         L = _lib.lib()
         return int(L.mlz_get_counter(self.handle, 10)), int(L.mlz_get_counter(self.handle, 11))
 
@@ -271,6 +271,25 @@ class DeviceReader:
         if r < 0:
             _raise(r, self.ctx)
         return int(r), (int(stats[0]), int(stats[1]), int(stats[2]))
+
+    def search_many(self, patterns, d_counts, d_offsets, d_which, cap, ignore_crc=False, no_tables=False, stream=None):
+        """mlz_dev_reader_search_many.  patterns: a sequence of up to 4096 bytes objects of 1 .. 256 bytes; d_counts: device address of room
+        for len(patterns) uint64 (or None), which receives every pattern's number of occurrences; d_offsets, d_which: device addresses of
+        room for `cap` uint64 and `cap` uint32 (None with cap == 0), which receive the smallest min(total, cap) pairs (position, pattern
+        index) in ascending order.  The chunks that any pattern's tables admit are decoded once and scanned once for all patterns.
+        -> (total pairs, (data chunks, chunks decoded or copied, chunks with a usable search table, patterns the tables could not serve))."""
+        if not self.handle:
+            raise ValueError("DeviceReader is closed")
+        pats = [bytes(p) for p in patterns]
+        blob = b"".join(pats)
+        lens = np.asarray([len(p) for p in pats], dtype=np.uint32)
+        stats = (C.c_uint64 * 4)()
+        flags = (STREAM_IGNORE_CRC if ignore_crc else 0) | (SEARCH_NO_TABLES if no_tables else 0)
+        r = _lib.lib().mlz_dev_reader_search_many(self.handle, stream, flags, blob if pats else None, lens.ctypes.data if pats else None, len(pats), d_counts, d_offsets,
+                                                  d_which, cap, stats)
+        if r < 0:
+            _raise(r, self.ctx)
+        return int(r), tuple(int(v) for v in stats)
 
     def close(self):
         if self.handle:

@@ -1,6 +1,8 @@
 // mlz_stream_search.h — what the block search tables' writer, the device-resident pattern search (mlz_stream_search.hip.inc) and their host
 // check (tools/stream_search_check.cpp) share: the table hash (SPEC_SEARCH.md 3.1), the size and the bytes of a table chunk (2.0, 2.1, 3.2),
 // the probe of one table and the rule that turns the probes of all chunks into the set of chunks to decode (Appendix B.4.1).
+// For the search for many patterns (mlz_stream_search_many.hip.inc, tools/stream_search_many_check.cpp): the marking form of that rule, the
+// layout for patterns of several lengths, the pattern index and the scan rule of one tile.
 // Plain C++: compiles for the host alone and for gfx950.  Table types 1 (no prefix), 2 (1 to 8 prefix byte values), 3 (a 256-bit mask of
 // prefix byte values; SPEC_SEARCH.md 3.3) and 4 (a long prefix of 1 to 256 bytes with extra matches; 3.3.4), uncompressed table chunks (0x45) only.
 #pragma once
@@ -227,6 +229,146 @@ void search_layout(size_t n_jobs, const std::vector<size_t>& gend, Off out_off_o
         if (j1 < n_jobs && adjacent(j1)) lay->carry[g] = uint32_t(run_have < L - 1 ? run_have : L - 1);
         if (o > lay->scratch_max) lay->scratch_max = o;
         lay->tile_end[g] = lay->tiles.size();
+    }
+}
+
+// ---- many patterns in one call (mlz_dev_reader_search_many) ----
+constexpr uint32_t kSearchMaxPatterns = 4096;
+
+// One pattern as the plan kernel sees it: its nw groups of gsize window hashes lie at hashes[h_off ...); t_min and L as in search_decoded_set.
+struct SearchManyPat { uint32_t h_off, nw, gsize, t_min, L, pad; };
+static_assert(sizeof(SearchManyPat) == 24, "a record shared with the kernels");
+
+// The part of search_decoded_set's rule that belongs to chunk k, marking only: take[k] and the chunks behind it that hold any of the L - 1
+// bytes after its end become 1 when k is a candidate; nothing is cleared.  Over all k this marks what search_decoded_set takes, so the
+// union of several patterns' sets is this function over every (k, pattern) on one array.  Every store is a 1: lanes may run it side by side.
+template <class A, class S, class N>
+MLZ_SEARCH_HD void search_decoded_mark(size_t k, size_t nck, A a_of, S s_of, N n_of, uint32_t nw, uint32_t L, uint8_t* take, uint32_t t_min = 1) {
+    if (!n_of(k)) return;
+    const bool last = k + 1 == nck;
+    const uint32_t a_k = a_of(k);
+    if (a_k != nw) {   // (s_next is looked at only where it decides)
+        if (last) return;
+        const uint32_t s_next = n_of(k + 1) < L ? nw : s_of(k + 1);
+        if (!search_candidate(a_k, s_next, nw, last, t_min)) return;
+    }
+    take[k] = 1;
+    uint64_t need = L - 1;
+    for (size_t j = k + 1; j < nck && need; j++) {
+        const uint64_t nj = n_of(j);
+        if (nj) take[j] = 1;
+        need = nj >= need ? 0 : need - nj;
+    }
+}
+
+// The layout of the decoded set for patterns of lengths lmin .. lmax: search_layout's groups, places and runs, with lmax - 1 carried bytes.
+// A tile is up to kSearchManyTile start positions of one run in one group; EVERY pattern is examined at each of them, pattern i under
+// i + L <= hi_end (hi_end: where the run's bytes end in this group, counted from src_off).  A start position belongs to the first group
+// that holds lmax bytes of the run from it on, or to the group in which the run ends: where the run goes on in the next group, the tiles
+// stop lmax - 1 bytes before the run's end in this one, and exactly those positions are the carried bytes in front of the next group's
+// first chunk.  So every position of a run is in exactly one tile, with all its patterns at once, and the tiles ascend: the pairs come out
+// in (position, pattern) order.  (Examining a pair in the first group that holds ITS bytes would find a short pattern at p + 1 a group
+// before a long one at p.)
+constexpr uint32_t kSearchManyTile = 16384;
+struct SearchManyTile { int64_t src_off; uint64_t gpos; uint32_t count, hi_end; };
+static_assert(sizeof(SearchManyTile) == 24, "a record shared with the kernels");
+struct SearchManyLayout {   // (the fields of SearchLayout)
+    std::vector<uint64_t> at;
+    std::vector<SearchManyTile> tiles;
+    std::vector<size_t> tile_end;
+    std::vector<uint32_t> carry;
+    std::vector<uint64_t> used;
+    uint64_t scratch_max = 0;
+};
+template <class Off, class N>
+void search_many_layout(size_t n_jobs, const std::vector<size_t>& gend, Off out_off_of, N n_of, uint32_t lmin, uint32_t lmax, SearchManyLayout* lay) {
+    const size_t ng = gend.size();
+    lay->at.assign(n_jobs, 0); lay->tiles.clear(); lay->tile_end.assign(ng, 0); lay->carry.assign(ng, 0); lay->used.assign(ng, 0); lay->scratch_max = 0;
+    auto adjacent = [&](size_t i) { return out_off_of(i - 1) + n_of(i - 1) == out_off_of(i); };
+    uint64_t run_have = 0;   // bytes of the current run that lie in the scratch in front of the next chunk
+    for (size_t g = 0, j0 = 0; g < ng; j0 = gend[g++]) {
+        const size_t j1 = gend[g];
+        uint64_t o = kSearchPad;
+        for (size_t j = j0; j < j1;) {
+            size_t e = j + 1;   // a part: jobs [j, e) are neighbours
+            while (e < j1 && adjacent(e)) e++;
+            if (!(j == j0 && j0 > 0 && adjacent(j0))) run_have = 0;
+            const uint64_t ps = o, gp = out_off_of(j);
+            for (size_t i = j; i < e; i++) { lay->at[i] = o; o += n_of(i); }
+            const uint64_t lower = ps - (run_have < lmax - 1 ? run_have : lmax - 1);
+            const uint32_t keep = e == j1 && j1 < n_jobs && adjacent(j1) ? lmax : lmin;   // (the run goes on in the next group : it ends here)
+            if (o - lower >= keep)
+                for (uint64_t s0 = lower, upper = o - keep + 1; s0 < upper; s0 += kSearchManyTile)
+                    lay->tiles.push_back(SearchManyTile{int64_t(s0), gp + s0 - ps, uint32_t(upper - s0 < kSearchManyTile ? upper - s0 : kSearchManyTile), uint32_t(o - s0)});
+            run_have += o - ps;
+            j = e;
+        }
+        lay->used[g] = o;
+        if (j1 < n_jobs && adjacent(j1)) lay->carry[g] = uint32_t(run_have < lmax - 1 ? run_have : lmax - 1);
+        if (o > lay->scratch_max) lay->scratch_max = o;
+        lay->tile_end[g] = lay->tiles.size();
+    }
+}
+
+// The pattern index of the scan: the key of a pattern is its first m = min(4, lmin) bytes, hashed to hb bits; heads[h] .. heads[h + 1] are the
+// places in `order` of the patterns whose key hashes to h, ascending by pattern index (a CSR), so a lane that walks a bucket meets the
+// patterns that match at its position in pattern order.  off[i] .. off[i + 1]: pattern i's bytes in the blob.  n <= 4096: 16-bit values do.
+// hb = the bits of n - 1 within 8 .. 12: about one entry per bucket at the most patterns, and at 12 bits the heads take 8 KiB of LDS.
+MLZ_SEARCH_HD uint32_t search_many_bits(uint32_t n) {
+    uint32_t b = 0;
+    for (uint32_t v = n ? n - 1 : 0; v; v >>= 1) b++;
+    return b < 8 ? 8 : b > 12 ? 12 : b;
+}
+// v: the bytes at a position, little-endian; those beyond m do not enter
+MLZ_SEARCH_HD uint32_t search_many_key(uint32_t v, uint32_t m, uint32_t hb) {
+    if (m < 4) v &= (1u << (8 * m)) - 1;
+    return (v * 2654435761u) >> (32 - hb);
+}
+struct SearchManyIndex {
+    uint32_t m = 0, hb = 0, lmin = 0, lmax = 0;
+    std::vector<uint16_t> heads, order;
+    std::vector<uint32_t> off;
+};
+// blob: the patterns back to back; len[i] in 1 .. 256, n in 1 .. kSearchMaxPatterns
+inline void search_many_index(const uint8_t* blob, const uint32_t* len, size_t n, SearchManyIndex* ix) {
+    ix->lmin = kSearchMaxPattern; ix->lmax = 1;
+    ix->off.assign(n + 1, 0);
+    for (size_t i = 0; i < n; i++) {
+        ix->off[i + 1] = ix->off[i] + len[i];
+        if (len[i] < ix->lmin) ix->lmin = len[i];
+        if (len[i] > ix->lmax) ix->lmax = len[i];
+    }
+    ix->m = ix->lmin < 4 ? ix->lmin : 4;
+    ix->hb = search_many_bits(uint32_t(n));
+    auto key = [&](size_t i) {
+        uint32_t v = 0;
+        for (uint32_t j = 0; j < ix->m; j++) v |= uint32_t(blob[ix->off[i] + j]) << (8 * j);
+        return search_many_key(v, ix->m, ix->hb);
+    };
+    const size_t nb = size_t(1) << ix->hb;
+    std::vector<uint32_t> fill(nb + 1, 0);
+    for (size_t i = 0; i < n; i++) fill[key(i) + 1]++;
+    for (size_t b = 0; b < nb; b++) fill[b + 1] += fill[b];
+    ix->heads.assign(fill.begin(), fill.end());
+    ix->order.assign(n, 0);
+    for (size_t i = 0; i < n; i++) ix->order[fill[key(i)]++] = uint16_t(i);   // (a counting sort: pattern order inside a bucket)
+}
+
+// The scan and write rule of one tile, as search_many_kernel applies it (and as the host check restates it with plain loops): the byte at
+// tile position i is s[i]; emit(i, pattern) is called for every pair the tile examines, positions ascending, patterns in bucket order.
+template <class Emit>
+inline void search_many_tile_pairs(const uint8_t* s, const SearchManyTile& t, const SearchManyIndex& ix, const uint8_t* blob, Emit emit) {
+    for (uint32_t i = 0; i < t.count; i++) {
+        uint32_t v = 0;
+        for (uint32_t j = 0; j < ix.m; j++) v |= uint32_t(s[i + j]) << (8 * j);
+        const uint32_t h = search_many_key(v, ix.m, ix.hb);
+        for (uint32_t e = ix.heads[h]; e < ix.heads[h + 1]; e++) {
+            const uint32_t p = ix.order[e], L = ix.off[p + 1] - ix.off[p];
+            if (i + L > t.hi_end) continue;
+            uint32_t j = 0;
+            while (j < L && s[i + j] == blob[ix.off[p] + j]) j++;
+            if (j == L) emit(i, p);
+        }
     }
 }
 

@@ -196,6 +196,93 @@ int64_t dev_reader_search_tables(mlz_dev_reader* rd, hipStream_t sm, bool ignore
     return 0;
 }
 
+// The decoded set of a search on its way through the scratch, shared by the search for one pattern and the search for many: the decode
+// list in stream order, its groups (range_group_ends), every chunk's place and the tiles of start positions (Lay: SearchLayout or
+// SearchManyLayout), the stored chunks' copies, and where the carried bytes, the tiles and the jobs' results lie in the two workspaces.
+template <class Lay> struct SearchDecode {
+    typedef typename decltype(Lay::tiles)::value_type Tile;
+    std::vector<ChunkJob> jobs;
+    std::vector<size_t> gend, place_end;
+    std::vector<PlaceDesc> places;   // stored chunks: copied from the stream
+    Lay lay;
+    Region<uint8_t> carry;
+    Region<Tile> tiles, htiles;
+    Region<PlaceDesc> hplaces;
+    ChunkJobResults res;
+};
+
+// layout(n_jobs, gend, out_off_of, n_of, &lay): search_layout or its sibling with the call's lengths
+template <class Lay, class LayoutFn>
+void search_decode_plan(const mlz_dev_reader* rd, const std::vector<uint8_t>& take, size_t n_take, LayoutFn layout, SearchDecode<Lay>* sd) {
+    const size_t nck = rd->chunks.size();
+    sd->jobs.reserve(n_take);
+    for (size_t k = 0; k < nck; k++) if (take[k]) sd->jobs.push_back(ChunkJob{k, nullptr});
+    const std::vector<ChunkJob>& jobs = sd->jobs;
+    mlz::range_group_ends(jobs.size(), [&](size_t i) { return uint64_t(rd->chunks[jobs[i].ck].n); }, &sd->gend);
+    layout(jobs.size(), sd->gend, [&](size_t i) { return uint64_t(rd->chunks[jobs[i].ck].out_off); }, [&](size_t i) { return uint64_t(rd->chunks[jobs[i].ck].n); }, &sd->lay);
+    const size_t ng = sd->gend.size();
+    sd->place_end.assign(ng, 0);
+    for (size_t g = 0, j0 = 0; g < ng; j0 = sd->gend[g++]) {
+        for (size_t i = j0; i < sd->gend[g]; i++) {
+            const StreamChunk& ck = rd->chunks[jobs[i].ck];
+            if (ck.type == kChunkUncompressed)
+                place_pieces(ck.body_off, sd->lay.at[i], ck.n, 1, [&](const PlaceDesc& d) { sd->places.push_back(d); });
+        }
+        sd->place_end[g] = sd->places.size();
+    }
+}
+
+// Its regions: carried bytes | tiles in the workspace (c->d_rplan), results | tiles | places in the pinned buffer
+template <class Lay> void search_decode_take(SearchDecode<Lay>* sd, Carve* cv, Carve* pin) {
+    typedef typename SearchDecode<Lay>::Tile Tile;
+    const size_t nt = sd->lay.tiles.size();
+    sd->carry = cv->take<uint8_t>(mlz::kSearchMaxPattern);
+    sd->tiles = cv->take<Tile>(nt);
+    sd->res = take_chunk_job_results(pin, sd->jobs.size());
+    sd->htiles = pin->take<Tile>(nt, 64);
+    sd->hplaces = pin->take<PlaceDesc>(sd->places.size(), 8);
+}
+
+// Every buffer of the call, once: the workspace and the pinned buffer as the caller carved them, the scratch, the copies' descriptors
+template <class Lay> int search_decode_ready(mlz_ctx* c, const SearchDecode<Lay>& sd, const Carve& cv, const Carve& pin) {
+    HIPCHK(c, c->d_rplan.ensure(cv.bytes));
+    HIPCHK(c, c->d_range.ensure(size_t(sd.lay.scratch_max) + 64));
+    if (!sd.places.empty()) HIPCHK(c, c->d_place.ensure(sd.places.size() * sizeof(PlaceDesc)));
+    return ensure_stream_objects(c, 0, pin.bytes);
+}
+
+// Decodes the set group by group into the scratch (stored chunks: copied), calls scan(g, t0, t1) for the tiles [t0, t1) of group g with its
+// bytes in place, and carries a run's last bytes in front of the next group.  Returns stream_run_chunk_jobs' verdict.
+template <class Lay, class Scan>
+int64_t search_decode_run(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, SearchDecode<Lay>* sd, Scan scan) {
+    typedef typename SearchDecode<Lay>::Tile Tile;
+    mlz_ctx* c = rd->ctx;
+    const Lay& lay = sd->lay;
+    const size_t nt = lay.tiles.size(), np = sd->places.size();
+    uint8_t *scratch = c->d_range.as<uint8_t>(), *d_carry = sd->carry.at(c->d_rplan.p);
+    Tile *d_tiles = sd->tiles.at(c->d_rplan.p), *h_tiles = sd->htiles.at(c->pinned2);
+    PlaceDesc* h_places = sd->hplaces.at(c->pinned2);
+    if (nt) std::memcpy(h_tiles, lay.tiles.data(), nt * sizeof(Tile));
+    if (np) std::memcpy(h_places, sd->places.data(), np * sizeof(PlaceDesc));
+    for (size_t i = 0; i < sd->jobs.size(); i++) {
+        const StreamChunk& ck = rd->chunks[sd->jobs[i].ck];
+        sd->jobs[i].at = ck.type == kChunkUncompressed ? rd->d_src + ck.body_off : scratch + lay.at[i];   // (a stored chunk's CRC: over the stream's own bytes)
+    }
+    if (nt) HIPCHK(c, hipMemcpyAsync(d_tiles, h_tiles, nt * sizeof(Tile), hipMemcpyHostToDevice, sm));
+    if (np) HIPCHK(c, hipMemcpyAsync(c->d_place.p, h_places, np * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
+    auto scan_group = [&](size_t g) -> int {
+        const size_t t0 = g ? lay.tile_end[g - 1] : 0, t1 = lay.tile_end[g], q0 = g ? sd->place_end[g - 1] : 0, q1 = sd->place_end[g];
+        if (q1 > q0) hipLaunchKernelGGL(stream_place_kernel, dim3(uint32_t(q1 - q0)), dim3(256), 0, sm, rd->d_src, rd->d_src, nullptr, scratch, c->d_place.as<PlaceDesc>() + q0);
+        if (t1 > t0) { const int e = scan(g, t0, t1); if (e) return e; }
+        if (lay.carry[g]) {   // the run goes on in the next group: its last bytes in front of that group's first chunk
+            HIPCHK(c, hipMemcpyAsync(d_carry, scratch + lay.used[g] - lay.carry[g], lay.carry[g], hipMemcpyDeviceToDevice, sm));
+            HIPCHK(c, hipMemcpyAsync(scratch + mlz::kSearchPad - lay.carry[g], d_carry, lay.carry[g], hipMemcpyDeviceToDevice, sm));
+        }
+        return 0;
+    };
+    return stream_run_chunk_jobs(c, sm, ignore_crc, rd->d_src, rd->chunks, sd->jobs, sd->gend, sd->res, scan_group);
+}
+
 int64_t dev_reader_search_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* pattern, uint32_t L, uint64_t* d_offsets, uint64_t cap, uint64_t* stats) {
     mlz_ctx* c = rd->ctx;
     const size_t nck = rd->chunks.size();
@@ -254,75 +341,31 @@ int64_t dev_reader_search_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t fl
     if (n_take == 0) return 0;
 
     // the decode list, its groups, every chunk's place in the scratch and the tiles of start positions (search_layout), the stored chunks' copies
-    std::vector<ChunkJob> jobs;
-    jobs.reserve(n_take);
-    for (size_t k = 0; k < nck; k++) if (take[k]) jobs.push_back(ChunkJob{k, nullptr});
-    std::vector<size_t> gend;
-    mlz::range_group_ends(jobs.size(), [&](size_t i) { return uint64_t(rd->chunks[jobs[i].ck].n); }, &gend);
-    const size_t ng = gend.size();
-    mlz::SearchLayout lay;
-    mlz::search_layout(jobs.size(), gend, [&](size_t i) { return uint64_t(rd->chunks[jobs[i].ck].out_off); }, [&](size_t i) { return uint64_t(rd->chunks[jobs[i].ck].n); }, L, &lay);
-    const std::vector<uint64_t>& at = lay.at;
-    const std::vector<mlz::SearchTile>& tiles = lay.tiles;
-    const std::vector<size_t>& tile_end = lay.tile_end;
-    const std::vector<uint32_t>& carry = lay.carry;
-    const std::vector<uint64_t>& used = lay.used;
-    const uint64_t scratch_max = lay.scratch_max;
-    std::vector<size_t> place_end(ng);
-    std::vector<PlaceDesc> places;   // stored chunks: copied from the stream
-    for (size_t g = 0, j0 = 0; g < ng; j0 = gend[g++]) {
-        for (size_t i = j0; i < gend[g]; i++) {
-            const StreamChunk& ck = rd->chunks[jobs[i].ck];
-            if (ck.type == kChunkUncompressed)
-                place_pieces(ck.body_off, at[i], ck.n, 1, [&](const PlaceDesc& d) { places.push_back(d); });
-        }
-        place_end[g] = places.size();
-    }
-    const size_t nt = tiles.size(), np = places.size();
+    SearchDecode<mlz::SearchLayout> sd;
+    search_decode_plan(rd, take, n_take, [&](size_t nj, const std::vector<size_t>& gend, auto off_of, auto n_of, mlz::SearchLayout* lay) { mlz::search_layout(nj, gend, off_of, n_of, L, lay); }, &sd);
+    const size_t nt = sd.lay.tiles.size();
     if (nt > 0x7fffffffu) return -MLZ_ERR_ARG;
-    Carve cv, pin;   // workspace: pattern | carried bytes | total | tiles | counts | prefix | bitmaps; pinned: results | tiles | places | pattern
-    const auto r_pat = cv.take<uint8_t>(mlz::kSearchMaxPattern), r_carry = cv.take<uint8_t>(mlz::kSearchMaxPattern);
+    Carve cv, pin;   // workspace: pattern | total | counts | prefix | bitmaps | the decode's; pinned: the decode's | pattern
+    const auto r_pat = cv.take<uint8_t>(mlz::kSearchMaxPattern);
     const auto r_total = cv.take<uint64_t>(2);
-    const auto r_tiles = cv.take<mlz::SearchTile>(nt);
     const auto r_counts = cv.take<uint32_t>(nt, 4);
     const auto r_prefix = cv.take<uint64_t>(nt), r_masks = cv.take<uint64_t>(nt * mlz::kSearchTileWords, 8);
-    const ChunkJobResults res = take_chunk_job_results(&pin, jobs.size());
-    const auto r_htiles = pin.take<mlz::SearchTile>(nt, 64);
-    const auto r_hplaces = pin.take<PlaceDesc>(np, 8);
+    search_decode_take(&sd, &cv, &pin);
     const auto r_hpat = pin.take<uint8_t>(mlz::kSearchMaxPattern + 16, 8);
-    HIPCHK(c, c->d_rplan.ensure(cv.bytes));
-    HIPCHK(c, c->d_range.ensure(size_t(scratch_max) + 64));
-    if (np) HIPCHK(c, c->d_place.ensure(np * sizeof(PlaceDesc)));
-    int e = ensure_stream_objects(c, 0, pin.bytes);
+    int e = search_decode_ready(c, sd, cv, pin);
     if (e) return e;
-    uint8_t *ws = r_pat.at(c->d_rplan.p), *h_pat = r_hpat.at(c->pinned2), *scratch = c->d_range.as<uint8_t>();
-    mlz::SearchTile *d_tiles = r_tiles.at(c->d_rplan.p), *h_tiles = r_htiles.at(c->pinned2);
-    PlaceDesc* h_places = r_hplaces.at(c->pinned2);
-    if (nt) std::memcpy(h_tiles, tiles.data(), nt * sizeof(mlz::SearchTile));
-    if (np) std::memcpy(h_places, places.data(), np * sizeof(PlaceDesc));
+    uint8_t *ws = r_pat.at(c->d_rplan.p), *h_pat = r_hpat.at(c->pinned2);
     std::memcpy(h_pat, pattern, L);
     uint32_t* d_counts = r_counts.at(c->d_rplan.p);
     uint64_t *d_prefix = r_prefix.at(c->d_rplan.p), *d_masks = r_masks.at(c->d_rplan.p), *d_total = r_total.at(c->d_rplan.p);
-    for (size_t i = 0; i < jobs.size(); i++) {
-        const StreamChunk& ck = rd->chunks[jobs[i].ck];
-        jobs[i].at = ck.type == kChunkUncompressed ? rd->d_src + ck.body_off : scratch + at[i];   // (a stored chunk's CRC: over the stream's own bytes)
-    }
+    const mlz::SearchTile* d_tiles = sd.tiles.at(c->d_rplan.p);
     { WorkspaceOrder order(c, sm); }
     HIPCHK(c, hipMemcpyAsync(ws, h_pat, L, hipMemcpyHostToDevice, sm));
     HIPCHK(c, hipMemsetAsync(d_total, 0, 16, sm));
-    if (nt) HIPCHK(c, hipMemcpyAsync(d_tiles, h_tiles, nt * sizeof(mlz::SearchTile), hipMemcpyHostToDevice, sm));
-    if (np) HIPCHK(c, hipMemcpyAsync(c->d_place.p, h_places, np * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
-    auto scan_group = [&](size_t g) -> int {
-        const size_t t0 = g ? tile_end[g - 1] : 0, t1 = tile_end[g], q0 = g ? place_end[g - 1] : 0, q1 = place_end[g];
-        if (q1 > q0) hipLaunchKernelGGL(stream_place_kernel, dim3(uint32_t(q1 - q0)), dim3(256), 0, sm, rd->d_src, rd->d_src, nullptr, scratch, c->d_place.as<PlaceDesc>() + q0);
-        if (t1 > t0) hipLaunchKernelGGL(mlz::search_scan_kernel, dim3(uint32_t(t1 - t0)), dim3(256), 0, sm, scratch, d_tiles, uint32_t(t0), ws, L, d_masks, d_counts);
-        if (carry[g]) {   // the run goes on in the next group: its last bytes in front of that group's first chunk
-            HIPCHK(c, hipMemcpyAsync(ws + r_carry.off, scratch + used[g] - carry[g], carry[g], hipMemcpyDeviceToDevice, sm));
-            HIPCHK(c, hipMemcpyAsync(scratch + mlz::kSearchPad - carry[g], ws + r_carry.off, carry[g], hipMemcpyDeviceToDevice, sm));
-        }
+    const int64_t r = search_decode_run(rd, sm, ignore_crc, &sd, [&](size_t, size_t t0, size_t t1) {
+        hipLaunchKernelGGL(mlz::search_scan_kernel, dim3(uint32_t(t1 - t0)), dim3(256), 0, sm, c->d_range.as<uint8_t>(), d_tiles, uint32_t(t0), ws, L, d_masks, d_counts);
         return 0;
-    };
-    const int64_t r = stream_run_chunk_jobs(c, sm, ignore_crc, rd->d_src, rd->chunks, jobs, gend, res, scan_group);
+    });
     if (r < 0) return r;
     if (nt == 0) return 0;
     hipLaunchKernelGGL(mlz::search_prefix_kernel, dim3(1), dim3(1024), 0, sm, d_counts, uint32_t(nt), d_prefix, d_total);

@@ -1,0 +1,324 @@
+// mlz_stream_search_many.hip.inc — mlz_dev_reader_search_many: where each of up to 4096 byte strings occurs in a .mz stream that lies in HBM,
+// in one call (included behind mlz_stream_search.hip.inc, whose per-handle tables, decode helpers and prefix rule it uses).
+//
+// Plan: the host computes every pattern's windows and their hashes (search_windows, search_hash: work proportional to the patterns);
+// search_many_plan_kernel, one lane per (data chunk, pattern), probes the chunk's table and the next one's and applies the decoded-set rule
+// of that pattern (search_decoded_mark) to ONE byte array: the union of the patterns' sets.  Only those nck bytes come back.  A pattern the
+// tables cannot serve puts every chunk into the set, so the kernel is not run then.
+// Scan: the set is decoded once, group by group (search_decode_run), and search_many_kernel<false> examines each tile of start positions:
+// the tile's bytes are staged in LDS, a lane walks 64 neighbouring positions, hashes the first m bytes of each to a bucket of the pattern
+// index (heads and order in LDS) and verifies the bucket's patterns as far as the run holds their bytes.  Per-pattern counts gather in LDS and leave
+// with one 64-bit atomic per non-zero counter.  Per group, search_many_prefix_kernel then continues the running sum over the tile counts
+// and search_many_kernel<true> finds the pairs of the tiles below `cap` again, while the group's bytes are still in the scratch, and
+// writes (position, pattern) in ascending order.
+
+namespace mlz {
+
+// What the scan needs of a SearchManyIndex, in device memory
+struct SearchManyIx { const uint16_t* heads; const uint16_t* order; const uint32_t* off; const uint8_t* blob; uint32_t n, hb, m, lmax, blob_bytes, in_lds; };
+
+constexpr uint32_t kSearchManyThreads = 256, kSearchManyPer = kSearchManyTile / kSearchManyThreads;
+static_assert(kSearchManyPer == 64, "a lane's positions are one skew unit");
+// The tile's bytes in LDS: a word of padding behind every 64 bytes, so that the lanes' words (17 apart) fall into different banks
+__host__ __device__ constexpr uint32_t search_many_skew(uint32_t b) { return b + ((b >> 6) << 2); }
+constexpr uint32_t kSearchManyTileLds = (search_many_skew(kSearchManyTile + kSearchMaxPattern + 8) + 8) & ~3u;
+// LDS of one workgroup, in words: heads | order | per-pattern counters | scan | tile bytes | (pattern offsets | pattern bytes, when they fit)
+constexpr uint32_t kSearchManyLdsBudget = 64u << 10;
+struct SearchManyLds { uint32_t heads, order, counts, scan, tile, off, blob, words; };
+__host__ __device__ inline SearchManyLds search_many_lds(uint32_t n, uint32_t hb, uint32_t blob_bytes, bool in_lds) {
+    SearchManyLds l;
+    uint32_t w = 0;
+    l.heads = w; w += ((1u << hb) + 2) / 2;
+    l.order = w; w += (n + 1) / 2;
+    l.counts = w; w += n;
+    l.scan = w; w += kSearchManyThreads;
+    l.tile = w; w += kSearchManyTileLds / 4;
+    l.off = l.blob = w;
+    if (in_lds) { w += n + 1; l.blob = w; w += (blob_bytes + 3) / 4; }
+    l.words = w;
+    return l;
+}
+
+// One lane per (data chunk, served pattern): the pattern's decoded-set rule for that chunk, ORed into take[]
+__global__ __launch_bounds__(256) void search_many_plan_kernel(const uint8_t* __restrict__ src, const SearchTab* __restrict__ tabs, const uint64_t* __restrict__ n_of, uint32_t nck,
+                                                               uint32_t B, const uint32_t* __restrict__ hashes, const SearchManyPat* __restrict__ pats, uint32_t np,
+                                                               uint8_t* __restrict__ take) {
+    const uint64_t idx = uint64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (idx >= uint64_t(nck) * np) return;
+    const uint32_t k = uint32_t(idx % nck);
+    const SearchManyPat pt = pats[idx / nck];
+    const uint32_t* h = hashes + pt.h_off;
+    auto probe = [&](size_t j, bool lead) {
+        const SearchTab t = tabs[j];
+        uint32_t a = pt.nw, s = pt.nw;
+        if (t.R != kSearchNoTable) search_probe(src + t.off, B - t.R, h, pt.nw, &a, &s, pt.gsize);
+        return lead ? a : s;
+    };
+    search_decoded_mark(k, nck, [&](size_t j) { return probe(j, true); }, [&](size_t j) { return probe(j, false); }, [&](size_t j) { return n_of[j]; }, pt.nw, pt.L, take, pt.t_min);
+}
+
+// One workgroup per tile.  kWrite = false: counts[tile] = the tile's pairs, pat_counts[p] += pattern p's.  kWrite = true: the pairs of a tile
+// whose first pair lies below cap go to out_pos / out_which from prefix[tile] on, as far as they lie below cap.
+template <bool kWrite>
+__global__ __launch_bounds__(kSearchManyThreads) void search_many_kernel(const uint8_t* __restrict__ scratch, const SearchManyTile* __restrict__ tiles, uint32_t tile0, SearchManyIx ix,
+                                                                         uint32_t* __restrict__ tile_counts, unsigned long long* __restrict__ pat_counts,
+                                                                         const uint64_t* __restrict__ prefix, uint64_t cap, uint64_t* __restrict__ out_pos,
+                                                                         uint32_t* __restrict__ out_which) {
+    extern __shared__ uint32_t lds[];
+    const uint32_t tid = threadIdx.x, tile = tile0 + blockIdx.x;
+    uint64_t first = 0;
+    if (kWrite) {
+        first = prefix[tile];
+        if (first >= cap) return;   // (the whole workgroup)
+    }
+    const SearchManyLds l = search_many_lds(ix.n, ix.hb, ix.blob_bytes, ix.in_lds != 0);
+    uint16_t *heads = reinterpret_cast<uint16_t*>(lds + l.heads), *order = reinterpret_cast<uint16_t*>(lds + l.order);
+    uint32_t *counts = lds + l.counts, *scan = lds + l.scan, *tw = lds + l.tile;
+    const uint8_t* tb = reinterpret_cast<const uint8_t*>(tw);
+    const SearchManyTile t = tiles[tile];
+    for (uint32_t i = tid; i < (1u << ix.hb) + 1; i += kSearchManyThreads) heads[i] = ix.heads[i];
+    for (uint32_t i = tid; i < ix.n; i += kSearchManyThreads) order[i] = ix.order[i];
+    if (!kWrite) for (uint32_t i = tid; i < ix.n; i += kSearchManyThreads) counts[i] = 0;
+    const uint32_t* off = ix.off;
+    const uint8_t* blob = ix.blob;
+    if (ix.in_lds) {
+        uint32_t *lo = lds + l.off, *lb = lds + l.blob;
+        for (uint32_t i = tid; i < ix.n + 1; i += kSearchManyThreads) lo[i] = ix.off[i];
+        const uint32_t* gb = reinterpret_cast<const uint32_t*>(ix.blob);   // (the blob's room is a whole number of words)
+        for (uint32_t i = tid; i < (ix.blob_bytes + 3) / 4; i += kSearchManyThreads) lb[i] = gb[i];
+        off = lo;
+        blob = reinterpret_cast<const uint8_t*>(lb);
+    }
+    // the bytes the tile's pairs can touch: count - 1 + lmax from src_off on, as far as the run has them in this group; whole words from
+    // the word that holds src_off (the scratch has room behind its last chunk)
+    const uint32_t shift = uint32_t(t.src_off) & 3;
+    uint32_t avail = t.count - 1 + ix.lmax;
+    if (avail > t.hi_end) avail = t.hi_end;
+    const uint32_t* gw = reinterpret_cast<const uint32_t*>(scratch + (t.src_off - shift));
+    for (uint32_t w = tid; w < (shift + avail + 3) / 4; w += kSearchManyThreads) tw[w + (w >> 4)] = gw[w];
+    __syncthreads();
+    auto byte_at = [&](uint32_t i) { return uint32_t(tb[search_many_skew(shift + i)]); };
+    const uint32_t i0 = tid * kSearchManyPer, i1 = i0 + kSearchManyPer < t.count ? i0 + kSearchManyPer : t.count;
+    auto walk = [&](auto emit) {
+        if (i0 >= i1) return;
+        uint32_t w = byte_at(i0) | byte_at(i0 + 1) << 8 | byte_at(i0 + 2) << 16;   // (bytes beyond the tile's: in the LDS array, masked off or unused)
+        for (uint32_t i = i0; i < i1; i++) {
+            w |= byte_at(i + 3) << 24;
+            const uint32_t h = search_many_key(w, ix.m, ix.hb);
+            w >>= 8;
+            for (uint32_t e = heads[h], e1 = heads[h + 1]; e < e1; e++) {
+                const uint32_t p = order[e], po = off[p], L = off[p + 1] - po, end = i + L;
+                if (end > t.hi_end) continue;   // (the run ends in this group, in front of the pattern's end)
+                uint32_t j = 0;
+                while (j < L && byte_at(i + j) == blob[po + j]) j++;
+                if (j == L) emit(i, p);
+            }
+        }
+    };
+    auto plus = [](uint32_t x, uint32_t y) { return x + y; };
+    uint32_t cnt = 0;
+    if (!kWrite) {
+        walk([&](uint32_t, uint32_t p) { atomicAdd(&counts[p], 1u); cnt++; });
+        uint32_t total;
+        wg_scan<kSearchManyThreads>(cnt, scan, tid, plus, &total);   // (its barriers also settle the counters)
+        if (tid == 0) tile_counts[tile] = total;
+        for (uint32_t i = tid; i < ix.n; i += kSearchManyThreads) {
+            const uint32_t v = counts[i];
+            if (v) atomicAdd(&pat_counts[i], static_cast<unsigned long long>(v));
+        }
+    } else {
+        walk([&](uint32_t, uint32_t) { cnt++; });
+        uint64_t at = first + wg_scan<kSearchManyThreads>(cnt, scan, tid, plus);
+        walk([&](uint32_t i, uint32_t p) {
+            if (at < cap) { out_pos[at] = t.gpos + i; out_which[at] = p; }
+            at++;
+        });
+    }
+}
+
+// prefix[i] = *total + the pairs of the tiles [t0, i) for t0 <= i < t1, then *total += all of them: run group by group, in stream order
+__global__ __launch_bounds__(1024) void search_many_prefix_kernel(const uint32_t* __restrict__ counts, uint32_t t0, uint32_t t1, uint64_t* __restrict__ prefix, uint64_t* __restrict__ total) {
+    __shared__ uint64_t lds[1024];
+    const uint32_t tid = threadIdx.x;
+    uint64_t carry = *total;
+    for (uint32_t base = t0; base < t1; base += 1024) {
+        const uint32_t i = base + tid;
+        uint64_t sum;
+        const uint64_t before = wg_scan<1024>(uint64_t(i < t1 ? counts[i] : 0), lds, tid, [](uint64_t x, uint64_t y) { return x + y; }, &sum);
+        if (i < t1) prefix[i] = carry + before;
+        carry += sum;
+    }
+    __syncthreads();   // (every lane has read *total)
+    if (tid == 0) *total = carry;
+}
+
+}  // namespace mlz
+
+namespace {
+
+// The union of the patterns' decoded sets -> take[], their number; stats[2], stats[3] and the context's counter 11.  off[i]: pattern i's bytes in `patterns`.
+int64_t dev_reader_search_many_plan(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* patterns, const std::vector<uint32_t>& off, size_t n,
+                                    std::vector<uint8_t>* take, size_t* n_take, uint64_t* unserved) {
+    mlz_ctx* c = rd->ctx;
+    const size_t nck = rd->chunks.size();
+    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0;
+    *unserved = n;
+    if (!(flags & MLZ_SEARCH_NO_TABLES)) {
+        const int64_t r = dev_reader_search_tables(rd, sm, ignore_crc);
+        if (r) return r;
+        const mlz_dev_reader::SearchTables& st = rd->search[ignore_crc ? 1 : 0];
+        if (st.info && st.usable) {
+            std::vector<uint32_t> win(st.T == 4 ? mlz::kSearchMaxWindows : mlz::kSearchMaxPattern), hs;
+            std::vector<mlz::SearchManyPat> pats;
+            for (size_t i = 0; i < n; i++) {
+                const uint8_t* p = patterns + off[i];
+                const uint32_t L = off[i + 1] - off[i];
+                uint32_t t_min = 1, gsize = 1;
+                const uint32_t nw = mlz::search_windows(p, L, st.T, st.M, st.field, win.data(), &t_min, &gsize);
+                if (!nw) continue;
+                pats.push_back(mlz::SearchManyPat{uint32_t(hs.size()), nw, gsize, t_min, L, 0});
+                for (uint32_t w = 0; w < nw * gsize; w++) {
+                    uint64_t v = 0;
+                    for (uint32_t j = 0; j < st.M; j++) v |= uint64_t(p[win[w] + j]) << (8 * j);
+                    hs.push_back(mlz::search_hash(v, st.B, st.M));
+                }
+            }
+            *unserved = n - pats.size();
+            if (!pats.empty()) c->search_tables = st.usable;
+            if (*unserved == 0) {
+                // hashes, pattern records and the chunks' sizes go up as one block, staged in the pinned buffer; one byte per chunk comes back
+                Carve up;
+                const auto u_hs = up.take<uint32_t>(hs.size());
+                const auto u_pats = up.take<mlz::SearchManyPat>(pats.size());
+                const auto u_n = up.take<uint64_t>(nck);
+                Carve cv;
+                const auto r_up = cv.take<uint8_t>(up.bytes);
+                const auto r_take = cv.take<uint8_t>(nck);
+                HIPCHK(c, c->d_rplan.ensure(cv.bytes));
+                int e = ensure_stream_objects(c, 0, up.bytes > nck ? up.bytes : nck);
+                if (e) return e;
+                void *ws = r_up.at(c->d_rplan.p), *h_up = c->pinned2;
+                std::memcpy(u_hs.at(h_up), hs.data(), hs.size() * 4);
+                std::memcpy(u_pats.at(h_up), pats.data(), pats.size() * sizeof(mlz::SearchManyPat));
+                uint64_t* h_n = u_n.at(h_up);
+                for (size_t k = 0; k < nck; k++) h_n[k] = rd->chunks[k].n;
+                uint8_t* d_take = r_take.at(c->d_rplan.p);
+                { WorkspaceOrder order(c, sm); }
+                HIPCHK(c, hipMemcpyAsync(ws, h_up, up.bytes, hipMemcpyHostToDevice, sm));
+                HIPCHK(c, hipMemsetAsync(d_take, 0, nck, sm));
+                const uint64_t lanes = uint64_t(nck) * pats.size();
+                hipLaunchKernelGGL(mlz::search_many_plan_kernel, dim3(uint32_t((lanes + 255) / 256)), dim3(256), 0, sm, rd->d_src, static_cast<const mlz::SearchTab*>(st.d_tabs),
+                                   u_n.at(ws), uint32_t(nck), st.B, u_hs.at(ws), u_pats.at(ws), uint32_t(pats.size()), d_take);
+                if ((e = fetch(c, sm, c->pinned2, d_take, nck))) return e;   // (behind the upload on sm: the staged block has left the pinned buffer)
+                std::memcpy(take->data(), c->pinned2, nck);
+                *n_take = 0;
+                for (size_t k = 0; k < nck; k++) *n_take += (*take)[k];
+                return 0;
+            }
+        }
+    }
+    *n_take = 0;   // a pattern the tables cannot serve: every chunk that holds a byte
+    for (size_t k = 0; k < nck; k++) *n_take += ((*take)[k] = rd->chunks[k].n ? 1 : 0);
+    return 0;
+}
+
+int64_t dev_reader_search_many_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* patterns, const uint32_t* pattern_len, size_t n, uint64_t* d_counts,
+                                      uint64_t* d_offsets, uint32_t* d_which, uint64_t cap, uint64_t* stats) {
+    mlz_ctx* c = rd->ctx;
+    const size_t nck = rd->chunks.size();
+    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0;
+    c->search_chunks = c->search_tables = 0;
+    if (stats) { stats[0] = nck; stats[1] = stats[2] = stats[3] = 0; }
+    HIPCHK(c, hipSetDevice(c->device));
+    auto nothing = [&]() -> int64_t {   // no chunk to scan: every count is 0
+        if (d_counts) {
+            HIPCHK(c, hipMemsetAsync(d_counts, 0, n * 8, sm));
+            HIPCHK(c, hipStreamSynchronize(sm));
+        }
+        return 0;
+    };
+    if (nck == 0) return nothing();
+    mlz::SearchManyIndex index;
+    mlz::search_many_index(patterns, pattern_len, n, &index);
+    std::vector<uint8_t> take(nck, 0);
+    size_t n_take = 0;
+    uint64_t unserved = 0;
+    const int64_t pr = dev_reader_search_many_plan(rd, sm, flags, patterns, index.off, n, &take, &n_take, &unserved);
+    if (pr) return pr;
+    c->search_chunks = n_take;
+    if (stats) { stats[1] = n_take; stats[2] = c->search_tables; stats[3] = unserved; }
+    if (n_take == 0) return nothing();
+
+    SearchDecode<mlz::SearchManyLayout> sd;
+    search_decode_plan(rd, take, n_take, [&](size_t nj, const std::vector<size_t>& gend, auto off_of, auto n_of, mlz::SearchManyLayout* lay) {
+        mlz::search_many_layout(nj, gend, off_of, n_of, index.lmin, index.lmax, lay);
+    }, &sd);
+    const size_t nt = sd.lay.tiles.size(), nheads = index.heads.size();
+    if (nt > 0x7fffffffu) return -MLZ_ERR_ARG;
+    const uint32_t blob_bytes = index.off[n];
+    Carve up;        // the pattern index as one block: heads | order | offsets | pattern bytes (a whole number of words)
+    const auto u_heads = up.take<uint16_t>(nheads), u_order = up.take<uint16_t>(n);
+    const auto u_off = up.take<uint32_t>(n + 1);
+    const auto u_blob = up.take<uint8_t>(size_t(blob_bytes) + 4);
+    Carve cv, pin;   // workspace: per-pattern counts | total | the index | tile counts | prefix | the decode's; pinned: the decode's | the index
+    const auto r_pc = cv.take<unsigned long long>(n);
+    const auto r_total = cv.take<uint64_t>(2);
+    const auto r_up = cv.take<uint8_t>(up.bytes);
+    const auto r_counts = cv.take<uint32_t>(nt, 4);
+    const auto r_prefix = cv.take<uint64_t>(nt);
+    search_decode_take(&sd, &cv, &pin);
+    const auto r_hup = pin.take<uint8_t>(up.bytes);
+    int e = search_decode_ready(c, sd, cv, pin);
+    if (e) return e;
+    void* ws = c->d_rplan.p;
+    unsigned long long* d_pc = r_pc.at(ws);
+    uint64_t *d_total = r_total.at(ws), *d_prefix = r_prefix.at(ws);
+    uint32_t* d_tc = r_counts.at(ws);
+    const mlz::SearchManyTile* d_tiles = sd.tiles.at(ws);
+    const bool in_lds = mlz::search_many_lds(uint32_t(n), index.hb, blob_bytes, true).words * 4 <= mlz::kSearchManyLdsBudget;
+    void *d_up = r_up.at(ws), *h_up = r_hup.at(c->pinned2);
+    std::memcpy(u_heads.at(h_up), index.heads.data(), nheads * 2);
+    std::memcpy(u_order.at(h_up), index.order.data(), n * 2);
+    std::memcpy(u_off.at(h_up), index.off.data(), (n + 1) * 4);
+    std::memcpy(u_blob.at(h_up), patterns, blob_bytes);
+    const mlz::SearchManyIx ix{u_heads.at(d_up), u_order.at(d_up), u_off.at(d_up), u_blob.at(d_up), uint32_t(n), index.hb, index.m, index.lmax, blob_bytes, in_lds ? 1u : 0u};
+    const uint32_t lds_bytes = mlz::search_many_lds(uint32_t(n), index.hb, blob_bytes, in_lds).words * 4;
+    { WorkspaceOrder order(c, sm); }
+    HIPCHK(c, hipMemsetAsync(d_pc, 0, n * sizeof(unsigned long long), sm));
+    HIPCHK(c, hipMemsetAsync(d_total, 0, 16, sm));
+    HIPCHK(c, hipMemcpyAsync(d_up, h_up, up.bytes, hipMemcpyHostToDevice, sm));
+    const int64_t r = search_decode_run(rd, sm, ignore_crc, &sd, [&](size_t, size_t t0, size_t t1) {
+        const uint8_t* scratch = c->d_range.as<uint8_t>();
+        hipLaunchKernelGGL(mlz::search_many_kernel<false>, dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), lds_bytes, sm, scratch, d_tiles, uint32_t(t0), ix, d_tc, d_pc,
+                           static_cast<const uint64_t*>(nullptr), uint64_t(0), static_cast<uint64_t*>(nullptr), static_cast<uint32_t*>(nullptr));
+        hipLaunchKernelGGL(mlz::search_many_prefix_kernel, dim3(1), dim3(1024), 0, sm, d_tc, uint32_t(t0), uint32_t(t1), d_prefix, d_total);
+        if (cap) hipLaunchKernelGGL(mlz::search_many_kernel<true>, dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), lds_bytes, sm, scratch, d_tiles, uint32_t(t0), ix, d_tc, d_pc,
+                                    static_cast<const uint64_t*>(d_prefix), cap, d_offsets, d_which);
+        return 0;
+    });
+    if (r < 0) return r;
+    if (d_counts) HIPCHK(c, hipMemcpyAsync(d_counts, d_pc, n * 8, hipMemcpyDeviceToDevice, sm));
+    if ((e = fetch(c, sm, c->pinned2, d_total, 8))) return e;
+    return int64_t(*static_cast<const uint64_t*>(c->pinned2));
+}
+
+}  // namespace
+
+extern "C" int64_t mlz_dev_reader_search_many(mlz_dev_reader* rd, void* stream, uint32_t flags, const uint8_t* patterns, const uint32_t* pattern_len, size_t n_patterns,
+                                              uint64_t* d_counts, uint64_t* d_offsets, uint32_t* d_which, size_t cap, uint64_t* stats) {
+    if (!rd || n_patterns > MLZ_SEARCH_MAX_PATTERNS || (n_patterns && (!patterns || !pattern_len)) || (cap && (!d_offsets || !d_which))) return -MLZ_ERR_ARG;
+    for (size_t i = 0; i < n_patterns; i++)
+        if (pattern_len[i] == 0 || pattern_len[i] > mlz::kSearchMaxPattern) return -MLZ_ERR_ARG;
+    mlz_ctx* c = rd->ctx;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
+    if (n_patterns && ((d_counts && !on_device(c, d_counts)) || (cap && (!on_device(c, d_offsets) || !on_device(c, d_which))))) return -MLZ_ERR_ARG;
+    if (n_patterns == 0) {
+        c->search_chunks = c->search_tables = 0;
+        if (stats) { stats[0] = rd->chunks.size(); stats[1] = stats[2] = stats[3] = 0; }
+        return 0;
+    }
+    begin_decode_call(c);
+    hipStream_t sm = static_cast<hipStream_t>(stream);
+    return settled(sm, dev_reader_search_many_locked(rd, sm, flags, patterns, pattern_len, n_patterns, d_counts, d_offsets, d_which, uint64_t(cap), stats));
+}

@@ -233,6 +233,22 @@ class DeviceStream:
         total, _ = self.reader.search(pattern, out.data_ptr() if max_results else None, max_results, ignore_crc=ignore_crc, no_tables=no_tables, stream=st)
         return out[:min(total, max_results)], total
 
+    def search_many(self, patterns, max_results, ignore_crc=False, no_tables=False):
+        """Where each of `patterns` (a sequence of up to 4096 bytes objects of 1 .. 256 bytes) occurs in the decoded stream, in one pass over
+        the blocks that any pattern's search tables admit -> (positions int64, which int32, counts int64, total): the smallest
+        min(total, max_results) pairs (position, pattern index) in ascending order, every pattern's own number of occurrences and the
+        number of all pairs; tensors on the stream's device."""
+        dev = self.t.device
+        pats = list(patterns)
+        pos = torch.empty(max(max_results, 1), dtype=torch.int64, device=dev)
+        which = torch.empty(max(max_results, 1), dtype=torch.int32, device=dev)
+        counts = torch.zeros(max(len(pats), 1), dtype=torch.int64, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        total, _ = self.reader.search_many(pats, counts.data_ptr(), pos.data_ptr() if max_results else None, which.data_ptr() if max_results else None, max_results,
+                                           ignore_crc=ignore_crc, no_tables=no_tables, stream=st)
+        k = min(total, max_results)
+        return pos[:k], which[:k], counts[:len(pats)], total
+
     def ReadAt(self, n, offset, ignore_crc=False):
         """Up to n decoded bytes from `offset`, clamped at the end of the stream -> a new uint8 tensor."""
         if n < 0 or offset < 0 or offset > self.size:
