@@ -1,8 +1,9 @@
 // mlz_stream_search.h — what the block search tables' writer, the device-resident pattern search (mlz_stream_search.hip.inc) and their host
 // check (tools/stream_search_check.cpp) share: the table hash (SPEC_SEARCH.md 3.1), the size and the bytes of a table chunk (2.0, 2.1, 3.2),
 // the probe of one table and the rule that turns the probes of all chunks into the set of chunks to decode (Appendix B.4.1).
-// For the search for many patterns (mlz_stream_search_many.hip.inc, tools/stream_search_many_check.cpp): the marking form of that rule, the
-// layout for patterns of several lengths, the pattern index and the scan rule of one tile.
+// Both searches (one pattern, and many in one call: mlz_stream_search_many.hip.inc, tools/stream_search_many_check.cpp) use one rule per
+// chunk (search_decoded_mark), one pattern record with its window hashes (search_pattern_hashes) and one layout of the decoded set in the
+// scratch (search_layout, for patterns of lengths lmin .. lmax); the search for many adds the pattern index and the scan rule of one tile.
 // Plain C++: compiles for the host alone and for gfx950.  Table types 1 (no prefix), 2 (1 to 8 prefix byte values), 3 (a 256-bit mask of
 // prefix byte values; SPEC_SEARCH.md 3.3) and 4 (a long prefix of 1 to 256 bytes with extra matches; 3.3.4), uncompressed table chunks (0x45) only.
 #pragma once
@@ -130,6 +131,26 @@ MLZ_SEARCH_HD uint32_t search_windows(const uint8_t* pat, uint32_t L, uint32_t T
     return nw;
 }
 
+// One pattern as the plan sees it: its nw groups of gsize window hashes lie at hashes[h_off ...); t_min and L as in search_decoded_mark.
+struct SearchManyPat { uint32_t h_off, nw, gsize, t_min, L, pad; };
+static_assert(sizeof(SearchManyPat) == 24, "a record shared with the kernels");
+
+// The pattern's record and its window hashes, appended to *hs: search_windows (win: its room), then per window the M bytes little-endian,
+// hashed at B bits.  False, and nothing appended: the tables cannot serve this pattern.
+inline bool search_pattern_hashes(const uint8_t* pat, uint32_t L, uint32_t T, uint32_t M, uint32_t B, const uint8_t* field, uint32_t* win, std::vector<uint32_t>* hs,
+                                  SearchManyPat* out) {
+    uint32_t t_min = 1, gsize = 1;
+    const uint32_t nw = search_windows(pat, L, T, M, field, win, &t_min, &gsize);
+    if (!nw) return false;
+    *out = SearchManyPat{uint32_t(hs->size()), nw, gsize, t_min, L, 0};
+    for (uint32_t w = 0; w < nw * gsize; w++) {
+        uint64_t v = 0;
+        for (uint32_t j = 0; j < M; j++) v |= uint64_t(pat[win[w] + j]) << (8 * j);
+        hs->push_back(search_hash(v, B, M));
+    }
+    return true;
+}
+
 // One table against the pattern's nw groups of gsize windows (h[g * gsize + j] = the hash of window j of group g at B bits; bits = B - R of
 // this table): a = the leading groups whose windows are all present, s = the trailing ones.  Both are nw when all are present.
 MLZ_SEARCH_HD void search_probe(const uint8_t* table, uint32_t bits, const uint32_t* h, uint32_t nw, uint32_t* a, uint32_t* s, uint32_t gsize = 1) {
@@ -162,89 +183,14 @@ MLZ_SEARCH_HD bool search_candidate(uint32_t a_k, uint32_t s_next, uint32_t nw, 
     return lo <= a_k;   // (a_k < nw here)
 }
 
-// The decoded set: every candidate plus the chunks behind it that hold any of the L - 1 bytes after its end.  a[k], s[k]: the probe of
-// chunk k (nw, nw without a usable table); n[k] > 0: its decoded bytes.  take[k] = 1 for the chunks to decode.  Returns their number.
-template <class A, class S, class N>
-size_t search_decoded_set(size_t nck, A a_of, S s_of, N n_of, uint32_t nw, uint32_t L, uint8_t* take, uint32_t t_min = 1) {
-    for (size_t k = 0; k < nck; k++) take[k] = 0;
-    for (size_t k = 0; k < nck; k++) {
-        if (!n_of(k)) continue;   // (a chunk of no bytes holds nothing)
-        const bool last = k + 1 == nck;
-        const uint32_t s_next = last ? 0 : (n_of(k + 1) < L ? nw : s_of(k + 1));
-        if (!search_candidate(a_of(k), s_next, nw, last, t_min)) continue;
-        take[k] = 1;
-        uint64_t need = L - 1;
-        for (size_t j = k + 1; j < nck && need; j++) {
-            const uint64_t nj = n_of(j);
-            if (nj) take[j] = 1;
-            need = nj >= need ? 0 : need - nj;
-        }
-    }
-    size_t cnt = 0;
-    for (size_t k = 0; k < nck; k++) cnt += take[k];
-    return cnt;
-}
-
-// ---- the decoded set in the scratch ----
-// The chunks of the decoded set ("jobs", in stream order) are decoded group by group into one scratch buffer that every group reuses.  A group
-// starts behind kSearchPad bytes of room; chunks that are neighbours in the decoded stream lie side by side, so a run of neighbours is one
-// piece of decoded stream, and where a run goes on in the next group its last L - 1 bytes are copied in front of that group's first chunk.
-// A tile is up to kSearchTile start positions of one run: scratch[src_off + i, + L) is compared for i < count, position i is decoded byte
-// gpos + i.  Every start position of every run whose L bytes lie inside the run is in exactly one tile, in ascending order.
-constexpr uint32_t kSearchTile = 8192, kSearchTileWords = kSearchTile / 64, kSearchPad = 256;
-struct SearchTile { int64_t src_off; uint64_t gpos; uint32_t count, pad; };
-static_assert(sizeof(SearchTile) == 24 && kSearchPad >= kSearchMaxPattern, "a record shared with the kernels; the carried bytes fit in front of a group");
-struct SearchLayout {
-    std::vector<uint64_t> at;            // per job: where its chunk lies in the scratch
-    std::vector<SearchTile> tiles;       // group by group
-    std::vector<size_t> tile_end;        // per group: one past its last tile
-    std::vector<uint32_t> carry;         // per group: bytes that go from its end, scratch[used - carry, used), to scratch[kSearchPad - carry, kSearchPad)
-    std::vector<uint64_t> used;          // per group: the end of its last chunk in the scratch
-    uint64_t scratch_max = 0;
-};
-// gend[g]: one past the last job of group g; out_off_of(j), n_of(j): job j's place in the decoded stream and its decoded bytes
-template <class Off, class N>
-void search_layout(size_t n_jobs, const std::vector<size_t>& gend, Off out_off_of, N n_of, uint32_t L, SearchLayout* lay) {
-    const size_t ng = gend.size();
-    lay->at.assign(n_jobs, 0); lay->tiles.clear(); lay->tile_end.assign(ng, 0); lay->carry.assign(ng, 0); lay->used.assign(ng, 0); lay->scratch_max = 0;
-    auto adjacent = [&](size_t i) { return out_off_of(i - 1) + n_of(i - 1) == out_off_of(i); };
-    uint64_t run_have = 0;   // bytes of the current run that lie in the scratch in front of the next chunk
-    for (size_t g = 0, j0 = 0; g < ng; j0 = gend[g++]) {
-        const size_t j1 = gend[g];
-        uint64_t o = kSearchPad;
-        for (size_t j = j0; j < j1;) {
-            size_t e = j + 1;   // a part: jobs [j, e) are neighbours
-            while (e < j1 && adjacent(e)) e++;
-            if (!(j == j0 && j0 > 0 && adjacent(j0))) run_have = 0;
-            const uint64_t ps = o, gp = out_off_of(j);
-            for (size_t i = j; i < e; i++) { lay->at[i] = o; o += n_of(i); }
-            const uint64_t lower = ps - (run_have < L - 1 ? run_have : L - 1);
-            if (o - lower >= L)
-                for (uint64_t s0 = lower, upper = o - L + 1; s0 < upper; s0 += kSearchTile)
-                    lay->tiles.push_back(SearchTile{int64_t(s0), gp + s0 - ps, uint32_t(upper - s0 < kSearchTile ? upper - s0 : kSearchTile), 0});
-            run_have += o - ps;
-            j = e;
-        }
-        lay->used[g] = o;
-        if (j1 < n_jobs && adjacent(j1)) lay->carry[g] = uint32_t(run_have < L - 1 ? run_have : L - 1);
-        if (o > lay->scratch_max) lay->scratch_max = o;
-        lay->tile_end[g] = lay->tiles.size();
-    }
-}
-
-// ---- many patterns in one call (mlz_dev_reader_search_many) ----
-constexpr uint32_t kSearchMaxPatterns = 4096;
-
-// One pattern as the plan kernel sees it: its nw groups of gsize window hashes lie at hashes[h_off ...); t_min and L as in search_decoded_set.
-struct SearchManyPat { uint32_t h_off, nw, gsize, t_min, L, pad; };
-static_assert(sizeof(SearchManyPat) == 24, "a record shared with the kernels");
-
-// The part of search_decoded_set's rule that belongs to chunk k, marking only: take[k] and the chunks behind it that hold any of the L - 1
-// bytes after its end become 1 when k is a candidate; nothing is cleared.  Over all k this marks what search_decoded_set takes, so the
-// union of several patterns' sets is this function over every (k, pattern) on one array.  Every store is a 1: lanes may run it side by side.
+// The decoded set: every candidate plus the chunks behind it that hold any of the L - 1 bytes after its end.  a_of(k), s_of(k): the probe
+// of chunk k (nw, nw without a usable table); n_of(k) > 0: its decoded bytes.
+// search_decoded_mark is the part of the rule that belongs to chunk k, marking only: take[k] and the chunks behind it become 1 when k is a
+// candidate; nothing is cleared.  The union of several patterns' sets is this function over every (k, pattern) on one array.  Every store
+// is a 1: lanes may run it side by side.
 template <class A, class S, class N>
 MLZ_SEARCH_HD void search_decoded_mark(size_t k, size_t nck, A a_of, S s_of, N n_of, uint32_t nw, uint32_t L, uint8_t* take, uint32_t t_min = 1) {
-    if (!n_of(k)) return;
+    if (!n_of(k)) return;   // (a chunk of no bytes holds nothing)
     const bool last = k + 1 == nck;
     const uint32_t a_k = a_of(k);
     if (a_k != nw) {   // (s_next is looked at only where it decides)
@@ -260,28 +206,43 @@ MLZ_SEARCH_HD void search_decoded_mark(size_t k, size_t nck, A a_of, S s_of, N n
         need = nj >= need ? 0 : need - nj;
     }
 }
+// One pattern's set: take[k] = 1 for the chunks to decode, 0 for the others.  Returns their number.
+template <class A, class S, class N>
+size_t search_decoded_set(size_t nck, A a_of, S s_of, N n_of, uint32_t nw, uint32_t L, uint8_t* take, uint32_t t_min = 1) {
+    for (size_t k = 0; k < nck; k++) take[k] = 0;
+    for (size_t k = 0; k < nck; k++) search_decoded_mark(k, nck, a_of, s_of, n_of, nw, L, take, t_min);
+    size_t cnt = 0;
+    for (size_t k = 0; k < nck; k++) cnt += take[k];
+    return cnt;
+}
 
-// The layout of the decoded set for patterns of lengths lmin .. lmax: search_layout's groups, places and runs, with lmax - 1 carried bytes.
-// A tile is up to kSearchManyTile start positions of one run in one group; EVERY pattern is examined at each of them, pattern i under
-// i + L <= hi_end (hi_end: where the run's bytes end in this group, counted from src_off).  A start position belongs to the first group
-// that holds lmax bytes of the run from it on, or to the group in which the run ends: where the run goes on in the next group, the tiles
-// stop lmax - 1 bytes before the run's end in this one, and exactly those positions are the carried bytes in front of the next group's
-// first chunk.  So every position of a run is in exactly one tile, with all its patterns at once, and the tiles ascend: the pairs come out
-// in (position, pattern) order.  (Examining a pair in the first group that holds ITS bytes would find a short pattern at p + 1 a group
-// before a long one at p.)
-constexpr uint32_t kSearchManyTile = 16384;
-struct SearchManyTile { int64_t src_off; uint64_t gpos; uint32_t count, hi_end; };
-static_assert(sizeof(SearchManyTile) == 24, "a record shared with the kernels");
-struct SearchManyLayout {   // (the fields of SearchLayout)
-    std::vector<uint64_t> at;
-    std::vector<SearchManyTile> tiles;
-    std::vector<size_t> tile_end;
-    std::vector<uint32_t> carry;
-    std::vector<uint64_t> used;
+// ---- the decoded set in the scratch ----
+// The chunks of the decoded set ("jobs", in stream order) are decoded group by group into one scratch buffer that every group reuses.  A group
+// starts behind kSearchPad bytes of room; chunks that are neighbours in the decoded stream lie side by side, so a run of neighbours is one
+// piece of decoded stream, and where a run goes on in the next group its last lmax - 1 bytes are copied in front of that group's first chunk.
+// The patterns of a call have lengths lmin .. lmax (one pattern: both are L).  A tile is up to `tile` start positions of one run in one
+// group: position i is scratch[src_off + i], decoded byte gpos + i, and EVERY pattern is examined at each i < count, a pattern of L bytes
+// under i + L <= hi_end (hi_end: where the run's bytes end in this group, counted from src_off; with one length that holds for every i).
+// A start position belongs to the first group that holds lmax bytes of the run from it on, or to the group in which the run ends: where the
+// run goes on in the next group, the tiles stop lmax - 1 bytes before the run's end in this one, and exactly those positions are the
+// carried bytes in front of the next group's first chunk.  So every position of a run at which a pattern fits is in exactly one tile, with
+// all its patterns at once, and the tiles ascend: the pairs come out in (position, pattern) order.  (Examining a pair in the first group
+// that holds ITS bytes would find a short pattern at p + 1 a group before a long one at p.)
+// kSearchTile: the tile of the search for one pattern, tied to its bitmap kernels; kSearchManyTile: of the search for many.
+constexpr uint32_t kSearchTile = 8192, kSearchTileWords = kSearchTile / 64, kSearchManyTile = 16384, kSearchPad = 256;
+struct SearchTile { int64_t src_off; uint64_t gpos; uint32_t count, hi_end; };
+static_assert(sizeof(SearchTile) == 24 && kSearchPad >= kSearchMaxPattern, "a record shared with the kernels; the carried bytes fit in front of a group");
+struct SearchLayout {
+    std::vector<uint64_t> at;            // per job: where its chunk lies in the scratch
+    std::vector<SearchTile> tiles;       // group by group
+    std::vector<size_t> tile_end;        // per group: one past its last tile
+    std::vector<uint32_t> carry;         // per group: bytes that go from its end, scratch[used - carry, used), to scratch[kSearchPad - carry, kSearchPad)
+    std::vector<uint64_t> used;          // per group: the end of its last chunk in the scratch
     uint64_t scratch_max = 0;
 };
+// gend[g]: one past the last job of group g; out_off_of(j), n_of(j): job j's place in the decoded stream and its decoded bytes
 template <class Off, class N>
-void search_many_layout(size_t n_jobs, const std::vector<size_t>& gend, Off out_off_of, N n_of, uint32_t lmin, uint32_t lmax, SearchManyLayout* lay) {
+void search_layout(size_t n_jobs, const std::vector<size_t>& gend, Off out_off_of, N n_of, uint32_t lmin, uint32_t lmax, uint32_t tile, SearchLayout* lay) {
     const size_t ng = gend.size();
     lay->at.assign(n_jobs, 0); lay->tiles.clear(); lay->tile_end.assign(ng, 0); lay->carry.assign(ng, 0); lay->used.assign(ng, 0); lay->scratch_max = 0;
     auto adjacent = [&](size_t i) { return out_off_of(i - 1) + n_of(i - 1) == out_off_of(i); };
@@ -298,8 +259,8 @@ void search_many_layout(size_t n_jobs, const std::vector<size_t>& gend, Off out_
             const uint64_t lower = ps - (run_have < lmax - 1 ? run_have : lmax - 1);
             const uint32_t keep = e == j1 && j1 < n_jobs && adjacent(j1) ? lmax : lmin;   // (the run goes on in the next group : it ends here)
             if (o - lower >= keep)
-                for (uint64_t s0 = lower, upper = o - keep + 1; s0 < upper; s0 += kSearchManyTile)
-                    lay->tiles.push_back(SearchManyTile{int64_t(s0), gp + s0 - ps, uint32_t(upper - s0 < kSearchManyTile ? upper - s0 : kSearchManyTile), uint32_t(o - s0)});
+                for (uint64_t s0 = lower, upper = o - keep + 1; s0 < upper; s0 += tile)
+                    lay->tiles.push_back(SearchTile{int64_t(s0), gp + s0 - ps, uint32_t(upper - s0 < tile ? upper - s0 : tile), uint32_t(o - s0)});
             run_have += o - ps;
             j = e;
         }
@@ -309,6 +270,9 @@ void search_many_layout(size_t n_jobs, const std::vector<size_t>& gend, Off out_
         lay->tile_end[g] = lay->tiles.size();
     }
 }
+
+// ---- many patterns in one call (mlz_dev_reader_search_many) ----
+constexpr uint32_t kSearchMaxPatterns = 4096;
 
 // The pattern index of the scan: the key of a pattern is its first m = min(4, lmin) bytes, hashed to hb bits; heads[h] .. heads[h + 1] are the
 // places in `order` of the patterns whose key hashes to h, ascending by pattern index (a CSR), so a lane that walks a bucket meets the
@@ -357,7 +321,7 @@ inline void search_many_index(const uint8_t* blob, const uint32_t* len, size_t n
 // The scan and write rule of one tile, as search_many_kernel applies it (and as the host check restates it with plain loops): the byte at
 // tile position i is s[i]; emit(i, pattern) is called for every pair the tile examines, positions ascending, patterns in bucket order.
 template <class Emit>
-inline void search_many_tile_pairs(const uint8_t* s, const SearchManyTile& t, const SearchManyIndex& ix, const uint8_t* blob, Emit emit) {
+inline void search_many_tile_pairs(const uint8_t* s, const SearchTile& t, const SearchManyIndex& ix, const uint8_t* blob, Emit emit) {
     for (uint32_t i = 0; i < t.count; i++) {
         uint32_t v = 0;
         for (uint32_t j = 0; j < ix.m; j++) v |= uint32_t(s[i + j]) << (8 * j);

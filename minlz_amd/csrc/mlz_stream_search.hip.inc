@@ -6,10 +6,11 @@
 // of the stream's prefix bytes, which are the only ones its blocks index; with a long-prefix table (type 4) the groups of E + 1 windows behind
 // an occurrence of the stream's prefix in the pattern, probed group by group.  Per handle, once: search_info_kernel reads the info chunk, search_locate_kernel
 // (one lane per data chunk) hops over the chunk headers between the previous data chunk's end and its own start to the first table chunk
-// that fits, and the existing CRC pass checks the tables.  Per call: search_probe_kernel looks the pattern's windows up in every table
-// (8 bytes per chunk come back), the rule of mlz_stream_search.h turns that into the set of chunks to decode, stream_run_chunk_jobs decodes
+// that fits, and the existing CRC pass checks the tables.  Per call: the host hashes the pattern's windows (search_pattern_hashes),
+// search_probe_kernel looks them up in every table (8 bytes per chunk come back) and the rule of mlz_stream_search.h (search_decoded_set)
+// turns that into the set of chunks to decode.  stream_run_chunk_jobs decodes
 // exactly those into the scratch, chunks that are neighbours in the stream side by side, and search_scan_kernel marks the occurrences of every
-// run in a bitmap (one bit per decoded byte of the set) and counts them per tile.  A scan over the tile counts and search_write_kernel then
+// run in a bitmap (one bit per decoded byte of the set) and counts them per tile.  search_prefix_kernel's scan over the tile counts and search_write_kernel then
 // put the smallest `cap` positions out in ascending order.
 
 namespace mlz {
@@ -67,6 +68,7 @@ __global__ __launch_bounds__(64) void search_locate_kernel(const uint8_t* __rest
     tabs[k] = t;
 }
 
+// One lane per data chunk: the leading and the trailing run of the pattern's windows (groups) that the chunk's table holds
 __global__ __launch_bounds__(64) void search_probe_kernel(const uint8_t* __restrict__ src, const SearchTab* __restrict__ tabs, uint32_t nck, uint32_t B,
                                                           const uint32_t* __restrict__ hashes, uint32_t nw, uint32_t gsize, uint2* __restrict__ out) {
     const uint32_t k = blockIdx.x * 64 + threadIdx.x;
@@ -106,18 +108,20 @@ __global__ __launch_bounds__(256) void search_scan_kernel(const uint8_t* __restr
     if (tid == 0) counts[tile] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
-// prefix[i] = the occurrences in the tiles in front of tile i; *total = all of them
-__global__ __launch_bounds__(1024) void search_prefix_kernel(const uint32_t* __restrict__ counts, uint32_t nt, uint64_t* __restrict__ prefix, uint64_t* __restrict__ total) {
+// prefix[i] = *total + the counts of the tiles [t0, i) for t0 <= i < t1, then *total += all of them: run once over all tiles with *total = 0
+// (one pattern), or group by group in stream order (many)
+__global__ __launch_bounds__(1024) void search_prefix_kernel(const uint32_t* __restrict__ counts, uint32_t t0, uint32_t t1, uint64_t* __restrict__ prefix, uint64_t* __restrict__ total) {
     __shared__ uint64_t lds[1024];
     const uint32_t tid = threadIdx.x;
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < nt; base += 1024) {
+    uint64_t carry = *total;
+    for (uint32_t base = t0; base < t1; base += 1024) {
         const uint32_t i = base + tid;
         uint64_t sum;
-        const uint64_t before = wg_scan<1024>(uint64_t(i < nt ? counts[i] : 0), lds, tid, [](uint64_t x, uint64_t y) { return x + y; }, &sum);
-        if (i < nt) prefix[i] = carry + before;
+        const uint64_t before = wg_scan<1024>(uint64_t(i < t1 ? counts[i] : 0), lds, tid, [](uint64_t x, uint64_t y) { return x + y; }, &sum);
+        if (i < t1) prefix[i] = carry + before;
         carry += sum;
     }
+    __syncthreads();   // (every lane has read *total)
     if (tid == 0) *total = carry;
 }
 
@@ -197,29 +201,28 @@ int64_t dev_reader_search_tables(mlz_dev_reader* rd, hipStream_t sm, bool ignore
 }
 
 // The decoded set of a search on its way through the scratch, shared by the search for one pattern and the search for many: the decode
-// list in stream order, its groups (range_group_ends), every chunk's place and the tiles of start positions (Lay: SearchLayout or
-// SearchManyLayout), the stored chunks' copies, and where the carried bytes, the tiles and the jobs' results lie in the two workspaces.
-template <class Lay> struct SearchDecode {
-    typedef typename decltype(Lay::tiles)::value_type Tile;
+// list in stream order, its groups (range_group_ends), every chunk's place and the tiles of start positions (search_layout),
+// the stored chunks' copies, and where the carried bytes, the tiles and the jobs' results lie in the two workspaces.
+struct SearchDecode {
     std::vector<ChunkJob> jobs;
     std::vector<size_t> gend, place_end;
     std::vector<PlaceDesc> places;   // stored chunks: copied from the stream
-    Lay lay;
+    mlz::SearchLayout lay;
     Region<uint8_t> carry;
-    Region<Tile> tiles, htiles;
+    Region<mlz::SearchTile> tiles, htiles;
     Region<PlaceDesc> hplaces;
     ChunkJobResults res;
 };
 
-// layout(n_jobs, gend, out_off_of, n_of, &lay): search_layout or its sibling with the call's lengths
-template <class Lay, class LayoutFn>
-void search_decode_plan(const mlz_dev_reader* rd, const std::vector<uint8_t>& take, size_t n_take, LayoutFn layout, SearchDecode<Lay>* sd) {
+// lmin, lmax: the shortest and the longest pattern of the call; tile: the most start positions of a tile (search_layout)
+void search_decode_plan(const mlz_dev_reader* rd, const std::vector<uint8_t>& take, size_t n_take, uint32_t lmin, uint32_t lmax, uint32_t tile, SearchDecode* sd) {
     const size_t nck = rd->chunks.size();
     sd->jobs.reserve(n_take);
     for (size_t k = 0; k < nck; k++) if (take[k]) sd->jobs.push_back(ChunkJob{k, nullptr});
     const std::vector<ChunkJob>& jobs = sd->jobs;
     mlz::range_group_ends(jobs.size(), [&](size_t i) { return uint64_t(rd->chunks[jobs[i].ck].n); }, &sd->gend);
-    layout(jobs.size(), sd->gend, [&](size_t i) { return uint64_t(rd->chunks[jobs[i].ck].out_off); }, [&](size_t i) { return uint64_t(rd->chunks[jobs[i].ck].n); }, &sd->lay);
+    mlz::search_layout(jobs.size(), sd->gend, [&](size_t i) { return uint64_t(rd->chunks[jobs[i].ck].out_off); }, [&](size_t i) { return uint64_t(rd->chunks[jobs[i].ck].n); },
+                       lmin, lmax, tile, &sd->lay);
     const size_t ng = sd->gend.size();
     sd->place_end.assign(ng, 0);
     for (size_t g = 0, j0 = 0; g < ng; j0 = sd->gend[g++]) {
@@ -233,18 +236,17 @@ void search_decode_plan(const mlz_dev_reader* rd, const std::vector<uint8_t>& ta
 }
 
 // Its regions: carried bytes | tiles in the workspace (c->d_rplan), results | tiles | places in the pinned buffer
-template <class Lay> void search_decode_take(SearchDecode<Lay>* sd, Carve* cv, Carve* pin) {
-    typedef typename SearchDecode<Lay>::Tile Tile;
+void search_decode_take(SearchDecode* sd, Carve* cv, Carve* pin) {
     const size_t nt = sd->lay.tiles.size();
     sd->carry = cv->take<uint8_t>(mlz::kSearchMaxPattern);
-    sd->tiles = cv->take<Tile>(nt);
+    sd->tiles = cv->take<mlz::SearchTile>(nt);
     sd->res = take_chunk_job_results(pin, sd->jobs.size());
-    sd->htiles = pin->take<Tile>(nt, 64);
+    sd->htiles = pin->take<mlz::SearchTile>(nt, 64);
     sd->hplaces = pin->take<PlaceDesc>(sd->places.size(), 8);
 }
 
 // Every buffer of the call, once: the workspace and the pinned buffer as the caller carved them, the scratch, the copies' descriptors
-template <class Lay> int search_decode_ready(mlz_ctx* c, const SearchDecode<Lay>& sd, const Carve& cv, const Carve& pin) {
+int search_decode_ready(mlz_ctx* c, const SearchDecode& sd, const Carve& cv, const Carve& pin) {
     HIPCHK(c, c->d_rplan.ensure(cv.bytes));
     HIPCHK(c, c->d_range.ensure(size_t(sd.lay.scratch_max) + 64));
     if (!sd.places.empty()) HIPCHK(c, c->d_place.ensure(sd.places.size() * sizeof(PlaceDesc)));
@@ -253,22 +255,21 @@ template <class Lay> int search_decode_ready(mlz_ctx* c, const SearchDecode<Lay>
 
 // Decodes the set group by group into the scratch (stored chunks: copied), calls scan(g, t0, t1) for the tiles [t0, t1) of group g with its
 // bytes in place, and carries a run's last bytes in front of the next group.  Returns stream_run_chunk_jobs' verdict.
-template <class Lay, class Scan>
-int64_t search_decode_run(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, SearchDecode<Lay>* sd, Scan scan) {
-    typedef typename SearchDecode<Lay>::Tile Tile;
+template <class Scan>
+int64_t search_decode_run(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, SearchDecode* sd, Scan scan) {
     mlz_ctx* c = rd->ctx;
-    const Lay& lay = sd->lay;
+    const mlz::SearchLayout& lay = sd->lay;
     const size_t nt = lay.tiles.size(), np = sd->places.size();
     uint8_t *scratch = c->d_range.as<uint8_t>(), *d_carry = sd->carry.at(c->d_rplan.p);
-    Tile *d_tiles = sd->tiles.at(c->d_rplan.p), *h_tiles = sd->htiles.at(c->pinned2);
+    mlz::SearchTile *d_tiles = sd->tiles.at(c->d_rplan.p), *h_tiles = sd->htiles.at(c->pinned2);
     PlaceDesc* h_places = sd->hplaces.at(c->pinned2);
-    if (nt) std::memcpy(h_tiles, lay.tiles.data(), nt * sizeof(Tile));
+    if (nt) std::memcpy(h_tiles, lay.tiles.data(), nt * sizeof(mlz::SearchTile));
     if (np) std::memcpy(h_places, sd->places.data(), np * sizeof(PlaceDesc));
     for (size_t i = 0; i < sd->jobs.size(); i++) {
         const StreamChunk& ck = rd->chunks[sd->jobs[i].ck];
         sd->jobs[i].at = ck.type == kChunkUncompressed ? rd->d_src + ck.body_off : scratch + lay.at[i];   // (a stored chunk's CRC: over the stream's own bytes)
     }
-    if (nt) HIPCHK(c, hipMemcpyAsync(d_tiles, h_tiles, nt * sizeof(Tile), hipMemcpyHostToDevice, sm));
+    if (nt) HIPCHK(c, hipMemcpyAsync(d_tiles, h_tiles, nt * sizeof(mlz::SearchTile), hipMemcpyHostToDevice, sm));
     if (np) HIPCHK(c, hipMemcpyAsync(c->d_place.p, h_places, np * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
     auto scan_group = [&](size_t g) -> int {
         const size_t t0 = g ? lay.tile_end[g - 1] : 0, t1 = lay.tile_end[g], q0 = g ? sd->place_end[g - 1] : 0, q1 = sd->place_end[g];
@@ -283,12 +284,17 @@ int64_t search_decode_run(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, S
     return stream_run_chunk_jobs(c, sm, ignore_crc, rd->d_src, rd->chunks, sd->jobs, sd->gend, sd->res, scan_group);
 }
 
+// The opening of both searches: counters 10 and 11 cleared, stats = {data chunks, 0, 0, 0}
+void search_begin(mlz_dev_reader* rd, uint64_t* stats) {
+    rd->ctx->search_chunks = rd->ctx->search_tables = 0;
+    if (stats) { stats[0] = rd->chunks.size(); stats[1] = stats[2] = stats[3] = 0; }
+}
+
 int64_t dev_reader_search_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* pattern, uint32_t L, uint64_t* d_offsets, uint64_t cap, uint64_t* stats) {
     mlz_ctx* c = rd->ctx;
     const size_t nck = rd->chunks.size();
     const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0;
-    c->search_chunks = c->search_tables = 0;
-    if (stats) { stats[0] = nck; stats[1] = stats[2] = stats[3] = 0; }
+    search_begin(rd, stats);
     if (nck == 0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<uint8_t> take(nck, 1);
@@ -298,23 +304,14 @@ int64_t dev_reader_search_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t fl
         const int64_t r = dev_reader_search_tables(rd, sm, ignore_crc);
         if (r) return r;
         const mlz_dev_reader::SearchTables& st = rd->search[ignore_crc ? 1 : 0];
-        // the windows the tables answer for: all of them (type 1), or those behind a prefix byte; none: the tables cannot serve this pattern
-        // (type 4: the groups of windows behind the prefix's occurrences in the pattern; nw counts groups of gsize windows)
-        std::vector<uint32_t> win(st.T == 4 ? mlz::kSearchMaxWindows : mlz::kSearchMaxPattern);
-        uint32_t t_min = 1, gsize = 1;
-        const uint32_t nw = st.info && st.usable ? mlz::search_windows(pattern, L, st.T, st.M, st.field, win.data(), &t_min, &gsize) : 0;
-        with_tables = nw != 0;
+        // the windows the tables answer for and their hashes (search_pattern_hashes); none: the tables cannot serve this pattern
+        std::vector<uint32_t> win(st.T == 4 ? mlz::kSearchMaxWindows : mlz::kSearchMaxPattern), hs;
+        mlz::SearchManyPat pt;
+        with_tables = st.info && st.usable && mlz::search_pattern_hashes(pattern, L, st.T, st.M, st.B, st.field, win.data(), &hs, &pt);
         if (with_tables) {
             // the windows' hashes go up, two counts per chunk come back
-            const uint32_t nh = nw * gsize;
-            std::vector<uint32_t> hs(nh);
-            for (uint32_t i = 0; i < nh; i++) {
-                uint64_t v = 0;
-                for (uint32_t j = 0; j < st.M; j++) v |= uint64_t(pattern[win[i] + j]) << (8 * j);
-                hs[i] = mlz::search_hash(v, st.B, st.M);
-            }
             Carve cv;
-            const auto r_hs = cv.take<uint32_t>(nh);
+            const auto r_hs = cv.take<uint32_t>(hs.size());
             const auto r_out = cv.take<uint2>(nck);
             HIPCHK(c, c->d_rplan.ensure(cv.bytes));
             int e = ensure_stream_objects(c, 0, nck * 8);
@@ -322,13 +319,13 @@ int64_t dev_reader_search_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t fl
             uint32_t* d_hs = r_hs.at(c->d_rplan.p);
             uint2* d_out = r_out.at(c->d_rplan.p);
             { WorkspaceOrder order(c, sm); }
-            HIPCHK(c, hipMemcpyAsync(d_hs, hs.data(), size_t(nh) * 4, hipMemcpyHostToDevice, sm));
+            HIPCHK(c, hipMemcpyAsync(d_hs, hs.data(), hs.size() * 4, hipMemcpyHostToDevice, sm));
             hipLaunchKernelGGL(mlz::search_probe_kernel, dim3(uint32_t((nck + 63) / 64)), dim3(64), 0, sm, rd->d_src, static_cast<const mlz::SearchTab*>(st.d_tabs), uint32_t(nck), st.B,
-                               d_hs, nw, gsize, d_out);
+                               d_hs, pt.nw, pt.gsize, d_out);
             if ((e = fetch(c, sm, c->pinned2, d_out, nck * 8))) return e;
             const uint32_t* as = static_cast<const uint32_t*>(c->pinned2);
             n_take = mlz::search_decoded_set(nck, [&](size_t k) { return as[2 * k]; }, [&](size_t k) { return as[2 * k + 1]; },
-                                             [&](size_t k) { return uint64_t(rd->chunks[k].n); }, nw, L, take.data(), t_min);
+                                             [&](size_t k) { return uint64_t(rd->chunks[k].n); }, pt.nw, L, take.data(), pt.t_min);
             c->search_tables = st.usable;
         }
     }
@@ -341,8 +338,8 @@ int64_t dev_reader_search_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t fl
     if (n_take == 0) return 0;
 
     // the decode list, its groups, every chunk's place in the scratch and the tiles of start positions (search_layout), the stored chunks' copies
-    SearchDecode<mlz::SearchLayout> sd;
-    search_decode_plan(rd, take, n_take, [&](size_t nj, const std::vector<size_t>& gend, auto off_of, auto n_of, mlz::SearchLayout* lay) { mlz::search_layout(nj, gend, off_of, n_of, L, lay); }, &sd);
+    SearchDecode sd;
+    search_decode_plan(rd, take, n_take, L, L, mlz::kSearchTile, &sd);
     const size_t nt = sd.lay.tiles.size();
     if (nt > 0x7fffffffu) return -MLZ_ERR_ARG;
     Carve cv, pin;   // workspace: pattern | total | counts | prefix | bitmaps | the decode's; pinned: the decode's | pattern
@@ -368,7 +365,7 @@ int64_t dev_reader_search_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t fl
     });
     if (r < 0) return r;
     if (nt == 0) return 0;
-    hipLaunchKernelGGL(mlz::search_prefix_kernel, dim3(1), dim3(1024), 0, sm, d_counts, uint32_t(nt), d_prefix, d_total);
+    hipLaunchKernelGGL(mlz::search_prefix_kernel, dim3(1), dim3(1024), 0, sm, d_counts, 0u, uint32_t(nt), d_prefix, d_total);   // (d_total: cleared above)
     if (cap) hipLaunchKernelGGL(mlz::search_write_kernel, dim3(uint32_t(nt)), dim3(mlz::kSearchTileWords), 0, sm, d_tiles, d_masks, d_prefix, cap, d_offsets);
     if ((e = fetch(c, sm, c->pinned2, d_total, 8))) return e;
     return int64_t(*static_cast<const uint64_t*>(c->pinned2));

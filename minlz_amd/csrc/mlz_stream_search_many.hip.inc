@@ -1,14 +1,14 @@
 // mlz_stream_search_many.hip.inc — mlz_dev_reader_search_many: where each of up to 4096 byte strings occurs in a .mz stream that lies in HBM,
-// in one call (included behind mlz_stream_search.hip.inc, whose per-handle tables, decode helpers and prefix rule it uses).
+// in one call (included behind mlz_stream_search.hip.inc, whose per-handle tables, decode helpers and prefix kernel it uses).
 //
-// Plan: the host computes every pattern's windows and their hashes (search_windows, search_hash: work proportional to the patterns);
-// search_many_plan_kernel, one lane per (data chunk, pattern), probes the chunk's table and the next one's and applies the decoded-set rule
-// of that pattern (search_decoded_mark) to ONE byte array: the union of the patterns' sets.  Only those nck bytes come back.  A pattern the
-// tables cannot serve puts every chunk into the set, so the kernel is not run then.
+// Plan (dev_reader_search_many_plan): the host computes every pattern's windows and their hashes
+// (search_pattern_hashes: work proportional to the patterns); search_many_plan_kernel, one lane per (data chunk, pattern), probes the chunk's
+// table and the next one's and applies the decoded-set rule of that pattern (search_decoded_mark) to ONE byte array: the union of the
+// patterns' sets.  Only those nck bytes come back.  A pattern the tables cannot serve puts every chunk into the set, so the kernel is not run then.
 // Scan: the set is decoded once, group by group (search_decode_run), and search_many_kernel<false> examines each tile of start positions:
 // the tile's bytes are staged in LDS, a lane walks 64 neighbouring positions, hashes the first m bytes of each to a bucket of the pattern
 // index (heads and order in LDS) and verifies the bucket's patterns as far as the run holds their bytes.  Per-pattern counts gather in LDS and leave
-// with one 64-bit atomic per non-zero counter.  Per group, search_many_prefix_kernel then continues the running sum over the tile counts
+// with one 64-bit atomic per non-zero counter.  Per group, search_prefix_kernel then continues the running sum over the tile counts
 // and search_many_kernel<true> finds the pairs of the tiles below `cap` again, while the group's bytes are still in the scratch, and
 // writes (position, pattern) in ascending order.
 
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void search_many_plan_kernel(const uint8_t* __
 // One workgroup per tile.  kWrite = false: counts[tile] = the tile's pairs, pat_counts[p] += pattern p's.  kWrite = true: the pairs of a tile
 // whose first pair lies below cap go to out_pos / out_which from prefix[tile] on, as far as they lie below cap.
 template <bool kWrite>
-__global__ __launch_bounds__(kSearchManyThreads) void search_many_kernel(const uint8_t* __restrict__ scratch, const SearchManyTile* __restrict__ tiles, uint32_t tile0, SearchManyIx ix,
+__global__ __launch_bounds__(kSearchManyThreads) void search_many_kernel(const uint8_t* __restrict__ scratch, const SearchTile* __restrict__ tiles, uint32_t tile0, SearchManyIx ix,
                                                                          uint32_t* __restrict__ tile_counts, unsigned long long* __restrict__ pat_counts,
                                                                          const uint64_t* __restrict__ prefix, uint64_t cap, uint64_t* __restrict__ out_pos,
                                                                          uint32_t* __restrict__ out_which) {
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(kSearchManyThreads) void search_many_kernel(const u
     uint16_t *heads = reinterpret_cast<uint16_t*>(lds + l.heads), *order = reinterpret_cast<uint16_t*>(lds + l.order);
     uint32_t *counts = lds + l.counts, *scan = lds + l.scan, *tw = lds + l.tile;
     const uint8_t* tb = reinterpret_cast<const uint8_t*>(tw);
-    const SearchManyTile t = tiles[tile];
+    const SearchTile t = tiles[tile];
     for (uint32_t i = tid; i < (1u << ix.hb) + 1; i += kSearchManyThreads) heads[i] = ix.heads[i];
     for (uint32_t i = tid; i < ix.n; i += kSearchManyThreads) order[i] = ix.order[i];
     if (!kWrite) for (uint32_t i = tid; i < ix.n; i += kSearchManyThreads) counts[i] = 0;
@@ -136,27 +136,14 @@ __global__ __launch_bounds__(kSearchManyThreads) void search_many_kernel(const u
     }
 }
 
-// prefix[i] = *total + the pairs of the tiles [t0, i) for t0 <= i < t1, then *total += all of them: run group by group, in stream order
-__global__ __launch_bounds__(1024) void search_many_prefix_kernel(const uint32_t* __restrict__ counts, uint32_t t0, uint32_t t1, uint64_t* __restrict__ prefix, uint64_t* __restrict__ total) {
-    __shared__ uint64_t lds[1024];
-    const uint32_t tid = threadIdx.x;
-    uint64_t carry = *total;
-    for (uint32_t base = t0; base < t1; base += 1024) {
-        const uint32_t i = base + tid;
-        uint64_t sum;
-        const uint64_t before = wg_scan<1024>(uint64_t(i < t1 ? counts[i] : 0), lds, tid, [](uint64_t x, uint64_t y) { return x + y; }, &sum);
-        if (i < t1) prefix[i] = carry + before;
-        carry += sum;
-    }
-    __syncthreads();   // (every lane has read *total)
-    if (tid == 0) *total = carry;
-}
-
 }  // namespace mlz
 
 namespace {
 
-// The union of the patterns' decoded sets -> take[], their number; stats[2], stats[3] and the context's counter 11.  off[i]: pattern i's bytes in `patterns`.
+// The plan: the union of the patterns' decoded sets -> take[] and their number, the patterns the tables cannot serve and the context's
+// counter 11.  off[i]: pattern i's bytes in `patterns`.  The host hashes every pattern's windows (search_pattern_hashes);
+// search_many_plan_kernel marks the set and one byte per chunk comes back.  A pattern that is not served puts every chunk with a byte into
+// the set, so the kernel is not run then.
 int64_t dev_reader_search_many_plan(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* patterns, const std::vector<uint32_t>& off, size_t n,
                                     std::vector<uint8_t>* take, size_t* n_take, uint64_t* unserved) {
     mlz_ctx* c = rd->ctx;
@@ -171,17 +158,8 @@ int64_t dev_reader_search_many_plan(mlz_dev_reader* rd, hipStream_t sm, uint32_t
             std::vector<uint32_t> win(st.T == 4 ? mlz::kSearchMaxWindows : mlz::kSearchMaxPattern), hs;
             std::vector<mlz::SearchManyPat> pats;
             for (size_t i = 0; i < n; i++) {
-                const uint8_t* p = patterns + off[i];
-                const uint32_t L = off[i + 1] - off[i];
-                uint32_t t_min = 1, gsize = 1;
-                const uint32_t nw = mlz::search_windows(p, L, st.T, st.M, st.field, win.data(), &t_min, &gsize);
-                if (!nw) continue;
-                pats.push_back(mlz::SearchManyPat{uint32_t(hs.size()), nw, gsize, t_min, L, 0});
-                for (uint32_t w = 0; w < nw * gsize; w++) {
-                    uint64_t v = 0;
-                    for (uint32_t j = 0; j < st.M; j++) v |= uint64_t(p[win[w] + j]) << (8 * j);
-                    hs.push_back(mlz::search_hash(v, st.B, st.M));
-                }
+                mlz::SearchManyPat pt;
+                if (mlz::search_pattern_hashes(patterns + off[i], off[i + 1] - off[i], st.T, st.M, st.B, st.field, win.data(), &hs, &pt)) pats.push_back(pt);
             }
             *unserved = n - pats.size();
             if (!pats.empty()) c->search_tables = st.usable;
@@ -227,8 +205,7 @@ int64_t dev_reader_search_many_locked(mlz_dev_reader* rd, hipStream_t sm, uint32
     mlz_ctx* c = rd->ctx;
     const size_t nck = rd->chunks.size();
     const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0;
-    c->search_chunks = c->search_tables = 0;
-    if (stats) { stats[0] = nck; stats[1] = stats[2] = stats[3] = 0; }
+    search_begin(rd, stats);
     HIPCHK(c, hipSetDevice(c->device));
     auto nothing = [&]() -> int64_t {   // no chunk to scan: every count is 0
         if (d_counts) {
@@ -249,10 +226,8 @@ int64_t dev_reader_search_many_locked(mlz_dev_reader* rd, hipStream_t sm, uint32
     if (stats) { stats[1] = n_take; stats[2] = c->search_tables; stats[3] = unserved; }
     if (n_take == 0) return nothing();
 
-    SearchDecode<mlz::SearchManyLayout> sd;
-    search_decode_plan(rd, take, n_take, [&](size_t nj, const std::vector<size_t>& gend, auto off_of, auto n_of, mlz::SearchManyLayout* lay) {
-        mlz::search_many_layout(nj, gend, off_of, n_of, index.lmin, index.lmax, lay);
-    }, &sd);
+    SearchDecode sd;
+    search_decode_plan(rd, take, n_take, index.lmin, index.lmax, mlz::kSearchManyTile, &sd);
     const size_t nt = sd.lay.tiles.size(), nheads = index.heads.size();
     if (nt > 0x7fffffffu) return -MLZ_ERR_ARG;
     const uint32_t blob_bytes = index.off[n];
@@ -274,7 +249,7 @@ int64_t dev_reader_search_many_locked(mlz_dev_reader* rd, hipStream_t sm, uint32
     unsigned long long* d_pc = r_pc.at(ws);
     uint64_t *d_total = r_total.at(ws), *d_prefix = r_prefix.at(ws);
     uint32_t* d_tc = r_counts.at(ws);
-    const mlz::SearchManyTile* d_tiles = sd.tiles.at(ws);
+    const mlz::SearchTile* d_tiles = sd.tiles.at(ws);
     const bool in_lds = mlz::search_many_lds(uint32_t(n), index.hb, blob_bytes, true).words * 4 <= mlz::kSearchManyLdsBudget;
     void *d_up = r_up.at(ws), *h_up = r_hup.at(c->pinned2);
     std::memcpy(u_heads.at(h_up), index.heads.data(), nheads * 2);
@@ -291,7 +266,7 @@ int64_t dev_reader_search_many_locked(mlz_dev_reader* rd, hipStream_t sm, uint32
         const uint8_t* scratch = c->d_range.as<uint8_t>();
         hipLaunchKernelGGL(mlz::search_many_kernel<false>, dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), lds_bytes, sm, scratch, d_tiles, uint32_t(t0), ix, d_tc, d_pc,
                            static_cast<const uint64_t*>(nullptr), uint64_t(0), static_cast<uint64_t*>(nullptr), static_cast<uint32_t*>(nullptr));
-        hipLaunchKernelGGL(mlz::search_many_prefix_kernel, dim3(1), dim3(1024), 0, sm, d_tc, uint32_t(t0), uint32_t(t1), d_prefix, d_total);
+        hipLaunchKernelGGL(mlz::search_prefix_kernel, dim3(1), dim3(1024), 0, sm, d_tc, uint32_t(t0), uint32_t(t1), d_prefix, d_total);
         if (cap) hipLaunchKernelGGL(mlz::search_many_kernel<true>, dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), lds_bytes, sm, scratch, d_tiles, uint32_t(t0), ix, d_tc, d_pc,
                                     static_cast<const uint64_t*>(d_prefix), cap, d_offsets, d_which);
         return 0;
@@ -314,8 +289,7 @@ extern "C" int64_t mlz_dev_reader_search_many(mlz_dev_reader* rd, void* stream, 
     if (hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
     if (n_patterns && ((d_counts && !on_device(c, d_counts)) || (cap && (!on_device(c, d_offsets) || !on_device(c, d_which))))) return -MLZ_ERR_ARG;
     if (n_patterns == 0) {
-        c->search_chunks = c->search_tables = 0;
-        if (stats) { stats[0] = rd->chunks.size(); stats[1] = stats[2] = stats[3] = 0; }
+        search_begin(rd, stats);
         return 0;
     }
     begin_decode_call(c);

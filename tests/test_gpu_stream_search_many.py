@@ -154,6 +154,49 @@ def test_against_brute_force_and_single_calls(ctx, name):
         sr.close()
 
 
+# ---- one pattern: the n = 1 case of the same plan ----
+
+def single_call(sr, p, cap):
+    """mlz_dev_reader_search with all four statistics -> (total, positions, stats); guarded like ManySearcher's arrays."""
+    pos = torch.full((cap + GUARD,), SENT, dtype=torch.int64, device="cuda")
+    stats = (C.c_uint64 * 4)(*([SENT32] * 4))
+    total = _lib.lib().mlz_dev_reader_search(sr.rd.handle, None, 0, p, len(p), pos.data_ptr(), cap, stats)
+    torch.cuda.synchronize()
+    assert total >= 0
+    q = pos.cpu().numpy()
+    k = min(total, cap)
+    assert (q[k:] == SENT).all(), "written beyond the results"
+    return total, q[:k].tolist(), tuple(int(v) for v in stats)
+
+
+@pytest.mark.parametrize("name", list(CONFIGS))
+def test_single_is_many_with_one_pattern(ctx, name):
+    """search(p, cap) and search_many([p], cap) share one layout, one decoded-set rule and one prefix scan: the same total, the same
+    positions (`which` all 0), the same first three statistics, and the single call's fourth statistic is 0 whether the tables serve the
+    pattern or not.  cap once above the total and once 1 below it.  (Both calls are held to brute force on this stream by
+    test_against_brute_force_and_single_calls.)"""
+    bs, M = 64 << 10, 6
+    d = synth.json_like(bs * 9 + 500, 5).tobytes()
+    stream = gather(ctx, d, bs, **CONFIGS[name])
+    sr = ManySearcher(ctx, stream)
+    try:
+        not_served = []                                                      # per pattern: search_many's fourth statistic
+        for p in mixed_patterns(d, M, bs) + served_needles(d, bs):
+            full = sr.single(p)
+            for cap in (full + 3, max(full - 1, 0)):
+                total, pos, st = single_call(sr, p, cap)
+                mtotal, pairs, counts, mst = sr([p], cap)
+                what = (name, p[:16], len(p), cap)
+                assert total == mtotal == full and counts == [full], what
+                assert pos == [q for q, _ in pairs] and all(w == 0 for _, w in pairs), what
+                assert st[:3] == mst[:3] and st[3] == 0 and mst[3] in (0, 1), (what, st, mst)
+            not_served.append(mst[3])                                        # (it does not depend on cap)
+        # both branches of the plan: served_needles holds at least three patterns that every table type serves
+        assert not_served.count(1) >= 1 and (not_served.count(0) >= 3 or name == "no tables")
+    finally:
+        sr.close()
+
+
 # ---- the plan ----
 
 @pytest.mark.parametrize("kind", SC.KINDS)

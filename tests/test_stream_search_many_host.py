@@ -236,7 +236,7 @@ def _check_layout_lines(lines, want, meta):
 
 
 def test_layout_with_mixed_lengths_finds_what_brute_force_finds(checker, layout_cases):
-    """search_many_layout, search_many_index and the scan rule executed on the host: small groups, so that runs of neighbouring chunks cross
+    """search_layout (lengths lmin .. lmax), search_many_index and the scan rule executed on the host: small groups, so that runs of neighbouring chunks cross
     many group borders, chunks shorter than the shortest and the longest pattern (carried bytes then come from more than one group back),
     gaps between runs; the pairs in (position, pattern) order, each once."""
     recs, want, meta = layout_cases

@@ -8,7 +8,7 @@
 //           CRC of the table bytes), probed by search_probe.  flags: 1 = MLZ_SEARCH_NO_TABLES, 2 = MLZ_STREAM_IGNORE_CRC
 //   kind 4  u32 B; (B - 8 + 1) x u32 pop                             -> table bytes and R (search_reduce_rule)
 //   kind 5  u32 nck, n_take, L; u64 group bytes, data bytes; nck x u64 n; n_take x u32 chunk; pattern; data
-//           -> the occurrences found by search_layout's tiles, executed as the search executes them: the taken chunks of a group copied to
+//           -> the occurrences found by search_layout's tiles (lmin = lmax = L, tiles of kSearchTile), executed as the search executes them: the taken chunks of a group copied to
 //           their places in ONE reused scratch, every tile compared position by position, the carried bytes copied in front of the next
 //           group: "count tiles groups scratch_max :" and the positions
 // The prefix tables' rules (table types 2 and 3), for tests/test_stream_search_prefix_host.py:
@@ -193,7 +193,7 @@ int main(int argc, char** argv) {
                 gend.push_back(i);
             }
             mlz::SearchLayout lay;
-            mlz::search_layout(n_take, gend, [&](size_t i) { return off[jobs[i]]; }, [&](size_t i) { return n[jobs[i]]; }, L, &lay);
+            mlz::search_layout(n_take, gend, [&](size_t i) { return off[jobs[i]]; }, [&](size_t i) { return n[jobs[i]]; }, L, L, mlz::kSearchTile, &lay);
             std::vector<uint8_t> scratch(size_t(lay.scratch_max), 0xEE), keep(mlz::kSearchMaxPattern);
             std::vector<uint64_t> found;
             for (size_t g = 0, j0 = 0; g < gend.size(); j0 = gend[g++]) {

@@ -1,12 +1,12 @@
 // stream_search_many_check.cpp — the host code that mlz_dev_reader_search_many shares with its kernels (minlz_amd/csrc/mlz_stream_search.h:
-// search_decoded_mark, search_many_layout, search_many_index, search_many_tile_pairs), for tests/test_stream_search_many_host.py:
+// search_pattern_hashes, search_decoded_mark, search_layout, search_many_index, search_many_tile_pairs), for tests/test_stream_search_many_host.py:
 //   g++ -O2 -std=c++17 -o ssm tools/stream_search_many_check.cpp && ./ssm cases.bin
 // The case file is a sequence of little-endian records, one output line each:
 //   kind 1  u32 T, M, B, field bytes, nck, npat; the field; nck x u64 n; nck x (u32 R or 0xffffffff, u32 table bytes, the table); npat x u32 len; the patterns
-//           -> "served unserved :" and the union of the patterns' decoded sets as the plan kernel marks it: search_windows, search_hash and
+//           -> "served unserved :" and the union of the patterns' decoded sets as the plan kernel marks it: search_pattern_hashes and
 //           search_probe per pattern, search_decoded_mark over every (chunk, pattern) on one array (an unserved pattern: every non-empty chunk)
 //   kind 2  u32 nck, n_take, npat; u64 group bytes, data bytes; nck x u64 n; n_take x u32 chunk; npat x u32 len; the patterns; data
-//           -> the pairs found by search_many_layout's tiles, executed as the search executes them: the taken chunks of a group copied to
+//           -> the pairs found by search_layout's tiles (lmin .. lmax, tiles of kSearchManyTile), executed as the search executes them: the taken chunks of a group copied to
 //           their places in ONE reused scratch, every tile walked by search_many_tile_pairs (the index look-up and the verify as far as
 //           the run holds a pattern's bytes), its pairs appended in the order found (the write rule), the carried bytes copied in front of the next group:
 //           "count tiles groups scratch_max :" and the pairs as position:pattern
@@ -70,21 +70,14 @@ int main(int argc, char** argv) {
             std::vector<uint32_t> win(mlz::kSearchMaxWindows);
             uint32_t served = 0;
             for (uint32_t i = 0; i < npat; i++) {
-                const uint8_t* p = ps.blob.data() + ps.off[i];
-                const uint32_t L = ps.len[i];
-                uint32_t t_min = 1, gsize = 1;
-                const uint32_t nw = mlz::search_windows(p, L, T, M, field, win.data(), &t_min, &gsize);
-                if (!nw) {
+                std::vector<uint32_t> h;
+                mlz::SearchManyPat pt;
+                if (!mlz::search_pattern_hashes(ps.blob.data() + ps.off[i], ps.len[i], T, M, B, field, win.data(), &h, &pt)) {
                     for (uint32_t k = 0; k < nck; k++) if (n[k]) take[k] = 1;
                     continue;
                 }
                 served++;
-                std::vector<uint32_t> h(nw * gsize);
-                for (uint32_t w = 0; w < nw * gsize; w++) {
-                    uint64_t v = 0;
-                    for (uint32_t j = 0; j < M; j++) v |= uint64_t(p[win[w] + j]) << (8 * j);
-                    h[w] = mlz::search_hash(v, B, M);
-                }
+                const uint32_t nw = pt.nw, gsize = pt.gsize, t_min = pt.t_min, L = pt.L;
                 auto probe = [&](size_t k, bool lead) {
                     uint32_t a = nw, s = nw;
                     if (R[k] != mlz::kSearchNoTable) mlz::search_probe(tab[k].data(), B - R[k], h.data(), nw, &a, &s, gsize);
@@ -115,8 +108,8 @@ int main(int argc, char** argv) {
             }
             mlz::SearchManyIndex ix;
             mlz::search_many_index(ps.blob.data(), ps.len.data(), npat, &ix);
-            mlz::SearchManyLayout lay;
-            mlz::search_many_layout(n_take, gend, [&](size_t i) { return off[jobs[i]]; }, [&](size_t i) { return n[jobs[i]]; }, ix.lmin, ix.lmax, &lay);
+            mlz::SearchLayout lay;
+            mlz::search_layout(n_take, gend, [&](size_t i) { return off[jobs[i]]; }, [&](size_t i) { return n[jobs[i]]; }, ix.lmin, ix.lmax, mlz::kSearchManyTile, &lay);
             std::vector<uint8_t> keep(mlz::kSearchMaxPattern);
             std::vector<uint64_t> pos;
             std::vector<uint32_t> which;
@@ -124,7 +117,7 @@ int main(int argc, char** argv) {
             for (size_t g = 0, j0 = 0; g < gend.size(); j0 = gend[g++]) {
                 for (size_t i = j0; i < gend[g]; i++) std::memcpy(scratch.data() + lay.at[i], d + off[jobs[i]], size_t(n[jobs[i]]));
                 for (size_t t = g ? lay.tile_end[g - 1] : 0; t < lay.tile_end[g]; t++) {
-                    const mlz::SearchManyTile& tl = lay.tiles[t];
+                    const mlz::SearchTile& tl = lay.tiles[t];
                     if (tl.src_off < 1 || tl.count < 1 || tl.count > mlz::kSearchManyTile ||
                         uint64_t(tl.src_off) + tl.hi_end > lay.used[g] || tl.count - 1 + ix.lmin > tl.hi_end) {
                         std::fprintf(stderr, "a tile reads outside the group's bytes\n");
