@@ -194,8 +194,9 @@ int64_t mlz_stream_decode(mlz_ctx* ctx, uint32_t flags, const uint8_t* src, size
  * halves R times, while at most a quarter of the folded bits are set and 32 bytes remain.  Two kernels build and fold the tables over the raw blocks in HBM;
  * 12 more bytes per block visit the host (table bytes or 0, R, CRC).  The seek index names a block by the offset at which its chunks start: its table chunk
  * when it has one.  mlz_stream_bound with the flag adds 7 + (12 + max(32, 2^(B - 3))) per block.  Without the flag every byte is what it was before the
- * flag existed.  Table type 4 (the long prefix) is written by mlz_stream_encode_gather_device_long_prefix below.  Out of scope: compressed tables (0x46),
- * sidecars and remote references (0x47). */
+ * flag existed.  Table type 4 (the long prefix) is written by mlz_stream_encode_gather_device_long_prefix below.  Tables for a stream that exists
+ * already — any writer's — go into a sidecar: mlz_dev_reader_build_sidecar below.  Out of scope: compressed tables (0x46) and a Writer that emits a
+ * sidecar while it encodes (the reference's WriterSidecar). */
 int64_t mlz_stream_encode_gather_device(mlz_ctx* ctx, int level, uint32_t block_size, uint32_t flags, const uint8_t* const* d_src, const size_t* src_len,
                                         int n_ranges, uint8_t* d_dst, size_t dst_cap);
 
@@ -326,8 +327,9 @@ void mlz_dev_reader_close(mlz_dev_reader* reader);
 
 /* Pattern search over a stream that lies in HBM, with the reference's block search tables (SPEC_SEARCH.md; search_table.go, search_index.go) where
  * the stream has them: table types 1 (no prefix), 2 (1 to 8 prefix byte values), 3 (a mask of prefix byte values) and 4 (a long prefix with extra
- * matches) in uncompressed table chunks (0x45) behind an info chunk (0x44).  Compressed tables (0x46) and remote references (0x47) are stepped over:
- * their blocks count as having no table.
+ * matches) in uncompressed table chunks (0x45) behind an info chunk (0x44).  Compressed tables (0x46) are stepped over: their blocks count as having
+ * no table.  The tables may also come from a sidecar, a second stream that names the blocks of this one with remote references (0x47):
+ * mlz_dev_reader_build_sidecar and mlz_dev_reader_attach_sidecar below; remote references inside the searched stream itself are stepped over.
  *
  * mlz_dev_reader_search: returns the number of positions p of the decoded stream with decoded[p, p + pattern_len) == pattern (overlapping occurrences
  *   count; the value may exceed cap); d_offsets (on the handle's device; may be NULL when cap == 0) receives the min(total, cap) smallest positions in
@@ -383,6 +385,61 @@ int64_t mlz_dev_reader_search_many(mlz_dev_reader* reader, void* stream, uint32_
                                    uint64_t* d_counts,               /* device, n_patterns values; may be NULL */
                                    uint64_t* d_offsets, uint32_t* d_which, size_t cap,   /* device; both may be NULL when cap == 0 */
                                    uint64_t* stats /* host, may be NULL: 4 values */);
+
+/* Sidecar search indexes (SEARCH.md "Sidecar Streams", SPEC_SEARCH.md 1.1 and 2.3; the reference's BuildSidecar and SidecarSearcher): search tables
+ * for a stream that exists already, in a separate valid MinLZ stream.  The main stream is never touched, so this serves ANY stream in HBM: the
+ * reference Writer's (whose tables are compressed, 0x46), old ones, mlz_stream_encode's and the Python Writer's, stored blocks.  A sidecar carries up to
+ * MLZ_SIDECAR_MAX_CONFIGS table configurations; a block is skipped when any one of them proves the pattern absent.  All three calls are synchronous;
+ * `stream` and MLZ_STREAM_IGNORE_CRC as for mlz_dev_reader_read.
+ *
+ * mlz_dev_reader_build_sidecar: writes the sidecar of the handle's stream to d_dst (on the handle's device) and returns its size.  Its bytes: the main
+ *   stream's 10-byte identifier; one info chunk `44 len24 | T M B | field` per configuration in the order given, B = the table bits of the identifier's
+ *   block size; for every data chunk of the main stream that decodes to at least one byte, in order, one `45 len24 | T M B | field | R | crc32le | table`
+ *   per configuration whose table is kept and then `47 len24 | uvarint(offset of the data chunk's 4-byte header in the main stream) | uvarint(block size
+ *   - decoded bytes)`; the EOF chunk `20 01 00 00 00`.  A table is what the device Writer's rules give for that type (above: the 70 % rule, folds up to
+ *   25 % for type 1 and 10 % for the others, 32 bytes at the least, the all-zero table for a block without an indexed position), with two differences, both
+ *   the reference's (sidecar.go): stored chunks (0x01) get tables like any other, and a block's overlap is the first bytes of the NEXT DATA CHUNK only, cut
+ *   at that chunk's length, zeros beyond it even when more chunks follow; the last data chunk has none.
+ *   Every chunk is decoded (groups of about 64 MiB through the ReadSeeker's scratch, a group plus one block at the most; a group's table slots take
+ *   64 MiB of workspace at the most) and its CRC checked unless the flag says otherwise; a decode or CRC error of the first failing chunk is returned as
+ *   by mlz_dev_reader_read, and d_dst's contents are then unspecified.  12 bytes per (chunk, configuration) visit the host (table bytes, R, CRC), no payload.
+ *   -MLZ_ERR_ARG: n_cfgs outside 1 .. 4, a configuration the Writer calls above would refuse (reserved bytes that are not 0 included), d_dst not on the
+ *   handle's device.  -MLZ_ERR_DST_TOO_SMALL: the result exceeds dst_cap (with a dst_cap below mlz_dev_reader_sidecar_bound the sizes are found by a
+ *   pass of their own first).  -MLZ_ERR_UNSUPPORTED: the main stream holds a second stream identifier (concatenated streams).  These are decided
+ *   before anything is written; nothing outside d_dst[0, result) is written in any case.
+ * mlz_dev_reader_sidecar_bound: host only; a dst_cap that always suffices for the handle and these configurations, or -MLZ_ERR_ARG.
+ * mlz_dev_reader_attach_sidecar: from this call on, mlz_dev_reader_search and mlz_dev_reader_search_many on the handle use the sidecar's tables
+ *   (d_side[0, n_side), on the handle's device; the handle REFERS to it, the caller keeps it alive) instead of the main stream's inline ones;
+ *   d_side == NULL with n_side == 0 detaches.  The sidecar is walked on the device like any stream.  Its configurations are the first up to 4 valid
+ *   info chunks in front of its first 0x45 or 0x47.  A 0x47 payload is a list of (offset, block size - decoded bytes) pairs, the first offset
+ *   absolute, the others relative and not 0; every reference must name the header offset of a data chunk of the handle's stream and state its
+ *   decoded bytes, and references ascend over the whole sidecar.  The first reference of a 0x47 owns the tables in front of it: per configuration the
+ *   first 0x45 between the previous 0x47 and this one that fits it (type, M, B, field, R, length) with a good CRC (not checked under
+ *   MLZ_STREAM_IGNORE_CRC); a broken one is passed over for the next that fits; 0x46 chunks are stepped over; a data chunk without a reference has
+ *   no table.  Errors — nothing is attached, the handle keeps what it had: -MLZ_ERR_ARG for a pointer not on the handle's device; the walk's own
+ *   error for a framing error or a missing EOF chunk; -MLZ_ERR_CORRUPT for a bad varint, an empty 0x47, a reference that names no data chunk, a size
+ *   that disagrees, an order that does not ascend, a data chunk inside the sidecar; -MLZ_ERR_UNSUPPORTED for a second identifier.  A sidecar
+ *   without a usable info chunk attaches, and the searches then decode everything.
+ *   Plan with several configurations: a configuration votes on a chunk when it serves the pattern and has a usable table for the chunk, by the rule of
+ *   mlz_dev_reader_search (probing the next chunk's table of the same configuration); a chunk is a candidate when no vote is "no".  A sidecar's table
+ *   is built over the next chunk's bytes alone, so a configuration does not vote on a chunk that is followed by one with fewer bytes than its overlap
+ *   (M - 1, M, or K - 1 + M + E for types 1, 2 and 3, 4): that chunk is decoded, and every position is returned as without a sidecar.  The third
+ *   statistic counts the chunks with a usable table of at least one configuration that serves a pattern, the fourth the patterns no configuration serves.
+ * Out of scope: compressed tables (0x46), ExtractSidecar, the Writer-side sidecar, concatenated streams, sidecars read from host memory. */
+#define MLZ_SIDECAR_MAX_CONFIGS 4
+typedef struct {
+    uint8_t table_type;   /* 1 .. 4 */
+    uint8_t match_len;    /* 0 = 6; 1 .. 8 */
+    uint8_t extras;       /* type 4: 0 .. 15, match_len + extras <= 16; else 0 */
+    uint8_t reserved;     /* 0 */
+    uint16_t prefix_len;  /* type 2: 1 .. 8 values; type 4: 1 .. 256 bytes; types 1, 3: ignored */
+    uint8_t reserved2[2]; /* 0 */
+    uint8_t prefix[256];  /* type 2: the values; type 3: the 32 mask bytes; type 4: the prefix */
+} mlz_search_config;
+int64_t mlz_dev_reader_sidecar_bound(const mlz_dev_reader* reader, const mlz_search_config* cfgs, int n_cfgs);
+int64_t mlz_dev_reader_build_sidecar(mlz_dev_reader* reader, void* stream, uint32_t flags, const mlz_search_config* cfgs, int n_cfgs, uint8_t* d_dst,
+                                     size_t dst_cap);
+int64_t mlz_dev_reader_attach_sidecar(mlz_dev_reader* reader, void* stream, uint32_t flags, const uint8_t* d_side, size_t n_side);
 
 /* ---- tuning / introspection (not part of the reference surface) ---- */
 #define MLZ_OPT_DECODE_ALGO 1  /* 0 = parallel (default), 1 = serial one-wave-per-block, 3 = parallel with every block on the tile path (cross-checks) */

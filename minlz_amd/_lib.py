@@ -22,6 +22,7 @@ SYMBOLS = [
     "mlz_dev_reader_read_device", "mlz_dev_reader_search", "mlz_dev_reader_search_many",
     "mlz_stream_bound_tables", "mlz_stream_encode_gather_device_tables",
     "mlz_stream_bound_long_prefix", "mlz_stream_encode_gather_device_long_prefix",
+    "mlz_dev_reader_sidecar_bound", "mlz_dev_reader_build_sidecar", "mlz_dev_reader_attach_sidecar",
 ]
 
 
@@ -38,6 +39,12 @@ class SearchTables(C.Structure):
 class SearchLongPrefix(C.Structure):
     """mlz_search_long_prefix: table type 4, a prefix of 1 .. 256 bytes, match length (0 = 6) and extras (0 .. 15, match_len + extras <= 16)."""
     _fields_ = [("match_len", C.c_uint8), ("extras", C.c_uint8), ("prefix_len", C.c_uint16), ("reserved", C.c_uint8 * 4), ("prefix", C.c_uint8 * 256)]
+
+
+class SearchConfig(C.Structure):
+    """mlz_search_config: one table configuration of a sidecar, any table type 1 .. 4."""
+    _fields_ = [("table_type", C.c_uint8), ("match_len", C.c_uint8), ("extras", C.c_uint8), ("reserved", C.c_uint8), ("prefix_len", C.c_uint16),
+                ("reserved2", C.c_uint8 * 2), ("prefix", C.c_uint8 * 256)]
 
 
 class BlockDesc(C.Structure):
@@ -105,5 +112,8 @@ def lib():
     L.mlz_dev_reader_read_device.argtypes = [vp, vp, u32, vp, vp, sz, vp, sz, vp]; L.mlz_dev_reader_read_device.restype = i64
     L.mlz_dev_reader_search.argtypes = [vp, vp, u32, vp, sz, vp, sz, C.POINTER(u64)]; L.mlz_dev_reader_search.restype = i64
     L.mlz_dev_reader_search_many.argtypes = [vp, vp, u32, vp, vp, sz, vp, vp, vp, sz, C.POINTER(u64)]; L.mlz_dev_reader_search_many.restype = i64
+    L.mlz_dev_reader_sidecar_bound.argtypes = [vp, C.POINTER(SearchConfig), i32]; L.mlz_dev_reader_sidecar_bound.restype = i64
+    L.mlz_dev_reader_build_sidecar.argtypes = [vp, vp, u32, C.POINTER(SearchConfig), i32, vp, sz]; L.mlz_dev_reader_build_sidecar.restype = i64
+    L.mlz_dev_reader_attach_sidecar.argtypes = [vp, vp, u32, vp, sz]; L.mlz_dev_reader_attach_sidecar.restype = i64
     _lib = L
     return L

@@ -291,6 +291,52 @@ class DeviceReader:
             _raise(r, self.ctx)
         return int(r), tuple(int(v) for v in stats)
 
+    @staticmethod
+    def _configs(cfgs):
+        cfgs = list(cfgs)
+        arr = (_lib.SearchConfig * max(len(cfgs), 1))()
+        for i, q in enumerate(cfgs):
+            arr[i] = q
+        return arr, len(cfgs)
+
+    def sidecar_bound(self, cfgs):
+        """mlz_dev_reader_sidecar_bound: room that always suffices for build_sidecar with these configurations (api.search_config)."""
+        if not self.handle:
+            raise ValueError("DeviceReader is closed")
+        arr, n = self._configs(cfgs)
+        r = _lib.lib().mlz_dev_reader_sidecar_bound(self.handle, arr, n)
+        if r < 0:
+            _raise(r, self.ctx)
+        return int(r)
+
+    def build_sidecar(self, cfgs, d_dst, cap, ignore_crc=False, stream=None):
+        """mlz_dev_reader_build_sidecar: the sidecar of this stream for 1 .. 4 configurations (api.search_config) — search tables for every
+        data chunk in a separate stream that names the chunks by remote references — into `cap` bytes at device address d_dst -> its size."""
+        if not self.handle:
+            raise ValueError("DeviceReader is closed")
+        arr, n = self._configs(cfgs)
+        r = _lib.lib().mlz_dev_reader_build_sidecar(self.handle, stream, STREAM_IGNORE_CRC if ignore_crc else 0, arr, n, d_dst, cap)
+        if r < 0:
+            _raise(r, self.ctx)
+        return int(r)
+
+    def attach_sidecar(self, d_side, n, ignore_crc=False, stream=None):
+        """mlz_dev_reader_attach_sidecar: search and search_many use the tables of the sidecar at device address d_side (n bytes) from now
+        on.  The caller keeps those bytes alive and unchanged.  A sidecar that does not belong to this stream raises, and nothing changes."""
+        if not self.handle:
+            raise ValueError("DeviceReader is closed")
+        r = _lib.lib().mlz_dev_reader_attach_sidecar(self.handle, stream, STREAM_IGNORE_CRC if ignore_crc else 0, d_side, n)
+        if r < 0:
+            _raise(r, self.ctx)
+
+    def detach_sidecar(self):
+        """The searches use the stream's inline tables again."""
+        if not self.handle:
+            raise ValueError("DeviceReader is closed")
+        r = _lib.lib().mlz_dev_reader_attach_sidecar(self.handle, None, 0, None, 0)
+        if r < 0:
+            _raise(r, self.ctx)
+
     def close(self):
         if self.handle:
             _lib.lib().mlz_dev_reader_close(self.handle)
@@ -517,6 +563,39 @@ def search_long_prefix_config(match_len, prefix, extras=0):
     cfg.match_len, cfg.extras, cfg.prefix_len = match_len, extras, len(pfx)
     for i, v in enumerate(pfx):
         cfg.prefix[i] = v
+    return cfg
+
+
+def search_config(table_type, match_len=None, prefix=b"", extras=0):
+    """An mlz_search_config, one table configuration of a sidecar (DeviceReader.build_sidecar).  table_type 1: no prefix; 2: `prefix` holds
+    1 .. 8 byte values, kept in the order given; 3: `prefix` holds the byte values of the set (any number; the 256-bit mask is made here);
+    4: `prefix` is the long prefix of 1 .. 256 bytes, `extras` 0 .. 15 with match length + extras <= 16.  match_len None or 0 = 6."""
+    table_type, match_len, extras, pfx = int(table_type), int(match_len or 0), int(extras), bytes(prefix)
+    if not 1 <= table_type <= 4:
+        raise ValueError("search_config: table type 1 .. 4")
+    if not 0 <= match_len <= 8:
+        raise ValueError("search_match_len: 0 .. 8")
+    if table_type != 4 and extras:
+        raise ValueError("search_extras: table type 4 only")
+    cfg = _lib.SearchConfig()
+    cfg.table_type, cfg.match_len, cfg.extras = table_type, match_len, extras
+    if table_type == 2:
+        if not 1 <= len(pfx) <= 8:
+            raise ValueError("search_config: type 2 takes 1 .. 8 byte values")
+        cfg.prefix_len = len(pfx)
+        for i, v in enumerate(pfx):
+            cfg.prefix[i] = v
+    elif table_type == 3:
+        for v in pfx:
+            cfg.prefix[v >> 3] |= 1 << (v & 7)
+    elif table_type == 4:
+        if not 1 <= len(pfx) <= 256:
+            raise ValueError("search_long_prefix: 1 .. 256 bytes")
+        if not 0 <= extras <= 15 or (match_len or 6) + extras > 16:
+            raise ValueError("search_extras: 0 .. 15, match length + extras <= 16")
+        cfg.prefix_len = len(pfx)
+        for i, v in enumerate(pfx):
+            cfg.prefix[i] = v
     return cfg
 
 

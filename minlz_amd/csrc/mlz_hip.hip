@@ -1309,3 +1309,4 @@ int mlz_debug_idxprof(unsigned long long* out) {
 #include "mlz_stream_ranges_dev.hip.inc"
 #include "mlz_stream_search.hip.inc"
 #include "mlz_stream_search_many.hip.inc"
+#include "mlz_stream_sidecar.hip.inc"

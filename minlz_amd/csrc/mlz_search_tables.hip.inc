@@ -24,6 +24,8 @@
 // stab_build_long_kernel is that form: a lane's 8 positions are prefix starts and every read goes forward.  Stage one compares the first
 //   min(K, 8) prefix bytes in registers with the lane's 16 loaded bytes and gathers 8 verdicts into a bit mask; stage two loops over the set
 //   bits only, compares the rest of the prefix (in LDS behind the bitmap) and hashes the E + 1 windows.
+// Every kernel also has the block-list form (StabCommon::list: blocks of uneven sizes anywhere in a buffer, each with its own overlap behind it —
+//   the chunks of a decoded stream, for a sidecar's tables): stab_share reads the block's place from the list, and nothing else differs.
 // Both forms share stab_zero, stab_share, stab_positions, stab_mark and stab_flush (the zeroing of the bitmap, a workgroup's (part, slice, block)
 //   and its positions, the slice-filtered bit and the write-out or merge); they stay kernels of their own: the short forms keep the bytes behind
 //   the range in a register, the long form in LDS.
@@ -34,6 +36,11 @@ namespace mlz {
 
 constexpr uint32_t kStabSliceBits = 20, kStabThreads = 1024, kStabPerThread = 8;
 
+// The block-list form (a sidecar's tables over the chunks of a decoded stream, mlz_stream_sidecar.hip.inc): block b lies at src + off, and
+// `over` bytes of the stream that follow it (the next data chunk's first ones, cut at that chunk's length) lie behind its last byte; beyond them zeros
+struct StabBlock { uint64_t off; uint32_t bytes, over; };
+static_assert(sizeof(StabBlock) == 16, "a record shared with the host");
+
 // What every build kernel is told
 struct StabCommon {
     const uint8_t* src;      // the range
@@ -41,6 +48,7 @@ struct StabCommon {
     uint32_t tail_n;         // how many bytes behind the range (the next range's first ones) exist (0: the range ends the stream)
     uint32_t bs, cnt, B, M, parts, slices;
     uint32_t* tabs;          // cnt tables of 2^B bits
+    const StabBlock* list;   // nullptr: block b is src[b * bs ...) of the range; else the block-list form (len, bs and the tail are unused, tail_n is 0)
 };
 struct StabArgs : StabCommon {
     uint64_t tail;           // the bytes behind the range, little-endian
@@ -52,13 +60,20 @@ __device__ __forceinline__ uint32_t stab_words(const StabCommon& a) { return 1u 
 __device__ __forceinline__ void stab_zero(uint32_t* bits, uint32_t words) {
     for (uint32_t i = threadIdx.x; i < words; i += kStabThreads) bits[i] = 0;
 }
-// The workgroup's share: part `part` of block b's positions, the bits of slice `slice`.  next: a block follows this one in the stream
-struct StabShare { uint32_t part, slice, b, blen; uint64_t b0; bool next; };
+// The workgroup's share: part `part` of block b's positions, the bits of slice `slice`.  next: a block follows this one in the stream;
+// end: where the bytes that can be read at src end for this block (the range's end; the list form: the end of the block's overlap)
+struct StabShare { uint32_t part, slice, b, blen; uint64_t b0, end; bool next; };
 __device__ __forceinline__ StabShare stab_share(const StabCommon& a) {
     StabShare w;
     w.part = blockIdx.x % a.parts; w.slice = (blockIdx.x / a.parts) % a.slices; w.b = blockIdx.x / (a.parts * a.slices);
+    if (a.list) {
+        const StabBlock blk = a.list[w.b];
+        w.b0 = blk.off; w.blen = blk.bytes; w.end = blk.off + blk.bytes + blk.over; w.next = blk.over != 0;
+        return w;
+    }
     w.b0 = uint64_t(w.b) * a.bs;
     w.blen = uint32_t(a.len - w.b0 < a.bs ? a.len - w.b0 : a.bs);
+    w.end = a.len;
     w.next = w.b + 1 < a.cnt || a.tail_n != 0;
     return w;
 }
@@ -87,10 +102,10 @@ __device__ __forceinline__ void stab_flush(const StabCommon& a, const StabShare&
     }
 }
 
-// byte q of the range, continued by the next range's first bytes and zeros
-__device__ __forceinline__ uint64_t stab_byte(const StabArgs& a, uint64_t q) {
-    if (q < a.len) return a.src[q];
-    const uint64_t over = q - a.len;
+// byte q of the range, continued by the next range's first bytes and zeros (end: StabShare::end)
+__device__ __forceinline__ uint64_t stab_byte(const StabArgs& a, uint64_t end, uint64_t q) {
+    if (q < end) return a.src[q];
+    const uint64_t over = q - end;
     return over < a.tail_n ? (a.tail >> (8 * over)) & 0xff : 0;
 }
 
@@ -119,12 +134,12 @@ __global__ __launch_bounds__(kStabThreads) void stab_build_kernel(const StabArgs
         const uint32_t back = kPrefix && i ? 1 : 0;
         const uint64_t q = b0 + i - back;
         uint64_t lo, hi;
-        if (q + 16 <= a.len) {
+        if (q + 16 <= w.end) {
             __builtin_memcpy(&lo, a.src + q, 8);
             __builtin_memcpy(&hi, a.src + q + 8, 8);
         } else {
             lo = hi = 0;
-            for (uint32_t j = 0; j < 8; j++) { lo |= stab_byte(a, q + j) << (8 * j); hi |= stab_byte(a, q + 8 + j) << (8 * j); }
+            for (uint32_t j = 0; j < 8; j++) { lo |= stab_byte(a, w.end, q + j) << (8 * j); hi |= stab_byte(a, w.end, q + 8 + j) << (8 * j); }
         }
         if constexpr (kPrefix) {
             if (!back) { hi = (hi << 8) | (lo >> 56); lo <<= 8; }
@@ -175,19 +190,19 @@ __global__ __launch_bounds__(kStabThreads) void stab_build_long_kernel(const Sta
     __syncthreads();
     const uint32_t M = a.M, B = a.B, E = a.E, K = a.K;
     const StabShare w = stab_share(a);
-    const uint64_t b0 = w.b0, real = a.len + a.tail_n;   // real: where the stream's bytes that this range can see end
+    const uint64_t b0 = w.b0, end = w.end, real = end + a.tail_n;   // real: where the stream's bytes that this block can see end
     // prefix starts [0, npos): every position with a block behind, else those whose prefix and windows lie inside the block
     const uint32_t npos = w.next ? w.blen : (w.blen >= K + M + E ? w.blen - K - M - E + 1 : 0);
     uint32_t p0, p1;
     stab_positions(a, w.part, npos, &p0, &p1);
     auto byte_at = [&](uint64_t q) -> uint64_t {   // byte q of the range, continued by the bytes behind it and zeros
-        if (q < a.len) return a.src[q];
-        const uint64_t over = q - a.len;
+        if (q < end) return a.src[q];
+        const uint64_t over = q - end;
         return over < kStabLongTail ? ltail[over] : 0;
     };
     auto load8 = [&](uint64_t q) -> uint64_t {
         uint64_t v = 0;
-        if (q + 8 <= a.len) __builtin_memcpy(&v, a.src + q, 8);
+        if (q + 8 <= end) __builtin_memcpy(&v, a.src + q, 8);
         else for (uint32_t j = 0; j < 8; j++) v |= byte_at(q + j) << (8 * j);
         return v;
     };
@@ -260,31 +275,18 @@ __global__ __launch_bounds__(kStabThreads) void stab_reduce_kernel(uint32_t* __r
 
 namespace {
 
-// The tables of the cnt blocks of a range (len bytes at d_src), built and reduced on sm: c->d_stab then holds cnt slots of 2^(B - 3) bytes, each
-// with its block's table at the front, and behind them (at *info_off) cnt records (table bytes or 0, R).  tail: the tail_n bytes that follow
-// the range in the stream (the next range's first ones, StreamTables::overlap() at the most; host memory).  T, field: the table type and
-// its prefix field.  Caller holds c->mu.
-// The short forms take the first 8 of them, in a register.  They come as M - 1 (type 1) or M (types 2, 3) bytes: search_hash reads only the
-// M low bytes of its argument, so zeros behind them give the bits that more of the stream's bytes would.  The kernels read "a block
-// follows" from tail_n != 0: type 1 with M = 1 reaches no byte behind its block (tail_n is 0 there), and with or without a following block
-// its blocks index all their blen positions.
-int search_tables_build(mlz_ctx* c, hipStream_t sm, const uint8_t* d_src, size_t len, uint32_t bs, size_t cnt, uint32_t T, const uint8_t* field, uint32_t M, uint32_t B,
-                        const uint8_t* tail, uint32_t tail_n, size_t* info_off) {
-    const size_t slot = size_t(1) << (B - 3);
-    *info_off = cnt * slot;
-    HIPCHK(c, c->d_stab.ensure(cnt * slot + cnt * sizeof(uint2) + 64));
+// The launch both callers share: a.src, a.len / a.list, a.bs (the largest block), a.cnt, a.tail_n and a.tabs are set; `info` receives cnt records.
+int stab_launch(mlz_ctx* c, hipStream_t sm, mlz::StabCommon a, uint32_t T, const uint8_t* field, uint32_t M, uint32_t B, const uint8_t* tail, uint2* info) {
+    const size_t slot = size_t(1) << (B - 3), cnt = a.cnt;
     const uint32_t lbits = std::min(B, mlz::kStabSliceBits), lds = 1u << (lbits - 3);
     constexpr uint32_t kBitmap = 1u << (mlz::kStabSliceBits - 3);
     if (int r = raise_lds_once(c, c->stab_attr, Kernels{{mlz::stab_build_kernel<false>, kBitmap}, {mlz::stab_build_kernel<true>, kBitmap + 32},
                                                         {mlz::stab_build_long_kernel, kBitmap + mlz::kSearchMaxPrefix + mlz::kStabLongTail}})) return r;
-    mlz::StabCommon a{};
-    a.src = d_src; a.len = len; a.bs = bs; a.cnt = uint32_t(cnt); a.B = B; a.M = M;
-    a.tail_n = std::min(tail_n, T == 4 ? mlz::kStabLongTail : 8u);
+    a.B = B; a.M = M;
     a.slices = 1u << (B - lbits);
     // few large blocks: parts of at least 64 KiB, until the device has about two workgroups per CU
     const uint64_t want = std::max<uint64_t>(1, uint64_t(2 * std::max(c->n_cus, 1)) / (cnt * a.slices));
-    a.parts = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(want, bs >> 16)));
-    a.tabs = c->d_stab.as<uint32_t>();
+    a.parts = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(want, a.bs >> 16)));
     if (a.parts > 1) HIPCHK(c, hipMemsetAsync(a.tabs, 0, cnt * slot, sm));
     const dim3 grid(uint32_t(cnt * a.slices * a.parts)), wg(mlz::kStabThreads);
     if (T == 4) {
@@ -304,9 +306,38 @@ int search_tables_build(mlz_ctx* c, hipStream_t sm, const uint8_t* d_src, size_t
             hipLaunchKernelGGL(mlz::stab_build_kernel<true>, grid, wg, lds + 32, sm, sa);
         }
     }
-    hipLaunchKernelGGL(mlz::stab_reduce_kernel, dim3(uint32_t(cnt)), dim3(mlz::kStabThreads), 0, sm, a.tabs, B, mlz::search_fold_limit(T),
-                       reinterpret_cast<uint2*>(c->d_stab.as<uint8_t>() + *info_off));
+    hipLaunchKernelGGL(mlz::stab_reduce_kernel, dim3(uint32_t(cnt)), dim3(mlz::kStabThreads), 0, sm, a.tabs, B, mlz::search_fold_limit(T), info);
     return 0;
+}
+
+// The tables of the cnt blocks of a range (len bytes at d_src), built and reduced on sm: c->d_stab then holds cnt slots of 2^(B - 3) bytes, each
+// with its block's table at the front, and behind them (at *info_off) cnt records (table bytes or 0, R).  tail: the tail_n bytes that follow
+// the range in the stream (the next range's first ones, StreamTables::overlap() at the most; host memory).  T, field: the table type and
+// its prefix field.  Caller holds c->mu.
+// The short forms take the first 8 of them, in a register.  They come as M - 1 (type 1) or M (types 2, 3) bytes: search_hash reads only the
+// M low bytes of its argument, so zeros behind them give the bits that more of the stream's bytes would.  The kernels read "a block
+// follows" from tail_n != 0: type 1 with M = 1 reaches no byte behind its block (tail_n is 0 there), and with or without a following block
+// its blocks index all their blen positions.
+int search_tables_build(mlz_ctx* c, hipStream_t sm, const uint8_t* d_src, size_t len, uint32_t bs, size_t cnt, uint32_t T, const uint8_t* field, uint32_t M, uint32_t B,
+                        const uint8_t* tail, uint32_t tail_n, size_t* info_off) {
+    const size_t slot = size_t(1) << (B - 3);
+    *info_off = cnt * slot;
+    HIPCHK(c, c->d_stab.ensure(cnt * slot + cnt * sizeof(uint2) + 64));
+    mlz::StabCommon a{};
+    a.src = d_src; a.len = len; a.bs = bs; a.cnt = uint32_t(cnt);
+    a.tail_n = std::min(tail_n, T == 4 ? mlz::kStabLongTail : 8u);
+    a.tabs = c->d_stab.as<uint32_t>();
+    return stab_launch(c, sm, a, T, field, M, B, tail, reinterpret_cast<uint2*>(c->d_stab.as<uint8_t>() + *info_off));
+}
+
+// The block-list form: the tables of the cnt blocks d_list names inside d_src (a decoded group in the scratch), of one configuration, to
+// `tabs` (cnt slots of 2^(B - 3) bytes in c->d_stab, which the caller has sized) and their records to `info`.  max_block: the largest block.
+int search_tables_build_list(mlz_ctx* c, hipStream_t sm, const uint8_t* d_src, const mlz::StabBlock* d_list, size_t cnt, uint32_t max_block, uint32_t T, const uint8_t* field,
+                             uint32_t M, uint32_t B, uint32_t* tabs, uint2* info) {
+    mlz::StabCommon a{};
+    a.src = d_src; a.list = d_list; a.bs = max_block; a.cnt = uint32_t(cnt);
+    a.tabs = tabs;
+    return stab_launch(c, sm, a, T, field, M, B, nullptr, info);
 }
 
 }  // namespace

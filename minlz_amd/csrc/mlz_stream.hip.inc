@@ -151,7 +151,7 @@ struct StreamTables {
     uint8_t field[mlz::kSearchMaxField] = {};
     uint32_t flen() const { return mlz::search_field_len(T, field); }
     // bytes behind a block that its prefixes and windows reach
-    uint32_t overlap() const { return T == 1 ? M - 1 : T == 4 ? mlz::search_long_k(field) - 1 + M + mlz::search_long_e(field) : M; }
+    uint32_t overlap() const { return mlz::search_overlap(T, M, field); }
     // the stream's head: magic chunk and, with tables, the info chunk
     uint32_t head_bytes() const { return T ? 17 + flen() : 10; }
 };
@@ -712,6 +712,7 @@ struct StreamChunk {
     size_t n, out_off;
     size_t res_idx;             // where the device left this chunk's decode verdict
     size_t crc_idx;             // type 0x03: where the device left the CRC of its compressed bytes
+    size_t hdr_off = 0;         // the device walk: where the chunk's 4-byte header lies in the stream (a sidecar's references name it)
 };
 
 // Reader.Read's chunk walk (reader.go:248-543).  Fills `chunks`, returns total decoded bytes or -MLZ_ERR_*; on an error `chunks` holds the

@@ -63,16 +63,20 @@ struct mlz_dev_reader {
     int64_t size = 0;
     std::vector<StreamChunk> chunks;          // the data chunks: body offset and length, decoded length, CRC, type, output offset
     std::vector<mlz::RdevChunk> dchunks;      // the planners' and the plan kernels' view of them
-    // mlz_dev_reader_search: (T, M, B, prefix field) of the stream's info chunk and every data chunk's search table, found by the first search of the handle
-    // ([0]: table CRCs checked, [1]: under MLZ_STREAM_IGNORE_CRC)
+    uint32_t n_ident = 0;                     // stream identifiers in the stream (more than one: concatenated streams)
+    uint8_t ident_byte = 0;                   // the first identifier's block-size byte, which a sidecar repeats
+    // mlz_dev_reader_search: a stream's table sets — the configuration (T, M, B, prefix field) of each and every data chunk's table of each.
+    // search[]: the one set of the stream's inline tables (its info chunk), found by the first search of the handle ([0]: table CRCs checked,
+    // [1]: under MLZ_STREAM_IGNORE_CRC); side: the sets of the attached sidecar (mlz_dev_reader_attach_sidecar), which the searches use while side_on.
     struct SearchTables {
-        bool ready = false, info = false;
-        uint32_t M = 0, B = 0, T = 0;
-        uint8_t field[mlz::kSearchMaxField] = {};
-        size_t usable = 0;
-        void* d_tabs = nullptr;               // mlz::SearchTab per data chunk, device memory the handle owns
+        bool ready = false;
+        uint32_t ncfg = 0;                    // 0: no usable info chunk
+        mlz::SearchConfig cfg[mlz::kSidecarMaxConfigs] = {};
+        const uint8_t* base = nullptr;        // the tables' offsets count from here: the stream, or the sidecar
+        void* d_tabs = nullptr;               // mlz::SearchTab per (set, data chunk), set by set; device memory the handle owns
         std::vector<mlz::SearchTab> tabs;
-    } search[2];
+    } search[2], side;
+    bool side_on = false;
 };
 
 namespace {
@@ -147,7 +151,7 @@ int64_t mlz_stream_open_device(mlz_ctx* c, void* stream, const uint8_t* d_src, s
     mlz_dev_reader* rd = new (std::nothrow) mlz_dev_reader;
     if (!rd) return -MLZ_ERR_HIP;
     int64_t parsed = 0;
-    const int e = stream_walk_device(c, static_cast<hipStream_t>(stream), d_src, n, &rd->chunks, &parsed);
+    const int e = stream_walk_device(c, static_cast<hipStream_t>(stream), d_src, n, &rd->chunks, &parsed, &rd->n_ident, &rd->ident_byte);
     if (e || parsed < 0) { delete rd; return e ? e : parsed; }   // a framing error: no handle
     rd->ctx = c; rd->d_src = d_src; rd->n = n; rd->size = parsed;
     rd->dchunks.reserve(rd->chunks.size());
@@ -175,10 +179,10 @@ int64_t mlz_dev_reader_read(mlz_dev_reader* rd, void* stream, uint32_t flags, co
 }
 
 void mlz_dev_reader_close(mlz_dev_reader* rd) {
-    if (rd && (rd->d_chunks || rd->search[0].d_tabs || rd->search[1].d_tabs)) {
+    if (rd && (rd->d_chunks || rd->search[0].d_tabs || rd->search[1].d_tabs || rd->side.d_tabs)) {
         std::lock_guard<std::mutex> lk(rd->ctx->mu);
         if (hipSetDevice(rd->ctx->device) == hipSuccess)
-            for (void* p : {rd->d_chunks, rd->search[0].d_tabs, rd->search[1].d_tabs}) if (p) (void)hipFree(p);
+            for (void* p : {rd->d_chunks, rd->search[0].d_tabs, rd->search[1].d_tabs, rd->side.d_tabs}) if (p) (void)hipFree(p);
     }
     delete rd;
 }

@@ -4,6 +4,8 @@
 // Both searches (one pattern, and many in one call: mlz_stream_search_many.hip.inc, tools/stream_search_many_check.cpp) use one rule per
 // chunk (search_decoded_mark), one pattern record with its window hashes (search_pattern_hashes) and one layout of the decoded set in the
 // scratch (search_layout, for patterns of lengths lmin .. lmax); the search for many adds the pattern index and the scan rule of one tile.
+// The sidecar section adds what a stream of tables for ANOTHER stream needs: the remote reference chunk (0x47) written and parsed, the
+// check of a reference against the main stream's chunks, and the rule over several table sets (search_decoded_mark_all).
 // Plain C++: compiles for the host alone and for gfx950.  Table types 1 (no prefix), 2 (1 to 8 prefix byte values), 3 (a 256-bit mask of
 // prefix byte values; SPEC_SEARCH.md 3.3) and 4 (a long prefix of 1 to 256 bytes with extra matches; 3.3.4), uncompressed table chunks (0x45) only.
 #pragma once
@@ -11,6 +13,8 @@
 #include <stdint.h>
 
 #include <vector>
+
+#include "mlz_stream_walk.h"   // walk_uvarint, for a sidecar's remote references
 
 #if defined(__HIPCC__)
 #define MLZ_SEARCH_HD __host__ __device__ inline
@@ -94,6 +98,11 @@ MLZ_SEARCH_HD bool search_info(const uint8_t* p, uint32_t clen, uint32_t* T, uin
     *T = p[0]; *M = p[1]; *B = p[2];
     for (uint32_t i = 0; i < kSearchMaxField; i++) field[i] = i < f ? p[3 + i] : 0;
     return true;
+}
+
+// The bytes behind a block that its table indexes into: the longest reach of a window (a group) that belongs to the block
+MLZ_SEARCH_HD uint32_t search_overlap(uint32_t T, uint32_t M, const uint8_t* field) {
+    return T == 1 ? M - 1 : T == 4 ? search_long_k(field) - 1 + M + search_long_e(field) : M;
 }
 
 // The pattern's windows that the tables can answer for, in groups of *gsize windows that one block's table holds together, and t_min.
@@ -184,20 +193,26 @@ MLZ_SEARCH_HD bool search_candidate(uint32_t a_k, uint32_t s_next, uint32_t nw, 
 }
 
 // The decoded set: every candidate plus the chunks behind it that hold any of the L - 1 bytes after its end.  a_of(k), s_of(k): the probe
-// of chunk k (nw, nw without a usable table); n_of(k) > 0: its decoded bytes.
-// search_decoded_mark is the part of the rule that belongs to chunk k, marking only: take[k] and the chunks behind it become 1 when k is a
-// candidate; nothing is cleared.  The union of several patterns' sets is this function over every (k, pattern) on one array.  Every store
-// is a 1: lanes may run it side by side.
+// of chunk k (nw, nw without a usable table); n_of(k) > 0: its decoded bytes.  The rule has two halves, each said once:
+// search_chunk_candidate is the verdict of ONE table set on chunk k (s_next is looked at only where it decides); search_mark_from marks a
+// candidate and the chunks behind it.  search_decoded_mark is the two together for one table set, marking only: nothing is cleared, every
+// store is a 1, so lanes may run it side by side and the union of several patterns' sets is this function over every (k, pattern) on one array.
+// ov: how many bytes behind chunk k its table was built over when those bytes come from the NEXT chunk alone (a sidecar's tables:
+// search_overlap of the set; 0 for a stream's inline tables, which the Writer builds over the bytes that follow in the stream, whichever chunks hold them).  Where the
+// next chunk is shorter than that, the windows that reach beyond it were hashed over zeros, the table proves nothing about an occurrence
+// that starts in k, and the set abstains: it admits k.
 template <class A, class S, class N>
-MLZ_SEARCH_HD void search_decoded_mark(size_t k, size_t nck, A a_of, S s_of, N n_of, uint32_t nw, uint32_t L, uint8_t* take, uint32_t t_min = 1) {
-    if (!n_of(k)) return;   // (a chunk of no bytes holds nothing)
+MLZ_SEARCH_HD bool search_chunk_candidate(size_t k, size_t nck, A a_of, S s_of, N n_of, uint32_t nw, uint32_t L, uint32_t t_min = 1, uint32_t ov = 0) {
     const bool last = k + 1 == nck;
+    if (!last && n_of(k + 1) < ov) return true;
     const uint32_t a_k = a_of(k);
-    if (a_k != nw) {   // (s_next is looked at only where it decides)
-        if (last) return;
-        const uint32_t s_next = n_of(k + 1) < L ? nw : s_of(k + 1);
-        if (!search_candidate(a_k, s_next, nw, last, t_min)) return;
-    }
+    if (a_k == nw) return true;
+    if (last) return false;
+    const uint32_t s_next = n_of(k + 1) < L ? nw : s_of(k + 1);
+    return search_candidate(a_k, s_next, nw, last, t_min);
+}
+template <class N>
+MLZ_SEARCH_HD void search_mark_from(size_t k, size_t nck, N n_of, uint32_t L, uint8_t* take) {
     take[k] = 1;
     uint64_t need = L - 1;
     for (size_t j = k + 1; j < nck && need; j++) {
@@ -205,6 +220,21 @@ MLZ_SEARCH_HD void search_decoded_mark(size_t k, size_t nck, A a_of, S s_of, N n
         if (nj) take[j] = 1;
         need = nj >= need ? 0 : need - nj;
     }
+}
+template <class A, class S, class N>
+MLZ_SEARCH_HD void search_decoded_mark(size_t k, size_t nck, A a_of, S s_of, N n_of, uint32_t nw, uint32_t L, uint8_t* take, uint32_t t_min = 1) {
+    if (!n_of(k)) return;   // (a chunk of no bytes holds nothing)
+    if (search_chunk_candidate(k, nck, a_of, s_of, n_of, nw, L, t_min)) search_mark_from(k, nck, n_of, L, take);
+}
+// Several table sets over one stream (the configurations of a sidecar; a stream's inline tables are one set): chunk k is a candidate when
+// EVERY set admits it.  admits(c) is set c's search_chunk_candidate; a set that cannot serve the pattern (search_windows gives no group)
+// or has no usable table for k admits it, and so does a sidecar's set in front of a chunk shorter than its overlap (search_chunk_candidate's
+// ov).  Each set's verdict alone is then a necessary condition for an occurrence that starts in k, so their conjunction is one too.
+template <class Admits, class N>
+MLZ_SEARCH_HD void search_decoded_mark_all(size_t k, size_t nck, uint32_t n_sets, Admits admits, N n_of, uint32_t L, uint8_t* take) {
+    if (!n_of(k)) return;
+    for (uint32_t c = 0; c < n_sets; c++) if (!admits(c)) return;
+    search_mark_from(k, nck, n_of, L, take);
 }
 // One pattern's set: take[k] = 1 for the chunks to decode, 0 for the others.  Returns their number.
 template <class A, class S, class N>
@@ -334,6 +364,88 @@ inline void search_many_tile_pairs(const uint8_t* s, const SearchTile& t, const 
             if (j == L) emit(i, p);
         }
     }
+}
+
+// ---- sidecars (SPEC_SEARCH.md 1.1, 2.3): a stream of table chunks that names the blocks of ANOTHER stream ----
+// A sidecar is a valid stream without data chunks: identifier, one info chunk (0x44) per table configuration, then per block of the main
+// stream its table chunks (0x45) followed by a remote block reference (0x47), EOF.  A 0x47 payload is a list of pairs
+// uvarint(offset) uvarint(max block size - decoded bytes): the first offset is where the block's data chunk header lies in the main stream,
+// further offsets count from the one before and are not 0.  Only the first reference of a chunk owns the tables in front of it.
+constexpr uint8_t kChunkRemoteRef = 0x47;
+constexpr uint32_t kSidecarMaxConfigs = 4;
+// One table configuration: what search_info reads from an info chunk
+struct SearchConfig { uint32_t T, M, B, ok; uint8_t field[kSearchMaxField + 2]; };
+static_assert(sizeof(SearchConfig) == 276, "a record shared with the kernels");
+
+MLZ_SEARCH_HD uint32_t search_put_uvarint(uint8_t* b, uint64_t v) {
+    uint32_t i = 0;
+    for (; v >= 0x80; v >>= 7) b[i++] = uint8_t(v) | 0x80;
+    b[i++] = uint8_t(v);
+    return i;
+}
+// The 0x47 chunk of one reference (24 bytes of room); returns its bytes
+MLZ_SEARCH_HD uint32_t sidecar_put_ref(uint8_t* b, uint64_t hdr_off, uint64_t max_minus_actual) {
+    uint32_t n = search_put_uvarint(b + 4, hdr_off);
+    n += search_put_uvarint(b + 4 + n, max_minus_actual);
+    b[0] = kChunkRemoteRef; b[1] = uint8_t(n); b[2] = b[3] = 0;
+    return 4 + n;
+}
+constexpr uint32_t kSidecarRefBound = 4 + 10 + 10;
+MLZ_SEARCH_HD uint32_t search_uvarint_len(uint64_t v) { uint32_t n = 1; for (; v >= 0x80; v >>= 7) n++; return n; }
+MLZ_SEARCH_HD uint32_t sidecar_ref_bytes(uint64_t hdr_off, uint64_t max_minus_actual) { return 4 + search_uvarint_len(hdr_off) + search_uvarint_len(max_minus_actual); }
+// The references of a 0x47 payload (parseRemoteBlockRef): ref(offset, decoded bytes) for each, in order.  Returns their number, or -1: an
+// empty payload, a varint that is cut short or overflows, a relative offset of 0, an offset beyond 2^63, a size outside 1 .. max_block.
+template <class Ref>
+MLZ_SEARCH_HD int sidecar_parse_refs(const uint8_t* p, uint32_t clen, uint64_t max_block, Ref ref) {
+    if (clen == 0) return -1;
+    int cnt = 0;
+    uint64_t prev = 0;
+    for (uint32_t o = 0; o < clen; cnt++) {
+        uint64_t off = 0, mma = 0;
+        const int n1 = walk_uvarint(p + o, clen - o, &off);
+        if (n1 <= 0) return -1;
+        o += uint32_t(n1);
+        const int n2 = walk_uvarint(p + o, clen - o, &mma);
+        if (n2 <= 0) return -1;
+        o += uint32_t(n2);
+        if (cnt && off == 0) return -1;
+        const uint64_t abs = cnt ? prev + off : off;
+        if (abs >> 63 || (cnt && abs < prev)) return -1;
+        if (mma >= max_block) return -1;   // (the decoded bytes are max_block - mma: 1 .. max_block)
+        ref(abs, max_block - mma);
+        prev = abs;
+    }
+    return cnt;
+}
+// The data chunk of the main stream whose header lies at `off` (hdr_of(k): ascending), or -1
+template <class H>
+MLZ_SEARCH_HD int64_t sidecar_find_chunk(size_t nck, H hdr_of, uint64_t off) {
+    size_t lo = 0, hi = nck;
+    while (lo < hi) {
+        const size_t mid = lo + (hi - lo) / 2;
+        if (hdr_of(mid) < off) lo = mid + 1; else hi = mid;
+    }
+    return lo < nck && hdr_of(lo) == off ? int64_t(lo) : -1;
+}
+// One 0x47 chunk against the main stream, as the attach applies it: every reference names a data chunk (hdr_of), states its decoded bytes
+// (n_of) and lies behind `floor` (the last reference of the 0x47 chunk before this one; none: have_floor = false).  Returns the chunk the
+// FIRST reference names (the owner of the tables in front of the 0x47) and *last = the last reference's offset, or -1.
+template <class H, class N>
+MLZ_SEARCH_HD int64_t sidecar_check_refs(const uint8_t* p, uint32_t clen, uint64_t max_block, size_t nck, H hdr_of, N n_of, bool have_floor, uint64_t floor, uint64_t* last) {
+    int64_t first = -1;
+    bool bad = false, have = have_floor;
+    uint64_t prev = floor;
+    int seen = 0;
+    const int cnt = sidecar_parse_refs(p, clen, max_block, [&](uint64_t off, uint64_t size) {
+        if (have && off <= prev) bad = true;
+        const int64_t k = sidecar_find_chunk(nck, hdr_of, off);
+        if (k < 0 || n_of(size_t(k)) != size) bad = true;
+        if (seen++ == 0) first = k;
+        have = true; prev = off;
+    });
+    if (cnt <= 0 || bad) return -1;
+    *last = prev;
+    return first;
 }
 
 // ---- the writer's side: the reductions of one table (3.2, the reference's population rules) ----

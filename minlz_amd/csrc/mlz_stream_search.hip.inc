@@ -7,15 +7,16 @@
 // an occurrence of the stream's prefix in the pattern, probed group by group.  Per handle, once: search_info_kernel reads the info chunk, search_locate_kernel
 // (one lane per data chunk) hops over the chunk headers between the previous data chunk's end and its own start to the first table chunk
 // that fits, and the existing CRC pass checks the tables.  Per call: the host hashes the pattern's windows (search_pattern_hashes),
-// search_probe_kernel looks them up in every table (8 bytes per chunk come back) and the rule of mlz_stream_search.h (search_decoded_set)
-// turns that into the set of chunks to decode.  stream_run_chunk_jobs decodes
+// search_plan_kernel looks them up in every table of every table set (one set for a stream's inline tables, up to four for an attached
+// sidecar: mlz_stream_sidecar.hip.inc) and applies the rule of mlz_stream_search.h (search_decoded_mark_all); one byte per chunk comes back:
+// the set of chunks to decode.  The search for many patterns plans through the same function.  stream_run_chunk_jobs decodes
 // exactly those into the scratch, chunks that are neighbours in the stream side by side, and search_scan_kernel marks the occurrences of every
 // run in a bitmap (one bit per decoded byte of the set) and counts them per tile.  search_prefix_kernel's scan over the tile counts and search_write_kernel then
 // put the smallest `cap` positions out in ascending order.
 
 namespace mlz {
 
-struct SearchInfo { uint32_t M, B, ok, T; uint8_t field[kSearchMaxField + 2]; };
+using SearchInfo = SearchConfig;   // (T, M, B, prefix field) of an info chunk; ok = 0: none that is usable
 struct SearchHop { uint64_t from, limit; };                               // where a lane starts to hop and the data chunk's body, which it never reaches
 
 __device__ __forceinline__ bool search_is_data(uint8_t t) { return t >= 1 && t <= 3; }
@@ -68,15 +69,35 @@ __global__ __launch_bounds__(64) void search_locate_kernel(const uint8_t* __rest
     tabs[k] = t;
 }
 
-// One lane per data chunk: the leading and the trailing run of the pattern's windows (groups) that the chunk's table holds
-__global__ __launch_bounds__(64) void search_probe_kernel(const uint8_t* __restrict__ src, const SearchTab* __restrict__ tabs, uint32_t nck, uint32_t B,
-                                                          const uint32_t* __restrict__ hashes, uint32_t nw, uint32_t gsize, uint2* __restrict__ out) {
-    const uint32_t k = blockIdx.x * 64 + threadIdx.x;
-    if (k >= nck) return;
-    const SearchTab t = tabs[k];
-    uint32_t a = nw, s = nw;
-    if (t.R != kSearchNoTable) search_probe(src + t.off, B - t.R, hashes, nw, &a, &s, gsize);
-    out[k] = make_uint2(a, s);
+// The plan of both searches.  The table sets of a handle: one for a stream's inline tables, up to kSidecarMaxConfigs for an attached sidecar;
+// set c's table of chunk k is tabs[c * nck + k], its bytes lie at base + off (base: the stream, or the sidecar).  pats[p * sets.n + c] is
+// pattern p as set c sees it (nw = 0: the set cannot serve the pattern; L is set in every record).
+// ov[c]: search_chunk_candidate's ov, a sidecar set's overlap (0 for inline tables).
+struct SearchPlanSets { uint32_t n, B[kSidecarMaxConfigs], ov[kSidecarMaxConfigs]; };
+// One lane per (data chunk, pattern): every set's verdict on the chunk (search_chunk_candidate over the probes of its table and the next
+// chunk's), their conjunction, and the marking (search_decoded_mark_all) ORed into take[].  A lane loops over the sets: there are four at the
+// most, and the conjunction wants all votes of a (chunk, pattern) in one place.
+__global__ __launch_bounds__(256) void search_plan_kernel(const uint8_t* __restrict__ base, const SearchTab* __restrict__ tabs, const uint64_t* __restrict__ n_of, uint32_t nck,
+                                                          SearchPlanSets sets, const uint32_t* __restrict__ hashes, const SearchManyPat* __restrict__ pats, uint32_t np,
+                                                          uint8_t* __restrict__ take) {
+    const uint64_t idx = uint64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (idx >= uint64_t(nck) * np) return;
+    const uint32_t k = uint32_t(idx % nck);
+    const SearchManyPat* mine = pats + (idx / nck) * sets.n;
+    auto sizes = [&](size_t j) { return n_of[j]; };
+    auto admits = [&](uint32_t c) {
+        const SearchManyPat pt = mine[c];
+        if (!pt.nw) return true;
+        const uint32_t* h = hashes + pt.h_off;
+        auto probe = [&](size_t j, bool lead) {
+            const SearchTab t = tabs[size_t(c) * nck + j];
+            uint32_t a = pt.nw, s = pt.nw;
+            if (t.R != kSearchNoTable) search_probe(base + t.off, sets.B[c] - t.R, h, pt.nw, &a, &s, pt.gsize);
+            return lead ? a : s;
+        };
+        return search_chunk_candidate(k, nck, [&](size_t j) { return probe(j, true); }, [&](size_t j) { return probe(j, false); }, sizes, pt.nw, pt.L, pt.t_min, sets.ov[c]);
+    };
+    search_decoded_mark_all(k, nck, sets.n, admits, sizes, mine[0].L, take);
 }
 
 // One workgroup per tile: bit i of the tile's bitmap = "the pattern starts at the tile's position i"; counts[tile] = the set bits.
@@ -178,9 +199,10 @@ int64_t dev_reader_search_tables(mlz_dev_reader* rd, hipStream_t sm, bool ignore
         HIPCHK(c, hipMemcpyAsync(h_tabs, d_tabs, nck * sizeof(mlz::SearchTab), hipMemcpyDeviceToHost, sm));
         if ((r = fetch(c, sm, h_info, d_info, sizeof(mlz::SearchInfo)))) return r;
         st.tabs.assign(h_tabs, h_tabs + nck);
-        st.M = h_info->M; st.B = h_info->B; st.T = h_info->T; st.info = h_info->ok != 0;
-        std::memcpy(st.field, h_info->field, sizeof(st.field));
-        if (ignore_crc || !st.info) break;
+        st.ncfg = h_info->ok ? 1 : 0;
+        st.cfg[0] = *h_info;
+        st.base = rd->d_src;
+        if (ignore_crc || !st.ncfg) break;
         std::vector<mlz_block_desc> desc;
         std::vector<size_t> who;
         for (size_t k = 0; k < nck; k++)
@@ -194,9 +216,101 @@ int64_t dev_reader_search_tables(mlz_dev_reader* rd, hipStream_t sm, bool ignore
             if (h_crc[i] != st.tabs[who[i]].crc) { skip[who[i]]++; again = true; }   // a broken table: the next one that fits, if there is one
         if (!again) break;
     }
-    st.usable = 0;
-    for (size_t k = 0; k < nck; k++) st.usable += st.tabs[k].R != mlz::kSearchNoTable ? 1 : 0;
     st.ready = true;
+    return 0;
+}
+
+// The table sets a search on the handle uses: those of the attached sidecar, else the stream's inline ones (found by the handle's first search)
+int64_t dev_reader_search_sets(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, const mlz_dev_reader::SearchTables** out) {
+    if (rd->side_on) { *out = &rd->side; return 0; }
+    *out = &rd->search[ignore_crc ? 1 : 0];
+    return dev_reader_search_tables(rd, sm, ignore_crc);
+}
+
+// The plan of both searches: the union of the patterns' decoded sets -> take[] and their number, the patterns no table set can serve and the
+// context's counter 11 (the chunks with a usable table of at least one set that serves a pattern).  off[i]: pattern i's bytes in `patterns`.
+// The host hashes every pattern's windows for every set (search_pattern_hashes); search_plan_kernel marks the set and one byte per chunk
+// comes back.  A pattern that is not served puts every chunk with a byte into the set, so the kernel is not run then.
+int64_t dev_reader_search_plan(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* patterns, const std::vector<uint32_t>& off, size_t n,
+                               std::vector<uint8_t>* take, size_t* n_take, uint64_t* unserved) {
+    mlz_ctx* c = rd->ctx;
+    const size_t nck = rd->chunks.size();
+    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0;
+    *unserved = n;
+    if (!(flags & MLZ_SEARCH_NO_TABLES)) {
+        const mlz_dev_reader::SearchTables* stp = nullptr;
+        const int64_t r = dev_reader_search_sets(rd, sm, ignore_crc, &stp);
+        if (r) return r;
+        const mlz_dev_reader::SearchTables& st = *stp;
+        auto usable_of = [&](uint32_t serving /* a bit per set */) {
+            size_t u = 0;
+            for (size_t k = 0; k < nck; k++) {
+                bool any = false;
+                for (uint32_t s = 0; s < st.ncfg; s++) any = any || (((serving >> s) & 1) && st.tabs[s * nck + k].R != mlz::kSearchNoTable);
+                u += any ? 1 : 0;
+            }
+            return u;
+        };
+        if (st.ncfg && usable_of((1u << st.ncfg) - 1)) {
+            std::vector<uint32_t> win(mlz::kSearchMaxWindows), hs;
+            std::vector<mlz::SearchManyPat> pats(n * st.ncfg);
+            uint32_t serving = 0;
+            size_t served = 0;
+            for (size_t i = 0; i < n; i++) {
+                bool any = false;
+                for (uint32_t s = 0; s < st.ncfg; s++) {
+                    const mlz::SearchConfig& cf = st.cfg[s];
+                    mlz::SearchManyPat& pt = pats[i * st.ncfg + s];
+                    pt = mlz::SearchManyPat{0, 0, 1, 1, off[i + 1] - off[i], 0};
+                    if (mlz::search_pattern_hashes(patterns + off[i], off[i + 1] - off[i], cf.T, cf.M, cf.B, cf.field, win.data(), &hs, &pt)) { any = true; serving |= 1u << s; }
+                }
+                served += any ? 1 : 0;
+            }
+            const size_t usable = usable_of(serving);
+            // (a pattern whose serving sets hold no table at all is one the tables cannot serve)
+            if (!usable) served = 0;
+            *unserved = n - served;
+            if (served) c->search_tables = usable;
+            if (*unserved == 0) {
+                // hashes, pattern records and the chunks' sizes go up as one block, staged in the pinned buffer; one byte per chunk comes back
+                Carve up;
+                const auto u_hs = up.take<uint32_t>(hs.size());
+                const auto u_pats = up.take<mlz::SearchManyPat>(pats.size());
+                const auto u_n = up.take<uint64_t>(nck);
+                Carve cv;
+                const auto r_up = cv.take<uint8_t>(up.bytes);
+                const auto r_take = cv.take<uint8_t>(nck);
+                HIPCHK(c, c->d_rplan.ensure(cv.bytes));
+                int e = ensure_stream_objects(c, 0, up.bytes > nck ? up.bytes : nck);
+                if (e) return e;
+                void *ws = r_up.at(c->d_rplan.p), *h_up = c->pinned2;
+                std::memcpy(u_hs.at(h_up), hs.data(), hs.size() * 4);
+                std::memcpy(u_pats.at(h_up), pats.data(), pats.size() * sizeof(mlz::SearchManyPat));
+                uint64_t* h_n = u_n.at(h_up);
+                for (size_t k = 0; k < nck; k++) h_n[k] = rd->chunks[k].n;
+                uint8_t* d_take = r_take.at(c->d_rplan.p);
+                mlz::SearchPlanSets sets{};
+                sets.n = st.ncfg;
+                for (uint32_t s = 0; s < st.ncfg; s++) {
+                    sets.B[s] = st.cfg[s].B;
+                    sets.ov[s] = stp == &rd->side ? mlz::search_overlap(st.cfg[s].T, st.cfg[s].M, st.cfg[s].field) : 0;
+                }
+                { WorkspaceOrder order(c, sm); }
+                HIPCHK(c, hipMemcpyAsync(ws, h_up, up.bytes, hipMemcpyHostToDevice, sm));
+                HIPCHK(c, hipMemsetAsync(d_take, 0, nck, sm));
+                const uint64_t lanes = uint64_t(nck) * n;
+                hipLaunchKernelGGL(mlz::search_plan_kernel, dim3(uint32_t((lanes + 255) / 256)), dim3(256), 0, sm, st.base, static_cast<const mlz::SearchTab*>(st.d_tabs),
+                                   u_n.at(ws), uint32_t(nck), sets, u_hs.at(ws), u_pats.at(ws), uint32_t(n), d_take);
+                if ((e = fetch(c, sm, c->pinned2, d_take, nck))) return e;   // (behind the upload on sm: the staged block has left the pinned buffer)
+                std::memcpy(take->data(), c->pinned2, nck);
+                *n_take = 0;
+                for (size_t k = 0; k < nck; k++) *n_take += (*take)[k];
+                return 0;
+            }
+        }
+    }
+    *n_take = 0;   // a pattern the tables cannot serve: every chunk that holds a byte
+    for (size_t k = 0; k < nck; k++) *n_take += ((*take)[k] = rd->chunks[k].n ? 1 : 0);
     return 0;
 }
 
@@ -297,42 +411,11 @@ int64_t dev_reader_search_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t fl
     search_begin(rd, stats);
     if (nck == 0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
-    std::vector<uint8_t> take(nck, 1);
+    std::vector<uint8_t> take(nck, 0);
     size_t n_take = 0;
-    bool with_tables = (flags & MLZ_SEARCH_NO_TABLES) == 0;
-    if (with_tables) {
-        const int64_t r = dev_reader_search_tables(rd, sm, ignore_crc);
-        if (r) return r;
-        const mlz_dev_reader::SearchTables& st = rd->search[ignore_crc ? 1 : 0];
-        // the windows the tables answer for and their hashes (search_pattern_hashes); none: the tables cannot serve this pattern
-        std::vector<uint32_t> win(st.T == 4 ? mlz::kSearchMaxWindows : mlz::kSearchMaxPattern), hs;
-        mlz::SearchManyPat pt;
-        with_tables = st.info && st.usable && mlz::search_pattern_hashes(pattern, L, st.T, st.M, st.B, st.field, win.data(), &hs, &pt);
-        if (with_tables) {
-            // the windows' hashes go up, two counts per chunk come back
-            Carve cv;
-            const auto r_hs = cv.take<uint32_t>(hs.size());
-            const auto r_out = cv.take<uint2>(nck);
-            HIPCHK(c, c->d_rplan.ensure(cv.bytes));
-            int e = ensure_stream_objects(c, 0, nck * 8);
-            if (e) return e;
-            uint32_t* d_hs = r_hs.at(c->d_rplan.p);
-            uint2* d_out = r_out.at(c->d_rplan.p);
-            { WorkspaceOrder order(c, sm); }
-            HIPCHK(c, hipMemcpyAsync(d_hs, hs.data(), hs.size() * 4, hipMemcpyHostToDevice, sm));
-            hipLaunchKernelGGL(mlz::search_probe_kernel, dim3(uint32_t((nck + 63) / 64)), dim3(64), 0, sm, rd->d_src, static_cast<const mlz::SearchTab*>(st.d_tabs), uint32_t(nck), st.B,
-                               d_hs, pt.nw, pt.gsize, d_out);
-            if ((e = fetch(c, sm, c->pinned2, d_out, nck * 8))) return e;
-            const uint32_t* as = static_cast<const uint32_t*>(c->pinned2);
-            n_take = mlz::search_decoded_set(nck, [&](size_t k) { return as[2 * k]; }, [&](size_t k) { return as[2 * k + 1]; },
-                                             [&](size_t k) { return uint64_t(rd->chunks[k].n); }, pt.nw, L, take.data(), pt.t_min);
-            c->search_tables = st.usable;
-        }
-    }
-    if (!with_tables) {
-        n_take = 0;
-        for (size_t k = 0; k < nck; k++) n_take += (take[k] = rd->chunks[k].n ? 1 : 0);
-    }
+    uint64_t unserved = 0;
+    const int64_t pr = dev_reader_search_plan(rd, sm, flags, pattern, std::vector<uint32_t>{0, L}, 1, &take, &n_take, &unserved);
+    if (pr) return pr;
     c->search_chunks = n_take;
     if (stats) { stats[1] = n_take; stats[2] = c->search_tables; }
     if (n_take == 0) return 0;

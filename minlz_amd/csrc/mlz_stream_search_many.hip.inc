@@ -1,10 +1,10 @@
 // mlz_stream_search_many.hip.inc — mlz_dev_reader_search_many: where each of up to 4096 byte strings occurs in a .mz stream that lies in HBM,
 // in one call (included behind mlz_stream_search.hip.inc, whose per-handle tables, decode helpers and prefix kernel it uses).
 //
-// Plan (dev_reader_search_many_plan): the host computes every pattern's windows and their hashes
-// (search_pattern_hashes: work proportional to the patterns); search_many_plan_kernel, one lane per (data chunk, pattern), probes the chunk's
-// table and the next one's and applies the decoded-set rule of that pattern (search_decoded_mark) to ONE byte array: the union of the
-// patterns' sets.  Only those nck bytes come back.  A pattern the tables cannot serve puts every chunk into the set, so the kernel is not run then.
+// Plan (dev_reader_search_plan, mlz_stream_search.hip.inc: the plan of the search for one pattern with more patterns): the host computes every
+// pattern's windows and their hashes (search_pattern_hashes: work proportional to the patterns); search_plan_kernel, one lane per (data chunk,
+// pattern), probes the chunk's table and the next one's in every table set and applies the decoded-set rule of that pattern to ONE byte array:
+// the union of the patterns' sets.  Only those nck bytes come back.  A pattern the tables cannot serve puts every chunk into the set, so the kernel is not run then.
 // Scan: the set is decoded once, group by group (search_decode_run), and search_many_kernel<false> examines each tile of start positions:
 // the tile's bytes are staged in LDS, a lane walks 64 neighbouring positions, hashes the first m bytes of each to a bucket of the pattern
 // index (heads and order in LDS) and verifies the bucket's patterns as far as the run holds their bytes.  Per-pattern counts gather in LDS and leave
@@ -37,24 +37,6 @@ __host__ __device__ inline SearchManyLds search_many_lds(uint32_t n, uint32_t hb
     if (in_lds) { w += n + 1; l.blob = w; w += (blob_bytes + 3) / 4; }
     l.words = w;
     return l;
-}
-
-// One lane per (data chunk, served pattern): the pattern's decoded-set rule for that chunk, ORed into take[]
-__global__ __launch_bounds__(256) void search_many_plan_kernel(const uint8_t* __restrict__ src, const SearchTab* __restrict__ tabs, const uint64_t* __restrict__ n_of, uint32_t nck,
-                                                               uint32_t B, const uint32_t* __restrict__ hashes, const SearchManyPat* __restrict__ pats, uint32_t np,
-                                                               uint8_t* __restrict__ take) {
-    const uint64_t idx = uint64_t(blockIdx.x) * 256 + threadIdx.x;
-    if (idx >= uint64_t(nck) * np) return;
-    const uint32_t k = uint32_t(idx % nck);
-    const SearchManyPat pt = pats[idx / nck];
-    const uint32_t* h = hashes + pt.h_off;
-    auto probe = [&](size_t j, bool lead) {
-        const SearchTab t = tabs[j];
-        uint32_t a = pt.nw, s = pt.nw;
-        if (t.R != kSearchNoTable) search_probe(src + t.off, B - t.R, h, pt.nw, &a, &s, pt.gsize);
-        return lead ? a : s;
-    };
-    search_decoded_mark(k, nck, [&](size_t j) { return probe(j, true); }, [&](size_t j) { return probe(j, false); }, [&](size_t j) { return n_of[j]; }, pt.nw, pt.L, take, pt.t_min);
 }
 
 // One workgroup per tile.  kWrite = false: counts[tile] = the tile's pairs, pat_counts[p] += pattern p's.  kWrite = true: the pairs of a tile
@@ -140,66 +122,6 @@ __global__ __launch_bounds__(kSearchManyThreads) void search_many_kernel(const u
 
 namespace {
 
-// The plan: the union of the patterns' decoded sets -> take[] and their number, the patterns the tables cannot serve and the context's
-// counter 11.  off[i]: pattern i's bytes in `patterns`.  The host hashes every pattern's windows (search_pattern_hashes);
-// search_many_plan_kernel marks the set and one byte per chunk comes back.  A pattern that is not served puts every chunk with a byte into
-// the set, so the kernel is not run then.
-int64_t dev_reader_search_many_plan(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* patterns, const std::vector<uint32_t>& off, size_t n,
-                                    std::vector<uint8_t>* take, size_t* n_take, uint64_t* unserved) {
-    mlz_ctx* c = rd->ctx;
-    const size_t nck = rd->chunks.size();
-    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0;
-    *unserved = n;
-    if (!(flags & MLZ_SEARCH_NO_TABLES)) {
-        const int64_t r = dev_reader_search_tables(rd, sm, ignore_crc);
-        if (r) return r;
-        const mlz_dev_reader::SearchTables& st = rd->search[ignore_crc ? 1 : 0];
-        if (st.info && st.usable) {
-            std::vector<uint32_t> win(st.T == 4 ? mlz::kSearchMaxWindows : mlz::kSearchMaxPattern), hs;
-            std::vector<mlz::SearchManyPat> pats;
-            for (size_t i = 0; i < n; i++) {
-                mlz::SearchManyPat pt;
-                if (mlz::search_pattern_hashes(patterns + off[i], off[i + 1] - off[i], st.T, st.M, st.B, st.field, win.data(), &hs, &pt)) pats.push_back(pt);
-            }
-            *unserved = n - pats.size();
-            if (!pats.empty()) c->search_tables = st.usable;
-            if (*unserved == 0) {
-                // hashes, pattern records and the chunks' sizes go up as one block, staged in the pinned buffer; one byte per chunk comes back
-                Carve up;
-                const auto u_hs = up.take<uint32_t>(hs.size());
-                const auto u_pats = up.take<mlz::SearchManyPat>(pats.size());
-                const auto u_n = up.take<uint64_t>(nck);
-                Carve cv;
-                const auto r_up = cv.take<uint8_t>(up.bytes);
-                const auto r_take = cv.take<uint8_t>(nck);
-                HIPCHK(c, c->d_rplan.ensure(cv.bytes));
-                int e = ensure_stream_objects(c, 0, up.bytes > nck ? up.bytes : nck);
-                if (e) return e;
-                void *ws = r_up.at(c->d_rplan.p), *h_up = c->pinned2;
-                std::memcpy(u_hs.at(h_up), hs.data(), hs.size() * 4);
-                std::memcpy(u_pats.at(h_up), pats.data(), pats.size() * sizeof(mlz::SearchManyPat));
-                uint64_t* h_n = u_n.at(h_up);
-                for (size_t k = 0; k < nck; k++) h_n[k] = rd->chunks[k].n;
-                uint8_t* d_take = r_take.at(c->d_rplan.p);
-                { WorkspaceOrder order(c, sm); }
-                HIPCHK(c, hipMemcpyAsync(ws, h_up, up.bytes, hipMemcpyHostToDevice, sm));
-                HIPCHK(c, hipMemsetAsync(d_take, 0, nck, sm));
-                const uint64_t lanes = uint64_t(nck) * pats.size();
-                hipLaunchKernelGGL(mlz::search_many_plan_kernel, dim3(uint32_t((lanes + 255) / 256)), dim3(256), 0, sm, rd->d_src, static_cast<const mlz::SearchTab*>(st.d_tabs),
-                                   u_n.at(ws), uint32_t(nck), st.B, u_hs.at(ws), u_pats.at(ws), uint32_t(pats.size()), d_take);
-                if ((e = fetch(c, sm, c->pinned2, d_take, nck))) return e;   // (behind the upload on sm: the staged block has left the pinned buffer)
-                std::memcpy(take->data(), c->pinned2, nck);
-                *n_take = 0;
-                for (size_t k = 0; k < nck; k++) *n_take += (*take)[k];
-                return 0;
-            }
-        }
-    }
-    *n_take = 0;   // a pattern the tables cannot serve: every chunk that holds a byte
-    for (size_t k = 0; k < nck; k++) *n_take += ((*take)[k] = rd->chunks[k].n ? 1 : 0);
-    return 0;
-}
-
 int64_t dev_reader_search_many_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* patterns, const uint32_t* pattern_len, size_t n, uint64_t* d_counts,
                                       uint64_t* d_offsets, uint32_t* d_which, uint64_t cap, uint64_t* stats) {
     mlz_ctx* c = rd->ctx;
@@ -220,7 +142,7 @@ int64_t dev_reader_search_many_locked(mlz_dev_reader* rd, hipStream_t sm, uint32
     std::vector<uint8_t> take(nck, 0);
     size_t n_take = 0;
     uint64_t unserved = 0;
-    const int64_t pr = dev_reader_search_many_plan(rd, sm, flags, patterns, index.off, n, &take, &n_take, &unserved);
+    const int64_t pr = dev_reader_search_plan(rd, sm, flags, patterns, index.off, n, &take, &n_take, &unserved);
     if (pr) return pr;
     c->search_chunks = n_take;
     if (stats) { stats[1] = n_take; stats[2] = c->search_tables; stats[3] = unserved; }

@@ -91,7 +91,8 @@ MLZ_WALK_HD WalkChunk walk_classify(const uint8_t* src, uint64_t n, uint64_t p) 
 constexpr int kWalkErrCorrupt = 1, kWalkErrTooLarge = 2, kWalkErrUnsupported = 3;
 
 // Reader.Read's running state over the table (stream_parse in mlz_stream.hip.inc, chunk for chunk and check for check in its order): `data(type,
-// crc, body_off, body_len, n, out_off)` is called for every data chunk in front of the first error.  Returns the decoded size or -MLZ_ERR_*.
+// crc, body_off, body_len, n, out_off, hdr_off)` is called for every data chunk in front of the first error (hdr_off: where the chunk's 4-byte
+// header lies, which a sidecar's remote references name).  Returns the decoded size or -MLZ_ERR_*.
 // The table ends where the walk ended: at the end of the stream, at a stub or at a chunk that runs past the end (both errors here).
 template <class Data>
 int64_t walk_parse_table(const WalkChunk* t, size_t cnt, uint64_t max_block_limit, Data data) {
@@ -115,7 +116,7 @@ int64_t walk_parse_table(const WalkChunk* t, size_t cnt, uint64_t max_block_limi
             if (w.val > max_block) return -kWalkErrTooLarge;
             const uint64_t body = clen - 4 - uint64_t(w.hl);
             if (w.val == 0 || w.val < body) return -kWalkErrCorrupt;
-            data(type, w.crc, p + 4 + uint64_t(w.hl), body, w.val, out);
+            data(type, w.crc, p + 4 + uint64_t(w.hl), body, w.val, out, w.off);
             out += w.val; stream_out += w.val;
             break;
         }
@@ -124,7 +125,7 @@ int64_t walk_parse_table(const WalkChunk* t, size_t cnt, uint64_t max_block_limi
             const uint64_t nn = clen - 4;
             if (nn > max_block) return -kWalkErrTooLarge;
             if (trunc) return -kWalkErrCorrupt;
-            data(type, w.crc, p + 4, nn, nn, out);
+            data(type, w.crc, p + 4, nn, nn, out, w.off);
             out += nn; stream_out += nn;
             break;
         }

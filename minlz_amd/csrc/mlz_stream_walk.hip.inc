@@ -18,7 +18,8 @@
 //                                  4 KiB region on the way.
 //   W5 count / scan / emit         a lane per entered 4 KiB region steps through the chunk headers inside it (usually one), counts those that
 //                                  enter the table, and after an exclusive scan of the counts writes their records (walk_classify,
-//                                  mlz_stream_walk.h) in stream order.  Skippable chunks that lie inside the stream never enter the table.
+//                                  mlz_stream_walk.h) in stream order.  Skippable chunks that lie inside the stream never enter the table —
+//                                  but for the walk of a sidecar, which keeps the chunks of types 0x44, 0x45 and 0x47.
 //
 // The table (32 bytes per chunk) is read back and the Reader's running state (block size, header / EOF bookkeeping, output offsets, the
 // first error) is applied to it on the host by walk_parse_table — the same code the host check runs (a serial pass over 32-byte
@@ -141,9 +142,12 @@ __global__ __launch_bounds__(64) void walk_mid_kernel(uint64_t n, uint32_t nreg1
 }
 
 // W5: the chunk headers of one entered 4 KiB region, in order.  EMIT = false counts the table's entries, EMIT = true writes them.
+// keep_search: the walk of a sidecar, whose info, table and reference chunks (0x44, 0x45, 0x47) enter the table like the others.
+__host__ __device__ inline bool walk_search_chunk(uint8_t type) { return type == 0x44 || type == 0x45 || type == 0x47; }
+inline bool walk_search_chunk_type(const WalkChunk& w) { return walk_search_chunk(uint8_t(w.tl >> 24)); }
 template <bool EMIT>
 __global__ __launch_bounds__(64) void walk_list_kernel(const uint8_t* __restrict__ src, uint64_t n, uint32_t nreg0, const uint32_t* __restrict__ entry0,
-                                                       uint32_t* __restrict__ counts, const uint32_t* __restrict__ first, WalkChunk* __restrict__ table) {
+                                                       uint32_t* __restrict__ counts, const uint32_t* __restrict__ first, WalkChunk* __restrict__ table, bool keep_search) {
     const uint32_t r0 = blockIdx.x * 64 + threadIdx.x;
     if (r0 >= nreg0) return;
     const uint32_t ent = entry0[r0];
@@ -161,7 +165,7 @@ __global__ __launch_bounds__(64) void walk_list_kernel(const uint8_t* __restrict
             }
             uint8_t type;
             const uint32_t clen = walk_header(src, e, &type);
-            if (!walk_skippable(type, clen, n - e - 4)) {
+            if (!walk_skippable(type, clen, n - e - 4) || (keep_search && walk_search_chunk(type))) {
                 if (EMIT) table[at + cnt] = walk_classify(src, n, e);
                 cnt++;
             }
@@ -219,9 +223,15 @@ int64_t settled(hipStream_t sm, int64_t r) {
 
 // The chunk walk of d_src[0, n) on c's device: `chunks` = the data chunks in front of the first framing error, *parsed = what stream_parse
 // returns for the same bytes.  Returns 0 or -MLZ_ERR_HIP.  Synchronous on st.  Caller holds c->mu.
-int stream_walk_device(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, size_t n, std::vector<StreamChunk>* chunks, int64_t* parsed) {
+// n_ident, ident_byte (may be NULL): the stream identifiers the table holds and the first one's block-size byte.  side (may be NULL): the walk of a sidecar — its search chunks (0x44, 0x45,
+// 0x47) enter the table, *side receives the whole table (which also stays in c->d_walk_tab for the caller's kernels), and the Reader's
+// state is applied to the other records.
+int stream_walk_device(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, size_t n, std::vector<StreamChunk>* chunks, int64_t* parsed, uint32_t* n_ident = nullptr,
+                       uint8_t* ident_byte = nullptr, std::vector<mlz::WalkChunk>* side = nullptr) {
     chunks->clear();
     *parsed = 0;
+    if (n_ident) *n_ident = 0;
+    if (side) side->clear();
     if (n == 0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t nreg0 = (uint64_t(n) + kWalkR0 - 1) >> kWalkR0Log, nreg1 = (uint64_t(n) + kWalkR1 - 1) >> kWalkR1Log;
@@ -245,7 +255,7 @@ int stream_walk_device(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, size_t 
         hipLaunchKernelGGL(mlz::walk_top_kernel, dim3(1), dim3(64), 0, st, uint64_t(n), x1, entry1);
         hipLaunchKernelGGL(mlz::walk_mid_kernel, dim3(uint32_t((nreg1 + 63) / 64)), dim3(64), 0, st, uint64_t(n), uint32_t(nreg1), x0, entry1, entry0);
         hipLaunchKernelGGL(mlz::walk_list_kernel<false>, dim3(uint32_t((nreg0 + 63) / 64)), dim3(64), 0, st, d_src, uint64_t(n), uint32_t(nreg0), entry0, counts, first,
-                           static_cast<mlz::WalkChunk*>(nullptr));
+                           static_cast<mlz::WalkChunk*>(nullptr), side != nullptr);
         hipLaunchKernelGGL(mlz::walk_scan_kernel, dim3(1), dim3(1024), 0, st, counts, uint32_t(nreg0), first, total);
         if ((r = fetch(c, st, c->pinned2, total, 4))) return r;
         h_total = *static_cast<uint32_t*>(c->pinned2);
@@ -254,15 +264,29 @@ int stream_walk_device(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, size_t 
             r = ensure_stream_objects(c, 0, size_t(h_total) * sizeof(mlz::WalkChunk));
             if (r) return r;
             mlz::WalkChunk* tab = c->d_walk_tab.as<mlz::WalkChunk>();
-            hipLaunchKernelGGL(mlz::walk_list_kernel<true>, dim3(uint32_t((nreg0 + 63) / 64)), dim3(64), 0, st, d_src, uint64_t(n), uint32_t(nreg0), entry0, counts, first, tab);
+            hipLaunchKernelGGL(mlz::walk_list_kernel<true>, dim3(uint32_t((nreg0 + 63) / 64)), dim3(64), 0, st, d_src, uint64_t(n), uint32_t(nreg0), entry0, counts, first, tab,
+                               side != nullptr);
             if ((r = fetch(c, st, c->pinned2, tab, size_t(h_total) * sizeof(mlz::WalkChunk)))) return r;
         }
     }
-    chunks->reserve(h_total);
-    *parsed = mlz::walk_parse_table(static_cast<const mlz::WalkChunk*>(c->pinned2), h_total, kMaxBlockSize,
-                                 [&](uint8_t type, uint32_t crc, uint64_t body_off, uint64_t body_len, uint64_t nn, uint64_t out_off) {
+    const mlz::WalkChunk* table = static_cast<const mlz::WalkChunk*>(c->pinned2);
+    size_t n_table = h_total;
+    std::vector<mlz::WalkChunk> others;
+    if (side) {   // the Reader never sees a search chunk that lies inside the stream
+        side->assign(table, table + h_total);
+        for (const mlz::WalkChunk& w : *side)
+            if (!(mlz::walk_search_chunk_type(w) && !(w.flags & (mlz::kWalkTrunc | mlz::kWalkStub)))) others.push_back(w);
+        table = others.data(); n_table = others.size();
+    }
+    if (n_ident)
+        for (size_t i = 0; i < n_table; i++)
+            if (!(table[i].flags & mlz::kWalkStub) && (table[i].tl >> 24) == 0xff && (*n_ident)++ == 0 && ident_byte) *ident_byte = uint8_t(table[i].val);
+    chunks->reserve(n_table);
+    *parsed = mlz::walk_parse_table(table, n_table, kMaxBlockSize,
+                                 [&](uint8_t type, uint32_t crc, uint64_t body_off, uint64_t body_len, uint64_t nn, uint64_t out_off, uint64_t hdr_off) {
                                      StreamChunk ck{};
                                      ck.type = type; ck.crc = crc; ck.body_off = size_t(body_off); ck.body_len = size_t(body_len); ck.n = size_t(nn); ck.out_off = size_t(out_off);
+                                     ck.hdr_off = size_t(hdr_off);
                                      chunks->push_back(ck);
                                  });
     return 0;

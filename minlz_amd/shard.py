@@ -180,6 +180,7 @@ class DeviceStream:
         st = torch.cuda.current_stream(t.device).cuda_stream
         self.reader = ctx.stream_open_device(t.data_ptr(), t.numel(), stream=st)
         self.size = self.reader.size
+        self.side = None   # the attached sidecar's tensor
 
     def read_ranges(self, offsets, lengths, ignore_crc=False, return_starts=False):
         """Decoded bytes [offsets[i], offsets[i] + lengths[i]) for every i, back to back in the order given -> one new uint8 tensor.
@@ -248,6 +249,29 @@ class DeviceStream:
                                            ignore_crc=ignore_crc, no_tables=no_tables, stream=st)
         k = min(total, max_results)
         return pos[:k], which[:k], counts[:len(pats)], total
+
+    def build_sidecar(self, cfgs, ignore_crc=False):
+        """A sidecar search index of this stream for 1 .. 4 configurations (api.search_config): search tables for every block, whoever
+        wrote the stream, in a separate .mz stream -> a new uint8 tensor on the stream's device."""
+        dev = self.t.device
+        cap = self.reader.sidecar_bound(cfgs)
+        out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        got = self.reader.build_sidecar(cfgs, out.data_ptr(), cap, ignore_crc=ignore_crc, stream=st)
+        return out[:got].clone()
+
+    def attach_sidecar(self, side, ignore_crc=False):
+        """search and search_many use the tables of the sidecar `side` (a uint8 tensor on the stream's device, as build_sidecar returns
+        it) from now on; None detaches.  The stream keeps the tensor alive."""
+        if side is None:
+            self.reader.detach_sidecar()
+            self.side = None
+            return
+        if side.dtype != torch.uint8 or side.dim() != 1 or not side.is_contiguous() or side.device != self.t.device:
+            raise ValueError("attach_sidecar: a contiguous 1-d uint8 tensor on the stream's device")
+        st = torch.cuda.current_stream(self.t.device).cuda_stream
+        self.reader.attach_sidecar(side.data_ptr(), side.numel(), ignore_crc=ignore_crc, stream=st)
+        self.side = side
 
     def ReadAt(self, n, offset, ignore_crc=False):
         """Up to n decoded bytes from `offset`, clamped at the end of the stream -> a new uint8 tensor."""

@@ -100,7 +100,7 @@ int main(int argc, char** argv) {
         walk(buf.data(), len, &table);
         uint64_t prefix = 0;
         const int64_t r = walk_parse_table(table.data(), table.size(), uint64_t(8) << 20,
-                                           [&](uint8_t, uint32_t, uint64_t, uint64_t, uint64_t nn, uint64_t out_off) { prefix = out_off + nn; });
+                                           [&](uint8_t, uint32_t, uint64_t, uint64_t, uint64_t nn, uint64_t out_off, uint64_t) { prefix = out_off + nn; });
         std::printf("%lld %llu %zu\n", (long long)r, (unsigned long long)(r >= 0 ? uint64_t(r) : prefix), table.size());
     }
     std::fclose(f);
