@@ -4,7 +4,6 @@ import numpy as np
 
 from minlz_amd import synth
 from tests import search_cases as SC
-from tests import search_long_prefix_tables as SL
 
 USER = b'"user":"'           # the natural prefix of synth.json_like
 ID = b'"id":"'
@@ -50,9 +49,3 @@ def designed(kind, bs, nblk, tail, M, E, pfx, seed=2):
         pats.append(("natural_inside", d[at - 3:at + K + W + 1]))
     return d, pats
 
-
-def model_plan(stream, pattern, ignore_crc=False):
-    """-> (plan, sizes, usable tables) of a search for `pattern` over `stream` by the model."""
-    T, M, B, field, tables = SL.read_tables(stream, ignore_crc)
-    sizes = [n for n, _ in SL.data_grid(stream)]
-    return SL.plan(tables, sizes, pattern, T, M, B, field), sizes, SL.usable_tables(tables, pattern, T, M, field)

@@ -4,9 +4,9 @@ import numpy as np
 
 from minlz_amd import synth
 from tests import search_cases as SC
-from tests import search_prefix_tables as SP
+from tests import search_model as SMod
 
-SETS = {"json4": b'":, ', "nonalnum": SP.NON_ALNUM}      # 4 values: table type 2; 194 values: type 3
+SETS = {"json4": b'":, ', "nonalnum": SMod.NON_ALNUM}      # 4 values: table type 2; 194 values: type 3
 PFX = ord(":")                                          # a prefix byte of both sets
 
 
@@ -26,7 +26,7 @@ def designed(kind, bs, nblk, tail, M, pset, seed=2, L=16):
       absent       16 random bytes
       absent_keyed an absent pattern that starts like a JSON key: windows to check, none of them in the data"""
     d = bytearray(getattr(synth, kind)(bs * nblk + tail, seed).tobytes())
-    mask = SP.mask_of(*SP.field_of(pset))
+    mask = SMod.mask_of(*SMod.field_of(pset))
     one = letters(L - M - 1, seed + 10) + bytes([PFX]) + letters(M, seed + 11)
     unusable = letters(L - M, seed + 12) + bytes([PFX]) + letters(M - 1, seed + 13)
     late = letters(L - 1, seed + 14) + bytes([PFX])

@@ -1,6 +1,5 @@
 """Sidecar search indexes (the reference's SEARCH.md "Sidecar Streams", SPEC_SEARCH.md 1.1 and 2.3) in plain Python, written from the
-specification alone, on top of the three table models (tests/search_tables.py: type 1, tests/search_prefix_tables.py: types 2 and 3,
-tests/search_long_prefix_tables.py: type 4).
+specification alone, on top of the model of the table types (tests/search_model.py).
 
 A sidecar is a valid stream without data chunks: the main stream's identifier, one info chunk (0x44) per table configuration, then for
 every data chunk of the main stream its table chunks (0x45, one per configuration whose table is kept) and a remote block reference (0x47:
@@ -11,9 +10,7 @@ A configuration is (T, M, field): the table type, the match length and the prefi
 import numpy as np
 
 import oracle as O
-from tests import search_long_prefix_tables as SL
-from tests import search_prefix_tables as SP
-from tests import search_tables as ST
+from tests import search_model as SMod
 
 CHUNK_REF = 0x47
 EOF_CHUNK = b"\x20\x01\x00\x00\x00"
@@ -26,28 +23,6 @@ class SidecarError(Exception):
     def __init__(self, kind, why):
         super().__init__("%s: %s" % (kind, why))
         self.kind = kind
-
-
-def config(T, M=6, prefix=b"", extras=0):
-    """(T, M, field) as api.search_config describes it: type 2 keeps 1 .. 8 values in the order given (the last one repeated), type 3 makes
-    the mask of the values, type 4 is `K-1 | E | prefix`."""
-    prefix = bytes(prefix)
-    if T == 1:
-        return 1, M, b""
-    if T == 2:
-        assert 1 <= len(prefix) <= 8
-        return 2, M, prefix + prefix[-1:] * (8 - len(prefix))
-    if T == 3:
-        m = bytearray(32)
-        for v in prefix:
-            m[v >> 3] |= 1 << (v & 7)
-        return 3, M, bytes(m)
-    return 4, M, SL.field_of(prefix, extras)
-
-
-def overlap(cfg):
-    T, M, field = cfg
-    return M - 1 if T == 1 else M if T in (2, 3) else SL.overlap(M, field)
 
 
 def uvarint(v):
@@ -76,7 +51,7 @@ def read_uvarint(b, p):
 
 
 def ref_chunk(hdr_off, max_minus_actual):
-    return ST.frame(CHUNK_REF, uvarint(hdr_off) + uvarint(max_minus_actual))
+    return SMod.frame(CHUNK_REF, uvarint(hdr_off) + uvarint(max_minus_actual))
 
 
 def parse_refs(payload, max_block):
@@ -107,11 +82,11 @@ def parse_refs(payload, max_block):
 def main_chunks(stream):
     """[(header offset, decoded bytes)] of the main stream's data chunks."""
     out = []
-    for p, t, n in ST.chunks_of(stream):
+    for p, t, n in SMod.chunks_of(stream):
         if t == 0x01:
             out.append((p, n - 4))
         elif t in (0x02, 0x03):
-            out.append((p, ST.S.uvarint(stream, p + 8)[0]))
+            out.append((p, SMod.S.uvarint(stream, p + 8)[0]))
     return out
 
 
@@ -124,7 +99,7 @@ def framed(data, sizes, size_byte=6):
         blk = data[o:o + sz]
         enc = O.encode(blk, 1)
         stored = len(enc) == sz + 2
-        out.append(ST.frame(0x01 if stored else 0x02, O.crc(blk).to_bytes(4, "little") + (blk if stored else enc[1:])))
+        out.append(SMod.frame(0x01 if stored else 0x02, O.crc(blk).to_bytes(4, "little") + (blk if stored else enc[1:])))
         o += sz
     n = uvarint(len(data))
     out.append(b"\x20" + bytes([len(n), 0, 0]) + n)
@@ -132,7 +107,7 @@ def framed(data, sizes, size_byte=6):
 
 
 def identifier(stream):
-    for p, t, n in ST.chunks_of(stream):
+    for p, t, n in SMod.chunks_of(stream):
         if t == 0xFF:
             return bytes(stream[p:p + 10])
     return None
@@ -140,27 +115,6 @@ def identifier(stream):
 
 def max_block_of(ident):
     return 1 << ((ident[9] & 15) + 10)
-
-
-def table_of(cfg, block, nxt, B):
-    """(table, R) or (None, 0).  nxt: the next data chunk's bytes (all of them; each model cuts what it needs), None for the last one."""
-    T, M, field = cfg
-    if T == 1:
-        return ST.build_table(block, nxt, B, M)
-    if T in (2, 3):
-        return SP.build_table(block, nxt, B, M, SP.mask_of(T, field))
-    return SL.build_table(block, nxt, B, M, field)
-
-
-def info_chunk(cfg, B):
-    T, M, field = cfg
-    return ST.frame(ST.CHUNK_INFO, bytes([T, M, B]) + field)
-
-
-def table_chunk(cfg, B, table, R, crc=None):
-    T, M, field = cfg
-    crc = O.crc(table) if crc is None else crc
-    return ST.frame(ST.CHUNK_TABLE, bytes([T, M, B]) + field + bytes([R]) + crc.to_bytes(4, "little") + table)
 
 
 def build(stream, data, cfgs, with_tables=False, cache=None):
@@ -171,8 +125,8 @@ def build(stream, data, cfgs, with_tables=False, cache=None):
     ident = identifier(stream)
     assert ident is not None and 1 <= len(cfgs) <= MAX_CONFIGS
     mb = max_block_of(ident)
-    B = ST.table_bits(mb)
-    out = [ident] + [info_chunk(c, B) for c in cfgs]
+    B = SMod.table_bits(mb)
+    out = [ident] + [SMod.info_chunk(c, B) for c in cfgs]
     dcs = main_chunks(stream)
     tables = [[None] * len(dcs) for _ in cfgs]
     live = [i for i, (_, n) in enumerate(dcs) if n]          # a chunk of no bytes: no table, no reference, nobody's next chunk
@@ -188,12 +142,12 @@ def build(stream, data, cfgs, with_tables=False, cache=None):
             if cache is not None and (c, i) in cache:
                 tab, R = cache[c, i]
             else:
-                tab, R = table_of(c, blk, nxt, B)
+                tab, R = SMod.build_table(c, blk, nxt, B)
                 if cache is not None:
                     cache[c, i] = (tab, R)
             if tab is not None:
                 tables[ci][i] = (tab, R)
-                out.append(table_chunk(c, B, tab, R))
+                out.append(SMod.table_chunk(c, B, tab, R))
         out.append(ref_chunk(p, mb - n))
     out.append(EOF_CHUNK)
     side = b"".join(out)
@@ -245,10 +199,10 @@ def parse(side, main_stream, ignore_crc=False):
     mb = max_block_of(ident)
     cfgs, Bs = [], []
     for p, t, n in cks:
-        if t in (ST.CHUNK_TABLE, CHUNK_REF):
+        if t in (SMod.CHUNK_TABLE, CHUNK_REF):
             break
-        if t == ST.CHUNK_INFO and len(cfgs) < MAX_CONFIGS:
-            got = SL.info_of(bytes(side[p + 4:p + 4 + n]))
+        if t == SMod.CHUNK_INFO and len(cfgs) < MAX_CONFIGS:
+            got = SMod.info_of(bytes(side[p + 4:p + 4 + n]))
             if got is not None:
                 cfgs.append((got[0], got[1], got[3]))
                 Bs.append(got[2])
@@ -256,7 +210,7 @@ def parse(side, main_stream, ignore_crc=False):
     pending, floor = [], None
     for p, t, n in cks:
         body = bytes(side[p + 4:p + 4 + n])
-        if t == ST.CHUNK_TABLE:
+        if t == SMod.CHUNK_TABLE:
             pending.append(body)
         elif t == CHUNK_REF:
             refs = parse_refs(body, mb)
@@ -269,76 +223,16 @@ def parse(side, main_stream, ignore_crc=False):
                     raise SidecarError("corrupt", "a reference names no data chunk of this size")
                 floor = off
             k = where[refs[0][0]]
-            for ci, (T, M, field) in enumerate(cfgs):
-                B, f = Bs[ci], len(field)
-                for tb in pending:
-                    if len(tb) >= 8 + f + 32 and tb[:3 + f] == bytes([T, M, B]) + field:
-                        R = tb[3 + f]
-                        if R <= B - 8 and len(tb) - 8 - f == 1 << (B - R - 3):
-                            tab = tb[8 + f:]
-                            if ignore_crc or O.crc(tab) == int.from_bytes(tb[4 + f:8 + f], "little"):
-                                tables[ci][k] = (tab, R)
-                                break
+            for ci, c in enumerate(cfgs):
+                fits = (SMod.table_fits(tb, c, Bs[ci]) for tb in pending)
+                tables[ci][k] = next((f[:2] for f in fits if f is not None and (ignore_crc or O.crc(f[0]) == f[2])), None)
             pending = []
     return cfgs, Bs, tables
 
 
-def probes(tables, pattern, cfg, B):
-    """One configuration against the pattern -> (a, s, nw, t_min) with a[k], s[k] the probe of chunk k, or None: it cannot serve the pattern."""
-    T, M, field = cfg
-    P = np.frombuffer(bytes(pattern), np.uint8)
-    if T == 4:
-        G, t_min = SL.groups(pattern, M, field)
-        if not G:
-            return None
-        K, E, _ = SL.parts_of(field)
-        h = ST.hash_windows(P, B, M)
-        gh = [[int(h[i + K + j]) for j in range(E + 1)] for i in G]
-        pr = [SL.probe(t[0], t[1], B, gh) if t is not None else (len(gh), len(gh)) for t in tables]
-        return [p[0] for p in pr], [p[1] for p in pr], len(gh), t_min
-    W, t_min = SP.windows(pattern, T, M, field)
-    if not W:
-        return None
-    h = ST.hash_windows(P, B, M)
-    hs = [int(h[i]) for i in W]
-    pr = [ST.probe(t[0], t[1], B, hs) if t is not None else (len(hs), len(hs)) for t in tables]
-    return [p[0] for p in pr], [p[1] for p in pr], len(hs), t_min
-
-
-def admits(a, s, sizes, nw, L, t_min, ov=0):
-    """One table set's verdict per chunk: all windows (groups) in its own table, or a split with the next chunk's.  ov: the set's overlap.
-    A block's table is built over the next chunk's bytes alone, so in front of a chunk shorter than the overlap the windows that reach
-    beyond that chunk were hashed over zeros: the table proves nothing there, and the set abstains (it admits the chunk)."""
-    n, out = len(sizes), []
-    for k in range(n):
-        cand = a[k] == nw or (k + 1 < n and sizes[k + 1] < ov)
-        if not cand and k + 1 < n:
-            s_next = nw if sizes[k + 1] < L else s[k + 1]
-            cand = max(t_min, nw - s_next) <= a[k]
-        out.append(cand)
-    return out
-
-
-def decoded_set(votes, sizes, L):
-    """votes: one list of verdicts per voting table set -> the chunks to decode: every chunk with bytes that no set refuses, plus the chunks
-    that hold the L - 1 bytes behind it."""
-    n, take = len(sizes), set()
-    for k in range(n):
-        if not sizes[k] or not all(v[k] for v in votes):
-            continue
-        take.add(k)
-        need, j = L - 1, k + 1
-        while need > 0 and j < n:
-            if sizes[j]:
-                take.add(j)
-            need -= sizes[j]
-            j += 1
-    return sorted(take)
-
-
 def serving(tables_per_cfg, pattern, cfgs, Bs):
     """The probes of the configurations that vote: those that serve the pattern (all without a single usable table among them: none)."""
-    got = [(ci, probes(tables_per_cfg[ci], pattern, c, Bs[ci])) for ci, c in enumerate(cfgs)]
+    got = [(ci, SMod.probed(tables_per_cfg[ci], pattern, c, Bs[ci])) for ci, c in enumerate(cfgs)]
     got = [(ci, p) for ci, p in got if p is not None]
     if not any(t is not None for ci, _ in got for t in tables_per_cfg[ci]):
         return []
@@ -348,8 +242,8 @@ def serving(tables_per_cfg, pattern, cfgs, Bs):
 def plan(tables_per_cfg, sizes, pattern, cfgs, Bs):
     """The chunks a search for `pattern` through the sidecar decodes: the AND rule over the configurations that vote."""
     L = len(pattern)
-    votes = [admits(p[0], p[1], sizes, p[2], L, p[3], overlap(cfgs[ci])) for ci, p in serving(tables_per_cfg, pattern, cfgs, Bs)]
-    return decoded_set(votes, sizes, L)
+    votes = [SMod.admits(p[0], p[1], sizes, p[2], L, p[3], SMod.overlap(cfgs[ci])) for ci, p in serving(tables_per_cfg, pattern, cfgs, Bs)]
+    return SMod.decoded_set(votes, sizes, L)
 
 
 def usable(tables_per_cfg, patterns, cfgs, Bs):

@@ -12,7 +12,7 @@ import oracle as O
 from minlz_amd import _lib, shard, synth
 from minlz_amd.api import search_config
 from tests import search_cases as SC
-from tests import search_tables as ST
+from tests import search_model as SMod
 from tests import sidecar_model as SM
 from tests.search_gpu import SENT, data_for, first_difference, gather_into
 
@@ -26,7 +26,7 @@ USER = b'"user":"'
 
 def cfg(T, M=6, prefix=b"", extras=0):
     """(the library's configuration, the model's)"""
-    return search_config(T, M, prefix, extras), SM.config(T, M, prefix, extras)
+    return search_config(T, M, prefix, extras), SMod.config(T, M, prefix, extras)
 
 
 T1 = {M: cfg(1, M) for M in (1, 4, 6, 8)}
@@ -121,12 +121,12 @@ def test_build_over_own_writer_stream(ctx, kind, bs, nblk):
     """(a) The device Writer's stream without tables, its random block stored: that block gets a table exactly when its population allows."""
     d = data_for(kind, bs, nblk, 1234)
     stream = own_stream(ctx, d, bs)
-    grid = ST.data_grid(stream)
+    grid = SMod.data_grid(stream)
     assert grid[1][1] == 0x01 and grid[-1][0] == 1234
     sides = check_builds(ctx, stream, d)
-    B = ST.table_bits(bs)
+    B = SMod.table_bits(bs)
     blk = np.frombuffer(d[bs:2 * bs + 5], np.uint8)          # the stored block and its overlap, type 1 at M = 6
-    pop = len(np.unique(ST.hash_windows(blk, B, 6)))
+    pop = len(np.unique(SMod.hash_windows(blk, B, 6)))
     _, _, tables = SM.parse(sides[2], stream)
     assert (tables[0][1] is not None) == (pop * 100 // (1 << B) <= 70), (pop, B)
     if bs == 4 << 10:
@@ -153,7 +153,7 @@ def uneven_stream():
     d[n - 9 - 4:n - 9 + 4] = USER                             # across the last border: its windows run into zeros
     d = bytes(d)
     stream = SM.framed(d, UNEVEN)
-    assert O.stream_decode(stream, n) == d and [s for s, _ in ST.data_grid(stream)] == UNEVEN
+    assert O.stream_decode(stream, n) == d and [s for s, _ in SMod.data_grid(stream)] == UNEVEN
     return stream, d
 
 
@@ -166,9 +166,9 @@ def test_build_over_a_stream_with_inline_tables_and_index(ctx):
     """(d) Table and index chunks of the main stream are stepped over; the references still name the data chunks' headers."""
     d = data_for("enwik_like", BS, 9, 1234)
     stream = own_stream(ctx, d, BS, add_index=True, search_match_len=6)
-    assert any(t == 0x45 for _, t, _ in ST.chunks_of(stream)) and any(t == 0x40 for _, t, _ in ST.chunks_of(stream))
+    assert any(t == 0x45 for _, t, _ in SMod.chunks_of(stream)) and any(t == 0x40 for _, t, _ in SMod.chunks_of(stream))
     sides = check_builds(ctx, stream, d, [[T1[6]], [T2, T4]])
-    refs = [SM.parse_refs(sides[0][p + 4:p + 4 + n], BS)[0][0] for p, t, n in ST.chunks_of(sides[0]) if t == SM.CHUNK_REF]
+    refs = [SM.parse_refs(sides[0][p + 4:p + 4 + n], BS)[0][0] for p, t, n in SMod.chunks_of(sides[0]) if t == SM.CHUNK_REF]
     assert refs == [p for p, _ in SM.main_chunks(stream)] and all(stream[p] in (1, 2) for p in refs)
 
 
@@ -183,7 +183,7 @@ def test_build_over_two_groups(ctx):
 
 def expect(data, sizes, plan, pattern):
     """What a search that decodes `plan` finds: the occurrences whose chunks are all decoded."""
-    pos = np.asarray(ST.brute(data, pattern), np.int64)
+    pos = np.asarray(SMod.brute(data, pattern), np.int64)
     if not len(pos):
         return []
     got = set(plan)
@@ -215,7 +215,7 @@ def test_search_through_a_sidecar(ctx, which):
     try:
         for p in pats[:2]:
             total, pos, stats = h.search(p)
-            assert stats[1] == stats[0] == len(sizes) and stats[2] == 0 and pos == ST.brute(d, p)   # no sidecar: everything
+            assert stats[1] == stats[0] == len(sizes) and stats[2] == 0 and pos == SMod.brute(d, p)   # no sidecar: everything
         plans = {}
         for name, cfgs in (("one", [T1[6]]), ("other", [T2]), ("both", [T1[6], T2])):
             model = [c[1] for c in cfgs]
@@ -229,10 +229,10 @@ def test_search_through_a_sidecar(ctx, which):
                     plan = SM.plan(tables, sizes, p, mcfgs, Bs)
                     assert stats == (len(sizes), len(plan), SM.usable(tables, [p], mcfgs, Bs)), (which, name, p)
                     assert pos == expect(d, sizes, plan, p) and total == len(pos), (which, name, p)
-                    assert pos == ST.brute(d, p), (which, name, p)
+                    assert pos == SMod.brute(d, p), (which, name, p)
                     plans[name, p] = set(plan)
             if planted is not None and name == "one":
-                assert len(plans[name, planted]) <= 12 and h.search(planted)[1] == ST.brute(d, planted)
+                assert len(plans[name, planted]) <= 12 and h.search(planted)[1] == SMod.brute(d, planted)
         for p in pats:
             assert plans["both", p] <= plans["one", p] and plans["both", p] <= plans["other", p]
         # many patterns in one call are the loop of single searches
@@ -247,7 +247,7 @@ def test_search_through_a_sidecar(ctx, which):
                 assert pairs == sorted((q, i) for i, s in enumerate(singles) for q in s[1])
         h.rd.detach_sidecar()
         total, pos, stats = h.search(pats[0])
-        assert stats[1] == len(sizes) and stats[2] == 0 and pos == ST.brute(d, pats[0])
+        assert stats[1] == len(sizes) and stats[2] == 0 and pos == SMod.brute(d, pats[0])
     finally:
         h.close()
 
@@ -261,7 +261,7 @@ def test_device_stream_front_end(ctx):
         assert side.cpu().numpy().tobytes() == SM.build(O.stream_encode(d, 1, BS), d, [T1[6][1], T4[1]])
         codec_stream.attach_sidecar(side)
         pos, total = codec_stream.search(nd, 100)
-        assert pos.cpu().tolist() == ST.brute(d, nd) and ctx.search_plan()[0] < 16
+        assert pos.cpu().tolist() == SMod.brute(d, nd) and ctx.search_plan()[0] < 16
         codec_stream.attach_sidecar(None)
         codec_stream.search(nd, 100)
         assert ctx.search_plan() == (16, 0)
@@ -283,7 +283,7 @@ def lying():
 def test_broken_tables_are_passed_over(ctx, lying):
     d, stream, model, side = lying
     sizes = [n for _, n in SM.main_chunks(stream)]
-    tabs = [(p, n) for p, t, n in ST.chunks_of(side) if t == ST.CHUNK_TABLE]
+    tabs = [(p, n) for p, t, n in SMod.chunks_of(side) if t == SMod.CHUNK_TABLE]
     p0 = tabs[4][0]
     flipped = side[:p0 + 40] + bytes([side[p0 + 40] ^ 0x10]) + side[p0 + 41:]
     as46 = side[:p0] + b"\x46" + side[p0 + 1:]
@@ -299,7 +299,7 @@ def test_broken_tables_are_passed_over(ctx, lying):
                 assert stats == (len(sizes), len(plan), SM.usable(tables, [p], mcfgs, Bs))
                 assert pos == expect(d, sizes, plan, p)
                 if not kw:
-                    assert pos == ST.brute(d, p)
+                    assert pos == SMod.brute(d, p)
         good = SM.parse(side, stream)[2]
         for src in (flipped, as46):
             t = SM.parse(src, stream)[2]
@@ -314,11 +314,11 @@ def test_refused_sidecars_leave_the_handle_alone(ctx, lying):
     d, stream, model, side = lying
     sizes = [n for _, n in SM.main_chunks(stream)]
     dcs = SM.main_chunks(stream)
-    refs = [(p, n) for p, t, n in ST.chunks_of(side) if t == SM.CHUNK_REF]
+    refs = [(p, n) for p, t, n in SMod.chunks_of(side) if t == SM.CHUNK_REF]
 
     def with_ref(i, payload):
         p, n = refs[i]
-        return side[:p] + ST.frame(SM.CHUNK_REF, payload) + side[p + 4 + n:]
+        return side[:p] + SMod.frame(SM.CHUNK_REF, payload) + side[p + 4 + n:]
 
     u = SM.uvarint
     p3, n3 = refs[3]
@@ -346,7 +346,7 @@ def test_refused_sidecars_leave_the_handle_alone(ctx, lying):
             if first is not None:
                 h.attach(first)
             before = h.search(pat)
-            assert before[1] == ST.brute(d, pat) and (before[2][1] < len(sizes)) == (first is not None)
+            assert before[1] == SMod.brute(d, pat) and (before[2][1] < len(sizes)) == (first is not None)
             for name, (b, err) in bad.items():
                 with pytest.raises(err):
                     h.attach(b)
@@ -412,7 +412,7 @@ def test_build_arguments(ctx):
     h = Handle(ctx, empty)
     try:
         got = h.build([T1[6], T2])
-        assert got == empty[:10] + SM.info_chunk(T1[6][1], 16) + SM.info_chunk(T2[1], 16) + SM.EOF_CHUNK == SM.build(empty, b"", [T1[6][1], T2[1]])
+        assert got == empty[:10] + SMod.info_chunk(T1[6][1], 16) + SMod.info_chunk(T2[1], 16) + SM.EOF_CHUNK == SM.build(empty, b"", [T1[6][1], T2[1]])
         h.attach(got)
         assert h.search(b"abc")[0] == 0
     finally:

@@ -1,5 +1,5 @@
 """Block search tables written by the device-resident Writer (MLZ_STREAM_SEARCH_TABLES on mlz_stream_encode_gather_device) and the pattern
-search over streams in HBM (mlz_dev_reader_search, DeviceReader.search, DeviceStream.search), against tests/search_tables.py: the
+search over streams in HBM (mlz_dev_reader_search, DeviceReader.search, DeviceStream.search), against tests/search_model.py: the
 specification in plain Python.  The Writer's stream must be the flag-off stream of the same call with the model's chunks spliced in; a
 search must return what a brute-force search of the decoded bytes returns and decode exactly the chunks the model's plan rule names."""
 import ctypes as C
@@ -13,10 +13,12 @@ import minlz_amd as mz
 import oracle as O
 from minlz_amd import _lib, shard, stream as S, synth
 from tests import search_cases as SC
-from tests import search_tables as ST
+from tests import search_model as SMod
 from tests.search_gpu import SENT, data_for, gather_into
 
 pytestmark = pytest.mark.gpu
+
+TYPES = (1,)            # these tests read a stream's tables as a searcher that knows type 1 alone
 
 MLZ_ERR_ARG = 8
 
@@ -55,15 +57,15 @@ def writer_case(ctx, kind, bs, nblk, M, add_index, parts=1, mctx=None):
     c = mctx or ctx
     off = gather(c, ranges, 1, bs, add_index, None)
     on = gather(c, ranges, 1, bs, add_index, M)
-    B = ST.table_bits(bs)
-    want, tables = ST.splice(off, d, M, B, index=add_index)
+    B = SMod.table_bits(bs)
+    want, tables = SMod.splice(off, d, SMod.config(1, M), B, index=add_index)
     what = "%s bs=%d M=%d index=%s parts=%d" % (kind, bs, M, add_index, parts)
     assert len(on) == len(want), what
     assert on == want, what + ": first difference at %d" % next(i for i in range(len(on)) if on[i] != want[i])
-    grid = ST.data_grid(on)
+    grid = SMod.data_grid(on)
     assert grid[1][1] == 0x01 and tables[1] is None and grid[-1][0] == 1234, what   # the incompressible block: stored, no table; a short last block
     assert sum(t is not None for t in tables) >= (len(tables) // 2 if M >= 4 else 0), what
-    assert ST.read_tables(on)[2] == tables
+    assert SMod.read_tables(on, types=TYPES)[2] == tables
     check_stream(ctx, on, d, bs, M, add_index, what)
     return on, d, tables
 
@@ -98,7 +100,7 @@ def test_writer_several_ranges_on_two_contexts(ctx):
         d = data_for("text_like", bs, 4, 3)
         off = gather(m, [d[:2 * bs], b"", d[2 * bs:4 * bs], d[4 * bs:]], 1, bs, False, None)
         on = gather(m, [d[:2 * bs], b"", d[2 * bs:4 * bs], d[4 * bs:]], 1, bs, False, 6)
-        assert on == ST.splice(off, d, 6, 16)[0]
+        assert on == SMod.splice(off, d, SMod.config(1, 6), 16)[0]
     finally:
         m.close()
 
@@ -118,7 +120,7 @@ def test_writer_arguments(ctx):
         assert int(str(e.value).split()[2]) == MLZ_ERR_ARG
     for bs in (4 << 10, 64 << 10, 8 << 20):
         n = 3 * bs + 5
-        B = ST.table_bits(bs)
+        B = SMod.table_bits(bs)
         assert L.mlz_stream_bound(n, bs, 4) == L.mlz_stream_bound(n, bs, 0) + 7 + 4 * (12 + max(32, 1 << (B - 3)))
     assert gather(ctx, [b""], 1, 4096, False, 6) == gather(ctx, [b""], 1, 4096, False, None)   # an empty stream: no header, no info chunk
 
@@ -147,16 +149,16 @@ class Searcher:
 
 
 def check_search(sr, stream, d, pattern, what, cap=None, ignore_crc=False):
-    want = ST.brute(d, pattern)
-    M, B, tables = ST.read_tables(stream, ignore_crc)
-    sizes = [n for n, _ in ST.data_grid(stream)]
-    plan = ST.plan(tables, sizes, pattern, M, B, use_tables=any(t is not None for t in tables))
+    want = SMod.brute(d, pattern)
+    cfg, B, tables = SMod.read_tables(stream, ignore_crc, TYPES)
+    sizes = [n for n, _ in SMod.data_grid(stream)]
+    plan = SMod.plan(tables, sizes, pattern, cfg, B, use_tables=any(t is not None for t in tables))
     cap = len(want) + 3 if cap is None else cap
     total, pos, stats = sr(pattern, cap, ignore_crc=ignore_crc)
     assert total == len(want) and pos == want[:cap], what
-    usable = sum(t is not None for t in tables) if M is not None and len(pattern) >= M else 0
+    usable = sum(t is not None for t in tables) if cfg is not None and len(pattern) >= cfg[1] else 0
     assert stats == (len(sizes), len(plan), usable), what
-    assert ST.chunks_touched(sizes, want, len(pattern)) <= set(plan), what
+    assert SMod.chunks_touched(sizes, want, len(pattern)) <= set(plan), what
     total, pos, all_stats = sr(pattern, cap, ignore_crc=ignore_crc, no_tables=True)
     assert total == len(want) and pos == want[:cap] and all_stats == (len(sizes), sum(1 for n in sizes if n), 0), what + " (no tables)"
     return stats   # (of the search with tables)
@@ -193,7 +195,7 @@ def test_search_over_the_writers_streams(ctx, M):
         for name, p in pattern_set(d, nd, big, M, bs):
             check_search(sr, stream, d, p, "M=%d %s" % (M, name))
         # cap below the total, cap = 0 with NULL
-        want = ST.brute(d, b"aaaa")
+        want = SMod.brute(d, b"aaaa")
         assert len(want) >= 47
         for cap in (1, 5, len(want) - 1, len(want)):
             check_search(sr, stream, d, b"aaaa", "cap %d" % cap, cap=cap)
@@ -202,7 +204,7 @@ def test_search_over_the_writers_streams(ctx, M):
         # the tensor front end
         with shard.HipTensorCodec(ctx).open_stream(sr.t) as ds:
             t, total = ds.search(nd, 2)
-            assert total == 3 and t.dtype == torch.int64 and t.is_cuda and t.cpu().tolist() == ST.brute(d, nd)[:2]
+            assert total == 3 and t.dtype == torch.int64 and t.is_cuda and t.cpu().tolist() == SMod.brute(d, nd)[:2]
     finally:
         sr.close()
 
@@ -221,10 +223,11 @@ def test_search_streams_without_tables_and_foreign_streams(ctx):
     for level, obs in ((1, bs), (2, 1 << 20)):
         o = O.stream_encode(d, level, obs)
         cases.append(("oracle L%d" % level, o))
-        cases.append(("oracle L%d spliced" % level, ST.splice(o, d, 6, ST.table_bits(obs))[0]))
-    cases.append(("python writer spliced, stored chunks too", ST.splice(w.getvalue(), d, 6, 16, stored_too=True)[0]))
+        cases.append(("oracle L%d spliced" % level, SMod.splice(o, d, SMod.config(1, 6), SMod.table_bits(obs))[0]))
+    # (the block in front of the 2-byte block gets a table that saw those 2 bytes and zeros: a writer that looks at the next chunk alone)
+    cases.append(("python writer spliced, stored chunks too", SMod.splice(w.getvalue(), d, SMod.config(1, 6), 16, stored_too=True, next_chunk_only=True)[0]))
     r = synth.random_bytes(3 * bs, seed=2).tobytes() + d[:2 * bs]
-    cases.append(("stored chunks spliced", ST.splice(O.stream_encode(r, 1, bs), r, 6, 16, stored_too=True)[0]))
+    cases.append(("stored chunks spliced", SMod.splice(O.stream_encode(r, 1, bs), r, SMod.config(1, 6), 16, stored_too=True)[0]))
     for name, stream in cases:
         data = r if name.startswith("stored") else d
         assert O.stream_decode(stream, len(data)) == data, name
@@ -272,7 +275,7 @@ def test_designated_input_decodes_a_handful(ctx, kind):
             st = check_search(sr, stream, d, nd, "%s seed %d" % (kind, seed))
             print(kind, seed, "decoded", st[1], "of", st[0], "tables", st[2])
             assert st[0] == nblk and st[1] <= 12
-            assert sorted(set(ST.brute(d, nd)) & set(at)) == sorted(at)
+            assert sorted(set(SMod.brute(d, nd)) & set(at)) == sorted(at)
         finally:
             sr.close()
 
@@ -281,13 +284,13 @@ def test_broken_table_and_broken_chunks(ctx):
     bs, nblk = 64 << 10, 16
     d, nd, at = SC.planted("text_like", bs, nblk, 16, 2)
     stream = gather(ctx, [d], 1, bs, False, 6)
-    M, B, tables = ST.read_tables(stream)
-    sizes = [n for n, _ in ST.data_grid(stream)]
-    plan = ST.plan(tables, sizes, nd, M, B)
+    cfg, B, tables = SMod.read_tables(stream, types=TYPES)
+    sizes = [n for n, _ in SMod.data_grid(stream)]
+    plan = SMod.plan(tables, sizes, nd, cfg, B)
     assert len(plan) < nblk - 2
     skipped = next(k for k in range(nblk) if k not in plan)
-    tabs = [c for c in ST.chunks_of(stream) if c[1] == ST.CHUNK_TABLE]
-    datas = [c for c in ST.chunks_of(stream) if c[1] in (1, 2, 3)]
+    tabs = [c for c in SMod.chunks_of(stream) if c[1] == SMod.CHUNK_TABLE]
+    datas = [c for c in SMod.chunks_of(stream) if c[1] in (1, 2, 3)]
     assert len(tabs) == nblk
     # a table with one more bit set and its old CRC: table-less with the CRC check, used without it
     b = bytearray(stream)
@@ -314,11 +317,11 @@ def test_broken_table_and_broken_chunks(ctx):
             if want_err:
                 with pytest.raises(mz.ErrCRC):
                     sr(nd, 10)
-                assert sr(nd, 10, ignore_crc=True)[:2] == (3, ST.brute(d, nd))
+                assert sr(nd, 10, ignore_crc=True)[:2] == (3, SMod.brute(d, nd))
                 with pytest.raises(mz.ErrCRC):
                     sr(nd, 10, no_tables=True)
             else:
-                assert sr(nd, 10)[:2] == (3, ST.brute(d, nd))
+                assert sr(nd, 10)[:2] == (3, SMod.brute(d, nd))
                 with pytest.raises(mz.ErrCRC):
                     sr(nd, 10, no_tables=True)
         finally:

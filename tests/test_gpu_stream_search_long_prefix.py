@@ -1,6 +1,6 @@
 """Search tables with a long prefix and extra matches (table type 4) written by the device-resident Writer
 (mlz_stream_encode_gather_device_long_prefix, HipCtx.stream_encode_gather_device(search_long_prefix=...)) and used by the pattern search
-(mlz_dev_reader_search), against tests/search_long_prefix_tables.py: the specification in plain Python.  The Writer's stream must be the
+(mlz_dev_reader_search), against tests/search_model.py: the specification in plain Python.  The Writer's stream must be the
 table-less stream of the same call with the model's chunks spliced in; a search must return what a brute-force search of the decoded bytes
 returns and decode exactly the chunks the model's plan names."""
 import ctypes as C
@@ -15,7 +15,7 @@ from minlz_amd import _lib, synth
 from minlz_amd.api import search_long_prefix_config
 from tests import search_cases as SC
 from tests import search_long_prefix_cases as LC
-from tests import search_long_prefix_tables as SL
+from tests import search_model as SMod
 from tests import search_prefix_cases as PC
 from tests.search_gpu import SENT, Searcher, data_for, first_difference, gather_into, on_device
 
@@ -46,11 +46,11 @@ def writer_case(ctx, d, bs, M, E, pfx, add_index=False, cuts=None, what=""):
     ranges = [d[cuts[i]:cuts[i + 1]] for i in range(len(cuts) - 1)]
     off = gather(ctx, ranges, bs, add_index)
     on = gather(ctx, ranges, bs, add_index, M, pfx, E)
-    field, B = SL.field_of(pfx, E), SL.table_bits(bs)
-    want, tables = SL.splice(off, d, M, B, field, index=add_index)
+    field, B = SMod.config(4, M, pfx, E)[2], SMod.table_bits(bs)
+    want, tables = SMod.splice(off, d, (4, M, field), B, index=add_index)
     what = "%s bs=%d K=%d M=%d E=%d index=%s ranges=%d" % (what, bs, len(pfx), M, E, add_index, len(ranges))
     assert len(on) == len(want) and on == want, what + ": lengths %d / %d, first difference at %d" % (len(on), len(want), first_difference(on, want))
-    assert SL.read_tables(on) == (4, M, B, field, tables), what
+    assert SMod.read_tables(on) == ((4, M, field), B, tables), what
     assert mz.stream_decode(on, ctx=ctx) == d and O.stream_decode(on, len(d)) == d, what
     return on, tables
 
@@ -69,7 +69,7 @@ def test_writer_stream_is_the_models(ctx, kind, bs, nblk):
     for pfx, M, E in configs:
         for add_index in ((False, True) if bs == 64 << 10 else (bs == 2 << 20,)):
             on, tables = writer_case(ctx, d, bs, M, E, pfx, add_index, what=kind)
-            grid = SL.data_grid(on)
+            grid = SMod.data_grid(on)
             assert grid[1][1] == 0x01 and tables[1] is None and grid[-1][0] == 1234       # the incompressible block: stored, no table; a ragged tail
             assert sum(t is not None for t in tables) == len(tables) - 1
             assert any(popcount(t[0]) for t in tables if t is not None)
@@ -112,7 +112,7 @@ def indexed_by_rule(sizes, g, K, M, E):
 
 def single_plant(ctx, bs, sizes, g, pfx, M, E):
     """One plant: exactly the model's bits, E + 1 at the most, in exactly the table of the block where the prefix starts."""
-    K, B = len(pfx), SL.table_bits(bs)
+    K, B = len(pfx), SMod.table_bits(bs)
     zero = (bytes(32), B - 8)
     d = hand_built(sizes, [g], pfx)
     on, tables = writer_case(ctx, d, bs, M, E, pfx, what="plant at %d" % g)
@@ -120,7 +120,7 @@ def single_plant(ctx, bs, sizes, g, pfx, M, E):
     assert all(t in (zero, None) for i, t in enumerate(tables) if i != k), g
     starts = np.concatenate([[0], np.cumsum(sizes)])
     follow = d[starts[k + 1]:starts[k + 1] + K - 1 + M + E] if k + 1 < len(sizes) else None
-    hashes = set(SL.indexed_hashes(d[starts[k]:starts[k + 1]], follow, B, M, SL.field_of(pfx, E)).tolist())
+    hashes = set(SMod.indexed_hashes(SMod.config(4, M, pfx, E), d[starts[k]:starts[k + 1]], follow, B).tolist())
     assert bool(hashes) == indexed, (g, "the model and the rule, written out, disagree")
     if not indexed:
         assert tables[k] in (zero, None), g
@@ -165,11 +165,11 @@ def test_hand_built_parts_and_slices(ctx):
         dense = {m + o for m in steps for o in (-2, -1, 0) if m + o < bs} | {bs + m - 1 for m in steps} | {0, bs - 1, nblk * bs - 1, nblk * bs + 4999 - 10}
         d = hand_built(sizes, sorted(dense), b"<")
         on, tables = writer_case(ctx, d, bs, 6, 3, b"<", what="parts, K = 1")
-        assert all(t is not None for t in tables) and tables[0][1] < SL.table_bits(bs) - 8
+        assert all(t is not None for t in tables) and tables[0][1] < SMod.table_bits(bs) - 8
         across = {m - 4 for m in steps} | {bs + m - 8 for m in steps if m < bs} | {bs - 9, nblk * bs - 1}
         d = hand_built(sizes, sorted(across), prefix_of(9))
         on, tables = writer_case(ctx, d, bs, 8, 8, prefix_of(9), what="parts, K = 9")
-        assert all(t is not None for t in tables) and tables[0][1] < SL.table_bits(bs) - 8
+        assert all(t is not None for t in tables) and tables[0][1] < SMod.table_bits(bs) - 8
     single_plant(ctx, 1 << 20, [1 << 20, 1 << 20, 5000], (1 << 20) - 4, prefix_of(9), 6, 3)
     single_plant(ctx, 2 << 20, [2 << 20, 2 << 20, 5000], (1 << 20) + (64 << 10) - 3, prefix_of(9), 6, 3)
 
@@ -284,13 +284,13 @@ def test_writer_arguments(ctx):
 # ---- search ----
 
 def check_search(sr, stream, d, pattern, what, cap=None, ignore_crc=False):
-    want = SL.brute(d, pattern)
-    plan, sizes, usable = LC.model_plan(stream, pattern, ignore_crc)
+    want = SMod.brute(d, pattern)
+    plan, sizes, usable = SMod.plan_of_stream(stream, pattern, ignore_crc)
     cap = len(want) + 3 if cap is None else cap
     total, pos, stats = sr(pattern, cap, ignore_crc=ignore_crc)
     assert total == len(want) and pos == want[:cap], what
     assert stats == (len(sizes), len(plan), usable), (what, stats, plan)
-    assert SL.chunks_touched(sizes, want, len(pattern)) <= set(plan), what
+    assert SMod.chunks_touched(sizes, want, len(pattern)) <= set(plan), what
     total, pos, all_stats = sr(pattern, cap, ignore_crc=ignore_crc, no_tables=True)
     assert total == len(want) and pos == want[:cap] and all_stats == (len(sizes), sum(1 for n in sizes if n), 0), what + " (no tables)"
     return stats
@@ -301,7 +301,7 @@ def test_search_over_the_writers_streams(ctx, pfx, M, E):
     bs, nblk = 64 << 10, 8
     d, pats = LC.designed("json_like", bs, nblk, 777, M, E, pfx)
     stream = gather(ctx, [d], bs, True, M, pfx, E)
-    assert SL.read_tables(stream)[:4] == (4, M, 16, SL.field_of(pfx, E))
+    assert SMod.read_tables(stream)[:2] == (SMod.config(4, M, pfx, E), 16)
     sr = Searcher(ctx, stream)
     try:
         res = {name: check_search(sr, stream, d, p, "K=%d M=%d E=%d %s" % (len(pfx), M, E, name)) for name, p in pats + SC.patterns(d, M, bs)}
@@ -315,7 +315,7 @@ def test_search_over_the_writers_streams(ctx, pfx, M, E):
             assert res["absent_keyed"][1] <= 2
         # small caps
         frequent = b'","user":"user_'
-        want = SL.brute(d, frequent)
+        want = SMod.brute(d, frequent)
         assert len(want) > 100
         for cap in (0, 1, 7, len(want) - 1):
             check_search(sr, stream, d, frequent, "cap %d" % cap, cap=cap)
@@ -326,16 +326,16 @@ def test_search_over_the_writers_streams(ctx, pfx, M, E):
 def test_search_foreign_streams(ctx):
     """Model-spliced streams of other writers: oracle level 1 and 2 blocks, a chunk without a table in the middle, stored chunks with tables."""
     bs, M, E = 64 << 10, 6, 3
-    field = SL.field_of(LC.USER, E)
+    field = SMod.config(4, M, LC.USER, E)[2]
     d, pats = LC.designed("json_like", bs, 8, 777, M, E, LC.USER)
     r = bytearray(synth.random_bytes(3 * bs, seed=2).tobytes() + d[:2 * bs])
     r[bs + 100:bs + 100 + len(pats[0][1])] = pats[0][1]                      # an occurrence inside a stored chunk
     r = bytes(r)
     cases = []
     for level, obs in ((1, bs), (2, 1 << 20)):
-        cases.append(("oracle L%d" % level, SL.splice(O.stream_encode(d, level, obs), d, M, SL.table_bits(obs), field)[0], d))
-    cases.append(("a table-less chunk in the middle", SL.splice(O.stream_encode(d, 1, bs), d, M, 16, field, skip=(4,))[0], d))
-    cases.append(("stored chunks", SL.splice(O.stream_encode(r, 1, bs), r, M, 16, field, stored_too=True)[0], r))
+        cases.append(("oracle L%d" % level, SMod.splice(O.stream_encode(d, level, obs), d, (4, M, field), SMod.table_bits(obs))[0], d))
+    cases.append(("a table-less chunk in the middle", SMod.splice(O.stream_encode(d, 1, bs), d, (4, M, field), 16, skip=(4,))[0], d))
+    cases.append(("stored chunks", SMod.splice(O.stream_encode(r, 1, bs), r, (4, M, field), 16, stored_too=True)[0], r))
     for name, stream, data in cases:
         assert O.stream_decode(stream, len(data)) == data, name
         sr = Searcher(ctx, stream)
@@ -356,14 +356,14 @@ def test_search_table_verdicts(ctx):
     K = len(LC.USER)
     d, pats = LC.designed("json_like", bs, nblk, 777, M, E, LC.USER)
     stream = gather(ctx, [d], bs, False, M, LC.USER, E)
-    T, _, B, field, tables = SL.read_tables(stream)
+    (T, _, field), B, tables = SMod.read_tables(stream)
     p = dict(pats)["p0"]
-    plan = LC.model_plan(stream, p)[0]
+    plan = SMod.plan_of_stream(stream, p)[0]
     skipped = next(k for k in range(1, nblk) if k not in plan)
-    off = [c for c in SL.chunks_of(stream) if c[1] == SL.CHUNK_TABLE][skipped][0]
+    off = [c for c in SMod.chunks_of(stream) if c[1] == SMod.CHUNK_TABLE][skipped][0]
     t2 = list(tables); t2[skipped] = None
     for name, b in (("extras", stream[:off + 8] + bytes([E - 1]) + stream[off + 9:]), ("prefix byte", stream[:off + 9 + K - 1] + b"'" + stream[off + 9 + K:])):
-        assert SL.read_tables(b)[4] == t2
+        assert SMod.read_tables(b)[2] == t2
         sr = Searcher(ctx, b)
         try:
             for ignore in (False, True):
@@ -374,9 +374,9 @@ def test_search_table_verdicts(ctx):
         finally:
             sr.close()
     ilen = 4 + 3 + 2 + K
-    for name, b in (("M + E = 17", stream[:10] + SL.info_chunk(M, B, bytes([K - 1, 9]) + LC.USER) + stream[10 + ilen:]),
-                    ("short field", stream[:10] + SL.frame(SL.CHUNK_INFO, bytes([4, M, B]) + field[:5]) + stream[10 + ilen:])):
-        assert SL.read_tables(b)[0] is None
+    for name, b in (("M + E = 17", stream[:10] + SMod.info_chunk((4, M, bytes([K - 1, 9]) + LC.USER), B) + stream[10 + ilen:]),
+                    ("short field", stream[:10] + SMod.frame(SMod.CHUNK_INFO, bytes([4, M, B]) + field[:5]) + stream[10 + ilen:])):
+        assert SMod.read_tables(b)[0] is None
         sr = Searcher(ctx, b)
         try:
             assert check_search(sr, b, d, p, name)[1:] == (nblk + 1, 0)
@@ -397,7 +397,7 @@ def test_designated_input_decodes_a_handful(ctx, kind):
             st = check_search(sr, stream, d, nd, "%s seed %d" % (kind, seed))
             print(kind, seed, "decoded", st[1], "of", st[0], "tables", st[2], "stream", len(stream))
             assert st[0] == nblk and st[1] <= 12
-            assert sorted(set(SL.brute(d, nd)) & set(at)) == sorted(at)
+            assert sorted(set(SMod.brute(d, nd)) & set(at)) == sorted(at)
         finally:
             sr.close()
 

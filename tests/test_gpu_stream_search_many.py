@@ -11,10 +11,8 @@ import oracle as O
 from minlz_amd import _lib, shard, synth
 from tests import search_cases as SC
 from tests import search_long_prefix_cases as LC
-from tests import search_long_prefix_tables as SL
+from tests import search_model as SMod
 from tests import search_prefix_cases as PC
-from tests import search_prefix_tables as SP
-from tests import search_tables as ST
 from tests.search_gpu import SENT, gather_into
 
 pytestmark = pytest.mark.gpu
@@ -28,7 +26,7 @@ def gather(ctx, d, bs, **kw):
     """The Writer's stream over `d` with the tables `kw` asks for (none: a stream without tables); room for the largest table per block."""
     L = _lib.lib()
     nblk = (len(d) + bs - 1) // bs
-    cap = L.mlz_stream_bound(len(d), bs, 1) + (nblk + 2) * (12 + 260 + (1 << (ST.table_bits(bs) - 3))) + 1024
+    cap = L.mlz_stream_bound(len(d), bs, 1) + (nblk + 2) * (12 + 260 + (1 << (SMod.table_bits(bs) - 3))) + 1024
     return gather_into(ctx, [d], cap, 1, bs, True, **kw)
 
 
@@ -60,7 +58,7 @@ class ManySearcher:
 
 
 def brute_pairs(d, pats):
-    per = [ST.brute(d, p) for p in pats]
+    per = [SMod.brute(d, p) for p in pats]
     return sorted((q, i) for i, qs in enumerate(per) for q in qs), [len(qs) for qs in per]
 
 
@@ -105,19 +103,11 @@ def served_needles(d, bs):
 
 def model_plans(name, stream, pats):
     """-> (the models' plans, (windows or groups, t_min) per pattern) over the Writer's stream."""
-    if name == "type 1":
-        M, B, tables = ST.read_tables(stream)
-        sizes = [n for n, _ in ST.data_grid(stream)]
-        return [ST.plan(tables, sizes, p, M, B) for p in pats], [(len(p) - M + 1, 1) for p in pats]
-    if name in ("type 2", "type 3"):
-        T, M, B, field, tables = SP.read_tables(stream)
-        sizes = [n for n, _ in SP.data_grid(stream)]
-        assert T == int(name[-1])
-        return [SP.plan(tables, sizes, p, T, M, B, field) for p in pats], [(len(SP.windows(p, T, M, field)[0]), SP.windows(p, T, M, field)[1]) for p in pats]
-    T, M, B, field, tables = SL.read_tables(stream)
-    sizes = [n for n, _ in SL.data_grid(stream)]
-    assert T == 4
-    return [SL.plan(tables, sizes, p, T, M, B, field) for p in pats], [(len(SL.groups(p, M, field)[0]), SL.groups(p, M, field)[1]) for p in pats]
+    cfg, B, tables = SMod.read_tables(stream)
+    sizes = [n for n, _ in SMod.data_grid(stream)]
+    assert cfg[0] == int(name[-1])
+    starts = SMod.groups if cfg[0] == 4 else SMod.windows
+    return [SMod.plan(tables, sizes, p, cfg, B) for p in pats], [(len(starts(p, cfg)[0]), starts(p, cfg)[1]) for p in pats]
 
 
 @pytest.mark.parametrize("name", list(CONFIGS))
@@ -205,12 +195,12 @@ def test_plan_is_the_union_of_the_models_plans(ctx, kind):
     bs, nblk, M = 64 << 10, 128, 6
     d, nd, at = SC.planted(kind, bs, nblk, 16, 1)
     stream = gather(ctx, d, bs, search_match_len=M)
-    gM, B, tables = ST.read_tables(stream)
-    sizes = [n for n, _ in ST.data_grid(stream)]
-    assert gM == M and len(sizes) == nblk
+    cfg, B, tables = SMod.read_tables(stream, types=(1,))
+    sizes = [n for n, _ in SMod.data_grid(stream)]
+    assert cfg == (1, M, b"") and len(sizes) == nblk
     absent = [bytes(SC.needle(16, 200 + s)) for s in range(8)]
-    planted_plan = ST.plan(tables, sizes, nd, M, B)
-    absent_plans = [ST.plan(tables, sizes, p, M, B) for p in absent]
+    planted_plan = SMod.plan(tables, sizes, nd, cfg, B)
+    absent_plans = [SMod.plan(tables, sizes, p, cfg, B) for p in absent]
     union = set(planted_plan).union(*[set(a) for a in absent_plans])
     assert len(planted_plan) <= 12 and len(union) <= 12 + sum(len(a) for a in absent_plans)
     sr = ManySearcher(ctx, stream)
@@ -218,7 +208,7 @@ def test_plan_is_the_union_of_the_models_plans(ctx, kind):
         stats = check_many(sr, d, [nd] + absent, kind)
         print(kind, "decoded", stats[1], "of", stats[0], "planted alone", len(planted_plan), "absent add", [len(a) for a in absent_plans])
         assert stats == (nblk, len(union), sum(t is not None for t in tables), 0)
-        assert sorted(set(ST.brute(d, nd)) & set(at)) == sorted(at)
+        assert sorted(set(SMod.brute(d, nd)) & set(at)) == sorted(at)
         stats = check_many(sr, d, [nd] + absent + [nd[:M - 1]], kind + " + one unserved", cap=50)
         assert stats == (nblk, sum(1 for n in sizes if n), sum(t is not None for t in tables), 1)
         stats = check_many(sr, d, [nd[:3], nd[:5], nd], kind + " two unserved", cap=50)
@@ -302,9 +292,9 @@ def test_group_border(ctx):
             L = len(needles[i])
             assert {(border - L, i), (border - L // 2, i), (border - 1, i), (border, i)} <= set(pairs)
         stats = check_many(sr, d, needles, "group border", no_tables=True)
-        assert stats[1] == len([n for n, _ in ST.data_grid(stream) if n]) == 67
+        assert stats[1] == len([n for n, _ in SMod.data_grid(stream) if n]) == 67
         freq = b'":['                                                          # once per record
-        assert len(ST.brute(d[:1 << 20], freq)) > 1000
+        assert len(SMod.brute(d[:1 << 20], freq)) > 1000
         check_many(sr, d, needles + [freq], "group border, frequent", cap=1000, no_tables=True)
     finally:
         sr.close()

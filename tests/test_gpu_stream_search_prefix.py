@@ -1,6 +1,6 @@
 """Search tables with byte prefixes (table types 2 and 3) written by the device-resident Writer (mlz_stream_encode_gather_device_tables,
 HipCtx.stream_encode_gather_device(search_prefix=...)) and used by the pattern search (mlz_dev_reader_search), against
-tests/search_prefix_tables.py: the specification in plain Python.  The Writer's stream must be the table-less stream of the same call with
+tests/search_model.py: the specification in plain Python.  The Writer's stream must be the table-less stream of the same call with
 the model's chunks spliced in; a search must return what a brute-force search of the decoded bytes returns and decode exactly the chunks
 the model's plan names."""
 import ctypes as C
@@ -14,11 +14,13 @@ import oracle as O
 from minlz_amd import _lib, synth
 from minlz_amd.api import search_tables_config
 from tests import search_cases as SC
+from tests import search_model as SMod
 from tests import search_prefix_cases as PC
-from tests import search_prefix_tables as SP
 from tests.search_gpu import SENT, Searcher, data_for, first_difference, gather_into, on_device
 
 pytestmark = pytest.mark.gpu
+
+TYPES = (1, 2, 3)       # these tests read a stream's tables as a searcher that knows the types 1 to 3
 
 MLZ_ERR_ARG = 8
 FILL = ord("a")          # in neither prefix set
@@ -44,12 +46,12 @@ def writer_case(ctx, d, bs, M, pset, add_index, cuts=None, what=""):
     ranges = [d[cuts[i]:cuts[i + 1]] for i in range(len(cuts) - 1)]
     off = gather(ctx, ranges, bs, add_index)
     on = gather(ctx, ranges, bs, add_index, M, pset)
-    T, field = SP.field_of(pset)
-    B = SP.table_bits(bs)
-    want, tables = SP.splice(off, d, T, M, B, field, index=add_index)
+    T, field = SMod.field_of(pset)
+    B = SMod.table_bits(bs)
+    want, tables = SMod.splice(off, d, (T, M, field), B, index=add_index)
     what = "%s bs=%d M=%d T=%d index=%s ranges=%d" % (what, bs, M, T, add_index, len(ranges))
     assert len(on) == len(want) and on == want, what + ": lengths %d / %d, first difference at %d" % (len(on), len(want), first_difference(on, want))
-    assert SP.read_tables(on) == (T, M, B, field, tables), what
+    assert SMod.read_tables(on, types=TYPES) == ((T, M, field), B, tables), what
     assert mz.stream_decode(on, ctx=ctx) == d and O.stream_decode(on, len(d)) == d, what
     return on, tables
 
@@ -62,7 +64,7 @@ def writer_case(ctx, d, bs, M, pset, add_index, cuts=None, what=""):
 def test_writer_stream_is_the_models(ctx, kind, bs, nblk, set_name):
     d = data_for(kind, bs, nblk, 1234)
     on, tables = writer_case(ctx, d, bs, 6, PC.SETS[set_name], add_index=(bs in (64 << 10, 8 << 20)), what=kind)
-    grid = SP.data_grid(on)
+    grid = SMod.data_grid(on)
     assert grid[1][1] == 0x01 and tables[1] is None and grid[-1][0] == 1234       # the incompressible block: stored, no table; a ragged tail
     assert sum(t is not None for t in tables) == len(tables) - 1
 
@@ -150,10 +152,10 @@ def hand_case(ctx, bs, sizes, plants, M, pset=b":"):
     assert all(s == bs for s in sizes[:-1]) and len(set(plants)) == len(plants)
     d = hand_built(sizes, plants)
     on, tables = writer_case(ctx, d, bs, M, pset, False, what="hand-built")
-    T, field = SP.field_of(pset)
-    mask, B = SP.mask_of(T, field), SP.table_bits(bs)
+    T, field = SMod.field_of(pset)
+    B = SMod.table_bits(bs)
     starts = np.concatenate([[0], np.cumsum(sizes)])
-    n_idx = sum(len(SP.indexed_hashes(d[starts[k]:starts[k + 1]], d[starts[k + 1]:starts[k + 1] + 8] if k + 1 < len(sizes) else None, B, M, mask)) for k in range(len(sizes)))
+    n_idx = sum(len(SMod.indexed_hashes((T, M, field), d[starts[k]:starts[k + 1]], d[starts[k + 1]:starts[k + 1] + 8] if k + 1 < len(sizes) else None, B)) for k in range(len(sizes)))
     assert n_idx == indexed_by_rule(sizes, plants, M), "the model and the rule, written out, disagree"
     return d, on, tables
 
@@ -193,7 +195,7 @@ def test_hand_built_parts_and_slices(ctx):
             plants.update(p * per + o for p in range(1, parts) for o in (-2, -1, 0) if p * per < bs)
         plants.update((0, bs - 1, nblk * bs - 1, nblk * bs + 4999))
         d, on, tables = hand_case(ctx, bs, sizes, sorted(plants), 6)
-        assert all(t is not None for t in tables) and tables[0][1] < SP.table_bits(bs) - 8
+        assert all(t is not None for t in tables) and tables[0][1] < SMod.table_bits(bs) - 8
 
 
 @pytest.mark.parametrize("M", [2, 6, 8])
@@ -216,7 +218,7 @@ def test_hand_built_empty_tables(ctx):
     assert tables[0] == tables[2] == (bytes(32), 8) and tables[1] != tables[0]
     text = data_for("text_like", bs, 3, 500)
     on, tables = writer_case(ctx, text, bs, 6, b"", True)
-    assert SP.read_tables(on)[0] == 3 and on[10:17] == bytes([0x44, 35, 0, 0, 3, 6, 16]) and on[17:49] == bytes(32)
+    assert SMod.read_tables(on, types=TYPES)[0][0] == 3 and on[10:17] == bytes([0x44, 35, 0, 0, 3, 6, 16]) and on[17:49] == bytes(32)
     assert tables == [(bytes(32), 8), None, (bytes(32), 8), (bytes(32), 8)]               # (block 1 is incompressible: stored, no table)
     sr = Searcher(ctx, on)
     try:
@@ -262,7 +264,7 @@ def test_writer_arguments(ctx):
         ctx.stream_encode_gather_device(1, bs, False, [src.data_ptr()], [len(d)], out.data_ptr(), out.numel(), search_prefix=b":")
     # the existing calls return what they did
     for b2 in (4 << 10, 64 << 10, 8 << 20):
-        n2, B = 3 * b2 + 5, SP.table_bits(b2)
+        n2, B = 3 * b2 + 5, SMod.table_bits(b2)
         assert L.mlz_stream_bound(n2, b2, 4) == L.mlz_stream_bound(n2, b2, 0) + 7 + 4 * (12 + max(32, 1 << (B - 3)))
     assert gather(ctx, [b""], 4096, False, 6, b":") == gather(ctx, [b""], 4096, False)                 # an empty stream: no header, no info chunk
 
@@ -270,15 +272,15 @@ def test_writer_arguments(ctx):
 # ---- search ----
 
 def check_search(sr, stream, d, pattern, what, cap=None, ignore_crc=False):
-    want = SP.brute(d, pattern)
-    T, M, B, field, tables = SP.read_tables(stream, ignore_crc)
-    sizes = [n for n, _ in SP.data_grid(stream)]
-    plan = SP.plan(tables, sizes, pattern, T, M, B, field)
+    want = SMod.brute(d, pattern)
+    cfg, B, tables = SMod.read_tables(stream, ignore_crc, TYPES)
+    sizes = [n for n, _ in SMod.data_grid(stream)]
+    plan = SMod.plan(tables, sizes, pattern, cfg, B)
     cap = len(want) + 3 if cap is None else cap
     total, pos, stats = sr(pattern, cap, ignore_crc=ignore_crc)
     assert total == len(want) and pos == want[:cap], what
-    assert stats == (len(sizes), len(plan), SP.usable_tables(tables, pattern, T, M, field)), (what, stats, plan)
-    assert SP.chunks_touched(sizes, want, len(pattern)) <= set(plan), what
+    assert stats == (len(sizes), len(plan), SMod.usable_tables(tables, pattern, cfg)), (what, stats, plan)
+    assert SMod.chunks_touched(sizes, want, len(pattern)) <= set(plan), what
     total, pos, all_stats = sr(pattern, cap, ignore_crc=ignore_crc, no_tables=True)
     assert total == len(want) and pos == want[:cap] and all_stats == (len(sizes), sum(1 for n in sizes if n), 0), what + " (no tables)"
     return stats
@@ -290,8 +292,8 @@ def test_search_over_the_writers_streams(ctx, set_name, M):
     pset = PC.SETS[set_name]
     d, pats = PC.designed("json_like", bs, nblk, 777, M, pset)
     stream = gather(ctx, [d], bs, True, M, pset)
-    T, field = SP.field_of(pset)
-    assert SP.read_tables(stream)[:4] == (T, M, 16, field)
+    T, field = SMod.field_of(pset)
+    assert SMod.read_tables(stream, types=TYPES)[:2] == ((T, M, field), 16)
     sr = Searcher(ctx, stream)
     try:
         res = {name: check_search(sr, stream, d, p, "%s M=%d %s" % (set_name, M, name)) for name, p in pats + SC.patterns(d, M, bs)}
@@ -300,7 +302,7 @@ def test_search_over_the_writers_streams(ctx, set_name, M):
             assert res["one_window"][1] < nblk + 1 and res["border_last"][1] < nblk + 1 and res["absent_keyed"][1] <= 2
         # a small cap
         frequent = b'","user":"user_'
-        want = SP.brute(d, frequent)
+        want = SMod.brute(d, frequent)
         assert len(want) > 100
         for cap in (1, 7, len(want) - 1):
             check_search(sr, stream, d, frequent, "cap %d" % cap, cap=cap)
@@ -312,16 +314,16 @@ def test_search_foreign_streams(ctx):
     """Model-spliced streams of other writers: oracle level 1 and 2 blocks, stored chunks with tables, a chunk without a table in the middle."""
     bs, M = 64 << 10, 6
     pset = PC.SETS["json4"]
-    T, field = SP.field_of(pset)
+    T, field = SMod.field_of(pset)
     d, pats = PC.designed("json_like", bs, 8, 777, M, pset)
     r = synth.random_bytes(3 * bs, seed=2).tobytes() + d[:2 * bs]
     cases = []
     for level, obs in ((1, bs), (2, 1 << 20)):
-        cases.append(("oracle L%d" % level, SP.splice(O.stream_encode(d, level, obs), d, T, M, SP.table_bits(obs), field)[0], d))
-    cases.append(("a table-less chunk in the middle", SP.splice(O.stream_encode(d, 1, bs), d, T, M, 16, field, skip=(4,))[0], d))
-    T3, field3 = SP.field_of(PC.SETS["nonalnum"])
-    cases.append(("type 3", SP.splice(O.stream_encode(d, 1, bs), d, T3, M, 16, field3)[0], d))
-    cases.append(("stored chunks", SP.splice(O.stream_encode(r, 1, bs), r, T, M, 16, field, stored_too=True)[0], r))
+        cases.append(("oracle L%d" % level, SMod.splice(O.stream_encode(d, level, obs), d, (T, M, field), SMod.table_bits(obs))[0], d))
+    cases.append(("a table-less chunk in the middle", SMod.splice(O.stream_encode(d, 1, bs), d, (T, M, field), 16, skip=(4,))[0], d))
+    T3, field3 = SMod.field_of(PC.SETS["nonalnum"])
+    cases.append(("type 3", SMod.splice(O.stream_encode(d, 1, bs), d, (T3, M, field3), 16)[0], d))
+    cases.append(("stored chunks", SMod.splice(O.stream_encode(r, 1, bs), r, (T, M, field), 16, stored_too=True)[0], r))
     for name, stream, data in cases:
         assert O.stream_decode(stream, len(data)) == data, name
         sr = Searcher(ctx, stream)
@@ -341,17 +343,17 @@ def test_search_patched_prefix_field(ctx):
     pset = PC.SETS["json4"]
     d, pats = PC.designed("json_like", bs, nblk, 777, M, pset)
     stream = gather(ctx, [d], bs, False, M, pset)
-    T, _, B, field, tables = SP.read_tables(stream)
-    sizes = [n for n, _ in SP.data_grid(stream)]
+    cfg, B, tables = SMod.read_tables(stream, types=TYPES)
+    sizes = [n for n, _ in SMod.data_grid(stream)]
     p = dict(pats)["one_window"]
-    plan = SP.plan(tables, sizes, p, T, M, B, field)
+    plan = SMod.plan(tables, sizes, p, cfg, B)
     skipped = next(k for k in range(1, nblk) if k not in plan)
-    tabs = [c for c in SP.chunks_of(stream) if c[1] == SP.CHUNK_TABLE]
+    tabs = [c for c in SMod.chunks_of(stream) if c[1] == SMod.CHUNK_TABLE]
     b = bytearray(stream)
     b[tabs[skipped][0] + 4 + 3 + 7] ^= 0x20
     b = bytes(b)
     t2 = list(tables); t2[skipped] = None
-    assert SP.read_tables(b)[4] == t2
+    assert SMod.read_tables(b, types=TYPES)[2] == t2
     sr = Searcher(ctx, b)
     try:
         for ignore in (False, True):
@@ -384,6 +386,6 @@ def test_designated_input_decodes_a_handful(ctx, kind, set_name):
             st = check_search(sr, stream, d, nd, "%s %s seed %d" % (kind, set_name, seed))
             print(kind, set_name, seed, "decoded", st[1], "of", st[0], "tables", st[2], "stream", len(stream))
             assert st[0] == nblk and st[1] <= 12
-            assert sorted(set(SP.brute(d, nd)) & set(at)) == sorted(at)
+            assert sorted(set(SMod.brute(d, nd)) & set(at)) == sorted(at)
         finally:
             sr.close()

@@ -2,7 +2,7 @@
 that run into the bytes behind it; the Writer hands those bytes over from the next non-empty range (StreamTables::overlap() of them, all four
 table types by the same path).  For each table type: 4 KiB blocks, five whole blocks of text and a tail of t bytes, with an indexed
 occurrence planted across every cut; every set of cuts must give the uncut stream, and the uncut stream is the model's splice
-(tests/search_tables.py, search_prefix_tables.py, search_long_prefix_tables.py).
+(tests/search_model.py).
 
 Not vacuous: for every cut used, the model's table of the block in front of it changes when the bytes behind the cut are zeros (so a tail
 that is lost, short or misplaced shows), and every whole block has a table (none is stored, none has its table dropped; the tail of a few
@@ -17,16 +17,14 @@ import pytest
 
 from minlz_amd import _lib, synth
 from minlz_amd.api import search_long_prefix_config, search_tables_config
-from tests import search_long_prefix_tables as SL
+from tests import search_model as SMod
 from tests import search_prefix_cases as PC
-from tests import search_prefix_tables as SP
-from tests import search_tables as ST
 from tests.search_gpu import first_difference, gather_into
 
 pytestmark = pytest.mark.gpu
 
 BS, NBLK, M, E = 4 << 10, 5, 6, 3
-B = ST.table_bits(BS)
+B = SMod.table_bits(BS)
 TAILS = (3, 9, 100)
 CUT_SETS = ([2 * BS], [2 * BS, 2 * BS], [5 * BS], [BS, BS, 2 * BS, 2 * BS, 5 * BS])
 CUTS = sorted({c for cs in CUT_SETS for c in cs})
@@ -66,24 +64,23 @@ def data_for_cuts(name, t):
     return bytes(d)
 
 
-def model(name, off, d):
-    """-> (the model's splice of the table-less stream `off`, its tables)"""
+def model_config(name):
     kw, K = CONFIGS[name]
     if K is not None:
-        return SL.splice(off, d, M, B, SL.field_of(kw["search_long_prefix"], E))
+        return SMod.config(4, M, kw["search_long_prefix"], E)
     if "search_prefix" in kw:
-        T, field = SP.field_of(kw["search_prefix"])
-        return SP.splice(off, d, T, M, B, field)
-    return ST.splice(off, d, M, B)
+        T, field = SMod.field_of(kw["search_prefix"])
+        return T, M, field
+    return SMod.config(1, M)
+
+
+def model(name, off, d):
+    """-> (the model's splice of the table-less stream `off`, its tables)"""
+    return SMod.splice(off, d, model_config(name), B)
 
 
 def block_table(name, block, follow):
-    kw, K = CONFIGS[name]
-    if K is not None:
-        return SL.build_table(block, follow, B, M, SL.field_of(kw["search_long_prefix"], E))
-    if "search_prefix" in kw:
-        return SP.build_table(block, follow, B, M, SP.mask_of(*SP.field_of(kw["search_prefix"])))
-    return ST.build_table(block, follow, B, M)
+    return SMod.build_table(model_config(name), block, follow, B)
 
 
 def tail_matters(name, d):
@@ -115,7 +112,7 @@ def test_cuts_do_not_change_the_stream(ctx, name, t):
     one = write(ctx, d, [], kw)
     want, tables = model(name, off, d)
     assert len(tables) == NBLK + 1 and all(tb is not None for tb in tables[:NBLK]), "a block without a table"
-    assert all(typ == 0x02 for _, typ in ST.data_grid(off)[:NBLK]), "a stored block"
+    assert all(typ == 0x02 for _, typ in SMod.data_grid(off)[:NBLK]), "a stored block"
     assert one == want, "uncut: lengths %d / %d, first difference at %d" % (len(one), len(want), first_difference(one, want))
     for cuts in CUT_SETS:
         got = write(ctx, d, cuts, kw)

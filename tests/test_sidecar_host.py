@@ -3,10 +3,8 @@ minlz_amd/csrc/mlz_stream_search.h on the host (the 0x47 writer and parser, the 
 tests/sidecar_model.py is the same specification in Python, written separately.  The two must agree, and a plan through a sidecar must
 hold every chunk with a byte of a true occurrence."""
 import ctypes as C
-import os
 import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,57 +13,37 @@ import oracle as O
 from minlz_amd import _lib, synth
 from minlz_amd.api import search_config
 from tests import search_cases as SC
-from tests import search_tables as ST
+from tests import search_host as H
+from tests import search_model as SMod
 from tests import sidecar_model as SM
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tools", "sidecar_check.cpp")
+SRC = "sidecar_check.cpp"
 BS = 64 << 10
 
-CFG1 = SM.config(1, 6)
-CFG2 = SM.config(2, 6, b'":, ')
-CFG3 = SM.config(3, 5, bytes(v for v in range(256) if not chr(v).isalnum()))
-CFG4 = SM.config(4, 6, b'"user":"', 3)
-
-
-def runner(exe):
-    def run(records):
-        path = os.path.join(os.path.dirname(exe), "cases.bin")
-        with open(path, "wb") as f:
-            for r in records:
-                f.write(r)
-        r = subprocess.run([exe, path], capture_output=True, text=True, timeout=900)
-        os.unlink(path)
-        assert r.returncode == 0, r.stderr[-2000:]
-        return r.stdout.splitlines()
-    return run
+CFG1 = SMod.config(1, 6)
+CFG2 = SMod.config(2, 6, b'":, ')
+CFG3 = SMod.config(3, 5, bytes(v for v in range(256) if not chr(v).isalnum()))
+CFG4 = SMod.config(4, 6, b'"user":"', 3)
 
 
 @pytest.fixture(scope="module")
 def checkers(tmp_path_factory):
-    """The plain build, and the same program under AddressSanitizer and UBSan where this g++ links their runtimes (a stand-alone
-    program: nothing is preloaded)."""
-    d = tmp_path_factory.mktemp("sidecar")
-    exe = str(d / "sc")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-o", exe, SRC], check=True)
-    san = str(d / "san" / "sc")
-    os.makedirs(os.path.dirname(san))
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", san, SRC], capture_output=True, text=True)
-    return runner(exe), (runner(san) if r.returncode == 0 else None), r.stderr[-300:]
+    """The plain build, and the same program under AddressSanitizer and UBSan where this g++ links their runtimes."""
+    return H.build_checker(tmp_path_factory, SRC), H.build_checker(tmp_path_factory, SRC, sanitized=True)
 
 
 def both(checkers, records):
     """The plain program's lines; the sanitized build runs the same cases and must print the same."""
-    plain, san, _ = checkers
-    lines = plain(records)
+    plain, san = checkers
+    lines = plain(records)[0]
     if san is not None:
-        assert san(records) == lines
+        assert san(records)[0] == lines
     return lines
 
 
 def test_sanitized_build_links(checkers):
     if checkers[1] is None:
-        pytest.skip("this g++ does not link the sanitizer runtimes: " + checkers[2])
+        pytest.skip("this g++ does not link the sanitizer runtimes: " + H.LINK_ERROR[SRC][-300:])
     assert shutil.which("g++")
 
 
@@ -119,9 +97,9 @@ def test_rule_over_several_sets_against_the_model(checkers):
                 ov = int(rng.choice([0, 1, 3, 5, 7, 18, 271]))
                 sets.append((nw, t_min, ov, a, s))
                 if nw:
-                    votes.append(SM.admits(a, s, sizes, nw, L, t_min, ov))
+                    votes.append(SMod.admits(a, s, sizes, nw, L, t_min, ov))
             recs.append(rec_rule(sets, sizes, L))
-            want.append(SM.decoded_set(votes, sizes, L))
+            want.append(SMod.decoded_set(votes, sizes, L))
     got = both(checkers, recs)
     assert len(got) == len(want)
     for i, line in enumerate(got):
@@ -201,7 +179,7 @@ def test_spliced_streams_against_the_model(checkers, streams, kind):
             got = parse_line(lines[ci * len(pats) + pi])
             want = SM.plan(tables, sizes, p, cfgs, Bs)
             assert got == ((len(cf), SM.usable(tables, [p], cfgs, Bs)), want), (kind, ci, name)
-            assert ST.chunks_touched(sizes, ST.brute(data, p), len(p)) <= set(want), (kind, ci, name)
+            assert SMod.chunks_touched(sizes, SMod.brute(data, p), len(p)) <= set(want), (kind, ci, name)
             plans[ci, pi] = set(want)
     for pi in range(len(pats)):
         assert plans[3, pi] <= plans[0, pi] and plans[3, pi] <= plans[1, pi]
@@ -235,7 +213,7 @@ def test_chunks_shorter_than_the_overlap_hide_nothing(checkers):
         pruned = 0
         for i, p in enumerate(pats):
             plan = SM.plan(tables, UNEVEN, p, cfgs, Bs)
-            assert ST.chunks_touched(UNEVEN, ST.brute(d, p), len(p)) <= set(plan), (cf, i)
+            assert SMod.chunks_touched(UNEVEN, SMod.brute(d, p), len(p)) <= set(plan), (cf, i)
             pruned += len(plan) < len(UNEVEN)
             if i % 7 == 0 or i >= len(pats) - 3:
                 recs.append(rec_attach(side, stream, p))
@@ -248,14 +226,14 @@ def test_attach_validation_against_the_model(checkers, streams):
     """Lying and broken sidecars: the shared header refuses exactly what the model refuses, and passes over what the model passes over."""
     data, stream = streams["json_like"]
     side, _ = SM.build(stream, data, [CFG1, CFG2], with_tables=True)
-    cks = ST.chunks_of(side)
+    cks = SMod.chunks_of(side)
     refs = [(p, n) for p, t, n in cks if t == SM.CHUNK_REF]
-    tabs = [(p, n) for p, t, n in cks if t == ST.CHUNK_TABLE]
+    tabs = [(p, n) for p, t, n in cks if t == SMod.CHUNK_TABLE]
     mb = BS
 
     def with_ref(i, payload):
         p, n = refs[i]
-        return side[:p] + ST.frame(SM.CHUNK_REF, payload) + side[p + 4 + n:]
+        return side[:p] + SMod.frame(SM.CHUNK_REF, payload) + side[p + 4 + n:]
 
     dcs = SM.main_chunks(stream)
     cases = {
@@ -273,7 +251,7 @@ def test_attach_validation_against_the_model(checkers, streams):
     # a reference chunk with two references, followed by the rest minus the block it swallowed: valid
     p3, n3 = refs[3]
     p4, n4 = refs[4]
-    merged = side[:p3] + ST.frame(SM.CHUNK_REF, SM.uvarint(dcs[3][0]) + SM.uvarint(0) + SM.uvarint(dcs[4][0] - dcs[3][0]) + SM.uvarint(0)) + side[p3 + 4 + n3:p4] + side[p4 + 4 + n4:]
+    merged = side[:p3] + SMod.frame(SM.CHUNK_REF, SM.uvarint(dcs[3][0]) + SM.uvarint(0) + SM.uvarint(dcs[4][0] - dcs[3][0]) + SM.uvarint(0)) + side[p3 + 4 + n3:p4] + side[p4 + 4 + n4:]
     cases["merged references"] = merged
     pat = data[5 * BS // 3:5 * BS // 3 + 16]
     names = list(cases)

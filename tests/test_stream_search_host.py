@@ -1,64 +1,25 @@
 """The rules of the block search tables and of mlz_dev_reader_search's plan without a GPU: tools/stream_search_check.cpp runs the shared
 header minlz_amd/csrc/mlz_stream_search.h (the hash, a table chunk's checks, the probe, the rule that picks the chunks to decode, the
-writer's reduction rule) on the host, with the kernels' hops over the chunk headers as plain loops, and tests/search_tables.py is the same
+writer's reduction rule) on the host, with the kernels' hops over the chunk headers as plain loops, and tests/search_model.py is the same
 specification in Python, written separately.  The two must agree, and the decoded set must hold every chunk with a byte of a true occurrence."""
-import os
-import struct
-import subprocess
-
 import numpy as np
 import pytest
 
 import oracle as O
 from minlz_amd import _lib, synth
 from tests import search_cases as SC
-from tests import search_tables as ST
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import search_model as SMod
+from tests.search_host import build_checker, parse_stream_line, rec_hash, rec_layout, rec_reduce, rec_rule, rec_stream
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("ssc") / "ssc"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-o", str(exe), os.path.join(ROOT, "tools", "stream_search_check.cpp")], check=True)
-
-    def run(records):
-        path = exe.parent / "cases.bin"
-        with open(path, "wb") as f:
-            for r in records:
-                f.write(r)
-        r = subprocess.run([str(exe), str(path)], capture_output=True, text=True, timeout=900, check=True)
-        os.unlink(path)
-        return r.stdout.splitlines()
-    return run
+    run = build_checker(tmp_path_factory, "stream_search_check.cpp")
+    return lambda records: run(records)[0]
 
 
-def rec_hash(triples):
-    return struct.pack("<II", 1, len(triples)) + b"".join(struct.pack("<QII", v, B, M) for v, B, M in triples)
-
-
-def rec_rule(a, s, sizes, nw, L):
-    n = len(sizes)
-    return struct.pack("<IIII", 2, n, nw, L) + np.asarray(a, np.uint32).tobytes() + np.asarray(s, np.uint32).tobytes() + np.asarray(sizes, np.uint64).tobytes()
-
-
-def rec_stream(stream, pattern, flags=0):
-    return struct.pack("<IQII", 3, len(stream), len(pattern), flags) + stream + pattern
-
-
-def rec_reduce(B, pops):
-    return struct.pack("<II", 4, B) + np.asarray(pops, np.uint32).tobytes()
-
-
-def rec_layout(sizes, jobs, pattern, data, group_bytes):
-    return (struct.pack("<IIIIQQ", 5, len(sizes), len(jobs), len(pattern), group_bytes, len(data)) + np.asarray(sizes, np.uint64).tobytes() +
-            np.asarray(jobs, np.uint32).tobytes() + pattern + data)
-
-
-def parse_stream_line(line):
-    head, _, rest = line.partition(":")
-    M, B, usable = (int(v) for v in head.split())
-    return M, B, usable, [int(v) for v in rest.split()]
+def type1(M):
+    return SMod.config(1, M)
 
 
 def test_exported():
@@ -75,16 +36,16 @@ def test_hash_against_python_integers(checker):
             triples += [(v, B, M) for v in vals]
     assert (2 in {M for _, _, M in triples}) and {15, 16} <= {B for _, B, M in triples if M == 2}
     got = [int(v) for v in checker([rec_hash(triples)])[0].split()]
-    want = [ST.hash_value(v, B, M) for v, B, M in triples]
+    want = [SMod.hash_value(v, B, M) for v, B, M in triples]
     assert got == want
     # bytes beyond M do not enter; the vectorised model agrees with the integer one
     buf = rng.integers(0, 256, 300, dtype=np.uint8)
     for M in range(1, 9):
         for B in (8, 15, 16, 23):
-            hv = ST.hash_windows(buf, B, M)
+            hv = SMod.hash_windows(buf, B, M)
             for i in (0, 7, len(hv) - 1):
                 v = int.from_bytes(buf[i:i + M].tobytes(), "little")
-                assert int(hv[i]) == ST.hash_value(v, B, M) == ST.hash_value(v | (0xAB << (8 * M)) if M < 8 else v, B, M)
+                assert int(hv[i]) == SMod.hash_value(v, B, M) == SMod.hash_value(v | (0xAB << (8 * M)) if M < 8 else v, B, M)
             assert int(hv.max()) < (1 << B)
 
 
@@ -103,7 +64,7 @@ def test_rule_on_generated_vectors(checker):
         s[a == nw] = nw
         sizes = rng.choice([0, 1, 3, L - 1 if L > 1 else 1, L, 4096, 65536], n)
         recs.append(rec_rule(a, s, sizes, nw, L))
-        want.append(ST.decoded_set(a.tolist(), s.tolist(), sizes.tolist(), nw, L))
+        want.append(SMod.decoded_set([SMod.admits(a.tolist(), s.tolist(), sizes.tolist(), nw, L, 1)], sizes.tolist(), L))
     got = [[int(v) for v in line.split()] for line in checker(recs)]
     assert got == want
 
@@ -111,8 +72,8 @@ def test_rule_on_generated_vectors(checker):
 def _spliced(kind, bs, nblk, M, seed=2, tail=777, level=1):
     d = getattr(synth, kind)(bs * nblk + tail, seed).tobytes()
     s = O.stream_encode(d, level, bs)
-    B = ST.table_bits(bs)
-    sp, tables = ST.splice(s, d, M, B)
+    B = SMod.table_bits(bs)
+    sp, tables = SMod.splice(s, d, type1(M), B)
     assert O.stream_decode(sp, len(d)) == d
     return d, sp, tables, B
 
@@ -122,23 +83,23 @@ def _spliced(kind, bs, nblk, M, seed=2, tail=777, level=1):
 def test_spliced_streams_decoded_set_holds_every_occurrence(checker, kind, M):
     bs, nblk = 64 << 10, 12
     d, sp, tables, B = _spliced(kind, bs, nblk, M)
-    sizes = [n for n, _ in ST.data_grid(sp)]
+    sizes = [n for n, _ in SMod.data_grid(sp)]
     assert any(t is not None for t in tables) or M <= 2
     pats = SC.patterns(d, M, bs)
-    lines = checker([rec_stream(sp, p) for _, p in pats] + [rec_stream(sp, p, 1) for _, p in pats[:2]])
+    lines = checker([rec_stream(3, sp, p) for _, p in pats] + [rec_stream(3, sp, p, 1) for _, p in pats[:2]])
     assert {len(p) for _, p in pats} >= {1, max(1, M - 1), M, M + 1, 16, 256}
     for (name, p), line in zip(pats, lines):
-        gM, gB, usable, got = parse_stream_line(line)
-        want = ST.plan(tables, sizes, p, M, B)
+        (gM, gB, usable), got = parse_stream_line(line)
+        want = SMod.plan(tables, sizes, p, type1(M), B)
         assert got == want, (kind, M, name)
         if len(p) >= M and usable:
             assert (gM, gB, usable) == (M, B, sum(t is not None for t in tables))
-        touched = ST.chunks_touched(sizes, ST.brute(d, p), len(p))
+        touched = SMod.chunks_touched(sizes, SMod.brute(d, p), len(p))
         assert touched <= set(got), (kind, M, name, sorted(touched - set(got)))
         if name != "absent":
             assert touched
     for line in lines[len(pats):]:
-        assert parse_stream_line(line)[3] == list(range(len(sizes)))
+        assert parse_stream_line(line)[1] == list(range(len(sizes)))
 
 
 def test_real_tables_every_block_size(checker):
@@ -147,50 +108,52 @@ def test_real_tables_every_block_size(checker):
         d = bytearray(synth.text_like(bs * nblk + 300, 7).tobytes())
         d[bs:2 * bs] = synth.random_bytes(bs, seed=3).tobytes()
         d = bytes(d)
-        M, B = 6, ST.table_bits(bs)
-        sp, tables = ST.splice(O.stream_encode(d, 1, bs), d, M, B)
-        sizes = [n for n, _ in ST.data_grid(sp)]
+        M, B = 6, SMod.table_bits(bs)
+        sp, tables = SMod.splice(O.stream_encode(d, 1, bs), d, type1(M), B)
+        sizes = [n for n, _ in SMod.data_grid(sp)]
         assert tables[1] is None and tables[0] is not None and sizes[-1] == 300
         pats = [d[bs // 2:bs // 2 + 16], d[2 * bs - 8:2 * bs + 8], d[-20:], d[bs + 100:bs + 116], bytes(SC.needle(16, 5))]
-        lines = checker([rec_stream(sp, p) for p in pats])
+        lines = checker([rec_stream(3, sp, p) for p in pats])
         for p, line in zip(pats, lines):
-            _, _, _, got = parse_stream_line(line)
-            assert got == ST.plan(tables, sizes, p, M, B)
-            assert ST.chunks_touched(sizes, ST.brute(d, p), len(p)) <= set(got)
-        absent = parse_stream_line(lines[-1])[3]
+            _, got = parse_stream_line(line)
+            assert got == SMod.plan(tables, sizes, p, type1(M), B)
+            assert SMod.chunks_touched(sizes, SMod.brute(d, p), len(p)) <= set(got)
+        absent = parse_stream_line(lines[-1])[1]
         assert {1, 2} <= set(absent)   # the stored block has no table: it and the chunk behind it are always decoded
 
 
 def test_broken_and_foreign_tables_count_as_none(checker):
     bs, nblk, M = 64 << 10, 6, 6
     d, sp, tables, B = _spliced("json_like", bs, nblk, M)
-    sizes = [n for n, _ in ST.data_grid(sp)]
+    sizes = [n for n, _ in SMod.data_grid(sp)]
     p = bytes(SC.needle(16, 8))
-    base = parse_stream_line(checker([rec_stream(sp, p)])[0])
-    assert base[2] == sum(t is not None for t in tables) == nblk + 1 and base[3] == ST.plan(tables, sizes, p, M, B)
-    cks = [c for c in ST.chunks_of(sp) if c[1] == ST.CHUNK_TABLE]
+    base = parse_stream_line(checker([rec_stream(3, sp, p)])[0])
+    assert base[0][2] == sum(t is not None for t in tables) == nblk + 1 and base[1] == SMod.plan(tables, sizes, p, type1(M), B)
+    cks = [c for c in SMod.chunks_of(sp) if c[1] == SMod.CHUNK_TABLE]
     off = cks[2][0]
     flipped = bytearray(sp)
     flipped[off + 12 + 5] ^= 0x10          # a table bit; the CRC is now stale
     t2 = list(tables); t2[2] = None
-    got = parse_stream_line(checker([rec_stream(bytes(flipped), p)])[0])
-    assert got[2] == nblk and got[3] == ST.plan(t2, sizes, p, M, B) and 2 in got[3]
+    got = parse_stream_line(checker([rec_stream(3, bytes(flipped), p)])[0])
+    assert got[0][2] == nblk and got[1] == SMod.plan(t2, sizes, p, type1(M), B) and 2 in got[1]
     tb = bytearray(tables[2][0]); tb[5] ^= 0x10
     t3 = list(tables); t3[2] = (bytes(tb), tables[2][1])
-    got = parse_stream_line(checker([rec_stream(bytes(flipped), p, 2)])[0])
-    assert got[2] == nblk + 1 and got[3] == ST.plan(t3, sizes, p, M, B)
+    got = parse_stream_line(checker([rec_stream(3, bytes(flipped), p, 2)])[0])
+    assert got[0][2] == nblk + 1 and got[1] == SMod.plan(t3, sizes, p, type1(M), B)
     for mutate in ("type", "M", "B", "R", "0x46"):
         b = bytearray(sp)
         if mutate == "0x46":
             b[off] = 0x46
         else:
             b[off + 4 + ("type", "M", "B", "R").index(mutate)] += 1
-        got = parse_stream_line(checker([rec_stream(bytes(b), p, 2)])[0])
-        assert got[2] == nblk and 2 in got[3], mutate
+        got = parse_stream_line(checker([rec_stream(3, bytes(b), p, 2)])[0])
+        assert got[0][2] == nblk and 2 in got[1], mutate
     # no info chunk, a pattern shorter than M: every chunk is decoded
     noinfo = sp[:10] + sp[17:]
-    assert parse_stream_line(checker([rec_stream(noinfo, p)])[0])[2:] == (0, list(range(nblk + 1)))
-    assert parse_stream_line(checker([rec_stream(sp, p[:M - 1])])[0])[2:] == (0, list(range(nblk + 1)))
+    head, got = parse_stream_line(checker([rec_stream(3, noinfo, p)])[0])
+    assert (head[2], got) == (0, list(range(nblk + 1)))
+    head, got = parse_stream_line(checker([rec_stream(3, sp, p[:M - 1])])[0])
+    assert (head[2], got) == (0, list(range(nblk + 1)))
 
 
 def test_reduce_rule_agrees_with_the_model(checker):
@@ -230,12 +193,12 @@ def test_designated_input_skips_most_chunks(kind):
     for seed in (1, 2, 3):
         bs, nblk, M = 64 << 10, 128, 6
         d, nd, at = SC.planted(kind, bs, nblk, 16, seed)
-        B = ST.table_bits(bs)
+        B = SMod.table_bits(bs)
         tables = []
         for k in range(nblk):
-            t, R = ST.build_table(d[k * bs:(k + 1) * bs], d[(k + 1) * bs:(k + 1) * bs + 8] if k + 1 < nblk else None, B, M)
+            t, R = SMod.build_table(type1(M), d[k * bs:(k + 1) * bs], d[(k + 1) * bs:(k + 1) * bs + 8] if k + 1 < nblk else None, B)
             tables.append(None if t is None else (t, R))
-        got = ST.plan(tables, [bs] * nblk, nd, M, B)
+        got = SMod.plan(tables, [bs] * nblk, nd, type1(M), B)
         print(kind, seed, len(got), got)
         assert {3, 64, 126, 127} <= set(got) and len(got) <= 12
 
@@ -265,7 +228,7 @@ def test_scratch_layout_finds_what_brute_force_finds(checker):
         taken = np.zeros(len(d) + 1, dtype=bool)
         for k in jobs:
             taken[starts[k]:starts[k + 1]] = True
-        want.append([p for p in ST.brute(d, pat) if taken[p:p + L].all()])
+        want.append([p for p in SMod.brute(d, pat) if taken[p:p + L].all()])
         meta.append((nck, L, group, full))
     lines = checker(recs)
     several_groups = 0

@@ -1,11 +1,8 @@
 """The rules of the long-prefix search tables (table type 4) and of the search's plan over them without a GPU:
 tools/stream_search_check.cpp runs the shared header minlz_amd/csrc/mlz_stream_search.h on the host (record kinds 10 and 11) and
-tests/search_long_prefix_tables.py is the same specification in Python, written separately.  The two must agree, and the decoded set must
+tests/search_model.py is the same specification in Python, written separately.  The two must agree, and the decoded set must
 hold every chunk with a byte of a true occurrence."""
 import ctypes as C
-import os
-import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,39 +12,14 @@ from minlz_amd import _lib, synth
 from minlz_amd.api import search_long_prefix_config
 from tests import search_cases as SC
 from tests import search_long_prefix_cases as LC
-from tests import search_long_prefix_tables as SL
-from tests import search_prefix_tables as SP
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import search_model as SMod
+from tests.search_host import build_checker, parse_stream_line, rec_groups, rec_stream
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("sscl") / "ssc"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-o", str(exe), os.path.join(ROOT, "tools", "stream_search_check.cpp")], check=True)
-
-    def run(records):
-        path = exe.parent / "cases.bin"
-        with open(path, "wb") as f:
-            for r in records:
-                f.write(r)
-        r = subprocess.run([str(exe), str(path)], capture_output=True, text=True, timeout=900, check=True)
-        os.unlink(path)
-        return r.stdout.splitlines()
-    return run
-
-
-def rec_stream(stream, pattern, flags=0):
-    return struct.pack("<IQII", 10, len(stream), len(pattern), flags) + stream + pattern
-
-
-def rec_groups(M, field, pattern):
-    return struct.pack("<IIII", 11, M, len(pattern), len(field)) + bytes(field) + pattern
-
-
-def parse_stream_line(line):
-    head, _, rest = line.partition(":")
-    return tuple(int(v) for v in head.split()), [int(v) for v in rest.split()]      # (T, M, B, usable, ng, t_min, gsize), the plan
+    run = build_checker(tmp_path_factory, "stream_search_check.cpp")
+    return lambda records: run(records)[0]
 
 
 def test_exported():
@@ -72,7 +44,7 @@ def test_bound_and_arguments_on_the_host():
     L = _lib.lib()
     for bs in (4 << 10, 64 << 10, 2 << 20, 8 << 20):
         n = 3 * bs + 5
-        B = SL.table_bits(bs)
+        B = SMod.table_bits(bs)
         for idx in (0, 1):
             plain = L.mlz_stream_bound(n, bs, idx)
             for K in (1, 8, 9, 256):
@@ -112,9 +84,9 @@ def test_groups_against_the_model(checker):
     recs, want = [], []
 
     def add(M, E, pfx, pat):
-        field = SL.field_of(pfx, E)
-        recs.append(rec_groups(M, field, pat))
-        G, t_min = SL.groups(pat, M, field)
+        cfg4 = SMod.config(4, M, pfx, E)
+        recs.append(rec_groups(M, cfg4[2], pat))
+        G, t_min = SMod.groups(pat, cfg4)
         want.append(((t_min, E + 1) if G else None, [i + len(pfx) for i in G]))      # (t_min and the group size matter only where there is a group)
     for M in (1, 2, 4, 6, 8):
         for E in sorted({0, 3, 15 - M, 16 - M if M > 1 else 15}):
@@ -151,33 +123,34 @@ CONFIGS = [(LC.USER, 6, 3), (LC.USER, 6, 0), (b'":"', 8, 8), (b'"user":"u', 1, 1
 
 def _spliced(kind, bs, nblk, M, E, pfx, tail=777, level=1, **kw):
     d, pats = LC.designed(kind, bs, nblk, tail, M, E, pfx)
-    field = SL.field_of(pfx, E)
-    B = SL.table_bits(bs)
-    sp, tables = SL.splice(O.stream_encode(d, level, bs), d, M, B, field, **kw)
+    field = SMod.config(4, M, pfx, E)[2]
+    B = SMod.table_bits(bs)
+    sp, tables = SMod.splice(O.stream_encode(d, level, bs), d, (4, M, field), B, **kw)
     assert O.stream_decode(sp, len(d)) == d
     return d, pats, sp, tables, (4, M, B, field)
 
 
 def _check_patterns(checker, d, sp, pats, what, model_stream=None):
     """The checker's plan over `sp` is the model's, and it holds every chunk with a byte of an occurrence."""
-    T, M, B, field, tables = SL.read_tables(sp if model_stream is None else model_stream)
-    sizes = [n for n, _ in SL.data_grid(sp)]
+    cfg, B, tables = SMod.read_tables(sp if model_stream is None else model_stream)
+    T, M, field = cfg or (None, None, b"")
+    sizes = [n for n, _ in SMod.data_grid(sp)]
     everything = [k for k in range(len(sizes)) if sizes[k]]
-    lines = checker([rec_stream(sp, p) for _, p in pats])
+    lines = checker([rec_stream(10, sp, p) for _, p in pats])
     n_tables = sum(t is not None for t in tables)
     out = {}
     for (name, p), line in zip(pats, lines):
         head, got = parse_stream_line(line)
-        assert got == SL.plan(tables, sizes, p, T, M, B, field), (what, name)
-        assert head[3] == SL.usable_tables(tables, p, T, M, field), (what, name, head)
+        assert got == SMod.plan(tables, sizes, p, cfg, B), (what, name)
+        assert head[3] == SMod.usable_tables(tables, p, cfg), (what, name, head)
         if T == 4:
-            G, t_min = SL.groups(p, M, field)
+            G, t_min = SMod.groups(p, cfg)
             assert head[:3] == (T, M, B) and head[4] == (len(G) if n_tables else 0), (what, name, head)
             if G and n_tables:
                 assert head[5:] == (t_min, field[1] + 1), (what, name, head)
             else:
                 assert got == everything, (what, name)
-        touched = SL.chunks_touched(sizes, SL.brute(d, p), len(p))
+        touched = SMod.chunks_touched(sizes, SMod.brute(d, p), len(p))
         assert touched <= set(got), (what, name, sorted(touched - set(got)))
         if not name.startswith("absent"):
             assert touched, (what, name)
@@ -201,7 +174,7 @@ def test_spliced_streams_decoded_set_holds_every_occurrence(checker, kind, pfx, 
         assert {0, 1} <= set(res["two_groups"][1]) and {1, 2} <= set(res["straddle"][1]) and {2, 3} <= set(res["ends_on_last"][1])
         assert len(res["absent_keyed"][1]) <= 2
     # MLZ_SEARCH_NO_TABLES
-    head, got = parse_stream_line(checker([rec_stream(sp, pats[0][1], 1)])[0])
+    head, got = parse_stream_line(checker([rec_stream(10, sp, pats[0][1], 1)])[0])
     assert head[3:5] == (0, 0) and got == everything
 
 
@@ -216,21 +189,22 @@ def test_user_prefix_figures(checker):
     """json_like, seed 2, 16 x 64 KiB + 777, prefix '"user":"', M = 6, E = 3: the set bits, the fold and the admitted chunks."""
     bs, nblk = 64 << 10, 16
     d = synth.json_like(bs * nblk + 777, 2).tobytes()
-    field = SL.field_of(LC.USER, 3)
-    sp, tables = SL.splice(O.stream_encode(d, 1, bs), d, 6, 16, field)
+    cfg4 = SMod.config(4, 6, LC.USER, 3)
+    field = cfg4[2]
+    sp, tables = SMod.splice(O.stream_encode(d, 1, bs), d, cfg4, 16)
     assert all(t is not None for t in tables)
     for k in range(nblk):
-        bits = len(set(SL.indexed_hashes(d[k * bs:(k + 1) * bs], d[(k + 1) * bs:(k + 1) * bs + 32], 16, 6, field).tolist()))
+        bits = len(set(SMod.indexed_hashes(cfg4, d[k * bs:(k + 1) * bs], d[(k + 1) * bs:(k + 1) * bs + 32], 16).tolist()))
         assert 500 <= bits <= 900, (k, bits)
         assert tables[k][1] == 3 and len(tables[k][0]) == 1024, (k, tables[k][1])
     share = sum(12 + len(field) + len(t[0]) for t in tables) / len(d)
     assert share < 0.02
-    head, got = parse_stream_line(checker([rec_stream(sp, LC.ABSENT_USER)])[0])
+    head, got = parse_stream_line(checker([rec_stream(10, sp, LC.ABSENT_USER)])[0])
     assert head == (4, 6, 16, nblk + 1, 1, 0, 4) and len(got) <= 2
     at = d.find(LC.USER, 5 * bs + 1000)
     present = d[at - 3:at + 19]
-    head, got = parse_stream_line(checker([rec_stream(sp, present)])[0])
-    assert SL.chunks_touched([bs] * nblk + [777], SL.brute(d, present), 22) <= set(got) and len(got) < nblk
+    head, got = parse_stream_line(checker([rec_stream(10, sp, present)])[0])
+    assert SMod.chunks_touched([bs] * nblk + [777], SMod.brute(d, present), 22) <= set(got) and len(got) < nblk
 
 
 def test_table_verdicts(checker):
@@ -239,40 +213,40 @@ def test_table_verdicts(checker):
     bs, nblk, M, E = 64 << 10, 6, 8, 8
     d, pats, sp, tables, (T, _, B, field) = _spliced("json_like", bs, nblk, M, E, LC.USER)
     K = len(LC.USER)
-    sizes = [n for n, _ in SL.data_grid(sp)]
+    sizes = [n for n, _ in SMod.data_grid(sp)]
     everything = list(range(nblk + 1))
     assert all(t is not None for t in tables)
     base = _check_patterns(checker, d, sp, pats, "base")
     assert base["p0"][1] != everything
     ilen = 4 + 3 + 2 + K
-    assert sp[10:10 + ilen] == SL.info_chunk(M, B, field)
+    assert sp[10:10 + ilen] == SMod.info_chunk((4, M, field), B)
     # M + E = 17 (in the info chunk alone, and in every chunk)
     bad_field = bytes([K - 1, 9]) + LC.USER
-    every = SL.splice(O.stream_encode(d, 1, bs), d, M, B, bad_field)[0]
-    for name, b in (("info E + 1", sp[:10] + SL.info_chunk(M, B, bad_field) + sp[10 + ilen:]), ("E = 9 everywhere", every),
-                    ("short field", sp[:10] + SL.frame(SL.CHUNK_INFO, bytes([T, M, B]) + field[:5]) + sp[10 + ilen:]),
-                    ("no extras byte", sp[:10] + SL.frame(SL.CHUNK_INFO, bytes([T, M, B, K - 1])) + sp[10 + ilen:])):
+    every = SMod.splice(O.stream_encode(d, 1, bs), d, (4, M, bad_field), B)[0]
+    for name, b in (("info E + 1", sp[:10] + SMod.info_chunk((4, M, bad_field), B) + sp[10 + ilen:]), ("E = 9 everywhere", every),
+                    ("short field", sp[:10] + SMod.frame(SMod.CHUNK_INFO, bytes([T, M, B]) + field[:5]) + sp[10 + ilen:]),
+                    ("no extras byte", sp[:10] + SMod.frame(SMod.CHUNK_INFO, bytes([T, M, B, K - 1])) + sp[10 + ilen:])):
         assert O.stream_decode(b, len(d)) == d, name
-        assert SL.read_tables(b)[0] is None, name
+        assert SMod.read_tables(b)[0] is None, name
         res = _check_patterns(checker, d, b, pats, name)
         assert all(got == everything and head[:5] == (0, 0, 0, 0, 0) for head, got in res.values()), name
     # one table patched: its extras, one prefix byte; replaced by a type 2 table
-    tabs = [c for c in SL.chunks_of(sp) if c[1] == SL.CHUNK_TABLE]
+    tabs = [c for c in SMod.chunks_of(sp) if c[1] == SMod.CHUNK_TABLE]
     p0 = dict(pats)["p0"]
     skipped = next(k for k in range(1, nblk) if k not in base["p0"][1])
     off, _, tn = tabs[skipped]
     t2 = list(tables); t2[skipped] = None
-    tab2, R2 = SP.build_table(d[skipped * bs:(skipped + 1) * bs], d[(skipped + 1) * bs:(skipped + 1) * bs + 8], B, M, SP.mask_of(2, b"::::::::"))
+    tab2, R2 = SMod.build_table((2, M, b"::::::::"), d[skipped * bs:(skipped + 1) * bs], d[(skipped + 1) * bs:(skipped + 1) * bs + 8], B)
     for name, b in (("extras", sp[:off + 8] + bytes([E - 1]) + sp[off + 9:]), ("prefix byte", sp[:off + 9 + 3] + b"t" + sp[off + 9 + 4:]),
                     ("last prefix byte", sp[:off + 9 + K - 1] + b"'" + sp[off + 9 + K:]),
-                    ("type 2 table", sp[:off] + SP.table_chunk(tab2, R2, 2, M, B, b"::::::::") + sp[off + 4 + tn:])):
+                    ("type 2 table", sp[:off] + SMod.table_chunk((2, M, b"::::::::"), B, tab2, R2) + sp[off + 4 + tn:])):
         assert O.stream_decode(b, len(d)) == d, name
-        assert SL.read_tables(b)[4] == t2, name
+        assert SMod.read_tables(b)[2] == t2, name
         res = _check_patterns(checker, d, b, pats, name)
         assert res["p0"][0][3] == nblk and skipped in res["p0"][1], name
     # ... and with the right table behind the wrong one: found
-    b = sp[:off] + SP.table_chunk(tab2, R2, 2, M, B, b"::::::::") + sp[off:]
-    assert SL.read_tables(b)[4] == tables and _check_patterns(checker, d, b, pats, "both") == base
+    b = sp[:off] + SMod.table_chunk((2, M, b"::::::::"), B, tab2, R2) + sp[off:]
+    assert SMod.read_tables(b)[2] == tables and _check_patterns(checker, d, b, pats, "both") == base
 
 
 def test_the_two_models_agree_for_one_prefix_byte():
@@ -281,27 +255,25 @@ def test_the_two_models_agree_for_one_prefix_byte():
     d = synth.json_like(bs * nblk, 3).tobytes()
     for M in (1, 2, 6, 8):
         for v in (b":", b'"', b"e"):
-            field = SL.field_of(v, 0)
-            mask = SP.mask_of(2, v * 8)
+            cfg4, cfg2 = SMod.config(4, M, v, 0), SMod.config(2, M, v)
             for k in range(nblk):
                 blk = d[k * bs:(k + 1) * bs]
                 follow = d[(k + 1) * bs:(k + 1) * bs + 8] if k + 1 < nblk else None
-                assert SL.build_table(blk, follow, 16, M, field) == SP.build_table(blk, follow, 16, M, mask), (M, v, k)
+                assert SMod.build_table(cfg4, blk, follow, 16) == SMod.build_table(cfg2, blk, follow, 16), (M, v, k)
 
 
 def test_model_block_rules():
     """The indexed starts, written out: block borders, the last block's limit and a prefix that would run beyond the stream's end."""
-    f = SL.field_of(b"ab", 1)              # K = 2, M = 3, E = 1: the last block indexes the starts 0 .. n - 6
-    M = 3
-    assert SL.indexed_starts(b"zzzzzzzab", b"cdefgh", M, f) == [7]
-    assert SL.indexed_starts(b"zzzzzzzza", b"bcdefg", M, f) == [8]                 # the prefix straddles the border: it belongs to this block
-    assert SL.indexed_starts(b"bzzzzzzzz", b"zzzzzz", M, f) == []                  # ... and not to the next one
-    assert SL.indexed_starts(b"zzzabcdef", None, M, f) == [3] and SL.indexed_starts(b"zzzzabcde", None, M, f) == []
-    assert SL.indexed_starts(b"abcde", None, M, f) == [] and SL.indexed_starts(b"abcdef", None, M, f) == [0]
-    assert SL.indexed_starts(b"aaaa", b"aaaaaa", M, SL.field_of(b"aa", 1)) == [0, 1, 2, 3]
-    assert SL.indexed_starts(b"zzz\0", b"", M, SL.field_of(b"\0\0", 1)) == []      # zeros beyond the end are no prefix bytes
-    assert SL.indexed_starts(b"zzz\0", b"\0", M, SL.field_of(b"\0\0", 1)) == [3]
+    f = SMod.config(4, 3, b"ab", 1)             # K = 2, M = 3, E = 1: the last block indexes the starts 0 .. n - 6
+    assert SMod.indexed_starts(f, b"zzzzzzzab", b"cdefgh") == [7]
+    assert SMod.indexed_starts(f, b"zzzzzzzza", b"bcdefg") == [8]                 # the prefix straddles the border: it belongs to this block
+    assert SMod.indexed_starts(f, b"bzzzzzzzz", b"zzzzzz") == []                  # ... and not to the next one
+    assert SMod.indexed_starts(f, b"zzzabcdef", None) == [3] and SMod.indexed_starts(f, b"zzzzabcde", None) == []
+    assert SMod.indexed_starts(f, b"abcde", None) == [] and SMod.indexed_starts(f, b"abcdef", None) == [0]
+    assert SMod.indexed_starts(SMod.config(4, 3, b"aa", 1), b"aaaa", b"aaaaaa") == [0, 1, 2, 3]
+    assert SMod.indexed_starts(SMod.config(4, 3, b"\0\0", 1), b"zzz\0", b"") == []      # zeros beyond the end are no prefix bytes
+    assert SMod.indexed_starts(SMod.config(4, 3, b"\0\0", 1), b"zzz\0", b"\0") == [3]
     # the windows of a start near the end take zeros beyond the stream
-    h = SL.indexed_hashes(b"zzzzzzzab", b"c", 16, M, f)
-    want = SL.hash_windows(np.frombuffer(b"c\0\0\0", np.uint8), 16, M)
+    h = SMod.indexed_hashes(f, b"zzzzzzzab", b"c", 16)
+    want = SMod.hash_windows(np.frombuffer(b"c\0\0\0", np.uint8), 16, 3)
     assert h.tolist() == want.tolist()

@@ -1,10 +1,8 @@
 """mlz_dev_reader_search_many without a GPU: tools/stream_search_many_check.cpp runs the host code the call shares with its kernels
 (minlz_amd/csrc/mlz_stream_search.h: the marking form of the decoded-set rule, the layout for patterns of several lengths, the pattern
-index and the scan rule of one tile) and the Python models of the three table families say what must come out: the union of the
+index and the scan rule of one tile) and the Python model of the table types (tests/search_model.py) says what must come out: the union of the
 patterns' plans, and every pair (position, pattern) of a brute-force search over the taken chunks, in order, each once."""
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,35 +10,18 @@ import pytest
 import oracle as O
 from minlz_amd import _lib, synth
 from tests import search_cases as SC
+from tests import search_host as H
 from tests import search_long_prefix_cases as LC
-from tests import search_long_prefix_tables as SL
+from tests import search_model as SMod
 from tests import search_prefix_cases as PC
-from tests import search_prefix_tables as SP
-from tests import search_tables as ST
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tools", "stream_search_many_check.cpp")
+SRC = "stream_search_many_check.cpp"
 NO_TABLE = 0xFFFFFFFF
-
-
-def _runner(exe, env=None):
-    def run(records):
-        path = exe.parent / "cases.bin"
-        with open(path, "wb") as f:
-            for r in records:
-                f.write(r)
-        r = subprocess.run([str(exe), str(path)], capture_output=True, text=True, timeout=900, env=env)
-        os.unlink(path)
-        assert r.returncode == 0, r.stderr[-2000:]
-        return r.stdout.splitlines(), r.stderr
-    return run
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("ssm") / "ssm"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-o", str(exe), SRC], check=True)
-    run = _runner(exe)
+    run = H.build_checker(tmp_path_factory, SRC)
     return lambda records: run(records)[0]
 
 
@@ -80,28 +61,29 @@ def test_exported():
 def _configs(kind, M):
     """(name, T, M, B, field, sizes, tables, [(name, pattern)], plan(pattern), served(pattern)) over spliced 12 x 64 KiB streams, one per table family."""
     bs, nblk, tail = 64 << 10, 12, 777
-    B = ST.table_bits(bs)
+    B = SMod.table_bits(bs)
     d = getattr(synth, kind)(bs * nblk + tail, 2).tobytes()
-    sp, tables = ST.splice(O.stream_encode(d, 1, bs), d, M, B)
-    sizes = [n for n, _ in ST.data_grid(sp)]
+    cfg = SMod.config(1, M)
+    sp, tables = SMod.splice(O.stream_encode(d, 1, bs), d, cfg, B)
+    sizes = [n for n, _ in SMod.data_grid(sp)]
     use = any(t is not None for t in tables)
     yield ("type 1", 1, M, B, b"", sizes, tables, SC.patterns(d, M, bs),
-           lambda p, tables=tables, sizes=sizes, use=use: ST.plan(tables, sizes, p, M, B, use_tables=use), lambda p: len(p) >= M)
+           lambda p, cfg=cfg, tables=tables, sizes=sizes, use=use: SMod.plan(tables, sizes, p, cfg, B, use_tables=use), lambda p: len(p) >= M)
     for sname, pset in PC.SETS.items():
-        T, field = SP.field_of(pset)
+        T, field = SMod.field_of(pset)
+        cfg = (T, M, field)
         d2, pats = PC.designed(kind, bs, nblk, tail, M, pset)
-        sp, tables = SP.splice(O.stream_encode(d2, 1, bs), d2, T, M, B, field)
-        sizes = [n for n, _ in SP.data_grid(sp)]
+        sp, tables = SMod.splice(O.stream_encode(d2, 1, bs), d2, cfg, B)
+        sizes = [n for n, _ in SMod.data_grid(sp)]
         yield ("type %d %s" % (T, sname), T, M, B, field, sizes, tables, pats + SC.patterns(d2, M, bs),
-               lambda p, T=T, field=field, tables=tables, sizes=sizes: SP.plan(tables, sizes, p, T, M, B, field),
-               lambda p, T=T, field=field: bool(SP.windows(p, T, M, field)[0]) if len(p) >= M else False)
-    E = 3
-    field = SL.field_of(LC.USER, E)
-    d4, pats = LC.designed(kind, bs, nblk, tail, M, E, LC.USER)
-    sp, tables = SL.splice(O.stream_encode(d4, 1, bs), d4, M, B, field)
-    sizes = [n for n, _ in SL.data_grid(sp)]
-    yield ("type 4", 4, M, B, field, sizes, tables, pats + SC.patterns(d4, M, bs),
-           lambda p, field=field, tables=tables, sizes=sizes: SL.plan(tables, sizes, p, 4, M, B, field), lambda p, field=field: bool(SL.groups(p, M, field)[0]))
+               lambda p, cfg=cfg, tables=tables, sizes=sizes: SMod.plan(tables, sizes, p, cfg, B),
+               lambda p, cfg=cfg: bool(SMod.windows(p, cfg)[0]) if len(p) >= M else False)
+    cfg = SMod.config(4, M, LC.USER, 3)
+    d4, pats = LC.designed(kind, bs, nblk, tail, M, 3, LC.USER)
+    sp, tables = SMod.splice(O.stream_encode(d4, 1, bs), d4, cfg, B)
+    sizes = [n for n, _ in SMod.data_grid(sp)]
+    yield ("type 4", 4, M, B, cfg[2], sizes, tables, pats + SC.patterns(d4, M, bs),
+           lambda p, cfg=cfg, tables=tables, sizes=sizes: SMod.plan(tables, sizes, p, cfg, B), lambda p, cfg=cfg: bool(SMod.groups(p, cfg)[0]))
 
 
 @pytest.mark.parametrize("kind", SC.KINDS)
@@ -139,18 +121,18 @@ def test_one_short_pattern_marks_every_nonempty_chunk(checker):
     """Chunk sizes with zeros among them, real tables of a 6 x 64 KiB stream on the others."""
     bs, M = 64 << 10, 6
     d = synth.json_like(bs * 6, 3).tobytes()
-    B = ST.table_bits(bs)
-    sp, tables = ST.splice(O.stream_encode(d, 1, bs), d, M, B)
-    sizes = [n for n, _ in ST.data_grid(sp)]
+    B, cfg = SMod.table_bits(bs), SMod.config(1, M)
+    sp, tables = SMod.splice(O.stream_encode(d, 1, bs), d, cfg, B)
+    sizes = [n for n, _ in SMod.data_grid(sp)]
     sizes2 = [sizes[0], 0, sizes[1], sizes[2], 0, 0, sizes[3], sizes[4], sizes[5]]
     tables2 = [tables[0], None, tables[1], tables[2], None, None, tables[3], tables[4], tables[5]]
     absent = bytes(SC.needle(16, 99))
-    want_absent = ST.plan(tables2, sizes2, absent, M, B)
+    want_absent = SMod.plan(tables2, sizes2, absent, cfg, B)
     lines = checker([rec_plan(1, M, B, b"", sizes2, tables2, [absent]), rec_plan(1, M, B, b"", sizes2, tables2, [absent, d[100:105]]),
                      rec_plan(1, M, B, b"", sizes2, tables2, [absent, d[3 * bs - 8:3 * bs + 8]])])
     assert parse_plan(lines[0]) == (1, 0, want_absent) and len(want_absent) < 6
     assert parse_plan(lines[1]) == (1, 1, [0, 2, 3, 6, 7, 8])
-    both = sorted(set(want_absent) | set(ST.plan(tables2, sizes2, d[3 * bs - 8:3 * bs + 8], M, B)))
+    both = sorted(set(want_absent) | set(SMod.plan(tables2, sizes2, d[3 * bs - 8:3 * bs + 8], cfg, B)))
     assert parse_plan(lines[2]) == (2, 0, both) and {3, 6} <= set(both)   # (chunks 3 and 6 are neighbours in the data: the empty ones hold nothing)
 
 
@@ -188,7 +170,7 @@ def _layout_case(rng, pats, case, nck=None, big=9000):
         if L not in ok:
             c = np.concatenate([[0], np.cumsum(~taken[:len(d)])])
             ok[L] = (c[L:] - c[:len(c) - L]) == 0 if len(d) >= L else np.zeros(0, dtype=bool)
-        pairs += [(q, i) for q in ST.brute(d, p) if ok[L][q]]
+        pairs += [(q, i) for q in SMod.brute(d, p) if ok[L][q]]
     pairs.sort()
     return rec_layout(sizes, jobs, pats, d, group), pairs, (nck, lmin, lmax, group, full, len(pats))
 
@@ -250,13 +232,11 @@ def test_layout_with_mixed_lengths_finds_what_brute_force_finds(checker, layout_
 def test_layout_under_the_sanitizers(tmp_path_factory, layout_cases):
     """The check tool built once with -fsanitize=address,undefined, on the same case file: no read outside the staged bytes of a tile,
     the pattern blob or the index."""
-    exe = tmp_path_factory.mktemp("ssm_san") / "ssm_san"
     # (the runtimes linked statically: a stand-alone program that needs nothing of its environment)
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-o", str(exe), SRC],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
+    run = H.build_checker(tmp_path_factory, SRC, sanitized=True, flags=("-static-libasan", "-static-libubsan"))
+    assert run is not None, H.LINK_ERROR[SRC]
     recs, want, meta = layout_cases
-    lines, err = _runner(exe)(recs + [rec_index([b"ab", b"abc", b"b"])])
+    lines, err = run(recs + [rec_index([b"ab", b"abc", b"b"])])
     assert "ERROR" not in err and "runtime error" not in err, err[-2000:]
     _check_layout_lines(lines[:-1], want, meta)
 
