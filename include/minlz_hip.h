@@ -386,6 +386,48 @@ int64_t mlz_dev_reader_search_many(mlz_dev_reader* reader, void* stream, uint32_
                                    uint64_t* d_offsets, uint32_t* d_which, size_t cap,   /* device; both may be NULL when cap == 0 */
                                    uint64_t* stats /* host, may be NULL: 4 values */);
 
+/* mlz_dev_reader_search_records: the RECORDS of the decoded stream that hold the pattern, each once, in stream order, packed into d_dst — what
+ *   `mz search pattern file.mz` prints, and with rec_cap == 0 and dst_cap == 0 what `-c` counts.  A record is a maximal run of decoded bytes that
+ *   holds no `delimiter`; the delimiter itself belongs to no record.  The call looks at most W = max_reach bytes to either side of an occurrence
+ *   (0 = 65536; above MLZ_RECORDS_MAX_REACH: -MLZ_ERR_ARG).  With size = the decoded size and L = pattern_len, an occurrence at p (what
+ *   mlz_dev_reader_search reports) has the window lo = max(0, p - W), hi = min(size, p + L + W), and
+ *     s(p) = the position behind the last delimiter in [lo, p), or lo when there is none (then, when lo > 0, the record is CUT LEFT);
+ *     e(p) = the position of the first delimiter in [p + L, hi), or hi when there is none (then, when hi < size, the record is CUT RIGHT).
+ *   Occurrences are taken in ascending order; occurrence i opens a record when i == 0 or s(p_i) != s(p_i-1), else it belongs to the record of the
+ *   occurrence before it.  A record is [s, e) with s of the occurrence that opens it and e of its last occurrence (e ascends with p).  When no
+ *   record is longer than W this is exactly "every line that contains the pattern, once, in stream order".  Records longer than W come out cut
+ *   and flagged, and two cut records may overlap: that is the price of a bounded reach.
+ *   Returns the number of records R (it may exceed rec_cap).  The first k records are written, whole: k is the largest value with k <= rec_cap
+ *   and the first k records' bytes summing to at most dst_cap.  d_rec_off[0 .. k): each record's start in the decoded stream; d_rec_start[0 .. k]
+ *   (may be NULL): each record's start in d_dst, d_rec_start[k] = the bytes written; d_rec_flags[0 .. k) (may be NULL): bit 0 = cut left, bit 1 =
+ *   cut right; d_dst[0, d_rec_start[k]): the records' bytes.  Nothing beyond these is written and no record is written in part.  All four are
+ *   device memory of the handle's device; d_dst may be NULL when dst_cap == 0, d_rec_off when rec_cap == 0.
+ *   totals (host, may be NULL): R, the bytes of all R records, the occurrences, the records with a flag.
+ *   `pattern` is host memory, pattern_len 1 .. 256.  -MLZ_ERR_ARG, each decided before anything is launched, nothing written: the argument
+ *   errors of mlz_dev_reader_search; a pattern that contains the delimiter (a line search cannot match across lines); max_reach above the
+ *   maximum; d_dst NULL with dst_cap > 0 or d_rec_off NULL with rec_cap > 0; one of d_dst (dst_cap > 0), d_rec_off (rec_cap > 0), d_rec_start
+ *   (not NULL) and d_rec_flags (not NULL, rec_cap > 0) that is not on the handle's device.  Found later: more than 2^31 occurrences (-MLZ_ERR_ARG).
+ *   Two phases under one lock.  The search phase is mlz_dev_reader_search's plan, decode and scan with the same pattern and flags
+ *   (MLZ_STREAM_IGNORE_CRC, MLZ_SEARCH_NO_TABLES; an attached sidecar is used): stats and mlz_get_counter 10 / 11 describe it exactly as there.
+ *   Zero occurrences returns 0 behind it and launches nothing more.  The read phase is mlz_dev_reader_read_device over the occurrences' windows,
+ *   merged where they touch or overlap: every chunk a window touches is decoded once, with its CRC — also a chunk that the tables pruned in the
+ *   search phase and a record reaches into; mlz_get_counter 7 / 8 / 9 describe it.  Kernels then find the bounds (a wavefront per occurrence),
+ *   number the records, cut at the caps and copy; a 16-byte and a 48-byte header visit the host, nothing per occurrence or per record does.
+ *   Decode and CRC errors: the first failing decoded chunk of the search phase, else of the read phase; the arrays' contents are then
+ *   unspecified, but never beyond their sizes.  Synchronous; `stream` as for mlz_dev_reader_read.
+ *   Workspace, grow-only and part of mlz_get_counter 4: about 100 bytes per occurrence, and a window buffer of the merged windows' bytes —
+ *   at most min(decoded size, occurrences * (2 W + L)). */
+#define MLZ_RECORDS_MAX_REACH (1u << 20)
+int64_t mlz_dev_reader_search_records(mlz_dev_reader* reader, void* stream, uint32_t flags,
+                                      const uint8_t* pattern, size_t pattern_len,   /* host, 1 .. 256 */
+                                      uint8_t delimiter, uint32_t max_reach,        /* 0 = 65536; 1 .. MLZ_RECORDS_MAX_REACH */
+                                      uint8_t* d_dst, size_t dst_cap,               /* device: the records' bytes, packed */
+                                      uint64_t* d_rec_off,                          /* device, rec_cap values: where each record starts in the decoded stream */
+                                      uint64_t* d_rec_start,                        /* device, rec_cap + 1 values: where each record starts in d_dst; may be NULL */
+                                      uint8_t* d_rec_flags,                         /* device, rec_cap values; may be NULL */
+                                      size_t rec_cap,
+                                      uint64_t* totals /* host, may be NULL: 4 values */, uint64_t* stats /* host, may be NULL: as mlz_dev_reader_search */);
+
 /* Sidecar search indexes (SEARCH.md "Sidecar Streams", SPEC_SEARCH.md 1.1 and 2.3; the reference's BuildSidecar and SidecarSearcher): search tables
  * for a stream that exists already, in a separate valid MinLZ stream.  The main stream is never touched, so this serves ANY stream in HBM: the
  * reference Writer's (whose tables are compressed, 0x46), old ones, mlz_stream_encode's and the Python Writer's, stored blocks.  A sidecar carries up to
@@ -488,12 +530,12 @@ const char* mlz_timer_name(int idx);
  * which = 5: decode calls whose general blocks fell back to the tile chain because the general pass's buffers could not be allocated.
  * which = 6: workgroups per block (1, 2 or 4) the general-block pass of the last decode call settled with (the largest over the
  *            groups of the call, as for 2); 0 = it had no general block.
- * which = 7 / 8: the plan of the context's last mlz_dev_reader_read or mlz_dev_reader_read_device: 7 = chunks it decoded or copied (each touched chunk counts once), 8 = decoded bytes
+ * which = 7 / 8: the plan of the context's last mlz_dev_reader_read or mlz_dev_reader_read_device (or the read phase of mlz_dev_reader_search_records): 7 = chunks it decoded or copied (each touched chunk counts once), 8 = decoded bytes
  *            it put into the scratch (chunks decoded straight into d_dst and stored chunks: none).
  * which = 9: bytes of plan data that crossed between host and device, both directions together, during the context's last mlz_dev_reader_read_device:
  *            32 + 32 per touched chunk (32 alone for a refused call or one that touches nothing).  Not counted: the results of the chunks' decode and CRC
  *            (12 bytes per chunk, as in every stream decode) and the one-time upload of a handle's chunk table.
- * which = 10 / 11: the context's last mlz_dev_reader_search: 10 = chunks it decoded or copied, 11 = chunks with a usable search table (0 when the call
+ * which = 10 / 11: the context's last mlz_dev_reader_search, mlz_dev_reader_search_many or search phase of mlz_dev_reader_search_records: 10 = chunks it decoded or copied, 11 = chunks with a usable search table (0 when the call
  *            used none: MLZ_SEARCH_NO_TABLES, no info chunk, a pattern shorter than M). */
 int64_t mlz_get_counter(mlz_ctx* ctx, int which);
 

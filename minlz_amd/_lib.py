@@ -23,6 +23,7 @@ SYMBOLS = [
     "mlz_stream_bound_tables", "mlz_stream_encode_gather_device_tables",
     "mlz_stream_bound_long_prefix", "mlz_stream_encode_gather_device_long_prefix",
     "mlz_dev_reader_sidecar_bound", "mlz_dev_reader_build_sidecar", "mlz_dev_reader_attach_sidecar",
+    "mlz_dev_reader_search_records",
 ]
 
 
@@ -115,5 +116,7 @@ def lib():
     L.mlz_dev_reader_sidecar_bound.argtypes = [vp, C.POINTER(SearchConfig), i32]; L.mlz_dev_reader_sidecar_bound.restype = i64
     L.mlz_dev_reader_build_sidecar.argtypes = [vp, vp, u32, C.POINTER(SearchConfig), i32, vp, sz]; L.mlz_dev_reader_build_sidecar.restype = i64
     L.mlz_dev_reader_attach_sidecar.argtypes = [vp, vp, u32, vp, sz]; L.mlz_dev_reader_attach_sidecar.restype = i64
+    L.mlz_dev_reader_search_records.argtypes = [vp, vp, u32, vp, sz, C.c_uint8, u32, vp, sz, vp, vp, vp, sz, C.POINTER(u64), C.POINTER(u64)]
+    L.mlz_dev_reader_search_records.restype = i64
     _lib = L
     return L

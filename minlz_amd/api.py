@@ -291,6 +291,29 @@ class DeviceReader:
             _raise(r, self.ctx)
         return int(r), tuple(int(v) for v in stats)
 
+    def search_records(self, pattern, delimiter, d_dst, dst_cap, d_rec_off, d_rec_start, d_rec_flags, rec_cap, max_reach=0, ignore_crc=False, no_tables=False, stream=None):
+        """mlz_dev_reader_search_records: the records (maximal runs without the byte `delimiter`) that hold `pattern` (1 .. 256 bytes without
+        the delimiter), each once, in stream order.  d_dst: device address of room for dst_cap bytes (None with dst_cap == 0), which
+        receives the first k records' bytes, packed; d_rec_off: room for rec_cap uint64 (None with rec_cap == 0), each record's start in
+        the decoded stream; d_rec_start: room for rec_cap + 1 uint64 or None, each record's start in d_dst and the bytes written;
+        d_rec_flags: room for rec_cap bytes or None, bit 0 = cut left, bit 1 = cut right.  k: the most records that both caps hold whole.
+        max_reach: how far the call looks to either side of an occurrence (0 = 65536, at most 2^20); longer records come out cut.
+        -> (records, (records, bytes of all records, occurrences, records with a flag), (data chunks, chunks decoded or copied by the
+        search phase, chunks with a usable search table))."""
+        if not self.handle:
+            raise ValueError("DeviceReader is closed")
+        p = bytes(pattern)
+        d = bytes(delimiter) if not isinstance(delimiter, int) else bytes([delimiter])
+        if len(d) != 1:
+            raise ValueError("search_records: a delimiter of one byte")
+        totals, stats = (C.c_uint64 * 4)(), (C.c_uint64 * 4)()
+        flags = (STREAM_IGNORE_CRC if ignore_crc else 0) | (SEARCH_NO_TABLES if no_tables else 0)
+        r = _lib.lib().mlz_dev_reader_search_records(self.handle, stream, flags, p, len(p), d[0], max_reach, d_dst, dst_cap, d_rec_off, d_rec_start, d_rec_flags, rec_cap,
+                                                     totals, stats)
+        if r < 0:
+            _raise(r, self.ctx)
+        return int(r), tuple(int(v) for v in totals), (int(stats[0]), int(stats[1]), int(stats[2]))
+
     @staticmethod
     def _configs(cfgs):
         cfgs = list(cfgs)

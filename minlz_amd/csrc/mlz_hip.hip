@@ -146,6 +146,7 @@ struct mlz_ctx {
     DevBuf d_walk, d_walk_tab;   // the device-resident Reader's chunk walk: exit tables (8 bytes per stream byte) and the chunk table
     DevBuf d_range;              // the device-resident ReadSeeker: where partly wanted chunks of a group are decoded (a group plus one block at the most)
     DevBuf d_rplan;              // mlz_dev_reader_read_device: the plan kernels' workspace (16 bytes per range, 28 per chunk of the stream)
+    DevBuf d_records, d_rwin;    // mlz_dev_reader_search_records: what lives across its read phase (the occurrences, windows and records: about 100 bytes per occurrence), and the merged windows' bytes (at most the decoded size)
     uint64_t range_plan_host = 0;   // plan bytes that crossed between host and device in the last mlz_dev_reader_read_device (mlz_get_counter 9)
     uint64_t search_chunks = 0, search_tables = 0;  // the last mlz_dev_reader_search: chunks decoded or copied, chunks with a usable table (mlz_get_counter 10 / 11)
     uint64_t range_chunks = 0, range_scratch = 0;   // the last range read: chunks decoded or copied, decoded bytes that went through d_range (mlz_get_counter 7 / 8)
@@ -183,7 +184,7 @@ struct mlz_ctx {
     // Every DevBuf above, once, by side: 0 = what mlz_get_counter 3 sums (encode), 1 = counter 4 (decode), 2 = the rest; mlz_destroy frees all three.  A buffer added to the struct is added here.
     std::vector<DevBuf*> bufs(int side) {
         if (side == 0) return {&d_scratch, &d_tile_size, &d_tile_out, &d_flags, &d_far, &d_recs, &d_piece_cnt, &d_farbin, &d_stab};
-        if (side == 1) return {&d_dec, &d_idx, &d_walk, &d_walk_tab, &d_range, &d_rplan};
+        if (side == 1) return {&d_dec, &d_idx, &d_walk, &d_walk_tab, &d_range, &d_rplan, &d_records, &d_rwin};
         return {&d_blocks_k[0], &d_blocks_k[1], &d_tile_block_k[0], &d_tile_block_k[1], &d_seg_block_k[0], &d_seg_block_k[1], &d_place, &d_gen_acc, &d_in, &d_out, &d_len, &d_crc, &d_crc_tabs, &d_crc_tiles, &d_prof};
     }
     // A ring of event pairs per timer, resolved kTimerRing uses later (long complete by then), so reading the clock never stalls the caller and
@@ -1310,3 +1311,4 @@ int mlz_debug_idxprof(unsigned long long* out) {
 #include "mlz_stream_search.hip.inc"
 #include "mlz_stream_search_many.hip.inc"
 #include "mlz_stream_sidecar.hip.inc"
+#include "mlz_stream_records.hip.inc"

@@ -12,7 +12,8 @@
 // the set of chunks to decode.  The search for many patterns plans through the same function.  stream_run_chunk_jobs decodes
 // exactly those into the scratch, chunks that are neighbours in the stream side by side, and search_scan_kernel marks the occurrences of every
 // run in a bitmap (one bit per decoded byte of the set) and counts them per tile.  search_prefix_kernel's scan over the tile counts and search_write_kernel then
-// put the smallest `cap` positions out in ascending order.
+// put the smallest `cap` positions out in ascending order.  The call's body ends at the prefix kernel (dev_reader_search_scan_locked); the write and
+// the total's way home are steps of their own, so that the search for records (mlz_stream_records.hip.inc) can size its buffer by the total first.
 
 namespace mlz {
 
@@ -404,7 +405,21 @@ void search_begin(mlz_dev_reader* rd, uint64_t* stats) {
     if (stats) { stats[0] = rd->chunks.size(); stats[1] = stats[2] = stats[3] = 0; }
 }
 
-int64_t dev_reader_search_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* pattern, uint32_t L, uint64_t* d_offsets, uint64_t cap, uint64_t* stats) {
+// What a search leaves in the workspace (c->d_rplan) behind its count pass and its prefix scan, until the workspace is carved anew: the tiles,
+// their bitmaps and prefixes and the total, still on its way (nt == 0: nothing was scanned and the total is 0).  search_found_write puts the
+// smallest `cap` positions out; a caller that sizes its buffer by the total fetches *d_total first.
+struct SearchFound {
+    size_t nt = 0;
+    const mlz::SearchTile* d_tiles = nullptr;
+    const uint64_t *d_masks = nullptr, *d_prefix = nullptr, *d_total = nullptr;
+};
+
+void search_found_write(hipStream_t sm, const SearchFound& f, uint64_t cap, uint64_t* d_offsets) {
+    if (cap && f.nt) hipLaunchKernelGGL(mlz::search_write_kernel, dim3(uint32_t(f.nt)), dim3(mlz::kSearchTileWords), 0, sm, f.d_tiles, f.d_masks, f.d_prefix, cap, d_offsets);
+}
+
+// The plan, the decode and the scan of a search for one pattern, up to the prefix kernel: everything but the positions and the total's way home.
+int64_t dev_reader_search_scan_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* pattern, uint32_t L, uint64_t* stats, SearchFound* found) {
     mlz_ctx* c = rd->ctx;
     const size_t nck = rd->chunks.size();
     const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0;
@@ -449,9 +464,24 @@ int64_t dev_reader_search_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t fl
     if (r < 0) return r;
     if (nt == 0) return 0;
     hipLaunchKernelGGL(mlz::search_prefix_kernel, dim3(1), dim3(1024), 0, sm, d_counts, 0u, uint32_t(nt), d_prefix, d_total);   // (d_total: cleared above)
-    if (cap) hipLaunchKernelGGL(mlz::search_write_kernel, dim3(uint32_t(nt)), dim3(mlz::kSearchTileWords), 0, sm, d_tiles, d_masks, d_prefix, cap, d_offsets);
-    if ((e = fetch(c, sm, c->pinned2, d_total, 8))) return e;
+    *found = SearchFound{nt, d_tiles, d_masks, d_prefix, d_total};
+    return 0;
+}
+
+// The total of a search whose scan is enqueued (SearchFound), waited for
+int64_t search_found_total(mlz_ctx* c, hipStream_t sm, const SearchFound& f) {
+    if (f.nt == 0) return 0;
+    const int e = fetch(c, sm, c->pinned2, f.d_total, 8);
+    if (e) return e;
     return int64_t(*static_cast<const uint64_t*>(c->pinned2));
+}
+
+int64_t dev_reader_search_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* pattern, uint32_t L, uint64_t* d_offsets, uint64_t cap, uint64_t* stats) {
+    SearchFound found;
+    const int64_t r = dev_reader_search_scan_locked(rd, sm, flags, pattern, L, stats, &found);
+    if (r < 0) return r;
+    search_found_write(sm, found, cap, d_offsets);
+    return search_found_total(rd->ctx, sm, found);
 }
 
 }  // namespace

@@ -250,6 +250,25 @@ class DeviceStream:
         k = min(total, max_results)
         return pos[:k], which[:k], counts[:len(pats)], total
 
+    def search_records(self, pattern, delimiter=b"\n", max_records=1024, max_bytes=1 << 20, max_reach=0, ignore_crc=False, no_tables=False):
+        """The records (lines, for the default delimiter) of the decoded stream that hold `pattern`, each once, in stream order ->
+        (total_records, data, rec_off, rec_start, flags, totals): the first k records' bytes back to back (uint8), where each starts in the
+        decoded stream (int64, k values) and in `data` (int64, k + 1 values: the last is data's size), its flags (uint8: 1 = cut left,
+        2 = cut right — records longer than max_reach, 0 = 65536) — tensors on the stream's device, trimmed to what was written: k is
+        the most records that max_records and max_bytes hold whole — and totals = (records, bytes of all records, occurrences, flagged
+        records).  max_records = max_bytes = 0 counts."""
+        dev = self.t.device
+        data = torch.empty(max(max_bytes, 1), dtype=torch.uint8, device=dev)
+        rec_off = torch.empty(max(max_records, 1), dtype=torch.int64, device=dev)
+        rec_start = torch.zeros(max_records + 1, dtype=torch.int64, device=dev)
+        flags = torch.empty(max(max_records, 1), dtype=torch.uint8, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        total, totals, _ = self.reader.search_records(pattern, delimiter, data.data_ptr() if max_bytes else None, max_bytes, rec_off.data_ptr() if max_records else None,
+                                                      rec_start.data_ptr(), flags.data_ptr() if max_records else None, max_records, max_reach=max_reach,
+                                                      ignore_crc=ignore_crc, no_tables=no_tables, stream=st)
+        k = int((rec_start[1:] != 0).sum())   # (no record is empty: the starts behind the first are positive as far as they were written)
+        return total, data[:int(rec_start[k])], rec_off[:k], rec_start[:k + 1], flags[:k], totals
+
     def build_sidecar(self, cfgs, ignore_crc=False):
         """A sidecar search index of this stream for 1 .. 4 configurations (api.search_config): search tables for every block, whoever
         wrote the stream, in a separate .mz stream -> a new uint8 tensor on the stream's device."""
