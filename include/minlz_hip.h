@@ -428,6 +428,52 @@ int64_t mlz_dev_reader_search_records(mlz_dev_reader* reader, void* stream, uint
                                       size_t rec_cap,
                                       uint64_t* totals /* host, may be NULL: 4 values */, uint64_t* stats /* host, may be NULL: as mlz_dev_reader_search */);
 
+/* The record index: read records of a stream in HBM by NUMBER, and number positions by record (`mz search -n`, `sed -n 'a,bp'`).  With size = the
+ * decoded size and D[0] < D[1] < ... < D[k-1] the positions of all decoded bytes equal to `delimiter`, the stream has N records: N = k + 1 when
+ * size > 0 and the last byte is no delimiter (k == 0 included), else N = k.  Record r (0-based) is [start(r), end(r)): start(0) = 0,
+ * start(r) = D[r-1] + 1; end(r) = D[r] for r < k, end(k) = size.  Empty records (doubled delimiters) exist and are counted; the delimiter
+ * belongs to no record: data.split(delimiter) with one trailing empty piece dropped, what `grep -n` counts.  A record that
+ * mlz_dev_reader_search_records returns without a left cut starts at some start(r).  The record number of a position p < size is the count of
+ * D[j] < p: a delimiter's own position has the number of the record it ends.  All calls are synchronous and run under the context's lock;
+ * `stream` and MLZ_STREAM_IGNORE_CRC as for mlz_dev_reader_read.
+ *
+ * mlz_dev_reader_index_records: builds the index for `delimiter` and returns N.  Every data chunk with bytes is decoded exactly once, in groups of
+ *   about 64 MiB through the ReadSeeker's scratch (a group's chunks side by side; stored chunks are copied there), and its CRC checked unless the
+ *   flag says otherwise.  Per group two passes over the decoded bytes (count per 64 KiB tile, then emit) and 8 bytes that visit the host.  info
+ *   (host, may be NULL): N, k, the bytes of index the handle now holds, the chunks this call decoded.  The index is 8 bytes per delimiter (allocated
+ *   exactly for a stream of one group, else grown geometrically: at most twice that) in device memory that the handle owns: freed by
+ *   mlz_dev_reader_close, not part of the workspace that mlz_get_counter 4 reports, kept until the handle closes or another delimiter is indexed.  A
+ *   second call with the same delimiter returns N and decodes nothing (info[3] == 0); a call with another delimiter replaces the index.  On a decode
+ *   or CRC error the first failing chunk's error in stream order is returned, as by mlz_dev_reader_read, and the handle keeps whatever index it
+ *   had; an allocation failure returns -MLZ_ERR_HIP.  An empty stream indexes to N = 0.
+ * mlz_dev_reader_record_count: N, or -MLZ_ERR_ARG when the handle has no index.  Every call below returns -MLZ_ERR_ARG without an index too, before
+ *   anything is launched.
+ * mlz_dev_reader_record_spans: d_off[i] = start(d_idx[i]), d_len[i] = end - start for every i < n; all three arrays are device memory of the handle's
+ *   device.  Returns the sum of the lengths (what a destination must hold).  Indices may repeat and come in any order.  An index >= N: -MLZ_ERR_ARG,
+ *   found by the kernel; the two arrays are then unspecified, never beyond n entries.  Also -MLZ_ERR_ARG: n > 2^31, a pointer that is not on the
+ *   handle's device.  n == 0 returns 0 and launches nothing.  16 bytes visit the host.
+ * mlz_dev_reader_read_records: the records d_idx[0 .. n) packed into d_dst in the order given; d_starts (may be NULL) receives n + 1 values, where each
+ *   record starts in d_dst and the total.  The spans go into context workspace (16 bytes per record, part of mlz_get_counter 4) and
+ *   mlz_dev_reader_read_device's plan reads them: exactly the touched chunks are decoded, each once, with its CRC (mlz_get_counter 7 / 8 / 9), and
+ *   everything else is that call's contract.  An index >= N returns -MLZ_ERR_ARG, a total above dst_cap -MLZ_ERR_DST_TOO_SMALL; both are decided
+ *   before anything is written to d_dst or d_starts.  n == 0 returns 0 and writes nothing.  Returns the bytes written.
+ * mlz_dev_reader_record_numbers: d_no[i] = the record number of position d_pos[i], or UINT64_MAX for d_pos[i] >= size; returns how many positions
+ *   were < size.  A binary search in the index, a lane per position.  Fed with d_rec_off of mlz_dev_reader_search_records it gives the line
+ *   numbers (0-based) of the matching lines.
+ * mlz_dev_reader_record_range: host convenience for "records first .. first + count - 1 as ONE range": *off = start(first), *len = end(first + count
+ *   - 1) - start(first), the inner delimiters included; count == 0 gives length 0 (at start(first), or at size for first == N).  first + count > N:
+ *   -MLZ_ERR_ARG.  Two table entries visit the host; the caller reads the range with mlz_dev_reader_read.  Returns 0.
+ * Out of scope: delimiters of more than one byte; an index persisted into a stream or a sidecar; an index built while the Writer encodes; record
+ *   numbers as an output of mlz_dev_reader_search_records itself (its signature stays). */
+int64_t mlz_dev_reader_index_records(mlz_dev_reader* reader, void* stream, uint32_t flags, uint8_t delimiter,
+                                     uint64_t* info /* host, may be NULL: 4 values */);
+int64_t mlz_dev_reader_record_count(const mlz_dev_reader* reader);
+int64_t mlz_dev_reader_record_spans(mlz_dev_reader* reader, void* stream, const uint64_t* d_idx, size_t n, uint64_t* d_off, uint64_t* d_len);
+int64_t mlz_dev_reader_read_records(mlz_dev_reader* reader, void* stream, uint32_t flags, const uint64_t* d_idx, size_t n, uint8_t* d_dst, size_t dst_cap,
+                                    uint64_t* d_starts /* may be NULL */);
+int64_t mlz_dev_reader_record_numbers(mlz_dev_reader* reader, void* stream, const uint64_t* d_pos, size_t n, uint64_t* d_no);
+int64_t mlz_dev_reader_record_range(mlz_dev_reader* reader, uint64_t first, uint64_t count, uint64_t* off, uint64_t* len);
+
 /* Sidecar search indexes (SEARCH.md "Sidecar Streams", SPEC_SEARCH.md 1.1 and 2.3; the reference's BuildSidecar and SidecarSearcher): search tables
  * for a stream that exists already, in a separate valid MinLZ stream.  The main stream is never touched, so this serves ANY stream in HBM: the
  * reference Writer's (whose tables are compressed, 0x46), old ones, mlz_stream_encode's and the Python Writer's, stored blocks.  A sidecar carries up to

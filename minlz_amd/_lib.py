@@ -24,6 +24,8 @@ SYMBOLS = [
     "mlz_stream_bound_long_prefix", "mlz_stream_encode_gather_device_long_prefix",
     "mlz_dev_reader_sidecar_bound", "mlz_dev_reader_build_sidecar", "mlz_dev_reader_attach_sidecar",
     "mlz_dev_reader_search_records",
+    "mlz_dev_reader_index_records", "mlz_dev_reader_record_count", "mlz_dev_reader_record_spans", "mlz_dev_reader_read_records",
+    "mlz_dev_reader_record_numbers", "mlz_dev_reader_record_range",
 ]
 
 
@@ -118,5 +120,11 @@ def lib():
     L.mlz_dev_reader_attach_sidecar.argtypes = [vp, vp, u32, vp, sz]; L.mlz_dev_reader_attach_sidecar.restype = i64
     L.mlz_dev_reader_search_records.argtypes = [vp, vp, u32, vp, sz, C.c_uint8, u32, vp, sz, vp, vp, vp, sz, C.POINTER(u64), C.POINTER(u64)]
     L.mlz_dev_reader_search_records.restype = i64
+    L.mlz_dev_reader_index_records.argtypes = [vp, vp, u32, C.c_uint8, C.POINTER(u64)]; L.mlz_dev_reader_index_records.restype = i64
+    L.mlz_dev_reader_record_count.argtypes = [vp]; L.mlz_dev_reader_record_count.restype = i64
+    L.mlz_dev_reader_record_spans.argtypes = [vp, vp, vp, sz, vp, vp]; L.mlz_dev_reader_record_spans.restype = i64
+    L.mlz_dev_reader_read_records.argtypes = [vp, vp, u32, vp, sz, vp, sz, vp]; L.mlz_dev_reader_read_records.restype = i64
+    L.mlz_dev_reader_record_numbers.argtypes = [vp, vp, vp, sz, vp]; L.mlz_dev_reader_record_numbers.restype = i64
+    L.mlz_dev_reader_record_range.argtypes = [vp, u64, u64, C.POINTER(u64), C.POINTER(u64)]; L.mlz_dev_reader_record_range.restype = i64
     _lib = L
     return L

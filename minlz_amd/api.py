@@ -314,6 +314,77 @@ class DeviceReader:
             _raise(r, self.ctx)
         return int(r), tuple(int(v) for v in totals), (int(stats[0]), int(stats[1]), int(stats[2]))
 
+    def index_records(self, delimiter=b"\n", ignore_crc=False, stream=None):
+        """mlz_dev_reader_index_records: builds the record index for the one-byte `delimiter` — the positions of all delimiters of the
+        decoded stream, 8 bytes each in device memory the handle owns — by one decode of the stream.  Record r is the bytes between
+        delimiter r - 1 and delimiter r; empty records count; a stream that ends without a delimiter has one more record.  The same
+        delimiter again costs nothing; another one replaces the index.
+        -> (N, (N, delimiters, bytes of index held, chunks this call decoded))."""
+        if not self.handle:
+            raise ValueError("DeviceReader is closed")
+        d = bytes(delimiter) if not isinstance(delimiter, int) else bytes([delimiter])
+        if len(d) != 1:
+            raise ValueError("index_records: a delimiter of one byte")
+        info = (C.c_uint64 * 4)()
+        r = _lib.lib().mlz_dev_reader_index_records(self.handle, stream, STREAM_IGNORE_CRC if ignore_crc else 0, d[0], info)
+        if r < 0:
+            _raise(r, self.ctx)
+        return int(r), tuple(int(v) for v in info)
+
+    def record_count(self):
+        """mlz_dev_reader_record_count: the records of the indexed stream; raises without an index."""
+        if not self.handle:
+            raise ValueError("DeviceReader is closed")
+        r = _lib.lib().mlz_dev_reader_record_count(self.handle)
+        if r < 0:
+            _raise(r, self.ctx)
+        return int(r)
+
+    def record_spans(self, d_idx, n, d_off, d_len, stream=None):
+        """mlz_dev_reader_record_spans.  d_idx: device address of n uint64 record numbers (any order, repeats allowed); d_off, d_len:
+        device addresses of room for n uint64 each, which receive every record's first byte in the decoded stream and its length.
+        -> the sum of the lengths.  A number >= record_count() raises."""
+        if not self.handle:
+            raise ValueError("DeviceReader is closed")
+        r = _lib.lib().mlz_dev_reader_record_spans(self.handle, stream, d_idx, n, d_off, d_len)
+        if r < 0:
+            _raise(r, self.ctx)
+        return int(r)
+
+    def read_records(self, d_idx, n, d_dst, dst_cap, d_starts=None, ignore_crc=False, stream=None):
+        """mlz_dev_reader_read_records: the records d_idx[0 .. n) (device address of uint64 record numbers) packed into d_dst in the order
+        given; d_starts (device address of n + 1 uint64, or None) receives where each record starts in d_dst and the total.  Only the
+        chunks the records touch are decoded, each once.  -> the bytes written.  A number >= record_count() or a total above dst_cap
+        raises, and nothing has been written then."""
+        if not self.handle:
+            raise ValueError("DeviceReader is closed")
+        r = _lib.lib().mlz_dev_reader_read_records(self.handle, stream, STREAM_IGNORE_CRC if ignore_crc else 0, d_idx, n, d_dst, dst_cap, d_starts)
+        if r < 0:
+            _raise(r, self.ctx)
+        return int(r)
+
+    def record_numbers(self, d_pos, n, d_no, stream=None):
+        """mlz_dev_reader_record_numbers.  d_pos: device address of n uint64 positions of the decoded stream; d_no: room for n uint64, which
+        receive each position's record number (0-based; a delimiter has the number of the record it ends; 2^64 - 1 for a position at or
+        beyond the size).  -> how many positions lie inside the stream."""
+        if not self.handle:
+            raise ValueError("DeviceReader is closed")
+        r = _lib.lib().mlz_dev_reader_record_numbers(self.handle, stream, d_pos, n, d_no)
+        if r < 0:
+            _raise(r, self.ctx)
+        return int(r)
+
+    def record_range(self, first, count):
+        """mlz_dev_reader_record_range: records first .. first + count - 1 as one byte range, the delimiters between them included
+        -> (off, len), to be read with read().  first + count > record_count() raises."""
+        if not self.handle:
+            raise ValueError("DeviceReader is closed")
+        off, ln = C.c_uint64(), C.c_uint64()
+        r = _lib.lib().mlz_dev_reader_record_range(self.handle, first, count, C.byref(off), C.byref(ln))
+        if r < 0:
+            _raise(r, self.ctx)
+        return int(off.value), int(ln.value)
+
     @staticmethod
     def _configs(cfgs):
         cfgs = list(cfgs)

@@ -77,6 +77,12 @@ struct mlz_dev_reader {
         std::vector<mlz::SearchTab> tabs;
     } search[2], side;
     bool side_on = false;
+    // mlz_dev_reader_index_records: the positions of all delimiters of the decoded stream (8 bytes each; device memory the handle owns, not
+    // part of the context's workspace), kept until the handle closes or another delimiter is indexed
+    void* d_index = nullptr;
+    uint64_t index_cap = 0, index_k = 0, index_n = 0;   // entries allocated, delimiters, records
+    bool index_ready = false;
+    uint8_t index_delim = 0;
 };
 
 namespace {
@@ -179,10 +185,10 @@ int64_t mlz_dev_reader_read(mlz_dev_reader* rd, void* stream, uint32_t flags, co
 }
 
 void mlz_dev_reader_close(mlz_dev_reader* rd) {
-    if (rd && (rd->d_chunks || rd->search[0].d_tabs || rd->search[1].d_tabs || rd->side.d_tabs)) {
+    if (rd && (rd->d_chunks || rd->search[0].d_tabs || rd->search[1].d_tabs || rd->side.d_tabs || rd->d_index)) {
         std::lock_guard<std::mutex> lk(rd->ctx->mu);
         if (hipSetDevice(rd->ctx->device) == hipSuccess)
-            for (void* p : {rd->d_chunks, rd->search[0].d_tabs, rd->search[1].d_tabs, rd->side.d_tabs}) if (p) (void)hipFree(p);
+            for (void* p : {rd->d_chunks, rd->search[0].d_tabs, rd->search[1].d_tabs, rd->side.d_tabs, rd->d_index}) if (p) (void)hipFree(p);
     }
     delete rd;
 }

@@ -269,6 +269,54 @@ class DeviceStream:
         k = int((rec_start[1:] != 0).sum())   # (no record is empty: the starts behind the first are positive as far as they were written)
         return total, data[:int(rec_start[k])], rec_off[:k], rec_start[:k + 1], flags[:k], totals
 
+    def index_records(self, delimiter=b"\n", ignore_crc=False):
+        """Builds the record index of the decoded stream for the one-byte `delimiter` (one decode of the stream; 8 bytes per delimiter
+        stay on the device until close() or another delimiter) -> the number of records N.  read_records, line_numbers and
+        read_record_range need it."""
+        st = torch.cuda.current_stream(self.t.device).cuda_stream
+        return self.reader.index_records(delimiter, ignore_crc=ignore_crc, stream=st)[0]
+
+    def _items(self, a, what):
+        if not torch.is_tensor(a) or a.dtype not in (torch.int64, torch.uint64) or a.dim() != 1 or not a.is_contiguous() or a.device != self.t.device:
+            raise ValueError(what + ": a contiguous 1-d int64 or uint64 tensor on the stream's device")
+        return a
+
+    def read_records(self, idx, ignore_crc=False):
+        """The records with the numbers `idx` (int64 or uint64 tensor on the stream's device; any order, repeats allowed), back to back in
+        the order given -> (a new uint8 tensor, the n + 1 places where the records start in it and its size: int64).  The one thing that
+        visits the host is the records' total size, which sizes the output."""
+        idx = self._items(idx, "read_records")
+        dev, n = self.t.device, idx.numel()
+        starts = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        if n == 0:
+            self.reader.record_count()   # (without an index this raises, as every call on it does)
+            return torch.empty(0, dtype=torch.uint8, device=dev), starts
+        st = torch.cuda.current_stream(dev).cuda_stream
+        spans = torch.empty(2 * n, dtype=torch.int64, device=dev)
+        total = self.reader.record_spans(idx.data_ptr(), n, spans.data_ptr(), spans[n:].data_ptr(), stream=st)
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        got = self.reader.read_records(idx.data_ptr(), n, out.data_ptr(), total, d_starts=starts.data_ptr(), ignore_crc=ignore_crc, stream=st)
+        return out[:got], starts
+
+    def line_numbers(self, positions):
+        """The record number (0-based) of every position of the decoded stream in `positions` (int64 or uint64 tensor on the stream's
+        device) -> an int64 tensor; -1 for a position at or beyond the size.  With search_records' rec_off: the line numbers of the
+        matching lines."""
+        positions = self._items(positions, "line_numbers")
+        n = positions.numel()
+        out = torch.empty(n, dtype=torch.int64, device=self.t.device)
+        st = torch.cuda.current_stream(self.t.device).cuda_stream
+        if n == 0:
+            self.reader.record_count()
+        else:
+            self.reader.record_numbers(positions.data_ptr(), n, out.data_ptr(), stream=st)
+        return out
+
+    def read_record_range(self, first, count, ignore_crc=False):
+        """Records first .. first + count - 1 as they lie in the decoded stream, the delimiters between them included -> a new uint8 tensor."""
+        off, ln = self.reader.record_range(first, count)
+        return self.read_ranges([off], [ln], ignore_crc)
+
     def build_sidecar(self, cfgs, ignore_crc=False):
         """A sidecar search index of this stream for 1 .. 4 configurations (api.search_config): search tables for every block, whoever
         wrote the stream, in a separate .mz stream -> a new uint8 tensor on the stream's device."""
