@@ -95,8 +95,9 @@ def _uvarint(v):
     return out
 
 
+@pytest.mark.parametrize("level", [-1, 1, 2])
 @pytest.mark.parametrize("seed", range(4))
-def test_random_inputs_roundtrip(ctx, seed):
+def test_random_inputs_roundtrip(ctx, seed, level):
     rng = np.random.default_rng(77 + seed)
     blocks = []
     for _ in range(12):
@@ -117,7 +118,7 @@ def test_random_inputs_roundtrip(ctx, seed):
             if n > 64:
                 d[rng.integers(0, n, size=n // 64)] ^= 1
         blocks.append(np.ascontiguousarray(d).tobytes())
-    encs = mz.encode_batch(blocks, 1, ctx)
+    encs = mz.encode_batch(blocks, level, ctx)
     for b, e in zip(blocks, encs):
         assert len(e) <= mz.MaxEncodedLen(len(b))
         assert O.decode(e, guard=32) == b

@@ -14,6 +14,7 @@ import oracle as O
 from minlz_amd import synth
 from minlz_amd._lib import BlockDesc
 from tests import tile_levels as TL
+from tests.tile_levels_gpu import check_single as _check_single
 
 pytestmark = pytest.mark.gpu
 
@@ -110,14 +111,6 @@ def test_hand_built_blocks(leg, opts, counts):
         assert not bad, "\n".join(bad)
     finally:
         ctx.close()
-
-
-def _check_single(ctx, enc, want, what):
-    assert mz.decode_batch([enc], ctx) == [want], what
-    body, dlen = TL.block_body(enc)
-    v = TL.verdict(TL.walk(body, dlen), dlen) if body is not None else TL.make_verdict(TL.ORDER, None, False)
-    assert (ctx.general_blocks(), ctx.general_team()) == (int(v.general), v.team), (what, v)
-    return v
 
 
 def test_oracle_blocks_against_the_restatement(ctx):

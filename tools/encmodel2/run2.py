@@ -35,6 +35,34 @@ def def_for(nbytes, level=1, l2_free=True):
         return dict(DEF)
     return dict(DEF, near_bits=13, near_unit=0, far_bits=small_far_bits(nbytes))
 
+# The encoder's five kernel configurations (mlz_hip.hip: match_plan), each named once.  A row of kMatch with FAR = false builds and probes
+# no far table and is otherwise the same template: near tables seeded with every second earlier position of the tile (kSeedStride; every
+# position only with FP, which is LevelBalanced) and the same three-position lazy parse — so the far-less legs are the far ones with far = 0.
+LEGS = ('superfast', 'fastest-far0', 'fastest-far1', 'balanced-levels', 'balanced-free')
+
+def params_for(nbytes, leg):
+    """The model's parameters for a block of nbytes at one of LEGS."""
+    if leg == 'superfast':       # M_SUPERFAST: 12-bit near tables at every size (kM2HashBitsSuperFast), no far tables
+        return dict(DEF, far=0)
+    if leg == 'fastest-far0':    # M_L1_BIG / M_L1_SMALL (MLZ_OPT_ENCODE_FAR = 0): the block class's near tables, no far tables
+        return dict(def_for(nbytes, 1), far=0)
+    if leg == 'fastest-far1':    # M_L1_BIG_FAR / M_L1_SMALL_FAR
+        return def_for(nbytes, 1)
+    if leg == 'balanced-levels':  # M_L2_* with MLZ_OPT_L2_FREE = 0
+        return def_for(nbytes, 2, False)
+    if leg == 'balanced-free':   # M_L2_*, the level's default
+        return def_for(nbytes, 2, True)
+    raise KeyError(leg)
+
+def model_body(a, leg):
+    """The token stream (no block header) the model writes for the block `a` (contiguous uint8) at `leg`; b'' for an empty block."""
+    p = P(**params_for(a.size, leg))
+    cap = a.size + a.size // 8 + 64   # model2_block's output bound; the bytes behind it must stay untouched
+    out = np.full(cap + 64, 0xA5, dtype=np.uint8)
+    n = L.model2_block(a.ctypes.data, a.size, C.byref(p), out.ctypes.data, None)
+    assert n <= cap and (out[cap:] == 0xA5).all(), 'the model wrote beyond its output bound'
+    return out[:n].tobytes()
+
 def run(data, check=True, block=8 << 20, **kw):
     d = dict(DEF); d.update(kw); p = P(**d)
     a = np.ascontiguousarray(data)
