@@ -270,6 +270,44 @@ int64_t mlz_stream_encode_gather_device_long_prefix(mlz_ctx* ctx, int level, uin
 int64_t mlz_stream_decoded_len_device(mlz_ctx* ctx, void* stream, const uint8_t* d_src, size_t n, uint64_t* prefix_len);
 int64_t mlz_stream_decode_device(mlz_ctx* ctx, void* stream, uint32_t flags, const uint8_t* d_src, size_t n, uint8_t* d_dst, size_t dst_cap);
 
+/* Batches of streams in HBM: many .mz streams of one buffer walked, decoded or encoded by ONE call (an object store keeps each object as its own stream:
+ * the per-tensor streams of a checkpoint, the objects of a request batch).  `streams[i]` is an mlz_block_desc for one stream: offsets count from d_src and
+ * d_dst as in the *_batch_device calls, both buffers lie on one device of the context, and out_len is a HOST array.  All three calls are synchronous
+ * and take `stream` like mlz_stream_decode_device.  They return 0 when the call ran (n_streams == 0: at once, nothing is launched); every stream's own result is
+ * in out_len[i], and one stream's error changes nothing for any other.  -MLZ_ERR_ARG, with nothing launched and nothing written: a NULL array with
+ * n_streams > 0, n_streams < 0 or above 2^20, d_src or d_dst that no device of the context holds (or not the same one), a src_len above 2^36, a span that
+ * leaves the allocation its base pointer lies in, two destinations with dst_cap > 0 that overlap (source spans may overlap or repeat), a batch whose chunk
+ * table could pass 2^32 entries.  -MLZ_ERR_HIP: a HIP failure.
+ *
+ * mlz_stream_decoded_len_batch_device: the chunk walk alone.  out_len[i] / prefix_len[i] (may be NULL) = what mlz_stream_decoded_len_device returns / stores
+ *   for (d_src + src_off, src_len); dst_off and dst_cap are ignored.
+ * mlz_stream_decode_batch_device: NewReader(src_i) read to EOF, for every i.  out_len[i] = what mlz_stream_decode_device(ctx, stream, flags, d_src + src_off,
+ *   src_len, d_dst + dst_off, dst_cap) returns for stream i alone: the decoded size, or the first error in that stream's order (the chunks in front of a
+ *   framing error are decoded and checked first; a stream that decodes to more than dst_cap gives -MLZ_ERR_DST_TOO_SMALL and nothing of it is decoded).
+ *   Nothing outside the streams' [dst_off, dst_off + dst_cap) is written, d_src is only read, and no byte at src_off + src_len or beyond enters stream
+ *   i's verdict (the next stream of the batch lies there).  MLZ_STREAM_IGNORE_CRC as in the single call.
+ * mlz_stream_encode_batch_device: NewWriter(dst_i, level, block size, index).EncodeBuffer(src_i) + Close(), for every i.  out_len[i] and
+ *   d_dst[dst_off, +out_len[i]) are byte for byte what mlz_stream_encode_gather_device gives for the one range (d_src + src_off, src_len); dst_cap below
+ *   mlz_stream_bound(src_len, block_size, flags) gives that stream -MLZ_ERR_DST_TOO_SMALL and writes nothing of it.  MLZ_STREAM_ADD_INDEX is honoured;
+ *   MLZ_STREAM_SEARCH_TABLES or match-length bits fail the whole call with -MLZ_ERR_ARG (tables in batches are out of scope), and the level and the
+ *   block size are checked as in the single call.
+ *
+ * The walk: one lane per stream steps through its chunk headers from offset 0, first counting the table's entries, then — after a scan of the counts —
+ * writing them; no region tables.  Workspace: 32 bytes per table entry + 8 bytes and a flag bit per stream, part of mlz_get_counter(ctx, 4) (the streams'
+ * descriptors, 32 bytes each, lie with the other descriptors).  Two read-backs for the whole batch: the places with the sum, then the table; the Reader's
+ * state is applied per stream on the host.  A lane stops after 4096 chunk headers: such a LONG stream (many skippable chunks) is walked inside the same
+ * call by the region kernels of mlz_stream_decoded_len_device, one after the other — the same answers, only slower; mlz_get_counter(ctx, 12) counts them.
+ * Decode: the chunks of all streams run as one list through the decode and CRC kernels (groups of about 64 MiB), stored chunks by one copy kernel; 12 bytes
+ * per chunk come back.  Encode: the blocks of all streams through one encode and one CRC launch sequence; 12 bytes per block visit the host, which lays
+ * every stream out; bodies, identifiers, EOF chunks and indexes are placed by one kernel, chunk headers by another.
+ * Out of scope: search tables and sidecars in batches, an asynchronous form, a batch fanned out over several devices. */
+int mlz_stream_decoded_len_batch_device(mlz_ctx* ctx, void* stream, const uint8_t* d_src, const mlz_block_desc* streams, int n_streams, int64_t* out_len,
+                                        uint64_t* prefix_len);
+int mlz_stream_decode_batch_device(mlz_ctx* ctx, void* stream, uint32_t flags, const uint8_t* d_src, uint8_t* d_dst, const mlz_block_desc* streams,
+                                   int n_streams, int64_t* out_len);
+int mlz_stream_encode_batch_device(mlz_ctx* ctx, void* stream, int level, uint32_t block_size, uint32_t flags, const uint8_t* d_src, uint8_t* d_dst,
+                                   const mlz_block_desc* streams, int n_streams, int64_t* out_len);
+
 /* The device-resident ReadSeeker: Reader.ReadSeeker / ReadSeeker.ReadAt (reader.go:1322-1487) for a stream that lies in HBM, with the chunk walk's table
  * in the place of the seek index (index.go:114 Index.Find): any byte ranges of the decoded stream, decoded on the device into device memory.
  *
@@ -582,7 +620,8 @@ const char* mlz_timer_name(int idx);
  *            32 + 32 per touched chunk (32 alone for a refused call or one that touches nothing).  Not counted: the results of the chunks' decode and CRC
  *            (12 bytes per chunk, as in every stream decode) and the one-time upload of a handle's chunk table.
  * which = 10 / 11: the context's last mlz_dev_reader_search, mlz_dev_reader_search_many or search phase of mlz_dev_reader_search_records: 10 = chunks it decoded or copied, 11 = chunks with a usable search table (0 when the call
- *            used none: MLZ_SEARCH_NO_TABLES, no info chunk, a pattern shorter than M). */
+ *            used none: MLZ_SEARCH_NO_TABLES, no info chunk, a pattern shorter than M).
+ * which = 12: streams that the context's last mlz_stream_*_batch_device call sent through the region walk because they hold more than 4096 chunk headers. */
 int64_t mlz_get_counter(mlz_ctx* ctx, int which);
 
 #ifdef __cplusplus

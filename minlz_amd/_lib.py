@@ -18,6 +18,7 @@ SYMBOLS = [
     "mlz_stream_decode", "mlz_get_counter", "mlz_init_devices", "mlz_device_count", "mlz_device_ctx",
     "mlz_stream_encode_gather_device", "mlz_release_stream", "mlz_stream_decoded_prefix_len",
     "mlz_stream_decoded_len_device", "mlz_stream_decode_device",
+    "mlz_stream_decoded_len_batch_device", "mlz_stream_decode_batch_device", "mlz_stream_encode_batch_device",
     "mlz_stream_open_device", "mlz_dev_reader_size", "mlz_dev_reader_read", "mlz_dev_reader_close",
     "mlz_dev_reader_read_device", "mlz_dev_reader_search", "mlz_dev_reader_search_many",
     "mlz_stream_bound_tables", "mlz_stream_encode_gather_device_tables",
@@ -108,6 +109,11 @@ def lib():
     L.mlz_stream_decode.argtypes = [vp, u32, vp, sz, vp, sz]; L.mlz_stream_decode.restype = i64
     L.mlz_stream_decoded_len_device.argtypes = [vp, vp, vp, sz, C.POINTER(u64)]; L.mlz_stream_decoded_len_device.restype = i64
     L.mlz_stream_decode_device.argtypes = [vp, vp, u32, vp, sz, vp, sz]; L.mlz_stream_decode_device.restype = i64
+    L.mlz_stream_decoded_len_batch_device.argtypes = [vp, vp, vp, C.POINTER(BlockDesc), i32, C.POINTER(i64), C.POINTER(u64)]
+    L.mlz_stream_decoded_len_batch_device.restype = i32
+    L.mlz_stream_decode_batch_device.argtypes = [vp, vp, u32, vp, vp, C.POINTER(BlockDesc), i32, C.POINTER(i64)]; L.mlz_stream_decode_batch_device.restype = i32
+    L.mlz_stream_encode_batch_device.argtypes = [vp, vp, i32, u32, u32, vp, vp, C.POINTER(BlockDesc), i32, C.POINTER(i64)]
+    L.mlz_stream_encode_batch_device.restype = i32
     L.mlz_stream_open_device.argtypes = [vp, vp, vp, sz, C.POINTER(vp)]; L.mlz_stream_open_device.restype = i64
     L.mlz_dev_reader_size.argtypes = [vp]; L.mlz_dev_reader_size.restype = i64
     L.mlz_dev_reader_read.argtypes = [vp, vp, u32, vp, sz, vp, sz]; L.mlz_dev_reader_read.restype = i64

@@ -202,6 +202,49 @@ class Context:
             _raise(r, self)
         return int(r)
 
+    # ---- batches of streams in device memory: one call for many streams; per-stream results come back as lists, nothing is raised per stream ----
+    @staticmethod
+    def _stream_descs(descs):
+        if isinstance(descs, C.Array):
+            return descs
+        return (BlockDesc * max(len(descs), 1))(*[BlockDesc(*[int(v) for v in (tuple(d) + (0, 0))[:4]]) for d in descs])
+
+    def stream_decoded_len_batch_device(self, d_src, spans, stream=None):
+        """mlz_stream_decoded_len_batch_device: the chunk walk of every stream (src_off, src_len) of the buffer at d_src ->
+        [(result, prefix_len)], each as stream_decoded_len_device gives it for that stream alone."""
+        n = len(spans)
+        out = (C.c_int64 * max(n, 1))()
+        prefix = (C.c_uint64 * max(n, 1))()
+        r = _lib.lib().mlz_stream_decoded_len_batch_device(self.handle, stream, d_src, self._stream_descs(spans), n, out, prefix)
+        if r:
+            _raise(r, self)
+        return [(int(out[i]), int(prefix[i])) for i in range(n)]
+
+    def stream_decode_batch_device(self, d_src, d_dst, descs, ignore_crc=False, stream=None):
+        """mlz_stream_decode_batch_device: every stream (src_off, src_len, dst_off, dst_cap) of the buffer at d_src decoded to its place in the
+        buffer at d_dst -> [result]: the decoded size or -MLZ_ERR_* of each stream, as mlz_stream_decode_device returns it for that stream alone."""
+        n = len(descs)
+        out = (C.c_int64 * max(n, 1))()
+        r = _lib.lib().mlz_stream_decode_batch_device(self.handle, stream, STREAM_IGNORE_CRC if ignore_crc else 0, d_src, d_dst, self._stream_descs(descs), n, out)
+        if r:
+            _raise(r, self)
+        return [int(out[i]) for i in range(n)]
+
+    def stream_encode_batch_device(self, level, block_size, add_index, d_src, d_dst, descs, stream=None, flags=0):
+        """mlz_stream_encode_batch_device: every input (src_off, src_len, dst_off, dst_cap) of the buffer at d_src written as a stream of its own to
+        its place in the buffer at d_dst -> [result]: the stream's size or -MLZ_ERR_* of each.  flags: further MLZ_STREAM_* bits, as they are."""
+        n = len(descs)
+        out = (C.c_int64 * max(n, 1))()
+        r = _lib.lib().mlz_stream_encode_batch_device(self.handle, stream, level, block_size, (STREAM_ADD_INDEX if add_index else 0) | flags, d_src, d_dst,
+                                                      self._stream_descs(descs), n, out)
+        if r:
+            _raise(r, self)
+        return [int(out[i]) for i in range(n)]
+
+    def batch_long_streams(self):
+        """Streams that the context's last stream batch call walked by the region kernels: more than 4096 chunk headers (mlz_get_counter 12)."""
+        return int(_lib.lib().mlz_get_counter(self.handle, 12))
+
 
     def stream_open_device(self, d_src, n, stream=None):
         """mlz_stream_open_device: a stream in device memory opened for range reads -> DeviceReader.  The caller keeps d_src alive and unchanged

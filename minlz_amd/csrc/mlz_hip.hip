@@ -144,6 +144,9 @@ struct mlz_ctx {
     // decode workspace
     DevBuf d_dec, d_idx;
     DevBuf d_walk, d_walk_tab;   // the device-resident Reader's chunk walk: exit tables (8 bytes per stream byte) and the chunk table
+    DevBuf d_batch;              // the batch calls over many streams: counts and places of the batch walk (8 bytes per stream, a flag bit each); its table is d_walk_tab
+    DevBuf d_batch_desc;         // ... and the streams' descriptors on the device (32 bytes per stream)
+    uint64_t batch_long = 0;     // streams the last batch call sent through the region walk (mlz_get_counter 12)
     DevBuf d_range;              // the device-resident ReadSeeker: where partly wanted chunks of a group are decoded (a group plus one block at the most)
     DevBuf d_rplan;              // mlz_dev_reader_read_device: the plan kernels' workspace (16 bytes per range, 28 per chunk of the stream)
     DevBuf d_records, d_rwin;    // mlz_dev_reader_search_records: what lives across its read phase (the occurrences, windows and records: about 100 bytes per occurrence), and the merged windows' bytes (at most the decoded size)
@@ -184,8 +187,8 @@ struct mlz_ctx {
     // Every DevBuf above, once, by side: 0 = what mlz_get_counter 3 sums (encode), 1 = counter 4 (decode), 2 = the rest; mlz_destroy frees all three.  A buffer added to the struct is added here.
     std::vector<DevBuf*> bufs(int side) {
         if (side == 0) return {&d_scratch, &d_tile_size, &d_tile_out, &d_flags, &d_far, &d_recs, &d_piece_cnt, &d_farbin, &d_stab};
-        if (side == 1) return {&d_dec, &d_idx, &d_walk, &d_walk_tab, &d_range, &d_rplan, &d_records, &d_rwin};
-        return {&d_blocks_k[0], &d_blocks_k[1], &d_tile_block_k[0], &d_tile_block_k[1], &d_seg_block_k[0], &d_seg_block_k[1], &d_place, &d_gen_acc, &d_in, &d_out, &d_len, &d_crc, &d_crc_tabs, &d_crc_tiles, &d_prof};
+        if (side == 1) return {&d_dec, &d_idx, &d_walk, &d_walk_tab, &d_batch, &d_range, &d_rplan, &d_records, &d_rwin};
+        return {&d_blocks_k[0], &d_blocks_k[1], &d_tile_block_k[0], &d_tile_block_k[1], &d_seg_block_k[0], &d_seg_block_k[1], &d_place, &d_batch_desc, &d_gen_acc, &d_in, &d_out, &d_len, &d_crc, &d_crc_tabs, &d_crc_tiles, &d_prof};
     }
     // A ring of event pairs per timer, resolved kTimerRing uses later (long complete by then), so reading the clock never stalls the caller and
     // launches can run ahead of the device.  A device batch runs as one or more internal groups, each firing the timers: acc_ms sums them and
@@ -1225,6 +1228,7 @@ int64_t mlz_get_counter(mlz_ctx* c, int which) {
     if (which == 5) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->gen_fallbacks); }
     if (which == 7 || which == 8) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(which == 7 ? c->range_chunks : c->range_scratch); }
     if (which == 9) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->range_plan_host); }
+    if (which == 12) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->batch_long); }
     if (which == 10 || which == 11) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(which == 10 ? c->search_chunks : c->search_tables); }
     std::lock_guard<std::mutex> lk(c->q_mu);
     return which == 0 ? int64_t(c->q_batches) : which == 1 ? int64_t(c->q_requests) : -MLZ_ERR_ARG;
@@ -1307,6 +1311,7 @@ int mlz_debug_idxprof(unsigned long long* out) {
 #include "mlz_stream.hip.inc"
 #include "mlz_stream_walk.hip.inc"
 #include "mlz_stream_ranges.hip.inc"
+#include "mlz_stream_batch.hip.inc"
 #include "mlz_stream_ranges_dev.hip.inc"
 #include "mlz_stream_search.hip.inc"
 #include "mlz_stream_search_many.hip.inc"

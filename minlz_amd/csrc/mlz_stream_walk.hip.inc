@@ -28,6 +28,7 @@
 // Workspace: 8 bytes per stream byte (x0, x1) + 12 bytes per 4 KiB + 32 bytes per table entry.
 
 #include "mlz_stream_walk.h"
+#include "mlz_stream_batch.h"
 #include "mlz_stream_ranges.h"
 
 namespace mlz {
@@ -306,11 +307,14 @@ ChunkJobResults take_chunk_job_results(Carve* pin, size_t nj) { return ChunkJobR
 // token bytes in the stream —, each with the lowest target address as its base pointer and the targets' distances from it in the descriptors;
 // after_group(g) is then called with sm still running (the range read enqueues the group's copy there).  One synchronise at the end; per chunk
 // 8 + 4 bytes of results come back, to `res`.  The caller has begun the decode call, sized c->pinned2 for its carve (res is part of it)
-// and holds c->mu.  Returns 0 or the error of the first failing chunk of the list.
+// and holds c->mu.  Returns 0 or the error of the first failing chunk of the list.  per_job (the batch calls, whose list holds many streams):
+// receives every job's own verdict (mlz::chunk_job_verdict), and the chunks' errors are then not the call's: it returns 0.
 template <class AfterGroup>
 int64_t stream_run_chunk_jobs(mlz_ctx* c, hipStream_t sm, bool ignore_crc, const uint8_t* d_src, const std::vector<StreamChunk>& chunks,
-                              const std::vector<ChunkJob>& jobs, const std::vector<size_t>& gend, const ChunkJobResults& res, AfterGroup after_group) {
+                              const std::vector<ChunkJob>& jobs, const std::vector<size_t>& gend, const ChunkJobResults& res, AfterGroup after_group,
+                              std::vector<int64_t>* per_job = nullptr) {
     const size_t nj = jobs.size();
+    if (per_job) per_job->assign(nj, 0);
     if (nj == 0) return 0;
     HIPCHK(c, c->d_len.ensure(sizeof(int64_t) * nj));
     HIPCHK(c, c->d_crc.ensure(sizeof(uint32_t) * nj + 64));
@@ -357,11 +361,10 @@ int64_t stream_run_chunk_jobs(mlz_ctx* c, hipStream_t sm, bool ignore_crc, const
     HIPCHK(c, hipGetLastError());
     for (size_t j = 0; j < nj; j++) {
         const StreamChunk& ck = chunks[jobs[j].ck];
-        if (ck.type != kChunkUncompressed) {
-            const int64_t got = h_len[res_idx[j]];
-            if (got != int64_t(ck.n)) return got < 0 ? got : -MLZ_ERR_CORRUPT;
-        }
-        if (!ignore_crc && h_crc[j] != ck.crc) return -MLZ_ERR_CRC;
+        const bool compressed = ck.type != kChunkUncompressed;
+        const int64_t v = mlz::chunk_job_verdict(compressed, compressed ? h_len[res_idx[j]] : 0, ck.n, !ignore_crc, ignore_crc ? 0 : h_crc[j], ck.crc);
+        if (per_job) (*per_job)[j] = v;
+        else if (v) return v;
     }
     return 0;
 }

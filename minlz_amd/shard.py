@@ -163,6 +163,71 @@ class HipTensorCodec:
         r = self.ctx.stream_decode_device(t.data_ptr(), t.numel(), out.data_ptr(), cap, ignore_crc=ignore_crc, stream=st)
         return out[:r]
 
+    @staticmethod
+    def _raise_stream(what, i, code):
+        """The error of stream i of a batch: the class of its code, the index in the message and in .index."""
+        from . import api
+        e = api._ERRS.get(-code, api.MinLZError)("%s: stream %d of the batch: minlz error %d" % (what, i, -code))
+        e.code, e.index = -code, i
+        raise e
+
+    def decode_streams(self, t, spans, ignore_crc=False):
+        """Many .mz streams that lie in one uint8 tensor on the device, stream i at t[off_i : off_i + len_i] for spans[i] = (off_i, len_i) ->
+        (out, starts): their decoded bytes packed into one new uint8 tensor on the same device, and the n + 1 places where they start in it
+        (a list of ints; the last is out's size).  One batch walk sizes the output (mlz_stream_decoded_len_batch_device), one batch call
+        decodes (mlz_stream_decode_batch_device).  Raises the first failing stream's error, which names its index (.index)."""
+        if t.dtype != torch.uint8 or not t.is_cuda:
+            raise ValueError("decode_streams: a uint8 tensor on the device")
+        t = t.contiguous()
+        spans = [(int(o), int(n)) for o, n in spans]
+        for o, n in spans:
+            if o < 0 or n < 0 or o + n > t.numel():
+                raise ValueError("decode_streams: a span leaves the tensor")
+        if not spans:
+            return torch.empty(0, dtype=torch.uint8, device=t.device), [0]
+        st = torch.cuda.current_stream(t.device).cuda_stream
+        lens = self.ctx.stream_decoded_len_batch_device(t.data_ptr(), spans, stream=st)
+        starts = [0]
+        for r, prefix in lens:   # a framing error: the chunks in front of it are decoded and checked first
+            starts.append(starts[-1] + (r if r >= 0 else prefix))
+        out = torch.empty(max(starts[-1], 1), dtype=torch.uint8, device=t.device)
+        descs = [(o, n, starts[i], starts[i + 1] - starts[i]) for i, (o, n) in enumerate(spans)]
+        res = self.ctx.stream_decode_batch_device(t.data_ptr(), out.data_ptr(), descs, ignore_crc=ignore_crc, stream=st)
+        for i, r in enumerate(res):
+            if r < 0:
+                self._raise_stream("decode_streams", i, r)
+        return out[:starts[-1]], starts
+
+    def encode_streams(self, t, spans, level, block_size=1 << 20, add_index=False):
+        """Every input t[off_i : off_i + len_i] (a uint8 tensor on the device, spans[i] = (off_i, len_i)) as a .mz stream of its own ->
+        (out, stream_spans): one new uint8 tensor on the same device and where each stream lies in it, [(off, len)] (with room between
+        them: every stream is written at the place its bound reserves).  One call (mlz_stream_encode_batch_device); the bytes are
+        api.stream_encode's.  Raises the first failing stream's error, which names its index (.index)."""
+        from . import _lib
+        if t.dtype != torch.uint8 or not t.is_cuda:
+            raise ValueError("encode_streams: a uint8 tensor on the device")
+        t = t.contiguous()
+        spans = [(int(o), int(n)) for o, n in spans]
+        flags = 1 if add_index else 0
+        descs, at = [], 0
+        for o, n in spans:
+            if o < 0 or n < 0 or o + n > t.numel():
+                raise ValueError("encode_streams: a span leaves the tensor")
+            cap = int(_lib.lib().mlz_stream_bound(n, block_size, flags))
+            if cap < 0:
+                raise ValueError("encode_streams: block size %d" % block_size)
+            descs.append((o, n, at, cap))
+            at += cap
+        out = torch.empty(max(at, 1), dtype=torch.uint8, device=t.device)
+        if not spans:
+            return out[:0], []
+        st = torch.cuda.current_stream(t.device).cuda_stream
+        res = self.ctx.stream_encode_batch_device(level, block_size, add_index, t.data_ptr(), out.data_ptr(), descs, stream=st)
+        for i, r in enumerate(res):
+            if r < 0:
+                self._raise_stream("encode_streams", i, r)
+        return out, [(d[2], r) for d, r in zip(descs, res)]
+
     def open_stream(self, t):
         """A .mz stream that lies on the device (uint8 tensor) opened for range reads -> DeviceStream (ReadAt, read_ranges).  The chunk walk
         runs once, here; a framing error raises."""
