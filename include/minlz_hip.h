@@ -501,8 +501,8 @@ int64_t mlz_dev_reader_search_records(mlz_dev_reader* reader, void* stream, uint
  * mlz_dev_reader_record_range: host convenience for "records first .. first + count - 1 as ONE range": *off = start(first), *len = end(first + count
  *   - 1) - start(first), the inner delimiters included; count == 0 gives length 0 (at start(first), or at size for first == N).  first + count > N:
  *   -MLZ_ERR_ARG.  Two table entries visit the host; the caller reads the range with mlz_dev_reader_read.  Returns 0.
- * Out of scope: delimiters of more than one byte; an index persisted into a stream or a sidecar; an index built while the Writer encodes; record
- *   numbers as an output of mlz_dev_reader_search_records itself (its signature stays). */
+ * Out of scope: delimiters of more than one byte; an index persisted into a stream or a sidecar; an index built while the Writer encodes.  Record
+ *   numbers of the matching records come from mlz_dev_reader_grep_records below (mlz_dev_reader_search_records' signature stays). */
 int64_t mlz_dev_reader_index_records(mlz_dev_reader* reader, void* stream, uint32_t flags, uint8_t delimiter,
                                      uint64_t* info /* host, may be NULL: 4 values */);
 int64_t mlz_dev_reader_record_count(const mlz_dev_reader* reader);
@@ -511,6 +511,44 @@ int64_t mlz_dev_reader_read_records(mlz_dev_reader* reader, void* stream, uint32
                                     uint64_t* d_starts /* may be NULL */);
 int64_t mlz_dev_reader_record_numbers(mlz_dev_reader* reader, void* stream, const uint64_t* d_pos, size_t n, uint64_t* d_no);
 int64_t mlz_dev_reader_record_range(mlz_dev_reader* reader, uint64_t first, uint64_t count, uint64_t* off, uint64_t* len);
+
+/* mlz_dev_reader_grep_records: grep over the record index — many patterns, inverted match, context records and record numbers in one call: what
+ *   `mz search -f keys -n -v -A a -B b file.mz` selects, and with rec_cap == 0 what `-c` counts.  N, start, end and number(p) are those of the
+ *   handle's record index above, and so is the delimiter.  `patterns`, pattern_len and n_patterns (host) as for mlz_dev_reader_search_many.
+ *     M = the records r for which some pattern i occurs at a position p with number(p) == r (patterns hold no delimiter, so an occurrence lies
+ *         inside one record);
+ *     S = M, or {0 .. N-1} \ M with MLZ_GREP_INVERT (empty records exist, never match, and are therefore selected under invert);
+ *     C = the records r < N with some s in S and s - before <= r <= s + after.  Any value of before / after is valid; values >= N behave like N.
+ *   Returns R = |C| (it may exceed rec_cap).  d_rec_no[0 .. k), k = min(R, rec_cap), receives the k smallest members of C in ascending order;
+ *   d_rec_kind[j] (may be NULL) is 1 when record d_rec_no[j] is in S and 0 when it is context only (grep's `:` against `-`).  Nothing beyond k entries of either
+ *   array is written, and after any error return nothing has been written to either.  totals (host, may be NULL): R; |S|; the bytes of the k
+ *   written records — exactly what mlz_dev_reader_read_records over d_rec_no[0 .. k) needs as dst_cap —; the bytes of all R records.  No record
+ *   is cut, there is no reach and no position list: a match goes from the scan kernel into one bit per record.
+ *   Equivalence: for truthful tables, M is the set of mlz_dev_reader_record_numbers of the positions that mlz_dev_reader_search_many reports
+ *   with the same patterns and flags.
+ *   Flags: MLZ_STREAM_IGNORE_CRC, MLZ_SEARCH_NO_TABLES, MLZ_GREP_INVERT.
+ *   -MLZ_ERR_ARG, each decided before anything is launched, nothing written: a handle without an index; the argument errors of
+ *   mlz_dev_reader_search_many (n_patterns, the lengths, NULL patterns); a pattern that contains the index's delimiter (as
+ *   mlz_dev_reader_search_records decides it); d_rec_no NULL with rec_cap > 0; d_rec_no or d_rec_kind (not NULL), with rec_cap > 0, that is not
+ *   on the handle's device; N >= 2^32.  n_patterns == 0 is valid: M is empty, no chunk is decoded, and under invert every record is selected.
+ *   N == 0 returns 0.
+ *   The search phase is mlz_dev_reader_search_many's plan and decode with the same patterns and flags (an attached sidecar is used): stats
+ *   (host, may be NULL: 4 values) and mlz_get_counter 10 / 11 describe it exactly as there.  Decode and CRC errors as there: the first failing
+ *   decoded chunk in stream order; a broken chunk that the tables prune goes unnoticed.  Each decoded group is scanned ONCE (no count pass, no
+ *   write pass); two kernels then select (complement, context by a forward and a backward scan of the nearest selected record: independent of
+ *   the sizes of before / after) and compact.  32 bytes visit the host, behind the search phase's own; nothing per record or per occurrence does.
+ *   Synchronous; `stream` as for mlz_dev_reader_read.  Workspace, grow-only and part of mlz_get_counter 4: 16 bytes per 32 records (two
+ *   bitmaps and two scan arrays) beside the search phase's.
+ *   Out of scope: regular expressions and case folding; per-record lists of which pattern matched; delimiters of more than one byte; grep over
+ *   batches of streams; a call that works without a record index (mlz_dev_reader_search_records remains the bounded-reach form for that). */
+#define MLZ_GREP_INVERT 16u
+int64_t mlz_dev_reader_grep_records(mlz_dev_reader* reader, void* stream, uint32_t flags,
+                                    const uint8_t* patterns, const uint32_t* pattern_len, size_t n_patterns,   /* host, as mlz_dev_reader_search_many */
+                                    uint64_t before, uint64_t after,                                          /* context records: -B, -A */
+                                    uint64_t* d_rec_no,                                                       /* device, rec_cap values; may be NULL when rec_cap == 0 */
+                                    uint8_t* d_rec_kind,                                                      /* device, rec_cap values; may be NULL */
+                                    size_t rec_cap,
+                                    uint64_t* totals /* host, may be NULL: 4 values */, uint64_t* stats /* host, may be NULL: as mlz_dev_reader_search_many */);
 
 /* Sidecar search indexes (SEARCH.md "Sidecar Streams", SPEC_SEARCH.md 1.1 and 2.3; the reference's BuildSidecar and SidecarSearcher): search tables
  * for a stream that exists already, in a separate valid MinLZ stream.  The main stream is never touched, so this serves ANY stream in HBM: the
@@ -619,7 +657,7 @@ const char* mlz_timer_name(int idx);
  * which = 9: bytes of plan data that crossed between host and device, both directions together, during the context's last mlz_dev_reader_read_device:
  *            32 + 32 per touched chunk (32 alone for a refused call or one that touches nothing).  Not counted: the results of the chunks' decode and CRC
  *            (12 bytes per chunk, as in every stream decode) and the one-time upload of a handle's chunk table.
- * which = 10 / 11: the context's last mlz_dev_reader_search, mlz_dev_reader_search_many or search phase of mlz_dev_reader_search_records: 10 = chunks it decoded or copied, 11 = chunks with a usable search table (0 when the call
+ * which = 10 / 11: the context's last mlz_dev_reader_search, mlz_dev_reader_search_many or search phase of mlz_dev_reader_search_records or mlz_dev_reader_grep_records: 10 = chunks it decoded or copied, 11 = chunks with a usable search table (0 when the call
  *            used none: MLZ_SEARCH_NO_TABLES, no info chunk, a pattern shorter than M).
  * which = 12: streams that the context's last mlz_stream_*_batch_device call sent through the region walk because they hold more than 4096 chunk headers. */
 int64_t mlz_get_counter(mlz_ctx* ctx, int which);

@@ -27,6 +27,7 @@ SYMBOLS = [
     "mlz_dev_reader_search_records",
     "mlz_dev_reader_index_records", "mlz_dev_reader_record_count", "mlz_dev_reader_record_spans", "mlz_dev_reader_read_records",
     "mlz_dev_reader_record_numbers", "mlz_dev_reader_record_range",
+    "mlz_dev_reader_grep_records",
 ]
 
 
@@ -132,5 +133,7 @@ def lib():
     L.mlz_dev_reader_read_records.argtypes = [vp, vp, u32, vp, sz, vp, sz, vp]; L.mlz_dev_reader_read_records.restype = i64
     L.mlz_dev_reader_record_numbers.argtypes = [vp, vp, vp, sz, vp]; L.mlz_dev_reader_record_numbers.restype = i64
     L.mlz_dev_reader_record_range.argtypes = [vp, u64, u64, C.POINTER(u64), C.POINTER(u64)]; L.mlz_dev_reader_record_range.restype = i64
+    L.mlz_dev_reader_grep_records.argtypes = [vp, vp, u32, vp, vp, sz, u64, u64, vp, vp, sz, C.POINTER(u64), C.POINTER(u64)]
+    L.mlz_dev_reader_grep_records.restype = i64
     _lib = L
     return L

@@ -261,7 +261,7 @@ class Context:
         return int(L.mlz_get_counter(self.handle, 7)), int(L.mlz_get_counter(self.handle, 8))
 
     def search_plan(self):
-        """(chunks decoded or copied, chunks with a usable search table) of the context's last DeviceReader.search or search_many (mlz_get_counter 10, 11)."""
+        """(chunks decoded or copied, chunks with a usable search table) of the context's last DeviceReader.search, search_many or grep_records (mlz_get_counter 10, 11)."""
         L = _lib.lib()
         return int(L.mlz_get_counter(self.handle, 10)), int(L.mlz_get_counter(self.handle, 11))
 
@@ -416,6 +416,27 @@ class DeviceReader:
         if r < 0:
             _raise(r, self.ctx)
         return int(r)
+
+    def grep_records(self, patterns, d_rec_no, d_rec_kind, rec_cap, invert=False, before=0, after=0, ignore_crc=False, no_tables=False, stream=None):
+        """mlz_dev_reader_grep_records: grep over the record index.  patterns: a sequence of up to 4096 bytes objects of 1 .. 256 bytes
+        without the index's delimiter (none: nothing matches, and under invert every record is selected); a record is selected when it
+        holds one of them, with invert when it holds none; before, after: context records in front of and behind every selected one.
+        d_rec_no: device address of room for rec_cap uint64 (None with rec_cap == 0), which receives the smallest min(R, rec_cap) numbers
+        of the selected and context records, ascending; d_rec_kind: room for rec_cap bytes or None, 1 = selected, 0 = context only.
+        -> (R, (R, selected records, bytes of the written records: read_records' dst_cap, bytes of all R records), (data chunks, chunks
+        decoded or copied, chunks with a usable search table, patterns the tables could not serve))."""
+        if not self.handle:
+            raise ValueError("DeviceReader is closed")
+        pats = [bytes(p) for p in patterns]
+        blob = b"".join(pats)
+        lens = np.asarray([len(p) for p in pats], dtype=np.uint32)
+        totals, stats = (C.c_uint64 * 4)(), (C.c_uint64 * 4)()
+        flags = (STREAM_IGNORE_CRC if ignore_crc else 0) | (SEARCH_NO_TABLES if no_tables else 0) | (GREP_INVERT if invert else 0)
+        r = _lib.lib().mlz_dev_reader_grep_records(self.handle, stream, flags, blob if pats else None, lens.ctypes.data if pats else None, len(pats), before, after, d_rec_no,
+                                                   d_rec_kind, rec_cap, totals, stats)
+        if r < 0:
+            _raise(r, self.ctx)
+        return int(r), tuple(int(v) for v in totals), tuple(int(v) for v in stats)
 
     def record_range(self, first, count):
         """mlz_dev_reader_record_range: records first .. first + count - 1 as one byte range, the delimiters between them included
@@ -663,7 +684,7 @@ def decode_batch(blocks, ctx=None):
     return res
 
 
-STREAM_ADD_INDEX, STREAM_IGNORE_CRC, STREAM_SEARCH_TABLES, SEARCH_NO_TABLES = 1, 2, 4, 8
+STREAM_ADD_INDEX, STREAM_IGNORE_CRC, STREAM_SEARCH_TABLES, SEARCH_NO_TABLES, GREP_INVERT = 1, 2, 4, 8, 16
 
 
 def search_tables_config(match_len, prefix):

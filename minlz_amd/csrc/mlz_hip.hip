@@ -1318,3 +1318,4 @@ int mlz_debug_idxprof(unsigned long long* out) {
 #include "mlz_stream_sidecar.hip.inc"
 #include "mlz_stream_records.hip.inc"
 #include "mlz_stream_record_index.hip.inc"
+#include "mlz_stream_grep.hip.inc"

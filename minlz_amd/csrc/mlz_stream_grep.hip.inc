@@ -1,0 +1,194 @@
+// mlz_stream_grep.hip.inc — mlz_dev_reader_grep_records: grep over the record index of a .mz stream in HBM — many patterns, inverted match,
+// context records, record numbers out (included at the end of mlz_hip.hip, behind the record index, whose table it reads, and the search for
+// many patterns, whose plan, decode and walk it runs).  The rules are those of mlz_stream_grep.h, which the host check runs as plain loops.
+//
+//   mark      the search phase of mlz_dev_reader_search_many, unchanged (dev_reader_search_plan, search_decode_plan / take / ready / run), with
+//             search_many_kernel<kSearchManyMarkRecords> on every group: one pass, a verified pair sets the bit of its position's record in a
+//             bitmap of N bits in the workspace.  No count pass, no prefix, no position list.
+//   select    grep_select_kernel (one workgroup, a slab of words per lane, as rindex_scan_kernel and records_number_kernel run): the
+//             complement under MLZ_GREP_INVERT, the forward and the backward scan of the nearest selected record, a word's context bits from
+//             the two, the popcounts' exclusive prefix; R and |S|.
+//   compact   grep_compact_kernel, a lane per word: numbers and kinds of the ranks below rec_cap, and end - start of every record (two
+//             loads of D) summed into the bytes written and the bytes of all R records: two 64-bit atomics per workgroup.
+// 32 bytes come home, behind the decode's verdicts; the caller's arrays are written by the compact kernel alone, which runs behind them.
+// No kernel waits for another workgroup.
+
+#include "mlz_stream_grep.h"
+
+namespace mlz {
+
+// One workgroup.  sel: the marked words in, S out; ctx: C; above: the backward scan's value per word; rank: the records of C in front of a word
+__global__ __launch_bounds__(kGrepScanThreads) void grep_select_kernel(uint32_t* __restrict__ sel, uint32_t* __restrict__ ctx, uint32_t* __restrict__ above, uint32_t* __restrict__ rank,
+                                                                       uint64_t W, uint64_t N, uint32_t invert, uint64_t before, uint64_t after, GrepTotals* __restrict__ tot) {
+    __shared__ uint32_t lds[kGrepScanThreads];
+    const uint32_t tid = threadIdx.x;
+    auto most = [](uint32_t x, uint32_t y) { return x > y ? x : y; };
+    auto plus = [](uint32_t x, uint32_t y) { return x + y; };
+    const GrepSlab sl = grep_slab(W, tid);
+    uint32_t last = 0, first = 0, nsel = 0;
+    for (uint64_t w = sl.b; w < sl.e; w++) {
+        const uint32_t s = grep_select_word(sel[w], w, N, invert != 0);
+        sel[w] = s;
+        nsel += rindex_popcount(s);
+        last = most(last, grep_last_key(s, w));
+        first = most(first, grep_first_key(s, w, N));
+    }
+    uint32_t below = wg_scan<kGrepScanThreads>(last, lds, tid, most);                           // over the lanes in front
+    uint32_t beyond = wg_scan<kGrepScanThreads>(first, lds, kGrepScanThreads - 1 - tid, most);  // the lanes in reverse: over those behind
+    for (uint64_t w = sl.e; w > sl.b; w--) {
+        above[w - 1] = beyond;
+        beyond = most(beyond, grep_first_key(sel[w - 1], w - 1, N));
+    }
+    uint32_t cnt = 0, total = 0, selected = 0;
+    for (uint64_t w = sl.b; w < sl.e; w++) {
+        const uint32_t s = sel[w], cw = grep_context_word(s, w, below, above[w], before, after, N);
+        ctx[w] = cw;
+        cnt += rindex_popcount(cw);
+        below = most(below, grep_last_key(s, w));
+    }
+    uint32_t run = wg_scan<kGrepScanThreads>(cnt, lds, tid, plus, &total);   // (at most N < 2^32)
+    for (uint64_t w = sl.b; w < sl.e; w++) { rank[w] = run; run += rindex_popcount(ctx[w]); }
+    wg_scan<kGrepScanThreads>(nsel, lds, tid, plus, &selected);
+    if (tid == 0) { tot->records = total; tot->selected = selected; }
+}
+
+struct GrepBytes { uint64_t written, bytes; };
+
+// A lane per word of C.  rec_no[rank], rec_kind[rank] (may be NULL) for the ranks below rec_cap; tot->written, tot->bytes += the records' lengths
+__global__ __launch_bounds__(kGrepCompactThreads) void grep_compact_kernel(const uint32_t* __restrict__ ctx, const uint32_t* __restrict__ sel, const uint32_t* __restrict__ rank, uint64_t W,
+                                                                           const uint64_t* __restrict__ D, uint64_t k, uint64_t size, uint64_t rec_cap, uint64_t* __restrict__ rec_no,
+                                                                           uint8_t* __restrict__ rec_kind, GrepTotals* __restrict__ tot) {
+    __shared__ GrepBytes lds[kGrepCompactThreads];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t w = uint64_t(blockIdx.x) * kGrepCompactThreads + tid;
+    GrepBytes mine{0, 0}, sum{0, 0};
+    if (w < W) {
+        const uint32_t cw = ctx[w];
+        if (cw)
+            grep_emit_word(cw, sel[w], w, rank[w], rec_cap, [&](uint64_t r) { return rindex_span([&](uint64_t j) { return D[j]; }, k, size, r).len; },
+                           [&](uint64_t at, uint64_t r, uint8_t kind) { rec_no[at] = r; if (rec_kind) rec_kind[at] = kind; }, &mine.written, &mine.bytes);
+    }
+    wg_scan<kGrepCompactThreads>(mine, lds, tid, [](GrepBytes x, GrepBytes y) { return GrepBytes{x.written + y.written, x.bytes + y.bytes}; }, &sum);
+    if (tid == 0) {
+        if (sum.written) atomicAdd(reinterpret_cast<unsigned long long*>(&tot->written), static_cast<unsigned long long>(sum.written));
+        if (sum.bytes) atomicAdd(reinterpret_cast<unsigned long long*>(&tot->bytes), static_cast<unsigned long long>(sum.bytes));
+    }
+}
+
+}  // namespace mlz
+
+namespace {
+
+struct GrepOut { uint64_t* d_rec_no; uint8_t* d_rec_kind; uint64_t rec_cap; };
+
+int64_t dev_reader_grep_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* patterns, const uint32_t* pattern_len, size_t n, uint64_t before, uint64_t after,
+                               const GrepOut& out, uint64_t* totals, uint64_t* stats) {
+    mlz_ctx* c = rd->ctx;
+    const size_t nck = rd->chunks.size();
+    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0;
+    search_begin(rd, stats);
+    if (totals) totals[0] = totals[1] = totals[2] = totals[3] = 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t N = rd->index_n, W = mlz::grep_words(N);
+    if (N == 0) return 0;
+    // the search phase's plan: as dev_reader_search_many_locked
+    mlz::SearchManyIndex index;
+    std::vector<uint8_t> take(nck, 0);
+    size_t n_take = 0;
+    if (n && nck) {
+        mlz::search_many_index(patterns, pattern_len, n, &index);
+        uint64_t unserved = 0;
+        const int64_t pr = dev_reader_search_plan(rd, sm, flags, patterns, index.off, n, &take, &n_take, &unserved);
+        if (pr) return pr;
+        c->search_chunks = n_take;
+        if (stats) { stats[1] = n_take; stats[2] = c->search_tables; stats[3] = unserved; }
+    }
+    Carve cv, pin, up;   // workspace: totals | marks, then S | C | the backward scan | ranks | the index | the decode's; pinned: the decode's | the index
+    const auto r_tot = cv.take<mlz::GrepTotals>(1);
+    const auto r_sel = cv.take<uint32_t>(size_t(W)), r_ctx = cv.take<uint32_t>(size_t(W)), r_above = cv.take<uint32_t>(size_t(W)), r_rank = cv.take<uint32_t>(size_t(W));
+    SearchDecode sd;
+    const uint32_t blob_bytes = n_take ? index.off[n] : 0;
+    const size_t nheads = index.heads.size();
+    Region<uint16_t> u_heads{}, u_order{};
+    Region<uint32_t> u_off{};
+    Region<uint8_t> u_blob{}, r_up{}, r_hup{};
+    if (n_take) {
+        search_decode_plan(rd, take, n_take, index.lmin, index.lmax, mlz::kSearchManyTile, &sd);
+        if (sd.lay.tiles.size() > 0x7fffffffu) return -MLZ_ERR_ARG;
+        u_heads = up.take<uint16_t>(nheads); u_order = up.take<uint16_t>(n);   // the pattern index as one block, as the search for many lays it out
+        u_off = up.take<uint32_t>(n + 1);
+        u_blob = up.take<uint8_t>(size_t(blob_bytes) + 4);
+        r_up = cv.take<uint8_t>(up.bytes);
+        search_decode_take(&sd, &cv, &pin);
+        r_hup = pin.take<uint8_t>(up.bytes);
+        const int e = search_decode_ready(c, sd, cv, pin);
+        if (e) return e;
+    } else {
+        HIPCHK(c, c->d_rplan.ensure(cv.bytes));
+        const int e = ensure_stream_objects(c, 0, 64);
+        if (e) return e;
+    }
+    void* ws = c->d_rplan.p;
+    mlz::GrepTotals* d_tot = r_tot.at(ws);
+    uint32_t *d_sel = r_sel.at(ws), *d_ctx = r_ctx.at(ws), *d_above = r_above.at(ws), *d_rank = r_rank.at(ws);
+    const uint64_t* D = static_cast<const uint64_t*>(rd->d_index);
+    { WorkspaceOrder order(c, sm); }
+    HIPCHK(c, hipMemsetAsync(d_tot, 0, sizeof(mlz::GrepTotals), sm));
+    HIPCHK(c, hipMemsetAsync(d_sel, 0, size_t(W) * 4, sm));
+    if (n_take) {
+        const bool in_lds = mlz::search_many_lds(uint32_t(n), index.hb, blob_bytes, true).words * 4 <= mlz::kSearchManyLdsBudget;
+        void *d_up = r_up.at(ws), *h_up = r_hup.at(c->pinned2);
+        std::memcpy(u_heads.at(h_up), index.heads.data(), nheads * 2);
+        std::memcpy(u_order.at(h_up), index.order.data(), n * 2);
+        std::memcpy(u_off.at(h_up), index.off.data(), (n + 1) * 4);
+        std::memcpy(u_blob.at(h_up), patterns, blob_bytes);
+        const mlz::SearchManyIx ix{u_heads.at(d_up), u_order.at(d_up), u_off.at(d_up), u_blob.at(d_up), uint32_t(n), index.hb, index.m, index.lmax, blob_bytes, in_lds ? 1u : 0u};
+        const uint32_t lds_bytes = mlz::search_many_lds(uint32_t(n), index.hb, blob_bytes, in_lds).words * 4;
+        const mlz::SearchTile* d_tiles = sd.tiles.at(ws);
+        const mlz::SearchManyMark mk{D, rd->index_k, d_sel};
+        HIPCHK(c, hipMemcpyAsync(d_up, h_up, up.bytes, hipMemcpyHostToDevice, sm));
+        const int64_t r = search_decode_run(rd, sm, ignore_crc, &sd, [&](size_t, size_t t0, size_t t1) {
+            hipLaunchKernelGGL(mlz::search_many_kernel<mlz::kSearchManyMarkRecords>, dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), lds_bytes, sm, c->d_range.as<uint8_t>(), d_tiles,
+                               uint32_t(t0), ix, static_cast<uint32_t*>(nullptr), static_cast<unsigned long long*>(nullptr), static_cast<const uint64_t*>(nullptr), uint64_t(0),
+                               static_cast<uint64_t*>(nullptr), static_cast<uint32_t*>(nullptr), mk);
+            return 0;
+        });
+        if (r < 0) return r;   // (nothing has been written to the caller's arrays)
+    }
+    hipLaunchKernelGGL(mlz::grep_select_kernel, dim3(1), dim3(mlz::kGrepScanThreads), 0, sm, d_sel, d_ctx, d_above, d_rank, W, N, (flags & MLZ_GREP_INVERT) ? 1u : 0u,
+                       mlz::grep_clamp(before, N), mlz::grep_clamp(after, N), d_tot);
+    hipLaunchKernelGGL(mlz::grep_compact_kernel, dim3(uint32_t((W + mlz::kGrepCompactThreads - 1) / mlz::kGrepCompactThreads)), dim3(mlz::kGrepCompactThreads), 0, sm,
+                       static_cast<const uint32_t*>(d_ctx), static_cast<const uint32_t*>(d_sel), static_cast<const uint32_t*>(d_rank), W, D, rd->index_k, uint64_t(rd->size), out.rec_cap,
+                       out.d_rec_no, out.d_rec_kind, d_tot);
+    const int e = fetch(c, sm, c->pinned2, d_tot, sizeof(mlz::GrepTotals));
+    if (e) return e;
+    const mlz::GrepTotals t = *static_cast<const mlz::GrepTotals*>(c->pinned2);
+    if (t.records > N || t.selected > t.records || t.written > t.bytes || t.bytes > uint64_t(rd->size)) {
+        c->err = "mlz_dev_reader_grep_records: the totals do not fit the index";
+        return -MLZ_ERR_HIP;
+    }
+    if (totals) { totals[0] = t.records; totals[1] = t.selected; totals[2] = t.written; totals[3] = t.bytes; }
+    return int64_t(t.records);
+}
+
+}  // namespace
+
+extern "C" int64_t mlz_dev_reader_grep_records(mlz_dev_reader* rd, void* stream, uint32_t flags, const uint8_t* patterns, const uint32_t* pattern_len, size_t n_patterns, uint64_t before,
+                                               uint64_t after, uint64_t* d_rec_no, uint8_t* d_rec_kind, size_t rec_cap, uint64_t* totals, uint64_t* stats) {
+    if (!rd || n_patterns > MLZ_SEARCH_MAX_PATTERNS || (n_patterns && (!patterns || !pattern_len)) || (rec_cap && !d_rec_no)) return -MLZ_ERR_ARG;
+    size_t blob = 0;
+    for (size_t i = 0; i < n_patterns; i++) {
+        if (pattern_len[i] == 0 || pattern_len[i] > mlz::kSearchMaxPattern) return -MLZ_ERR_ARG;
+        blob += pattern_len[i];
+    }
+    mlz_ctx* c = rd->ctx;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!rd->index_ready || rd->index_n >= mlz::kGrepMaxRecords) return -MLZ_ERR_ARG;
+    if (blob && std::memchr(patterns, rd->index_delim, blob)) return -MLZ_ERR_ARG;   // a line search cannot match across lines
+    if (hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
+    if (rec_cap && (!on_device(c, d_rec_no) || (d_rec_kind && !on_device(c, d_rec_kind)))) return -MLZ_ERR_ARG;
+    begin_decode_call(c);
+    hipStream_t sm = static_cast<hipStream_t>(stream);
+    const GrepOut out{rec_cap ? d_rec_no : nullptr, rec_cap ? d_rec_kind : nullptr, uint64_t(rec_cap)};
+    return settled(sm, dev_reader_grep_locked(rd, sm, flags, patterns, pattern_len, n_patterns, before, after, out, totals, stats));
+}

@@ -5,12 +5,16 @@
 // pattern's windows and their hashes (search_pattern_hashes: work proportional to the patterns); search_plan_kernel, one lane per (data chunk,
 // pattern), probes the chunk's table and the next one's in every table set and applies the decoded-set rule of that pattern to ONE byte array:
 // the union of the patterns' sets.  Only those nck bytes come back.  A pattern the tables cannot serve puts every chunk into the set, so the kernel is not run then.
-// Scan: the set is decoded once, group by group (search_decode_run), and search_many_kernel<false> examines each tile of start positions:
+// Scan: the set is decoded once, group by group (search_decode_run), and search_many_kernel<kSearchManyCount> examines each tile of start positions:
 // the tile's bytes are staged in LDS, a lane walks 64 neighbouring positions, hashes the first m bytes of each to a bucket of the pattern
 // index (heads and order in LDS) and verifies the bucket's patterns as far as the run holds their bytes.  Per-pattern counts gather in LDS and leave
 // with one 64-bit atomic per non-zero counter.  Per group, search_prefix_kernel then continues the running sum over the tile counts
-// and search_many_kernel<true> finds the pairs of the tiles below `cap` again, while the group's bytes are still in the scratch, and
+// and search_many_kernel<kSearchManyWrite> finds the pairs of the tiles below `cap` again, while the group's bytes are still in the scratch, and
 // writes (position, pattern) in ascending order.
+// The grep over the record index (mlz_stream_grep.hip.inc) runs the same walk in a third mode, once per group: every verified pair sets the bit
+// of its position's record in a bitmap, and nothing is counted or written.
+
+#include "mlz_stream_grep.h"
 
 namespace mlz {
 
@@ -39,13 +43,20 @@ __host__ __device__ inline SearchManyLds search_many_lds(uint32_t n, uint32_t hb
     return l;
 }
 
-// One workgroup per tile.  kWrite = false: counts[tile] = the tile's pairs, pat_counts[p] += pattern p's.  kWrite = true: the pairs of a tile
-// whose first pair lies below cap go to out_pos / out_which from prefix[tile] on, as far as they lie below cap.
-template <bool kWrite>
+// The third mode's arguments: the handle's record index D[0, k) and the bitmap of its records, a bit each
+struct SearchManyMark { const uint64_t* D; uint64_t k; uint32_t* bits; };
+enum { kSearchManyCount = 0, kSearchManyWrite = 1, kSearchManyMarkRecords = 2 };
+
+// One workgroup per tile.  kSearchManyCount: counts[tile] = the tile's pairs, pat_counts[p] += pattern p's.  kSearchManyWrite: the pairs of a tile
+// whose first pair lies below cap go to out_pos / out_which from prefix[tile] on, as far as they lie below cap.  kSearchManyMarkRecords: bit
+// number(position) of mk.bits is set for every pair (mlz_stream_grep.h, mark); the tile's two record numbers lie in the scan words of the LDS
+// layout, which this mode does not use otherwise, and every lane reads the same two words (a broadcast).
+template <int kMode>
 __global__ __launch_bounds__(kSearchManyThreads) void search_many_kernel(const uint8_t* __restrict__ scratch, const SearchTile* __restrict__ tiles, uint32_t tile0, SearchManyIx ix,
                                                                          uint32_t* __restrict__ tile_counts, unsigned long long* __restrict__ pat_counts,
                                                                          const uint64_t* __restrict__ prefix, uint64_t cap, uint64_t* __restrict__ out_pos,
-                                                                         uint32_t* __restrict__ out_which) {
+                                                                         uint32_t* __restrict__ out_which, SearchManyMark mk) {
+    constexpr bool kWrite = kMode == kSearchManyWrite;
     extern __shared__ uint32_t lds[];
     const uint32_t tid = threadIdx.x, tile = tile0 + blockIdx.x;
     uint64_t first = 0;
@@ -60,7 +71,7 @@ __global__ __launch_bounds__(kSearchManyThreads) void search_many_kernel(const u
     const SearchTile t = tiles[tile];
     for (uint32_t i = tid; i < (1u << ix.hb) + 1; i += kSearchManyThreads) heads[i] = ix.heads[i];
     for (uint32_t i = tid; i < ix.n; i += kSearchManyThreads) order[i] = ix.order[i];
-    if (!kWrite) for (uint32_t i = tid; i < ix.n; i += kSearchManyThreads) counts[i] = 0;
+    if (kMode == kSearchManyCount) for (uint32_t i = tid; i < ix.n; i += kSearchManyThreads) counts[i] = 0;
     const uint32_t* off = ix.off;
     const uint8_t* blob = ix.blob;
     if (ix.in_lds) {
@@ -78,6 +89,8 @@ __global__ __launch_bounds__(kSearchManyThreads) void search_many_kernel(const u
     if (avail > t.hi_end) avail = t.hi_end;
     const uint32_t* gw = reinterpret_cast<const uint32_t*>(scratch + (t.src_off - shift));
     for (uint32_t w = tid; w < (shift + avail + 3) / 4; w += kSearchManyThreads) tw[w + (w >> 4)] = gw[w];
+    if (kMode == kSearchManyMarkRecords && tid < 2 && t.count)   // two lanes: the numbers of the tile's first and last start position (below 2^32)
+        scan[tid] = uint32_t(rindex_number([&](uint64_t j) { return mk.D[j]; }, mk.k, tid ? t.gpos + t.count - 1 : t.gpos));
     __syncthreads();
     auto byte_at = [&](uint32_t i) { return uint32_t(tb[search_many_skew(shift + i)]); };
     const uint32_t i0 = tid * kSearchManyPer, i1 = i0 + kSearchManyPer < t.count ? i0 + kSearchManyPer : t.count;
@@ -99,7 +112,16 @@ __global__ __launch_bounds__(kSearchManyThreads) void search_many_kernel(const u
     };
     auto plus = [](uint32_t x, uint32_t y) { return x + y; };
     uint32_t cnt = 0;
-    if (!kWrite) {
+    if (kMode == kSearchManyMarkRecords) {
+        const GrepNarrow nr{scan[0], scan[1]};
+        walk([&](uint32_t i, uint32_t) {
+            const uint64_t r = grep_number_between([&](uint64_t j) { return mk.D[j]; }, nr, t.gpos + i);
+            uint32_t* word = mk.bits + (r >> 5);
+            const uint32_t bit = 1u << (uint32_t(r) & 31);
+            // the test in front of the atomic: a record with thousands of occurrences costs a few atomics, not thousands; a stale word only costs another
+            if (!(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit)) atomicOr(word, bit);
+        });
+    } else if (kMode == kSearchManyCount) {
         walk([&](uint32_t, uint32_t p) { atomicAdd(&counts[p], 1u); cnt++; });
         uint32_t total;
         wg_scan<kSearchManyThreads>(cnt, scan, tid, plus, &total);   // (its barriers also settle the counters)
@@ -186,11 +208,11 @@ int64_t dev_reader_search_many_locked(mlz_dev_reader* rd, hipStream_t sm, uint32
     HIPCHK(c, hipMemcpyAsync(d_up, h_up, up.bytes, hipMemcpyHostToDevice, sm));
     const int64_t r = search_decode_run(rd, sm, ignore_crc, &sd, [&](size_t, size_t t0, size_t t1) {
         const uint8_t* scratch = c->d_range.as<uint8_t>();
-        hipLaunchKernelGGL(mlz::search_many_kernel<false>, dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), lds_bytes, sm, scratch, d_tiles, uint32_t(t0), ix, d_tc, d_pc,
-                           static_cast<const uint64_t*>(nullptr), uint64_t(0), static_cast<uint64_t*>(nullptr), static_cast<uint32_t*>(nullptr));
+        hipLaunchKernelGGL(mlz::search_many_kernel<mlz::kSearchManyCount>, dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), lds_bytes, sm, scratch, d_tiles, uint32_t(t0), ix, d_tc, d_pc,
+                           static_cast<const uint64_t*>(nullptr), uint64_t(0), static_cast<uint64_t*>(nullptr), static_cast<uint32_t*>(nullptr), mlz::SearchManyMark{});
         hipLaunchKernelGGL(mlz::search_prefix_kernel, dim3(1), dim3(1024), 0, sm, d_tc, uint32_t(t0), uint32_t(t1), d_prefix, d_total);
-        if (cap) hipLaunchKernelGGL(mlz::search_many_kernel<true>, dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), lds_bytes, sm, scratch, d_tiles, uint32_t(t0), ix, d_tc, d_pc,
-                                    static_cast<const uint64_t*>(d_prefix), cap, d_offsets, d_which);
+        if (cap) hipLaunchKernelGGL(mlz::search_many_kernel<mlz::kSearchManyWrite>, dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), lds_bytes, sm, scratch, d_tiles, uint32_t(t0), ix, d_tc, d_pc,
+                                    static_cast<const uint64_t*>(d_prefix), cap, d_offsets, d_which, mlz::SearchManyMark{});
         return 0;
     });
     if (r < 0) return r;

@@ -377,6 +377,37 @@ class DeviceStream:
             self.reader.record_numbers(positions.data_ptr(), n, out.data_ptr(), stream=st)
         return out
 
+    def grep(self, patterns, invert=False, before=0, after=0, max_records=1 << 20, count_only=False, ignore_crc=False, no_tables=False):
+        """grep over the decoded stream's lines: the records that hold one of `patterns` (a sequence of up to 4096 bytes objects of
+        1 .. 256 bytes without the delimiter; a single bytes object is one pattern), with invert those that hold none, and `before` /
+        `after` context records around each, every record once, in stream order.  Builds the record index for b"\n" when the stream has
+        none (index_records chooses another delimiter).
+        -> (R, numbers, kinds, data, starts): the number of such records; the smallest min(R, max_records) record numbers (int64); 1 for a
+        selected record and 0 for one that is context only (uint8); those records' bytes back to back (uint8) and the k + 1 places where
+        they start in it and its size (int64) — tensors on the stream's device.
+        count_only (grep -c): -> (R, the selected records) and nothing is written or read."""
+        from . import api
+        dev = self.t.device
+        pats = [patterns] if isinstance(patterns, (bytes, bytearray)) else list(patterns)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        try:
+            self.reader.record_count()
+        except api.MinLZError:   # (no index yet)
+            self.reader.index_records(b"\n", ignore_crc=ignore_crc, stream=st)
+        kw = dict(invert=invert, before=before, after=after, ignore_crc=ignore_crc, no_tables=no_tables, stream=st)
+        if count_only:
+            _, totals, _ = self.reader.grep_records(pats, None, None, 0, **kw)
+            return totals[0], totals[1]
+        cap = min(max_records, self.reader.record_count())
+        numbers = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        kinds = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        R, totals, _ = self.reader.grep_records(pats, numbers.data_ptr() if cap else None, kinds.data_ptr() if cap else None, cap, **kw)
+        k = min(R, cap)
+        starts = torch.zeros(k + 1, dtype=torch.int64, device=dev)
+        data = torch.empty(max(totals[2], 1), dtype=torch.uint8, device=dev)
+        got = self.reader.read_records(numbers.data_ptr(), k, data.data_ptr(), totals[2], d_starts=starts.data_ptr(), ignore_crc=ignore_crc, stream=st) if k else 0
+        return R, numbers[:k], kinds[:k], data[:got], starts
+
     def read_record_range(self, first, count, ignore_crc=False):
         """Records first .. first + count - 1 as they lie in the decoded stream, the delimiters between them included -> a new uint8 tensor."""
         off, ln = self.reader.record_range(first, count)
