@@ -16,6 +16,8 @@
 // stream_tabhdr_kernel write the device-resident Writer's chunk headers).  StreamTables is the one configuration of the search tables,
 // whichever call it came in by.
 
+#include "mlz_stream_scratch.h"
+
 namespace {
 
 constexpr uint8_t kChunkUncompressed = 0x01, kChunkMinLZ = 0x02, kChunkMinLZCompCRC = 0x03, kChunkEOF = 0x20, kChunkIndex = 0x40,
@@ -253,12 +255,7 @@ int64_t first_own_verdict(const std::vector<int64_t>& rcs) {
 // alias, the caller's page-locked buffer (the per-block copy-out of a pinned buffer runs as shader copies on this ROCm build and queues up
 // behind every kernel of the stream: 22.6 GB/s against 31.3 into pageable memory for 100 MB).  desc.pad selects the source: for the Writer
 // 0 = the encoder's output, 1 = the raw block (stored chunks), 2 = the block's search table; a caller with fewer sources passes nullptr.
-struct PlaceDesc { uint64_t src_off, dst_off; uint32_t len, pad; };
-constexpr uint32_t kPlacePiece = 64 << 10;
-// The span of `len` bytes from src_off to dst_off, cut into pieces of 64 KiB: put(PlaceDesc) for each, in order
-template <class Put> void place_pieces(uint64_t src_off, uint64_t dst_off, uint64_t len, uint32_t pad, Put put) {
-    for (uint64_t o = 0; o < len; o += kPlacePiece) put(PlaceDesc{src_off + o, dst_off + o, uint32_t(std::min<uint64_t>(kPlacePiece, len - o)), pad});
-}
+using mlz::PlaceDesc; using mlz::kPlacePiece; using mlz::place_pieces;   // mlz_stream_scratch.h
 __global__ __launch_bounds__(256) void stream_place_kernel(const uint8_t* __restrict__ src0, const uint8_t* __restrict__ src1, const uint8_t* __restrict__ src2,
                                                            uint8_t* __restrict__ dst, const PlaceDesc* __restrict__ descs) {
     const PlaceDesc d = descs[blockIdx.x];

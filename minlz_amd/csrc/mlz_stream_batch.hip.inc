@@ -10,9 +10,9 @@
 //            walk_batch_kernel<true> writes the records.  No region tables: 32 bytes per table entry, 8 bytes and a flag bit per stream.
 //            A lane stops after kBatchWalkSteps headers; its stream is LONG and goes through stream_walk_device inside the same call.
 //            Two read-backs: places, long flags and the sum; then the table.  walk_parse_table runs per stream on the host.
-//   decode   the chunks of all streams form ONE job list (bodies relative to d_src, targets in d_dst), grouped by range_group_ends and run by
-//            stream_run_chunk_jobs; stored chunks of all streams by one stream_place_kernel launch; per-job verdicts become per-stream ones
-//            by mlz::batch_stream_verdicts.
+//   decode   the chunks of all streams form ONE job list (bodies relative to d_src, targets in d_dst) for the in-place decode of the
+//            single-stream call (stream_decode_jobs_in_place: stored chunks of all streams by one stream_place_kernel launch, groups by
+//            range_group_ends); per-job verdicts become per-stream ones by mlz::batch_stream_verdicts.
 //   encode   the blocks of all streams through one encode_device_locked and one crc_device_locked; 12 bytes per block visit the host, which
 //            lays every stream out as stream_gather_range and stream_foot do for one; bodies, heads and feet by one stream_place_kernel
 //            launch (the heads and feet are host-made bytes, uploaded once), chunk headers by one stream_hdr_kernel launch.
@@ -90,7 +90,7 @@ int batch_args(mlz_ctx* c, const uint8_t* d_src, const uint8_t* d_dst, bool with
     // two destinations that overlap: one stream's bytes would change another's
     std::sort(d.begin(), d.end());
     for (size_t i = 1; i < d.size(); i++) if (d[i].first < d[i - 1].first + d[i - 1].second) return -MLZ_ERR_ARG;
-    if (hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_ARG; }
+    if (enter_device(c)) return -MLZ_ERR_ARG;
     if (!span_inside_allocation(d_src, src_end) || (with_dst && !span_inside_allocation(d_dst, dst_end))) return -MLZ_ERR_ARG;
     *run = c;
     return 0;
@@ -185,38 +185,14 @@ int64_t stream_decode_batch_locked(mlz_ctx* c, hipStream_t sm, bool ignore_crc, 
     std::vector<size_t> job_first(n + 1, 0);
     std::vector<ChunkJob> jobs;
     jobs.reserve(bw.chunks.size());
-    size_t n_place = 0;
     for (size_t i = 0; i < n; i++) {
         job_first[i] = jobs.size();
         if (bw.prefix(i) > streams[i].dst_cap) { verdict[i] = -MLZ_ERR_DST_TOO_SMALL; continue; }
-        for (size_t k = bw.c0[i]; k < bw.c1[i]; k++) {
-            const StreamChunk& ck = bw.chunks[k];
-            jobs.push_back(ChunkJob{k, d_dst + streams[i].dst_off + ck.out_off});
-            if (ck.type == kChunkUncompressed) n_place += (ck.n + kPlacePiece - 1) / kPlacePiece;
-        }
+        for (size_t k = bw.c0[i]; k < bw.c1[i]; k++) jobs.push_back(ChunkJob{k, d_dst + streams[i].dst_off + bw.chunks[k].out_off});
     }
     job_first[n] = jobs.size();
-    const size_t nj = jobs.size();
-    Carve pin;
-    const ChunkJobResults res = take_chunk_job_results(&pin, nj);
-    const auto r_place = pin.take<PlaceDesc>(n_place, 64);
-    if ((r = ensure_stream_objects(c, 0, pin.bytes))) return r;
-    if (n_place) {   // the stored chunks of all streams: 64 KiB pieces, one launch
-        HIPCHK(c, c->d_place.ensure(n_place * sizeof(PlaceDesc)));
-        PlaceDesc* h_place = r_place.at(c->pinned2);
-        size_t q = 0;
-        for (const ChunkJob& jb : jobs) {
-            const StreamChunk& ck = bw.chunks[jb.ck];
-            if (ck.type == kChunkUncompressed) place_pieces(ck.body_off, uint64_t(jb.at - d_dst), ck.n, 0, [&](const PlaceDesc& d) { h_place[q++] = d; });
-        }
-        WorkspaceOrder order(c, sm);
-        HIPCHK(c, hipMemcpyAsync(c->d_place.p, h_place, n_place * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
-        hipLaunchKernelGGL(stream_place_kernel, dim3(uint32_t(n_place)), dim3(256), 0, sm, d_src, nullptr, nullptr, d_dst, c->d_place.as<PlaceDesc>());
-    }
-    std::vector<size_t> gend;
-    mlz::range_group_ends(nj, [&](size_t j) { return uint64_t(bw.chunks[jobs[j].ck].n); }, &gend);
     std::vector<int64_t> job_rc;
-    const int64_t e = stream_run_chunk_jobs(c, sm, ignore_crc, d_src, bw.chunks, jobs, gend, res, [](size_t) { return 0; }, &job_rc);
+    const int64_t e = stream_decode_jobs_in_place(c, sm, ignore_crc, d_src, bw.chunks, jobs, d_dst, &job_rc);
     if (e) return e;
     mlz::batch_stream_verdicts(verdict.data(), job_first.data(), job_rc.data(), n, out_len);
     return 0;

@@ -2,7 +2,7 @@
 // context records, record numbers out (included at the end of mlz_hip.hip, behind the record index, whose table it reads, and the search for
 // many patterns, whose plan, decode and walk it runs).  The rules are those of mlz_stream_grep.h, which the host check runs as plain loops.
 //
-//   mark      the search phase of mlz_dev_reader_search_many, unchanged (dev_reader_search_plan, search_decode_plan / take / ready / run), with
+//   mark      the search phase of mlz_dev_reader_search_many, unchanged (dev_reader_search_plan, search_decode_plan / ready / run), with
 //             search_many_kernel<kSearchManyMarkRecords> on every group: one pass, a verified pair sets the bit of its position's record in a
 //             bitmap of N bits in the workspace.  No count pass, no prefix, no position list.
 //   select    grep_select_kernel (one workgroup, a slab of words per lane, as rindex_scan_kernel and records_number_kernel run): the
@@ -97,31 +97,19 @@ int64_t dev_reader_grep_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flag
     size_t n_take = 0;
     if (n && nck) {
         mlz::search_many_index(patterns, pattern_len, n, &index);
-        uint64_t unserved = 0;
-        const int64_t pr = dev_reader_search_plan(rd, sm, flags, patterns, index.off, n, &take, &n_take, &unserved);
+        const int64_t pr = dev_reader_search_plan(rd, sm, flags, patterns, index.off, n, &take, &n_take, stats, true);
         if (pr) return pr;
-        c->search_chunks = n_take;
-        if (stats) { stats[1] = n_take; stats[2] = c->search_tables; stats[3] = unserved; }
     }
-    Carve cv, pin, up;   // workspace: totals | marks, then S | C | the backward scan | ranks | the index | the decode's; pinned: the decode's | the index
+    Carve cv, pin;   // workspace: totals | marks, then S | C | the backward scan | ranks | the index | the decode's; pinned: the index | the decode's
     const auto r_tot = cv.take<mlz::GrepTotals>(1);
     const auto r_sel = cv.take<uint32_t>(size_t(W)), r_ctx = cv.take<uint32_t>(size_t(W)), r_above = cv.take<uint32_t>(size_t(W)), r_rank = cv.take<uint32_t>(size_t(W));
     SearchDecode sd;
-    const uint32_t blob_bytes = n_take ? index.off[n] : 0;
-    const size_t nheads = index.heads.size();
-    Region<uint16_t> u_heads{}, u_order{};
-    Region<uint32_t> u_off{};
-    Region<uint8_t> u_blob{}, r_up{}, r_hup{};
+    SearchManyUpload up;
     if (n_take) {
         search_decode_plan(rd, take, n_take, index.lmin, index.lmax, mlz::kSearchManyTile, &sd);
         if (sd.lay.tiles.size() > 0x7fffffffu) return -MLZ_ERR_ARG;
-        u_heads = up.take<uint16_t>(nheads); u_order = up.take<uint16_t>(n);   // the pattern index as one block, as the search for many lays it out
-        u_off = up.take<uint32_t>(n + 1);
-        u_blob = up.take<uint8_t>(size_t(blob_bytes) + 4);
-        r_up = cv.take<uint8_t>(up.bytes);
-        search_decode_take(&sd, &cv, &pin);
-        r_hup = pin.take<uint8_t>(up.bytes);
-        const int e = search_decode_ready(c, sd, cv, pin);
+        up.take(index, n, &cv, &pin);   // the pattern index, as the search for many lays it out
+        const int e = search_decode_ready(rd, &sd, &cv, &pin);
         if (e) return e;
     } else {
         HIPCHK(c, c->d_rplan.ensure(cv.bytes));
@@ -136,20 +124,13 @@ int64_t dev_reader_grep_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flag
     HIPCHK(c, hipMemsetAsync(d_tot, 0, sizeof(mlz::GrepTotals), sm));
     HIPCHK(c, hipMemsetAsync(d_sel, 0, size_t(W) * 4, sm));
     if (n_take) {
-        const bool in_lds = mlz::search_many_lds(uint32_t(n), index.hb, blob_bytes, true).words * 4 <= mlz::kSearchManyLdsBudget;
-        void *d_up = r_up.at(ws), *h_up = r_hup.at(c->pinned2);
-        std::memcpy(u_heads.at(h_up), index.heads.data(), nheads * 2);
-        std::memcpy(u_order.at(h_up), index.order.data(), n * 2);
-        std::memcpy(u_off.at(h_up), index.off.data(), (n + 1) * 4);
-        std::memcpy(u_blob.at(h_up), patterns, blob_bytes);
-        const mlz::SearchManyIx ix{u_heads.at(d_up), u_order.at(d_up), u_off.at(d_up), u_blob.at(d_up), uint32_t(n), index.hb, index.m, index.lmax, blob_bytes, in_lds ? 1u : 0u};
-        const uint32_t lds_bytes = mlz::search_many_lds(uint32_t(n), index.hb, blob_bytes, in_lds).words * 4;
         const mlz::SearchTile* d_tiles = sd.tiles.at(ws);
         const mlz::SearchManyMark mk{D, rd->index_k, d_sel};
-        HIPCHK(c, hipMemcpyAsync(d_up, h_up, up.bytes, hipMemcpyHostToDevice, sm));
+        const int e = up.send(c, sm, index, patterns, n);
+        if (e) return e;
         const int64_t r = search_decode_run(rd, sm, ignore_crc, &sd, [&](size_t, size_t t0, size_t t1) {
-            hipLaunchKernelGGL(mlz::search_many_kernel<mlz::kSearchManyMarkRecords>, dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), lds_bytes, sm, c->d_range.as<uint8_t>(), d_tiles,
-                               uint32_t(t0), ix, static_cast<uint32_t*>(nullptr), static_cast<unsigned long long*>(nullptr), static_cast<const uint64_t*>(nullptr), uint64_t(0),
+            hipLaunchKernelGGL(mlz::search_many_kernel<mlz::kSearchManyMarkRecords>, dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), up.lds_bytes, sm, c->d_range.as<uint8_t>(), d_tiles,
+                               uint32_t(t0), up.ix, static_cast<uint32_t*>(nullptr), static_cast<unsigned long long*>(nullptr), static_cast<const uint64_t*>(nullptr), uint64_t(0),
                                static_cast<uint64_t*>(nullptr), static_cast<uint32_t*>(nullptr), mk);
             return 0;
         });
@@ -185,7 +166,7 @@ extern "C" int64_t mlz_dev_reader_grep_records(mlz_dev_reader* rd, void* stream,
     std::lock_guard<std::mutex> lk(c->mu);
     if (!rd->index_ready || rd->index_n >= mlz::kGrepMaxRecords) return -MLZ_ERR_ARG;
     if (blob && std::memchr(patterns, rd->index_delim, blob)) return -MLZ_ERR_ARG;   // a line search cannot match across lines
-    if (hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
+    if (enter_device(c)) return -MLZ_ERR_HIP;
     if (rec_cap && (!on_device(c, d_rec_no) || (d_rec_kind && !on_device(c, d_rec_kind)))) return -MLZ_ERR_ARG;
     begin_decode_call(c);
     hipStream_t sm = static_cast<hipStream_t>(stream);

@@ -309,7 +309,7 @@ extern "C" int64_t mlz_dev_reader_read_device(mlz_dev_reader* rd, void* stream, 
     std::lock_guard<std::mutex> lk(c->mu);
     c->range_plan_host = 0;
     if (n_ranges == 0) return 0;
-    if (hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
+    if (enter_device(c)) return -MLZ_ERR_HIP;
     if (!on_device(c, d_off) || !on_device(c, d_len) || (d_dst && !on_device(c, d_dst)) || (d_starts && !on_device(c, d_starts))) return -MLZ_ERR_ARG;
     begin_decode_call(c);
     c->range_chunks = c->range_scratch = 0;

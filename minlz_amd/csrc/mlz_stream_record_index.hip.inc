@@ -4,7 +4,7 @@
 // host check runs as plain loops.
 //
 // Build (mlz_dev_reader_index_records): the handle's data chunks with bytes are decoded group by group (about 64 MiB, range_group_ends) into
-// the ReadSeeker's scratch, side by side from scratch[0] on (stream_run_chunk_jobs; stored chunks are copied there).  Per group:
+// the ReadSeeker's scratch, side by side from scratch[0] on (ScratchDecode, mlz_stream_walk.hip.inc; stored chunks are copied there).  Per group:
 //   count   rindex_count_kernel: a workgroup per 64 KiB tile, a 16-byte load per lane and step, the popcounts reduced to one word per tile;
 //   scan    rindex_scan_kernel (one workgroup): the tiles' exclusive bases and the group's total, which comes home (8 bytes); the host adds
 //           it to the running base and grows the table to fit (exactly with one group, else geometrically with a device-to-device copy);
@@ -141,63 +141,42 @@ int64_t dev_reader_index_records_locked(mlz_dev_reader* rd, hipStream_t sm, bool
     mlz_ctx* c = rd->ctx;
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t size = uint64_t(rd->size);
-    std::vector<size_t> dc;   // the data chunks with bytes
-    for (size_t k = 0; k < rd->chunks.size(); k++) if (rd->chunks[k].n) dc.push_back(k);
+    ScratchDecode dec;   // the data chunks with bytes; a group's chunks side by side from scratch[0] on
+    const std::vector<size_t> dc = mlz::chunks_with_bytes(rd->chunks.size(), [&](size_t k) { return rd->chunks[k].n; });
     const size_t nd = dc.size();
-    std::vector<size_t> gend;
-    mlz::range_group_ends(nd, [&](size_t i) { return uint64_t(rd->chunks[dc[i]].n); }, &gend);
-    const size_t ng = gend.size();
-    // the decode list: a group's chunks side by side from scratch[0] on
-    std::vector<ChunkJob> jobs(nd);
-    std::vector<uint64_t> at(nd), gbytes(ng), gfirst(ng);
-    std::vector<size_t> place_end(ng);
-    std::vector<PlaceDesc> places;
-    uint64_t scratch_max = 0;
+    mlz::range_group_ends(nd, [&](size_t i) { return uint64_t(rd->chunks[dc[i]].n); }, &dec.gend);
+    const size_t ng = dec.gend.size();
+    dec.jobs.resize(nd); dec.at.resize(nd);
+    std::vector<uint64_t> gbytes(ng), gfirst(ng);
     for (size_t g = 0, i = 0; g < ng; g++) {
         uint64_t o = 0;
         gfirst[g] = uint64_t(rd->chunks[dc[i]].out_off);
-        for (; i < gend[g]; i++) {
+        for (; i < dec.gend[g]; i++) {
             const StreamChunk& ck = rd->chunks[dc[i]];
             if (uint64_t(ck.out_off) != gfirst[g] + o) { c->err = "mlz_dev_reader_index_records: the chunks' output offsets are not contiguous"; return -MLZ_ERR_HIP; }
-            at[i] = o;
-            if (ck.type == kChunkUncompressed) place_pieces(ck.body_off, o, ck.n, 1, [&](const PlaceDesc& d) { places.push_back(d); });
+            dec.jobs[i] = ChunkJob{dc[i], nullptr}; dec.at[i] = o;
             o += ck.n;
         }
         gbytes[g] = o;
-        place_end[g] = places.size();
-        scratch_max = std::max(scratch_max, o);
     }
-    const uint64_t tiles_max = mlz::rindex_tiles(15, scratch_max);
-    Carve cv, pin;   // workspace: the group's total | tile counts | tile bases; pinned: the decode's results | the total | the stored chunks' pieces
+    Carve cv, pin;   // workspace: the group's total | tile counts | tile bases; pinned: the decode's | the total
+    int e = dec.take(c, rd->chunks, &pin);
+    if (e) return e;
+    const uint64_t tiles_max = mlz::rindex_tiles(15, dec.sp.scratch_max);
     const auto r_total = cv.take<uint64_t>(2);
     const auto r_count = cv.take<uint32_t>(size_t(tiles_max)), r_base = cv.take<uint32_t>(size_t(tiles_max));
-    const ChunkJobResults res = take_chunk_job_results(&pin, nd);
     const auto h_total_r = pin.take<uint64_t>(2);
-    const auto h_places_r = pin.take<PlaceDesc>(places.size(), 8);
     HIPCHK(c, c->d_records.ensure(cv.bytes));
-    HIPCHK(c, c->d_range.ensure(size_t(scratch_max) + 64));
-    if (!places.empty()) HIPCHK(c, c->d_place.ensure(places.size() * sizeof(PlaceDesc)));
-    int e = ensure_stream_objects(c, 0, pin.bytes);
-    if (e) return e;
+    if ((e = ensure_stream_objects(c, 0, pin.bytes))) return e;
     void* ws = c->d_records.p;
     uint8_t* scratch = c->d_range.as<uint8_t>();
     uint64_t *d_total = r_total.at(ws), *h_total = h_total_r.at(c->pinned2);
     uint32_t *d_count = r_count.at(ws), *d_base = r_base.at(ws);
-    for (size_t i = 0; i < nd; i++) {
-        const StreamChunk& ck = rd->chunks[dc[i]];
-        jobs[i] = ChunkJob{dc[i], ck.type == kChunkUncompressed ? rd->d_src + ck.body_off : scratch + at[i]};   // (a stored chunk's CRC: over the stream's own bytes)
-    }
     { WorkspaceOrder order(c, sm); }
-    if (!places.empty()) {
-        std::memcpy(h_places_r.at(c->pinned2), places.data(), places.size() * sizeof(PlaceDesc));
-        HIPCHK(c, hipMemcpyAsync(c->d_place.p, h_places_r.at(c->pinned2), places.size() * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
-    }
     RindexTable tab;
     uint64_t k = 0;
-    // a group's bytes are in the scratch (stored chunks: copied now): count, scan, the total home, room in the table, emit
+    // a group's bytes are in the scratch: count, scan, the total home, room in the table, emit
     auto index_group = [&](size_t g) -> int {
-        const size_t q0 = g ? place_end[g - 1] : 0, q1 = place_end[g];
-        if (q1 > q0) hipLaunchKernelGGL(stream_place_kernel, dim3(uint32_t(q1 - q0)), dim3(256), 0, sm, rd->d_src, rd->d_src, nullptr, scratch, c->d_place.as<PlaceDesc>() + q0);
         const uint64_t n = gbytes[g], ntiles = mlz::rindex_tiles(reinterpret_cast<uintptr_t>(scratch) & 15, n);
         if (ntiles == 0 || ntiles > tiles_max) { c->err = "mlz_dev_reader_index_records: a group's tiles do not fit the workspace"; return -MLZ_ERR_HIP; }
         hipLaunchKernelGGL(mlz::rindex_count_kernel, dim3(uint32_t(ntiles)), dim3(mlz::kRindexThreads), 0, sm, scratch, n, delim, d_count);
@@ -222,7 +201,7 @@ int64_t dev_reader_index_records_locked(mlz_dev_reader* rd, hipStream_t sm, bool
         k += total;
         return 0;
     };
-    const int64_t r = stream_run_chunk_jobs(c, sm, ignore_crc, rd->d_src, rd->chunks, jobs, gend, res, index_group);
+    const int64_t r = dec.run(c, sm, ignore_crc, rd->d_src, rd->chunks, index_group);
     if (r < 0) return r;
     HIPCHK(c, hipStreamSynchronize(sm));
     HIPCHK(c, hipGetLastError());
@@ -280,7 +259,7 @@ int64_t mlz_dev_reader_index_records(mlz_dev_reader* rd, void* stream, uint32_t 
     std::lock_guard<std::mutex> lk(c->mu);
     uint64_t decoded = 0;
     if (!(rd->index_ready && rd->index_delim == delimiter)) {
-        if (hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
+        if (enter_device(c)) return -MLZ_ERR_HIP;
         begin_decode_call(c);
         hipStream_t sm = static_cast<hipStream_t>(stream);
         const int64_t r = settled(sm, dev_reader_index_records_locked(rd, sm, (flags & MLZ_STREAM_IGNORE_CRC) != 0, delimiter, &decoded));
@@ -302,7 +281,7 @@ int64_t mlz_dev_reader_record_spans(mlz_dev_reader* rd, void* stream, const uint
     std::lock_guard<std::mutex> lk(c->mu);
     if (rindex_enter(rd, n)) return -MLZ_ERR_ARG;
     if (n == 0) return 0;
-    if (hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
+    if (enter_device(c)) return -MLZ_ERR_HIP;
     if (!on_device(c, d_idx) || !on_device(c, d_off) || !on_device(c, d_len)) return -MLZ_ERR_ARG;
     hipStream_t sm = static_cast<hipStream_t>(stream);
     mlz::RindexSums sums{};
@@ -319,7 +298,7 @@ int64_t mlz_dev_reader_read_records(mlz_dev_reader* rd, void* stream, uint32_t f
     if (rindex_enter(rd, n)) return -MLZ_ERR_ARG;
     c->range_plan_host = 0;
     if (n == 0) return 0;
-    if (hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
+    if (enter_device(c)) return -MLZ_ERR_HIP;
     if (!on_device(c, d_idx) || (d_dst && !on_device(c, d_dst)) || (d_starts && !on_device(c, d_starts))) return -MLZ_ERR_ARG;
     begin_decode_call(c);
     c->range_chunks = c->range_scratch = 0;
@@ -347,7 +326,7 @@ int64_t mlz_dev_reader_record_numbers(mlz_dev_reader* rd, void* stream, const ui
     std::lock_guard<std::mutex> lk(c->mu);
     if (rindex_enter(rd, n)) return -MLZ_ERR_ARG;
     if (n == 0) return 0;
-    if (hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
+    if (enter_device(c)) return -MLZ_ERR_HIP;
     if (!on_device(c, d_pos) || !on_device(c, d_no)) return -MLZ_ERR_ARG;
     hipStream_t sm = static_cast<hipStream_t>(stream);
     int64_t r = rindex_header(c, sm, sizeof(mlz::RindexSums));
@@ -364,7 +343,7 @@ int64_t mlz_dev_reader_record_range(mlz_dev_reader* rd, uint64_t first, uint64_t
     mlz_ctx* c = rd->ctx;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!rd->index_ready || first > rd->index_n || count > rd->index_n - first) return -MLZ_ERR_ARG;
-    if (hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
+    if (enter_device(c)) return -MLZ_ERR_HIP;
     const uint64_t k = rd->index_k, size = uint64_t(rd->size), last = count ? first + count - 1 : first;
     // the two entries of the table that the range's ends need
     uint64_t before = 0, behind = 0;

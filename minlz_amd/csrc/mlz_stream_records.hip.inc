@@ -299,7 +299,7 @@ extern "C" int64_t mlz_dev_reader_search_records(mlz_dev_reader* rd, void* strea
     if (std::memchr(pattern, delimiter, pattern_len)) return -MLZ_ERR_ARG;   // a line search cannot match across lines
     mlz_ctx* c = rd->ctx;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
+    if (enter_device(c)) return -MLZ_ERR_HIP;
     if ((dst_cap && !on_device(c, d_dst)) || (rec_cap && !on_device(c, d_rec_off)) || (d_rec_start && !on_device(c, d_rec_start)) ||
         (rec_cap && d_rec_flags && !on_device(c, d_rec_flags)))
         return -MLZ_ERR_ARG;

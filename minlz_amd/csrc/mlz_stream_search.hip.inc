@@ -9,8 +9,8 @@
 // that fits, and the existing CRC pass checks the tables.  Per call: the host hashes the pattern's windows (search_pattern_hashes),
 // search_plan_kernel looks them up in every table of every table set (one set for a stream's inline tables, up to four for an attached
 // sidecar: mlz_stream_sidecar.hip.inc) and applies the rule of mlz_stream_search.h (search_decoded_mark_all); one byte per chunk comes back:
-// the set of chunks to decode.  The search for many patterns plans through the same function.  stream_run_chunk_jobs decodes
-// exactly those into the scratch, chunks that are neighbours in the stream side by side, and search_scan_kernel marks the occurrences of every
+// the set of chunks to decode.  The search for many patterns plans through the same function.  The scratch decode (ScratchDecode,
+// mlz_stream_walk.hip.inc) brings exactly those into the scratch, chunks that are neighbours in the stream side by side, and search_scan_kernel marks the occurrences of every
 // run in a bitmap (one bit per decoded byte of the set) and counts them per tile.  search_prefix_kernel's scan over the tile counts and search_write_kernel then
 // put the smallest `cap` positions out in ascending order.  The call's body ends at the prefix kernel (dev_reader_search_scan_locked); the write and
 // the total's way home are steps of their own, so that the search for records (mlz_stream_records.hip.inc) can size its buffer by the total first.
@@ -233,11 +233,16 @@ int64_t dev_reader_search_sets(mlz_dev_reader* rd, hipStream_t sm, bool ignore_c
 // The host hashes every pattern's windows for every set (search_pattern_hashes); search_plan_kernel marks the set and one byte per chunk
 // comes back.  A pattern that is not served puts every chunk with a byte into the set, so the kernel is not run then.
 int64_t dev_reader_search_plan(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* patterns, const std::vector<uint32_t>& off, size_t n,
-                               std::vector<uint8_t>* take, size_t* n_take, uint64_t* unserved) {
+                               std::vector<uint8_t>* take, size_t* n_take, uint64_t* stats, bool many) {
     mlz_ctx* c = rd->ctx;
     const size_t nck = rd->chunks.size();
     const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0;
-    *unserved = n;
+    uint64_t unserved = n;
+    auto planned = [&]() {   // what every caller reports: counter 10, stats[1 .. 2] and, for many patterns, stats[3]
+        c->search_chunks = *n_take;
+        if (stats) { stats[1] = *n_take; stats[2] = c->search_tables; if (many) stats[3] = unserved; }
+        return 0;
+    };
     if (!(flags & MLZ_SEARCH_NO_TABLES)) {
         const mlz_dev_reader::SearchTables* stp = nullptr;
         const int64_t r = dev_reader_search_sets(rd, sm, ignore_crc, &stp);
@@ -270,9 +275,9 @@ int64_t dev_reader_search_plan(mlz_dev_reader* rd, hipStream_t sm, uint32_t flag
             const size_t usable = usable_of(serving);
             // (a pattern whose serving sets hold no table at all is one the tables cannot serve)
             if (!usable) served = 0;
-            *unserved = n - served;
+            unserved = n - served;
             if (served) c->search_tables = usable;
-            if (*unserved == 0) {
+            if (unserved == 0) {
                 // hashes, pattern records and the chunks' sizes go up as one block, staged in the pinned buffer; one byte per chunk comes back
                 Carve up;
                 const auto u_hs = up.take<uint32_t>(hs.size());
@@ -306,97 +311,70 @@ int64_t dev_reader_search_plan(mlz_dev_reader* rd, hipStream_t sm, uint32_t flag
                 std::memcpy(take->data(), c->pinned2, nck);
                 *n_take = 0;
                 for (size_t k = 0; k < nck; k++) *n_take += (*take)[k];
-                return 0;
+                return planned();
             }
         }
     }
     *n_take = 0;   // a pattern the tables cannot serve: every chunk that holds a byte
     for (size_t k = 0; k < nck; k++) *n_take += ((*take)[k] = rd->chunks[k].n ? 1 : 0);
-    return 0;
+    return planned();
 }
 
-// The decoded set of a search on its way through the scratch, shared by the search for one pattern and the search for many: the decode
-// list in stream order, its groups (range_group_ends), every chunk's place and the tiles of start positions (search_layout),
-// the stored chunks' copies, and where the carried bytes, the tiles and the jobs' results lie in the two workspaces.
+// The decoded set of both searches on its way through the scratch (ScratchDecode): the decode list in stream order, its groups (range_group_ends), every
+// chunk's place and the tiles of start positions (search_layout), and where the carried bytes and the tiles lie in the two workspaces.
 struct SearchDecode {
-    std::vector<ChunkJob> jobs;
-    std::vector<size_t> gend, place_end;
-    std::vector<PlaceDesc> places;   // stored chunks: copied from the stream
+    ScratchDecode dec;
     mlz::SearchLayout lay;
     Region<uint8_t> carry;
     Region<mlz::SearchTile> tiles, htiles;
-    Region<PlaceDesc> hplaces;
-    ChunkJobResults res;
 };
 
 // lmin, lmax: the shortest and the longest pattern of the call; tile: the most start positions of a tile (search_layout)
 void search_decode_plan(const mlz_dev_reader* rd, const std::vector<uint8_t>& take, size_t n_take, uint32_t lmin, uint32_t lmax, uint32_t tile, SearchDecode* sd) {
-    const size_t nck = rd->chunks.size();
-    sd->jobs.reserve(n_take);
-    for (size_t k = 0; k < nck; k++) if (take[k]) sd->jobs.push_back(ChunkJob{k, nullptr});
-    const std::vector<ChunkJob>& jobs = sd->jobs;
-    mlz::range_group_ends(jobs.size(), [&](size_t i) { return uint64_t(rd->chunks[jobs[i].ck].n); }, &sd->gend);
-    mlz::search_layout(jobs.size(), sd->gend, [&](size_t i) { return uint64_t(rd->chunks[jobs[i].ck].out_off); }, [&](size_t i) { return uint64_t(rd->chunks[jobs[i].ck].n); },
+    std::vector<ChunkJob>& jobs = sd->dec.jobs;
+    jobs.reserve(n_take);
+    for (size_t k = 0; k < rd->chunks.size(); k++) if (take[k]) jobs.push_back(ChunkJob{k, nullptr});
+    mlz::range_group_ends(jobs.size(), [&](size_t i) { return uint64_t(rd->chunks[jobs[i].ck].n); }, &sd->dec.gend);
+    mlz::search_layout(jobs.size(), sd->dec.gend, [&](size_t i) { return uint64_t(rd->chunks[jobs[i].ck].out_off); }, [&](size_t i) { return uint64_t(rd->chunks[jobs[i].ck].n); },
                        lmin, lmax, tile, &sd->lay);
-    const size_t ng = sd->gend.size();
-    sd->place_end.assign(ng, 0);
-    for (size_t g = 0, j0 = 0; g < ng; j0 = sd->gend[g++]) {
-        for (size_t i = j0; i < sd->gend[g]; i++) {
-            const StreamChunk& ck = rd->chunks[jobs[i].ck];
-            if (ck.type == kChunkUncompressed)
-                place_pieces(ck.body_off, sd->lay.at[i], ck.n, 1, [&](const PlaceDesc& d) { sd->places.push_back(d); });
-        }
-        sd->place_end[g] = sd->places.size();
-    }
+    sd->dec.at = sd->lay.at;
 }
 
-// Its regions: carried bytes | tiles in the workspace (c->d_rplan), results | tiles | places in the pinned buffer
-void search_decode_take(SearchDecode* sd, Carve* cv, Carve* pin) {
+// Behind the caller's own regions: carried bytes | tiles in the workspace (c->d_rplan), the decode's | tiles in the pinned buffer; then every
+// buffer of the call, once: the workspace and the pinned buffer as they are carved now, the scratch, the copies' descriptors
+int search_decode_ready(mlz_dev_reader* rd, SearchDecode* sd, Carve* cv, Carve* pin) {
+    mlz_ctx* c = rd->ctx;
     const size_t nt = sd->lay.tiles.size();
     sd->carry = cv->take<uint8_t>(mlz::kSearchMaxPattern);
     sd->tiles = cv->take<mlz::SearchTile>(nt);
-    sd->res = take_chunk_job_results(pin, sd->jobs.size());
+    if (const int e = sd->dec.take(c, rd->chunks, pin)) return e;
     sd->htiles = pin->take<mlz::SearchTile>(nt, 64);
-    sd->hplaces = pin->take<PlaceDesc>(sd->places.size(), 8);
+    HIPCHK(c, c->d_rplan.ensure(cv->bytes));
+    return ensure_stream_objects(c, 0, pin->bytes);
 }
 
-// Every buffer of the call, once: the workspace and the pinned buffer as the caller carved them, the scratch, the copies' descriptors
-int search_decode_ready(mlz_ctx* c, const SearchDecode& sd, const Carve& cv, const Carve& pin) {
-    HIPCHK(c, c->d_rplan.ensure(cv.bytes));
-    HIPCHK(c, c->d_range.ensure(size_t(sd.lay.scratch_max) + 64));
-    if (!sd.places.empty()) HIPCHK(c, c->d_place.ensure(sd.places.size() * sizeof(PlaceDesc)));
-    return ensure_stream_objects(c, 0, pin.bytes);
-}
-
-// Decodes the set group by group into the scratch (stored chunks: copied), calls scan(g, t0, t1) for the tiles [t0, t1) of group g with its
-// bytes in place, and carries a run's last bytes in front of the next group.  Returns stream_run_chunk_jobs' verdict.
+// Decodes the set group by group into the scratch, calls scan(g, t0, t1) for the tiles [t0, t1) of group g with its bytes in place, and
+// carries a run's last bytes in front of the next group.  Returns stream_run_chunk_jobs' verdict.
 template <class Scan>
 int64_t search_decode_run(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, SearchDecode* sd, Scan scan) {
     mlz_ctx* c = rd->ctx;
     const mlz::SearchLayout& lay = sd->lay;
-    const size_t nt = lay.tiles.size(), np = sd->places.size();
+    const size_t nt = lay.tiles.size();
     uint8_t *scratch = c->d_range.as<uint8_t>(), *d_carry = sd->carry.at(c->d_rplan.p);
     mlz::SearchTile *d_tiles = sd->tiles.at(c->d_rplan.p), *h_tiles = sd->htiles.at(c->pinned2);
-    PlaceDesc* h_places = sd->hplaces.at(c->pinned2);
-    if (nt) std::memcpy(h_tiles, lay.tiles.data(), nt * sizeof(mlz::SearchTile));
-    if (np) std::memcpy(h_places, sd->places.data(), np * sizeof(PlaceDesc));
-    for (size_t i = 0; i < sd->jobs.size(); i++) {
-        const StreamChunk& ck = rd->chunks[sd->jobs[i].ck];
-        sd->jobs[i].at = ck.type == kChunkUncompressed ? rd->d_src + ck.body_off : scratch + lay.at[i];   // (a stored chunk's CRC: over the stream's own bytes)
+    if (nt) {
+        std::memcpy(h_tiles, lay.tiles.data(), nt * sizeof(mlz::SearchTile));
+        HIPCHK(c, hipMemcpyAsync(d_tiles, h_tiles, nt * sizeof(mlz::SearchTile), hipMemcpyHostToDevice, sm));
     }
-    if (nt) HIPCHK(c, hipMemcpyAsync(d_tiles, h_tiles, nt * sizeof(mlz::SearchTile), hipMemcpyHostToDevice, sm));
-    if (np) HIPCHK(c, hipMemcpyAsync(c->d_place.p, h_places, np * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
-    auto scan_group = [&](size_t g) -> int {
-        const size_t t0 = g ? lay.tile_end[g - 1] : 0, t1 = lay.tile_end[g], q0 = g ? sd->place_end[g - 1] : 0, q1 = sd->place_end[g];
-        if (q1 > q0) hipLaunchKernelGGL(stream_place_kernel, dim3(uint32_t(q1 - q0)), dim3(256), 0, sm, rd->d_src, rd->d_src, nullptr, scratch, c->d_place.as<PlaceDesc>() + q0);
+    return sd->dec.run(c, sm, ignore_crc, rd->d_src, rd->chunks, [&](size_t g) -> int {
+        const size_t t0 = g ? lay.tile_end[g - 1] : 0, t1 = lay.tile_end[g];
         if (t1 > t0) { const int e = scan(g, t0, t1); if (e) return e; }
         if (lay.carry[g]) {   // the run goes on in the next group: its last bytes in front of that group's first chunk
             HIPCHK(c, hipMemcpyAsync(d_carry, scratch + lay.used[g] - lay.carry[g], lay.carry[g], hipMemcpyDeviceToDevice, sm));
             HIPCHK(c, hipMemcpyAsync(scratch + mlz::kSearchPad - lay.carry[g], d_carry, lay.carry[g], hipMemcpyDeviceToDevice, sm));
         }
         return 0;
-    };
-    return stream_run_chunk_jobs(c, sm, ignore_crc, rd->d_src, rd->chunks, sd->jobs, sd->gend, sd->res, scan_group);
+    });
 }
 
 // The opening of both searches: counters 10 and 11 cleared, stats = {data chunks, 0, 0, 0}
@@ -428,11 +406,8 @@ int64_t dev_reader_search_scan_locked(mlz_dev_reader* rd, hipStream_t sm, uint32
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<uint8_t> take(nck, 0);
     size_t n_take = 0;
-    uint64_t unserved = 0;
-    const int64_t pr = dev_reader_search_plan(rd, sm, flags, pattern, std::vector<uint32_t>{0, L}, 1, &take, &n_take, &unserved);
+    const int64_t pr = dev_reader_search_plan(rd, sm, flags, pattern, std::vector<uint32_t>{0, L}, 1, &take, &n_take, stats, false);
     if (pr) return pr;
-    c->search_chunks = n_take;
-    if (stats) { stats[1] = n_take; stats[2] = c->search_tables; }
     if (n_take == 0) return 0;
 
     // the decode list, its groups, every chunk's place in the scratch and the tiles of start positions (search_layout), the stored chunks' copies
@@ -440,14 +415,13 @@ int64_t dev_reader_search_scan_locked(mlz_dev_reader* rd, hipStream_t sm, uint32
     search_decode_plan(rd, take, n_take, L, L, mlz::kSearchTile, &sd);
     const size_t nt = sd.lay.tiles.size();
     if (nt > 0x7fffffffu) return -MLZ_ERR_ARG;
-    Carve cv, pin;   // workspace: pattern | total | counts | prefix | bitmaps | the decode's; pinned: the decode's | pattern
+    Carve cv, pin;   // workspace: pattern | total | counts | prefix | bitmaps | the decode's; pinned: pattern | the decode's
     const auto r_pat = cv.take<uint8_t>(mlz::kSearchMaxPattern);
     const auto r_total = cv.take<uint64_t>(2);
     const auto r_counts = cv.take<uint32_t>(nt, 4);
     const auto r_prefix = cv.take<uint64_t>(nt), r_masks = cv.take<uint64_t>(nt * mlz::kSearchTileWords, 8);
-    search_decode_take(&sd, &cv, &pin);
     const auto r_hpat = pin.take<uint8_t>(mlz::kSearchMaxPattern + 16, 8);
-    int e = search_decode_ready(c, sd, cv, pin);
+    int e = search_decode_ready(rd, &sd, &cv, &pin);
     if (e) return e;
     uint8_t *ws = r_pat.at(c->d_rplan.p), *h_pat = r_hpat.at(c->pinned2);
     std::memcpy(h_pat, pattern, L);
@@ -491,7 +465,7 @@ extern "C" int64_t mlz_dev_reader_search(mlz_dev_reader* rd, void* stream, uint3
     if (!rd || !pattern || pattern_len == 0 || pattern_len > mlz::kSearchMaxPattern || (!d_offsets && cap)) return -MLZ_ERR_ARG;
     mlz_ctx* c = rd->ctx;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
+    if (enter_device(c)) return -MLZ_ERR_HIP;
     if (cap && !on_device(c, d_offsets)) return -MLZ_ERR_ARG;
     begin_decode_call(c);
     hipStream_t sm = static_cast<hipStream_t>(stream);

@@ -144,6 +144,38 @@ __global__ __launch_bounds__(kSearchManyThreads) void search_many_kernel(const u
 
 namespace {
 
+// The pattern index of a call on its way to the device, as one block: heads | order | offsets | pattern bytes (a whole number of words).
+// take: its copies in the workspace (c->d_rplan) and in the pinned buffer; send (behind the caller's ensures, where the caller's stream
+// order wants the upload): fills the pinned copy and enqueues it; ix, lds_bytes: the index and a workgroup's LDS as the kernels take them.
+struct SearchManyUpload {
+    Carve up;
+    Region<uint16_t> u_heads, u_order;
+    Region<uint32_t> u_off;
+    Region<uint8_t> u_blob, dev, host;
+    mlz::SearchManyIx ix{};
+    uint32_t lds_bytes = 0;
+
+    void take(const mlz::SearchManyIndex& index, size_t n, Carve* cv, Carve* pin) {
+        u_heads = up.take<uint16_t>(index.heads.size()); u_order = up.take<uint16_t>(n);
+        u_off = up.take<uint32_t>(n + 1); u_blob = up.take<uint8_t>(size_t(index.off[n]) + 4);
+        dev = cv->take<uint8_t>(up.bytes);
+        host = pin->take<uint8_t>(up.bytes);
+    }
+    int send(mlz_ctx* c, hipStream_t sm, const mlz::SearchManyIndex& index, const uint8_t* patterns, size_t n) {
+        const uint32_t blob_bytes = index.off[n];
+        void *d_up = dev.at(c->d_rplan.p), *h_up = host.at(c->pinned2);
+        std::memcpy(u_heads.at(h_up), index.heads.data(), index.heads.size() * 2);
+        std::memcpy(u_order.at(h_up), index.order.data(), n * 2);
+        std::memcpy(u_off.at(h_up), index.off.data(), (n + 1) * 4);
+        std::memcpy(u_blob.at(h_up), patterns, blob_bytes);
+        const bool in_lds = mlz::search_many_lds(uint32_t(n), index.hb, blob_bytes, true).words * 4 <= mlz::kSearchManyLdsBudget;
+        ix = mlz::SearchManyIx{u_heads.at(d_up), u_order.at(d_up), u_off.at(d_up), u_blob.at(d_up), uint32_t(n), index.hb, index.m, index.lmax, blob_bytes, in_lds ? 1u : 0u};
+        lds_bytes = mlz::search_many_lds(uint32_t(n), index.hb, blob_bytes, in_lds).words * 4;
+        HIPCHK(c, hipMemcpyAsync(d_up, h_up, up.bytes, hipMemcpyHostToDevice, sm));
+        return 0;
+    }
+};
+
 int64_t dev_reader_search_many_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* patterns, const uint32_t* pattern_len, size_t n, uint64_t* d_counts,
                                       uint64_t* d_offsets, uint32_t* d_which, uint64_t cap, uint64_t* stats) {
     mlz_ctx* c = rd->ctx;
@@ -163,55 +195,38 @@ int64_t dev_reader_search_many_locked(mlz_dev_reader* rd, hipStream_t sm, uint32
     mlz::search_many_index(patterns, pattern_len, n, &index);
     std::vector<uint8_t> take(nck, 0);
     size_t n_take = 0;
-    uint64_t unserved = 0;
-    const int64_t pr = dev_reader_search_plan(rd, sm, flags, patterns, index.off, n, &take, &n_take, &unserved);
+    const int64_t pr = dev_reader_search_plan(rd, sm, flags, patterns, index.off, n, &take, &n_take, stats, true);
     if (pr) return pr;
-    c->search_chunks = n_take;
-    if (stats) { stats[1] = n_take; stats[2] = c->search_tables; stats[3] = unserved; }
     if (n_take == 0) return nothing();
 
     SearchDecode sd;
     search_decode_plan(rd, take, n_take, index.lmin, index.lmax, mlz::kSearchManyTile, &sd);
-    const size_t nt = sd.lay.tiles.size(), nheads = index.heads.size();
+    const size_t nt = sd.lay.tiles.size();
     if (nt > 0x7fffffffu) return -MLZ_ERR_ARG;
-    const uint32_t blob_bytes = index.off[n];
-    Carve up;        // the pattern index as one block: heads | order | offsets | pattern bytes (a whole number of words)
-    const auto u_heads = up.take<uint16_t>(nheads), u_order = up.take<uint16_t>(n);
-    const auto u_off = up.take<uint32_t>(n + 1);
-    const auto u_blob = up.take<uint8_t>(size_t(blob_bytes) + 4);
-    Carve cv, pin;   // workspace: per-pattern counts | total | the index | tile counts | prefix | the decode's; pinned: the decode's | the index
+    Carve cv, pin;   // workspace: per-pattern counts | total | the index | tile counts | prefix | the decode's; pinned: the index | the decode's
     const auto r_pc = cv.take<unsigned long long>(n);
     const auto r_total = cv.take<uint64_t>(2);
-    const auto r_up = cv.take<uint8_t>(up.bytes);
+    SearchManyUpload up;
+    up.take(index, n, &cv, &pin);
     const auto r_counts = cv.take<uint32_t>(nt, 4);
     const auto r_prefix = cv.take<uint64_t>(nt);
-    search_decode_take(&sd, &cv, &pin);
-    const auto r_hup = pin.take<uint8_t>(up.bytes);
-    int e = search_decode_ready(c, sd, cv, pin);
+    int e = search_decode_ready(rd, &sd, &cv, &pin);
     if (e) return e;
     void* ws = c->d_rplan.p;
     unsigned long long* d_pc = r_pc.at(ws);
     uint64_t *d_total = r_total.at(ws), *d_prefix = r_prefix.at(ws);
     uint32_t* d_tc = r_counts.at(ws);
     const mlz::SearchTile* d_tiles = sd.tiles.at(ws);
-    const bool in_lds = mlz::search_many_lds(uint32_t(n), index.hb, blob_bytes, true).words * 4 <= mlz::kSearchManyLdsBudget;
-    void *d_up = r_up.at(ws), *h_up = r_hup.at(c->pinned2);
-    std::memcpy(u_heads.at(h_up), index.heads.data(), nheads * 2);
-    std::memcpy(u_order.at(h_up), index.order.data(), n * 2);
-    std::memcpy(u_off.at(h_up), index.off.data(), (n + 1) * 4);
-    std::memcpy(u_blob.at(h_up), patterns, blob_bytes);
-    const mlz::SearchManyIx ix{u_heads.at(d_up), u_order.at(d_up), u_off.at(d_up), u_blob.at(d_up), uint32_t(n), index.hb, index.m, index.lmax, blob_bytes, in_lds ? 1u : 0u};
-    const uint32_t lds_bytes = mlz::search_many_lds(uint32_t(n), index.hb, blob_bytes, in_lds).words * 4;
     { WorkspaceOrder order(c, sm); }
     HIPCHK(c, hipMemsetAsync(d_pc, 0, n * sizeof(unsigned long long), sm));
     HIPCHK(c, hipMemsetAsync(d_total, 0, 16, sm));
-    HIPCHK(c, hipMemcpyAsync(d_up, h_up, up.bytes, hipMemcpyHostToDevice, sm));
+    if ((e = up.send(c, sm, index, patterns, n))) return e;
     const int64_t r = search_decode_run(rd, sm, ignore_crc, &sd, [&](size_t, size_t t0, size_t t1) {
         const uint8_t* scratch = c->d_range.as<uint8_t>();
-        hipLaunchKernelGGL(mlz::search_many_kernel<mlz::kSearchManyCount>, dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), lds_bytes, sm, scratch, d_tiles, uint32_t(t0), ix, d_tc, d_pc,
+        hipLaunchKernelGGL(mlz::search_many_kernel<mlz::kSearchManyCount>, dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), up.lds_bytes, sm, scratch, d_tiles, uint32_t(t0), up.ix, d_tc, d_pc,
                            static_cast<const uint64_t*>(nullptr), uint64_t(0), static_cast<uint64_t*>(nullptr), static_cast<uint32_t*>(nullptr), mlz::SearchManyMark{});
         hipLaunchKernelGGL(mlz::search_prefix_kernel, dim3(1), dim3(1024), 0, sm, d_tc, uint32_t(t0), uint32_t(t1), d_prefix, d_total);
-        if (cap) hipLaunchKernelGGL(mlz::search_many_kernel<mlz::kSearchManyWrite>, dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), lds_bytes, sm, scratch, d_tiles, uint32_t(t0), ix, d_tc, d_pc,
+        if (cap) hipLaunchKernelGGL(mlz::search_many_kernel<mlz::kSearchManyWrite>, dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), up.lds_bytes, sm, scratch, d_tiles, uint32_t(t0), up.ix, d_tc, d_pc,
                                     static_cast<const uint64_t*>(d_prefix), cap, d_offsets, d_which, mlz::SearchManyMark{});
         return 0;
     });
@@ -230,7 +245,7 @@ extern "C" int64_t mlz_dev_reader_search_many(mlz_dev_reader* rd, void* stream, 
         if (pattern_len[i] == 0 || pattern_len[i] > mlz::kSearchMaxPattern) return -MLZ_ERR_ARG;
     mlz_ctx* c = rd->ctx;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
+    if (enter_device(c)) return -MLZ_ERR_HIP;
     if (n_patterns && ((d_counts && !on_device(c, d_counts)) || (cap && (!on_device(c, d_offsets) || !on_device(c, d_which))))) return -MLZ_ERR_ARG;
     if (n_patterns == 0) {
         search_begin(rd, stats);

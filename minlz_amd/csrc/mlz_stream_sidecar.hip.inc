@@ -7,8 +7,8 @@
 // so ANY stream can be searched by tables: those of other writers, stored blocks, streams whose tables are compressed (0x46).
 //
 // Build (mlz_dev_reader_build_sidecar): the handle's data chunks are decoded group by group into the ReadSeeker's scratch, side by side
-// (stream_run_chunk_jobs; the first chunk of the next group is decoded behind a group's last one, so that every chunk's overlap lies behind
-// it).  Per group and configuration the block-list form of the table kernels (mlz_search_tables.hip.inc: StabBlock) builds and folds the
+// (ScratchDecode, mlz_stream_walk.hip.inc; the first chunk of the next group is a job of both groups and lies behind a group's last one, so
+// that every chunk's overlap lies behind it).  Per group and configuration the block-list form of the table kernels (mlz_search_tables.hip.inc: StabBlock) builds and folds the
 // tables; 8 bytes per (chunk, configuration) visit the host (table bytes or 0, R), the existing CRC pass runs over the kept tables (4 more
 // bytes each), and sidecar_place_kernel writes the group's chunks — and, with the first and the last group, the identifier with the info
 // chunks and the EOF — at offsets the host has summed up from those sizes.
@@ -191,8 +191,7 @@ int64_t sidecar_build_pass(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, 
     mlz_ctx* c = rd->ctx;
     const uint32_t ncfg = uint32_t(stb.size()), max_block = sidecar_max_block(rd), B = mlz::search_table_bits(max_block);
     const size_t slot = size_t(1) << (B - 3);
-    std::vector<size_t> dc;   // the data chunks with bytes
-    for (size_t k = 0; k < rd->chunks.size(); k++) if (rd->chunks[k].n) dc.push_back(k);
+    const std::vector<size_t> dc = mlz::chunks_with_bytes(rd->chunks.size(), [&](size_t k) { return rd->chunks[k].n; });
     const size_t nd = dc.size();
     // groups: about 64 MiB of chunk output (as range_group_ends) and table slots within kSidecarTableBytes
     const size_t group_chunks = std::max<size_t>(1, kSidecarTableBytes / (slot * ncfg));
@@ -205,25 +204,16 @@ int64_t sidecar_build_pass(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, 
     }
     const size_t ng = gfirst.size() - 1;
     // the decode list: a group's chunks side by side from scratch[0] on, then the next group's first chunk (its first bytes are the last chunk's overlap)
-    std::vector<ChunkJob> jobs;
-    std::vector<size_t> gend, place_end;
-    std::vector<uint64_t> at;
-    std::vector<PlaceDesc> places;
-    uint64_t scratch_max = 0;
+    ScratchDecode dec;
     size_t cnt_max = 0;
     for (size_t g = 0; g < ng; g++) {
         const size_t i1 = gfirst[g + 1] < nd ? gfirst[g + 1] + 1 : nd;
         uint64_t o = 0;
         for (size_t i = gfirst[g]; i < i1; i++) {
-            const StreamChunk& ck = rd->chunks[dc[i]];
-            jobs.push_back(ChunkJob{dc[i], nullptr});
-            at.push_back(o);
-            if (ck.type == kChunkUncompressed) place_pieces(ck.body_off, o, ck.n, 1, [&](const PlaceDesc& d) { places.push_back(d); });
-            o += ck.n;
+            dec.jobs.push_back(ChunkJob{dc[i], nullptr}); dec.at.push_back(o);
+            o += rd->chunks[dc[i]].n;
         }
-        gend.push_back(jobs.size());
-        place_end.push_back(places.size());
-        scratch_max = std::max(scratch_max, o);
+        dec.gend.push_back(dec.jobs.size());
         cnt_max = std::max(cnt_max, gfirst[g + 1] - gfirst[g]);
     }
     // per configuration the block list of every group (a chunk's place in ITS group's scratch and the bytes of overlap behind it)
@@ -258,24 +248,21 @@ int64_t sidecar_build_pass(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, 
     if (head.size() + 5 > dst_cap) return -MLZ_ERR_DST_TOO_SMALL;
 
     const size_t nrec = size_t(ncfg) * cnt_max;
-    Carve cv, pin;   // workspace: configurations | head | block lists | table CRCs | block records; pinned: the decode's results | (bytes, R) | table CRCs | block records | uploads
+    Carve cv, pin;   // workspace: configurations | head | block lists | table CRCs | block records; pinned: the decode's | (bytes, R) | table CRCs | block records | uploads
     const auto r_cfg = cv.take<mlz::SearchConfig>(ncfg);
     const auto r_head = cv.take<uint8_t>(head.size());
     const auto r_lists = cv.take<mlz::StabBlock>(lists.size());
     const auto r_tcrc = cv.take<uint32_t>(nrec + 16);
     const auto r_rec = cv.take<mlz::SidePlace>(cnt_max);
-    const ChunkJobResults res = take_chunk_job_results(&pin, jobs.size());
+    int e = dec.take(c, rd->chunks, &pin);
+    if (e) return e;
     const auto h_info_r = pin.take<uint2>(nrec);
     const auto h_tcrc_r = pin.take<uint32_t>(nrec);
     const auto h_rec_r = pin.take<mlz::SidePlace>(cnt_max);
     const auto h_up_r = pin.take<uint8_t>(r_tcrc.off, 64);   // what goes up once, as one block: configurations | head | block lists, laid out as in the workspace
-    const auto h_places_r = pin.take<PlaceDesc>(places.size(), 8);
     HIPCHK(c, c->d_rplan.ensure(cv.bytes));
-    HIPCHK(c, c->d_range.ensure(size_t(scratch_max) + 64));
     HIPCHK(c, c->d_stab.ensure(nrec * slot + nrec * sizeof(uint2) + 64));
-    if (!places.empty()) HIPCHK(c, c->d_place.ensure(places.size() * sizeof(PlaceDesc)));
-    int e = ensure_stream_objects(c, 0, pin.bytes);
-    if (e) return e;
+    if ((e = ensure_stream_objects(c, 0, pin.bytes))) return e;
     void* ws = c->d_rplan.p;
     uint8_t *scratch = c->d_range.as<uint8_t>(), *h_up = h_up_r.at(c->pinned2);
     const mlz::SearchConfig* d_cfg = r_cfg.at(ws);
@@ -283,18 +270,11 @@ int64_t sidecar_build_pass(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, 
     uint32_t *d_tcrc = r_tcrc.at(ws), *h_tcrc = h_tcrc_r.at(c->pinned2);
     mlz::SidePlace *d_rec = r_rec.at(ws), *h_rec = h_rec_r.at(c->pinned2);
     uint2 *h_info = h_info_r.at(c->pinned2), *d_info = reinterpret_cast<uint2*>(c->d_stab.as<uint8_t>() + nrec * slot);
-    PlaceDesc* h_places = h_places_r.at(c->pinned2);
     std::memcpy(r_cfg.at(h_up), cfg.data(), ncfg * sizeof(mlz::SearchConfig));
     std::memcpy(r_head.at(h_up), head.data(), head.size());
     if (!lists.empty()) std::memcpy(r_lists.at(h_up), lists.data(), lists.size() * sizeof(mlz::StabBlock));
-    if (!places.empty()) std::memcpy(h_places, places.data(), places.size() * sizeof(PlaceDesc));
-    for (size_t j = 0; j < jobs.size(); j++) {
-        const StreamChunk& ck = rd->chunks[jobs[j].ck];
-        jobs[j].at = ck.type == kChunkUncompressed ? rd->d_src + ck.body_off : scratch + at[j];   // (a stored chunk's CRC: over the stream's own bytes)
-    }
     { WorkspaceOrder order(c, sm); }
     HIPCHK(c, hipMemcpyAsync(ws, h_up, r_tcrc.off, hipMemcpyHostToDevice, sm));
-    if (!places.empty()) HIPCHK(c, hipMemcpyAsync(c->d_place.p, h_places, places.size() * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
 
     uint64_t total = head.size();
     auto launch_place = [&](uint32_t cnt, bool first, bool last_one) {
@@ -304,10 +284,9 @@ int64_t sidecar_build_pass(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, 
         a.cnt = cnt; a.ncfg = ncfg; a.slot = uint32_t(slot); a.pieces = uint32_t(std::max<size_t>(1, slot / kPlacePiece)); a.head_n = first ? uint32_t(head.size()) : 0;
         hipLaunchKernelGGL(mlz::sidecar_place_kernel, dim3(std::max<uint32_t>(1, cnt * ncfg * a.pieces)), dim3(256), 0, sm, a);
     };
-    // a group's bytes are in the scratch (stored chunks: copied now): its tables, their sizes and CRCs, its chunks' places, the placement
+    // a group's bytes are in the scratch: its tables, their sizes and CRCs, its chunks' places, the placement
     auto tables_of_group = [&](size_t g) -> int {
-        const size_t i0 = gfirst[g], cnt = gfirst[g + 1] - i0, q0 = g ? place_end[g - 1] : 0, q1 = place_end[g];
-        if (q1 > q0) hipLaunchKernelGGL(stream_place_kernel, dim3(uint32_t(q1 - q0)), dim3(256), 0, sm, rd->d_src, rd->d_src, nullptr, scratch, c->d_place.as<PlaceDesc>() + q0);
+        const size_t i0 = gfirst[g], cnt = gfirst[g + 1] - i0;
         for (uint32_t s = 0; s < ncfg; s++) {
             const int r = search_tables_build_list(c, sm, scratch, d_lists + size_t(s) * nd + i0, cnt, max_block, stb[s].T, stb[s].field, stb[s].M, B,
                                                    reinterpret_cast<uint32_t*>(c->d_stab.as<uint8_t>() + size_t(s) * cnt * slot), d_info + size_t(s) * cnt);
@@ -348,7 +327,7 @@ int64_t sidecar_build_pass(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, 
     if (ng == 0) {
         if (place) launch_place(0, true, true);
     } else {
-        const int64_t r = stream_run_chunk_jobs(c, sm, ignore_crc, rd->d_src, rd->chunks, jobs, gend, res, tables_of_group);
+        const int64_t r = dec.run(c, sm, ignore_crc, rd->d_src, rd->chunks, tables_of_group);
         if (r < 0) return r;
     }
     HIPCHK(c, hipStreamSynchronize(sm));
@@ -462,7 +441,7 @@ int64_t mlz_dev_reader_build_sidecar(mlz_dev_reader* rd, void* stream, uint32_t 
     if (!rd || !d_dst || !sidecar_configs(cfgs, n_cfgs, &stb)) return -MLZ_ERR_ARG;
     mlz_ctx* c = rd->ctx;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
+    if (enter_device(c)) return -MLZ_ERR_HIP;
     if (!on_device(c, d_dst)) return -MLZ_ERR_ARG;
     if (rd->n_ident > 1) return -MLZ_ERR_UNSUPPORTED;
     if (rd->n_ident == 0) return -MLZ_ERR_CORRUPT;   // (an empty stream: no identifier to repeat)
@@ -475,7 +454,7 @@ int64_t mlz_dev_reader_attach_sidecar(mlz_dev_reader* rd, void* stream, uint32_t
     if (!rd || (!d_side && n_side)) return -MLZ_ERR_ARG;
     mlz_ctx* c = rd->ctx;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return -MLZ_ERR_HIP; }
+    if (enter_device(c)) return -MLZ_ERR_HIP;
     if (!d_side) {   // detach: the handle searches by its inline tables again
         if (rd->side.d_tabs) (void)hipFree(rd->side.d_tabs);
         rd->side = mlz_dev_reader::SearchTables{};

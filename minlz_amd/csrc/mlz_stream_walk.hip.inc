@@ -25,6 +25,8 @@
 // first error) is applied to it on the host by walk_parse_table — the same code the host check runs (a serial pass over 32-byte
 // records; streams of very many DATA chunks would want it as scans on the device).  Decode and CRC then run on the stream where it lies: descriptors point into
 // d_src (token-only mode, nothing is patched) and d_dst, stored chunks are copied by one kernel over a descriptor list.
+// Every device-resident call stages its chunk list for stream_run_chunk_jobs in one of two ways, written here once: in place (stream_decode_jobs_in_place:
+// this call and the batch decode) or through the scratch (ScratchDecode: the searches, the grep, the record index and the sidecar build).
 // Workspace: 8 bytes per stream byte (x0, x1) + 12 bytes per 4 KiB + 32 bytes per table entry.
 
 #include "mlz_stream_walk.h"
@@ -208,6 +210,9 @@ bool on_device(const mlz_ctx* c, const void* p) {
     return true;
 }
 
+// An entry point's first word to the runtime: the calling thread works on the context's device
+int enter_device(mlz_ctx* c) { return hipSetDevice(c->device) == hipSuccess ? 0 : ((void)hipGetLastError(), -MLZ_ERR_HIP); }
+
 // `bytes` from device memory to the host, waited for; an error of anything sm was given before shows here too
 int fetch(mlz_ctx* c, hipStream_t sm, void* host, const void* dev, size_t bytes) {
     HIPCHK(c, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, sm));
@@ -369,35 +374,79 @@ int64_t stream_run_chunk_jobs(mlz_ctx* c, hipStream_t sm, bool ignore_crc, const
     return 0;
 }
 
-// All chunks of a walked stream, where they lie: stored chunks by one kernel, then decode and CRC over d_dst (stream_run_chunk_jobs).
-// Returns 0 or the first chunk's error in stream order.
-int64_t stream_decode_chunks_device(mlz_ctx* c, hipStream_t sm, bool ignore_crc, const uint8_t* d_src, const std::vector<StreamChunk>& chunks, uint8_t* d_dst) {
-    const size_t nck = chunks.size();
-    begin_decode_call(c);
-    if (nck == 0) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    size_t n_place = 0;
-    for (const StreamChunk& ck : chunks)
-        if (ck.type == kChunkUncompressed) n_place += (ck.n + kPlacePiece - 1) / kPlacePiece;
-    Carve pin;
-    const ChunkJobResults res = take_chunk_job_results(&pin, nck);
-    const auto r_place = pin.take<PlaceDesc>(n_place, 64);
-    int r = ensure_stream_objects(c, 0, pin.bytes);
-    if (r) return r;
-    if (n_place) {   // stored chunks: 64 KiB pieces, one launch
-        HIPCHK(c, c->d_place.ensure(n_place * sizeof(PlaceDesc)));
-        PlaceDesc* h_place = r_place.at(c->pinned2);
-        size_t q = 0;
-        for (const StreamChunk& ck : chunks)
-            if (ck.type == kChunkUncompressed) place_pieces(ck.body_off, ck.out_off, ck.n, 0, [&](const PlaceDesc& d) { h_place[q++] = d; });
-        HIPCHK(c, hipMemcpyAsync(c->d_place.p, h_place, n_place * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
-        hipLaunchKernelGGL(stream_place_kernel, dim3(uint32_t(n_place)), dim3(256), 0, sm, d_src, nullptr, nullptr, d_dst, c->d_place.as<PlaceDesc>());
-    }
-    std::vector<ChunkJob> jobs(nck);
-    for (size_t i = 0; i < nck; i++) jobs[i] = ChunkJob{i, d_dst + chunks[i].out_off};
+// The scratch decode: a list of a handle's chunks decoded group by group into the context's scratch (c->d_range), which every group reuses,
+// for the calls that read decoded bytes without keeping them (the searches, the grep, the record index, the sidecar build).  The caller
+// fills jobs (ck; in stream order), gend and at (every job's offset in the scratch); the rest is the rule of mlz_stream_scratch.h.
+struct ScratchDecode {
+    std::vector<ChunkJob> jobs;
     std::vector<size_t> gend;
-    mlz::range_group_ends(nck, [&](size_t i) { return uint64_t(chunks[i].n); }, &gend);
-    return stream_run_chunk_jobs(c, sm, ignore_crc, d_src, chunks, jobs, gend, res, [](size_t) { return 0; });
+    std::vector<uint64_t> at;
+    mlz::ScratchPlaces sp;
+    ChunkJobResults res;
+    Region<PlaceDesc> hplaces;
+
+    // Its regions of the caller's carve of the pinned buffer, in front of the caller's ensure_stream_objects; the scratch, the copies' descriptors
+    int take(mlz_ctx* c, const std::vector<StreamChunk>& chunks, Carve* pin) {
+        sp = mlz::scratch_places(jobs.size(), gend, [&](size_t i) -> const StreamChunk& { return chunks[jobs[i].ck]; }, at);
+        res = take_chunk_job_results(pin, jobs.size());
+        hplaces = pin->take<PlaceDesc>(sp.places.size(), 8);
+        HIPCHK(c, c->d_range.ensure(size_t(sp.scratch_max) + 64));
+        if (!sp.places.empty()) HIPCHK(c, c->d_place.ensure(sp.places.size() * sizeof(PlaceDesc)));
+        return 0;
+    }
+    // Decodes the list; per group the stored chunks' copies are enqueued and after_group(g) is called with the group's bytes in place (sm still running)
+    template <class AfterGroup>
+    int64_t run(mlz_ctx* c, hipStream_t sm, bool ignore_crc, const uint8_t* d_src, const std::vector<StreamChunk>& chunks, AfterGroup after_group) {
+        uint8_t* scratch = c->d_range.as<uint8_t>();
+        const size_t np = sp.places.size();
+        for (size_t i = 0; i < jobs.size(); i++) {
+            const StreamChunk& ck = chunks[jobs[i].ck];
+            jobs[i].at = ck.type == kChunkUncompressed ? d_src + ck.body_off : scratch + at[i];   // (a stored chunk's CRC: over the stream's own bytes)
+        }
+        if (np) {
+            std::memcpy(hplaces.at(c->pinned2), sp.places.data(), np * sizeof(PlaceDesc));
+            HIPCHK(c, hipMemcpyAsync(c->d_place.p, hplaces.at(c->pinned2), np * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
+        }
+        return stream_run_chunk_jobs(c, sm, ignore_crc, d_src, chunks, jobs, gend, res, [&](size_t g) -> int {
+            const size_t q0 = g ? sp.place_end[g - 1] : 0, q1 = sp.place_end[g];
+            if (q1 > q0) hipLaunchKernelGGL(stream_place_kernel, dim3(uint32_t(q1 - q0)), dim3(256), 0, sm, d_src, d_src, nullptr, scratch, c->d_place.as<PlaceDesc>() + q0);
+            return after_group(g);
+        });
+    }
+};
+
+// The in-place decode: a job list whose targets all lie in d_dst, where the chunks finally lie.  Stored chunks by one stream_place_kernel launch over
+// their 64 KiB pieces, then decode and CRC group by group (range_group_ends, stream_run_chunk_jobs and its per_job).  The caller has begun the decode call.
+int64_t stream_decode_jobs_in_place(mlz_ctx* c, hipStream_t sm, bool ignore_crc, const uint8_t* d_src, const std::vector<StreamChunk>& chunks, const std::vector<ChunkJob>& jobs,
+                                    uint8_t* d_dst, std::vector<int64_t>* per_job = nullptr) {
+    std::vector<uint64_t> at(jobs.size());   // the stored chunks' pieces: the rule of the scratch decode for one group that is d_dst
+    for (size_t j = 0; j < jobs.size(); j++) at[j] = uint64_t(jobs[j].at - d_dst);
+    const std::vector<PlaceDesc> places = mlz::scratch_places(jobs.size(), {jobs.size()}, [&](size_t j) -> const StreamChunk& { return chunks[jobs[j].ck]; }, at).places;
+    const size_t np = places.size();
+    Carve pin;
+    const ChunkJobResults res = take_chunk_job_results(&pin, jobs.size());
+    const auto r_place = pin.take<PlaceDesc>(np, 64);
+    if (const int r = ensure_stream_objects(c, 0, pin.bytes)) return r;
+    { WorkspaceOrder order(c, sm); }
+    if (np) {
+        HIPCHK(c, c->d_place.ensure(np * sizeof(PlaceDesc)));
+        std::memcpy(r_place.at(c->pinned2), places.data(), np * sizeof(PlaceDesc));
+        HIPCHK(c, hipMemcpyAsync(c->d_place.p, r_place.at(c->pinned2), np * sizeof(PlaceDesc), hipMemcpyHostToDevice, sm));
+        hipLaunchKernelGGL(stream_place_kernel, dim3(uint32_t(np)), dim3(256), 0, sm, d_src, d_src, nullptr, d_dst, c->d_place.as<PlaceDesc>());
+    }
+    std::vector<size_t> gend;
+    mlz::range_group_ends(jobs.size(), [&](size_t j) { return uint64_t(chunks[jobs[j].ck].n); }, &gend);
+    return stream_run_chunk_jobs(c, sm, ignore_crc, d_src, chunks, jobs, gend, res, [](size_t) { return 0; }, per_job);
+}
+
+// All chunks of a walked stream, where they lie in d_dst.  Returns 0 or the first chunk's error in stream order.
+int64_t stream_decode_chunks_device(mlz_ctx* c, hipStream_t sm, bool ignore_crc, const uint8_t* d_src, const std::vector<StreamChunk>& chunks, uint8_t* d_dst) {
+    begin_decode_call(c);
+    if (chunks.empty()) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<ChunkJob> jobs(chunks.size());
+    for (size_t i = 0; i < jobs.size(); i++) jobs[i] = ChunkJob{i, d_dst + chunks[i].out_off};
+    return stream_decode_jobs_in_place(c, sm, ignore_crc, d_src, chunks, jobs, d_dst);
 }
 
 }  // namespace

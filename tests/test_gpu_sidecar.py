@@ -179,6 +179,18 @@ def test_build_over_two_groups(ctx):
     check_builds(ctx, O.stream_encode(d, 1, bs), d, [[T1[6]]])
 
 
+def test_build_over_two_groups_with_stored_chunks_at_the_border(ctx):
+    """(f) 9 blocks of 8 MiB, blocks 7 and 8 random bytes, hence stored: the ninth is copied into the scratch twice, as the overlap behind
+    group 0's last chunk and as group 1's first chunk."""
+    bs = 8 << 20
+    d = data_for("text_like", bs, 9, 0, random_block=None)
+    d = d[:7 * bs] + synth.random_bytes(2 * bs, seed=8).tobytes()
+    stream = own_stream(ctx, d, bs)
+    grid = SMod.data_grid(stream)
+    assert [n for n, _ in grid] == [bs] * 9 and grid[7][1] == grid[8][1] == 0x01 and all(t != 0x01 for _, t in grid[:7])
+    check_builds(ctx, stream, d, [[T1[6]]])
+
+
 # ---- search by sidecar ----
 
 def expect(data, sizes, plan, pattern):

@@ -239,6 +239,24 @@ def test_two_groups(two_groups):
     assert h.ctx.range_plan()[0] == 2                   # the chunks on either side of the border, each once
 
 
+def test_stored_chunks_on_both_sides_of_the_group_border(ctx):
+    """9 blocks of 8 MiB, block 7 (the last of group 0) and block 8 (the first of group 1) random bytes, hence stored: the second group's
+    stored chunk is copied into the scratch by pieces that lie behind the first group's, and its delimiters enter the table."""
+    bs = 8 << 20
+    unit = bytes(lines((1 << 20) + 37, 21))
+    d = (unit * (7 * bs // len(unit) + 1))[:7 * bs] + synth.random_bytes(2 * bs, seed=8).tobytes()
+    stream = gather(ctx, [d], bs)
+    grid = SMod.data_grid(stream)
+    assert [n for n, _ in grid] == [bs] * 9 and grid[7][1] == grid[8][1] == 0x01 and all(t != 0x01 for _, t in grid[:7])
+    h = Indexed(ctx, stream, d)
+    try:
+        h.index()
+        start, length = h.check_all_spans()
+        assert (start >= 8 * bs).sum() > 1000               # records that lie in the second group's stored chunk
+    finally:
+        h.close()
+
+
 def test_read_records(plain):
     h, bs = plain
     start, length = IM.spans(h.data, NL)

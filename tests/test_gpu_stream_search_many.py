@@ -13,7 +13,8 @@ from tests import search_cases as SC
 from tests import search_long_prefix_cases as LC
 from tests import search_model as SMod
 from tests import search_prefix_cases as PC
-from tests.search_gpu import SENT, gather_into
+from tests.search_gpu import SENT, Searcher, gather_into
+from tests.test_gpu_stream_search import check_search
 
 pytestmark = pytest.mark.gpu
 
@@ -298,6 +299,33 @@ def test_group_border(ctx):
         check_many(sr, d, needles + [freq], "group border, frequent", cap=1000, no_tables=True)
     finally:
         sr.close()
+
+
+def test_stored_chunks_on_both_sides_of_the_group_border(ctx):
+    """9 blocks of 8 MiB, block 7 (the last of group 0) and block 8 (the first of group 1) random bytes, hence stored: the second group's
+    stored chunk is copied into the scratch by pieces that lie behind the first group's.  Needles inside block 8, inside block 7 and
+    across their border, which is the border of the groups; the search for one pattern takes the same way."""
+    bs = 8 << 20
+    base = synth.json_like(bs, 9).tobytes()
+    d = bytearray(base * 7 + synth.random_bytes(2 * bs, seed=8).tobytes())
+    needles = [bytes(SC.needle(24, 40 + i)) for i in range(3)]
+    for nd, o in zip(needles, (8 * bs + 3 * (bs // 4) + 5, 7 * bs + 100_001, 8 * bs - 11)):
+        d[o:o + 24] = nd
+    d = bytes(d)
+    stream = gather(ctx, d, bs)
+    grid = SMod.data_grid(stream)
+    assert [n for n, _ in grid] == [bs] * 9 and grid[7][1] == grid[8][1] == 0x01 and all(t != 0x01 for _, t in grid[:7])
+    sr = ManySearcher(ctx, stream)
+    one = Searcher(ctx, stream)
+    try:
+        pairs, counts = brute_pairs(d, needles)
+        assert counts == [1, 1, 1]
+        stats = check_many(sr, d, needles + [d[8 * bs + 70_000:8 * bs + 70_003]], "stored chunks at the group border", no_tables=True)
+        assert stats[1] == 9
+        assert check_search(one, stream, d, needles[2], "stored chunks at the group border, one pattern")[1] == 9
+    finally:
+        sr.close()
+        one.close()
 
 
 # ---- arguments ----
