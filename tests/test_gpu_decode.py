@@ -148,7 +148,7 @@ def test_literal_runs_longer_than_a_region_group(ctx):
     # segment instead, and the runs cross segment boundaries (entries deep inside a segment: the chain kernel's slow exits).  Literal
     # bytes are drawn from the values that long-literal and copy3 tags have, so the parse from a wrong start derails as far as it can.
     rng = np.random.default_rng(23)
-    taggy = np.array([0xE8, 0xF0, 0xF8, 0xFF, 0x07, 0x0F, 0xFB, 0x02, 0x01, 0x00], dtype=np.uint8)
+    from tests.decode_shapes import TAGGY as taggy
     for trial in range(3):
         tok = bytearray()
         out = bytearray()

@@ -32,6 +32,45 @@ def test_crc_batch_device(ctx):
     assert got == [O.crc(d[o:o + l]) for o, l in cuts]
 
 
+def test_crc_beyond_the_table_of_tile_powers(ctx):
+    # crc_block_kernel folds a lane's run of tiles with a table constant up to 255 tiles in front of the last one and with a computed power
+    # beyond (j >= 256: 262 tiles and more); a lane's run is ceil(last / 64) tiles, so `last` around 64 and 128 changes the runs; the ragged
+    # last tile takes a computed power per lane, in pieces of 128 bytes.  Not text, and not only whole tiles.
+    from tests.tile_levels import TILE as T
+    d = synth.random_bytes(300 * T + 129, 19)
+    sizes = [tiles * T + tail for tiles in (262, 300) for tail in (0, 1, 127, 128, 129)]
+    sizes += [last * T + tail for last in (63, 64, 65, 128, 129) for tail in (1, 127, 128, 129)]
+    for n in sizes:
+        assert mz.crc(d[:n], ctx) == O.crc(d[:n]), n
+    # zeros, and one non-zero byte as the first and as the last byte
+    for n in (262 * T + 129, 64 * T + 1, 129 * T + 128, 63 * T + 127):
+        z = np.zeros(n, dtype=np.uint8)
+        assert mz.crc(z, ctx) == O.crc(z), n
+        z[0] = 1
+        assert mz.crc(z, ctx) == O.crc(z), (n, "first")
+        z[0] = 0
+        z[-1] = 0x80
+        assert mz.crc(z, ctx) == O.crc(z), (n, "last")
+
+
+def test_crc_batch_device_alignments_and_edges(ctx):
+    # one call, 40 spans: every residue mod 16 of the source offset, lengths around multiples of a thread's 128 bytes and of a tile, empty spans between
+    import torch
+    from minlz_amd._lib import BlockDesc
+    d = synth.random_bytes(3_000_000, 23)
+    t = torch.from_numpy(d).cuda()
+    lens = [0, 127, 128, 129, 1, 255, 256, 257, 32767, 32768, 32769, 0, 65535, 65536, 65537, 32768 + 127, 32768 + 128, 32768 + 129, 98303, 98304, 98305, 15, 16, 17, 0,
+            4095, 4096, 4097, 32768 - 129, 32768 - 128, 32768 - 127, 383, 384, 385, 0, 65536 + 1, 65536 - 129, 2, 98304 - 127, 98304 + 129]
+    assert len(lens) == 40
+    cuts = [(70_000 * i + i % 16, n) for i, n in enumerate(lens)]
+    assert {o % 16 for o, _ in cuts} == set(range(16)) and all(o + n <= d.size for o, n in cuts)
+    out = torch.zeros(len(cuts), dtype=torch.int32, device="cuda")
+    ctx.crc_batch_device(torch.cuda.current_stream().cuda_stream, t.data_ptr(), [BlockDesc(o, l, 0, 0) for o, l in cuts], out.data_ptr())
+    torch.cuda.synchronize()
+    got = [int(x) & 0xffffffff for x in out.cpu().tolist()]
+    assert got == [O.crc(d[o:o + l]) for o, l in cuts]
+
+
 @pytest.mark.parametrize("level", [0, 1, 2])
 def test_writer_reader_roundtrip_and_reference_reader(ctx, level):
     be = S.HipBackend(ctx)
