@@ -7,11 +7,34 @@ import numpy as np
 from . import _lib
 from ._lib import BlockDesc
 
+# ---- the constants of include/minlz_hip.h (tests/test_abi.py holds every one against its #define) ----
 LevelSuperFast, LevelUncompressed, LevelFastest, LevelBalanced = -1, 0, 1, 2  # encode.go:25-43 (LevelSmallest = 3 is CPU-only)
 MaxBlockSize = 8 << 20  # minlz.go:84
 
-OPT_DECODE_ALGO, OPT_ENCODE_FAR, OPT_TIMING = 1, 2, 100
-OPT_L2_FREE, OPT_GEN_SPIN, OPT_GEN_PACKED, OPT_DEVICE_GROUP, OPT_L2_GAP = 14, 9, 13, 17, 19   # include/minlz_hip.h
+ERR_CORRUPT, ERR_TOO_LARGE, ERR_UNSUPPORTED, ERR_INVALID_LEVEL, ERR_CRC, ERR_DST_TOO_SMALL, ERR_HIP, ERR_ARG = 1, 2, 3, 4, 5, 6, 7, 8
+
+STREAM_ADD_INDEX, STREAM_IGNORE_CRC, STREAM_SEARCH_TABLES, SEARCH_NO_TABLES, GREP_INVERT = 1, 2, 4, 8, 16
+SEARCH_MAX_PATTERNS = 4096
+
+OPT_DECODE_ALGO, OPT_ENCODE_FAR, OPT_DEBUG_STATUS, OPT_PROFILE, OPT_PROFILE_READ, OPT_TILE_TIMELINE_READ, OPT_GENERAL_ALGO = 1, 2, 3, 4, 5, 7, 8
+OPT_GEN_SPIN, OPT_HOST_GROUP_ENC, OPT_HOST_GROUP_DEC, OPT_TIMER_MASK, OPT_GEN_PACKED, OPT_L2_FREE, OPT_DEVICE_GROUP = 9, 10, 11, 12, 13, 14, 17
+OPT_FAR_SLICES_L2, OPT_L2_GAP, OPT_GEN_SETTLE_CAP, OPT_FUSED_SERIALIZER, OPT_LEVEL0_KERNEL, OPT_FOLD_LAYOUT = 18, 19, 20, 21, 23, 24
+OPT_TIMING = 100  # MLZ_TIMER_ENABLE
+
+# mlz_get_counter(ctx, which): the header numbers them without names
+COUNTER_COMBINE_BATCHES = 0       # batches run by the combining queue of the single-block host calls
+COUNTER_COMBINE_REQUESTS = 1      # requests that queue served
+COUNTER_GENERAL_BLOCKS = 2        # blocks of the last decode call that went through the general-block path
+COUNTER_ENCODE_WORKSPACE = 3      # bytes of device workspace held for encoding (grow-only)
+COUNTER_DECODE_WORKSPACE = 4      # bytes of device workspace held for decoding (grow-only)
+COUNTER_GENERAL_FALLBACKS = 5     # decode calls whose general blocks fell back to the tile chain
+COUNTER_GENERAL_TEAM = 6          # workgroups per block (1, 2 or 4) of the last decode call's general-block pass; 0 = no general block
+COUNTER_RANGE_CHUNKS = 7          # chunks the last range read decoded or copied
+COUNTER_RANGE_SCRATCH_BYTES = 8   # decoded bytes it put into the scratch
+COUNTER_RANGE_HOST_BYTES = 9      # bytes of plan data that crossed between host and device in the last read_device
+COUNTER_SEARCH_CHUNKS = 10        # chunks the last search decoded or copied
+COUNTER_SEARCH_TABLES = 11        # chunks with a usable search table in the last search
+COUNTER_BATCH_LONG_STREAMS = 12   # streams the last stream batch call sent through the region walk (more than 4096 chunk headers)
 
 
 class MinLZError(Exception):
@@ -20,42 +43,78 @@ class MinLZError(Exception):
 
 class ErrCorrupt(MinLZError):
     """minlz: corrupt input (decode.go:31)"""
-    code = 1
+    code = ERR_CORRUPT
 
 
 class ErrTooLarge(MinLZError):
     """minlz: decoded block is too large (decode.go:35)"""
-    code = 2
+    code = ERR_TOO_LARGE
 
 
 class ErrUnsupported(MinLZError):
     """minlz: unsupported input (decode.go:37)"""
-    code = 3
+    code = ERR_UNSUPPORTED
 
 
 class ErrInvalidLevel(MinLZError):
     """minlz: invalid compression level (decode.go:39)"""
-    code = 4
+    code = ERR_INVALID_LEVEL
 
 
 class ErrCRC(MinLZError):
     """minlz: corrupt input, crc mismatch (decode.go:33)"""
-    code = 5
+    code = ERR_CRC
 
 
 class ErrHIP(MinLZError):
-    code = 7
+    code = ERR_HIP
 
 
-_ERRS = {1: ErrCorrupt, 2: ErrTooLarge, 3: ErrUnsupported, 4: ErrInvalidLevel, 5: ErrCRC, 7: ErrHIP}
+_ERRS = {e.code: e for e in (ErrCorrupt, ErrTooLarge, ErrUnsupported, ErrInvalidLevel, ErrCRC, ErrHIP)}
+
+
+def _error(code, before="", after=""):
+    """The exception of the (positive) error code: its class, "minlz error <code>" between the two texts."""
+    return _ERRS.get(code, MinLZError)("%sminlz error %d%s" % (before, code, after))
 
 
 def _raise(code, ctx=None):
     code = -code if code < 0 else code
-    msg = ""
-    if ctx is not None and code == 7:
-        msg = _lib.lib().mlz_last_error(ctx.handle).decode()
-    raise _ERRS.get(code, MinLZError)("minlz error %d %s" % (code, msg))
+    raise _error(code, after=" " + (_lib.lib().mlz_last_error(ctx.handle).decode() if ctx is not None and code == ERR_HIP else ""))
+
+
+# ---- argument marshalling, each form once ----
+
+def _flags(add_index=False, ignore_crc=False, no_tables=False, invert=False):
+    return (STREAM_ADD_INDEX if add_index else 0) | (STREAM_IGNORE_CRC if ignore_crc else 0) | (SEARCH_NO_TABLES if no_tables else 0) | (GREP_INVERT if invert else 0)
+
+
+def _patterns(patterns):
+    """A sequence of bytes objects -> (their bytes back to back, their uint32 lengths, their number): the three arguments of the ABI."""
+    pats = [bytes(p) for p in patterns]
+    return (b"".join(pats), (C.c_uint32 * len(pats))(*[len(p) for p in pats]), len(pats)) if pats else (None, None, 0)
+
+
+def _delimiter(d, what):
+    d = bytes(d) if not isinstance(d, int) else bytes([d])
+    if len(d) != 1:
+        raise ValueError(what + ": a delimiter of one byte")
+    return d[0]
+
+
+def _block_descs(descs):
+    """A BlockDesc array as it is, or a sequence of BlockDesc or of tuples (src_off, src_len[, dst_off, dst_cap]) -> the array of as many."""
+    if isinstance(descs, C.Array):
+        return descs
+    return (BlockDesc * len(descs))(*[d if isinstance(d, BlockDesc) else BlockDesc(*[int(v) for v in (tuple(d) + (0, 0))[:4]]) for d in descs])
+
+
+def _stats():
+    return (C.c_uint64 * 4)()
+
+
+def _ints(a, n=4):
+    return tuple(int(a[i]) for i in range(n))
 
 
 class Context:
@@ -77,8 +136,15 @@ class Context:
         if r != 0:
             raise ErrHIP("mlz_init failed (%d): no HIP device?" % r)
 
+    def _call(self, name, *args):
+        """The ABI function `name` on this context -> its result; a negative one raises its error."""
+        r = getattr(_lib.lib(), name)(self.handle, *args)
+        if r < 0:
+            _raise(r, self)
+        return int(r)
+
     def device_count(self):
-        return int(_lib.lib().mlz_device_count(self.handle))
+        return self._call("mlz_device_count")
 
     def close(self):
         if self.handle:
@@ -92,9 +158,7 @@ class Context:
             pass
 
     def set_option(self, opt, value):
-        r = _lib.lib().mlz_set_option(self.handle, opt, int(value))
-        if r:
-            _raise(r, self)
+        self._call("mlz_set_option", opt, int(value))
 
     def device_name(self):
         buf = C.create_string_buffer(256)
@@ -106,29 +170,46 @@ class Context:
         n = _lib.lib().mlz_get_timers(self.handle, arr, 16)
         return {_lib.lib().mlz_timer_name(i).decode(): arr[i] for i in range(n) if arr[i] >= 0}
 
+    def counter(self, which):
+        """mlz_get_counter: one of COUNTER_*."""
+        return int(_lib.lib().mlz_get_counter(self.handle, which))
+
     def combine_stats(self):
         """(batches run, requests served) by the combining queue of the single-block host calls."""
-        L = _lib.lib()
-        return int(L.mlz_get_counter(self.handle, 0)), int(L.mlz_get_counter(self.handle, 1))
+        return self.counter(COUNTER_COMBINE_BATCHES), self.counter(COUNTER_COMBINE_REQUESTS)
 
     def workspace_bytes(self):
         """(encode side, decode side): device workspace the context holds — grow-only, i.e. the high-water mark of its calls (mlz_get_counter 3, 4)."""
-        L = _lib.lib()
-        return int(L.mlz_get_counter(self.handle, 3)), int(L.mlz_get_counter(self.handle, 4))
+        return self.counter(COUNTER_ENCODE_WORKSPACE), self.counter(COUNTER_DECODE_WORKSPACE)
 
     def general_blocks(self):
         """Blocks of the last decode call that took the path for streams of other encoders (mlz_get_counter 2)."""
-        return int(_lib.lib().mlz_get_counter(self.handle, 2))
+        return self.counter(COUNTER_GENERAL_BLOCKS)
 
     def general_team(self):
         """Workgroups per block (1, 2 or 4) the general-block pass of the last decode call settled with; 0 = no general block (mlz_get_counter 6)."""
-        return int(_lib.lib().mlz_get_counter(self.handle, 6))
+        return self.counter(COUNTER_GENERAL_TEAM)
+
+    def batch_long_streams(self):
+        """Streams that the context's last stream batch call walked by the region kernels: more than 4096 chunk headers (mlz_get_counter 12)."""
+        return self.counter(COUNTER_BATCH_LONG_STREAMS)
+
+    def range_plan(self):
+        """(chunks decoded or copied, decoded bytes put into the scratch) by the context's last DeviceReader.read (mlz_get_counter 7, 8)."""
+        return self.counter(COUNTER_RANGE_CHUNKS), self.counter(COUNTER_RANGE_SCRATCH_BYTES)
+
+    def search_plan(self):
+        """(chunks decoded or copied, chunks with a usable search table) of the context's last DeviceReader.search, search_many or grep_records (mlz_get_counter 10, 11)."""
+        return self.counter(COUNTER_SEARCH_CHUNKS), self.counter(COUNTER_SEARCH_TABLES)
+
+    def range_plan_host_bytes(self):
+        """Bytes of plan data that crossed between host and device, both directions together, in the context's last DeviceReader.read_device
+        (mlz_get_counter 9): a header and two records per TOUCHED CHUNK, nothing per range."""
+        return self.counter(COUNTER_RANGE_HOST_BYTES)
 
     def release_stream(self, stream):
         """mlz_release_stream: call before destroying a stream that carried a *_batch_device call of this context."""
-        r = _lib.lib().mlz_release_stream(self.handle, stream)
-        if r:
-            _raise(r, self)
+        self._call("mlz_release_stream", stream)
 
     def stream_encode_gather_device(self, level, block_size, add_index, d_srcs, lens, d_dst, dst_cap, search_match_len=None, search_prefix=None,
                                     search_long_prefix=None, search_extras=0):
@@ -141,49 +222,26 @@ class Context:
         match length + extras <= 16).
         Returns the stream size."""
         n = len(d_srcs)
-        sp = (C.c_void_p * n)(*d_srcs); sl = (C.c_size_t * n)(*lens)
-        if search_long_prefix is not None:
-            if search_prefix is not None:
-                raise ValueError("search_long_prefix and search_prefix exclude each other")
-            if search_match_len is None:
-                raise ValueError("search_long_prefix needs search_match_len")
-            cfg = search_long_prefix_config(search_match_len, search_long_prefix, search_extras)
-            r = _lib.lib().mlz_stream_encode_gather_device_long_prefix(self.handle, level, block_size, STREAM_ADD_INDEX if add_index else 0, C.byref(cfg), sp, sl, n,
-                                                                       d_dst, dst_cap)
-            if r < 0:
-                _raise(r, self)
-            return int(r)
-        if search_extras:
-            raise ValueError("search_extras needs search_long_prefix")
-        if search_prefix is not None:
-            if search_match_len is None:
-                raise ValueError("search_prefix needs search_match_len")
-            cfg = search_tables_config(search_match_len, search_prefix)
-            r = _lib.lib().mlz_stream_encode_gather_device_tables(self.handle, level, block_size, STREAM_ADD_INDEX if add_index else 0, C.byref(cfg), sp, sl, n, d_dst, dst_cap)
-            if r < 0:
-                _raise(r, self)
-            return int(r)
-        flags = (STREAM_ADD_INDEX if add_index else 0) | (0 if search_match_len is None else STREAM_SEARCH_TABLES | (search_match_len & 15) << 8)
-        r = _lib.lib().mlz_stream_encode_gather_device(self.handle, level, block_size, flags, sp, sl, n, d_dst, dst_cap)
-        if r < 0:
-            _raise(r, self)
-        return int(r)
+        suffix, flags, cfg = _writer_tables(search_match_len, search_prefix, search_long_prefix, search_extras)
+        return self._call("mlz_stream_encode_gather_device" + suffix, level, block_size, _flags(add_index=add_index) | flags, *cfg,
+                          (C.c_void_p * n)(*d_srcs), (C.c_size_t * n)(*lens), n, d_dst, dst_cap)
 
     # ---- device-resident batch calls: pointers are raw device addresses (e.g. tensor.data_ptr()) ----
+    # (the three block calls are the benchmark's step: the ctypes call and its check stand here themselves, nothing between them and the caller)
     def encode_batch_device(self, stream, level, d_src, d_dst, descs, d_out_len):
-        arr = (BlockDesc * len(descs))(*descs) if not isinstance(descs, C.Array) else descs
+        arr = descs if isinstance(descs, C.Array) else _block_descs(descs)
         r = _lib.lib().mlz_encode_batch_device(self.handle, stream, level, d_src, d_dst, arr, len(arr), d_out_len)
         if r:
             _raise(r, self)
 
     def crc_batch_device(self, stream, d_base, descs, d_out_u32):
-        arr = (BlockDesc * len(descs))(*descs) if not isinstance(descs, C.Array) else descs
+        arr = descs if isinstance(descs, C.Array) else _block_descs(descs)
         r = _lib.lib().mlz_crc_batch_device(self.handle, stream, d_base, arr, len(arr), d_out_u32)
         if r:
             _raise(r, self)
 
     def decode_batch_device(self, stream, d_src, d_dst, descs, d_out_len):
-        arr = (BlockDesc * len(descs))(*descs) if not isinstance(descs, C.Array) else descs
+        arr = descs if isinstance(descs, C.Array) else _block_descs(descs)
         r = _lib.lib().mlz_decode_batch_device(self.handle, stream, d_src, d_dst, arr, len(arr), d_out_len)
         if r:
             _raise(r, self)
@@ -197,78 +255,42 @@ class Context:
 
     def stream_decode_device(self, d_src, n, d_dst, dst_cap, ignore_crc=False, stream=None):
         """mlz_stream_decode_device: NewReader(src) read to EOF, source and destination in device memory -> decoded size."""
-        r = _lib.lib().mlz_stream_decode_device(self.handle, stream, STREAM_IGNORE_CRC if ignore_crc else 0, d_src, n, d_dst, dst_cap)
-        if r < 0:
-            _raise(r, self)
-        return int(r)
+        return self._call("mlz_stream_decode_device", stream, _flags(ignore_crc=ignore_crc), d_src, n, d_dst, dst_cap)
 
     # ---- batches of streams in device memory: one call for many streams; per-stream results come back as lists, nothing is raised per stream ----
-    @staticmethod
-    def _stream_descs(descs):
-        if isinstance(descs, C.Array):
-            return descs
-        return (BlockDesc * max(len(descs), 1))(*[BlockDesc(*[int(v) for v in (tuple(d) + (0, 0))[:4]]) for d in descs])
-
     def stream_decoded_len_batch_device(self, d_src, spans, stream=None):
         """mlz_stream_decoded_len_batch_device: the chunk walk of every stream (src_off, src_len) of the buffer at d_src ->
         [(result, prefix_len)], each as stream_decoded_len_device gives it for that stream alone."""
-        n = len(spans)
+        arr = _block_descs(spans)
+        n = len(arr)
         out = (C.c_int64 * max(n, 1))()
         prefix = (C.c_uint64 * max(n, 1))()
-        r = _lib.lib().mlz_stream_decoded_len_batch_device(self.handle, stream, d_src, self._stream_descs(spans), n, out, prefix)
-        if r:
-            _raise(r, self)
+        self._call("mlz_stream_decoded_len_batch_device", stream, d_src, arr, n, out, prefix)
         return [(int(out[i]), int(prefix[i])) for i in range(n)]
 
     def stream_decode_batch_device(self, d_src, d_dst, descs, ignore_crc=False, stream=None):
         """mlz_stream_decode_batch_device: every stream (src_off, src_len, dst_off, dst_cap) of the buffer at d_src decoded to its place in the
         buffer at d_dst -> [result]: the decoded size or -MLZ_ERR_* of each stream, as mlz_stream_decode_device returns it for that stream alone."""
-        n = len(descs)
+        arr = _block_descs(descs)
+        n = len(arr)
         out = (C.c_int64 * max(n, 1))()
-        r = _lib.lib().mlz_stream_decode_batch_device(self.handle, stream, STREAM_IGNORE_CRC if ignore_crc else 0, d_src, d_dst, self._stream_descs(descs), n, out)
-        if r:
-            _raise(r, self)
+        self._call("mlz_stream_decode_batch_device", stream, _flags(ignore_crc=ignore_crc), d_src, d_dst, arr, n, out)
         return [int(out[i]) for i in range(n)]
 
     def stream_encode_batch_device(self, level, block_size, add_index, d_src, d_dst, descs, stream=None, flags=0):
         """mlz_stream_encode_batch_device: every input (src_off, src_len, dst_off, dst_cap) of the buffer at d_src written as a stream of its own to
         its place in the buffer at d_dst -> [result]: the stream's size or -MLZ_ERR_* of each.  flags: further MLZ_STREAM_* bits, as they are."""
-        n = len(descs)
+        arr = _block_descs(descs)
+        n = len(arr)
         out = (C.c_int64 * max(n, 1))()
-        r = _lib.lib().mlz_stream_encode_batch_device(self.handle, stream, level, block_size, (STREAM_ADD_INDEX if add_index else 0) | flags, d_src, d_dst,
-                                                      self._stream_descs(descs), n, out)
-        if r:
-            _raise(r, self)
+        self._call("mlz_stream_encode_batch_device", stream, level, block_size, _flags(add_index=add_index) | flags, d_src, d_dst, arr, n, out)
         return [int(out[i]) for i in range(n)]
-
-    def batch_long_streams(self):
-        """Streams that the context's last stream batch call walked by the region kernels: more than 4096 chunk headers (mlz_get_counter 12)."""
-        return int(_lib.lib().mlz_get_counter(self.handle, 12))
-
 
     def stream_open_device(self, d_src, n, stream=None):
         """mlz_stream_open_device: a stream in device memory opened for range reads -> DeviceReader.  The caller keeps d_src alive and unchanged
         while the reader is open.  A stream with a framing error raises that error (no reader)."""
         h = C.c_void_p()
-        r = _lib.lib().mlz_stream_open_device(self.handle, stream, d_src, n, C.byref(h))
-        if r < 0:
-            _raise(r, self)
-        return DeviceReader(self, h, int(r))
-
-    def range_plan(self):
-        """(chunks decoded or copied, decoded bytes put into the scratch) by the context's last DeviceReader.read (mlz_get_counter 7, 8)."""
-        L = _lib.lib()
-        return int(L.mlz_get_counter(self.handle, 7)), int(L.mlz_get_counter(self.handle, 8))
-
-    def search_plan(self):
-        """(chunks decoded or copied, chunks with a usable search table) of the context's last DeviceReader.search, search_many or grep_records (mlz_get_counter 10, 11)."""
-        L = _lib.lib()
-        return int(L.mlz_get_counter(self.handle, 10)), int(L.mlz_get_counter(self.handle, 11))
-
-    def range_plan_host_bytes(self):
-        """Bytes of plan data that crossed between host and device, both directions together, in the context's last DeviceReader.read_device
-        (mlz_get_counter 9): a header and two records per TOUCHED CHUNK, nothing per range."""
-        return int(_lib.lib().mlz_get_counter(self.handle, 9))
+        return DeviceReader(self, h, self._call("mlz_stream_open_device", stream, d_src, n, C.byref(h)))
 
 
 class DeviceReader:
@@ -277,27 +299,30 @@ class DeviceReader:
     def __init__(self, ctx, handle, size):
         self.ctx, self.handle, self.size = ctx, handle, size
 
-    def read(self, ranges, d_dst, dst_cap, ignore_crc=False, stream=None):
-        """mlz_dev_reader_read.  ranges: (off, len, dst_off) triples, or a C-contiguous uint64 array of shape (k, 3): decoded bytes
-        [off, off + len) go to d_dst[dst_off, dst_off + len).  -> the sum of the lengths."""
+    def _open(self):
         if not self.handle:
             raise ValueError("DeviceReader is closed")
-        a = np.ascontiguousarray(ranges, dtype=np.uint64).reshape(-1, 3)
-        r = _lib.lib().mlz_dev_reader_read(self.handle, stream, STREAM_IGNORE_CRC if ignore_crc else 0, a.ctypes.data if a.size else None, a.shape[0], d_dst, dst_cap)
+        return self.handle
+
+    def _call(self, name, *args):
+        """The ABI function `name` on this reader -> its result; a closed reader is refused, a negative result raises its error."""
+        handle = self._open()
+        r = getattr(_lib.lib(), name)(handle, *args)
         if r < 0:
             _raise(r, self.ctx)
         return int(r)
+
+    def read(self, ranges, d_dst, dst_cap, ignore_crc=False, stream=None):
+        """mlz_dev_reader_read.  ranges: (off, len, dst_off) triples, or a C-contiguous uint64 array of shape (k, 3): decoded bytes
+        [off, off + len) go to d_dst[dst_off, dst_off + len).  -> the sum of the lengths."""
+        a = np.ascontiguousarray(ranges, dtype=np.uint64).reshape(-1, 3)
+        return self._call("mlz_dev_reader_read", stream, _flags(ignore_crc=ignore_crc), _ptr(a), a.shape[0], d_dst, dst_cap)
 
     def read_device(self, d_off, d_len, n, d_dst, dst_cap, d_starts=None, ignore_crc=False, stream=None):
         """mlz_dev_reader_read_device.  d_off, d_len: device addresses of n uint64 offsets and lengths; decoded bytes [off[i], off[i] + len[i])
         go to d_dst packed in the order given; d_starts (device address of n + 1 uint64, or None) receives where each range starts and the
         total.  -> the sum of the lengths."""
-        if not self.handle:
-            raise ValueError("DeviceReader is closed")
-        r = _lib.lib().mlz_dev_reader_read_device(self.handle, stream, STREAM_IGNORE_CRC if ignore_crc else 0, d_off, d_len, n, d_dst, dst_cap, d_starts)
-        if r < 0:
-            _raise(r, self.ctx)
-        return int(r)
+        return self._call("mlz_dev_reader_read_device", stream, _flags(ignore_crc=ignore_crc), d_off, d_len, n, d_dst, dst_cap, d_starts)
 
     def search(self, pattern, d_offsets, cap, ignore_crc=False, no_tables=False, stream=None):
         """mlz_dev_reader_search.  pattern: 1 .. 256 bytes; d_offsets: device address of room for `cap` uint64 (None with cap == 0), which
@@ -305,15 +330,9 @@ class DeviceReader:
         Uses the stream's block search tables of type 1, 2, 3 or 4 (with a prefix table: the pattern's windows that follow a prefix byte; a
         pattern without one is served by decoding every chunk, and the usable-table count is then 0).
         -> (total, (data chunks, chunks decoded or copied, chunks with a usable search table))."""
-        if not self.handle:
-            raise ValueError("DeviceReader is closed")
-        p = bytes(pattern)
-        stats = (C.c_uint64 * 4)()
-        flags = (STREAM_IGNORE_CRC if ignore_crc else 0) | (SEARCH_NO_TABLES if no_tables else 0)
-        r = _lib.lib().mlz_dev_reader_search(self.handle, stream, flags, p, len(p), d_offsets, cap, stats)
-        if r < 0:
-            _raise(r, self.ctx)
-        return int(r), (int(stats[0]), int(stats[1]), int(stats[2]))
+        p, stats = bytes(pattern), _stats()
+        r = self._call("mlz_dev_reader_search", stream, _flags(ignore_crc=ignore_crc, no_tables=no_tables), p, len(p), d_offsets, cap, stats)
+        return r, _ints(stats, 3)
 
     def search_many(self, patterns, d_counts, d_offsets, d_which, cap, ignore_crc=False, no_tables=False, stream=None):
         """mlz_dev_reader_search_many.  patterns: a sequence of up to 4096 bytes objects of 1 .. 256 bytes; d_counts: device address of room
@@ -321,18 +340,9 @@ class DeviceReader:
         room for `cap` uint64 and `cap` uint32 (None with cap == 0), which receive the smallest min(total, cap) pairs (position, pattern
         index) in ascending order.  The chunks that any pattern's tables admit are decoded once and scanned once for all patterns.
         -> (total pairs, (data chunks, chunks decoded or copied, chunks with a usable search table, patterns the tables could not serve))."""
-        if not self.handle:
-            raise ValueError("DeviceReader is closed")
-        pats = [bytes(p) for p in patterns]
-        blob = b"".join(pats)
-        lens = np.asarray([len(p) for p in pats], dtype=np.uint32)
-        stats = (C.c_uint64 * 4)()
-        flags = (STREAM_IGNORE_CRC if ignore_crc else 0) | (SEARCH_NO_TABLES if no_tables else 0)
-        r = _lib.lib().mlz_dev_reader_search_many(self.handle, stream, flags, blob if pats else None, lens.ctypes.data if pats else None, len(pats), d_counts, d_offsets,
-                                                  d_which, cap, stats)
-        if r < 0:
-            _raise(r, self.ctx)
-        return int(r), tuple(int(v) for v in stats)
+        stats = _stats()
+        r = self._call("mlz_dev_reader_search_many", stream, _flags(ignore_crc=ignore_crc, no_tables=no_tables), *_patterns(patterns), d_counts, d_offsets, d_which, cap, stats)
+        return r, _ints(stats)
 
     def search_records(self, pattern, delimiter, d_dst, dst_cap, d_rec_off, d_rec_start, d_rec_flags, rec_cap, max_reach=0, ignore_crc=False, no_tables=False, stream=None):
         """mlz_dev_reader_search_records: the records (maximal runs without the byte `delimiter`) that hold `pattern` (1 .. 256 bytes without
@@ -343,19 +353,11 @@ class DeviceReader:
         max_reach: how far the call looks to either side of an occurrence (0 = 65536, at most 2^20); longer records come out cut.
         -> (records, (records, bytes of all records, occurrences, records with a flag), (data chunks, chunks decoded or copied by the
         search phase, chunks with a usable search table))."""
-        if not self.handle:
-            raise ValueError("DeviceReader is closed")
-        p = bytes(pattern)
-        d = bytes(delimiter) if not isinstance(delimiter, int) else bytes([delimiter])
-        if len(d) != 1:
-            raise ValueError("search_records: a delimiter of one byte")
-        totals, stats = (C.c_uint64 * 4)(), (C.c_uint64 * 4)()
-        flags = (STREAM_IGNORE_CRC if ignore_crc else 0) | (SEARCH_NO_TABLES if no_tables else 0)
-        r = _lib.lib().mlz_dev_reader_search_records(self.handle, stream, flags, p, len(p), d[0], max_reach, d_dst, dst_cap, d_rec_off, d_rec_start, d_rec_flags, rec_cap,
-                                                     totals, stats)
-        if r < 0:
-            _raise(r, self.ctx)
-        return int(r), tuple(int(v) for v in totals), (int(stats[0]), int(stats[1]), int(stats[2]))
+        self._open()
+        p, totals, stats = bytes(pattern), _stats(), _stats()
+        r = self._call("mlz_dev_reader_search_records", stream, _flags(ignore_crc=ignore_crc, no_tables=no_tables), p, len(p), _delimiter(delimiter, "search_records"),
+                       max_reach, d_dst, dst_cap, d_rec_off, d_rec_start, d_rec_flags, rec_cap, totals, stats)
+        return r, _ints(totals), _ints(stats, 3)
 
     def index_records(self, delimiter=b"\n", ignore_crc=False, stream=None):
         """mlz_dev_reader_index_records: builds the record index for the one-byte `delimiter` — the positions of all delimiters of the
@@ -363,59 +365,33 @@ class DeviceReader:
         delimiter r - 1 and delimiter r; empty records count; a stream that ends without a delimiter has one more record.  The same
         delimiter again costs nothing; another one replaces the index.
         -> (N, (N, delimiters, bytes of index held, chunks this call decoded))."""
-        if not self.handle:
-            raise ValueError("DeviceReader is closed")
-        d = bytes(delimiter) if not isinstance(delimiter, int) else bytes([delimiter])
-        if len(d) != 1:
-            raise ValueError("index_records: a delimiter of one byte")
-        info = (C.c_uint64 * 4)()
-        r = _lib.lib().mlz_dev_reader_index_records(self.handle, stream, STREAM_IGNORE_CRC if ignore_crc else 0, d[0], info)
-        if r < 0:
-            _raise(r, self.ctx)
-        return int(r), tuple(int(v) for v in info)
+        self._open()
+        info = _stats()
+        r = self._call("mlz_dev_reader_index_records", stream, _flags(ignore_crc=ignore_crc), _delimiter(delimiter, "index_records"), info)
+        return r, _ints(info)
 
     def record_count(self):
         """mlz_dev_reader_record_count: the records of the indexed stream; raises without an index."""
-        if not self.handle:
-            raise ValueError("DeviceReader is closed")
-        r = _lib.lib().mlz_dev_reader_record_count(self.handle)
-        if r < 0:
-            _raise(r, self.ctx)
-        return int(r)
+        return self._call("mlz_dev_reader_record_count")
 
     def record_spans(self, d_idx, n, d_off, d_len, stream=None):
         """mlz_dev_reader_record_spans.  d_idx: device address of n uint64 record numbers (any order, repeats allowed); d_off, d_len:
         device addresses of room for n uint64 each, which receive every record's first byte in the decoded stream and its length.
         -> the sum of the lengths.  A number >= record_count() raises."""
-        if not self.handle:
-            raise ValueError("DeviceReader is closed")
-        r = _lib.lib().mlz_dev_reader_record_spans(self.handle, stream, d_idx, n, d_off, d_len)
-        if r < 0:
-            _raise(r, self.ctx)
-        return int(r)
+        return self._call("mlz_dev_reader_record_spans", stream, d_idx, n, d_off, d_len)
 
     def read_records(self, d_idx, n, d_dst, dst_cap, d_starts=None, ignore_crc=False, stream=None):
         """mlz_dev_reader_read_records: the records d_idx[0 .. n) (device address of uint64 record numbers) packed into d_dst in the order
         given; d_starts (device address of n + 1 uint64, or None) receives where each record starts in d_dst and the total.  Only the
         chunks the records touch are decoded, each once.  -> the bytes written.  A number >= record_count() or a total above dst_cap
         raises, and nothing has been written then."""
-        if not self.handle:
-            raise ValueError("DeviceReader is closed")
-        r = _lib.lib().mlz_dev_reader_read_records(self.handle, stream, STREAM_IGNORE_CRC if ignore_crc else 0, d_idx, n, d_dst, dst_cap, d_starts)
-        if r < 0:
-            _raise(r, self.ctx)
-        return int(r)
+        return self._call("mlz_dev_reader_read_records", stream, _flags(ignore_crc=ignore_crc), d_idx, n, d_dst, dst_cap, d_starts)
 
     def record_numbers(self, d_pos, n, d_no, stream=None):
         """mlz_dev_reader_record_numbers.  d_pos: device address of n uint64 positions of the decoded stream; d_no: room for n uint64, which
         receive each position's record number (0-based; a delimiter has the number of the record it ends; 2^64 - 1 for a position at or
         beyond the size).  -> how many positions lie inside the stream."""
-        if not self.handle:
-            raise ValueError("DeviceReader is closed")
-        r = _lib.lib().mlz_dev_reader_record_numbers(self.handle, stream, d_pos, n, d_no)
-        if r < 0:
-            _raise(r, self.ctx)
-        return int(r)
+        return self._call("mlz_dev_reader_record_numbers", stream, d_pos, n, d_no)
 
     def grep_records(self, patterns, d_rec_no, d_rec_kind, rec_cap, invert=False, before=0, after=0, ignore_crc=False, no_tables=False, stream=None):
         """mlz_dev_reader_grep_records: grep over the record index.  patterns: a sequence of up to 4096 bytes objects of 1 .. 256 bytes
@@ -425,28 +401,16 @@ class DeviceReader:
         of the selected and context records, ascending; d_rec_kind: room for rec_cap bytes or None, 1 = selected, 0 = context only.
         -> (R, (R, selected records, bytes of the written records: read_records' dst_cap, bytes of all R records), (data chunks, chunks
         decoded or copied, chunks with a usable search table, patterns the tables could not serve))."""
-        if not self.handle:
-            raise ValueError("DeviceReader is closed")
-        pats = [bytes(p) for p in patterns]
-        blob = b"".join(pats)
-        lens = np.asarray([len(p) for p in pats], dtype=np.uint32)
-        totals, stats = (C.c_uint64 * 4)(), (C.c_uint64 * 4)()
-        flags = (STREAM_IGNORE_CRC if ignore_crc else 0) | (SEARCH_NO_TABLES if no_tables else 0) | (GREP_INVERT if invert else 0)
-        r = _lib.lib().mlz_dev_reader_grep_records(self.handle, stream, flags, blob if pats else None, lens.ctypes.data if pats else None, len(pats), before, after, d_rec_no,
-                                                   d_rec_kind, rec_cap, totals, stats)
-        if r < 0:
-            _raise(r, self.ctx)
-        return int(r), tuple(int(v) for v in totals), tuple(int(v) for v in stats)
+        totals, stats = _stats(), _stats()
+        r = self._call("mlz_dev_reader_grep_records", stream, _flags(ignore_crc=ignore_crc, no_tables=no_tables, invert=invert), *_patterns(patterns), before, after,
+                       d_rec_no, d_rec_kind, rec_cap, totals, stats)
+        return r, _ints(totals), _ints(stats)
 
     def record_range(self, first, count):
         """mlz_dev_reader_record_range: records first .. first + count - 1 as one byte range, the delimiters between them included
         -> (off, len), to be read with read().  first + count > record_count() raises."""
-        if not self.handle:
-            raise ValueError("DeviceReader is closed")
         off, ln = C.c_uint64(), C.c_uint64()
-        r = _lib.lib().mlz_dev_reader_record_range(self.handle, first, count, C.byref(off), C.byref(ln))
-        if r < 0:
-            _raise(r, self.ctx)
+        self._call("mlz_dev_reader_record_range", first, count, C.byref(off), C.byref(ln))
         return int(off.value), int(ln.value)
 
     @staticmethod
@@ -459,41 +423,21 @@ class DeviceReader:
 
     def sidecar_bound(self, cfgs):
         """mlz_dev_reader_sidecar_bound: room that always suffices for build_sidecar with these configurations (api.search_config)."""
-        if not self.handle:
-            raise ValueError("DeviceReader is closed")
-        arr, n = self._configs(cfgs)
-        r = _lib.lib().mlz_dev_reader_sidecar_bound(self.handle, arr, n)
-        if r < 0:
-            _raise(r, self.ctx)
-        return int(r)
+        return self._call("mlz_dev_reader_sidecar_bound", *self._configs(cfgs))
 
     def build_sidecar(self, cfgs, d_dst, cap, ignore_crc=False, stream=None):
         """mlz_dev_reader_build_sidecar: the sidecar of this stream for 1 .. 4 configurations (api.search_config) — search tables for every
         data chunk in a separate stream that names the chunks by remote references — into `cap` bytes at device address d_dst -> its size."""
-        if not self.handle:
-            raise ValueError("DeviceReader is closed")
-        arr, n = self._configs(cfgs)
-        r = _lib.lib().mlz_dev_reader_build_sidecar(self.handle, stream, STREAM_IGNORE_CRC if ignore_crc else 0, arr, n, d_dst, cap)
-        if r < 0:
-            _raise(r, self.ctx)
-        return int(r)
+        return self._call("mlz_dev_reader_build_sidecar", stream, _flags(ignore_crc=ignore_crc), *self._configs(cfgs), d_dst, cap)
 
     def attach_sidecar(self, d_side, n, ignore_crc=False, stream=None):
         """mlz_dev_reader_attach_sidecar: search and search_many use the tables of the sidecar at device address d_side (n bytes) from now
         on.  The caller keeps those bytes alive and unchanged.  A sidecar that does not belong to this stream raises, and nothing changes."""
-        if not self.handle:
-            raise ValueError("DeviceReader is closed")
-        r = _lib.lib().mlz_dev_reader_attach_sidecar(self.handle, stream, STREAM_IGNORE_CRC if ignore_crc else 0, d_side, n)
-        if r < 0:
-            _raise(r, self.ctx)
+        self._call("mlz_dev_reader_attach_sidecar", stream, _flags(ignore_crc=ignore_crc), d_side, n)
 
     def detach_sidecar(self):
         """The searches use the stream's inline tables again."""
-        if not self.handle:
-            raise ValueError("DeviceReader is closed")
-        r = _lib.lib().mlz_dev_reader_attach_sidecar(self.handle, None, 0, None, 0)
-        if r < 0:
-            _raise(r, self.ctx)
+        self._call("mlz_dev_reader_attach_sidecar", None, 0, None, 0)
 
     def close(self):
         if self.handle:
@@ -553,10 +497,7 @@ def DecodedLen(src):
 def IsMinLZ(src):
     """decode.go:114-117 -> (ok, size); raises like the reference returns err."""
     a = _np(src)
-    r = _lib.lib().mlz_decoded_len(_ptr(a), a.size)
-    if r < 0:
-        _raise(r)
-    return (a.size > 0 and a[0] == 0), r
+    return (a.size > 0 and a[0] == 0), DecodedLen(a)
 
 
 def Encode(src, level=LevelFastest, ctx=None):
@@ -567,10 +508,7 @@ def Encode(src, level=LevelFastest, ctx=None):
     if cap_ < 0:
         raise ErrTooLarge()
     out = np.empty(cap_, dtype=np.uint8)
-    r = _lib.lib().mlz_encode(ctx.handle, level, _ptr(a), a.size, out.ctypes.data, cap_)
-    if r < 0:
-        _raise(r, ctx)
-    return out[:r].tobytes()
+    return out[:ctx._call("mlz_encode", level, _ptr(a), a.size, out.ctypes.data, cap_)].tobytes()
 
 
 def AppendEncoded(dst, src, level=LevelFastest, ctx=None):
@@ -612,79 +550,70 @@ def AppendDecoded(dst, src, ctx=None):
 
 def crc(b, ctx=None):
     """crc(b) of minlz.go:133-140 (masked CRC32C), computed on the device."""
-    ctx = ctx or default_context()
     a = _np(b)
-    r = _lib.lib().mlz_crc(ctx.handle, _ptr(a), a.size)
-    if r < 0:
-        _raise(r, ctx)
-    return int(r)
+    return (ctx or default_context())._call("mlz_crc", _ptr(a), a.size)
 
 
 def encode_block(src, level=LevelFastest, ctx=None):
     """encodeBlock(dst, src) / WriterCustomEncoder contract (writer.go:1293-1304): tokens only; b'' = incompressible."""
-    ctx = ctx or default_context()
     a = _np(src)
     out = np.empty(a.size + 16, dtype=np.uint8)
-    r = _lib.lib().mlz_encode_block(ctx.handle, level, _ptr(a), a.size, out.ctypes.data, out.size)
-    if r < 0:
-        _raise(r, ctx)
-    return out[:r].tobytes()
+    return out[:(ctx or default_context())._call("mlz_encode_block", level, _ptr(a), a.size, out.ctypes.data, out.size)].tobytes()
 
 
 def decode_block(body, dlen, ctx=None):
     """minLZDecode(dst[:dlen], body) (decode.go:178): returns (code, bytes)."""
-    ctx = ctx or default_context()
     a = _np(body)
     out = np.zeros(max(dlen, 1), dtype=np.uint8)
-    r = _lib.lib().mlz_decode_block(ctx.handle, _ptr(a), a.size, out.ctypes.data, dlen)
-    if r < 0:
-        _raise(r, ctx)
-    return r, out[:dlen].tobytes()
+    return (ctx or default_context())._call("mlz_decode_block", _ptr(a), a.size, out.ctypes.data, dlen), out[:dlen].tobytes()
+
+
+def _host_batch(ctx, name, lead, blocks, caps):
+    """The host-pointer batch call `name` (arguments `lead` in front of the count) over `blocks`, block i into caps(block i) bytes of room
+    -> the results' bytes; the first block that failed raises its error."""
+    ctx = ctx or default_context()
+    arrs = [_np(b) for b in blocks]
+    n = len(arrs)
+    caps = [caps(a) for a in arrs]
+    outs = [np.empty(max(c, 1), dtype=np.uint8) for c in caps]
+    vp, sz = C.c_void_p, C.c_size_t
+    ol = (C.c_int64 * n)()
+    ctx._call(name, *lead, n, (vp * n)(*[_ptr(a) for a in arrs]), (sz * n)(*[a.size for a in arrs]), (vp * n)(*[o.ctypes.data for o in outs]), (sz * n)(*caps), ol)
+    for v in ol:
+        if v < 0:
+            _raise(v, ctx)
+    return [o[:v].tobytes() for o, v in zip(outs, ol)]
 
 
 def encode_batch(blocks, level=LevelFastest, ctx=None):
     """mlz_encode_batch over a list of byte blocks -> list of encoded blocks."""
-    ctx = ctx or default_context()
-    arrs = [_np(b) for b in blocks]
-    n = len(arrs)
-    outs = [np.empty(max(MaxEncodedLen(a.size), 1), dtype=np.uint8) for a in arrs]
-    vp, sz = C.c_void_p, C.c_size_t
-    srcp = (vp * n)(*[_ptr(a) for a in arrs]); srcl = (sz * n)(*[a.size for a in arrs])
-    dstp = (vp * n)(*[o.ctypes.data for o in outs]); dstc = (sz * n)(*[o.size for o in outs])
-    ol = (C.c_int64 * n)()
-    r = _lib.lib().mlz_encode_batch(ctx.handle, level, n, srcp, srcl, dstp, dstc, ol)
-    if r:
-        _raise(r, ctx)
-    res = []
-    for i in range(n):
-        if ol[i] < 0:
-            _raise(ol[i], ctx)
-        res.append(outs[i][:ol[i]].tobytes())
-    return res
+    return _host_batch(ctx, "mlz_encode_batch", (level,), blocks, lambda a: max(MaxEncodedLen(a.size), 1))
 
 
 def decode_batch(blocks, ctx=None):
-    ctx = ctx or default_context()
-    arrs = [_np(b) for b in blocks]
-    n = len(arrs)
-    lens = [DecodedLen(a) for a in arrs]
-    outs = [np.empty(max(l, 1), dtype=np.uint8) for l in lens]
-    vp, sz = C.c_void_p, C.c_size_t
-    srcp = (vp * n)(*[_ptr(a) for a in arrs]); srcl = (sz * n)(*[a.size for a in arrs])
-    dstp = (vp * n)(*[o.ctypes.data for o in outs]); dstc = (sz * n)(*lens)
-    ol = (C.c_int64 * n)()
-    r = _lib.lib().mlz_decode_batch(ctx.handle, n, srcp, srcl, dstp, dstc, ol)
-    if r:
-        _raise(r, ctx)
-    res = []
-    for i in range(n):
-        if ol[i] < 0:
-            _raise(ol[i], ctx)
-        res.append(outs[i][:ol[i]].tobytes())
-    return res
+    return _host_batch(ctx, "mlz_decode_batch", (), blocks, DecodedLen)
 
 
-STREAM_ADD_INDEX, STREAM_IGNORE_CRC, STREAM_SEARCH_TABLES, SEARCH_NO_TABLES, GREP_INVERT = 1, 2, 4, 8, 16
+# ---- search table configurations ----
+
+def _put_prefix(cfg, pfx, mask=False):
+    """The prefix field of a configuration: the bytes as they come, or (mask) the 256-bit set of their values."""
+    for i, v in enumerate(pfx):
+        if mask:
+            cfg.prefix[v >> 3] |= 1 << (v & 7)
+        else:
+            cfg.prefix[i] = v
+    return len(pfx)
+
+
+def _check_ranges(match_len, long_prefix=None, extras=0):
+    """The ranges of the match length and, for a long prefix (table type 4), of its length and the extras."""
+    if long_prefix is not None and not 1 <= len(long_prefix) <= 256:
+        raise ValueError("search_long_prefix: 1 .. 256 bytes")
+    if not 0 <= match_len <= 8:
+        raise ValueError("search_match_len: 0 .. 8")
+    if long_prefix is not None and (not 0 <= extras <= 15 or (match_len or 6) + extras > 16):
+        raise ValueError("search_extras: 0 .. 15, match length + extras <= 16")
 
 
 def search_tables_config(match_len, prefix):
@@ -696,31 +625,20 @@ def search_tables_config(match_len, prefix):
     cfg = _lib.SearchTables()
     cfg.match_len = match_len & 255
     if 1 <= len(vals) <= 8:
-        cfg.table_type, cfg.n_prefix = 2, len(vals)
-        for i, v in enumerate(vals):
-            cfg.prefix[i] = v
+        cfg.table_type, cfg.n_prefix = 2, _put_prefix(cfg, vals)
     else:
         cfg.table_type = 3
-        for v in vals:
-            cfg.prefix[v >> 3] |= 1 << (v & 7)
+        _put_prefix(cfg, vals, mask=True)
     return cfg
 
 
 def search_long_prefix_config(match_len, prefix, extras=0):
     """An mlz_search_long_prefix (table type 4): a prefix of 1 .. 256 bytes, match length 0 (= 6) .. 8, extras 0 .. 15 with match length +
     extras <= 16.  ValueError outside these ranges."""
-    pfx = bytes(prefix)
-    match_len, extras = int(match_len), int(extras)
-    if not 1 <= len(pfx) <= 256:
-        raise ValueError("search_long_prefix: 1 .. 256 bytes")
-    if not 0 <= match_len <= 8:
-        raise ValueError("search_match_len: 0 .. 8")
-    if not 0 <= extras <= 15 or (match_len or 6) + extras > 16:
-        raise ValueError("search_extras: 0 .. 15, match length + extras <= 16")
+    pfx, match_len, extras = bytes(prefix), int(match_len), int(extras)
+    _check_ranges(match_len, pfx, extras)
     cfg = _lib.SearchLongPrefix()
-    cfg.match_len, cfg.extras, cfg.prefix_len = match_len, extras, len(pfx)
-    for i, v in enumerate(pfx):
-        cfg.prefix[i] = v
+    cfg.match_len, cfg.extras, cfg.prefix_len = match_len, extras, _put_prefix(cfg, pfx)
     return cfg
 
 
@@ -731,45 +649,56 @@ def search_config(table_type, match_len=None, prefix=b"", extras=0):
     table_type, match_len, extras, pfx = int(table_type), int(match_len or 0), int(extras), bytes(prefix)
     if not 1 <= table_type <= 4:
         raise ValueError("search_config: table type 1 .. 4")
-    if not 0 <= match_len <= 8:
-        raise ValueError("search_match_len: 0 .. 8")
+    _check_ranges(match_len)
     if table_type != 4 and extras:
         raise ValueError("search_extras: table type 4 only")
     cfg = _lib.SearchConfig()
     cfg.table_type, cfg.match_len, cfg.extras = table_type, match_len, extras
-    if table_type == 2:
-        if not 1 <= len(pfx) <= 8:
-            raise ValueError("search_config: type 2 takes 1 .. 8 byte values")
-        cfg.prefix_len = len(pfx)
-        for i, v in enumerate(pfx):
-            cfg.prefix[i] = v
-    elif table_type == 3:
-        for v in pfx:
-            cfg.prefix[v >> 3] |= 1 << (v & 7)
-    elif table_type == 4:
-        if not 1 <= len(pfx) <= 256:
-            raise ValueError("search_long_prefix: 1 .. 256 bytes")
-        if not 0 <= extras <= 15 or (match_len or 6) + extras > 16:
-            raise ValueError("search_extras: 0 .. 15, match length + extras <= 16")
-        cfg.prefix_len = len(pfx)
-        for i, v in enumerate(pfx):
-            cfg.prefix[i] = v
+    if table_type == 2 and not 1 <= len(pfx) <= 8:
+        raise ValueError("search_config: type 2 takes 1 .. 8 byte values")
+    if table_type == 4:
+        _check_ranges(match_len, pfx, extras)
+    if table_type == 3:
+        _put_prefix(cfg, pfx, mask=True)
+    elif table_type != 1:
+        cfg.prefix_len = _put_prefix(cfg, pfx)
     return cfg
+
+
+def _writer_tables(search_match_len, search_prefix, search_long_prefix, search_extras):
+    """The Writer's search keywords -> (which C entry points: the suffix of mlz_stream_bound and mlz_stream_encode_gather_device, their
+    search flags, their config argument: a tuple of one or none)."""
+    if search_long_prefix is not None:
+        if search_prefix is not None:
+            raise ValueError("search_long_prefix and search_prefix exclude each other")
+        if search_match_len is None:
+            raise ValueError("search_long_prefix needs search_match_len")
+        return "_long_prefix", 0, (C.byref(search_long_prefix_config(search_match_len, search_long_prefix, search_extras)),)
+    if search_extras:
+        raise ValueError("search_extras needs search_long_prefix")
+    if search_prefix is not None:
+        if search_match_len is None:
+            raise ValueError("search_prefix needs search_match_len")
+        return "_tables", 0, (C.byref(search_tables_config(search_match_len, search_prefix)),)
+    return "", 0 if search_match_len is None else STREAM_SEARCH_TABLES | (search_match_len & 15) << 8, ()
+
+
+def stream_bound(n, block_size, add_index=False, search_match_len=None, search_prefix=None, search_long_prefix=None, search_extras=0):
+    """mlz_stream_bound, _tables or _long_prefix: the room that always suffices for a stream of n bytes written with these settings (the
+    search keywords are Context.stream_encode_gather_device's).  Host only; raises for a block size or a configuration the Writer refuses."""
+    suffix, flags, cfg = _writer_tables(search_match_len, search_prefix, search_long_prefix, search_extras)
+    r = getattr(_lib.lib(), "mlz_stream_bound" + suffix)(n, block_size, _flags(add_index=add_index) | flags, *cfg)
+    if r < 0:
+        _raise(r)
+    return int(r)
 
 
 def stream_encode(src, level=LevelFastest, block_size=2 << 20, add_index=False, ctx=None):
     """mlz_stream_encode: NewWriter(...).EncodeBuffer(src) + Close() in one call -> the .mz stream bytes."""
     ctx = ctx or default_context()
     a = _np(src)
-    flags = STREAM_ADD_INDEX if add_index else 0
-    cap = _lib.lib().mlz_stream_bound(a.size, block_size, flags)
-    if cap < 0:
-        _raise(cap, ctx)
-    out = np.empty(cap, dtype=np.uint8)
-    r = _lib.lib().mlz_stream_encode(ctx.handle, level, block_size, flags, _ptr(a), a.size, out.ctypes.data, out.size)
-    if r < 0:
-        _raise(r, ctx)
-    return out[:r].tobytes()
+    out = np.empty(stream_bound(a.size, block_size, add_index), dtype=np.uint8)
+    return out[:ctx._call("mlz_stream_encode", level, block_size, _flags(add_index=add_index), _ptr(a), a.size, out.ctypes.data, out.size)].tobytes()
 
 
 def stream_decode(src, ignore_crc=False, ctx=None):
@@ -780,7 +709,4 @@ def stream_decode(src, ignore_crc=False, ctx=None):
     if n < 0:   # a framing error: the chunks in front of it are decoded first, and their first error wins (stream order)
         n = _lib.lib().mlz_stream_decoded_prefix_len(_ptr(a), a.size)
     out = np.empty(max(n, 1), dtype=np.uint8)
-    r = _lib.lib().mlz_stream_decode(ctx.handle, STREAM_IGNORE_CRC if ignore_crc else 0, _ptr(a), a.size, out.ctypes.data, n)
-    if r < 0:
-        _raise(r, ctx)
-    return out[:r].tobytes()
+    return out[:ctx._call("mlz_stream_decode", _flags(ignore_crc=ignore_crc), _ptr(a), a.size, out.ctypes.data, n)].tobytes()

@@ -12,6 +12,7 @@ import torch
 import torch.distributed as dist
 
 from . import stream as S
+from .device import HipTensorCodec, DeviceStream  # noqa: F401  (the tensor layer: its names resolve here as before)
 
 
 def owner(block_index, world):
@@ -102,354 +103,6 @@ def range_of(rank, world, n_blocks):
     per, extra = divmod(n_blocks, world)
     b0 = rank * per + min(rank, extra)
     return b0, b0 + per + (1 if rank < extra else 0)
-
-
-class HipTensorCodec:
-    """CUDA tensors through the C ABI's device-resident batch calls (the product path)."""
-
-    def __init__(self, ctx):
-        self.ctx = ctx
-
-    def encode(self, src, block_lens, level):
-        from ._lib import BlockDesc
-        n = len(block_lens)
-        stride = (max(block_lens + [0]) + 2 + 255) & ~255
-        dev = src.device
-        enc = torch.empty(max(n * stride, 1), dtype=torch.uint8, device=dev)
-        lens = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
-        crc32 = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-        if n:
-            offs = np.concatenate([[0], np.cumsum(block_lens)[:-1]]).tolist()
-            desc = (BlockDesc * n)(*[BlockDesc(int(offs[i]), int(block_lens[i]), i * stride, stride) for i in range(n)])
-            st = torch.cuda.current_stream(dev).cuda_stream
-            self.ctx.encode_batch_device(st, level, src.data_ptr(), enc.data_ptr(), desc, lens.data_ptr())
-            self.ctx.crc_batch_device(st, src.data_ptr(), desc, crc32.data_ptr())
-        return enc, stride, lens[:n], (crc32[:n].to(torch.int64) & 0xFFFFFFFF)
-
-    def decode(self, enc, blocks, out):
-        """blocks: [(src_off, src_len, dst_off, dst_len)] — whole blocks `00 uvarint(N) tokens` / `00 00 raw` inside `enc`, decoded
-        to out[dst_off : dst_off + dst_len].  -> int64 tensor on the device: the decoded length of each block or -MLZ_ERR_*."""
-        from ._lib import BlockDesc
-        n = len(blocks)
-        lens = torch.zeros(max(n, 1), dtype=torch.int64, device=enc.device)
-        if n:
-            desc = (BlockDesc * n)(*[BlockDesc(int(a), int(b), int(c), int(d)) for a, b, c, d in blocks])
-            st = torch.cuda.current_stream(enc.device).cuda_stream
-            self.ctx.decode_batch_device(st, enc.data_ptr(), out.data_ptr(), desc, lens.data_ptr())
-        return lens[:n]
-
-    def crcs(self, base, spans):
-        """Masked CRC32C (minlz.go:133-140) of base[off : off + len] for each (off, len) -> int64 tensor on the device."""
-        from ._lib import BlockDesc
-        n = len(spans)
-        crc32 = torch.zeros(max(n, 1), dtype=torch.int32, device=base.device)
-        if n:
-            desc = (BlockDesc * n)(*[BlockDesc(int(o), int(l), 0, 0) for o, l in spans])
-            st = torch.cuda.current_stream(base.device).cuda_stream
-            self.ctx.crc_batch_device(st, base.data_ptr(), desc, crc32.data_ptr())
-        return crc32[:n].to(torch.int64) & 0xFFFFFFFF
-
-    def decode_stream(self, t, ignore_crc=False):
-        """A whole .mz stream that lies on the device (uint8 tensor) -> its decoded bytes, a new uint8 tensor on the same device.  The chunks
-        are found on the device (mlz_stream_decoded_len_device sizes the output) and decoded where they lie (mlz_stream_decode_device): no
-        payload visits the host.  Raises the Reader's first error in stream order, like api.stream_decode."""
-        if t.dtype != torch.uint8 or not t.is_cuda:
-            raise ValueError("decode_stream: a uint8 tensor on the device")
-        t = t.contiguous()
-        st = torch.cuda.current_stream(t.device).cuda_stream
-        n, prefix = self.ctx.stream_decoded_len_device(t.data_ptr(), t.numel(), stream=st)
-        cap = n if n >= 0 else prefix   # a framing error: the chunks in front of it are decoded and checked first
-        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=t.device)
-        r = self.ctx.stream_decode_device(t.data_ptr(), t.numel(), out.data_ptr(), cap, ignore_crc=ignore_crc, stream=st)
-        return out[:r]
-
-    @staticmethod
-    def _raise_stream(what, i, code):
-        """The error of stream i of a batch: the class of its code, the index in the message and in .index."""
-        from . import api
-        e = api._ERRS.get(-code, api.MinLZError)("%s: stream %d of the batch: minlz error %d" % (what, i, -code))
-        e.code, e.index = -code, i
-        raise e
-
-    def decode_streams(self, t, spans, ignore_crc=False):
-        """Many .mz streams that lie in one uint8 tensor on the device, stream i at t[off_i : off_i + len_i] for spans[i] = (off_i, len_i) ->
-        (out, starts): their decoded bytes packed into one new uint8 tensor on the same device, and the n + 1 places where they start in it
-        (a list of ints; the last is out's size).  One batch walk sizes the output (mlz_stream_decoded_len_batch_device), one batch call
-        decodes (mlz_stream_decode_batch_device).  Raises the first failing stream's error, which names its index (.index)."""
-        if t.dtype != torch.uint8 or not t.is_cuda:
-            raise ValueError("decode_streams: a uint8 tensor on the device")
-        t = t.contiguous()
-        spans = [(int(o), int(n)) for o, n in spans]
-        for o, n in spans:
-            if o < 0 or n < 0 or o + n > t.numel():
-                raise ValueError("decode_streams: a span leaves the tensor")
-        if not spans:
-            return torch.empty(0, dtype=torch.uint8, device=t.device), [0]
-        st = torch.cuda.current_stream(t.device).cuda_stream
-        lens = self.ctx.stream_decoded_len_batch_device(t.data_ptr(), spans, stream=st)
-        starts = [0]
-        for r, prefix in lens:   # a framing error: the chunks in front of it are decoded and checked first
-            starts.append(starts[-1] + (r if r >= 0 else prefix))
-        out = torch.empty(max(starts[-1], 1), dtype=torch.uint8, device=t.device)
-        descs = [(o, n, starts[i], starts[i + 1] - starts[i]) for i, (o, n) in enumerate(spans)]
-        res = self.ctx.stream_decode_batch_device(t.data_ptr(), out.data_ptr(), descs, ignore_crc=ignore_crc, stream=st)
-        for i, r in enumerate(res):
-            if r < 0:
-                self._raise_stream("decode_streams", i, r)
-        return out[:starts[-1]], starts
-
-    def encode_streams(self, t, spans, level, block_size=1 << 20, add_index=False):
-        """Every input t[off_i : off_i + len_i] (a uint8 tensor on the device, spans[i] = (off_i, len_i)) as a .mz stream of its own ->
-        (out, stream_spans): one new uint8 tensor on the same device and where each stream lies in it, [(off, len)] (with room between
-        them: every stream is written at the place its bound reserves).  One call (mlz_stream_encode_batch_device); the bytes are
-        api.stream_encode's.  Raises the first failing stream's error, which names its index (.index)."""
-        from . import _lib
-        if t.dtype != torch.uint8 or not t.is_cuda:
-            raise ValueError("encode_streams: a uint8 tensor on the device")
-        t = t.contiguous()
-        spans = [(int(o), int(n)) for o, n in spans]
-        flags = 1 if add_index else 0
-        descs, at = [], 0
-        for o, n in spans:
-            if o < 0 or n < 0 or o + n > t.numel():
-                raise ValueError("encode_streams: a span leaves the tensor")
-            cap = int(_lib.lib().mlz_stream_bound(n, block_size, flags))
-            if cap < 0:
-                raise ValueError("encode_streams: block size %d" % block_size)
-            descs.append((o, n, at, cap))
-            at += cap
-        out = torch.empty(max(at, 1), dtype=torch.uint8, device=t.device)
-        if not spans:
-            return out[:0], []
-        st = torch.cuda.current_stream(t.device).cuda_stream
-        res = self.ctx.stream_encode_batch_device(level, block_size, add_index, t.data_ptr(), out.data_ptr(), descs, stream=st)
-        for i, r in enumerate(res):
-            if r < 0:
-                self._raise_stream("encode_streams", i, r)
-        return out, [(d[2], r) for d, r in zip(descs, res)]
-
-    def open_stream(self, t):
-        """A .mz stream that lies on the device (uint8 tensor) opened for range reads -> DeviceStream (ReadAt, read_ranges).  The chunk walk
-        runs once, here; a framing error raises."""
-        if t.dtype != torch.uint8 or not t.is_cuda:
-            raise ValueError("open_stream: a uint8 tensor on the device")
-        return DeviceStream(self.ctx, t.contiguous())
-
-
-class DeviceStream:
-    """A .mz stream on the device opened for random access (HipTensorCodec.open_stream): ReadSeeker.ReadAt (reader.go:1401-1487) with the
-    device walk's chunk table in the place of the seek index.  Keeps the stream's tensor alive."""
-
-    def __init__(self, ctx, t):
-        self.t = t
-        st = torch.cuda.current_stream(t.device).cuda_stream
-        self.reader = ctx.stream_open_device(t.data_ptr(), t.numel(), stream=st)
-        self.size = self.reader.size
-        self.side = None   # the attached sidecar's tensor
-
-    def read_ranges(self, offsets, lengths, ignore_crc=False, return_starts=False):
-        """Decoded bytes [offsets[i], offsets[i] + lengths[i]) for every i, back to back in the order given -> one new uint8 tensor.
-        return_starts: -> (that tensor, the n + 1 places where the ranges start in it and its size: int64 on the stream's device).
-        Two CUDA tensors (int64 or uint64, contiguous, on the stream's device) take the device path (mlz_dev_reader_read_device): the ranges
-        stay in device memory and are planned by kernels; the one thing that visits the host is the scalar int(lengths.sum()), which sizes the
-        output.  Lists and numpy arrays (and tensors on the CPU) are planned on the host."""
-        if torch.is_tensor(offsets) and torch.is_tensor(lengths) and offsets.is_cuda and lengths.is_cuda:
-            return self._read_ranges_device(offsets, lengths, ignore_crc, return_starts)
-        if torch.is_tensor(offsets):
-            offsets = offsets.numpy()
-        if torch.is_tensor(lengths):
-            lengths = lengths.numpy()
-        r = np.empty((len(offsets), 3), dtype=np.uint64)
-        r[:, 0] = offsets
-        r[:, 1] = lengths
-        total = int(r[:, 1].sum())
-        r[:, 2] = np.cumsum(r[:, 1]) - r[:, 1]
-        out = torch.empty(max(total, 1), dtype=torch.uint8, device=self.t.device)
-        st = torch.cuda.current_stream(self.t.device).cuda_stream
-        got = self.reader.read(r, out.data_ptr(), total, ignore_crc=ignore_crc, stream=st)
-        if return_starts:
-            return out[:got], torch.from_numpy(np.concatenate([r[:, 2], [total]]).astype(np.int64)).to(self.t.device)
-        return out[:got]
-
-    def _read_ranges_device(self, offsets, lengths, ignore_crc, return_starts):
-        dev = self.t.device
-        for a in (offsets, lengths):
-            if a.dtype not in (torch.int64, torch.uint64) or a.dim() != 1 or not a.is_contiguous() or a.device != dev:
-                raise ValueError("read_ranges: device ranges are contiguous 1-d int64 or uint64 tensors on the stream's device")
-        n = offsets.numel()
-        if lengths.numel() != n:
-            raise ValueError("read_ranges: as many lengths as offsets")
-        # (a length that is negative as int64 is beyond every stream: the call finds it whatever this sum comes to)
-        total = int(lengths.view(torch.int64).sum()) if n else 0
-        if total < 0 or total > n * self.size:
-            total = 0
-        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-        starts = torch.zeros(n + 1, dtype=torch.int64, device=dev) if return_starts else None
-        st = torch.cuda.current_stream(dev).cuda_stream
-        got = self.reader.read_device(offsets.data_ptr() if n else None, lengths.data_ptr() if n else None, n, out.data_ptr(), total,
-                                      d_starts=starts.data_ptr() if return_starts and n else None, ignore_crc=ignore_crc, stream=st)
-        return (out[:got], starts) if return_starts else out[:got]
-
-    def search(self, pattern, max_results, ignore_crc=False, no_tables=False):
-        """Where `pattern` (1 .. 256 bytes) occurs in the decoded stream -> (the smallest min(total, max_results) positions, ascending: an
-        int64 tensor on the stream's device; the total).  Only the blocks whose search tables (types 1 to 4) admit the pattern are decoded."""
-        dev = self.t.device
-        out = torch.empty(max(max_results, 1), dtype=torch.int64, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        total, _ = self.reader.search(pattern, out.data_ptr() if max_results else None, max_results, ignore_crc=ignore_crc, no_tables=no_tables, stream=st)
-        return out[:min(total, max_results)], total
-
-    def search_many(self, patterns, max_results, ignore_crc=False, no_tables=False):
-        """Where each of `patterns` (a sequence of up to 4096 bytes objects of 1 .. 256 bytes) occurs in the decoded stream, in one pass over
-        the blocks that any pattern's search tables admit -> (positions int64, which int32, counts int64, total): the smallest
-        min(total, max_results) pairs (position, pattern index) in ascending order, every pattern's own number of occurrences and the
-        number of all pairs; tensors on the stream's device."""
-        dev = self.t.device
-        pats = list(patterns)
-        pos = torch.empty(max(max_results, 1), dtype=torch.int64, device=dev)
-        which = torch.empty(max(max_results, 1), dtype=torch.int32, device=dev)
-        counts = torch.zeros(max(len(pats), 1), dtype=torch.int64, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        total, _ = self.reader.search_many(pats, counts.data_ptr(), pos.data_ptr() if max_results else None, which.data_ptr() if max_results else None, max_results,
-                                           ignore_crc=ignore_crc, no_tables=no_tables, stream=st)
-        k = min(total, max_results)
-        return pos[:k], which[:k], counts[:len(pats)], total
-
-    def search_records(self, pattern, delimiter=b"\n", max_records=1024, max_bytes=1 << 20, max_reach=0, ignore_crc=False, no_tables=False):
-        """The records (lines, for the default delimiter) of the decoded stream that hold `pattern`, each once, in stream order ->
-        (total_records, data, rec_off, rec_start, flags, totals): the first k records' bytes back to back (uint8), where each starts in the
-        decoded stream (int64, k values) and in `data` (int64, k + 1 values: the last is data's size), its flags (uint8: 1 = cut left,
-        2 = cut right — records longer than max_reach, 0 = 65536) — tensors on the stream's device, trimmed to what was written: k is
-        the most records that max_records and max_bytes hold whole — and totals = (records, bytes of all records, occurrences, flagged
-        records).  max_records = max_bytes = 0 counts."""
-        dev = self.t.device
-        data = torch.empty(max(max_bytes, 1), dtype=torch.uint8, device=dev)
-        rec_off = torch.empty(max(max_records, 1), dtype=torch.int64, device=dev)
-        rec_start = torch.zeros(max_records + 1, dtype=torch.int64, device=dev)
-        flags = torch.empty(max(max_records, 1), dtype=torch.uint8, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        total, totals, _ = self.reader.search_records(pattern, delimiter, data.data_ptr() if max_bytes else None, max_bytes, rec_off.data_ptr() if max_records else None,
-                                                      rec_start.data_ptr(), flags.data_ptr() if max_records else None, max_records, max_reach=max_reach,
-                                                      ignore_crc=ignore_crc, no_tables=no_tables, stream=st)
-        k = int((rec_start[1:] != 0).sum())   # (no record is empty: the starts behind the first are positive as far as they were written)
-        return total, data[:int(rec_start[k])], rec_off[:k], rec_start[:k + 1], flags[:k], totals
-
-    def index_records(self, delimiter=b"\n", ignore_crc=False):
-        """Builds the record index of the decoded stream for the one-byte `delimiter` (one decode of the stream; 8 bytes per delimiter
-        stay on the device until close() or another delimiter) -> the number of records N.  read_records, line_numbers and
-        read_record_range need it."""
-        st = torch.cuda.current_stream(self.t.device).cuda_stream
-        return self.reader.index_records(delimiter, ignore_crc=ignore_crc, stream=st)[0]
-
-    def _items(self, a, what):
-        if not torch.is_tensor(a) or a.dtype not in (torch.int64, torch.uint64) or a.dim() != 1 or not a.is_contiguous() or a.device != self.t.device:
-            raise ValueError(what + ": a contiguous 1-d int64 or uint64 tensor on the stream's device")
-        return a
-
-    def read_records(self, idx, ignore_crc=False):
-        """The records with the numbers `idx` (int64 or uint64 tensor on the stream's device; any order, repeats allowed), back to back in
-        the order given -> (a new uint8 tensor, the n + 1 places where the records start in it and its size: int64).  The one thing that
-        visits the host is the records' total size, which sizes the output."""
-        idx = self._items(idx, "read_records")
-        dev, n = self.t.device, idx.numel()
-        starts = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        if n == 0:
-            self.reader.record_count()   # (without an index this raises, as every call on it does)
-            return torch.empty(0, dtype=torch.uint8, device=dev), starts
-        st = torch.cuda.current_stream(dev).cuda_stream
-        spans = torch.empty(2 * n, dtype=torch.int64, device=dev)
-        total = self.reader.record_spans(idx.data_ptr(), n, spans.data_ptr(), spans[n:].data_ptr(), stream=st)
-        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-        got = self.reader.read_records(idx.data_ptr(), n, out.data_ptr(), total, d_starts=starts.data_ptr(), ignore_crc=ignore_crc, stream=st)
-        return out[:got], starts
-
-    def line_numbers(self, positions):
-        """The record number (0-based) of every position of the decoded stream in `positions` (int64 or uint64 tensor on the stream's
-        device) -> an int64 tensor; -1 for a position at or beyond the size.  With search_records' rec_off: the line numbers of the
-        matching lines."""
-        positions = self._items(positions, "line_numbers")
-        n = positions.numel()
-        out = torch.empty(n, dtype=torch.int64, device=self.t.device)
-        st = torch.cuda.current_stream(self.t.device).cuda_stream
-        if n == 0:
-            self.reader.record_count()
-        else:
-            self.reader.record_numbers(positions.data_ptr(), n, out.data_ptr(), stream=st)
-        return out
-
-    def grep(self, patterns, invert=False, before=0, after=0, max_records=1 << 20, count_only=False, ignore_crc=False, no_tables=False):
-        """grep over the decoded stream's lines: the records that hold one of `patterns` (a sequence of up to 4096 bytes objects of
-        1 .. 256 bytes without the delimiter; a single bytes object is one pattern), with invert those that hold none, and `before` /
-        `after` context records around each, every record once, in stream order.  Builds the record index for b"\n" when the stream has
-        none (index_records chooses another delimiter).
-        -> (R, numbers, kinds, data, starts): the number of such records; the smallest min(R, max_records) record numbers (int64); 1 for a
-        selected record and 0 for one that is context only (uint8); those records' bytes back to back (uint8) and the k + 1 places where
-        they start in it and its size (int64) — tensors on the stream's device.
-        count_only (grep -c): -> (R, the selected records) and nothing is written or read."""
-        from . import api
-        dev = self.t.device
-        pats = [patterns] if isinstance(patterns, (bytes, bytearray)) else list(patterns)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        try:
-            self.reader.record_count()
-        except api.MinLZError:   # (no index yet)
-            self.reader.index_records(b"\n", ignore_crc=ignore_crc, stream=st)
-        kw = dict(invert=invert, before=before, after=after, ignore_crc=ignore_crc, no_tables=no_tables, stream=st)
-        if count_only:
-            _, totals, _ = self.reader.grep_records(pats, None, None, 0, **kw)
-            return totals[0], totals[1]
-        cap = min(max_records, self.reader.record_count())
-        numbers = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
-        kinds = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
-        R, totals, _ = self.reader.grep_records(pats, numbers.data_ptr() if cap else None, kinds.data_ptr() if cap else None, cap, **kw)
-        k = min(R, cap)
-        starts = torch.zeros(k + 1, dtype=torch.int64, device=dev)
-        data = torch.empty(max(totals[2], 1), dtype=torch.uint8, device=dev)
-        got = self.reader.read_records(numbers.data_ptr(), k, data.data_ptr(), totals[2], d_starts=starts.data_ptr(), ignore_crc=ignore_crc, stream=st) if k else 0
-        return R, numbers[:k], kinds[:k], data[:got], starts
-
-    def read_record_range(self, first, count, ignore_crc=False):
-        """Records first .. first + count - 1 as they lie in the decoded stream, the delimiters between them included -> a new uint8 tensor."""
-        off, ln = self.reader.record_range(first, count)
-        return self.read_ranges([off], [ln], ignore_crc)
-
-    def build_sidecar(self, cfgs, ignore_crc=False):
-        """A sidecar search index of this stream for 1 .. 4 configurations (api.search_config): search tables for every block, whoever
-        wrote the stream, in a separate .mz stream -> a new uint8 tensor on the stream's device."""
-        dev = self.t.device
-        cap = self.reader.sidecar_bound(cfgs)
-        out = torch.empty(cap, dtype=torch.uint8, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        got = self.reader.build_sidecar(cfgs, out.data_ptr(), cap, ignore_crc=ignore_crc, stream=st)
-        return out[:got].clone()
-
-    def attach_sidecar(self, side, ignore_crc=False):
-        """search and search_many use the tables of the sidecar `side` (a uint8 tensor on the stream's device, as build_sidecar returns
-        it) from now on; None detaches.  The stream keeps the tensor alive."""
-        if side is None:
-            self.reader.detach_sidecar()
-            self.side = None
-            return
-        if side.dtype != torch.uint8 or side.dim() != 1 or not side.is_contiguous() or side.device != self.t.device:
-            raise ValueError("attach_sidecar: a contiguous 1-d uint8 tensor on the stream's device")
-        st = torch.cuda.current_stream(self.t.device).cuda_stream
-        self.reader.attach_sidecar(side.data_ptr(), side.numel(), ignore_crc=ignore_crc, stream=st)
-        self.side = side
-
-    def ReadAt(self, n, offset, ignore_crc=False):
-        """Up to n decoded bytes from `offset`, clamped at the end of the stream -> a new uint8 tensor."""
-        if n < 0 or offset < 0 or offset > self.size:
-            raise ValueError("ReadAt: offset outside the stream")
-        return self.read_ranges([offset], [min(n, self.size - offset)], ignore_crc)
-
-    def close(self):
-        self.reader.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 def frame_run(codec, src, block_lens, level):

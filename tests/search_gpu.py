@@ -1,16 +1,27 @@
-"""What the GPU tests of the device-resident Writer's search tables and of the pattern search share (tests/test_gpu_stream_search*.py,
-tests/test_gpu_stream_writer_cuts.py): inputs on the device, the Writer call with a guarded destination, the search call with guarded
-results."""
+"""What the GPU tests of the device-resident Writer's search tables, of the pattern search and of the record calls share
+(tests/test_gpu_stream_*.py, tests/test_gpu_sidecar.py): inputs on the device, the Writer call with a guarded destination, an opened
+stream, the search call with guarded results."""
 import numpy as np
 import torch
 
-from minlz_amd import synth
+from minlz_amd import api, synth
 
 SENT = 0x5A5A5A5A5A5A5A5A
 
 
+def dev_u8(b):
+    """bytes -> a uint8 tensor on the device."""
+    return torch.from_numpy(np.frombuffer(b, np.uint8).copy()).cuda() if len(b) else torch.empty(0, dtype=torch.uint8, device="cuda")
+
+
+def dev_u64(values):
+    """uint64 values -> an int64 tensor on the device with the same bits."""
+    a = np.asarray(values, dtype=np.uint64).view(np.int64)
+    return torch.from_numpy(a.copy()).cuda() if a.size else torch.empty(0, dtype=torch.int64, device="cuda")
+
+
 def on_device(parts):
-    return [torch.from_numpy(np.frombuffer(p, np.uint8).copy()).cuda() if len(p) else torch.empty(0, dtype=torch.uint8, device="cuda") for p in parts]
+    return [dev_u8(p) for p in parts]
 
 
 def gather_into(ctx, parts, cap, level, bs, add_index, **kw):
@@ -25,6 +36,14 @@ def gather_into(ctx, parts, cap, level, bs, add_index, **kw):
     return o[:got].tobytes()
 
 
+def gather(ctx, parts, bs, add_index=False, level=1, cap=None, **tables):
+    """The device-resident Writer's stream of `parts` (bytes objects, one range each), without tables or with those the search_* keywords
+    of Context.stream_encode_gather_device ask for.  The room is what api.stream_bound says (or `cap`), and nothing is written behind it."""
+    if cap is None:
+        cap = api.stream_bound(sum(len(p) for p in parts), bs, add_index, **tables)
+    return gather_into(ctx, parts, cap, level, bs, add_index, **tables)
+
+
 def first_difference(a, b):
     return next((i for i in range(min(len(a), len(b))) if a[i] != b[i]), min(len(a), len(b)))
 
@@ -36,22 +55,25 @@ def data_for(kind, bs, nblk, tail, seed=4, random_block=1):
     return bytes(d)
 
 
-class Searcher:
-    def __init__(self, ctx, stream):
-        self.ctx = ctx
-        self.t = torch.from_numpy(np.frombuffer(stream, np.uint8).copy()).cuda()
-        self.rd = ctx.stream_open_device(self.t.data_ptr(), len(stream))
+class Opened:
+    """A stream's bytes on the device and the reader opened on them."""
 
-    def __call__(self, pattern, cap, **kw):
+    def __init__(self, ctx, stream):
+        self.ctx, self.t = ctx, dev_u8(stream)
+        self.rd = ctx.stream_open_device(self.t.data_ptr() if len(stream) else None, len(stream))
+
+    def close(self):
+        self.rd.close()
+
+
+class Searcher(Opened):
+    def __call__(self, pattern, cap, null=False, **kw):
         """-> (total, positions, stats); checks that nothing beyond min(total, cap) was written."""
         out = torch.full((cap + 8,), SENT, dtype=torch.int64, device="cuda")
-        total, stats = self.rd.search(pattern, out.data_ptr(), cap, **kw)
+        total, stats = self.rd.search(pattern, None if null else out.data_ptr(), cap, **kw)
         torch.cuda.synchronize()
         o = out.cpu().numpy()
         k = min(total, cap)
         assert (o[k:] == SENT).all(), "written beyond the results"
         assert self.ctx.search_plan() == stats[1:]
         return total, o[:k].tolist(), stats
-
-    def close(self):
-        self.rd.close()

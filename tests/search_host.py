@@ -1,5 +1,5 @@
-"""What the host tests of the search share (tests/test_stream_search*_host.py, tests/test_sidecar_host.py): the build of a tools/*_check.cpp
-with g++ and the run of its case file, and the records and result lines of tools/stream_search_check.cpp (the record kinds are the
+"""What the host tests share (tests/test_stream_*_host.py, tests/test_sidecar_host.py): the build of a tools/*_check.cpp with g++, plain
+and sanitized, and the run of its case file, and the records and result lines of tools/stream_search_check.cpp (the record kinds are the
 program's)."""
 import os
 import struct
@@ -12,8 +12,8 @@ LINK_ERROR = {}          # source -> the end of g++'s messages where a sanitized
 
 
 def build_checker(tmp_path_factory, source, sanitized=False, flags=()):
-    """Compiles tools/<source> -> run(records) -> (the program's stdout lines, its stderr); an exit status other than 0 fails with the
-    stderr.  sanitized: the same stand-alone program under AddressSanitizer and UBSan (nothing is preloaded), or None where this g++ does
+    """Compiles tools/<source> -> run(records, argv=()) -> (the program's stdout lines, its stderr): the program gets argv and then the
+    path of a file that holds the records (bytes objects) back to back; an exit status other than 0 fails with the stderr.  sanitized: the same stand-alone program under AddressSanitizer and UBSan (nothing is preloaded), or None where this g++ does
     not link their runtimes (LINK_ERROR[source] then says why)."""
     exe = str(tmp_path_factory.mktemp(source.partition(".")[0] + ("_san" if sanitized else "")) / "check")
     opt = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitized else ["-O2", "-std=c++17"]
@@ -23,16 +23,30 @@ def build_checker(tmp_path_factory, source, sanitized=False, flags=()):
         return None
     assert r.returncode == 0, r.stderr[-2000:]
 
-    def run(records):
+    def run(records, argv=()):
         path = os.path.join(os.path.dirname(exe), "cases.bin")
         with open(path, "wb") as f:
             for rec in records:
                 f.write(rec)
-        r = subprocess.run([exe, path], capture_output=True, text=True, timeout=900)
+        r = subprocess.run([exe] + list(argv) + [path], capture_output=True, text=True, timeout=900)
         os.unlink(path)
-        assert r.returncode == 0, r.stderr[-2000:]
+        assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
         return r.stdout.splitlines(), r.stderr
     return run
+
+
+def checkers(tmp_path_factory, source):
+    """The plain build, and the same program under AddressSanitizer and UBSan where this g++ links their runtimes (else None)."""
+    return build_checker(tmp_path_factory, source), build_checker(tmp_path_factory, source, sanitized=True)
+
+
+def both(checkers, records, argv=()):
+    """The plain program's lines; the sanitized build runs the same cases and must print the same."""
+    plain, san = checkers
+    lines = plain(records, argv)[0]
+    if san is not None:
+        assert san(records, argv)[0] == lines
+    return lines
 
 
 # ---- tools/stream_search_check.cpp ----

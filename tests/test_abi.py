@@ -18,10 +18,19 @@ def lib():
     return _lib.lib()
 
 
+def header_text():
+    """include/minlz_hip.h without its comments."""
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "minlz_hip.h")).read(), flags=re.S)
+
+
 def header_symbols():
-    txt = open(os.path.join(ROOT, "include", "minlz_hip.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(mlz_[a-z_0-9]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"\b(mlz_[a-z_0-9]+)\s*\(", header_text())))
+
+
+def header_defines():
+    """Every #define of the header with a plain integer value -> {name: value}."""
+    found = re.findall(r"^#define (MLZ_\w+) \(?(-?\d+)u?\)?\s*$", header_text(), flags=re.M)
+    return {name: int(value) for name, value in found}
 
 
 def test_header_symbols_exported(lib):
@@ -30,6 +39,50 @@ def test_header_symbols_exported(lib):
     for s in syms:
         assert hasattr(lib, s), "libminlz_hip.so does not export %s" % s
     assert sorted(_lib.SYMBOLS) == syms
+
+
+def test_abi_table_has_the_arity_of_every_prototype():
+    """Every prototype `mlz_x(...);` of the header, in its order, has an entry in _lib.ABI with as many argument types as it has parameters
+    (none for `void`), and the table holds nothing else."""
+    protos = re.findall(r"\b(mlz_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", header_text())
+    assert len(protos) == 58 and [name for name, _ in protos] == list(_lib.ABI)
+    for name, params in protos:
+        params = params.strip()
+        assert len(_lib.ABI[name][1]) == (0 if params == "void" else params.count(",") + 1), name
+
+
+LEVELS = {"MLZ_LEVEL_SUPERFAST": "LevelSuperFast", "MLZ_LEVEL_UNCOMPRESSED": "LevelUncompressed", "MLZ_LEVEL_FASTEST": "LevelFastest",
+          "MLZ_LEVEL_BALANCED": "LevelBalanced"}
+
+
+def test_constants_are_the_headers():
+    """Every MLZ_LEVEL_ / ERR_ / STREAM_ / SEARCH_ / GREP_ / OPT_ define with a plain integer value, and MLZ_TIMER_ENABLE, has its name in api with
+    that value; api has no OPT_ or flag name without a define."""
+    from minlz_amd import api
+    want = {}
+    for name, value in header_defines().items():
+        if name in LEVELS:
+            want[LEVELS[name]] = value
+        elif name == "MLZ_TIMER_ENABLE":
+            want["OPT_TIMING"] = value
+        elif re.match(r"MLZ_(ERR|STREAM|SEARCH|GREP|OPT)_", name):
+            want[name[4:]] = value
+    assert len(want) == 4 + 8 + 3 + 2 + 1 + 20 + 1
+    for name, value in want.items():
+        assert getattr(api, name) == value, name
+    have = {n for n in dir(api) if re.match(r"(ERR|STREAM|SEARCH|GREP|OPT)_", n) or n.startswith("Level")}
+    assert have == set(want)
+    counters = sorted(getattr(api, n) for n in dir(api) if n.startswith("COUNTER_"))
+    assert counters == list(range(13))
+
+
+def test_struct_sizes():
+    """sizeof of the structures as the header's fields give it (no padding anywhere: every field lies at a multiple of its size)."""
+    assert C.sizeof(_lib.BlockDesc) == 4 * 8          # mlz_block_desc: four uint64
+    assert C.sizeof(_lib.Range) == 3 * 8              # mlz_range: three uint64
+    assert C.sizeof(_lib.SearchTables) == 4 + 32      # mlz_search_tables: four bytes and prefix[32]
+    assert C.sizeof(_lib.SearchConfig) == 4 + 2 + 2 + 256   # mlz_search_config: four bytes, a uint16, reserved2[2], prefix[256]
+    assert C.sizeof(_lib.SearchLongPrefix) == 2 + 2 + 4 + 256
 
 
 def test_max_encoded_len(lib):

@@ -155,17 +155,17 @@ def test_stream_prefix_len_is_host_only():
     cs = [c for c in CM.chunks(s) if c.type in (0x01, 0x02, 0x03)]
     n = [O.decoded_len(b"\x00" + s[c.off + 8:c.off + 4 + c.clen]) if c.type == 0x02 else c.clen - 4 for c in cs]
 
-    def both(b):
+    def host_lens(b):
         a = np.frombuffer(b, dtype=np.uint8)
         return L.mlz_stream_decoded_len(a.ctypes.data, a.size), L.mlz_stream_decoded_prefix_len(a.ctypes.data, a.size)
 
-    assert both(s) == (len(d), len(d))
-    assert both(s[:cs[-1].off + 7]) == (-O.ERR_CORRUPT, sum(n[:-1]))
-    assert both(s[:cs[2].off]) == (-O.ERR_CORRUPT, sum(n[:2]))
+    assert host_lens(s) == (len(d), len(d))
+    assert host_lens(s[:cs[-1].off + 7]) == (-O.ERR_CORRUPT, sum(n[:-1]))
+    assert host_lens(s[:cs[2].off]) == (-O.ERR_CORRUPT, sum(n[:2]))
     b = bytearray(s); b[cs[1].off] = 0x00
-    assert both(bytes(b)) == (-O.ERR_UNSUPPORTED, n[0])
-    assert both(s[:5]) == (-O.ERR_CORRUPT, 0)
+    assert host_lens(bytes(b)) == (-O.ERR_UNSUPPORTED, n[0])
+    assert host_lens(s[:5]) == (-O.ERR_CORRUPT, 0)
     # a stored chunk over the block size in a cut stream: ErrTooLarge, as the oracle says (the size is checked before the bytes are read)
     name, b = next(x for x in CM.stream_mutants(s) if x[0] == "uncompressed_too_large_cut")
     assert CM.stream_verdict(b, len(d))[0] == O.ERR_TOO_LARGE
-    assert both(b)[0] == -O.ERR_TOO_LARGE
+    assert host_lens(b)[0] == -O.ERR_TOO_LARGE

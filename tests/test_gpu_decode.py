@@ -254,7 +254,7 @@ def test_general_block_paths_agree(ctx):
             mutated.append(bytes(m))
     results = {}
     for algo in (0, 1):
-        ctx.set_option(8, algo)
+        ctx.set_option(mz.OPT_GENERAL_ALGO, algo)
         try:
             assert mz.decode_batch(encs, ctx) == want
             verdicts = []
@@ -265,7 +265,7 @@ def test_general_block_paths_agree(ctx):
                     verdicts.append(("err", type(ex).__name__))
             results[algo] = verdicts
         finally:
-            ctx.set_option(8, 0)
+            ctx.set_option(mz.OPT_GENERAL_ALGO, 0)
     assert results[0] == results[1]
     for m, v in zip(mutated, results[0]):
         try:
@@ -413,21 +413,21 @@ def test_general_block_barrier_is_bounded(ctx):
     ref = O.encode(d, 1)                      # reference-algorithm stream: a general block
     assert mz.Decode(ref, ctx) == d.tobytes()
     assert ctx.general_blocks() == 1          # it did take the general path
-    ctx.set_option(9, 1)
+    ctx.set_option(mz.OPT_GEN_SPIN, 1)
     try:
         with pytest.raises(mz.ErrHIP):
             mz.Decode(ref, ctx)
     finally:
-        ctx.set_option(9, 1 << 24)
+        ctx.set_option(mz.OPT_GEN_SPIN, 1 << 24)
     assert mz.Decode(ref, ctx) == d.tobytes()
     # a batch with one general and one conformant block: only the general one fails
     own = mz.Encode(d, 1, ctx)
-    ctx.set_option(9, 1)
+    ctx.set_option(mz.OPT_GEN_SPIN, 1)
     try:
         with pytest.raises(mz.ErrHIP):
             mz.decode_batch([own, ref], ctx)
     finally:
-        ctx.set_option(9, 1 << 24)
+        ctx.set_option(mz.OPT_GEN_SPIN, 1 << 24)
     assert mz.decode_batch([own, ref], ctx) == [d.tobytes(), d.tobytes()]
     # the Reader's entry point (minLZDecode contract: 0 ok, 1 corrupt, < 0 error): a device failure must come back as
     # < 0 — the shim's cue to run minLZDecodeGo — and never as 1, which the Reader would report as ErrCorrupt for a
@@ -436,12 +436,12 @@ def test_general_block_barrier_is_bounded(ctx):
     _, hl = uvarint(ref, 1)
     body = ref[1 + hl:]
     assert mz.decode_block(body, d.size, ctx) == (0, d.tobytes())
-    ctx.set_option(9, 1)
+    ctx.set_option(mz.OPT_GEN_SPIN, 1)
     try:
         with pytest.raises(mz.ErrHIP):
             mz.decode_block(body, d.size, ctx)
     finally:
-        ctx.set_option(9, 1 << 24)
+        ctx.set_option(mz.OPT_GEN_SPIN, 1 << 24)
     assert mz.decode_block(body, d.size, ctx) == (0, d.tobytes())
     assert mz.decode_block(body[:len(body) // 2], d.size, ctx)[0] == 1
 
@@ -480,7 +480,7 @@ def test_level0_tiles_by_the_parallel_kernel_or_by_the_exec_pass(ctx):
     # own streams of every level pattern and block class, damaged own streams (the damage lands in level-0 tiles as well), the reference's negative corpus.
     import zipfile, os
     other = mz.Context(0)
-    other.set_option(23, 0)
+    other.set_option(mz.OPT_LEVEL0_KERNEL, 0)
     try:
         rng = np.random.default_rng(17)
         blocks, want = [], []

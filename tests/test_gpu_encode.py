@@ -504,7 +504,7 @@ def test_fused_serializer_writes_the_same_bytes(level):
              synth.pattern("zeros", 2_000_001), synth.random_bytes(1 << 20, seed=2), synth.text_like(65_536 + 9, 10), synth.text_like(5, 11)]
     a, b_ = mz.Context(0), mz.Context(0)
     try:
-        b_.set_option(21, 0)
+        b_.set_option(mz.OPT_FUSED_SERIALIZER, 0)
         fused = mz.encode_batch([p.tobytes() for p in parts], level, a)
         apart = mz.encode_batch([p.tobytes() for p in parts], level, b_)
         assert fused == apart
@@ -523,7 +523,7 @@ def test_layout_inside_the_gather_kernel_writes_the_same_blocks(level):
              synth.text_like(32_768, 5), synth.text_like(32_769, 6), synth.pattern("zeros", 2_000_001), synth.text_like(5, 11), synth.random_bytes(40_000, seed=3)]
     a, b_ = mz.Context(0), mz.Context(0)
     try:
-        b_.set_option(24, 0)
+        b_.set_option(mz.OPT_FOLD_LAYOUT, 0)
         raw = [p.tobytes() for p in parts]
         fa, fb = mz.encode_batch(raw, level, a), mz.encode_batch(raw, level, b_)
         assert fa == fb

@@ -13,7 +13,7 @@ import pytest
 
 import minlz_amd as mz
 import oracle as O
-from minlz_amd import _lib, synth
+from minlz_amd import synth
 
 pytestmark = pytest.mark.gpu
 
@@ -60,7 +60,7 @@ def test_decode_beside_a_busy_queue():
             assert mz.encode_batch(data[:4], mz.LevelFastest, ctx) == own[:4]
             rounds += 1
         assert counts[0] > before, "the co-running load made no progress: the test did not test anything"
-        assert int(_lib.lib().mlz_get_counter(ctx.handle, 5)) == 0   # no call fell back to the tile chain
+        assert ctx.counter(mz.COUNTER_GENERAL_FALLBACKS) == 0   # no call fell back to the tile chain
     finally:
         stop.set()
         if th.is_alive():

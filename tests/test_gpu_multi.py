@@ -46,7 +46,7 @@ def test_init_devices_surface(ctx):
         k0, k1 = L.mlz_device_ctx(m.handle, 0), L.mlz_device_ctx(m.handle, 1)
         assert k0 and k1 and k0 != k1 and not L.mlz_device_ctx(m.handle, 2)
         assert L.mlz_device_ctx(ctx.handle, 0) == ctx.handle.value and not L.mlz_device_ctx(ctx.handle, 1)
-        m.set_option(17, 64)                       # an option reaches every device
+        m.set_option(mz.OPT_DEVICE_GROUP, 64)                       # an option reaches every device
         assert m.workspace_bytes() == (0, 0)       # counters sum over the devices
     finally:
         m.close()
@@ -171,7 +171,7 @@ def test_single_block_calls_take_the_devices_in_turn(multi):
     for (enc, dec), b in zip(out, blocks):
         assert dec == b and O.decode(enc) == b
     L = _lib.lib()
-    served = [int(L.mlz_get_counter(L.mlz_device_ctx(multi.handle, i), 1)) for i in range(multi.device_count())]
+    served = [int(L.mlz_get_counter(L.mlz_device_ctx(multi.handle, i), mz.COUNTER_COMBINE_REQUESTS)) for i in range(multi.device_count())]
     assert all(s > 0 for s in served) and sum(served) == multi.combine_stats()[1], served
     assert mz.crc(b"abcd", multi).to_bytes(4, "little").hex() == "6810e6b6"
 

@@ -14,7 +14,7 @@ from minlz_amd.api import search_config
 from tests import search_cases as SC
 from tests import search_model as SMod
 from tests import sidecar_model as SM
-from tests.search_gpu import SENT, data_for, first_difference, gather_into
+from tests.search_gpu import SENT, Opened, data_for, dev_u8, first_difference, gather_into
 
 pytestmark = pytest.mark.gpu
 
@@ -34,17 +34,12 @@ T2, T3, T4 = cfg(2, 6, b'":, '), cfg(3, 6, NON_ALNUM), cfg(4, 6, USER, 3)
 ALL_SETS = [[T1[1]], [T1[4]], [T1[6]], [T1[8]], [T2], [T3], [T4], [T1[6], T2, T3, T4]]
 
 
-def dev(b):
-    return torch.from_numpy(np.frombuffer(b, np.uint8).copy()).cuda()
-
-
-class Handle:
+class Handle(Opened):
     """A stream on the device, opened; builds go into a guarded destination."""
 
     def __init__(self, ctx, stream):
-        self.ctx, self.stream = ctx, stream
-        self.t = dev(stream)
-        self.rd = ctx.stream_open_device(self.t.data_ptr(), len(stream))
+        super().__init__(ctx, stream)
+        self.stream = stream
         self.keep = None
 
     def build(self, cfgs, cap=None, **kw):
@@ -59,7 +54,7 @@ class Handle:
         return o[:got].tobytes()
 
     def attach(self, side, **kw):
-        t = dev(side)
+        t = dev_u8(side)
         self.rd.attach_sidecar(t.data_ptr(), len(side), **kw)
         self.keep = t
 
@@ -83,13 +78,10 @@ class Handle:
         assert (pos.cpu().numpy()[k:] == SENT).all() and (counts.cpu().numpy()[len(pats):] == SENT).all()
         return total, list(zip(pos.cpu().numpy()[:k].tolist(), which.cpu().numpy()[:k].tolist())), counts.cpu().numpy()[:len(pats)].tolist(), stats
 
-    def close(self):
-        self.rd.close()
-
 
 def check_sidecar_is_a_stream(ctx, side):
     assert O.stream_decode(side, 0) == b""
-    t = dev(side)
+    t = dev_u8(side)
     assert ctx.stream_decoded_len_device(t.data_ptr(), len(side)) == (0, 0)
 
 
@@ -266,7 +258,7 @@ def test_search_through_a_sidecar(ctx, which):
 
 def test_device_stream_front_end(ctx):
     d, nd, at = SC.planted("json_like", BS, 16, 16, 3)
-    codec_stream = shard.DeviceStream(ctx, dev(O.stream_encode(d, 1, BS)))
+    codec_stream = shard.DeviceStream(ctx, dev_u8(O.stream_encode(d, 1, BS)))
     try:
         side = codec_stream.build_sidecar([T1[6][0], T4[0]])
         assert side.is_cuda and side.dtype == torch.uint8

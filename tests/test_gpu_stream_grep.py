@@ -15,7 +15,7 @@ from minlz_amd.api import search_config
 from tests import corrupt as CM
 from tests import grep_model as GM
 from tests import search_model as SMod
-from tests.search_gpu import SENT, gather_into
+from tests.search_gpu import SENT, Opened, dev_u64, gather
 
 pytestmark = pytest.mark.gpu
 
@@ -28,13 +28,6 @@ RARE = b"@zq-needle-77@"
 HOT = b"hot!"
 SHORT = b'":'          # shorter than M = 6: the tables cannot serve it
 CONTEXTS = [(0, 0), (1, 0), (0, 1), (3, 3), (None, None)]      # (before, after); None: N
-
-
-def gather(ctx, d, bs, **kw):
-    """The Writer's stream over `d` with the tables `kw` asks for (none: a stream without tables); room for the largest table per block."""
-    nblk = (len(d) + bs - 1) // bs
-    cap = _lib.lib().mlz_stream_bound(len(d), bs, 1) + (nblk + 2) * (12 + 260 + (1 << (SMod.table_bits(bs) - 3))) + 1024
-    return gather_into(ctx, [d], cap, 1, bs, True, **kw)
 
 
 def grep_case(bs, nblk):
@@ -68,18 +61,12 @@ def lds_fits(pats):
     return words * 4 <= 64 << 10
 
 
-def dev(values):
-    a = np.asarray(values, dtype=np.uint64).view(np.int64)
-    return torch.from_numpy(a.copy()).cuda() if a.size else torch.empty(0, dtype=torch.int64, device="cuda")
-
-
-class Grep:
+class Grep(Opened):
     """A stream on the device, its decoded bytes and an open handle with an index; check() compares a call whole with the model."""
 
     def __init__(self, ctx, stream, data, delim=NL, index=True, **kw):
-        self.ctx, self.data, self.stream, self.delim = ctx, bytes(data), bytes(stream), delim
-        self.t = torch.from_numpy(np.frombuffer(stream, np.uint8).copy()).cuda() if len(stream) else torch.empty(0, dtype=torch.uint8, device="cuda")
-        self.rd = ctx.stream_open_device(self.t.data_ptr() if len(stream) else None, len(stream))
+        super().__init__(ctx, stream)
+        self.data, self.stream, self.delim = bytes(data), bytes(stream), delim
         self.side = None
         self.models = {}
         if index:
@@ -155,9 +142,6 @@ class Grep:
         assert (no[r:] == SENT).all() and (kd[:r] == 1).all() and totals[:2] == (r, r), what
         return no[:r].tolist()
 
-    def close(self):
-        self.rd.close()
-
 
 def pattern_sets(d):
     """name -> patterns: one; two that hit the same records; duplicates; the hot one; one the tables cannot serve; 300 whose index does
@@ -181,7 +165,7 @@ def main(ctx, request):
     name = request.param
     bs, nblk = (4 << 10, 40) if name == "4K blocks" else (64 << 10, 6)
     d = grep_case(bs, nblk)
-    stream = gather(ctx, d, bs, **({} if name in ("no tables", "sidecar") else dict(search_match_len=6)))
+    stream = gather(ctx, [d], bs, True, **({} if name in ("no tables", "sidecar") else dict(search_match_len=6)))
     grid = SMod.data_grid(stream)
     assert grid[1][1] == 0x01 and len(grid) == nblk + 1                      # the random block: stored
     h = Grep(ctx, stream, d)
@@ -257,7 +241,7 @@ def test_written_bytes_are_what_read_records_needs(main):
     assert r > cap
     want, starts = GM.lines(h.data, NL, no[:cap].tolist())
     assert totals[2] == len(want)
-    d_no = dev(no[:cap])
+    d_no = dev_u64(no[:cap])
     dst = torch.full((totals[2] + 64,), 0x5A, dtype=torch.uint8, device="cuda")
     assert h.rd.read_records(d_no.data_ptr(), cap, dst.data_ptr(), totals[2]) == totals[2]
     torch.cuda.synchronize()
@@ -268,7 +252,7 @@ def test_written_bytes_are_what_read_records_needs(main):
 
 def test_every_record_empty(ctx):
     d = NL * 70000
-    h = Grep(ctx, gather(ctx, d, 64 << 10), d)
+    h = Grep(ctx, gather(ctx, [d], 64 << 10, True), d)
     try:
         assert h.N == 70000
         want, _ = h.check([b"x"], "70 000 empty records")
@@ -283,7 +267,7 @@ def test_every_record_empty(ctx):
 
 def test_one_record_and_the_empty_stream(ctx):
     d = b"one record with a needle and no delimiter"
-    h = Grep(ctx, gather(ctx, d, 64 << 10), d)
+    h = Grep(ctx, gather(ctx, [d], 64 << 10, True), d)
     try:
         assert h.N == 1
         for pats, inv, R in (([b"needle"], False, 1), ([b"needle"], True, 0), ([b"absent"], False, 0), ([b"absent"], True, 1), ([], True, 1)):
@@ -307,7 +291,7 @@ def test_argument_errors_write_nothing(ctx):
     bs = 64 << 10
     d = grep_case(bs, 6)
     L = _lib.lib()
-    h = Grep(ctx, gather(ctx, d, bs, search_match_len=6), d, index=False)
+    h = Grep(ctx, gather(ctx, [d], bs, True, search_match_len=6), d, index=False)
     try:
         r, no, kd, totals, stats = h.raw([RARE], 8)                                                 # a handle without an index
         assert r == -MLZ_ERR_ARG and (no == SENT).all() and (kd == KIND_SENT).all()
@@ -343,7 +327,7 @@ def test_argument_errors_write_nothing(ctx):
 def test_another_delimiter_replaces_the_index(ctx):
     bs = 64 << 10
     d = grep_case(bs, 6)
-    h = Grep(ctx, gather(ctx, d, bs, search_match_len=6), d)
+    h = Grep(ctx, gather(ctx, [d], bs, True, search_match_len=6), d)
     try:
         h.check([RARE], "by lines", before=1, after=1)
         h.N = h.rd.index_records(b",")[0]
@@ -362,7 +346,7 @@ def test_broken_chunks(ctx):
     prune goes unnoticed.  Under MLZ_STREAM_IGNORE_CRC the call follows search_many."""
     bs = 64 << 10
     d = grep_case(bs, 6)
-    s = gather(ctx, d, bs, search_match_len=6)
+    s = gather(ctx, [d], bs, True, search_match_len=6)
     cfg, B, tables = SMod.read_tables(s)
     sizes = [n for n, _ in SMod.data_grid(s)]
     plan = SMod.plan(tables, sizes, RARE, cfg, B)
@@ -399,7 +383,7 @@ def test_broken_chunks(ctx):
 def test_device_stream_grep(ctx):
     bs = 64 << 10
     d = grep_case(bs, 6)
-    t = torch.from_numpy(np.frombuffer(gather(ctx, d, bs, search_match_len=6), np.uint8).copy()).cuda()
+    t = torch.from_numpy(np.frombuffer(gather(ctx, [d], bs, True, search_match_len=6), np.uint8).copy()).cuda()
     with shard.HipTensorCodec(ctx).open_stream(t) as ds:
         for pats, kw in (([RARE], dict(before=2, after=1)), (RARE, {}), ([RARE, HOT], dict(invert=True, max_records=50)), ([HOT, SHORT], dict(after=1, max_records=7)), ([], {})):
             plist = [pats] if isinstance(pats, bytes) else pats

@@ -15,7 +15,7 @@ from tests import record_index_model as IM
 from tests import records_model as RM
 from tests import search_model as SMod
 from tests import stream_device_cases as SC
-from tests.search_gpu import SENT, gather_into
+from tests.search_gpu import SENT, Opened, dev_u64, gather
 
 pytestmark = pytest.mark.gpu
 
@@ -24,33 +24,20 @@ NL = b"\n"
 NONE = -1   # UINT64_MAX as the int64 the tensors hold
 
 
-def gather(ctx, parts, bs, M=None):
-    n = sum(len(p) for p in parts)
-    cap = _lib.lib().mlz_stream_bound(n, bs, 0 if M is None else 4 | (M << 8))
-    return gather_into(ctx, parts, cap, 1, bs, False, search_match_len=M)
-
-
 def lines(n, seed, kind="json_like"):
     return bytearray(getattr(synth, kind)(n, seed).tobytes())
-
-
-def dev(values):
-    """uint64 values -> an int64 tensor on the device with the same bits."""
-    a = np.asarray(values, dtype=np.uint64).view(np.int64)
-    return torch.from_numpy(a.copy()).cuda() if a.size else torch.empty(0, dtype=torch.int64, device="cuda")
 
 
 def guarded(n, extra=8):
     return torch.full((n + extra,), SENT, dtype=torch.int64, device="cuda")
 
 
-class Indexed:
+class Indexed(Opened):
     """A stream on the device, its decoded bytes and an open handle; the calls compare everything they return and write with the model."""
 
     def __init__(self, ctx, stream, data):
-        self.ctx, self.data, self.stream = ctx, bytes(data), bytes(stream)
-        self.t = torch.from_numpy(np.frombuffer(stream, np.uint8).copy()).cuda() if len(stream) else torch.empty(0, dtype=torch.uint8, device="cuda")
-        self.rd = ctx.stream_open_device(self.t.data_ptr() if len(stream) else None, len(stream))
+        super().__init__(ctx, stream)
+        self.data, self.stream = bytes(data), bytes(stream)
         self.grid = SMod.data_grid(stream) if len(stream) else []
         self.nck = sum(1 for n, _ in self.grid if n)
         self.ck_start = np.concatenate([[0], np.cumsum([n for n, _ in self.grid])]).astype(np.int64)
@@ -67,7 +54,7 @@ class Indexed:
     def spans_raw(self, idx):
         """-> (the call's value, off, len): the guarded arrays whole."""
         n = len(idx)
-        d_idx, off, ln = dev(idx), guarded(n), guarded(n)
+        d_idx, off, ln = dev_u64(idx), guarded(n), guarded(n)
         r = _lib.lib().mlz_dev_reader_record_spans(self.rd.handle, None, d_idx.data_ptr() if n else None, n, off.data_ptr(), ln.data_ptr())
         torch.cuda.synchronize()
         return r, off.cpu().numpy(), ln.cpu().numpy()
@@ -86,7 +73,7 @@ class Indexed:
     def read_raw(self, idx, dst_cap, starts=True, **kw):
         """-> (the call's value, dst, starts): the guarded arrays whole."""
         n = len(idx)
-        d_idx = dev(idx)
+        d_idx = dev_u64(idx)
         dst = torch.full((dst_cap + 64,), 0x5A, dtype=torch.uint8, device="cuda")
         st = guarded(n + 1)
         flags = 1 if kw.get("ignore_crc") else 0
@@ -105,9 +92,6 @@ class Indexed:
                 j1 = int(np.searchsorted(self.ck_start, start[r] + length[r] - 1, side="right")) - 1
                 seen.update(range(j0, j1 + 1))
         return seen
-
-    def close(self):
-        self.rd.close()
 
 
 def plain_case(bs, nblk):
@@ -294,7 +278,7 @@ def test_read_records(plain):
     assert got == -MLZ_ERR_ARG and (dst == 0x5A).all() and (st == SENT).all()
     got, dst, st = h.read_raw(idx, len(want) - 1)
     assert got == -MLZ_ERR_DST_TOO_SMALL and (dst == 0x5A).all() and (st == SENT).all()
-    d_bad = dev(bad)
+    d_bad = dev_u64(bad)
     with pytest.raises(mz.MinLZError):
         h.rd.read_records(d_bad.data_ptr(), len(bad), None, 0)
 
@@ -313,7 +297,7 @@ def test_record_spans_arguments(plain):
     assert r == 0 and (off == SENT).all() and (ln == SENT).all()
     L = _lib.lib()
     host = np.zeros(8, np.uint64)
-    d_idx, o, l_ = dev([1, 2]), guarded(2), guarded(2)
+    d_idx, o, l_ = dev_u64([1, 2]), guarded(2), guarded(2)
     bad = [L.mlz_dev_reader_record_spans(h.rd.handle, None, host.ctypes.data, 2, o.data_ptr(), l_.data_ptr()),
            L.mlz_dev_reader_record_spans(h.rd.handle, None, d_idx.data_ptr(), 2, host.ctypes.data, l_.data_ptr()),
            L.mlz_dev_reader_record_spans(h.rd.handle, None, d_idx.data_ptr(), 2, o.data_ptr(), host.ctypes.data),
@@ -326,7 +310,7 @@ def test_record_spans_arguments(plain):
 
 def numbers_raw(h, pos):
     n = len(pos)
-    d_pos, no = dev(pos), guarded(n)
+    d_pos, no = dev_u64(pos), guarded(n)
     r = _lib.lib().mlz_dev_reader_record_numbers(h.rd.handle, None, d_pos.data_ptr() if n else None, n, no.data_ptr())
     torch.cuda.synchronize()
     return r, no.cpu().numpy()
@@ -359,7 +343,7 @@ def test_line_numbers_of_a_search(ctx):
     for at in (0, 2 * bs - 5, 3 * bs + 1000, 3 * bs + 1100, len(d) - len(NEEDLE)):
         d[at:at + len(NEEDLE)] = NEEDLE
     d = bytes(d)
-    h = Indexed(ctx, gather(ctx, [d], bs, 6), d)
+    h = Indexed(ctx, gather(ctx, [d], bs, search_match_len=6), d)
     try:
         h.index()
         want = RM.result(d, NEEDLE, NL, 0, 64, 1 << 20)
@@ -486,7 +470,7 @@ def test_device_stream(ctx):
     bs = 64 << 10
     d = plain_case(bs, 6)
     codec = shard.HipTensorCodec(ctx)
-    t = torch.from_numpy(np.frombuffer(gather(ctx, [d], bs, 6), np.uint8).copy()).cuda()
+    t = torch.from_numpy(np.frombuffer(gather(ctx, [d], bs, search_match_len=6), np.uint8).copy()).cuda()
     with codec.open_stream(t) as ds:
         with pytest.raises(mz.MinLZError):
             ds.read_records(torch.tensor([0], dtype=torch.int64, device="cuda"))

@@ -8,19 +8,12 @@ import minlz_amd as mz
 from minlz_amd import _lib, api, shard, synth
 from tests import records_model as RM
 from tests import search_model as SMod
-from tests.search_gpu import SENT, gather_into
+from tests.search_gpu import SENT, Opened, gather
 
 pytestmark = pytest.mark.gpu
 
 MLZ_ERR_ARG = 8
 NL = b"\n"
-
-
-def gather(ctx, parts, bs, M):
-    """The device-resident Writer's stream of `parts`: without tables (M None) or with type 1 tables of match length M."""
-    n = sum(len(p) for p in parts)
-    cap = _lib.lib().mlz_stream_bound(n, bs, 0 if M is None else 4 | (M << 8))
-    return gather_into(ctx, parts, cap, 1, bs, False, search_match_len=M)
 
 
 def lines(n, seed, kind="json_like"):
@@ -31,13 +24,12 @@ def plant(d, at, what):
     d[at:at + len(what)] = what
 
 
-class Records:
+class Records(Opened):
     """A stream on the device and its decoded bytes; a call compares everything the call returns and writes with the model."""
 
     def __init__(self, ctx, stream, data):
-        self.ctx, self.data = ctx, bytes(data)
-        self.t = torch.from_numpy(np.frombuffer(stream, np.uint8).copy()).cuda() if len(stream) else torch.empty(0, dtype=torch.uint8, device="cuda")
-        self.rd = ctx.stream_open_device(self.t.data_ptr() if len(stream) else None, len(stream))
+        super().__init__(ctx, stream)
+        self.data = bytes(data)
         self.nck = len(SMod.data_grid(stream))
 
     def raw(self, pat, delim, W, rec_cap, dst_cap, starts=True, flags=True, **kw):
@@ -74,9 +66,6 @@ class Records:
         assert (dst[nb:] == 0x5A).all(), what
         return want, stats
 
-    def close(self):
-        self.rd.close()
-
 
 NEEDLE = b"@zq-needle-77@"
 
@@ -99,7 +88,7 @@ def plain_case(bs, nblk):
 def plain(ctx, request):
     bs, nblk = request.param
     d = plain_case(bs, nblk)
-    stream = gather(ctx, [d], bs, None)
+    stream = gather(ctx, [d], bs)
     assert SMod.data_grid(stream)[1][1] == 0x01   # the random block: stored
     h = Records(ctx, stream, d)
     yield h, bs
@@ -206,7 +195,7 @@ def typed_case(bs, nblk):
 def typed(ctx, request):
     bs, nblk = request.param
     d, needles = typed_case(bs, nblk)
-    stream = gather(ctx, [d], bs, 6)
+    stream = gather(ctx, [d], bs, search_match_len=6)
     cfg, B, tables = SMod.read_tables(stream, types=(1,))
     sizes = [n for n, _ in SMod.data_grid(stream)]
     assert cfg is not None and sum(t is not None for t in tables) >= len(tables) // 2
@@ -264,7 +253,7 @@ def test_record_over_four_chunks(ctx, bs, nblk):
     plant(d, at, NL + long_line + NL)
     d = bytes(d)
     for M in (None, 6):
-        h = Records(ctx, gather(ctx, [d], bs, M), d)
+        h = Records(ctx, gather(ctx, [d], bs, search_match_len=M), d)
         try:
             want, _ = h(NEEDLE, W=n + 5, rec_cap=4, dst_cap=n + 100)
             assert want["R"] == 1 and want["dst"] == long_line and want["rec_off"] == [at + 1] and want["flags"] == [0]
@@ -284,7 +273,7 @@ def test_stream_without_a_delimiter(ctx):
         plant(d, at, NEEDLE)
     d = bytes(d)
     assert NL not in d
-    h = Records(ctx, gather(ctx, [d], bs, 6), d)
+    h = Records(ctx, gather(ctx, [d], bs, search_match_len=6), d)
     try:
         want, _ = h(NEEDLE, dst_cap=1 << 20)                  # the default reach cuts: two overlapping pieces
         assert want["R"] == 4 and want["flags"] == [2, 3, 3, 1]
@@ -314,7 +303,7 @@ def test_words(ctx):
     occ = RM.occurrences(d, pat)
     assert len(occ) >= 2000 and b" " not in pat
     for M in (None, 6):
-        h = Records(ctx, gather(ctx, [d], bs, M), d)
+        h = Records(ctx, gather(ctx, [d], bs, search_match_len=M), d)
         try:
             want, _ = h(pat, delim=b" ", W=64, rec_cap=len(occ) + 8, dst_cap=1 << 20)
             assert want["R"] > 1024 and want["k"] == want["R"] and want["totals"][2] == len(occ)
@@ -330,7 +319,7 @@ def test_device_stream(ctx):
     bs = 64 << 10
     d = plain_case(bs, 6)
     codec = shard.HipTensorCodec(ctx)
-    t = torch.from_numpy(np.frombuffer(gather(ctx, [d], bs, 6), np.uint8).copy()).cuda()
+    t = torch.from_numpy(np.frombuffer(gather(ctx, [d], bs, search_match_len=6), np.uint8).copy()).cuda()
     ds = codec.open_stream(t)
     want = RM.result(d, NEEDLE, NL, 0, 3, 1 << 20)
     total, data, rec_off, rec_start, flags, totals = ds.search_records(NEEDLE, max_records=3)

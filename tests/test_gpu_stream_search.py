@@ -2,7 +2,6 @@
 search over streams in HBM (mlz_dev_reader_search, DeviceReader.search, DeviceStream.search), against tests/search_model.py: the
 specification in plain Python.  The Writer's stream must be the flag-off stream of the same call with the model's chunks spliced in; a
 search must return what a brute-force search of the decoded bytes returns and decode exactly the chunks the model's plan rule names."""
-import ctypes as C
 import io
 
 import numpy as np
@@ -14,22 +13,13 @@ import oracle as O
 from minlz_amd import _lib, shard, stream as S, synth
 from tests import search_cases as SC
 from tests import search_model as SMod
-from tests.search_gpu import SENT, data_for, gather_into
+from tests.search_gpu import Searcher, data_for, gather
 
 pytestmark = pytest.mark.gpu
 
 TYPES = (1,)            # these tests read a stream's tables as a searcher that knows type 1 alone
 
 MLZ_ERR_ARG = 8
-
-
-def gather(ctx, parts, level, bs, add_index, M):
-    """mlz_stream_encode_gather_device over `parts` (bytes objects, one range each) -> the stream's bytes."""
-    L = _lib.lib()
-    n = sum(len(p) for p in parts)
-    flags = (1 if add_index else 0) | (0 if M is None else 4 | (M << 8))
-    cap = L.mlz_stream_bound(n, bs, flags)
-    return gather_into(ctx, parts, cap, level, bs, add_index, search_match_len=M)
 
 
 def check_stream(ctx, stream, d, bs, M, add_index, what):
@@ -55,8 +45,8 @@ def writer_case(ctx, kind, bs, nblk, M, add_index, parts=1, mctx=None):
     cut = [0] + [((nblk * i) // parts) * bs for i in range(1, parts)] + [len(d)]
     ranges = [d[cut[i]:cut[i + 1]] for i in range(parts)]
     c = mctx or ctx
-    off = gather(c, ranges, 1, bs, add_index, None)
-    on = gather(c, ranges, 1, bs, add_index, M)
+    off = gather(c, ranges, bs, add_index)
+    on = gather(c, ranges, bs, add_index, search_match_len=M)
     B = SMod.table_bits(bs)
     want, tables = SMod.splice(off, d, SMod.config(1, M), B, index=add_index)
     what = "%s bs=%d M=%d index=%s parts=%d" % (kind, bs, M, add_index, parts)
@@ -85,7 +75,7 @@ def test_writer_every_match_length(ctx, M, bs, nblk):
 def test_writer_default_match_length_and_index_both_ways(ctx):
     d = data_for("text_like", 64 << 10, 40, 99, random_block=None)
     for idx in (False, True):
-        a, b = gather(ctx, [d], 1, 64 << 10, idx, 0), gather(ctx, [d], 1, 64 << 10, idx, 6)
+        a, b = gather(ctx, [d], 64 << 10, idx, search_match_len=0), gather(ctx, [d], 64 << 10, idx, search_match_len=6)
         assert a == b and a[10:17] == bytes([0x44, 3, 0, 0, 1, 6, 16])
 
 
@@ -98,8 +88,8 @@ def test_writer_several_ranges_on_two_contexts(ctx):
         # an empty range between two others, and a last range shorter than the overlap
         bs = 64 << 10
         d = data_for("text_like", bs, 4, 3)
-        off = gather(m, [d[:2 * bs], b"", d[2 * bs:4 * bs], d[4 * bs:]], 1, bs, False, None)
-        on = gather(m, [d[:2 * bs], b"", d[2 * bs:4 * bs], d[4 * bs:]], 1, bs, False, 6)
+        off = gather(m, [d[:2 * bs], b"", d[2 * bs:4 * bs], d[4 * bs:]], bs, False)
+        on = gather(m, [d[:2 * bs], b"", d[2 * bs:4 * bs], d[4 * bs:]], bs, False, search_match_len=6)
         assert on == SMod.splice(off, d, SMod.config(1, 6), 16)[0]
     finally:
         m.close()
@@ -122,31 +112,10 @@ def test_writer_arguments(ctx):
         n = 3 * bs + 5
         B = SMod.table_bits(bs)
         assert L.mlz_stream_bound(n, bs, 4) == L.mlz_stream_bound(n, bs, 0) + 7 + 4 * (12 + max(32, 1 << (B - 3)))
-    assert gather(ctx, [b""], 1, 4096, False, 6) == gather(ctx, [b""], 1, 4096, False, None)   # an empty stream: no header, no info chunk
+    assert gather(ctx, [b""], 4096, False, search_match_len=6) == gather(ctx, [b""], 4096, False)   # an empty stream: no header, no info chunk
 
 
 # ---- search ----
-
-class Searcher:
-    def __init__(self, ctx, stream):
-        self.ctx = ctx
-        self.t = torch.from_numpy(np.frombuffer(stream, np.uint8).copy()).cuda() if len(stream) else torch.empty(0, dtype=torch.uint8, device="cuda")
-        self.rd = ctx.stream_open_device(self.t.data_ptr() if len(stream) else None, len(stream))
-
-    def __call__(self, pattern, cap, null=False, **kw):
-        """-> (total, positions, stats); checks that nothing beyond min(total, cap) was written."""
-        out = torch.full((cap + 8,), SENT, dtype=torch.int64, device="cuda")
-        total, stats = self.rd.search(pattern, None if null else out.data_ptr(), cap, **kw)
-        torch.cuda.synchronize()
-        o = out.cpu().numpy()
-        k = min(total, cap)
-        assert (o[k:] == SENT).all(), "written beyond the results"
-        assert self.ctx.search_plan() == stats[1:]
-        return total, o[:k].tolist(), stats
-
-    def close(self):
-        self.rd.close()
-
 
 def check_search(sr, stream, d, pattern, what, cap=None, ignore_crc=False):
     want = SMod.brute(d, pattern)
@@ -189,7 +158,7 @@ def pattern_set(d, nd, big, M, bs):
 def test_search_over_the_writers_streams(ctx, M):
     bs = 64 << 10
     d, nd, big = search_data(bs, 9, 500, M)
-    stream = gather(ctx, [d], 1, bs, True, M)
+    stream = gather(ctx, [d], bs, True, search_match_len=M)
     sr = Searcher(ctx, stream)
     try:
         for name, p in pattern_set(d, nd, big, M, bs):
@@ -212,7 +181,7 @@ def test_search_over_the_writers_streams(ctx, M):
 def test_search_streams_without_tables_and_foreign_streams(ctx):
     bs = 64 << 10
     d, nd, big = search_data(bs, 9, 500, 6)
-    cases = [("flag off", gather(ctx, [d], 1, bs, False, None))]
+    cases = [("flag off", gather(ctx, [d], bs, False))]
     w = io.BytesIO()
     wr = S.Writer(w, level=1, block_size=bs, concurrency=4, backend=S.HipBackend(ctx))
     for a, b in ((0, 100), (100, 3 * bs + 7), (3 * bs + 7, 3 * bs + 9), (3 * bs + 9, len(d))):   # short interior blocks, one shorter than the pattern
@@ -254,7 +223,7 @@ def test_search_many_chunks_cross_group_borders(ctx):
     for o in (5, (64 << 20) - 20, (64 << 20) - 40, (64 << 20), (128 << 20) - 1, len(d) - 40):
         d[o:o + 40] = nd
     d = bytes(d)
-    stream = gather(ctx, [d], 1, bs, False, 6)
+    stream = gather(ctx, [d], bs, False, search_match_len=6)
     sr = Searcher(ctx, stream)
     try:
         st = check_search(sr, stream, d, nd, "many chunks")
@@ -269,7 +238,7 @@ def test_designated_input_decodes_a_handful(ctx, kind):
     for seed in (1, 2, 3):
         bs, nblk = 64 << 10, 128
         d, nd, at = SC.planted(kind, bs, nblk, 16, seed)
-        stream = gather(ctx, [d], 1, bs, False, 6)
+        stream = gather(ctx, [d], bs, False, search_match_len=6)
         sr = Searcher(ctx, stream)
         try:
             st = check_search(sr, stream, d, nd, "%s seed %d" % (kind, seed))
@@ -283,7 +252,7 @@ def test_designated_input_decodes_a_handful(ctx, kind):
 def test_broken_table_and_broken_chunks(ctx):
     bs, nblk = 64 << 10, 16
     d, nd, at = SC.planted("text_like", bs, nblk, 16, 2)
-    stream = gather(ctx, [d], 1, bs, False, 6)
+    stream = gather(ctx, [d], bs, False, search_match_len=6)
     cfg, B, tables = SMod.read_tables(stream, types=TYPES)
     sizes = [n for n, _ in SMod.data_grid(stream)]
     plan = SMod.plan(tables, sizes, nd, cfg, B)

@@ -12,12 +12,11 @@ import torch
 import minlz_amd as mz
 import oracle as O
 from minlz_amd import _lib, synth
-from minlz_amd.api import search_long_prefix_config
 from tests import search_cases as SC
 from tests import search_long_prefix_cases as LC
 from tests import search_model as SMod
 from tests import search_prefix_cases as PC
-from tests.search_gpu import SENT, Searcher, data_for, first_difference, gather_into, on_device
+from tests.search_gpu import Searcher, data_for, first_difference, gather, on_device
 
 pytestmark = pytest.mark.gpu
 
@@ -26,26 +25,12 @@ FILL = ord("a")
 ME = [(6, 0), (6, 3), (8, 8), (1, 15)]
 
 
-def gather(ctx, parts, bs, add_index, M=None, pfx=None, E=0, level=1):
-    """The stream of `parts` (bytes objects, one range each): without tables (M None) or with long-prefix tables.  The room is what the
-    bound says, and nothing is written behind it."""
-    L = _lib.lib()
-    n = sum(len(p) for p in parts)
-    idx = 1 if add_index else 0
-    if pfx is None:
-        cap = L.mlz_stream_bound(n, bs, idx)
-    else:
-        cap = L.mlz_stream_bound_long_prefix(n, bs, idx, C.byref(search_long_prefix_config(M, pfx, E)))
-    kw = {} if pfx is None else dict(search_match_len=M, search_long_prefix=pfx, search_extras=E)
-    return gather_into(ctx, parts, cap, level, bs, add_index, **kw)
-
-
 def writer_case(ctx, d, bs, M, E, pfx, add_index=False, cuts=None, what=""):
     """-> (stream, tables): the Writer's stream, equal to the model's splice of the table-less stream of the same call."""
     cuts = [0] + list(cuts or []) + [len(d)]
     ranges = [d[cuts[i]:cuts[i + 1]] for i in range(len(cuts) - 1)]
     off = gather(ctx, ranges, bs, add_index)
-    on = gather(ctx, ranges, bs, add_index, M, pfx, E)
+    on = gather(ctx, ranges, bs, add_index, search_match_len=M, search_long_prefix=pfx, search_extras=E)
     field, B = SMod.config(4, M, pfx, E)[2], SMod.table_bits(bs)
     want, tables = SMod.splice(off, d, (4, M, field), B, index=add_index)
     what = "%s bs=%d K=%d M=%d E=%d index=%s ranges=%d" % (what, bs, len(pfx), M, E, add_index, len(ranges))
@@ -262,7 +247,7 @@ def test_writer_arguments(ctx):
         assert call(flags, cfg()) == -MLZ_ERR_ARG
     assert (out.cpu().numpy() == 0x5A).all()
     n = call(1, cfg(m=0))
-    assert n > 0 and out[:n].cpu().numpy().tobytes() == gather(ctx, [d], bs, True, 6, LC.USER, 3)        # match_len 0 = 6
+    assert n > 0 and out[:n].cpu().numpy().tobytes() == gather(ctx, [d], bs, True, search_match_len=6, search_long_prefix=LC.USER, search_extras=3)        # match_len 0 = 6
     assert out[10:17].cpu().numpy().tobytes() == bytes([0x44, 3 + 2 + 8, 0, 0, 4, 6, 16]) and out[17:27].cpu().numpy().tobytes() == bytes([7, 3]) + LC.USER
     n = call(0, cfg(b"x" * 256, m=8, e=8))
     assert n > 0 and out[10:14].cpu().numpy().tobytes() == bytes([0x44, (3 + 258) & 255, (3 + 258) >> 8, 0])
@@ -278,7 +263,7 @@ def test_writer_arguments(ctx):
     c4 = _lib.SearchTables()
     c4.table_type, c4.match_len = 4, 6
     assert L.mlz_stream_encode_gather_device_tables(ctx.handle, 1, bs, 0, C.byref(c4), sp, sl, 1, out.data_ptr(), out.numel()) == -MLZ_ERR_ARG
-    assert gather(ctx, [b""], 4096, False, 6, LC.USER, 3) == gather(ctx, [b""], 4096, False)             # an empty stream: no header, no info chunk
+    assert gather(ctx, [b""], 4096, False, search_match_len=6, search_long_prefix=LC.USER, search_extras=3) == gather(ctx, [b""], 4096, False)             # an empty stream: no header, no info chunk
 
 
 # ---- search ----
@@ -300,7 +285,7 @@ def check_search(sr, stream, d, pattern, what, cap=None, ignore_crc=False):
 def test_search_over_the_writers_streams(ctx, pfx, M, E):
     bs, nblk = 64 << 10, 8
     d, pats = LC.designed("json_like", bs, nblk, 777, M, E, pfx)
-    stream = gather(ctx, [d], bs, True, M, pfx, E)
+    stream = gather(ctx, [d], bs, True, search_match_len=M, search_long_prefix=pfx, search_extras=E)
     assert SMod.read_tables(stream)[:2] == (SMod.config(4, M, pfx, E), 16)
     sr = Searcher(ctx, stream)
     try:
@@ -355,7 +340,7 @@ def test_search_table_verdicts(ctx):
     bs, nblk, M, E = 64 << 10, 8, 8, 8
     K = len(LC.USER)
     d, pats = LC.designed("json_like", bs, nblk, 777, M, E, LC.USER)
-    stream = gather(ctx, [d], bs, False, M, LC.USER, E)
+    stream = gather(ctx, [d], bs, False, search_match_len=M, search_long_prefix=LC.USER, search_extras=E)
     (T, _, field), B, tables = SMod.read_tables(stream)
     p = dict(pats)["p0"]
     plan = SMod.plan_of_stream(stream, p)[0]
@@ -391,7 +376,7 @@ def test_designated_input_decodes_a_handful(ctx, kind):
     for seed in (1, 2, 3):
         bs, nblk = 64 << 10, 128
         d, nd, at = PC.planted_id(kind, bs, nblk, seed)
-        stream = gather(ctx, [d], bs, False, 6, LC.ID, 3)
+        stream = gather(ctx, [d], bs, False, search_match_len=6, search_long_prefix=LC.ID, search_extras=3)
         sr = Searcher(ctx, stream)
         try:
             st = check_search(sr, stream, d, nd, "%s seed %d" % (kind, seed))
@@ -408,7 +393,7 @@ def test_user_prefix_absent_pattern(ctx):
     bs, nblk = 64 << 10, 16
     d = synth.json_like(bs * nblk + 777, 2).tobytes()
     plain = gather(ctx, [d], bs, False)
-    stream = gather(ctx, [d], bs, False, 6, LC.USER, 3)
+    stream = gather(ctx, [d], bs, False, search_match_len=6, search_long_prefix=LC.USER, search_extras=3)
     print("tables", len(stream) - len(plain), "bytes of", len(d))
     sr = Searcher(ctx, stream)
     try:

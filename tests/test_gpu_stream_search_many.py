@@ -13,7 +13,7 @@ from tests import search_cases as SC
 from tests import search_long_prefix_cases as LC
 from tests import search_model as SMod
 from tests import search_prefix_cases as PC
-from tests.search_gpu import SENT, Searcher, gather_into
+from tests.search_gpu import SENT, Opened, Searcher, gather
 from tests.test_gpu_stream_search import check_search
 
 pytestmark = pytest.mark.gpu
@@ -23,20 +23,7 @@ SENT32 = 0x5A5A5A5A
 GUARD = 8
 
 
-def gather(ctx, d, bs, **kw):
-    """The Writer's stream over `d` with the tables `kw` asks for (none: a stream without tables); room for the largest table per block."""
-    L = _lib.lib()
-    nblk = (len(d) + bs - 1) // bs
-    cap = L.mlz_stream_bound(len(d), bs, 1) + (nblk + 2) * (12 + 260 + (1 << (SMod.table_bits(bs) - 3))) + 1024
-    return gather_into(ctx, [d], cap, 1, bs, True, **kw)
-
-
-class ManySearcher:
-    def __init__(self, ctx, stream):
-        self.ctx = ctx
-        self.t = torch.from_numpy(np.frombuffer(stream, np.uint8).copy()).cuda() if len(stream) else torch.empty(0, dtype=torch.uint8, device="cuda")
-        self.rd = ctx.stream_open_device(self.t.data_ptr() if len(stream) else None, len(stream))
-
+class ManySearcher(Opened):
     def __call__(self, pats, cap, null=False, **kw):
         """-> (total, [(position, pattern)], counts, stats); nothing is written beyond min(total, cap) pairs and len(pats) counts."""
         n = len(pats)
@@ -53,9 +40,6 @@ class ManySearcher:
 
     def single(self, p, **kw):
         return self.rd.search(p, None, 0, **kw)[0]
-
-    def close(self):
-        self.rd.close()
 
 
 def brute_pairs(d, pats):
@@ -115,7 +99,7 @@ def model_plans(name, stream, pats):
 def test_against_brute_force_and_single_calls(ctx, name):
     bs, M = 64 << 10, 6
     d = synth.json_like(bs * 9 + 500, 5).tobytes()
-    stream = gather(ctx, d, bs, **CONFIGS[name])
+    stream = gather(ctx, [d], bs, True, **CONFIGS[name])
     assert O.stream_decode(stream, len(d)) == d
     pats = mixed_patterns(d, M, bs)
     sr = ManySearcher(ctx, stream)
@@ -168,7 +152,7 @@ def test_single_is_many_with_one_pattern(ctx, name):
     test_against_brute_force_and_single_calls.)"""
     bs, M = 64 << 10, 6
     d = synth.json_like(bs * 9 + 500, 5).tobytes()
-    stream = gather(ctx, d, bs, **CONFIGS[name])
+    stream = gather(ctx, [d], bs, True, **CONFIGS[name])
     sr = ManySearcher(ctx, stream)
     try:
         not_served = []                                                      # per pattern: search_many's fourth statistic
@@ -195,7 +179,7 @@ def test_plan_is_the_union_of_the_models_plans(ctx, kind):
     """128 x 64 KiB, M = 6, the planted needle of SC.planted and absent ones: the union of the models' plans is decoded, a handful of chunks."""
     bs, nblk, M = 64 << 10, 128, 6
     d, nd, at = SC.planted(kind, bs, nblk, 16, 1)
-    stream = gather(ctx, d, bs, search_match_len=M)
+    stream = gather(ctx, [d], bs, True, search_match_len=M)
     cfg, B, tables = SMod.read_tables(stream, types=(1,))
     sizes = [n for n, _ in SMod.data_grid(stream)]
     assert cfg == (1, M, b"") and len(sizes) == nblk
@@ -226,7 +210,7 @@ def test_many_patterns(ctx, n):
     bs = 64 << 10
     rng = np.random.default_rng(n)
     d = synth.text_like(bs * 9 + 321, 8).tobytes()
-    stream = gather(ctx, d, bs, search_match_len=6)
+    stream = gather(ctx, [d], bs, True, search_match_len=6)
     pats = []
     for i in range(n - 1):
         if i % 3 == 2:
@@ -253,7 +237,7 @@ def test_cap(ctx):
     d[5 * bs - 20:5 * bs + 30] = b"a" * 50
     d[7 * bs - 8:7 * bs + 8] = bytes(SC.needle(16, 78))                         # across a border, behind the run of a
     d = bytes(d)
-    stream = gather(ctx, d, bs, search_match_len=6)
+    stream = gather(ctx, [d], bs, True, search_match_len=6)
     pats = [b"aaaaaa", b"aaaaaaa", b"aaaaaa", bytes(SC.needle(16, 77)), bytes(SC.needle(16, 78))]
     pairs, counts = brute_pairs(d, pats)
     assert len(pairs) > 100 and pairs[0][0] == pairs[1][0] == pairs[2][0] and [i for _, i in pairs[:3]] == [0, 1, 2]
@@ -284,7 +268,7 @@ def test_group_border(ctx):
         d[o:o + 40] = rnd
     d = bytes(d)
     needles = [b"\xf1" * 2, b"\xf1" * 40, b"\xf1" * 256, rnd]
-    stream = gather(ctx, d, bs, search_match_len=6)
+    stream = gather(ctx, [d], bs, True, search_match_len=6)
     sr = ManySearcher(ctx, stream)
     try:
         pairs, counts = brute_pairs(d, needles)
@@ -312,7 +296,7 @@ def test_stored_chunks_on_both_sides_of_the_group_border(ctx):
     for nd, o in zip(needles, (8 * bs + 3 * (bs // 4) + 5, 7 * bs + 100_001, 8 * bs - 11)):
         d[o:o + 24] = nd
     d = bytes(d)
-    stream = gather(ctx, d, bs)
+    stream = gather(ctx, [d], bs, True)
     grid = SMod.data_grid(stream)
     assert [n for n, _ in grid] == [bs] * 9 and grid[7][1] == grid[8][1] == 0x01 and all(t != 0x01 for _, t in grid[:7])
     sr = ManySearcher(ctx, stream)
@@ -379,7 +363,7 @@ def test_arguments(ctx):
 def test_tensor_front_end(ctx):
     bs = 64 << 10
     d, nd, at = SC.planted("text_like", bs, 9, 16, 2, tail=100)
-    stream = gather(ctx, d, bs, search_match_len=6)
+    stream = gather(ctx, [d], bs, True, search_match_len=6)
     t = torch.from_numpy(np.frombuffer(stream, np.uint8).copy()).cuda()
     pats = [nd, b"the ", nd[:8]]
     pairs, counts = brute_pairs(d, pats)

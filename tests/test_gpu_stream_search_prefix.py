@@ -12,11 +12,10 @@ import torch
 import minlz_amd as mz
 import oracle as O
 from minlz_amd import _lib, synth
-from minlz_amd.api import search_tables_config
 from tests import search_cases as SC
 from tests import search_model as SMod
 from tests import search_prefix_cases as PC
-from tests.search_gpu import SENT, Searcher, data_for, first_difference, gather_into, on_device
+from tests.search_gpu import Searcher, data_for, first_difference, gather, on_device
 
 pytestmark = pytest.mark.gpu
 
@@ -26,26 +25,12 @@ MLZ_ERR_ARG = 8
 FILL = ord("a")          # in neither prefix set
 
 
-def gather(ctx, parts, bs, add_index, M=None, pset=None, level=1):
-    """The stream of `parts` (bytes objects, one range each): without tables (M None), with type 1 tables (pset None) or with prefix tables.
-    The room is what mlz_stream_bound_tables says, and nothing is written behind it."""
-    L = _lib.lib()
-    n = sum(len(p) for p in parts)
-    idx = 1 if add_index else 0
-    if pset is None:
-        cap = L.mlz_stream_bound(n, bs, idx | (0 if M is None else 4 | (M << 8)))
-    else:
-        cfg = search_tables_config(M, pset)
-        cap = L.mlz_stream_bound_tables(n, bs, idx, C.byref(cfg))
-    return gather_into(ctx, parts, cap, level, bs, add_index, search_match_len=M, search_prefix=pset)
-
-
 def writer_case(ctx, d, bs, M, pset, add_index, cuts=None, what=""):
     """-> (stream, tables): the Writer's stream, equal to the model's splice of the table-less stream of the same call."""
     cuts = [0] + list(cuts or []) + [len(d)]
     ranges = [d[cuts[i]:cuts[i + 1]] for i in range(len(cuts) - 1)]
     off = gather(ctx, ranges, bs, add_index)
-    on = gather(ctx, ranges, bs, add_index, M, pset)
+    on = gather(ctx, ranges, bs, add_index, search_match_len=M, search_prefix=pset)
     T, field = SMod.field_of(pset)
     B = SMod.table_bits(bs)
     want, tables = SMod.splice(off, d, (T, M, field), B, index=add_index)
@@ -100,7 +85,7 @@ def test_type_1_through_the_new_call_is_the_flag_path(ctx):
     sp, sl = (C.c_void_p * 1)(src.data_ptr()), (C.c_size_t * 1)(len(d))
     for M in (0, 1, 6, 8):
         for idx in (0, 1):
-            want = gather(ctx, [d], bs, bool(idx), M)
+            want = gather(ctx, [d], bs, bool(idx), search_match_len=M)
             cfg = _lib.SearchTables()
             cfg.table_type, cfg.match_len = 1, M
             cap = L.mlz_stream_bound_tables(len(d), bs, idx, C.byref(cfg))
@@ -251,7 +236,7 @@ def test_writer_arguments(ctx):
         assert call(flags, cfg(2)) == -MLZ_ERR_ARG and L.mlz_stream_bound_tables(len(d), bs, flags, C.byref(cfg(2))) == -MLZ_ERR_ARG
     assert (out.cpu().numpy() == 0x5A).all()
     n = call(1, cfg(2, m=0))
-    assert n > 0 and out[:n].cpu().numpy().tobytes() == gather(ctx, [d], bs, True, 6, b":")        # match_len 0 = 6
+    assert n > 0 and out[:n].cpu().numpy().tobytes() == gather(ctx, [d], bs, True, search_match_len=6, search_prefix=b":")        # match_len 0 = 6
     assert call(0, cfg(3, n=200)) > 0                                                                # n_prefix is ignored outside type 2
     c8 = cfg(2, n=8)
     for i, v in enumerate(b":,\" ={}["):
@@ -266,7 +251,7 @@ def test_writer_arguments(ctx):
     for b2 in (4 << 10, 64 << 10, 8 << 20):
         n2, B = 3 * b2 + 5, SMod.table_bits(b2)
         assert L.mlz_stream_bound(n2, b2, 4) == L.mlz_stream_bound(n2, b2, 0) + 7 + 4 * (12 + max(32, 1 << (B - 3)))
-    assert gather(ctx, [b""], 4096, False, 6, b":") == gather(ctx, [b""], 4096, False)                 # an empty stream: no header, no info chunk
+    assert gather(ctx, [b""], 4096, False, search_match_len=6, search_prefix=b":") == gather(ctx, [b""], 4096, False)                 # an empty stream: no header, no info chunk
 
 
 # ---- search ----
@@ -291,7 +276,7 @@ def test_search_over_the_writers_streams(ctx, set_name, M):
     bs, nblk = 64 << 10, 8
     pset = PC.SETS[set_name]
     d, pats = PC.designed("json_like", bs, nblk, 777, M, pset)
-    stream = gather(ctx, [d], bs, True, M, pset)
+    stream = gather(ctx, [d], bs, True, search_match_len=M, search_prefix=pset)
     T, field = SMod.field_of(pset)
     assert SMod.read_tables(stream, types=TYPES)[:2] == ((T, M, field), 16)
     sr = Searcher(ctx, stream)
@@ -342,7 +327,7 @@ def test_search_patched_prefix_field(ctx):
     bs, nblk, M = 64 << 10, 8, 6
     pset = PC.SETS["json4"]
     d, pats = PC.designed("json_like", bs, nblk, 777, M, pset)
-    stream = gather(ctx, [d], bs, False, M, pset)
+    stream = gather(ctx, [d], bs, False, search_match_len=M, search_prefix=pset)
     cfg, B, tables = SMod.read_tables(stream, types=TYPES)
     sizes = [n for n, _ in SMod.data_grid(stream)]
     p = dict(pats)["one_window"]
@@ -380,7 +365,7 @@ def test_designated_input_decodes_a_handful(ctx, kind, set_name):
     for seed in (1, 2, 3):
         bs, nblk = 64 << 10, 128
         d, nd, at = PC.planted_id(kind, bs, nblk, seed)
-        stream = gather(ctx, [d], bs, False, 6, pset)
+        stream = gather(ctx, [d], bs, False, search_match_len=6, search_prefix=pset)
         sr = Searcher(ctx, stream)
         try:
             st = check_search(sr, stream, d, nd, "%s %s seed %d" % (kind, set_name, seed))

@@ -14,6 +14,7 @@ from minlz_amd import _lib, synth
 from minlz_amd.api import search_config
 from tests import search_cases as SC
 from tests import search_host as H
+from tests.search_host import both
 from tests import search_model as SMod
 from tests import sidecar_model as SM
 
@@ -28,17 +29,7 @@ CFG4 = SMod.config(4, 6, b'"user":"', 3)
 
 @pytest.fixture(scope="module")
 def checkers(tmp_path_factory):
-    """The plain build, and the same program under AddressSanitizer and UBSan where this g++ links their runtimes."""
-    return H.build_checker(tmp_path_factory, SRC), H.build_checker(tmp_path_factory, SRC, sanitized=True)
-
-
-def both(checkers, records):
-    """The plain program's lines; the sanitized build runs the same cases and must print the same."""
-    plain, san = checkers
-    lines = plain(records)[0]
-    if san is not None:
-        assert san(records)[0] == lines
-    return lines
+    return H.checkers(tmp_path_factory, SRC)
 
 
 def test_sanitized_build_links(checkers):

@@ -2,9 +2,7 @@
 code of minlz_amd/csrc/mlz_stream_batch.h (what walk_batch_kernel and the batch decode run) over streams laid BACK TO BACK in one buffer.
 Every stream's verdict and decoded prefix must be the host Reader's chunk walk's (mlz_stream_decoded_len / _prefix_len) of that stream
 alone: the next stream of the batch lies right behind it, so a byte read past a stream's end changes a verdict here."""
-import os
 import struct
-import subprocess
 from collections import Counter
 
 import numpy as np
@@ -15,47 +13,33 @@ from minlz_amd import _lib
 from tests import corrupt as CM
 from tests import stream_batch_cases as BC
 from tests import stream_device_cases as SC
+from tests.search_host import LINK_ERROR, build_checker
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tools", "stream_batch_check.cpp")
+SRC = "stream_batch_check.cpp"
 WALK_STEPS = 4096   # kBatchWalkSteps
 
 
-def _checker(tmp_path_factory, name, extra):
-    exe = tmp_path_factory.mktemp(name) / name
-    subprocess.run(["g++", "-O2", "-std=c++17"] + extra + ["-o", str(exe), SRC], check=True)
+def _checker(tmp_path_factory, sanitized):
+    program = build_checker(tmp_path_factory, SRC, sanitized=sanitized)
+    assert program is not None, LINK_ERROR.get(SRC)
 
     def walk(streams):
         buf, spans = BC.back_to_back(streams)
-        path = exe.parent / "batch.bin"
-        with open(path, "wb") as f:
-            f.write(struct.pack("<Q", len(spans)))
-            for o, n in spans:
-                f.write(struct.pack("<QQ", o, n))
-            f.write(struct.pack("<Q", len(buf)) + buf)
-        r = subprocess.run([str(exe), "walk", str(path)], capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
-        return [tuple(int(v) for v in line.split()) for line in r.stdout.splitlines()]
-
-    def verdicts(text):
-        path = exe.parent / "jobs.txt"
-        path.write_text(text)
-        r = subprocess.run([str(exe), "verdicts", str(path)], capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
-        return [int(v) for v in r.stdout.split()]
-    walk.verdicts = verdicts
+        records = [struct.pack("<Q", len(spans))] + [struct.pack("<QQ", o, n) for o, n in spans] + [struct.pack("<Q", len(buf)) + buf]
+        return [tuple(int(v) for v in line.split()) for line in program(records, ["walk"])[0]]
+    walk.verdicts = lambda text: [int(v) for line in program([text.encode()], ["verdicts"])[0] for v in line.split()]
     return walk
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    return _checker(tmp_path_factory, "sbc", [])
+    return _checker(tmp_path_factory, False)
 
 
 @pytest.fixture(scope="module")
 def checker_san(tmp_path_factory):
     """The same program under the address and undefined-behaviour sanitizers: stand-alone, nothing preloaded."""
-    return _checker(tmp_path_factory, "sbc_san", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+    return _checker(tmp_path_factory, True)
 
 
 def _host(s):

@@ -2,9 +2,7 @@
 minlz_amd/csrc/mlz_stream_walk.hip.inc on the host and runs the library's own record and running-state code (mlz_stream_walk.h) on what it
 finds; its verdict and decoded prefix must be the host Reader's chunk walk's (mlz_stream_decoded_len / _prefix_len) for valid streams, for
 every mutant of tests/corrupt.py's stream_mutants, for cuts at every length near the chunk borders and for the stream of many tiny chunks."""
-import os
 import struct
-import subprocess
 from collections import Counter
 
 import numpy as np
@@ -13,23 +11,14 @@ import pytest
 from minlz_amd import _lib
 from tests import corrupt as CM
 from tests import stream_device_cases as SC
+from tests.search_host import build_checker
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("swc") / "swc"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-o", str(exe), os.path.join(ROOT, "tools", "stream_walk_check.cpp")], check=True)
-
-    def run(streams):
-        path = exe.parent / "streams.bin"
-        with open(path, "wb") as f:
-            for s in streams:
-                f.write(struct.pack("<Q", len(s)) + s)
-        r = subprocess.run([str(exe), str(path)], capture_output=True, text=True, timeout=600, check=True)
-        return [tuple(int(v) for v in line.split()) for line in r.stdout.splitlines()]
-    return run
+    program = build_checker(tmp_path_factory, "stream_walk_check.cpp")
+    return lambda streams: [tuple(int(v) for v in line.split()) for line in program([struct.pack("<Q", len(s)) + s for s in streams])[0]]
 
 
 def _host(s):

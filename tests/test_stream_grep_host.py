@@ -12,6 +12,7 @@ from minlz_amd import _lib
 from tests import grep_model as GM
 from tests import record_index_model as IM
 from tests import search_host as H
+from tests.search_host import both
 
 SRC = "stream_grep_check.cpp"
 NL = b"\n"
@@ -21,16 +22,7 @@ BIG = 1 << 40
 
 @pytest.fixture(scope="module")
 def checkers(tmp_path_factory):
-    """The plain build, and the same program under AddressSanitizer and UBSan where this g++ links their runtimes."""
-    return H.build_checker(tmp_path_factory, SRC), H.build_checker(tmp_path_factory, SRC, sanitized=True)
-
-
-def both(checkers, records):
-    plain, san = checkers
-    lines = plain(records)[0]
-    if san is not None:
-        assert san(records)[0] == lines
-    return lines
+    return H.checkers(tmp_path_factory, SRC)
 
 
 def occurrences(data, pattern):

@@ -4,9 +4,7 @@ and intersection arithmetic) as plain loops and executes the outcome with memcpy
 under every range set of stream_ranges_cases.range_sets (the (off, len) columns, destinations packed in the order given) and under generated
 sets, the destination image must be the concatenation of the slices, touched chunks and scratch bytes the brute-force model's, and the plan
 (touched list, each chunk's class, each place, the groups) what plan_ranges gives for the same ranges: the tool compares the two itself."""
-import os
 import struct
-import subprocess
 import zlib
 
 import numpy as np
@@ -15,31 +13,27 @@ import pytest
 from minlz_amd import _lib
 from tests import stream_device_cases as SC
 from tests import stream_ranges_cases as RC
+from tests.search_host import build_checker
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_DST_TOO_SMALL, ERR_ARG = 6, 8
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("rdc") / "rdc"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-o", str(exe), os.path.join(ROOT, "tools", "stream_ranges_dev_check.cpp")], check=True)
+    program = build_checker(tmp_path_factory, "stream_ranges_dev_check.cpp")
 
     def run(cases):
         """cases: (grid or None = the case before's, pairs, dst_cap, data or None = plan only) -> a tuple of ints per case."""
-        path = exe.parent / "cases.bin"
-        with open(path, "wb") as f:
-            for grid, pairs, cap, data in cases:
-                flags = (1 if data is None else 0) | (2 if grid is None else 0)
-                f.write(struct.pack("<4Q", len(grid or ()), len(pairs), cap, flags))
-                if grid is not None:
-                    f.write(np.asarray(grid, dtype=np.uint64).reshape(-1, 2).tobytes())
-                f.write(np.ascontiguousarray(pairs, dtype=np.uint64).tobytes())
-                if grid is not None and data is not None:
-                    f.write(data)
-        r = subprocess.run([str(exe), str(path)], capture_output=True, text=True, timeout=900, check=True)
-        os.unlink(path)
-        return [tuple(int(v) for v in line.split()) for line in r.stdout.splitlines()]
+        records = []
+        for grid, pairs, cap, data in cases:
+            flags = (1 if data is None else 0) | (2 if grid is None else 0)
+            records.append(struct.pack("<4Q", len(grid or ()), len(pairs), cap, flags))
+            if grid is not None:
+                records.append(np.asarray(grid, dtype=np.uint64).reshape(-1, 2).tobytes())
+            records.append(np.ascontiguousarray(pairs, dtype=np.uint64).tobytes())
+            if grid is not None and data is not None:
+                records.append(data)
+        return [tuple(int(v) for v in line.split()) for line in program(records)[0]]
     return run
 
 

@@ -2,9 +2,7 @@
 (minlz_amd/csrc/mlz_stream_ranges.h) and executes the plan with memcpy; the destination image, the touched chunks and the scratch bytes
 must be the brute-force model's (tests/stream_ranges_cases.py) for every stream of stream_device_cases.valid_streams_cpu() under every
 range set, the scratch must stay within a group plus one block, and the argument rules that need no device are the planner's."""
-import os
 import struct
-import subprocess
 import zlib
 
 import numpy as np
@@ -13,32 +11,28 @@ import pytest
 from minlz_amd import _lib
 from tests import stream_device_cases as SC
 from tests import stream_ranges_cases as RC
+from tests.search_host import build_checker
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_DST_TOO_SMALL, ERR_ARG = 6, 8
 MiB = 1 << 20
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("src") / "src"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-o", str(exe), os.path.join(ROOT, "tools", "stream_ranges_check.cpp")], check=True)
+    program = build_checker(tmp_path_factory, "stream_ranges_check.cpp")
 
     def run(cases):
         """cases: (grid or None = the case before's, ranges, dst_cap, data or None = plan only) -> a tuple of ints per case."""
-        path = exe.parent / "cases.bin"
-        with open(path, "wb") as f:
-            for grid, ranges, cap, data in cases:
-                flags = (1 if data is None else 0) | (2 if grid is None else 0)
-                f.write(struct.pack("<4Q", len(grid or ()), len(ranges), cap, flags))
-                if grid is not None:
-                    f.write(np.asarray(grid, dtype=np.uint64).reshape(-1, 2).tobytes())
-                f.write(np.ascontiguousarray(ranges, dtype=np.uint64).tobytes())
-                if grid is not None and data is not None:
-                    f.write(data)
-        r = subprocess.run([str(exe), str(path)], capture_output=True, text=True, timeout=900, check=True)
-        os.unlink(path)
-        return [tuple(int(v) for v in line.split()) for line in r.stdout.splitlines()]
+        records = []
+        for grid, ranges, cap, data in cases:
+            flags = (1 if data is None else 0) | (2 if grid is None else 0)
+            records.append(struct.pack("<4Q", len(grid or ()), len(ranges), cap, flags))
+            if grid is not None:
+                records.append(np.asarray(grid, dtype=np.uint64).reshape(-1, 2).tobytes())
+            records.append(np.ascontiguousarray(ranges, dtype=np.uint64).tobytes())
+            if grid is not None and data is not None:
+                records.append(data)
+        return [tuple(int(v) for v in line.split()) for line in program(records)[0]]
     return run
 
 

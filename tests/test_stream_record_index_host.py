@@ -11,6 +11,7 @@ import pytest
 from minlz_amd import _lib
 from tests import record_index_model as IM
 from tests import search_host as H
+from tests.search_host import both
 
 SRC = "stream_record_index_check.cpp"
 SHIFTS = (0, 5, 15)
@@ -20,16 +21,7 @@ NEW_SYMBOLS = ["mlz_dev_reader_index_records", "mlz_dev_reader_record_count", "m
 
 @pytest.fixture(scope="module")
 def checkers(tmp_path_factory):
-    """The plain build, and the same program under AddressSanitizer and UBSan where this g++ links their runtimes."""
-    return H.build_checker(tmp_path_factory, SRC), H.build_checker(tmp_path_factory, SRC, sanitized=True)
-
-
-def both(checkers, records):
-    plain, san = checkers
-    lines = plain(records)[0]
-    if san is not None:
-        assert san(records)[0] == lines
-    return lines
+    return H.checkers(tmp_path_factory, SRC)
 
 
 def idx_case(data, delim, pos=(), shift=0):

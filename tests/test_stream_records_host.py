@@ -11,6 +11,7 @@ import pytest
 from minlz_amd import _lib
 from tests import records_model as RM
 from tests import search_host as H
+from tests.search_host import both
 
 SRC = "stream_records_check.cpp"
 BIG = 1 << 40
@@ -18,16 +19,7 @@ BIG = 1 << 40
 
 @pytest.fixture(scope="module")
 def checkers(tmp_path_factory):
-    """The plain build, and the same program under AddressSanitizer and UBSan where this g++ links their runtimes."""
-    return H.build_checker(tmp_path_factory, SRC), H.build_checker(tmp_path_factory, SRC, sanitized=True)
-
-
-def both(checkers, records):
-    plain, san = checkers
-    lines = plain(records)[0]
-    if san is not None:
-        assert san(records)[0] == lines
-    return lines
+    return H.checkers(tmp_path_factory, SRC)
 
 
 def rec_case(data, pat, delim, W, rec_cap=BIG, dst_cap=BIG, shift=0):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests import search_host as H
+from tests.search_host import both
 
 SRC = "stream_scratch_check.cpp"
 PIECE = 64 << 10
@@ -15,16 +16,7 @@ STORED, COMPRESSED, COMPRESSED_CRC = 1, 2, 3
 
 @pytest.fixture(scope="module")
 def checkers(tmp_path_factory):
-    """The plain build, and the same program under AddressSanitizer and UBSan where this g++ links their runtimes."""
-    return H.build_checker(tmp_path_factory, SRC), H.build_checker(tmp_path_factory, SRC, sanitized=True)
-
-
-def both(checkers, records):
-    plain, san = checkers
-    lines = plain(records)[0]
-    if san is not None:
-        assert san(records)[0] == lines
-    return lines
+    return H.checkers(tmp_path_factory, SRC)
 
 
 def staged(chunks, groups, pad=0, seed=1):
