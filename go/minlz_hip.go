@@ -278,6 +278,10 @@ func HIPDecodeStream(dst, src []byte, ignoreCRC bool) ([]byte, error) {
 	return dst[:n], nil
 }
 
+// SearchIgnoreCase is the flag of the searches over a stream in HBM (mlz_dev_reader_search, _search_many, _search_records,
+// _grep_records) that makes A .. Z equal a .. z, as grep -i does in the C locale; it combines with every other flag they take.
+const SearchIgnoreCase = uint32(C.MLZ_SEARCH_IGNORE_CASE)
+
 // LongPrefixTables configures block search tables of type 4 (SPEC_SEARCH.md 3.3.4; WriterSearchTable with WithLongPrefix / WithExtras):
 // every block indexes the Extras + 1 windows of MatchLen bytes behind each occurrence of Prefix (1 to 256 bytes).
 // MatchLen 0 is the reference's default 6; MatchLen + Extras is at most 16.

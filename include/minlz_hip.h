@@ -386,11 +386,24 @@ void mlz_dev_reader_close(mlz_dev_reader* reader);
  *   ones a block indexes, each in the block that holds the byte in front of it.  Without any such window the tables cannot serve the pattern: every data
  *   chunk is decoded and the third statistic is 0.  The split rule is the same over these windows, with j >= 0 when pattern[0] is no prefix byte.
  *   MLZ_SEARCH_NO_TABLES: every data chunk is decoded and scanned (cross-checks, the timing baseline).
+ *   MLZ_SEARCH_IGNORE_CASE (grep -i in the C locale; also taken by the three calls below, with every flag they take): with fold(b) = b | 0x20 for
+ *   0x41 <= b <= 0x5A and b otherwise — ASCII only: 0x40, 0x5B, 0x60, 0x7B and every byte >= 0x80 stay — the call returns what the call without the
+ *   flag returns for fold(decoded stream) and fold(pattern): positions, counts, pairs and their order, record numbers, kinds and totals.  Two
+ *   exceptions: the record bytes mlz_dev_reader_search_records packs are the stream's original bytes, and records are split at the delimiter's own
+ *   byte, which is never folded (so that call and mlz_dev_reader_grep_records return -MLZ_ERR_ARG for the flag with a delimiter that is an ASCII
+ *   letter, before anything is launched).  Patterns that become equal under folding count each for itself.  The pattern is folded once on the host,
+ *   the scan folds every data byte in a register, the stream and the scratch are never rewritten.  Plan under the flag: a table bit stands for a
+ *   window's exact bytes, so a window counts as present when the bit of ANY of its case variants is set; a window with more than 3 letters abstains
+ *   (present everywhere, no look-up); a pattern whose windows all abstain is not served (every chunk is decoded, as for pattern_len < M).  Types 2
+ *   and 3 use a window only when every case variant of the byte in front of it is a prefix byte; a type 4 prefix that holds a letter cannot serve a
+ *   folded pattern.  At most 2^22 variant hashes are made per call; a pattern beyond that is not served.  A pattern without ASCII letters gives
+ *   exactly the plan, stats and result of the call without the flag.
  *   stats (host, may be NULL) receives: data chunks of the stream, chunks decoded or copied, chunks with a usable table, 0.  mlz_get_counter 10 / 11
  *   report the second and third for the context's last search.
  *   Workspace: the decoded chunks go through the ReadSeeker's scratch in groups of about 64 MiB; one bit per decoded byte of the set marks the
  *   occurrences between the count pass and the write pass (part of mlz_get_counter 4). */
 #define MLZ_SEARCH_NO_TABLES 8u
+#define MLZ_SEARCH_IGNORE_CASE (1u << 5)   /* 32u */
 int64_t mlz_dev_reader_search(mlz_dev_reader* reader, void* stream, uint32_t flags, const uint8_t* pattern, size_t pattern_len, uint64_t* d_offsets, size_t cap,
                               uint64_t* stats /* host, may be NULL: 4 values */);
 
@@ -405,7 +418,8 @@ int64_t mlz_dev_reader_search(mlz_dev_reader* reader, void* stream, uint32_t fla
  *   of mlz_dev_reader_search on the same handle with the same flags: d_counts[i] is call i's return value and the pairs are the merge of the n_patterns
  *   position lists.  A table with a good CRC that lies (a cleared bit) may make the two differ: this call scans every chunk it decodes for every
  *   pattern, so it also reports occurrences of pattern i in chunks that only another pattern's tables admitted.
- *   Flags: MLZ_STREAM_IGNORE_CRC and MLZ_SEARCH_NO_TABLES as for mlz_dev_reader_search.
+ *   Flags: MLZ_STREAM_IGNORE_CRC, MLZ_SEARCH_NO_TABLES and MLZ_SEARCH_IGNORE_CASE as for mlz_dev_reader_search (under the last one the index key is taken
+ *   over folded bytes; patterns the letter cap or the hash budget leaves unserved count in stats[3]).
  *   -MLZ_ERR_ARG, each decided before anything is launched, nothing written: n_patterns > MLZ_SEARCH_MAX_PATTERNS; a length of 0 or above 256; NULL
  *   patterns or pattern_len with n_patterns > 0; d_offsets or d_which NULL with cap > 0; a device pointer that is not on the handle's device.
  *   n_patterns == 0 returns 0 and launches nothing.  Decode and CRC errors as for mlz_dev_reader_search: the first failing decoded chunk in stream order.
@@ -446,7 +460,8 @@ int64_t mlz_dev_reader_search_many(mlz_dev_reader* reader, void* stream, uint32_
  *   maximum; d_dst NULL with dst_cap > 0 or d_rec_off NULL with rec_cap > 0; one of d_dst (dst_cap > 0), d_rec_off (rec_cap > 0), d_rec_start
  *   (not NULL) and d_rec_flags (not NULL, rec_cap > 0) that is not on the handle's device.  Found later: more than 2^31 occurrences (-MLZ_ERR_ARG).
  *   Two phases under one lock.  The search phase is mlz_dev_reader_search's plan, decode and scan with the same pattern and flags
- *   (MLZ_STREAM_IGNORE_CRC, MLZ_SEARCH_NO_TABLES; an attached sidecar is used): stats and mlz_get_counter 10 / 11 describe it exactly as there.
+ *   (MLZ_STREAM_IGNORE_CRC, MLZ_SEARCH_NO_TABLES, MLZ_SEARCH_IGNORE_CASE — with the last one a delimiter that is an ASCII letter is -MLZ_ERR_ARG, and the
+ *   packed record bytes are the stream's original ones; an attached sidecar is used): stats and mlz_get_counter 10 / 11 describe it exactly as there.
  *   Zero occurrences returns 0 behind it and launches nothing more.  The read phase is mlz_dev_reader_read_device over the occurrences' windows,
  *   merged where they touch or overlap: every chunk a window touches is decoded once, with its CRC — also a chunk that the tables pruned in the
  *   search phase and a record reaches into; mlz_get_counter 7 / 8 / 9 describe it.  Kernels then find the bounds (a wavefront per occurrence),
@@ -526,7 +541,7 @@ int64_t mlz_dev_reader_record_range(mlz_dev_reader* reader, uint64_t first, uint
  *   is cut, there is no reach and no position list: a match goes from the scan kernel into one bit per record.
  *   Equivalence: for truthful tables, M is the set of mlz_dev_reader_record_numbers of the positions that mlz_dev_reader_search_many reports
  *   with the same patterns and flags.
- *   Flags: MLZ_STREAM_IGNORE_CRC, MLZ_SEARCH_NO_TABLES, MLZ_GREP_INVERT.
+ *   Flags: MLZ_STREAM_IGNORE_CRC, MLZ_SEARCH_NO_TABLES, MLZ_GREP_INVERT, MLZ_SEARCH_IGNORE_CASE (-MLZ_ERR_ARG when the index was built on an ASCII letter).
  *   -MLZ_ERR_ARG, each decided before anything is launched, nothing written: a handle without an index; the argument errors of
  *   mlz_dev_reader_search_many (n_patterns, the lengths, NULL patterns); a pattern that contains the index's delimiter (as
  *   mlz_dev_reader_search_records decides it); d_rec_no NULL with rec_cap > 0; d_rec_no or d_rec_kind (not NULL), with rec_cap > 0, that is not
@@ -539,7 +554,7 @@ int64_t mlz_dev_reader_record_range(mlz_dev_reader* reader, uint64_t first, uint
  *   the sizes of before / after) and compact.  32 bytes visit the host, behind the search phase's own; nothing per record or per occurrence does.
  *   Synchronous; `stream` as for mlz_dev_reader_read.  Workspace, grow-only and part of mlz_get_counter 4: 16 bytes per 32 records (two
  *   bitmaps and two scan arrays) beside the search phase's.
- *   Out of scope: regular expressions and case folding; per-record lists of which pattern matched; delimiters of more than one byte; grep over
+ *   Out of scope: regular expressions; Unicode or locale folding; per-record lists of which pattern matched; delimiters of more than one byte; grep over
  *   batches of streams; a call that works without a record index (mlz_dev_reader_search_records remains the bounded-reach form for that). */
 #define MLZ_GREP_INVERT 16u
 int64_t mlz_dev_reader_grep_records(mlz_dev_reader* reader, void* stream, uint32_t flags,

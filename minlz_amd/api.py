@@ -14,6 +14,7 @@ MaxBlockSize = 8 << 20  # minlz.go:84
 ERR_CORRUPT, ERR_TOO_LARGE, ERR_UNSUPPORTED, ERR_INVALID_LEVEL, ERR_CRC, ERR_DST_TOO_SMALL, ERR_HIP, ERR_ARG = 1, 2, 3, 4, 5, 6, 7, 8
 
 STREAM_ADD_INDEX, STREAM_IGNORE_CRC, STREAM_SEARCH_TABLES, SEARCH_NO_TABLES, GREP_INVERT = 1, 2, 4, 8, 16
+IGNORE_CASE = 32                  # MLZ_SEARCH_IGNORE_CASE: the searches' ignore_case=True
 SEARCH_MAX_PATTERNS = 4096
 
 OPT_DECODE_ALGO, OPT_ENCODE_FAR, OPT_DEBUG_STATUS, OPT_PROFILE, OPT_PROFILE_READ, OPT_TILE_TIMELINE_READ, OPT_GENERAL_ALGO = 1, 2, 3, 4, 5, 7, 8
@@ -85,8 +86,9 @@ def _raise(code, ctx=None):
 
 # ---- argument marshalling, each form once ----
 
-def _flags(add_index=False, ignore_crc=False, no_tables=False, invert=False):
-    return (STREAM_ADD_INDEX if add_index else 0) | (STREAM_IGNORE_CRC if ignore_crc else 0) | (SEARCH_NO_TABLES if no_tables else 0) | (GREP_INVERT if invert else 0)
+def _flags(add_index=False, ignore_crc=False, no_tables=False, invert=False, ignore_case=False):
+    return ((STREAM_ADD_INDEX if add_index else 0) | (STREAM_IGNORE_CRC if ignore_crc else 0) | (SEARCH_NO_TABLES if no_tables else 0) | (GREP_INVERT if invert else 0) |
+            (IGNORE_CASE if ignore_case else 0))
 
 
 def _patterns(patterns):
@@ -324,38 +326,43 @@ class DeviceReader:
         total.  -> the sum of the lengths."""
         return self._call("mlz_dev_reader_read_device", stream, _flags(ignore_crc=ignore_crc), d_off, d_len, n, d_dst, dst_cap, d_starts)
 
-    def search(self, pattern, d_offsets, cap, ignore_crc=False, no_tables=False, stream=None):
+    def search(self, pattern, d_offsets, cap, ignore_crc=False, no_tables=False, stream=None, ignore_case=False):
         """mlz_dev_reader_search.  pattern: 1 .. 256 bytes; d_offsets: device address of room for `cap` uint64 (None with cap == 0), which
         receives the smallest min(total, cap) positions of the pattern in the decoded stream, ascending.
         Uses the stream's block search tables of type 1, 2, 3 or 4 (with a prefix table: the pattern's windows that follow a prefix byte; a
         pattern without one is served by decoding every chunk, and the usable-table count is then 0).
+        ignore_case (here and in the three calls below): grep -i in the C locale — the result is that of the call on the stream and the
+        pattern with A .. Z folded to a .. z; the stream is not changed.  Windows of the pattern with more than three letters cannot be
+        pruned by the tables.
         -> (total, (data chunks, chunks decoded or copied, chunks with a usable search table))."""
         p, stats = bytes(pattern), _stats()
-        r = self._call("mlz_dev_reader_search", stream, _flags(ignore_crc=ignore_crc, no_tables=no_tables), p, len(p), d_offsets, cap, stats)
+        r = self._call("mlz_dev_reader_search", stream, _flags(ignore_crc=ignore_crc, no_tables=no_tables, ignore_case=ignore_case), p, len(p), d_offsets, cap, stats)
         return r, _ints(stats, 3)
 
-    def search_many(self, patterns, d_counts, d_offsets, d_which, cap, ignore_crc=False, no_tables=False, stream=None):
+    def search_many(self, patterns, d_counts, d_offsets, d_which, cap, ignore_crc=False, no_tables=False, stream=None, ignore_case=False):
         """mlz_dev_reader_search_many.  patterns: a sequence of up to 4096 bytes objects of 1 .. 256 bytes; d_counts: device address of room
         for len(patterns) uint64 (or None), which receives every pattern's number of occurrences; d_offsets, d_which: device addresses of
         room for `cap` uint64 and `cap` uint32 (None with cap == 0), which receive the smallest min(total, cap) pairs (position, pattern
         index) in ascending order.  The chunks that any pattern's tables admit are decoded once and scanned once for all patterns.
         -> (total pairs, (data chunks, chunks decoded or copied, chunks with a usable search table, patterns the tables could not serve))."""
         stats = _stats()
-        r = self._call("mlz_dev_reader_search_many", stream, _flags(ignore_crc=ignore_crc, no_tables=no_tables), *_patterns(patterns), d_counts, d_offsets, d_which, cap, stats)
+        r = self._call("mlz_dev_reader_search_many", stream, _flags(ignore_crc=ignore_crc, no_tables=no_tables, ignore_case=ignore_case), *_patterns(patterns), d_counts, d_offsets, d_which, cap, stats)
         return r, _ints(stats)
 
-    def search_records(self, pattern, delimiter, d_dst, dst_cap, d_rec_off, d_rec_start, d_rec_flags, rec_cap, max_reach=0, ignore_crc=False, no_tables=False, stream=None):
+    def search_records(self, pattern, delimiter, d_dst, dst_cap, d_rec_off, d_rec_start, d_rec_flags, rec_cap, max_reach=0, ignore_crc=False, no_tables=False, stream=None,
+                       ignore_case=False):
         """mlz_dev_reader_search_records: the records (maximal runs without the byte `delimiter`) that hold `pattern` (1 .. 256 bytes without
         the delimiter), each once, in stream order.  d_dst: device address of room for dst_cap bytes (None with dst_cap == 0), which
         receives the first k records' bytes, packed; d_rec_off: room for rec_cap uint64 (None with rec_cap == 0), each record's start in
         the decoded stream; d_rec_start: room for rec_cap + 1 uint64 or None, each record's start in d_dst and the bytes written;
         d_rec_flags: room for rec_cap bytes or None, bit 0 = cut left, bit 1 = cut right.  k: the most records that both caps hold whole.
         max_reach: how far the call looks to either side of an occurrence (0 = 65536, at most 2^20); longer records come out cut.
+        ignore_case: the records come out with their original bytes; a delimiter that is an ASCII letter raises.
         -> (records, (records, bytes of all records, occurrences, records with a flag), (data chunks, chunks decoded or copied by the
         search phase, chunks with a usable search table))."""
         self._open()
         p, totals, stats = bytes(pattern), _stats(), _stats()
-        r = self._call("mlz_dev_reader_search_records", stream, _flags(ignore_crc=ignore_crc, no_tables=no_tables), p, len(p), _delimiter(delimiter, "search_records"),
+        r = self._call("mlz_dev_reader_search_records", stream, _flags(ignore_crc=ignore_crc, no_tables=no_tables, ignore_case=ignore_case), p, len(p), _delimiter(delimiter, "search_records"),
                        max_reach, d_dst, dst_cap, d_rec_off, d_rec_start, d_rec_flags, rec_cap, totals, stats)
         return r, _ints(totals), _ints(stats, 3)
 
@@ -393,16 +400,17 @@ class DeviceReader:
         beyond the size).  -> how many positions lie inside the stream."""
         return self._call("mlz_dev_reader_record_numbers", stream, d_pos, n, d_no)
 
-    def grep_records(self, patterns, d_rec_no, d_rec_kind, rec_cap, invert=False, before=0, after=0, ignore_crc=False, no_tables=False, stream=None):
+    def grep_records(self, patterns, d_rec_no, d_rec_kind, rec_cap, invert=False, before=0, after=0, ignore_crc=False, no_tables=False, stream=None, ignore_case=False):
         """mlz_dev_reader_grep_records: grep over the record index.  patterns: a sequence of up to 4096 bytes objects of 1 .. 256 bytes
         without the index's delimiter (none: nothing matches, and under invert every record is selected); a record is selected when it
         holds one of them, with invert when it holds none; before, after: context records in front of and behind every selected one.
+        ignore_case: grep -i; an index built on an ASCII letter raises.
         d_rec_no: device address of room for rec_cap uint64 (None with rec_cap == 0), which receives the smallest min(R, rec_cap) numbers
         of the selected and context records, ascending; d_rec_kind: room for rec_cap bytes or None, 1 = selected, 0 = context only.
         -> (R, (R, selected records, bytes of the written records: read_records' dst_cap, bytes of all R records), (data chunks, chunks
         decoded or copied, chunks with a usable search table, patterns the tables could not serve))."""
         totals, stats = _stats(), _stats()
-        r = self._call("mlz_dev_reader_grep_records", stream, _flags(ignore_crc=ignore_crc, no_tables=no_tables, invert=invert), *_patterns(patterns), before, after,
+        r = self._call("mlz_dev_reader_grep_records", stream, _flags(ignore_crc=ignore_crc, no_tables=no_tables, invert=invert, ignore_case=ignore_case), *_patterns(patterns), before, after,
                        d_rec_no, d_rec_kind, rec_cap, totals, stats)
         return r, _ints(totals), _ints(stats)
 

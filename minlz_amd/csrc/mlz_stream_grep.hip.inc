@@ -85,7 +85,9 @@ int64_t dev_reader_grep_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flag
                                const GrepOut& out, uint64_t* totals, uint64_t* stats) {
     mlz_ctx* c = rd->ctx;
     const size_t nck = rd->chunks.size();
-    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0;
+    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0, fold = (flags & MLZ_SEARCH_IGNORE_CASE) != 0;
+    std::vector<uint8_t> keep;
+    patterns = search_many_folded(flags, patterns, pattern_len, n, &keep);
     search_begin(rd, stats);
     if (totals) totals[0] = totals[1] = totals[2] = totals[3] = 0;
     HIPCHK(c, hipSetDevice(c->device));
@@ -129,7 +131,7 @@ int64_t dev_reader_grep_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flag
         const int e = up.send(c, sm, index, patterns, n);
         if (e) return e;
         const int64_t r = search_decode_run(rd, sm, ignore_crc, &sd, [&](size_t, size_t t0, size_t t1) {
-            hipLaunchKernelGGL(mlz::search_many_kernel<mlz::kSearchManyMarkRecords>, dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), up.lds_bytes, sm, c->d_range.as<uint8_t>(), d_tiles,
+            hipLaunchKernelGGL(search_many_kernel_of<mlz::kSearchManyMarkRecords>(fold), dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), up.lds_bytes, sm, c->d_range.as<uint8_t>(), d_tiles,
                                uint32_t(t0), up.ix, static_cast<uint32_t*>(nullptr), static_cast<unsigned long long*>(nullptr), static_cast<const uint64_t*>(nullptr), uint64_t(0),
                                static_cast<uint64_t*>(nullptr), static_cast<uint32_t*>(nullptr), mk);
             return 0;
@@ -166,6 +168,7 @@ extern "C" int64_t mlz_dev_reader_grep_records(mlz_dev_reader* rd, void* stream,
     std::lock_guard<std::mutex> lk(c->mu);
     if (!rd->index_ready || rd->index_n >= mlz::kGrepMaxRecords) return -MLZ_ERR_ARG;
     if (blob && std::memchr(patterns, rd->index_delim, blob)) return -MLZ_ERR_ARG;   // a line search cannot match across lines
+    if ((flags & MLZ_SEARCH_IGNORE_CASE) && mlz::search_is_letter(rd->index_delim)) return -MLZ_ERR_ARG;   // records are split at the delimiter's own byte, which is never folded
     if (enter_device(c)) return -MLZ_ERR_HIP;
     if (rec_cap && (!on_device(c, d_rec_no) || (d_rec_kind && !on_device(c, d_rec_kind)))) return -MLZ_ERR_ARG;
     begin_decode_call(c);

@@ -297,6 +297,7 @@ extern "C" int64_t mlz_dev_reader_search_records(mlz_dev_reader* rd, void* strea
     if (!rd || !pattern || pattern_len == 0 || pattern_len > mlz::kSearchMaxPattern || max_reach > MLZ_RECORDS_MAX_REACH || (!d_dst && dst_cap) || (!d_rec_off && rec_cap))
         return -MLZ_ERR_ARG;
     if (std::memchr(pattern, delimiter, pattern_len)) return -MLZ_ERR_ARG;   // a line search cannot match across lines
+    if ((flags & MLZ_SEARCH_IGNORE_CASE) && mlz::search_is_letter(delimiter)) return -MLZ_ERR_ARG;   // records are split at the delimiter's own byte, which is never folded
     mlz_ctx* c = rd->ctx;
     std::lock_guard<std::mutex> lk(c->mu);
     if (enter_device(c)) return -MLZ_ERR_HIP;

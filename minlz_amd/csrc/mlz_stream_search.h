@@ -6,6 +6,8 @@
 // scratch (search_layout, for patterns of lengths lmin .. lmax); the search for many adds the pattern index and the scan rule of one tile.
 // The sidecar section adds what a stream of tables for ANOTHER stream needs: the remote reference chunk (0x47) written and parsed, the
 // check of a reference against the main stream's chunks, and the rule over several table sets (search_decoded_mark_all).
+// The case-folding section adds what MLZ_SEARCH_IGNORE_CASE needs: the byte and the dword fold, and the plan rule over the windows' case variants
+// (search_windows_fold, search_pattern_hashes_fold, search_probe_fold; tools/stream_search_fold_check.cpp).
 // Plain C++: compiles for the host alone and for gfx950.  Table types 1 (no prefix), 2 (1 to 8 prefix byte values), 3 (a 256-bit mask of
 // prefix byte values; SPEC_SEARCH.md 3.3) and 4 (a long prefix of 1 to 256 bytes with extra matches; 3.3.4), uncompressed table chunks (0x45) only.
 #pragma once
@@ -105,14 +107,20 @@ MLZ_SEARCH_HD uint32_t search_overlap(uint32_t T, uint32_t M, const uint8_t* fie
     return T == 1 ? M - 1 : T == 4 ? search_long_k(field) - 1 + M + search_long_e(field) : M;
 }
 
+// An ASCII letter: the bytes that have a case variant
+MLZ_SEARCH_HD bool search_is_letter(uint8_t b) { return (uint32_t(b | 0x20u) - 0x61u) < 26u; }
+
 // The pattern's windows that the tables can answer for, in groups of *gsize windows that one block's table holds together, and t_min.
 // w[g * gsize + j] = where window j of group g starts in the pattern, groups ascending; room for kSearchMaxWindows values (L for types
 // 1 .. 3).  Returns the number of groups; 0 = the tables cannot serve this pattern.
 // Type 1: every window 0 .. L - M is a group of one, t_min = 1.  Types 2 and 3: the windows 1 <= i <= L - M behind a prefix byte P[i - 1],
 // groups of one; t_min = 1 when P[0] is a prefix byte, else 0.  Type 4: a group per prefix occurrence P[i, i + K) == pfx with
 // i + K + M + E <= L, its E + 1 windows start at i + K + j; t_min = 1 when the first group has i = 0, else 0.
+// fold (MLZ_SEARCH_IGNORE_CASE; the rule's reasons stand in the case-folding section below): types 2 and 3 take window i, and t_min = 1, only when
+// EVERY case variant of the byte in front is a prefix byte; type 4 has no group when the prefix holds a letter.  pat may be folded or not.
+// A pattern without letters gets the same windows either way.
 MLZ_SEARCH_HD uint32_t search_windows(const uint8_t* pat, uint32_t L, uint32_t T, uint32_t M, const uint8_t* field, uint32_t* w, uint32_t* t_min,
-                                      uint32_t* gsize = nullptr) {
+                                      uint32_t* gsize = nullptr, bool fold = false) {
     *t_min = 1;
     if (gsize) *gsize = 1;
     if (L < M) return 0;
@@ -123,6 +131,7 @@ MLZ_SEARCH_HD uint32_t search_windows(const uint8_t* pat, uint32_t L, uint32_t T
         const uint8_t* pfx = search_long_prefix(field);
         if (gsize) *gsize = gs;
         *t_min = 0;
+        if (fold) for (uint32_t j = 0; j < K; j++) if (search_is_letter(pfx[j])) return 0;
         for (uint32_t i = 0; i + K + M + E <= L; i++) {
             uint32_t j = 0;
             while (j < K && pat[i + j] == pfx[j]) j++;
@@ -135,8 +144,12 @@ MLZ_SEARCH_HD uint32_t search_windows(const uint8_t* pat, uint32_t L, uint32_t T
     }
     uint32_t mask[8];
     search_prefix_mask(T, field, mask);
-    *t_min = search_is_prefix(mask, pat[0]) ? 1 : 0;
-    for (uint32_t i = 1; i + M <= L; i++) if (search_is_prefix(mask, pat[i - 1])) w[nw++] = i;
+    auto prefix = [&](uint8_t b) {   // b is a prefix byte; under folding: every case variant of b is one
+        if (!fold || !search_is_letter(b)) return search_is_prefix(mask, b);
+        return search_is_prefix(mask, uint8_t(b | 0x20u)) && search_is_prefix(mask, uint8_t(b & ~0x20u));
+    };
+    *t_min = prefix(pat[0]) ? 1 : 0;
+    for (uint32_t i = 1; i + M <= L; i++) if (prefix(pat[i - 1])) w[nw++] = i;
     return nw;
 }
 
@@ -168,6 +181,96 @@ MLZ_SEARCH_HD void search_probe(const uint8_t* table, uint32_t bits, const uint3
         for (uint32_t j = 0; j < gsize; j++) {
             const uint32_t x = h[g * gsize + j] & mask;
             if (!((table[x >> 3] >> (x & 7)) & 1)) return false;
+        }
+        return true;
+    };
+    uint32_t lead = 0, trail = 0;
+    while (lead < nw && has(lead)) lead++;
+    if (lead == nw) { *a = *s = nw; return; }
+    while (trail < nw && has(nw - 1 - trail)) trail++;
+    *a = lead; *s = trail;
+}
+
+// ---- case folding (MLZ_SEARCH_IGNORE_CASE: grep -i in the C locale) ----
+// fold(b) = b | 0x20 for 0x41 <= b <= 0x5A ('A' .. 'Z'), b otherwise.  The patterns are folded once on the host; the scans fold every data
+// byte in registers on its way into a comparison (the scratch keeps the stream's bytes).
+MLZ_SEARCH_HD uint8_t search_fold(uint8_t b) { return uint8_t(b | ((uint32_t(b) - 0x41u < 26u) ? 0x20u : 0u)); }
+// Four bytes at once, no carry between them: with y = the low 7 bits of every byte, bit 7 of y + 0x3f is set for y >= 0x41 and bit 7 of
+// y + 0x25 for y >= 0x5b (both sums stay below 0x100 per byte); a byte with its own bit 7 set is no letter.  The 0x80 marks, shifted to 0x20.
+MLZ_SEARCH_HD uint32_t search_fold4(uint32_t x) {
+    const uint32_t y = x & 0x7f7f7f7fu;
+    const uint32_t m = ((y + 0x3f3f3f3fu) & ~(y + 0x25252525u) & ~x & 0x80808080u) >> 2;
+    return x | m;
+}
+
+// The plan under folding.  A table bit stands for the exact bytes of a window, so a window of the folded pattern is PRESENT in a table when
+// the bit of ANY of its case variants is set (the 2^k strings that differ in the case of its k letters).  search_candidate and
+// search_chunk_candidate are monotone in presence, so whatever errs towards "present" keeps a verdict a necessary condition:
+//   a window with more than kSearchFoldMaxLetters letters ABSTAINS: present in every table, no hashes (at a table population of 10 %, one of
+//   2^k variants is present by chance with probability 1 - 0.9^(2^k): 0.57 for k = 3, 0.998 for k = 6: such a window proves nothing);
+//   types 2 and 3: window i is one the tables answer for only when EVERY case variant of P[i - 1] is a prefix byte (the data may hold
+//   either case in front of the window, and only a prefix byte makes a block index it); t_min = 1 only when every variant of P[0] is one;
+//   type 4: a group at i exists only when P[i, i + K) equals the prefix byte for byte and the prefix holds no letter (the data may hold the
+//   prefix in another case, which no block indexes).
+// A pattern whose windows all abstain is not served.  The variant hashes lie CSR-wise: voff[w] .. voff[w + 1] are window w's in hs
+// (none: the window abstains); a pattern's record (SearchManyPat) has h_off = where its nw * gsize + 1 offsets start in voff.
+constexpr uint32_t kSearchFoldMaxLetters = 3, kSearchFoldMaxHashes = 1u << 22;
+
+// search_windows for a search that folds: the one window rule with its fold parameter set
+MLZ_SEARCH_HD uint32_t search_windows_fold(const uint8_t* pat, uint32_t L, uint32_t T, uint32_t M, const uint8_t* field, uint32_t* w, uint32_t* t_min,
+                                           uint32_t* gsize = nullptr) {
+    return search_windows(pat, L, T, M, field, w, t_min, gsize, true);
+}
+
+// search_pattern_hashes for a search that folds: per window one offset appended to *voff (and one behind the last) and its variant hashes to
+// *hs — variant v of a window with k <= kSearchFoldMaxLetters letters has its j-th letter in upper case where bit j of v is set, v = 0 .. 2^k - 1.
+// False, and nothing appended: the tables cannot serve the pattern (no window, or every window abstains), or its hashes do not fit into
+// `budget` (what is left of kSearchFoldMaxHashes: *over = true then).
+inline bool search_pattern_hashes_fold(const uint8_t* pat, uint32_t L, uint32_t T, uint32_t M, uint32_t B, const uint8_t* field, uint32_t* win, std::vector<uint32_t>* voff,
+                                       std::vector<uint32_t>* hs, SearchManyPat* out, uint32_t budget = kSearchFoldMaxHashes, bool* over = nullptr) {
+    uint32_t t_min = 1, gsize = 1;
+    if (over) *over = false;
+    const uint32_t nw = search_windows_fold(pat, L, T, M, field, win, &t_min, &gsize);
+    if (!nw) return false;
+    const size_t v0 = voff->size(), h0 = hs->size();
+    auto undo = [&]() { voff->resize(v0); hs->resize(h0); return false; };
+    for (uint32_t w = 0; w < nw * gsize; w++) {
+        voff->push_back(uint32_t(hs->size()));
+        uint32_t k = 0, at[kSearchFoldMaxLetters];
+        uint64_t v = 0;
+        for (uint32_t j = 0; j < M; j++) {
+            const uint8_t b = search_fold(pat[win[w] + j]);
+            if (search_is_letter(b)) { if (k < kSearchFoldMaxLetters) at[k] = j; k++; }
+            v |= uint64_t(b) << (8 * j);
+        }
+        if (k > kSearchFoldMaxLetters) continue;   // (abstains)
+        if (hs->size() - h0 + (size_t(1) << k) > budget) { if (over) *over = true; return undo(); }
+        for (uint32_t var = 0; var < (1u << k); var++) {
+            uint64_t x = v;
+            for (uint32_t j = 0; j < k; j++) if ((var >> j) & 1) x &= ~(uint64_t(0x20) << (8 * at[j]));
+            hs->push_back(search_hash(x, B, M));
+        }
+    }
+    if (hs->size() == h0) return undo();
+    voff->push_back(uint32_t(hs->size()));
+    *out = SearchManyPat{uint32_t(v0), nw, gsize, t_min, L, 0};
+    return true;
+}
+
+// search_probe under folding: voff = the pattern's nw * gsize + 1 offsets into hs.  A window is present when it abstains or one of its
+// variants' bits is set; a group when all its windows are.
+MLZ_SEARCH_HD void search_probe_fold(const uint8_t* table, uint32_t bits, const uint32_t* voff, const uint32_t* hs, uint32_t nw, uint32_t* a, uint32_t* s, uint32_t gsize = 1) {
+    const uint32_t mask = (1u << bits) - 1;
+    auto has = [&](uint32_t g) {
+        for (uint32_t j = 0; j < gsize; j++) {
+            uint32_t e = voff[g * gsize + j];
+            const uint32_t e1 = voff[g * gsize + j + 1];
+            if (e == e1) continue;
+            for (; e < e1; e++) {
+                const uint32_t x = hs[e] & mask;
+                if ((table[x >> 3] >> (x & 7)) & 1) break;
+            }
+            if (e == e1) return false;
         }
         return true;
     };
@@ -350,17 +453,20 @@ inline void search_many_index(const uint8_t* blob, const uint32_t* len, size_t n
 
 // The scan and write rule of one tile, as search_many_kernel applies it (and as the host check restates it with plain loops): the byte at
 // tile position i is s[i]; emit(i, pattern) is called for every pair the tile examines, positions ascending, patterns in bucket order.
+// fold (MLZ_SEARCH_IGNORE_CASE): the blob and the index are those of the FOLDED patterns (search_fold over every byte, then search_many_index:
+// the key is taken over folded pattern bytes), and every data byte is folded on its way into the key and into the comparison.
 template <class Emit>
-inline void search_many_tile_pairs(const uint8_t* s, const SearchTile& t, const SearchManyIndex& ix, const uint8_t* blob, Emit emit) {
+inline void search_many_tile_pairs(const uint8_t* s, const SearchTile& t, const SearchManyIndex& ix, const uint8_t* blob, Emit emit, bool fold = false) {
+    auto at = [&](uint32_t i) { return fold ? search_fold(s[i]) : s[i]; };
     for (uint32_t i = 0; i < t.count; i++) {
         uint32_t v = 0;
-        for (uint32_t j = 0; j < ix.m; j++) v |= uint32_t(s[i + j]) << (8 * j);
+        for (uint32_t j = 0; j < ix.m; j++) v |= uint32_t(at(i + j)) << (8 * j);
         const uint32_t h = search_many_key(v, ix.m, ix.hb);
         for (uint32_t e = ix.heads[h]; e < ix.heads[h + 1]; e++) {
             const uint32_t p = ix.order[e], L = ix.off[p + 1] - ix.off[p];
             if (i + L > t.hi_end) continue;
             uint32_t j = 0;
-            while (j < L && s[i + j] == blob[ix.off[p] + j]) j++;
+            while (j < L && at(i + j) == blob[ix.off[p] + j]) j++;
             if (j == L) emit(i, p);
         }
     }

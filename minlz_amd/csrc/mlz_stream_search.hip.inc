@@ -14,6 +14,8 @@
 // run in a bitmap (one bit per decoded byte of the set) and counts them per tile.  search_prefix_kernel's scan over the tile counts and search_write_kernel then
 // put the smallest `cap` positions out in ascending order.  The call's body ends at the prefix kernel (dev_reader_search_scan_locked); the write and
 // the total's way home are steps of their own, so that the search for records (mlz_stream_records.hip.inc) can size its buffer by the total first.
+// MLZ_SEARCH_IGNORE_CASE: the pattern is folded once on the host, the plan probes the windows' case variants (search_plan_kernel<true>) and the scan folds
+// every data byte in a register (search_scan_kernel<true>); the <false> instantiations are the code without the flag.
 
 namespace mlz {
 
@@ -75,12 +77,15 @@ __global__ __launch_bounds__(64) void search_locate_kernel(const uint8_t* __rest
 // pattern p as set c sees it (nw = 0: the set cannot serve the pattern; L is set in every record).
 // ov[c]: search_chunk_candidate's ov, a sidecar set's overlap (0 for inline tables).
 struct SearchPlanSets { uint32_t n, B[kSidecarMaxConfigs], ov[kSidecarMaxConfigs]; };
+// kFold (MLZ_SEARCH_IGNORE_CASE): a pattern's h_off names its window offsets in voff, which name the windows' variant hashes in `hashes`
+// (search_pattern_hashes_fold); a lane loops over a window's variants until one bit is set (search_probe_fold).  Without it voff is not read.
 // One lane per (data chunk, pattern): every set's verdict on the chunk (search_chunk_candidate over the probes of its table and the next
 // chunk's), their conjunction, and the marking (search_decoded_mark_all) ORed into take[].  A lane loops over the sets: there are four at the
 // most, and the conjunction wants all votes of a (chunk, pattern) in one place.
+template <bool kFold>
 __global__ __launch_bounds__(256) void search_plan_kernel(const uint8_t* __restrict__ base, const SearchTab* __restrict__ tabs, const uint64_t* __restrict__ n_of, uint32_t nck,
-                                                          SearchPlanSets sets, const uint32_t* __restrict__ hashes, const SearchManyPat* __restrict__ pats, uint32_t np,
-                                                          uint8_t* __restrict__ take) {
+                                                          SearchPlanSets sets, const uint32_t* __restrict__ hashes, const uint32_t* __restrict__ voff,
+                                                          const SearchManyPat* __restrict__ pats, uint32_t np, uint8_t* __restrict__ take) {
     const uint64_t idx = uint64_t(blockIdx.x) * 256 + threadIdx.x;
     if (idx >= uint64_t(nck) * np) return;
     const uint32_t k = uint32_t(idx % nck);
@@ -93,7 +98,10 @@ __global__ __launch_bounds__(256) void search_plan_kernel(const uint8_t* __restr
         auto probe = [&](size_t j, bool lead) {
             const SearchTab t = tabs[size_t(c) * nck + j];
             uint32_t a = pt.nw, s = pt.nw;
-            if (t.R != kSearchNoTable) search_probe(base + t.off, sets.B[c] - t.R, h, pt.nw, &a, &s, pt.gsize);
+            if (t.R != kSearchNoTable) {
+                if (kFold) search_probe_fold(base + t.off, sets.B[c] - t.R, voff + pt.h_off, hashes, pt.nw, &a, &s, pt.gsize);
+                else search_probe(base + t.off, sets.B[c] - t.R, h, pt.nw, &a, &s, pt.gsize);
+            }
             return lead ? a : s;
         };
         return search_chunk_candidate(k, nck, [&](size_t j) { return probe(j, true); }, [&](size_t j) { return probe(j, false); }, sizes, pt.nw, pt.L, pt.t_min, sets.ov[c]);
@@ -102,6 +110,8 @@ __global__ __launch_bounds__(256) void search_plan_kernel(const uint8_t* __restr
 }
 
 // One workgroup per tile: bit i of the tile's bitmap = "the pattern starts at the tile's position i"; counts[tile] = the set bits.
+// kFold (MLZ_SEARCH_IGNORE_CASE): pat is folded, and every byte of the scratch is folded in a register on its way into a comparison.
+template <bool kFold>
 __global__ __launch_bounds__(256) void search_scan_kernel(const uint8_t* __restrict__ scratch, const SearchTile* __restrict__ tiles, uint32_t tile0,
                                                           const uint8_t* __restrict__ pat, uint32_t L, uint64_t* __restrict__ masks, uint32_t* __restrict__ counts) {
     __shared__ uint8_t sp[kSearchMaxPattern];
@@ -113,13 +123,14 @@ __global__ __launch_bounds__(256) void search_scan_kernel(const uint8_t* __restr
     const uint8_t* s = scratch + t.src_off;
     uint64_t* m = masks + size_t(tile) * kSearchTileWords;
     const uint8_t p0 = sp[0];
+    auto at = [&](uint32_t i) { return kFold ? search_fold(s[i]) : s[i]; };
     uint32_t cnt = 0;
     for (uint32_t it = 0; it < kSearchTile / 256; it++) {
         const uint32_t i = it * 256 + tid;
         bool hit = false;
-        if (i < t.count && s[i] == p0) {
+        if (i < t.count && at(i) == p0) {
             uint32_t j = 1;
-            while (j < L && s[i + j] == sp[j]) j++;
+            while (j < L && at(i + j) == sp[j]) j++;
             hit = j == L;
         }
         const uint64_t b = __ballot(hit);
@@ -232,11 +243,13 @@ int64_t dev_reader_search_sets(mlz_dev_reader* rd, hipStream_t sm, bool ignore_c
 // context's counter 11 (the chunks with a usable table of at least one set that serves a pattern).  off[i]: pattern i's bytes in `patterns`.
 // The host hashes every pattern's windows for every set (search_pattern_hashes); search_plan_kernel marks the set and one byte per chunk
 // comes back.  A pattern that is not served puts every chunk with a byte into the set, so the kernel is not run then.
+// Under MLZ_SEARCH_IGNORE_CASE `patterns` are the FOLDED patterns, and the hashes are those of the windows' case variants
+// (search_pattern_hashes_fold, at most kSearchFoldMaxHashes in a call: a pattern that does not fit is not served).
 int64_t dev_reader_search_plan(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* patterns, const std::vector<uint32_t>& off, size_t n,
                                std::vector<uint8_t>* take, size_t* n_take, uint64_t* stats, bool many) {
     mlz_ctx* c = rd->ctx;
     const size_t nck = rd->chunks.size();
-    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0;
+    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0, fold = (flags & MLZ_SEARCH_IGNORE_CASE) != 0;
     uint64_t unserved = n;
     auto planned = [&]() {   // what every caller reports: counter 10, stats[1 .. 2] and, for many patterns, stats[3]
         c->search_chunks = *n_take;
@@ -258,18 +271,34 @@ int64_t dev_reader_search_plan(mlz_dev_reader* rd, hipStream_t sm, uint32_t flag
             return u;
         };
         if (st.ncfg && usable_of((1u << st.ncfg) - 1)) {
-            std::vector<uint32_t> win(mlz::kSearchMaxWindows), hs;
+            std::vector<uint32_t> win(mlz::kSearchMaxWindows), hs, voff;
             std::vector<mlz::SearchManyPat> pats(n * st.ncfg);
             uint32_t serving = 0;
             size_t served = 0;
             for (size_t i = 0; i < n; i++) {
                 bool any = false;
+                uint32_t mine = 0;   // the sets that serve pattern i
+                const size_t h0 = hs.size(), v0 = voff.size();
                 for (uint32_t s = 0; s < st.ncfg; s++) {
                     const mlz::SearchConfig& cf = st.cfg[s];
                     mlz::SearchManyPat& pt = pats[i * st.ncfg + s];
                     pt = mlz::SearchManyPat{0, 0, 1, 1, off[i + 1] - off[i], 0};
-                    if (mlz::search_pattern_hashes(patterns + off[i], off[i + 1] - off[i], cf.T, cf.M, cf.B, cf.field, win.data(), &hs, &pt)) { any = true; serving |= 1u << s; }
+                    if (!fold) {
+                        if (mlz::search_pattern_hashes(patterns + off[i], off[i + 1] - off[i], cf.T, cf.M, cf.B, cf.field, win.data(), &hs, &pt)) { any = true; mine |= 1u << s; }
+                        continue;
+                    }
+                    // under folding the call's variant hashes have a budget; a pattern that does not fit entirely, over all sets, is not served
+                    bool over = false;
+                    if (mlz::search_pattern_hashes_fold(patterns + off[i], off[i + 1] - off[i], cf.T, cf.M, cf.B, cf.field, win.data(), &voff, &hs, &pt,
+                                                        uint32_t(mlz::kSearchFoldMaxHashes - hs.size()), &over)) { any = true; mine |= 1u << s; }
+                    else if (over) {
+                        for (uint32_t b = 0; b < st.ncfg; b++) pats[i * st.ncfg + b] = mlz::SearchManyPat{0, 0, 1, 1, off[i + 1] - off[i], 0};   // (L is set in every record)
+                        hs.resize(h0); voff.resize(v0);
+                        any = false; mine = 0;
+                        break;
+                    }
                 }
+                serving |= mine;
                 served += any ? 1 : 0;
             }
             const size_t usable = usable_of(serving);
@@ -283,6 +312,8 @@ int64_t dev_reader_search_plan(mlz_dev_reader* rd, hipStream_t sm, uint32_t flag
                 const auto u_hs = up.take<uint32_t>(hs.size());
                 const auto u_pats = up.take<mlz::SearchManyPat>(pats.size());
                 const auto u_n = up.take<uint64_t>(nck);
+                Region<uint32_t> u_voff{};
+                if (fold) u_voff = up.take<uint32_t>(voff.size());   // (behind the unflagged call's block, which stays as it is)
                 Carve cv;
                 const auto r_up = cv.take<uint8_t>(up.bytes);
                 const auto r_take = cv.take<uint8_t>(nck);
@@ -292,6 +323,7 @@ int64_t dev_reader_search_plan(mlz_dev_reader* rd, hipStream_t sm, uint32_t flag
                 void *ws = r_up.at(c->d_rplan.p), *h_up = c->pinned2;
                 std::memcpy(u_hs.at(h_up), hs.data(), hs.size() * 4);
                 std::memcpy(u_pats.at(h_up), pats.data(), pats.size() * sizeof(mlz::SearchManyPat));
+                if (fold) std::memcpy(u_voff.at(h_up), voff.data(), voff.size() * 4);
                 uint64_t* h_n = u_n.at(h_up);
                 for (size_t k = 0; k < nck; k++) h_n[k] = rd->chunks[k].n;
                 uint8_t* d_take = r_take.at(c->d_rplan.p);
@@ -305,8 +337,9 @@ int64_t dev_reader_search_plan(mlz_dev_reader* rd, hipStream_t sm, uint32_t flag
                 HIPCHK(c, hipMemcpyAsync(ws, h_up, up.bytes, hipMemcpyHostToDevice, sm));
                 HIPCHK(c, hipMemsetAsync(d_take, 0, nck, sm));
                 const uint64_t lanes = uint64_t(nck) * n;
-                hipLaunchKernelGGL(mlz::search_plan_kernel, dim3(uint32_t((lanes + 255) / 256)), dim3(256), 0, sm, st.base, static_cast<const mlz::SearchTab*>(st.d_tabs),
-                                   u_n.at(ws), uint32_t(nck), sets, u_hs.at(ws), u_pats.at(ws), uint32_t(n), d_take);
+                hipLaunchKernelGGL(fold ? mlz::search_plan_kernel<true> : mlz::search_plan_kernel<false>, dim3(uint32_t((lanes + 255) / 256)), dim3(256), 0, sm, st.base,
+                                   static_cast<const mlz::SearchTab*>(st.d_tabs), u_n.at(ws), uint32_t(nck), sets, u_hs.at(ws), fold ? u_voff.at(ws) : static_cast<const uint32_t*>(nullptr),
+                                   u_pats.at(ws), uint32_t(n), d_take);
                 if ((e = fetch(c, sm, c->pinned2, d_take, nck))) return e;   // (behind the upload on sm: the staged block has left the pinned buffer)
                 std::memcpy(take->data(), c->pinned2, nck);
                 *n_take = 0;
@@ -400,10 +433,15 @@ void search_found_write(hipStream_t sm, const SearchFound& f, uint64_t cap, uint
 int64_t dev_reader_search_scan_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* pattern, uint32_t L, uint64_t* stats, SearchFound* found) {
     mlz_ctx* c = rd->ctx;
     const size_t nck = rd->chunks.size();
-    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0;
+    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0, fold = (flags & MLZ_SEARCH_IGNORE_CASE) != 0;
     search_begin(rd, stats);
     if (nck == 0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
+    uint8_t folded[mlz::kSearchMaxPattern];
+    if (fold) {   // the pattern is folded once, here; the plan and the scan see the folded one
+        for (uint32_t i = 0; i < L; i++) folded[i] = mlz::search_fold(pattern[i]);
+        pattern = folded;
+    }
     std::vector<uint8_t> take(nck, 0);
     size_t n_take = 0;
     const int64_t pr = dev_reader_search_plan(rd, sm, flags, pattern, std::vector<uint32_t>{0, L}, 1, &take, &n_take, stats, false);
@@ -432,7 +470,7 @@ int64_t dev_reader_search_scan_locked(mlz_dev_reader* rd, hipStream_t sm, uint32
     HIPCHK(c, hipMemcpyAsync(ws, h_pat, L, hipMemcpyHostToDevice, sm));
     HIPCHK(c, hipMemsetAsync(d_total, 0, 16, sm));
     const int64_t r = search_decode_run(rd, sm, ignore_crc, &sd, [&](size_t, size_t t0, size_t t1) {
-        hipLaunchKernelGGL(mlz::search_scan_kernel, dim3(uint32_t(t1 - t0)), dim3(256), 0, sm, c->d_range.as<uint8_t>(), d_tiles, uint32_t(t0), ws, L, d_masks, d_counts);
+        hipLaunchKernelGGL(fold ? mlz::search_scan_kernel<true> : mlz::search_scan_kernel<false>, dim3(uint32_t(t1 - t0)), dim3(256), 0, sm, c->d_range.as<uint8_t>(), d_tiles, uint32_t(t0), ws, L, d_masks, d_counts);
         return 0;
     });
     if (r < 0) return r;

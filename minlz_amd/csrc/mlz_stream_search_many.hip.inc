@@ -51,7 +51,9 @@ enum { kSearchManyCount = 0, kSearchManyWrite = 1, kSearchManyMarkRecords = 2 };
 // whose first pair lies below cap go to out_pos / out_which from prefix[tile] on, as far as they lie below cap.  kSearchManyMarkRecords: bit
 // number(position) of mk.bits is set for every pair (mlz_stream_grep.h, mark); the tile's two record numbers lie in the scan words of the LDS
 // layout, which this mode does not use otherwise, and every lane reads the same two words (a broadcast).
-template <int kMode>
+// kFold (MLZ_SEARCH_IGNORE_CASE): the index and the blob are those of the folded patterns, and the tile's bytes are folded a word at a time
+// (search_fold4) on their way from the scratch into LDS, so the key and the verify loop compare folded bytes at no cost per position.
+template <int kMode, bool kFold>
 __global__ __launch_bounds__(kSearchManyThreads) void search_many_kernel(const uint8_t* __restrict__ scratch, const SearchTile* __restrict__ tiles, uint32_t tile0, SearchManyIx ix,
                                                                          uint32_t* __restrict__ tile_counts, unsigned long long* __restrict__ pat_counts,
                                                                          const uint64_t* __restrict__ prefix, uint64_t cap, uint64_t* __restrict__ out_pos,
@@ -88,7 +90,7 @@ __global__ __launch_bounds__(kSearchManyThreads) void search_many_kernel(const u
     uint32_t avail = t.count - 1 + ix.lmax;
     if (avail > t.hi_end) avail = t.hi_end;
     const uint32_t* gw = reinterpret_cast<const uint32_t*>(scratch + (t.src_off - shift));
-    for (uint32_t w = tid; w < (shift + avail + 3) / 4; w += kSearchManyThreads) tw[w + (w >> 4)] = gw[w];
+    for (uint32_t w = tid; w < (shift + avail + 3) / 4; w += kSearchManyThreads) tw[w + (w >> 4)] = kFold ? search_fold4(gw[w]) : gw[w];
     if (kMode == kSearchManyMarkRecords && tid < 2 && t.count)   // two lanes: the numbers of the tile's first and last start position (below 2^32)
         scan[tid] = uint32_t(rindex_number([&](uint64_t j) { return mk.D[j]; }, mk.k, tid ? t.gpos + t.count - 1 : t.gpos));
     __syncthreads();
@@ -176,11 +178,27 @@ struct SearchManyUpload {
     }
 };
 
+// search_many_kernel<kMode> with or without folding
+template <int kMode>
+auto search_many_kernel_of(bool fold) { return fold ? mlz::search_many_kernel<kMode, true> : mlz::search_many_kernel<kMode, false>; }
+
+// The patterns of a call as its plan, index and scan see them: folded under MLZ_SEARCH_IGNORE_CASE (once, here), else the caller's
+const uint8_t* search_many_folded(uint32_t flags, const uint8_t* patterns, const uint32_t* pattern_len, size_t n, std::vector<uint8_t>* keep) {
+    if (!(flags & MLZ_SEARCH_IGNORE_CASE)) return patterns;
+    size_t bytes = 0;
+    for (size_t i = 0; i < n; i++) bytes += pattern_len[i];
+    keep->resize(bytes);
+    for (size_t i = 0; i < bytes; i++) (*keep)[i] = mlz::search_fold(patterns[i]);
+    return keep->data();
+}
+
 int64_t dev_reader_search_many_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* patterns, const uint32_t* pattern_len, size_t n, uint64_t* d_counts,
                                       uint64_t* d_offsets, uint32_t* d_which, uint64_t cap, uint64_t* stats) {
     mlz_ctx* c = rd->ctx;
     const size_t nck = rd->chunks.size();
-    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0;
+    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0, fold = (flags & MLZ_SEARCH_IGNORE_CASE) != 0;
+    std::vector<uint8_t> keep;
+    patterns = search_many_folded(flags, patterns, pattern_len, n, &keep);
     search_begin(rd, stats);
     HIPCHK(c, hipSetDevice(c->device));
     auto nothing = [&]() -> int64_t {   // no chunk to scan: every count is 0
@@ -223,10 +241,10 @@ int64_t dev_reader_search_many_locked(mlz_dev_reader* rd, hipStream_t sm, uint32
     if ((e = up.send(c, sm, index, patterns, n))) return e;
     const int64_t r = search_decode_run(rd, sm, ignore_crc, &sd, [&](size_t, size_t t0, size_t t1) {
         const uint8_t* scratch = c->d_range.as<uint8_t>();
-        hipLaunchKernelGGL(mlz::search_many_kernel<mlz::kSearchManyCount>, dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), up.lds_bytes, sm, scratch, d_tiles, uint32_t(t0), up.ix, d_tc, d_pc,
+        hipLaunchKernelGGL(search_many_kernel_of<mlz::kSearchManyCount>(fold), dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), up.lds_bytes, sm, scratch, d_tiles, uint32_t(t0), up.ix, d_tc, d_pc,
                            static_cast<const uint64_t*>(nullptr), uint64_t(0), static_cast<uint64_t*>(nullptr), static_cast<uint32_t*>(nullptr), mlz::SearchManyMark{});
         hipLaunchKernelGGL(mlz::search_prefix_kernel, dim3(1), dim3(1024), 0, sm, d_tc, uint32_t(t0), uint32_t(t1), d_prefix, d_total);
-        if (cap) hipLaunchKernelGGL(mlz::search_many_kernel<mlz::kSearchManyWrite>, dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), up.lds_bytes, sm, scratch, d_tiles, uint32_t(t0), up.ix, d_tc, d_pc,
+        if (cap) hipLaunchKernelGGL(search_many_kernel_of<mlz::kSearchManyWrite>(fold), dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), up.lds_bytes, sm, scratch, d_tiles, uint32_t(t0), up.ix, d_tc, d_pc,
                                     static_cast<const uint64_t*>(d_prefix), cap, d_offsets, d_which, mlz::SearchManyMark{});
         return 0;
     });

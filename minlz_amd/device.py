@@ -204,14 +204,15 @@ class DeviceStream:
                                       d_starts=starts.data_ptr() if return_starts and n else None, ignore_crc=ignore_crc, stream=_stream(self.dev))
         return (out[:got], starts) if return_starts else out[:got]
 
-    def search(self, pattern, max_results, ignore_crc=False, no_tables=False):
+    def search(self, pattern, max_results, ignore_crc=False, no_tables=False, ignore_case=False):
         """Where `pattern` (1 .. 256 bytes) occurs in the decoded stream -> (the smallest min(total, max_results) positions, ascending: an
-        int64 tensor on the stream's device; the total).  Only the blocks whose search tables (types 1 to 4) admit the pattern are decoded."""
+        int64 tensor on the stream's device; the total).  Only the blocks whose search tables (types 1 to 4) admit the pattern are decoded.
+        ignore_case (here, in search_many, search_records and grep): grep -i in the C locale, A .. Z equal a .. z; the stream stays as it is."""
         out, d_out = _room(max_results, torch.int64, self.dev)
-        total, _ = self.reader.search(pattern, d_out, max_results, ignore_crc=ignore_crc, no_tables=no_tables, stream=_stream(self.dev))
+        total, _ = self.reader.search(pattern, d_out, max_results, ignore_crc=ignore_crc, no_tables=no_tables, stream=_stream(self.dev), ignore_case=ignore_case)
         return out[:min(total, max_results)], total
 
-    def search_many(self, patterns, max_results, ignore_crc=False, no_tables=False):
+    def search_many(self, patterns, max_results, ignore_crc=False, no_tables=False, ignore_case=False):
         """Where each of `patterns` (a sequence of up to 4096 bytes objects of 1 .. 256 bytes) occurs in the decoded stream, in one pass over
         the blocks that any pattern's search tables admit -> (positions int64, which int32, counts int64, total): the smallest
         min(total, max_results) pairs (position, pattern index) in ascending order, every pattern's own number of occurrences and the
@@ -220,23 +221,24 @@ class DeviceStream:
         pos, d_pos = _room(max_results, torch.int64, self.dev)
         which, d_which = _room(max_results, torch.int32, self.dev)
         counts, _ = _room(len(pats), torch.int64, self.dev, torch.zeros)
-        total, _ = self.reader.search_many(pats, counts.data_ptr(), d_pos, d_which, max_results, ignore_crc=ignore_crc, no_tables=no_tables, stream=_stream(self.dev))
+        total, _ = self.reader.search_many(pats, counts.data_ptr(), d_pos, d_which, max_results, ignore_crc=ignore_crc, no_tables=no_tables, stream=_stream(self.dev),
+                                           ignore_case=ignore_case)
         k = min(total, max_results)
         return pos[:k], which[:k], counts[:len(pats)], total
 
-    def search_records(self, pattern, delimiter=b"\n", max_records=1024, max_bytes=1 << 20, max_reach=0, ignore_crc=False, no_tables=False):
+    def search_records(self, pattern, delimiter=b"\n", max_records=1024, max_bytes=1 << 20, max_reach=0, ignore_crc=False, no_tables=False, ignore_case=False):
         """The records (lines, for the default delimiter) of the decoded stream that hold `pattern`, each once, in stream order ->
         (total_records, data, rec_off, rec_start, flags, totals): the first k records' bytes back to back (uint8), where each starts in the
         decoded stream (int64, k values) and in `data` (int64, k + 1 values: the last is data's size), its flags (uint8: 1 = cut left,
         2 = cut right — records longer than max_reach, 0 = 65536) — tensors on the stream's device, trimmed to what was written: k is
         the most records that max_records and max_bytes hold whole — and totals = (records, bytes of all records, occurrences, flagged
-        records).  max_records = max_bytes = 0 counts."""
+        records).  max_records = max_bytes = 0 counts.  With ignore_case the records' bytes are the stream's original ones."""
         data, d_data = _room(max_bytes, torch.uint8, self.dev)
         rec_off, d_rec_off = _room(max_records, torch.int64, self.dev)
         rec_start = torch.zeros(max_records + 1, dtype=torch.int64, device=self.dev)
         flags, d_flags = _room(max_records, torch.uint8, self.dev)
         total, totals, _ = self.reader.search_records(pattern, delimiter, d_data, max_bytes, d_rec_off, rec_start.data_ptr(), d_flags, max_records, max_reach=max_reach,
-                                                      ignore_crc=ignore_crc, no_tables=no_tables, stream=_stream(self.dev))
+                                                      ignore_crc=ignore_crc, no_tables=no_tables, stream=_stream(self.dev), ignore_case=ignore_case)
         k = int((rec_start[1:] != 0).sum())   # (no record is empty: the starts behind the first are positive as far as they were written)
         return total, data[:int(rec_start[k])], rec_off[:k], rec_start[:k + 1], flags[:k], totals
 
@@ -276,7 +278,7 @@ class DeviceStream:
             self.reader.record_numbers(positions.data_ptr(), n, out.data_ptr(), stream=_stream(self.dev))
         return out
 
-    def grep(self, patterns, invert=False, before=0, after=0, max_records=1 << 20, count_only=False, ignore_crc=False, no_tables=False):
+    def grep(self, patterns, invert=False, before=0, after=0, max_records=1 << 20, count_only=False, ignore_crc=False, no_tables=False, ignore_case=False):
         """grep over the decoded stream's lines: the records that hold one of `patterns` (a sequence of up to 4096 bytes objects of
         1 .. 256 bytes without the delimiter; a single bytes object is one pattern), with invert those that hold none, and `before` /
         `after` context records around each, every record once, in stream order.  Builds the record index for b"\n" when the stream has
@@ -292,7 +294,7 @@ class DeviceStream:
             self.reader.record_count()
         except api.MinLZError:   # (no index yet)
             self.reader.index_records(b"\n", ignore_crc=ignore_crc, stream=st)
-        kw = dict(invert=invert, before=before, after=after, ignore_crc=ignore_crc, no_tables=no_tables, stream=st)
+        kw = dict(invert=invert, before=before, after=after, ignore_crc=ignore_crc, no_tables=no_tables, stream=st, ignore_case=ignore_case)
         if count_only:
             _, totals, _ = self.reader.grep_records(pats, None, None, 0, **kw)
             return totals[0], totals[1]
