@@ -17,11 +17,13 @@
 // whichever call it came in by.
 
 #include "mlz_stream_scratch.h"
+#include "mlz_stream_walk.h"
+#include "mlz_stream_batch.h"
+#include "mlz_stream_ranges.h"
 
 namespace {
 
-constexpr uint8_t kChunkUncompressed = 0x01, kChunkMinLZ = 0x02, kChunkMinLZCompCRC = 0x03, kChunkEOF = 0x20, kChunkIndex = 0x40,
-                  kChunkStreamID = 0xff, kMaxNonSkippable = 0x3f;  // minlz.go:108-131
+constexpr uint8_t kChunkUncompressed = 0x01, kChunkMinLZ = 0x02, kChunkMinLZCompCRC = 0x03, kChunkEOF = 0x20, kChunkIndex = 0x40;  // minlz.go:108-131
 constexpr uint32_t kMinStreamBlock = 4u << 10;                      // minlz.go:98
 const uint8_t kMagicChunk[9] = {0xff, 0x06, 0x00, 0x00, 'M', 'i', 'n', 'L', 'z'};
 constexpr size_t kStreamGroupBytes = 64u << 20;   // per group: copy-in, kernels and copy-out of different groups overlap
@@ -33,21 +35,6 @@ size_t put_uvarint64(uint8_t* d, uint64_t v) {
     return i;
 }
 size_t put_varint64(uint8_t* d, int64_t v) { return put_uvarint64(d, (uint64_t(v) << 1) ^ uint64_t(v >> 63)); }  // binary.PutVarint
-// binary.Uvarint: bytes read (0 = short buffer, < 0 = overflow)
-int get_uvarint64(const uint8_t* b, size_t n, uint64_t* out) {
-    uint64_t x = 0; unsigned s = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (i == 10) return -int(i + 1);
-        const uint8_t c = b[i];
-        if (c < 0x80) {
-            if (i == 9 && c > 1) return -int(i + 1);
-            *out = x | uint64_t(c) << s;
-            return int(i + 1);
-        }
-        x |= uint64_t(c & 0x7f) << s; s += 7;
-    }
-    return 0;
-}
 
 // Seek index, write side (Index.reset / add / reduce / reduceLight / appendTo, index.go:56-269).
 struct SeekIndex {
@@ -705,197 +692,139 @@ int64_t stream_bound_checked(uint64_t n, uint32_t block_size, uint32_t flags, co
 struct StreamChunk {
     uint8_t type;
     uint32_t crc;
-    size_t body_off, body_len;  // tokens (0x02) or raw bytes (0x01) inside the stream
+    size_t body_off, body_len;  // tokens (0x02 / 0x03) or raw bytes (0x01) inside the stream
     size_t n, out_off;
-    size_t res_idx;             // where the device left this chunk's decode verdict
-    size_t crc_idx;             // type 0x03: where the device left the CRC of its compressed bytes
-    size_t hdr_off = 0;         // the device walk: where the chunk's 4-byte header lies in the stream (a sidecar's references name it)
+    size_t hdr_off;             // where the chunk's 4-byte header lies in the stream (a sidecar's references name it)
 };
 
-// Reader.Read's chunk walk (reader.go:248-543).  Fills `chunks`, returns total decoded bytes or -MLZ_ERR_*; on an error `chunks` holds the
-// chunks in front of it, which the Reader decodes (and may fail on) before it reaches the error.
+// WalkReader's `data`: the chunk appended to `chunks`, its body and header offsets counted from `base` bytes in front of the stream
+auto stream_chunk_sink(std::vector<StreamChunk>* chunks, uint64_t base = 0) {
+    return [chunks, base](uint8_t type, uint32_t crc, uint64_t body_off, uint64_t body_len, uint64_t n, uint64_t out_off, uint64_t hdr_off) {
+        chunks->push_back(StreamChunk{type, crc, size_t(base + body_off), size_t(body_len), size_t(n), size_t(out_off), size_t(base + hdr_off)});
+    };
+}
+
+// Reader.Read's chunk walk (reader.go:248-543) over a stream in host memory: the walk, the records and the running state of
+// mlz_stream_walk.h, header by header, up to the first error and not a byte further.  Fills `chunks`, returns total decoded bytes or
+// -MLZ_ERR_*; on an error `chunks` holds the chunks in front of it, which the Reader decodes (and may fail on) before it reaches the error.
 int64_t stream_parse(const uint8_t* src, size_t slen, std::vector<StreamChunk>* chunks) {
-    size_t p = 0, out = 0, max_block = kMaxBlockSize, stream_out = 0;
-    bool read_header = false, want_eof = false;
-    for (;;) {
-        if (p == slen) return want_eof ? -MLZ_ERR_CORRUPT : int64_t(out);  // io.ErrUnexpectedEOF when an EOF chunk is owed
-        if (slen - p < 4) return -MLZ_ERR_CORRUPT;
-        const uint8_t type = src[p];
-        const size_t clen = size_t(src[p + 1]) | size_t(src[p + 2]) << 8 | size_t(src[p + 3]) << 16;
-        p += 4;
-        if (!read_header) {
-            if (type == kChunkStreamID) read_header = true;
-            else if (type <= kMaxNonSkippable && type != kChunkEOF) return -MLZ_ERR_CORRUPT;  // reader.go:273-283
-        }
-        switch (type) {
-        case kChunkMinLZ: case kChunkMinLZCompCRC: {
-            if (clen < 4 || clen > size_t(mlz_max_encoded_len(max_block)) + 4 || slen - p < clen) return -MLZ_ERR_CORRUPT;
-            StreamChunk ck;
-            ck.type = type;
-            std::memcpy(&ck.crc, src + p, 4);
-            uint64_t nn = 0;
-            const int hl = get_uvarint64(src + p + 4, clen - 4, &nn);
-            if (hl <= 0 || nn > 0xffffffffull) return -MLZ_ERR_CORRUPT;
-            if (nn > max_block) return -MLZ_ERR_TOO_LARGE;
-            const size_t body = clen - 4 - size_t(hl);
-            if (nn == 0 || nn < body) return -MLZ_ERR_CORRUPT;  // reader.go:327
-            ck.body_off = p + 4 + size_t(hl); ck.body_len = body; ck.n = size_t(nn); ck.out_off = out;
-            chunks->push_back(ck);
-            out += size_t(nn); stream_out += size_t(nn);
-            p += clen;
-            break;
-        }
-        case kChunkUncompressed: {
-            if (clen < 4 || clen > size_t(mlz_max_encoded_len(max_block)) + 4 || slen - p < 4) return -MLZ_ERR_CORRUPT;
-            const size_t nn = clen - 4;
-            if (nn > max_block) return -MLZ_ERR_TOO_LARGE;   // (before the bytes are read: reader.go:411-464)
-            if (slen - p < clen) return -MLZ_ERR_CORRUPT;
-            StreamChunk ck;
-            ck.type = type;
-            std::memcpy(&ck.crc, src + p, 4);
-            ck.body_off = p + 4; ck.body_len = nn; ck.n = nn; ck.out_off = out;
-            chunks->push_back(ck);
-            out += nn; stream_out += nn;
-            p += clen;
-            break;
-        }
-        case kChunkEOF: {
-            if (clen > 10 || slen - p < clen) return -MLZ_ERR_CORRUPT;
-            if (clen) {
-                uint64_t want = 0;
-                const int vn = get_uvarint64(src + p, clen, &want);
-                if (vn != int(clen) || want != stream_out) return -MLZ_ERR_CORRUPT;  // reader.go:476-491
-            }
-            p += clen;
-            want_eof = read_header = false;
-            break;
-        }
-        case kChunkStreamID: {
-            if (clen != 6 || slen - p < 6) return -MLZ_ERR_CORRUPT;
-            if (std::memcmp(src + p, "MinLz", 5) != 0) return -MLZ_ERR_UNSUPPORTED;
-            const uint8_t v = src[p + 5];
-            if (v & 0xc0) return -MLZ_ERR_CORRUPT;
-            const unsigned lg = (v & 15) + 10;
-            if (lg > 23) return -MLZ_ERR_CORRUPT;
-            max_block = size_t(1) << lg;
-            if (max_block > kMaxBlockSize) return -MLZ_ERR_TOO_LARGE;
-            p += 6;
-            stream_out = 0;
-            want_eof = true;
-            break;
-        }
-        default:
-            if (type == 0x00) return -MLZ_ERR_UNSUPPORTED;                 // legacy S2/Snappy chunk
-            if (type <= kMaxNonSkippable) return -MLZ_ERR_UNSUPPORTED;     // reserved unskippable, reader.go:530-536
-            if (slen - p < clen) return -MLZ_ERR_CORRUPT;
-            p += clen;                                                     // skippable (index, padding, user chunks)
-        }
+    mlz::WalkReader rd(kMaxBlockSize);
+    int err = 0;
+    mlz::walk_headers(src, slen, 0, slen, false, mlz::kWalkNoCap, [&](uint64_t e) {
+        err = rd.step(mlz::walk_classify(src, slen, e), stream_chunk_sink(chunks));
+        return err == 0;
+    });
+    return err ? err : rd.finish();
+}
+
+// One chunk of a decode list: `at` is where a compressed chunk (0x02 / 0x03) is decoded to, and where the bytes of a stored one (0x01) lie
+// for its CRC.  The targets of one list may lie in several allocations (the caller's destination, the context's scratch, the stream itself).
+struct ChunkJob { size_t ck; const uint8_t* at; };
+
+// The decode and CRC descriptors of one group, jobs [j0, j1) of a list.  A compressed chunk gets a decode descriptor; every chunk gets one
+// CRC descriptor, a 0x03 chunk's over its token bytes (reader.go:341-344), the others' over the bytes at `at`.  The chunk at stream offset
+// body_off has its tokens at tok + (body_off - tok_bias): the stream itself, or the part of it a worker copied in.  Each list has its
+// lowest address as base and holds distances from it (the decode's sources: from tok).  res_idx[j]: job j's place among the decode
+// results, which the group's come to from `res0` on.
+struct ChunkGroupDescs { std::vector<mlz_block_desc> dec, crc; uintptr_t dbase, cbase; };
+void chunk_group_descs(const uint8_t* tok, size_t tok_bias, const std::vector<StreamChunk>& chunks, const ChunkJob* jobs, size_t j0, size_t j1, size_t res0,
+                       size_t* res_idx, ChunkGroupDescs* d) {
+    auto crc_at = [&](size_t j) {
+        const StreamChunk& ck = chunks[jobs[j].ck];
+        return reinterpret_cast<uintptr_t>(ck.type == kChunkMinLZCompCRC ? tok + (ck.body_off - tok_bias) : jobs[j].at);
+    };
+    d->dbase = d->cbase = ~uintptr_t(0);
+    for (size_t j = j0; j < j1; j++) {
+        if (chunks[jobs[j].ck].type != kChunkUncompressed) d->dbase = std::min(d->dbase, reinterpret_cast<uintptr_t>(jobs[j].at));
+        d->cbase = std::min(d->cbase, crc_at(j));
+    }
+    d->dec.clear(); d->crc.clear();
+    for (size_t j = j0; j < j1; j++) {
+        const StreamChunk& ck = chunks[jobs[j].ck];
+        d->crc.push_back(mlz_block_desc{uint64_t(crc_at(j) - d->cbase), ck.type == kChunkMinLZCompCRC ? ck.body_len : ck.n, 0, 0});
+        if (ck.type == kChunkUncompressed) continue;
+        res_idx[j] = res0 + d->dec.size();
+        d->dec.push_back(mlz_block_desc{ck.body_off - tok_bias, ck.body_len, uint64_t(reinterpret_cast<uintptr_t>(jobs[j].at) - d->dbase), ck.n});
     }
 }
 
 // Chunks [k0, k1) of a parsed stream: their bytes to the device, decode, CRC, output to its final place in dst (every chunk's output offset
 // is known from the chunk walk, so ranges of one stream are independent: reader.go:830-859 hands blocks to goroutines the same way).
+// The groups (range_group_ends), their descriptors (chunk_group_descs) and the verdict (chunk_job_verdict) are the device-resident Reader's;
+// the pipeline is this function's own: copy-in on s_in, kernels on c->stream, results and output home on s_out, three events per group.
 // Returns 0, or the error of the FIRST chunk of the range that fails (-MLZ_ERR_*).
-int64_t stream_decode_range(mlz_ctx* c, bool ignore_crc, const uint8_t* src, std::vector<StreamChunk>& chunks, size_t k0, size_t k1, uint8_t* dst,
+int64_t stream_decode_range(mlz_ctx* c, bool ignore_crc, const uint8_t* src, const std::vector<StreamChunk>& chunks, size_t k0, size_t k1, uint8_t* dst,
                             uint64_t mir_total /* bytes of dst that may be written through a pinned alias; 0 = ask nothing */) {
     if (k1 <= k0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nck = k1 - k0;
-    // groups of chunks covering ~64 MiB of output; the range's part of the stream image goes to the device group by group
-    std::vector<size_t> gstart{k0};
-    {
-        size_t acc = 0;
-        for (size_t i = k0; i < k1; i++) {
-            acc += chunks[i].n;
-            if (acc >= kStreamGroupBytes && i + 1 < k1) { gstart.push_back(i + 1); acc = 0; }
-        }
-        gstart.push_back(k1);
-    }
-    const size_t ngroups = gstart.size() - 1;
+    std::vector<size_t> gend;   // groups of chunks covering ~64 MiB of output; the range's part of the stream image goes to the device group by group
+    mlz::range_group_ends(nck, [&](size_t i) { return uint64_t(chunks[k0 + i].n); }, &gend);
     // this worker's buffers hold its range only: stream bytes from s_base, output from o_base
     const size_t s_base = chunks[k0].body_off, s_end = chunks[k1 - 1].body_off + chunks[k1 - 1].body_len;
     const size_t o_base = chunks[k0].out_off, o_end = chunks[k1 - 1].out_off + chunks[k1 - 1].n;
     HIPCHK(c, c->d_in.ensure(s_end - s_base + 64));
     HIPCHK(c, c->d_out.ensure(o_end - o_base + 64));
     HIPCHK(c, c->d_len.ensure(sizeof(int64_t) * nck));
-    HIPCHK(c, c->d_crc.ensure(sizeof(uint32_t) * 2 * nck + 64));   // [nck, 2 nck): chunks of type 0x03 (CRC of the compressed bytes)
-    int r = ensure_stream_objects(c, 3 * ngroups, nck * 16);
+    HIPCHK(c, c->d_crc.ensure(sizeof(uint32_t) * nck + 64));
+    int r = ensure_stream_objects(c, 3 * gend.size(), nck * 12);
     if (r) return r;
     int64_t* h_len = static_cast<int64_t*>(c->pinned2);
     uint32_t* h_crc = reinterpret_cast<uint32_t*>(h_len + nck);
-    uint32_t* h_crc3 = h_crc + nck;
     uint8_t* d_in = c->d_in.as<uint8_t>();
     uint8_t* d_out = c->d_out.as<uint8_t>();
     hipStream_t sm = c->stream;
-    std::vector<mlz_block_desc> ddesc, cdesc(nck), c3desc;
-    std::vector<size_t> dmap, c3map;
+    std::vector<ChunkJob> jobs(nck);   // job i - k0: chunk i, in this worker's d_out
+    for (size_t i = k0; i < k1; i++) jobs[i - k0] = ChunkJob{i, d_out + (chunks[i].out_off - o_base)};
+    std::vector<size_t> res_idx(nck, 0);
+    ChunkGroupDescs gd;
     // A page-locked destination is written by the decode kernels themselves, tile by tile as they finish (the copy-out of a pinned
     // buffer runs as shader copies on this ROCm build and queues up behind every kernel of the stream: 11.4 ms against 4.4 ms into
     // pageable memory for 100 MB); stored chunks are copied on the host, from the stream image the caller handed in.
     const uint64_t mir_base = (mir_total && c->decode_algo == 0 && c->general_algo == 0) ? pinned_alias(dst, size_t(mir_total)) : 0;
     std::vector<uint64_t> dmir;
-    for (size_t g = 0; g < ngroups; g++) {
-        const size_t c0 = gstart[g], c1 = gstart[g + 1], r0 = c0 - k0;   // r0: the group's first chunk, counted inside the range
+    for (size_t g = 0, r0 = 0; g < gend.size(); r0 = gend[g++]) {   // r0, r1: the group's chunks, counted inside the range
+        const size_t r1 = gend[g], c0 = k0 + r0, c1 = k0 + r1;
         hipEvent_t e_in = c->evpool[3 * g], e_k = c->evpool[3 * g + 1], e_out = c->evpool[3 * g + 2];
         // stream bytes of this group: from its first chunk's body to the end of its last chunk's body
         const size_t s0 = chunks[c0].body_off, s1 = chunks[c1 - 1].body_off + chunks[c1 - 1].body_len;
         HIPCHK(c, hipMemcpyAsync(d_in + (s0 - s_base), src + s0, s1 - s0, hipMemcpyHostToDevice, c->s_in));
         HIPCHK(c, hipEventRecord(e_in, c->s_in));
         HIPCHK(c, hipStreamWaitEvent(sm, e_in, 0));
-        ddesc.clear(); dmap.clear(); c3desc.clear(); c3map.clear(); dmir.clear();
+        dmir.clear();
         for (size_t i = c0; i < c1; i++) {
             const StreamChunk& ck = chunks[i];
-            // (a 0x03 chunk's CRC covers its token bytes — the second launch below —: its decoded bytes get an empty descriptor here)
-            cdesc[i - k0] = mlz_block_desc{ck.out_off - o_base, ck.type == kChunkMinLZCompCRC ? uint64_t(0) : uint64_t(ck.n), 0, 0};
-            if (ck.type == kChunkMinLZ || ck.type == kChunkMinLZCompCRC) {
-                ddesc.push_back(mlz_block_desc{ck.body_off - s_base, ck.body_len, ck.out_off - o_base, ck.n});
-                dmap.push_back(i);
-                dmir.push_back(mir_base + ck.out_off);
-                if (ck.type == kChunkMinLZCompCRC) {  // its CRC covers the token bytes, not the decoded ones (reader.go:341-344)
-                    c3desc.push_back(mlz_block_desc{ck.body_off - s_base, ck.body_len, 0, 0});
-                    c3map.push_back(i);
-                }
-            } else {
-                HIPCHK(c, hipMemcpyAsync(d_out + (ck.out_off - o_base), d_in + (ck.body_off - s_base), ck.n, hipMemcpyDeviceToDevice, sm));
-                if (mir_base) std::memcpy(dst + ck.out_off, src + ck.body_off, ck.n);
-            }
+            if (ck.type != kChunkUncompressed) { dmir.push_back(mir_base + ck.out_off); continue; }
+            HIPCHK(c, hipMemcpyAsync(d_out + (ck.out_off - o_base), d_in + (ck.body_off - s_base), ck.n, hipMemcpyDeviceToDevice, sm));
+            if (mir_base) std::memcpy(dst + ck.out_off, src + ck.body_off, ck.n);
         }
-        if (!ddesc.empty()) {
-            // minLZDecode(dst[:n], tokens) contract: lengths come back compacted, scatter them to chunk order below
-            r = decode_device_locked(c, sm, d_in, d_out, ddesc.data(), int(ddesc.size()), c->d_len.as<int64_t>() + r0, true, mir_base ? dmir.data() : nullptr, false);
+        // the group's decode results come to h_len[r0 .. r0 + its compressed chunks), compacted; its CRCs to h_crc[r0 .. r1)
+        chunk_group_descs(d_in, s_base, chunks, jobs.data(), r0, r1, r0, res_idx.data(), &gd);
+        if (!gd.dec.empty()) {
+            r = decode_device_locked(c, sm, d_in, reinterpret_cast<uint8_t*>(gd.dbase), gd.dec.data(), int(gd.dec.size()), c->d_len.as<int64_t>() + r0, true,
+                                     mir_base ? dmir.data() : nullptr, false);
             if (r) return r;
         }
         if (!ignore_crc) {
-            r = crc_device_locked(c, sm, d_out, cdesc.data() + r0, int(c1 - c0), c->d_crc.as<uint32_t>() + r0);
+            r = crc_device_locked(c, sm, reinterpret_cast<const uint8_t*>(gd.cbase), gd.crc.data(), int(r1 - r0), c->d_crc.as<uint32_t>() + r0);
             if (r) return r;
-            if (!c3desc.empty()) {
-                r = crc_device_locked(c, sm, d_in, c3desc.data(), int(c3desc.size()), c->d_crc.as<uint32_t>() + nck + r0);
-                if (r) return r;
-            }
         }
         HIPCHK(c, hipEventRecord(e_k, sm));
         HIPCHK(c, hipStreamWaitEvent(c->s_out, e_k, 0));
-        if (!ddesc.empty())
-            HIPCHK(c, hipMemcpyAsync(h_len + r0, c->d_len.as<int64_t>() + r0, sizeof(int64_t) * ddesc.size(), hipMemcpyDeviceToHost, c->s_out));
+        if (!gd.dec.empty())
+            HIPCHK(c, hipMemcpyAsync(h_len + r0, c->d_len.as<int64_t>() + r0, sizeof(int64_t) * gd.dec.size(), hipMemcpyDeviceToHost, c->s_out));
         if (!ignore_crc)
-            HIPCHK(c, hipMemcpyAsync(h_crc + r0, c->d_crc.as<uint32_t>() + r0, sizeof(uint32_t) * (c1 - c0), hipMemcpyDeviceToHost, c->s_out));
-        if (!ignore_crc && !c3desc.empty())
-            HIPCHK(c, hipMemcpyAsync(h_crc3 + r0, c->d_crc.as<uint32_t>() + nck + r0, sizeof(uint32_t) * c3desc.size(), hipMemcpyDeviceToHost, c->s_out));
-        for (size_t k = 0; k < c3map.size(); k++) chunks[c3map[k]].crc_idx = r0 + k;
+            HIPCHK(c, hipMemcpyAsync(h_crc + r0, c->d_crc.as<uint32_t>() + r0, sizeof(uint32_t) * (r1 - r0), hipMemcpyDeviceToHost, c->s_out));
         const size_t o0 = chunks[c0].out_off, o1 = chunks[c1 - 1].out_off + chunks[c1 - 1].n;
         if (!mir_base) HIPCHK(c, hipMemcpyAsync(dst + o0, d_out + (o0 - o_base), o1 - o0, hipMemcpyDeviceToHost, c->s_out));
         HIPCHK(c, hipEventRecord(e_out, c->s_out));
-        // the decode results of the group occupy h_len[r0 .. r0 + ddesc.size()), in dmap order; checked after the loop
-        for (size_t k = 0; k < dmap.size(); k++) chunks[dmap[k]].res_idx = r0 + k;
     }
     HIPCHK(c, hipStreamSynchronize(c->s_out));
-    for (size_t i = k0; i < k1; i++) {
-        const StreamChunk& ck = chunks[i];
-        if (ck.type == kChunkMinLZ || ck.type == kChunkMinLZCompCRC) {
-            const int64_t got = h_len[ck.res_idx];
-            if (got != int64_t(ck.n)) return got < 0 ? got : -MLZ_ERR_CORRUPT;  // decoded length, or -MLZ_ERR_*
-        }
-        if (!ignore_crc && (ck.type == kChunkMinLZCompCRC ? h_crc3[ck.crc_idx] : h_crc[i - k0]) != ck.crc) return -MLZ_ERR_CRC;
+    for (size_t j = 0; j < nck; j++) {
+        const StreamChunk& ck = chunks[k0 + j];
+        const bool compressed = ck.type != kChunkUncompressed;
+        const int64_t v = mlz::chunk_job_verdict(compressed, compressed ? h_len[res_idx[j]] : 0, ck.n, !ignore_crc, ignore_crc ? 0 : h_crc[j], ck.crc);
+        if (v) return v;
     }
     return 0;
 }

@@ -1,6 +1,6 @@
 // mlz_stream_batch.h — what the batch calls over many streams in HBM (mlz_stream_batch.hip.inc) share with their host check
-// (tools/stream_batch_check.cpp): the chunk walk one lane runs over one stream of the batch, the verdict of one decoded chunk, and the
-// verdicts of the streams from those of their chunks.  Plain C++: compiles for the host alone and for gfx950.
+// (tools/stream_batch_check.cpp): the chunk walk one lane runs over one stream of the batch (mlz_stream_walk.h's header step under a cap),
+// the verdict of one decoded chunk (the host Reader's too), and the verdicts of the streams from those of their chunks.  Plain C++: compiles for the host alone and for gfx950.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -13,31 +13,18 @@ namespace mlz {
 // count is 0 and its flag is set, and the call walks it by the region kernels of mlz_stream_walk.hip.inc instead.
 constexpr uint32_t kBatchWalkSteps = 4096;
 
-// The chunk walk of the stream src[0, n) from offset 0, header by header (the loop walk_list_kernel runs inside one region): a stub ends
-// the walk and enters the table, a chunk enters the table unless walk_skippable says it changes nothing, e += 4 + clen.  EMIT: the records
-// go to out[0, limit); without it they are counted.  Returns the entries; *is_long: the stream has more than max_steps headers (the
-// entries are then void).  Reads what walk_header and walk_classify read: src[0, n) and nothing else.
+// The chunk walk of the whole stream src[0, n), header by header (walk_headers, which walk_list_kernel runs inside one region), under a
+// step cap.  EMIT: the records go to out[0, limit); without it they are counted.  Returns the entries; *is_long: the stream has more than
+// max_steps headers (the entries are then void).  Reads what walk_headers and walk_classify read: src[0, n) and nothing else.
 template <bool EMIT>
 MLZ_WALK_HD uint32_t batch_walk_lane(const uint8_t* src, uint64_t n, uint32_t max_steps, WalkChunk* out, uint32_t limit, bool* is_long) {
-    uint32_t cnt = 0, steps = 0;
-    uint64_t e = 0;
-    *is_long = false;
-    while (e < n) {
-        if (steps++ == max_steps) { *is_long = true; return 0; }
-        if (n - e < 4) {   // the stub the walk ends on
-            if (EMIT && cnt < limit) out[cnt] = walk_classify(src, n, e);
-            cnt++;
-            break;
-        }
-        uint8_t type;
-        const uint32_t clen = walk_header(src, e, &type);
-        if (!walk_skippable(type, clen, n - e - 4)) {
-            if (EMIT && cnt < limit) out[cnt] = walk_classify(src, n, e);
-            cnt++;
-        }
-        e += 4 + uint64_t(clen);
-    }
-    return cnt;
+    uint32_t cnt = 0;
+    *is_long = !walk_headers(src, n, 0, n, false, max_steps, [&](uint64_t e) {
+        if (EMIT && cnt < limit) out[cnt] = walk_classify(src, n, e);
+        cnt++;
+        return true;
+    });
+    return *is_long ? 0 : cnt;
 }
 
 // Error codes as in include/minlz_hip.h (MLZ_ERR_*), negated on return.

@@ -5,8 +5,8 @@
 // mlz_stream_encode_gather_device over one range); what a batch saves is the fixed cost per stream: the six launches and two read-backs of
 // the region walk, the decode's launch sequence and read-back, the Writer's.
 //
-//   walk     walk_batch_kernel<false>: a lane per stream steps through its chunk headers from offset 0 (mlz::batch_walk_lane, the loop
-//            walk_list_kernel runs inside one region) and counts the table's entries; walk_scan_kernel turns the counts into places;
+//   walk     walk_batch_kernel<false>: a lane per stream steps through its chunk headers from offset 0 (mlz::batch_walk_lane: walk_headers, the step
+//            walk_list_kernel runs inside one region, under a cap) and counts the table's entries; walk_scan_kernel turns the counts into places;
 //            walk_batch_kernel<true> writes the records.  No region tables: 32 bytes per table entry, 8 bytes and a flag bit per stream.
 //            A lane stops after kBatchWalkSteps headers; its stream is LONG and goes through stream_walk_device inside the same call.
 //            Two read-backs: places, long flags and the sum; then the table.  walk_parse_table runs per stream on the host.
@@ -151,13 +151,7 @@ int stream_batch_walk(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, const ml
         if (h_first[i + 1] < h_first[i]) { c->err = "stream_batch_walk: the table's places do not ascend"; return -MLZ_ERR_HIP; }
         const uint64_t base = streams[i].src_off;
         bw->c0[i] = bw->chunks.size();
-        bw->parsed[i] = mlz::walk_parse_table(table + h_first[i], h_first[i + 1] - h_first[i], kMaxBlockSize,
-                                              [&](uint8_t type, uint32_t crc, uint64_t body_off, uint64_t body_len, uint64_t nn, uint64_t out_off, uint64_t hdr_off) {
-                                                  StreamChunk ck{};
-                                                  ck.type = type; ck.crc = crc; ck.body_off = size_t(base + body_off); ck.body_len = size_t(body_len); ck.n = size_t(nn);
-                                                  ck.out_off = size_t(out_off); ck.hdr_off = size_t(base + hdr_off);
-                                                  bw->chunks.push_back(ck);
-                                              });
+        bw->parsed[i] = mlz::walk_parse_table(table + h_first[i], h_first[i + 1] - h_first[i], kMaxBlockSize, stream_chunk_sink(&bw->chunks, base));
         bw->c1[i] = bw->chunks.size();
     }
     // long streams: the region walk, one after the other (it takes c->pinned2 and c->d_walk_tab over: the batch's table is spent by now)

@@ -1,7 +1,8 @@
 // mlz_stream_walk.hip.inc — the device-resident Reader: the chunk walk of a .mz stream that lies in HBM, and its decode in place
-// (included at the end of mlz_hip.hip, behind mlz_stream.hip.inc whose chunk types and decode helpers it uses).
+// (included at the end of mlz_hip.hip, behind mlz_stream.hip.inc whose chunk types, chunk list (StreamChunk, ChunkJob, chunk_group_descs)
+// and decode helpers it uses; the framing rules themselves are mlz_stream_walk.h's, the same code the host Reader runs).
 //
-// A stream carries no table of its chunks, but every chunk type advances the Reader by 4 + clen (stream_parse: all of its cases do), so
+// A stream carries no table of its chunks, but every chunk type advances the Reader by 4 + clen (walk_headers: every step does), so
 // next(p) = p + 4 + clen(p) is defined for EVERY byte offset p and the chunk starts are the orbit of offset 0 under next.  A parse that
 // starts at a wrong offset never falls in step with the real one (unlike a token stream: mlz_decode.hip.inc D2 guesses, this cannot), so the
 // exits are kept for every offset and the orbit is followed top-down through two sizes of region:
@@ -16,22 +17,18 @@
 //                                  min(chunks, n / 256 KiB) dependent loads — bounded by the stream's size, not by its chunk count.
 //   W4 mid     walk_mid_kernel     a lane per entered 256 KiB region follows x0 from its entry (at most 64 hops) and notes the entry of every
 //                                  4 KiB region on the way.
-//   W5 count / scan / emit         a lane per entered 4 KiB region steps through the chunk headers inside it (usually one), counts those that
-//                                  enter the table, and after an exclusive scan of the counts writes their records (walk_classify,
+//   W5 count / scan / emit         a lane per entered 4 KiB region steps through the chunk headers inside it (walk_headers; usually one), counts
+//                                  those that enter the table, and after an exclusive scan of the counts writes their records (walk_classify,
 //                                  mlz_stream_walk.h) in stream order.  Skippable chunks that lie inside the stream never enter the table —
 //                                  but for the walk of a sidecar, which keeps the chunks of types 0x44, 0x45 and 0x47.
 //
 // The table (32 bytes per chunk) is read back and the Reader's running state (block size, header / EOF bookkeeping, output offsets, the
-// first error) is applied to it on the host by walk_parse_table — the same code the host check runs (a serial pass over 32-byte
-// records; streams of very many DATA chunks would want it as scans on the device).  Decode and CRC then run on the stream where it lies: descriptors point into
+// first error: WalkReader) is applied to it on the host by walk_parse_table — the state the host Reader and the host check run (a serial
+// pass over 32-byte records; streams of very many DATA chunks would want it as scans on the device).  Decode and CRC then run on the stream where it lies: descriptors point into
 // d_src (token-only mode, nothing is patched) and d_dst, stored chunks are copied by one kernel over a descriptor list.
 // Every device-resident call stages its chunk list for stream_run_chunk_jobs in one of two ways, written here once: in place (stream_decode_jobs_in_place:
 // this call and the batch decode) or through the scratch (ScratchDecode: the searches, the grep, the record index and the sidecar build).
 // Workspace: 8 bytes per stream byte (x0, x1) + 12 bytes per 4 KiB + 32 bytes per table entry.
-
-#include "mlz_stream_walk.h"
-#include "mlz_stream_batch.h"
-#include "mlz_stream_ranges.h"
 
 namespace mlz {
 
@@ -144,10 +141,8 @@ __global__ __launch_bounds__(64) void walk_mid_kernel(uint64_t n, uint32_t nreg1
     }
 }
 
-// W5: the chunk headers of one entered 4 KiB region, in order.  EMIT = false counts the table's entries, EMIT = true writes them.
+// W5: the chunk headers of one entered 4 KiB region, in order (walk_headers).  EMIT = false counts the table's entries, EMIT = true writes them.
 // keep_search: the walk of a sidecar, whose info, table and reference chunks (0x44, 0x45, 0x47) enter the table like the others.
-__host__ __device__ inline bool walk_search_chunk(uint8_t type) { return type == 0x44 || type == 0x45 || type == 0x47; }
-inline bool walk_search_chunk_type(const WalkChunk& w) { return walk_search_chunk(uint8_t(w.tl >> 24)); }
 template <bool EMIT>
 __global__ __launch_bounds__(64) void walk_list_kernel(const uint8_t* __restrict__ src, uint64_t n, uint32_t nreg0, const uint32_t* __restrict__ entry0,
                                                        uint32_t* __restrict__ counts, const uint32_t* __restrict__ first, WalkChunk* __restrict__ table, bool keep_search) {
@@ -158,22 +153,12 @@ __global__ __launch_bounds__(64) void walk_list_kernel(const uint8_t* __restrict
     if (ent != kWalkNoEntry) {
         const uint64_t base = uint64_t(r0) << kWalkR0Log;
         const uint64_t end = base + kWalkR0 < n ? base + kWalkR0 : n;
-        uint64_t e = base + ent;
         const uint32_t at = EMIT ? first[r0] : 0;
-        while (e < end) {
-            if (n - e < 4) {   // the stub the orbit ends on
-                if (EMIT) table[at + cnt] = walk_classify(src, n, e);
-                cnt++;
-                break;
-            }
-            uint8_t type;
-            const uint32_t clen = walk_header(src, e, &type);
-            if (!walk_skippable(type, clen, n - e - 4) || (keep_search && walk_search_chunk(type))) {
-                if (EMIT) table[at + cnt] = walk_classify(src, n, e);
-                cnt++;
-            }
-            e += 4 + uint64_t(clen);
-        }
+        walk_headers(src, n, base + ent, end, keep_search, kWalkNoCap, [&](uint64_t e) {
+            if (EMIT) table[at + cnt] = walk_classify(src, n, e);
+            cnt++;
+            return true;
+        });
     }
     if (!EMIT) counts[r0] = cnt;
 }
@@ -281,26 +266,16 @@ int stream_walk_device(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, size_t 
     if (side) {   // the Reader never sees a search chunk that lies inside the stream
         side->assign(table, table + h_total);
         for (const mlz::WalkChunk& w : *side)
-            if (!(mlz::walk_search_chunk_type(w) && !(w.flags & (mlz::kWalkTrunc | mlz::kWalkStub)))) others.push_back(w);
+            if (!(mlz::walk_search_chunk(uint8_t(w.tl >> 24)) && !(w.flags & (mlz::kWalkTrunc | mlz::kWalkStub)))) others.push_back(w);
         table = others.data(); n_table = others.size();
     }
     if (n_ident)
         for (size_t i = 0; i < n_table; i++)
             if (!(table[i].flags & mlz::kWalkStub) && (table[i].tl >> 24) == 0xff && (*n_ident)++ == 0 && ident_byte) *ident_byte = uint8_t(table[i].val);
     chunks->reserve(n_table);
-    *parsed = mlz::walk_parse_table(table, n_table, kMaxBlockSize,
-                                 [&](uint8_t type, uint32_t crc, uint64_t body_off, uint64_t body_len, uint64_t nn, uint64_t out_off, uint64_t hdr_off) {
-                                     StreamChunk ck{};
-                                     ck.type = type; ck.crc = crc; ck.body_off = size_t(body_off); ck.body_len = size_t(body_len); ck.n = size_t(nn); ck.out_off = size_t(out_off);
-                                     ck.hdr_off = size_t(hdr_off);
-                                     chunks->push_back(ck);
-                                 });
+    *parsed = mlz::walk_parse_table(table, n_table, kMaxBlockSize, stream_chunk_sink(chunks));
     return 0;
 }
-
-// One chunk of a decode list: `at` is where a compressed chunk (0x02 / 0x03) is decoded to, and where the bytes of a stored one (0x01) lie
-// for its CRC.  The targets of one list may lie in several allocations (the caller's destination, the context's scratch, the stream itself).
-struct ChunkJob { size_t ck; const uint8_t* at; };
 
 // What comes back per job, in c->pinned2: the caller takes the regions from its carve of that buffer, in front of its last ensure
 struct ChunkJobResults { Region<int64_t> len; Region<uint32_t> crc; };
@@ -309,7 +284,8 @@ ChunkJobResults take_chunk_job_results(Carve* pin, size_t nj) { return ChunkJobR
 // The decode / CRC / verdict of a list of chunks of a stream that lies at d_src, shared by the whole-stream call and the range read.  jobs: in
 // stream order; gend[g]: one past the last job of group g (range_group_ends: about 64 MiB of chunk output).  Per group one decode launch
 // sequence (token-only mode: d_src is not touched) and one CRC launch over all its chunks — 0x01 / 0x02 over the bytes at `at`, 0x03 over the
-// token bytes in the stream —, each with the lowest target address as its base pointer and the targets' distances from it in the descriptors;
+// token bytes in the stream —, each with the lowest target address as its base pointer and the targets' distances from it in the descriptors
+// (chunk_group_descs, which the host decode's pipeline fills its launches from as well);
 // after_group(g) is then called with sm still running (the range read enqueues the group's copy there).  One synchronise at the end; per chunk
 // 8 + 4 bytes of results come back, to `res`.  The caller has begun the decode call, sized c->pinned2 for its carve (res is part of it)
 // and holds c->mu.  Returns 0 or the error of the first failing chunk of the list.  per_job (the batch calls, whose list holds many streams):
@@ -326,37 +302,22 @@ int64_t stream_run_chunk_jobs(mlz_ctx* c, hipStream_t sm, bool ignore_crc, const
     if (c->pinned2_cap < res.crc.off + sizeof(uint32_t) * nj) { c->err = "stream_run_chunk_jobs: the result buffer was not sized"; return -MLZ_ERR_HIP; }
     int64_t* h_len = res.len.at(c->pinned2);
     uint32_t* h_crc = res.crc.at(c->pinned2);
-    std::vector<mlz_block_desc> ddesc, cdesc;
+    ChunkGroupDescs gd;
     std::vector<size_t> res_idx(nj, 0);
     size_t n_dec = 0;
     int r = 0;
     for (size_t g = 0, j0 = 0; g < gend.size(); j0 = gend[g++]) {
         const size_t j1 = gend[g];
-        uintptr_t dbase = ~uintptr_t(0), cbase = ~uintptr_t(0);
-        for (size_t j = j0; j < j1; j++) {
-            const StreamChunk& ck = chunks[jobs[j].ck];
-            if (ck.type != kChunkUncompressed) dbase = std::min(dbase, reinterpret_cast<uintptr_t>(jobs[j].at));
-            cbase = std::min(cbase, reinterpret_cast<uintptr_t>(ck.type == kChunkMinLZCompCRC ? d_src + ck.body_off : jobs[j].at));
-        }
-        ddesc.clear(); cdesc.clear();
-        for (size_t j = j0; j < j1; j++) {
-            const StreamChunk& ck = chunks[jobs[j].ck];
-            const uintptr_t at = reinterpret_cast<uintptr_t>(jobs[j].at);
-            if (ck.type == kChunkMinLZCompCRC) cdesc.push_back(mlz_block_desc{uint64_t(reinterpret_cast<uintptr_t>(d_src + ck.body_off) - cbase), ck.body_len, 0, 0});
-            else cdesc.push_back(mlz_block_desc{uint64_t(at - cbase), ck.n, 0, 0});
-            if (ck.type == kChunkUncompressed) continue;
-            res_idx[j] = n_dec + ddesc.size();
-            ddesc.push_back(mlz_block_desc{ck.body_off, ck.body_len, uint64_t(at - dbase), ck.n});
-        }
-        if (!ddesc.empty()) {
-            r = decode_device_locked(c, sm, d_src, reinterpret_cast<uint8_t*>(dbase), ddesc.data(), int(ddesc.size()), c->d_len.as<int64_t>() + n_dec, true, nullptr, false);
+        chunk_group_descs(d_src, 0, chunks, jobs.data(), j0, j1, n_dec, res_idx.data(), &gd);
+        if (!gd.dec.empty()) {
+            r = decode_device_locked(c, sm, d_src, reinterpret_cast<uint8_t*>(gd.dbase), gd.dec.data(), int(gd.dec.size()), c->d_len.as<int64_t>() + n_dec, true, nullptr, false);
             if (r) return r;
         }
         if (!ignore_crc) {
-            r = crc_device_locked(c, sm, reinterpret_cast<const uint8_t*>(cbase), cdesc.data(), int(j1 - j0), c->d_crc.as<uint32_t>() + j0);
+            r = crc_device_locked(c, sm, reinterpret_cast<const uint8_t*>(gd.cbase), gd.crc.data(), int(j1 - j0), c->d_crc.as<uint32_t>() + j0);
             if (r) return r;
         }
-        n_dec += ddesc.size();
+        n_dec += gd.dec.size();
         r = after_group(g);
         if (r) return r;
     }

@@ -208,15 +208,17 @@ def test_stream_abi_errors(ctx):
     assert mz.stream_decode(kat, ctx=ctx) == b"abcd"
 
 
-def _to_compcrc(stream):
-    """Rewrite every 0x02 chunk as 0x03 (same body; the CRC covers the token bytes, SPEC chunk 0x03 / reader.go:341-344)."""
+def _to_compcrc(stream, every=1):
+    """Rewrite every 0x02 chunk (every = 2: every second one, the first included) as 0x03 (same body; the CRC covers the token bytes, SPEC
+    chunk 0x03 / reader.go:341-344)."""
     from minlz_amd.stream import uvarint
     b = bytearray(stream)
-    p = 0
+    p = seen = 0
     while p + 4 <= len(b):
         t = b[p]
         n = b[p + 1] | b[p + 2] << 8 | b[p + 3] << 16
-        if t == 0x02:
+        seen += t == 0x02
+        if t == 0x02 and (seen - 1) % every == 0:
             _, hl = uvarint(b, p + 8)
             b[p] = 0x03
             b[p + 4:p + 8] = O.crc(bytes(b[p + 8 + hl:p + 4 + n])).to_bytes(4, "little")
@@ -242,3 +244,77 @@ def test_chunk_type_3_crc_over_compressed_bytes(ctx):
     with pytest.raises(mz.MinLZError) as got:
         mz.stream_decode(bytes(bad), ctx=ctx)
     assert got.value.code == want.value.code
+
+
+def _abi_decode(ctx, st, cap, pinned):
+    """mlz_stream_decode into pageable memory or into a page-locked destination (which the kernels write through its device alias) -> (result, bytes)."""
+    import torch
+    from minlz_amd import _lib
+    src = np.frombuffer(st, dtype=np.uint8)
+    dst = torch.zeros(max(cap, 1), dtype=torch.uint8, pin_memory=pinned)
+    r = _lib.lib().mlz_stream_decode(ctx.handle, 0, src.ctypes.data, src.size, dst.data_ptr(), cap)
+    return r, dst.numpy()[:max(r, 0)].tobytes()
+
+
+def test_one_crc_launch_over_three_chunk_kinds(ctx):
+    # One group that holds stored (0x01), compressed (0x02) and compressed-CRC (0x03) chunks: every chunk's CRC comes from one launch,
+    # a 0x03 chunk's over its token bytes in the copied-in stream, the others' over the output.  Pageable and pinned destination, good
+    # CRCs and a bad one in a chunk of each kind, two bad ones, and a bad body under a bad CRC: the oracle's code every time.
+    from tests import corrupt as CM
+    bs = 64 << 10
+    d = synth.text_like(5 * bs, 71).tobytes() + synth.random_bytes(2 * bs, seed=72).tobytes() + synth.text_like(5 * bs - 1234, 73).tobytes()
+    s = _to_compcrc(O.stream_encode(d, 1, bs), every=2)
+    data = [c for c in CM.chunks(s) if c.type in (1, 2, 3)]
+    assert len(data) == 12 and {c.type for c in data} == {1, 2, 3}
+    assert O.stream_decode(s, len(d)) == d
+
+    def code_of(b):
+        want = CM.stream_verdict(b, len(d))[0]
+        for pinned in (False, True):
+            r, out = _abi_decode(ctx, b, len(d), pinned)
+            assert (r, out) == (len(d), d) if want == 0 else r == -want, (pinned, r, want)
+        return want
+
+    assert code_of(s) == 0
+    first = {t: next(c for c in data if c.type == t) for t in (1, 2, 3)}
+    for t in (1, 2, 3):                                              # a CRC byte of one chunk of each kind
+        bad = bytearray(s)
+        bad[first[t].off + 5] ^= 0x21
+        assert code_of(bytes(bad)) == O.ERR_CRC, t
+    bad = bytearray(s)                                               # a 0x03 chunk in front, a 0x01 chunk behind it
+    assert first[3].off < first[1].off
+    bad[first[3].off + 4] ^= 0x80
+    bad[first[1].off + 7] ^= 0x01
+    assert code_of(bytes(bad)) == O.ERR_CRC
+    # a body byte of a 0x03 chunk: its CRC (over the token bytes) is then wrong as well, and the body's error comes first
+    c3 = [c for c in data if c.type == 3][1]
+    for at in range(c3.off + 16, c3.off + 4 + c3.clen):
+        bad = bytearray(s)
+        bad[at] ^= 0xFF
+        if CM.stream_verdict(bytes(bad), len(d))[0] == O.ERR_CORRUPT:
+            break
+    else:
+        assert False, "no byte of the chunk's body makes the oracle's decode fail"
+    assert code_of(bytes(bad)) == O.ERR_CORRUPT
+
+
+def test_three_groups_of_chunks(ctx):
+    # 17 chunks of 8 MiB: groups of 8, 8 and 1 chunks by the close-at-64-MiB rule — a full middle group and a last group of one chunk, the
+    # smallest shape at which a group's place among the results and the split of the chunks over two workers can go wrong.
+    from tests import corrupt as CM
+    bs = 8 << 20
+    d = synth.text_like(17 * bs, 81).tobytes()
+    s = mz.stream_encode(d, 1, bs, ctx=ctx)
+    data = [c for c in CM.chunks(s) if c.type in (1, 2, 3)]
+    assert len(data) == 17
+    bad = bytearray(s)
+    bad[data[-1].off + 6] ^= 0x04                                    # a CRC byte of the last chunk
+    c2 = mz.Context(devices=[0, 0])
+    try:
+        for c in (ctx, c2):
+            assert mz.stream_decode(mz.stream_encode(d, 1, bs, ctx=c), ctx=c) == d
+            assert mz.stream_decode(s, ctx=c) == d
+            with pytest.raises(mz.ErrCRC):
+                mz.stream_decode(bytes(bad), ctx=c)
+    finally:
+        c2.close()

@@ -1,5 +1,5 @@
 // stream_batch_check.cpp — the batch calls over many streams in HBM, on the host (no GPU): the lane walk, its step cap and the verdict
-// code of minlz_amd/csrc/mlz_stream_batch.h, the SAME functions walk_batch_kernel and the batch decode run, and the record and
+// code of minlz_amd/csrc/mlz_stream_batch.h, the SAME functions walk_batch_kernel and the batch decode run, and the header step, record and
 // running-state code of mlz_stream_walk.h.  tests/test_stream_batch_host.py compares what it prints with the host Reader's chunk walk of
 // every stream alone.
 //
@@ -40,7 +40,7 @@ int walk_mode(const char* path) {
         const uint8_t* src = buf.data() + off;
         bool is_long = false, again = false;
         uint32_t cnt = batch_walk_lane<false>(src, len, kBatchWalkSteps, nullptr, 0, &is_long);
-        const uint32_t cap = is_long ? 0xffffffffu : kBatchWalkSteps;
+        const uint32_t cap = is_long ? kWalkNoCap : kBatchWalkSteps;
         if (is_long) cnt = batch_walk_lane<false>(src, len, cap, nullptr, 0, &again);
         table.assign(cnt, WalkChunk{});
         const uint32_t put = batch_walk_lane<true>(src, len, cap, table.data(), cnt, &again);

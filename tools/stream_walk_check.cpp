@@ -1,11 +1,14 @@
 // stream_walk_check.cpp — the device-resident Reader's chunk walk, on the host (no GPU): the region algorithm of
 // minlz_amd/csrc/mlz_stream_walk.hip.inc restated in plain C++ (exits of every offset from its 4 KiB region, lifted to 256 KiB regions, the
-// entries followed top-down, the chunk headers of every entered region listed), then the SAME record and running-state code the library
-// uses (mlz_stream_walk.h).  tests/test_stream_device_host.py compares its verdicts with the host Reader's chunk walk (stream_parse).
+// entries followed top-down; the chunk headers of every entered region listed by the library's own step, walk_headers), then the SAME record
+// and running-state code the library uses (mlz_stream_walk.h).  Beside it the host Reader's walk as stream_parse runs it: the same step,
+// record and state from offset 0, stopping at the first error.  tests/test_stream_device_host.py compares both with the library's host
+// Reader and with the oracle; under the sanitizers the exact-size buffer shows that neither reads a byte past the stream's end.
 //
 //   g++ -O2 -std=c++17 -o swc tools/stream_walk_check.cpp && ./swc streams.bin
-// streams.bin: for every stream a little-endian u64 length and its bytes.  One line per stream: `<result> <prefix_len> <table entries>`,
-// result as mlz_stream_decoded_len, prefix_len as mlz_stream_decoded_prefix_len.
+// streams.bin: for every stream a little-endian u64 length and its bytes.  One line per stream: `<result> <prefix_len> <table entries>
+// <host result> <host prefix_len>`, result as mlz_stream_decoded_len, prefix_len as mlz_stream_decoded_prefix_len; the first three from the
+// region walk, the last two from the host Reader's walk.
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -74,14 +77,23 @@ void walk(const uint8_t* src, uint64_t n, std::vector<WalkChunk>* table) {
     for (uint64_t r0 = 0; r0 < nreg0; r0++) {
         if (entry0[r0] == kNone) continue;
         const uint64_t base = r0 << kR0Log, end = base + kR0 < n ? base + kR0 : n;
-        uint64_t e = base + entry0[r0];
-        while (e < end) {
-            if (n - e < 4) { table->push_back(walk_classify(src, n, e)); break; }
-            const uint32_t clen = uint32_t(src[e + 1]) | uint32_t(src[e + 2]) << 8 | uint32_t(src[e + 3]) << 16;
-            if (!walk_skippable(src[e], clen, n - e - 4)) table->push_back(walk_classify(src, n, e));
-            e += 4 + uint64_t(clen);
-        }
+        walk_headers(src, n, base + entry0[r0], end, false, kWalkNoCap, [&](uint64_t e) { table->push_back(walk_classify(src, n, e)); return true; });
     }
+}
+
+// The host Reader's walk (stream_parse in mlz_stream.hip.inc): the headers from offset 0, a record and a step of the running state for each
+// that enters, up to the first error and not a byte further
+int64_t host_reader(const uint8_t* src, uint64_t n, uint64_t* prefix) {
+    WalkReader rd(uint64_t(8) << 20);
+    int err = 0;
+    *prefix = 0;
+    walk_headers(src, n, 0, n, false, kWalkNoCap, [&](uint64_t e) {
+        err = rd.step(walk_classify(src, n, e), [&](uint8_t, uint32_t, uint64_t, uint64_t, uint64_t nn, uint64_t out_off, uint64_t) { *prefix = out_off + nn; });
+        return err == 0;
+    });
+    const int64_t r = err ? err : rd.finish();
+    if (r >= 0) *prefix = uint64_t(r);
+    return r;
 }
 
 }  // namespace
@@ -101,7 +113,9 @@ int main(int argc, char** argv) {
         uint64_t prefix = 0;
         const int64_t r = walk_parse_table(table.data(), table.size(), uint64_t(8) << 20,
                                            [&](uint8_t, uint32_t, uint64_t, uint64_t, uint64_t nn, uint64_t out_off, uint64_t) { prefix = out_off + nn; });
-        std::printf("%lld %llu %zu\n", (long long)r, (unsigned long long)(r >= 0 ? uint64_t(r) : prefix), table.size());
+        uint64_t host_prefix = 0;
+        const int64_t host = host_reader(buf.data(), len, &host_prefix);
+        std::printf("%lld %llu %zu %lld %llu\n", (long long)r, (unsigned long long)(r >= 0 ? uint64_t(r) : prefix), table.size(), (long long)host, (unsigned long long)host_prefix);
     }
     std::fclose(f);
     return 0;
