@@ -300,7 +300,7 @@ int64_t mlz_stream_decode_device(mlz_ctx* ctx, void* stream, uint32_t flags, con
  * Decode: the chunks of all streams run as one list through the decode and CRC kernels (groups of about 64 MiB), stored chunks by one copy kernel; 12 bytes
  * per chunk come back.  Encode: the blocks of all streams through one encode and one CRC launch sequence; 12 bytes per block visit the host, which lays
  * every stream out; bodies, identifiers, EOF chunks and indexes are placed by one kernel, chunk headers by another.
- * Out of scope: search tables and sidecars in batches, an asynchronous form, a batch fanned out over several devices. */
+ * Out of scope: search tables written by the batch encode and sidecars in batches (mlz_stream_search_batch_device decodes every chunk), an asynchronous form, a batch fanned out over several devices. */
 int mlz_stream_decoded_len_batch_device(mlz_ctx* ctx, void* stream, const uint8_t* d_src, const mlz_block_desc* streams, int n_streams, int64_t* out_len,
                                         uint64_t* prefix_len);
 int mlz_stream_decode_batch_device(mlz_ctx* ctx, void* stream, uint32_t flags, const uint8_t* d_src, uint8_t* d_dst, const mlz_block_desc* streams,
@@ -437,6 +437,9 @@ int64_t mlz_dev_reader_search_many(mlz_dev_reader* reader, void* stream, uint32_
                                    uint64_t* d_counts,               /* device, n_patterns values; may be NULL */
                                    uint64_t* d_offsets, uint32_t* d_which, size_t cap,   /* device; both may be NULL when cap == 0 */
                                    uint64_t* stats /* host, may be NULL: 4 values */);
+
+/* The search over a BATCH of streams in HBM — which of these objects hold any of these keys, and where — is declared in a header of its own,
+ * include/minlz_hip_search_batch.h, which includes this one. */
 
 /* mlz_dev_reader_search_records: the RECORDS of the decoded stream that hold the pattern, each once, in stream order, packed into d_dst — what
  *   `mz search pattern file.mz` prints, and with rec_cap == 0 and dst_cap == 0 what `-c` counts.  A record is a maximal run of decoded bytes that

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/minlz_hip.h.
+"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension header include/minlz_hip_search_batch.h.
 
 There is no CPU fallback here: if libminlz_hip.so is missing or HIP is unavailable, calls raise.
 """
@@ -102,6 +102,14 @@ ABI = {
 }
 SYMBOLS = list(ABI)
 
+# The functions of the extension headers beside include/minlz_hip.h, header by header -> {name: (restype, argtypes)}, bound like the ABI's
+# (tests/test_stream_search_batch_host.py holds the table against the header's prototypes)
+ABI_EXT = {
+    "minlz_hip_search_batch.h": {
+        "mlz_stream_search_batch_device": (i64, [vp, vp, u32, vp, P(BlockDesc), i32, vp, vp, sz, P(i64), vp, vp, vp, vp, vp, vp, sz, P(u64)]),
+    },
+}
+
 _lib = None
 
 
@@ -111,7 +119,7 @@ def lib():
         if not os.path.exists(SO):
             raise RuntimeError("minlz_amd: %s not built (run python -c 'import __graft_entry__ as g; g.build()')" % SO)
         L = C.CDLL(SO)
-        for name, (restype, argtypes) in ABI.items():
+        for name, (restype, argtypes) in list(ABI.items()) + [kv for table in ABI_EXT.values() for kv in table.items()]:
             f = getattr(L, name)
             f.restype, f.argtypes = restype, argtypes
         _lib = L

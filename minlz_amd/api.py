@@ -288,6 +288,22 @@ class Context:
         self._call("mlz_stream_encode_batch_device", stream, level, block_size, _flags(add_index=add_index) | flags, d_src, d_dst, arr, n, out)
         return [int(out[i]) for i in range(n)]
 
+    def stream_search_batch_device(self, d_src, spans, patterns, d_stream_counts=None, d_pattern_counts=None, d_present=None, d_hit_stream=None, d_hit_pos=None,
+                                   d_hit_which=None, cap=0, ignore_crc=False, ignore_case=False, stream=None, flags=0):
+        """mlz_stream_search_batch_device: every stream (src_off, src_len) of the buffer at d_src searched for `patterns` (1 .. 4096 bytes objects
+        of 1 .. 256 bytes) in one call.  Device addresses or None: d_stream_counts (n uint64), d_pattern_counts (one uint64 per pattern),
+        d_present (n rows of ceil(patterns / 32) uint32: bit p of row i = pattern p occurs in stream i), d_hit_stream / d_hit_pos / d_hit_which
+        (room for `cap` uint32 / uint64 / uint32: the smallest min(total, cap) triples in (stream, position, pattern) order).
+        flags: further MLZ_* bits, as they are.
+        -> (total triples over the healthy streams, [result]: the occurrences in each stream or its -MLZ_ERR_*, (data chunks, chunks decoded over
+        all passes, streams that failed in the decode, scan passes))."""
+        arr = _block_descs(spans)
+        n = len(arr)
+        out, stats = (C.c_int64 * max(n, 1))(), _stats()
+        r = self._call("mlz_stream_search_batch_device", stream, _flags(ignore_crc=ignore_crc, ignore_case=ignore_case) | flags, d_src, arr, n, *_patterns(patterns), out,
+                       d_stream_counts, d_pattern_counts, d_present, d_hit_stream, d_hit_pos, d_hit_which, cap, stats)
+        return r, [int(out[i]) for i in range(n)], _ints(stats)
+
     def stream_open_device(self, d_src, n, stream=None):
         """mlz_stream_open_device: a stream in device memory opened for range reads -> DeviceReader.  The caller keeps d_src alive and unchanged
         while the reader is open.  A stream with a framing error raises that error (no reader)."""

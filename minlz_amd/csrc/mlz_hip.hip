@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/minlz_hip.h"
+#include "../../include/minlz_hip_search_batch.h"
 #include "mlz_format.h"
 #include "mlz_kernels.h"
 
@@ -1315,6 +1316,7 @@ int mlz_debug_idxprof(unsigned long long* out) {
 #include "mlz_stream_ranges_dev.hip.inc"
 #include "mlz_stream_search.hip.inc"
 #include "mlz_stream_search_many.hip.inc"
+#include "mlz_stream_search_batch.hip.inc"
 #include "mlz_stream_sidecar.hip.inc"
 #include "mlz_stream_records.hip.inc"
 #include "mlz_stream_record_index.hip.inc"

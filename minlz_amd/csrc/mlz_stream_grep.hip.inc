@@ -108,10 +108,10 @@ int64_t dev_reader_grep_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flag
     SearchDecode sd;
     SearchManyUpload up;
     if (n_take) {
-        search_decode_plan(rd, take, n_take, index.lmin, index.lmax, mlz::kSearchManyTile, &sd);
+        search_decode_plan(rd->chunks, take, n_take, index.lmin, index.lmax, mlz::kSearchManyTile, &sd);
         if (sd.lay.tiles.size() > 0x7fffffffu) return -MLZ_ERR_ARG;
         up.take(index, n, &cv, &pin);   // the pattern index, as the search for many lays it out
-        const int e = search_decode_ready(rd, &sd, &cv, &pin);
+        const int e = search_decode_ready(rd->ctx, rd->chunks, &sd, &cv, &pin);
         if (e) return e;
     } else {
         HIPCHK(c, c->d_rplan.ensure(cv.bytes));
@@ -127,10 +127,10 @@ int64_t dev_reader_grep_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flag
     HIPCHK(c, hipMemsetAsync(d_sel, 0, size_t(W) * 4, sm));
     if (n_take) {
         const mlz::SearchTile* d_tiles = sd.tiles.at(ws);
-        const mlz::SearchManyMark mk{D, rd->index_k, d_sel};
+        const mlz::SearchManyMark mk{D, rd->index_k, d_sel, nullptr, 0};
         const int e = up.send(c, sm, index, patterns, n);
         if (e) return e;
-        const int64_t r = search_decode_run(rd, sm, ignore_crc, &sd, [&](size_t, size_t t0, size_t t1) {
+        const int64_t r = search_decode_run(rd->ctx, rd->d_src, rd->chunks, sm, ignore_crc, &sd, [&](size_t, size_t t0, size_t t1) {
             hipLaunchKernelGGL(search_many_kernel_of<mlz::kSearchManyMarkRecords>(fold), dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), up.lds_bytes, sm, c->d_range.as<uint8_t>(), d_tiles,
                                uint32_t(t0), up.ix, static_cast<uint32_t*>(nullptr), static_cast<unsigned long long*>(nullptr), static_cast<const uint64_t*>(nullptr), uint64_t(0),
                                static_cast<uint64_t*>(nullptr), static_cast<uint32_t*>(nullptr), mk);

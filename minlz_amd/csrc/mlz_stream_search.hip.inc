@@ -362,35 +362,43 @@ struct SearchDecode {
     Region<mlz::SearchTile> tiles, htiles;
 };
 
+// The groups (range_group_ends), every chunk's place and the tiles (search_layout) of a decode list that stands in sd->dec.jobs; out_off_of(i):
+// job i's place in the decoded sequence the layout sees (a stream's own positions; the virtual positions of a batch of streams)
+template <class Off>
+void search_decode_layout(const std::vector<StreamChunk>& chunks, Off out_off_of, uint32_t lmin, uint32_t lmax, uint32_t tile, SearchDecode* sd) {
+    const std::vector<ChunkJob>& jobs = sd->dec.jobs;
+    mlz::range_group_ends(jobs.size(), [&](size_t i) { return uint64_t(chunks[jobs[i].ck].n); }, &sd->dec.gend);
+    mlz::search_layout(jobs.size(), sd->dec.gend, out_off_of, [&](size_t i) { return uint64_t(chunks[jobs[i].ck].n); }, lmin, lmax, tile, &sd->lay);
+    sd->dec.at = sd->lay.at;
+}
+
+// The three helpers below take the context, the stream's bytes and its chunk table, not a handle: the handle calls pass rd->ctx, rd->d_src and
+// rd->chunks, the search over a batch of streams (mlz_stream_search_batch.hip.inc) its batch's.
 // lmin, lmax: the shortest and the longest pattern of the call; tile: the most start positions of a tile (search_layout)
-void search_decode_plan(const mlz_dev_reader* rd, const std::vector<uint8_t>& take, size_t n_take, uint32_t lmin, uint32_t lmax, uint32_t tile, SearchDecode* sd) {
+void search_decode_plan(const std::vector<StreamChunk>& chunks, const std::vector<uint8_t>& take, size_t n_take, uint32_t lmin, uint32_t lmax, uint32_t tile, SearchDecode* sd) {
     std::vector<ChunkJob>& jobs = sd->dec.jobs;
     jobs.reserve(n_take);
-    for (size_t k = 0; k < rd->chunks.size(); k++) if (take[k]) jobs.push_back(ChunkJob{k, nullptr});
-    mlz::range_group_ends(jobs.size(), [&](size_t i) { return uint64_t(rd->chunks[jobs[i].ck].n); }, &sd->dec.gend);
-    mlz::search_layout(jobs.size(), sd->dec.gend, [&](size_t i) { return uint64_t(rd->chunks[jobs[i].ck].out_off); }, [&](size_t i) { return uint64_t(rd->chunks[jobs[i].ck].n); },
-                       lmin, lmax, tile, &sd->lay);
-    sd->dec.at = sd->lay.at;
+    for (size_t k = 0; k < chunks.size(); k++) if (take[k]) jobs.push_back(ChunkJob{k, nullptr});
+    search_decode_layout(chunks, [&](size_t i) { return uint64_t(chunks[jobs[i].ck].out_off); }, lmin, lmax, tile, sd);
 }
 
 // Behind the caller's own regions: carried bytes | tiles in the workspace (c->d_rplan), the decode's | tiles in the pinned buffer; then every
 // buffer of the call, once: the workspace and the pinned buffer as they are carved now, the scratch, the copies' descriptors
-int search_decode_ready(mlz_dev_reader* rd, SearchDecode* sd, Carve* cv, Carve* pin) {
-    mlz_ctx* c = rd->ctx;
+int search_decode_ready(mlz_ctx* c, const std::vector<StreamChunk>& chunks, SearchDecode* sd, Carve* cv, Carve* pin) {
     const size_t nt = sd->lay.tiles.size();
     sd->carry = cv->take<uint8_t>(mlz::kSearchMaxPattern);
     sd->tiles = cv->take<mlz::SearchTile>(nt);
-    if (const int e = sd->dec.take(c, rd->chunks, pin)) return e;
+    if (const int e = sd->dec.take(c, chunks, pin)) return e;
     sd->htiles = pin->take<mlz::SearchTile>(nt, 64);
     HIPCHK(c, c->d_rplan.ensure(cv->bytes));
     return ensure_stream_objects(c, 0, pin->bytes);
 }
 
 // Decodes the set group by group into the scratch, calls scan(g, t0, t1) for the tiles [t0, t1) of group g with its bytes in place, and
-// carries a run's last bytes in front of the next group.  Returns stream_run_chunk_jobs' verdict.
+// carries a run's last bytes in front of the next group.  Returns stream_run_chunk_jobs' verdict (with per_job: every job's own, and 0).
 template <class Scan>
-int64_t search_decode_run(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, SearchDecode* sd, Scan scan) {
-    mlz_ctx* c = rd->ctx;
+int64_t search_decode_run(mlz_ctx* c, const uint8_t* d_src, const std::vector<StreamChunk>& chunks, hipStream_t sm, bool ignore_crc, SearchDecode* sd, Scan scan,
+                          std::vector<int64_t>* per_job = nullptr) {
     const mlz::SearchLayout& lay = sd->lay;
     const size_t nt = lay.tiles.size();
     uint8_t *scratch = c->d_range.as<uint8_t>(), *d_carry = sd->carry.at(c->d_rplan.p);
@@ -399,7 +407,7 @@ int64_t search_decode_run(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, S
         std::memcpy(h_tiles, lay.tiles.data(), nt * sizeof(mlz::SearchTile));
         HIPCHK(c, hipMemcpyAsync(d_tiles, h_tiles, nt * sizeof(mlz::SearchTile), hipMemcpyHostToDevice, sm));
     }
-    return sd->dec.run(c, sm, ignore_crc, rd->d_src, rd->chunks, [&](size_t g) -> int {
+    return sd->dec.run(c, sm, ignore_crc, d_src, chunks, [&](size_t g) -> int {
         const size_t t0 = g ? lay.tile_end[g - 1] : 0, t1 = lay.tile_end[g];
         if (t1 > t0) { const int e = scan(g, t0, t1); if (e) return e; }
         if (lay.carry[g]) {   // the run goes on in the next group: its last bytes in front of that group's first chunk
@@ -407,7 +415,7 @@ int64_t search_decode_run(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, S
             HIPCHK(c, hipMemcpyAsync(scratch + mlz::kSearchPad - lay.carry[g], d_carry, lay.carry[g], hipMemcpyDeviceToDevice, sm));
         }
         return 0;
-    });
+    }, per_job);
 }
 
 // The opening of both searches: counters 10 and 11 cleared, stats = {data chunks, 0, 0, 0}
@@ -450,7 +458,7 @@ int64_t dev_reader_search_scan_locked(mlz_dev_reader* rd, hipStream_t sm, uint32
 
     // the decode list, its groups, every chunk's place in the scratch and the tiles of start positions (search_layout), the stored chunks' copies
     SearchDecode sd;
-    search_decode_plan(rd, take, n_take, L, L, mlz::kSearchTile, &sd);
+    search_decode_plan(rd->chunks, take, n_take, L, L, mlz::kSearchTile, &sd);
     const size_t nt = sd.lay.tiles.size();
     if (nt > 0x7fffffffu) return -MLZ_ERR_ARG;
     Carve cv, pin;   // workspace: pattern | total | counts | prefix | bitmaps | the decode's; pinned: pattern | the decode's
@@ -459,7 +467,7 @@ int64_t dev_reader_search_scan_locked(mlz_dev_reader* rd, hipStream_t sm, uint32
     const auto r_counts = cv.take<uint32_t>(nt, 4);
     const auto r_prefix = cv.take<uint64_t>(nt), r_masks = cv.take<uint64_t>(nt * mlz::kSearchTileWords, 8);
     const auto r_hpat = pin.take<uint8_t>(mlz::kSearchMaxPattern + 16, 8);
-    int e = search_decode_ready(rd, &sd, &cv, &pin);
+    int e = search_decode_ready(rd->ctx, rd->chunks, &sd, &cv, &pin);
     if (e) return e;
     uint8_t *ws = r_pat.at(c->d_rplan.p), *h_pat = r_hpat.at(c->pinned2);
     std::memcpy(h_pat, pattern, L);
@@ -469,7 +477,7 @@ int64_t dev_reader_search_scan_locked(mlz_dev_reader* rd, hipStream_t sm, uint32
     { WorkspaceOrder order(c, sm); }
     HIPCHK(c, hipMemcpyAsync(ws, h_pat, L, hipMemcpyHostToDevice, sm));
     HIPCHK(c, hipMemsetAsync(d_total, 0, 16, sm));
-    const int64_t r = search_decode_run(rd, sm, ignore_crc, &sd, [&](size_t, size_t t0, size_t t1) {
+    const int64_t r = search_decode_run(rd->ctx, rd->d_src, rd->chunks, sm, ignore_crc, &sd, [&](size_t, size_t t0, size_t t1) {
         hipLaunchKernelGGL(fold ? mlz::search_scan_kernel<true> : mlz::search_scan_kernel<false>, dim3(uint32_t(t1 - t0)), dim3(256), 0, sm, c->d_range.as<uint8_t>(), d_tiles, uint32_t(t0), ws, L, d_masks, d_counts);
         return 0;
     });

@@ -1,0 +1,216 @@
+// mlz_stream_search_batch.hip.inc — mlz_stream_search_batch_device: which streams of a batch in HBM hold which of up to 4096 byte strings, and
+// where (included behind mlz_stream_batch.hip.inc, whose walk and argument checks it uses, and mlz_stream_search_many.hip.inc, whose pattern
+// index, decode helpers and scan kernel it runs).
+//
+// The batch is laid out as ONE decoded sequence with a one-byte hole behind every stream (mlz_stream_search_batch.h: the virtual positions),
+// so search_layout, the scratch decode and search_many_kernel run as they do for one stream: the chunks of all healthy streams form one job
+// list in descriptor order, decoded group by group into the scratch; per group search_many_kernel<kSearchManyCount> counts, search_prefix_kernel
+// continues the running prefix over ALL tiles, <kSearchManyWrite> writes (virtual position, pattern) below cap and <kSearchManyMarkStreams>
+// sets the presence bits.  search_batch_finish_kernel then gives every stream its count (the prefix at its tiles' ends) and turns every written
+// virtual position into (stream, position).  A stream whose decode or CRC fails is known only when the job results come back, with its garbage
+// scanned: it is then dropped from the list and the whole scan runs once more over the rest (failures are deterministic: two passes at the most).
+
+#include "mlz_stream_search_batch.h"
+
+namespace mlz {
+
+// After the last group.  A lane per stream: counts[i] (and stream_counts[i], when given) = the pairs of stream i's tiles.  A lane per written
+// triple: hit_stream[k] = the stream of the virtual position hit_pos[k], which becomes the position inside that stream.  vbase: n + 1 values.
+__global__ __launch_bounds__(256) void search_batch_finish_kernel(const uint64_t* __restrict__ prefix, const uint64_t* __restrict__ total, uint32_t nt,
+                                                                  const uint32_t* __restrict__ tile_first, const uint64_t* __restrict__ vbase, uint32_t n,
+                                                                  uint64_t* __restrict__ counts, uint64_t* __restrict__ stream_counts, uint64_t cap,
+                                                                  uint32_t* __restrict__ hit_stream, uint64_t* __restrict__ hit_pos) {
+    const uint64_t all = *total, written = all < cap ? all : cap, step = uint64_t(gridDim.x) * 256;
+    for (uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += step) {
+        const uint64_t v = batch_stream_count([&](size_t t) { return prefix[t]; }, nt, all, tile_first, size_t(i));
+        counts[i] = v;
+        if (stream_counts) stream_counts[i] = v;
+    }
+    for (uint64_t k = uint64_t(blockIdx.x) * 256 + threadIdx.x; k < written; k += step) {
+        const uint64_t v = hit_pos[k];
+        const size_t s = batch_stream_of(vbase, n, v);
+        hit_stream[k] = uint32_t(s);
+        hit_pos[k] = v - vbase[s];
+    }
+}
+
+}  // namespace mlz
+
+namespace {
+
+struct SearchBatchOut {
+    uint64_t *d_stream_counts, *d_pattern_counts;
+    uint32_t* d_present;
+    uint32_t* d_hit_stream;
+    uint64_t* d_hit_pos;
+    uint32_t* d_hit_which;
+    uint64_t cap;
+};
+
+// One pass: the streams with alive[i] are decoded and scanned.  rc[i] = 0 or the stream's first failing chunk's error; *total and counts[i]
+// are valid (and the device outputs written) when no stream failed.  *n_jobs: the chunks the pass decoded.
+int64_t stream_search_batch_pass(mlz_ctx* c, hipStream_t sm, bool ignore_crc, bool fold, const uint8_t* d_src, const BatchWalk& bw, size_t n, const std::vector<uint8_t>& alive,
+                                 const mlz::SearchManyIndex& index, const uint8_t* patterns, size_t np, const SearchBatchOut& out, std::vector<int64_t>* rc,
+                                 std::vector<uint64_t>* counts, uint64_t* total, size_t* n_jobs, bool* failed) {
+    // the virtual positions and the one job list: every alive stream's chunks that have bytes, in descriptor order
+    std::vector<uint64_t> size(n, 0), vbase(n + 1, 0);
+    for (size_t i = 0; i < n; i++) if (alive[i]) size[i] = bw.prefix(i);
+    mlz::batch_vbases(size.data(), n, vbase.data());
+    SearchDecode sd;
+    std::vector<ChunkJob>& jobs = sd.dec.jobs;
+    std::vector<size_t> job_first(n + 1, 0);
+    std::vector<uint64_t> voff;
+    for (size_t i = 0; i < n; i++) {
+        job_first[i] = jobs.size();
+        for (size_t k = bw.c0[i]; alive[i] && k < bw.c1[i]; k++)
+            if (bw.chunks[k].n) { jobs.push_back(ChunkJob{k, nullptr}); voff.push_back(vbase[i] + bw.chunks[k].out_off); }
+    }
+    job_first[n] = jobs.size();
+    *n_jobs = jobs.size();
+    search_decode_layout(bw.chunks, [&](size_t j) { return voff[j]; }, index.lmin, index.lmax, mlz::kSearchManyTile, &sd);
+    const size_t nt = sd.lay.tiles.size();
+    if (nt > 0x7fffffffu) return -MLZ_ERR_ARG;
+    std::vector<uint32_t> tile_stream(nt), tile_first(n + 1);
+    if (!mlz::batch_tile_streams(sd.lay.tiles.data(), nt, vbase.data(), n, tile_stream.data(), tile_first.data())) {
+        c->err = "stream_search_batch: a tile crosses a stream";
+        return -MLZ_ERR_HIP;
+    }
+    const size_t words = (np + 31) / 32;
+    Carve cv, pin;   // workspace: pattern counts | total | the index | tile counts | prefix | tile streams | tile firsts | vbase | stream counts | the decode's
+    const auto r_pc = cv.take<unsigned long long>(np);
+    const auto r_total = cv.take<uint64_t>(2);
+    SearchManyUpload up;
+    up.take(index, np, &cv, &pin);
+    const auto r_tc = cv.take<uint32_t>(nt, 4);
+    const auto r_prefix = cv.take<uint64_t>(nt);
+    // (tile streams | tile firsts | vbase go up as one block; stream counts | total come back as one)
+    Carve blk;
+    const auto u_ts = blk.take<uint32_t>(nt, 4), u_tf = blk.take<uint32_t>(n + 1, 4);
+    const auto u_vb = blk.take<uint64_t>(n + 1, 8);
+    const auto r_blk = cv.take<uint8_t>(blk.bytes), h_blk = pin.take<uint8_t>(blk.bytes);
+    const auto r_sc = cv.take<uint64_t>(n + 1);
+    const auto h_sc = pin.take<uint64_t>(n + 1);
+    int e = search_decode_ready(c, bw.chunks, &sd, &cv, &pin);
+    if (e) return e;
+    void* ws = c->d_rplan.p;
+    unsigned long long* d_pc = r_pc.at(ws);
+    uint64_t *d_total = r_total.at(ws), *d_prefix = r_prefix.at(ws), *d_sc = r_sc.at(ws);
+    uint32_t* d_tc = r_tc.at(ws);
+    uint8_t *d_blk = r_blk.at(ws), *hb = h_blk.at(c->pinned2);
+    const uint32_t *d_ts = u_ts.at(d_blk), *d_tf = u_tf.at(d_blk);
+    const uint64_t* d_vb = u_vb.at(d_blk);
+    const mlz::SearchTile* d_tiles = sd.tiles.at(ws);
+    if (nt) std::memcpy(u_ts.at(hb), tile_stream.data(), nt * 4);
+    std::memcpy(u_tf.at(hb), tile_first.data(), (n + 1) * 4);
+    std::memcpy(u_vb.at(hb), vbase.data(), (n + 1) * 8);
+    { WorkspaceOrder order(c, sm); }
+    HIPCHK(c, hipMemsetAsync(d_pc, 0, np * sizeof(unsigned long long), sm));
+    HIPCHK(c, hipMemsetAsync(d_total, 0, 16, sm));
+    if (out.d_present) HIPCHK(c, hipMemsetAsync(out.d_present, 0, n * words * 4, sm));
+    HIPCHK(c, hipMemcpyAsync(d_blk, hb, blk.bytes, hipMemcpyHostToDevice, sm));
+    if ((e = up.send(c, sm, index, patterns, np))) return e;
+    const mlz::SearchManyMark mk{nullptr, 0, out.d_present, d_ts, uint32_t(words)};
+    std::vector<int64_t> job_rc;
+    const int64_t r = search_decode_run(c, d_src, bw.chunks, sm, ignore_crc, &sd, [&](size_t, size_t t0, size_t t1) {
+        const uint8_t* scratch = c->d_range.as<uint8_t>();
+        const dim3 grid(uint32_t(t1 - t0)), block(mlz::kSearchManyThreads);
+        hipLaunchKernelGGL(search_many_kernel_of<mlz::kSearchManyCount>(fold), grid, block, up.lds_bytes, sm, scratch, d_tiles, uint32_t(t0), up.ix, d_tc, d_pc,
+                           static_cast<const uint64_t*>(nullptr), uint64_t(0), static_cast<uint64_t*>(nullptr), static_cast<uint32_t*>(nullptr), mlz::SearchManyMark{});
+        hipLaunchKernelGGL(mlz::search_prefix_kernel, dim3(1), dim3(1024), 0, sm, d_tc, uint32_t(t0), uint32_t(t1), d_prefix, d_total);
+        if (out.cap) hipLaunchKernelGGL(search_many_kernel_of<mlz::kSearchManyWrite>(fold), grid, block, up.lds_bytes, sm, scratch, d_tiles, uint32_t(t0), up.ix, d_tc, d_pc,
+                                        static_cast<const uint64_t*>(d_prefix), out.cap, out.d_hit_pos, out.d_hit_which, mlz::SearchManyMark{});
+        if (out.d_present) hipLaunchKernelGGL(search_many_kernel_of<mlz::kSearchManyMarkStreams>(fold), grid, block, up.lds_bytes, sm, scratch, d_tiles, uint32_t(t0), up.ix,
+                                              static_cast<uint32_t*>(nullptr), static_cast<unsigned long long*>(nullptr), static_cast<const uint64_t*>(nullptr), uint64_t(0),
+                                              static_cast<uint64_t*>(nullptr), static_cast<uint32_t*>(nullptr), mk);
+        return 0;
+    }, &job_rc);
+    if (r < 0) return r;
+    std::vector<int64_t> zero(n, 0);
+    rc->assign(n, 0);
+    mlz::batch_stream_verdicts(zero.data(), job_first.data(), job_rc.data(), n, rc->data());
+    *failed = false;
+    for (size_t i = 0; i < n; i++) *failed = *failed || (*rc)[i] < 0;
+    if (*failed) {   // what this pass wrote is void; the caller clears the triples it may have written: it needs the pass's total for that
+        if (nt == 0) { *total = 0; return 0; }
+        if ((e = fetch(c, sm, c->pinned2, d_total, 8))) return e;
+        *total = *static_cast<const uint64_t*>(c->pinned2);
+        return 0;
+    }
+    const uint64_t lanes = std::max<uint64_t>(n, out.cap);
+    hipLaunchKernelGGL(mlz::search_batch_finish_kernel, dim3(uint32_t(std::min<uint64_t>((lanes + 255) / 256, 4096))), dim3(256), 0, sm, d_prefix, d_total, uint32_t(nt), d_tf, d_vb,
+                       uint32_t(n), d_sc, out.d_stream_counts, out.cap, out.d_hit_stream, out.d_hit_pos);
+    if (out.d_pattern_counts) HIPCHK(c, hipMemcpyAsync(out.d_pattern_counts, d_pc, np * 8, hipMemcpyDeviceToDevice, sm));
+    HIPCHK(c, hipMemcpyAsync(d_sc + n, d_total, 8, hipMemcpyDeviceToDevice, sm));
+    uint64_t* h = h_sc.at(c->pinned2);
+    if ((e = fetch(c, sm, h, d_sc, (n + 1) * 8))) return e;
+    counts->assign(h, h + n);
+    *total = h[n];
+    return 0;
+}
+
+// mlz_stream_search_batch_device behind its argument checks.  Returns the number of all triples or -MLZ_ERR_*; the streams' results go to out_count.
+int64_t stream_search_batch_locked(mlz_ctx* c, hipStream_t sm, uint32_t flags, const uint8_t* d_src, const mlz_block_desc* streams, size_t n, const uint8_t* patterns,
+                                   const uint32_t* pattern_len, size_t np, int64_t* out_count, const SearchBatchOut& out, uint64_t* stats) {
+    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0, fold = (flags & MLZ_SEARCH_IGNORE_CASE) != 0;
+    BatchWalk bw;
+    int r = stream_batch_walk(c, sm, d_src, streams, n, &bw);
+    if (r) return r;
+    begin_decode_call(c);
+    c->search_chunks = c->search_tables = 0;
+    std::vector<uint8_t> keep;
+    patterns = search_many_folded(flags, patterns, pattern_len, np, &keep);
+    mlz::SearchManyIndex index;
+    mlz::search_many_index(patterns, pattern_len, np, &index);
+    // a stream with a framing error keeps the walk's code, and nothing of it is searched
+    std::vector<uint8_t> alive(n);
+    std::vector<int64_t> verdict(n, 0), rc;
+    for (size_t i = 0; i < n; i++) { alive[i] = bw.parsed[i] >= 0; if (!alive[i]) verdict[i] = bw.parsed[i]; }
+    std::vector<uint64_t> counts(n, 0);
+    uint64_t total = 0, decoded = 0, bad = 0, passes = 0;
+    for (;;) {
+        size_t n_jobs = 0;
+        bool failed = false;
+        const int64_t e = stream_search_batch_pass(c, sm, ignore_crc, fold, d_src, bw, n, alive, index, patterns, np, out, &rc, &counts, &total, &n_jobs, &failed);
+        if (e < 0) return e;
+        decoded += n_jobs;
+        passes += n_jobs ? 1 : 0;
+        if (!failed) break;
+        if (passes > 1) { c->err = "stream_search_batch: a stream failed in the second pass only"; return -MLZ_ERR_HIP; }
+        for (size_t i = 0; i < n; i++) if (rc[i] < 0) { alive[i] = 0; verdict[i] = rc[i]; bad++; }
+        // the triples the void pass wrote: cleared (never anything at cap or beyond)
+        const uint64_t wrote = std::min<uint64_t>(total, out.cap);
+        if (wrote) {
+            HIPCHK(c, hipMemsetAsync(out.d_hit_pos, 0, wrote * 8, sm));
+            HIPCHK(c, hipMemsetAsync(out.d_hit_which, 0, wrote * 4, sm));
+        }
+    }
+    for (size_t i = 0; i < n; i++) out_count[i] = verdict[i] < 0 ? verdict[i] : int64_t(counts[i]);
+    c->search_chunks = decoded;
+    if (stats) { stats[0] = bw.chunks.size(); stats[1] = decoded; stats[2] = bad; stats[3] = passes; }
+    return int64_t(total);
+}
+
+}  // namespace
+
+extern "C" int64_t mlz_stream_search_batch_device(mlz_ctx* c, void* stream, uint32_t flags, const uint8_t* d_src, const mlz_block_desc* streams, int n_streams,
+                                                  const uint8_t* patterns, const uint32_t* pattern_len, size_t n_patterns, int64_t* out_count, uint64_t* d_stream_counts,
+                                                  uint64_t* d_pattern_counts, uint32_t* d_present, uint32_t* d_hit_stream, uint64_t* d_hit_pos, uint32_t* d_hit_which, size_t cap,
+                                                  uint64_t* stats) {
+    if (flags & ~uint32_t(MLZ_STREAM_IGNORE_CRC | MLZ_SEARCH_IGNORE_CASE | MLZ_SEARCH_NO_TABLES)) return -MLZ_ERR_ARG;
+    if (n_patterns == 0 || n_patterns > MLZ_SEARCH_MAX_PATTERNS || !patterns || !pattern_len || (cap && (!d_hit_stream || !d_hit_pos || !d_hit_which))) return -MLZ_ERR_ARG;
+    for (size_t i = 0; i < n_patterns; i++)
+        if (pattern_len[i] == 0 || pattern_len[i] > mlz::kSearchMaxPattern) return -MLZ_ERR_ARG;
+    const int a = batch_args(c, d_src, nullptr, false, streams, n_streams, out_count, &c);
+    if (a) {
+        if (a > 0 && stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+        return a < 0 ? a : 0;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (enter_device(c)) return -MLZ_ERR_HIP;
+    for (const void* p : {static_cast<const void*>(d_stream_counts), static_cast<const void*>(d_pattern_counts), static_cast<const void*>(d_present)})
+        if (p && !on_device(c, p)) return -MLZ_ERR_ARG;
+    if (cap && (!on_device(c, d_hit_stream) || !on_device(c, d_hit_pos) || !on_device(c, d_hit_which))) return -MLZ_ERR_ARG;
+    hipStream_t sm = static_cast<hipStream_t>(stream);
+    const SearchBatchOut out{d_stream_counts, d_pattern_counts, d_present, d_hit_stream, d_hit_pos, d_hit_which, uint64_t(cap)};
+    return settled(sm, stream_search_batch_locked(c, sm, flags, d_src, streams, size_t(n_streams), patterns, pattern_len, n_patterns, out_count, out, stats));
+}

@@ -13,6 +13,8 @@
 // writes (position, pattern) in ascending order.
 // The grep over the record index (mlz_stream_grep.hip.inc) runs the same walk in a third mode, once per group: every verified pair sets the bit
 // of its position's record in a bitmap, and nothing is counted or written.
+// The search over a batch of streams (mlz_stream_search_batch.hip.inc) runs the count and write modes over the tiles of all its streams and a
+// fourth mode once per group: every verified pair sets the bit of its pattern in the row of the tile's stream, the presence matrix.
 
 #include "mlz_stream_grep.h"
 
@@ -43,14 +45,17 @@ __host__ __device__ inline SearchManyLds search_many_lds(uint32_t n, uint32_t hb
     return l;
 }
 
-// The third mode's arguments: the handle's record index D[0, k) and the bitmap of its records, a bit each
-struct SearchManyMark { const uint64_t* D; uint64_t k; uint32_t* bits; };
-enum { kSearchManyCount = 0, kSearchManyWrite = 1, kSearchManyMarkRecords = 2 };
+// The marking modes' arguments.  Records: the handle's record index D[0, k) and the bitmap of its records, a bit each.  Streams (the search
+// over a batch of streams, mlz_stream_search_batch.hip.inc): every tile's stream and the presence matrix `bits`, a row of `words` words per stream
+struct SearchManyMark { const uint64_t* D; uint64_t k; uint32_t* bits; const uint32_t* tile_stream; uint32_t words; };
+enum { kSearchManyCount = 0, kSearchManyWrite = 1, kSearchManyMarkRecords = 2, kSearchManyMarkStreams = 3 };
 
 // One workgroup per tile.  kSearchManyCount: counts[tile] = the tile's pairs, pat_counts[p] += pattern p's.  kSearchManyWrite: the pairs of a tile
 // whose first pair lies below cap go to out_pos / out_which from prefix[tile] on, as far as they lie below cap.  kSearchManyMarkRecords: bit
 // number(position) of mk.bits is set for every pair (mlz_stream_grep.h, mark); the tile's two record numbers lie in the scan words of the LDS
 // layout, which this mode does not use otherwise, and every lane reads the same two words (a broadcast).
+// kSearchManyMarkStreams: bit p of row mk.tile_stream[tile] of mk.bits is set for every pair of pattern p; the tile's stream is one uniform
+// load for the workgroup, and nothing is counted or written.
 // kFold (MLZ_SEARCH_IGNORE_CASE): the index and the blob are those of the folded patterns, and the tile's bytes are folded a word at a time
 // (search_fold4) on their way from the scratch into LDS, so the key and the verify loop compare folded bytes at no cost per position.
 template <int kMode, bool kFold>
@@ -121,6 +126,14 @@ __global__ __launch_bounds__(kSearchManyThreads) void search_many_kernel(const u
             uint32_t* word = mk.bits + (r >> 5);
             const uint32_t bit = 1u << (uint32_t(r) & 31);
             // the test in front of the atomic: a record with thousands of occurrences costs a few atomics, not thousands; a stale word only costs another
+            if (!(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit)) atomicOr(word, bit);
+        });
+    } else if (kMode == kSearchManyMarkStreams) {
+        uint32_t* row = mk.bits + size_t(mk.tile_stream[tile]) * mk.words;   // (the same address in every lane: read once)
+        walk([&](uint32_t, uint32_t p) {
+            uint32_t* word = row + (p >> 5);
+            const uint32_t bit = 1u << (p & 31);
+            // as for the records: a stream with thousands of occurrences of one key costs a few atomics
             if (!(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit)) atomicOr(word, bit);
         });
     } else if (kMode == kSearchManyCount) {
@@ -218,7 +231,7 @@ int64_t dev_reader_search_many_locked(mlz_dev_reader* rd, hipStream_t sm, uint32
     if (n_take == 0) return nothing();
 
     SearchDecode sd;
-    search_decode_plan(rd, take, n_take, index.lmin, index.lmax, mlz::kSearchManyTile, &sd);
+    search_decode_plan(rd->chunks, take, n_take, index.lmin, index.lmax, mlz::kSearchManyTile, &sd);
     const size_t nt = sd.lay.tiles.size();
     if (nt > 0x7fffffffu) return -MLZ_ERR_ARG;
     Carve cv, pin;   // workspace: per-pattern counts | total | the index | tile counts | prefix | the decode's; pinned: the index | the decode's
@@ -228,7 +241,7 @@ int64_t dev_reader_search_many_locked(mlz_dev_reader* rd, hipStream_t sm, uint32
     up.take(index, n, &cv, &pin);
     const auto r_counts = cv.take<uint32_t>(nt, 4);
     const auto r_prefix = cv.take<uint64_t>(nt);
-    int e = search_decode_ready(rd, &sd, &cv, &pin);
+    int e = search_decode_ready(rd->ctx, rd->chunks, &sd, &cv, &pin);
     if (e) return e;
     void* ws = c->d_rplan.p;
     unsigned long long* d_pc = r_pc.at(ws);
@@ -239,7 +252,7 @@ int64_t dev_reader_search_many_locked(mlz_dev_reader* rd, hipStream_t sm, uint32
     HIPCHK(c, hipMemsetAsync(d_pc, 0, n * sizeof(unsigned long long), sm));
     HIPCHK(c, hipMemsetAsync(d_total, 0, 16, sm));
     if ((e = up.send(c, sm, index, patterns, n))) return e;
-    const int64_t r = search_decode_run(rd, sm, ignore_crc, &sd, [&](size_t, size_t t0, size_t t1) {
+    const int64_t r = search_decode_run(rd->ctx, rd->d_src, rd->chunks, sm, ignore_crc, &sd, [&](size_t, size_t t0, size_t t1) {
         const uint8_t* scratch = c->d_range.as<uint8_t>();
         hipLaunchKernelGGL(search_many_kernel_of<mlz::kSearchManyCount>(fold), dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), up.lds_bytes, sm, scratch, d_tiles, uint32_t(t0), up.ix, d_tc, d_pc,
                            static_cast<const uint64_t*>(nullptr), uint64_t(0), static_cast<uint64_t*>(nullptr), static_cast<uint32_t*>(nullptr), mlz::SearchManyMark{});

@@ -355,9 +355,11 @@ struct ScratchDecode {
         if (!sp.places.empty()) HIPCHK(c, c->d_place.ensure(sp.places.size() * sizeof(PlaceDesc)));
         return 0;
     }
-    // Decodes the list; per group the stored chunks' copies are enqueued and after_group(g) is called with the group's bytes in place (sm still running)
+    // Decodes the list; per group the stored chunks' copies are enqueued and after_group(g) is called with the group's bytes in place (sm still running).
+    // per_job: stream_run_chunk_jobs' (a list that holds many streams' chunks: every job's own verdict)
     template <class AfterGroup>
-    int64_t run(mlz_ctx* c, hipStream_t sm, bool ignore_crc, const uint8_t* d_src, const std::vector<StreamChunk>& chunks, AfterGroup after_group) {
+    int64_t run(mlz_ctx* c, hipStream_t sm, bool ignore_crc, const uint8_t* d_src, const std::vector<StreamChunk>& chunks, AfterGroup after_group,
+                std::vector<int64_t>* per_job = nullptr) {
         uint8_t* scratch = c->d_range.as<uint8_t>();
         const size_t np = sp.places.size();
         for (size_t i = 0; i < jobs.size(); i++) {
@@ -372,7 +374,7 @@ struct ScratchDecode {
             const size_t q0 = g ? sp.place_end[g - 1] : 0, q1 = sp.place_end[g];
             if (q1 > q0) hipLaunchKernelGGL(stream_place_kernel, dim3(uint32_t(q1 - q0)), dim3(256), 0, sm, d_src, d_src, nullptr, scratch, c->d_place.as<PlaceDesc>() + q0);
             return after_group(g);
-        });
+        }, per_job);
     }
 };
 

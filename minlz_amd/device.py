@@ -149,6 +149,39 @@ class HipTensorCodec:
                 self._raise_stream("encode_streams", i, r)
         return out, [(d[2], r) for d, r in zip(descs, res)]
 
+    def search_streams(self, t, spans, patterns, max_results=0, present=True, ignore_crc=False, ignore_case=False, on_error="raise"):
+        """Which of many .mz streams that lie in one uint8 tensor on the device (stream i at t[off_i : off_i + len_i] for spans[i]) hold which
+        of `patterns` (1 .. 4096 bytes objects of 1 .. 256 bytes), and where, in one call (mlz_stream_search_batch_device) ->
+        (counts, present, hit_stream, hit_pos, hit_which, pattern_counts, total), tensors on t's device: every stream's occurrences (int64, n
+        values); present[i, p] = pattern p occurs in stream i (bool, n x patterns; None with present=False), exact whatever max_results is;
+        the smallest min(total, max_results) triples in (stream, position inside the stream's decoded bytes, pattern) order (int32, int64,
+        int32); every pattern's occurrences (int64); the number of all triples.
+        on_error "raise": the first failing stream's error, which names its index (.index), as decode_streams; "keep": that stream's
+        negative code in counts, its row of present False, and the other streams' results as without it."""
+        if on_error not in ("raise", "keep"):
+            raise ValueError("search_streams: on_error is \"raise\" or \"keep\"")
+        t = _u8(t, "search_streams")
+        dev = t.device
+        spans, pats = _spans(t, spans, "search_streams"), list(patterns)
+        n, words = len(spans), (len(pats) + 31) // 32
+        pos, d_pos = _room(max_results, torch.int64, dev)
+        hs, d_hs = _room(max_results, torch.int32, dev)
+        which, d_which = _room(max_results, torch.int32, dev)
+        pc, _ = _room(len(pats), torch.int64, dev, torch.zeros)
+        bits, d_bits = _room(n * words if present else 0, torch.int32, dev, torch.zeros)
+        total, res, _ = self.ctx.stream_search_batch_device(t.data_ptr(), spans, pats, None, pc.data_ptr(), d_bits, d_hs, d_pos, d_which, max_results, ignore_crc=ignore_crc,
+                                                            ignore_case=ignore_case, stream=_stream(dev))
+        for i, r in enumerate(res):
+            if r < 0 and on_error == "raise":
+                self._raise_stream("search_streams", i, r)
+        counts = torch.tensor(res, dtype=torch.int64).to(dev)
+        k = min(total, max_results)
+        p = None
+        if present:
+            shifts = torch.arange(32, dtype=torch.int32, device=dev)
+            p = ((bits[:n * words].view(n, words, 1) >> shifts) & 1).view(n, words * 32)[:, :len(pats)].bool()
+        return counts, p, hs[:k], pos[:k], which[:k], pc[:len(pats)], total
+
     def open_stream(self, t):
         """A .mz stream that lies on the device (uint8 tensor) opened for range reads -> DeviceStream (ReadAt, read_ranges).  The chunk walk
         runs once, here; a framing error raises."""
