@@ -636,7 +636,8 @@ int64_t mlz_dev_reader_attach_sidecar(mlz_dev_reader* reader, void* stream, uint
                                 * batches of few large blocks.  The decoder measures the distance itself: any stream that keeps it decodes this way. */
 #define MLZ_OPT_FUSED_SERIALIZER 21 /* encode: 1 (default) = the match kernel's waves turn their own token records into token bytes (tile bytes and ring in LDS, records and
                                 * far-source lines still in the L2); 0 = the separate serializer kernel of rounds 2-5 on the same records (byte-identical; cross-checks) */
-#define MLZ_OPT_LEVEL0_KERNEL 23 /* decode: 1 (default) = a batch's level-0 tiles, when no more than the device has CUs, are decoded by dec_level0_kernel before the exec pass; 0 = by the exec pass (cross-checks) */
+#define MLZ_OPT_LEVEL0_KERNEL 23 /* decode: 1 (default) = a batch's level-0 candidates (tile 16 j of every block), when no more than the device has CUs, are decoded by dec_level0_kernel before the exec pass,
+                                * with the blocks' verdicts and the tile schedule made in the same launch; 0 = verdicts and schedule by kernels of their own, every tile by the exec pass (cross-checks) */
 #define MLZ_OPT_FOLD_LAYOUT 24  /* encode: 1 (default) = a group whose every block has tiles and room gets its layout (piece offsets, stored-or-not, header, length) from the gather kernel; 0 = always encode_layout_kernel (cross-checks) */
 #define MLZ_OPT_GEN_SPIN 9     /* patience of the general-block decode with a tile's ready flag, in polls (~0.3 us each; default 2^24); tests */
 #define MLZ_OPT_GEN_PACKED 13  /* tests: 1 = general blocks settle through the byte-packed pool (the fallback of tiles whose slots do not fit) */
@@ -650,6 +651,8 @@ int64_t mlz_dev_reader_attach_sidecar(mlz_dev_reader* reader, void* stream, uint
 #define MLZ_OPT_TIMER_MASK 12       /* which timers record events (bit i = mlz_timer_name(i); default all) */
 #define MLZ_OPT_FAR_SLICES_L2 18    /* debug, cross-checks: 1 = LevelBalanced's far tables by far_build_kernel (the slice kernel of round 4) even without tile levels */
 #define MLZ_OPT_GEN_SETTLE_CAP 20   /* tuning: role S workgroups of the general-block pass at most (default: a quarter of the device) */
+/* 25 (debug, tests; it has no name here or in the Python module): level-0 candidates dec_level0_kernel is launched for at most (default 0: the device's CU count);
+ * a group with more takes the path of option 23 = 0 */
 /* (15 and 16 are retired: they selected a removed index pass and a debug stop; the numbers are not reused) */
 int mlz_set_option(mlz_ctx* ctx, int opt, int64_t value);
 /* Milliseconds spent in each kernel family, measured with HIP events on the caller's stream.
@@ -677,7 +680,8 @@ const char* mlz_timer_name(int idx);
  *            (12 bytes per chunk, as in every stream decode) and the one-time upload of a handle's chunk table.
  * which = 10 / 11: the context's last mlz_dev_reader_search, mlz_dev_reader_search_many or search phase of mlz_dev_reader_search_records or mlz_dev_reader_grep_records: 10 = chunks it decoded or copied, 11 = chunks with a usable search table (0 when the call
  *            used none: MLZ_SEARCH_NO_TABLES, no info chunk, a pattern shorter than M).
- * which = 12: streams that the context's last mlz_stream_*_batch_device call sent through the region walk because they hold more than 4096 chunk headers. */
+ * which = 12: streams that the context's last mlz_stream_*_batch_device call sent through the region walk because they hold more than 4096 chunk headers.
+ * which = 13 (debug, tests; no name in the Python module): internal groups of the last decode call whose level-0 candidates, verdicts and schedule went in one launch (MLZ_OPT_LEVEL0_KERNEL); 0 = every group took the separate kernels. */
 int64_t mlz_get_counter(mlz_ctx* ctx, int which);
 
 #ifdef __cplusplus

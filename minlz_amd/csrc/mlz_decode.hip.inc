@@ -551,10 +551,11 @@ __global__ __launch_bounds__(kChainThreads) void dec_chain_kernel(const BlockInf
 // segment; runs of segments of one block inside a wavefront are combined first, so a block gets an atomic per 64 segments.  Whoever sets
 // the last of the three pattern bits flags the block as general: it fits no level pattern.  (Round 5 tried this at the head of the
 // one-workgroup schedule kernel, a launch less: 18.5 us against 4.9 + 9.1 — the fences between the atomics and the schedule's reads cost
-// more than the launch.)
-__global__ __launch_bounds__(256) void dec_viol_kernel(const uint32_t* __restrict__ seg_block, const uint8_t* __restrict__ seg_viol, DecBlock* __restrict__ dec,
-                                                        uint32_t* __restrict__ n_general /* null: general blocks stay on the tile path */, uint32_t segs) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+// more than the launch.  Since the level-0 hand-over both run in ONE workgroup of dec_level0_kernel's launch, beside the level-0 candidates: a barrier
+// between the two parts is enough there.  The kernels of their own serve the groups that do not take that launch.)
+// (a device function: dec_viol_kernel runs it a thread per segment, the verdict workgroup of dec_level0_kernel in steps of its 1024 threads)
+__device__ __forceinline__ void dec_viol_gather(const uint32_t* __restrict__ seg_block, const uint8_t* __restrict__ seg_viol, DecBlock* __restrict__ dec,
+                                                uint32_t* __restrict__ n_general /* null: general blocks stay on the tile path */, uint32_t segs, uint32_t i /* my segment; whole wavefronts call */) {
     const int lane = threadIdx.x & 63;
     uint32_t v = 0, bi = 0xffffffffu;
     if (i < segs) {
@@ -579,19 +580,23 @@ __global__ __launch_bounds__(256) void dec_viol_kernel(const uint32_t* __restric
         }
     }
 }
+__global__ __launch_bounds__(256) void dec_viol_kernel(const uint32_t* __restrict__ seg_block, const uint8_t* __restrict__ seg_viol, DecBlock* __restrict__ dec,
+                                                        uint32_t* __restrict__ n_general, uint32_t segs) {
+    dec_viol_gather(seg_block, seg_viol, dec, n_general, segs, blockIdx.x * 256 + threadIdx.x);
+}
 
 // ---------------- D3d: schedule ----------------
 // order[ticket] = global tile index.  Tiles of "general" blocks come first in position order
 // (a tile may wait on any earlier tile of its block); then the tiles of level-conformant blocks,
 // level 0 first: a tile only ever waits on tiles with a smaller ticket, so the exec pass cannot
 // deadlock however few wavefronts are resident.  One 1024-thread workgroup, two passes.
-__global__ __launch_bounds__(1024) void dec_schedule_kernel(const BlockInfo* __restrict__ blocks, const uint32_t* __restrict__ tile_block,
-                                                           DecBlock* __restrict__ dec, uint32_t* __restrict__ order, uint32_t total_tiles,
-                                                           uint32_t n_blocks, uint32_t* __restrict__ gen_list /* null: no general pass */,
-                                                           uint32_t* __restrict__ gen_ctl /* GenCtl: [0] blocks on the list, [2] their largest tile count */,
-                                                           uint32_t n_settle /* role S workgroups of dec_general_kernel */,
-                                                           uint32_t* __restrict__ call_acc /* per API call, over its internal groups: [0] general blocks, [1] largest team */,
-                                                           uint32_t acc_reset /* first group of the call */) {
+__device__ __forceinline__ void dec_schedule_body(const BlockInfo* __restrict__ blocks, const uint32_t* __restrict__ tile_block,
+                                                     DecBlock* __restrict__ dec, uint32_t* __restrict__ order, uint32_t total_tiles,
+                                                     uint32_t n_blocks, uint32_t* __restrict__ gen_list /* null: no general pass */,
+                                                     uint32_t* __restrict__ gen_ctl /* GenCtl: [0] blocks on the list, [2] their largest tile count */,
+                                                     uint32_t n_settle /* role S workgroups of dec_general_kernel */,
+                                                     uint32_t* __restrict__ call_acc /* per API call, over its internal groups: [0] general blocks, [1] largest team */,
+                                                     uint32_t acc_reset /* first group of the call */) {
     // buckets: 0 = general blocks that stay on the tile path (position order matters: a tile there may wait for any earlier tile
     // of its block), 1 .. kLevels = levels of conformant blocks, kLevels + 1 = general blocks decoded by dec_general_kernel
     // (the exec pass returns at once for their tiles: last, any order)
@@ -621,8 +626,6 @@ __global__ __launch_bounds__(1024) void dec_schedule_kernel(const BlockInfo* __r
     if (tid == 0) {
         uint32_t run = 0;
         for (uint32_t b = 0; b < kBuckets; b++) { base[b] = run; run += cnt[b]; }
-        // the level-0 tiles of conformant blocks (bucket 1) and where they start in the order: dec_level0_kernel / the exec pass (GenCtl::n_level0, l0_first)
-        gen_ctl[6] = cnt[1]; gen_ctl[7] = cnt[0];
     }
     __syncthreads();
     // pass 2: placement.  Inside a level (and in the last bucket) the order is free — tiles of one level never wait for each
@@ -685,6 +688,11 @@ __global__ __launch_bounds__(1024) void dec_schedule_kernel(const BlockInfo* __r
             }
         }
     } else if (tid == 0 && call_acc && acc_reset) { call_acc[0] = 0; call_acc[1] = 0; }
+}
+__global__ __launch_bounds__(1024) void dec_schedule_kernel(const BlockInfo* __restrict__ blocks, const uint32_t* __restrict__ tile_block, DecBlock* __restrict__ dec,
+                                                           uint32_t* __restrict__ order, uint32_t total_tiles, uint32_t n_blocks, uint32_t* __restrict__ gen_list,
+                                                           uint32_t* __restrict__ gen_ctl, uint32_t n_settle, uint32_t* __restrict__ call_acc, uint32_t acc_reset) {
+    dec_schedule_body(blocks, tile_block, dec, order, total_tiles, n_blocks, gen_list, gen_ctl, n_settle, call_acc, acc_reset);
 }
 
 // ---------------- D4: exec ----------------

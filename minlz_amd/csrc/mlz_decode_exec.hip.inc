@@ -92,7 +92,7 @@ __global__ __launch_bounds__(kExecThreads, MLZ_EXEC_MINWAVES) void dec_exec2_ker
                                                                  const uint32_t* __restrict__ round_rep, const uint32_t* __restrict__ order,
                                                                  uint32_t* __restrict__ tile_done, uint32_t* __restrict__ ticket, uint32_t total_tiles,
                                                                  unsigned long long* __restrict__ prof,
-                                                                 const uint32_t* __restrict__ gen_ctl /* GenCtl */, uint32_t l0_grid /* workgroups dec_level0_kernel ran with; 0 = not launched */) {
+                                                                 uint32_t l0_ran /* dec_level0_kernel ran before this pass: some tiles' done flags may be up already */) {
     extern __shared__ __attribute__((aligned(16))) uint8_t tilebuf[];
     volatile uint32_t* sh = reinterpret_cast<volatile uint32_t*>(tilebuf + kTile);  // [0] ticket, [2] failure site, [3] turn: first chunk not yet complete
     // ([2] and [3] are polled together with one 8-byte read)
@@ -117,6 +117,11 @@ __global__ __launch_bounds__(kExecThreads, MLZ_EXEC_MINWAVES) void dec_exec2_ker
         trace[0] = __builtin_amdgcn_s_memrealtime() | (hw << 44) | (xcc << 40);
     }
     gt = rdfirst(order[gt]);  // ticket -> tile (D3d)
+    // A tile that dec_level0_kernel has decoded and published (a level-0 candidate it could finish): nothing left to do.  One load by one lane; the flag was
+    // raised before this launch began and only this workgroup would raise it now, so the waves agree.
+    // (Requested here, beside the descriptor loads, and looked at behind them.)
+    uint32_t l0_flag = 0;
+    if (l0_ran && lane == 0) l0_flag = __hip_atomic_load(&tile_done[gt], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint32_t bi = tile_block[gt];
     const BlockInfo b = blocks[bi];
     const DecBlock db = dec[bi];
@@ -126,13 +131,8 @@ __global__ __launch_bounds__(kExecThreads, MLZ_EXEC_MINWAVES) void dec_exec2_ker
     uint32_t bad = 0;  // 0 ok, else failure site (reported as corrupt)
     bool plain_stores = false;  // the tile was (partly) written with ordinary stores: publish needs the L2 write-back
     uint8_t* dst = dst_base + b.dst_off;
+    if (rdfirst(l0_flag) != 0) return;
     if (db.general & 2) return;  // decoded as a whole by dec_general_kernel; nobody waits for its tiles
-    // level-0 tiles of conformant blocks: decoded and published by dec_level0_kernel when they are no more than its workgroups (the same test on the
-    // same word, GenCtl::n_level0, there)
-    if (l0_grid && !db.general && db.status == 0 && !db.literals && tstart < db.dlen && tile_level_p(k, block_pattern(db)) == 0) {
-        const uint32_t n0 = gen_ctl[6];
-        if (n0 != 0 && n0 <= l0_grid) return;
-    }
     if (db.status == 0 && db.literals) {
         // Stored block: a straight copy.  No tile of such a block is ever the source of a copy, so
         // nothing is published (the release fence of 32 768 tiles was 80 % of the time of config 4).

@@ -47,11 +47,9 @@ struct GenCtl {
     uint32_t failed;      // somebody gave up waiting (debug)
     uint32_t done_wgs;    // workgroups of dec_general_kernel that have left (the last one writes the batch's results)
     uint32_t team;        // D3d: tiles of a block that role S settles side by side (1, 2 or 4: team_of, the smallest of the batch's general blocks)
-    uint32_t n_level0;    // D3d: level-0 tiles of the batch's level-conformant blocks (dec_level0_kernel decodes them when they are few: see there)
-    uint32_t l0_first;    // ... and where they start in the schedule (order[l0_first .. l0_first + n_level0))
-    uint32_t l0_ticket;   // dec_level0_kernel: next ticket
 };
 
+constexpr uint32_t kL0Done = 2;   // what dec_level0_kernel leaves in a finished tile's done flag: "done" to the exec pass (non-zero), "not explained" to role S (bit 0)
 struct ExtEnt { uint32_t src, where; };   // source position in the block's output; pool offset | (length - 1) << 16
 struct GenTile { uint32_t n_ext, lit_top; };   // role E -> role S, per tile: entries (bit 31: byte-packed pool, exact stores), literal bytes at the pool's bottom
 
@@ -111,9 +109,10 @@ __device__ __forceinline__ uint32_t opaque(uint32_t x) { asm volatile("" : "+v"(
 // every wait is bounded.  (Mid-round 4 the roles were two kernels on two streams for a while — blamed for a register-allocation
 // fault that turned out to be a sign extension in `uni` —: the event hand-over between the streams cost every decode call, with or
 // without general blocks, ~40 us.)
-// L0 = true (dec_level0_kernel, round 6): role E only, over the batch's LEVEL-0 tiles of level-conformant blocks (tickets into the schedule), and instead of
+// L0 = true (dec_level0_kernel, round 6): role E only, on ONE tile (tile l0_t of block l0_bi: a level-0 candidate, see the kernel), and instead of
 // leaving map and pool for role S the tile is finished here — a level-0 tile reads nothing but itself, so every byte's terminal is a literal of the tile:
-// gather through the map, flush, raise the exec pass's done flag.
+// gather through the map, flush, raise the exec pass's done flag.  A tile that turns out to read an earlier one, or to hold a bad token, is left alone —
+// found while the tile is parsed, before its first store —: no byte, no flag, no status; the exec pass or the general pass decodes it as if nobody had tried.
 template <bool L0>
 __device__ __forceinline__ void dec_general_body(const uint8_t* __restrict__ src_base, uint8_t* __restrict__ dst_base,
                                                                   const BlockInfo* __restrict__ blocks, DecBlock* __restrict__ dec,
@@ -123,8 +122,7 @@ __device__ __forceinline__ void dec_general_body(const uint8_t* __restrict__ src
                                                                   ExtEnt* __restrict__ ext_all, GenTile* __restrict__ tile_info,
                                                                   uint32_t* __restrict__ tile_ready, GenCtl* __restrict__ ctl, uint32_t nE, uint32_t nS,
                                                                   uint32_t spin_limit, uint32_t force_packed,
-                                                                  const uint32_t* __restrict__ order = nullptr, const uint32_t* __restrict__ tile_block = nullptr,
-                                                                  uint32_t* __restrict__ tile_done = nullptr) {
+                                                                  uint32_t l0_bi = 0, uint32_t l0_t = 0, uint32_t* __restrict__ tile_done = nullptr) {
     const uint32_t ngen = L0 ? 0u : __hip_atomic_load(&ctl->n_general, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     extern __shared__ __attribute__((aligned(16))) uint8_t gl[];
     // shared words: [0] ticket / flag verdict, [1] entries, [2] failure, [3] literal bytes.  (Not `volatile`: the address-space inference skips
@@ -139,7 +137,8 @@ __device__ __forceinline__ void dec_general_body(const uint8_t* __restrict__ src
     };
 
     // (a settling workgroup that has no unit to settle — fewer blocks x team than settling workgroups — explains instead: tickets are drawn, not dealt)
-    const uint32_t team0 = uni(__hip_atomic_load(&ctl->team, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    // (L0 reads no word of ctl: the verdict workgroup of its launch is writing them)
+    const uint32_t team0 = L0 ? 1u : uni(__hip_atomic_load(&ctl->team, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     if (L0 || blockIdx.x < nE || blockIdx.x - nE >= ngen * (team0 ? team0 : 1u)) {
         // =========================== role E ===========================
         // Every output byte of the tile -> the offset of its TERMINAL in the tile's pool: a literal byte (laid down here, from the
@@ -149,35 +148,24 @@ __device__ __forceinline__ void dec_general_body(const uint8_t* __restrict__ src
         uint8_t* pool = gl + 2 * kTile;
         uint32_t* toktab = reinterpret_cast<uint32_t*>(gl + 3 * kTile);   // the token table of mlz_toktab.h (role E leaves the fourth 32 KiB alone)
         for (uint32_t i = tid; i < 256; i += kGenThreads) toktab[i] = g_toktab.e[i];
-        const uint32_t maxT = __hip_atomic_load(&ctl->max_tiles, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t maxT = L0 ? 1u : __hip_atomic_load(&ctl->max_tiles, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // tickets: groups of nS blocks (a group = the blocks the S workgroups settle side by side), position-major inside a group
         const uint32_t teamE = team0;
         const uint32_t nSb = nS / (teamE ? teamE : 1u);       // blocks role S settles side by side (a team of workgroups per block)
         const uint32_t per_group = L0 ? 1u : maxT * nSb;
-        const uint32_t l0_first = L0 ? uni(__hip_atomic_load(&ctl->l0_first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : 0u;
-        const uint32_t total_tickets = L0 ? uni(__hip_atomic_load(&ctl->n_level0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : per_group * ((ngen + nSb - 1) / nSb);
-        for (;;) {
+        const uint32_t total_tickets = L0 ? 1u : per_group * ((ngen + nSb - 1) / nSb);
+        for (uint32_t turn = 0;; turn++) {
             MLZ_GP(7);
-            __syncthreads();
-            if (tid == 0) {
-                const uint32_t tk0 = atomicAdd(L0 ? &ctl->l0_ticket : &ctl->e_ticket, 1u);
-                shw[0] = tk0;
-                if (L0 && tk0 < total_tickets) {  // the block's status, read ONCE for the workgroup (another tile may fail it meanwhile: every wave must take the same branch)
-                    DecBlock* db0 = &dec[tile_block[order[l0_first + tk0]]];
-                    // (skipped, i.e. left to the exec pass, exactly where its early return does not apply: failed blocks, stored blocks — a straight copy there)
-                    shw[5] = uint32_t(__hip_atomic_load(reinterpret_cast<int*>(&db0->status), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) | uint32_t(db0->literals ? 1u : 0u) | (db0->ntok == 0 ? 1u : 0u);
-                }
-            }
-            __syncthreads();
-            const uint32_t tk = shw[0];
-            if (tk >= total_tickets) break;
             uint32_t t, bi;
-            if (L0) {   // the tk-th level-0 tile of the schedule
-                const uint32_t g = uni(order[l0_first + tk]);
-                bi = uni(tile_block[g]);
-                t = g - uni(blocks[bi].first_tile);
-                if (uni(shw[5]) != 0) continue;   // (a failed or stored block: the exec pass handles its tiles, as it always did)
+            if (L0) {   // the one tile it was called for
+                if (turn) break;
+                t = l0_t; bi = l0_bi;
             } else {
+                __syncthreads();
+                if (tid == 0) shw[0] = atomicAdd(&ctl->e_ticket, 1u);
+                __syncthreads();
+                const uint32_t tk = shw[0];
+                if (tk >= total_tickets) break;
                 const uint32_t rem = tk % per_group;
                 const uint32_t slot = (tk / per_group) * nSb + rem % nSb;
                 t = rem / nSb;
@@ -202,7 +190,7 @@ __device__ __forceinline__ void dec_general_body(const uint8_t* __restrict__ src
             const uint32_t j_first = rank0 >> 6, j_last = r_last >> 6;
             gp_tiles++;
             ExtEnt* ext = L0 ? nullptr : ext_all + uni(ext_index(first_seg, first_tile, bi, t, rank0));
-            if (MLZ_GEN_DEBUG && tid == 0) printf("E wg %u tk %u bi %u t %u gt %u dlen %u clen %u ntok %u rank0 %u r_last %u first_seg %u first_tile %u ext %p src %p tpos %p\n", blockIdx.x, tk, bi, t, gt, dlen, clen, ntok, rank0, r_last, first_seg, first_tile, (void*)ext, (const void*)src, (const void*)tpos);
+            if (MLZ_GEN_DEBUG && tid == 0) printf("E wg %u turn %u bi %u t %u gt %u dlen %u clen %u ntok %u rank0 %u r_last %u first_seg %u first_tile %u ext %p src %p tpos %p\n", blockIdx.x, turn, bi, t, gt, dlen, clen, ntok, rank0, r_last, first_seg, first_tile, (void*)ext, (const void*)src, (const void*)tpos);
             bool tile_failed = false;
             uint32_t packed = (MLZ_GEN_FORCE_PACKED || force_packed) ? 1u : 0u;   // 0: 8-byte slots from the pool's top; 1: byte-packed behind the literals (always fits)
             for (;;) {
@@ -262,7 +250,7 @@ __device__ __forceinline__ void dec_general_body(const uint8_t* __restrict__ src
                             const bool lit_bad = lit != 0 && (uint64_t(lit_s) + lit > clen || uint64_t(dtok) + lit > dlen);
                             const uint64_t b_inv = ballot64(invalid);
                             if (b_inv || ballot64(lit_bad)) {
-                                if (lane == 0) { atomicExch(reinterpret_cast<int*>(&dec[bi].status), int(1 | ((b_inv ? 5 : 4) << 8))); shw[2] = 1; }
+                                if (lane == 0) { if (!L0) atomicExch(reinterpret_cast<int*>(&dec[bi].status), int(1 | ((b_inv ? 5 : 4) << 8))); shw[2] = 1; }   // (L0: the exec pass gives the verdict)
                                 failed = true;
                                 continue;
                             }
@@ -278,8 +266,8 @@ __device__ __forceinline__ void dec_general_body(const uint8_t* __restrict__ src
                             const uint32_t i0 = n_ext ? e1 : c0;                      // first byte that reads this tile
                             const uint32_t nl = has_lit ? l1 - l0 : 0;
                             const uint32_t cnt = L0 ? 0u : (n_ext + kExtMax - 1) / kExtMax;
-                            if (L0 && ballot64(n_ext != 0)) {   // a level-0 tile that reads another tile: the index pass's verdict says it cannot be (defensive)
-                                if (lane == 0) { atomicExch(reinterpret_cast<int*>(&dec[bi].status), int(1 | (11 << 8))); shw[2] = 1; }
+                            if (L0 && ballot64(n_ext != 0)) {   // the candidate reads an earlier tile (tile 16 of a block without levels): not a level-0 tile after all
+                                if (lane == 0) shw[2] = 1;
                                 failed = true;
                                 continue;
                             }
@@ -475,11 +463,13 @@ __device__ __forceinline__ void dec_general_body(const uint8_t* __restrict__ src
                     store8_wt(&tile_info[gt], uint64_t(shw[1] | (packed << 31)) | (uint64_t(lit_top) << 32));
                 }
                 }
-            } else if (!L0 && tid == 0) store8_wt(&tile_info[gt], 0ull);
+            } else if (L0) break;   // abandoned: nothing stored, no flag
+            else if (tid == 0) store8_wt(&tile_info[gt], 0ull);
             // publish: every store above is a write-through one and only has to have left the CU
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
-            if (tid == 0) __hip_atomic_store(L0 ? &tile_done[gt] : &tile_ready[gt], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (L0: the exec pass's done flag of the tile)
+            // (L0: the exec pass's done flag of the tile, and kL0Done, not 1: the tile may belong to a block that turns out general, whose tiles' flags role E raises for role S)
+            if (tid == 0) __hip_atomic_store(L0 ? &tile_done[gt] : &tile_ready[gt], L0 ? kL0Done : 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             MLZ_GP(4);
         }
         if (MLZ_GEN_PROF && blockIdx.x == 0 && tid == 0)
@@ -544,11 +534,11 @@ __device__ __forceinline__ void dec_general_body(const uint8_t* __restrict__ src
                 const uint32_t t = known + uint32_t(lane);
                 uint32_t ok = 1, spins = 0, ready = 0;
                 if (t < ntile) {
-                    ready = __hip_atomic_load(&tile_ready[first_tile + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    ready = __hip_atomic_load(&tile_ready[first_tile + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1u;   // (bit 0: role E's; kL0Done is not)
                     while (!ready && t < want) {
                         __builtin_amdgcn_s_sleep(4);
                         if (++spins >= spin_limit) { ok = 0; break; }
-                        ready = __hip_atomic_load(&tile_ready[first_tile + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        ready = __hip_atomic_load(&tile_ready[first_tile + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1u;
                     }
                 }
                 uint32_t verdict = ballot64(ok == 0) ? 0u : 1u;
@@ -839,26 +829,49 @@ __global__ __launch_bounds__(kGenThreads) void dec_general_kernel(const uint8_t*
     }
 }
 
-// dec_level0_kernel (round 6): the level-0 tiles of level-conformant blocks, when there are no more of them than CUs.  The exec pass runs a batch's
+// dec_level0_kernel (round 6): level-0 tiles decoded before the exec pass, when there are no more of them than CUs.  The exec pass runs a batch's
 // tiles level by level and a tile's latency is its ordered chain (~73 us whatever else the device does): with twelve 8 MiB blocks the first of its four
 // slot-waves holds 191 level-0 tiles and idles four fifths of the device.  A level-0 tile reads nothing but itself, which is the case role E of the
 // general pass reduces in parallel — every byte to its terminal by pointer jumping in LDS, ~30 us with 1024 threads —, so these tiles are decoded
-// that way BEFORE the exec pass, one per CU, and the exec pass starts at level 1 (its workgroups of level-0 tiles return at once; its level-1 tiles
-// find the done flags up).  More level-0 tiles than CUs (many small blocks): the tile chain's throughput is the better one, this kernel leaves at
-// once and the exec pass does them as before — both kernels read the same count, written by dec_schedule_kernel.
-__device__ __forceinline__ bool level0_by_e(const GenCtl* ctl, uint32_t n_wgs) {
-    const uint32_t n0 = __hip_atomic_load(&ctl->n_level0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return n0 != 0 && n0 <= n_wgs;
-}
+// that way BEFORE the exec pass, one per CU; an exec workgroup that finds its tile's done flag up returns at once.
+//
+// Which tiles: the CANDIDATES, tile 16 j of every block — level 0 under each of the three level patterns, so the kernel needs no verdict and no
+// schedule, only the token list: it depends on dec_index2_kernel alone.  The host lists them (L0Cands, a kernel argument: workgroup c takes entry c)
+// and launches when they are no more than the device has CUs — many small blocks: the tile chain's throughput is the better one, the exec pass does
+// every tile as in rounds 2-5.  A candidate of a failed, stored or empty block, or beyond the block's decoded length, is skipped; one that cannot be
+// finished (dec_general_body) is left to the later passes; the tiles 4, 8, 12 (mod 16) of the fast pattern are level 0 and no candidates: the exec pass's.
+//
+// The LAST workgroup is not a candidate's: it gives the blocks' verdicts (dec_viol_kernel's gather) and then makes the schedule and the general-block
+// list (dec_schedule_kernel), on a CU the candidates leave free — two launches less between the index pass and the exec pass, both inside the ~40 us the
+// candidates take.  Nothing it writes (DecBlock::viol / general, the order, GenCtl, the call's counters) is read by a candidate's workgroup.
+constexpr uint32_t kL0MaxCands = 256, kL0BlockBits = 28;
+struct L0Cands { uint32_t e[kL0MaxCands]; };   // block | (tile / 16) << kL0BlockBits
+struct L0Sched {   // what the verdict workgroup needs: the arguments of dec_viol_kernel and dec_schedule_kernel
+    const uint32_t *seg_block, *tile_block; const uint8_t* seg_viol;
+    uint32_t *n_general, *order, *gen_list, *gen_ctl, *call_acc;
+    uint32_t segs, tiles, n_blocks, n_settle, acc_reset;
+};
 __global__ __launch_bounds__(kGenThreads) void dec_level0_kernel(const uint8_t* __restrict__ src_base, uint8_t* __restrict__ dst_base,
                                                                  const BlockInfo* __restrict__ blocks, DecBlock* __restrict__ dec,
                                                                  const uint32_t* __restrict__ tok_pos, const uint32_t* __restrict__ round_d,
                                                                  const uint32_t* __restrict__ round_rep, const TileStart* __restrict__ tile_start,
-                                                                 const uint32_t* __restrict__ order, const uint32_t* __restrict__ tile_block,
-                                                                 uint32_t* __restrict__ tile_done, GenCtl* __restrict__ ctl) {
-    if (!level0_by_e(ctl, gridDim.x)) return;
-    dec_general_body<true>(src_base, dst_base, blocks, dec, tok_pos, round_d, round_rep, tile_start, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ctl,
-                           gridDim.x, 0u, 1u, 0u, order, tile_block, tile_done);
+                                                                 uint32_t* __restrict__ tile_done, const L0Cands cands, const L0Sched sc) {
+    if (blockIdx.x == gridDim.x - 1) {
+        for (uint32_t i0 = 0; i0 < sc.segs; i0 += kGenThreads) dec_viol_gather(sc.seg_block, sc.seg_viol, dec, sc.n_general, sc.segs, i0 + threadIdx.x);
+        // the verdicts are complete (every atomic has returned) before the schedule reads them: one workgroup, so a barrier orders the two parts;
+        // the schedule's loads must not be served from what this CU cached before (nothing, unless a candidate of an earlier launch left it)
+        __syncthreads();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        dec_schedule_body(blocks, sc.tile_block, dec, sc.order, sc.tiles, sc.n_blocks, sc.gen_list, sc.gen_ctl, sc.n_settle, sc.call_acc, sc.acc_reset);
+        return;
+    }
+    const uint32_t e = cands.e[blockIdx.x];
+    const uint32_t bi = e & ((1u << kL0BlockBits) - 1), t = (e >> kL0BlockBits) << 4;
+    // (DecBlock word by word: viol and general are being written)
+    const uint32_t skip = uni(uint32_t(dec[bi].status) | dec[bi].literals | (dec[bi].ntok == 0 ? 1u : 0u) | ((t << kTileLog) >= dec[bi].dlen ? 1u : 0u));
+    if (skip) return;
+    dec_general_body<true>(src_base, dst_base, blocks, dec, tok_pos, round_d, round_rep, tile_start, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           1u, 0u, 1u, 0u, bi, t, tile_done);
 }
 
 }  // namespace mlz

@@ -107,7 +107,7 @@ struct mlz_ctx {
     std::vector<SingleReq*> q_pending;
     bool q_leader = false;
     uint64_t q_batches = 0, q_requests = 0;  // mlz_get_counter
-    uint64_t acc_call = 0;                   // the decode call (dec_call) whose first schedule kernel has reset d_gen_acc
+    uint64_t acc_call = 0;                   // the decode call (dec_call) whose first group has reset d_gen_acc
     uint64_t dec_call = 0;                   // call_seq at the start of the last decode API call: its host groups, stream groups and internal groups share it
     std::string err;
     std::string dev_name;
@@ -154,7 +154,8 @@ struct mlz_ctx {
     uint64_t range_plan_host = 0;   // plan bytes that crossed between host and device in the last mlz_dev_reader_read_device (mlz_get_counter 9)
     uint64_t search_chunks = 0, search_tables = 0;  // the last mlz_dev_reader_search: chunks decoded or copied, chunks with a usable table (mlz_get_counter 10 / 11)
     uint64_t range_chunks = 0, range_scratch = 0;   // the last range read: chunks decoded or copied, decoded bytes that went through d_range (mlz_get_counter 7 / 8)
-    DevBuf d_gen_acc;      // two words summed over a call's internal groups by dec_schedule_kernel: general blocks, largest team (mlz_get_counter 2 / 6)
+    DevBuf d_gen_acc;      // two words summed over a call's internal groups by the schedule code: general blocks, largest team (mlz_get_counter 2 / 6)
+    uint64_t l0_launches = 0;   // internal groups of the last decode call whose level-0 candidates, verdicts and schedule went in dec_level0_kernel's launch (mlz_get_counter 13)
     int general_algo = 0;  // 0 = pointer-jumping pass for general blocks, 1 = tile chain in the exec pass
     size_t host_group_enc = kHostGroupEncodeDefault, host_group_dec = kHostGroupDecodeDefault;  // host-pointer batches: bytes per overlapped group
     int gen_grid = 0;      // workgroups of dec_general_kernel the device holds at once
@@ -167,7 +168,8 @@ struct mlz_ctx {
     uint64_t gen_fallbacks = 0;  // decode calls whose general blocks took the tile chain because the general pass's buffers could not be allocated (mlz_get_counter 5)
     int gen_force_packed = 0;  // tests: every tile of a general block takes the byte-packed pool (the fallback path)
     int fold_layout = 1;       // option 24: the encode layout rides in the gather kernel when every block of the group has tiles and room (0: always encode_layout_kernel)
-    int level0_by_e = 1;       // option 23: few level-0 tiles are decoded by dec_level0_kernel before the exec pass (0: by the exec pass, rounds 2-5)
+    int level0_by_e = 1;       // option 23: few level-0 candidates (tile 16 j of a block) are decoded by dec_level0_kernel before the exec pass, verdicts and schedule beside them (0: dec_viol_kernel, dec_schedule_kernel, every tile by the exec pass: rounds 2-5)
+    int l0_grid_cap = 0;       // debug option 25: candidates dec_level0_kernel is launched for at most (0 = as many as the device has CUs)
     int fuse_ser = 1;          // option 21: the match kernel serializes its pieces itself (0: serialize_pieces_kernel, rounds 2-5; cross-checks)
     // host-pointer staging
     DevBuf d_in, d_out, d_len, d_crc, d_crc_tabs, d_crc_tiles;
@@ -179,7 +181,7 @@ struct mlz_ctx {
     // options
     int decode_algo = 0;
     int encode_far = 1;
-    bool enc_attrs = false, far_attr = false, farbin_attr = false, stab_attr = false, dec_attrs = false, gen_attr = false, l0_attr = false;  // per device: dynamic-LDS limits raised (raise_lds_once)
+    bool enc_attrs = false, far_attr = false, farbin_attr = false, stab_attr = false, dec_attrs = false, gen_attr = false, l0_attr = false, l0_attr_failed = false;  // per device: dynamic-LDS limits raised (raise_lds_once)
     uint32_t timer_mask = 0xffffffffu;  // timers that record events (an event pair costs ~10 us of idle device per kernel boundary)
     int timing = 0;  // 0 off, 1 = the last call's kernel times, 2 = running mean over the calls since it was enabled (no sync per call)
     int debug_status = 0;
@@ -578,6 +580,30 @@ int decode_parallel(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, uint8_t* d
     const uint32_t* tile_block = c->d_tile_block_cur().as<uint32_t>();
     const uint32_t* seg_block = c->d_seg_block_cur().as<uint32_t>();
     if ((r = raise_lds_once(c, c->dec_attrs, Kernels{{dec_exit_kernel, kExitLds}, {dec_index1_kernel, kIdxLds}, {dec_exec2_kernel, kExecLds}}))) return r;
+    // The hand-over from the index pass to the exec pass.  Few level-0 candidates (tile 16 j of a block: level 0 under every pattern; at most one per CU):
+    // ONE launch decodes them and, in a workgroup of its own, gives the verdicts and makes the schedule (dec_level0_kernel).  Otherwise — many small
+    // blocks, option 23 = 0, another decode_algo, a device that refuses the kernel its LDS — dec_viol_kernel and dec_schedule_kernel, and the exec pass
+    // decodes every tile.
+    L0Cands cands;
+    uint32_t n_cand = 0;
+    bool l0 = tiles && c->level0_by_e && c->decode_algo == 0 && uint64_t(n) < (1ull << kL0BlockBits);
+    if (l0) {
+        const uint32_t cap = std::min<uint32_t>(c->l0_grid_cap > 0 ? uint32_t(c->l0_grid_cap) : uint32_t(c->n_cus), kL0MaxCands);
+        for (int i = 0; i < n && n_cand <= cap; i++)
+            for (uint32_t j = 0; 16 * j < c->h_blocks[i].n_tiles && n_cand <= cap; j++, n_cand++)
+                if (n_cand < cap) cands.e[n_cand] = uint32_t(i) | (j << kL0BlockBits);
+        l0 = n_cand >= 1 && n_cand <= cap;
+    }
+    if (l0 && !c->l0_attr) {   // refused: not a reason to fail the call
+        if (!c->l0_attr_failed && hipFuncSetAttribute(reinterpret_cast<const void*>(dec_level0_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(kGenLds)) == hipSuccess) c->l0_attr = true;
+        else { (void)hipGetLastError(); c->l0_attr_failed = true; l0 = false; }
+    }
+    uint32_t* n_general = jump ? &gen->n_general : nullptr;
+    // the call's counters (d_gen_acc) start from 0 in its first group, whether or not that group has tiles to schedule
+    HIPCHK(c, c->d_gen_acc.ensure(64));
+    const uint32_t acc_reset = c->acc_call != c->dec_call ? 1u : 0u;
+    if (acc_reset) c->l0_launches = 0;
+    c->acc_call = c->dec_call;
     {
         Timer t(c, T_DEC_PARSE, st);
         // the header pass also initialises the workspace words the later passes expect (two memsets = two more launches otherwise)
@@ -608,30 +634,26 @@ int decode_parallel(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, uint8_t* d
             HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(dec_general_kernel), kGenThreads, kGenLds));
             c->gen_grid = per_cu >= 1 ? c->n_cus * per_cu : 0;
         }
-        if (segs)
-            hipLaunchKernelGGL(dec_viol_kernel, dim3((segs + 255) / 256), dim3(256), 0, st, seg_block, sviol, dec, jump ? &gen->n_general : nullptr, segs);
-        if (tiles) {
-            HIPCHK(c, c->d_gen_acc.ensure(64));
-            const uint32_t reset = c->acc_call != c->dec_call ? 1u : 0u;
-            c->acc_call = c->dec_call;
+        if (!l0 && segs)
+            hipLaunchKernelGGL(dec_viol_kernel, dim3((segs + 255) / 256), dim3(256), 0, st, seg_block, sviol, dec, n_general, segs);
+        if (!l0 && tiles)
             hipLaunchKernelGGL(dec_schedule_kernel, dim3(1), dim3(1024), 0, st, blocks, tile_block, dec, order, tiles, uint32_t(n),
-                               gen_list, gen_words, gen_settle_wgs(c, n), c->d_gen_acc.as<uint32_t>(), reset);
-        }
+                               gen_list, gen_words, gen_settle_wgs(c, n), c->d_gen_acc.as<uint32_t>(), acc_reset);
+        if (!tiles && acc_reset) HIPCHK(c, hipMemsetAsync(c->d_gen_acc.p, 0, 8, st));   // (no schedule in this group: the call's counters still start from 0)
     }
     {
         Timer t(c, T_DEC_EXEC, st);
         unsigned long long* prof = c->prof_on ? c->d_prof.as<unsigned long long>() : nullptr;
-        // level-0 tiles first, by role E of the general pass, when they are few (dec_level0_kernel; option 23 = 0: off)
-        uint32_t l0_grid = 0;
-        if (tiles && c->level0_by_e && c->decode_algo == 0) {
-            if ((r = raise_lds_once(c, c->l0_attr, Kernels{{dec_level0_kernel, kGenLds}}))) return r;
-            l0_grid = std::min<uint32_t>(uint32_t(c->n_cus), tiles);
-            hipLaunchKernelGGL(dec_level0_kernel, dim3(l0_grid), dim3(kGenThreads), kGenLds, st, d_src, d_dst, blocks, dec, tok_pos, round_d, round_rep, tile_start,
-                               order, tile_block, tile_done, gen);
+        // the level-0 candidates first, by role E of the general pass, one per workgroup; the last workgroup gives the verdicts and makes the schedule
+        if (l0) {
+            const L0Sched sc{seg_block, tile_block, sviol, n_general, order, gen_list, gen_words, c->d_gen_acc.as<uint32_t>(), segs, tiles, uint32_t(n), gen_settle_wgs(c, n), acc_reset};
+            hipLaunchKernelGGL(dec_level0_kernel, dim3(n_cand + 1), dim3(kGenThreads), kGenLds, st, d_src, d_dst, blocks, dec, tok_pos, round_d, round_rep, tile_start,
+                               tile_done, cands, sc);
+            c->l0_launches++;
         }
         if (tiles)
             hipLaunchKernelGGL(dec_exec2_kernel, dim3(tiles), dim3(kExecThreads), kExecLds, st, d_src, d_dst, blocks, tile_block, dec, tile_start, tok_pos,
-                               round_d, round_rep, order, tile_done, ticket, tiles, prof, gen_words, l0_grid);
+                               round_d, round_rep, order, tile_done, ticket, tiles, prof, l0 ? 1u : 0u);
     }
     {
         Timer tg(c, T_DEC_GENERAL, st);   // (+ the result pass)
@@ -680,7 +702,7 @@ int decode_device_group(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, uint8_
 }
 
 // A decode API call starts: counters 2 and 6 (mlz_get_counter) describe it alone from here on.  Every decode_device_locked of the call
-// (host groups, stream groups) adds to d_gen_acc, the first schedule kernel of the call resets it, and a call that launches none reports 0.
+// (host groups, stream groups) adds to d_gen_acc, the call's first group resets it, and a call that runs none reports 0.
 void begin_decode_call(mlz_ctx* c) { c->call_seq++; c->dec_call = c->call_seq; }
 
 int decode_device_locked(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, uint8_t* d_dst, const mlz_block_desc* desc, int n, int64_t* d_out_len,
@@ -1146,6 +1168,7 @@ int mlz_set_option(mlz_ctx* c, int opt, int64_t value) {
     case MLZ_OPT_LEVEL0_KERNEL: c->level0_by_e = int(value); return 0;  // decode: 1 (default) = level-0 tiles, when no more than CUs, by dec_level0_kernel before the exec pass; 0 = by the exec pass
     case MLZ_OPT_FUSED_SERIALIZER: c->fuse_ser = int(value); return 0;  // encode: 1 (default) = the match kernel serializes its pieces itself, 0 = the separate serializer kernel of rounds 2-5 (cross-checks)
     case MLZ_OPT_GEN_SETTLE_CAP: c->gen_settle_cap = int(value); return 0;  // tuning: role S workgroups of the general pass at most
+    case 25 /* debug, unnamed in the header */: c->l0_grid_cap = int(value); return 0;  // debug: level-0 candidates dec_level0_kernel is launched for at most (0 = the CU count)
     case MLZ_OPT_L2_FREE: c->l2_free = int(value); return 0;  // LevelBalanced: 1 = no tile levels (ratio of the reference's L2 and better; blocks decode as general blocks)
     case MLZ_OPT_GEN_PACKED: c->gen_force_packed = int(value); return 0;  // tests: general blocks settle through the byte-packed pool (fallback path of dec_general_kernel)
     case MLZ_OPT_GEN_SPIN: c->gen_spin_limit = value > 0 ? uint32_t(value) : 1u; return 0;  // grid-barrier patience of the general-block pass, in polls (tests)
@@ -1214,7 +1237,7 @@ int64_t mlz_get_counter(mlz_ctx* c, int which) {
         // 2: blocks of the last decode call that fit no level pattern; 6: workgroups per block (1, 2 or 4) its general pass settled with (0 = no general block).
         // Both over ALL internal groups of the call (sum / maximum, kept by dec_schedule_kernel); waits for the device.
         std::lock_guard<std::mutex> lk(c->mu);
-        if (!c->d_gen_acc.p || c->acc_call != c->dec_call) return 0;   // (the last decode call launched no schedule kernel: nothing reset the words)
+        if (!c->d_gen_acc.p || c->acc_call != c->dec_call) return 0;   // (the last decode call ran no group of the parallel decoder: nothing reset the words)
         uint32_t v[2] = {0, 0};
         if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
             hipMemcpy(v, c->d_gen_acc.p, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return -MLZ_ERR_HIP;
@@ -1230,6 +1253,7 @@ int64_t mlz_get_counter(mlz_ctx* c, int which) {
     if (which == 7 || which == 8) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(which == 7 ? c->range_chunks : c->range_scratch); }
     if (which == 9) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->range_plan_host); }
     if (which == 12) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->batch_long); }
+    if (which == 13) { std::lock_guard<std::mutex> lk(c->mu); return c->acc_call == c->dec_call ? int64_t(c->l0_launches) : 0; }   // groups of the last decode call that took dec_level0_kernel's launch
     if (which == 10 || which == 11) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(which == 10 ? c->search_chunks : c->search_tables); }
     std::lock_guard<std::mutex> lk(c->q_mu);
     return which == 0 ? int64_t(c->q_batches) : which == 1 ? int64_t(c->q_requests) : -MLZ_ERR_ARG;
