@@ -439,7 +439,9 @@ int64_t mlz_dev_reader_search_many(mlz_dev_reader* reader, void* stream, uint32_
                                    uint64_t* stats /* host, may be NULL: 4 values */);
 
 /* The search over a BATCH of streams in HBM — which of these objects hold any of these keys, and where — is declared in a header of its own,
- * include/minlz_hip_search_batch.h, which includes this one. */
+ * include/minlz_hip_search_batch.h, which includes this one.  A batch of streams opened as ONE handle (mlz_stream_open_batch_device), on which every
+ * mlz_dev_reader_* call below and above works as on the streams' concatenation, and the calls that turn its positions and record numbers back into
+ * (stream, position or record inside the stream), are declared in include/minlz_hip_stream_set.h. */
 
 /* mlz_dev_reader_search_records: the RECORDS of the decoded stream that hold the pattern, each once, in stream order, packed into d_dst — what
  *   `mz search pattern file.mz` prints, and with rec_cap == 0 and dst_cap == 0 what `-c` counts.  A record is a maximal run of decoded bytes that
@@ -557,8 +559,9 @@ int64_t mlz_dev_reader_record_range(mlz_dev_reader* reader, uint64_t first, uint
  *   the sizes of before / after) and compact.  32 bytes visit the host, behind the search phase's own; nothing per record or per occurrence does.
  *   Synchronous; `stream` as for mlz_dev_reader_read.  Workspace, grow-only and part of mlz_get_counter 4: 16 bytes per 32 records (two
  *   bitmaps and two scan arrays) beside the search phase's.
- *   Out of scope: regular expressions; Unicode or locale folding; per-record lists of which pattern matched; delimiters of more than one byte; grep over
- *   batches of streams; a call that works without a record index (mlz_dev_reader_search_records remains the bounded-reach form for that). */
+ *   Out of scope: regular expressions; Unicode or locale folding; per-record lists of which pattern matched; delimiters of more than one byte; a grep over
+ *   batches of streams other than on a set handle (include/minlz_hip_stream_set.h: the streams' concatenation); a call that works without a record
+ *   index (mlz_dev_reader_search_records remains the bounded-reach form for that). */
 #define MLZ_GREP_INVERT 16u
 int64_t mlz_dev_reader_grep_records(mlz_dev_reader* reader, void* stream, uint32_t flags,
                                     const uint8_t* patterns, const uint32_t* pattern_len, size_t n_patterns,   /* host, as mlz_dev_reader_search_many */

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension header include/minlz_hip_search_batch.h.
+"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension headers include/minlz_hip_search_batch.h and include/minlz_hip_stream_set.h.
 
 There is no CPU fallback here: if libminlz_hip.so is missing or HIP is unavailable, calls raise.
 """
@@ -103,10 +103,19 @@ ABI = {
 SYMBOLS = list(ABI)
 
 # The functions of the extension headers beside include/minlz_hip.h, header by header -> {name: (restype, argtypes)}, bound like the ABI's
-# (tests/test_stream_search_batch_host.py holds the table against the header's prototypes)
+# (tests/test_stream_search_batch_host.py and tests/test_stream_set_host.py hold the tables against the headers' prototypes)
 ABI_EXT = {
     "minlz_hip_search_batch.h": {
         "mlz_stream_search_batch_device": (i64, [vp, vp, u32, vp, P(BlockDesc), i32, vp, vp, sz, P(i64), vp, vp, vp, vp, vp, vp, sz, P(u64)]),
+    },
+    "minlz_hip_stream_set.h": {
+        "mlz_stream_open_batch_device": (i64, [vp, vp, vp, P(BlockDesc), i32, P(i64), P(vp)]),
+        "mlz_dev_reader_stream_count": (i64, [vp]),
+        "mlz_dev_reader_stream_bases": (i64, [vp, P(u64)]),
+        "mlz_dev_reader_locate": (i64, [vp, vp, vp, sz, vp, vp]),
+        "mlz_dev_reader_read_streams_device": (i64, [vp, vp, u32, vp, vp, vp, sz, vp, sz, vp]),
+        "mlz_dev_reader_stream_records": (i64, [vp, vp, P(u64), P(u64)]),
+        "mlz_dev_reader_locate_records": (i64, [vp, vp, vp, sz, vp, vp]),
     },
 }
 

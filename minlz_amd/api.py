@@ -310,9 +310,21 @@ class Context:
         h = C.c_void_p()
         return DeviceReader(self, h, self._call("mlz_stream_open_device", stream, d_src, n, C.byref(h)))
 
+    def stream_open_batch_device(self, d_src, spans, stream=None):
+        """mlz_stream_open_batch_device (include/minlz_hip_stream_set.h): every stream (src_off, src_len) of the buffer at d_src opened as ONE
+        reader over the streams' decoded bytes one behind the other -> (DeviceReader, [result]: the decoded size or the framing error
+        -MLZ_ERR_* of each stream; a failed one is left out of the reader).  The caller keeps d_src alive and unchanged while it is open."""
+        arr = _block_descs(spans)
+        n = len(arr)
+        out = (C.c_int64 * max(n, 1))()
+        h = C.c_void_p()
+        size = self._call("mlz_stream_open_batch_device", stream, d_src, arr, n, out, C.byref(h))
+        return DeviceReader(self, h, size), [int(out[i]) for i in range(n)]
+
 
 class DeviceReader:
-    """mlz_dev_reader: the device-resident ReadSeeker of one stream (Context.stream_open_device).  A context manager; close() frees it."""
+    """mlz_dev_reader: the device-resident ReadSeeker of one stream (Context.stream_open_device) or of a set of streams
+    (Context.stream_open_batch_device).  A context manager; close() frees it."""
 
     def __init__(self, ctx, handle, size):
         self.ctx, self.handle, self.size = ctx, handle, size
@@ -436,6 +448,40 @@ class DeviceReader:
         off, ln = C.c_uint64(), C.c_uint64()
         self._call("mlz_dev_reader_record_range", first, count, C.byref(off), C.byref(ln))
         return int(off.value), int(ln.value)
+
+    # ---- a set of streams behind the reader (include/minlz_hip_stream_set.h); a reader of one stream answers as a set of one ----
+    def stream_count(self):
+        """mlz_dev_reader_stream_count: the streams the reader was opened with, failed ones included."""
+        return self._call("mlz_dev_reader_stream_count")
+
+    def stream_bases(self):
+        """mlz_dev_reader_stream_bases -> the count + 1 bases: stream i's decoded bytes are [bases[i], bases[i + 1]) of the reader."""
+        out = (C.c_uint64 * (self.stream_count() + 1))()
+        self._call("mlz_dev_reader_stream_bases", out)
+        return [int(v) for v in out]
+
+    def locate(self, d_pos, n, d_which, d_local, stream=None):
+        """mlz_dev_reader_locate.  d_pos: device address of n uint64 positions of the reader; d_which, d_local: room for n uint32 and n uint64,
+        which receive each position's stream and the position inside it (0xFFFFFFFF and 0 at or beyond the size).  -> the positions inside."""
+        return self._call("mlz_dev_reader_locate", stream, d_pos, n, d_which, d_local)
+
+    def read_streams_device(self, d_which, d_off, d_len, n, d_dst, dst_cap, d_starts=None, ignore_crc=False, stream=None):
+        """mlz_dev_reader_read_streams_device: read_device with range i = bytes [off[i], off[i] + len[i]) of stream which[i] (device addresses
+        of n uint32, uint64, uint64).  A range that leaves its stream raises, and nothing has been written then.  -> the sum of the lengths."""
+        return self._call("mlz_dev_reader_read_streams_device", stream, _flags(ignore_crc=ignore_crc), d_which, d_off, d_len, n, d_dst, dst_cap, d_starts)
+
+    def stream_records(self, stream=None):
+        """mlz_dev_reader_stream_records -> (first, joined): first[i] = the records that start in front of stream i (count + 1 values, the last
+        is the record count); joined = the streams whose last record runs on into the next stream.  Raises without a record index."""
+        first, joined = (C.c_uint64 * (self.stream_count() + 1))(), C.c_uint64()
+        self._call("mlz_dev_reader_stream_records", stream, first, C.byref(joined))
+        return [int(v) for v in first], int(joined.value)
+
+    def locate_records(self, d_rec_no, n, d_which, d_local_no, stream=None):
+        """mlz_dev_reader_locate_records.  d_rec_no: device address of n uint64 record numbers; d_which, d_local_no: room for n uint32 and n
+        uint64, which receive the stream each record starts in and its number inside that stream (0xFFFFFFFF and 0 at or beyond the record
+        count).  -> the numbers in range.  Raises without a record index."""
+        return self._call("mlz_dev_reader_locate_records", stream, d_rec_no, n, d_which, d_local_no)
 
     @staticmethod
     def _configs(cfgs):

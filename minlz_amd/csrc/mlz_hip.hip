@@ -18,6 +18,7 @@
 
 #include "../../include/minlz_hip.h"
 #include "../../include/minlz_hip_search_batch.h"
+#include "../../include/minlz_hip_stream_set.h"
 #include "mlz_format.h"
 #include "mlz_kernels.h"
 
@@ -1345,3 +1346,4 @@ int mlz_debug_idxprof(unsigned long long* out) {
 #include "mlz_stream_records.hip.inc"
 #include "mlz_stream_record_index.hip.inc"
 #include "mlz_stream_grep.hip.inc"
+#include "mlz_stream_set.hip.inc"

@@ -83,6 +83,12 @@ struct mlz_dev_reader {
     uint64_t index_cap = 0, index_k = 0, index_n = 0;   // entries allocated, delimiters, records
     bool index_ready = false;
     uint8_t index_delim = 0;
+    // mlz_stream_open_batch_device (mlz_stream_set.hip.inc): a set of streams behind one handle.  bases: count + 1 values, stream i's decoded
+    // bytes are [bases[i], bases[i + 1]) of the handle ({0, size} for a handle of one stream); d_bases: the same where kernels can read them
+    // (device memory the handle owns, uploaded by the first call that needs them).  A set searches without inline tables and takes no sidecar.
+    bool set = false;
+    std::vector<uint64_t> bases;
+    void* d_bases = nullptr;
 };
 
 namespace {
@@ -160,6 +166,7 @@ int64_t mlz_stream_open_device(mlz_ctx* c, void* stream, const uint8_t* d_src, s
     const int e = stream_walk_device(c, static_cast<hipStream_t>(stream), d_src, n, &rd->chunks, &parsed, &rd->n_ident, &rd->ident_byte);
     if (e || parsed < 0) { delete rd; return e ? e : parsed; }   // a framing error: no handle
     rd->ctx = c; rd->d_src = d_src; rd->n = n; rd->size = parsed;
+    rd->bases = {0, uint64_t(parsed)};
     rd->dchunks.reserve(rd->chunks.size());
     for (const StreamChunk& ck : rd->chunks) rd->dchunks.push_back(mlz::RdevChunk{uint64_t(ck.out_off), uint64_t(ck.body_off), uint32_t(ck.n), ck.type});
     *out = rd;
@@ -185,10 +192,10 @@ int64_t mlz_dev_reader_read(mlz_dev_reader* rd, void* stream, uint32_t flags, co
 }
 
 void mlz_dev_reader_close(mlz_dev_reader* rd) {
-    if (rd && (rd->d_chunks || rd->search[0].d_tabs || rd->search[1].d_tabs || rd->side.d_tabs || rd->d_index)) {
+    if (rd && (rd->d_chunks || rd->search[0].d_tabs || rd->search[1].d_tabs || rd->side.d_tabs || rd->d_index || rd->d_bases)) {
         std::lock_guard<std::mutex> lk(rd->ctx->mu);
         if (hipSetDevice(rd->ctx->device) == hipSuccess)
-            for (void* p : {rd->d_chunks, rd->search[0].d_tabs, rd->search[1].d_tabs, rd->side.d_tabs, rd->d_index}) if (p) (void)hipFree(p);
+            for (void* p : {rd->d_chunks, rd->search[0].d_tabs, rd->search[1].d_tabs, rd->side.d_tabs, rd->d_index, rd->d_bases}) if (p) (void)hipFree(p);
     }
     delete rd;
 }

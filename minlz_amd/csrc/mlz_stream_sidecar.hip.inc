@@ -439,6 +439,7 @@ int64_t mlz_dev_reader_sidecar_bound(const mlz_dev_reader* rd, const mlz_search_
 int64_t mlz_dev_reader_build_sidecar(mlz_dev_reader* rd, void* stream, uint32_t flags, const mlz_search_config* cfgs, int n_cfgs, uint8_t* d_dst, size_t dst_cap) {
     std::vector<StreamTables> stb;
     if (!rd || !d_dst || !sidecar_configs(cfgs, n_cfgs, &stb)) return -MLZ_ERR_ARG;
+    if (rd->set) return -MLZ_ERR_UNSUPPORTED;   // a set of streams (mlz_stream_open_batch_device): as concatenated streams
     mlz_ctx* c = rd->ctx;
     std::lock_guard<std::mutex> lk(c->mu);
     if (enter_device(c)) return -MLZ_ERR_HIP;
@@ -452,6 +453,7 @@ int64_t mlz_dev_reader_build_sidecar(mlz_dev_reader* rd, void* stream, uint32_t 
 
 int64_t mlz_dev_reader_attach_sidecar(mlz_dev_reader* rd, void* stream, uint32_t flags, const uint8_t* d_side, size_t n_side) {
     if (!rd || (!d_side && n_side)) return -MLZ_ERR_ARG;
+    if (rd->set) return -MLZ_ERR_UNSUPPORTED;
     mlz_ctx* c = rd->ctx;
     std::lock_guard<std::mutex> lk(c->mu);
     if (enter_device(c)) return -MLZ_ERR_HIP;

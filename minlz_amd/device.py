@@ -1,7 +1,8 @@
 """The tensor layer over the C ABI: CUDA tensors through the device-resident calls of api.Context and api.DeviceReader.
 
 HipTensorCodec is the block and stream codec on tensors (the product path, what bench.py times); DeviceStream is a .mz stream in HBM
-opened for range reads, searches and record reads.  Every call runs on the current stream of the tensor's device.
+opened for range reads, searches and record reads, DeviceStreamSet many of them opened as one.  Every call runs on the current stream of
+the tensor's device.
 """
 import numpy as np
 import torch
@@ -187,6 +188,21 @@ class HipTensorCodec:
         runs once, here; a framing error raises."""
         return DeviceStream(self.ctx, _u8(t, "open_stream"))
 
+    def open_streams(self, t, spans, on_error="raise"):
+        """Many .mz streams that lie in one uint8 tensor on the device (stream i at t[off_i : off_i + len_i] for spans[i]) opened as ONE
+        DeviceStreamSet: a DeviceStream over their decoded bytes one behind the other, in the order of the spans (one call,
+        mlz_stream_open_batch_device).  on_error "raise": the first stream with a framing error raises its error, which names its index
+        (.index); "skip": such a stream is left out (size 0), and .errors names it."""
+        if on_error not in ("raise", "skip"):
+            raise ValueError("open_streams: on_error is \"raise\" or \"skip\"")
+        t = _u8(t, "open_streams")
+        s = DeviceStreamSet(self.ctx, t, _spans(t, spans, "open_streams"))
+        if on_error == "raise" and s.errors:
+            i = min(s.errors)
+            s.close()
+            self._raise_stream("open_streams", i, s.errors[i])
+        return s
+
 
 class DeviceStream:
     """A .mz stream on the device opened for random access (HipTensorCodec.open_stream): ReadSeeker.ReadAt (reader.go:1401-1487) with the
@@ -320,26 +336,32 @@ class DeviceStream:
         selected record and 0 for one that is context only (uint8); those records' bytes back to back (uint8) and the k + 1 places where
         they start in it and its size (int64) — tensors on the stream's device.
         count_only (grep -c): -> (R, the selected records) and nothing is written or read."""
-        dev = self.dev
-        pats = [patterns] if isinstance(patterns, (bytes, bytearray)) else list(patterns)
-        st = _stream(dev)
-        try:
-            self.reader.record_count()
-        except api.MinLZError:   # (no index yet)
-            self.reader.index_records(b"\n", ignore_crc=ignore_crc, stream=st)
-        kw = dict(invert=invert, before=before, after=after, ignore_crc=ignore_crc, no_tables=no_tables, stream=st, ignore_case=ignore_case)
+        dev, st = self.dev, _stream(self.dev)
+        R, totals, numbers, kinds = self._grep_numbers(patterns, 0 if count_only else max_records, invert=invert, before=before, after=after, ignore_crc=ignore_crc,
+                                                       no_tables=no_tables, ignore_case=ignore_case)
         if count_only:
-            _, totals, _ = self.reader.grep_records(pats, None, None, 0, **kw)
             return totals[0], totals[1]
-        cap = min(max_records, self.reader.record_count())
-        numbers, d_numbers = _room(cap, torch.int64, dev)
-        kinds, d_kinds = _room(cap, torch.uint8, dev)
-        R, totals, _ = self.reader.grep_records(pats, d_numbers, d_kinds, cap, **kw)
-        k = min(R, cap)
+        k = numbers.numel()
         starts = torch.zeros(k + 1, dtype=torch.int64, device=dev)
         data = torch.empty(max(totals[2], 1), dtype=torch.uint8, device=dev)
         got = self.reader.read_records(numbers.data_ptr(), k, data.data_ptr(), totals[2], d_starts=starts.data_ptr(), ignore_crc=ignore_crc, stream=st) if k else 0
-        return R, numbers[:k], kinds[:k], data[:got], starts
+        return R, numbers, kinds, data[:got], starts
+
+    def _grep_numbers(self, patterns, max_records, **kw):
+        """grep's first half -> (R, the call's totals, the smallest min(R, max_records) record numbers, their kinds); builds the index for b"\n"
+        when the stream has none."""
+        dev, st = self.dev, _stream(self.dev)
+        pats = [patterns] if isinstance(patterns, (bytes, bytearray)) else list(patterns)
+        try:
+            self.reader.record_count()
+        except api.MinLZError:   # (no index yet)
+            self.reader.index_records(b"\n", ignore_crc=kw.get("ignore_crc", False), stream=st)
+        cap = min(max_records, self.reader.record_count())
+        numbers, d_numbers = _room(cap, torch.int64, dev)
+        kinds, d_kinds = _room(cap, torch.uint8, dev)
+        R, totals, _ = self.reader.grep_records(pats, d_numbers, d_kinds, cap, stream=st, **kw)
+        k = min(R, cap)
+        return R, totals, numbers[:k], kinds[:k]
 
     def read_record_range(self, first, count, ignore_crc=False):
         """Records first .. first + count - 1 as they lie in the decoded stream, the delimiters between them included -> a new uint8 tensor."""
@@ -378,3 +400,87 @@ class DeviceStream:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class DeviceStreamSet(DeviceStream):
+    """Many .mz streams on the device opened as ONE DeviceStream (HipTensorCodec.open_streams): its decoded bytes are the streams' decoded
+    bytes one behind the other, and read_ranges, search, search_many, search_records, index_records, read_records, line_numbers and grep
+    work on that concatenation — a range, an occurrence or a record may cross from one stream into the next.  The calls here turn positions
+    and record numbers back into (stream, position or record inside the stream), on the device.  No search tables and no sidecar.
+    .sizes: every stream's decoded size (0 for a failed one); .errors: {index: negative code} of the streams left out for a framing error;
+    .bases: the n + 1 places where the streams start in the set (a list of ints; the last is .size)."""
+
+    def __init__(self, ctx, t, spans):
+        self.t, self.dev, self.spans = t, t.device, spans
+        self.reader, res = ctx.stream_open_batch_device(t.data_ptr() if spans else None, spans, stream=_stream(t.device))
+        self.size = self.reader.size
+        self.side = None
+        self.sizes = [max(r, 0) for r in res]
+        self.errors = {i: r for i, r in enumerate(res) if r < 0}
+        self.bases = self.reader.stream_bases()
+
+    def _located(self, call, items, what):
+        items = _items(items, self.dev, what)
+        n = items.numel()
+        which = torch.full((max(n, 1),), -1, dtype=torch.int32, device=self.dev)
+        local = torch.zeros(max(n, 1), dtype=torch.int64, device=self.dev)
+        if n:
+            call(items.data_ptr(), n, which.data_ptr(), local.data_ptr(), stream=_stream(self.dev))
+        return which[:n], local[:n]
+
+    def locate(self, positions):
+        """(which, local): the stream of every position of the set in `positions` (int64 or uint64 tensor on the device) and the position
+        inside that stream's decoded bytes — int32 and int64 tensors; -1 and 0 for a position at or beyond the size.  With the offsets of
+        search / search_many and a pattern of L bytes: local + L > sizes[which] is an occurrence that crosses a stream's end."""
+        return self._located(self.reader.locate, positions, "locate")
+
+    def locate_records(self, rec_no):
+        """(which, local_no): the stream in which every record of `rec_no` (int64 or uint64 tensor on the device) starts and its number
+        inside that stream — int32 and int64 tensors; -1 and 0 at or beyond the record count.  Needs the record index."""
+        if _items(rec_no, self.dev, "locate_records").numel() == 0:
+            self.reader.record_count()
+        return self._located(self.reader.locate_records, rec_no, "locate_records")
+
+    def read_stream_ranges(self, which, offsets, lengths, ignore_crc=False, return_starts=False):
+        """read_ranges with every range relative to its stream: bytes [offsets[i], offsets[i] + lengths[i]) of stream which[i], back to back in
+        the order given -> one new uint8 tensor (return_starts: and the n + 1 places where the ranges start in it).  which: an int32 or int64
+        tensor on the device; offsets, lengths: int64 or uint64.  A range that leaves its stream raises."""
+        for a in (offsets, lengths):
+            _items(a, self.dev, "read_stream_ranges")
+        if not torch.is_tensor(which) or which.dtype not in (torch.int32, torch.int64) or which.dim() != 1 or which.device != self.dev:
+            raise ValueError("read_stream_ranges: which is a 1-d int32 or int64 tensor on the stream's device")
+        n = offsets.numel()
+        if lengths.numel() != n or which.numel() != n:
+            raise ValueError("read_stream_ranges: as many streams and lengths as offsets")
+        if which.dtype == torch.int64:   # (a number that does not fit is beyond every count: it stays so)
+            which = which.clamp(-1, 0x7FFFFFFF).to(torch.int32)
+        which = which.contiguous()
+        total = int(lengths.view(torch.int64).sum()) if n else 0
+        if total < 0 or total > n * max(self.sizes + [0]):
+            total = 0
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=self.dev)
+        starts = torch.zeros(n + 1, dtype=torch.int64, device=self.dev) if return_starts else None
+        got = self.reader.read_streams_device(which.data_ptr() if n else None, offsets.data_ptr() if n else None, lengths.data_ptr() if n else None, n, out.data_ptr(), total,
+                                              d_starts=starts.data_ptr() if return_starts and n else None, ignore_crc=ignore_crc, stream=_stream(self.dev))
+        return (out[:got], starts) if return_starts else out[:got]
+
+    def stream_records(self):
+        """(first, joined): first[i] = the records of the set that start in front of stream i (n + 1 ints; the last is the record count);
+        joined = the streams whose last record runs on into the next stream.  With joined == 0 stream i's own records are the set's
+        records first[i] .. first[i + 1] - 1.  Needs the record index."""
+        return self.reader.stream_records(stream=_stream(self.dev))
+
+    def grep_streams(self, patterns, invert=False, before=0, after=0, max_records=1 << 20, ignore_crc=False, no_tables=False, ignore_case=False):
+        """grep -H -n over the set: grep's selected and context records as (which, line_in_stream, kind) — the stream each record starts in
+        (int32), its number inside that stream (int64, from 0) and 1 for a selected record, 0 for context only (uint8); tensors on the
+        device, in the set's order.  grep followed by locate_records; nothing per record visits the host."""
+        _, _, numbers, kinds = self._grep_numbers(patterns, max_records, invert=invert, before=before, after=after, ignore_crc=ignore_crc, no_tables=no_tables,
+                                                  ignore_case=ignore_case)
+        which, line = self.locate_records(numbers)
+        return which, line, kinds
+
+    def build_sidecar(self, cfgs, ignore_crc=False):
+        raise api.ErrUnsupported("build_sidecar: a set of streams takes no sidecar")
+
+    def attach_sidecar(self, side, ignore_crc=False):
+        raise api.ErrUnsupported("attach_sidecar: a set of streams takes no sidecar")
