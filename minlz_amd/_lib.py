@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension headers include/minlz_hip_search_batch.h and include/minlz_hip_stream_set.h.
+"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension headers include/minlz_hip_search_batch.h, include/minlz_hip_stream_set.h and include/minlz_hip_regex.h.
 
 There is no CPU fallback here: if libminlz_hip.so is missing or HIP is unavailable, calls raise.
 """
@@ -116,6 +116,13 @@ ABI_EXT = {
         "mlz_dev_reader_read_streams_device": (i64, [vp, vp, u32, vp, vp, vp, sz, vp, sz, vp]),
         "mlz_dev_reader_stream_records": (i64, [vp, vp, P(u64), P(u64)]),
         "mlz_dev_reader_locate_records": (i64, [vp, vp, vp, sz, vp, vp]),
+    },
+    "minlz_hip_regex.h": {
+        "mlz_regex_compile": (i32, [vp, vp, sz, u32, P(vp), P(u64)]),
+        "mlz_regex_free": (None, [vp]),
+        "mlz_regex_info": (i32, [vp, P(u64)]),
+        "mlz_regex_test": (i32, [vp, vp, sz]),
+        "mlz_dev_reader_grep_regex": (i64, [vp, vp, u32, vp, u64, u64, vp, vp, sz, P(u64), P(u64)]),
     },
 }
 

@@ -16,6 +16,8 @@ ERR_CORRUPT, ERR_TOO_LARGE, ERR_UNSUPPORTED, ERR_INVALID_LEVEL, ERR_CRC, ERR_DST
 STREAM_ADD_INDEX, STREAM_IGNORE_CRC, STREAM_SEARCH_TABLES, SEARCH_NO_TABLES, GREP_INVERT = 1, 2, 4, 8, 16
 IGNORE_CASE = 32                  # MLZ_SEARCH_IGNORE_CASE: the searches' ignore_case=True
 SEARCH_MAX_PATTERNS = 4096
+REGEX_IGNORE_CASE = 1             # MLZ_REGEX_IGNORE_CASE (include/minlz_hip_regex.h): Regex(..., ignore_case=True)
+REGEX_MAX_RECORD = 1 << 20        # MLZ_REGEX_MAX_RECORD: the longest record grep_regex accepts
 
 OPT_DECODE_ALGO, OPT_ENCODE_FAR, OPT_DEBUG_STATUS, OPT_PROFILE, OPT_PROFILE_READ, OPT_TILE_TIMELINE_READ, OPT_GENERAL_ALGO = 1, 2, 3, 4, 5, 7, 8
 OPT_GEN_SPIN, OPT_HOST_GROUP_ENC, OPT_HOST_GROUP_DEC, OPT_TIMER_MASK, OPT_GEN_PACKED, OPT_L2_FREE, OPT_DEVICE_GROUP = 9, 10, 11, 12, 13, 14, 17
@@ -119,6 +121,56 @@ def _ints(a, n=4):
     return tuple(int(a[i]) for i in range(n))
 
 
+class Regex:
+    """mlz_regex: regular expressions over bytes (a bytes object, or a sequence of up to 256 of them: grep -E -e a -e b) compiled on the host
+    into one search automaton, for DeviceReader.grep_regex.  The syntax is the subset of Python's `re` on bytes that
+    include/minlz_hip_regex.h lists; ignore_case: re.IGNORECASE on bytes.  Needs no context and no GPU.  A context manager; close() frees it.
+    A syntax error raises MinLZError and a refused construct or a limit ErrUnsupported, with the expression's index and the offset."""
+
+    def __init__(self, exprs, ignore_case=False):
+        self.handle = C.c_void_p()
+        exprs = [bytes(exprs)] if isinstance(exprs, (bytes, bytearray, memoryview)) else [bytes(e) for e in exprs]
+        where = (C.c_uint64 * 2)()
+        blob, lens, n = _patterns(exprs)
+        r = _lib.lib().mlz_regex_compile(blob, lens, n, REGEX_IGNORE_CASE if ignore_case else 0, C.byref(self.handle), where)
+        if r < 0:
+            self.handle = C.c_void_p()
+            raise _error(-r, "Regex: ", " in expression %d at offset %d" % (where[0], where[1]))
+
+    def _open(self):
+        if not self.handle:
+            raise ValueError("Regex is closed")
+        return self.handle
+
+    def info(self):
+        """mlz_regex_info -> (states, byte classes, bytes of class map and table as the kernel holds them, whether the empty record matches)."""
+        info = _stats()
+        _lib.lib().mlz_regex_info(self._open(), info)
+        return int(info[0]), int(info[1]), int(info[2]), bool(info[3] & 1)
+
+    def test(self, record):
+        """mlz_regex_test: does `record` hold a match, by the rule the kernel runs."""
+        rec = bytes(record)
+        return _lib.lib().mlz_regex_test(self._open(), rec, len(rec)) == 1
+
+    def close(self):
+        if self.handle:
+            _lib.lib().mlz_regex_free(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     """One HIP device context (mlz_ctx). Thread-safe on the C side."""
 
@@ -201,7 +253,7 @@ class Context:
         return self.counter(COUNTER_RANGE_CHUNKS), self.counter(COUNTER_RANGE_SCRATCH_BYTES)
 
     def search_plan(self):
-        """(chunks decoded or copied, chunks with a usable search table) of the context's last DeviceReader.search, search_many or grep_records (mlz_get_counter 10, 11)."""
+        """(chunks decoded or copied, chunks with a usable search table) of the context's last DeviceReader.search, search_many, grep_records or grep_regex (mlz_get_counter 10, 11)."""
         return self.counter(COUNTER_SEARCH_CHUNKS), self.counter(COUNTER_SEARCH_TABLES)
 
     def range_plan_host_bytes(self):
@@ -440,6 +492,17 @@ class DeviceReader:
         totals, stats = _stats(), _stats()
         r = self._call("mlz_dev_reader_grep_records", stream, _flags(ignore_crc=ignore_crc, no_tables=no_tables, invert=invert, ignore_case=ignore_case), *_patterns(patterns), before, after,
                        d_rec_no, d_rec_kind, rec_cap, totals, stats)
+        return r, _ints(totals), _ints(stats)
+
+    def grep_regex(self, regex, d_rec_no, d_rec_kind, rec_cap, invert=False, before=0, after=0, ignore_crc=False, stream=None):
+        """mlz_dev_reader_grep_regex: grep_records with the selected records decided by `regex` (a Regex): a record is selected when its
+        bytes, the delimiter excluded, hold a match (an empty record: when the expression matches the empty string), with invert when they
+        hold none.  d_rec_no, d_rec_kind, rec_cap, before and after as in grep_records.  Every chunk is decoded once; an index with a
+        record longer than REGEX_MAX_RECORD raises ErrUnsupported before that.
+        -> (R, (R, selected records, bytes of the written records, bytes of all R records), (data chunks, chunks decoded, 0, 0))."""
+        self._open()
+        totals, stats = _stats(), _stats()
+        r = self._call("mlz_dev_reader_grep_regex", stream, _flags(ignore_crc=ignore_crc, invert=invert), regex._open(), before, after, d_rec_no, d_rec_kind, rec_cap, totals, stats)
         return r, _ints(totals), _ints(stats)
 
     def record_range(self, first, count):

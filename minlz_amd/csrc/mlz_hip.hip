@@ -1347,3 +1347,4 @@ int mlz_debug_idxprof(unsigned long long* out) {
 #include "mlz_stream_record_index.hip.inc"
 #include "mlz_stream_grep.hip.inc"
 #include "mlz_stream_set.hip.inc"
+#include "mlz_stream_regex.hip.inc"

@@ -80,6 +80,30 @@ __global__ __launch_bounds__(kGrepCompactThreads) void grep_compact_kernel(const
 namespace {
 
 struct GrepOut { uint64_t* d_rec_no; uint8_t* d_rec_kind; uint64_t rec_cap; };
+// A grep's regions of the workspace: the totals (zeroed) | the marked words, then S | C | the backward scan | ranks, W words each
+struct GrepWork { mlz::GrepTotals* tot; uint32_t *sel, *ctx, *above, *rank; };
+
+// What every grep runs behind its mark phase, whose bits are in w.sel: select and compact, the totals home and their check against the index.
+// Returns R; `call` names the entry point in an error's text.
+int64_t grep_select_compact(mlz_dev_reader* rd, hipStream_t sm, const char* call, bool invert, uint64_t before, uint64_t after, const GrepOut& out, const GrepWork& w, uint64_t* totals) {
+    mlz_ctx* c = rd->ctx;
+    const uint64_t N = rd->index_n, W = mlz::grep_words(N);
+    const uint64_t* D = static_cast<const uint64_t*>(rd->d_index);
+    hipLaunchKernelGGL(mlz::grep_select_kernel, dim3(1), dim3(mlz::kGrepScanThreads), 0, sm, w.sel, w.ctx, w.above, w.rank, W, N, invert ? 1u : 0u, mlz::grep_clamp(before, N),
+                       mlz::grep_clamp(after, N), w.tot);
+    hipLaunchKernelGGL(mlz::grep_compact_kernel, dim3(uint32_t((W + mlz::kGrepCompactThreads - 1) / mlz::kGrepCompactThreads)), dim3(mlz::kGrepCompactThreads), 0, sm,
+                       static_cast<const uint32_t*>(w.ctx), static_cast<const uint32_t*>(w.sel), static_cast<const uint32_t*>(w.rank), W, D, rd->index_k, uint64_t(rd->size), out.rec_cap,
+                       out.d_rec_no, out.d_rec_kind, w.tot);
+    const int e = fetch(c, sm, c->pinned2, w.tot, sizeof(mlz::GrepTotals));
+    if (e) return e;
+    const mlz::GrepTotals t = *static_cast<const mlz::GrepTotals*>(c->pinned2);
+    if (t.records > N || t.selected > t.records || t.written > t.bytes || t.bytes > uint64_t(rd->size)) {
+        c->err = std::string(call) + ": the totals do not fit the index";
+        return -MLZ_ERR_HIP;
+    }
+    if (totals) { totals[0] = t.records; totals[1] = t.selected; totals[2] = t.written; totals[3] = t.bytes; }
+    return int64_t(t.records);
+}
 
 int64_t dev_reader_grep_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* patterns, const uint32_t* pattern_len, size_t n, uint64_t before, uint64_t after,
                                const GrepOut& out, uint64_t* totals, uint64_t* stats) {
@@ -138,20 +162,7 @@ int64_t dev_reader_grep_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flag
         });
         if (r < 0) return r;   // (nothing has been written to the caller's arrays)
     }
-    hipLaunchKernelGGL(mlz::grep_select_kernel, dim3(1), dim3(mlz::kGrepScanThreads), 0, sm, d_sel, d_ctx, d_above, d_rank, W, N, (flags & MLZ_GREP_INVERT) ? 1u : 0u,
-                       mlz::grep_clamp(before, N), mlz::grep_clamp(after, N), d_tot);
-    hipLaunchKernelGGL(mlz::grep_compact_kernel, dim3(uint32_t((W + mlz::kGrepCompactThreads - 1) / mlz::kGrepCompactThreads)), dim3(mlz::kGrepCompactThreads), 0, sm,
-                       static_cast<const uint32_t*>(d_ctx), static_cast<const uint32_t*>(d_sel), static_cast<const uint32_t*>(d_rank), W, D, rd->index_k, uint64_t(rd->size), out.rec_cap,
-                       out.d_rec_no, out.d_rec_kind, d_tot);
-    const int e = fetch(c, sm, c->pinned2, d_tot, sizeof(mlz::GrepTotals));
-    if (e) return e;
-    const mlz::GrepTotals t = *static_cast<const mlz::GrepTotals*>(c->pinned2);
-    if (t.records > N || t.selected > t.records || t.written > t.bytes || t.bytes > uint64_t(rd->size)) {
-        c->err = "mlz_dev_reader_grep_records: the totals do not fit the index";
-        return -MLZ_ERR_HIP;
-    }
-    if (totals) { totals[0] = t.records; totals[1] = t.selected; totals[2] = t.written; totals[3] = t.bytes; }
-    return int64_t(t.records);
+    return grep_select_compact(rd, sm, "mlz_dev_reader_grep_records", (flags & MLZ_GREP_INVERT) != 0, before, after, out, GrepWork{d_tot, d_sel, d_ctx, d_above, d_rank}, totals);
 }
 
 }  // namespace

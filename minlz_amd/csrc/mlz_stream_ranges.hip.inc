@@ -83,6 +83,10 @@ struct mlz_dev_reader {
     uint64_t index_cap = 0, index_k = 0, index_n = 0;   // entries allocated, delimiters, records
     bool index_ready = false;
     uint8_t index_delim = 0;
+    // mlz_dev_reader_grep_regex (mlz_stream_regex.hip.inc): the length of the index's longest record, found by the first such call and kept
+    // beside the index; whatever replaces the index clears longest_ready
+    uint64_t index_longest = 0;
+    bool index_longest_ready = false;
     // mlz_stream_open_batch_device (mlz_stream_set.hip.inc): a set of streams behind one handle.  bases: count + 1 values, stream i's decoded
     // bytes are [bases[i], bases[i + 1]) of the handle ({0, size} for a handle of one stream); d_bases: the same where kernels can read them
     // (device memory the handle owns, uploaded by the first call that needs them).  A set searches without inline tables and takes no sidecar.

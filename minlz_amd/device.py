@@ -336,32 +336,60 @@ class DeviceStream:
         selected record and 0 for one that is context only (uint8); those records' bytes back to back (uint8) and the k + 1 places where
         they start in it and its size (int64) — tensors on the stream's device.
         count_only (grep -c): -> (R, the selected records) and nothing is written or read."""
-        dev, st = self.dev, _stream(self.dev)
         R, totals, numbers, kinds = self._grep_numbers(patterns, 0 if count_only else max_records, invert=invert, before=before, after=after, ignore_crc=ignore_crc,
                                                        no_tables=no_tables, ignore_case=ignore_case)
+        return self._grep_lines(R, totals, numbers, kinds, count_only, ignore_crc)
+
+    def _grep_lines(self, R, totals, numbers, kinds, count_only, ignore_crc):
+        """grep's second half: what _grep_numbers or _grep_regex_numbers found -> what grep returns (the records' bytes by read_records)."""
         if count_only:
             return totals[0], totals[1]
-        k = numbers.numel()
+        dev, k = self.dev, numbers.numel()
         starts = torch.zeros(k + 1, dtype=torch.int64, device=dev)
         data = torch.empty(max(totals[2], 1), dtype=torch.uint8, device=dev)
-        got = self.reader.read_records(numbers.data_ptr(), k, data.data_ptr(), totals[2], d_starts=starts.data_ptr(), ignore_crc=ignore_crc, stream=st) if k else 0
+        got = self.reader.read_records(numbers.data_ptr(), k, data.data_ptr(), totals[2], d_starts=starts.data_ptr(), ignore_crc=ignore_crc, stream=_stream(dev)) if k else 0
         return R, numbers, kinds, data[:got], starts
 
     def _grep_numbers(self, patterns, max_records, **kw):
         """grep's first half -> (R, the call's totals, the smallest min(R, max_records) record numbers, their kinds); builds the index for b"\n"
         when the stream has none."""
-        dev, st = self.dev, _stream(self.dev)
         pats = [patterns] if isinstance(patterns, (bytes, bytearray)) else list(patterns)
+        return self._grep_call(lambda d_numbers, d_kinds, cap, st: self.reader.grep_records(pats, d_numbers, d_kinds, cap, stream=st, **kw), max_records, kw.get("ignore_crc", False))
+
+    def _grep_call(self, call, max_records, ignore_crc):
+        """The index for b"\n" when the stream has none, room for min(max_records, N) numbers and kinds, call(d_numbers, d_kinds, cap, stream) ->
+        (R, the call's totals, the numbers, the kinds)."""
+        dev, st = self.dev, _stream(self.dev)
         try:
             self.reader.record_count()
         except api.MinLZError:   # (no index yet)
-            self.reader.index_records(b"\n", ignore_crc=kw.get("ignore_crc", False), stream=st)
+            self.reader.index_records(b"\n", ignore_crc=ignore_crc, stream=st)
         cap = min(max_records, self.reader.record_count())
         numbers, d_numbers = _room(cap, torch.int64, dev)
         kinds, d_kinds = _room(cap, torch.uint8, dev)
-        R, totals, _ = self.reader.grep_records(pats, d_numbers, d_kinds, cap, stream=st, **kw)
+        R, totals, _ = call(d_numbers, d_kinds, cap, st)
         k = min(R, cap)
         return R, totals, numbers[:k], kinds[:k]
+
+    def _grep_regex_numbers(self, exprs, max_records, ignore_case=False, ignore_crc=False, **kw):
+        """_grep_numbers for regular expressions (a bytes object, a sequence of them, or an api.Regex, which stays the caller's)."""
+        regex = exprs if isinstance(exprs, api.Regex) else api.Regex(exprs, ignore_case=ignore_case)
+        try:
+            return self._grep_call(lambda d_numbers, d_kinds, cap, st: self.reader.grep_regex(regex, d_numbers, d_kinds, cap, ignore_crc=ignore_crc, stream=st, **kw), max_records, ignore_crc)
+        finally:
+            if regex is not exprs:
+                regex.close()
+
+    def grep_regex(self, exprs, invert=False, before=0, after=0, max_records=1 << 20, count_only=False, ignore_crc=False, ignore_case=False):
+        """grep -E over the decoded stream's lines: grep() with the selected records decided by regular expressions over bytes — `exprs` is a
+        bytes object, a sequence of up to 256 of them (a record is selected when it holds a match of any) or a compiled api.Regex (whose own
+        ignore_case then holds); the syntax is the subset of Python's `re` that include/minlz_hip_regex.h lists, ^ and $ are a record's start
+        and end, and an empty line is selected exactly when the expression matches the empty string (b"^$").  Every chunk is decoded once: no
+        search table prunes for an expression.  Lines longer than api.REGEX_MAX_RECORD raise ErrUnsupported.
+        -> what grep returns: (R, numbers, kinds, data, starts), or with count_only (R, the selected records)."""
+        R, totals, numbers, kinds = self._grep_regex_numbers(exprs, 0 if count_only else max_records, ignore_case=ignore_case, ignore_crc=ignore_crc, invert=invert, before=before,
+                                                             after=after)
+        return self._grep_lines(R, totals, numbers, kinds, count_only, ignore_crc)
 
     def read_record_range(self, first, count, ignore_crc=False):
         """Records first .. first + count - 1 as they lie in the decoded stream, the delimiters between them included -> a new uint8 tensor."""
@@ -404,7 +432,7 @@ class DeviceStream:
 
 class DeviceStreamSet(DeviceStream):
     """Many .mz streams on the device opened as ONE DeviceStream (HipTensorCodec.open_streams): its decoded bytes are the streams' decoded
-    bytes one behind the other, and read_ranges, search, search_many, search_records, index_records, read_records, line_numbers and grep
+    bytes one behind the other, and read_ranges, search, search_many, search_records, index_records, read_records, line_numbers, grep and grep_regex
     work on that concatenation — a range, an occurrence or a record may cross from one stream into the next.  The calls here turn positions
     and record numbers back into (stream, position or record inside the stream), on the device.  No search tables and no sidecar.
     .sizes: every stream's decoded size (0 for a failed one); .errors: {index: negative code} of the streams left out for a framing error;
@@ -476,6 +504,13 @@ class DeviceStreamSet(DeviceStream):
         device, in the set's order.  grep followed by locate_records; nothing per record visits the host."""
         _, _, numbers, kinds = self._grep_numbers(patterns, max_records, invert=invert, before=before, after=after, ignore_crc=ignore_crc, no_tables=no_tables,
                                                   ignore_case=ignore_case)
+        which, line = self.locate_records(numbers)
+        return which, line, kinds
+
+    def grep_streams_regex(self, exprs, invert=False, before=0, after=0, max_records=1 << 20, ignore_crc=False, ignore_case=False):
+        """grep -E -H -n over the set: grep_streams with the selected records decided by regular expressions (exprs as in grep_regex)
+        -> (which, line_in_stream, kind).  grep_regex's first half followed by locate_records."""
+        _, _, numbers, kinds = self._grep_regex_numbers(exprs, max_records, ignore_case=ignore_case, ignore_crc=ignore_crc, invert=invert, before=before, after=after)
         which, line = self.locate_records(numbers)
         return which, line, kinds
 
