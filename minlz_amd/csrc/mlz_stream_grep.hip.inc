@@ -2,16 +2,16 @@
 // context records, record numbers out (included at the end of mlz_hip.hip, behind the record index, whose table it reads, and the search for
 // many patterns, whose plan, decode and walk it runs).  The rules are those of mlz_stream_grep.h, which the host check runs as plain loops.
 //
-//   mark      the search phase of mlz_dev_reader_search_many, unchanged (dev_reader_search_plan, search_decode_plan / ready / run), with
-//             search_many_kernel<kSearchManyMarkRecords> on every group: one pass, a verified pair sets the bit of its position's record in a
-//             bitmap of N bits in the workspace.  No count pass, no prefix, no position list.
+//   mark      the search phase of mlz_dev_reader_search_many (SearchManyScan, dev_reader_search_plan, search_decode_plan / ready / run) with
+//             SearchManyScan::mark_records on every group: one pass of search_many_kernel<kSearchManyMarkRecords>, a verified pair sets the
+//             bit of its position's record in a bitmap of N bits in the workspace.  No count pass, no prefix, no position list.
 //   select    grep_select_kernel (one workgroup, a slab of words per lane, as rindex_scan_kernel and records_number_kernel run): the
 //             complement under MLZ_GREP_INVERT, the forward and the backward scan of the nearest selected record, a word's context bits from
 //             the two, the popcounts' exclusive prefix; R and |S|.
 //   compact   grep_compact_kernel, a lane per word: numbers and kinds of the ranks below rec_cap, and end - start of every record (two
 //             loads of D) summed into the bytes written and the bytes of all R records: two 64-bit atomics per workgroup.
 // 32 bytes come home, behind the decode's verdicts; the caller's arrays are written by the compact kernel alone, which runs behind them.
-// No kernel waits for another workgroup.
+// No kernel waits for another workgroup.  The regex grep (mlz_stream_regex.hip.inc) shares grep_enter, GrepWork and grep_select_compact.
 
 #include "mlz_stream_grep.h"
 
@@ -80,8 +80,41 @@ __global__ __launch_bounds__(kGrepCompactThreads) void grep_compact_kernel(const
 namespace {
 
 struct GrepOut { uint64_t* d_rec_no; uint8_t* d_rec_kind; uint64_t rec_cap; };
-// A grep's regions of the workspace: the totals (zeroed) | the marked words, then S | C | the backward scan | ranks, W words each
-struct GrepWork { mlz::GrepTotals* tot; uint32_t *sel, *ctx, *above, *rank; };
+
+// What both greps run under the context's lock, in front of their bodies: the index is there and small enough, the call's own checks pass
+// (call_ok()), the device, the outputs lie on it, the decode call begun; *out = the outputs as the kernels take them.  Returns 0 or the call's error.
+template <class Ok>
+int grep_enter(mlz_dev_reader* rd, Ok call_ok, uint64_t* d_rec_no, uint8_t* d_rec_kind, size_t rec_cap, GrepOut* out) {
+    mlz_ctx* c = rd->ctx;
+    if (!rd->index_ready || rd->index_n >= mlz::kGrepMaxRecords || !call_ok()) return -MLZ_ERR_ARG;
+    if (enter_device(c)) return -MLZ_ERR_HIP;
+    if (rec_cap && (!on_device(c, d_rec_no) || (d_rec_kind && !on_device(c, d_rec_kind)))) return -MLZ_ERR_ARG;
+    begin_decode_call(c);
+    *out = GrepOut{rec_cap ? d_rec_no : nullptr, rec_cap ? d_rec_kind : nullptr, uint64_t(rec_cap)};
+    return 0;
+}
+
+void grep_zero_totals(uint64_t* totals) { if (totals) totals[0] = totals[1] = totals[2] = totals[3] = 0; }
+
+// A grep's regions of the workspace (c->d_rplan): the totals | the marked words, then S | C | the backward scan | ranks, W words each.
+// take: from the caller's carve; clear, behind the caller's ensure: the regions as pointers, the totals and the marks zeroed.
+struct GrepWork {
+    mlz::GrepTotals* tot = nullptr;
+    uint32_t *sel = nullptr, *ctx = nullptr, *above = nullptr, *rank = nullptr;
+    void take(Carve* cv, uint64_t words) {
+        W = size_t(words); r_tot = cv->take<mlz::GrepTotals>(1);
+        for (Region<uint32_t>& r : r_words) r = cv->take<uint32_t>(W);
+    }
+    int clear(mlz_ctx* c, hipStream_t sm) {
+        void* ws = c->d_rplan.p;
+        tot = r_tot.at(ws); sel = r_words[0].at(ws); ctx = r_words[1].at(ws); above = r_words[2].at(ws); rank = r_words[3].at(ws);
+        HIPCHK(c, hipMemsetAsync(tot, 0, sizeof(mlz::GrepTotals), sm));
+        HIPCHK(c, hipMemsetAsync(sel, 0, W * 4, sm));
+        return 0;
+    }
+private:
+    size_t W = 0; Region<mlz::GrepTotals> r_tot{}; Region<uint32_t> r_words[4]{};
+};
 
 // What every grep runs behind its mark phase, whose bits are in w.sel: select and compact, the totals home and their check against the index.
 // Returns R; `call` names the entry point in an error's text.
@@ -109,32 +142,27 @@ int64_t dev_reader_grep_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flag
                                const GrepOut& out, uint64_t* totals, uint64_t* stats) {
     mlz_ctx* c = rd->ctx;
     const size_t nck = rd->chunks.size();
-    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0, fold = (flags & MLZ_SEARCH_IGNORE_CASE) != 0;
-    std::vector<uint8_t> keep;
-    patterns = search_many_folded(flags, patterns, pattern_len, n, &keep);
     search_begin(rd, stats);
-    if (totals) totals[0] = totals[1] = totals[2] = totals[3] = 0;
+    grep_zero_totals(totals);
     HIPCHK(c, hipSetDevice(c->device));
-    const uint64_t N = rd->index_n, W = mlz::grep_words(N);
+    const uint64_t N = rd->index_n;
     if (N == 0) return 0;
-    // the search phase's plan: as dev_reader_search_many_locked
-    mlz::SearchManyIndex index;
+    SearchManyScan scan;
+    scan.prepare(flags, patterns, pattern_len, n);
     std::vector<uint8_t> take(nck, 0);
     size_t n_take = 0;
     if (n && nck) {
-        mlz::search_many_index(patterns, pattern_len, n, &index);
-        const int64_t pr = dev_reader_search_plan(rd, sm, flags, patterns, index.off, n, &take, &n_take, stats, true);
+        const int64_t pr = dev_reader_search_plan(rd, sm, flags, scan.patterns, scan.index.off, n, &take, &n_take, stats, true);
         if (pr) return pr;
     }
-    Carve cv, pin;   // workspace: totals | marks, then S | C | the backward scan | ranks | the index | the decode's; pinned: the index | the decode's
-    const auto r_tot = cv.take<mlz::GrepTotals>(1);
-    const auto r_sel = cv.take<uint32_t>(size_t(W)), r_ctx = cv.take<uint32_t>(size_t(W)), r_above = cv.take<uint32_t>(size_t(W)), r_rank = cv.take<uint32_t>(size_t(W));
+    Carve cv, pin;   // workspace: the grep's (totals | marks, then S | C | the backward scan | ranks) | the index | the decode's; pinned: the index | the decode's
+    GrepWork w;
+    w.take(&cv, mlz::grep_words(N));
     SearchDecode sd;
-    SearchManyUpload up;
     if (n_take) {
-        search_decode_plan(rd->chunks, take, n_take, index.lmin, index.lmax, mlz::kSearchManyTile, &sd);
+        search_decode_plan(rd->chunks, take, n_take, scan.index.lmin, scan.index.lmax, mlz::kSearchManyTile, &sd);
         if (sd.lay.tiles.size() > 0x7fffffffu) return -MLZ_ERR_ARG;
-        up.take(index, n, &cv, &pin);   // the pattern index, as the search for many lays it out
+        scan.take(&cv, &pin, nullptr);   // (nothing is counted)
         const int e = search_decode_ready(rd->ctx, rd->chunks, &sd, &cv, &pin);
         if (e) return e;
     } else {
@@ -142,48 +170,32 @@ int64_t dev_reader_grep_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flag
         const int e = ensure_stream_objects(c, 0, 64);
         if (e) return e;
     }
-    void* ws = c->d_rplan.p;
-    mlz::GrepTotals* d_tot = r_tot.at(ws);
-    uint32_t *d_sel = r_sel.at(ws), *d_ctx = r_ctx.at(ws), *d_above = r_above.at(ws), *d_rank = r_rank.at(ws);
-    const uint64_t* D = static_cast<const uint64_t*>(rd->d_index);
     { WorkspaceOrder order(c, sm); }
-    HIPCHK(c, hipMemsetAsync(d_tot, 0, sizeof(mlz::GrepTotals), sm));
-    HIPCHK(c, hipMemsetAsync(d_sel, 0, size_t(W) * 4, sm));
+    int e = w.clear(c, sm);
+    if (e) return e;
     if (n_take) {
-        const mlz::SearchTile* d_tiles = sd.tiles.at(ws);
-        const mlz::SearchManyMark mk{D, rd->index_k, d_sel, nullptr, 0};
-        const int e = up.send(c, sm, index, patterns, n);
-        if (e) return e;
-        const int64_t r = search_decode_run(rd->ctx, rd->d_src, rd->chunks, sm, ignore_crc, &sd, [&](size_t, size_t t0, size_t t1) {
-            hipLaunchKernelGGL(search_many_kernel_of<mlz::kSearchManyMarkRecords>(fold), dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), up.lds_bytes, sm, c->d_range.as<uint8_t>(), d_tiles,
-                               uint32_t(t0), up.ix, static_cast<uint32_t*>(nullptr), static_cast<unsigned long long*>(nullptr), static_cast<const uint64_t*>(nullptr), uint64_t(0),
-                               static_cast<uint64_t*>(nullptr), static_cast<uint32_t*>(nullptr), mk);
+        if ((e = scan.send(c, sm, sd.tiles.at(c->d_rplan.p)))) return e;
+        const uint64_t* D = static_cast<const uint64_t*>(rd->d_index);
+        const int64_t r = search_decode_run(rd->ctx, rd->d_src, rd->chunks, sm, (flags & MLZ_STREAM_IGNORE_CRC) != 0, &sd, [&](size_t, size_t t0, size_t t1) {
+            scan.mark_records(t0, t1, D, rd->index_k, w.sel);
             return 0;
         });
         if (r < 0) return r;   // (nothing has been written to the caller's arrays)
     }
-    return grep_select_compact(rd, sm, "mlz_dev_reader_grep_records", (flags & MLZ_GREP_INVERT) != 0, before, after, out, GrepWork{d_tot, d_sel, d_ctx, d_above, d_rank}, totals);
+    return grep_select_compact(rd, sm, "mlz_dev_reader_grep_records", (flags & MLZ_GREP_INVERT) != 0, before, after, out, w, totals);
 }
 
 }  // namespace
 
 extern "C" int64_t mlz_dev_reader_grep_records(mlz_dev_reader* rd, void* stream, uint32_t flags, const uint8_t* patterns, const uint32_t* pattern_len, size_t n_patterns, uint64_t before,
                                                uint64_t after, uint64_t* d_rec_no, uint8_t* d_rec_kind, size_t rec_cap, uint64_t* totals, uint64_t* stats) {
-    if (!rd || n_patterns > MLZ_SEARCH_MAX_PATTERNS || (n_patterns && (!patterns || !pattern_len)) || (rec_cap && !d_rec_no)) return -MLZ_ERR_ARG;
-    size_t blob = 0;
-    for (size_t i = 0; i < n_patterns; i++) {
-        if (pattern_len[i] == 0 || pattern_len[i] > mlz::kSearchMaxPattern) return -MLZ_ERR_ARG;
-        blob += pattern_len[i];
-    }
-    mlz_ctx* c = rd->ctx;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (!rd->index_ready || rd->index_n >= mlz::kGrepMaxRecords) return -MLZ_ERR_ARG;
-    if (blob && std::memchr(patterns, rd->index_delim, blob)) return -MLZ_ERR_ARG;   // a line search cannot match across lines
-    if ((flags & MLZ_SEARCH_IGNORE_CASE) && mlz::search_is_letter(rd->index_delim)) return -MLZ_ERR_ARG;   // records are split at the delimiter's own byte, which is never folded
-    if (enter_device(c)) return -MLZ_ERR_HIP;
-    if (rec_cap && (!on_device(c, d_rec_no) || (d_rec_kind && !on_device(c, d_rec_kind)))) return -MLZ_ERR_ARG;
-    begin_decode_call(c);
+    const int64_t blob = rd ? search_pattern_list(patterns, pattern_len, n_patterns) : -1;
+    if (blob < 0 || (rec_cap && !d_rec_no)) return -MLZ_ERR_ARG;
+    std::lock_guard<std::mutex> lk(rd->ctx->mu);
+    // a line search cannot match across lines; records are split at the delimiter's own byte, which is never folded
+    auto pattern_ok = [&] { return !(blob && std::memchr(patterns, rd->index_delim, size_t(blob))) && !((flags & MLZ_SEARCH_IGNORE_CASE) && mlz::search_is_letter(rd->index_delim)); };
+    GrepOut out;
+    if (const int e = grep_enter(rd, pattern_ok, d_rec_no, d_rec_kind, rec_cap, &out)) return e;
     hipStream_t sm = static_cast<hipStream_t>(stream);
-    const GrepOut out{rec_cap ? d_rec_no : nullptr, rec_cap ? d_rec_kind : nullptr, uint64_t(rec_cap)};
     return settled(sm, dev_reader_grep_locked(rd, sm, flags, patterns, pattern_len, n_patterns, before, after, out, totals, stats));
 }

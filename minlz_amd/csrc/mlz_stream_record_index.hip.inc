@@ -4,7 +4,7 @@
 // host check runs as plain loops.
 //
 // Build (mlz_dev_reader_index_records): the handle's data chunks with bytes are decoded group by group (about 64 MiB, range_group_ends) into
-// the ReadSeeker's scratch, side by side from scratch[0] on (ScratchDecode, mlz_stream_walk.hip.inc; stored chunks are copied there).  Per group:
+// the ReadSeeker's scratch, side by side from scratch[0] on (scratch_decode_whole, ScratchDecode, mlz_stream_walk.hip.inc; stored chunks are copied there).  Per group:
 //   count   rindex_count_kernel: a workgroup per 64 KiB tile, a 16-byte load per lane and step, the popcounts reduced to one word per tile;
 //   scan    rindex_scan_kernel (one workgroup): the tiles' exclusive bases and the group's total, which comes home (8 bytes); the host adds
 //           it to the running base and grows the table to fit (exactly with one group, else geometrically with a device-to-device copy);
@@ -141,27 +141,13 @@ int64_t dev_reader_index_records_locked(mlz_dev_reader* rd, hipStream_t sm, bool
     mlz_ctx* c = rd->ctx;
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t size = uint64_t(rd->size);
-    ScratchDecode dec;   // the data chunks with bytes; a group's chunks side by side from scratch[0] on
-    const std::vector<size_t> dc = mlz::chunks_with_bytes(rd->chunks.size(), [&](size_t k) { return rd->chunks[k].n; });
-    const size_t nd = dc.size();
-    mlz::range_group_ends(nd, [&](size_t i) { return uint64_t(rd->chunks[dc[i]].n); }, &dec.gend);
-    const size_t ng = dec.gend.size();
-    dec.jobs.resize(nd); dec.at.resize(nd);
-    std::vector<uint64_t> gbytes(ng), gfirst(ng);
-    for (size_t g = 0, i = 0; g < ng; g++) {
-        uint64_t o = 0;
-        gfirst[g] = uint64_t(rd->chunks[dc[i]].out_off);
-        for (; i < dec.gend[g]; i++) {
-            const StreamChunk& ck = rd->chunks[dc[i]];
-            if (uint64_t(ck.out_off) != gfirst[g] + o) { c->err = "mlz_dev_reader_index_records: the chunks' output offsets are not contiguous"; return -MLZ_ERR_HIP; }
-            dec.jobs[i] = ChunkJob{dc[i], nullptr}; dec.at[i] = o;
-            o += ck.n;
-        }
-        gbytes[g] = o;
-    }
-    Carve cv, pin;   // workspace: the group's total | tile counts | tile bases; pinned: the decode's | the total
-    int e = dec.take(c, rd->chunks, &pin);
+    ScratchDecode dec;
+    mlz::WholeStreamList groups;
+    int e = scratch_decode_whole(c, "mlz_dev_reader_index_records", rd->chunks, size, &dec, &groups);
     if (e) return e;
+    const size_t nd = dec.jobs.size(), ng = dec.gend.size();
+    Carve cv, pin;   // workspace: the group's total | tile counts | tile bases; pinned: the decode's | the total
+    if ((e = dec.take(c, rd->chunks, &pin))) return e;
     const uint64_t tiles_max = mlz::rindex_tiles(15, dec.sp.scratch_max);
     const auto r_total = cv.take<uint64_t>(2);
     const auto r_count = cv.take<uint32_t>(size_t(tiles_max)), r_base = cv.take<uint32_t>(size_t(tiles_max));
@@ -177,7 +163,7 @@ int64_t dev_reader_index_records_locked(mlz_dev_reader* rd, hipStream_t sm, bool
     uint64_t k = 0;
     // a group's bytes are in the scratch: count, scan, the total home, room in the table, emit
     auto index_group = [&](size_t g) -> int {
-        const uint64_t n = gbytes[g], ntiles = mlz::rindex_tiles(reinterpret_cast<uintptr_t>(scratch) & 15, n);
+        const uint64_t n = groups.bytes[g], ntiles = mlz::rindex_tiles(reinterpret_cast<uintptr_t>(scratch) & 15, n);
         if (ntiles == 0 || ntiles > tiles_max) { c->err = "mlz_dev_reader_index_records: a group's tiles do not fit the workspace"; return -MLZ_ERR_HIP; }
         hipLaunchKernelGGL(mlz::rindex_count_kernel, dim3(uint32_t(ntiles)), dim3(mlz::kRindexThreads), 0, sm, scratch, n, delim, d_count);
         hipLaunchKernelGGL(mlz::rindex_scan_kernel, dim3(1), dim3(mlz::kRecordsScanThreads), 0, sm, d_count, ntiles, d_base, d_total);
@@ -197,7 +183,7 @@ int64_t dev_reader_index_records_locked(mlz_dev_reader* rd, hipStream_t sm, bool
             if (tab.p) (void)hipFree(tab.p);
             tab.p = fresh; tab.cap = want;
         }
-        hipLaunchKernelGGL(mlz::rindex_emit_kernel, dim3(uint32_t(ntiles)), dim3(mlz::kRindexThreads), 0, sm, scratch, n, delim, d_base, gfirst[g], total, tab.p + k);
+        hipLaunchKernelGGL(mlz::rindex_emit_kernel, dim3(uint32_t(ntiles)), dim3(mlz::kRindexThreads), 0, sm, scratch, n, delim, d_base, groups.first[g], total, tab.p + k);
         k += total;
         return 0;
     };

@@ -7,13 +7,13 @@
 //             An index with a record beyond MLZ_REGEX_MAX_RECORD is refused here, before any chunk is decoded.
 //   bounds    regex_bounds_kernel, a lane per decode group: the group's first and last record (two bisections), 16 bytes per group home: they size
 //             the mark launches.
-//   mark      every data chunk with bytes is decoded once, group by group into the scratch, as the index build does it (ScratchDecode).  Per group
+//   mark      every data chunk with bytes is decoded once, group by group into the scratch (scratch_decode_whole, the index build's list; its groups are the RegexGroups).  Per group
 //             regex_mark_kernel: class map and table into LDS by 16-byte loads; a lane per record walks its bytes in 16-byte aligned blocks of the
 //             scratch, a step being one add and one 16-bit LDS read (the class of each of a block's bytes is read in front of the chain); a lane
 //             leaves its loop at dead or matched, a wavefront when no lane is left; the verdicts' ballot goes out as two words ORed into the
 //             bitmap by lanes 0 and 32, and the one lane that runs into the group's end writes the carry.  A workgroup takes slices of 256
 //             records in turn, so a large group loads the table kRegexMaxGrid times at the most.
-//   select, compact   grep_select_compact (mlz_stream_grep.hip.inc).
+//   select, compact   grep_select_compact (mlz_stream_grep.hip.inc, as are grep_enter and GrepWork).
 // No kernel waits for another workgroup; the bitmap takes no atomics.  The table is looked up through the class map; a table indexed by the byte
 // itself (S * 256 entries) was not built, so there is no measurement of it against this one.
 
@@ -91,60 +91,39 @@ int64_t dev_reader_grep_regex_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_
     mlz_ctx* c = rd->ctx;
     const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0;
     search_begin(rd, stats);
-    if (totals) totals[0] = totals[1] = totals[2] = totals[3] = 0;
+    grep_zero_totals(totals);
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t N = rd->index_n, W = mlz::grep_words(N), size = uint64_t(rd->size);
     if (N == 0) return 0;
-    // the decode: as dev_reader_index_records_locked forms it
     ScratchDecode dec;
-    const std::vector<size_t> dc = mlz::chunks_with_bytes(rd->chunks.size(), [&](size_t i) { return rd->chunks[i].n; });
-    const size_t nd = dc.size();
-    mlz::range_group_ends(nd, [&](size_t i) { return uint64_t(rd->chunks[dc[i]].n); }, &dec.gend);
-    const size_t ng = dec.gend.size();
-    dec.jobs.resize(nd); dec.at.resize(nd);
+    mlz::WholeStreamList whole;
+    int e = scratch_decode_whole(c, "mlz_dev_reader_grep_regex", rd->chunks, size, &dec, &whole);
+    if (e) return e;
+    const size_t nd = dec.jobs.size(), ng = dec.gend.size();
     std::vector<mlz::RegexGroup> groups(ng);
-    for (size_t g = 0, i = 0; g < ng; g++) {
-        uint64_t o = 0;
-        groups[g].first = uint64_t(rd->chunks[dc[i]].out_off);
-        for (; i < dec.gend[g]; i++) {
-            const StreamChunk& ck = rd->chunks[dc[i]];
-            if (uint64_t(ck.out_off) != groups[g].first + o) { c->err = "mlz_dev_reader_grep_regex: the chunks' output offsets are not contiguous"; return -MLZ_ERR_HIP; }
-            dec.jobs[i] = ChunkJob{dc[i], nullptr}; dec.at[i] = o;
-            o += ck.n;
-        }
-        groups[g].n = o;
-        if (o == 0 || groups[g].first + o > size || (g && groups[g].first != groups[g - 1].first + groups[g - 1].n)) {
-            c->err = "mlz_dev_reader_grep_regex: the groups do not tile the stream";
-            return -MLZ_ERR_HIP;
-        }
-    }
-    if (ng == 0 || groups[0].first != 0 || groups[ng - 1].first + groups[ng - 1].n != size) { c->err = "mlz_dev_reader_grep_regex: the groups do not tile the stream"; return -MLZ_ERR_HIP; }
+    for (size_t g = 0; g < ng; g++) { groups[g].first = whole.first[g]; groups[g].n = whole.bytes[g]; }
     const uint32_t image_bytes = pr.image_bytes();
-    Carve cv, pin;   // workspace: totals | marks, then S | C | the backward scan | ranks | longest, bounds | groups | carry slots | image; pinned: the decode's | the same four
-    const auto r_tot = cv.take<mlz::GrepTotals>(1);
-    const auto r_sel = cv.take<uint32_t>(size_t(W)), r_ctx = cv.take<uint32_t>(size_t(W)), r_above = cv.take<uint32_t>(size_t(W)), r_rank = cv.take<uint32_t>(size_t(W));
+    Carve cv, pin;   // workspace: the grep's (totals | marks, then S | C | the backward scan | ranks) | longest, bounds | groups | carry slots | image; pinned: the decode's | the same four
+    GrepWork w;
+    w.take(&cv, W);
     const auto r_home = cv.take<uint64_t>(2 + 2 * ng);   // the longest record (and a pad) | the bounds: what comes home in front of the decode
     const auto r_groups = cv.take<mlz::RegexGroup>(ng);
     const auto r_carry = cv.take<mlz::RegexCarry>(2);
     const auto r_image = cv.take<uint8_t>(image_bytes);
-    int e = dec.take(c, rd->chunks, &pin);
-    if (e) return e;
+    if ((e = dec.take(c, rd->chunks, &pin))) return e;
     const auto h_home_r = pin.take<uint64_t>(2 + 2 * ng);
     const auto h_groups_r = pin.take<mlz::RegexGroup>(ng);
     const auto h_image_r = pin.take<uint8_t>(image_bytes);
     HIPCHK(c, c->d_rplan.ensure(cv.bytes));
     if ((e = ensure_stream_objects(c, 0, pin.bytes))) return e;
     void* ws = c->d_rplan.p;
-    mlz::GrepTotals* d_tot = r_tot.at(ws);
-    uint32_t *d_sel = r_sel.at(ws), *d_ctx = r_ctx.at(ws), *d_above = r_above.at(ws), *d_rank = r_rank.at(ws);
     uint64_t *d_home = r_home.at(ws), *h_home = h_home_r.at(c->pinned2);
     mlz::RegexGroup *d_groups = r_groups.at(ws), *h_groups = h_groups_r.at(c->pinned2);
     mlz::RegexCarry* d_carry = r_carry.at(ws);
     uint8_t *d_image = r_image.at(ws), *h_image = h_image_r.at(c->pinned2);
     const uint64_t* D = static_cast<const uint64_t*>(rd->d_index);
     { WorkspaceOrder order(c, sm); }
-    HIPCHK(c, hipMemsetAsync(d_tot, 0, sizeof(mlz::GrepTotals), sm));
-    HIPCHK(c, hipMemsetAsync(d_sel, 0, size_t(W) * 4, sm));
+    if ((e = w.clear(c, sm))) return e;
     HIPCHK(c, hipMemsetAsync(d_home, 0, 2 * sizeof(uint64_t), sm));
     HIPCHK(c, hipMemsetAsync(d_carry, 0xff, 2 * sizeof(mlz::RegexCarry), sm));   // (no record has that number)
     std::memcpy(h_groups, groups.data(), ng * sizeof(mlz::RegexGroup));
@@ -178,11 +157,11 @@ int64_t dev_reader_grep_regex_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_
         const uint32_t grid = uint32_t(std::min<uint64_t>(mlz::regex_slices(bounds[g]), mlz::kRegexMaxGrid));
         hipLaunchKernelGGL(mlz::regex_mark_kernel, dim3(grid), dim3(mlz::kRegexThreads), image_bytes, sm, scratch, groups[g], size, D, rd->index_k, bounds[g],
                            reinterpret_cast<const uint4*>(d_image), image_bytes, pr.C, pr.start, pr.end_hi, static_cast<const mlz::RegexCarry*>(d_carry + (g & 1)), d_carry + ((g + 1) & 1),
-                           d_sel, W);
+                           w.sel, W);
         return 0;
     });
     if (r < 0) return r;   // (nothing has been written to the caller's arrays)
-    return grep_select_compact(rd, sm, "mlz_dev_reader_grep_regex", (flags & MLZ_GREP_INVERT) != 0, before, after, out, GrepWork{d_tot, d_sel, d_ctx, d_above, d_rank}, totals);
+    return grep_select_compact(rd, sm, "mlz_dev_reader_grep_regex", (flags & MLZ_GREP_INVERT) != 0, before, after, out, w, totals);
 }
 
 }  // namespace
@@ -216,14 +195,10 @@ int mlz_regex_test(const mlz_regex* re, const uint8_t* record, size_t len) {
 int64_t mlz_dev_reader_grep_regex(mlz_dev_reader* rd, void* stream, uint32_t flags, const mlz_regex* re, uint64_t before, uint64_t after, uint64_t* d_rec_no, uint8_t* d_rec_kind,
                                   size_t rec_cap, uint64_t* totals, uint64_t* stats) {
     if (!rd || !re || (flags & ~uint32_t(MLZ_STREAM_IGNORE_CRC | MLZ_GREP_INVERT)) || (rec_cap && !d_rec_no)) return -MLZ_ERR_ARG;
-    mlz_ctx* c = rd->ctx;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (!rd->index_ready || rd->index_n >= mlz::kGrepMaxRecords) return -MLZ_ERR_ARG;
-    if (enter_device(c)) return -MLZ_ERR_HIP;
-    if (rec_cap && (!on_device(c, d_rec_no) || (d_rec_kind && !on_device(c, d_rec_kind)))) return -MLZ_ERR_ARG;
-    begin_decode_call(c);
+    std::lock_guard<std::mutex> lk(rd->ctx->mu);
+    GrepOut out;
+    if (const int e = grep_enter(rd, [] { return true; }, d_rec_no, d_rec_kind, rec_cap, &out)) return e;
     hipStream_t sm = static_cast<hipStream_t>(stream);
-    const GrepOut out{rec_cap ? d_rec_no : nullptr, rec_cap ? d_rec_kind : nullptr, uint64_t(rec_cap)};
     return settled(sm, dev_reader_grep_regex_locked(rd, sm, flags, re->prog, before, after, out, totals, stats));
 }
 

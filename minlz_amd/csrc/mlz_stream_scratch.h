@@ -28,6 +28,34 @@ template <class N> std::vector<size_t> chunks_with_bytes(size_t n_chunks, N n_of
     for (size_t k = 0; k < n_chunks; k++) if (n_of(k)) dc.push_back(k);
     return dc;
 }
+// The whole-stream list (the record index build, the regex grep): every chunk with bytes is a job, and a group's chunks lie side by side from
+// scratch[0] on.  dc: chunks_with_bytes; gend: the groups of that list; n_of(k), off_of(k): chunk k's decoded bytes and where they lie in the
+// decoded stream; size: the stream's decoded bytes.  -> at[i]: job i's place in the scratch; first[g], bytes[g]: group g's first decoded
+// position and its bytes; status: kWholeOk, or a chunk does not begin where the one in front of it in its group ends, or the groups are
+// not [0, size) cut into non-empty pieces in order (no group and size == 0 are).  The arrays are complete under kWholeOk only.
+enum { kWholeOk = 0, kWholeNotContiguous = 1, kWholeNotTiled = 2 };
+struct WholeStreamList { std::vector<uint64_t> at, first, bytes; int status = kWholeOk; };
+template <class N, class Off>
+WholeStreamList whole_stream_list(const std::vector<size_t>& dc, const std::vector<size_t>& gend, N n_of, Off off_of, uint64_t size) {
+    WholeStreamList w;
+    w.at.resize(dc.size()); w.first.resize(gend.size()); w.bytes.resize(gend.size());
+    uint64_t pos = 0;   // where the groups in front end: at most size
+    for (size_t g = 0, i = 0; g < gend.size(); g++) {
+        const size_t end = std::min(gend[g], dc.size());
+        const uint64_t first = i < end ? uint64_t(off_of(dc[i])) : pos;
+        uint64_t o = 0;
+        for (; i < end; i++) {
+            if (uint64_t(off_of(dc[i])) != first + o) { w.status = kWholeNotContiguous; return w; }
+            w.at[i] = o;
+            o += n_of(dc[i]);
+        }
+        w.first[g] = first; w.bytes[g] = o;
+        if (o == 0 || first != pos || o > size - pos) { w.status = kWholeNotTiled; return w; }
+        pos += o;
+    }
+    if (pos != size) w.status = kWholeNotTiled;
+    return w;
+}
 // The copies of a staged list: the stored chunks' pieces (pad 1: the stream is stream_place_kernel's second source), group after group, in
 // job order; group g's are places[place_end[g - 1], place_end[g]); the scratch holds scratch_max bytes, the largest at[i] + n of the list.
 // chunk_of(i): job i's chunk, with the members type (0x01: stored), body_off and n.

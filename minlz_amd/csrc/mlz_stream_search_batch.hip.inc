@@ -4,9 +4,9 @@
 //
 // The batch is laid out as ONE decoded sequence with a one-byte hole behind every stream (mlz_stream_search_batch.h: the virtual positions),
 // so search_layout, the scratch decode and search_many_kernel run as they do for one stream: the chunks of all healthy streams form one job
-// list in descriptor order, decoded group by group into the scratch; per group search_many_kernel<kSearchManyCount> counts, search_prefix_kernel
-// continues the running prefix over ALL tiles, <kSearchManyWrite> writes (virtual position, pattern) below cap and <kSearchManyMarkStreams>
-// sets the presence bits.  search_batch_finish_kernel then gives every stream its count (the prefix at its tiles' ends) and turns every written
+// list in descriptor order, decoded group by group into the scratch; per group SearchManyScan::count_prefix_write counts, continues the running
+// prefix over ALL tiles and writes (virtual position, pattern) below cap, and SearchManyScan::mark_streams sets the presence bits.  The scan is
+// prepared once for the call and takes its regions anew in every pass.  search_batch_finish_kernel then gives every stream its count (the prefix at its tiles' ends) and turns every written
 // virtual position into (stream, position).  A stream whose decode or CRC fails is known only when the job results come back, with its garbage
 // scanned: it is then dropped from the list and the whole scan runs once more over the rest (failures are deterministic: two passes at the most).
 
@@ -49,9 +49,9 @@ struct SearchBatchOut {
 
 // One pass: the streams with alive[i] are decoded and scanned.  rc[i] = 0 or the stream's first failing chunk's error; *total and counts[i]
 // are valid (and the device outputs written) when no stream failed.  *n_jobs: the chunks the pass decoded.
-int64_t stream_search_batch_pass(mlz_ctx* c, hipStream_t sm, bool ignore_crc, bool fold, const uint8_t* d_src, const BatchWalk& bw, size_t n, const std::vector<uint8_t>& alive,
-                                 const mlz::SearchManyIndex& index, const uint8_t* patterns, size_t np, const SearchBatchOut& out, std::vector<int64_t>* rc,
-                                 std::vector<uint64_t>* counts, uint64_t* total, size_t* n_jobs, bool* failed) {
+int64_t stream_search_batch_pass(mlz_ctx* c, hipStream_t sm, bool ignore_crc, const uint8_t* d_src, const BatchWalk& bw, size_t n, const std::vector<uint8_t>& alive,
+                                 SearchManyScan& scan, const SearchBatchOut& out, std::vector<int64_t>* rc, std::vector<uint64_t>* counts, uint64_t* total, size_t* n_jobs,
+                                 bool* failed) {
     // the virtual positions and the one job list: every alive stream's chunks that have bytes, in descriptor order
     std::vector<uint64_t> size(n, 0), vbase(n + 1, 0);
     for (size_t i = 0; i < n; i++) if (alive[i]) size[i] = bw.prefix(i);
@@ -67,7 +67,7 @@ int64_t stream_search_batch_pass(mlz_ctx* c, hipStream_t sm, bool ignore_crc, bo
     }
     job_first[n] = jobs.size();
     *n_jobs = jobs.size();
-    search_decode_layout(bw.chunks, [&](size_t j) { return voff[j]; }, index.lmin, index.lmax, mlz::kSearchManyTile, &sd);
+    search_decode_layout(bw.chunks, [&](size_t j) { return voff[j]; }, scan.index.lmin, scan.index.lmax, mlz::kSearchManyTile, &sd);
     const size_t nt = sd.lay.tiles.size();
     if (nt > 0x7fffffffu) return -MLZ_ERR_ARG;
     std::vector<uint32_t> tile_stream(nt), tile_first(n + 1);
@@ -75,14 +75,9 @@ int64_t stream_search_batch_pass(mlz_ctx* c, hipStream_t sm, bool ignore_crc, bo
         c->err = "stream_search_batch: a tile crosses a stream";
         return -MLZ_ERR_HIP;
     }
-    const size_t words = (np + 31) / 32;
-    Carve cv, pin;   // workspace: pattern counts | total | the index | tile counts | prefix | tile streams | tile firsts | vbase | stream counts | the decode's
-    const auto r_pc = cv.take<unsigned long long>(np);
-    const auto r_total = cv.take<uint64_t>(2);
-    SearchManyUpload up;
-    up.take(index, np, &cv, &pin);
-    const auto r_tc = cv.take<uint32_t>(nt, 4);
-    const auto r_prefix = cv.take<uint64_t>(nt);
+    const size_t words = (scan.n + 31) / 32;
+    Carve cv, pin;   // workspace: the scan's (pattern counts | total | the index | tile counts | prefix) | tile streams | tile firsts | vbase | stream counts | the decode's
+    scan.take(&cv, &pin, &nt);
     // (tile streams | tile firsts | vbase go up as one block; stream counts | total come back as one)
     Carve blk;
     const auto u_ts = blk.take<uint32_t>(nt, 4), u_tf = blk.take<uint32_t>(n + 1, 4);
@@ -93,35 +88,23 @@ int64_t stream_search_batch_pass(mlz_ctx* c, hipStream_t sm, bool ignore_crc, bo
     int e = search_decode_ready(c, bw.chunks, &sd, &cv, &pin);
     if (e) return e;
     void* ws = c->d_rplan.p;
-    unsigned long long* d_pc = r_pc.at(ws);
-    uint64_t *d_total = r_total.at(ws), *d_prefix = r_prefix.at(ws), *d_sc = r_sc.at(ws);
-    uint32_t* d_tc = r_tc.at(ws);
+    uint64_t* d_sc = r_sc.at(ws);
     uint8_t *d_blk = r_blk.at(ws), *hb = h_blk.at(c->pinned2);
     const uint32_t *d_ts = u_ts.at(d_blk), *d_tf = u_tf.at(d_blk);
     const uint64_t* d_vb = u_vb.at(d_blk);
-    const mlz::SearchTile* d_tiles = sd.tiles.at(ws);
+    const uint64_t *d_prefix = scan.prefixes.at(ws), *d_total = scan.total.at(ws);
     if (nt) std::memcpy(u_ts.at(hb), tile_stream.data(), nt * 4);
     std::memcpy(u_tf.at(hb), tile_first.data(), (n + 1) * 4);
     std::memcpy(u_vb.at(hb), vbase.data(), (n + 1) * 8);
     { WorkspaceOrder order(c, sm); }
-    HIPCHK(c, hipMemsetAsync(d_pc, 0, np * sizeof(unsigned long long), sm));
-    HIPCHK(c, hipMemsetAsync(d_total, 0, 16, sm));
+    if ((e = scan.clear(c, sm))) return e;
     if (out.d_present) HIPCHK(c, hipMemsetAsync(out.d_present, 0, n * words * 4, sm));
     HIPCHK(c, hipMemcpyAsync(d_blk, hb, blk.bytes, hipMemcpyHostToDevice, sm));
-    if ((e = up.send(c, sm, index, patterns, np))) return e;
-    const mlz::SearchManyMark mk{nullptr, 0, out.d_present, d_ts, uint32_t(words)};
+    if ((e = scan.send(c, sm, sd.tiles.at(ws)))) return e;
     std::vector<int64_t> job_rc;
     const int64_t r = search_decode_run(c, d_src, bw.chunks, sm, ignore_crc, &sd, [&](size_t, size_t t0, size_t t1) {
-        const uint8_t* scratch = c->d_range.as<uint8_t>();
-        const dim3 grid(uint32_t(t1 - t0)), block(mlz::kSearchManyThreads);
-        hipLaunchKernelGGL(search_many_kernel_of<mlz::kSearchManyCount>(fold), grid, block, up.lds_bytes, sm, scratch, d_tiles, uint32_t(t0), up.ix, d_tc, d_pc,
-                           static_cast<const uint64_t*>(nullptr), uint64_t(0), static_cast<uint64_t*>(nullptr), static_cast<uint32_t*>(nullptr), mlz::SearchManyMark{});
-        hipLaunchKernelGGL(mlz::search_prefix_kernel, dim3(1), dim3(1024), 0, sm, d_tc, uint32_t(t0), uint32_t(t1), d_prefix, d_total);
-        if (out.cap) hipLaunchKernelGGL(search_many_kernel_of<mlz::kSearchManyWrite>(fold), grid, block, up.lds_bytes, sm, scratch, d_tiles, uint32_t(t0), up.ix, d_tc, d_pc,
-                                        static_cast<const uint64_t*>(d_prefix), out.cap, out.d_hit_pos, out.d_hit_which, mlz::SearchManyMark{});
-        if (out.d_present) hipLaunchKernelGGL(search_many_kernel_of<mlz::kSearchManyMarkStreams>(fold), grid, block, up.lds_bytes, sm, scratch, d_tiles, uint32_t(t0), up.ix,
-                                              static_cast<uint32_t*>(nullptr), static_cast<unsigned long long*>(nullptr), static_cast<const uint64_t*>(nullptr), uint64_t(0),
-                                              static_cast<uint64_t*>(nullptr), static_cast<uint32_t*>(nullptr), mk);
+        scan.count_prefix_write(t0, t1, out.cap, out.d_hit_pos, out.d_hit_which);
+        if (out.d_present) scan.mark_streams(t0, t1, d_ts, out.d_present, uint32_t(words));
         return 0;
     }, &job_rc);
     if (r < 0) return r;
@@ -139,7 +122,7 @@ int64_t stream_search_batch_pass(mlz_ctx* c, hipStream_t sm, bool ignore_crc, bo
     const uint64_t lanes = std::max<uint64_t>(n, out.cap);
     hipLaunchKernelGGL(mlz::search_batch_finish_kernel, dim3(uint32_t(std::min<uint64_t>((lanes + 255) / 256, 4096))), dim3(256), 0, sm, d_prefix, d_total, uint32_t(nt), d_tf, d_vb,
                        uint32_t(n), d_sc, out.d_stream_counts, out.cap, out.d_hit_stream, out.d_hit_pos);
-    if (out.d_pattern_counts) HIPCHK(c, hipMemcpyAsync(out.d_pattern_counts, d_pc, np * 8, hipMemcpyDeviceToDevice, sm));
+    if (out.d_pattern_counts) HIPCHK(c, hipMemcpyAsync(out.d_pattern_counts, scan.pat_counts.at(ws), scan.n * 8, hipMemcpyDeviceToDevice, sm));
     HIPCHK(c, hipMemcpyAsync(d_sc + n, d_total, 8, hipMemcpyDeviceToDevice, sm));
     uint64_t* h = h_sc.at(c->pinned2);
     if ((e = fetch(c, sm, h, d_sc, (n + 1) * 8))) return e;
@@ -151,16 +134,14 @@ int64_t stream_search_batch_pass(mlz_ctx* c, hipStream_t sm, bool ignore_crc, bo
 // mlz_stream_search_batch_device behind its argument checks.  Returns the number of all triples or -MLZ_ERR_*; the streams' results go to out_count.
 int64_t stream_search_batch_locked(mlz_ctx* c, hipStream_t sm, uint32_t flags, const uint8_t* d_src, const mlz_block_desc* streams, size_t n, const uint8_t* patterns,
                                    const uint32_t* pattern_len, size_t np, int64_t* out_count, const SearchBatchOut& out, uint64_t* stats) {
-    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0, fold = (flags & MLZ_SEARCH_IGNORE_CASE) != 0;
+    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0;
     BatchWalk bw;
     int r = stream_batch_walk(c, sm, d_src, streams, n, &bw);
     if (r) return r;
     begin_decode_call(c);
     c->search_chunks = c->search_tables = 0;
-    std::vector<uint8_t> keep;
-    patterns = search_many_folded(flags, patterns, pattern_len, np, &keep);
-    mlz::SearchManyIndex index;
-    mlz::search_many_index(patterns, pattern_len, np, &index);
+    SearchManyScan scan;
+    scan.prepare(flags, patterns, pattern_len, np);
     // a stream with a framing error keeps the walk's code, and nothing of it is searched
     std::vector<uint8_t> alive(n);
     std::vector<int64_t> verdict(n, 0), rc;
@@ -170,7 +151,7 @@ int64_t stream_search_batch_locked(mlz_ctx* c, hipStream_t sm, uint32_t flags, c
     for (;;) {
         size_t n_jobs = 0;
         bool failed = false;
-        const int64_t e = stream_search_batch_pass(c, sm, ignore_crc, fold, d_src, bw, n, alive, index, patterns, np, out, &rc, &counts, &total, &n_jobs, &failed);
+        const int64_t e = stream_search_batch_pass(c, sm, ignore_crc, d_src, bw, n, alive, scan, out, &rc, &counts, &total, &n_jobs, &failed);
         if (e < 0) return e;
         decoded += n_jobs;
         passes += n_jobs ? 1 : 0;
@@ -197,9 +178,7 @@ extern "C" int64_t mlz_stream_search_batch_device(mlz_ctx* c, void* stream, uint
                                                   uint64_t* d_pattern_counts, uint32_t* d_present, uint32_t* d_hit_stream, uint64_t* d_hit_pos, uint32_t* d_hit_which, size_t cap,
                                                   uint64_t* stats) {
     if (flags & ~uint32_t(MLZ_STREAM_IGNORE_CRC | MLZ_SEARCH_IGNORE_CASE | MLZ_SEARCH_NO_TABLES)) return -MLZ_ERR_ARG;
-    if (n_patterns == 0 || n_patterns > MLZ_SEARCH_MAX_PATTERNS || !patterns || !pattern_len || (cap && (!d_hit_stream || !d_hit_pos || !d_hit_which))) return -MLZ_ERR_ARG;
-    for (size_t i = 0; i < n_patterns; i++)
-        if (pattern_len[i] == 0 || pattern_len[i] > mlz::kSearchMaxPattern) return -MLZ_ERR_ARG;
+    if (n_patterns == 0 || search_pattern_list(patterns, pattern_len, n_patterns) < 0 || (cap && (!d_hit_stream || !d_hit_pos || !d_hit_which))) return -MLZ_ERR_ARG;
     const int a = batch_args(c, d_src, nullptr, false, streams, n_streams, out_count, &c);
     if (a) {
         if (a > 0 && stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;

@@ -159,24 +159,60 @@ __global__ __launch_bounds__(kSearchManyThreads) void search_many_kernel(const u
 
 namespace {
 
-// The pattern index of a call on its way to the device, as one block: heads | order | offsets | pattern bytes (a whole number of words).
-// take: its copies in the workspace (c->d_rplan) and in the pinned buffer; send (behind the caller's ensures, where the caller's stream
-// order wants the upload): fills the pinned copy and enqueues it; ix, lds_bytes: the index and a workgroup's LDS as the kernels take them.
-struct SearchManyUpload {
-    Carve up;
-    Region<uint16_t> u_heads, u_order;
-    Region<uint32_t> u_off;
-    Region<uint8_t> u_blob, dev, host;
-    mlz::SearchManyIx ix{};
-    uint32_t lds_bytes = 0;
+// The pattern list of a call: at most MLZ_SEARCH_MAX_PATTERNS patterns of 1 .. kSearchMaxPattern bytes, back to back in `patterns`.  Returns
+// their bytes together or -MLZ_ERR_ARG; whether n == 0 is an error is the caller's rule.
+int64_t search_pattern_list(const uint8_t* patterns, const uint32_t* pattern_len, size_t n) {
+    if (n > MLZ_SEARCH_MAX_PATTERNS || (n && (!patterns || !pattern_len))) return -MLZ_ERR_ARG;
+    int64_t blob = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (pattern_len[i] == 0 || pattern_len[i] > mlz::kSearchMaxPattern) return -MLZ_ERR_ARG;
+        blob += pattern_len[i];
+    }
+    return blob;
+}
 
-    void take(const mlz::SearchManyIndex& index, size_t n, Carve* cv, Carve* pin) {
+// The many-pattern scan of one call, host side: prepare (fold and index, once), take (from the caller's carves, which the caller then ensures),
+// clear and send (behind that ensure), then one launch per method over the tiles [t0, t1) of a group whose bytes are in the scratch (DESIGN.md).
+struct SearchManyScan {
+    bool fold = false, counting = false;
+    size_t n = 0;
+    const uint8_t* patterns = nullptr;   // folded under `fold` (then in `folded`), else the caller's
+    std::vector<uint8_t> folded;
+    mlz::SearchManyIndex index;
+    // The counting regions of the workspace (c->d_rplan): per-pattern counts | total | (the index) | tile counts | prefix; taken only when `counting`
+    Region<unsigned long long> pat_counts{};
+    Region<uint64_t> total{}, prefixes{};
+    Region<uint32_t> tile_counts{};
+    void prepare(uint32_t flags, const uint8_t* pats, const uint32_t* pattern_len, size_t n_patterns) {
+        fold = (flags & MLZ_SEARCH_IGNORE_CASE) != 0; n = n_patterns; patterns = pats;
+        if (fold) {
+            size_t bytes = 0;
+            for (size_t i = 0; i < n; i++) bytes += pattern_len[i];
+            folded.resize(bytes);
+            for (size_t i = 0; i < bytes; i++) folded[i] = mlz::search_fold(pats[i]);
+            patterns = folded.data();
+        }
+        mlz::search_many_index(patterns, pattern_len, n, &index);
+    }
+    // nt: the tiles to count, or NULL where nothing is counted (the grep).  The index goes up as one block: heads | order | offsets | pattern bytes
+    void take(Carve* cv, Carve* pin, const size_t* nt) {
+        counting = nt != nullptr;
+        up = Carve{};   // (the batch search takes anew for its second pass)
+        if (counting) { pat_counts = cv->take<unsigned long long>(n); total = cv->take<uint64_t>(2); }
         u_heads = up.take<uint16_t>(index.heads.size()); u_order = up.take<uint16_t>(n);
         u_off = up.take<uint32_t>(n + 1); u_blob = up.take<uint8_t>(size_t(index.off[n]) + 4);
-        dev = cv->take<uint8_t>(up.bytes);
-        host = pin->take<uint8_t>(up.bytes);
+        dev = cv->take<uint8_t>(up.bytes); host = pin->take<uint8_t>(up.bytes);
+        if (counting) { tile_counts = cv->take<uint32_t>(*nt, 4); prefixes = cv->take<uint64_t>(*nt); }
     }
-    int send(mlz_ctx* c, hipStream_t sm, const mlz::SearchManyIndex& index, const uint8_t* patterns, size_t n) {
+    int clear(mlz_ctx* c, hipStream_t sm) const {
+        if (!counting) return 0;
+        HIPCHK(c, hipMemsetAsync(pat_counts.at(c->d_rplan.p), 0, n * sizeof(unsigned long long), sm));
+        HIPCHK(c, hipMemsetAsync(total.at(c->d_rplan.p), 0, 16, sm));
+        return 0;
+    }
+    // The upload; d_tiles and sm are those of every launch that follows
+    int send(mlz_ctx* ctx, hipStream_t stream, const mlz::SearchTile* tiles) {
+        c = ctx; sm = stream; d_tiles = tiles;
         const uint32_t blob_bytes = index.off[n];
         void *d_up = dev.at(c->d_rplan.p), *h_up = host.at(c->pinned2);
         std::memcpy(u_heads.at(h_up), index.heads.data(), index.heads.size() * 2);
@@ -189,29 +225,44 @@ struct SearchManyUpload {
         HIPCHK(c, hipMemcpyAsync(d_up, h_up, up.bytes, hipMemcpyHostToDevice, sm));
         return 0;
     }
+    void count(size_t t0, size_t t1) const { launch<mlz::kSearchManyCount>(t0, t1, 0, nullptr, nullptr, mlz::SearchManyMark{}); }
+    void prefix(size_t t0, size_t t1) const {
+        void* ws = c->d_rplan.p;
+        hipLaunchKernelGGL(mlz::search_prefix_kernel, dim3(1), dim3(1024), 0, sm, tile_counts.at(ws), uint32_t(t0), uint32_t(t1), prefixes.at(ws), total.at(ws));
+    }
+    void write(size_t t0, size_t t1, uint64_t cap, uint64_t* out_pos, uint32_t* out_which) const { launch<mlz::kSearchManyWrite>(t0, t1, cap, out_pos, out_which, mlz::SearchManyMark{}); }
+    void mark_records(size_t t0, size_t t1, const uint64_t* D, uint64_t k, uint32_t* bits) const { launch<mlz::kSearchManyMarkRecords>(t0, t1, 0, nullptr, nullptr, mlz::SearchManyMark{D, k, bits, nullptr, 0}); }
+    void mark_streams(size_t t0, size_t t1, const uint32_t* ts, uint32_t* bits, uint32_t words) const { launch<mlz::kSearchManyMarkStreams>(t0, t1, 0, nullptr, nullptr, mlz::SearchManyMark{nullptr, 0, bits, ts, words}); }
+    // What the counting calls run per group: count, the running prefix continued and, while the group's bytes are still in the scratch, the pairs below cap
+    void count_prefix_write(size_t t0, size_t t1, uint64_t cap, uint64_t* out_pos, uint32_t* out_which) const {
+        count(t0, t1);
+        prefix(t0, t1);
+        if (cap) write(t0, t1, cap, out_pos, out_which);
+    }
+private:
+    mlz_ctx* c = nullptr;   // (c, sm and d_tiles: send's)
+    hipStream_t sm = nullptr;
+    const mlz::SearchTile* d_tiles = nullptr;
+    Carve up;
+    Region<uint16_t> u_heads{}, u_order{};
+    Region<uint32_t> u_off{};
+    Region<uint8_t> u_blob{}, dev{}, host{};   // the block's layout, and its copies in the workspace and the pinned buffer
+    mlz::SearchManyIx ix{};
+    uint32_t lds_bytes = 0;
+    // Every launch of search_many_kernel.  The counting regions go to every mode of a counting call (NULL otherwise); a mode reads only its own arguments
+    template <int kMode>
+    void launch(size_t t0, size_t t1, uint64_t cap, uint64_t* out_pos, uint32_t* out_which, const mlz::SearchManyMark& mk) const {
+        void* ws = counting ? c->d_rplan.p : nullptr;
+        const auto kernel = fold ? mlz::search_many_kernel<kMode, true> : mlz::search_many_kernel<kMode, false>;
+        hipLaunchKernelGGL(kernel, dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), lds_bytes, sm, c->d_range.as<uint8_t>(), d_tiles, uint32_t(t0), ix, ws ? tile_counts.at(ws) : nullptr,
+                           ws ? pat_counts.at(ws) : nullptr, ws ? static_cast<const uint64_t*>(prefixes.at(ws)) : nullptr, cap, out_pos, out_which, mk);
+    }
 };
-
-// search_many_kernel<kMode> with or without folding
-template <int kMode>
-auto search_many_kernel_of(bool fold) { return fold ? mlz::search_many_kernel<kMode, true> : mlz::search_many_kernel<kMode, false>; }
-
-// The patterns of a call as its plan, index and scan see them: folded under MLZ_SEARCH_IGNORE_CASE (once, here), else the caller's
-const uint8_t* search_many_folded(uint32_t flags, const uint8_t* patterns, const uint32_t* pattern_len, size_t n, std::vector<uint8_t>* keep) {
-    if (!(flags & MLZ_SEARCH_IGNORE_CASE)) return patterns;
-    size_t bytes = 0;
-    for (size_t i = 0; i < n; i++) bytes += pattern_len[i];
-    keep->resize(bytes);
-    for (size_t i = 0; i < bytes; i++) (*keep)[i] = mlz::search_fold(patterns[i]);
-    return keep->data();
-}
 
 int64_t dev_reader_search_many_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* patterns, const uint32_t* pattern_len, size_t n, uint64_t* d_counts,
                                       uint64_t* d_offsets, uint32_t* d_which, uint64_t cap, uint64_t* stats) {
     mlz_ctx* c = rd->ctx;
     const size_t nck = rd->chunks.size();
-    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0, fold = (flags & MLZ_SEARCH_IGNORE_CASE) != 0;
-    std::vector<uint8_t> keep;
-    patterns = search_many_folded(flags, patterns, pattern_len, n, &keep);
     search_begin(rd, stats);
     HIPCHK(c, hipSetDevice(c->device));
     auto nothing = [&]() -> int64_t {   // no chunk to scan: every count is 0
@@ -222,48 +273,30 @@ int64_t dev_reader_search_many_locked(mlz_dev_reader* rd, hipStream_t sm, uint32
         return 0;
     };
     if (nck == 0) return nothing();
-    mlz::SearchManyIndex index;
-    mlz::search_many_index(patterns, pattern_len, n, &index);
+    SearchManyScan scan;
+    scan.prepare(flags, patterns, pattern_len, n);
     std::vector<uint8_t> take(nck, 0);
     size_t n_take = 0;
-    const int64_t pr = dev_reader_search_plan(rd, sm, flags, patterns, index.off, n, &take, &n_take, stats, true);
+    const int64_t pr = dev_reader_search_plan(rd, sm, flags, scan.patterns, scan.index.off, n, &take, &n_take, stats, true);
     if (pr) return pr;
     if (n_take == 0) return nothing();
-
     SearchDecode sd;
-    search_decode_plan(rd->chunks, take, n_take, index.lmin, index.lmax, mlz::kSearchManyTile, &sd);
+    search_decode_plan(rd->chunks, take, n_take, scan.index.lmin, scan.index.lmax, mlz::kSearchManyTile, &sd);
     const size_t nt = sd.lay.tiles.size();
     if (nt > 0x7fffffffu) return -MLZ_ERR_ARG;
-    Carve cv, pin;   // workspace: per-pattern counts | total | the index | tile counts | prefix | the decode's; pinned: the index | the decode's
-    const auto r_pc = cv.take<unsigned long long>(n);
-    const auto r_total = cv.take<uint64_t>(2);
-    SearchManyUpload up;
-    up.take(index, n, &cv, &pin);
-    const auto r_counts = cv.take<uint32_t>(nt, 4);
-    const auto r_prefix = cv.take<uint64_t>(nt);
+    Carve cv, pin;   // workspace: the scan's (per-pattern counts | total | the index | tile counts | prefix) | the decode's; pinned: the index | the decode's
+    scan.take(&cv, &pin, &nt);
     int e = search_decode_ready(rd->ctx, rd->chunks, &sd, &cv, &pin);
     if (e) return e;
-    void* ws = c->d_rplan.p;
-    unsigned long long* d_pc = r_pc.at(ws);
-    uint64_t *d_total = r_total.at(ws), *d_prefix = r_prefix.at(ws);
-    uint32_t* d_tc = r_counts.at(ws);
-    const mlz::SearchTile* d_tiles = sd.tiles.at(ws);
     { WorkspaceOrder order(c, sm); }
-    HIPCHK(c, hipMemsetAsync(d_pc, 0, n * sizeof(unsigned long long), sm));
-    HIPCHK(c, hipMemsetAsync(d_total, 0, 16, sm));
-    if ((e = up.send(c, sm, index, patterns, n))) return e;
-    const int64_t r = search_decode_run(rd->ctx, rd->d_src, rd->chunks, sm, ignore_crc, &sd, [&](size_t, size_t t0, size_t t1) {
-        const uint8_t* scratch = c->d_range.as<uint8_t>();
-        hipLaunchKernelGGL(search_many_kernel_of<mlz::kSearchManyCount>(fold), dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), up.lds_bytes, sm, scratch, d_tiles, uint32_t(t0), up.ix, d_tc, d_pc,
-                           static_cast<const uint64_t*>(nullptr), uint64_t(0), static_cast<uint64_t*>(nullptr), static_cast<uint32_t*>(nullptr), mlz::SearchManyMark{});
-        hipLaunchKernelGGL(mlz::search_prefix_kernel, dim3(1), dim3(1024), 0, sm, d_tc, uint32_t(t0), uint32_t(t1), d_prefix, d_total);
-        if (cap) hipLaunchKernelGGL(search_many_kernel_of<mlz::kSearchManyWrite>(fold), dim3(uint32_t(t1 - t0)), dim3(mlz::kSearchManyThreads), up.lds_bytes, sm, scratch, d_tiles, uint32_t(t0), up.ix, d_tc, d_pc,
-                                    static_cast<const uint64_t*>(d_prefix), cap, d_offsets, d_which, mlz::SearchManyMark{});
+    if ((e = scan.clear(c, sm)) || (e = scan.send(c, sm, sd.tiles.at(c->d_rplan.p)))) return e;
+    const int64_t r = search_decode_run(rd->ctx, rd->d_src, rd->chunks, sm, (flags & MLZ_STREAM_IGNORE_CRC) != 0, &sd, [&](size_t, size_t t0, size_t t1) {
+        scan.count_prefix_write(t0, t1, cap, d_offsets, d_which);
         return 0;
     });
     if (r < 0) return r;
-    if (d_counts) HIPCHK(c, hipMemcpyAsync(d_counts, d_pc, n * 8, hipMemcpyDeviceToDevice, sm));
-    if ((e = fetch(c, sm, c->pinned2, d_total, 8))) return e;
+    if (d_counts) HIPCHK(c, hipMemcpyAsync(d_counts, scan.pat_counts.at(c->d_rplan.p), n * 8, hipMemcpyDeviceToDevice, sm));
+    if ((e = fetch(c, sm, c->pinned2, scan.total.at(c->d_rplan.p), 8))) return e;
     return int64_t(*static_cast<const uint64_t*>(c->pinned2));
 }
 
@@ -271,9 +304,7 @@ int64_t dev_reader_search_many_locked(mlz_dev_reader* rd, hipStream_t sm, uint32
 
 extern "C" int64_t mlz_dev_reader_search_many(mlz_dev_reader* rd, void* stream, uint32_t flags, const uint8_t* patterns, const uint32_t* pattern_len, size_t n_patterns,
                                               uint64_t* d_counts, uint64_t* d_offsets, uint32_t* d_which, size_t cap, uint64_t* stats) {
-    if (!rd || n_patterns > MLZ_SEARCH_MAX_PATTERNS || (n_patterns && (!patterns || !pattern_len)) || (cap && (!d_offsets || !d_which))) return -MLZ_ERR_ARG;
-    for (size_t i = 0; i < n_patterns; i++)
-        if (pattern_len[i] == 0 || pattern_len[i] > mlz::kSearchMaxPattern) return -MLZ_ERR_ARG;
+    if (!rd || search_pattern_list(patterns, pattern_len, n_patterns) < 0 || (cap && (!d_offsets || !d_which))) return -MLZ_ERR_ARG;
     mlz_ctx* c = rd->ctx;
     std::lock_guard<std::mutex> lk(c->mu);
     if (enter_device(c)) return -MLZ_ERR_HIP;

@@ -337,7 +337,7 @@ int64_t stream_run_chunk_jobs(mlz_ctx* c, hipStream_t sm, bool ignore_crc, const
 
 // The scratch decode: a list of a handle's chunks decoded group by group into the context's scratch (c->d_range), which every group reuses,
 // for the calls that read decoded bytes without keeping them (the searches, the grep, the record index, the sidecar build).  The caller
-// fills jobs (ck; in stream order), gend and at (every job's offset in the scratch); the rest is the rule of mlz_stream_scratch.h.
+// fills jobs (ck; in stream order), gend and at (every job's offset in the scratch; scratch_decode_whole: for all chunks); the rest is the rule of mlz_stream_scratch.h.
 struct ScratchDecode {
     std::vector<ChunkJob> jobs;
     std::vector<size_t> gend;
@@ -377,6 +377,21 @@ struct ScratchDecode {
         }, per_job);
     }
 };
+
+// The whole-stream decode of a handle's chunk table (mlz::whole_stream_list): jobs, gend and at of *dec; *w keeps every group's first decoded
+// position and bytes.  size: the stream's decoded bytes; `call` names the entry point in an error's text.  An empty stream (size 0, no chunk with bytes) passes with no job and no group: a caller that launches per group must be ready for none.
+int scratch_decode_whole(mlz_ctx* c, const char* call, const std::vector<StreamChunk>& chunks, uint64_t size, ScratchDecode* dec, mlz::WholeStreamList* w) {
+    const std::vector<size_t> dc = mlz::chunks_with_bytes(chunks.size(), [&](size_t k) { return chunks[k].n; });
+    mlz::range_group_ends(dc.size(), [&](size_t i) { return uint64_t(chunks[dc[i]].n); }, &dec->gend);
+    *w = mlz::whole_stream_list(dc, dec->gend, [&](size_t k) { return uint64_t(chunks[k].n); }, [&](size_t k) { return uint64_t(chunks[k].out_off); }, size);
+    if (w->status != mlz::kWholeOk) {
+        c->err = std::string(call) + (w->status == mlz::kWholeNotContiguous ? ": the chunks' output offsets are not contiguous" : ": the groups do not tile the stream");
+        return -MLZ_ERR_HIP;
+    }
+    for (size_t k : dc) dec->jobs.push_back(ChunkJob{k, nullptr});
+    dec->at = w->at;
+    return 0;
+}
 
 // The in-place decode: a job list whose targets all lie in d_dst, where the chunks finally lie.  Stored chunks by one stream_place_kernel launch over
 // their 64 KiB pieces, then decode and CRC group by group (range_group_ends, stream_run_chunk_jobs and its per_job).  The caller has begun the decode call.

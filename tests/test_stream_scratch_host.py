@@ -81,6 +81,54 @@ def test_the_program_sees_a_wrong_list(checkers):
         checkers[0]([bad])
 
 
+def whole(chunks, groups, size):
+    """chunks: [(n, out_off)] of a chunk table; groups: per group how many of the chunks WITH bytes it holds, in order.  -> (the record,
+    the line the program must print): the count below is whole_stream_list's rule in Python."""
+    dc = [k for k, (n, _) in enumerate(chunks) if n]
+    gend = list(np.cumsum(groups, dtype=np.int64)) if groups else []
+    rec = struct.pack("<IIIQ", 3, len(chunks), len(gend), size)
+    rec += b"".join(struct.pack("<QQ", n, off) for n, off in chunks) + np.asarray(gend, np.uint64).tobytes()
+    spans, at, pos, i = [], [], 0, 0
+    for e in gend:
+        first, o = chunks[dc[i]][1] if i < e else pos, 0
+        for k in dc[i:e]:
+            if chunks[k][1] != first + o:
+                return rec, "status 1"
+            at.append(o)
+            o += chunks[k][0]
+        i = e
+        spans.append((first, o))
+        if o == 0 or first != pos or pos + o > size:
+            return rec, "status 2"
+        pos += o
+    if pos != size:
+        return rec, "status 2"
+    return rec, "status 0 groups%s at%s" % ("".join(" %d+%d" % s for s in spans), "".join(" %d" % a for a in at))
+
+
+# (chunks as (n, out_off), the groups' job counts, the decoded size) -> the status
+WHOLE = {
+    "one group": ([(700, 0), (300, 700), (5000, 1000)], [3], 6000, 0),
+    "three groups, empty chunks between and at both ends": ([(0, 0), (90, 0), (10, 90), (0, 100), (0, 100), (400, 100), (0, 500), (7, 500), (1, 507), (0, 508)], [2, 1, 2], 508, 0),
+    "an out_off one too high inside a group": ([(700, 0), (300, 701), (50, 1001)], [2, 1], 1051, 1),
+    "a gap between two groups": ([(700, 0), (300, 700), (50, 1001)], [2, 1], 1051, 2),
+    "the first group does not start at 0": ([(700, 1), (300, 701)], [1, 1], 1001, 2),
+    "the last group ends short of the size": ([(700, 0), (300, 700)], [1, 1], 1001, 2),
+    "the last group ends beyond the size": ([(700, 0), (300, 700)], [1, 1], 999, 2),
+    "a group without a chunk": ([(700, 0), (300, 700)], [1, 0, 1], 1000, 2),
+    "no chunk with bytes, size 0": ([(0, 0), (0, 0)], [], 0, 0),
+    "no chunk with bytes, size 5": ([(0, 0)], [], 5, 2),
+}
+
+
+@pytest.mark.parametrize("name", list(WHOLE))
+def test_whole_stream_list(checkers, name):
+    chunks, groups, size, status = WHOLE[name]
+    rec, want = whole(chunks, groups, size)
+    assert want.startswith("status %d" % status)
+    assert both(checkers, [rec]) == [want]
+
+
 def test_chunks_with_bytes(checkers):
     sizes = [0, 5, 0, 0, 1, 1 << 40, 0]
     recs = [struct.pack("<II", 2, len(s)) + np.asarray(s, np.uint64).tobytes() for s in (sizes, [], [0, 0])]

@@ -10,6 +10,8 @@
 //           stream (status 3 otherwise):
 //           "places <n> ends <place_end ...> max <scratch_max>"
 //   kind 2  u32 chunks; per chunk u64 n -> chunks_with_bytes: "with bytes <k ...>"
+//   kind 3  u32 chunks, groups; u64 size; per chunk u64 n, out_off; per group u64 gend (over the chunks with bytes)
+//           -> whole_stream_list over chunks_with_bytes: "status <s>", and under status 0 " groups <first>+<bytes> ... at <at ...>"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -85,6 +87,26 @@ void staged(In& in) {
     std::printf(" max %llu\n", (unsigned long long)scratch_max);
 }
 
+void whole(In& in) {
+    const uint32_t n = in.get<uint32_t>(), ng = in.get<uint32_t>();
+    const uint64_t size = in.get<uint64_t>();
+    std::vector<uint64_t> sizes(n), offs(n);
+    for (uint32_t k = 0; k < n; k++) { sizes[k] = in.get<uint64_t>(); offs[k] = in.get<uint64_t>(); }
+    std::vector<size_t> gend(ng);
+    for (uint32_t g = 0; g < ng; g++) gend[g] = size_t(in.get<uint64_t>());
+    const std::vector<size_t> dc = mlz::chunks_with_bytes(n, [&](size_t k) { return sizes[k]; });
+    const mlz::WholeStreamList w = mlz::whole_stream_list(dc, gend, [&](size_t k) { return sizes[k]; }, [&](size_t k) { return offs[k]; }, size);
+    std::printf("status %d", w.status);
+    if (w.status == mlz::kWholeOk) {
+        if (w.at.size() != dc.size() || w.first.size() != ng || w.bytes.size() != ng) fail("the list's arrays do not fit its jobs and groups", w.at.size());
+        std::printf(" groups");
+        for (uint32_t g = 0; g < ng; g++) std::printf(" %llu+%llu", (unsigned long long)w.first[g], (unsigned long long)w.bytes[g]);
+        std::printf(" at");
+        for (uint64_t a : w.at) std::printf(" %llu", (unsigned long long)a);
+    }
+    std::printf("\n");
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -100,6 +122,7 @@ int main(int argc, char** argv) {
     while (in.p < in.b.size()) {
         const uint32_t kind = in.get<uint32_t>();
         if (kind == 1) { staged(in); continue; }
+        if (kind == 3) { whole(in); continue; }
         if (kind != 2) { std::fprintf(stderr, "unknown record %u\n", kind); return 2; }
         const uint32_t n = in.get<uint32_t>();
         std::vector<uint64_t> sizes(n);
