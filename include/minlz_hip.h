@@ -195,7 +195,7 @@ int64_t mlz_stream_decode(mlz_ctx* ctx, uint32_t flags, const uint8_t* src, size
  * 12 more bytes per block visit the host (table bytes or 0, R, CRC).  The seek index names a block by the offset at which its chunks start: its table chunk
  * when it has one.  mlz_stream_bound with the flag adds 7 + (12 + max(32, 2^(B - 3))) per block.  Without the flag every byte is what it was before the
  * flag existed.  Table type 4 (the long prefix) is written by mlz_stream_encode_gather_device_long_prefix below.  Tables for a stream that exists
- * already — any writer's — go into a sidecar: mlz_dev_reader_build_sidecar below.  Out of scope: compressed tables (0x46) and a Writer that emits a
+ * already — any writer's — go into a sidecar: mlz_dev_reader_build_sidecar below.  Out of scope: WRITING compressed tables (0x46; the searches read them) and a Writer that emits a
  * sidecar while it encodes (the reference's WriterSidecar). */
 int64_t mlz_stream_encode_gather_device(mlz_ctx* ctx, int level, uint32_t block_size, uint32_t flags, const uint8_t* const* d_src, const size_t* src_len,
                                         int n_ranges, uint8_t* d_dst, size_t dst_cap);
@@ -365,8 +365,9 @@ void mlz_dev_reader_close(mlz_dev_reader* reader);
 
 /* Pattern search over a stream that lies in HBM, with the reference's block search tables (SPEC_SEARCH.md; search_table.go, search_index.go) where
  * the stream has them: table types 1 (no prefix), 2 (1 to 8 prefix byte values), 3 (a mask of prefix byte values) and 4 (a long prefix with extra
- * matches) in uncompressed table chunks (0x45) behind an info chunk (0x44).  Compressed tables (0x46) are stepped over: their blocks count as having
- * no table.  The tables may also come from a sidecar, a second stream that names the blocks of this one with remote references (0x47):
+ * matches) in uncompressed table chunks (0x45) and in compressed ones (0x46: expanded once per handle, by its first search, into device memory the handle
+ * owns; minlz_hip_search_compressed.h, mlz_get_counter 14) behind an info chunk (0x44); the first fitting table in front of a block is taken, whichever of
+ * the two it is, and a 0x46 table that does not parse, decode or pass its CRC is passed over like a broken 0x45 one.  The tables may also come from a sidecar, a second stream that names the blocks of this one with remote references (0x47):
  * mlz_dev_reader_build_sidecar and mlz_dev_reader_attach_sidecar below; remote references inside the searched stream itself are stepped over.
  *
  * mlz_dev_reader_search: returns the number of positions p of the decoded stream with decoded[p, p + pattern_len) == pattern (overlapping occurrences
@@ -600,8 +601,8 @@ int64_t mlz_dev_reader_grep_records(mlz_dev_reader* reader, void* stream, uint32
  *   info chunks in front of its first 0x45 or 0x47.  A 0x47 payload is a list of (offset, block size - decoded bytes) pairs, the first offset
  *   absolute, the others relative and not 0; every reference must name the header offset of a data chunk of the handle's stream and state its
  *   decoded bytes, and references ascend over the whole sidecar.  The first reference of a 0x47 owns the tables in front of it: per configuration the
- *   first 0x45 between the previous 0x47 and this one that fits it (type, M, B, field, R, length) with a good CRC (not checked under
- *   MLZ_STREAM_IGNORE_CRC); a broken one is passed over for the next that fits; 0x46 chunks are stepped over; a data chunk without a reference has
+ *   first 0x45 or 0x46 between the previous 0x47 and this one that fits it (type, M, B, field, R, length) with a good CRC (not checked under
+ *   MLZ_STREAM_IGNORE_CRC); a broken one is passed over for the next that fits; 0x46 tables are expanded by the attach; a data chunk without a reference has
  *   no table.  Errors — nothing is attached, the handle keeps what it had: -MLZ_ERR_ARG for a pointer not on the handle's device; the walk's own
  *   error for a framing error or a missing EOF chunk; -MLZ_ERR_CORRUPT for a bad varint, an empty 0x47, a reference that names no data chunk, a size
  *   that disagrees, an order that does not ascend, a data chunk inside the sidecar; -MLZ_ERR_UNSUPPORTED for a second identifier.  A sidecar
@@ -611,7 +612,7 @@ int64_t mlz_dev_reader_grep_records(mlz_dev_reader* reader, void* stream, uint32
  *   is built over the next chunk's bytes alone, so a configuration does not vote on a chunk that is followed by one with fewer bytes than its overlap
  *   (M - 1, M, or K - 1 + M + E for types 1, 2 and 3, 4): that chunk is decoded, and every position is returned as without a sidecar.  The third
  *   statistic counts the chunks with a usable table of at least one configuration that serves a pattern, the fourth the patterns no configuration serves.
- * Out of scope: compressed tables (0x46), ExtractSidecar, the Writer-side sidecar, concatenated streams, sidecars read from host memory. */
+ * Out of scope: writing compressed tables (0x46; build_sidecar emits 0x45), ExtractSidecar, the Writer-side sidecar, concatenated streams, sidecars read from host memory. */
 #define MLZ_SIDECAR_MAX_CONFIGS 4
 typedef struct {
     uint8_t table_type;   /* 1 .. 4 */

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension headers include/minlz_hip_search_batch.h, include/minlz_hip_stream_set.h and include/minlz_hip_regex.h.
+"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension headers include/minlz_hip_search_batch.h, include/minlz_hip_stream_set.h, include/minlz_hip_regex.h and include/minlz_hip_search_compressed.h.
 
 There is no CPU fallback here: if libminlz_hip.so is missing or HIP is unavailable, calls raise.
 """
@@ -124,7 +124,14 @@ ABI_EXT = {
         "mlz_regex_test": (i32, [vp, vp, sz]),
         "mlz_dev_reader_grep_regex": (i64, [vp, vp, u32, vp, u64, u64, vp, vp, sz, P(u64), P(u64)]),
     },
+    "minlz_hip_search_compressed.h": {
+        "mlz_search_table_expand": (i64, [vp, sz, vp, sz, P(u32), u32]),
+    },
 }
+
+# mlz_get_counter(ctx, 14): of the chunks with a usable search table in the last search (counter 11), those whose table came from a compressed
+# table chunk, 0x46 (api.Context.search_compressed_tables; the names of the counters 0 .. 12 stand in api)
+COUNTER_SEARCH_COMPRESSED = 14
 
 _lib = None
 
@@ -135,7 +142,12 @@ def lib():
         if not os.path.exists(SO):
             raise RuntimeError("minlz_amd: %s not built (run python -c 'import __graft_entry__ as g; g.build()')" % SO)
         L = C.CDLL(SO)
+        # Under the development override a library from before an extension header loads without that header's functions (tools/ time the
+        # parent commit's library against this tree's); calling one of them then raises AttributeError.  The tree's own library has them all.
+        old = bool(os.environ.get("MINLZ_HIP_LIB"))
         for name, (restype, argtypes) in list(ABI.items()) + [kv for table in ABI_EXT.values() for kv in table.items()]:
+            if old and name not in ABI and not hasattr(L, name):
+                continue
             f = getattr(L, name)
             f.restype, f.argtypes = restype, argtypes
         _lib = L

@@ -256,6 +256,11 @@ class Context:
         """(chunks decoded or copied, chunks with a usable search table) of the context's last DeviceReader.search, search_many, grep_records or grep_regex (mlz_get_counter 10, 11)."""
         return self.counter(COUNTER_SEARCH_CHUNKS), self.counter(COUNTER_SEARCH_TABLES)
 
+    def search_compressed_tables(self):
+        """Of the chunks with a usable search table in the context's last search, those whose table came from a compressed table chunk, 0x46
+        (mlz_get_counter 14)."""
+        return self.counter(_lib.COUNTER_SEARCH_COMPRESSED)
+
     def range_plan_host_bytes(self):
         """Bytes of plan data that crossed between host and device, both directions together, in the context's last DeviceReader.read_device
         (mlz_get_counter 9): a header and two records per TOUCHED CHUNK, nothing per range."""
@@ -685,6 +690,18 @@ def crc(b, ctx=None):
     """crc(b) of minlz.go:133-140 (masked CRC32C), computed on the device."""
     a = _np(b)
     return (ctx or default_context())._call("mlz_crc", _ptr(a), a.size)
+
+
+def expand_search_table(body, ignore_crc=False):
+    """mlz_search_table_expand (include/minlz_hip_search_compressed.h): the payload of a compressed block search table chunk (0x46) ->
+    (R, the table's bytes), on the host; needs no context and no GPU.  A chunk that is refused raises ErrCorrupt, a stale CRC ErrCRC."""
+    a = _np(body)
+    R = C.c_uint32()
+    out = np.empty(1 << 20, dtype=np.uint8)     # the largest table: 2^23 bits
+    r = _lib.lib().mlz_search_table_expand(_ptr(a), a.size, out.ctypes.data, out.size, C.byref(R), _flags(ignore_crc=ignore_crc))
+    if r < 0:
+        _raise(r)
+    return int(R.value), out[:r].tobytes()
 
 
 def encode_block(src, level=LevelFastest, ctx=None):

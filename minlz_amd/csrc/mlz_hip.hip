@@ -19,6 +19,7 @@
 #include "../../include/minlz_hip.h"
 #include "../../include/minlz_hip_search_batch.h"
 #include "../../include/minlz_hip_stream_set.h"
+#include "../../include/minlz_hip_search_compressed.h"
 #include "mlz_format.h"
 #include "mlz_kernels.h"
 
@@ -27,6 +28,7 @@
 #include "mlz_decode_serial.hip.inc"
 #include "mlz_toktab.h"
 #include "mlz_stream_search.h"
+#include "mlz_search_compressed.h"
 #include "mlz_decode.hip.inc"
 #include "mlz_decode_index.hip.inc"
 #include "mlz_decode_exec.hip.inc"
@@ -153,6 +155,7 @@ struct mlz_ctx {
     DevBuf d_rplan;              // mlz_dev_reader_read_device: the plan kernels' workspace (16 bytes per range, 28 per chunk of the stream)
     DevBuf d_records, d_rwin;    // mlz_dev_reader_search_records: what lives across its read phase (the occurrences, windows and records: about 100 bytes per occurrence), and the merged windows' bytes (at most the decoded size)
     uint64_t range_plan_host = 0;   // plan bytes that crossed between host and device in the last mlz_dev_reader_read_device (mlz_get_counter 9)
+    uint64_t search_compressed = 0;                 // of search_tables, the chunks whose usable table came from a compressed chunk, 0x46 (mlz_get_counter 14)
     uint64_t search_chunks = 0, search_tables = 0;  // the last mlz_dev_reader_search: chunks decoded or copied, chunks with a usable table (mlz_get_counter 10 / 11)
     uint64_t range_chunks = 0, range_scratch = 0;   // the last range read: chunks decoded or copied, decoded bytes that went through d_range (mlz_get_counter 7 / 8)
     DevBuf d_gen_acc;      // two words summed over a call's internal groups by the schedule code: general blocks, largest team (mlz_get_counter 2 / 6)
@@ -1255,6 +1258,7 @@ int64_t mlz_get_counter(mlz_ctx* c, int which) {
     if (which == 9) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->range_plan_host); }
     if (which == 12) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->batch_long); }
     if (which == 13) { std::lock_guard<std::mutex> lk(c->mu); return c->acc_call == c->dec_call ? int64_t(c->l0_launches) : 0; }   // groups of the last decode call that took dec_level0_kernel's launch
+    if (which == 14) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->search_compressed); }
     if (which == 10 || which == 11) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(which == 10 ? c->search_chunks : c->search_tables); }
     std::lock_guard<std::mutex> lk(c->q_mu);
     return which == 0 ? int64_t(c->q_batches) : which == 1 ? int64_t(c->q_requests) : -MLZ_ERR_ARG;
@@ -1339,6 +1343,7 @@ int mlz_debug_idxprof(unsigned long long* out) {
 #include "mlz_stream_ranges.hip.inc"
 #include "mlz_stream_batch.hip.inc"
 #include "mlz_stream_ranges_dev.hip.inc"
+#include "mlz_stream_search_compressed.hip.inc"
 #include "mlz_stream_search.hip.inc"
 #include "mlz_stream_search_many.hip.inc"
 #include "mlz_stream_search_batch.hip.inc"

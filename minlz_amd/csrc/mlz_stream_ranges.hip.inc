@@ -74,6 +74,8 @@ struct mlz_dev_reader {
         mlz::SearchConfig cfg[mlz::kSidecarMaxConfigs] = {};
         const uint8_t* base = nullptr;        // the tables' offsets count from here: the stream, or the sidecar
         void* d_tabs = nullptr;               // mlz::SearchTab per (set, data chunk), set by set; device memory the handle owns
+        void* d_arena = nullptr;              // the expanded bitmaps of the sets' compressed tables (0x46), device memory the handle owns
+        size_t arena_bytes = 0;
         std::vector<mlz::SearchTab> tabs;
     } search[2], side;
     bool side_on = false;
@@ -199,7 +201,8 @@ void mlz_dev_reader_close(mlz_dev_reader* rd) {
     if (rd && (rd->d_chunks || rd->search[0].d_tabs || rd->search[1].d_tabs || rd->side.d_tabs || rd->d_index || rd->d_bases)) {
         std::lock_guard<std::mutex> lk(rd->ctx->mu);
         if (hipSetDevice(rd->ctx->device) == hipSuccess)
-            for (void* p : {rd->d_chunks, rd->search[0].d_tabs, rd->search[1].d_tabs, rd->side.d_tabs, rd->d_index, rd->d_bases}) if (p) (void)hipFree(p);
+            for (void* p : {rd->d_chunks, rd->search[0].d_tabs, rd->search[1].d_tabs, rd->side.d_tabs, rd->search[0].d_arena, rd->search[1].d_arena, rd->side.d_arena, rd->d_index, rd->d_bases})
+                if (p) (void)hipFree(p);
     }
     delete rd;
 }

@@ -9,7 +9,7 @@
 // The case-folding section adds what MLZ_SEARCH_IGNORE_CASE needs: the byte and the dword fold, and the plan rule over the windows' case variants
 // (search_windows_fold, search_pattern_hashes_fold, search_probe_fold; tools/stream_search_fold_check.cpp).
 // Plain C++: compiles for the host alone and for gfx950.  Table types 1 (no prefix), 2 (1 to 8 prefix byte values), 3 (a 256-bit mask of
-// prefix byte values; SPEC_SEARCH.md 3.3) and 4 (a long prefix of 1 to 256 bytes with extra matches; 3.3.4), uncompressed table chunks (0x45) only.
+// prefix byte values; SPEC_SEARCH.md 3.3) and 4 (a long prefix of 1 to 256 bytes with extra matches; 3.3.4), uncompressed table chunks (0x45); compressed ones (0x46): mlz_search_compressed.h.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -31,8 +31,10 @@ constexpr uint32_t kSearchMaxPattern = 256, kSearchDefaultMatchLen = 6;
 constexpr uint32_t kSearchNoTable = 0xffffffffu;
 
 // A data chunk's table as the search keeps it: where its bytes lie in the stream, their number, the reductions (kSearchNoTable: no usable
-// table) and the CRC its chunk states.
+// table) and the CRC its chunk states.  pad = kSearchTabArena: the table came from a compressed chunk (0x46) and its expanded bytes lie in
+// the handle's arena, at arena + off, not in the stream (between the locate kernel and the expansion: off and bytes name the chunk's body).
 struct SearchTab { uint64_t off; uint32_t bytes, R, crc, pad; };
+constexpr uint32_t kSearchTabArena = 1;
 static_assert(sizeof(SearchTab) == 24, "a record shared with the kernels");
 
 // HashValue(val, tableSize, matchLen): `val` holds the window's bytes little-endian (bytes beyond matchLen are ignored).

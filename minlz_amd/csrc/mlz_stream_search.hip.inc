@@ -43,7 +43,9 @@ __global__ __launch_bounds__(64) void search_info_kernel(const uint8_t* __restri
     }
 }
 
-// skip[k]: fitting tables in front of chunk k that an earlier round found broken (CRC) and that are passed over
+// skip[k]: fitting tables in front of chunk k that an earlier round found broken (a stale CRC; a compressed table that does not parse or
+// decode) and that are passed over.  A fitting compressed table (0x46) is taken as a candidate: pad = kSearchTabArena, off and bytes = its body
+// (cst_resolve, mlz_stream_search_compressed.hip.inc, expands it or has it skipped).
 __global__ __launch_bounds__(64) void search_locate_kernel(const uint8_t* __restrict__ src, const SearchHop* __restrict__ hop, const uint32_t* __restrict__ skip, uint32_t nck,
                                                            const SearchInfo* __restrict__ info, SearchTab* __restrict__ tabs) {
     const uint32_t k = blockIdx.x * 64 + threadIdx.x;
@@ -65,6 +67,13 @@ __global__ __launch_bounds__(64) void search_locate_kernel(const uint8_t* __rest
                     t = SearchTab{p + 12 + f, clen - 8 - f, uint32_t(R), uint32_t(q[0]) | uint32_t(q[1]) << 8 | uint32_t(q[2]) << 16 | uint32_t(q[3]) << 24, 0};
                     break;
                 }
+            } else if (type == kChunkSearchTableCompressed && p + 4 + clen <= limit) {
+                const int R = cst_fixed_fields(src + p + 4, clen, in.M, in.B, in.T, in.field);
+                if (R >= 0 && left-- == 0) {
+                    const uint8_t* q = src + p + 8 + search_field_len(in.T, in.field);
+                    t = SearchTab{p + 4, clen, uint32_t(R), uint32_t(q[0]) | uint32_t(q[1]) << 8 | uint32_t(q[2]) << 16 | uint32_t(q[3]) << 24, kSearchTabArena};
+                    break;
+                }
             }
             p += 4 + uint64_t(clen);
         }
@@ -73,7 +82,8 @@ __global__ __launch_bounds__(64) void search_locate_kernel(const uint8_t* __rest
 }
 
 // The plan of both searches.  The table sets of a handle: one for a stream's inline tables, up to kSidecarMaxConfigs for an attached sidecar;
-// set c's table of chunk k is tabs[c * nck + k], its bytes lie at base + off (base: the stream, or the sidecar).  pats[p * sets.n + c] is
+// set c's table of chunk k is tabs[c * nck + k], its bytes lie at base + off (base: the stream, or the sidecar), those of an expanded
+// compressed table (pad = kSearchTabArena) at arena + off.  pats[p * sets.n + c] is
 // pattern p as set c sees it (nw = 0: the set cannot serve the pattern; L is set in every record).
 // ov[c]: search_chunk_candidate's ov, a sidecar set's overlap (0 for inline tables).
 struct SearchPlanSets { uint32_t n, B[kSidecarMaxConfigs], ov[kSidecarMaxConfigs]; };
@@ -83,7 +93,7 @@ struct SearchPlanSets { uint32_t n, B[kSidecarMaxConfigs], ov[kSidecarMaxConfigs
 // chunk's), their conjunction, and the marking (search_decoded_mark_all) ORed into take[].  A lane loops over the sets: there are four at the
 // most, and the conjunction wants all votes of a (chunk, pattern) in one place.
 template <bool kFold>
-__global__ __launch_bounds__(256) void search_plan_kernel(const uint8_t* __restrict__ base, const SearchTab* __restrict__ tabs, const uint64_t* __restrict__ n_of, uint32_t nck,
+__global__ __launch_bounds__(256) void search_plan_kernel(const uint8_t* __restrict__ base, const uint8_t* __restrict__ arena, const SearchTab* __restrict__ tabs, const uint64_t* __restrict__ n_of, uint32_t nck,
                                                           SearchPlanSets sets, const uint32_t* __restrict__ hashes, const uint32_t* __restrict__ voff,
                                                           const SearchManyPat* __restrict__ pats, uint32_t np, uint8_t* __restrict__ take) {
     const uint64_t idx = uint64_t(blockIdx.x) * 256 + threadIdx.x;
@@ -99,8 +109,9 @@ __global__ __launch_bounds__(256) void search_plan_kernel(const uint8_t* __restr
             const SearchTab t = tabs[size_t(c) * nck + j];
             uint32_t a = pt.nw, s = pt.nw;
             if (t.R != kSearchNoTable) {
-                if (kFold) search_probe_fold(base + t.off, sets.B[c] - t.R, voff + pt.h_off, hashes, pt.nw, &a, &s, pt.gsize);
-                else search_probe(base + t.off, sets.B[c] - t.R, h, pt.nw, &a, &s, pt.gsize);
+                const uint8_t* bits = (t.pad ? arena : base) + t.off;
+                if (kFold) search_probe_fold(bits, sets.B[c] - t.R, voff + pt.h_off, hashes, pt.nw, &a, &s, pt.gsize);
+                else search_probe(bits, sets.B[c] - t.R, h, pt.nw, &a, &s, pt.gsize);
             }
             return lead ? a : s;
         };
@@ -214,16 +225,19 @@ int64_t dev_reader_search_tables(mlz_dev_reader* rd, hipStream_t sm, bool ignore
         st.ncfg = h_info->ok ? 1 : 0;
         st.cfg[0] = *h_info;
         st.base = rd->d_src;
-        if (ignore_crc || !st.ncfg) break;
+        if (!st.ncfg) break;
+        bool again = false;
+        if ((r = cst_resolve(c, sm, rd->d_src, &st, &st.tabs, nck, ignore_crc, &skip, &again, st.d_tabs))) return r;   // the compressed tables: expanded, or skipped
+        if (again) continue;
+        if (ignore_crc) break;
         std::vector<mlz_block_desc> desc;
         std::vector<size_t> who;
         for (size_t k = 0; k < nck; k++)
-            if (st.tabs[k].R != mlz::kSearchNoTable) { desc.push_back(mlz_block_desc{st.tabs[k].off, st.tabs[k].bytes, 0, 0}); who.push_back(k); }
+            if (st.tabs[k].R != mlz::kSearchNoTable && !st.tabs[k].pad) { desc.push_back(mlz_block_desc{st.tabs[k].off, st.tabs[k].bytes, 0, 0}); who.push_back(k); }
         if (desc.empty()) break;
         r = crc_device_locked(c, sm, rd->d_src, desc.data(), int(desc.size()), d_crc);
         if (r) return r;
         if ((r = fetch(c, sm, h_crc, d_crc, desc.size() * 4))) return r;
-        bool again = false;
         for (size_t i = 0; i < who.size(); i++)
             if (h_crc[i] != st.tabs[who[i]].crc) { skip[who[i]]++; again = true; }   // a broken table: the next one that fits, if there is one
         if (!again) break;
@@ -261,13 +275,20 @@ int64_t dev_reader_search_plan(mlz_dev_reader* rd, hipStream_t sm, uint32_t flag
         const int64_t r = dev_reader_search_sets(rd, sm, ignore_crc, &stp);
         if (r) return r;
         const mlz_dev_reader::SearchTables& st = *stp;
-        auto usable_of = [&](uint32_t serving /* a bit per set */) {
-            size_t u = 0;
+        auto usable_of = [&](uint32_t serving /* a bit per set */, size_t* compressed = nullptr) {   // *compressed: those with a table that came from a 0x46 chunk
+            size_t u = 0, uc = 0;
             for (size_t k = 0; k < nck; k++) {
-                bool any = false;
-                for (uint32_t s = 0; s < st.ncfg; s++) any = any || (((serving >> s) & 1) && st.tabs[s * nck + k].R != mlz::kSearchNoTable);
+                bool any = false, anyc = false;
+                for (uint32_t s = 0; s < st.ncfg; s++) {
+                    const mlz::SearchTab& t = st.tabs[s * nck + k];
+                    const bool use = ((serving >> s) & 1) && t.R != mlz::kSearchNoTable;
+                    any = any || use;
+                    anyc = anyc || (use && t.pad);
+                }
                 u += any ? 1 : 0;
+                uc += anyc ? 1 : 0;
             }
+            if (compressed) *compressed = uc;
             return u;
         };
         if (st.ncfg && usable_of((1u << st.ncfg) - 1)) {
@@ -301,11 +322,12 @@ int64_t dev_reader_search_plan(mlz_dev_reader* rd, hipStream_t sm, uint32_t flag
                 serving |= mine;
                 served += any ? 1 : 0;
             }
-            const size_t usable = usable_of(serving);
+            size_t usable_compressed = 0;
+            const size_t usable = usable_of(serving, &usable_compressed);
             // (a pattern whose serving sets hold no table at all is one the tables cannot serve)
             if (!usable) served = 0;
             unserved = n - served;
-            if (served) c->search_tables = usable;
+            if (served) { c->search_tables = usable; c->search_compressed = usable_compressed; }
             if (unserved == 0) {
                 // hashes, pattern records and the chunks' sizes go up as one block, staged in the pinned buffer; one byte per chunk comes back
                 Carve up;
@@ -338,6 +360,7 @@ int64_t dev_reader_search_plan(mlz_dev_reader* rd, hipStream_t sm, uint32_t flag
                 HIPCHK(c, hipMemsetAsync(d_take, 0, nck, sm));
                 const uint64_t lanes = uint64_t(nck) * n;
                 hipLaunchKernelGGL(fold ? mlz::search_plan_kernel<true> : mlz::search_plan_kernel<false>, dim3(uint32_t((lanes + 255) / 256)), dim3(256), 0, sm, st.base,
+                                   static_cast<const uint8_t*>(st.d_arena),
                                    static_cast<const mlz::SearchTab*>(st.d_tabs), u_n.at(ws), uint32_t(nck), sets, u_hs.at(ws), fold ? u_voff.at(ws) : static_cast<const uint32_t*>(nullptr),
                                    u_pats.at(ws), uint32_t(n), d_take);
                 if ((e = fetch(c, sm, c->pinned2, d_take, nck))) return e;   // (behind the upload on sm: the staged block has left the pinned buffer)
@@ -418,9 +441,9 @@ int64_t search_decode_run(mlz_ctx* c, const uint8_t* d_src, const std::vector<St
     }, per_job);
 }
 
-// The opening of both searches: counters 10 and 11 cleared, stats = {data chunks, 0, 0, 0}
+// The opening of both searches: counters 10, 11 and 14 cleared, stats = {data chunks, 0, 0, 0}
 void search_begin(mlz_dev_reader* rd, uint64_t* stats) {
-    rd->ctx->search_chunks = rd->ctx->search_tables = 0;
+    rd->ctx->search_chunks = rd->ctx->search_tables = rd->ctx->search_compressed = 0;
     if (stats) { stats[0] = rd->chunks.size(); stats[1] = stats[2] = stats[3] = 0; }
 }
 

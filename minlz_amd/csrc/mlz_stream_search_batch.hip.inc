@@ -139,7 +139,7 @@ int64_t stream_search_batch_locked(mlz_ctx* c, hipStream_t sm, uint32_t flags, c
     int r = stream_batch_walk(c, sm, d_src, streams, n, &bw);
     if (r) return r;
     begin_decode_call(c);
-    c->search_chunks = c->search_tables = 0;
+    c->search_chunks = c->search_tables = c->search_compressed = 0;
     SearchManyScan scan;
     scan.prepare(flags, patterns, pattern_len, np);
     // a stream with a framing error keeps the walk's code, and nothing of it is searched

@@ -82,7 +82,7 @@ __global__ __launch_bounds__(64) void sidecar_info_kernel(const uint8_t* __restr
     uint32_t n = 0;
     for (uint32_t i = 0; i < ns && n < kSidecarMaxConfigs; i++) {
         const uint8_t type = uint8_t(rec[i].tl >> 24);
-        if (type == kChunkSearchTable || type == kChunkRemoteRef) break;
+        if (type == kChunkSearchTable || type == kChunkSearchTableCompressed || type == kChunkRemoteRef) break;
         if (type != kChunkSearchInfo || (rec[i].flags & (kWalkTrunc | kWalkStub))) continue;
         SearchConfig& o = out[n];   // (filled in place: the field is too large for registers)
         if (search_info(side + rec[i].off + 4, rec[i].tl & 0xffffffu, &o.T, &o.M, &o.B, o.field)) { o.ok = 1; n++; }
@@ -124,9 +124,20 @@ __global__ __launch_bounds__(64) void sidecar_attach_kernel(const uint8_t* __res
         const SearchConfig& cf = cfg[c];
         uint32_t left = skip[size_t(c) * nck + size_t(k)];
         for (uint32_t t = j; t < i; t++) {
-            if (uint8_t(rec[t].tl >> 24) != kChunkSearchTable || (rec[t].flags & (kWalkTrunc | kWalkStub))) continue;
+            const uint8_t type = uint8_t(rec[t].tl >> 24);
+            if ((type != kChunkSearchTable && type != kChunkSearchTableCompressed) || (rec[t].flags & (kWalkTrunc | kWalkStub))) continue;
             const uint32_t clen = rec[t].tl & 0xffffffu;
             const uint8_t* p = side + rec[t].off + 4;
+            if (type == kChunkSearchTableCompressed) {   // a candidate for cst_resolve, as search_locate_kernel takes it
+                const int R = cst_fixed_fields(p, clen, cf.M, cf.B, cf.T, cf.field);
+                if (R >= 0 && left-- == 0) {
+                    const uint8_t* q = p + 4 + search_field_len(cf.T, cf.field);
+                    tabs[size_t(c) * nck + size_t(k)] =
+                        SearchTab{rec[t].off + 4, clen, uint32_t(R), uint32_t(q[0]) | uint32_t(q[1]) << 8 | uint32_t(q[2]) << 16 | uint32_t(q[3]) << 24, kSearchTabArena};
+                    break;
+                }
+                continue;
+            }
             const int R = search_table_reductions(p, clen, cf.M, cf.B, cf.T, cf.field);
             if (R >= 0 && left-- == 0) {
                 const uint32_t f = search_field_len(cf.T, cf.field);
@@ -408,16 +419,22 @@ int64_t dev_reader_attach_sidecar_locked(mlz_dev_reader* rd, hipStream_t sm, boo
         if ((e = fetch(c, sm, h_cfg + kMaxCfg, d_err, 4))) return e;
         if (*reinterpret_cast<const uint32_t*>(h_cfg + kMaxCfg)) return -MLZ_ERR_CORRUPT;
         out->tabs.assign(h_tabs, h_tabs + size_t(ncfg) * nck);
-        if (ignore_crc || !ncfg) break;
+        if (!ncfg) break;
+        bool again = false;
+        if (nck) {   // the compressed tables: expanded, or skipped
+            const int x = cst_resolve(c, sm, d_side, out, &out->tabs, nck, ignore_crc, &skip, &again, out->d_tabs);
+            if (x) return x;
+        }
+        if (again) continue;
+        if (ignore_crc) break;
         std::vector<mlz_block_desc> desc;
         std::vector<size_t> who;
         for (size_t t = 0; t < out->tabs.size(); t++)
-            if (out->tabs[t].R != mlz::kSearchNoTable) { desc.push_back(mlz_block_desc{out->tabs[t].off, out->tabs[t].bytes, 0, 0}); who.push_back(t); }
+            if (out->tabs[t].R != mlz::kSearchNoTable && !out->tabs[t].pad) { desc.push_back(mlz_block_desc{out->tabs[t].off, out->tabs[t].bytes, 0, 0}); who.push_back(t); }
         if (desc.empty()) break;
         int r = crc_device_locked(c, sm, d_side, desc.data(), int(desc.size()), d_crc);
         if (r) return r;
         if ((r = fetch(c, sm, h_crc, d_crc, desc.size() * 4))) return r;
-        bool again = false;
         for (size_t i = 0; i < who.size(); i++)
             if (h_crc[i] != out->tabs[who[i]].crc) { skip[who[i]]++; again = true; }   // a broken table: the next one that fits, if there is one
         if (!again) break;
@@ -458,7 +475,7 @@ int64_t mlz_dev_reader_attach_sidecar(mlz_dev_reader* rd, void* stream, uint32_t
     std::lock_guard<std::mutex> lk(c->mu);
     if (enter_device(c)) return -MLZ_ERR_HIP;
     if (!d_side) {   // detach: the handle searches by its inline tables again
-        if (rd->side.d_tabs) (void)hipFree(rd->side.d_tabs);
+        search_tables_release(&rd->side);
         rd->side = mlz_dev_reader::SearchTables{};
         rd->side_on = false;
         return 0;
@@ -468,10 +485,10 @@ int64_t mlz_dev_reader_attach_sidecar(mlz_dev_reader* rd, void* stream, uint32_t
     mlz_dev_reader::SearchTables fresh;
     const int64_t r = settled(sm, dev_reader_attach_sidecar_locked(rd, sm, (flags & MLZ_STREAM_IGNORE_CRC) != 0, d_side, n_side, &fresh));
     if (r < 0) {   // nothing is attached: the handle keeps what it had
-        if (fresh.d_tabs) (void)hipFree(fresh.d_tabs);
+        search_tables_release(&fresh);
         return r;
     }
-    if (rd->side.d_tabs) (void)hipFree(rd->side.d_tabs);
+    search_tables_release(&rd->side);
     rd->side = std::move(fresh);
     rd->side_on = true;
     return 0;

@@ -51,7 +51,7 @@ MLZ_WALK_HD int walk_uvarint(const uint8_t* b, size_t n, uint64_t* out) {
 MLZ_WALK_HD bool walk_skippable(uint8_t type, uint64_t clen, uint64_t left /* bytes behind the header */) { return type > 0x3f && type != 0xff && left >= clen; }
 
 // A sidecar's info, table and reference chunks: skippable, but the walk of a sidecar keeps them
-MLZ_WALK_HD bool walk_search_chunk(uint8_t type) { return type == 0x44 || type == 0x45 || type == 0x47; }
+MLZ_WALK_HD bool walk_search_chunk(uint8_t type) { return type == 0x44 || type == 0x45 || type == 0x46 || type == 0x47; }
 
 // The 4-byte header of the chunk at p (p + 4 <= n): the length of what follows; *type: the chunk's type
 MLZ_WALK_HD uint32_t walk_header(const uint8_t* src, uint64_t p, uint8_t* type) {

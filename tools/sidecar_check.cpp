@@ -8,8 +8,8 @@
 //   kind 4  u64 sidecar bytes, main stream bytes; u32 L, flags; the sidecar; the main stream; the pattern
 //           -> "error" for a sidecar the attach refuses, else "n_sets usable :" and the decoded set of a search for the pattern, with
 //           the attach done as sidecar_info_kernel and sidecar_attach_kernel do it (the configurations from the head of the chunk list,
-//           sidecar_check_refs per 0x47 against the main stream's data chunks, per configuration the first fitting 0x45 in front of it with a
-//           good CRC) and the plan as search_plan_kernel does it.  flags: 2 = MLZ_STREAM_IGNORE_CRC.  Both streams are well framed (the
+//           sidecar_check_refs per 0x47 against the main stream's data chunks, per configuration the first fitting 0x45 or 0x46 in front of it
+//           with a good CRC, a 0x46 table expanded by the rules of mlz_search_compressed.h) and the plan as search_plan_kernel does it.  flags: 2 = MLZ_STREAM_IGNORE_CRC.  Both streams are well framed (the
 //           walk's own errors are the walk's to check: tools/stream_walk_check.cpp).
 #include <cstdio>
 #include <cstdlib>
@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../minlz_amd/csrc/mlz_stream_search.h"
+#include "../minlz_amd/csrc/mlz_search_compressed.h"
 
 namespace {
 
@@ -87,7 +88,7 @@ void run_attach(const uint8_t* side, uint64_t ns, const uint8_t* mainb, uint64_t
     // sidecar_info_kernel
     std::vector<mlz::SearchConfig> cfg;
     for (const Chunk& c : rec) {
-        if (c.type == mlz::kChunkSearchTable || c.type == mlz::kChunkRemoteRef || cfg.size() == mlz::kSidecarMaxConfigs) break;
+        if (c.type == mlz::kChunkSearchTable || c.type == mlz::kChunkSearchTableCompressed || c.type == mlz::kChunkRemoteRef || cfg.size() == mlz::kSidecarMaxConfigs) break;
         if (c.type != mlz::kChunkSearchInfo) continue;
         mlz::SearchConfig o{};
         if (mlz::search_info(side + c.off + 4, c.clen, &o.T, &o.M, &o.B, o.field)) cfg.push_back(o);
@@ -95,6 +96,7 @@ void run_attach(const uint8_t* side, uint64_t ns, const uint8_t* mainb, uint64_t
     // sidecar_attach_kernel, with the CRC decided on the spot (the kernel's rounds pass over broken tables one by one: the same choice)
     const mlz::SearchTab none{0, 0, mlz::kSearchNoTable, 0, 0};
     std::vector<std::vector<mlz::SearchTab>> tabs(cfg.size(), std::vector<mlz::SearchTab>(nck, none));
+    std::vector<std::vector<std::vector<uint8_t>>> expanded(cfg.size(), std::vector<std::vector<uint8_t>>(nck));   // the bitmaps of 0x46 tables (the arena)
     bool bad = false;
     for (size_t i = 0; i < rec.size() && !bad; i++) {
         if (rec[i].type != mlz::kChunkRemoteRef) continue;
@@ -108,8 +110,25 @@ void run_attach(const uint8_t* side, uint64_t ns, const uint8_t* mainb, uint64_t
         if (k < 0) { bad = true; break; }
         for (size_t c = 0; c < cfg.size(); c++)
             for (size_t t = j; t < i; t++) {
-                if (rec[t].type != mlz::kChunkSearchTable) continue;
+                if (rec[t].type != mlz::kChunkSearchTable && rec[t].type != mlz::kChunkSearchTableCompressed) continue;
                 const uint8_t* p = side + rec[t].off + 4;
+                if (rec[t].type == mlz::kChunkSearchTableCompressed) {   // a candidate: expanded, or passed over (cst_settle)
+                    const int R = mlz::cst_fixed_fields(p, rec[t].clen, cfg[c].M, cfg[c].B, cfg[c].T, cfg[c].field);
+                    if (R < 0) continue;
+                    mlz::CstPlan plan;
+                    std::vector<uint8_t> bm(size_t(1) << (cfg[c].B - uint32_t(R) - 3));
+                    uint32_t stated = 0;
+                    std::memcpy(&stated, p + 4 + mlz::search_field_len(cfg[c].T, cfg[c].field), 4);
+                    std::vector<mlz::SearchTab> one{mlz::SearchTab{rec[t].off + 4, rec[t].clen, uint32_t(R), stated, mlz::kSearchTabArena}};
+                    const uint32_t good = mlz::cst_expand_host(p, rec[t].clen, bm.data(), bm.size(), &plan) == int64_t(bm.size()) ? 1 : 0;
+                    const uint32_t crc = good ? masked_crc(bm.data(), bm.size()) : 0;
+                    const uint64_t at = 0, size = bm.size();
+                    std::vector<uint32_t> skip(1, 0);
+                    if (mlz::cst_settle(&one, std::vector<size_t>{0}, &at, &size, &good, (flags & 2) ? nullptr : &crc, &skip)) continue;
+                    tabs[c][size_t(k)] = one[0];
+                    expanded[c][size_t(k)] = std::move(bm);
+                    break;
+                }
                 const int R = mlz::search_table_reductions(p, rec[t].clen, cfg[c].M, cfg[c].B, cfg[c].T, cfg[c].field);
                 if (R < 0) continue;
                 const uint32_t f = mlz::search_field_len(cfg[c].T, cfg[c].field);
@@ -138,7 +157,7 @@ void run_attach(const uint8_t* side, uint64_t ns, const uint8_t* mainb, uint64_t
         st.nw = pt.nw; st.t_min = pt.t_min; st.gsize = pt.gsize;
         st.a.assign(nck, pt.nw); st.s.assign(nck, pt.nw);
         for (size_t k = 0; k < nck; k++)
-            if (tabs[c][k].R != mlz::kSearchNoTable) mlz::search_probe(side + tabs[c][k].off, cfg[c].B - tabs[c][k].R, hs.data(), pt.nw, &st.a[k], &st.s[k], pt.gsize);
+            if (tabs[c][k].R != mlz::kSearchNoTable) mlz::search_probe(tabs[c][k].pad ? expanded[c][k].data() : side + tabs[c][k].off, cfg[c].B - tabs[c][k].R, hs.data(), pt.nw, &st.a[k], &st.s[k], pt.gsize);
     }
     size_t usable = 0;
     for (size_t k = 0; k < nck; k++) {

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../minlz_amd/csrc/mlz_stream_search.h"
+#include "../minlz_amd/csrc/mlz_search_compressed.h"
 
 namespace {
 
@@ -86,6 +87,7 @@ void run_stream(const uint8_t* s, uint64_t slen, const uint8_t* pat, uint32_t L,
     }
     // search_locate_kernel and the CRC rounds
     std::vector<mlz::SearchTab> tabs(nck, mlz::SearchTab{0, 0, mlz::kSearchNoTable, 0, 0});
+    std::vector<std::vector<uint8_t>> expanded(nck);   // the bitmaps of compressed tables (the handle's arena)
     size_t usable = 0;
     if (ok)
         for (size_t k = 0; k < nck; k++) {
@@ -100,6 +102,28 @@ void run_stream(const uint8_t* s, uint64_t slen, const uint8_t* pat, uint32_t L,
                     uint32_t crc = 0;
                     if (R >= 0) std::memcpy(&crc, s + p + 8 + f, 4);
                     if (R >= 0 && ((flags & 2) || masked_crc(s + p + 12 + f, clen - 8 - f) == crc)) { tabs[k] = mlz::SearchTab{p + 12 + f, clen - 8 - f, uint32_t(R), crc, 0}; usable++; break; }
+                } else if (type == mlz::kChunkSearchTableCompressed && p + 4 + clen <= limit) {
+                    // a compressed table: a candidate that cst_settle turns into a table in the arena, into no table (flags & 4: the arena
+                    // could not be allocated) or into one that is passed over (cst_resolve's rounds: the same choice, made on the spot)
+                    const int R = mlz::cst_fixed_fields(s + p + 4, clen, M, B, T, field);
+                    if (R >= 0) {
+                        mlz::CstPlan plan;
+                        std::vector<uint8_t> bm(size_t(1) << (B - uint32_t(R) - 3));
+                        const uint32_t f = mlz::search_field_len(T, field);
+                        uint32_t stated = 0;
+                        std::memcpy(&stated, s + p + 8 + f, 4);
+                        tabs[k] = mlz::SearchTab{p + 4, clen, uint32_t(R), stated, mlz::kSearchTabArena};
+                        const uint32_t good = mlz::cst_expand_host(s + p + 4, clen, bm.data(), bm.size(), &plan) == int64_t(bm.size()) ? 1 : 0;
+                        const uint32_t crc = good ? masked_crc(bm.data(), bm.size()) : 0;
+                        const uint64_t at = 0, size = bm.size();
+                        std::vector<uint32_t> skip(nck, 0);
+                        const bool again = mlz::cst_settle(&tabs, std::vector<size_t>{k}, &at, &size, (flags & 4) ? nullptr : &good, (flags & 2) ? nullptr : &crc, &skip);
+                        if (again) tabs[k] = mlz::SearchTab{0, 0, mlz::kSearchNoTable, 0, 0};
+                        else {
+                            if (tabs[k].R != mlz::kSearchNoTable) { expanded[k] = std::move(bm); usable++; }
+                            break;
+                        }
+                    }
                 }
                 p += 4 + uint64_t(clen);
             }
@@ -123,7 +147,7 @@ void run_stream(const uint8_t* s, uint64_t slen, const uint8_t* pat, uint32_t L,
         h[i] = mlz::search_hash(v, B, M);
     }
     for (size_t k = 0; k < nck; k++)
-        if (tabs[k].R != mlz::kSearchNoTable) mlz::search_probe(s + tabs[k].off, B - tabs[k].R, h.data(), nw, &a[k], &sv[k], gsize);
+        if (tabs[k].R != mlz::kSearchNoTable) mlz::search_probe(tabs[k].pad ? expanded[k].data() : s + tabs[k].off, B - tabs[k].R, h.data(), nw, &a[k], &sv[k], gsize);
     mlz::search_decoded_set(nck, [&](size_t k) { return a[k]; }, [&](size_t k) { return sv[k]; }, [&](size_t k) { return ck[k].n; }, nw, L, take.data(), t_min);
     if (long_kind) std::printf("%u %u %u %zu %u %u %u :", T, M, B, usable, nw, t_min, gsize);
     else if (prefix_kind) std::printf("%u %u %u %zu %u %u :", T, M, B, usable, nw, t_min);
