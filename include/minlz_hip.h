@@ -168,6 +168,11 @@ int mlz_crc_batch_device(mlz_ctx* ctx, void* stream, const uint8_t* d_base, cons
  * (byte prefixes) are configured with an mlz_search_tables through mlz_stream_encode_gather_device_tables. */
 #define MLZ_STREAM_SEARCH_TABLES 4u
 #define MLZ_STREAM_SEARCH_MATCH_LEN(m) ((uint32_t)(m) << 8) /* bits 8..11; 0 = the reference's default 6; 1..8 valid; 9..15: -MLZ_ERR_ARG */
+/* Compressed table chunks (0x46, SPEC_SEARCH.md 2.2) from the device-resident Writer: honoured by mlz_stream_encode_gather_device, _tables and
+ * _long_prefix, where it needs tables (-MLZ_ERR_ARG without a configuration), and by mlz_dev_reader_build_sidecar; accepted and without effect in
+ * mlz_stream_bound* (a 0x46 chunk is only written where it is smaller than the 0x45 chunk of the same table); without effect in mlz_stream_encode and
+ * mlz_stream_encode_batch_device, which write no tables.  See mlz_stream_encode_gather_device below and include/minlz_hip_search_compress.h. */
+#define MLZ_STREAM_SEARCH_COMPRESS (1u << 6)   /* 64u */
 int64_t mlz_stream_bound(uint64_t n, uint32_t block_size, uint32_t flags); /* dst_cap that always suffices */
 int64_t mlz_stream_encode(mlz_ctx* ctx, int level, uint32_t block_size, uint32_t flags, const uint8_t* src, size_t n, uint8_t* dst,
                           size_t dst_cap);
@@ -195,8 +200,15 @@ int64_t mlz_stream_decode(mlz_ctx* ctx, uint32_t flags, const uint8_t* src, size
  * 12 more bytes per block visit the host (table bytes or 0, R, CRC).  The seek index names a block by the offset at which its chunks start: its table chunk
  * when it has one.  mlz_stream_bound with the flag adds 7 + (12 + max(32, 2^(B - 3))) per block.  Without the flag every byte is what it was before the
  * flag existed.  Table type 4 (the long prefix) is written by mlz_stream_encode_gather_device_long_prefix below.  Tables for a stream that exists
- * already — any writer's — go into a sidecar: mlz_dev_reader_build_sidecar below.  Out of scope: WRITING compressed tables (0x46; the searches read them) and a Writer that emits a
- * sidecar while it encodes (the reference's WriterSidecar). */
+ * already — any writer's — go into a sidecar: mlz_dev_reader_build_sidecar below.
+ * MLZ_STREAM_SEARCH_COMPRESS (with any of the three table configurations): every table is also compressed on the device, by the rule of
+ * include/minlz_hip_search_compress.h (the reference's default writer without its shared tables and its skips), and its chunk is written as
+ * `46 len24 | the same fixed fields | h0_bs h0_tc | table descriptions | sub-blocks` where that is strictly smaller than the 0x45 chunk, that is where the
+ * section is shorter than the table; else the 0x45 chunk is written as without the flag.  A stream whose tables do not compress (tables of 512 bytes and
+ * below never did) is byte for byte the stream without the flag, and mlz_stream_bound* holds unchanged.  Payload stays on the device: 8 more bytes per
+ * table (the section's length) visit the host, in the read-back of the tables' CRCs.  mlz_get_counter(ctx, 15): the chunks the last call wrote as 0x46.
+ * Out of scope: tables shared between sub-blocks and the reference's popcount-band and minimum-size skips, and a Writer that emits a sidecar while it
+ * encodes (the reference's WriterSidecar). */
 int64_t mlz_stream_encode_gather_device(mlz_ctx* ctx, int level, uint32_t block_size, uint32_t flags, const uint8_t* const* d_src, const size_t* src_len,
                                         int n_ranges, uint8_t* d_dst, size_t dst_cap);
 
@@ -612,7 +624,8 @@ int64_t mlz_dev_reader_grep_records(mlz_dev_reader* reader, void* stream, uint32
  *   is built over the next chunk's bytes alone, so a configuration does not vote on a chunk that is followed by one with fewer bytes than its overlap
  *   (M - 1, M, or K - 1 + M + E for types 1, 2 and 3, 4): that chunk is decoded, and every position is returned as without a sidecar.  The third
  *   statistic counts the chunks with a usable table of at least one configuration that serves a pattern, the fourth the patterns no configuration serves.
- * Out of scope: writing compressed tables (0x46; build_sidecar emits 0x45), ExtractSidecar, the Writer-side sidecar, concatenated streams, sidecars read from host memory. */
+ * flags may hold MLZ_STREAM_SEARCH_COMPRESS: every table chunk is then written compressed (0x46) where that is strictly smaller, as the device Writer does it; the size returned, and
+ *   the one a capacity is checked against, are the real ones; mlz_get_counter(ctx, 15) counts the 0x46 chunks.  Out of scope: ExtractSidecar, the Writer-side sidecar, concatenated streams, sidecars read from host memory. */
 #define MLZ_SIDECAR_MAX_CONFIGS 4
 typedef struct {
     uint8_t table_type;   /* 1 .. 4 */

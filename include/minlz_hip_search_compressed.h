@@ -3,7 +3,8 @@
  *
  * The searches of minlz_hip.h read such tables by themselves: the first search on a handle (and mlz_dev_reader_attach_sidecar for a sidecar) expands every
  * fitting 0x46 table once into device memory the handle owns, and the plan then probes it like an uncompressed one.  mlz_get_counter(ctx, 14) reports, of
- * the chunks behind counter 11, those whose usable table came from a 0x46 chunk.  Writing 0x46 is out of scope: no Writer here emits it.
+ * the chunks behind counter 11, those whose usable table came from a 0x46 chunk.  The write side is minlz_hip_search_compress.h: the device Writer and build_sidecar emit
+ * 0x46 chunks under MLZ_STREAM_SEARCH_COMPRESS, and two calls compress single bitmaps.
  *
  * The one call of this header is the same expansion on the host, for a client that holds a table chunk in host memory. */
 #ifndef MINLZ_HIP_SEARCH_COMPRESSED_H

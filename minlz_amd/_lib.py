@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension headers include/minlz_hip_search_batch.h, include/minlz_hip_stream_set.h, include/minlz_hip_regex.h and include/minlz_hip_search_compressed.h.
+"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension headers include/minlz_hip_search_batch.h, include/minlz_hip_stream_set.h, include/minlz_hip_regex.h, include/minlz_hip_search_compressed.h and include/minlz_hip_search_compress.h.
 
 There is no CPU fallback here: if libminlz_hip.so is missing or HIP is unavailable, calls raise.
 """
@@ -127,11 +127,17 @@ ABI_EXT = {
     "minlz_hip_search_compressed.h": {
         "mlz_search_table_expand": (i64, [vp, sz, vp, sz, P(u32), u32]),
     },
+    "minlz_hip_search_compress.h": {
+        "mlz_search_bitmap_compress": (i64, [vp, sz, vp, sz]),
+        "mlz_search_bitmaps_compress_device": (i32, [vp, vp, vp, vp, P(BlockDesc), i32, vp]),
+    },
 }
 
 # mlz_get_counter(ctx, 14): of the chunks with a usable search table in the last search (counter 11), those whose table came from a compressed
 # table chunk, 0x46 (api.Context.search_compressed_tables; the names of the counters 0 .. 12 stand in api)
 COUNTER_SEARCH_COMPRESSED = 14
+# mlz_get_counter(ctx, 15): table chunks the last device Writer or build_sidecar call wrote compressed, as 0x46 (api.Context.tables_written_compressed)
+COUNTER_TABLES_COMPRESSED = 15
 
 _lib = None
 

@@ -15,6 +15,7 @@ ERR_CORRUPT, ERR_TOO_LARGE, ERR_UNSUPPORTED, ERR_INVALID_LEVEL, ERR_CRC, ERR_DST
 
 STREAM_ADD_INDEX, STREAM_IGNORE_CRC, STREAM_SEARCH_TABLES, SEARCH_NO_TABLES, GREP_INVERT = 1, 2, 4, 8, 16
 IGNORE_CASE = 32                  # MLZ_SEARCH_IGNORE_CASE: the searches' ignore_case=True
+COMPRESS_TABLES = 64              # MLZ_STREAM_SEARCH_COMPRESS: the device Writer's search_compress=True
 SEARCH_MAX_PATTERNS = 4096
 REGEX_IGNORE_CASE = 1             # MLZ_REGEX_IGNORE_CASE (include/minlz_hip_regex.h): Regex(..., ignore_case=True)
 REGEX_MAX_RECORD = 1 << 20        # MLZ_REGEX_MAX_RECORD: the longest record grep_regex accepts
@@ -261,6 +262,11 @@ class Context:
         (mlz_get_counter 14)."""
         return self.counter(_lib.COUNTER_SEARCH_COMPRESSED)
 
+    @property
+    def tables_written_compressed(self):
+        """Table chunks the context's last stream_encode_gather_device or build_sidecar wrote compressed, as 0x46 (mlz_get_counter 15)."""
+        return self.counter(_lib.COUNTER_TABLES_COMPRESSED)
+
     def range_plan_host_bytes(self):
         """Bytes of plan data that crossed between host and device, both directions together, in the context's last DeviceReader.read_device
         (mlz_get_counter 9): a header and two records per TOUCHED CHUNK, nothing per range."""
@@ -271,7 +277,7 @@ class Context:
         self._call("mlz_release_stream", stream)
 
     def stream_encode_gather_device(self, level, block_size, add_index, d_srcs, lens, d_dst, dst_cap, search_match_len=None, search_prefix=None,
-                                    search_long_prefix=None, search_extras=0):
+                                    search_long_prefix=None, search_extras=0, search_compress=False):
         """mlz_stream_encode_gather_device: ranges of one stream resident on the context's devices -> the framed stream in d_dst (device memory).
         search_match_len: None = no search tables; 0 = block search tables with the reference's default match length (6); 1 .. 8 = with that one.
         search_prefix (with search_match_len): an iterable of byte values; the tables then index only the positions behind one of them
@@ -279,9 +285,12 @@ class Context:
         search_long_prefix (with search_match_len, not with search_prefix): 1 .. 256 bytes; the tables then index the search_extras + 1
         windows behind every occurrence of that byte string (mlz_stream_encode_gather_device_long_prefix, table type 4; search_extras 0 .. 15,
         match length + extras <= 16).
+        search_compress (MLZ_STREAM_SEARCH_COMPRESS, with any of these tables): a table's chunk is written compressed (0x46) where that is
+        smaller; the property tables_written_compressed then says how many were.
         Returns the stream size."""
         n = len(d_srcs)
         suffix, flags, cfg = _writer_tables(search_match_len, search_prefix, search_long_prefix, search_extras)
+        flags |= COMPRESS_TABLES if search_compress else 0
         return self._call("mlz_stream_encode_gather_device" + suffix, level, block_size, _flags(add_index=add_index) | flags, *cfg,
                           (C.c_void_p * n)(*d_srcs), (C.c_size_t * n)(*lens), n, d_dst, dst_cap)
 
@@ -304,6 +313,13 @@ class Context:
         r = _lib.lib().mlz_decode_batch_device(self.handle, stream, d_src, d_dst, arr, len(arr), d_out_len)
         if r:
             _raise(r, self)
+
+    def search_bitmaps_compress_device(self, d_src, d_dst, descs, d_len, stream=None):
+        """mlz_search_bitmaps_compress_device (include/minlz_hip_search_compress.h): every bitmap (src_off, src_len, dst_off, dst_cap) of the
+        buffer at d_src -> the huff0 section of its compressed chunk at its place in the buffer at d_dst, by kernels; d_len: device memory
+        of one int64 per item, which receives the section's length or the item's own -MLZ_ERR_*.  Returns when the kernels have run."""
+        arr = _block_descs(descs)
+        self._call("mlz_search_bitmaps_compress_device", stream, d_src, d_dst, arr, len(arr), d_len)
 
     def stream_decoded_len_device(self, d_src, n, stream=None):
         """mlz_stream_decoded_len_device: the chunk walk of a stream in device memory -> (result, prefix_len).  `result` is the raw return
@@ -563,10 +579,11 @@ class DeviceReader:
         """mlz_dev_reader_sidecar_bound: room that always suffices for build_sidecar with these configurations (api.search_config)."""
         return self._call("mlz_dev_reader_sidecar_bound", *self._configs(cfgs))
 
-    def build_sidecar(self, cfgs, d_dst, cap, ignore_crc=False, stream=None):
+    def build_sidecar(self, cfgs, d_dst, cap, ignore_crc=False, stream=None, compress=False):
         """mlz_dev_reader_build_sidecar: the sidecar of this stream for 1 .. 4 configurations (api.search_config) — search tables for every
-        data chunk in a separate stream that names the chunks by remote references — into `cap` bytes at device address d_dst -> its size."""
-        return self._call("mlz_dev_reader_build_sidecar", stream, _flags(ignore_crc=ignore_crc), *self._configs(cfgs), d_dst, cap)
+        data chunk in a separate stream that names the chunks by remote references — into `cap` bytes at device address d_dst -> its size.
+        compress (MLZ_STREAM_SEARCH_COMPRESS): a table's chunk is written compressed (0x46) where that is smaller."""
+        return self._call("mlz_dev_reader_build_sidecar", stream, _flags(ignore_crc=ignore_crc) | (COMPRESS_TABLES if compress else 0), *self._configs(cfgs), d_dst, cap)
 
     def attach_sidecar(self, d_side, n, ignore_crc=False, stream=None):
         """mlz_dev_reader_attach_sidecar: search and search_many use the tables of the sidecar at device address d_side (n bytes) from now
@@ -704,6 +721,19 @@ def expand_search_table(body, ignore_crc=False):
     return int(R.value), out[:r].tobytes()
 
 
+def compress_search_bitmap(bitmap, cap=None):
+    """mlz_search_bitmap_compress (include/minlz_hip_search_compress.h): a search table's bitmap (a power of two of 32 bytes to 1 MiB) -> the
+    huff0 section of its compressed chunk (0x46): `h0_bs h0_tc | table descriptions | sub-blocks`, what stands behind the CRC.  On the
+    host; needs no context and no GPU.  cap: the room offered (default: the largest section, n + 18).  A refused size raises MinLZError
+    (code ERR_ARG), a cap below the section's length MinLZError (code ERR_DST_TOO_SMALL)."""
+    a = _np(bitmap)
+    out = np.empty(a.size + 18 if cap is None else max(int(cap), 1), dtype=np.uint8)
+    r = _lib.lib().mlz_search_bitmap_compress(_ptr(a), a.size, out.ctypes.data, out.size if cap is None else int(cap))
+    if r < 0:
+        _raise(r)
+    return out[:r].tobytes()
+
+
 def encode_block(src, level=LevelFastest, ctx=None):
     """encodeBlock(dst, src) / WriterCustomEncoder contract (writer.go:1293-1304): tokens only; b'' = incompressible."""
     a = _np(src)
@@ -833,10 +863,12 @@ def _writer_tables(search_match_len, search_prefix, search_long_prefix, search_e
     return "", 0 if search_match_len is None else STREAM_SEARCH_TABLES | (search_match_len & 15) << 8, ()
 
 
-def stream_bound(n, block_size, add_index=False, search_match_len=None, search_prefix=None, search_long_prefix=None, search_extras=0):
+def stream_bound(n, block_size, add_index=False, search_match_len=None, search_prefix=None, search_long_prefix=None, search_extras=0, search_compress=False):
     """mlz_stream_bound, _tables or _long_prefix: the room that always suffices for a stream of n bytes written with these settings (the
-    search keywords are Context.stream_encode_gather_device's).  Host only; raises for a block size or a configuration the Writer refuses."""
+    search keywords are Context.stream_encode_gather_device's; search_compress changes nothing: a compressed table chunk is only written
+    where it is smaller).  Host only; raises for a block size or a configuration the Writer refuses."""
     suffix, flags, cfg = _writer_tables(search_match_len, search_prefix, search_long_prefix, search_extras)
+    flags |= COMPRESS_TABLES if search_compress else 0
     r = getattr(_lib.lib(), "mlz_stream_bound" + suffix)(n, block_size, _flags(add_index=add_index) | flags, *cfg)
     if r < 0:
         _raise(r)

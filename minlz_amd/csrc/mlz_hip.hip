@@ -20,6 +20,7 @@
 #include "../../include/minlz_hip_search_batch.h"
 #include "../../include/minlz_hip_stream_set.h"
 #include "../../include/minlz_hip_search_compressed.h"
+#include "../../include/minlz_hip_search_compress.h"
 #include "mlz_format.h"
 #include "mlz_kernels.h"
 
@@ -145,6 +146,12 @@ struct mlz_ctx {
     // encode workspace
     DevBuf d_scratch, d_tile_size, d_tile_out, d_flags, d_far, d_recs, d_piece_cnt, d_farbin;
     DevBuf d_stab;               // the device-resident Writer's block search tables: 2^(B - 3) bytes per block of a range, 8 bytes of verdict each
+    // compressed search tables, the write side (mlz_search_tables_compress.hip.inc): the kernels' records, codes and descriptions, and the host's
+    // item and job lists, which outlive the launches of a call that synchronises later
+    DevBuf d_cstw;
+    std::vector<mlz::CstwItem> h_cstw_items;
+    std::vector<mlz::CstwJob> h_cstw_jobs;
+    uint64_t tables_compressed = 0;   // table chunks the last device Writer or sidecar build call wrote as 0x46 (mlz_get_counter 15)
     // decode workspace
     DevBuf d_dec, d_idx;
     DevBuf d_walk, d_walk_tab;   // the device-resident Reader's chunk walk: exit tables (8 bytes per stream byte) and the chunk table
@@ -193,7 +200,7 @@ struct mlz_ctx {
     DevBuf d_prof;
     // Every DevBuf above, once, by side: 0 = what mlz_get_counter 3 sums (encode), 1 = counter 4 (decode), 2 = the rest; mlz_destroy frees all three.  A buffer added to the struct is added here.
     std::vector<DevBuf*> bufs(int side) {
-        if (side == 0) return {&d_scratch, &d_tile_size, &d_tile_out, &d_flags, &d_far, &d_recs, &d_piece_cnt, &d_farbin, &d_stab};
+        if (side == 0) return {&d_scratch, &d_tile_size, &d_tile_out, &d_flags, &d_far, &d_recs, &d_piece_cnt, &d_farbin, &d_stab, &d_cstw};
         if (side == 1) return {&d_dec, &d_idx, &d_walk, &d_walk_tab, &d_batch, &d_range, &d_rplan, &d_records, &d_rwin};
         return {&d_blocks_k[0], &d_blocks_k[1], &d_tile_block_k[0], &d_tile_block_k[1], &d_seg_block_k[0], &d_seg_block_k[1], &d_place, &d_batch_desc, &d_gen_acc, &d_in, &d_out, &d_len, &d_crc, &d_crc_tabs, &d_crc_tiles, &d_prof};
     }
@@ -1259,6 +1266,7 @@ int64_t mlz_get_counter(mlz_ctx* c, int which) {
     if (which == 12) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->batch_long); }
     if (which == 13) { std::lock_guard<std::mutex> lk(c->mu); return c->acc_call == c->dec_call ? int64_t(c->l0_launches) : 0; }   // groups of the last decode call that took dec_level0_kernel's launch
     if (which == 14) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->search_compressed); }
+    if (which == 15) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->tables_compressed); }
     if (which == 10 || which == 11) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(which == 10 ? c->search_chunks : c->search_tables); }
     std::lock_guard<std::mutex> lk(c->q_mu);
     return which == 0 ? int64_t(c->q_batches) : which == 1 ? int64_t(c->q_requests) : -MLZ_ERR_ARG;
@@ -1338,6 +1346,7 @@ int mlz_debug_idxprof(unsigned long long* out) {
 }  // extern "C"
 
 #include "mlz_search_tables.hip.inc"
+#include "mlz_search_tables_compress.hip.inc"
 #include "mlz_stream.hip.inc"
 #include "mlz_stream_walk.hip.inc"
 #include "mlz_stream_ranges.hip.inc"

@@ -9,6 +9,9 @@
 // table's layout and fill (cst_table_starts, cst_table_fill), one stream's decode loop (cst_decode_stream) and the sparse walk
 // (cst_sparse_decode).  Every read is bounded by the chunk body the caller names: a malformed chunk yields an error, or garbage inside its
 // own sub-block that the CRC then rejects, never a read outside [body, body + clen) or a write outside the sub-block.
+// Behind the read side stands the write side (cst_w_*, cst_compress_host): a bitmap -> its huff0 section by the model's default writer's
+// rule, shared by the host call mlz_search_bitmap_compress, the kernels of mlz_search_tables_compress.hip.inc and
+// tools/search_compress_check.cpp.
 // Plain C++: compiles for the host alone and for gfx950.  tests/search_compressed_model.py is the same format in Python.
 #pragma once
 #include <stddef.h>
@@ -387,6 +390,323 @@ inline int64_t cst_expand_host(const uint8_t* body, uint32_t clen, uint8_t* bitm
             }
     }
     return int64_t(plan->n);
+}
+
+// ---- the write side: a bitmap -> its huff0 section (`h0_bs h0_tc | table descriptions | sub-blocks`, what a 0x46 payload carries behind
+// the CRC).  The rule is tests/search_compressed_model.py's default writer, byte for byte: the partition cst_w_bs; per sub-block one byte
+// value -> RLE, else the smallest of raw (sub), sparse (its bytes + 3) and huff (description + 9 + ceil(bits / 8) + 3), ties in that
+// order; a table of its own per tabled sub-block.  The host call (cst_compress_host), the kernels (mlz_search_tables_compress.hip.inc)
+// and tools/search_compress_check.cpp share what follows. ----
+
+// The partition: bitmaps up to 32 KiB are one sub-block; up to 512 KiB, 32 KiB sub-blocks; else 64 KiB ones.  n: a power of two
+MLZ_SEARCH_HD uint32_t cst_w_bs(uint32_t n) { return n <= (32u << 10) ? cst_highbit(n) : n <= (512u << 10) ? 15u : 16u; }
+MLZ_SEARCH_HD bool cst_w_size_ok(uint64_t n) { return n >= 32 && n <= (1u << 20) && !(n & (n - 1)); }
+// The longest section of an n-byte bitmap: every sub-block raw
+MLZ_SEARCH_HD uint32_t cst_w_bound(uint32_t n) { return n + 2 + kCstMaxSub; }
+
+// Code lengths.  Nodes are merged two at a time, the smallest first by (weight, smallest symbol in the node); where the tree is deeper
+// than 11 all counts are halved once more (max(1, count >> shift)) and the tree is built again.  A slot holds a live node: key =
+// weight << 8 | smallest symbol (weights are at most 2^16), ~0 for none; node ids 0 .. 255 are the symbols, 256 .. 510 the merges in the
+// order they were made, so that a parent's id is above its children's.
+struct CstHuffScratch { uint32_t key[256]; uint16_t node[256], parent[512]; uint8_t d[512]; };
+constexpr uint32_t kCstNoNode = 0xffffffffu;
+
+// The keys of a round: symbol s of the histogram under `shift`
+MLZ_SEARCH_HD uint32_t cst_w_key(uint32_t count, uint32_t shift, uint32_t s) {
+    if (!count) return kCstNoNode;
+    const uint32_t w = count >> shift;
+    return (w ? w : 1u) << 8 | s;
+}
+// Two nodes' keys -> their merge's
+MLZ_SEARCH_HD uint32_t cst_w_merge_key(uint32_t ka, uint32_t kb) {
+    const uint32_t sa = ka & 255, sb = kb & 255;
+    return ((ka >> 8) + (kb >> 8)) << 8 | (sa < sb ? sa : sb);
+}
+// parent[] of `nodes` ids (root = nodes - 1) -> depth[s] of the symbols with hist[s] > 0, 0 for the others.  Returns the largest depth.
+MLZ_SEARCH_HD uint32_t cst_w_depths(const uint32_t* hist, uint32_t nodes, CstHuffScratch* hs, uint8_t* depth) {
+    uint32_t deepest = 0;
+    hs->d[nodes - 1] = 0;
+    for (uint32_t id = nodes - 1; id-- > 0;) {
+        if (id < 256 && !hist[id]) { depth[id] = 0; continue; }
+        const uint32_t dd = hs->d[hs->parent[id]] + 1u;
+        hs->d[id] = uint8_t(dd);
+        if (id < 256) { depth[id] = uint8_t(dd); if (dd > deepest) deepest = dd; }
+    }
+    return deepest;
+}
+// hist[256] with at least two counts above 0 -> depth[256]; returns the table log (the deepest leaf, 1 .. 11); *out_shift: the halvings
+inline uint32_t cst_w_code_lengths(const uint32_t* hist, uint8_t* depth, CstHuffScratch* hs, uint32_t* out_shift) {
+    for (uint32_t shift = 0;; shift++) {
+        uint32_t live = 0, next = 256;
+        for (uint32_t s = 0; s < 256; s++) {
+            hs->key[s] = cst_w_key(hist[s], shift, s);
+            hs->node[s] = uint16_t(s);
+            live += hist[s] ? 1 : 0;
+        }
+        while (live > 1) {
+            uint32_t a = 0, b = 0, ka = kCstNoNode, kb = kCstNoNode;   // the smallest and the next
+            for (uint32_t s = 0; s < 256; s++) {
+                const uint32_t k = hs->key[s];
+                if (k < ka) { kb = ka; b = a; ka = k; a = s; }
+                else if (k < kb) { kb = k; b = s; }
+            }
+            hs->parent[hs->node[a]] = hs->parent[hs->node[b]] = uint16_t(next);
+            hs->key[a] = cst_w_merge_key(ka, kb);
+            hs->node[a] = uint16_t(next++);
+            hs->key[b] = kCstNoNode;
+            live--;
+        }
+        const uint32_t deepest = cst_w_depths(hist, next, hs, depth);
+        if (deepest <= kCstMaxTableLog) { if (out_shift) *out_shift = shift; return deepest; }
+    }
+}
+
+// depth[256], log -> w[256] (weight log + 1 - depth, 0 for an absent symbol) and the canonical codes: symbols by ascending weight, by
+// value within a weight; code[s] = code | length << 16.  Returns `last`, the largest present symbol: the description lists w[0, last).
+MLZ_SEARCH_HD uint32_t cst_w_codes(const uint8_t* depth, uint32_t log, uint8_t* w, uint32_t* code) {
+    uint32_t last = 0;
+    for (uint32_t s = 0; s < 256; s++) {
+        w[s] = depth[s] ? uint8_t(log + 1 - depth[s]) : 0;
+        code[s] = 0;
+        if (depth[s]) last = s;
+    }
+    uint32_t at = 0;
+    for (uint32_t wt = 1; wt <= log; wt++)
+        for (uint32_t s = 0; s < 256; s++)
+            if (w[s] == wt) { code[s] = (at >> (wt - 1)) | (log + 1 - wt) << 16; at += 1u << (wt - 1); }
+    return last;
+}
+
+// v's low k bits (k <= 16) at bit `pos` of a zeroed buffer, little-endian
+MLZ_SEARCH_HD void cst_w_put(uint8_t* buf, uint32_t pos, uint32_t v, uint32_t k) {
+    uint32_t x = (v & ((1u << k) - 1)) << (pos & 7);
+    for (uint32_t i = pos >> 3; x; i++, x >>= 8) buf[i] |= uint8_t(x);
+}
+
+// FSE-compressed weights: w[0, n), 2 <= n <= 255, each at most 11 -> out[0, return value), the model's fse_encode_weights: accuracy log
+// 6, counts c * 64 / n rounded and at least 1, the largest (the first of them) moved until they sum to 64; one value only: a second
+// symbol of probability 1 that never occurs; the two-state stream written from the decoder's last read up.  out: kCstFseOutCap bytes.
+constexpr uint32_t kCstFseOutCap = 256;   // a description of at most 13 counts (below 20 bytes) and at most 253 * 6 + 12 + 1 bits of stream
+MLZ_SEARCH_HD uint32_t cst_w_fse_weights(const uint8_t* w, uint32_t n, uint8_t* out, CstFseScratch* fs) {
+    if (n < 2) return 0;
+    const uint32_t log = kCstFseMaxLog, size = 1u << log;
+    uint32_t hist[kCstMaxWeight + 1], nsym = 0, present = 0, only = 0;
+    int norm[kCstMaxWeight + 2];
+    for (uint32_t i = 0; i <= kCstMaxWeight; i++) hist[i] = 0;
+    for (uint32_t i = 0; i < n; i++) { hist[w[i]]++; if (w[i] + 1u > nsym) nsym = w[i] + 1u; }
+    for (uint32_t i = 0; i < nsym; i++) if (hist[i]) { present++; only = i; }
+    for (uint32_t i = 0; i < kCstMaxWeight + 2; i++) norm[i] = 0;
+    if (present == 1) {
+        const uint32_t spare = only ? 0 : 1;
+        if (spare + 1 > nsym) nsym = spare + 1;
+        norm[only] = int(size) - 1;
+        norm[spare] = 1;
+    } else {
+        int sum = 0;
+        for (uint32_t i = 0; i < nsym; i++) {
+            if (hist[i]) { const uint32_t v = (hist[i] * size + n / 2) / n; norm[i] = v ? int(v) : 1; }
+            sum += norm[i];
+        }
+        while (sum != int(size)) {
+            uint32_t big = 0;
+            for (uint32_t i = 1; i < nsym; i++) if (norm[i] > norm[big]) big = i;
+            const int step = sum < int(size) ? 1 : -1;
+            norm[big] += step;
+            sum += step;
+        }
+    }
+    for (uint32_t i = 0; i < kCstFseOutCap; i++) out[i] = 0;
+    // the description
+    cst_w_put(out, 0, log - 5, 4);
+    uint32_t pos = 4, threshold = size, nb = log + 1, s = 0;
+    int remaining = int(size) + 1;
+    while (remaining > 1) {
+        int count = norm[s] + 1;
+        const int mx = int(2 * threshold) - 1 - remaining;
+        if (count >= int(threshold)) count += mx;
+        cst_w_put(out, pos, uint32_t(count), nb);
+        pos += count < mx ? nb - 1 : nb;
+        remaining -= norm[s];
+        while (remaining < int(threshold)) { nb--; threshold >>= 1; }
+        s++;
+        if (norm[s - 1] == 0 && remaining > 1) {
+            const uint32_t n0 = s;
+            while (s < nsym && norm[s] == 0) s++;
+            uint32_t run = s - n0;
+            while (run >= 3) { cst_w_put(out, pos, 3, 2); pos += 2; run -= 3; }
+            cst_w_put(out, pos, run, 2);
+            pos += 2;
+        }
+    }
+    const uint32_t used = (pos + 7) >> 3;
+    // The decode table's states as the reader builds them (no count is "less than one"): the spread, then per symbol its states in ascending
+    // order, list[cum[v] + k] the k-th of symbol v.  That state has x = norm[v] + k, reads log - highbit(x) bits and its range starts at
+    // (x << bits) - size: the ranges of a symbol's states tile 0 .. size - 1.
+    uint8_t *sym = fs->sym, *nxt = fs->nxt, *list = fs->nbits, *cum = fs->base;   // (nbits and base lend their bytes: size and 13 of them)
+    const uint32_t step = (size >> 1) + (size >> 3) + 3, mask = size - 1;
+    uint32_t at = 0, run = 0;
+    for (uint32_t i = 0; i < nsym; i++) {
+        cum[i] = uint8_t(run);
+        run += uint32_t(norm[i]);
+        nxt[i] = 0;
+        for (int k = 0; k < norm[i]; k++) { sym[at] = uint8_t(i); at = (at + step) & mask; }
+    }
+    for (uint32_t u = 0; u < size; u++) list[cum[sym[u]] + nxt[sym[u]]++] = uint8_t(u);
+    // the stream.  The decoder reads init(state 0), init(state 1), then the update behind weight 0, 1, ..., n - 3; written here from the
+    // last of these reads, which lies lowest.  A final state is the symbol's first state (the most bits, the first of them); an earlier
+    // one the symbol's state whose range holds the state that follows: with s = that state + size, x = s >> bits lies in [norm, 2 norm).
+    uint8_t* b = out + used;
+    uint32_t tot = 0, st[2] = {size, size};
+    for (uint32_t i = n; i-- > 0;) {
+        const uint32_t c = i & 1, v = w[i], cnt = uint32_t(norm[v]);
+        if (st[c] == size) { st[c] = list[cum[v]]; continue; }
+        const uint32_t s = st[c] + size;
+        uint32_t nb = log - cst_highbit(cnt), x = s >> nb;
+        if (x < cnt) { nb--; x = s >> nb; }
+        cst_w_put(b, tot, s - (x << nb), nb);
+        tot += nb;
+        st[c] = list[cum[v] + x - cnt];
+    }
+    cst_w_put(b, tot, st[1], log);
+    tot += log;
+    cst_w_put(b, tot, st[0], log);
+    tot += log;
+    cst_w_put(b, tot, 1, 1);
+    return used + ((tot + 8) >> 3);
+}
+
+// The description of w[0, last), last >= 1: direct 4-bit weights where last <= 128, FSE-compressed where that section has fewer than 128
+// bytes, the shorter of them, direct in a tie -> desc[0, return value), at most 129 bytes; 0 where neither form carries the weights.
+// desc: 1 + kCstFseOutCap bytes (the FSE section is written in place and kept or overwritten).
+MLZ_SEARCH_HD uint32_t cst_w_description(const uint8_t* w, uint32_t last, uint8_t* desc, CstFseScratch* fs) {
+    const uint32_t direct = last <= 128 ? 1 + (last + 1) / 2 : 0;
+    uint32_t fse = cst_w_fse_weights(w, last, desc + 1, fs);
+    fse = fse && fse < 128 ? fse + 1 : 0;
+    if (fse && (!direct || fse < direct)) { desc[0] = uint8_t(fse - 1); return fse; }
+    if (!direct) return 0;
+    desc[0] = uint8_t(127 + last);
+    for (uint32_t i = 0; i < (last + 1) / 2; i++) desc[1 + i] = uint8_t(w[2 * i] << 4 | (2 * i + 1 < last ? w[2 * i + 1] : 0));
+    return direct;
+}
+
+// The kind of a sub-block with more than one byte value: sparse_len = the sparse table's bytes; desc_len = 0: no description, huff is no
+// candidate; bits = the sum of the code lengths of its bytes.  -> kCstRaw, kCstSparse or 0 (a table of its own)
+MLZ_SEARCH_HD uint32_t cst_w_pick(uint32_t sub, uint32_t sparse_len, uint32_t desc_len, uint32_t bits) {
+    const uint32_t raw = sub, sparse = sparse_len + 3, huff = desc_len ? desc_len + 9 + (bits + 7) / 8 + 3 : 0xffffffffu;
+    if (raw <= sparse && raw <= huff) return kCstRaw;
+    return sparse <= huff ? kCstSparse : 0;
+}
+
+MLZ_SEARCH_HD uint32_t cst_w_uvarint_len(uint32_t v) { return v < 0x80 ? 1 : v < 0x4000 ? 2 : v < 0x200000 ? 3 : 4; }
+MLZ_SEARCH_HD uint32_t cst_w_put_uvarint(uint8_t* p, uint32_t v) {
+    uint32_t i = 0;
+    while (v >= 0x80) { p[i++] = uint8_t(v | 0x80); v >>= 7; }
+    p[i++] = uint8_t(v);
+    return i;
+}
+// The bytes a gap of `gap` zeros in front of a set bit takes in a sparse table: a 255 per full 255, then the rest
+MLZ_SEARCH_HD uint32_t cst_w_gap_bytes(uint32_t gap) { return gap / 255 + 1; }
+
+// One stream of a tabled sub-block: data[0, count) -> out[0, return value): the codes from the last symbol up, the first one just below
+// the end marker, little-endian.  out: count * 11 / 8 + 1 bytes at most
+inline uint32_t cst_w_encode_stream(const uint8_t* data, uint32_t count, const uint32_t* code, uint8_t* out) {
+    uint64_t acc = 0;
+    uint32_t nbit = 0, p = 0;
+    for (uint32_t i = count; i-- > 0;) {
+        const uint32_t c = code[data[i]];
+        acc |= uint64_t(c & 0xffff) << nbit;
+        nbit += c >> 16;
+        while (nbit >= 8) { out[p++] = uint8_t(acc); acc >>= 8; nbit -= 8; }
+    }
+    acc |= uint64_t(1) << nbit;
+    out[p++] = uint8_t(acc);
+    return p;
+}
+
+// The records of the kernels (mlz_search_tables_compress.hip.inc).  An item is a bitmap and its room; a job one of its sub-blocks
+struct CstwItem { uint64_t dst_off, dst_cap; uint32_t n, first_job, nsub, bs; };   // n = 0: a size that is refused
+struct CstwJob { uint64_t src_off; uint32_t item, sub; };                          // where the sub-block's bytes lie, 2^bs of them
+// What the plan leaves of a sub-block.  kind: kCstRaw, kCstRle, kCstSparse or 0 (a table of its own).  body_len: the whole record.
+// The layout kernel adds table, out_off and desc_off (places in the section).
+struct CstwRec { uint32_t kind, desc_len, body_len, rle, sparse_len, four_len, slen[4], table, out_off, desc_off, pad[3]; };
+constexpr uint32_t kCstwDescSlot = 144;      // a description's room in workspace (at most 129 bytes)
+
+// What the write side found on the way (tools/search_compress_check.cpp reports it)
+struct CstWriteStats { uint32_t raw, rle, sparse, huff, direct, fse, flattened, no_description; };
+
+// The whole compression in plain loops: bitmap[0, n), cst_w_size_ok(n) -> dst[0, return value), the section; -1 when cap is too small
+// (nothing useful is written).  Works in memory of its own (a section is at most cst_w_bound(n) bytes).
+inline int64_t cst_compress_host(const uint8_t* bitmap, uint32_t n, uint8_t* dst, size_t cap, CstWriteStats* stats = nullptr) {
+    const uint32_t bs = cst_w_bs(n), sub = 1u << bs, nsub = n >> bs;
+    std::vector<uint8_t> descs, recs, stream(size_t(sub / 4) * 11 / 8 + 8);
+    CstHuffScratch hs;
+    CstFseScratch fs;
+    uint8_t depth[256], w[256], desc[1 + kCstFseOutCap], uv[5];
+    uint32_t hist[256], code[256], tc = 0;
+    for (uint32_t j = 0; j < nsub; j++) {
+        const uint8_t* b = bitmap + size_t(j) * sub;
+        for (uint32_t s = 0; s < 256; s++) hist[s] = 0;
+        for (uint32_t i = 0; i < sub; i++) hist[b[i]]++;
+        if (hist[b[0]] == sub) {
+            recs.push_back(uint8_t(kCstRle));
+            recs.push_back(b[0]);
+            if (stats) stats->rle++;
+            continue;
+        }
+        uint32_t sparse_len = 0, prev = 0;   // prev: one behind the last set bit
+        for (uint32_t i = 0; i < sub; i++)
+            for (uint32_t v = b[i]; v; v &= v - 1) {
+                const uint32_t pos = 8 * i + uint32_t(__builtin_ctz(v));
+                sparse_len += cst_w_gap_bytes(pos - prev);
+                prev = pos + 1;
+            }
+        uint32_t shift = 0;
+        const uint32_t log = cst_w_code_lengths(hist, depth, &hs, &shift);
+        const uint32_t last = cst_w_codes(depth, log, w, code);
+        const uint32_t dlen = cst_w_description(w, last, desc, &fs);
+        uint32_t bits = 0;
+        for (uint32_t s = 0; s < 256; s++) bits += hist[s] * (code[s] >> 16);
+        const uint32_t kind = cst_w_pick(sub, sparse_len, dlen, bits);
+        if (stats) { stats->flattened += shift ? 1 : 0; stats->no_description += dlen ? 0 : 1; }
+        if (kind == kCstRaw) {
+            recs.push_back(uint8_t(kCstRaw));
+            recs.insert(recs.end(), b, b + sub);
+            if (stats) stats->raw++;
+        } else if (kind == kCstSparse) {
+            recs.push_back(uint8_t(kCstSparse));
+            recs.insert(recs.end(), uv, uv + cst_w_put_uvarint(uv, sparse_len));
+            prev = 0;
+            for (uint32_t i = 0; i < sub; i++)
+                for (uint32_t v = b[i]; v; v &= v - 1) {
+                    const uint32_t pos = 8 * i + uint32_t(__builtin_ctz(v));
+                    uint32_t gap = pos - prev;
+                    for (; gap >= 255; gap -= 255) recs.push_back(255);
+                    recs.push_back(uint8_t(gap));
+                    prev = pos + 1;
+                }
+            if (stats) stats->sparse++;
+        } else {
+            descs.insert(descs.end(), desc, desc + dlen);
+            const uint32_t seg = sub / 4;
+            std::vector<uint8_t> four(6);
+            for (uint32_t q = 0; q < 4; q++) {
+                const uint32_t len = cst_w_encode_stream(b + q * seg, seg, code, stream.data());
+                if (q < 3) { four[2 * q] = uint8_t(len); four[2 * q + 1] = uint8_t(len >> 8); }
+                four.insert(four.end(), stream.begin(), stream.begin() + len);
+            }
+            recs.push_back(uint8_t(tc++));
+            recs.insert(recs.end(), uv, uv + cst_w_put_uvarint(uv, uint32_t(four.size())));
+            recs.insert(recs.end(), four.begin(), four.end());
+            if (stats) { stats->huff++; (desc[0] >= 128 ? stats->direct : stats->fse)++; }
+        }
+    }
+    const size_t total = 2 + descs.size() + recs.size();
+    if (total > cap) return -1;
+    dst[0] = uint8_t(bs);
+    dst[1] = uint8_t(tc);
+    if (!descs.empty()) memcpy(dst + 2, descs.data(), descs.size());
+    memcpy(dst + 2 + descs.size(), recs.data(), recs.size());
+    return int64_t(total);
 }
 
 }  // namespace mlz

@@ -310,6 +310,9 @@ int stab_launch(mlz_ctx* c, hipStream_t sm, mlz::StabCommon a, uint32_t T, const
     return 0;
 }
 
+// Where a caller's own bytes start in c->d_stab behind the cnt slots and records of search_tables_build (whole 64-byte units)
+size_t search_tables_extra_off(size_t cnt, uint32_t B) { return (cnt * (size_t(1) << (B - 3)) + cnt * sizeof(uint2) + 64 + 63) & ~size_t(63); }
+
 // The tables of the cnt blocks of a range (len bytes at d_src), built and reduced on sm: c->d_stab then holds cnt slots of 2^(B - 3) bytes, each
 // with its block's table at the front, and behind them (at *info_off) cnt records (table bytes or 0, R).  tail: the tail_n bytes that follow
 // the range in the stream (the next range's first ones, StreamTables::overlap() at the most; host memory).  T, field: the table type and
@@ -319,10 +322,10 @@ int stab_launch(mlz_ctx* c, hipStream_t sm, mlz::StabCommon a, uint32_t T, const
 // follows" from tail_n != 0: type 1 with M = 1 reaches no byte behind its block (tail_n is 0 there), and with or without a following block
 // its blocks index all their blen positions.
 int search_tables_build(mlz_ctx* c, hipStream_t sm, const uint8_t* d_src, size_t len, uint32_t bs, size_t cnt, uint32_t T, const uint8_t* field, uint32_t M, uint32_t B,
-                        const uint8_t* tail, uint32_t tail_n, size_t* info_off) {
+                        const uint8_t* tail, uint32_t tail_n, size_t* info_off, size_t extra = 0 /* bytes the caller wants behind the records, from search_tables_extra_off on */) {
     const size_t slot = size_t(1) << (B - 3);
     *info_off = cnt * slot;
-    HIPCHK(c, c->d_stab.ensure(cnt * slot + cnt * sizeof(uint2) + 64));
+    HIPCHK(c, c->d_stab.ensure(search_tables_extra_off(cnt, B) + extra));
     mlz::StabCommon a{};
     a.src = d_src; a.len = len; a.bs = bs; a.cnt = uint32_t(cnt);
     a.tail_n = std::min(tail_n, T == 4 ? mlz::kStabLongTail : 8u);

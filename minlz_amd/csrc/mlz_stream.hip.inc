@@ -464,7 +464,7 @@ int64_t stream_encode_over(mlz_ctx* const* workers, size_t k, int level, uint32_
 // place; another one: hipMemcpyPeerAsync, which rides xGMI between the GPUs of a node).  Payload never visits the host.
 // stb: the search tables (T > 0), whose builder takes the tail_n bytes at `tail` (host memory) that follow the range in the stream.
 int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d_src, size_t len, size_t b0, uint8_t* d_dst, int dst_dev, StreamEncShared* sh, size_t j,
-                            uint32_t* framed, const StreamTables& stb, const uint8_t* tail, uint32_t tail_n) {
+                            uint32_t* framed, const StreamTables& stb, const uint8_t* tail, uint32_t tail_n, bool compress) {
     HIPCHK(c, hipSetDevice(c->device));
     const size_t cnt = (len + bs - 1) / bs;
     if (cnt == 0) { sh->publish(j, 0); return 0; }
@@ -482,6 +482,7 @@ int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d
     const auto r_crc = pin.take<uint32_t>(cnt);
     const auto r_tabinfo = pin.take<uint2>(tcnt);
     const auto r_tabcrc = pin.take<uint32_t>(tcnt);
+    const auto r_seclen = pin.take<int64_t>(compress ? tcnt : 0);
     const auto r_place = pin.take<PlaceDesc>(max_pieces, 64);
     const auto r_hdr = pin.take<HdrDesc>(cnt);
     const auto r_tabhdr = pin.take<TabHdrDesc>(tcnt);
@@ -491,6 +492,7 @@ int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d
     uint32_t* h_crc = r_crc.at(c->pinned2);
     uint2* h_tabinfo = r_tabinfo.at(c->pinned2);
     uint32_t* h_tabcrc = r_tabcrc.at(c->pinned2);
+    int64_t* h_seclen = r_seclen.at(c->pinned2);
     PlaceDesc* h_place = r_place.at(c->pinned2);
     HdrDesc* h_hdr = r_hdr.at(c->pinned2);
     TabHdrDesc* h_tabhdr = r_tabhdr.at(c->pinned2);
@@ -505,9 +507,11 @@ int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d
     if (r) return r;
     r = crc_device_locked(c, sm, d_src, desc.data(), int(cnt), c->d_crc.as<uint32_t>());
     if (r) return r;
+    // compressed tables (MLZ_STREAM_SEARCH_COMPRESS): behind the slots and records, a section area of a slot per table and their lengths
+    const size_t sec_off = search_m ? search_tables_extra_off(cnt, search_b) : 0, seclen_off = sec_off + cnt * tab_slot;
     if (search_m) {
         size_t tabinfo_off = 0;
-        r = search_tables_build(c, sm, d_src, len, bs, cnt, stb.T, stb.field, search_m, search_b, tail, tail_n, &tabinfo_off);
+        r = search_tables_build(c, sm, d_src, len, bs, cnt, stb.T, stb.field, search_m, search_b, tail, tail_n, &tabinfo_off, compress ? cnt * tab_slot + cnt * sizeof(int64_t) : 0);
         if (r) return r;
         HIPCHK(c, hipMemcpyAsync(h_tabinfo, c->d_stab.as<uint8_t>() + tabinfo_off, sizeof(uint2) * cnt, hipMemcpyDeviceToHost, sm));
     }
@@ -525,6 +529,16 @@ int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d
             if (h_tabinfo[i].x) tdesc.push_back(mlz_block_desc{i * tab_slot, h_tabinfo[i].x, 0, 0});
         }
         n_tabs = tdesc.size();
+        if (n_tabs && compress) {
+            // every table's section into its slot of the area, with one byte less of room than the table has: a section that is no shorter
+            // is that item's error and nothing is written for it (the chunk then stays 0x45).  The lengths come home with the CRCs.
+            std::vector<mlz_block_desc> cdesc(n_tabs);
+            for (size_t t = 0; t < n_tabs; t++) cdesc[t] = mlz_block_desc{tdesc[t].src_off, tdesc[t].src_len, sec_off + t * tab_slot, tdesc[t].src_len - 1};
+            int64_t* d_seclen = reinterpret_cast<int64_t*>(c->d_stab.as<uint8_t>() + seclen_off);
+            r = search_bitmaps_compress_locked(c, sm, c->d_stab.as<uint8_t>(), c->d_stab.as<uint8_t>(), cdesc.data(), int(n_tabs), d_seclen);
+            if (r) return r;
+            HIPCHK(c, hipMemcpyAsync(h_seclen, d_seclen, sizeof(int64_t) * n_tabs, hipMemcpyDeviceToHost, sm));
+        }
         if (n_tabs) {
             HIPCHK(c, c->d_crc.ensure(sizeof(uint32_t) * (cnt + n_tabs) + 64));
             r = crc_device_locked(c, sm, c->d_stab.as<uint8_t>(), tdesc.data(), int(n_tabs), c->d_crc.as<uint32_t>());
@@ -534,23 +548,26 @@ int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d
         }
     }
     // the run's layout: [type][len24][crc][body] per block, a block's table chunk in front of it
-    size_t run = 0, n_place = 0, tab_at = 0;
+    size_t run = 0, n_place = 0, tab_at = 0, wrote46 = 0;   // wrote46: table chunks laid out as 0x46, counted once the run is in place
     auto put_piece = [&](const PlaceDesc& d) { h_place[n_place++] = d; };
     for (size_t i = 0; i < cnt; i++) {
         if (h_len[i] < 0) return h_len[i];
         const ChunkShape s = chunk_shape(h_len[i], size_t(desc[i].src_len));
         framed[b0 + i] = 0;
         if (search_m && h_tabinfo[i].x) {   // 45 len24 | T M B | prefix field | R | crc32le | table
-            const uint32_t tb = h_tabinfo[i].x, tlen = thdr - 4 + tb;
+            // (compressed: 46 len24 | the same fields | the section, where that is shorter than the table)
+            const bool sect = compress && h_seclen[tab_at] > 0 && h_seclen[tab_at] < int64_t(h_tabinfo[i].x);
+            const uint32_t tb = sect ? uint32_t(h_seclen[tab_at]) : h_tabinfo[i].x, tlen = thdr - 4 + tb;
             TabHdrDesc& th = h_tabhdr[tab_at];
             th.dst_off = run; th.n = thdr;
-            th.b[0] = mlz::kChunkSearchTable; th.b[1] = uint8_t(tlen); th.b[2] = uint8_t(tlen >> 8); th.b[3] = uint8_t(tlen >> 16);
+            th.b[0] = sect ? mlz::kChunkSearchTableCompressed : mlz::kChunkSearchTable; th.b[1] = uint8_t(tlen); th.b[2] = uint8_t(tlen >> 8); th.b[3] = uint8_t(tlen >> 16);
             th.b[4] = uint8_t(stb.T); th.b[5] = uint8_t(search_m); th.b[6] = uint8_t(search_b);
             const uint32_t inl = stb.T == 4 ? 0 : flen;   // the field's bytes inside the record
             std::memcpy(th.b + 7, stb.field, inl);
             th.b[7 + inl] = uint8_t(h_tabinfo[i].y);
             std::memcpy(th.b + 8 + inl, &h_tabcrc[tab_at], 4);
-            place_pieces(i * tab_slot, run + thdr, tb, 2, put_piece);
+            place_pieces(sect ? sec_off + tab_at * tab_slot : i * tab_slot, run + thdr, tb, 2, put_piece);
+            wrote46 += sect ? 1 : 0;
             tab_at++;
             framed[b0 + i] = thdr + tb;
             run += thdr + tb;
@@ -590,6 +607,7 @@ int64_t stream_gather_range(mlz_ctx* c, int level, uint32_t bs, const uint8_t* d
     if (!local) HIPCHK(c, hipMemcpyPeerAsync(d_dst + base, dst_dev, d_run, c->device, run, sm));
     HIPCHK(c, hipStreamSynchronize(sm));
     HIPCHK(c, hipGetLastError());
+    c->tables_compressed += wrote46;
     return 0;
 }
 
@@ -600,8 +618,10 @@ int64_t stream_encode_gather_device_with(mlz_ctx* c, int level, uint32_t block_s
     if (block_size < kMinStreamBlock || block_size > kMaxBlockSize) return -MLZ_ERR_ARG;
     if (!valid_level(level)) return -MLZ_ERR_INVALID_LEVEL;
     if (!stb.valid) return -MLZ_ERR_ARG;
-    const bool add_index = (flags & MLZ_STREAM_ADD_INDEX) != 0;
+    const bool add_index = (flags & MLZ_STREAM_ADD_INDEX) != 0, compress = (flags & MLZ_STREAM_SEARCH_COMPRESS) != 0;
+    if (compress && !stb.T) return -MLZ_ERR_ARG;   // nothing to compress
     Workers w(c);
+    for (size_t q = 0; q < w.n; q++) { std::lock_guard<std::mutex> lk(w.list[q]->mu); w.list[q]->tables_compressed = 0; }
     const size_t k = size_t(n_ranges);
     // every range on the device that holds it; all but the last are whole blocks (a short block ends a stream)
     std::vector<mlz_ctx*> own(k, nullptr);
@@ -658,7 +678,7 @@ int64_t stream_encode_gather_device_with(mlz_ctx* c, int level, uint32_t block_s
         mlz_ctx* kc = ctxs[q];
         std::lock_guard<std::mutex> lk(kc->mu);
         for (size_t j : by_ctx[q]) {
-            rcs[j] = stream_gather_range(kc, level, block_size, d_src[j], src_len[j], first[j], d_dst, dst_dev, &sh, j, framed.data(), stb, &tails[j * need], tail_n[j]);
+            rcs[j] = stream_gather_range(kc, level, block_size, d_src[j], src_len[j], first[j], d_dst, dst_dev, &sh, j, framed.data(), stb, &tails[j * need], tail_n[j], compress);
             if (rcs[j]) { sh.fail(); (void)hipStreamSynchronize(kc->stream); }
         }
     };
@@ -667,7 +687,12 @@ int64_t stream_encode_gather_device_with(mlz_ctx* c, int level, uint32_t block_s
     work(0);
     for (std::thread& t : th) t.join();
     const int64_t rc = first_own_verdict(rcs);
-    if (rc) { std::lock_guard<std::mutex> lk(c->mu); for (size_t j = 0; j < k; j++) if (rcs[j] == rc) { c->err = own[j]->err; break; } return rc; }
+    if (rc) {   // a call that fails has written no stream: counter 15 says so, whatever ranges had come through
+        for (size_t q = 0; q < w.n; q++) { std::lock_guard<std::mutex> lk(w.list[q]->mu); w.list[q]->tables_compressed = 0; }
+        std::lock_guard<std::mutex> lk(c->mu);
+        for (size_t j = 0; j < k; j++) if (rcs[j] == rc) { c->err = own[j]->err; break; }
+        return rc;
+    }
     // stream header, EOF chunk and index: a few bytes from the host (writer.go:463-467, :1063-1122)
     mlz_ctx* c0 = w.list[0];
     std::lock_guard<std::mutex> lk(c0->mu);

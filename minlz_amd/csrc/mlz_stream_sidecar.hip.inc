@@ -21,7 +21,9 @@ namespace mlz {
 
 // One data chunk of the main stream as the attach kernel sees it
 struct SideMain { uint64_t hdr_off, n; };
-// One block's chunks in the sidecar: its table chunks (tb[c] bytes of table, 0 = none) start at dst_off, the reference follows them
+// One block's chunks in the sidecar: its table chunks (tb[c] bytes of table, 0 = none) start at dst_off, the reference follows them.
+// R[c] with kSideSection set: the chunk is a compressed one (0x46), tb[c] bytes of huff0 section, which lie sec_off behind the table's slot
+constexpr uint8_t kSideSection = 0x80;
 struct SidePlace { uint64_t dst_off, hdr_off; uint32_t mma, tb[kSidecarMaxConfigs], crc[kSidecarMaxConfigs]; uint8_t R[kSidecarMaxConfigs]; };
 static_assert(sizeof(SidePlace) == 56, "a record shared with the host");
 
@@ -33,6 +35,7 @@ struct SidePlaceArgs {
     const uint8_t* head;       // identifier and info chunks (head_n bytes, to dst[0 ...)); head_n = 0: not this launch
     uint64_t eof_at;           // where the EOF chunk goes; ~0: not this launch
     uint32_t cnt, ncfg, slot, pieces, head_n;
+    uint64_t sec_off;          // the section area: set c's section of block b at tabs + sec_off + (c * cnt + b) * slot
 };
 
 // A workgroup per (block, configuration, 64 KiB piece of a table slot): the table chunk's `45 len24 | T M B | field | R | crc32le` (piece 0)
@@ -56,22 +59,23 @@ __global__ __launch_bounds__(256) void sidecar_place_kernel(const SidePlaceArgs 
     if (!tb) return;
     const SearchConfig& cf = a.cfg[c];
     const uint32_t f = search_field_len(cf.T, cf.field), clen = 8 + f + tb;
+    const bool sect = (r.R[c] & kSideSection) != 0;
     if (piece == 0)
         for (uint32_t i = tid; i < 12 + f; i += 256) {
             uint8_t v;
-            if (i == 0) v = kChunkSearchTable;
+            if (i == 0) v = sect ? kChunkSearchTableCompressed : kChunkSearchTable;
             else if (i < 4) v = uint8_t(clen >> (8 * (i - 1)));
             else if (i == 4) v = uint8_t(cf.T);
             else if (i == 5) v = uint8_t(cf.M);
             else if (i == 6) v = uint8_t(cf.B);
             else if (i < 7 + f) v = cf.field[i - 7];
-            else if (i == 7 + f) v = r.R[c];
+            else if (i == 7 + f) v = r.R[c] & uint8_t(~kSideSection);
             else v = uint8_t(r.crc[c] >> (8 * (i - 8 - f)));
             a.dst[mine + i] = v;
         }
     const uint32_t p0 = piece * kPlacePiece;
     if (p0 >= tb) return;
-    wg_copy(a.dst + mine + 12 + f + p0, a.tabs + (size_t(c) * a.cnt + b) * a.slot + p0, tb - p0 < kPlacePiece ? tb - p0 : kPlacePiece, int(tid), 256);
+    wg_copy(a.dst + mine + 12 + f + p0, a.tabs + (sect ? a.sec_off : 0) + (size_t(c) * a.cnt + b) * a.slot + p0, tb - p0 < kPlacePiece ? tb - p0 : kPlacePiece, int(tid), 256);
 }
 
 // The configurations of a sidecar: the first kSidecarMaxConfigs valid info chunks in front of the first table or reference chunk of its
@@ -198,7 +202,7 @@ int64_t sidecar_bound(const mlz_dev_reader* rd, const std::vector<StreamTables>&
 constexpr size_t kSidecarTableBytes = size_t(64) << 20;   // a group's table slots take this much of c->d_stab at the most (or one chunk's)
 
 // One pass over the handle's stream: place = false only sums up the sidecar's size.  Returns the size or an error.
-int64_t sidecar_build_pass(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, const std::vector<StreamTables>& stb, uint8_t* d_dst, uint64_t dst_cap, bool place) {
+int64_t sidecar_build_pass(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, const std::vector<StreamTables>& stb, uint8_t* d_dst, uint64_t dst_cap, bool place, bool compress) {
     mlz_ctx* c = rd->ctx;
     const uint32_t ncfg = uint32_t(stb.size()), max_block = sidecar_max_block(rd), B = mlz::search_table_bits(max_block);
     const size_t slot = size_t(1) << (B - 3);
@@ -269,10 +273,13 @@ int64_t sidecar_build_pass(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, 
     if (e) return e;
     const auto h_info_r = pin.take<uint2>(nrec);
     const auto h_tcrc_r = pin.take<uint32_t>(nrec);
+    const auto h_seclen_r = pin.take<int64_t>(compress ? nrec : 0);
     const auto h_rec_r = pin.take<mlz::SidePlace>(cnt_max);
     const auto h_up_r = pin.take<uint8_t>(r_tcrc.off, 64);   // what goes up once, as one block: configurations | head | block lists, laid out as in the workspace
     HIPCHK(c, c->d_rplan.ensure(cv.bytes));
-    HIPCHK(c, c->d_stab.ensure(nrec * slot + nrec * sizeof(uint2) + 64));
+    // compressed tables (MLZ_STREAM_SEARCH_COMPRESS): behind the slots and records a section area of as many slots, and the sections' lengths
+    const size_t sec_off = (nrec * slot + nrec * sizeof(uint2) + 64 + 63) & ~size_t(63), seclen_off = sec_off + nrec * slot;
+    HIPCHK(c, c->d_stab.ensure(compress ? seclen_off + nrec * sizeof(int64_t) + 64 : nrec * slot + nrec * sizeof(uint2) + 64));
     if ((e = ensure_stream_objects(c, 0, pin.bytes))) return e;
     void* ws = c->d_rplan.p;
     uint8_t *scratch = c->d_range.as<uint8_t>(), *h_up = h_up_r.at(c->pinned2);
@@ -280,6 +287,7 @@ int64_t sidecar_build_pass(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, 
     const mlz::StabBlock* d_lists = r_lists.at(ws);
     uint32_t *d_tcrc = r_tcrc.at(ws), *h_tcrc = h_tcrc_r.at(c->pinned2);
     mlz::SidePlace *d_rec = r_rec.at(ws), *h_rec = h_rec_r.at(c->pinned2);
+    int64_t *h_seclen = h_seclen_r.at(c->pinned2), *d_seclen = reinterpret_cast<int64_t*>(c->d_stab.as<uint8_t>() + seclen_off);
     uint2 *h_info = h_info_r.at(c->pinned2), *d_info = reinterpret_cast<uint2*>(c->d_stab.as<uint8_t>() + nrec * slot);
     std::memcpy(r_cfg.at(h_up), cfg.data(), ncfg * sizeof(mlz::SearchConfig));
     std::memcpy(r_head.at(h_up), head.data(), head.size());
@@ -287,12 +295,13 @@ int64_t sidecar_build_pass(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, 
     { WorkspaceOrder order(c, sm); }
     HIPCHK(c, hipMemcpyAsync(ws, h_up, r_tcrc.off, hipMemcpyHostToDevice, sm));
 
-    uint64_t total = head.size();
+    uint64_t total = head.size(), wrote46 = 0;   // wrote46: table chunks placed as 0x46, counted once the whole sidecar is in place
     auto launch_place = [&](uint32_t cnt, bool first, bool last_one) {
         mlz::SidePlaceArgs a{};
         a.dst = d_dst; a.tabs = c->d_stab.as<uint8_t>(); a.rec = d_rec; a.cfg = d_cfg; a.head = r_head.at(ws);
         a.eof_at = last_one ? total : ~uint64_t(0);
         a.cnt = cnt; a.ncfg = ncfg; a.slot = uint32_t(slot); a.pieces = uint32_t(std::max<size_t>(1, slot / kPlacePiece)); a.head_n = first ? uint32_t(head.size()) : 0;
+        a.sec_off = sec_off;
         hipLaunchKernelGGL(mlz::sidecar_place_kernel, dim3(std::max<uint32_t>(1, cnt * ncfg * a.pieces)), dim3(256), 0, sm, a);
     };
     // a group's bytes are in the scratch: its tables, their sizes and CRCs, its chunks' places, the placement
@@ -308,6 +317,15 @@ int64_t sidecar_build_pass(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, 
         std::vector<mlz_block_desc> tdesc;   // the kept tables, in (configuration, block) order: slot t = s * cnt + b
         for (size_t t = 0; t < ncfg * cnt; t++)
             if (h_info[t].x) tdesc.push_back(mlz_block_desc{t * slot, h_info[t].x, 0, 0});
+        if (!tdesc.empty() && compress) {
+            // every kept table's section behind its slot's twin in the section area, with one byte less of room than the table has: a
+            // section that is no shorter is that item's error, nothing is written for it and its chunk stays 0x45.  Both passes run
+            // this: the sizing pass sums the real sizes.
+            std::vector<mlz_block_desc> cdesc(tdesc.size());
+            for (size_t q = 0; q < tdesc.size(); q++) cdesc[q] = mlz_block_desc{tdesc[q].src_off, tdesc[q].src_len, sec_off + tdesc[q].src_off, tdesc[q].src_len - 1};
+            if ((r = search_bitmaps_compress_locked(c, sm, c->d_stab.as<uint8_t>(), c->d_stab.as<uint8_t>(), cdesc.data(), int(cdesc.size()), d_seclen))) return r;
+            if ((r = fetch(c, sm, h_seclen, d_seclen, tdesc.size() * sizeof(int64_t)))) return r;
+        }
         if (!tdesc.empty() && place) {
             if ((r = crc_device_locked(c, sm, c->d_stab.as<uint8_t>(), tdesc.data(), int(tdesc.size()), d_tcrc))) return r;
             if ((r = fetch(c, sm, h_tcrc, d_tcrc, tdesc.size() * 4))) return r;
@@ -324,6 +342,11 @@ int64_t sidecar_build_pass(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, 
                 p.tb[s] = h_info[t].x; p.R[s] = uint8_t(h_info[t].y);
                 if (!p.tb[s]) continue;
                 if (place) p.crc[s] = h_tcrc[crc_at[t]];
+                if (compress && h_seclen[crc_at[t]] > 0 && h_seclen[crc_at[t]] < int64_t(p.tb[s])) {
+                    p.tb[s] = uint32_t(h_seclen[crc_at[t]]);
+                    p.R[s] |= mlz::kSideSection;
+                    if (place) wrote46++;
+                }
                 total += 12 + stb[s].flen() + p.tb[s];
             }
             total += mlz::sidecar_ref_bytes(p.hdr_off, p.mma);
@@ -343,20 +366,22 @@ int64_t sidecar_build_pass(mlz_dev_reader* rd, hipStream_t sm, bool ignore_crc, 
     }
     HIPCHK(c, hipStreamSynchronize(sm));
     HIPCHK(c, hipGetLastError());
+    if (place) c->tables_compressed = wrote46;
     return int64_t(total + 5);
 }
 
 int64_t dev_reader_build_sidecar_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const std::vector<StreamTables>& stb, uint8_t* d_dst, uint64_t dst_cap) {
     mlz_ctx* c = rd->ctx;
     HIPCHK(c, hipSetDevice(c->device));
-    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0;
+    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0, compress = (flags & MLZ_STREAM_SEARCH_COMPRESS) != 0;
+    c->tables_compressed = 0;
     // a capacity below the bound may not hold the result: the sizes are found first, so that nothing is written when it does not
     if (dst_cap < uint64_t(sidecar_bound(rd, stb))) {
-        const int64_t need = sidecar_build_pass(rd, sm, ignore_crc, stb, d_dst, dst_cap, false);
+        const int64_t need = sidecar_build_pass(rd, sm, ignore_crc, stb, d_dst, dst_cap, false, compress);
         if (need < 0) return need;
         if (uint64_t(need) > dst_cap) return -MLZ_ERR_DST_TOO_SMALL;
     }
-    return sidecar_build_pass(rd, sm, ignore_crc, stb, d_dst, dst_cap, true);
+    return sidecar_build_pass(rd, sm, ignore_crc, stb, d_dst, dst_cap, true, compress);
 }
 
 // The attach: the sidecar's table sets -> *out (device memory of its own).  Returns 0 or the error; nothing of the handle changes here.

@@ -396,12 +396,13 @@ class DeviceStream:
         off, ln = self.reader.record_range(first, count)
         return self.read_ranges([off], [ln], ignore_crc)
 
-    def build_sidecar(self, cfgs, ignore_crc=False):
+    def build_sidecar(self, cfgs, ignore_crc=False, compress=False):
         """A sidecar search index of this stream for 1 .. 4 configurations (api.search_config): search tables for every block, whoever
-        wrote the stream, in a separate .mz stream -> a new uint8 tensor on the stream's device."""
+        wrote the stream, in a separate .mz stream -> a new uint8 tensor on the stream's device.  compress: table chunks are written
+        compressed (0x46) where that is smaller."""
         cap = self.reader.sidecar_bound(cfgs)
         out = torch.empty(cap, dtype=torch.uint8, device=self.dev)
-        got = self.reader.build_sidecar(cfgs, out.data_ptr(), cap, ignore_crc=ignore_crc, stream=_stream(self.dev))
+        got = self.reader.build_sidecar(cfgs, out.data_ptr(), cap, ignore_crc=ignore_crc, stream=_stream(self.dev), compress=compress)
         return out[:got].clone()
 
     def attach_sidecar(self, side, ignore_crc=False):
@@ -514,7 +515,7 @@ class DeviceStreamSet(DeviceStream):
         which, line = self.locate_records(numbers)
         return which, line, kinds
 
-    def build_sidecar(self, cfgs, ignore_crc=False):
+    def build_sidecar(self, cfgs, ignore_crc=False, compress=False):
         raise api.ErrUnsupported("build_sidecar: a set of streams takes no sidecar")
 
     def attach_sidecar(self, side, ignore_crc=False):
