@@ -625,7 +625,9 @@ int64_t mlz_dev_reader_grep_records(mlz_dev_reader* reader, void* stream, uint32
  *   (M - 1, M, or K - 1 + M + E for types 1, 2 and 3, 4): that chunk is decoded, and every position is returned as without a sidecar.  The third
  *   statistic counts the chunks with a usable table of at least one configuration that serves a pattern, the fourth the patterns no configuration serves.
  * flags may hold MLZ_STREAM_SEARCH_COMPRESS: every table chunk is then written compressed (0x46) where that is strictly smaller, as the device Writer does it; the size returned, and
- *   the one a capacity is checked against, are the real ones; mlz_get_counter(ctx, 15) counts the 0x46 chunks.  Out of scope: ExtractSidecar, the Writer-side sidecar, concatenated streams, sidecars read from host memory. */
+ *   the one a capacity is checked against, are the real ones; mlz_get_counter(ctx, 15) counts the 0x46 chunks.  The reference's ExtractSidecar — the tables a stream carries inline copied into a sidecar, the stream written again without them — is
+ *   mlz_dev_reader_extract_sidecar in include/minlz_hip_sidecar_extract.h.  Out of scope: a Writer that diverts tables while it encodes (the device Writer followed by that call gives
+ *   WriterSidecar's sidecar), concatenated streams, sidecars read from host memory. */
 #define MLZ_SIDECAR_MAX_CONFIGS 4
 typedef struct {
     uint8_t table_type;   /* 1 .. 4 */

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension headers include/minlz_hip_search_batch.h, include/minlz_hip_stream_set.h, include/minlz_hip_regex.h, include/minlz_hip_search_compressed.h and include/minlz_hip_search_compress.h.
+"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension headers include/minlz_hip_search_batch.h, include/minlz_hip_stream_set.h, include/minlz_hip_regex.h, include/minlz_hip_search_compressed.h, include/minlz_hip_search_compress.h and include/minlz_hip_sidecar_extract.h.
 
 There is no CPU fallback here: if libminlz_hip.so is missing or HIP is unavailable, calls raise.
 """
@@ -29,6 +29,11 @@ class SearchConfig(C.Structure):
     """mlz_search_config: one table configuration of a sidecar, any table type 1 .. 4."""
     _fields_ = [("table_type", C.c_uint8), ("match_len", C.c_uint8), ("extras", C.c_uint8), ("reserved", C.c_uint8), ("prefix_len", C.c_uint16),
                 ("reserved2", C.c_uint8 * 2), ("prefix", C.c_uint8 * 256)]
+
+
+class SidecarExtractResult(C.Structure):
+    """mlz_sidecar_extract_result (include/minlz_hip_sidecar_extract.h)."""
+    _fields_ = [(name, C.c_uint64) for name in ("side_len", "main_len", "blocks", "info_chunks", "tables", "tables_compressed", "passed_bytes", "dropped_bytes")]
 
 
 class BlockDesc(C.Structure):
@@ -130,6 +135,10 @@ ABI_EXT = {
     "minlz_hip_search_compress.h": {
         "mlz_search_bitmap_compress": (i64, [vp, sz, vp, sz]),
         "mlz_search_bitmaps_compress_device": (i32, [vp, vp, vp, vp, P(BlockDesc), i32, vp]),
+    },
+    "minlz_hip_sidecar_extract.h": {
+        "mlz_dev_reader_extract_sidecar_bound": (i64, [vp, P(u64)]),
+        "mlz_dev_reader_extract_sidecar": (i64, [vp, vp, u32, vp, sz, vp, sz, P(SidecarExtractResult)]),
     },
 }
 

@@ -1,4 +1,5 @@
 """Block API mirror of the reference (encode.go:74-244, decode.go:50-156) over the C ABI."""
+import collections
 import ctypes as C
 import threading
 
@@ -73,6 +74,9 @@ class ErrCRC(MinLZError):
 class ErrHIP(MinLZError):
     code = ERR_HIP
 
+
+# mlz_sidecar_extract_result (include/minlz_hip_sidecar_extract.h), what DeviceReader.extract_sidecar returns
+SidecarExtract = collections.namedtuple("SidecarExtract", "side_len main_len blocks info_chunks tables tables_compressed passed_bytes dropped_bytes")
 
 _ERRS = {e.code: e for e in (ErrCorrupt, ErrTooLarge, ErrUnsupported, ErrInvalidLevel, ErrCRC, ErrHIP)}
 
@@ -593,6 +597,29 @@ class DeviceReader:
     def detach_sidecar(self):
         """The searches use the stream's inline tables again."""
         self._call("mlz_dev_reader_attach_sidecar", None, 0, None, 0)
+
+    def extract_sidecar_bound(self):
+        """mlz_dev_reader_extract_sidecar_bound (include/minlz_hip_sidecar_extract.h) -> (side_cap, main_cap) that always suffice for extract_sidecar."""
+        main = C.c_uint64(0)
+        side = self._call("mlz_dev_reader_extract_sidecar_bound", C.byref(main))
+        return side, int(main.value)
+
+    def extract_sidecar(self, d_side, side_cap, d_main=None, main_cap=0, stream=None):
+        """mlz_dev_reader_extract_sidecar: the search chunks this stream carries (0x44, 0x45, 0x46), copied as they are into a sidecar at device
+        address d_side with one remote reference per data chunk; nothing is decoded.  With d_main the stream is also written there without its
+        search and index chunks, with a fresh seek index, and the references name the offsets in d_main (which must not overlap the stream or
+        d_side); without it they name the offsets in this stream.  -> SidecarExtract.  Room that is too small raises MinLZError (error 6) whose
+        `needed` is (side_len, main_len)."""
+        out = _lib.SidecarExtractResult()
+        handle = self._open()
+        r = _lib.lib().mlz_dev_reader_extract_sidecar(handle, stream, 0, d_side, side_cap, d_main, main_cap, C.byref(out))
+        if r < 0:
+            try:
+                _raise(r, self.ctx)
+            except MinLZError as e:
+                e.needed = (int(out.side_len), int(out.main_len))
+                raise
+        return SidecarExtract(*(int(getattr(out, name)) for name in SidecarExtract._fields))
 
     def close(self):
         if self.handle:

@@ -21,6 +21,7 @@
 #include "../../include/minlz_hip_stream_set.h"
 #include "../../include/minlz_hip_search_compressed.h"
 #include "../../include/minlz_hip_search_compress.h"
+#include "../../include/minlz_hip_sidecar_extract.h"
 #include "mlz_format.h"
 #include "mlz_kernels.h"
 
@@ -1357,6 +1358,8 @@ int mlz_debug_idxprof(unsigned long long* out) {
 #include "mlz_stream_search_many.hip.inc"
 #include "mlz_stream_search_batch.hip.inc"
 #include "mlz_stream_sidecar.hip.inc"
+#include "mlz_stream_sidecar_extract.h"
+#include "mlz_stream_sidecar_extract.hip.inc"
 #include "mlz_stream_records.hip.inc"
 #include "mlz_stream_record_index.hip.inc"
 #include "mlz_stream_grep.hip.inc"

@@ -415,6 +415,17 @@ class DeviceStream:
             self.reader.attach_sidecar(side.data_ptr(), side.numel(), ignore_crc=ignore_crc, stream=_stream(self.dev))
         self.side = side
 
+    def extract_sidecar(self, strip=False):
+        """The search tables this stream carries inline, copied as they are into a sidecar (the reference's ExtractSidecar; nothing is
+        decoded or rebuilt) -> a new uint8 tensor on the stream's device, whose references name this stream's offsets.  strip: -> (side, main)
+        where `main` is this stream without its search and index chunks and with a fresh seek index, and the references name main's offsets:
+        open `main` and attach `side` to search it."""
+        side_cap, main_cap = self.reader.extract_sidecar_bound()
+        side = torch.empty(side_cap, dtype=torch.uint8, device=self.dev)
+        main = torch.empty(main_cap, dtype=torch.uint8, device=self.dev) if strip else None
+        got = self.reader.extract_sidecar(side.data_ptr(), side_cap, main.data_ptr() if strip else None, main_cap if strip else 0, stream=_stream(self.dev))
+        return (side[:got.side_len].clone(), main[:got.main_len].clone()) if strip else side[:got.side_len].clone()
+
     def ReadAt(self, n, offset, ignore_crc=False):
         """Up to n decoded bytes from `offset`, clamped at the end of the stream -> a new uint8 tensor."""
         if n < 0 or offset < 0 or offset > self.size:
@@ -520,3 +531,6 @@ class DeviceStreamSet(DeviceStream):
 
     def attach_sidecar(self, side, ignore_crc=False):
         raise api.ErrUnsupported("attach_sidecar: a set of streams takes no sidecar")
+
+    def extract_sidecar(self, strip=False):
+        raise api.ErrUnsupported("extract_sidecar: a set of streams takes no sidecar")
