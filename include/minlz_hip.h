@@ -572,7 +572,8 @@ int64_t mlz_dev_reader_record_range(mlz_dev_reader* reader, uint64_t first, uint
  *   the sizes of before / after) and compact.  32 bytes visit the host, behind the search phase's own; nothing per record or per occurrence does.
  *   Synchronous; `stream` as for mlz_dev_reader_read.  Workspace, grow-only and part of mlz_get_counter 4: 16 bytes per 32 records (two
  *   bitmaps and two scan arrays) beside the search phase's.
- *   Regular expressions: mlz_dev_reader_grep_regex (include/minlz_hip_regex.h), the same call with M decided by a compiled expression.
+ *   Regular expressions: mlz_dev_reader_grep_regex (include/minlz_hip_regex.h), the same call with M decided by a compiled expression;
+ *   include/minlz_hip_regex_prune.h: that call decoding only the chunks the search tables admit for the expression's required literals.
  *   Out of scope: Unicode or locale folding; per-record lists of which pattern matched; delimiters of more than one byte; a grep over
  *   batches of streams other than on a set handle (include/minlz_hip_stream_set.h: the streams' concatenation); a call that works without a record
  *   index (mlz_dev_reader_search_records remains the bounded-reach form for that). */

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension headers include/minlz_hip_search_batch.h, include/minlz_hip_stream_set.h, include/minlz_hip_regex.h, include/minlz_hip_search_compressed.h, include/minlz_hip_search_compress.h and include/minlz_hip_sidecar_extract.h.
+"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension headers include/minlz_hip_search_batch.h, include/minlz_hip_stream_set.h, include/minlz_hip_regex.h, include/minlz_hip_regex_prune.h, include/minlz_hip_search_compressed.h, include/minlz_hip_search_compress.h and include/minlz_hip_sidecar_extract.h.
 
 There is no CPU fallback here: if libminlz_hip.so is missing or HIP is unavailable, calls raise.
 """
@@ -128,6 +128,10 @@ ABI_EXT = {
         "mlz_regex_info": (i32, [vp, P(u64)]),
         "mlz_regex_test": (i32, [vp, vp, sz]),
         "mlz_dev_reader_grep_regex": (i64, [vp, vp, u32, vp, u64, u64, vp, vp, sz, P(u64), P(u64)]),
+    },
+    "minlz_hip_regex_prune.h": {
+        "mlz_regex_literals": (i32, [vp, vp, sz, P(u32), sz, P(u64)]),
+        "mlz_dev_reader_grep_regex_pruned": (i64, [vp, vp, u32, vp, u64, u64, vp, vp, sz, P(u64), P(u64)]),
     },
     "minlz_hip_search_compressed.h": {
         "mlz_search_table_expand": (i64, [vp, sz, vp, sz, P(u32), u32]),

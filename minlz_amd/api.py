@@ -153,6 +153,19 @@ class Regex:
         _lib.lib().mlz_regex_info(self._open(), info)
         return int(info[0]), int(info[1]), int(info[2]), bool(info[3] & 1)
 
+    def literals(self):
+        """mlz_regex_literals (include/minlz_hip_regex_prune.h) -> (the required literals, a sorted list of bytes objects of which every matching record
+        holds one, empty: none; whether they are folded: under ignore_case the record with A - Z folded to a - z holds one)."""
+        info = _stats()
+        n = _lib.lib().mlz_regex_literals(self._open(), None, 0, None, 0, info)
+        lens, buf = (C.c_uint32 * max(n, 1))(), (C.c_uint8 * max(int(info[1]), 1))()
+        _lib.lib().mlz_regex_literals(self._open(), buf, int(info[1]), lens, n, info)
+        blob, at, out = bytes(buf), 0, []
+        for i in range(n):
+            out.append(blob[at:at + lens[i]])
+            at += lens[i]
+        return out, bool(info[3] & 1)
+
     def test(self, record):
         """mlz_regex_test: does `record` hold a match, by the rule the kernel runs."""
         rec = bytes(record)
@@ -519,15 +532,21 @@ class DeviceReader:
                        d_rec_no, d_rec_kind, rec_cap, totals, stats)
         return r, _ints(totals), _ints(stats)
 
-    def grep_regex(self, regex, d_rec_no, d_rec_kind, rec_cap, invert=False, before=0, after=0, ignore_crc=False, stream=None):
+    def grep_regex(self, regex, d_rec_no, d_rec_kind, rec_cap, invert=False, before=0, after=0, ignore_crc=False, stream=None, prune=False, no_tables=False):
         """mlz_dev_reader_grep_regex: grep_records with the selected records decided by `regex` (a Regex): a record is selected when its
         bytes, the delimiter excluded, hold a match (an empty record: when the expression matches the empty string), with invert when they
         hold none.  d_rec_no, d_rec_kind, rec_cap, before and after as in grep_records.  Every chunk is decoded once; an index with a
         record longer than REGEX_MAX_RECORD raises ErrUnsupported before that.
-        -> (R, (R, selected records, bytes of the written records, bytes of all R records), (data chunks, chunks decoded, 0, 0))."""
+        prune: mlz_dev_reader_grep_regex_pruned (include/minlz_hip_regex_prune.h), the same results from the chunks that the search tables admit
+        for the expression's required literals (Regex.literals) and those that complete their records; no_tables (with prune only) decodes every chunk.
+        -> (R, (R, selected records, bytes of the written records, bytes of all R records), (data chunks, chunks decoded, 0, 0)); with prune the
+        last two are the chunks with a usable table and the chunks the plan took before it was widened to whole records."""
         self._open()
         totals, stats = _stats(), _stats()
-        r = self._call("mlz_dev_reader_grep_regex", stream, _flags(ignore_crc=ignore_crc, invert=invert), regex._open(), before, after, d_rec_no, d_rec_kind, rec_cap, totals, stats)
+        if no_tables and not prune:
+            raise ValueError("grep_regex: no_tables goes with prune=True")
+        r = self._call("mlz_dev_reader_grep_regex_pruned" if prune else "mlz_dev_reader_grep_regex", stream, _flags(ignore_crc=ignore_crc, invert=invert, no_tables=no_tables), regex._open(),
+                       before, after, d_rec_no, d_rec_kind, rec_cap, totals, stats)
         return r, _ints(totals), _ints(stats)
 
     def record_range(self, first, count):

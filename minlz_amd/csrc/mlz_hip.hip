@@ -193,7 +193,7 @@ struct mlz_ctx {
     // options
     int decode_algo = 0;
     int encode_far = 1;
-    bool enc_attrs = false, far_attr = false, farbin_attr = false, stab_attr = false, dec_attrs = false, gen_attr = false, l0_attr = false, l0_attr_failed = false;  // per device: dynamic-LDS limits raised (raise_lds_once)
+    bool enc_attrs = false, far_attr = false, farbin_attr = false, stab_attr = false, dec_attrs = false, gen_attr = false, l0_attr = false, l0_attr_failed = false, regex_runs_attr = false;  // per device: dynamic-LDS limits raised (raise_lds_once)
     uint32_t timer_mask = 0xffffffffu;  // timers that record events (an event pair costs ~10 us of idle device per kernel boundary)
     int timing = 0;  // 0 off, 1 = the last call's kernel times, 2 = running mean over the calls since it was enabled (no sync per call)
     int debug_status = 0;
@@ -1365,3 +1365,4 @@ int mlz_debug_idxprof(unsigned long long* out) {
 #include "mlz_stream_grep.hip.inc"
 #include "mlz_stream_set.hip.inc"
 #include "mlz_stream_regex.hip.inc"
+#include "mlz_stream_regex_prune.hip.inc"

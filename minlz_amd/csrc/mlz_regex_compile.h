@@ -23,6 +23,8 @@
 //   repeat, the second quantifier, the ? or + behind a quantifier, the byte behind "(?", the backslash of an escape, the first byte of a bad class
 //   item, the expression's length where it ends too early.  A limit of the automaton as a whole reports the last expression and its length; a bad
 //   count of expressions reports (n_exprs, 0).
+// Required literals (Literals below; the rule and its limits are written out in mlz_stream_regex_prune.h): a set of byte strings of which every
+//   matching record holds one, derived from the syntax tree.  Compiling never fails because of them: an expression too rich has none.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -30,9 +32,10 @@
 
 #include <algorithm>
 #include <map>
+#include <string>
 #include <vector>
 
-#include "mlz_stream_regex.h"
+#include "mlz_stream_regex_prune.h"
 
 namespace mlz {
 
@@ -48,6 +51,7 @@ struct RegexProgram {
     uint32_t n_end = 0;              // how many
     bool empty_ok = false;           // the start state accepts the empty record
     uint32_t flags = 0;
+    std::vector<std::string> literals;   // the required literals (mlz_stream_regex_prune.h), sorted, folded under kRegexIgnoreCase; empty: none
     uint32_t image_bytes() const { return regex_image_bytes(S, C); }
     // The image the kernel loads: cmap | next | zeros up to a multiple of 16
     void image(uint8_t* out) const {
@@ -314,6 +318,117 @@ struct Parser {
     }
 };
 
+// The required literals of a syntax tree, node by node: E, the finite set of all strings the node matches (or unknown), and F, the best set of
+// required factors (or none).  Sets are sorted and hold no string twice.
+using LitStrings = std::vector<std::string>;
+struct LitNode { bool e_known = false, f_some = false; LitStrings E, F; };
+
+inline void lit_normalize(LitStrings* v) { std::sort(v->begin(), v->end()); v->erase(std::unique(v->begin(), v->end()), v->end()); }
+inline LitStrings lit_union(const LitStrings& a, const LitStrings& b) { LitStrings u = a; u.insert(u.end(), b.begin(), b.end()); lit_normalize(&u); return u; }
+// a x b within the caps of a product; false beyond them
+inline bool lit_product(const LitStrings& a, const LitStrings& b, LitStrings* out) {
+    if (!regex_lit_product_fits(a.size(), b.size())) return false;
+    LitStrings p;
+    for (const std::string& x : a)
+        for (const std::string& y : b) {
+            if (x.size() + y.size() > kRegexMaxLiteralLen) return false;
+            p.push_back(x + y);
+        }
+    lit_normalize(&p);
+    *out = std::move(p);
+    return true;
+}
+inline size_t lit_shortest(const LitStrings& v) {
+    size_t m = ~size_t(0);
+    for (const std::string& s : v) m = std::min(m, s.size());
+    return v.empty() ? 0 : m;
+}
+// The candidates of a node in the order they arise; best(): regex_lit_better decides, the leftmost wins a tie
+struct LitCandidates {
+    bool some = false;
+    LitStrings best;
+    void offer(const LitStrings& v) {
+        if (v.empty() || lit_shortest(v) == 0) return;   // (a set that holds the empty string is no candidate)
+        if (!some || regex_lit_better(lit_shortest(v), v.size(), lit_shortest(best), best.size())) { best = v; some = true; }
+    }
+};
+
+struct Literals {
+    const Parser& ps;
+    bool fold;
+
+    static LitNode empty_string() { LitNode n; n.e_known = true; n.E.assign(1, std::string()); return n; }
+    LitNode of(int id) const {
+        const Node& nd = ps.nodes[id];
+        switch (nd.kind) {
+        case kEmpty: case kBegin: case kEnd: return empty_string();
+        case kSet: {
+            const ByteSet& s = ps.sets[nd.a];
+            ByteSet img;
+            for (uint32_t b = 0; b < 256; b++) if (s.has(b)) img.add(fold ? regex_lit_fold(uint8_t(b)) : b);
+            LitNode n;
+            for (uint32_t b = 0; b < 256; b++) if (img.has(b)) n.E.push_back(std::string(1, char(b)));
+            if (n.E.size() > kRegexLitSmallSet) { n.E.clear(); return n; }
+            n.e_known = n.f_some = true;
+            n.F = n.E;
+            return n;
+        }
+        case kCat: {
+            LitStrings X(1, std::string());
+            bool closed = false;
+            LitCandidates c;
+            for (int32_t i = nd.a; i < nd.b; i++) {
+                const LitNode k = of(ps.kids[i]);
+                LitStrings p;
+                if (k.e_known && lit_product(X, k.E, &p)) X = std::move(p);
+                else {
+                    c.offer(X);
+                    closed = true;
+                    X = k.e_known ? k.E : LitStrings(1, std::string());
+                }
+                if (k.f_some) c.offer(k.F);
+            }
+            c.offer(X);
+            LitNode n;
+            if (!closed) { n.e_known = true; n.E = X; }
+            n.f_some = c.some; n.F = c.best;
+            return n;
+        }
+        case kAlt: {
+            LitNode n;
+            n.e_known = n.f_some = true;
+            for (int32_t i = nd.a; i < nd.b; i++) {
+                const LitNode k = of(ps.kids[i]);
+                if (n.e_known && k.e_known) { n.E = lit_union(n.E, k.E); n.e_known = n.E.size() <= kRegexLitProduct; } else n.e_known = false;
+                if (n.f_some && k.f_some) { n.F = lit_union(n.F, k.F); n.f_some = n.F.size() <= kRegexMaxLiterals; } else n.f_some = false;
+            }
+            if (!n.e_known) n.E.clear();
+            if (!n.f_some) n.F.clear();
+            return n;
+        }
+        case kRep: {
+            const LitNode a = of(nd.a);
+            LitNode n;
+            if (nd.min == 0) {
+                if (nd.max == 1 && a.e_known) { n.E = lit_union(a.E, LitStrings(1, std::string())); n.e_known = n.E.size() <= kRegexLitProduct; }
+                if (!n.e_known) n.E.clear();
+                return n;
+            }
+            LitStrings pw(1, std::string());
+            bool known = a.e_known;
+            for (int32_t i = 0; i < nd.min && known; i++) { LitStrings p; known = lit_product(pw, a.E, &p); if (known) pw = std::move(p); }
+            LitCandidates c;
+            if (a.f_some) c.offer(a.F);
+            if (known) c.offer(pw);
+            n.f_some = c.some; n.F = c.best;
+            if (known && nd.min == nd.max) { n.e_known = true; n.E = pw; }
+            return n;
+        }
+        }
+        return LitNode();
+    }
+};
+
 // The NFA: kByte consumes a byte of its set and goes to out1; kSplit goes to out1 and out2 (-1: none) for nothing; kAtBegin / kAtEnd go to out1
 // for nothing in front of the first / behind the last byte only; kMatch is the end.
 enum NfaKind : uint8_t { kSplit, kByte, kAtBegin, kAtEnd, kMatch };
@@ -482,11 +597,18 @@ inline int regex_compile(const uint8_t* exprs, const uint32_t* expr_len, size_t 
     int32_t start = -1;
     uint64_t positions = 0;
     size_t at = 0;
+    LitStrings lits;          // the alternation of the expressions' roots: the union of their F while every one has some
+    bool lits_some = true;
     for (size_t i = 0; i < n; at += expr_len[i], i++) {
         static const uint8_t nothing = 0;
         Parser ps{total ? exprs + at : &nothing, expr_len[i], 0, fold, {}, {}, {}, {}};
         const int root = ps.parse();
         if (root < 0) return refuse(ps.err.code, i, ps.err.off);
+        if (lits_some) {
+            const LitNode ln = Literals{ps, fold}.of(root);
+            lits_some = ln.f_some;
+            if (lits_some) { lits = lit_union(lits, ln.F); lits_some = lits.size() <= kRegexMaxLiterals; }
+        }
         Builder b{ps, nfa, sets, false, {}};
         positions += b.positions(root);
         if (positions > kRegexMaxPositions) return refuse(kRegexErrUnsupported, i, expr_len[i]);
@@ -622,6 +744,7 @@ inline int regex_compile(const uint8_t* exprs, const uint32_t* expr_len, size_t 
     }
     pr.start = uint32_t(number[group[size_t(raw_start)]]) * C;
     pr.empty_ok = regex_verdict(pr.start, true, C, pr.end_hi) != 0;
+    pr.literals = lits_some ? lits : LitStrings();
     return 0;
 }
 

@@ -112,13 +112,17 @@ MLZ_REGEX_HD RegexLane regex_lane(At at, uint64_t k, uint64_t size, RegexGroup g
 // One lane's whole work: walk(from, to, state) -> state is regex_walk or regex_walk_blocks over the decoded positions.  in: the slot this group
 // reads.  finished: verdict is the record's; else carry is what the lane writes.
 struct RegexLaneOut { bool finished; uint32_t verdict; RegexCarry carry; };
-template <class At, class Walk>
-MLZ_REGEX_HD RegexLaneOut regex_run_lane(At at, uint64_t k, uint64_t size, RegexGroup g, uint64_t r, RegexCarry in, uint32_t start, uint32_t C, uint32_t end_hi, Walk walk) {
-    const RegexLane ln = regex_lane(at, k, size, g, r);
+// ... from the positions ln says (regex_lane; the pruned grep's lanes come from regex_run_lane_of, mlz_stream_regex_prune.h)
+template <class Walk>
+MLZ_REGEX_HD RegexLaneOut regex_lane_result(RegexLane ln, uint64_t r, RegexCarry in, uint32_t start, uint32_t C, uint32_t end_hi, Walk walk) {
     uint32_t state = ln.crossed_in ? (in.rec == r ? in.state : 0u) : start;   // (a carry for another record: the host check's failure; dead here)
     if (ln.from < ln.to) state = walk(ln.from, ln.to, state);
     if (ln.finishes) return RegexLaneOut{true, regex_verdict(state, true, C, end_hi), RegexCarry{r, state, 1}};
     return RegexLaneOut{false, 0, RegexCarry{r, state, regex_stopped(state, C) ? 1u : 0u}};
+}
+template <class At, class Walk>
+MLZ_REGEX_HD RegexLaneOut regex_run_lane(At at, uint64_t k, uint64_t size, RegexGroup g, uint64_t r, RegexCarry in, uint32_t start, uint32_t C, uint32_t end_hi, Walk walk) {
+    return regex_lane_result(regex_lane(at, k, size, g, r), r, in, start, C, end_hi, walk);
 }
 
 // ---- the mark layout ----

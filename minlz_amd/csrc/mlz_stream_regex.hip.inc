@@ -46,6 +46,25 @@ __global__ __launch_bounds__(64) void regex_bounds_kernel(const uint64_t* __rest
     if (g < ng) bounds[g] = regex_bounds([&](uint64_t i) { return D[i]; }, k, groups[g]);
 }
 
+// What both mark kernels (this one and regex_mark_runs_kernel, mlz_stream_regex_prune.hip.inc) do around their lanes' rule.
+// The class map and the table, image_bytes of them, into LDS by 16-byte loads
+__device__ __forceinline__ void regex_load_image(uint4* lds, const uint4* __restrict__ image, uint32_t image_bytes, uint32_t tid) {
+    for (uint32_t i = tid; i < image_bytes / 16; i += kRegexThreads) lds[i] = image[i];
+}
+// regex_walk_blocks over the bytes y in [from, to) of memory: al is a 16-byte boundary, the region [ylo, yhi) counts from it
+__device__ __forceinline__ uint32_t regex_walk_memory(const uint16_t* next, const uint8_t* cmap, uint32_t C, const uint8_t* al, int64_t ylo, int64_t yhi, int64_t from, int64_t to, uint32_t state) {
+    return regex_walk_blocks(next, cmap, C,
+                             [&](int64_t y, uint32_t* v) { const uint4 x = *reinterpret_cast<const uint4*>(al + y); v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w; },
+                             [&](int64_t y) { return al[y]; }, ylo, yhi, from, to, state);
+}
+// The verdicts of a wavefront's 64 records, the first of which is r - lane, into the bitmap: the ballot's halves by lanes 0 and 32
+__device__ __forceinline__ void regex_put_marks(uint32_t verdict, uint64_t r, uint32_t lane, uint32_t* __restrict__ sel, uint64_t W) {
+    const uint64_t ballot = __ballot(verdict != 0);
+    const uint32_t half = lane >> 5, bits = uint32_t(ballot >> (32 * half));
+    const uint64_t w = regex_word(r - lane, half);
+    if ((lane & 31) == 0 && bits && w < W) sel[w] |= bits;
+}
+
 // The group's bytes lie at base[0, g.n).  image: the class map and the table (image_bytes, a multiple of 16, at a 16-byte boundary).  in / out:
 // the carry slots this group reads and writes.  sel: the bitmap, W words.
 __global__ __launch_bounds__(kRegexThreads) void regex_mark_kernel(const uint8_t* __restrict__ base, RegexGroup g, uint64_t size, const uint64_t* __restrict__ D, uint64_t k, RegexBounds b,
@@ -53,7 +72,7 @@ __global__ __launch_bounds__(kRegexThreads) void regex_mark_kernel(const uint8_t
                                                                    const RegexCarry* __restrict__ in, RegexCarry* __restrict__ out, uint32_t* __restrict__ sel, uint64_t W) {
     extern __shared__ uint4 regex_lds[];
     const uint32_t tid = threadIdx.x, lane = tid & 63;
-    for (uint32_t i = tid; i < image_bytes / 16; i += kRegexThreads) regex_lds[i] = image[i];
+    regex_load_image(regex_lds, image, image_bytes, tid);
     __syncthreads();
     const uint8_t* cmap = reinterpret_cast<const uint8_t*>(regex_lds);
     const uint16_t* next = reinterpret_cast<const uint16_t*>(cmap + 256);
@@ -61,11 +80,7 @@ __global__ __launch_bounds__(kRegexThreads) void regex_mark_kernel(const uint8_t
     const uint8_t* al = base - mis;
     const RegexCarry carried = *in;
     auto at = [&](uint64_t j) { return D[j]; };
-    auto walk = [&](uint64_t from, uint64_t to, uint32_t state) {
-        return regex_walk_blocks(next, cmap, C,
-                                 [&](int64_t y, uint32_t* v) { const uint4 x = *reinterpret_cast<const uint4*>(al + y); v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w; },
-                                 [&](int64_t y) { return al[y]; }, ylo, yhi, int64_t(from - g.first) + mis, int64_t(to - g.first) + mis, state);
-    };
+    auto walk = [&](uint64_t from, uint64_t to, uint32_t state) { return regex_walk_memory(next, cmap, C, al, ylo, yhi, int64_t(from - g.first) + mis, int64_t(to - g.first) + mis, state); };
     const uint64_t slices = regex_slices(b);
     for (uint64_t s = blockIdx.x; s < slices; s += gridDim.x) {
         const uint64_t r = regex_lane_record(b, s * kRegexThreads + tid);
@@ -75,16 +90,26 @@ __global__ __launch_bounds__(kRegexThreads) void regex_mark_kernel(const uint8_t
             if (o.finished) verdict = o.verdict;
             else *out = o.carry;
         }
-        const uint64_t ballot = __ballot(verdict != 0);
-        const uint32_t half = lane >> 5, bits = uint32_t(ballot >> (32 * half));
-        const uint64_t w = regex_word(r - lane, half);
-        if ((lane & 31) == 0 && bits && w < W) sel[w] |= bits;
+        regex_put_marks(verdict, r, lane, sel, W);
     }
 }
 
 }  // namespace mlz
 
 namespace {
+
+// The longest record of the handle's index, for both regex greps: the reduction into *d_longest (zeroed by the caller) where the handle does not
+// know it yet; behind the caller's fetch regex_longest_keep; regex_longest_check refuses what no lane can walk, before any chunk is decoded.
+void regex_longest_launch(mlz_dev_reader* rd, hipStream_t sm, uint64_t* d_longest) {
+    const uint64_t items = rd->index_k + 1;
+    const uint32_t grid = uint32_t(std::min<uint64_t>((items + mlz::kRegexLongestThreads - 1) / mlz::kRegexLongestThreads, 1024));
+    hipLaunchKernelGGL(mlz::regex_longest_kernel, dim3(grid), dim3(mlz::kRegexLongestThreads), 0, sm, static_cast<const uint64_t*>(rd->d_index), rd->index_k, uint64_t(rd->size), d_longest);
+}
+void regex_longest_keep(mlz_dev_reader* rd, uint64_t longest) { rd->index_longest = longest; rd->index_longest_ready = true; }
+int regex_longest_check(mlz_dev_reader* rd, const char* call) {
+    if (rd->index_longest > uint64_t(rd->size)) { rd->ctx->err = std::string(call) + ": a record longer than the stream"; return -MLZ_ERR_HIP; }
+    return rd->index_longest > MLZ_REGEX_MAX_RECORD ? -MLZ_ERR_UNSUPPORTED : 0;
+}
 
 int64_t dev_reader_grep_regex_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const mlz::RegexProgram& pr, uint64_t before, uint64_t after, const GrepOut& out,
                                      uint64_t* totals, uint64_t* stats) {
@@ -130,17 +155,12 @@ int64_t dev_reader_grep_regex_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_
     pr.image(h_image);
     HIPCHK(c, hipMemcpyAsync(d_groups, h_groups, ng * sizeof(mlz::RegexGroup), hipMemcpyHostToDevice, sm));
     HIPCHK(c, hipMemcpyAsync(d_image, h_image, image_bytes, hipMemcpyHostToDevice, sm));
-    if (!rd->index_longest_ready) {
-        const uint64_t items = rd->index_k + 1;
-        const uint32_t grid = uint32_t(std::min<uint64_t>((items + mlz::kRegexLongestThreads - 1) / mlz::kRegexLongestThreads, 1024));
-        hipLaunchKernelGGL(mlz::regex_longest_kernel, dim3(grid), dim3(mlz::kRegexLongestThreads), 0, sm, D, rd->index_k, size, d_home);
-    }
+    if (!rd->index_longest_ready) regex_longest_launch(rd, sm, d_home);
     mlz::RegexBounds* d_bounds = reinterpret_cast<mlz::RegexBounds*>(d_home + 2);
     hipLaunchKernelGGL(mlz::regex_bounds_kernel, dim3(uint32_t((ng + 63) / 64)), dim3(64), 0, sm, D, rd->index_k, static_cast<const mlz::RegexGroup*>(d_groups), uint32_t(ng), d_bounds);
     if ((e = fetch(c, sm, h_home, d_home, (2 + 2 * ng) * sizeof(uint64_t)))) return e;
-    if (!rd->index_longest_ready) { rd->index_longest = h_home[0]; rd->index_longest_ready = true; }
-    if (rd->index_longest > size) { c->err = "mlz_dev_reader_grep_regex: a record longer than the stream"; return -MLZ_ERR_HIP; }
-    if (rd->index_longest > MLZ_REGEX_MAX_RECORD) return -MLZ_ERR_UNSUPPORTED;   // (no chunk has been decoded)
+    if (!rd->index_longest_ready) regex_longest_keep(rd, h_home[0]);
+    if ((e = regex_longest_check(rd, "mlz_dev_reader_grep_regex"))) return e;   // (no chunk has been decoded)
     std::vector<mlz::RegexBounds> bounds(ng);
     std::memcpy(bounds.data(), h_home + 2, ng * sizeof(mlz::RegexBounds));   // (the decode reuses the pinned buffer)
     for (size_t g = 0; g < ng; g++) {

@@ -380,15 +380,16 @@ class DeviceStream:
             if regex is not exprs:
                 regex.close()
 
-    def grep_regex(self, exprs, invert=False, before=0, after=0, max_records=1 << 20, count_only=False, ignore_crc=False, ignore_case=False):
+    def grep_regex(self, exprs, invert=False, before=0, after=0, max_records=1 << 20, count_only=False, ignore_crc=False, ignore_case=False, prune=False):
         """grep -E over the decoded stream's lines: grep() with the selected records decided by regular expressions over bytes — `exprs` is a
         bytes object, a sequence of up to 256 of them (a record is selected when it holds a match of any) or a compiled api.Regex (whose own
         ignore_case then holds); the syntax is the subset of Python's `re` that include/minlz_hip_regex.h lists, ^ and $ are a record's start
         and end, and an empty line is selected exactly when the expression matches the empty string (b"^$").  Every chunk is decoded once: no
-        search table prunes for an expression.  Lines longer than api.REGEX_MAX_RECORD raise ErrUnsupported.
+        search table prunes for an expression — unless prune is set: then only the chunks are decoded that the search tables admit for the
+        expression's required literals (api.Regex.literals), widened to whole lines, with the same result.  Lines longer than api.REGEX_MAX_RECORD raise ErrUnsupported.
         -> what grep returns: (R, numbers, kinds, data, starts), or with count_only (R, the selected records)."""
         R, totals, numbers, kinds = self._grep_regex_numbers(exprs, 0 if count_only else max_records, ignore_case=ignore_case, ignore_crc=ignore_crc, invert=invert, before=before,
-                                                             after=after)
+                                                             after=after, prune=prune)
         return self._grep_lines(R, totals, numbers, kinds, count_only, ignore_crc)
 
     def read_record_range(self, first, count, ignore_crc=False):
@@ -519,10 +520,10 @@ class DeviceStreamSet(DeviceStream):
         which, line = self.locate_records(numbers)
         return which, line, kinds
 
-    def grep_streams_regex(self, exprs, invert=False, before=0, after=0, max_records=1 << 20, ignore_crc=False, ignore_case=False):
+    def grep_streams_regex(self, exprs, invert=False, before=0, after=0, max_records=1 << 20, ignore_crc=False, ignore_case=False, prune=False):
         """grep -E -H -n over the set: grep_streams with the selected records decided by regular expressions (exprs as in grep_regex)
         -> (which, line_in_stream, kind).  grep_regex's first half followed by locate_records."""
-        _, _, numbers, kinds = self._grep_regex_numbers(exprs, max_records, ignore_case=ignore_case, ignore_crc=ignore_crc, invert=invert, before=before, after=after)
+        _, _, numbers, kinds = self._grep_regex_numbers(exprs, max_records, ignore_case=ignore_case, ignore_crc=ignore_crc, invert=invert, before=before, after=after, prune=prune)
         which, line = self.locate_records(numbers)
         return which, line, kinds
 
