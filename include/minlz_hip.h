@@ -534,7 +534,8 @@ int64_t mlz_dev_reader_search_records(mlz_dev_reader* reader, void* stream, uint
  * mlz_dev_reader_record_range: host convenience for "records first .. first + count - 1 as ONE range": *off = start(first), *len = end(first + count
  *   - 1) - start(first), the inner delimiters included; count == 0 gives length 0 (at start(first), or at size for first == N).  first + count > N:
  *   -MLZ_ERR_ARG.  Two table entries visit the host; the caller reads the range with mlz_dev_reader_read.  Returns 0.
- * Out of scope: delimiters of more than one byte; an index persisted into a stream or a sidecar; an index built while the Writer encodes.  Record
+ * The index saved as a compact blob, loaded from one without a decode, and built from the raw bytes that go to the Writer: include/minlz_hip_record_index_store.h.
+ * Out of scope: delimiters of more than one byte; the stored index as chunks inside the stream or inside a search sidecar.  Record
  *   numbers of the matching records come from mlz_dev_reader_grep_records below (mlz_dev_reader_search_records' signature stays). */
 int64_t mlz_dev_reader_index_records(mlz_dev_reader* reader, void* stream, uint32_t flags, uint8_t delimiter,
                                      uint64_t* info /* host, may be NULL: 4 values */);

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension headers include/minlz_hip_search_batch.h, include/minlz_hip_stream_set.h, include/minlz_hip_regex.h, include/minlz_hip_regex_prune.h, include/minlz_hip_search_compressed.h, include/minlz_hip_search_compress.h and include/minlz_hip_sidecar_extract.h.
+"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension headers include/minlz_hip_search_batch.h, include/minlz_hip_stream_set.h, include/minlz_hip_regex.h, include/minlz_hip_regex_prune.h, include/minlz_hip_search_compressed.h, include/minlz_hip_search_compress.h, include/minlz_hip_sidecar_extract.h and include/minlz_hip_record_index_store.h.
 
 There is no CPU fallback here: if libminlz_hip.so is missing or HIP is unavailable, calls raise.
 """
@@ -143,6 +143,14 @@ ABI_EXT = {
     "minlz_hip_sidecar_extract.h": {
         "mlz_dev_reader_extract_sidecar_bound": (i64, [vp, P(u64)]),
         "mlz_dev_reader_extract_sidecar": (i64, [vp, vp, u32, vp, sz, vp, sz, P(SidecarExtractResult)]),
+    },
+    "minlz_hip_record_index_store.h": {
+        "mlz_dev_reader_record_index_bound": (i64, [vp]),
+        "mlz_dev_reader_save_record_index": (i64, [vp, vp, vp, sz, P(u64)]),
+        "mlz_dev_reader_load_record_index": (i64, [vp, vp, u32, vp, sz, P(u64)]),
+        "mlz_record_index_bound": (i64, [u64]),
+        "mlz_record_index_build_device": (i64, [vp, vp, vp, sz, u8, vp, sz, P(u64)]),
+        "mlz_record_index_parse": (i64, [vp, sz, P(u64)]),
     },
 }
 

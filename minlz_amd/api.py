@@ -394,6 +394,14 @@ class Context:
                        d_stream_counts, d_pattern_counts, d_present, d_hit_stream, d_hit_pos, d_hit_which, cap, stats)
         return r, [int(out[i]) for i in range(n)], _ints(stats)
 
+    def record_index_build_device(self, d_raw, n, delimiter, d_dst, dst_cap, stream=None):
+        """mlz_record_index_build_device (include/minlz_hip_record_index_store.h): the record index blob of the n raw bytes at device address d_raw for
+        the one-byte `delimiter`, unbound, into dst_cap bytes at d_dst (record_index_bound(n) always suffices) — the index of a stream made while
+        the same bytes go to the device Writer.  -> (the blob's bytes, (bytes, sections, sparse tiles, dense tiles))."""
+        info = _stats()
+        r = self._call("mlz_record_index_build_device", stream, d_raw, n, _delimiter(delimiter, "record_index_build_device"), d_dst, dst_cap, info)
+        return r, _ints(info)
+
     def stream_open_device(self, d_src, n, stream=None):
         """mlz_stream_open_device: a stream in device memory opened for range reads -> DeviceReader.  The caller keeps d_src alive and unchanged
         while the reader is open.  A stream with a framing error raises that error (no reader)."""
@@ -640,6 +648,27 @@ class DeviceReader:
                 raise
         return SidecarExtract(*(int(getattr(out, name)) for name in SidecarExtract._fields))
 
+    def record_index_bound(self):
+        """mlz_dev_reader_record_index_bound (include/minlz_hip_record_index_store.h): bytes that always suffice for save_record_index; raises without an index."""
+        return self._call("mlz_dev_reader_record_index_bound")
+
+    def save_record_index(self, d_dst, dst_cap, stream=None):
+        """mlz_dev_reader_save_record_index: the handle's record index as a record index blob (about 2 bytes per record, bound to this stream) into
+        dst_cap bytes at device address d_dst -> (the blob's bytes, (bytes, sections, sparse tiles, dense tiles))."""
+        self._open()
+        info = _stats()
+        r = self._call("mlz_dev_reader_save_record_index", stream, d_dst, dst_cap, info)
+        return r, _ints(info)
+
+    def load_record_index(self, d_blob, n, ignore_crc=False, stream=None):
+        """mlz_dev_reader_load_record_index: the record index blob of n bytes at device address d_blob becomes this handle's record index; nothing is
+        decoded.  A blob that is malformed, fails a CRC or belongs to another stream raises, and the handle keeps the index it had.
+        -> (N, (N, delimiters, bytes of index held, 0))."""
+        self._open()
+        info = _stats()
+        r = self._call("mlz_dev_reader_load_record_index", stream, _flags(ignore_crc=ignore_crc), d_blob, n, info)
+        return r, _ints(info)
+
     def close(self):
         if self.handle:
             _lib.lib().mlz_dev_reader_close(self.handle)
@@ -753,6 +782,28 @@ def crc(b, ctx=None):
     """crc(b) of minlz.go:133-140 (masked CRC32C), computed on the device."""
     a = _np(b)
     return (ctx or default_context())._call("mlz_crc", _ptr(a), a.size)
+
+
+def record_index_bound(n):
+    """mlz_record_index_bound (include/minlz_hip_record_index_store.h): bytes that always suffice for Context.record_index_build_device over n raw
+    bytes; host only."""
+    r = _lib.lib().mlz_record_index_bound(n)
+    if r < 0:
+        _raise(r)
+    return int(r)
+
+
+def record_index_parse(blob):
+    """mlz_record_index_parse: the header chunk and the directory of a record index blob in host memory, checked against its length; needs no
+    context and no GPU -> a dict: flags, delimiter, size, k, N, longest (None when the blob does not know it), tag, data_chunks, nsections, bound.
+    An unknown magic raises ErrUnsupported, a malformed blob ErrCorrupt, a stale header CRC ErrCRC."""
+    a = _np(blob)
+    info = (C.c_uint64 * 8)()
+    r = _lib.lib().mlz_record_index_parse(_ptr(a) if a.size else info, a.size, info)
+    if r < 0:
+        _raise(r)
+    flags, delimiter, size, k, N, longest, tag, chunks = (int(v) for v in info)
+    return dict(flags=flags, delimiter=delimiter, size=size, k=k, N=N, longest=longest if flags & 2 else None, tag=tag, data_chunks=chunks, nsections=int(r), bound=bool(flags & 1))
 
 
 def expand_search_table(body, ignore_crc=False):

@@ -22,6 +22,7 @@
 #include "../../include/minlz_hip_search_compressed.h"
 #include "../../include/minlz_hip_search_compress.h"
 #include "../../include/minlz_hip_sidecar_extract.h"
+#include "../../include/minlz_hip_record_index_store.h"
 #include "mlz_format.h"
 #include "mlz_kernels.h"
 
@@ -1362,6 +1363,7 @@ int mlz_debug_idxprof(unsigned long long* out) {
 #include "mlz_stream_sidecar_extract.hip.inc"
 #include "mlz_stream_records.hip.inc"
 #include "mlz_stream_record_index.hip.inc"
+#include "mlz_stream_record_index_store.hip.inc"
 #include "mlz_stream_grep.hip.inc"
 #include "mlz_stream_set.hip.inc"
 #include "mlz_stream_regex.hip.inc"

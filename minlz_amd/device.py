@@ -183,6 +183,16 @@ class HipTensorCodec:
             p = ((bits[:n * words].view(n, words, 1) >> shifts) & 1).view(n, words * 32)[:, :len(pats)].bool()
         return counts, p, hs[:k], pos[:k], which[:k], pc[:len(pats)], total
 
+    def build_record_index(self, data, delimiter=b"\n"):
+        """The record index blob (include/minlz_hip_record_index_store.h) of the raw bytes `data` (uint8 tensor on the device) for the one-byte
+        `delimiter`, made without a stream: what DeviceStream.load_record_index takes for the stream these bytes are encoded into -> a new
+        uint8 tensor on data's device."""
+        data = _u8(data, "build_record_index")
+        cap = api.record_index_bound(data.numel())
+        out = torch.empty(cap, dtype=torch.uint8, device=data.device)
+        got, _ = self.ctx.record_index_build_device(data.data_ptr() if data.numel() else None, data.numel(), delimiter, out.data_ptr(), cap, stream=_stream(data.device))
+        return out[:got].clone()
+
     def open_stream(self, t):
         """A .mz stream that lies on the device (uint8 tensor) opened for range reads -> DeviceStream (ReadAt, read_ranges).  The chunk walk
         runs once, here; a framing error raises."""
@@ -426,6 +436,21 @@ class DeviceStream:
         main = torch.empty(main_cap, dtype=torch.uint8, device=self.dev) if strip else None
         got = self.reader.extract_sidecar(side.data_ptr(), side_cap, main.data_ptr() if strip else None, main_cap if strip else 0, stream=_stream(self.dev))
         return (side[:got.side_len].clone(), main[:got.main_len].clone()) if strip else side[:got.side_len].clone()
+
+    def save_record_index(self):
+        """The stream's record index (index_records, or a load) as a record index blob: about 2 bytes per record, bound to this stream ->
+        a new uint8 tensor on the stream's device.  load_record_index of a later open of the same stream takes it in the place of the decode."""
+        cap = self.reader.record_index_bound()
+        out = torch.empty(cap, dtype=torch.uint8, device=self.dev)
+        got, _ = self.reader.save_record_index(out.data_ptr(), cap, stream=_stream(self.dev))
+        return out[:got].clone()
+
+    def load_record_index(self, blob, ignore_crc=False):
+        """The record index blob `blob` (a uint8 tensor on the stream's device: save_record_index's, or HipTensorCodec.build_record_index's
+        over the stream's raw bytes) becomes the stream's record index without a decode -> the number of records N.  A blob that is
+        malformed or belongs to another stream raises, and the stream keeps the index it had."""
+        blob = _u8(blob, "load_record_index", self.dev)
+        return self.reader.load_record_index(blob.data_ptr(), blob.numel(), ignore_crc=ignore_crc, stream=_stream(self.dev))[0]
 
     def ReadAt(self, n, offset, ignore_crc=False):
         """Up to n decoded bytes from `offset`, clamped at the end of the stream -> a new uint8 tensor."""
