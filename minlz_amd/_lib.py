@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension headers include/minlz_hip_search_batch.h, include/minlz_hip_stream_set.h, include/minlz_hip_regex.h, include/minlz_hip_regex_prune.h, include/minlz_hip_search_compressed.h, include/minlz_hip_search_compress.h, include/minlz_hip_sidecar_extract.h and include/minlz_hip_record_index_store.h.
+"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension headers include/minlz_hip_search_batch.h, include/minlz_hip_search_batch_prune.h, include/minlz_hip_stream_set.h, include/minlz_hip_regex.h, include/minlz_hip_regex_prune.h, include/minlz_hip_search_compressed.h, include/minlz_hip_search_compress.h, include/minlz_hip_sidecar_extract.h and include/minlz_hip_record_index_store.h.
 
 There is no CPU fallback here: if libminlz_hip.so is missing or HIP is unavailable, calls raise.
 """
@@ -112,6 +112,9 @@ SYMBOLS = list(ABI)
 ABI_EXT = {
     "minlz_hip_search_batch.h": {
         "mlz_stream_search_batch_device": (i64, [vp, vp, u32, vp, P(BlockDesc), i32, vp, vp, sz, P(i64), vp, vp, vp, vp, vp, vp, sz, P(u64)]),
+    },
+    "minlz_hip_search_batch_prune.h": {
+        "mlz_stream_search_batch_device_pruned": (i64, [vp, vp, u32, vp, P(BlockDesc), i32, vp, vp, sz, P(i64), vp, vp, vp, vp, vp, vp, sz, P(u64)]),
     },
     "minlz_hip_stream_set.h": {
         "mlz_stream_open_batch_device": (i64, [vp, vp, vp, P(BlockDesc), i32, P(i64), P(vp)]),

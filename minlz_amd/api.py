@@ -379,20 +379,25 @@ class Context:
         return [int(out[i]) for i in range(n)]
 
     def stream_search_batch_device(self, d_src, spans, patterns, d_stream_counts=None, d_pattern_counts=None, d_present=None, d_hit_stream=None, d_hit_pos=None,
-                                   d_hit_which=None, cap=0, ignore_crc=False, ignore_case=False, stream=None, flags=0):
+                                   d_hit_which=None, cap=0, ignore_crc=False, ignore_case=False, stream=None, flags=0, prune=False):
         """mlz_stream_search_batch_device: every stream (src_off, src_len) of the buffer at d_src searched for `patterns` (1 .. 4096 bytes objects
         of 1 .. 256 bytes) in one call.  Device addresses or None: d_stream_counts (n uint64), d_pattern_counts (one uint64 per pattern),
         d_present (n rows of ceil(patterns / 32) uint32: bit p of row i = pattern p occurs in stream i), d_hit_stream / d_hit_pos / d_hit_which
         (room for `cap` uint32 / uint64 / uint32: the smallest min(total, cap) triples in (stream, position, pattern) order).
         flags: further MLZ_* bits, as they are.
-        -> (total triples over the healthy streams, [result]: the occurrences in each stream or its -MLZ_ERR_*, (data chunks, chunks decoded over
-        all passes, streams that failed in the decode, scan passes))."""
+        prune: mlz_stream_search_batch_device_pruned (include/minlz_hip_search_batch_prune.h) — only the chunks that the streams' inline block
+        search tables cannot rule out are decoded; four more stats: chunks with a usable table in a pruned stream, streams of which nothing
+        was decoded, configuration classes found, streams decoded whole.
+        -> (total triples over the healthy streams, [result]: the occurrences in each stream or its -MLZ_ERR_*, stats): stats = (data chunks,
+        chunks decoded over all passes, streams that failed in the decode, scan passes), and with prune=True four values more (chunks with a
+        usable table in a pruned stream, streams of which no chunk was decoded although they hold bytes, configuration classes found, streams
+        that hold bytes and are decoded whole).  counter(16) then is the bytes the plan brought to the host, the classes' configurations apart."""
         arr = _block_descs(spans)
         n = len(arr)
-        out, stats = (C.c_int64 * max(n, 1))(), _stats()
-        r = self._call("mlz_stream_search_batch_device", stream, _flags(ignore_crc=ignore_crc, ignore_case=ignore_case) | flags, d_src, arr, n, *_patterns(patterns), out,
+        out, stats = (C.c_int64 * max(n, 1))(), (C.c_uint64 * 8)() if prune else _stats()
+        r = self._call("mlz_stream_search_batch_device_pruned" if prune else "mlz_stream_search_batch_device", stream, _flags(ignore_crc=ignore_crc, ignore_case=ignore_case) | flags, d_src, arr, n, *_patterns(patterns), out,
                        d_stream_counts, d_pattern_counts, d_present, d_hit_stream, d_hit_pos, d_hit_which, cap, stats)
-        return r, [int(out[i]) for i in range(n)], _ints(stats)
+        return r, [int(out[i]) for i in range(n)], _ints(stats, 8 if prune else 4)
 
     def record_index_build_device(self, d_raw, n, delimiter, d_dst, dst_cap, stream=None):
         """mlz_record_index_build_device (include/minlz_hip_record_index_store.h): the record index blob of the n raw bytes at device address d_raw for

@@ -18,6 +18,7 @@
 
 #include "../../include/minlz_hip.h"
 #include "../../include/minlz_hip_search_batch.h"
+#include "../../include/minlz_hip_search_batch_prune.h"
 #include "../../include/minlz_hip_stream_set.h"
 #include "../../include/minlz_hip_search_compressed.h"
 #include "../../include/minlz_hip_search_compress.h"
@@ -164,6 +165,7 @@ struct mlz_ctx {
     DevBuf d_rplan;              // mlz_dev_reader_read_device: the plan kernels' workspace (16 bytes per range, 28 per chunk of the stream)
     DevBuf d_records, d_rwin;    // mlz_dev_reader_search_records: what lives across its read phase (the occurrences, windows and records: about 100 bytes per occurrence), and the merged windows' bytes (at most the decoded size)
     uint64_t range_plan_host = 0;   // plan bytes that crossed between host and device in the last mlz_dev_reader_read_device (mlz_get_counter 9)
+    uint64_t search_plan_bytes = 0;                 // the last mlz_stream_search_batch_device_pruned: bytes its plan brought to the host, the classes' configurations apart (mlz_get_counter 16)
     uint64_t search_compressed = 0;                 // of search_tables, the chunks whose usable table came from a compressed chunk, 0x46 (mlz_get_counter 14)
     uint64_t search_chunks = 0, search_tables = 0;  // the last mlz_dev_reader_search: chunks decoded or copied, chunks with a usable table (mlz_get_counter 10 / 11)
     uint64_t range_chunks = 0, range_scratch = 0;   // the last range read: chunks decoded or copied, decoded bytes that went through d_range (mlz_get_counter 7 / 8)
@@ -730,14 +732,10 @@ int decode_device_locked(mlz_ctx* c, hipStream_t st, const uint8_t* d_src, uint8
     });
 }
 
-int crc_device_locked(mlz_ctx* c, hipStream_t st, const uint8_t* d_base, const mlz_block_desc* desc, int n, uint32_t* d_out) {
-    if (n <= 0) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    WorkspaceOrder order(c, st);
-    c->call_seq++;
-    uint32_t tiles = 0;
-    int r = upload_blocks(c, st, desc, n, false, &tiles, nullptr, nullptr, true);
-    if (r) return r;
+// The CRC pass over blocks whose descriptors lie on the device: d_blocks[i] names block i's bytes at d_base (src_off, src_len) and its
+// tiles [first_tile, first_tile + n_tiles) of the `tiles` tiles in all, d_tile_block[t] the block of tile t.  crc_device_locked makes the
+// two from host descriptors; the pruned batch search makes them by a kernel from the tables it located (mlz_stream_search_batch_prune.hip.inc).
+int crc_device_described(mlz_ctx* c, hipStream_t st, const uint8_t* d_base, const BlockInfo* d_blocks, const uint32_t* d_tile_block, uint32_t tiles, int n, uint32_t* d_out) {
     static CrcPow pw;
     static CrcTabs tabs;
     static std::once_flag once;
@@ -757,12 +755,21 @@ int crc_device_locked(mlz_ctx* c, hipStream_t st, const uint8_t* d_base, const m
     HIPCHK(c, c->d_crc_tiles.ensure(sizeof(uint32_t) * (size_t(tiles) + 1)));
     Timer t(c, T_CRC, st);
     if (tiles)
-        hipLaunchKernelGGL(crc_tile_kernel, dim3(tiles), dim3(256), 0, st, d_base, c->d_blocks_cur().as<BlockInfo>(), c->d_tile_block_cur().as<uint32_t>(),
-                           c->d_crc_tabs.as<CrcTabs>(), pw, c->d_crc_tiles.as<uint32_t>());
-    hipLaunchKernelGGL(crc_block_kernel, dim3(n), dim3(64), 0, st, c->d_blocks_cur().as<BlockInfo>(), c->d_crc_tiles.as<uint32_t>(), c->d_crc_tabs.as<CrcTabs>(), pw,
-                       d_out, n);
+        hipLaunchKernelGGL(crc_tile_kernel, dim3(tiles), dim3(256), 0, st, d_base, d_blocks, d_tile_block, c->d_crc_tabs.as<CrcTabs>(), pw, c->d_crc_tiles.as<uint32_t>());
+    hipLaunchKernelGGL(crc_block_kernel, dim3(n), dim3(64), 0, st, d_blocks, c->d_crc_tiles.as<uint32_t>(), c->d_crc_tabs.as<CrcTabs>(), pw, d_out, n);
     HIPCHK(c, hipGetLastError());
     return 0;
+}
+
+int crc_device_locked(mlz_ctx* c, hipStream_t st, const uint8_t* d_base, const mlz_block_desc* desc, int n, uint32_t* d_out) {
+    if (n <= 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    WorkspaceOrder order(c, st);
+    c->call_seq++;
+    uint32_t tiles = 0;
+    int r = upload_blocks(c, st, desc, n, false, &tiles, nullptr, nullptr, true);
+    if (r) return r;
+    return crc_device_described(c, st, d_base, c->d_blocks_cur().as<BlockInfo>(), c->d_tile_block_cur().as<uint32_t>(), tiles, n, d_out);
 }
 
 // Device-visible address of the host range [p, p + len) when ALL of it lies in one page-locked (pinned, registered) allocation, else 0:
@@ -1268,6 +1275,7 @@ int64_t mlz_get_counter(mlz_ctx* c, int which) {
     if (which == 12) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->batch_long); }
     if (which == 13) { std::lock_guard<std::mutex> lk(c->mu); return c->acc_call == c->dec_call ? int64_t(c->l0_launches) : 0; }   // groups of the last decode call that took dec_level0_kernel's launch
     if (which == 14) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->search_compressed); }
+    if (which == 16) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->search_plan_bytes); }
     if (which == 15) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->tables_compressed); }
     if (which == 10 || which == 11) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(which == 10 ? c->search_chunks : c->search_tables); }
     std::lock_guard<std::mutex> lk(c->q_mu);
@@ -1358,6 +1366,7 @@ int mlz_debug_idxprof(unsigned long long* out) {
 #include "mlz_stream_search.hip.inc"
 #include "mlz_stream_search_many.hip.inc"
 #include "mlz_stream_search_batch.hip.inc"
+#include "mlz_stream_search_batch_prune.hip.inc"
 #include "mlz_stream_sidecar.hip.inc"
 #include "mlz_stream_sidecar_extract.h"
 #include "mlz_stream_sidecar_extract.hip.inc"

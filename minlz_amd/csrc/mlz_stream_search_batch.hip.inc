@@ -48,8 +48,9 @@ struct SearchBatchOut {
 };
 
 // One pass: the streams with alive[i] are decoded and scanned.  rc[i] = 0 or the stream's first failing chunk's error; *total and counts[i]
-// are valid (and the device outputs written) when no stream failed.  *n_jobs: the chunks the pass decoded.
-int64_t stream_search_batch_pass(mlz_ctx* c, hipStream_t sm, bool ignore_crc, const uint8_t* d_src, const BatchWalk& bw, size_t n, const std::vector<uint8_t>& alive,
+// are valid (and the device outputs written) when no stream failed.  *n_jobs: the chunks the pass decoded.  take (may be NULL: every chunk
+// that has bytes): a byte per chunk of the walk, the plan of the pruned call (mlz_stream_search_batch_prune.hip.inc).
+int64_t stream_search_batch_pass(mlz_ctx* c, hipStream_t sm, bool ignore_crc, const uint8_t* d_src, const BatchWalk& bw, size_t n, const std::vector<uint8_t>& alive, const uint8_t* take,
                                  SearchManyScan& scan, const SearchBatchOut& out, std::vector<int64_t>* rc, std::vector<uint64_t>* counts, uint64_t* total, size_t* n_jobs,
                                  bool* failed) {
     // the virtual positions and the one job list: every alive stream's chunks that have bytes, in descriptor order
@@ -63,7 +64,7 @@ int64_t stream_search_batch_pass(mlz_ctx* c, hipStream_t sm, bool ignore_crc, co
     for (size_t i = 0; i < n; i++) {
         job_first[i] = jobs.size();
         for (size_t k = bw.c0[i]; alive[i] && k < bw.c1[i]; k++)
-            if (bw.chunks[k].n) { jobs.push_back(ChunkJob{k, nullptr}); voff.push_back(vbase[i] + bw.chunks[k].out_off); }
+            if (bw.chunks[k].n && (!take || take[k])) { jobs.push_back(ChunkJob{k, nullptr}); voff.push_back(vbase[i] + bw.chunks[k].out_off); }
     }
     job_first[n] = jobs.size();
     *n_jobs = jobs.size();
@@ -131,17 +132,10 @@ int64_t stream_search_batch_pass(mlz_ctx* c, hipStream_t sm, bool ignore_crc, co
     return 0;
 }
 
-// mlz_stream_search_batch_device behind its argument checks.  Returns the number of all triples or -MLZ_ERR_*; the streams' results go to out_count.
-int64_t stream_search_batch_locked(mlz_ctx* c, hipStream_t sm, uint32_t flags, const uint8_t* d_src, const mlz_block_desc* streams, size_t n, const uint8_t* patterns,
-                                   const uint32_t* pattern_len, size_t np, int64_t* out_count, const SearchBatchOut& out, uint64_t* stats) {
-    const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0;
-    BatchWalk bw;
-    int r = stream_batch_walk(c, sm, d_src, streams, n, &bw);
-    if (r) return r;
-    begin_decode_call(c);
-    c->search_chunks = c->search_tables = c->search_compressed = 0;
-    SearchManyScan scan;
-    scan.prepare(flags, patterns, pattern_len, np);
+// The passes of both calls behind the walk: the first over every stream without a framing error, a second over the rest when a stream's
+// decode failed.  out_count[i] and the device outputs as the contract says; four[0 .. 3] = the call's first four stats.  take: the pass's.
+int64_t stream_search_batch_passes(mlz_ctx* c, hipStream_t sm, bool ignore_crc, const uint8_t* d_src, const BatchWalk& bw, size_t n, const uint8_t* take, SearchManyScan& scan,
+                                   int64_t* out_count, const SearchBatchOut& out, uint64_t* four) {
     // a stream with a framing error keeps the walk's code, and nothing of it is searched
     std::vector<uint8_t> alive(n);
     std::vector<int64_t> verdict(n, 0), rc;
@@ -151,7 +145,7 @@ int64_t stream_search_batch_locked(mlz_ctx* c, hipStream_t sm, uint32_t flags, c
     for (;;) {
         size_t n_jobs = 0;
         bool failed = false;
-        const int64_t e = stream_search_batch_pass(c, sm, ignore_crc, d_src, bw, n, alive, scan, out, &rc, &counts, &total, &n_jobs, &failed);
+        const int64_t e = stream_search_batch_pass(c, sm, ignore_crc, d_src, bw, n, alive, take, scan, out, &rc, &counts, &total, &n_jobs, &failed);
         if (e < 0) return e;
         decoded += n_jobs;
         passes += n_jobs ? 1 : 0;
@@ -167,8 +161,39 @@ int64_t stream_search_batch_locked(mlz_ctx* c, hipStream_t sm, uint32_t flags, c
     }
     for (size_t i = 0; i < n; i++) out_count[i] = verdict[i] < 0 ? verdict[i] : int64_t(counts[i]);
     c->search_chunks = decoded;
-    if (stats) { stats[0] = bw.chunks.size(); stats[1] = decoded; stats[2] = bad; stats[3] = passes; }
+    four[0] = bw.chunks.size(); four[1] = decoded; four[2] = bad; four[3] = passes;
     return int64_t(total);
+}
+
+// mlz_stream_search_batch_device behind its argument checks.  Returns the number of all triples or -MLZ_ERR_*; the streams' results go to out_count.
+int64_t stream_search_batch_locked(mlz_ctx* c, hipStream_t sm, uint32_t flags, const uint8_t* d_src, const mlz_block_desc* streams, size_t n, const uint8_t* patterns,
+                                   const uint32_t* pattern_len, size_t np, int64_t* out_count, const SearchBatchOut& out, uint64_t* stats) {
+    BatchWalk bw;
+    int r = stream_batch_walk(c, sm, d_src, streams, n, &bw);
+    if (r) return r;
+    begin_decode_call(c);
+    c->search_chunks = c->search_tables = c->search_compressed = 0;
+    SearchManyScan scan;
+    scan.prepare(flags, patterns, pattern_len, np);
+    uint64_t four[4];
+    const int64_t total = stream_search_batch_passes(c, sm, (flags & MLZ_STREAM_IGNORE_CRC) != 0, d_src, bw, n, nullptr, scan, out_count, out, four);
+    if (total >= 0 && stats) for (int i = 0; i < 4; i++) stats[i] = four[i];
+    return total;
+}
+
+// The argument checks of both calls.  Returns 0 with *run = the context that serves the call and its lock still to be taken, 1 (n_streams == 0) or -MLZ_ERR_ARG.
+int search_batch_args(mlz_ctx* c, uint32_t flags, const uint8_t* d_src, const mlz_block_desc* streams, int n_streams, const uint8_t* patterns, const uint32_t* pattern_len,
+                      size_t n_patterns, const int64_t* out_count, const uint32_t* d_hit_stream, const uint64_t* d_hit_pos, const uint32_t* d_hit_which, size_t cap, mlz_ctx** run) {
+    if (flags & ~uint32_t(MLZ_STREAM_IGNORE_CRC | MLZ_SEARCH_IGNORE_CASE | MLZ_SEARCH_NO_TABLES)) return -MLZ_ERR_ARG;
+    if (n_patterns == 0 || search_pattern_list(patterns, pattern_len, n_patterns) < 0 || (cap && (!d_hit_stream || !d_hit_pos || !d_hit_which))) return -MLZ_ERR_ARG;
+    return batch_args(c, d_src, nullptr, false, streams, n_streams, out_count, run);
+}
+
+// ... and those of the device outputs, under the context's lock
+bool search_batch_outputs_on_device(mlz_ctx* c, const SearchBatchOut& out) {
+    for (const void* p : {static_cast<const void*>(out.d_stream_counts), static_cast<const void*>(out.d_pattern_counts), static_cast<const void*>(out.d_present)})
+        if (p && !on_device(c, p)) return false;
+    return !out.cap || (on_device(c, out.d_hit_stream) && on_device(c, out.d_hit_pos) && on_device(c, out.d_hit_which));
 }
 
 }  // namespace
@@ -177,19 +202,15 @@ extern "C" int64_t mlz_stream_search_batch_device(mlz_ctx* c, void* stream, uint
                                                   const uint8_t* patterns, const uint32_t* pattern_len, size_t n_patterns, int64_t* out_count, uint64_t* d_stream_counts,
                                                   uint64_t* d_pattern_counts, uint32_t* d_present, uint32_t* d_hit_stream, uint64_t* d_hit_pos, uint32_t* d_hit_which, size_t cap,
                                                   uint64_t* stats) {
-    if (flags & ~uint32_t(MLZ_STREAM_IGNORE_CRC | MLZ_SEARCH_IGNORE_CASE | MLZ_SEARCH_NO_TABLES)) return -MLZ_ERR_ARG;
-    if (n_patterns == 0 || search_pattern_list(patterns, pattern_len, n_patterns) < 0 || (cap && (!d_hit_stream || !d_hit_pos || !d_hit_which))) return -MLZ_ERR_ARG;
-    const int a = batch_args(c, d_src, nullptr, false, streams, n_streams, out_count, &c);
+    const int a = search_batch_args(c, flags, d_src, streams, n_streams, patterns, pattern_len, n_patterns, out_count, d_hit_stream, d_hit_pos, d_hit_which, cap, &c);
     if (a) {
         if (a > 0 && stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
         return a < 0 ? a : 0;
     }
     std::lock_guard<std::mutex> lk(c->mu);
     if (enter_device(c)) return -MLZ_ERR_HIP;
-    for (const void* p : {static_cast<const void*>(d_stream_counts), static_cast<const void*>(d_pattern_counts), static_cast<const void*>(d_present)})
-        if (p && !on_device(c, p)) return -MLZ_ERR_ARG;
-    if (cap && (!on_device(c, d_hit_stream) || !on_device(c, d_hit_pos) || !on_device(c, d_hit_which))) return -MLZ_ERR_ARG;
-    hipStream_t sm = static_cast<hipStream_t>(stream);
     const SearchBatchOut out{d_stream_counts, d_pattern_counts, d_present, d_hit_stream, d_hit_pos, d_hit_which, uint64_t(cap)};
+    if (!search_batch_outputs_on_device(c, out)) return -MLZ_ERR_ARG;
+    hipStream_t sm = static_cast<hipStream_t>(stream);
     return settled(sm, stream_search_batch_locked(c, sm, flags, d_src, streams, size_t(n_streams), patterns, pattern_len, n_patterns, out_count, out, stats));
 }

@@ -150,7 +150,7 @@ class HipTensorCodec:
                 self._raise_stream("encode_streams", i, r)
         return out, [(d[2], r) for d, r in zip(descs, res)]
 
-    def search_streams(self, t, spans, patterns, max_results=0, present=True, ignore_crc=False, ignore_case=False, on_error="raise"):
+    def search_streams(self, t, spans, patterns, max_results=0, present=True, ignore_crc=False, ignore_case=False, on_error="raise", prune=False):
         """Which of many .mz streams that lie in one uint8 tensor on the device (stream i at t[off_i : off_i + len_i] for spans[i]) hold which
         of `patterns` (1 .. 4096 bytes objects of 1 .. 256 bytes), and where, in one call (mlz_stream_search_batch_device) ->
         (counts, present, hit_stream, hit_pos, hit_which, pattern_counts, total), tensors on t's device: every stream's occurrences (int64, n
@@ -158,7 +158,9 @@ class HipTensorCodec:
         the smallest min(total, max_results) triples in (stream, position inside the stream's decoded bytes, pattern) order (int32, int64,
         int32); every pattern's occurrences (int64); the number of all triples.
         on_error "raise": the first failing stream's error, which names its index (.index), as decode_streams; "keep": that stream's
-        negative code in counts, its row of present False, and the other streams' results as without it."""
+        negative code in counts, its row of present False, and the other streams' results as without it.
+        prune: decode only the chunks that the streams' inline block search tables cannot rule out (mlz_stream_search_batch_device_pruned);
+        the same results for streams whose tables are truthful."""
         if on_error not in ("raise", "keep"):
             raise ValueError("search_streams: on_error is \"raise\" or \"keep\"")
         t = _u8(t, "search_streams")
@@ -171,7 +173,7 @@ class HipTensorCodec:
         pc, _ = _room(len(pats), torch.int64, dev, torch.zeros)
         bits, d_bits = _room(n * words if present else 0, torch.int32, dev, torch.zeros)
         total, res, _ = self.ctx.stream_search_batch_device(t.data_ptr(), spans, pats, None, pc.data_ptr(), d_bits, d_hs, d_pos, d_which, max_results, ignore_crc=ignore_crc,
-                                                            ignore_case=ignore_case, stream=_stream(dev))
+                                                            ignore_case=ignore_case, stream=_stream(dev), prune=prune)
         for i, r in enumerate(res):
             if r < 0 and on_error == "raise":
                 self._raise_stream("search_streams", i, r)
