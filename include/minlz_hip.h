@@ -171,7 +171,7 @@ int mlz_crc_batch_device(mlz_ctx* ctx, void* stream, const uint8_t* d_base, cons
 /* Compressed table chunks (0x46, SPEC_SEARCH.md 2.2) from the device-resident Writer: honoured by mlz_stream_encode_gather_device, _tables and
  * _long_prefix, where it needs tables (-MLZ_ERR_ARG without a configuration), and by mlz_dev_reader_build_sidecar; accepted and without effect in
  * mlz_stream_bound* (a 0x46 chunk is only written where it is smaller than the 0x45 chunk of the same table); without effect in mlz_stream_encode and
- * mlz_stream_encode_batch_device, which write no tables.  See mlz_stream_encode_gather_device below and include/minlz_hip_search_compress.h. */
+ * mlz_stream_encode_batch_device (its form with tables, mlz_stream_encode_batch_device_tables, refuses the flag).  See mlz_stream_encode_gather_device below and include/minlz_hip_search_compress.h. */
 #define MLZ_STREAM_SEARCH_COMPRESS (1u << 6)   /* 64u */
 int64_t mlz_stream_bound(uint64_t n, uint32_t block_size, uint32_t flags); /* dst_cap that always suffices */
 int64_t mlz_stream_encode(mlz_ctx* ctx, int level, uint32_t block_size, uint32_t flags, const uint8_t* src, size_t n, uint8_t* dst,
@@ -301,7 +301,7 @@ int64_t mlz_stream_decode_device(mlz_ctx* ctx, void* stream, uint32_t flags, con
  * mlz_stream_encode_batch_device: NewWriter(dst_i, level, block size, index).EncodeBuffer(src_i) + Close(), for every i.  out_len[i] and
  *   d_dst[dst_off, +out_len[i]) are byte for byte what mlz_stream_encode_gather_device gives for the one range (d_src + src_off, src_len); dst_cap below
  *   mlz_stream_bound(src_len, block_size, flags) gives that stream -MLZ_ERR_DST_TOO_SMALL and writes nothing of it.  MLZ_STREAM_ADD_INDEX is honoured;
- *   MLZ_STREAM_SEARCH_TABLES or match-length bits fail the whole call with -MLZ_ERR_ARG (tables in batches are out of scope), and the level and the
+ *   MLZ_STREAM_SEARCH_TABLES or match-length bits fail the whole call with -MLZ_ERR_ARG (tables in batches: mlz_stream_encode_batch_device_tables, include/minlz_hip_encode_batch_tables.h), and the level and the
  *   block size are checked as in the single call.
  *
  * The walk: one lane per stream steps through its chunk headers from offset 0, first counting the table's entries, then — after a scan of the counts —
@@ -312,7 +312,8 @@ int64_t mlz_stream_decode_device(mlz_ctx* ctx, void* stream, uint32_t flags, con
  * Decode: the chunks of all streams run as one list through the decode and CRC kernels (groups of about 64 MiB), stored chunks by one copy kernel; 12 bytes
  * per chunk come back.  Encode: the blocks of all streams through one encode and one CRC launch sequence; 12 bytes per block visit the host, which lays
  * every stream out; bodies, identifiers, EOF chunks and indexes are placed by one kernel, chunk headers by another.
- * Out of scope: search tables written by the batch encode and sidecars in batches (mlz_stream_search_batch_device decodes every chunk), an asynchronous form, a batch fanned out over several devices. */
+ * Search tables in batches are written by mlz_stream_encode_batch_device_tables (include/minlz_hip_encode_batch_tables.h) and read by mlz_stream_search_batch_device_pruned.
+ * Out of scope: sidecars in batches, an asynchronous form, a batch fanned out over several devices. */
 int mlz_stream_decoded_len_batch_device(mlz_ctx* ctx, void* stream, const uint8_t* d_src, const mlz_block_desc* streams, int n_streams, int64_t* out_len,
                                         uint64_t* prefix_len);
 int mlz_stream_decode_batch_device(mlz_ctx* ctx, void* stream, uint32_t flags, const uint8_t* d_src, uint8_t* d_dst, const mlz_block_desc* streams,
@@ -703,6 +704,7 @@ const char* mlz_timer_name(int idx);
  * which = 10 / 11: the context's last mlz_dev_reader_search, mlz_dev_reader_search_many or search phase of mlz_dev_reader_search_records or mlz_dev_reader_grep_records: 10 = chunks it decoded or copied, 11 = chunks with a usable search table (0 when the call
  *            used none: MLZ_SEARCH_NO_TABLES, no info chunk, a pattern shorter than M).
  * which = 12: streams that the context's last mlz_stream_*_batch_device call sent through the region walk because they hold more than 4096 chunk headers.
+ * which = 17: bytes of table slots the context's last mlz_stream_encode_batch_device_tables call carved (include/minlz_hip_encode_batch_tables.h).
  * which = 13 (debug, tests; no name in the Python module): internal groups of the last decode call whose level-0 candidates, verdicts and schedule went in one launch (MLZ_OPT_LEVEL0_KERNEL); 0 = every group took the separate kernels. */
 int64_t mlz_get_counter(mlz_ctx* ctx, int which);
 

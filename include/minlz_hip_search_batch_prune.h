@@ -18,6 +18,7 @@ extern "C" {
  *     mlz_dev_reader_search_many with the same CRC and case flags and WITHOUT MLZ_SEARCH_NO_TABLES returns, summed over the patterns: an error in a chunk
  *     the plan pruned goes unnoticed, as in every search that prunes.  A pattern never matches across two streams; one stream's error changes nothing
  *     for another.
+ *   A batch with inline tables is written in one call by mlz_stream_encode_batch_device_tables (include/minlz_hip_encode_batch_tables.h).
  *   Which chunks are decoded: for stream i exactly the set mlz_dev_reader_search_many on stream i alone decodes — the union over the patterns of the
  *     rule of SPEC_SEARCH.md Appendix B.4.1, and every chunk with bytes once any pattern is not served by the stream's configuration (a pattern
  *     shorter than M, no window behind a prefix byte; under MLZ_SEARCH_IGNORE_CASE the budget of case-variant hashes as well) — with two exceptions:
@@ -37,7 +38,7 @@ extern "C" {
  *   Traffic to the host for the plan, besides the walk's: at most 32 bytes per stream plus one byte per data chunk — 16 bytes of key and one of class
  *     verdict per stream, one byte per data chunk, and unless MLZ_STREAM_IGNORE_CRC is given 4 bytes per CRC round (two rounds where no table is
  *     stale) —, and a class's configuration (264 bytes) once per class.  mlz_get_counter 16 reports the bytes of the last call, the configurations apart.
- *   Out of scope: compressed tables (0x46) and sidecars in batches, more than 4 pruning classes, tables written by mlz_stream_encode_batch_device, a
+ *   Out of scope: compressed tables (0x46) and sidecars in batches, more than 4 pruning classes, a
  *     per-(stream, pattern) count matrix, an asynchronous form, a batch fanned out over several devices. */
 int64_t mlz_stream_search_batch_device_pruned(mlz_ctx* ctx, void* stream, uint32_t flags,
                                               const uint8_t* d_src, const mlz_block_desc* streams, int n_streams,

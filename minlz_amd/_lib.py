@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension headers include/minlz_hip_search_batch.h, include/minlz_hip_search_batch_prune.h, include/minlz_hip_stream_set.h, include/minlz_hip_regex.h, include/minlz_hip_regex_prune.h, include/minlz_hip_search_compressed.h, include/minlz_hip_search_compress.h, include/minlz_hip_sidecar_extract.h and include/minlz_hip_record_index_store.h.
+"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension headers include/minlz_hip_search_batch.h, include/minlz_hip_search_batch_prune.h, include/minlz_hip_stream_set.h, include/minlz_hip_regex.h, include/minlz_hip_regex_prune.h, include/minlz_hip_search_compressed.h, include/minlz_hip_search_compress.h, include/minlz_hip_sidecar_extract.h, include/minlz_hip_record_index_store.h and include/minlz_hip_encode_batch_tables.h.
 
 There is no CPU fallback here: if libminlz_hip.so is missing or HIP is unavailable, calls raise.
 """
@@ -155,6 +155,11 @@ ABI_EXT = {
         "mlz_record_index_build_device": (i64, [vp, vp, vp, sz, u8, vp, sz, P(u64)]),
         "mlz_record_index_parse": (i64, [vp, sz, P(u64)]),
     },
+    "minlz_hip_encode_batch_tables.h": {
+        "mlz_stream_bound_config": (i64, [u64, u32, u32, P(SearchConfig)]),
+        "mlz_search_table_prefold": (i64, [u64, u32, u32]),
+        "mlz_stream_encode_batch_device_tables": (i32, [vp, vp, i32, u32, u32, P(SearchConfig), vp, vp, P(BlockDesc), i32, P(i64)]),
+    },
 }
 
 # mlz_get_counter(ctx, 14): of the chunks with a usable search table in the last search (counter 11), those whose table came from a compressed
@@ -162,6 +167,8 @@ ABI_EXT = {
 COUNTER_SEARCH_COMPRESSED = 14
 # mlz_get_counter(ctx, 15): table chunks the last device Writer or build_sidecar call wrote compressed, as 0x46 (api.Context.tables_written_compressed)
 COUNTER_TABLES_COMPRESSED = 15
+# mlz_get_counter(ctx, 17): bytes of table slots the last stream_encode_batch_device with search tables carved (api.Context.table_slot_bytes)
+COUNTER_TABLE_SLOT_BYTES = 17
 
 _lib = None
 

@@ -284,6 +284,12 @@ class Context:
         """Table chunks the context's last stream_encode_gather_device or build_sidecar wrote compressed, as 0x46 (mlz_get_counter 15)."""
         return self.counter(_lib.COUNTER_TABLES_COMPRESSED)
 
+    @property
+    def table_slot_bytes(self):
+        """Bytes of workspace the context's last stream_encode_batch_device with search tables carved for its blocks' tables: 2^(B - r0 - 3) per
+        block of a stream that had room, r0 = the folds the block's length makes certain (mlz_get_counter 17)."""
+        return self.counter(_lib.COUNTER_TABLE_SLOT_BYTES)
+
     def range_plan_host_bytes(self):
         """Bytes of plan data that crossed between host and device, both directions together, in the context's last DeviceReader.read_device
         (mlz_get_counter 9): a header and two records per TOUCHED CHUNK, nothing per range."""
@@ -369,13 +375,22 @@ class Context:
         self._call("mlz_stream_decode_batch_device", stream, _flags(ignore_crc=ignore_crc), d_src, d_dst, arr, n, out)
         return [int(out[i]) for i in range(n)]
 
-    def stream_encode_batch_device(self, level, block_size, add_index, d_src, d_dst, descs, stream=None, flags=0):
+    def stream_encode_batch_device(self, level, block_size, add_index, d_src, d_dst, descs, stream=None, flags=0, search_match_len=None, search_prefix=None,
+                                   search_long_prefix=None, search_extras=0):
         """mlz_stream_encode_batch_device: every input (src_off, src_len, dst_off, dst_cap) of the buffer at d_src written as a stream of its own to
-        its place in the buffer at d_dst -> [result]: the stream's size or -MLZ_ERR_* of each.  flags: further MLZ_STREAM_* bits, as they are."""
+        its place in the buffer at d_dst -> [result]: the stream's size or -MLZ_ERR_* of each.  flags: further MLZ_STREAM_* bits, as they are.
+        The search_* keywords are stream_encode_gather_device's: with search_match_len every stream carries block search tables of that one
+        configuration (mlz_stream_encode_batch_device_tables, include/minlz_hip_encode_batch_tables.h), byte for byte those of the gather
+        Writer on that input alone; api.stream_bound with the same keywords is a stream's room; table_slot_bytes then says what the tables
+        took of workspace."""
         arr = _block_descs(descs)
         n = len(arr)
         out = (C.c_int64 * max(n, 1))()
-        self._call("mlz_stream_encode_batch_device", stream, level, block_size, _flags(add_index=add_index) | flags, d_src, d_dst, arr, n, out)
+        cfg = batch_tables_config(search_match_len, search_prefix, search_long_prefix, search_extras)
+        if cfg is None:
+            self._call("mlz_stream_encode_batch_device", stream, level, block_size, _flags(add_index=add_index) | flags, d_src, d_dst, arr, n, out)
+        else:
+            self._call("mlz_stream_encode_batch_device_tables", stream, level, block_size, _flags(add_index=add_index) | flags, C.byref(cfg), d_src, d_dst, arr, n, out)
         return [int(out[i]) for i in range(n)]
 
     def stream_search_batch_device(self, d_src, spans, patterns, d_stream_counts=None, d_pattern_counts=None, d_present=None, d_hit_stream=None, d_hit_pos=None,
@@ -963,6 +978,25 @@ def _writer_tables(search_match_len, search_prefix, search_long_prefix, search_e
             raise ValueError("search_prefix needs search_match_len")
         return "_tables", 0, (C.byref(search_tables_config(search_match_len, search_prefix)),)
     return "", 0 if search_match_len is None else STREAM_SEARCH_TABLES | (search_match_len & 15) << 8, ()
+
+
+def batch_tables_config(search_match_len=None, search_prefix=None, search_long_prefix=None, search_extras=0):
+    """The Writer's search keywords -> the mlz_search_config of Context.stream_encode_batch_device, None without tables.  The table type is
+    chosen as the gather Writer chooses it: no prefix -> 1; 1 to 8 distinct prefix byte values -> 2 (sorted), more or none -> 3; a long
+    prefix -> 4."""
+    suffix, _, _ = _writer_tables(search_match_len, search_prefix, search_long_prefix, search_extras)   # (the keywords' own checks)
+    if search_match_len is None:
+        return None
+    if suffix == "_long_prefix":
+        return search_config(4, search_match_len, search_long_prefix, search_extras)
+    if suffix == "":
+        return search_config(1, search_match_len)
+    t = search_tables_config(search_match_len, search_prefix)
+    cfg = _lib.SearchConfig()
+    cfg.table_type, cfg.match_len, cfg.prefix_len = t.table_type, t.match_len, t.n_prefix
+    for i in range(32):
+        cfg.prefix[i] = t.prefix[i]
+    return cfg
 
 
 def stream_bound(n, block_size, add_index=False, search_match_len=None, search_prefix=None, search_long_prefix=None, search_extras=0, search_compress=False):

@@ -24,6 +24,7 @@
 #include "../../include/minlz_hip_search_compress.h"
 #include "../../include/minlz_hip_sidecar_extract.h"
 #include "../../include/minlz_hip_record_index_store.h"
+#include "../../include/minlz_hip_encode_batch_tables.h"
 #include "mlz_format.h"
 #include "mlz_kernels.h"
 
@@ -161,6 +162,7 @@ struct mlz_ctx {
     DevBuf d_batch;              // the batch calls over many streams: counts and places of the batch walk (8 bytes per stream, a flag bit each); its table is d_walk_tab
     DevBuf d_batch_desc;         // ... and the streams' descriptors on the device (32 bytes per stream)
     uint64_t batch_long = 0;     // streams the last batch call sent through the region walk (mlz_get_counter 12)
+    uint64_t table_slot_bytes = 0;   // bytes of table slots the last stream batch encode carved from d_stab (mlz_get_counter 17)
     DevBuf d_range;              // the device-resident ReadSeeker: where partly wanted chunks of a group are decoded (a group plus one block at the most)
     DevBuf d_rplan;              // mlz_dev_reader_read_device: the plan kernels' workspace (16 bytes per range, 28 per chunk of the stream)
     DevBuf d_records, d_rwin;    // mlz_dev_reader_search_records: what lives across its read phase (the occurrences, windows and records: about 100 bytes per occurrence), and the merged windows' bytes (at most the decoded size)
@@ -1277,6 +1279,7 @@ int64_t mlz_get_counter(mlz_ctx* c, int which) {
     if (which == 14) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->search_compressed); }
     if (which == 16) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->search_plan_bytes); }
     if (which == 15) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->tables_compressed); }
+    if (which == 17) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(c->table_slot_bytes); }
     if (which == 10 || which == 11) { std::lock_guard<std::mutex> lk(c->mu); return int64_t(which == 10 ? c->search_chunks : c->search_tables); }
     std::lock_guard<std::mutex> lk(c->q_mu);
     return which == 0 ? int64_t(c->q_batches) : which == 1 ? int64_t(c->q_requests) : -MLZ_ERR_ARG;

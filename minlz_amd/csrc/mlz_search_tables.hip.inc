@@ -29,6 +29,12 @@
 // Both forms share stab_zero, stab_share, stab_positions, stab_mark and stab_flush (the zeroing of the bitmap, a workgroup's (part, slice, block)
 //   and its positions, the slice-filtered bit and the write-out or merge); they stay kernels of their own: the short forms keep the bytes behind
 //   the range in a register, the long form in LDS.
+// The pre-folded block-list form (stab_build_kernel<*, true>, stab_build_long_kernel<true>, stab_reduce_fold_kernel; the batch Writer,
+//   mlz_stream_batch.hip.inc): a table's size comes from the call's block size, and in a batch every stream's last block is short, often its
+//   only one.  A block's record (StabFoldBlock) names r0 = search_prefold of the positions its length lets it index and its table's place:
+//   the block gets a slot of 2^(B - r0 - 3) bytes, its workgroup zeroes, marks (bit h & (2^(B - r0) - 1)) and writes 2^(min(B - r0, 20) - 5)
+//   words, a table that fits one slice uses slice 0 only (the grid stays one workgroup per (block, slice, part); the surplus ones return at
+//   once), and the reduce starts at R = r0.  The same (table, R) as the full build: mlz_stream_search.h says why.
 // stab_reduce_kernel: a workgroup per block counts the bits, applies the rules above fold by fold (search_reduce_rule's conditions) and leaves
 //   the table compact at the front of its slot; 8 bytes per block (table bytes or 0, R) go to the host next to the sizes and CRCs.
 
@@ -40,6 +46,9 @@ constexpr uint32_t kStabSliceBits = 20, kStabThreads = 1024, kStabPerThread = 8;
 // `over` bytes of the stream that follow it (the next data chunk's first ones, cut at that chunk's length) lie behind its last byte; beyond them zeros
 struct StabBlock { uint64_t off; uint32_t bytes, over; };
 static_assert(sizeof(StabBlock) == 16, "a record shared with the host");
+// The pre-folded form's record: the block is built folded r0 times, its table of 2^(B - r0 - 3) bytes lies tab_off bytes (a multiple of 32) into tabs
+struct StabFoldBlock : StabBlock { uint32_t r0, pad; uint64_t tab_off; };
+static_assert(sizeof(StabFoldBlock) == 32, "a record shared with the host");
 
 // What every build kernel is told
 struct StabCommon {
@@ -48,7 +57,8 @@ struct StabCommon {
     uint32_t tail_n;         // how many bytes behind the range (the next range's first ones) exist (0: the range ends the stream)
     uint32_t bs, cnt, B, M, parts, slices;
     uint32_t* tabs;          // cnt tables of 2^B bits
-    const StabBlock* list;   // nullptr: block b is src[b * bs ...) of the range; else the block-list form (len, bs and the tail are unused, tail_n is 0)
+    const StabBlock* list;   // nullptr: block b is src[b * bs ...) of the range; else the block-list form (len, bs and the tail are unused, tail_n is 0);
+                             // the pre-folded kernels: an array of StabFoldBlock
 };
 struct StabArgs : StabCommon {
     uint64_t tail;           // the bytes behind the range, little-endian
@@ -63,11 +73,12 @@ __device__ __forceinline__ void stab_zero(uint32_t* bits, uint32_t words) {
 // The workgroup's share: part `part` of block b's positions, the bits of slice `slice`.  next: a block follows this one in the stream;
 // end: where the bytes that can be read at src end for this block (the range's end; the list form: the end of the block's overlap)
 struct StabShare { uint32_t part, slice, b, blen; uint64_t b0, end; bool next; };
+template <bool kFold = false>
 __device__ __forceinline__ StabShare stab_share(const StabCommon& a) {
     StabShare w;
     w.part = blockIdx.x % a.parts; w.slice = (blockIdx.x / a.parts) % a.slices; w.b = blockIdx.x / (a.parts * a.slices);
-    if (a.list) {
-        const StabBlock blk = a.list[w.b];
+    if (kFold || a.list) {
+        const StabBlock blk = kFold ? static_cast<const StabBlock&>(static_cast<const StabFoldBlock*>(a.list)[w.b]) : a.list[w.b];
         w.b0 = blk.off; w.blen = blk.bytes; w.end = blk.off + blk.bytes + blk.over; w.next = blk.over != 0;
         return w;
     }
@@ -89,10 +100,26 @@ __device__ __forceinline__ void stab_mark(uint32_t* bits, uint32_t slice, uint32
         atomicOr(&bits[x >> 5], 1u << (x & 31));
     }
 }
+// The pre-folded form, read from the block's record in front of everything else: the workgroup's bitmap words, the mask of a hash, where its
+// slice of the table goes, and skip = the block's folded table has no such slice
+struct StabFold { uint32_t words, mask; uint32_t* out; bool skip; };
+__device__ __forceinline__ StabFold stab_fold(const StabCommon& a) {
+    const uint32_t slice = (blockIdx.x / a.parts) % a.slices;
+    const StabFoldBlock& blk = static_cast<const StabFoldBlock*>(a.list)[blockIdx.x / (a.parts * a.slices)];
+    const uint32_t bits = a.B - blk.r0, lbits = bits < kStabSliceBits ? bits : kStabSliceBits;
+    StabFold f;
+    f.words = 1u << (lbits - 5); f.mask = (1u << bits) - 1;
+    f.out = a.tabs + (blk.tab_off >> 2) + (size_t(slice) << (kStabSliceBits - 5));
+    f.skip = slice >= (1u << (bits - lbits));
+    return f;
+}
 // The bitmap to the block's table in HBM: written out, or, when several parts share the (zeroed) table, merged by its words that are not zero
+__device__ __forceinline__ void stab_flush_to(uint32_t* out, uint32_t parts, const uint32_t* bits, uint32_t words);
 __device__ __forceinline__ void stab_flush(const StabCommon& a, const StabShare& w, const uint32_t* bits, uint32_t words) {
-    uint32_t* out = a.tabs + (size_t(w.b) << (a.B - 5)) + (size_t(w.slice) << (kStabSliceBits - 5));
-    if (a.parts == 1) {
+    stab_flush_to(a.tabs + (size_t(w.b) << (a.B - 5)) + (size_t(w.slice) << (kStabSliceBits - 5)), a.parts, bits, words);
+}
+__device__ __forceinline__ void stab_flush_to(uint32_t* out, uint32_t parts, const uint32_t* bits, uint32_t words) {
+    if (parts == 1) {
         for (uint32_t i = threadIdx.x; i < words; i += kStabThreads) out[i] = bits[i];
     } else {
         for (uint32_t i = threadIdx.x; i < words; i += kStabThreads) {
@@ -109,16 +136,18 @@ __device__ __forceinline__ uint64_t stab_byte(const StabArgs& a, uint64_t end, u
     return over < a.tail_n ? (a.tail >> (8 * over)) & 0xff : 0;
 }
 
-template <bool kPrefix>
+template <bool kPrefix, bool kFold = false>
 __global__ __launch_bounds__(kStabThreads) void stab_build_kernel(const StabArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint32_t* bits = reinterpret_cast<uint32_t*>(smem);
-    const uint32_t tid = threadIdx.x, words = stab_words(a);
+    [[maybe_unused]] StabFold fold{};
+    if constexpr (kFold) { fold = stab_fold(a); if (fold.skip) return; }
+    const uint32_t tid = threadIdx.x, words = kFold ? fold.words : stab_words(a);
     stab_zero(bits, words);
     [[maybe_unused]] const uint32_t* pmask = bits + words;   // the prefix form: 32 bytes behind the bitmap
     if constexpr (kPrefix) { if (tid < 8) bits[words + tid] = a.mask[tid]; }
     __syncthreads();
-    const StabShare w = stab_share(a);
+    const StabShare w = stab_share<kFold>(a);
     const uint64_t b0 = w.b0;
     const uint32_t blen = w.blen;
     // positions [0, npos): every one with a next block, else those whose window lies inside the block.  The prefix form: position 0 is
@@ -127,7 +156,7 @@ __global__ __launch_bounds__(kStabThreads) void stab_build_kernel(const StabArgs
     uint32_t p0, p1;
     stab_positions(a, w.part, npos, &p0, &p1);
     const uint32_t M = a.M, B = a.B;
-    auto mark = [&](uint64_t v) { stab_mark(bits, w.slice, search_hash(v, B, M)); };
+    auto mark = [&](uint64_t v) { stab_mark(bits, w.slice, kFold ? search_hash(v, B, M) & fold.mask : search_hash(v, B, M)); };
     for (uint32_t i = p0 + tid * kStabPerThread; i < p1; i += kStabThreads * kStabPerThread) {
         // the prefix form reads from one byte in front of its first position (a part's first position looks at the part before it); the
         // block's first lane has no such byte and shifts a zero in, for position 0, which is skipped
@@ -167,7 +196,8 @@ __global__ __launch_bounds__(kStabThreads) void stab_build_kernel(const StabArgs
         }
     }
     __syncthreads();
-    stab_flush(a, w, bits, words);
+    if constexpr (kFold) stab_flush_to(fold.out, a.parts, bits, words);
+    else stab_flush(a, w, bits, words);
 }
 
 // The long-prefix form (table type 4).  The bytes behind the range (K - 1 + M + E at the most) and the prefix travel in the kernel arguments.
@@ -178,10 +208,13 @@ struct StabLongArgs : StabCommon {
     uint8_t tail[kStabLongTail];   // the bytes behind the range
 };
 
+template <bool kFold = false>
 __global__ __launch_bounds__(kStabThreads) void stab_build_long_kernel(const StabLongArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint32_t* bits = reinterpret_cast<uint32_t*>(smem);
-    const uint32_t tid = threadIdx.x, words = stab_words(a);
+    [[maybe_unused]] StabFold fold{};
+    if constexpr (kFold) { fold = stab_fold(a); if (fold.skip) return; }
+    const uint32_t tid = threadIdx.x, words = kFold ? fold.words : stab_words(a);
     stab_zero(bits, words);
     uint8_t* lpfx = smem + words * 4;            // the prefix and, behind it, the bytes that follow the range
     uint8_t* ltail = lpfx + kSearchMaxPrefix;
@@ -189,7 +222,7 @@ __global__ __launch_bounds__(kStabThreads) void stab_build_long_kernel(const Sta
     if (tid < kStabLongTail) ltail[tid] = tid < a.tail_n ? a.tail[tid] : 0;
     __syncthreads();
     const uint32_t M = a.M, B = a.B, E = a.E, K = a.K;
-    const StabShare w = stab_share(a);
+    const StabShare w = stab_share<kFold>(a);
     const uint64_t b0 = w.b0, end = w.end, real = end + a.tail_n;   // real: where the stream's bytes that this block can see end
     // prefix starts [0, npos): every position with a block behind, else those whose prefix and windows lie inside the block
     const uint32_t npos = w.next ? w.blen : (w.blen >= K + M + E ? w.blen - K - M - E + 1 : 0);
@@ -228,18 +261,19 @@ __global__ __launch_bounds__(kStabThreads) void stab_build_long_kernel(const Sta
             uint32_t t = 8;
             while (t < K && byte_at(s + t) == lpfx[t]) t++;
             if (t < K) continue;
-            for (uint32_t e = 0; e <= E; e++) stab_mark(bits, w.slice, search_hash(load8(s + K + e), B, M));
+            for (uint32_t e = 0; e <= E; e++) stab_mark(bits, w.slice, kFold ? search_hash(load8(s + K + e), B, M) & fold.mask : search_hash(load8(s + K + e), B, M));
         }
     }
     __syncthreads();
-    stab_flush(a, w, bits, words);
+    if constexpr (kFold) stab_flush_to(fold.out, a.parts, bits, words);
+    else stab_flush(a, w, bits, words);
 }
 
-// info[b] = (table bytes or 0, R); the table of 2^(B - R) bits is left at the front of its slot
-__global__ __launch_bounds__(kStabThreads) void stab_reduce_kernel(uint32_t* __restrict__ tabs, uint32_t B, uint32_t fold_limit /* per cent */, uint2* __restrict__ info) {
+// The rules over one table t of `words` words that was built folded R times (0: as the full kernels build it): *out = (table bytes or 0, R);
+// the table of 2^(B - R) bits is left at the front of its slot.  (A pre-folded table is never dropped: it holds a quarter of 2^(B - 1) bits at the most.)
+__device__ __forceinline__ void stab_reduce(uint32_t* __restrict__ t, uint32_t words, uint32_t R, uint32_t B, uint32_t fold_limit, uint2* __restrict__ out) {
     __shared__ uint32_t wsum[kStabThreads / 64];
-    const uint32_t tid = threadIdx.x, b = blockIdx.x;
-    uint32_t* t = tabs + (size_t(b) << (B - 5));
+    const uint32_t tid = threadIdx.x;
     // the workgroup's sum of `mine`
     auto total = [&](uint32_t mine) -> uint32_t {
         for (int o = 32; o; o >>= 1) mine += __shfl_down(mine, o);
@@ -250,14 +284,13 @@ __global__ __launch_bounds__(kStabThreads) void stab_reduce_kernel(uint32_t* __r
         for (uint32_t w = 0; w < kStabThreads / 64; w++) s += wsum[w];
         return s;
     };
-    uint32_t words = 1u << (B - 5), pop = 0;
+    uint32_t pop = 0;
     for (uint32_t i = tid; i < words; i += kStabThreads) pop += uint32_t(__popc(t[i]));
     pop = total(pop);
     if (search_table_dropped(pop, B)) {
-        if (tid == 0) info[b] = make_uint2(0, 0);
+        if (tid == 0) *out = make_uint2(0, 0);
         return;
     }
-    uint32_t R = 0;
     while (words * 4 >= 64) {
         const uint32_t half = words >> 1;
         uint32_t p = 0;
@@ -268,7 +301,19 @@ __global__ __launch_bounds__(kStabThreads) void stab_reduce_kernel(uint32_t* __r
         __syncthreads();
         words = half; R++;
     }
-    if (tid == 0) info[b] = make_uint2(words * 4, R);
+    if (tid == 0) *out = make_uint2(words * 4, R);
+}
+// info[b] = block b's record, its table at the front of its slot of 2^(B - 3) bytes
+__global__ __launch_bounds__(kStabThreads) void stab_reduce_kernel(uint32_t* __restrict__ tabs, uint32_t B, uint32_t fold_limit /* per cent */, uint2* __restrict__ info) {
+    const uint32_t b = blockIdx.x;
+    stab_reduce(tabs + (size_t(b) << (B - 5)), 1u << (B - 5), 0, B, fold_limit, info + b);
+}
+// The pre-folded form: block b's table of 2^(B - r0) bits lies where its record says
+__global__ __launch_bounds__(kStabThreads) void stab_reduce_fold_kernel(uint32_t* __restrict__ tabs, const StabFoldBlock* __restrict__ list, uint32_t B, uint32_t fold_limit,
+                                                                        uint2* __restrict__ info) {
+    const uint32_t b = blockIdx.x;
+    const StabFoldBlock blk = list[b];
+    stab_reduce(tabs + (blk.tab_off >> 2), 1u << (B - blk.r0 - 5), blk.r0, B, fold_limit, info + b);
 }
 
 }  // namespace mlz
@@ -276,18 +321,23 @@ __global__ __launch_bounds__(kStabThreads) void stab_reduce_kernel(uint32_t* __r
 namespace {
 
 // The launch both callers share: a.src, a.len / a.list, a.bs (the largest block), a.cnt, a.tail_n and a.tabs are set; `info` receives cnt records.
-int stab_launch(mlz_ctx* c, hipStream_t sm, mlz::StabCommon a, uint32_t T, const uint8_t* field, uint32_t M, uint32_t B, const uint8_t* tail, uint2* info) {
+// fold: the pre-folded form — a.list names StabFoldBlock records, the launch's largest table has 2^fold->bits bits, all tables together fold->bytes bytes.
+struct StabFoldLaunch { uint32_t bits; size_t bytes; };
+int stab_launch(mlz_ctx* c, hipStream_t sm, mlz::StabCommon a, uint32_t T, const uint8_t* field, uint32_t M, uint32_t B, const uint8_t* tail, uint2* info,
+                const StabFoldLaunch* fold = nullptr) {
     const size_t slot = size_t(1) << (B - 3), cnt = a.cnt;
-    const uint32_t lbits = std::min(B, mlz::kStabSliceBits), lds = 1u << (lbits - 3);
-    constexpr uint32_t kBitmap = 1u << (mlz::kStabSliceBits - 3);
-    if (int r = raise_lds_once(c, c->stab_attr, Kernels{{mlz::stab_build_kernel<false>, kBitmap}, {mlz::stab_build_kernel<true>, kBitmap + 32},
-                                                        {mlz::stab_build_long_kernel, kBitmap + mlz::kSearchMaxPrefix + mlz::kStabLongTail}})) return r;
+    const uint32_t lbits = std::min(fold ? fold->bits : B, mlz::kStabSliceBits), lds = 1u << (lbits - 3);   // dynamic LDS: the launch's largest bitmap
+    constexpr uint32_t kBitmap = 1u << (mlz::kStabSliceBits - 3), kLong = kBitmap + mlz::kSearchMaxPrefix + mlz::kStabLongTail;
+    if (int r = raise_lds_once(c, c->stab_attr, Kernels{{mlz::stab_build_kernel<false>, kBitmap}, {mlz::stab_build_kernel<true>, kBitmap + 32}, {mlz::stab_build_long_kernel<false>, kLong},
+                                                        {mlz::stab_build_kernel<false, true>, kBitmap}, {mlz::stab_build_kernel<true, true>, kBitmap + 32},
+                                                        {mlz::stab_build_long_kernel<true>, kLong}})) return r;
     a.B = B; a.M = M;
-    a.slices = 1u << (B - lbits);
+    a.slices = 1u << ((fold ? fold->bits : B) - lbits);
     // few large blocks: parts of at least 64 KiB, until the device has about two workgroups per CU
     const uint64_t want = std::max<uint64_t>(1, uint64_t(2 * std::max(c->n_cus, 1)) / (cnt * a.slices));
     a.parts = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(want, a.bs >> 16)));
-    if (a.parts > 1) HIPCHK(c, hipMemsetAsync(a.tabs, 0, cnt * slot, sm));
+    if (a.parts > 1) HIPCHK(c, hipMemsetAsync(a.tabs, 0, fold ? fold->bytes : cnt * slot, sm));
+    if (cnt * a.slices * a.parts > 0x7fffffffull) { c->err = "search tables: more workgroups than a launch takes"; return -MLZ_ERR_ARG; }
     const dim3 grid(uint32_t(cnt * a.slices * a.parts)), wg(mlz::kStabThreads);
     if (T == 4) {
         mlz::StabLongArgs la{};
@@ -295,18 +345,21 @@ int stab_launch(mlz_ctx* c, hipStream_t sm, mlz::StabCommon a, uint32_t T, const
         la.E = mlz::search_long_e(field); la.K = mlz::search_long_k(field);
         std::memcpy(la.pfx, mlz::search_long_prefix(field), la.K);
         if (a.tail_n) std::memcpy(la.tail, tail, a.tail_n);
-        hipLaunchKernelGGL(mlz::stab_build_long_kernel, grid, wg, lds + mlz::kSearchMaxPrefix + mlz::kStabLongTail, sm, la);
+        hipLaunchKernelGGL((fold ? mlz::stab_build_long_kernel<true> : mlz::stab_build_long_kernel<false>), grid, wg, lds + mlz::kSearchMaxPrefix + mlz::kStabLongTail, sm, la);
     } else {
         mlz::StabArgs sa{};
         static_cast<mlz::StabCommon&>(sa) = a;
         if (a.tail_n) std::memcpy(&sa.tail, tail, a.tail_n);
-        if (T == 1) hipLaunchKernelGGL(mlz::stab_build_kernel<false>, grid, wg, lds, sm, sa);
+        if (T == 1) hipLaunchKernelGGL((fold ? mlz::stab_build_kernel<false, true> : mlz::stab_build_kernel<false>), grid, wg, lds, sm, sa);
         else {
             mlz::search_prefix_mask(T, field, sa.mask);
-            hipLaunchKernelGGL(mlz::stab_build_kernel<true>, grid, wg, lds + 32, sm, sa);
+            hipLaunchKernelGGL((fold ? mlz::stab_build_kernel<true, true> : mlz::stab_build_kernel<true>), grid, wg, lds + 32, sm, sa);
         }
     }
-    hipLaunchKernelGGL(mlz::stab_reduce_kernel, dim3(uint32_t(cnt)), dim3(mlz::kStabThreads), 0, sm, a.tabs, B, mlz::search_fold_limit(T), info);
+    if (fold)
+        hipLaunchKernelGGL(mlz::stab_reduce_fold_kernel, dim3(uint32_t(cnt)), dim3(mlz::kStabThreads), 0, sm, a.tabs, static_cast<const mlz::StabFoldBlock*>(a.list), B,
+                           mlz::search_fold_limit(T), info);
+    else hipLaunchKernelGGL(mlz::stab_reduce_kernel, dim3(uint32_t(cnt)), dim3(mlz::kStabThreads), 0, sm, a.tabs, B, mlz::search_fold_limit(T), info);
     return 0;
 }
 
@@ -341,6 +394,31 @@ int search_tables_build_list(mlz_ctx* c, hipStream_t sm, const uint8_t* d_src, c
     a.src = d_src; a.list = d_list; a.bs = max_block; a.cnt = uint32_t(cnt);
     a.tabs = tabs;
     return stab_launch(c, sm, a, T, field, M, B, nullptr, info);
+}
+
+// A block's record of the pre-folded form by the Writer's rule: the block of `bytes` bytes at d_src + off with `behind` bytes of its stream
+// behind it (0: the stream's last block, which indexes only what lies inside it) sees min(overlap, behind) of them and zeros beyond, never
+// another stream's bytes.  Its slot of 2^(B - r0 - 3) bytes starts at *tab_bytes, which moves on.
+mlz::StabFoldBlock stab_fold_block(uint64_t off, uint32_t bytes, uint64_t behind, uint32_t T, const uint8_t* field, uint32_t M, uint32_t B, uint64_t* tab_bytes) {
+    mlz::StabFoldBlock blk{};
+    blk.off = off; blk.bytes = bytes;
+    blk.over = uint32_t(std::min<uint64_t>(mlz::search_overlap(T, M, field), behind));
+    blk.r0 = mlz::search_prefold(mlz::search_table_marks(T, M, field, bytes, behind != 0), B, mlz::search_fold_limit(T));
+    blk.tab_off = *tab_bytes;
+    *tab_bytes += uint64_t(1) << (B - blk.r0 - 3);
+    return blk;
+}
+
+// The pre-folded block-list form: the tables of the cnt blocks d_list names inside d_src (records made by stab_fold_block, on the device), of
+// one configuration, to `tabs` (tab_bytes bytes, which the caller has sized) and their records to `info`.  max_block: the largest block;
+// min_r0: the smallest r0 of the list.
+int search_tables_build_prefolded(mlz_ctx* c, hipStream_t sm, const uint8_t* d_src, const mlz::StabFoldBlock* d_list, size_t cnt, uint32_t max_block, uint32_t min_r0,
+                                  uint64_t tab_bytes, uint32_t T, const uint8_t* field, uint32_t M, uint32_t B, uint32_t* tabs, uint2* info) {
+    mlz::StabCommon a{};
+    a.src = d_src; a.list = d_list; a.bs = max_block; a.cnt = uint32_t(cnt);
+    a.tabs = tabs;
+    const StabFoldLaunch fold{B - min_r0, size_t(tab_bytes)};
+    return stab_launch(c, sm, a, T, field, M, B, nullptr, info, &fold);
 }
 
 }  // namespace

@@ -579,4 +579,26 @@ MLZ_SEARCH_HD uint32_t search_reduce_rule(const uint32_t* pop, uint32_t B, uint3
     return uint32_t(bytes);
 }
 
+// ---- tables built already folded (the batch Writer: a table's size comes from the call's block size, and every stream's last block is short) ----
+// A table folded r times is the bitmap of h & (2^(B - r) - 1).  pop[r] never exceeds `marks`, the distinct window positions a block indexes,
+// so with marks * 100 <= 2^(B - r) * limit and B - r >= 8 every fold up to r passes search_reduce_rule's two conditions whatever the data,
+// and the unfolded table holds a quarter of 2^(B - 1) bits at the most: the 70 % rule cannot drop it.  A builder may then set bit
+// h & (2^(B - r) - 1) of a table of 2^(B - r) bits and run the fold rule from R = r: the same (table, R).  search_prefold is the largest
+// such r, 0 when none >= 1 qualifies; marks = 0 gives B - 8, the all-zero table of 32 bytes.
+MLZ_SEARCH_HD uint32_t search_prefold(uint64_t marks, uint32_t B, uint32_t limit) {
+    for (uint32_t r = B - 8; r >= 1; r--)
+        if (marks * 100 <= (uint64_t(1) << (B - r)) * limit) return r;
+    return 0;
+}
+// The window positions a block of n bytes can index (the kernels' npos, and for type 4 the windows behind its prefix starts).  next: a block
+// follows in the stream.  Type 1: every position, the last block those whose window lies inside it; types 2 and 3: positions 1 .. n, the last
+// block's 1 .. n - M; type 4: the prefix starts 0 .. hi (hi = n - 1, the last block's n - K - M - E) reach the windows K .. hi + K + E.
+MLZ_SEARCH_HD uint64_t search_table_marks(uint32_t T, uint32_t M, const uint8_t* field, uint64_t n, bool next) {
+    if (T == 1) return next ? n : (n + 1 >= M ? n + 1 - M : 0);
+    if (T != 4) return next ? n : (n >= M ? n - M : 0);
+    const uint64_t K = search_long_k(field), E = search_long_e(field);
+    if (next) return n ? n + E : 0;
+    return n >= K + M + E ? n - K - M - E + 1 + E : 0;
+}
+
 }  // namespace mlz

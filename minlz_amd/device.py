@@ -127,16 +127,19 @@ class HipTensorCodec:
                 self._raise_stream("decode_streams", i, r)
         return out[:starts[-1]], starts
 
-    def encode_streams(self, t, spans, level, block_size=1 << 20, add_index=False):
+    def encode_streams(self, t, spans, level, block_size=1 << 20, add_index=False, search_match_len=None, search_prefix=None, search_long_prefix=None, search_extras=0):
         """Every input t[off_i : off_i + len_i] (a uint8 tensor on the device, spans[i] = (off_i, len_i)) as a .mz stream of its own ->
         (out, stream_spans): one new uint8 tensor on the same device and where each stream lies in it, [(off, len)] (with room between
         them: every stream is written at the place its bound reserves).  One call (mlz_stream_encode_batch_device); the bytes are
-        api.stream_encode's.  Raises the first failing stream's error, which names its index (.index)."""
+        api.stream_encode's.  With the search_* keywords (those of Context.stream_encode_gather_device) every stream carries block search
+        tables of that configuration, which search_streams(prune=True) reads; the bytes are then the gather Writer's for that input alone.
+        Raises the first failing stream's error, which names its index (.index)."""
         t = _u8(t, "encode_streams")
+        tables = dict(search_match_len=search_match_len, search_prefix=search_prefix, search_long_prefix=search_long_prefix, search_extras=search_extras)
         descs, at = [], 0
         for o, n in _spans(t, spans, "encode_streams"):
             try:
-                cap = api.stream_bound(n, block_size, add_index)
+                cap = api.stream_bound(n, block_size, add_index, **tables)
             except api.MinLZError:
                 raise ValueError("encode_streams: block size %d" % block_size)
             descs.append((o, n, at, cap))
@@ -144,7 +147,7 @@ class HipTensorCodec:
         out = torch.empty(max(at, 1), dtype=torch.uint8, device=t.device)
         if not descs:
             return out[:0], []
-        res = self.ctx.stream_encode_batch_device(level, block_size, add_index, t.data_ptr(), out.data_ptr(), descs, stream=_stream(t.device))
+        res = self.ctx.stream_encode_batch_device(level, block_size, add_index, t.data_ptr(), out.data_ptr(), descs, stream=_stream(t.device), **tables)
         for i, r in enumerate(res):
             if r < 0:
                 self._raise_stream("encode_streams", i, r)
