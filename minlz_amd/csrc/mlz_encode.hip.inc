@@ -113,7 +113,7 @@ __device__ __forceinline__ uint32_t match_len(const uint8_t* a, const uint8_t* b
 // table[(lv * n_epochs + epoch) << kFarBits | hash8] = min position q (block-relative) over the
 // sampled positions of that epoch whose tile level is <= lv.  "min" makes the result independent
 // of scheduling.  Each workgroup owns a 32 Ki-bucket slice of one table in LDS (128 KiB), scans the
-// epoch's sampled windows (coalesced reads, L2/MALL-served since every slice re-reads them), keeps
+// epoch's sampled windows (16-byte coalesced reads; the slices of an epoch share an L2, "Placement" below), keeps
 // the minima with LDS atomics and writes its slice out once — no global atomics, no memset.
 constexpr int kFarSliceBits = 15;
 // LevelBalanced's tables of 2^18 entries (blocks of kBigBlock and more) carry the top FOUR of the nine tag bits: the words far_bin_kernel sorts have
@@ -121,7 +121,6 @@ constexpr int kFarSliceBits = 15;
 // is rejected by the byte compare, so the output does not depend on the tag's width (1 false fetch in 16 foreign probes instead of 1 in 512).
 constexpr int kL2FarBitsBig = 18;
 __host__ __device__ constexpr uint32_t far_tag_mask(int FB) { return FB == kL2FarBitsBig ? 0x1E0u : kFarTagMask; }
-constexpr uint32_t far_slices(int fb) { return 1u << (fb - kFarSliceBits); }
 // A workgroup builds its slice for the level sets in turn, lowest first: it scans only the epoch's tiles of
 // level == lset and keeps accumulating minima in the same LDS slice, so level set L (levels <= L) is complete
 // after pass L and is written out then — each sampled window is hashed once per slice instead of once per
@@ -129,16 +128,36 @@ constexpr uint32_t far_slices(int fb) { return 1u << (fb - kFarSliceBits); }
 // FB: table entries per (epoch, level set), log2; ST: every ST-th 8-byte window is entered (LevelFastest 17 / 4, LevelBalanced 18 / 2).
 // FB = 0: the blocks below kBigBlock of a batch, each with small_far_bits(its length) — tables are tab_log apart then
 // (FB otherwise).  cls as in the match kernel: 0 = blocks below kBigBlock only, 1 = the others only, 2 = all.
+//
+// Placement.  The S = 2^slice_log slice workgroups of one (block, epoch) read the same sampled tiles, so they belong behind ONE L2.  Workgroups
+// are dispatched in linear order and workgroup L runs on XCD L % 8 (observed, not promised: the match kernel's tile map leans on the same
+// observation), and on a (slice, epoch, block) grid the four slices of an epoch sat on four XCDs: every source byte crossed the fabric four
+// times.  The grid is one-dimensional instead and far_place() reads it as
+//     x = L & 7, r = L >> 3, slice = r % S, j = r / S, group q = 8 j + x          (q = block * grid_epochs + epoch, n_groups of them)
+// so the slices of a group are 8 apart in L — one XCD, neighbouring dispatch slots, the second to the S-th reader of a tile hit in L2 — and
+// eight groups at a time take the eight XCDs.  The grid is 8 S ceil(n_groups / 8) workgroups; those with q >= n_groups leave at once.  A
+// placement for speed only: no workgroup waits for another, every workgroup writes its own slice whatever XCD it lands on.  grid_epochs is
+// the launch's count of epochs per block (1 for the class below kBigBlock, whose blocks have one), epochs_per_block the tables' layout.
 constexpr uint64_t kBigBlock = 1u << 20;
+struct FarPlace { uint32_t slice, group; };
+__host__ __device__ __forceinline__ FarPlace far_place(uint32_t wg, uint32_t slice_log) {
+    const uint32_t r = wg >> 3;
+    return {r & ((1u << slice_log) - 1), ((r >> slice_log) << 3) | (wg & 7)};
+}
+__host__ __device__ __forceinline__ uint32_t far_grid(uint32_t n_groups, uint32_t slice_log) { return ((n_groups + 7) / 8 * 8) << slice_log; }
 template <int FB, int ST>
 __global__ __launch_bounds__(1024) void far_build_kernel(const uint8_t* __restrict__ src_base, const BlockInfo* __restrict__ blocks,
                                                          uint32_t* __restrict__ far_tab, uint32_t epochs_per_block, uint32_t pattern,
-                                                         uint32_t tab_log, uint32_t cls) {
+                                                         uint32_t tab_log, uint32_t cls, uint32_t slice_log, uint32_t grid_epochs,
+                                                         uint32_t n_groups) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint32_t* slot = reinterpret_cast<uint32_t*>(smem);
-    const uint32_t slice = blockIdx.x;   // which 32 Ki buckets
-    const uint32_t ep = blockIdx.y;      // epoch
-    const BlockInfo b = blocks[blockIdx.z];
+    const FarPlace at = far_place(blockIdx.x, slice_log);
+    if (at.group >= n_groups) return;    // the padding of the last eight groups
+    const uint32_t slice = at.slice;                 // which 32 Ki buckets
+    const uint32_t blk = at.group / grid_epochs;     // block of the launch
+    const uint32_t ep = at.group % grid_epochs;      // epoch
+    const BlockInfo b = blocks[blk];
     if (cls != 2 && uint32_t(b.src_len >= kBigBlock) != cls) return;
     if (b.src_len > kMaxBlockSize) return;   // reported as too large by the layout pass; it has no tiles, nobody probes a table of it
     const int fb = FB ? FB : small_far_bits(b.src_len) + (ST == 2 ? 1 : 0);
@@ -151,11 +170,11 @@ __global__ __launch_bounds__(1024) void far_build_kernel(const uint8_t* __restri
     __syncthreads();
     const uint64_t e0 = uint64_t(ep) << kEpochLog;
     const uint64_t e1 = e0 + (1ull << kEpochLog) < b.src_len ? e0 + (1ull << kEpochLog) : b.src_len;
-    // Every thread takes one sampled window out of each run of 1024 of a tile; two tiles of the level are in
-    // flight at a time (16 loads are issued before the first hash), so the scan costs a memory round trip per
-    // 16 windows instead of one per tile.
+    // Every thread takes kPerTile of a tile's sampled windows; two tiles of the level are in flight at a time (all their
+    // loads are issued before the first hash), so the scan costs a memory round trip per 16 windows instead of one per tile.
+    // (Four tiles in flight, measured with the 16-byte loads below: 36.8 us against 35.5.)
     constexpr uint32_t kPerTile = kTile / ST / 1024;   // windows of one tile per thread (8 or 16)
-    constexpr int kFbTiles = ST >= 4 ? 2 : 1;          // tiles in flight at a time: 16 loads either way
+    constexpr int kFbTiles = ST >= 4 ? 2 : 1;          // tiles in flight at a time: 16 windows either way
     constexpr uint32_t kBatch = kFbTiles * kPerTile;
     const uint32_t tiles_in_epoch = e1 > e0 && b.src_len >= 8 ? uint32_t((e1 - e0 + kTile - 1) >> kTileLog) : 0;  // short blocks of a mixed batch have no such epoch
     constexpr uint32_t kEpochTiles = 1u << (kEpochLog - kTileLog);
@@ -181,29 +200,71 @@ __global__ __launch_bounds__(1024) void far_build_kernel(const uint8_t* __restri
             uint32_t kk[kFbTiles];
 #pragma unroll
             for (int t = 0; t < kFbTiles; t++) { kk[t] = todo ? g64 + uint32_t(ctz64(todo)) : tiles_in_epoch; todo &= todo - 1; }
-            uint64_t w[kBatch];
-            uint64_t qq[kBatch];
-            bool ok[kBatch];
+            // Whole tiles: when every tile of the batch lies inside the block with 8 bytes to spare — all but a block's last tile — every
+            // lane has its windows, the same answer for the whole workgroup, decided here once (as the match kernel's deep_tile).
+            bool whole = true;
 #pragma unroll
-            for (uint32_t u = 0; u < kBatch; u++) {
-                const uint32_t k = kk[u / kPerTile];                // tile of this level
-                const uint64_t q = e0 + (uint64_t(k) << kTileLog) + (uint64_t(u % kPerTile) * 1024 + tid) * ST;
-                qq[u] = q;
-                ok[u] = k < tiles_in_epoch && q + 8 <= b.src_len && q < e1;
-                // unconditional (lanes without a window read the block's first bytes): a load under a branch is
-                // followed by a wait for it, which turned these 16 loads into 16 round trips
-                w[u] = ld64u(s + (ok[u] ? q : 0));
-            }
+            for (int t = 0; t < kFbTiles; t++) whole = whole && kk[t] < tiles_in_epoch && e0 + (uint64_t(kk[t] + 1) << kTileLog) + 8 <= b.src_len;
+            if (whole) {
+                // A thread takes the 16 / ST windows that START in one 16-byte group: one 16-byte load per group and the 4 (ST = 2: 8)
+                // bytes behind it that its last windows reach into — 20 bytes and two load instructions per four windows where an 8-byte
+                // load per window at a stride of ST bytes took 32 and four.  The kernel was bound by its CU's load path, not by the
+                // fabric or the hashing: the workgroup placement above cut the fabric fetch fourfold for 1 us, the 32-bit positions and
+                // the missing predicate of this path took 40 % of the vector instructions for 1 us, these loads took 15 us of 50
+                // (profiles/far_build_placement_time.txt).  Which thread enters a window does not matter to the minimum.  Positions are
+                // 32-bit: a block has at most kMaxBlockSize bytes.  No merge of in-flight registers with the edge path: each path has
+                // its own loads AND its own hashes, behind a branch that is uniform for the workgroup.
+                constexpr uint32_t kWin = 16 / ST;               // windows of a group
+                constexpr uint32_t kGroups = kPerTile / kWin;    // groups of a tile per thread
+                constexpr uint32_t kG = kFbTiles * kGroups;      // groups in flight
+                constexpr uint32_t kX = ST == 4 ? 1 : 2;         // dwords behind the group
+                static_assert(ST == 2 || ST == 4, "windows start on even bytes of a group");
+                static_assert((kWin - 1) * ST + 8 <= 16 + 4 * kX && 4 * kX <= 8, "the last window ends inside the loaded bytes, those inside the tile's 8 spare bytes");
+                uint32_t at[kG];
+                uint32_t d[kG][4 + kX];
 #pragma unroll
-            for (uint32_t u = 0; u < kBatch; u++) {
-                const FarHash fh = far_hash(w[u], fb, far_tag_mask(FB));
-                if (ok[u] && (fh.idx >> sbits) == slice)
-                    atomicMin(&slot[fh.idx & ((1u << sbits) - 1)], (uint32_t(qq[u]) << kFarTagBits) | fh.tag);
+                for (uint32_t g = 0; g < kG; g++) at[g] = uint32_t(e0) + (kk[g / kGroups] << kTileLog) + ((g % kGroups) * 1024 + uint32_t(tid)) * 16;
+#pragma unroll
+                for (uint32_t g = 0; g < kG; g++) __builtin_memcpy(d[g], s + at[g], 16 + 4 * kX);
+#pragma unroll
+                for (uint32_t g = 0; g < kG; g++) {
+#pragma unroll
+                    for (uint32_t j = 0; j < kWin; j++) {
+                        const uint32_t o = j * ST;   // the window's first byte in the group
+                        const auto dword_at = [&](uint32_t i) {   // the loaded bytes [i, i + 4), i even
+                            if constexpr (ST == 4) return d[g][i / 4];
+                            else return i % 4 ? (d[g][i / 4] >> 16) | (d[g][i / 4 + 1] << 16) : d[g][i / 4];
+                        };
+                        const FarHash fh = far_hash(uint64_t(dword_at(o + 4)) << 32 | dword_at(o), fb, far_tag_mask(FB));
+                        if ((fh.idx >> sbits) == slice) atomicMin(&slot[fh.idx & ((1u << sbits) - 1)], ((at[g] + o) << kFarTagBits) | fh.tag);
+                    }
+                }
+            } else {
+                // the block's last tile (and a batch's missing second tile): a window per load, a predicate per lane
+                uint64_t w[kBatch];
+                uint64_t qq[kBatch];
+                bool ok[kBatch];
+#pragma unroll
+                for (uint32_t u = 0; u < kBatch; u++) {
+                    const uint32_t k = kk[u / kPerTile];                // tile of this level
+                    const uint64_t q = e0 + (uint64_t(k) << kTileLog) + (uint64_t(u % kPerTile) * 1024 + tid) * ST;
+                    qq[u] = q;
+                    ok[u] = k < tiles_in_epoch && q + 8 <= b.src_len && q < e1;
+                    // unconditional (lanes without a window read the block's first bytes): a load under a divergent branch is
+                    // followed by a wait for it, which turned these 16 loads into 16 round trips
+                    w[u] = ld64u(s + (ok[u] ? q : 0));
+                }
+#pragma unroll
+                for (uint32_t u = 0; u < kBatch; u++) {
+                    const FarHash fh = far_hash(w[u], fb, far_tag_mask(FB));
+                    if (ok[u] && (fh.idx >> sbits) == slice)
+                        atomicMin(&slot[fh.idx & ((1u << sbits) - 1)], (uint32_t(qq[u]) << kFarTagBits) | fh.tag);
+                }
             }
         }
       }
         __syncthreads();
-        const size_t tab = ((size_t(blockIdx.z) * far_sets(pattern) + lset) * epochs_per_block + ep) << tlog;
+        const size_t tab = ((size_t(blk) * far_sets(pattern) + lset) * epochs_per_block + ep) << tlog;
         uint32_t* out = far_tab + tab + (size_t(slice) << sbits);
         for (uint32_t i = tid; i < (1u << sbits) / 4; i += 1024) reinterpret_cast<uint4*>(out)[i] = reinterpret_cast<const uint4*>(slot)[i];
         __syncthreads();  // the copy-out is complete before the next pass lowers entries

@@ -388,7 +388,7 @@ const Kernel<MatchFn> kMatch[M_COUNT] = {
     {match_tiles_kernel<true, MLZ_M2_NW, kM2HashBitsSmall, 0, true>, M2Cfg<kM2HashBitsSmall>::kLds},                   // with far tables of the level's size or of the block's
     {match_tiles_kernel<false, MLZ_M2_NW, kM2HashBitsSmall, kL2FarBits, true>, M2Cfg<kM2HashBitsSmall>::kLds},         // no far tables, but the level's near-table seeding
 };
-using FarBuildFn = void (*)(const uint8_t*, const BlockInfo*, uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t);
+using FarBuildFn = void (*)(const uint8_t*, const BlockInfo*, uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t);
 const Kernel<FarBuildFn> kFarBuild[4] = {   // [2 * LevelBalanced + blocks of kBigBlock and more]; the smaller blocks' tables go with their length
     {far_build_kernel<0, kFarStride>, 4u << kFarSliceBits}, {far_build_kernel<kFarBits, kFarStride>, 4u << kFarSliceBits},
     {far_build_kernel<0, kL2FarStride>, 4u << kFarSliceBits}, {far_build_kernel<kL2FarBits, kL2FarStride>, 4u << kFarSliceBits},
@@ -422,8 +422,11 @@ int encode_far_tables(mlz_ctx* c, hipStream_t st, const EncGroup& g, const uint8
     const bool l2 = g.level == MLZ_LEVEL_BALANCED;
     HIPCHK(c, c->d_far.ensure(((size_t(g.n) * far_sets(g.pattern) * g.epochs) << g.fbits) * 4));
     if (int r = raise_lds_once(c, c->far_attr, kFarBuild)) return r;
-    auto build = [&](const Kernel<FarBuildFn>& v, dim3 grid, uint32_t lds, uint32_t cls) {
-        hipLaunchKernelGGL(v.fn, grid, dim3(1024), lds, st, d_src, g.blocks, c->d_far.as<uint32_t>(), g.epochs, g.pattern, uint32_t(g.fbits), cls);
+    // one-dimensional grid: the 2^slice_log slice workgroups of a (block, epoch) on one XCD (far_place, mlz_encode.hip.inc)
+    auto build = [&](const Kernel<FarBuildFn>& v, uint32_t slice_log, uint32_t grid_epochs, uint32_t lds, uint32_t cls) {
+        const uint32_t groups = uint32_t(g.n) * grid_epochs;
+        hipLaunchKernelGGL(v.fn, dim3(far_grid(groups, slice_log)), dim3(1024), lds, st, d_src, g.blocks, c->d_far.as<uint32_t>(), g.epochs, g.pattern, uint32_t(g.fbits), cls,
+                           slice_log, grid_epochs, groups);
     };
     if (g.any_big) {
         if (l2 && g.pattern == kPatternFree && !c->far_slices_l2) {
@@ -438,14 +441,14 @@ int encode_far_tables(mlz_ctx* c, hipStream_t st, const EncGroup& g, const uint8
             hipLaunchKernelGGL((far_bin_kernel<kL2FarBits, kL2FarStride>), dim3(uint32_t(units2)), dim3(256), FBn::kLds, st, d_src, g.blocks, g.tile_block, bins, binoff);
             hipLaunchKernelGGL((far_slice_kernel<kL2FarBits, kL2FarStride>), dim3(FBn::kSlices, g.epochs, g.n), dim3(1024), kSliceLds, st, g.blocks, bins, binoff, c->d_far.as<uint32_t>(), g.epochs);
         } else
-            build(kFarBuild[2 * l2 + 1], dim3(far_slices(l2 ? kL2FarBits : kFarBits), g.epochs, g.n), kFarBuild[2 * l2 + 1].lds, g.any_small ? 1u : 2u);
+            build(kFarBuild[2 * l2 + 1], uint32_t((l2 ? kL2FarBits : kFarBits) - kFarSliceBits), g.epochs, kFarBuild[2 * l2 + 1].lds, g.any_small ? 1u : 2u);
     }
     if (g.any_small) {
         uint64_t max_small = 0;
         for (int i = 0; i < g.n; i++) if (desc[i].src_len < kBigBlock) max_small = std::max<uint64_t>(max_small, desc[i].src_len);
         const int sb = small_far_bits(max_small) + (l2 ? 1 : 0);
         const uint32_t lds = 4u << std::min<int>(sb, kFarSliceBits);   // small tables leave room for more workgroups per CU
-        build(kFarBuild[2 * l2], dim3(1u << (std::max<int>(sb, kFarSliceBits) - kFarSliceBits), 1, g.n), lds, g.any_big ? 0u : 2u);
+        build(kFarBuild[2 * l2], uint32_t(std::max<int>(sb, kFarSliceBits) - kFarSliceBits), 1, lds, g.any_big ? 0u : 2u);
     }
     return 0;
 }
