@@ -455,7 +455,8 @@ int64_t mlz_dev_reader_search_many(mlz_dev_reader* reader, void* stream, uint32_
 /* The search over a BATCH of streams in HBM — which of these objects hold any of these keys, and where — is declared in a header of its own,
  * include/minlz_hip_search_batch.h, which includes this one.  A batch of streams opened as ONE handle (mlz_stream_open_batch_device), on which every
  * mlz_dev_reader_* call below and above works as on the streams' concatenation, and the calls that turn its positions and record numbers back into
- * (stream, position or record inside the stream), are declared in include/minlz_hip_stream_set.h. */
+ * (stream, position or record inside the stream), are declared in include/minlz_hip_stream_set.h; the open of such a handle whose searches prune by
+ * every stream's inline search tables in include/minlz_hip_stream_set_tables.h. */
 
 /* mlz_dev_reader_search_records: the RECORDS of the decoded stream that hold the pattern, each once, in stream order, packed into d_dst — what
  *   `mz search pattern file.mz` prints, and with rec_cap == 0 and dst_cap == 0 what `-c` counts.  A record is a maximal run of decoded bytes that

@@ -21,7 +21,7 @@ def stale():
         return True
     t = os.path.getmtime(SO)
     # every file under csrc/ is part of the one translation unit (mlz_hip.hip includes the rest)
-    paths = [os.path.join(CSRC, d) for d in sorted(os.listdir(CSRC))] + [os.path.join(os.path.dirname(HERE), "include", h) for h in ("minlz_hip.h", "minlz_hip_search_batch.h", "minlz_hip_search_batch_prune.h", "minlz_hip_stream_set.h", "minlz_hip_regex.h", "minlz_hip_regex_prune.h", "minlz_hip_search_compressed.h", "minlz_hip_search_compress.h", "minlz_hip_sidecar_extract.h", "minlz_hip_record_index_store.h", "minlz_hip_encode_batch_tables.h")]
+    paths = [os.path.join(CSRC, d) for d in sorted(os.listdir(CSRC))] + [os.path.join(os.path.dirname(HERE), "include", h) for h in ("minlz_hip.h", "minlz_hip_search_batch.h", "minlz_hip_search_batch_prune.h", "minlz_hip_stream_set.h", "minlz_hip_stream_set_tables.h", "minlz_hip_regex.h", "minlz_hip_regex_prune.h", "minlz_hip_search_compressed.h", "minlz_hip_search_compress.h", "minlz_hip_sidecar_extract.h", "minlz_hip_record_index_store.h", "minlz_hip_encode_batch_tables.h")]
     return any(os.path.getmtime(p) > t for p in paths)
 
 

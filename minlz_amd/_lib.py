@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension headers include/minlz_hip_search_batch.h, include/minlz_hip_search_batch_prune.h, include/minlz_hip_stream_set.h, include/minlz_hip_regex.h, include/minlz_hip_regex_prune.h, include/minlz_hip_search_compressed.h, include/minlz_hip_search_compress.h, include/minlz_hip_sidecar_extract.h, include/minlz_hip_record_index_store.h and include/minlz_hip_encode_batch_tables.h.
+"""ctypes binding of the C ABI declared in include/minlz_hip.h and its extension headers include/minlz_hip_search_batch.h, include/minlz_hip_search_batch_prune.h, include/minlz_hip_stream_set.h, include/minlz_hip_stream_set_tables.h, include/minlz_hip_regex.h, include/minlz_hip_regex_prune.h, include/minlz_hip_search_compressed.h, include/minlz_hip_search_compress.h, include/minlz_hip_sidecar_extract.h, include/minlz_hip_record_index_store.h and include/minlz_hip_encode_batch_tables.h.
 
 There is no CPU fallback here: if libminlz_hip.so is missing or HIP is unavailable, calls raise.
 """
@@ -124,6 +124,10 @@ ABI_EXT = {
         "mlz_dev_reader_read_streams_device": (i64, [vp, vp, u32, vp, vp, vp, sz, vp, sz, vp]),
         "mlz_dev_reader_stream_records": (i64, [vp, vp, P(u64), P(u64)]),
         "mlz_dev_reader_locate_records": (i64, [vp, vp, vp, sz, vp, vp]),
+    },
+    "minlz_hip_stream_set_tables.h": {
+        "mlz_stream_open_batch_device_tables": (i64, [vp, vp, vp, P(BlockDesc), i32, P(i64), P(vp)]),
+        "mlz_dev_reader_set_tables_info": (i64, [vp, P(u64)]),
     },
     "minlz_hip_regex.h": {
         "mlz_regex_compile": (i32, [vp, vp, sz, u32, P(vp), P(u64)]),

@@ -428,15 +428,17 @@ class Context:
         h = C.c_void_p()
         return DeviceReader(self, h, self._call("mlz_stream_open_device", stream, d_src, n, C.byref(h)))
 
-    def stream_open_batch_device(self, d_src, spans, stream=None):
+    def stream_open_batch_device(self, d_src, spans, stream=None, tables=False):
         """mlz_stream_open_batch_device (include/minlz_hip_stream_set.h): every stream (src_off, src_len) of the buffer at d_src opened as ONE
         reader over the streams' decoded bytes one behind the other -> (DeviceReader, [result]: the decoded size or the framing error
-        -MLZ_ERR_* of each stream; a failed one is left out of the reader).  The caller keeps d_src alive and unchanged while it is open."""
+        -MLZ_ERR_* of each stream; a failed one is left out of the reader).  The caller keeps d_src alive and unchanged while it is open.
+        tables: mlz_stream_open_batch_device_tables (include/minlz_hip_stream_set_tables.h) — the reader's searches prune by every stream's
+        inline search tables, with the same results."""
         arr = _block_descs(spans)
         n = len(arr)
         out = (C.c_int64 * max(n, 1))()
         h = C.c_void_p()
-        size = self._call("mlz_stream_open_batch_device", stream, d_src, arr, n, out, C.byref(h))
+        size = self._call("mlz_stream_open_batch_device_tables" if tables else "mlz_stream_open_batch_device", stream, d_src, arr, n, out, C.byref(h))
         return DeviceReader(self, h, size), [int(out[i]) for i in range(n)]
 
 
@@ -617,6 +619,15 @@ class DeviceReader:
         uint64, which receive the stream each record starts in and its number inside that stream (0xFFFFFFFF and 0 at or beyond the record
         count).  -> the numbers in range.  Raises without a record index."""
         return self._call("mlz_dev_reader_locate_records", stream, d_rec_no, n, d_which, d_local_no)
+
+    def set_tables_info(self):
+        """mlz_dev_reader_set_tables_info (include/minlz_hip_stream_set_tables.h): the last plan on a set opened with tables=True ->
+        (classes found, streams pruned by a class, streams with bytes decoded whole, chunks with a usable table in pruned streams, those of
+        them from a compressed table chunk, stream ends treated as crossed, and behind these six the 0x46 tables that stand expanded in the
+        reader's arenas, which stays as it is from the second search on): a 7-tuple.  Any other reader raises (error 8)."""
+        out = (C.c_uint64 * 6)()
+        expanded = self._call("mlz_dev_reader_set_tables_info", out)
+        return tuple(int(v) for v in out) + (expanded,)
 
     @staticmethod
     def _configs(cfgs):

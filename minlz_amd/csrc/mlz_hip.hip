@@ -20,6 +20,7 @@
 #include "../../include/minlz_hip_search_batch.h"
 #include "../../include/minlz_hip_search_batch_prune.h"
 #include "../../include/minlz_hip_stream_set.h"
+#include "../../include/minlz_hip_stream_set_tables.h"
 #include "../../include/minlz_hip_search_compressed.h"
 #include "../../include/minlz_hip_search_compress.h"
 #include "../../include/minlz_hip_sidecar_extract.h"
@@ -34,6 +35,7 @@
 #include "mlz_toktab.h"
 #include "mlz_stream_search.h"
 #include "mlz_search_compressed.h"
+#include "mlz_stream_set_tables.h"
 #include "mlz_decode.hip.inc"
 #include "mlz_decode_index.hip.inc"
 #include "mlz_decode_exec.hip.inc"
@@ -1381,5 +1383,6 @@ int mlz_debug_idxprof(unsigned long long* out) {
 #include "mlz_stream_record_index_store.hip.inc"
 #include "mlz_stream_grep.hip.inc"
 #include "mlz_stream_set.hip.inc"
+#include "mlz_stream_set_tables.hip.inc"
 #include "mlz_stream_regex.hip.inc"
 #include "mlz_stream_regex_prune.hip.inc"

@@ -152,7 +152,7 @@ int64_t dev_reader_grep_locked(mlz_dev_reader* rd, hipStream_t sm, uint32_t flag
     std::vector<uint8_t> take(nck, 0);
     size_t n_take = 0;
     if (n && nck) {
-        const int64_t pr = dev_reader_search_plan(rd, sm, flags, scan.patterns, scan.index.off, n, &take, &n_take, stats, true);
+        const int64_t pr = dev_reader_search_plan(rd, sm, flags, scan.patterns, scan.index.off, n, &take, &n_take, stats, true, true);   // (record-bound)
         if (pr) return pr;
     }
     Carve cv, pin;   // workspace: the grep's (totals | marks, then S | C | the backward scan | ranks) | the index | the decode's; pinned: the index | the decode's

@@ -95,6 +95,21 @@ struct mlz_dev_reader {
     bool set = false;
     std::vector<uint64_t> bases;
     void* d_bases = nullptr;
+    // mlz_stream_open_batch_device_tables (mlz_stream_set_tables.hip.inc): a set whose searches use every stream's inline tables.  The open
+    // leaves st (a descriptor's source span and its chunks in the handle's list; mode = whole or skipped); the first search finds the classes
+    // (cls, prunable) once and every data chunk's table once per CRC mode (search[]: set c = class c, ncfg = the classes that prune).
+    // d_chunks: mlz::SetTabChunk per data chunk; cross[0] / d_cross[0]: the streams' crossing flags of a position call, [1]: of a
+    // record-bound call, made anew when the record index is replaced.  info: what mlz_dev_reader_set_tables_info reports.
+    struct SetTabled {
+        bool on = false, classed = false, cross_ready[2] = {false, false};
+        uint32_t classes = 0, ncls = 0;
+        uint64_t expansions = 0;             // 0x46 tables that stand expanded in search[]'s arenas
+        std::vector<mlz::BatchPlanStream> st;
+        std::vector<uint8_t> prunable, cross[2];
+        mlz::SearchConfig cfg[mlz::kSidecarMaxConfigs] = {};
+        void *d_chunks = nullptr, *d_cross[2] = {nullptr, nullptr};
+        uint64_t info[mlz::kSetTabInfoValues] = {};
+    } tabled;
 };
 
 namespace {
@@ -198,10 +213,11 @@ int64_t mlz_dev_reader_read(mlz_dev_reader* rd, void* stream, uint32_t flags, co
 }
 
 void mlz_dev_reader_close(mlz_dev_reader* rd) {
-    if (rd && (rd->d_chunks || rd->search[0].d_tabs || rd->search[1].d_tabs || rd->side.d_tabs || rd->d_index || rd->d_bases)) {
+    if (rd && (rd->d_chunks || rd->search[0].d_tabs || rd->search[1].d_tabs || rd->side.d_tabs || rd->d_index || rd->d_bases || rd->tabled.d_chunks)) {
         std::lock_guard<std::mutex> lk(rd->ctx->mu);
         if (hipSetDevice(rd->ctx->device) == hipSuccess)
-            for (void* p : {rd->d_chunks, rd->search[0].d_tabs, rd->search[1].d_tabs, rd->side.d_tabs, rd->search[0].d_arena, rd->search[1].d_arena, rd->side.d_arena, rd->d_index, rd->d_bases})
+            for (void* p : {rd->d_chunks, rd->search[0].d_tabs, rd->search[1].d_tabs, rd->side.d_tabs, rd->search[0].d_arena, rd->search[1].d_arena, rd->side.d_arena, rd->d_index, rd->d_bases,
+                            rd->tabled.d_chunks, rd->tabled.d_cross[0], rd->tabled.d_cross[1]})
                 if (p) (void)hipFree(p);
     }
     delete rd;

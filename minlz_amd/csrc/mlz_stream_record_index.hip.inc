@@ -203,6 +203,7 @@ int64_t dev_reader_index_records_locked(mlz_dev_reader* rd, hipStream_t sm, bool
     tab.p = nullptr;
     rd->index_ready = true; rd->index_delim = delim; rd->index_k = k;
     rd->index_longest_ready = false;
+    rd->tabled.cross_ready[1] = false;   // (the joined flags of a set that keeps its tables belong to the index)
     rd->index_n = mlz::rindex_records(k, size, last_is_delim);
     *decoded = nd;
     return int64_t(rd->index_n);

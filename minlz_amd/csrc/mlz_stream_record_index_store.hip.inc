@@ -326,6 +326,7 @@ int64_t dev_reader_load_record_index_locked(mlz_dev_reader* rd, hipStream_t sm, 
     rd->index_ready = true; rd->index_delim = h.delim; rd->index_k = k; rd->index_n = h.N;
     rd->index_longest_ready = (h.flags & mlz::kRstoreLongest) != 0;
     rd->index_longest = rd->index_longest_ready ? h.longest : 0;
+    rd->tabled.cross_ready[1] = false;   // (the joined flags of a set that keeps its tables belong to the index)
     return int64_t(rd->index_n);
 }
 

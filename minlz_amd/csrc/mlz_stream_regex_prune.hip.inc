@@ -108,7 +108,7 @@ int64_t dev_reader_grep_regex_pruned_locked(mlz_dev_reader* rd, hipStream_t sm, 
     std::vector<uint8_t> take(nck, 0);
     size_t n_take = 0, n_data = 0;
     for (size_t k = 0; k < nck; k++) n_data += chunks[k].n ? 1 : 0;
-    const bool everything = pr.literals.empty() || (flags & MLZ_SEARCH_NO_TABLES) || rd->set || (fold && mlz::search_is_letter(rd->index_delim));
+    const bool everything = pr.literals.empty() || (flags & MLZ_SEARCH_NO_TABLES) || (rd->set && !rd->tabled.on) || (fold && mlz::search_is_letter(rd->index_delim));
     if (everything) {
         for (size_t k = 0; k < nck; k++) take[k] = chunks[k].n ? 1 : 0;
         n_take = n_data;
@@ -122,7 +122,7 @@ int64_t dev_reader_grep_regex_pruned_locked(mlz_dev_reader* rd, hipStream_t sm, 
         }
         if (off.size() > 1) {
             const uint32_t plan_flags = (flags & MLZ_STREAM_IGNORE_CRC) | (fold ? uint32_t(MLZ_SEARCH_IGNORE_CASE) : 0u);
-            const int64_t r = dev_reader_search_plan(rd, sm, plan_flags, blob.data(), off, off.size() - 1, &take, &n_take, nullptr, true);
+            const int64_t r = dev_reader_search_plan(rd, sm, plan_flags, blob.data(), off, off.size() - 1, &take, &n_take, nullptr, true, true);   // (record-bound)
             if (r) return r;
         }
     }

@@ -259,8 +259,13 @@ int64_t dev_reader_search_sets(mlz_dev_reader* rd, hipStream_t sm, bool ignore_c
 // comes back.  A pattern that is not served puts every chunk with a byte into the set, so the kernel is not run then.
 // Under MLZ_SEARCH_IGNORE_CASE `patterns` are the FOLDED patterns, and the hashes are those of the windows' case variants
 // (search_pattern_hashes_fold, at most kSearchFoldMaxHashes in a call: a pattern that does not fit is not served).
+// A set that keeps its streams' tables (mlz_stream_open_batch_device_tables) plans by the rule of mlz_stream_set_tables.h, which needs to know
+// the kind of call it serves.  records: an occurrence lies inside one record of the handle's index (grep and the pruned regex grep); else it
+// may lie anywhere (the position searches).
+int64_t dev_reader_set_tables_plan(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* patterns, const std::vector<uint32_t>& off, size_t np, bool records,
+                                   std::vector<uint8_t>* take, size_t* n_take, uint64_t* unserved, bool* planned);   // mlz_stream_set_tables.hip.inc
 int64_t dev_reader_search_plan(mlz_dev_reader* rd, hipStream_t sm, uint32_t flags, const uint8_t* patterns, const std::vector<uint32_t>& off, size_t n,
-                               std::vector<uint8_t>* take, size_t* n_take, uint64_t* stats, bool many) {
+                               std::vector<uint8_t>* take, size_t* n_take, uint64_t* stats, bool many, bool records = false) {
     mlz_ctx* c = rd->ctx;
     const size_t nck = rd->chunks.size();
     const bool ignore_crc = (flags & MLZ_STREAM_IGNORE_CRC) != 0, fold = (flags & MLZ_SEARCH_IGNORE_CASE) != 0;
@@ -270,7 +275,12 @@ int64_t dev_reader_search_plan(mlz_dev_reader* rd, hipStream_t sm, uint32_t flag
         if (stats) { stats[1] = *n_take; stats[2] = c->search_tables; if (many) stats[3] = unserved; }
         return 0;
     };
-    if (!(flags & MLZ_SEARCH_NO_TABLES)) {
+    if (!(flags & MLZ_SEARCH_NO_TABLES) && rd->tabled.on) {
+        bool done = false;
+        const int64_t r = dev_reader_set_tables_plan(rd, sm, flags, patterns, off, n, records, take, n_take, &unserved, &done);
+        if (r) return r;
+        if (done) return planned();
+    } else if (!(flags & MLZ_SEARCH_NO_TABLES)) {
         const mlz_dev_reader::SearchTables* stp = nullptr;
         const int64_t r = dev_reader_search_sets(rd, sm, ignore_crc, &stp);
         if (r) return r;

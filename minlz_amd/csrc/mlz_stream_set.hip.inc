@@ -111,6 +111,7 @@ int64_t stream_open_batch_locked(mlz_ctx* c, hipStream_t sm, const uint8_t* d_sr
         total += size[i];
         nck += bw.c1[i] - bw.c0[i];
     }
+    if (rd->tabled.on) rd->tabled.st.assign(n, mlz::BatchPlanStream{0, 0, 0, 0, mlz::kBatchPlanSkip, 0});
     if (nck > 0xffffffffull) return -MLZ_ERR_ARG;   // the planners count chunks in 32 bits
     rd->bases.assign(n + 1, 0);
     mlz::set_bases(size.data(), n, rd->bases.data());
@@ -118,6 +119,9 @@ int64_t stream_open_batch_locked(mlz_ctx* c, hipStream_t sm, const uint8_t* d_sr
     rd->dchunks.reserve(nck);
     for (size_t i = 0; i < n; i++) {
         if (bw.parsed[i] < 0) continue;
+        if (rd->tabled.on)   // the stream's source span up to its first data chunk's body, and its chunks in the handle's list
+            rd->tabled.st[i] = mlz::BatchPlanStream{streams[i].src_off, bw.c1[i] > bw.c0[i] ? uint64_t(bw.chunks[bw.c0[i]].body_off) : streams[i].src_off + streams[i].src_len,
+                                                    uint32_t(rd->chunks.size()), uint32_t(rd->chunks.size() + (bw.c1[i] - bw.c0[i])), mlz::kBatchPlanWhole, 0};
         for (size_t k = bw.c0[i]; k < bw.c1[i]; k++) {
             StreamChunk ck = bw.chunks[k];
             ck.out_off += size_t(rd->bases[i]);
@@ -133,11 +137,8 @@ int64_t stream_open_batch_locked(mlz_ctx* c, hipStream_t sm, const uint8_t* d_sr
 // The entry checks of the calls that translate n items: the handle, the count
 int set_enter(mlz_dev_reader* rd, size_t n) { return !rd || uint64_t(n) > mlz::kSetMaxItems ? -MLZ_ERR_ARG : 0; }
 
-}  // namespace
-
-extern "C" {
-
-int64_t mlz_stream_open_batch_device(mlz_ctx* c, void* stream, const uint8_t* d_src, const mlz_block_desc* streams, int n_streams, int64_t* out_len, mlz_dev_reader** out) {
+// mlz_stream_open_batch_device, and with `tabled` mlz_stream_open_batch_device_tables (mlz_stream_set_tables.hip.inc)
+int64_t stream_open_batch_handle(mlz_ctx* c, void* stream, const uint8_t* d_src, const mlz_block_desc* streams, int n_streams, int64_t* out_len, mlz_dev_reader** out, bool tabled) {
     if (out) *out = nullptr;
     if (!out) return -MLZ_ERR_ARG;
     const int a = batch_args(c, d_src, nullptr, false, streams, n_streams, out_len, &c);
@@ -148,8 +149,10 @@ int64_t mlz_stream_open_batch_device(mlz_ctx* c, void* stream, const uint8_t* d_
     if (!rd) return -MLZ_ERR_HIP;
     rd->ctx = c; rd->d_src = d_src; rd->set = true;
     rd->bases.assign(1, 0);
-    // no inline tables on a set: dev_reader_search_tables' hops would run from one stream into another
-    rd->search[0].ready = rd->search[1].ready = true;
+    // no inline tables on a plain set: dev_reader_search_tables' hops would run from one stream into another (a tabled set finds them stream
+    // by stream: dev_reader_set_tables)
+    rd->search[0].ready = rd->search[1].ready = !tabled;
+    rd->tabled.on = tabled;
     if (a == 0) {
         hipStream_t sm = static_cast<hipStream_t>(stream);
         const int64_t r = settled(sm, stream_open_batch_locked(c, sm, d_src, streams, size_t(n_streams), out_len, rd));
@@ -157,6 +160,14 @@ int64_t mlz_stream_open_batch_device(mlz_ctx* c, void* stream, const uint8_t* d_
     }
     *out = rd;
     return rd->size;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t mlz_stream_open_batch_device(mlz_ctx* c, void* stream, const uint8_t* d_src, const mlz_block_desc* streams, int n_streams, int64_t* out_len, mlz_dev_reader** out) {
+    return stream_open_batch_handle(c, stream, d_src, streams, n_streams, out_len, out, false);
 }
 
 int64_t mlz_dev_reader_stream_count(const mlz_dev_reader* rd) { return rd ? int64_t(rd->bases.size() - 1) : -MLZ_ERR_ARG; }

@@ -203,15 +203,16 @@ class HipTensorCodec:
         runs once, here; a framing error raises."""
         return DeviceStream(self.ctx, _u8(t, "open_stream"))
 
-    def open_streams(self, t, spans, on_error="raise"):
+    def open_streams(self, t, spans, on_error="raise", tables=False):
         """Many .mz streams that lie in one uint8 tensor on the device (stream i at t[off_i : off_i + len_i] for spans[i]) opened as ONE
         DeviceStreamSet: a DeviceStream over their decoded bytes one behind the other, in the order of the spans (one call,
         mlz_stream_open_batch_device).  on_error "raise": the first stream with a framing error raises its error, which names its index
-        (.index); "skip": such a stream is left out (size 0), and .errors names it."""
+        (.index); "skip": such a stream is left out (size 0), and .errors names it.  tables: the set's searches and greps prune by every
+        stream's inline search tables (mlz_stream_open_batch_device_tables), with the same results."""
         if on_error not in ("raise", "skip"):
             raise ValueError("open_streams: on_error is \"raise\" or \"skip\"")
         t = _u8(t, "open_streams")
-        s = DeviceStreamSet(self.ctx, t, _spans(t, spans, "open_streams"))
+        s = DeviceStreamSet(self.ctx, t, _spans(t, spans, "open_streams"), tables=tables)
         if on_error == "raise" and s.errors:
             i = min(s.errors)
             s.close()
@@ -477,18 +478,27 @@ class DeviceStreamSet(DeviceStream):
     """Many .mz streams on the device opened as ONE DeviceStream (HipTensorCodec.open_streams): its decoded bytes are the streams' decoded
     bytes one behind the other, and read_ranges, search, search_many, search_records, index_records, read_records, line_numbers, grep and grep_regex
     work on that concatenation — a range, an occurrence or a record may cross from one stream into the next.  The calls here turn positions
-    and record numbers back into (stream, position or record inside the stream), on the device.  No search tables and no sidecar.
+    and record numbers back into (stream, position or record inside the stream), on the device.  No search tables and no sidecar — unless the set was opened
+    with tables=True (.tables): then search, search_many, search_records, grep, grep_streams, grep_regex(prune=True) and
+    grep_streams_regex(prune=True) decode only the chunks that the streams' inline search tables admit (include/minlz_hip_stream_set_tables.h:
+    the greps prune as each stream alone would when every stream ends with the delimiter; the position searches also take every stream's last
+    bytes), no_tables=True turns that off per call, and tables_info() describes the last plan.  Still no sidecar.
     .sizes: every stream's decoded size (0 for a failed one); .errors: {index: negative code} of the streams left out for a framing error;
     .bases: the n + 1 places where the streams start in the set (a list of ints; the last is .size)."""
 
-    def __init__(self, ctx, t, spans):
-        self.t, self.dev, self.spans = t, t.device, spans
-        self.reader, res = ctx.stream_open_batch_device(t.data_ptr() if spans else None, spans, stream=_stream(t.device))
+    def __init__(self, ctx, t, spans, tables=False):
+        self.t, self.dev, self.spans, self.tables = t, t.device, spans, bool(tables)
+        self.reader, res = ctx.stream_open_batch_device(t.data_ptr() if spans else None, spans, stream=_stream(t.device), tables=self.tables)
         self.size = self.reader.size
         self.side = None
         self.sizes = [max(r, 0) for r in res]
         self.errors = {i: r for i, r in enumerate(res) if r < 0}
         self.bases = self.reader.stream_bases()
+
+    def tables_info(self):
+        """The last plan on a set opened with tables=True (api.DeviceReader.set_tables_info) -> (classes, streams pruned, streams decoded
+        whole, chunks with a usable table, those from compressed table chunks, stream ends treated as crossed, 0x46 tables that stand expanded)."""
+        return self.reader.set_tables_info()
 
     def _located(self, call, items, what):
         items = _items(items, self.dev, what)
